@@ -92,6 +92,23 @@ def reference_verdict(rows, gold_rows, sel, uncertified_local, dist, world: int)
     return (not bad), det
 
 
+def dump_outputs(out_dir: str, outs: dict, budget_bytes: int) -> None:
+    """Write one timed pass's outputs as .npy files of at most `budget_bytes` in all: ids [sum T, 4] float32 (the token rows, concatenated
+    in row order), lens [B] float64, wav [B, k] float32 and wav_columns [k] float64.  The waveforms are whole (k = all columns) when they
+    fit, else k columns drawn without replacement by a fixed seed, in ascending order -- the same columns for the same workload."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids = np.concatenate([np.asarray(r).reshape(-1, GPT.n_vq) for r in outs["ids"]], 0).astype(np.float32)
+    lens = np.asarray(outs["lens"], np.float64)
+    wav = np.asarray(outs["wav"], np.float32)
+    wav = wav.reshape(wav.shape[0], -1)
+    rows, n = wav.shape
+    room = budget_bytes - ids.nbytes - lens.nbytes - 4 * 128      # 128 bytes of .npy header per file
+    k = min(n, max(0, room // (4 * rows + 8)))
+    cols = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    for name, a in (("ids", ids), ("lens", lens), ("wav", np.ascontiguousarray(wav[:, cols])), ("wav_columns", cols.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def shard_workload(batch_per_gpu: int, world: int, rank: int, min_len: int, max_len: int, policy: str = "snake"):
     """The global C3 batch (64 utterances per GPU) and this rank's shard of it: prompts, masks, forced lengths, the GLOBAL indices of its
     utterances (chattts_amd.dist.deal_shards: sorted by prompt length and dealt in snake order, so every rank gets an equal share of long
@@ -564,6 +581,10 @@ def main():
                     help="(debug) the N ranks of a torch.distributed.run launch all use GPU 0 and rendezvous over gloo: a FUNCTIONAL run of the N-rank "
                          "path (shards, global row ids, the all-reduce before decoding, the per-rank reference verdict) on a one-GPU box; the line is marked "
                          "and is not a throughput measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write what the last one handed its caller as DIR/<name>.npy (float32 / float64, <= 64 MB "
+                         "in all): wav (the waveforms; a fixed seeded sample of columns when the batch is larger, indices in wav_columns), "
+                         "ids (the token rows, concatenated) and lens (tokens per utterance); with N ranks, rank r writes DIR/rank<r>/")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) run the CPU baseline leg alone and print its JSON")
     ap.add_argument("--cold-start-only", choices=["plain", "prewarmed"], default=None,
                     help="(internal) a FRESH process: load, optionally Chat.warm the workload's geometry, then time the first streamed chunk")
@@ -578,6 +599,8 @@ def main():
         return cold_start_child(args)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: spawn the N ranks ourselves (one process per GPU under torch.distributed.run,
         # rendezvous on 127.0.0.1) and relay rank 0's one JSON line -- never time ONE GPU and call it N
@@ -654,8 +677,10 @@ def main():
     max_new = int(stop.max()) + 1
     ids_d, mask_d, tm_d = ids_t.to(dev), mask_t, tm_t.to(dev)   # the prompt ids are resident; Embed.forward (a2) runs INSIDE the clock
 
-    def one_pass(eng, cdc, use_graph=True, profile_tag=None, decode_audio=True, profile_stride=1, keep_ids=False, teacher=None, keep_hidden=False):
-        """generate -> DVAE -> Vocos -> host numpy (the reference path's last op is `.cpu().numpy()`, core.py:508-510)"""
+    def one_pass(eng, cdc, use_graph=True, profile_tag=None, decode_audio=True, profile_stride=1, keep_ids=False, teacher=None, keep_hidden=False,
+                 rows_out=None):
+        """generate -> DVAE -> Vocos -> host numpy (the reference path's last op is `.cpu().numpy()`, core.py:508-510); `rows_out`: a dict that
+        receives the pass's token rows as the device tensors generate returned (no copy, no sync)"""
         out = None
         emb = eng.embed_prompt(ids_d, tm_d)      # a2: Embed.forward (embed.py:52-79)
         for out in eng.generate(emb, ids_d, temp, 625, mask_d, max_new, 0, (*procs, *warpers), return_hidden=True,
@@ -664,6 +689,8 @@ def main():
                                 teacher_ids=teacher, return_sampled=teacher is not None):
             pass
         lens = [int(t.shape[0]) for t in out.ids]
+        if rows_out is not None:
+            rows_out["ids"] = out.ids
         wav = cdc.to_host(cdc.decode_to_wavs(out.hiddens)) if decode_audio else None   # what Chat.decode_to_wavs returns
         if keep_hidden:
             return lens, [h.cpu().numpy() for h in out.hiddens], [t.cpu().numpy() for t in out.ids]
@@ -686,7 +713,7 @@ def main():
             pass
         return out
 
-    def sharded_pass(eng, cdc):
+    def sharded_pass(eng, cdc, rows_out=None):
         """the same pass through the PRODUCT's data-parallel entry (chattts_amd.dist.infer_sharded, gather=False: every rank ends with ITS
         utterances' float32 waveforms on its host): deal by prompt length, generate with global row ids, ONE 8-byte all-reduce(max) of the
         longest utterance, decode padded to it.  What `bench.py --gpus N` times whenever a process group exists."""
@@ -699,14 +726,19 @@ def main():
                                               p, gather=False, stop_at=torch.from_numpy(stop.astype(np.int32)), return_ids=True,
                                               use_graph=not args.no_graph, lanes=args.lanes)
         assert mine == list(wl["sel"]), "bench.shard_workload and dist.infer_sharded disagree on the shards"
+        if rows_out is not None:
+            rows_out["ids"] = ids_rows
         return [int(r.shape[0]) for r in ids_rows], wav, None
 
-    def timed(eng, cdc, steps, warmup, tag=None, pipeline=None):
+    def timed(eng, cdc, steps, warmup, tag=None, pipeline=None, sink=None):
         """K passes, one batch after the other -- or (pipeline) SOFTWARE-PIPELINED over the queue of batches: the acoustic decode + waveform
         D2H of batch i run on the codec engine's side stream while batch i+1 is generated (CodecEngine.decode_to_wavs_async; every
-        batch's float32 waveforms are on the host, as numpy, before the clock stops)."""
+        batch's float32 waveforms are on the host, as numpy, before the clock stops).  `sink`: a dict that receives what the LAST timed
+        pass handed its caller (wav, ids, lens), copied to the host after the clock stops."""
         pipeline = args.pipeline if pipeline is None else pipeline
-        a_pass = (lambda: sharded_pass(eng, cdc)) if (dist is not None and not pipeline) else (lambda: one_pass(eng, cdc, use_graph=not args.no_graph))
+        rows = {} if sink is not None else None
+        a_pass = ((lambda: sharded_pass(eng, cdc, rows_out=rows)) if (dist is not None and not pipeline)
+                  else (lambda: one_pass(eng, cdc, use_graph=not args.no_graph, rows_out=rows)))
         for _ in range(warmup):
             a_pass()
         if pipeline:     # the side stream's buffers exist before the clock starts
@@ -720,6 +752,8 @@ def main():
                 continue
             out = gpt_pass(eng)
             lens = [int(t.shape[0]) for t in out.ids]
+            if rows is not None:
+                rows["ids"] = out.ids
             nxt = cdc.decode_to_wavs_async(out.hiddens)
             if pend is not None:
                 wav = pend.result()
@@ -740,6 +774,8 @@ def main():
                 rank_times[tag] = [round(1e3 * float(x.item()) / steps, 3) for x in own]
         assert lens == wl["stop"].tolist(), "forced lengths not honoured"
         assert wav is not None and wav.dtype == np.float32 and bool(np.isfinite(wav).all())
+        if sink is not None:
+            sink.update(wav=wav, lens=list(lens), ids=[r.cpu().numpy() if torch.is_tensor(r) else np.asarray(r) for r in rows["ids"]])
         return dt
 
     # the reference's own run of the GLOBAL batch (oracle/make_bench_golden.py [--world N]): one rank compares all rows, N ranks each their
@@ -786,10 +822,10 @@ def main():
                         "is: ~10 of this workload's 85,752 draws); the ids of THIS run are checked against the reference's sha256 all the same "
                         "(`ids_check`), and --exact-fallback regenerates the flagged utterances on the f32 MFMA kernels inside the timed pass"}
 
-    def mode_leg(eng, cdc, steps, warmup, tag=None):
+    def mode_leg(eng, cdc, steps, warmup, tag=None, sink=None):
         """K timed passes of the workload on one engine + what they produced: graph replay == eager launches, sha256 of all token rows
         (against the reference's own run of this workload when the golden is here)"""
-        dt_ = timed(eng, cdc, steps, warmup, tag=tag)
+        dt_ = timed(eng, cdc, steps, warmup, tag=tag, sink=sink)
         n_st, dec_ms_ = eng.last_stats.get("steps", 0), eng.last_stats.get("decode_ms", 0.0)
         leg = {"dtype": eng.dtype, "value": round(audio_seconds(stop) * steps / dt_, 2), "unit": "audio-s/s", "steps": steps, "warmup": warmup,
                "ms_per_step": round(1000.0 * dt_ / steps, 3), "decode_ms_per_gpt_step": round(dec_ms_ / max(1, n_st - 1), 4),
@@ -812,7 +848,11 @@ def main():
         return leg, dt_, n_st, dec_ms_
 
     note("timed passes (%s)" % args.dtype)
-    main_leg, dt, gpt_steps, decode_ms = mode_leg(gpt, codec, args.steps, args.warmup, tag="main")
+    main_out = {} if args.dump_outputs else None
+    main_leg, dt, gpt_steps, decode_ms = mode_leg(gpt, codec, args.steps, args.warmup, tag="main", sink=main_out)
+    if main_out is not None:
+        dump_outputs(os.path.join(args.dump_outputs, "rank%d" % rank) if world > 1 else args.dump_outputs, main_out, 64_000_000 // world)
+        note("outputs of the last timed pass written to %s" % args.dump_outputs)
     value = audio_seconds(stop) * args.steps / dt      # all ranks, all steps
     ids_check = main_leg.get("ids_check")
 
