@@ -43,6 +43,17 @@ class GenState(C.Structure):
         ("infer_text", C.c_int32), ("teacher_ids", P), ("sampled_ids", P), ("order", P),
         ("rng_device", C.c_int32), ("rng_per_step", C.c_int32), ("rng_seed", P), ("rng_nonce", P),
         ("margin", P), ("row_base", P), ("proj_exact", C.c_int32), ("prefill_valid_rows", C.c_int32),
+        ("row_sampling", P),
+    ]
+
+
+class SamplingRow(C.Structure):
+    """ctts_sampling_row: one utterance slot's sampling parameters (ctts_gen_state.row_sampling), 128 bytes"""
+    _fields_ = [
+        ("temperature", C.c_float * 4), ("pow_table", C.c_float * 17), ("use_penalty", C.c_int32),
+        ("top_p_thr", C.c_float), ("use_top_p", C.c_int32), ("top_k", C.c_int32), ("use_top_k", C.c_int32),
+        ("min_new", C.c_int32), ("reserved0", C.c_int32), ("rng_seed", C.c_uint64), ("rng_per_step", C.c_int32),
+        ("reserved1", C.c_int32),
     ]
 
 

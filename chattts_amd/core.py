@@ -204,13 +204,31 @@ class Chat:
         # core.py:558-561: a scalar temperature is replicated over the 4 codebooks, a list is used as is
         temperature = torch.tensor(params.temperature if isinstance(params.temperature, list) else [params.temperature] * GPT.n_vq)
         warpers, procs = gen_logits(GPT.n_audio - 1, params.top_P, params.top_K, params.repetition_penalty)
-        emb = self.gpt.embed_prompt(input_ids, text_mask)
-        if params.spk_emb is not None and spk_emb_ids is not None:
-            apply_speaker(emb, params.spk_emb, input_ids, spk_emb_ids)
+        emb = self.prompt_embedding(input_ids, text_mask, params, spk_emb_ids)
         return self.gpt.generate(
             emb, input_ids, temperature, GPT.n_audio - 1, attention_mask, params.max_new_token, params.min_new_token,
             (*procs, *warpers), False, False, return_hidden, stream, params.show_tqdm, params.ensure_non_empty,
             params.stream_batch, params.manual_seed, self.context, **shard_kw)
+
+    def prompt_embedding(self, input_ids: torch.Tensor, text_mask: torch.Tensor, params: InferCodeParams,
+                         spk_emb_ids: Optional[int] = None) -> torch.Tensor:
+        """the prompt embedding of the code pass (core.py:616-637): Embed, then the speaker vector at the `[spk_emb]` positions"""
+        emb = self.gpt.embed_prompt(input_ids, text_mask)
+        if params.spk_emb is not None and spk_emb_ids is not None:
+            apply_speaker(emb, params.spk_emb, input_ids, spk_emb_ids)
+        return emb
+
+    def code_prompt(self, text, params: InferCodeParams):
+        """decorate (prompt, `txt_smp`, `spk_emb`) -> tokenise (+ audio-code prompt `spk_smp`) of ALREADY NORMALISED texts
+        (core.py:589-606): (input_ids [B,T,4], attention_mask [B,T], text_mask [B,T]).  The code pass of `Chat.infer` and the batched
+        server (serving.SpeechBatcher) both build their prompts here."""
+        self._need_tokenizer()
+        if not isinstance(text, list):
+            text = [text]
+        assert len(text), "text should not be empty"
+        prompt = Speaker.decode_prompt(params.spk_smp) if params.spk_smp is not None else None
+        return self.tokenizer.encode(Speaker.decorate_code_prompts(text, params.prompt, params.txt_smp, params.spk_emb), GPT.n_vq,
+                                     prompt=prompt)
 
     def refine_text_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, text_mask: torch.Tensor, eos_token: int,
                         params: RefineTextParams = RefineTextParams(), num_code: int = GPT.n_text, **kw) -> GenerationOutputs:
@@ -361,13 +379,7 @@ class Chat:
 
     def _infer_code(self, text, stream: bool, device, return_hidden: bool, params: InferCodeParams) -> Iterator[GenerationOutputs]:
         """core.py:542-662: decorate -> tokenise (+ audio-code prompt `spk_smp`) -> embed -> speaker -> generate."""
-        self._need_tokenizer()
-        if not isinstance(text, list):
-            text = [text]
-        assert len(text), "text should not be empty"
-        prompt = Speaker.decode_prompt(params.spk_smp) if params.spk_smp is not None else None
-        ids, attn, tmask = self.tokenizer.encode(
-            Speaker.decorate_code_prompts(text, params.prompt, params.txt_smp, params.spk_emb), GPT.n_vq, prompt=prompt)
+        ids, attn, tmask = self.code_prompt(text, params)
         return self.infer_code(ids, attn, tmask, params, stream=stream, return_hidden=return_hidden,
                                spk_emb_ids=self.tokenizer.spk_emb_ids)
 

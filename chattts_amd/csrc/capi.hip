@@ -240,6 +240,12 @@ struct Prof {
   }
 };
 
+static_assert(sizeof(SamplingRow) == sizeof(ctts_sampling_row) && sizeof(ctts_sampling_row) == 128, "ctts_sampling_row layout");
+static_assert(offsetof(SamplingRow, pow_table) == offsetof(ctts_sampling_row, pow_table) &&
+              offsetof(SamplingRow, min_new) == offsetof(ctts_sampling_row, min_new) &&
+              offsetof(SamplingRow, rng_seed) == offsetof(ctts_sampling_row, rng_seed) &&
+              offsetof(SamplingRow, rng_per_step) == offsetof(ctts_sampling_row, rng_per_step), "ctts_sampling_row layout");
+
 static SampleArgs make_sample_args(const ctts_gen_state* s, const float* logits) {
   SampleArgs a;
   a.logits = logits; a.ids_buf = s->ids_buf; a.tcap = s->cap ? s->cap : s->T + s->max_new; a.T = s->T; a.len = s->len; a.finish = s->finish;
@@ -253,6 +259,7 @@ static SampleArgs make_sample_args(const ctts_gen_state* s, const float* logits)
   a.desc = nullptr; a.rng_device = s->rng_device; a.rng_per_step = s->rng_per_step; a.rng_seed = reinterpret_cast<const unsigned long long*>(s->rng_seed);
   a.rng_nonce = s->rng_nonce;
   a.margin = s->margin; a.row_base = s->row_base;
+  a.rows = reinterpret_cast<const SamplingRow*>(s->row_sampling);
   memset(&a.next, 0, sizeof(a.next));
   return a;
 }
@@ -268,7 +275,8 @@ static int check_state(const ctts_gpt* g, const ctts_gen_state* s, int ws_T = 0)
   if (s->cap && s->T + 1 > s->cap) return fail("prompt does not fit the slot capacity");
   if (s->workspace_bytes < ctts_gpt_workspace_bytes(s->B, ws_T > 0 ? ws_T : s->T)) return fail("workspace too small");
   if (!s->rng_device && (s->nq <= 0 || !s->q)) return fail("q draws missing");
-  if (s->rng_device && !s->rng_seed) return fail("rng_device needs the rng_seed device scalar");
+  if (s->rng_device && !s->rng_seed && !s->row_sampling) return fail("rng_device needs the rng_seed device scalar (or row_sampling)");
+  if (s->row_sampling && s->infer_text) return fail("row_sampling serves the code mode only");
   if (s->rng_device && s->infer_text) return fail("the device generator serves the code mode only (refine-text samples from `q`)");
   if (g->w.weight_dtype == CTTS_BF16 && g->w.kv_dtype != CTTS_BF16) return fail("perf mode needs a bf16 KV cache");
   if (s->infer_text) {

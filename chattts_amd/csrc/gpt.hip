@@ -1553,11 +1553,34 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
   const int gen = len - (a.prompt_len ? a.prompt_len[b] : a.T);  // tokens generated so far == step index i of gpt.py:394
   const float* lrow = a.logits + ((size_t)m * NVQ + k) * NAUDIO;
   SSTAMP(1);   // row known
-  const float temp = a.temperature[k];
+  // sampling parameters: call-wide, or this utterance slot's row of the per-slot table (ctts_gen_state.row_sampling).  The table is
+  // read through the constant address space with a wave-uniform slot index, so its scalars arrive by s_load into SGPRs, issued in
+  // this first load round; with rows == null (a uniform kernel argument) the table is never touched.
+  float temp, thr;
+  const float* ptab;
+  int use_top_p, top_k, use_top_k, min_new, per_step;
+  unsigned long long seed;
+  bool nonce;
+  if (a.rows != nullptr) {
+    const int bu = __builtin_amdgcn_readfirstlane(b);
+    const __attribute__((address_space(4))) SamplingRow* r = (const __attribute__((address_space(4))) SamplingRow*)(a.rows + bu);
+    temp = r->temperature[__builtin_amdgcn_readfirstlane(k)];   // k is wave-uniform (one wave per codebook)
+    ptab = r->use_penalty ? a.rows[bu].pow_table : nullptr;
+    thr = r->top_p_thr; use_top_p = r->use_top_p; top_k = r->top_k; use_top_k = r->use_top_k; min_new = r->min_new;
+    per_step = r->rng_per_step;
+    seed = a.rng_device ? r->rng_seed : 0ull;
+    nonce = per_step != 0 && a.rng_nonce != nullptr;   // unseeded row: the per-admission fourth word; seeded row: the constant word
+  } else {
+    temp = a.temperature[k];
+    ptab = a.pow_table;
+    thr = a.top_p_thr; use_top_p = a.use_top_p; top_k = a.top_k; use_top_k = a.use_top_k; min_new = a.min_new;
+    per_step = a.rng_per_step;
+    seed = a.rng_device ? *a.rng_seed : 0ull;
+    nonce = a.rng_nonce != nullptr;
+  }
   // global sampling row (multi-GPU shards keep the reference's numbering; row_base: shards that are not contiguous row blocks)
   const int grow = (a.row_base != nullptr ? a.row_base[b] : a.row_offset + b * NVQ) + k;
-  const unsigned long long seed = a.rng_device ? *a.rng_seed : 0ull;
-  const uint32_t w3 = (a.rng_device && a.rng_nonce != nullptr) ? a.rng_nonce[b] : CTTS_RNG_WORD3;
+  const uint32_t w3 = (a.rng_device && nonce) ? a.rng_nonce[b] : CTTS_RNG_WORD3;
 
   // everything that depends only on (b, k, gen) is requested NOW, in one round: the logits, the Exp(1) draws consumed at the very
   // end, the <= 16 history tokens, the harness hooks
@@ -1574,12 +1597,12 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) qv[s] = (s * 64 + lane < NAUDIO) ? qrow[s * 64 + lane] : 1.f;
   }
-  const bool penal = a.pow_table != nullptr && grow < a.max_input_ids;
+  const bool penal = ptab != nullptr && grow < a.max_input_ids;
   const int nh = min(gen, 16);
   // the <=16 history tokens are fetched by 16 lanes in ONE load round and broadcast (a serial loop of
   // dependent global loads costs one L2 round trip per token)
   const int mine = (penal && lane < nh) ? (int)a.ids_buf[((size_t)b * a.tcap + (len - 1 - lane)) * NVQ + k] : -1;
-  const float ptab_reg = penal ? a.pow_table[min(lane, 16)] : 1.f;   // the 17-entry table penalty^count, one entry per lane
+  const float ptab_reg = penal ? ptab[min(lane, 16)] : 1.f;   // the 17-entry table penalty^count, one entry per lane
   const int sa = a.stop_at != nullptr ? a.stop_at[b] : -1;
   const bool forced_t = a.teacher != nullptr && gen < a.teacher_stride;
   const int64_t teach = forced_t ? a.teacher[((size_t)b * a.teacher_stride + gen) * NVQ + k] : 0;
@@ -1588,7 +1611,7 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
     for (int s = 0; s < SLOTS; ++s) {
       const int v = s * 64 + lane;
       float q4[4];
-      device_exp_draws4(seed, grow, a.rng_per_step ? gen : 0, v >> 2, q4, w3);
+      device_exp_draws4(seed, grow, per_step ? gen : 0, v >> 2, q4, w3);
       qv[s] = q4[v & 3];
     }
   }
@@ -1652,9 +1675,9 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
 
   // ---- the kept set.  Both warpers keep a PREFIX of the descending order (value desc, ties: lowest index first), so it is
   // described by its last element (v_last, i_last): kept = everything at or before it in that order.
-  const int kk = a.use_top_k ? min(max(a.top_k, 3), NAUDIO) : NAUDIO;
-  const float thr = a.top_p_thr;  // float32(1 - top_p): `cum <= (1 - top_p)` on a float tensor casts the scalar to float
-  const bool any_filter = a.use_top_p || a.use_top_k;
+  const int kk = use_top_k ? min(max(top_k, 3), NAUDIO) : NAUDIO;
+  // thr = float32(1 - top_p): `cum <= (1 - top_p)` on a float tensor casts the scalar to float
+  const bool any_filter = use_top_p || use_top_k;
   float v_last = INFINITY; int i_last = -1;   // nothing kept yet
   int n_kept = 0;
   bool done = !any_filter;
@@ -1666,7 +1689,7 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
   // total order as the serial extraction) together with the probability mass before them (double); then every candidate applies the
   // warpers' tests to itself and the prefix ends before the first one removed.  Falls back to the serial loop when more than 64
   // candidates survive.
-  if (any_filter && a.use_top_k && kk <= 64) {
+  if (any_filter && use_top_k && kk <= 64) {
     // t: the smallest lane maximum that has fewer than kk lane maxima strictly above it = the kk-th largest lane maximum
     int gtc = 0;
 #pragma unroll
@@ -1705,7 +1728,7 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
       // every candidate judges itself; the kept prefix ends before the first (lowest-rank) candidate a warper removes
       const unsigned long long whok = __ballot(act && rank == kk - 1);     // exists: C >= kk
       const float kth_val = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cv), (int)__ffsll((long long)whok) - 1));
-      const bool ok_p = !(a.use_top_p && rank >= 3 && (float)(sall - mass_above) <= thr);   // ascending cumulative prob incl. itself <= 1 - top_p
+      const bool ok_p = !(use_top_p && rank >= 3 && (float)(sall - mass_above) <= thr);   // ascending cumulative prob incl. itself <= 1 - top_p
       const bool ok_k = rank < kk || cv == kth_val;                                          // ties with the k-th largest value survive
       const int n = wave_min_dpp((act && !(ok_p && ok_k)) ? rank : C);
       const unsigned long long wlast = __ballot(act && rank == n - 1);      // n >= 3 (min_tokens_to_keep)
@@ -1726,8 +1749,8 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
           for (int s = 0; s < SLOTS; ++s) bm = fmaxf(bm, x[s] < t ? x[s] : -INFINITY);
           nxt = wave_max_dpp(bm);
         }
-        c_cut = (a.use_top_k && n > kk) ? 0.f : v_last - nxt;   // (ties with the k-th value were kept: an exact tie decided the set)
-        if (a.use_top_p) {
+        c_cut = (use_top_k && n > kk) ? 0.f : v_last - nxt;   // (ties with the k-th value were kept: an exact tie decided the set)
+        if (use_top_p) {
           // the top-p test of the last kept rank (if it was tested at all: rank >= 3) and of the rank top-p removed first
           const float cum = fmaxf((float)(sall - mass_above), 1e-38f);
           const bool mine = act && rank >= 3 && (rank == n - 1 || (rank == n && !ok_p));
@@ -1754,11 +1777,11 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
       float wv; int wi;
       wave_argmax(bv, bi, wv, wi);
       float cum = INFINITY;
-      if (a.use_top_p && n >= 3) {
+      if (use_top_p && n >= 3) {
         cum = (float)(sall - mass_above);
         if (cum <= thr) { nxt = wv; cum_drop = cum; break; }
       }
-      if (a.use_top_k && n >= kk && !(wv == kth_val)) { nxt = wv; break; }
+      if (use_top_k && n >= kk && !(wv == kth_val)) { nxt = wv; break; }
       cum_last = cum;
       const int ws = wi >> 6, wl = wi & 63;
       float pe = 0.f;
@@ -1773,14 +1796,14 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
     }
     n_kept = n;
     if (cert) {
-      c_cut = (a.use_top_k && n > kk) ? 0.f : v_last - nxt;
+      c_cut = (use_top_k && n > kk) ? 0.f : v_last - nxt;
       if (cum_last < INFINITY) c_p = fabsf(__logf(fmaxf(cum_last, 1e-38f) / thr));
       if (cum_drop >= 0.f) c_p = fminf(c_p, fabsf(__logf(fmaxf(cum_drop, 1e-38f) / thr)));
     }
   }
 
   // EOS handling (min_new_token and the bench harness's stop_at hook)
-  bool mask_eos = gen < a.min_new;
+  bool mask_eos = gen < min_new;
   SSTAMP(5);   // kept set known
   bool force_eos = false;
   if (sa >= 0) { mask_eos = mask_eos || (gen < sa); force_eos = gen >= sa; }

@@ -331,6 +331,20 @@ struct EmbedNext {
   StepPrep sp;
 };
 
+// ctts_sampling_row (include/chattts_amd.h), field for field: one utterance slot's sampling parameters (capi.hip asserts the layout)
+struct SamplingRow {
+  float temperature[4];
+  float pow_table[17];
+  int32_t use_penalty;
+  float top_p_thr; int32_t use_top_p;
+  int32_t top_k; int32_t use_top_k;
+  int32_t min_new;
+  int32_t reserved0;
+  unsigned long long rng_seed;
+  int32_t rng_per_step;
+  int32_t reserved1;
+};
+
 struct SampleArgs {
   const float* logits;      // [B, 4*626]
   int64_t* ids_buf;         // [B, Tcap, 4]
@@ -366,6 +380,7 @@ struct SampleArgs {
   EmbedNext next;           // fold of the next step's embedding kernel (next.x == null: off)
   float* margin;            // [slots] or null: parity certificate, lowered to the step's smallest decision margin (include/chattts_amd.h)
   const int32_t* row_base;  // [B] or null: global index of sampling row 0 of utterance b (replaces row_offset + 4 b)
+  const SamplingRow* rows;  // [slots] or null: per-slot sampling parameters replace temperature .. min_new and rng_seed / rng_per_step
   long long* dbg;           // probes only (tools/sample_phase_probe.py, env CTTS_SAMPLE_DBG_PTR): [rows][8] phase stamps (100 MHz), or null
 };
 hipError_t launch_exp_draws(unsigned long long seed, int step, int row0, int rows, int V, float* out, hipStream_t st);

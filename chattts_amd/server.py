@@ -14,12 +14,18 @@ from it).  What differs, deliberately:
     from chattts_amd.server import create_app
     chat = Chat(); chat.load(custom_path=..., dtype="bf16")
     app = create_app(chat, voices={"default": spk_emb_string})        # uvicorn.run(app, ...)
+
+`create_app(..., batch_slots=N)` serves concurrent non-streamed requests in ONE batch: a worker thread owns a slot pool of N utterance
+slots with per-request sampling parameters (serving.SpeechBatcher, serving.SlotPool(per_request=True)), so eight clients share the chip
+instead of queueing for it.  Every response is what the serial endpoint returns for the same request (the same tokens; PCM within one
+count).  Streamed requests keep the serial path; a threading lock keeps them and the worker from issuing GPU work at the same time.
 """
 from __future__ import annotations
 
 import asyncio
 import io
 import logging
+import threading
 import wave
 from typing import Dict, Optional
 
@@ -71,10 +77,13 @@ def _have_av() -> bool:
     return importlib.util.find_spec("av") is not None
 
 
-def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None):
+def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
+               batch_slots: Optional[int] = None, batcher=None):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
-    `infer_kwargs`: extra keywords for every `chat.infer` call (tests)."""
+    `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
+    reference's behaviour); N = non-streamed requests are batched in a pool of N slots (serving.SpeechBatcher; `batcher`: a ready one,
+    tests)."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -86,6 +95,23 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     app = FastAPI()
     app.state.chat = chat
     app.state.model_lock = asyncio.Lock()            # openai_api.py:66
+    gpu_lock = threading.Lock()                      # batching: the worker's chunks / decodes vs the streamed path's chunks
+    if batcher is None and batch_slots is not None:
+        from .serving import SpeechBatcher
+        batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log)
+    if batcher is not None:
+        gpu_lock = batcher.lock
+    app.state.batcher = batcher
+
+    def locked_chunks(gen):
+        """one chunk of a streamed response at a time under the GPU lock (batching on): the worker's chunks interleave with these"""
+        while True:
+            with gpu_lock:
+                try:
+                    chunk = next(gen)
+                except StopIteration:
+                    return
+            yield chunk
     formats = {"wav", "pcm"} | ({"mp3", "ogg"} if _have_av() else set())
 
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
@@ -143,7 +169,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        async for chunk in iterate_in_threadpool(infer(req)):
+                        gen = infer(req)
+                        async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
                             if fmt == "wav" and first:
                                 yield wav_stream_header()
                             first = False
@@ -153,11 +180,17 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                         log.error("speech synthesis failed mid-stream: %s", e)
             return StreamingResponse(audio_stream(), media_type=media)
 
-        async with app.state.model_lock:
+        if batcher is not None:
             try:
-                wavs = await run_in_threadpool(infer, req)
+                wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice)))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
+        else:
+            async with app.state.model_lock:
+                try:
+                    wavs = await run_in_threadpool(infer, req)
+                except Exception as e:
+                    raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         if len(wavs) == 0:
             raise HTTPException(500, detail="Speech synthesis failed: the engine returned no audio")
         body = encode(wavs[0], header=True)                                           # openai_api.py:277-288
@@ -166,6 +199,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     @app.get("/health")
     async def health():                                                               # openai_api.py:291-294
         loaded = bool(getattr(chat, "has_loaded", lambda: True)())
-        return {"status": "healthy" if loaded else "loading", "model_loaded": loaded, "formats": sorted(formats)}
+        out = {"status": "healthy" if loaded else "loading", "model_loaded": loaded, "formats": sorted(formats)}
+        if batcher is not None:
+            out["pool"] = batcher.occupancy()
+        return out
 
     return app

@@ -14,11 +14,22 @@ Parity contract: a request produces exactly the tokens `GptEngine.generate` prod
 `row_offset = 4*slot, total_rows = 4*S` (the Exp(1) draw of a sampling row is the pool row's), because nothing
 in the step mixes utterances.  With the host generator, seeded sampling only (`manual_seed`: the reference re-seeds its CPU
 generator every step, so the draw is one constant tensor for the whole session); `rng="device"` serves unseeded sampling too.
+
+Per-request sampling parameters (`SlotPool(..., per_request=True)`): every request carries its own `InferCodeParams` sampling fields
+and seed (the role of the reference's per-request `SamplingParams` in its vLLM engine, velocity/sampling_params.py:24), written into
+the slot's entry of the sampling kernel's per-slot table (include/chattts_amd.h, ctts_sampling_row) at admission, with its own Exp(1)
+rows and its own global sampling row.  Contract there: a request yields the tokens `GptEngine.generate` yields for it ALONE with the same
+parameters, `row_offset` and `total_rows` -- whatever runs beside it and whichever slot it lands in.
 """
 from __future__ import annotations
 
 import ctypes as C
+import itertools
+import queue
+import threading
+import time
 from collections import deque
+from concurrent.futures import Future
 from dataclasses import dataclass
 from typing import Deque, Iterator, List, Optional, Tuple
 
@@ -39,6 +50,58 @@ class _Req:
     tmask: torch.Tensor      # [T] bool
     max_new: int
     stop_at: int             # -1: none (benchmark hook, see engine.generate)
+    params: Optional["RequestParams"] = None   # per_request pools only
+    row_offset: int = 0
+    total_rows: int = GPT.n_vq
+    emb: Optional[torch.Tensor] = None         # [T, 768] prompt embedding (speaker applied), or None: embedded at admission
+
+
+# InferCodeParams' sampling fields and their defaults (core.py:48-64)
+_PARAM_DEFAULTS = dict(temperature=0.3, top_P=0.7, top_K=20, repetition_penalty=1.05, min_new_token=0, manual_seed=None,
+                       ensure_non_empty=True)
+
+
+@dataclass
+class RequestParams:
+    """the sampling parameters of one pooled request, validated: `temperature` has one entry per codebook"""
+    temperature: Tuple[float, ...]
+    plan: object             # engine.SamplingPlan
+    min_new_token: int
+    manual_seed: Optional[int]
+    ensure_non_empty: bool
+
+
+def request_params(params=None) -> RequestParams:
+    """`params`: an `InferCodeParams`, a dict of its fields, or None (the defaults).  Validated the way `GptEngine.generate` validates
+    them (gen_logits -> plan_from_processors), so a pool refuses exactly what a plain call refuses."""
+    get = (lambda k: params.get(k, _PARAM_DEFAULTS[k])) if isinstance(params, dict) else (lambda k: getattr(params, k, _PARAM_DEFAULTS[k]))
+    t = get("temperature")
+    temp = tuple(float(x) for x in t) if isinstance(t, (list, tuple)) else (float(t),) * GPT.n_vq   # core.py:558-561
+    if len(temp) != GPT.n_vq:
+        raise ValueError("temperature must be a scalar or one value per codebook")
+    warpers, procs = gen_logits(GPT.n_audio - 1, get("top_P"), get("top_K"), get("repetition_penalty"))
+    plan = plan_from_processors((*procs, *warpers))
+    seed = get("manual_seed")
+    return RequestParams(temp, plan, int(get("min_new_token")), None if seed is None else int(seed), bool(get("ensure_non_empty")))
+
+
+def sampling_row(p: RequestParams, rng_seed: int = 0, rng_per_step: bool = False) -> _lib.SamplingRow:
+    """the ctts_sampling_row of one request: the values `GptEngine.generate` puts into the call-wide fields for the same parameters"""
+    r = _lib.SamplingRow()
+    for i, t in enumerate(p.temperature):
+        r.temperature[i] = float(np.float32(t))
+    ptab = penalty_table(p.plan.penalty)
+    r.use_penalty = int(ptab is not None)
+    if ptab is not None:
+        for i, v in enumerate(ptab.tolist()):
+            r.pow_table[i] = v
+    r.top_p_thr = float(np.float32(1.0 - p.plan.top_p)) if p.plan.top_p is not None else 0.0
+    r.use_top_p = int(p.plan.top_p is not None)
+    r.top_k, r.use_top_k = int(p.plan.top_k or 0), int(p.plan.top_k is not None)
+    r.min_new = int(p.min_new_token)
+    r.rng_seed = int(rng_seed) & (2 ** 64 - 1)
+    r.rng_per_step = int(bool(rng_per_step))
+    return r
 
 
 class SlotPool:
@@ -46,14 +109,19 @@ class SlotPool:
 
     def __init__(self, engine: GptEngine, slots: int = 64, cap: int = 1536, hid_cap: int = 1024, *, temperature=(0.3,) * 4,
                  top_P: Optional[float] = 0.7, top_K: Optional[int] = 20, repetition_penalty: float = 1.05, manual_seed: int = 42,
-                 min_new_token: int = 0, eos_token: int = GPT.n_audio - 1, rng: str = "host", rng_seed: Optional[int] = None):
-        """`rng="device"`: the Exp(1) draws come from the sampling kernel's own generator (engine.generate's `rng`), which is what
+                 min_new_token: int = 0, eos_token: int = GPT.n_audio - 1, rng: str = "host", rng_seed: Optional[int] = None,
+                 per_request: bool = False):
+        """`per_request=True`: the sampling keywords above are not used; every request brings its own (`submit(params=...)`), with
+        the host generator each its own `manual_seed`; with the device generator seeded and unseeded requests share the pool (unseeded
+        ones draw from `rng_seed` -- random if None -- with a fresh counter word per admission, `nonce_of[rid]`).
+        `rng="device"`: the Exp(1) draws come from the sampling kernel's own generator (engine.generate's `rng`), which is what
         makes the reference's DEFAULT `manual_seed=None` servable here: a fresh draw per (admission, request step, pool row) without any
         per-step host work -- every admission gets its own number as the fourth word of the generator's counter, so a request never
         replays the stream of the slot's previous occupant (`nonce_of[rid]`; `generate(rng_nonce=...)` reproduces it in isolation).  The host stream (`rng="host"`) needs `manual_seed` (one constant tensor per session)."""
         if rng not in ("host", "device"):
             raise ValueError("rng must be 'host' or 'device'")
-        if manual_seed is None and rng != "device":
+        self.per_request = bool(per_request)
+        if manual_seed is None and rng != "device" and not self.per_request:
             raise NotImplementedError("SlotPool with the host generator needs manual_seed (one constant Exp(1) draw per session); "
                                       "use rng='device' for unseeded sampling")
         if cap > engine.max_pos:
@@ -86,7 +154,17 @@ class SlotPool:
             self.vcache = torch.zeros(kv_shape, dtype=engine.wdt, device=dev)
             self.n_active = torch.zeros((1,), dtype=torch.int32, device=dev)   # written by the step's first kernel
             self.device_rng, self.rng_per_step = rng == "device", manual_seed is None
-            if self.device_rng:
+            self.rows = self.row_base = None
+            if self.per_request:
+                # the per-slot sampling table and global sampling rows, written at admission (ctts_gen_state.row_sampling / row_base)
+                self.rows = torch.zeros((slots, C.sizeof(_lib.SamplingRow)), dtype=torch.uint8, device=dev)
+                self.row_base = torch.zeros((slots,), dtype=torch.int32, device=dev)
+                self.q = (torch.zeros((1,), dtype=torch.float32, device=dev) if self.device_rng else
+                          torch.ones((1, slots * nvq, GPT.n_audio), dtype=torch.float32, device=dev))   # host: each slot's rows at admission
+                self.rng_seed = None
+                self.pool_seed = int(rng_seed) if rng_seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+                self.rng_nonce = torch.zeros((slots,), dtype=torch.int32, device=dev) if self.device_rng else None
+            elif self.device_rng:
                 self.q = torch.zeros((1,), dtype=torch.float32, device=dev)
                 seed = int(rng_seed) if rng_seed is not None else (int(manual_seed) if manual_seed is not None
                                                                    else int(torch.randint(0, 2 ** 62, (1,)).item()))
@@ -100,8 +178,8 @@ class SlotPool:
                 self.q = ExpDraws(slots * nvq, GPT.n_audio, manual_seed).step(0).to(dev).reshape(1, slots * nvq, GPT.n_audio).contiguous()
                 self.rng_seed = None
                 self.rng_nonce = None
-            self.temp = torch.tensor(list(temperature), dtype=torch.float32, device=dev)
-            ptab = penalty_table(plan.penalty)
+            self.temp = None if self.per_request else torch.tensor(list(temperature), dtype=torch.float32, device=dev)
+            ptab = None if self.per_request else penalty_table(plan.penalty)
             self.ptab = None if ptab is None else ptab.to(dev)
             ws_bytes = self.lib.ctts_gpt_workspace_bytes(slots, 1)
             self.ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
@@ -136,7 +214,7 @@ class SlotPool:
         s.ids_buf, s.len, s.kv_start = self.ids_buf.data_ptr(), self.len.data_ptr(), self.kv_start.data_ptr()
         s.finish, s.end_idx, s.hiddens = self.finish.data_ptr(), self.end_idx.data_ptr(), self.hiddens.data_ptr()
         s.kcache, s.vcache, s.q, s.nq = self.kcache.data_ptr(), self.vcache.data_ptr(), self.q.data_ptr(), 1
-        s.temperature, s.pow_table = self.temp.data_ptr(), _lib.ptr(self.ptab)
+        s.temperature, s.pow_table = _lib.ptr(self.temp), _lib.ptr(self.ptab)
         p = self.plan
         s.top_p_thr = float(np.float32(1.0 - p.top_p)) if p.top_p is not None else 0.0
         s.use_top_p, s.top_k, s.use_top_k = int(p.top_p is not None), int(p.top_k or 0), int(p.top_k is not None)
@@ -149,17 +227,55 @@ class SlotPool:
         s.infer_text = 0
         s.rng_device, s.rng_per_step, s.rng_seed = int(self.device_rng), int(self.rng_per_step), _lib.ptr(self.rng_seed)
         s.rng_nonce = _lib.ptr(getattr(self, "rng_nonce", None))
+        if self.per_request:
+            s.temperature, s.pow_table = None, None
+            s.row_sampling, s.row_base = self.rows.data_ptr(), self.row_base.data_ptr()
         return s
 
     # -- request intake ---------------------------------------------------------------------------------------
-    def submit(self, rid, input_ids, text_mask=None, max_new_token: int = 512, stop_at: int = -1) -> None:
+    def submit(self, rid, input_ids, text_mask=None, max_new_token: int = 512, stop_at: int = -1, *, params=None, row_offset: int = 0,
+               total_rows: int = GPT.n_vq, emb: Optional[torch.Tensor] = None) -> None:
+        """Queues one request.  Per-request pools only: `params` (an `InferCodeParams` or a dict of its sampling fields: temperature,
+        top_P, top_K, repetition_penalty, min_new_token, manual_seed, ensure_non_empty), `row_offset` / `total_rows` (the request's
+        sampling rows inside the batch whose tokens it must reproduce -- (0, 4): alone at batch 1, what `Chat.infer` does for one text),
+        `emb` ([T, 768] prompt embedding with the speaker applied, `Chat.prompt_embedding`; None: the plain embedding of input_ids).
+        The request then yields exactly the tokens `GptEngine.generate` yields for it alone with those arguments.  Step 0 follows
+        generate's rule (gpt.py:527-570): a request whose first token is EOS yields no tokens (an empty result) -- unless it is unseeded
+        with `ensure_non_empty`, then it is generated again with a fresh draw."""
         ids = torch.as_tensor(input_ids).to(torch.int64)
         assert ids.dim() == 2 and ids.shape[1] == GPT.n_vq
         tm = torch.ones(ids.shape[0], dtype=torch.bool) if text_mask is None else torch.as_tensor(text_mask).bool()
         # 2 * POLL positions of slack: a request that ends by max_new_token (no EOS) is retired by the HOST, up to two chunks late
         if ids.shape[0] + max_new_token + 1 + 2 * self.POLL > self.cap or max_new_token > self.hid_cap:
             raise ValueError("request does not fit a slot (prompt + max_new_token + 2 * POLL vs cap, max_new_token vs hid_cap)")
-        self.queue.append(_Req(rid, ids, tm, int(max_new_token), int(stop_at)))
+        p = None
+        if self.per_request:
+            p = request_params(params)
+            if p.manual_seed is None and not self.device_rng:
+                raise NotImplementedError("a request without manual_seed needs a pool with the device generator (rng='device')")
+            if not (0 <= int(row_offset) and int(row_offset) + GPT.n_vq <= int(total_rows)):
+                raise ValueError("row_offset / total_rows: the request's 4 sampling rows must lie inside the batch")
+            if emb is not None and tuple(emb.shape) != (ids.shape[0], GPT.hidden):
+                raise ValueError("emb must be [T, 768] for a [T, 4] prompt")
+        elif params is not None or row_offset != 0 or total_rows != GPT.n_vq or emb is not None:
+            raise ValueError("params / row_offset / total_rows / emb need SlotPool(per_request=True)")
+        self.queue.append(_Req(rid, ids, tm, int(max_new_token), int(stop_at), p, int(row_offset), int(total_rows), emb))
+
+    def _admit_rows(self, slots: List[int], reqs: List[_Req], sl: torch.Tensor) -> None:
+        """per-request pools: the admitted slots' sampling table entries, global sampling rows and Exp(1) rows (stream-ordered)"""
+        dev, nvq = self.dev, GPT.n_vq
+        tab = []
+        for r in reqs:
+            seeded = r.params.manual_seed is not None
+            seed = (r.params.manual_seed if seeded else self.pool_seed) if self.device_rng else 0
+            row = sampling_row(r.params, seed, self.device_rng and not seeded)
+            tab.append(np.frombuffer(bytes(row), dtype=np.uint8))
+        self.rows[sl] = torch.from_numpy(np.stack(tab)).to(dev)
+        self.row_base[sl] = torch.tensor([r.row_offset for r in reqs], dtype=torch.int32, device=dev)
+        if not self.device_rng:
+            for s_, r in zip(slots, reqs):    # the request's rows of the draw of a total_rows batch (what generate uploads for it)
+                q = ExpDraws(r.total_rows, GPT.n_audio, r.params.manual_seed, row_begin=r.row_offset, row_end=r.row_offset + nvq).step(0)
+                self.q[0, s_ * nvq: (s_ + 1) * nvq] = q.to(dev)
 
     def _admit(self) -> None:
         # A group is left-padded to its longest prompt Tg, and every member then needs Tg + max_new_token + 1 <= cap (not just
@@ -189,6 +305,12 @@ class SlotPool:
         with torch.cuda.stream(self.st):
             sl = torch.tensor(slots, dtype=torch.long, device=dev)
             emb = self.eng.embed_prompt(ids, tmask)
+            for i, r in enumerate(reqs):
+                if r.emb is not None:
+                    t = int(r.ids.shape[0])
+                    emb[i, Tg - t:] = r.emb.to(device=dev, dtype=emb.dtype)
+            if self.per_request:
+                self._admit_rows(slots, reqs, sl)
             self.ids_buf[sl, :Tg] = ids.to(dev)
             self.len[sl] = Tg
             self.prompt_len[sl] = Tg
@@ -196,7 +318,7 @@ class SlotPool:
             self.finish[sl] = 0
             self.end_idx[sl] = 0
             self.stop_at[sl] = torch.tensor([r.stop_at for r in reqs], dtype=torch.int32, device=dev)
-            if getattr(self, "rng_nonce", None) is not None:
+            if getattr(self, "rng_nonce", None) is not None:   # (per-request pools: every admission; only unseeded rows read it)
                 self._admit_no = getattr(self, "_admit_no", 0) + n
                 # globally unique admission numbers (never the constant word of a plain generate() call)
                 self.rng_nonce[sl] = torch.arange(self._admit_no - n + 1, self._admit_no + 1, dtype=torch.int32, device=dev)
@@ -224,15 +346,18 @@ class SlotPool:
         self._snap_seq += 1
         return self._snap_seq - 1, blk, ev
 
-    def run(self) -> Iterator[Tuple[object, torch.Tensor, torch.Tensor]]:
+    def run(self, between=None) -> Iterator[Tuple[object, torch.Tensor, torch.Tensor]]:
         """Yields (request id, ids [n,4] int64, hiddens [n,768] float32) as requests complete, admitting queued
         requests into freed slots between decode chunks.  ONE chunk runs ahead: the next POLL steps are enqueued before the host
         looks at the previous chunk's flags, so the device never waits for the poll, the admission prefill or the result copies
         (a freed slot idles for at most two chunks instead of one).  A slot's entry only listens to snapshots enqueued after its
-        admission -- an older one still shows the previous occupant's flag."""
+        admission -- an older one still shows the previous occupant's flag.  `between` (optional callable): called once per chunk, before
+        admission -- a server submits newly arrived requests there and lets other GPU users in (SpeechBatcher)."""
         pending: Deque = deque()
         ready: Deque = deque()      # (event behind the result copies, results) of the previous poll
         while self.queue or self.active or pending:
+            if between is not None:
+                between()
             self._admit()
             if self.active:
                 _lib.check(self.lib.ctts_gpt_graph_launch(self.handle, self.POLL, self.st.cuda_stream), "ctts_gpt_graph_launch")
@@ -259,6 +384,15 @@ class SlotPool:
                 for s in done:
                     r, Tg, _ = self.active.pop(s)
                     n = min(int(end[s]), r.max_new)
+                    if self.per_request and n == 0 and bool(fin[s]) and r.stop_at < 0 and r.max_new > 0:
+                        # step 0 drew EOS: generate's rule (engine.py, gpt.py:527-570) -- an unseeded request with ensure_non_empty is
+                        # generated again (fresh admission number / draw), any other yields nothing
+                        self.finish[s] = 1
+                        if r.params.manual_seed is None and r.params.ensure_non_empty:
+                            self.queue.appendleft(r)
+                            continue
+                        outs.append((r.rid, self.ids_buf[s, :0].clone(), self.hiddens[s, :0].clone()))
+                        continue
                     outs.append((r.rid, self.ids_buf[s, Tg: Tg + n].clone(), self.hiddens[s, :n].clone()))
                     self.finish[s] = 1      # a request cut at max_new_token stops costing attention bandwidth
                 ev_out = torch.cuda.Event()
@@ -271,3 +405,141 @@ class SlotPool:
             wait_event(ev_out)
             for o in outs:
                 yield o
+
+
+class SpeechBatcher:
+    """Serves many non-streamed speech requests from ONE per-request slot pool (continuous batching behind `server.create_app(...,
+    batch_slots=N)`).  A single worker thread owns the pool and all GPU work of pooled requests: requests arrive through a thread-safe
+    queue (`submit` returns a Future), the worker builds their prompts with the code `Chat.infer` uses (normalise -> `Chat.code_prompt`
+    -> `Chat.prompt_embedding`), submits them between decode chunks, and decodes every finished request ALONE through the serial path's
+    decoder and silence strip (a ragged batch decode would let the DVAE conv biases of padded frames into the tails of shorter rows).
+    `gpu_lock` (a threading.Lock shared with the streamed path) is taken per decode chunk and per decode, never per request.
+    An error in one request fails that request's Future only.
+
+    `make_pool` (tests: a fake) builds the pool; by default a per-request SlotPool on `chat.gpt` with the engine's generator mode,
+    `cap` = the engine's position limit (the longest accepted prompt + max_new_token 2048 + slack), `hid_cap` 2048."""
+
+    def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
+                 logger=None):
+        import logging
+        self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
+        self.log = logger or logging.getLogger("chattts_amd.serving")
+        self._in: "queue.Queue" = queue.Queue()
+        self._futs: dict = {}
+        self._ids = itertools.count()
+        self.admissions = 0          # requests admitted into the pool
+        self.max_coresident = 0      # most requests resident in the pool at once
+        self.completed = 0
+        self.failed = 0
+        self._stop = False
+        if make_pool is None:
+            def make_pool():
+                eng = chat.gpt
+                return SlotPool(eng, slots=self.S, cap=cap if cap is not None else eng.max_pos, hid_cap=hid_cap,
+                                rng=getattr(eng, "rng", "host"), per_request=True)
+        self._make_pool = make_pool
+        with self.lock:
+            self.pool = make_pool()
+        self._thread = threading.Thread(target=self._loop, name="speech-batcher", daemon=True)
+        self._thread.start()
+
+    # -- public -------------------------------------------------------------------------------------------------------------
+    def submit(self, text: str, params) -> Future:
+        """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
+        int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return."""
+        fut: Future = Future()
+        self._in.put((next(self._ids), text, params, fut))
+        return fut
+
+    def occupancy(self) -> dict:
+        return {"slots": self.S, "active": len(getattr(self.pool, "active", {})), "queued": self._in.qsize() + len(getattr(self.pool, "queue", ())),
+                "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed}
+
+    def close(self):
+        self._stop = True
+        self._in.put(None)
+        self._thread.join(timeout=60)
+
+    # -- worker -------------------------------------------------------------------------------------------------------------
+    def _fail(self, rid, e: BaseException):
+        self.failed += 1
+        fut = self._futs.pop(rid, None)
+        if fut is not None and not fut.done():
+            fut.set_exception(e)
+
+    def _take(self, item) -> None:
+        """prompt of one request -> pool.submit (worker thread, GPU lock held)"""
+        rid, text, params, fut = item
+        self._futs[rid] = fut
+        try:
+            chat = self.chat
+            t = chat.normalizer(text, True, True, None)             # what Chat._infer does with do_text_normalization / homophones
+            ids, attn, tmask = chat.code_prompt([t], params)
+            emb = chat.prompt_embedding(ids, tmask, params, chat.tokenizer.spk_emb_ids)
+            keep = attn[0].bool()
+            self.pool.submit(rid, ids[0][keep], tmask[0][keep], max_new_token=params.max_new_token, params=params, emb=emb[0][keep.to(emb.device)])
+            self.admissions += 1
+        except Exception as e:        # this request's error, not the worker's
+            self._fail(rid, e)
+
+    def _drain(self, block: bool) -> bool:
+        """moves arrived requests into the pool; False once close() was called"""
+        while True:
+            try:
+                item = self._in.get(block=block, timeout=0.5 if block else None)
+            except queue.Empty:
+                return not self._stop
+            if item is None:
+                return False
+            block = False
+            with self.lock:
+                self._take(item)
+
+    def _between(self):
+        self.max_coresident = max(self.max_coresident, len(self.pool.active))
+        self.lock.release()           # one decode chunk done: a streamed request may take the GPU now
+        time.sleep(0)
+        self._drain(block=False)
+        self.lock.acquire()
+
+    def finish(self, hid: torch.Tensor) -> np.ndarray:
+        """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
+        from .audio import float_to_int16
+        if hid.shape[0] == 0:
+            raise RuntimeError("the engine returned no audio (the first token was EOS)")
+        wav = self.chat.decode_to_wavs([hid])[0]
+        return float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
+
+    def _loop(self):
+        while self._drain(block=True) or self.pool.queue:
+            if not self.pool.queue:
+                continue
+            self.lock.acquire()
+            try:
+                it = self.pool.run(between=self._between)
+                while True:
+                    try:
+                        rid, ids, hid = next(it)
+                    except StopIteration:
+                        break
+                    except Exception as e:     # the pool itself failed: the requests in it fail, a fresh pool serves the next ones
+                        self.log.error("slot pool failed: %s", e)
+                        for r in list(self._futs):
+                            self._fail(r, e)
+                        close = getattr(self.pool, "close", None)
+                        if close is not None:
+                            close()
+                        self.pool = self._make_pool()
+                        break
+                    fut = self._futs.pop(rid, None)
+                    if fut is None:
+                        continue
+                    try:
+                        pcm = self.finish(hid)
+                        self.completed += 1
+                        fut.set_result(pcm)
+                    except Exception as e:
+                        self.failed += 1
+                        fut.set_exception(e)
+            finally:
+                self.lock.release()

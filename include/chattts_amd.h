@@ -93,6 +93,26 @@ typedef struct {
   const void* const* wd_x3;
 } ctts_gpt_weights;
 
+/* Per-utterance-slot sampling parameters (ctts_gen_state.row_sampling): what the call-wide sampling fields of ctts_gen_state say, for
+ * ONE utterance slot, so that requests with different InferCodeParams (core.py:95-110) share one batch / one slot pool -- the role of
+ * the reference's per-request SamplingParams in its optional vLLM engine (ChatTTS/model/velocity/sampling_params.py:24).  Code mode
+ * only.  128 bytes, every field at a fixed offset (tests/test_sampling_rows_host.py checks the layout against the Python side). */
+typedef struct {
+  float temperature[4];            /* per-codebook temperature (gpt.py:350-355,487) */
+  float pow_table[17];             /* penalty^count, count 0..16, exactly as torch computes it (processors.py:29; rng.penalty_table) */
+  int32_t use_penalty;             /* 0: no repetition penalty (penalty == 1, the reference adds no processor, gpt.py:389-391) */
+  float top_p_thr;                 /* float32(1 - top_P), rounded on the host (processors.py:38-58, the `cum <= 1 - top_p` test) */
+  int32_t use_top_p;               /* 0: top_P is None */
+  int32_t top_k;                   /* TopK's k (min_tokens_to_keep 3 is applied by the kernel) */
+  int32_t use_top_k;               /* 0: top_K is None */
+  int32_t min_new;                 /* min_new_token (gpt.py:494-495) */
+  int32_t reserved0;
+  uint64_t rng_seed;               /* device generator only: this slot's seed (ctts_gen_state.rng_seed replaced) */
+  int32_t rng_per_step;            /* device generator only: 1 = fresh draw every step (manual_seed None; counter word 3 = rng_nonce[b]),
+                                      0 = the same draw every step (manual_seed set; counter word 3 = CTTS_RNG_WORD3) */
+  int32_t reserved1;
+} ctts_sampling_row;
+
 /* One generate() call's device state (every array is caller-allocated, device memory). */
 typedef struct {
   int32_t B, T, max_new;           /* rows, padded prompt length, max_new_token (gpt.py:323) */
@@ -183,6 +203,13 @@ typedef struct {
    * known to the host.  > 0: the prompt pass runs over those rows only instead of over all B * T left-padded rows (the reference computes
    * the pad rows and never consumes them, gpt.py:234-241).  0: every row.  Same KV cache contents for the valid slots, same token. */
   int32_t prefill_valid_rows;
+  /* [slots] or NULL, code mode only: per-utterance-slot sampling parameters (ctts_sampling_row above).  When set, the sampling of utterance
+   * slot b -- decode steps (eager and graph replay), the prefill's step-0 sample, ctts_k_sample -- reads temperature, pow_table,
+   * top_p_thr / use_top_p, top_k / use_top_k, min_new, and (device generator) rng_seed / rng_per_step from row_sampling[b] instead of
+   * the call-wide fields above, which are then not read (temperature / pow_table / rng_seed may be NULL).  Where the slot's draws come from
+   * is unchanged: row_base[b] (or row_offset + 4 b) is its global sampling row (the rows >= 625 penalty quirk, the device generator's
+   * counter), q[b] holds its own Exp(1) rows.  The parity certificate (margin) uses the row's own values.  NULL: the call-wide fields. */
+  const ctts_sampling_row* row_sampling;
 } ctts_gen_state;
 
 int ctts_gpt_create(ctts_gpt** out, const ctts_gpt_weights* w);

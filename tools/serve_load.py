@@ -1,0 +1,114 @@
+"""Load test of the speech endpoint: N concurrent non-streamed requests (several voices and texts) sent to the app in-process, once with
+batching (`create_app(..., batch_slots=S)`) and once without, plus the sampling kernel's cost in a per-request pool vs a plain pool.
+Prints one JSON line.  Not a bench.py leg.
+
+    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
+
+Synthetic weights (chattts_amd.weights) and the repository's test tokenizer: random weights do not stop on cue, so every request is capped
+at --max-new tokens (the endpoint's own max_new_token is 2048).  audio_s_per_s = seconds of returned audio / wall seconds of the burst."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import threading
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from chattts_amd import _lib, server  # noqa: E402
+from chattts_amd.core import Chat  # noqa: E402
+from chattts_amd.serving import SlotPool  # noqa: E402
+from chattts_amd.weights import synthetic_all  # noqa: E402
+
+TEXTS = ["What is [uv_break]your favorite english food?", "Hello there, how are you today?", "The quick brown fox jumps over the lazy dog.",
+         "Good morning, and welcome to the show.", "Numbers like 42 and 7 are read out loud.", "A longer sentence, with a pause, and an ending."]
+
+
+def burst(chat, voices, n, batch_slots):
+    from starlette.testclient import TestClient
+    app = server.create_app(chat, voices, batch_slots=batch_slots)
+    names = sorted(voices)
+    lat, samples, codes = [0.0] * n, [0] * n, [0] * n
+    with TestClient(app) as c:
+        c.post("/v1/audio/speech", json={"input": "Warm up.", "response_format": "pcm"})       # first-call costs out of the burst
+
+        def one(i):
+            t0 = time.perf_counter()
+            r = c.post("/v1/audio/speech", json={"input": TEXTS[i % len(TEXTS)], "voice": names[i % len(names)], "response_format": "pcm"})
+            lat[i] = time.perf_counter() - t0
+            codes[i] = r.status_code
+            if r.status_code == 200:
+                samples[i] = len(r.content) // 2
+            else:
+                print(f"request {i}: {r.status_code} {r.text[:300]}", file=sys.stderr)
+        t0 = time.perf_counter()
+        ths = [threading.Thread(target=one, args=(i,)) for i in range(n)]
+        for th in ths:
+            th.start()
+        for th in ths:
+            th.join()
+        wall = time.perf_counter() - t0
+        health = c.get("/health").json()
+    if app.state.batcher is not None:
+        app.state.batcher.close()
+    audio = sum(samples) / server.SAMPLE_RATE
+    return dict(failed=sum(c != 200 for c in codes), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3), audio_s=round(audio, 2),
+                p50_s=round(float(np.percentile(lat, 50)), 3), p95_s=round(float(np.percentile(lat, 95)), 3),
+                max_coresident=(health.get("pool") or {}).get("max_coresident", 1))
+
+
+def sample_k_ms(eng, per_request, slots, steps=64):
+    """mean sample_k time (profile tag 9) over `steps` eager decode steps of a full pool of identical requests"""
+    pool = SlotPool(eng, slots=slots, cap=512, hid_cap=256, manual_seed=42, per_request=per_request)
+    rs = np.random.RandomState(3)
+    for i in range(slots):
+        ids = np.repeat(rs.randint(1, 21178, size=(24, 1)), 4, axis=1).astype(np.int64)
+        kw = dict(params=dict(manual_seed=42)) if per_request else {}
+        pool.submit(i, ids, max_new_token=200, stop_at=200, **kw)
+    pool._admit()
+    lib = pool.lib
+    _lib.check(lib.ctts_gpt_profile_begin(pool.handle, 9, 4096, 1), "profile_begin")
+    for _ in range(steps):
+        _lib.check(lib.ctts_gpt_decode_step(pool.handle, C.byref(pool.dec), pool.st.cuda_stream), "decode_step")
+    pool.st.synchronize()
+    n, tot = C.c_int32(0), C.c_double(0.0)
+    _lib.check(lib.ctts_gpt_profile_end(pool.handle, C.byref(n), C.byref(tot)), "profile_end")
+    pool.close()
+    return tot.value / max(1, n.value)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=16)
+    ap.add_argument("--slots", type=int, default=8)
+    ap.add_argument("--max-new", type=int, default=256)
+    ap.add_argument("--dtype", default="bf16")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    gold = os.path.join(ROOT, "tests", "golden")
+    with open(os.path.join(gold, "spk_stat.txt"), encoding="utf-8") as f:
+        spk_stat = f.read()
+    chat = Chat()
+    assert chat.load(state_dicts=synthetic_all(), device=dev, dtype=a.dtype, tokenizer=os.path.join(gold, "tokenizer"), spk_stat=spk_stat)
+    torch.manual_seed(5)
+    voices = {"default": chat.sample_random_speaker(), "alloy": chat.sample_random_speaker(), "echo": chat.sample_random_speaker()}
+    orig = chat.InferCodeParams
+    chat.InferCodeParams = lambda **kw: orig(**{**kw, "max_new_token": a.max_new})
+    serial = burst(chat, voices, a.n, None)
+    batched = burst(chat, voices, a.n, a.slots)
+    plain_ms = sample_k_ms(chat.gpt, False, a.slots)
+    table_ms = sample_k_ms(chat.gpt, True, a.slots)
+    print(json.dumps(dict(metric="serve_load", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, serial=serial, batched=batched,
+                          speedup=round(batched["audio_s_per_s"] / serial["audio_s_per_s"], 2),
+                          sample_k_us=dict(plain_pool=round(plain_ms * 1e3, 2), per_request_pool=round(table_ms * 1e3, 2)))))
+
+
+if __name__ == "__main__":
+    main()
