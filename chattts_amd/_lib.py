@@ -120,6 +120,10 @@ SIGNATURES = {
     "ctts_float_to_int16": (C.c_int, [P, P, P, I32, C.c_int64, C.c_int64, I32, I32, F, P, P]),
     "ctts_dvae_decode": (C.c_int, [P, P, P, I32, I32, P, SZ, P]),
     "ctts_vocos_decode": (C.c_int, [P, P, P, I32, I32, P, SZ, P]),
+    "ctts_codec_ragged_workspace_bytes": (SZ, [I32, I32]),
+    "ctts_dvae_decode_ragged": (C.c_int, [P, P, P, P, I32, P, P, SZ, P]),
+    "ctts_vocos_decode_ragged": (C.c_int, [P, P, P, P, I32, P, P, SZ, P]),
+    "ctts_float_to_int16_ragged": (C.c_int, [P, P, P, P, P, I32, I32, F, P, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),
     "ctts_dvae_destroy": (None, [P]),
     "ctts_dvae_code_frames": (I32, [I32]),

@@ -26,7 +26,7 @@ from . import weights as W
 from .audio import float_to_int16
 from .config import GPT
 from .dvae import DvaeEngine
-from .engine import CodecEngine, Context, GenerationOutputs, GptEngine, gen_logits
+from .engine import CodecEngine, Context, GenerationOutputs, GptEngine, gen_logits, keep_offsets, ragged_views
 from .frontend import Normalizer, Speaker, Tokenizer, apply_speaker
 
 
@@ -243,11 +243,23 @@ class Chat:
             params.min_new_token, (*procs, *warpers), True, False, False, False, params.show_tqdm, params.ensure_non_empty,
             24, params.manual_seed, self.context, **kw))
 
-    def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None) -> np.ndarray:
+    def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None, *,
+                       ragged: bool = False):
         """`Chat._decode_to_wavs` (core.py:513-539) -> np.float32 [B, n]: per-row hidden states [T_b,768] through the
         decoder, or (use_decoder=False) per-row token ids [T_b,4] through the full DVAE's codebook; then Vocos.
-        `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded)."""
+        `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded).
+        `ragged=True` (not the reference's batch semantics): every row decoded as if alone, in one pass (CodecEngine.decode_ragged)
+        -> List[np.ndarray], row b's 256 (2 T_b - 1) samples; the decoder path only."""
+        if ragged and not use_decoder:
+            raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
+        if ragged:
+            if pad_to is not None:
+                raise ValueError("ragged decoding decodes every row at its own length: pad_to does not apply")
+            if len(result_list) == 0:
+                return []
+            wav, off = self.codec.decode_ragged(list(result_list))
+            return ragged_views(self.codec.to_host(wav), off)
         if len(result_list) == 0:
             return np.array([], dtype=np.float32)
         if use_decoder:
@@ -255,13 +267,17 @@ class Chat:
         return self.codec.to_host(self.codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to)))
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
-                        product: str = "f64") -> List[np.ndarray]:
+                        product: str = "f64", *, ragged: bool = False) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
         Returns one int16 array per utterance, equal to `float_to_int16(wav[np.abs(wav) > 1e-5])` bit for bit (the strip only removes
         samples that are far below one count, so the peak -- hence the scale -- is that of the unstripped row)."""
+        if ragged and not use_decoder:
+            raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
+        if ragged:
+            return self._decode_to_pcm16_ragged(result_list, strip, product)
         if len(result_list) == 0:
             return []
         wav = self.codec.decode_to_wavs(result_list) if use_decoder else self.codec.vocos_decode(self.dvae.decode_codes(result_list))
@@ -272,6 +288,28 @@ class Chat:
         keep_h = self.codec.to_host(keep)
         n = pcm_h.shape[1]
         return [pcm_h[b][np.unpackbits(keep_h[b])[:n].astype(bool)] for b in range(pcm_h.shape[0])]
+
+    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str) -> List[np.ndarray]:
+        """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
+        PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's result equals
+        `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w."""
+        if len(result_list) == 0:
+            return []
+        codec = self.codec
+        wav, off = codec.decode_ragged(list(result_list))
+        n = wav.numel()
+        kb = int(keep_offsets(off)[-1]) if strip else 0
+        blob = torch.empty(((2 * n + kb + 15) // 16 * 16,), dtype=torch.uint8, device=wav.device)
+        pcm_d = blob[: 2 * n].view(torch.int16)
+        keep_d = blob[2 * n: 2 * n + kb] if strip else None
+        _, _, keep_off = codec.float_to_int16_ragged(wav, off, product=product, keep_thr=1e-5 if strip else None, out=(pcm_d, keep_d))
+        host = codec.to_host(blob)
+        pcm_h = host[: 2 * n].view(np.int16)
+        pieces = ragged_views(pcm_h, off)
+        if not strip:
+            return pieces
+        keep_h = host[2 * n: 2 * n + kb]
+        return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
         """non-stream `Chat._infer` body for one batch (core.py:469-481, split_text=False, skip_refine_text=True),
@@ -421,12 +459,19 @@ class Chat:
     def infer(self, text, stream=False, lang=None, skip_refine_text=False, refine_text_only=False, use_decoder=True,
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
-              *, pcm16: bool = False):
+              *, pcm16: bool = False, ragged_decode: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
         `float_to_int16` (tools/audio/np.py:7-11) on each returned waveform / on each row of each streamed chunk, computed on the
-        device so that half the bytes cross PCIe: `infer(t, pcm16=True)[i] == float_to_int16(infer(t)[i])` bit for bit."""
+        device so that half the bytes cross PCIe: `infer(t, pcm16=True)[i] == float_to_int16(infer(t)[i])` bit for bit.
+        `ragged_decode=True` (keyword-only, non-streamed only; NOT the reference's batch semantics): every utterance of a batch is
+        decoded as if alone (CodecEngine.decode_ragged) instead of as a row of the reference's zero-padded batch, so a shorter
+        utterance's last second no longer depends on the longer ones it was batched with."""
+        if ragged_decode and stream:
+            raise ValueError("ragged_decode applies to non-streamed inference only")
+        if ragged_decode and not use_decoder:
+            raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         self.context.set(False)
         if split_text and isinstance(text, str):
             if "\n" in text:
@@ -438,7 +483,7 @@ class Chat:
             return []
         res_gen = self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
-                              pcm16=pcm16 and not refine_text_only and not (split_text and not stream))
+                              pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode)
         if stream:
             return res_gen
         if refine_text_only:
@@ -452,7 +497,8 @@ class Chat:
         return [np.concatenate(stripped)] if split_text else stripped
 
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
-               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False):
+               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
+               ragged: bool = False):
         """core.py:395-503 (generator)."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -485,7 +531,10 @@ class Chat:
             for result in self._infer_code(batch, stream, self.device, use_decoder, params_infer_code):
                 if not stream:
                     src = result.hiddens if use_decoder else result.ids
-                    wavs = self.decode_to_pcm16(src, use_decoder) if pcm16 else self.decode_to_wavs(src, use_decoder)
+                    if ragged:      # every utterance as if alone (Chat.infer's ragged_decode)
+                        wavs = self.decode_to_pcm16(src, ragged=True) if pcm16 else self.decode_to_wavs(src, ragged=True)
+                    else:
+                        wavs = self.decode_to_pcm16(src, use_decoder) if pcm16 else self.decode_to_wavs(src, use_decoder)
                     result.destroy()
                     yield wavs
                     continue

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <map>
 #include <vector>
 
@@ -866,14 +867,15 @@ static GemmArgs lin(const float* A, int lda, const float* W, float* C, int ldc, 
 }
 // dense layer of the decoder: f32 MFMA tiles, or split-bf16 tiles when the weights were packed [N][Kp/32][2][32] bf16
 static hipError_t dense(const ctts_codec* c, const GemmArgs& a, hipStream_t st);
-static GemmArgs conv(const float* X, int cin, const float* W, float* C, int cout, int B, int F, int taps, int pad, int epi) {
+// seg != null: B = 1, the F frames are packed segments and the gather stays inside each row's own segment (ragged decode)
+static GemmArgs conv(const float* X, int cin, const float* W, float* C, int cout, int B, int F, int taps, int pad, int epi, const int2* seg) {
   GemmArgs a = lin(X, cin, W, C, cout, B * F, cout, taps * cin, epi);
-  a.taps = taps; a.cin = cin; a.frames = F; a.pad = pad; a.dil = 1;
+  a.taps = taps; a.cin = cin; a.frames = F; a.pad = pad; a.dil = 1; a.seg = seg;
   return a;
 }
 
 static int convnext_stack(const ctts_codec* c, int n, const std::vector<const float*>* p, const std::vector<const void*>* px, int inter, int dil,
-                          CodecWs& ws, int B, int F, hipStream_t st) {
+                          CodecWs& ws, int B, int F, hipStream_t st, const int2* seg) {
   const int R = B * F;
   const bool f16 = c->w.gemm_mode == 2;   // one fp16 plane per operand (gemm_h1p_k) instead of hi | lo bf16 planes (gemm_x3p_k)
   const bool x3p = c->w.gemm_mode >= 1 && !px[0].empty() && c->x3p_min_rows > 0 && R >= c->x3p_min_rows && inter % 256 == 0;
@@ -881,7 +883,7 @@ static int convnext_stack(const ctts_codec* c, int n, const std::vector<const fl
     // depthwise conv + LayerNorm -> bf16 planes; pwconv1 + GELU -> bf16 planes; pwconv2 * gamma + residual -> f32 rows
     uint16_t* bp = reinterpret_cast<uint16_t*>(ws.b);     // [R256][512] as hi / lo planes: the bytes of the f32 buffer
     uint16_t* bigp = reinterpret_cast<uint16_t*>(ws.big);
-    CK(launch_dwconv_ln(ws.a, p[0][i], p[1][i], p[2][i], p[3][i], 1e-6f, dil, nullptr, B, F, 512, st, bp, f16 ? 1 : 0));
+    CK(launch_dwconv_ln(ws.a, p[0][i], p[1][i], p[2][i], p[3][i], 1e-6f, dil, nullptr, B, F, 512, st, bp, f16 ? 1 : 0, seg));
     if (f16 && mlp_fused_pays(R)) {   // round 6: the pair in one launch, the inter-wide activation stays on the CU (bit-identical)
       MlpArgs m;
       memset(&m, 0, sizeof(m));
@@ -899,7 +901,7 @@ static int convnext_stack(const ctts_codec* c, int n, const std::vector<const fl
     CK(f16 ? launch_gemm_h1p(g, st) : launch_gemm_x3p(g, st));
   }
   for (int i = 0; !x3p && i < n; ++i) {
-    CK(launch_dwconv_ln(ws.a, p[0][i], p[1][i], p[2][i], p[3][i], 1e-6f, dil, ws.b, B, F, 512, st));
+    CK(launch_dwconv_ln(ws.a, p[0][i], p[1][i], p[2][i], p[3][i], 1e-6f, dil, ws.b, B, F, 512, st, nullptr, 0, seg));
     GemmArgs g1 = lin(ws.b, 512, p[4][i], ws.big, inter, R, inter, 512, EPI_BIAS_GELU);
     g1.bias = p[5][i];
     CK(dense(c, g1, st));
@@ -914,27 +916,44 @@ static hipError_t dense(const ctts_codec* c, const GemmArgs& a, hipStream_t st) 
   return c->w.gemm_mode >= 1 ? launch_gemm_tiled_bf16x3(a, st) : launch_gemm_tiled(a, st);   // mode 2: only the ConvNeXt point-wise pairs are fp16
 }
 
+// the decoder bodies: [B, F] batches (seg null) or B = 1 packed segments (seg = the per-frame bounds table, ragged decode)
+static int dvae_body(ctts_codec* c, const float* hid, float* mel, int B, int F, CodecWs& ws, const int2* seg, hipStream_t st) {
+  // dvae.py:281-287: [B,T,768] viewed as [B,2T,384] channels-last
+  GemmArgs c0 = conv(hid, 384, c->w.conv_in0_w, ws.big, 128, B, F, 3, 1, EPI_BIAS_GELU, seg);
+  c0.bias = c->w.conv_in0_b;
+  CK(dense(c, c0, st));
+  GemmArgs c2 = conv(ws.big, 128, c->w.conv_in2_w, ws.a, 512, B, F, 3, 1, EPI_BIAS, seg);
+  c2.bias = c->w.conv_in2_b;
+  CK(dense(c, c2, st));
+  if (convnext_stack(c, c->w.n_dvae_blocks, c->d, c->dx, 2048, 2, ws, B, F, st, seg)) return -1;
+  CK(dense(c, lin(ws.a, 512, c->w.conv_out_w, ws.mid, 384, B * F, 384, 512, EPI_STORE), st));
+  GemmArgs oc = conv(ws.mid, 384, c->w.out_conv_w, mel, 100, B, F, 3, 1, EPI_SCALE, seg);
+  oc.gamma = c->w.coef;
+  CK(dense(c, oc, st));
+  return 0;
+}
+
+static int vocos_body(ctts_codec* c, const float* mel, int B, int F, CodecWs& ws, const int2* seg, hipStream_t st) {   // -> ws.big: the head
+  GemmArgs e = conv(mel, 100, c->w.v_embed_w, ws.b, 512, B, F, 7, 3, EPI_BIAS, seg);
+  e.bias = c->w.v_embed_b;
+  CK(dense(c, e, st));
+  CK(launch_layernorm(ws.b, c->w.v_norm_w, c->w.v_norm_b, 1e-6f, ws.a, B * F, 512, st));
+  if (convnext_stack(c, c->w.n_vocos_blocks, c->v, c->vx, 1536, 1, ws, B, F, st, seg)) return -1;
+  CK(launch_layernorm(ws.a, c->w.v_final_w, c->w.v_final_b, 1e-6f, ws.b, B * F, 512, st));
+  GemmArgs h = lin(ws.b, 512, c->w.head_w, ws.big, 1026, B * F, 1026, 512, EPI_BIAS);
+  h.bias = c->w.head_b;
+  CK(dense(c, h, st));
+  return 0;
+}
+
 extern "C" int ctts_dvae_decode(ctts_codec* c, const float* hid, float* mel, int32_t B, int32_t T, void* workspace, size_t ws_bytes,
                                 void* stream) {
   if (!c || B <= 0 || T <= 0) return fail("ctts_dvae_decode: bad arguments");
   CttsDeviceGuard dg(stream);
   const int F = 2 * T;
   if (ws_bytes < ctts_codec_workspace_bytes(B, F)) return fail("codec workspace too small");
-  hipStream_t st = (hipStream_t)stream;
   CodecWs ws = carve_codec(workspace, B, F);
-  // dvae.py:281-287: [B,T,768] viewed as [B,2T,384] channels-last
-  GemmArgs c0 = conv(hid, 384, c->w.conv_in0_w, ws.big, 128, B, F, 3, 1, EPI_BIAS_GELU);
-  c0.bias = c->w.conv_in0_b;
-  CK(dense(c, c0, st));
-  GemmArgs c2 = conv(ws.big, 128, c->w.conv_in2_w, ws.a, 512, B, F, 3, 1, EPI_BIAS);
-  c2.bias = c->w.conv_in2_b;
-  CK(dense(c, c2, st));
-  if (convnext_stack(c, c->w.n_dvae_blocks, c->d, c->dx, 2048, 2, ws, B, F, st)) return -1;
-  CK(dense(c, lin(ws.a, 512, c->w.conv_out_w, ws.mid, 384, B * F, 384, 512, EPI_STORE), st));
-  GemmArgs oc = conv(ws.mid, 384, c->w.out_conv_w, mel, 100, B, F, 3, 1, EPI_SCALE);
-  oc.gamma = c->w.coef;
-  CK(dense(c, oc, st));
-  return 0;
+  return dvae_body(c, hid, mel, B, F, ws, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int ctts_vocos_decode(ctts_codec* c, const float* mel, float* wav, int32_t B, int32_t F, void* workspace, size_t ws_bytes,
@@ -944,16 +963,63 @@ extern "C" int ctts_vocos_decode(ctts_codec* c, const float* mel, float* wav, in
   if (ws_bytes < ctts_codec_workspace_bytes(B, F)) return fail("codec workspace too small");
   hipStream_t st = (hipStream_t)stream;
   CodecWs ws = carve_codec(workspace, B, F);
-  GemmArgs e = conv(mel, 100, c->w.v_embed_w, ws.b, 512, B, F, 7, 3, EPI_BIAS);
-  e.bias = c->w.v_embed_b;
-  CK(dense(c, e, st));
-  CK(launch_layernorm(ws.b, c->w.v_norm_w, c->w.v_norm_b, 1e-6f, ws.a, B * F, 512, st));
-  if (convnext_stack(c, c->w.n_vocos_blocks, c->v, c->vx, 1536, 1, ws, B, F, st)) return -1;
-  CK(launch_layernorm(ws.a, c->w.v_final_w, c->w.v_final_b, 1e-6f, ws.b, B * F, 512, st));
-  GemmArgs h = lin(ws.b, 512, c->w.head_w, ws.big, 1026, B * F, 1026, 512, EPI_BIAS);
-  h.bias = c->w.head_b;
-  CK(dense(c, h, st));
+  if (vocos_body(c, mel, B, F, ws, nullptr, st)) return -1;
   CK(launch_istft(ws.big, c->w.window, c->w.twiddle, ws.frames, wav, B, F, st));
+  return 0;
+}
+
+// ---- ragged decode: packed segments, each decoded as if alone ---------------------------------------------------------------
+// workspace = the [1, sum F_i] codec workspace + the per-frame segment bounds table behind it
+static size_t ragged_table_offset(int total_tokens) { return carve_codec(nullptr, 1, 2 * total_tokens).bytes; }
+extern "C" size_t ctts_codec_ragged_workspace_bytes(int32_t n_seg, int32_t total_tokens) {
+  if (n_seg < 1 || total_tokens < n_seg) return 0;
+  return ragged_table_offset(total_tokens) + align_up((size_t)2 * total_tokens * sizeof(int2));
+}
+// token offsets (host copy): offs[0] = 0, strictly ascending (no empty segment); returns the total and the longest segment, or -1
+static int check_offsets(const char* who, const int32_t* offs, int n_seg, int* t_max) {
+  if (!offs || n_seg < 1) return fail("%s: need n_seg >= 1 and the host offsets", who);
+  if (offs[0] != 0) return fail("%s: the first token offset must be 0 (got %d)", who, offs[0]);
+  int mx = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    if (offs[i + 1] <= offs[i]) return fail("%s: segment %d is empty or the offsets do not ascend (%d -> %d)", who, i, offs[i], offs[i + 1]);
+    if (offs[i + 1] > (1 << 28)) return fail("%s: too many tokens", who);
+    mx = std::max(mx, offs[i + 1] - offs[i]);
+  }
+  *t_max = mx;
+  return offs[n_seg];
+}
+
+extern "C" int ctts_dvae_decode_ragged(ctts_codec* c, const float* hid, const int32_t* tok_off_dev, const int32_t* tok_off_host, int32_t n_seg,
+                                       float* mel, void* workspace, size_t ws_bytes, void* stream) {
+  if (!c || !hid || !mel || !tok_off_dev) return fail("ctts_dvae_decode_ragged: bad arguments");
+  int t_max = 0;
+  const int T = check_offsets("ctts_dvae_decode_ragged", tok_off_host, n_seg, &t_max);
+  if (T < 0) return -1;
+  if (!workspace || ws_bytes < ctts_codec_ragged_workspace_bytes(n_seg, T)) return fail("codec workspace too small");
+  CttsDeviceGuard dg(stream);
+  hipStream_t st = (hipStream_t)stream;
+  const int F = 2 * T;
+  CodecWs ws = carve_codec(workspace, 1, F);
+  int2* seg = (int2*)((char*)workspace + ragged_table_offset(T));
+  CK(launch_segment_table(tok_off_dev, n_seg, seg, st));
+  return dvae_body(c, hid, mel, 1, F, ws, seg, st);
+}
+
+extern "C" int ctts_vocos_decode_ragged(ctts_codec* c, const float* mel, const int32_t* tok_off_dev, const int32_t* tok_off_host, int32_t n_seg,
+                                        float* wav, void* workspace, size_t ws_bytes, void* stream) {
+  if (!c || !mel || !wav || !tok_off_dev) return fail("ctts_vocos_decode_ragged: bad arguments");
+  int t_max = 0;
+  const int T = check_offsets("ctts_vocos_decode_ragged", tok_off_host, n_seg, &t_max);
+  if (T < 0) return -1;
+  if (!workspace || ws_bytes < ctts_codec_ragged_workspace_bytes(n_seg, T)) return fail("codec workspace too small");
+  CttsDeviceGuard dg(stream);
+  hipStream_t st = (hipStream_t)stream;
+  const int F = 2 * T;
+  CodecWs ws = carve_codec(workspace, 1, F);
+  int2* seg = (int2*)((char*)workspace + ragged_table_offset(T));
+  CK(launch_segment_table(tok_off_dev, n_seg, seg, st));
+  if (vocos_body(c, mel, 1, F, ws, seg, st)) return -1;
+  CK(launch_istft_ragged(ws.big, c->w.window, c->w.twiddle, ws.frames, wav, tok_off_dev, n_seg, F, 2 * t_max, st));
   return 0;
 }
 
@@ -1206,6 +1272,20 @@ extern "C" int ctts_float_to_int16(const float* wav, int16_t* pcm, uint8_t* keep
   if (!wav || !pcm || !peak || rows < 0 || n < 0 || ld < n || (product != 0 && product != 1)) return fail("ctts_float_to_int16: bad arguments");
   CttsDeviceGuard dg(stream);
   CK(launch_float_to_int16(wav, n, ld, rows, per_row != 0, product, keep_thr, peak, pcm, keep_bits, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ctts_float_to_int16_ragged(const float* wav, int16_t* pcm, uint8_t* keep_bits, const int64_t* off_dev, const int64_t* off_host,
+                                          int32_t n_seg, int32_t product, float keep_thr, uint32_t* peak, void* stream) {
+  if (!wav || !pcm || !peak || !off_dev || !off_host || n_seg < 1 || (product != 0 && product != 1))
+    return fail("ctts_float_to_int16_ragged: bad arguments");
+  if (off_host[0] != 0) return fail("ctts_float_to_int16_ragged: the first sample offset must be 0");
+  long long n_max = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    if (off_host[i + 1] <= off_host[i]) return fail("ctts_float_to_int16_ragged: segment %d is empty or the offsets do not ascend", i);
+    n_max = std::max(n_max, (long long)(off_host[i + 1] - off_host[i]));
+  }
+  CttsDeviceGuard dg(stream);
+  CK(launch_float_to_int16_ragged(wav, (const long long*)off_dev, n_seg, n_max, product, keep_thr, peak, pcm, keep_bits, (hipStream_t)stream));
   return 0;
 }
 extern "C" int ctts_copy_bytes(void* dst, const void* src, size_t bytes, void* stream) {

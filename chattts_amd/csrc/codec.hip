@@ -55,11 +55,15 @@ __device__ __forceinline__ void ln_finish(float* y, const float* __restrict__ lw
   }
 }
 
-// w is the depthwise kernel transposed on the host to [7][C] so that a lane's CPL channels are contiguous
-template <int CPL, bool F16 = false>
+// w is the depthwise kernel transposed on the host to [7][C] so that a lane's CPL channels are contiguous.
+// SEG (all three dwconv kernels): B = 1 and the frames are packed segments; seg[f] = [lo, hi) of frame f's segment, and the tap pair
+// (output frame f, input row r) counts only when r lies in it -- every segment is zero padded at its own edges, as if decoded alone.
+// The plain instantiations (SEG = false) compile to the same code as before: the bounds are the constants 0 and F there.
+template <int CPL, bool F16 = false, bool SEG = false>
 __global__ __launch_bounds__(256) void dwconv_ln_k(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                    const float* __restrict__ lw, const float* __restrict__ lb, float eps, int dil,
-                                                   float* __restrict__ y, int F, int rows, uint16_t* __restrict__ yp) {
+                                                   float* __restrict__ y, int F, int rows, uint16_t* __restrict__ yp,
+                                                   const int2* __restrict__ seg) {
   constexpr int C = 64 * CPL;
   // XCD-aware frame order: workgroup L runs on XCD L % 8 (observed placement, speed only) and each XCD has its own L2.  The 7
   // taps of a frame are the rows f - 3 dil .. f + 3 dil; with the plain order every XCD touches every 8th group of 4 frames and
@@ -71,6 +75,7 @@ __global__ __launch_bounds__(256) void dwconv_ln_k(const float* __restrict__ x, 
   if (row >= rows) return;
   const int lane = threadIdx.x & 63, c0 = lane * CPL;
   const int bi = row / F, f = row - bi * F;
+  const int2 sb = SEG ? seg[row] : make_int2(0, F);
   float acc[CPL];
 #pragma unroll
   for (int q = 0; q < CPL / 4; ++q) {
@@ -80,7 +85,7 @@ __global__ __launch_bounds__(256) void dwconv_ln_k(const float* __restrict__ x, 
 #pragma unroll
   for (int j = 0; j < 7; ++j) {
     const int fs = f + (j - 3) * dil;
-    if (fs >= 0 && fs < F) {
+    if (fs >= sb.x && fs < sb.y) {
       const float* xp = x + ((size_t)bi * F + fs) * C + c0;
 #pragma unroll
       for (int q = 0; q < CPL / 4; ++q) {
@@ -100,10 +105,12 @@ __global__ __launch_bounds__(256) void dwconv_ln_k(const float* __restrict__ x, 
 // phase) and keeps the 7 rows of its current frame in a register ring of 9 (two rows requested ahead): every row is loaded once per
 // wave that needs it (+ 6 / RUN halo), the depthwise weights (56 registers) and the bias once per wave instead of once per frame.
 // Same arithmetic per frame as dwconv_ln_k: acc = bias, taps 0..6 in order (a tap outside [0, F) multiplies a zero row).
-template <int CPL, bool F16>
+// SEG: a run may cross segment boundaries; each (output frame, tap) pair is masked against the output frame's segment (see dwconv_ln_k).
+template <int CPL, bool F16, bool SEG = false>
 __global__ __launch_bounds__(256) void dwconv_ln_run_k(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                        const float* __restrict__ lw, const float* __restrict__ lb, float eps, int dil,
-                                                       float* __restrict__ y, int F, int B, int runs, uint16_t* __restrict__ yp) {
+                                                       float* __restrict__ y, int F, int B, int runs, uint16_t* __restrict__ yp,
+                                                       const int2* __restrict__ seg) {
   constexpr int C = 64 * CPL;
   constexpr int RUN = 36, NSL = 9;   // RUN % NSL == 0: the ring indices below are compile-time constants
   const int per = gridDim.x >> 3;    // XCD-aware order: one contiguous range of (utterance, run, phase) per XCD (see dwconv_ln_k)
@@ -148,14 +155,18 @@ __global__ __launch_bounds__(256) void dwconv_ln_run_k(const float* __restrict__
       const int t = t0 + u, f = f0 + dil * t;
       if (f >= F) return;                     // wave-uniform
       ldrow(s[(u + NSL - 1) % NSL], t + 5);   // row t + 5 = k 8 of this frame
+      const int row = bi * F + f;
+      const int2 sb = SEG ? seg[row] : make_int2(0, F);   // wave-uniform
       float acc[CPL];
 #pragma unroll
       for (int i = 0; i < CPL; ++i) acc[i] = bias[i];
 #pragma unroll
-      for (int j = 0; j < 7; ++j)
+      for (int j = 0; j < 7; ++j) {
+        const int r = f + (j - 3) * dil;
+        const bool in = !SEG || (r >= sb.x && r < sb.y);    // rows outside [0, F) are zeros in the ring already
 #pragma unroll
-        for (int i = 0; i < CPL; ++i) acc[i] = fmaf(wt[j][i], s[(u + j) % NSL][i], acc[i]);
-      const int row = bi * F + f;
+        for (int i = 0; i < CPL; ++i) acc[i] = fmaf(wt[j][i], in ? s[(u + j) % NSL][i] : 0.f, acc[i]);
+      }
       ln_finish<CPL, F16>(acc, lw, lb, eps, c0, y + (size_t)row * C, yp, row);
     }
   }
@@ -187,10 +198,10 @@ __device__ __forceinline__ void ln_pack(float* y, const float* __restrict__ lw, 
   }
 }
 
-template <bool F16, int DIL>
+template <bool F16, int DIL, bool SEG = false>
 __global__ __launch_bounds__(256) void dwconv_ln_seq_k(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                        const float* __restrict__ lw, const float* __restrict__ lb, float eps, int F, int B, int runs,
-                                                       uint16_t* __restrict__ yp) {
+                                                       uint16_t* __restrict__ yp, const int2* __restrict__ seg) {
   constexpr int CPL = 8, C = 512, KB16 = C / 16;
   constexpr int NSL = DIL == 1 ? 9 : 16, RUN = DIL == 1 ? 36 : 48;   // ring slots (6 DIL + 1 taps' span + 2 | 3 rows ahead); RUN % NSL == 0, RUN % 4 == 0
   constexpr int NP = F16 ? 1 : 2, RS = 65;                           // planes; LDS row stride in 16-byte units (65: the transposed reads hit distinct banks)
@@ -256,13 +267,17 @@ __global__ __launch_bounds__(256) void dwconv_ln_seq_k(const float* __restrict__
         return;
       }
       ldrow(s[(u + NSL - 1) % NSL], t - 3 * DIL + NSL - 1);
+      const int2 sb = SEG ? seg[bi * F + f] : make_int2(0, F);   // wave-uniform (see dwconv_ln_run_k)
       float acc[CPL];
 #pragma unroll
       for (int i = 0; i < CPL; ++i) acc[i] = bias[i];
 #pragma unroll
-      for (int j = 0; j < 7; ++j)
+      for (int j = 0; j < 7; ++j) {
+        const int r = f + (j - 3) * DIL;
+        const bool in = !SEG || (r >= sb.x && r < sb.y);
 #pragma unroll
-        for (int i = 0; i < CPL; ++i) acc[i] = fmaf(wt[j][i], s[(u + j * DIL) % NSL][i], acc[i]);
+        for (int i = 0; i < CPL; ++i) acc[i] = fmaf(wt[j][i], in ? s[(u + j * DIL) % NSL][i] : 0.f, acc[i]);
+      }
       uint4 hi, lo;
       ln_pack<CPL, F16>(acc, lw, lb, eps, c0, hi, lo);
       stg[wave][0][t & 3][lane] = hi;
@@ -272,13 +287,19 @@ __global__ __launch_bounds__(256) void dwconv_ln_seq_k(const float* __restrict__
   }
 }
 
-hipError_t launch_dwconv_ln(const float* x, const float* w, const float* b, const float* ln_w, const float* ln_b, float eps, int dil,
-                            float* y, int B, int F, int C, hipStream_t st, uint16_t* yp, int plane_f16) {
+static int dwconv_run_min() {
+  static int run_min = -1;   // CTTS_DWCONV_RUN_MIN_ROWS: frames from which the sliding-window kernel is used (0 = never); below it one wave per frame
+  if (run_min < 0) { const char* e = getenv("CTTS_DWCONV_RUN_MIN_ROWS"); run_min = e ? atoi(e) : 12288; }
+  return run_min;
+}
+
+template <bool SEG>
+static hipError_t dwconv_dispatch(const float* x, const float* w, const float* b, const float* ln_w, const float* ln_b, float eps, int dil,
+                                  float* y, int B, int F, int C, hipStream_t st, uint16_t* yp, int plane_f16, const int2* seg) {
   const int rows = B * F;
   const int nblk = ((rows + 3) / 4 + 7) / 8 * 8;   // multiple of 8: one contiguous run of frames per XCD (see the kernel)
   if (yp != nullptr && C != 512) return hipErrorInvalidValue;
-  static int run_min = -1;   // CTTS_DWCONV_RUN_MIN_ROWS: frames from which the sliding-window kernel is used (0 = never); below it one wave per frame
-  if (run_min < 0) { const char* e = getenv("CTTS_DWCONV_RUN_MIN_ROWS"); run_min = e ? atoi(e) : 12288; }
+  const int run_min = dwconv_run_min();
   if (C == 512 && run_min > 0 && rows >= run_min && dil >= 1 && dil <= 4) {
     // CTTS_DWCONV_SEQ (A/B, the bit-identity test; read at every launch): 0 = dwconv_ln_run_k's isolated 16-byte plane stores everywhere; 1 (default) =
     // dwconv_ln_seq_k at dilation 1 (Vocos: 415 -> 141 MB written, 148 -> 92 us per launch at 65,536 frames); 2 = also at dilation 2 (DVAE: 231 -> 169 MB
@@ -289,26 +310,33 @@ hipError_t launch_dwconv_ln(const float* x, const float* w, const float* b, cons
       const int run = dil == 1 ? 36 : 48, nruns = (F + run - 1) / run;
       const int nbs = ((B * nruns + 3) / 4 + 7) / 8 * 8;
       if (dil == 1) {
-        if (plane_f16) hipLaunchKernelGGL((dwconv_ln_seq_k<true, 1>), dim3(nbs), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, F, B, nruns, yp);
-        else hipLaunchKernelGGL((dwconv_ln_seq_k<false, 1>), dim3(nbs), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, F, B, nruns, yp);
+        if (plane_f16) hipLaunchKernelGGL((dwconv_ln_seq_k<true, 1, SEG>), dim3(nbs), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, F, B, nruns, yp, seg);
+        else hipLaunchKernelGGL((dwconv_ln_seq_k<false, 1, SEG>), dim3(nbs), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, F, B, nruns, yp, seg);
       } else {
-        if (plane_f16) hipLaunchKernelGGL((dwconv_ln_seq_k<true, 2>), dim3(nbs), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, F, B, nruns, yp);
-        else hipLaunchKernelGGL((dwconv_ln_seq_k<false, 2>), dim3(nbs), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, F, B, nruns, yp);
+        if (plane_f16) hipLaunchKernelGGL((dwconv_ln_seq_k<true, 2, SEG>), dim3(nbs), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, F, B, nruns, yp, seg);
+        else hipLaunchKernelGGL((dwconv_ln_seq_k<false, 2, SEG>), dim3(nbs), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, F, B, nruns, yp, seg);
       }
       return hipGetLastError();
     }
     const int runs = (F + 36 * dil - 1) / (36 * dil);
     const int waves = B * runs * dil;
     const int nb = ((waves + 3) / 4 + 7) / 8 * 8;
-    if (yp != nullptr && plane_f16) hipLaunchKernelGGL((dwconv_ln_run_k<8, true>), dim3(nb), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, B, runs, yp);
-    else hipLaunchKernelGGL((dwconv_ln_run_k<8, false>), dim3(nb), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, B, runs, yp);
+    if (yp != nullptr && plane_f16) hipLaunchKernelGGL((dwconv_ln_run_k<8, true, SEG>), dim3(nb), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, B, runs, yp, seg);
+    else hipLaunchKernelGGL((dwconv_ln_run_k<8, false, SEG>), dim3(nb), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, B, runs, yp, seg);
     return hipGetLastError();
   }
-  if (C == 512 && yp != nullptr && plane_f16) hipLaunchKernelGGL((dwconv_ln_k<8, true>), dim3(nblk), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, rows, yp);
-  else if (C == 512) hipLaunchKernelGGL(dwconv_ln_k<8>, dim3(nblk), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, rows, yp);
-  else if (C == 256) hipLaunchKernelGGL(dwconv_ln_k<4>, dim3(nblk), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, rows, (uint16_t*)nullptr);
+  if (C == 512 && yp != nullptr && plane_f16) hipLaunchKernelGGL((dwconv_ln_k<8, true, SEG>), dim3(nblk), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, rows, yp, seg);
+  else if (C == 512) hipLaunchKernelGGL((dwconv_ln_k<8, false, SEG>), dim3(nblk), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, rows, yp, seg);
+  else if (C == 256 && !SEG) hipLaunchKernelGGL(dwconv_ln_k<4>, dim3(nblk), dim3(256), 0, st, x, w, b, ln_w, ln_b, eps, dil, y, F, rows, (uint16_t*)nullptr, seg);
   else return hipErrorInvalidValue;
   return hipGetLastError();
+}
+
+hipError_t launch_dwconv_ln(const float* x, const float* w, const float* b, const float* ln_w, const float* ln_b, float eps, int dil,
+                            float* y, int B, int F, int C, hipStream_t st, uint16_t* yp, int plane_f16, const int2* seg) {
+  if (seg == nullptr) return dwconv_dispatch<false>(x, w, b, ln_w, ln_b, eps, dil, y, B, F, C, st, yp, plane_f16, nullptr);
+  if (B != 1 || C != 512) return hipErrorInvalidValue;   // packed segments: one sequence of frames, the decoder's width
+  return dwconv_dispatch<true>(x, w, b, ln_w, ln_b, eps, dil, y, B, F, C, st, yp, plane_f16, seg);
 }
 
 __global__ __launch_bounds__(256) void layernorm_k(const float* __restrict__ x, const float* __restrict__ lw, const float* __restrict__ lb,
@@ -374,23 +402,39 @@ __global__ __launch_bounds__(256) void istft_frames_k(const float* __restrict__ 
   for (int n = t; n < NFFT; n += 256) fp[n] = re[n] * (1.0f / NFFT) * window[n];
 }
 
-// overlap-add + envelope division + center trim:  wav[b, n], n in [0, HOP*(F-1))
-__global__ __launch_bounds__(256) void istft_ola_k(const float* __restrict__ frames, const float* __restrict__ window,
-                                                   float* __restrict__ wav, int F, int wlen) {
-  const int b = blockIdx.y;
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= wlen) return;
+// overlap-add + envelope division + center trim of one utterance's F frames (fr: its first frame):  sample n in [0, HOP*(F-1))
+__device__ __forceinline__ float istft_ola_one(const float* __restrict__ fr, const float* __restrict__ window, int F, int n) {
   const int tt = n + NFFT / 2;
   int f_hi = tt / HOP; if (f_hi > F - 1) f_hi = F - 1;
   int f_lo = (tt - (NFFT - 1) + HOP - 1) / HOP; if (f_lo < 0) f_lo = 0;
   float y = 0.f, env = 0.f;
   for (int f = f_lo; f <= f_hi; ++f) {
     const int o = tt - f * HOP;
-    y += frames[((size_t)b * F + f) * NFFT + o];
+    y += fr[(size_t)f * NFFT + o];
     const float w = window[o];
     env += w * w;
   }
-  wav[(size_t)b * wlen + n] = y / env;
+  return y / env;
+}
+
+//  wav[b, n], n in [0, HOP*(F-1))
+__global__ __launch_bounds__(256) void istft_ola_k(const float* __restrict__ frames, const float* __restrict__ window,
+                                                   float* __restrict__ wav, int F, int wlen) {
+  const int b = blockIdx.y;
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= wlen) return;
+  wav[(size_t)b * wlen + n] = istft_ola_one(frames + (size_t)b * F * NFFT, window, F, n);
+}
+
+// packed segments (blockIdx.y = segment): each has its own frame count, output offset, centre trim and window envelope -- the envelope
+// counts only the segment's own frames, as torch.istft does on the segment alone
+__global__ __launch_bounds__(256) void istft_ola_seg_k(const float* __restrict__ frames, const float* __restrict__ window,
+                                                       float* __restrict__ wav, const int32_t* __restrict__ tok_off) {
+  const int i = blockIdx.y;
+  const int f0 = 2 * tok_off[i], F = 2 * tok_off[i + 1] - f0;
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= HOP * (F - 1)) return;
+  wav[(size_t)HOP * (f0 - i) + n] = istft_ola_one(frames + (size_t)f0 * NFFT, window, F, n);
 }
 
 hipError_t launch_istft(const float* head, const float* window, const float* twiddle, float* frames, float* wav, int B, int F,
@@ -402,6 +446,26 @@ hipError_t launch_istft(const float* head, const float* window, const float* twi
   return hipGetLastError();
 }
 
+
+hipError_t launch_istft_ragged(const float* head, const float* window, const float* twiddle, float* frames, float* wav, const int32_t* tok_off,
+                               int n_seg, int F_total, int F_max, hipStream_t st) {
+  if (n_seg < 1 || F_max < 2 || F_total < 2 * n_seg) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(istft_frames_k, dim3(F_total), dim3(256), 0, st, head, window, (const float2*)twiddle, frames);
+  hipLaunchKernelGGL(istft_ola_seg_k, dim3((HOP * (F_max - 1) + 255) / 256, n_seg), dim3(256), 0, st, frames, window, wav, tok_off);
+  return hipGetLastError();
+}
+
+// one workgroup per segment: seg[f] = its mel frames [2 tok_off[i], 2 tok_off[i+1]) for each of them
+__global__ __launch_bounds__(256) void segment_table_k(const int32_t* __restrict__ tok_off, int2* __restrict__ seg) {
+  const int i = blockIdx.x;
+  const int lo = 2 * tok_off[i], hi = 2 * tok_off[i + 1];
+  for (int f = lo + (int)threadIdx.x; f < hi; f += 256) seg[f] = make_int2(lo, hi);
+}
+hipError_t launch_segment_table(const int32_t* tok_off, int n_seg, int2* seg, hipStream_t st) {
+  if (n_seg < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(segment_table_k, dim3(n_seg), dim3(256), 0, st, tok_off, seg);
+  return hipGetLastError();
+}
 
 // ------------------------------------------------------------------------------------------------
 // Shader copy: n bytes (a multiple of 16, both pointers 16-byte aligned) src -> dst.  The destination may be PINNED HOST memory (it
@@ -430,9 +494,14 @@ hipError_t launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t s
 // silence strip of Chat.infer can run on the int16 samples -- the waveform then leaves the GPU at 2 bytes + 1 bit per sample, not 4 bytes.
 // An all-zero input gives zeros (the reference divides by zero there).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void absmax_rows_k(const float* __restrict__ x, long long n, long long ld, int per_row, unsigned* __restrict__ peak) {
+// SEG (packed segments, blockIdx.y = segment): samples [off[i], off[i+1]) are segment i, one peak each (per_row), its PCM at the same
+// offsets and its keep mask from byte sum_{j<i} ceil(n_j / 8) on; n is then unused
+template <bool SEG = false>
+__global__ __launch_bounds__(256) void absmax_rows_k(const float* __restrict__ x, long long n, long long ld, int per_row, unsigned* __restrict__ peak,
+                                                     const long long* __restrict__ off) {
   const int row = blockIdx.y;
-  const float* xr = x + (size_t)row * ld;
+  if constexpr (SEG) n = off[row + 1] - off[row];
+  const float* xr = x + (SEG ? (size_t)off[row] : (size_t)row * ld);
   unsigned m = 0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
     m = max(m, __float_as_uint(xr[i]) & 0x7fffffffu);   // |x| as an unsigned: the IEEE order of non-negative floats
@@ -440,17 +509,24 @@ __global__ __launch_bounds__(256) void absmax_rows_k(const float* __restrict__ x
   for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
   if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(peak + (per_row ? row : 0), m);
 }
+template <bool SEG = false>
 __global__ __launch_bounds__(256) void pcm16_k(const float* __restrict__ x, long long n, long long ld, int per_row, int product,
                                                const unsigned* __restrict__ peak, float keep_thr, int16_t* __restrict__ out,
-                                               uint8_t* __restrict__ keep) {
+                                               uint8_t* __restrict__ keep, const long long* __restrict__ off) {
   const int row = blockIdx.y;
+  long long kb = (long long)row * ((n + 7) >> 3);        // this row's first mask byte
+  if constexpr (SEG) {
+    n = off[row + 1] - off[row];
+    kb = 0;
+    for (int j = 0; j < row; ++j) kb += (off[j + 1] - off[j] + 7) >> 3;   // wave-uniform: scalar loads
+  }
   const float pk = __uint_as_float(peak[per_row ? row : 0]);
   // a non-finite sample makes the peak Inf / NaN (the bit pattern of |x| orders above every finite value): the cast would be undefined
   // behaviour -- such a row gets scale 0, i.e. zeros (the reference's numpy path yields garbage there)
   const long long c = (pk < 3.0e38f) ? (long long)ceilf(pk) : 0;
   const long long am = c > 0 ? (32767ll * 32768ll) / (c * 32768ll) : 0;
-  const float* xr = x + (size_t)row * ld;
-  int16_t* orow = out + (size_t)row * n;
+  const float* xr = x + (SEG ? (size_t)off[row] : (size_t)row * ld);
+  int16_t* orow = out + (SEG ? (size_t)off[row] : (size_t)row * n);
   const long long nb = (n + 7) >> 3;                     // groups of 8 samples = 16 bytes of PCM = one byte of mask
   for (long long gi = (long long)blockIdx.x * 256 + threadIdx.x; gi < nb; gi += (long long)gridDim.x * 256) {
     unsigned bits = 0;
@@ -464,7 +540,7 @@ __global__ __launch_bounds__(256) void pcm16_k(const float* __restrict__ x, long
         if (fabsf(v) > keep_thr) bits |= 0x80u >> e;      // np.packbits order: first sample in the top bit
       }
     }
-    if (keep != nullptr) keep[(size_t)row * nb + gi] = (uint8_t)bits;
+    if (keep != nullptr) keep[(size_t)kb + gi] = (uint8_t)bits;
   }
 }
 hipError_t launch_float_to_int16(const float* wav, long long n, long long ld, int rows, int per_row, int product, float keep_thr,
@@ -474,9 +550,23 @@ hipError_t launch_float_to_int16(const float* wav, long long n, long long ld, in
   if (e != hipSuccess) return e;
   const long long per_blk = 256ll * 16;
   const unsigned gx = (unsigned)min((n + per_blk - 1) / per_blk, 1024ll);
-  hipLaunchKernelGGL(absmax_rows_k, dim3(gx, rows), dim3(256), 0, st, wav, n, ld, per_row, peak);
+  hipLaunchKernelGGL(absmax_rows_k<false>, dim3(gx, rows), dim3(256), 0, st, wav, n, ld, per_row, peak, (const long long*)nullptr);
   const long long nb = (n + 7) >> 3;
   const unsigned gx2 = (unsigned)min((nb + 255) / 256, 2048ll);
-  hipLaunchKernelGGL(pcm16_k, dim3(gx2, rows), dim3(256), 0, st, wav, n, ld, per_row, product, (const unsigned*)peak, keep_thr, pcm, keep);
+  hipLaunchKernelGGL(pcm16_k<false>, dim3(gx2, rows), dim3(256), 0, st, wav, n, ld, per_row, product, (const unsigned*)peak, keep_thr, pcm, keep,
+                     (const long long*)nullptr);
+  return hipGetLastError();
+}
+hipError_t launch_float_to_int16_ragged(const float* wav, const long long* off, int n_seg, long long n_max, int product, float keep_thr,
+                                        unsigned* peak, int16_t* pcm, uint8_t* keep, hipStream_t st) {
+  if (n_seg <= 0 || n_max <= 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(peak, 0, sizeof(unsigned) * n_seg, st);
+  if (e != hipSuccess) return e;
+  const long long per_blk = 256ll * 16;
+  const unsigned gx = (unsigned)min((n_max + per_blk - 1) / per_blk, 1024ll);
+  hipLaunchKernelGGL(absmax_rows_k<true>, dim3(gx, n_seg), dim3(256), 0, st, wav, 0ll, 0ll, 1, peak, off);
+  const long long nb = (n_max + 7) >> 3;
+  const unsigned gx2 = (unsigned)min((nb + 255) / 256, 2048ll);
+  hipLaunchKernelGGL(pcm16_k<true>, dim3(gx2, n_seg), dim3(256), 0, st, wav, 0ll, 0ll, 1, product, (const unsigned*)peak, keep_thr, pcm, keep, off);
   return hipGetLastError();
 }

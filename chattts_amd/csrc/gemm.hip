@@ -189,7 +189,9 @@ hipError_t launch_gemm_skinny(const GemmArgs& a, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // tiled (f32 weights)
 // ------------------------------------------------------------------------------------------------
-template <int EPI>
+// SEG (ragged conv, a.seg != null): A row m gathers rows [seg[m].x, seg[m].y) of one packed sequence only; the plain instantiations
+// compile exactly as before
+template <int EPI, bool SEG = false>
 __global__ __launch_bounds__(256) void gemm_tiled_f32_k(GemmArgs a) {
   constexpr int BM = 64, BN = 64, BK = 32, LD = BK + 1;  // +1 pad: conflict-free ds_read_b32 of MFMA fragments
   __shared__ float As[BM][LD];
@@ -205,11 +207,13 @@ __global__ __launch_bounds__(256) void gemm_tiled_f32_k(GemmArgs a) {
   // per-thread gather bases for its two A rows (rows lr and lr+32)
   int ab[2], af[2];
   bool aval[2];
+  int2 sg[2];
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     const int m = m0 + lr + 32 * p;
     aval[p] = m < M;
-    if (a.taps > 1) { ab[p] = m / a.frames; af[p] = m - ab[p] * a.frames; } else { ab[p] = 0; af[p] = m; }
+    if constexpr (SEG) { ab[p] = 0; af[p] = m; sg[p] = aval[p] ? a.seg[m] : make_int2(0, 0); }
+    else if (a.taps > 1) { ab[p] = m / a.frames; af[p] = m - ab[p] * a.frames; } else { ab[p] = 0; af[p] = m; }
   }
 
   f32x16 acc;
@@ -225,7 +229,8 @@ __global__ __launch_bounds__(256) void gemm_tiled_f32_k(GemmArgs a) {
         if (a.taps > 1) {
           const int tap = k / a.cin, c = k - tap * a.cin;
           const int fs = af[p] + (tap - a.pad) * a.dil;
-          if (fs >= 0 && fs < a.frames) v = *reinterpret_cast<const float4*>(a.A + ((size_t)ab[p] * a.frames + fs) * a.lda + c);
+          if constexpr (SEG) { if (fs >= sg[p].x && fs < sg[p].y) v = *reinterpret_cast<const float4*>(a.A + (size_t)fs * a.lda + c); }
+          else if (fs >= 0 && fs < a.frames) v = *reinterpret_cast<const float4*>(a.A + ((size_t)ab[p] * a.frames + fs) * a.lda + c);
         } else {
           v = *reinterpret_cast<const float4*>(a.A + (size_t)af[p] * a.lda + k);
         }
@@ -285,6 +290,16 @@ hipError_t launch_gemm_tiled(const GemmArgs& a, hipStream_t st) {
   if (a.wt != WT_F32 || a.K % 4 != 0 || a.lda % 4 != 0 || a.norm_w != nullptr) return hipErrorInvalidValue;
   if (a.taps > 1 && (a.cin % 4 != 0 || a.K != a.taps * a.cin)) return hipErrorInvalidValue;
   dim3 grid((a.N + 63) / 64, (a.M + 63) / 64), block(256);
+  if (a.seg != nullptr && a.taps > 1) {   // ragged conv: the epilogues of the codec's k3 / k7 convolutions
+    if (a.frames != a.M) return hipErrorInvalidValue;
+    switch (a.epi) {
+      case EPI_BIAS: CTTS_LAUNCH((gemm_tiled_f32_k<EPI_BIAS, true>), grid, block, st, a); break;
+      case EPI_BIAS_GELU: CTTS_LAUNCH((gemm_tiled_f32_k<EPI_BIAS_GELU, true>), grid, block, st, a); break;
+      case EPI_SCALE: CTTS_LAUNCH((gemm_tiled_f32_k<EPI_SCALE, true>), grid, block, st, a); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (a.epi) {
     case EPI_STORE: CTTS_LAUNCH((gemm_tiled_f32_k<EPI_STORE>), grid, block, st, a); break;
     case EPI_RES: CTTS_LAUNCH((gemm_tiled_f32_k<EPI_RES>), grid, block, st, a); break;
@@ -591,7 +606,8 @@ hipError_t launch_gemm_fast(const FastGemmArgs& a_in, hipStream_t st) {
 // NBUF = 2 (256x256 tile only: 2 x 80 KB = the CU's whole 160 KB LDS): the staged tile k+1 goes to the other LDS buffer
 // while tile k is multiplied, so a k-step has ONE barrier and the waves drift apart -- one wave of a SIMD converts /
 // writes LDS / sits blocked on its load issue while the other one feeds the MFMA pipe.
-template <int EPI, int WM, int WN, int MBLK, int NBLK, int NBUF = 1>
+// SEG: ragged conv gather, as gemm_tiled_f32_k
+template <int EPI, int WM, int WN, int MBLK, int NBLK, int NBUF = 1, bool SEG = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_tiled_bf16x3_k(GemmArgs a) {
   constexpr int NT = 64 * WM * WN;
   constexpr int BM = WM * MBLK * 32, BN = WN * NBLK * 32, BK = 32, LD = 40;  // LD: 80-byte rows -> conflict-free ds_read_b128
@@ -613,11 +629,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_til
   const int ar = tid >> 3, ak = (tid & 7) * 4;
   int ab[PA], af[PA];
   bool aval[PA];
+  int2 sg[PA];
 #pragma unroll
   for (int p = 0; p < PA; ++p) {
     const int m = m0 + ar + (NT / 8) * p;
     aval[p] = m < M;
-    if (a.taps > 1) { ab[p] = m / a.frames; af[p] = m - ab[p] * a.frames; } else { ab[p] = 0; af[p] = m; }
+    if constexpr (SEG) { ab[p] = 0; af[p] = m; sg[p] = aval[p] ? a.seg[m] : make_int2(0, 0); }
+    else if (a.taps > 1) { ab[p] = m / a.frames; af[p] = m - ab[p] * a.frames; } else { ab[p] = 0; af[p] = m; }
   }
   const int wr = tid >> 3, wk = (tid & 3) * 8, wlo = (tid >> 2) & 1;   // lanes 0-3 of a row: hi chunks, lanes 4-7: lo chunks
 
@@ -640,7 +658,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_til
       if (a.taps > 1) {                                                                                     \
         const int tap = k / a.cin, c = k - tap * a.cin;                                                     \
         const int fs = af[p_] + (tap - a.pad) * a.dil;                                                      \
-        if (fs >= 0 && fs < a.frames)                                                                       \
+        if constexpr (SEG) {                                                                                \
+          if (fs >= sg[p_].x && fs < sg[p_].y) v = *reinterpret_cast<const float4*>(a.A + (size_t)fs * a.lda + c); \
+        } else if (fs >= 0 && fs < a.frames)                                                                \
           v = *reinterpret_cast<const float4*>(a.A + ((size_t)ab[p_] * a.frames + fs) * a.lda + c);         \
       } else {                                                                                              \
         v = *reinterpret_cast<const float4*>(a.A + (size_t)af[p_] * a.lda + k);                             \
@@ -789,6 +809,16 @@ static hipError_t x3_dispatch(const GemmArgs& a, hipStream_t st) {
   constexpr int BM = WM * MBLK * 32, BN = WN * NBLK * 32;
   const int tiles = ((a.N + BN - 1) / BN) * ((a.M + BM - 1) / BM);
   dim3 grid(((tiles + 7) / 8) * 8), block(64 * WM * WN);  // 1-D grid, remapped XCD-aware inside the kernel
+  if (a.seg != nullptr && a.taps > 1) {   // ragged conv: the epilogues of the codec's k3 / k7 convolutions
+    if (a.frames != a.M) return hipErrorInvalidValue;
+    switch (a.epi) {
+      case EPI_BIAS: CTTS_LAUNCH((gemm_tiled_bf16x3_k<EPI_BIAS, WM, WN, MBLK, NBLK, NBUF, true>), grid, block, st, a); break;
+      case EPI_BIAS_GELU: CTTS_LAUNCH((gemm_tiled_bf16x3_k<EPI_BIAS_GELU, WM, WN, MBLK, NBLK, NBUF, true>), grid, block, st, a); break;
+      case EPI_SCALE: CTTS_LAUNCH((gemm_tiled_bf16x3_k<EPI_SCALE, WM, WN, MBLK, NBLK, NBUF, true>), grid, block, st, a); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (a.epi) {
     case EPI_STORE: CTTS_LAUNCH((gemm_tiled_bf16x3_k<EPI_STORE, WM, WN, MBLK, NBLK, NBUF>), grid, block, st, a); break;
     case EPI_RES: CTTS_LAUNCH((gemm_tiled_bf16x3_k<EPI_RES, WM, WN, MBLK, NBLK, NBUF>), grid, block, st, a); break;

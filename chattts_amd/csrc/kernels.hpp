@@ -80,6 +80,9 @@ struct GemmArgs {
   // X[b, f + (tap - pad)*dil, c] (zero outside [0,F)); taps == 1 -> plain GEMM.
   int taps, cin, frames, pad, dil;
   long long* dbg;      // -DCTTS_X3_PROBE builds only: [n_workgroups][8] accumulated phase times of the split-bf16 tiles, or null
+  // ragged conv (tiled kernels, taps > 1): null = the [B, F] gather above; else frames = M (one packed sequence) and row m reads only rows
+  // [seg[m].x, seg[m].y) -- its own segment -- so every segment sees zero padding at its own edges (ctts_dvae_decode_ragged)
+  const int2* seg;
 };
 
 hipError_t launch_gemm_skinny(const GemmArgs& a, hipStream_t st);  // weight-streaming, M-tiles of <=64 rows
@@ -432,15 +435,27 @@ bool mlp_fused_pays(int M);
 // ---- codec kernels (channels-last [B, F, C]) ---------------------------------------------------
 // yp != null (C = 512 only): the output goes out as the two bf16 planes gemm_x3p_k reads (plane_f16 = 0) or as the one fp16 plane
 // gemm_h1p_k reads (plane_f16 = 1) instead of f32 rows
+// seg != null (B = 1, C = 512): frames are packed segments, seg[f] = [lo, hi) of frame f's own segment; a tap outside it reads zero
 hipError_t launch_dwconv_ln(const float* x, const float* w /*[C,7]*/, const float* b, const float* ln_w, const float* ln_b,
-                            float eps, int dil, float* y, int B, int F, int C, hipStream_t st, uint16_t* yp = nullptr, int plane_f16 = 0);
+                            float eps, int dil, float* y, int B, int F, int C, hipStream_t st, uint16_t* yp = nullptr, int plane_f16 = 0,
+                            const int2* seg = nullptr);
 hipError_t launch_layernorm(const float* x, const float* w, const float* b, float eps, float* y, int rows, int C, hipStream_t st);
 hipError_t launch_istft(const float* head /*[B,F,1026]*/, const float* window /*[1024]*/, const float* twiddle /*[512,2]*/,
                         float* frames /*[B,F,1024] scratch*/, float* wav /*[B,256(F-1)]*/, int B, int F, hipStream_t st);
+// packed segments: tok_off [n_seg + 1] token offsets (device), segment i = mel frames [2 tok_off[i], 2 tok_off[i+1]); wav = the segments'
+// waveforms back to back, segment i at 256 (2 tok_off[i] - i) -- each one exactly what launch_istft gives for it alone.  F_total / F_max size the grids.
+hipError_t launch_istft_ragged(const float* head, const float* window, const float* twiddle, float* frames, float* wav, const int32_t* tok_off,
+                               int n_seg, int F_total, int F_max, hipStream_t st);
+// per-frame segment bounds of packed segments: seg[f] = [2 tok_off[i], 2 tok_off[i+1]) for every mel frame f of segment i
+hipError_t launch_segment_table(const int32_t* tok_off, int n_seg, int2* seg, hipStream_t st);
 
 // float32 waveform [rows][ld] (n samples per row) -> int16 PCM [rows][n] (+ optional keep mask [rows][ceil(n/8)]): tools/audio/np.py:7-11
 hipError_t launch_float_to_int16(const float* wav, long long n, long long ld, int rows, int per_row, int product, float keep_thr,
                                  unsigned* peak, int16_t* pcm, uint8_t* keep, hipStream_t st);
+// packed segments: samples [off[i], off[i+1]) are segment i (one peak each); pcm has the same layout, keep holds segment i's mask from byte
+// sum_{j<i} ceil(n_j / 8) on (every segment starts on a byte boundary).  n_max: the longest segment (grid size)
+hipError_t launch_float_to_int16_ragged(const float* wav, const long long* off, int n_seg, long long n_max, int product, float keep_thr,
+                                        unsigned* peak, int16_t* pcm, uint8_t* keep, hipStream_t st);
 hipError_t launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t st);   // shader copy (dst may be pinned host memory)
 
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------

@@ -1128,6 +1128,29 @@ class PendingWavs:
         return self._out
 
 
+def ragged_offsets(lens):
+    """packed-segment arithmetic of a ragged decode of rows with `lens` tokens: (token offsets int32, sample offsets int64 -- row i's
+    256 (2 T_i - 1) samples at [off[i], off[i+1]) --, keep-mask byte offsets int64 -- row i's ceil(n_i / 8) bytes, byte aligned)"""
+    lens = np.asarray(lens, dtype=np.int64)
+    tok = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=tok[1:])
+    off = VOCOS.hop * (2 * tok - np.arange(len(lens) + 1))
+    return tok.astype(np.int32), off, keep_offsets(off)
+
+
+def keep_offsets(off) -> np.ndarray:
+    """byte offsets of the per-segment keep masks of samples packed at `off` (every segment starts on a byte boundary)"""
+    off = np.asarray(off, dtype=np.int64)
+    k = np.zeros(len(off), np.int64)
+    np.cumsum((np.diff(off) + 7) // 8, out=k[1:])
+    return k
+
+
+def ragged_views(flat, off) -> list:
+    """the per-utterance pieces [off[i], off[i+1]) of a packed 1-D array or tensor (CodecEngine.decode_ragged): views, no copies"""
+    return [flat[int(off[i]): int(off[i + 1])] for i in range(len(off) - 1)]
+
+
 class CodecEngine:
     """DVAE decoder + Vocos on the device (channels-last)."""
 
@@ -1246,7 +1269,9 @@ class CodecEngine:
         fitted (tens of milliseconds each on this pool's hosts, profiles/r3e_c5_sched_probe.log).  Kernels of consecutive calls
         are stream-ordered on the caller's stream, so sharing the buffer needs no extra synchronisation as long as ONE stream
         drives the engine at a time (the documented contract of a handle, include/chattts_amd.h)."""
-        n = self.lib.ctts_codec_workspace_bytes(B, F)
+        return self._ws_bytes(self.lib.ctts_codec_workspace_bytes(B, F))
+
+    def _ws_bytes(self, n: int):
         cur = torch.cuda.current_stream(self.device)
         buf = getattr(self, "_ws_buf", None)
         if buf is None or buf.numel() < n or getattr(self, "_ws_stream", None) != cur.cuda_stream:
@@ -1299,6 +1324,68 @@ class CodecEngine:
                                                 1 if per_row else 0, {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), peak.data_ptr(), st),
                    "ctts_float_to_int16")
         return pcm, keep
+
+    # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
+    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False):
+        """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
+        packed frames (ctts_dvae_decode_ragged / ctts_vocos_decode_ragged): each utterance gets zero padding at its own edges in every
+        convolution, so its audio does not depend on what else is in the call -- unlike `decode_to_wavs`, whose zero-padded [B, Tmax]
+        batch (the reference's semantics, core.py:525-533) lets the padding's bias-driven activations into a shorter row's last ~51 tokens.
+        Returns (wav, off): ONE flat float32 device tensor with utterance i's 256 (2 T_i - 1) samples at [off[i], off[i+1]) (`off` a host
+        int64 array of len(rows) + 1; `ragged_views(wav, off)` gives the per-utterance views), plus the packed mel [sum 2 T_i, 100] as a
+        third element when `return_mel`.  With gemm "f32" and fewer than 12288 frames in all, every utterance is bit-identical to its B = 1
+        decode; otherwise within the tile-size tolerance of the mode."""
+        if len(rows) == 0:
+            raise ValueError("decode_ragged needs at least one row")
+        lens = [int(r.size(0)) for r in rows]
+        if min(lens) < 1:
+            raise ValueError("decode_ragged: every row needs at least one token")
+        for r in rows:
+            if r.dim() != 2 or r.size(1) != GPT.hidden:
+                raise ValueError("decode_ragged: rows must be [T, 768]")
+        tok, off, _ = ragged_offsets(lens)
+        T = int(tok[-1])
+        hid = torch.cat([r.to(device=self.device, dtype=torch.float32) for r in rows]) if len(rows) > 1 else \
+            rows[0].to(device=self.device, dtype=torch.float32).contiguous()
+        tok_d = torch.from_numpy(tok).to(self.device, non_blocking=False)
+        mel = torch.empty((2 * T, DVAE.n_mels), dtype=torch.float32, device=self.device)
+        wav = torch.empty((int(off[-1]),), dtype=torch.float32, device=self.device)
+        ws, n = self._ws_bytes(self.lib.ctts_codec_ragged_workspace_bytes(len(rows), T))
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        tok_h = tok.ctypes.data_as(C.c_void_p)
+        _lib.check(self.lib.ctts_dvae_decode_ragged(self.handle, hid.data_ptr(), tok_d.data_ptr(), tok_h, len(rows), mel.data_ptr(),
+                                                    ws.data_ptr(), n, st), "ctts_dvae_decode_ragged")
+        _lib.check(self.lib.ctts_vocos_decode_ragged(self.handle, mel.data_ptr(), tok_d.data_ptr(), tok_h, len(rows), wav.data_ptr(),
+                                                     ws.data_ptr(), n, st), "ctts_vocos_decode_ragged")
+        tok_d.record_stream(torch.cuda.current_stream(self.device))
+        return (wav, off, mel) if return_mel else (wav, off)
+
+    def float_to_int16_ragged(self, wav: torch.Tensor, off, product: str = "f64", keep_thr: Optional[float] = None, out=None):
+        """`float_to_int16` per utterance of a packed waveform (`decode_ragged`'s output): one peak per segment [off[i], off[i+1]), on the
+        device (ctts_float_to_int16_ragged).  Returns (pcm, keep, keep_off): pcm int16 in the waveform's layout; keep (keep_thr given) the
+        packed masks |x| > keep_thr (np.packbits order), segment i's from byte keep_off[i] on -- every segment starts on a byte boundary
+        -- else None.  `out`: optional (pcm, keep) device tensors to write into (e.g. views of one buffer, so that a single copy brings
+        both to the host).  Bit-exact against `audio.float_to_int16` of each segment."""
+        off = np.asarray(off, dtype=np.int64)
+        assert wav.dim() == 1 and wav.dtype == torch.float32 and wav.is_cuda and wav.numel() == int(off[-1])
+        n_seg = len(off) - 1
+        keep_off = keep_offsets(off)
+        if out is not None:
+            pcm, keep = out
+            assert pcm.dtype == torch.int16 and pcm.numel() == wav.numel() and (keep is None) == (keep_thr is None)
+            assert keep is None or (keep.dtype == torch.uint8 and keep.numel() == int(keep_off[-1]))
+        else:
+            pcm = torch.empty((wav.numel(),), dtype=torch.int16, device=wav.device)
+            keep = torch.empty((int(keep_off[-1]),), dtype=torch.uint8, device=wav.device) if keep_thr is not None else None
+        peak = torch.empty((n_seg,), dtype=torch.int32, device=wav.device)
+        off_d = torch.from_numpy(off).to(wav.device)
+        st = torch.cuda.current_stream(wav.device)
+        _lib.check(self.lib.ctts_float_to_int16_ragged(wav.data_ptr(), pcm.data_ptr(), _lib.ptr(keep), off_d.data_ptr(),
+                                                       off.ctypes.data_as(C.c_void_p), n_seg, {"f64": 0, "f32": 1}[product],
+                                                       float(keep_thr or 0.0), peak.data_ptr(), st.cuda_stream),
+                   "ctts_float_to_int16_ragged")
+        off_d.record_stream(st)
+        return pcm, keep, keep_off
 
     # receptive field of one output sample, in mel frames either side: ISTFT 4 overlapping frames; Vocos embed k7 + 8 ConvNeXt
     # blocks k7 = 27; DVAE conv_in k3 + k3, 12 ConvNeXt blocks k7 dilation 2, out_conv k3 = 75 (dvae.py:145-161, config.py:83-121)

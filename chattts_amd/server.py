@@ -78,12 +78,13 @@ def _have_av() -> bool:
 
 
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
-               batch_slots: Optional[int] = None, batcher=None):
+               batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
     reference's behaviour); N = non-streamed requests are batched in a pool of N slots (serving.SpeechBatcher; `batcher`: a ready one,
-    tests)."""
+    tests).  `ragged_decode` (batching only): the requests that finish together are decoded in one ragged pass, each as if alone,
+    instead of one decode per request (SpeechBatcher(ragged_decode=True))."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -98,7 +99,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     gpu_lock = threading.Lock()                      # batching: the worker's chunks / decodes vs the streamed path's chunks
     if batcher is None and batch_slots is not None:
         from .serving import SpeechBatcher
-        batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log)
+        batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode)
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher

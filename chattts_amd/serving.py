@@ -346,13 +346,14 @@ class SlotPool:
         self._snap_seq += 1
         return self._snap_seq - 1, blk, ev
 
-    def run(self, between=None) -> Iterator[Tuple[object, torch.Tensor, torch.Tensor]]:
+    def run(self, between=None, grouped: bool = False) -> Iterator:
         """Yields (request id, ids [n,4] int64, hiddens [n,768] float32) as requests complete, admitting queued
         requests into freed slots between decode chunks.  ONE chunk runs ahead: the next POLL steps are enqueued before the host
         looks at the previous chunk's flags, so the device never waits for the poll, the admission prefill or the result copies
         (a freed slot idles for at most two chunks instead of one).  A slot's entry only listens to snapshots enqueued after its
         admission -- an older one still shows the previous occupant's flag.  `between` (optional callable): called once per chunk, before
-        admission -- a server submits newly arrived requests there and lets other GPU users in (SpeechBatcher)."""
+        admission -- a server submits newly arrived requests there and lets other GPU users in (SpeechBatcher).  `grouped=True`: yields
+        instead ONE list of those triples per poll -- the requests that completed together (SpeechBatcher's ragged decode)."""
         pending: Deque = deque()
         ready: Deque = deque()      # (event behind the result copies, results) of the previous poll
         while self.queue or self.active or pending:
@@ -366,8 +367,7 @@ class SlotPool:
             while ready:          # the copies were enqueued in front of the chunk launched just now: the device stays busy while we wait
                 ev_out, outs = ready.popleft()
                 wait_event(ev_out)
-                for o in outs:
-                    yield o
+                yield from self._hand_out(outs, grouped)
             if len(pending) < 2 and self.active:
                 continue          # keep one chunk running ahead of the snapshot the host is about to read
             if not pending:
@@ -403,8 +403,14 @@ class SlotPool:
         while ready:
             ev_out, outs = ready.popleft()
             wait_event(ev_out)
-            for o in outs:
-                yield o
+            yield from self._hand_out(outs, grouped)
+
+    @staticmethod
+    def _hand_out(outs: list, grouped: bool):
+        if not grouped:
+            yield from outs
+        elif outs:
+            yield outs
 
 
 class SpeechBatcher:
@@ -412,17 +418,24 @@ class SpeechBatcher:
     batch_slots=N)`).  A single worker thread owns the pool and all GPU work of pooled requests: requests arrive through a thread-safe
     queue (`submit` returns a Future), the worker builds their prompts with the code `Chat.infer` uses (normalise -> `Chat.code_prompt`
     -> `Chat.prompt_embedding`), submits them between decode chunks, and decodes every finished request ALONE through the serial path's
-    decoder and silence strip (a ragged batch decode would let the DVAE conv biases of padded frames into the tails of shorter rows).
+    decoder and silence strip (a padded batch decode would let the DVAE conv biases of padded frames into the tails of shorter rows).
+    `ragged_decode=True`: the requests that finish in one poll are decoded TOGETHER instead, each still as if alone -- one ragged
+    decode (Chat.decode_to_pcm16(..., ragged=True)), one PCM16 pass and one device-to-host copy per poll.
     `gpu_lock` (a threading.Lock shared with the streamed path) is taken per decode chunk and per decode, never per request.
-    An error in one request fails that request's Future only.
+    An error in one request fails that request's Future only (an empty result -- step 0 drew EOS -- too).  `decode_calls` counts the
+    decodes, `decoded` the requests they served, `max_decode_group` the most requests one decode served.
 
     `make_pool` (tests: a fake) builds the pool; by default a per-request SlotPool on `chat.gpt` with the engine's generator mode,
     `cap` = the engine's position limit (the longest accepted prompt + max_new_token 2048 + slack), `hid_cap` 2048."""
 
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
-                 logger=None):
+                 logger=None, ragged_decode: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
+        self.ragged_decode = bool(ragged_decode)
+        self.decode_calls = 0        # decoder passes over finished requests
+        self.decoded = 0             # requests those passes served
+        self.max_decode_group = 0    # most requests one pass served
         self.log = logger or logging.getLogger("chattts_amd.serving")
         self._in: "queue.Queue" = queue.Queue()
         self._futs: dict = {}
@@ -453,7 +466,9 @@ class SpeechBatcher:
 
     def occupancy(self) -> dict:
         return {"slots": self.S, "active": len(getattr(self.pool, "active", {})), "queued": self._in.qsize() + len(getattr(self.pool, "queue", ())),
-                "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed}
+                "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed,
+                "ragged_decode": self.ragged_decode, "decode_calls": self.decode_calls, "decoded": self.decoded,
+                "max_decode_group": self.max_decode_group}
 
     def close(self):
         self._stop = True
@@ -507,8 +522,36 @@ class SpeechBatcher:
         from .audio import float_to_int16
         if hid.shape[0] == 0:
             raise RuntimeError("the engine returned no audio (the first token was EOS)")
+        self._count_decode(1)
         wav = self.chat.decode_to_wavs([hid])[0]
         return float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
+
+    def finish_group(self, hids: List[torch.Tensor]) -> list:
+        """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
+        returns for it) or the exception that fails it alone (an empty result)"""
+        out: list = [RuntimeError("the engine returned no audio (the first token was EOS)") if h.shape[0] == 0 else None for h in hids]
+        live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
+        if live:
+            self._count_decode(len(live))
+            for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True)):
+                out[i] = pcm
+        return out
+
+    def _count_decode(self, n: int) -> None:
+        self.decode_calls += 1
+        self.decoded += n
+        self.max_decode_group = max(self.max_decode_group, n)
+
+    def _deliver(self, rid, result) -> None:
+        fut = self._futs.pop(rid, None)
+        if fut is None:
+            return
+        if isinstance(result, BaseException):
+            self.failed += 1
+            fut.set_exception(result)
+        else:
+            self.completed += 1
+            fut.set_result(result)
 
     def _loop(self):
         while self._drain(block=True) or self.pool.queue:
@@ -516,10 +559,10 @@ class SpeechBatcher:
                 continue
             self.lock.acquire()
             try:
-                it = self.pool.run(between=self._between)
+                it = self.pool.run(between=self._between, grouped=True) if self.ragged_decode else self.pool.run(between=self._between)
                 while True:
                     try:
-                        rid, ids, hid = next(it)
+                        got = next(it)
                     except StopIteration:
                         break
                     except Exception as e:     # the pool itself failed: the requests in it fail, a fresh pool serves the next ones
@@ -531,15 +574,22 @@ class SpeechBatcher:
                             close()
                         self.pool = self._make_pool()
                         break
-                    fut = self._futs.pop(rid, None)
-                    if fut is None:
+                    if self.ragged_decode:
+                        group = [(rid, hid) for rid, _, hid in got if rid in self._futs]
+                        try:
+                            results = self.finish_group([h for _, h in group])
+                        except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
+                            results = [e] * len(group)
+                        for (rid, _), r in zip(group, results):
+                            self._deliver(rid, r)
+                        continue
+                    rid, ids, hid = got
+                    if rid not in self._futs:
                         continue
                     try:
                         pcm = self.finish(hid)
-                        self.completed += 1
-                        fut.set_result(pcm)
                     except Exception as e:
-                        self.failed += 1
-                        fut.set_exception(e)
+                        pcm = e
+                    self._deliver(rid, pcm)
             finally:
                 self.lock.release()

@@ -336,6 +336,24 @@ int ctts_copy_bytes(void* dst, const void* src, size_t bytes, void* stream);
 int ctts_dvae_decode(ctts_codec* c, const float* hid, float* mel, int32_t B, int32_t T, void* workspace, size_t ws_bytes, void* stream);
 int ctts_vocos_decode(ctts_codec* c, const float* mel, float* wav, int32_t B, int32_t F, void* workspace, size_t ws_bytes, void* stream);
 
+/* Ragged decode: n_seg utterances of T_i tokens packed back to back along the frame axis, each decoded exactly as if alone (zero padding
+ * at its own edges in every convolution; the padded [B, Tmax] entry points above let a short row's tail see the padding's activations).
+ *   hid [sum T_i, 768] -> mel [sum F_i, 100] (F_i = 2 T_i) -> wav [sum 256 (F_i - 1)], segment i's samples from 256 (2 tok_off[i] - i).
+ * tok_off_dev / tok_off_host: the same n_seg + 1 token offsets (int32, tok_off[0] = 0, strictly ascending -- empty segments are refused),
+ * on the device (read by the kernels) and on the host (grid sizes and the checks; the two must agree).  The workspace holds the
+ * per-frame segment bounds the kernels read.  Size-dependent kernel choices are keyed on the packed total.  With gemm_mode 0 and fewer
+ * than 12288 frames every segment is bit-identical to its B = 1 decode. */
+size_t ctts_codec_ragged_workspace_bytes(int32_t n_seg, int32_t total_tokens);   /* 0 when n_seg < 1 or total_tokens < n_seg */
+int ctts_dvae_decode_ragged(ctts_codec* c, const float* hid, const int32_t* tok_off_dev, const int32_t* tok_off_host, int32_t n_seg,
+                            float* mel, void* workspace, size_t ws_bytes, void* stream);
+int ctts_vocos_decode_ragged(ctts_codec* c, const float* mel, const int32_t* tok_off_dev, const int32_t* tok_off_host, int32_t n_seg,
+                             float* wav, void* workspace, size_t ws_bytes, void* stream);
+/* ctts_float_to_int16 over packed segments (one peak per segment): samples [off[i], off[i+1]) are segment i (int64 offsets, off[0] = 0,
+ * strictly ascending, on the device and the host); pcm has the same layout; keep_bits (NULL or sum_i ceil(n_i / 8) bytes) holds segment
+ * i's mask from byte sum_{j<i} ceil(n_j / 8) on -- every segment starts on a byte boundary; peak: [n_seg] uint32 device scratch. */
+int ctts_float_to_int16_ragged(const float* wav, int16_t* pcm, uint8_t* keep_bits, const int64_t* off_dev, const int64_t* off_host,
+                               int32_t n_seg, int32_t product, float keep_thr, uint32_t* peak, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Full DVAE (asset/DVAE.safetensors): audio -> 4 x T codes and codes -> mel through the GFSQ codebook.
  * Replaces `self.dvae(wav, "encode")` of `Chat.sample_audio_speaker` (ChatTTS/core.py:179-180 ->

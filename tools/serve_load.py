@@ -2,7 +2,10 @@
 batching (`create_app(..., batch_slots=S)`) and once without, plus the sampling kernel's cost in a per-request pool vs a plain pool.
 Prints one JSON line.  Not a bench.py leg.
 
-    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
+    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode]
+
+--ragged-decode: also the batched burst with `create_app(..., ragged_decode=True)` (the requests that finish in one poll decoded in one
+ragged pass) -- an A/B against the default batched burst (one decode per request), with both runs' decode-call counts.
 
 Synthetic weights (chattts_amd.weights) and the repository's test tokenizer: random weights do not stop on cue, so every request is capped
 at --max-new tokens (the endpoint's own max_new_token is 2048).  audio_s_per_s = seconds of returned audio / wall seconds of the burst."""
@@ -31,9 +34,9 @@ TEXTS = ["What is [uv_break]your favorite english food?", "Hello there, how are 
          "Good morning, and welcome to the show.", "Numbers like 42 and 7 are read out loud.", "A longer sentence, with a pause, and an ending."]
 
 
-def burst(chat, voices, n, batch_slots):
+def burst(chat, voices, n, batch_slots, ragged_decode=False, counts=False):
     from starlette.testclient import TestClient
-    app = server.create_app(chat, voices, batch_slots=batch_slots)
+    app = server.create_app(chat, voices, batch_slots=batch_slots, ragged_decode=ragged_decode)
     names = sorted(voices)
     lat, samples, codes = [0.0] * n, [0] * n, [0] * n
     with TestClient(app) as c:
@@ -59,9 +62,13 @@ def burst(chat, voices, n, batch_slots):
     if app.state.batcher is not None:
         app.state.batcher.close()
     audio = sum(samples) / server.SAMPLE_RATE
-    return dict(failed=sum(c != 200 for c in codes), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3), audio_s=round(audio, 2),
-                p50_s=round(float(np.percentile(lat, 50)), 3), p95_s=round(float(np.percentile(lat, 95)), 3),
-                max_coresident=(health.get("pool") or {}).get("max_coresident", 1))
+    out = dict(failed=sum(c != 200 for c in codes), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3), audio_s=round(audio, 2),
+               p50_s=round(float(np.percentile(lat, 50)), 3), p95_s=round(float(np.percentile(lat, 95)), 3),
+               max_coresident=(health.get("pool") or {}).get("max_coresident", 1))
+    if counts:       # the warm-up request is one of the decodes
+        pool = health.get("pool") or {}
+        out.update(decode_calls=pool.get("decode_calls"), max_decode_group=pool.get("max_decode_group"))
+    return out
 
 
 def sample_k_ms(eng, per_request, slots, steps=64):
@@ -90,6 +97,7 @@ def main():
     ap.add_argument("--slots", type=int, default=8)
     ap.add_argument("--max-new", type=int, default=256)
     ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--ragged-decode", action="store_true", help="A/B: also the batched burst with one ragged decode per poll")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     gold = os.path.join(ROOT, "tests", "golden")
@@ -102,11 +110,15 @@ def main():
     orig = chat.InferCodeParams
     chat.InferCodeParams = lambda **kw: orig(**{**kw, "max_new_token": a.max_new})
     serial = burst(chat, voices, a.n, None)
-    batched = burst(chat, voices, a.n, a.slots)
+    batched = burst(chat, voices, a.n, a.slots, counts=a.ragged_decode)
+    extra = {}
+    if a.ragged_decode:
+        r = burst(chat, voices, a.n, a.slots, ragged_decode=True, counts=True)
+        extra = dict(batched_ragged=r, ragged_speedup=round(r["audio_s_per_s"] / batched["audio_s_per_s"], 2))
     plain_ms = sample_k_ms(chat.gpt, False, a.slots)
     table_ms = sample_k_ms(chat.gpt, True, a.slots)
     print(json.dumps(dict(metric="serve_load", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, serial=serial, batched=batched,
-                          speedup=round(batched["audio_s_per_s"] / serial["audio_s_per_s"], 2),
+                          speedup=round(batched["audio_s_per_s"] / serial["audio_s_per_s"], 2), **extra,
                           sample_k_us=dict(plain_pool=round(plain_ms * 1e3, 2), per_request_pool=round(table_ms * 1e3, 2)))))
 
 
