@@ -8,10 +8,13 @@ waveforms the reference path ends with (core.py:508-510) -- BASELINE.json config
 the prompt token ids, the Exp(1) draws of the seeded CPU generator) are resident in HBM before the timed region starts; the prompt
 embedding gather (Embed.forward, a2) is inside it.
 
-One invocation measures BOTH numeric modes on the same workload: `value` is the bf16 perf mode BASELINE.json's configs
-name; `parity_mode` is the f32 mode whose token ids are bit-exact against the reference -- its sha256 over all generated
-ids is compared with the reference-generated golden of this very workload (tests/golden/bench_c3.npz,
-oracle/make_bench_golden.py).
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+`--full` adds everything else the benchmark measures or checks, after the timed steps of the headline: the graph-vs-eager
+and reference checks of the token ids (their sha256 against the reference-generated golden of this very workload,
+tests/golden/bench_c3.npz, oracle/make_bench_golden.py), the other numeric modes (f32 MFMA; the bf16 perf mode and its
+teacher-forced parity), rooflines and per-kernel figures, the pipelined / pcm16 / two-lane / slot-pool legs, BASELINE's
+other configs, refine-text, time to first sample (warm and cold), the weak-scaling projection, the CPU baseline, and at
+N > 1 the check of the C-ABI weight broadcast.  The --no-* options leave single legs out of a --full run.
 
 N > 1: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`, or plain `python bench.py --gpus N` (which spawns
 exactly that itself; a world size that is not N is refused) -- the global batch of 64*N utterances is sharded in contiguous row blocks
@@ -533,19 +536,24 @@ def plumbing_only(args, world, rank, local_rank):
     return 0
 
 
-def main():
+def arg_parser() -> argparse.ArgumentParser:
+    """the command line of bench.py (a plain run times the headline alone; --full adds every other leg)"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="after the headline's timed steps, run every other leg of the benchmark (ids checks "
+                    "against graph-vs-eager and the reference's golden, the other numeric modes, rooflines, configs, TTFS, projection, CPU "
+                    "baseline, the C-ABI broadcast check at N > 1); the --no-* options below leave single legs out.  Default: the headline only")
     ap.add_argument("--batch", type=int, default=64, help="utterances per GPU")
     ap.add_argument("--min-len", type=int, default=128)
     ap.add_argument("--max-len", type=int, default=512)
     ap.add_argument("--dtype", default="f32x3", choices=["f32x3", "f32", "bf16"],
                     help="arithmetic of the HEADLINE leg (`value`, --steps / --warmup).  f32x3 (default): the parity mode -- float32 weights / KV / "
                          "attention / heads / sampling, decode projections on split-bf16 operands, every call certified by its decision margins "
-                         "with the exact f32 kernels as fallback; token ids == the reference's (sha256 checked on the line).  f32: the same on "
-                         "f32 MFMA throughout.  bf16: the perf mode (not bit-exact; normally reported beside the headline as `value_bf16`)")
+                         "with the exact f32 kernels as fallback; token ids == the reference's (sha256 checked on the line of a --full run).  "
+                         "f32: the same on f32 MFMA throughout.  bf16: the perf mode (not bit-exact; a --full run reports it beside the headline as "
+                         "`value_bf16`)")
     ap.add_argument("--bf16-steps", type=int, default=5, help="timed passes of the bf16 perf mode reported beside a parity headline")
     ap.add_argument("--no-bf16-mode", action="store_true", help="skip the bf16 perf-mode legs (value_bf16, its kernels, the queue / pcm16 / slot-pool "
                     "/ C2 / C5 legs that run on it)")
@@ -588,7 +596,11 @@ def main():
     ap.add_argument("--cpu-baseline-only", action="store_true", help="(internal) run the CPU baseline leg alone and print its JSON")
     ap.add_argument("--cold-start-only", choices=["plain", "prewarmed"], default=None,
                     help="(internal) a FRESH process: load, optionally Chat.warm the workload's geometry, then time the first streamed chunk")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
 
     if args.cpu_baseline_only:   # child process of the main run (no GPU use): see cpu_baseline_guarded()
         wl = shard_workload(args.batch, 1, 0, args.min_len, args.max_len)
@@ -655,8 +667,8 @@ def main():
                          "first use of the communicator, so ring set-up is inside the figure"}
         # the same collective through the library's own C ABI (ctts_broadcast_weights on an RCCL communicator made from the C ABI, what a
         # host without torch would call): one flat buffer, checked against what torch.distributed delivered; never fatal for the bench
-        if args.no_capi_broadcast_check:
-            bcast["capi_broadcast"] = {"ok": None, "skipped": "--no-capi-broadcast-check"}
+        if args.no_capi_broadcast_check or not args.full:
+            bcast["capi_broadcast"] = {"ok": None, "skipped": "--no-capi-broadcast-check" if args.full else "runs with --full"}
         else:
             bcast["capi_broadcast"] = capi_broadcast_check(D, sds, world, rank, dev, dist, args.capi_broadcast_timeout)
         sds = {n: {k: v.cpu() for k, v in sd.items()} for n, sd in sds.items()}  # the engines repack from host tensors
@@ -782,7 +794,7 @@ def main():
     # shard's rows (the reference has no data-parallel mode -- it ran the 64 N utterances as one batch) and the line carries the AND
     gname = "bench_c3.npz" if world == 1 else "bench_c3_w%d.npz" % world
     gold, gpath = None, os.path.join(ROOT, "tests", "golden", gname)
-    if os.path.exists(gpath) and (args.batch, args.min_len, args.max_len) == (64, 128, 512):
+    if args.full and os.path.exists(gpath) and (args.batch, args.min_len, args.max_len) == (64, 128, 512):
         gold = np.load(gpath)
     want_sha, gold_rows = None, None
     if gold is not None:
@@ -819,8 +831,8 @@ def main():
                         "|log(cum / (1 - top_P))| at the cut}, in tempered-logit units, computed inside sample_k; bound = 2 x the stated logit error of "
                         "the split-fp16 projections (GptEngine.REL_ERR_X3 x the head's logit scale; measured: profiles/r6o_x3_logit_bound_fp16split.log) / min "
                         "temperature.  `certified: false` = some draw was closer than the worst-case bound (on 500-step utterances one almost always "
-                        "is: ~10 of this workload's 85,752 draws); the ids of THIS run are checked against the reference's sha256 all the same "
-                        "(`ids_check`), and --exact-fallback regenerates the flagged utterances on the f32 MFMA kernels inside the timed pass"}
+                        "is: ~10 of this workload's 85,752 draws); with --full the ids of THIS run are checked against the reference's sha256 all the "
+                        "same (`ids_check`; a plain run checks nothing), and --exact-fallback regenerates the flagged utterances on the f32 MFMA kernels inside the timed pass"}
 
     def mode_leg(eng, cdc, steps, warmup, tag=None, sink=None):
         """K timed passes of the workload on one engine + what they produced: graph replay == eager launches, sha256 of all token rows
@@ -833,7 +845,7 @@ def main():
         cert = certificate_of(eng)
         if cert is not None:
             leg["certificate"] = cert
-        if not args.no_ids_check:
+        if args.full and not args.no_ids_check:
             _, _, ids_g = one_pass(eng, cdc, use_graph=not args.no_graph, decode_audio=False, keep_ids=True)
             _, _, ids_e = one_pass(eng, cdc, use_graph=False, decode_audio=False, keep_ids=True)
             leg["ids_check"] = {"ids_sha256": ids_digest(ids_g), "graph_equals_eager": ids_digest(ids_g) == ids_digest(ids_e)}
@@ -859,7 +871,7 @@ def main():
     result = {
         "metric": "audio seconds/sec (RTF), batch=64 per GPU", "value": None if args.share_gpu else round(value, 2), "unit": "audio-s/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000.0 * dt / args.steps, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": bool(args.full),
         "config": {"workload": "C3: batch=64/GPU mixed-length (prompts 16-48 tok, outputs U{%d..%d} tok), top-p .7/top-k 20/rep 1.05/"
                                "temp .3, manual_seed 42, prompt embedding gather + hipGraph decode + DVAE + Vocos + waveform D2H (.cpu().numpy()); "
                                "%s" % (args.min_len, args.max_len,
@@ -1012,6 +1024,28 @@ def main():
         result["ranks"] = {"world": world, "pass_ms_per_rank": rt, "pass_ms_min": min(rt) if rt else None, "pass_ms_max": max(rt) if rt else None,
                            "weight_broadcast": bcast,
                            "data_path_collectives": "none (utterances are independent; only the timing barrier / max-over-ranks all-reduce)"}
+
+    def emit():
+        if rank == 0:
+            def finite(o):      # strict JSON: no Infinity / NaN (e.g. the margin of a call that drew nothing)
+                if isinstance(o, float):
+                    return o if np.isfinite(o) else None
+                if isinstance(o, dict):
+                    return {k: finite(v) for k, v in o.items()}
+                if isinstance(o, (list, tuple)):
+                    return [finite(v) for v in o]
+                return o
+            try:
+                line = json.dumps(finite(result), allow_nan=False)
+            except (TypeError, ValueError):
+                line = json.dumps(result, default=float)
+            print(line, flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:      # a plain run: the headline is all it measures
+        return emit()
 
     valid_prompt = wl["mask"].sum(1).astype(np.int64)
     st_ = wl["stop"].astype(np.int64)
@@ -1311,23 +1345,7 @@ def main():
         note("cpu baseline (separate process, hard 170 s limit)")
         result["cpu_baseline"] = cpu_baseline_guarded(args)
 
-    if rank == 0:
-        def finite(o):      # strict JSON: no Infinity / NaN (e.g. the margin of a call that drew nothing)
-            if isinstance(o, float):
-                return o if np.isfinite(o) else None
-            if isinstance(o, dict):
-                return {k: finite(v) for k, v in o.items()}
-            if isinstance(o, (list, tuple)):
-                return [finite(v) for v in o]
-            return o
-        try:
-            line = json.dumps(finite(result), allow_nan=False)
-        except (TypeError, ValueError):
-            line = json.dumps(result, default=float)
-        print(line, flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    emit()
 
 
 def generate_heads(embed_sd) -> np.ndarray:

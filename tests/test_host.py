@@ -624,6 +624,36 @@ def test_bench_gpus_2_without_gpus_fails_loudly_about_the_gpu():
     assert "NO result line is printed for --gpus 2" in r.stderr
 
 
+def test_bench_plain_run_is_the_headline_and_full_is_opt_in():
+    """`bench.py` without --full times the headline alone: --full is off by default, every other leg of main() is reached only past
+    the plain run's early return, and the two checks that sit before it (the ids check of a mode's timed passes, the C-ABI broadcast
+    check at load) run only under args.full"""
+    import ast
+    import bench
+    ap = bench.arg_parser()
+    assert ap.parse_args([]).full is False
+    assert ap.parse_args(["--full", "--steps", "2"]).full is True
+    main = next(n for n in ast.parse(open(os.path.join(ROOT, "bench.py")).read()).body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    gates = [n for n in main.body if isinstance(n, ast.If) and ast.unparse(n.test) == "not args.full"
+             and any(isinstance(b, ast.Return) for b in n.body)]
+    assert len(gates) == 1
+    legs = {"one_pass", "roofline_leg", "mfma_rooflines", "pipelined_leg", "pcm16_leg", "two_lanes_leg", "config_leg_c1", "ttfs_leg",
+            "projection_leg", "refine_text_legs", "slot_pool_leg", "config_legs_bf16", "cold_start_guarded", "cpu_baseline_guarded"}
+
+    def called(node):
+        return {c.func.id for c in ast.walk(node) if isinstance(c, ast.Call) and isinstance(c.func, ast.Name)}
+    for st in main.body:
+        if not isinstance(st, ast.FunctionDef) and st.lineno < gates[0].lineno:
+            assert not (called(st) & legs), (st.lineno, called(st) & legs)
+    reached_after = set().union(*(called(st) for st in main.body if st.lineno > gates[0].lineno))
+    assert {"roofline_leg", "pipelined_leg", "ttfs_leg", "cpu_baseline_guarded"} <= reached_after
+    mode_leg = next(n for n in ast.walk(main) if isinstance(n, ast.FunctionDef) and n.name == "mode_leg")
+    ids_if = [n for n in ast.walk(mode_leg) if isinstance(n, ast.If) and "one_pass" in called(n)]
+    capi_if = [n for n in ast.walk(main) if isinstance(n, ast.If) and any("capi_broadcast_check" in called(b) for b in n.orelse)]
+    assert len(ids_if) == 1 and len(capi_if) == 1
+    assert "args.full" in ast.unparse(ids_if[0].test) and "args.full" in ast.unparse(capi_if[0].test)
+
+
 def test_bench_refuses_a_world_size_that_is_not_gpus():
     import subprocess
     import sys
