@@ -1333,8 +1333,10 @@ class CodecEngine:
         batch (the reference's semantics, core.py:525-533) lets the padding's bias-driven activations into a shorter row's last ~51 tokens.
         Returns (wav, off): ONE flat float32 device tensor with utterance i's 256 (2 T_i - 1) samples at [off[i], off[i+1]) (`off` a host
         int64 array of len(rows) + 1; `ragged_views(wav, off)` gives the per-utterance views), plus the packed mel [sum 2 T_i, 100] as a
-        third element when `return_mel`.  With gemm "f32" and fewer than 12288 frames in all, every utterance is bit-identical to its B = 1
-        decode; otherwise within the tile-size tolerance of the mode."""
+        third element when `return_mel`.  With gemm "f32" or "bf16x3", every utterance's mel and waveform are bit-identical to its B = 1
+        decode at any packed size.  With "f16", a pack of at least CTTS_X3P_MIN_ROWS (default 1024) frames runs the point-wise pairs
+        on fp16 planes: an utterance of at least that many frames takes them alone too and is bit-identical, a shorter one takes
+        split-bf16 tiles alone and is within 2e-5 RMS."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
         lens = [int(r.size(0)) for r in rows]

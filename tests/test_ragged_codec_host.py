@@ -219,3 +219,37 @@ def test_batcher_default_still_decodes_each_request_alone():
         assert chat.pcm_calls == [] and chat.wav_calls == 3
     finally:
         b.close()
+
+
+EDGE_TOTALS = (1022, 1024, 1026, 12286, 12288, 12290, 40000)
+
+
+@pytest.mark.parametrize("total", EDGE_TOTALS)
+def test_ragged_edge_layout_puts_short_segments_at_every_kernel_edge(total):
+    """tests/gpu_util.ragged_edge_layout, the packs of tests/test_gpu_ragged_codec_edges.py: exactly `total` frames; 1-token segments
+    first and last; every short length (1, 2, 3, 4, 7 tokens) between two long segments (>= 8 tokens); aligned 32 / 36 / 48 / 64 /
+    128 / 256-frame windows holding many boundaries (the 1-token run); boundaries with a long neighbour at frame offsets 0, +2 and
+    -2 mod each of those (every boundary is at an even frame, so +-1 is out of reach); deterministic"""
+    from tests.gpu_util import EDGE_LONG, EDGE_MODS, EDGE_SHORTS, edge_residues, ragged_edge_layout, ragged_edge_rows
+    lens = ragged_edge_layout(total)
+    assert lens == ragged_edge_layout(total)
+    assert all(isinstance(t, int) and t >= 1 for t in lens) and 2 * sum(lens) == total
+    assert lens[0] == 1 and lens[-1] == 1
+    for s in EDGE_SHORTS:
+        assert any(lens[i] == s and lens[i - 1] >= EDGE_LONG and lens[i + 1] >= EDGE_LONG for i in range(1, len(lens) - 1)), s
+    assert EDGE_LONG * 2 > 13
+    bnd = 2 * np.cumsum(lens)[:-1]                         # frame offsets of the boundaries between segments
+    assert np.all(bnd % 2 == 0)
+    for m in EDGE_MODS:
+        inside = max(int(np.sum((bnd > j * m) & (bnd < (j + 1) * m))) for j in range(total // m))
+        assert inside >= min(m // 2 - 1, 64), (m, inside)  # every other frame of one aligned window is a boundary
+        long_nb = {int(bnd[i]) % m for i in range(len(bnd)) if max(lens[i], lens[i + 1]) >= EDGE_LONG}
+        for r in edge_residues(m):
+            assert r in long_nb, (m, r)
+    assert sorted(edge_residues(32)) == [0, 2, 30]
+    ones = max(len(run) for run in "".join("1" if t == 1 else "." for t in lens).split("."))
+    assert ones >= 64
+    lens2, rows = ragged_edge_rows(total)
+    assert lens2 == lens and [r.shape for r in rows] == [(t, 768) for t in lens] and rows[0].dtype == np.float32
+    if total >= 12288:
+        assert max(lens) >= 128                            # long segments of the bench's utterance lengths
