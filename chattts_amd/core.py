@@ -311,6 +311,12 @@ class Chat:
         keep_h = host[2 * n: 2 * n + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
+    def decode_windows_pcm16(self, store: torch.Tensor, windows) -> List[np.ndarray]:
+        """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
+        out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
+        (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream)"""
+        return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5)
+
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
         """non-stream `Chat._infer` body for one batch (core.py:469-481, split_text=False, skip_refine_text=True),
         BEFORE the sample-level silence strip of core.py:258-270."""

@@ -1023,6 +1023,69 @@ extern "C" int ctts_vocos_decode_ragged(ctts_codec* c, const float* mel, const i
   return 0;
 }
 
+// ---- window decode: the due chunks of many streams in one ragged pass, each window at its own position of its own slot ----------------
+static_assert(sizeof(ctts_window) == 32 && sizeof(CodecWindow) == 32 && offsetof(ctts_window, keep) == offsetof(CodecWindow, keep) &&
+              offsetof(ctts_window, c_lo) == offsetof(CodecWindow, c_lo), "ctts_window layout");
+// workspace = the ragged workspace | packed hidden rows [T, 768] | tok_off [n_win + 1] | mel [2 T, 100] | wav [256 (2 T - n_win)]
+struct WindowsWs {
+  float *hid, *mel, *wav;
+  int32_t* tok_off;
+  size_t ragged_bytes, bytes;
+};
+static WindowsWs carve_windows(void* base, int n_win, int T) {
+  WindowsWs w;
+  char* p = (char*)base;
+  size_t off = w.ragged_bytes = ctts_codec_ragged_workspace_bytes(n_win, T);
+  w.hid = (float*)(p + off); off += align_up((size_t)T * 768 * 4);
+  w.tok_off = (int32_t*)(p + off); off += align_up((size_t)(n_win + 1) * 4);
+  w.mel = (float*)(p + off); off += align_up((size_t)2 * T * 100 * 4);
+  w.wav = (float*)(p + off); off += align_up((size_t)256 * (2 * (size_t)T - n_win) * 4);
+  w.bytes = off;
+  return w;
+}
+extern "C" size_t ctts_codec_windows_workspace_bytes(int32_t n_win, int32_t total_tokens) {
+  if (n_win < 1 || total_tokens < n_win || ctts_codec_ragged_workspace_bytes(n_win, total_tokens) == 0) return 0;
+  return carve_windows(nullptr, n_win, total_tokens).bytes;
+}
+extern "C" int ctts_codec_decode_windows(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots, int32_t hid_cap,
+                                         const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win, int32_t out_type, void* out,
+                                         uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
+  const char* who = "ctts_codec_decode_windows";
+  if (!c || !hid || !win_dev || !win_host || !out) return fail("%s: bad arguments", who);
+  if (n_win < 1 || n_win > 1024) return fail("%s: need 1 <= n_win <= 1024 (got %d)", who, n_win);
+  if ((out_type != 0 && out_type != 1) || (product != 0 && product != 1)) return fail("%s: out_type and product must be 0 or 1", who);
+  if (n_slots < 1 || hid_cap < 1 || row_stride < 768 || slot_stride < (int64_t)hid_cap * row_stride || (row_stride & 3) || (slot_stride & 3) ||
+      ((uintptr_t)hid & 15) || ((uintptr_t)out & 15))
+    return fail("%s: the store must be [n_slots][hid_cap][768] floats with 16-byte aligned rows, the output 16-byte aligned", who);
+  std::vector<int32_t> tok(n_win + 1, 0);
+  for (int i = 0; i < n_win; ++i) {
+    const ctts_window& w = win_host[i];
+    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: window %d names slot %d of %d", who, i, w.slot, n_slots);
+    if (w.t_lo < 0 || w.t_hi <= w.t_lo) return fail("%s: window %d is empty (tokens %d -> %d)", who, i, w.t_lo, w.t_hi);
+    if (w.t_hi > hid_cap) return fail("%s: window %d ends at token %d beyond the slot's capacity %d", who, i, w.t_hi, hid_cap);
+    const int64_t n_samples = 256 * (2 * (int64_t)(w.t_hi - w.t_lo) - 1);
+    if (w.c_lo < 0 || w.c_hi <= w.c_lo || w.c_hi > n_samples)
+      return fail("%s: window %d crops samples %d -> %d outside its %lld samples", who, i, w.c_lo, w.c_hi, (long long)n_samples);
+    if (w.keep && !keep_bits) return fail("%s: window %d asks for a keep mask but keep_bits is null", who, i);
+    tok[i + 1] = tok[i] + (w.t_hi - w.t_lo);
+    if (tok[i + 1] > (1 << 28)) return fail("%s: too many tokens", who);
+  }
+  const int T = tok[n_win];
+  if (!workspace || ws_bytes < ctts_codec_windows_workspace_bytes(n_win, T)) return fail("codec workspace too small");
+  WindowsWs ws = carve_windows(workspace, n_win, T);
+  {
+    CttsDeviceGuard dg(stream);
+    CK(launch_gather_windows(hid, slot_stride, row_stride, (const CodecWindow*)win_dev, n_win, T, ws.hid, ws.tok_off, (hipStream_t)stream));
+  }
+  // the ragged stages, unchanged: every window is a segment, its edges are sequence edges
+  if (ctts_dvae_decode_ragged(c, ws.hid, ws.tok_off, tok.data(), n_win, ws.mel, workspace, ws.ragged_bytes, stream)) return -1;
+  if (ctts_vocos_decode_ragged(c, ws.mel, ws.tok_off, tok.data(), n_win, ws.wav, workspace, ws.ragged_bytes, stream)) return -1;
+  CttsDeviceGuard dg(stream);
+  CK(launch_crop_pcm16_windows(ws.wav, (const CodecWindow*)win_dev, n_win, out_type == 0 ? 1 : 0, product, keep_thr, out, keep_bits,
+                               (hipStream_t)stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // single-kernel entry points
 // ------------------------------------------------------------------------------------------------

@@ -509,6 +509,17 @@ __global__ __launch_bounds__(256) void absmax_rows_k(const float* __restrict__ x
   for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
   if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(peak + (per_row ? row : 0), m);
 }
+// the scale of a row whose peak |x| is pk, and one converted sample (shared by every PCM16 kernel of this file)
+__device__ __forceinline__ long long pcm16_scale(float pk) {
+  // a non-finite sample makes the peak Inf / NaN (the bit pattern of |x| orders above every finite value): the cast would be undefined
+  // behaviour -- such a row gets scale 0, i.e. zeros (the reference's numpy path yields garbage there)
+  const long long c = (pk < 3.0e38f) ? (long long)ceilf(pk) : 0;
+  return c > 0 ? (32767ll * 32768ll) / (c * 32768ll) : 0;
+}
+__device__ __forceinline__ int16_t pcm16_sample(float v, long long am, int product) {
+  const int q = product == 0 ? (int)((double)v * (double)am) : (int)(v * (float)am);
+  return (int16_t)q;
+}
 template <bool SEG = false>
 __global__ __launch_bounds__(256) void pcm16_k(const float* __restrict__ x, long long n, long long ld, int per_row, int product,
                                                const unsigned* __restrict__ peak, float keep_thr, int16_t* __restrict__ out,
@@ -520,11 +531,7 @@ __global__ __launch_bounds__(256) void pcm16_k(const float* __restrict__ x, long
     kb = 0;
     for (int j = 0; j < row; ++j) kb += (off[j + 1] - off[j] + 7) >> 3;   // wave-uniform: scalar loads
   }
-  const float pk = __uint_as_float(peak[per_row ? row : 0]);
-  // a non-finite sample makes the peak Inf / NaN (the bit pattern of |x| orders above every finite value): the cast would be undefined
-  // behaviour -- such a row gets scale 0, i.e. zeros (the reference's numpy path yields garbage there)
-  const long long c = (pk < 3.0e38f) ? (long long)ceilf(pk) : 0;
-  const long long am = c > 0 ? (32767ll * 32768ll) / (c * 32768ll) : 0;
+  const long long am = pcm16_scale(__uint_as_float(peak[per_row ? row : 0]));
   const float* xr = x + (SEG ? (size_t)off[row] : (size_t)row * ld);
   int16_t* orow = out + (SEG ? (size_t)off[row] : (size_t)row * n);
   const long long nb = (n + 7) >> 3;                     // groups of 8 samples = 16 bytes of PCM = one byte of mask
@@ -535,8 +542,7 @@ __global__ __launch_bounds__(256) void pcm16_k(const float* __restrict__ x, long
       const long long i = gi * 8 + e;
       if (i < n) {
         const float v = xr[i];
-        const int q = product == 0 ? (int)((double)v * (double)am) : (int)(v * (float)am);
-        orow[i] = (int16_t)q;
+        orow[i] = pcm16_sample(v, am, product);
         if (fabsf(v) > keep_thr) bits |= 0x80u >> e;      // np.packbits order: first sample in the top bit
       }
     }
@@ -568,5 +574,119 @@ hipError_t launch_float_to_int16_ragged(const float* wav, const long long* off, 
   const long long nb = (n_max + 7) >> 3;
   const unsigned gx2 = (unsigned)min((nb + 255) / 256, 2048ll);
   hipLaunchKernelGGL(pcm16_k<true>, dim3(gx2, n_seg), dim3(256), 0, st, wav, 0ll, 0ll, 1, product, (const unsigned*)peak, keep_thr, pcm, keep, off);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Window decode (ctts_codec_decode_windows): the chunks of many streamed utterances that are due at one poll, each at its own position.
+// A window = token rows [t_lo, t_hi) of one slot of a hidden-state store [slots][hid_cap][768]; it is decoded as one ragged segment and
+// samples [c_lo, c_hi) of its decode (relative to the window's first sample) are emitted.
+// ------------------------------------------------------------------------------------------------
+// Packs the windows' rows [sum n_i, 768] out of the store: one wave per row, three 16-byte loads and stores per lane.  Workgroup 0 also
+// writes the n_win + 1 token offsets the ragged stages read.  The window of a packed row is found by a wave-uniform walk of the table.
+__global__ __launch_bounds__(256) void gather_windows_k(const float* __restrict__ hid, long long slot_stride, long long row_stride,
+                                                        const CodecWindow* __restrict__ win, int n_win, int total_rows,
+                                                        float* __restrict__ packed, int32_t* __restrict__ tok_off) {
+  if (blockIdx.x == 0) {
+    for (int i = threadIdx.x; i <= n_win; i += 256) {
+      int t = 0;
+      for (int j = 0; j < i; ++j) t += win[j].t_hi - win[j].t_lo;
+      tok_off[i] = t;
+    }
+  }
+  const int r = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (r >= total_rows) return;
+  int base = 0, i = 0;
+  for (; i < n_win; ++i) {
+    const int n = win[i].t_hi - win[i].t_lo;
+    if (r < base + n) break;
+    base += n;
+  }
+  if (i == n_win) return;   // the device table holds fewer rows than the host mirror said: nothing is read or written for the rest
+  const u128* src = reinterpret_cast<const u128*>(hid + (long long)win[i].slot * slot_stride + (long long)(win[i].t_lo + r - base) * row_stride);
+  u128* dst = reinterpret_cast<u128*>(packed + (size_t)r * 768);
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dst[lane + 64 * k] = src[lane + 64 * k];
+}
+hipError_t launch_gather_windows(const float* hid, long long slot_stride, long long row_stride, const CodecWindow* win, int n_win, int total_rows,
+                                 float* packed, int32_t* tok_off, hipStream_t st) {
+  if (n_win < 1 || total_rows < n_win) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_windows_k, dim3((total_rows + 3) / 4), dim3(256), 0, st, hid, slot_stride, row_stride, win, n_win, total_rows, packed,
+                     tok_off);
+  return hipGetLastError();
+}
+
+// One workgroup per window: the peak over the CROPPED samples only, then the conversion of ctts_float_to_int16 (per_row) -- or, out_f32, the
+// crop alone.  Window i's samples go to element out_off[i] = sum_{j<i} ceil8(c_hi_j - c_lo_j) of the output (every window starts on a
+// 16-byte boundary of the int16 output; the pad samples are written as zeros) and, when win[i].keep, its mask |x| > keep_thr to byte
+// out_off[i] / 8 of keep (np.packbits order) -- the layout of float_to_int16_ragged's masks.  A thread converts 8 samples: two 16-byte
+// loads where the crop starts on a 16-byte boundary (every chunk of the streaming schedule does), one 16-byte store.
+__global__ __launch_bounds__(1024) void crop_pcm16_windows_k(const float* __restrict__ wav, const CodecWindow* __restrict__ win, int out_f32,
+                                                             int product, float keep_thr, void* __restrict__ out, uint8_t* __restrict__ keep) {
+  __shared__ unsigned red[16];
+  const int w = blockIdx.x;
+  long long tok = 0, oo = 0;
+  for (int j = 0; j < w; ++j) {      // wave-uniform: scalar loads
+    tok += win[j].t_hi - win[j].t_lo;
+    oo += (long long)((win[j].c_hi - win[j].c_lo + 7) & ~7);
+  }
+  const int n = win[w].c_hi - win[w].c_lo;
+  const float* x = wav + HOP * (2 * tok - w) + win[w].c_lo;
+  const int groups = (n + 7) >> 3;
+  const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  auto load8 = [&](int g, float (&v)[8]) {
+    if (vec && g * 8 + 8 <= n) {
+      const float4 a = reinterpret_cast<const float4*>(x)[2 * g], b = reinterpret_cast<const float4*>(x)[2 * g + 1];
+      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = g * 8 + e < n ? x[g * 8 + e] : 0.0f;
+    }
+  };
+  long long am = 0;
+  if (!out_f32) {
+    unsigned m = 0;
+    for (int g = threadIdx.x; g < groups; g += 1024) {
+      float v[8];
+      load8(g, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) m = max(m, __float_as_uint(v[e]) & 0x7fffffffu);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m = max(m, red[k]);
+    am = pcm16_scale(__uint_as_float(m));
+  }
+  const bool mask = keep != nullptr && win[w].keep != 0;
+  for (int g = threadIdx.x; g < groups; g += 1024) {
+    float v[8];
+    load8(g, v);
+    if (out_f32) {
+      float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + oo) + 2 * g;
+      o[0] = make_float4(v[0], v[1], v[2], v[3]);
+      o[1] = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+      union { u128 q; int16_t s[8]; } p;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) p.s[e] = pcm16_sample(v[e], am, product);
+      reinterpret_cast<u128*>(reinterpret_cast<int16_t*>(out) + oo)[g] = p.q;
+    }
+    if (mask) {
+      unsigned bits = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (g * 8 + e < n && fabsf(v[e]) > keep_thr) bits |= 0x80u >> e;
+      keep[(oo >> 3) + g] = (uint8_t)bits;
+    }
+  }
+}
+hipError_t launch_crop_pcm16_windows(const float* wav, const CodecWindow* win, int n_win, int out_f32, int product, float keep_thr, void* out,
+                                     uint8_t* keep, hipStream_t st) {
+  if (n_win < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(crop_pcm16_windows_k, dim3(n_win), dim3(1024), 0, st, wav, win, out_f32, product, keep_thr, out, keep);
   return hipGetLastError();
 }

@@ -456,6 +456,19 @@ hipError_t launch_float_to_int16(const float* wav, long long n, long long ld, in
 // sum_{j<i} ceil(n_j / 8) on (every segment starts on a byte boundary).  n_max: the longest segment (grid size)
 hipError_t launch_float_to_int16_ragged(const float* wav, const long long* off, int n_seg, long long n_max, int product, float keep_thr,
                                         unsigned* peak, int16_t* pcm, uint8_t* keep, hipStream_t st);
+// ctts_window (include/chattts_amd.h), field for field (capi.hip asserts the layout): token rows [t_lo, t_hi) of one slot of a hidden-state
+// store, decoded as one ragged segment; samples [c_lo, c_hi) of that decode (relative to its first sample) are emitted
+struct CodecWindow {
+  int32_t slot, t_lo, t_hi, c_lo, c_hi, keep, reserved[2];
+};
+// packs the windows' rows out of hid [slots][..][768] (strides in floats, multiples of 4) into packed [total_rows, 768]; writes tok_off [n_win + 1]
+hipError_t launch_gather_windows(const float* hid, long long slot_stride, long long row_stride, const CodecWindow* win, int n_win, int total_rows,
+                                 float* packed, int32_t* tok_off, hipStream_t st);
+// wav: the windows' ragged decode (window i at 256 (2 tok_off[i] - i)); out: int16 (or float32, out_f32) with window i's c_hi - c_lo samples
+// from element sum_{j<i} ceil8(c_hi_j - c_lo_j) on, one peak per window over its crop; keep (or null): the masks of the windows with .keep set,
+// window i's from byte (that element offset) / 8 on
+hipError_t launch_crop_pcm16_windows(const float* wav, const CodecWindow* win, int n_win, int out_f32, int product, float keep_thr, void* out,
+                                     uint8_t* keep, hipStream_t st);
 hipError_t launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t st);   // shader copy (dst may be pinned host memory)
 
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------

@@ -1151,6 +1151,31 @@ def ragged_views(flat, off) -> list:
     return [flat[int(off[i]): int(off[i + 1])] for i in range(len(off) - 1)]
 
 
+# receptive field of one output sample, in mel frames either side: ISTFT 4 overlapping frames; Vocos embed k7 + 8 ConvNeXt
+# blocks k7 = 27; DVAE conv_in k3 + k3, 12 ConvNeXt blocks k7 dilation 2, out_conv k3 = 75 (dvae.py:145-161, config.py:83-121)
+HALO_FRAMES = 27 + 75
+
+
+def window_for_samples(Tn: int, s_lo: int, s_hi: int):
+    """The token window that samples [s_lo, s_hi) of the decode of a `Tn`-token prefix depend on, and where they sit in its decode:
+    (t_lo, t_hi, c_lo, c_hi) -- tokens [t_lo, t_hi) decoded alone give the samples at [c_lo, c_hi) of that decode (HALO_FRAMES mel
+    frames + the 4 overlapping ISTFT frames either side; at the prefix's own ends the window's edge is the sequence's edge).  The range
+    is clipped to the prefix's 256 (2 Tn - 1) samples; None when nothing is left.  Pure host arithmetic (`decode_window`,
+    `decode_windows`)."""
+    Tn = int(Tn)
+    hop, nfft = VOCOS.hop, VOCOS.n_fft
+    total = hop * (2 * Tn - 1)
+    s_lo, s_hi = max(0, int(s_lo)), min(total, int(s_hi))
+    if s_hi <= s_lo:
+        return None
+    f_a = (s_lo + nfft // 2) // hop - (nfft // hop - 1)          # first / last ISTFT frame that overlaps the samples
+    f_b = min((s_hi - 1 + nfft // 2) // hop, 2 * Tn - 1)
+    t_lo = max(0, (f_a - HALO_FRAMES) // 2)
+    t_hi = min(Tn, (f_b + HALO_FRAMES) // 2 + 1)
+    off = 2 * hop * t_lo                                          # sample index of the window's first sample
+    return t_lo, t_hi, s_lo - off, s_hi - off
+
+
 class CodecEngine:
     """DVAE decoder + Vocos on the device (channels-last)."""
 
@@ -1389,9 +1414,7 @@ class CodecEngine:
         off_d.record_stream(st)
         return pcm, keep, keep_off
 
-    # receptive field of one output sample, in mel frames either side: ISTFT 4 overlapping frames; Vocos embed k7 + 8 ConvNeXt
-    # blocks k7 = 27; DVAE conv_in k3 + k3, 12 ConvNeXt blocks k7 dilation 2, out_conv k3 = 75 (dvae.py:145-161, config.py:83-121)
-    HALO_FRAMES = 27 + 75
+    HALO_FRAMES = HALO_FRAMES
 
     def decode_window(self, result_list: List[torch.Tensor], s_lo: int, s_hi: int) -> torch.Tensor:
         """Samples [s_lo, s_hi) of `decode_to_wavs(result_list)` WITHOUT decoding the whole batch: the acoustic decoder is a
@@ -1400,24 +1423,73 @@ class CodecEngine:
         through DVAE + Vocos; at the true ends of the sequence the window is the sequence's own edge, so the result equals
         the full decode up to summation order.  This is what makes streaming O(n): the reference re-decodes the entire
         prefix at every yield (core.py:482-497) to hand out the next `stream_speed` samples of it."""
-        Tn = max(int(r.size(0)) for r in result_list)
-        total = VOCOS.hop * (2 * Tn - 1)
-        s_lo, s_hi = max(0, int(s_lo)), min(total, int(s_hi))
-        if s_hi <= s_lo:
+        win = window_for_samples(max(int(r.size(0)) for r in result_list), s_lo, s_hi)
+        if win is None:
             return torch.empty((len(result_list), 0), dtype=torch.float32, device=self.device)
-        hop, nfft = VOCOS.hop, VOCOS.n_fft
-        f_a = (s_lo + nfft // 2) // hop - (nfft // hop - 1)          # first / last ISTFT frame that overlaps the samples
-        f_b = min((s_hi - 1 + nfft // 2) // hop, 2 * Tn - 1)
-        t_lo = max(0, (f_a - self.HALO_FRAMES) // 2)
-        t_hi = min(Tn, (f_b + self.HALO_FRAMES) // 2 + 1)
+        t_lo, t_hi, c_lo, c_hi = win
         batch = torch.zeros((len(result_list), t_hi - t_lo, GPT.hidden), dtype=torch.float32, device=self.device)
         for i, r in enumerate(result_list):
             n = min(int(r.size(0)), t_hi) - t_lo
             if n > 0:
                 batch[i, :n] = r[t_lo: t_lo + n]
         wav = self.vocos_decode(self.dvae_decode(batch))
-        off = 2 * hop * t_lo                                          # sample index of the window's first sample
-        return wav[:, s_lo - off: s_hi - off]
+        return wav[:, c_lo: c_hi]
+
+    def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64"):
+        """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
+        `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
+        or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
+        None: to the end) of the decode of the first Tn rows of that slot -- what `decode_window([store[slot, :Tn]], s_lo, s_hi)[0]`
+        returns, bit for bit with gemm "f32" / "bf16x3" (the ragged decoder's bar; "f16": within its 2e-5 RMS).  Returns one numpy
+        array per window: int16 through `float_to_int16`'s arithmetic with one peak per window over its own samples (`pcm16`), else
+        float32.  With `keep_thr`, a window marked `tail` comes back with its samples |x| <= keep_thr removed -- the serial path's
+        last chunk (core.py, `_infer`): the mask is taken from the float samples on the device, the conversion uses the peak over
+        the whole crop (the removed samples are all below the threshold, so that is the peak of the kept ones whenever any is kept).
+        One table upload, one pass, one device-to-host copy whatever the number of windows."""
+        assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
+        S, cap = int(store.size(0)), int(store.size(1))
+        dt = np.int16 if pcm16 else np.float32
+        out: list = [None] * len(windows)
+        rows, live = [], []
+        for i, w in enumerate(windows):
+            slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
+            tail = len(w) > 4 and bool(w[4]) and keep_thr is not None
+            if not (0 <= slot < S and 0 <= Tn <= cap):
+                raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
+            win = window_for_samples(Tn, s_lo, VOCOS.hop * (2 * Tn - 1) if s_hi is None else s_hi)
+            if win is None:
+                out[i] = np.zeros((0,), dt)
+                continue
+            rows.append((slot, *win, int(tail), 0, 0))
+            live.append(i)
+        if not live:
+            return out
+        tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]: slot, t_lo, t_hi, c_lo, c_hi, keep, 0, 0
+        n = (tab[:, 4] - tab[:, 3]).astype(np.int64)
+        off = np.zeros(len(live) + 1, np.int64)
+        np.cumsum((n + 7) // 8 * 8, out=off[1:])                             # every window starts on a multiple of 8 samples
+        esz = 2 if pcm16 else 4
+        n_out, any_keep = int(off[-1]) * esz, bool(tab[:, 5].any())
+        n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if any_keep else 0
+        cur = torch.cuda.current_stream(self.device)
+        buf = torch.empty((n_out + n_keep,), dtype=torch.uint8, device=self.device)      # samples | keep masks: one copy brings both
+        tab_d = torch.from_numpy(tab).to(self.device)
+        ws, nws = self._ws_bytes(self.lib.ctts_codec_windows_workspace_bytes(len(live), int((tab[:, 2] - tab[:, 1]).sum())))
+        _lib.check(self.lib.ctts_codec_decode_windows(self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap,
+                                                      tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(live), 1 if pcm16 else 0,
+                                                      buf.data_ptr(), buf.data_ptr() + n_out if any_keep else None,
+                                                      {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws,
+                                                      cur.cuda_stream), "ctts_codec_decode_windows")
+        tab_d.record_stream(cur)
+        host = self.to_host(buf)
+        vals = host[:n_out].view(dt)
+        for k, i in enumerate(live):
+            a = vals[int(off[k]): int(off[k]) + int(n[k])]
+            if tab[k, 5]:
+                kb = n_out + int(off[k]) // 8
+                a = a[np.unpackbits(host[kb: kb + (int(n[k]) + 7) // 8])[: int(n[k])].astype(bool)]
+            out[i] = a
+        return out
 
     def to_host(self, t: torch.Tensor) -> np.ndarray:
         """device tensor -> numpy, the `.cpu().numpy()` that ends the reference path (core.py:508-510), through a cached PINNED

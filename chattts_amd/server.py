@@ -18,7 +18,8 @@ from it).  What differs, deliberately:
 `create_app(..., batch_slots=N)` serves concurrent non-streamed requests in ONE batch: a worker thread owns a slot pool of N utterance
 slots with per-request sampling parameters (serving.SpeechBatcher, serving.SlotPool(per_request=True)), so eight clients share the chip
 instead of queueing for it.  Every response is what the serial endpoint returns for the same request (the same tokens; PCM within one
-count).  Streamed requests keep the serial path; a threading lock keeps them and the worker from issuing GPU work at the same time.
+count).  Streamed requests keep the serial path (a threading lock keeps them and the worker from issuing GPU work at the same time) unless
+`batch_streams=True`: then they are served from the same pool, their chunks decoded together (serving.SpeechBatcher.submit_stream).
 """
 from __future__ import annotations
 
@@ -78,13 +79,16 @@ def _have_av() -> bool:
 
 
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
-               batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False):
+               batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
     reference's behaviour); N = non-streamed requests are batched in a pool of N slots (serving.SpeechBatcher; `batcher`: a ready one,
     tests).  `ragged_decode` (batching only): the requests that finish together are decoded in one ragged pass, each as if alone,
-    instead of one decode per request (SpeechBatcher(ragged_decode=True))."""
+    instead of one decode per request (SpeechBatcher(ragged_decode=True)).  `batch_streams` (batching only; off: every path is as
+    without it): a request with `"stream": true` joins the pool too (SpeechBatcher.submit_stream) instead of taking `model_lock` and
+    running as a batch of one -- concurrent streams advance together, the chunks that are due at one poll come from one decoder pass,
+    and a client that goes away cancels its request."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -99,10 +103,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     gpu_lock = threading.Lock()                      # batching: the worker's chunks / decodes vs the streamed path's chunks
     if batcher is None and batch_slots is not None:
         from .serving import SpeechBatcher
-        batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode)
+        batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode, streams=bool(batch_streams))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
+    pool_streams = bool(batch_streams) and batcher is not None and bool(getattr(batcher, "streams", False))
 
     def locked_chunks(gen):
         """one chunk of a streamed response at a time under the GPU lock (batching on): the worker's chunks interleave with these"""
@@ -164,6 +169,23 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             if fmt == "pcm":
                 return pcm.tobytes()
             return _av_encode(pcm, fmt)
+
+        if req.stream and pool_streams:
+            async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
+                chunks = batcher.submit_stream(req.input, code_params(req.voice))
+                try:
+                    first = True
+                    async for chunk in iterate_in_threadpool(chunks):
+                        if fmt == "wav" and first:
+                            yield wav_stream_header()
+                        first = False
+                        if np.asarray(chunk).size:
+                            yield encode(chunk, header=False)
+                except Exception as e:
+                    log.error("speech synthesis failed mid-stream: %s", e)
+                finally:
+                    chunks.close()           # a client that went away: the request leaves the pool
+            return StreamingResponse(pooled_stream(), media_type=media)
 
         if req.stream:
             async def audio_stream():                                                 # openai_api.py:259-274

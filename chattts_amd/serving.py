@@ -54,6 +54,9 @@ class _Req:
     row_offset: int = 0
     total_rows: int = GPT.n_vq
     emb: Optional[torch.Tensor] = None         # [T, 768] prompt embedding (speaker applied), or None: embedded at admission
+    stream: Optional["StreamSpec"] = None      # a streamed request: its chunk schedule (run(events=True))
+    cursor: Optional["StreamCursor"] = None    # where that schedule stands (fresh at every admission)
+    cancelled: bool = False                    # cancel(rid): retired at the next poll, nothing is handed out
 
 
 # InferCodeParams' sampling fields and their defaults (core.py:48-64)
@@ -102,6 +105,82 @@ def sampling_row(p: RequestParams, rng_seed: int = 0, rng_per_step: bool = False
     r.rng_seed = int(rng_seed) & (2 ** 64 - 1)
     r.rng_per_step = int(bool(rng_per_step))
     return r
+
+
+@dataclass
+class StreamSpec:
+    """the streaming fields of a request's `InferCodeParams` (core.py:62-64)"""
+    stream_batch: int = 24
+    stream_speed: int = 12000
+    pass_first_n_batches: int = 2
+
+
+class StreamCursor:
+    """The chunk schedule of ONE streamed request, advanced by the token counts a pool reads at its polls.  It is the schedule
+    `GptEngine.generate(stream=True)` + the `stream` branch of `Chat._infer` produce for the request run alone as a batch of one:
+      * a yield at every multiple of `stream_batch` tokens the request reaches (generate yields there while the row is live), the
+        reference's duplicate yield when the row ends by EOS exactly on such a multiple (engine.py, "stream_iter quirk"), and
+        generate's final result, which passes through the same loop of `_infer`;
+      * the first `pass_first_n_batches` yields are dropped; every other one emits samples [length, length + stream_speed) of the
+        decode of the prefix of exactly that many tokens, clipped to its 256 (2 n - 1) samples, and moves `length` to the clipped end;
+      * the tail: everything from `length` to the end of the full decode.
+    Every method returns the chunks that became due, in order: (prefix_tokens, s_lo, s_hi, is_tail).  A chunk may be empty
+    (s_lo == s_hi): the serial path yields an empty array there."""
+
+    def __init__(self, spec: StreamSpec):
+        if int(spec.stream_batch) < 1 or int(spec.stream_speed) < 0:
+            raise ValueError("stream_batch must be positive, stream_speed non-negative")
+        self.spec = spec
+        self.boundary = int(spec.stream_batch)     # the next token count at which a live request yields
+        self.yields = 0
+        self.length = 0                            # samples emitted so far
+
+    def _yield(self, prefix: int, out: list) -> None:
+        self.yields += 1
+        if self.yields <= int(self.spec.pass_first_n_batches):
+            return
+        s_hi = max(self.length, min(self.length + int(self.spec.stream_speed), 256 * (2 * prefix - 1)))
+        out.append((prefix, self.length, s_hi, False))
+        self.length = s_hi
+
+    def advance(self, count: int) -> list:
+        """the request is live and holds `count` tokens"""
+        out: list = []
+        while self.boundary <= count:
+            self._yield(self.boundary, out)
+            self.boundary += int(self.spec.stream_batch)
+        return out
+
+    def finish(self, n: int, eos: bool) -> list:
+        """the request ended with `n` tokens; `eos`: by its finish flag (EOS), not by max_new_token"""
+        if n <= 0:
+            return []                              # step 0 drew EOS: no audio, no chunks
+        out = self.advance(n)
+        if eos and n % int(self.spec.stream_batch) == 0:
+            self._yield(n, out)                    # the duplicate yield
+        self._yield(n, out)                        # generate's final result
+        out.append((n, self.length, 256 * (2 * n - 1), True))
+        return out
+
+
+def stream_schedule(counts, n: int, eos: bool, spec: StreamSpec) -> list:
+    """Pure host function: the token counts a streamed request showed at successive polls while live (`counts`), then its end (`n`
+    tokens, `eos`) -> every chunk of its stream, [(prefix_tokens, s_lo, s_hi, is_tail)].  The result does not depend on where the polls
+    fell (a boundary passed between two polls is served at the later one, from the prefix of exactly that many tokens)."""
+    cur = StreamCursor(spec)
+    out: list = []
+    for c in counts:
+        out += cur.advance(min(int(c), int(n)))
+    return out + cur.finish(int(n), bool(eos))
+
+
+class StreamEvents:
+    """what `SlotPool.run(events=True)` yields at a poll at which chunks of streamed requests became due: `chunks` = [(request id,
+    slot, prefix_tokens, s_lo, s_hi, is_tail)].  The consumer decodes them from `pool.hiddens` BEFORE it resumes the generator (rows
+    below a live slot's prefix are final; a finished slot is freed, and may be re-admitted, only after the generator resumes)."""
+
+    def __init__(self, chunks: list):
+        self.chunks = chunks
 
 
 class SlotPool:
@@ -234,14 +313,15 @@ class SlotPool:
 
     # -- request intake ---------------------------------------------------------------------------------------
     def submit(self, rid, input_ids, text_mask=None, max_new_token: int = 512, stop_at: int = -1, *, params=None, row_offset: int = 0,
-               total_rows: int = GPT.n_vq, emb: Optional[torch.Tensor] = None) -> None:
+               total_rows: int = GPT.n_vq, emb: Optional[torch.Tensor] = None, stream: Optional[StreamSpec] = None) -> None:
         """Queues one request.  Per-request pools only: `params` (an `InferCodeParams` or a dict of its sampling fields: temperature,
         top_P, top_K, repetition_penalty, min_new_token, manual_seed, ensure_non_empty), `row_offset` / `total_rows` (the request's
         sampling rows inside the batch whose tokens it must reproduce -- (0, 4): alone at batch 1, what `Chat.infer` does for one text),
         `emb` ([T, 768] prompt embedding with the speaker applied, `Chat.prompt_embedding`; None: the plain embedding of input_ids).
         The request then yields exactly the tokens `GptEngine.generate` yields for it alone with those arguments.  Step 0 follows
         generate's rule (gpt.py:527-570): a request whose first token is EOS yields no tokens (an empty result) -- unless it is unseeded
-        with `ensure_non_empty`, then it is generated again with a fresh draw."""
+        with `ensure_non_empty`, then it is generated again with a fresh draw.
+        `stream` (any pool): the request is streamed -- `run(events=True)` also yields its chunk events (StreamEvents)."""
         ids = torch.as_tensor(input_ids).to(torch.int64)
         assert ids.dim() == 2 and ids.shape[1] == GPT.n_vq
         tm = torch.ones(ids.shape[0], dtype=torch.bool) if text_mask is None else torch.as_tensor(text_mask).bool()
@@ -259,7 +339,22 @@ class SlotPool:
                 raise ValueError("emb must be [T, 768] for a [T, 4] prompt")
         elif params is not None or row_offset != 0 or total_rows != GPT.n_vq or emb is not None:
             raise ValueError("params / row_offset / total_rows / emb need SlotPool(per_request=True)")
-        self.queue.append(_Req(rid, ids, tm, int(max_new_token), int(stop_at), p, int(row_offset), int(total_rows), emb))
+        if stream is not None:
+            StreamCursor(stream)      # validates the spec
+        self.queue.append(_Req(rid, ids, tm, int(max_new_token), int(stop_at), p, int(row_offset), int(total_rows), emb, stream))
+
+    def cancel(self, rid) -> bool:
+        """Drops a request: a queued one leaves the queue, an admitted one is retired at the next poll (its finish flag is set, its slot
+        freed, nothing more is handed out for it).  False when the pool does not know the request (it completed already)."""
+        for r in self.queue:
+            if r.rid == rid:
+                self.queue.remove(r)
+                return True
+        for r, _, _ in self.active.values():
+            if r.rid == rid:
+                r.cancelled = True
+                return True
+        return False
 
     def _admit_rows(self, slots: List[int], reqs: List[_Req], sl: torch.Tensor) -> None:
         """per-request pools: the admitted slots' sampling table entries, global sampling rows and Exp(1) rows (stream-ordered)"""
@@ -331,6 +426,7 @@ class SlotPool:
             self._keep = (ws, emb, rmap, sl)  # stream-ordered: stay alive until the next poll's sync, no extra sync here
         since = getattr(self, "_snap_seq", 0)      # snapshots enqueued before this admission still show the previous occupant
         for s_, r in zip(slots, reqs):
+            r.cursor = StreamCursor(r.stream) if r.stream is not None else None
             self.active[s_] = (r, Tg, since)
             self.slot_of[r.rid] = s_
 
@@ -346,14 +442,18 @@ class SlotPool:
         self._snap_seq += 1
         return self._snap_seq - 1, blk, ev
 
-    def run(self, between=None, grouped: bool = False) -> Iterator:
+    def run(self, between=None, grouped: bool = False, events: bool = False) -> Iterator:
         """Yields (request id, ids [n,4] int64, hiddens [n,768] float32) as requests complete, admitting queued
         requests into freed slots between decode chunks.  ONE chunk runs ahead: the next POLL steps are enqueued before the host
         looks at the previous chunk's flags, so the device never waits for the poll, the admission prefill or the result copies
         (a freed slot idles for at most two chunks instead of one).  A slot's entry only listens to snapshots enqueued after its
         admission -- an older one still shows the previous occupant's flag.  `between` (optional callable): called once per chunk, before
         admission -- a server submits newly arrived requests there and lets other GPU users in (SpeechBatcher).  `grouped=True`: yields
-        instead ONE list of those triples per poll -- the requests that completed together (SpeechBatcher's ragged decode)."""
+        instead ONE list of those triples per poll -- the requests that completed together (SpeechBatcher's ragged decode).
+        `events=True`: at a poll at which chunks of streamed requests (`submit(stream=...)`) became due, a `StreamEvents` is yielded
+        first -- at once, not one chunk later like the results: the consumer decodes the chunks from `self.hiddens` while the generator
+        is suspended, so a finished slot's rows are still its own (the slot is freed, and re-admitted, only after the generator resumes;
+        the device meanwhile runs the chunk that was enqueued ahead)."""
         pending: Deque = deque()
         ready: Deque = deque()      # (event behind the result copies, results) of the previous poll
         while self.queue or self.active or pending:
@@ -376,7 +476,25 @@ class SlotPool:
             wait_event(ev)        # polled, not an interrupt wait (chattts_amd/_sync.py)
             fin = blk[: self.S]
             end = blk[self._Sp:].view(torch.int32)[: self.S]
+            gone = [s for s, (r, _, _) in self.active.items() if r.cancelled]
+            if gone:                  # cancel(rid): the slot stops computing and is free for the next admission
+                with torch.cuda.stream(self.st):
+                    for s in gone:
+                        self.active.pop(s)
+                        self.finish[s] = 1
+                self.free.extend(gone)
+                self.free.sort()
             done = [s for s, (r, _, since) in self.active.items() if seq >= since and (bool(fin[s]) or int(end[s]) >= r.max_new)]
+            if events:
+                chunks = []
+                for s, (r, _, since) in self.active.items():
+                    if r.cursor is None or seq < since:
+                        continue
+                    n = min(int(end[s]), r.max_new)
+                    due = r.cursor.finish(n, bool(fin[s]) and int(end[s]) < r.max_new) if s in done else r.cursor.advance(n)
+                    chunks += [(r.rid, s, *c) for c in due]
+                if chunks:
+                    yield StreamEvents(chunks)
             if not done:
                 continue
             outs = []
@@ -413,6 +531,39 @@ class SlotPool:
             yield outs
 
 
+class _Cancel:
+    def __init__(self, rid):
+        self.rid = rid
+
+
+class SpeechStream:
+    """`SpeechBatcher.submit_stream`'s result: an iterator over one streamed request's int16 chunks, fed by the worker through a
+    thread-safe queue.  It ends when the request is complete; an error (an empty result too) is raised from `next`.  `close()` before
+    the end cancels the request: its slot is retired at the pool's next poll."""
+
+    def __init__(self, batcher: "SpeechBatcher", rid):
+        self._b, self.rid, self._q, self._done = batcher, rid, queue.Queue(), False
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> np.ndarray:
+        if self._done:
+            raise StopIteration
+        item = self._q.get()
+        if item is None or isinstance(item, BaseException):
+            self._done = True
+            if item is None:
+                raise StopIteration
+            raise item
+        return item
+
+    def close(self) -> None:
+        if not self._done:
+            self._done = True
+            self._b._in.put(_Cancel(self.rid))
+
+
 class SpeechBatcher:
     """Serves many non-streamed speech requests from ONE per-request slot pool (continuous batching behind `server.create_app(...,
     batch_slots=N)`).  A single worker thread owns the pool and all GPU work of pooled requests: requests arrive through a thread-safe
@@ -425,17 +576,28 @@ class SpeechBatcher:
     An error in one request fails that request's Future only (an empty result -- step 0 drew EOS -- too).  `decode_calls` counts the
     decodes, `decoded` the requests they served, `max_decode_group` the most requests one decode served.
 
+    `streams=True`: `submit_stream` serves streamed requests from the same pool.  The chunks of all streams that are due at one poll
+    are decoded by ONE window decode straight from the pool's hidden-state store (`Chat.decode_windows_pcm16` ->
+    `CodecEngine.decode_windows`), each what the serial streamed path yields for that request; `stream_decode_calls` counts those
+    decodes, `stream_chunks` the chunks they served, `max_stream_group` the most one decode served.
+
     `make_pool` (tests: a fake) builds the pool; by default a per-request SlotPool on `chat.gpt` with the engine's generator mode,
     `cap` = the engine's position limit (the longest accepted prompt + max_new_token 2048 + slack), `hid_cap` 2048."""
 
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
-                 logger=None, ragged_decode: bool = False):
+                 logger=None, ragged_decode: bool = False, streams: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
         self.decode_calls = 0        # decoder passes over finished requests
         self.decoded = 0             # requests those passes served
         self.max_decode_group = 0    # most requests one pass served
+        self.streams = bool(streams)
+        self.stream_decode_calls = 0  # window decodes over the due chunks of streamed requests
+        self.stream_chunks = 0        # chunks those decodes served (empty chunks included)
+        self.max_stream_group = 0     # most chunks one window decode served
+        self.cancelled = 0            # streams closed by their consumer before the end
+        self._streams: dict = {}      # request id -> SpeechStream
         self.log = logger or logging.getLogger("chattts_amd.serving")
         self._in: "queue.Queue" = queue.Queue()
         self._futs: dict = {}
@@ -464,7 +626,22 @@ class SpeechBatcher:
         self._in.put((next(self._ids), text, params, fut))
         return fut
 
+    def submit_stream(self, text: str, params) -> SpeechStream:
+        """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
+        params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request."""
+        if not self.streams:
+            raise RuntimeError("this SpeechBatcher was built without streams=True")
+        h = SpeechStream(self, next(self._ids))
+        self._in.put((h.rid, text, params, h))
+        return h
+
     def occupancy(self) -> dict:
+        if self.streams:
+            return {**self._occupancy(), "streams": len(self._streams), "stream_decode_calls": self.stream_decode_calls,
+                    "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled}
+        return self._occupancy()
+
+    def _occupancy(self) -> dict:
         return {"slots": self.S, "active": len(getattr(self.pool, "active", {})), "queued": self._in.qsize() + len(getattr(self.pool, "queue", ())),
                 "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed,
                 "ragged_decode": self.ragged_decode, "decode_calls": self.decode_calls, "decoded": self.decoded,
@@ -481,18 +658,27 @@ class SpeechBatcher:
         fut = self._futs.pop(rid, None)
         if fut is not None and not fut.done():
             fut.set_exception(e)
+        h = self._streams.pop(rid, None)
+        if h is not None:
+            h._q.put(e)
 
     def _take(self, item) -> None:
         """prompt of one request -> pool.submit (worker thread, GPU lock held)"""
         rid, text, params, fut = item
-        self._futs[rid] = fut
+        kw = {}
+        if isinstance(fut, SpeechStream):
+            self._streams[rid] = fut
+            kw["stream"] = StreamSpec(int(params.stream_batch), int(params.stream_speed), int(params.pass_first_n_batches))
+        else:
+            self._futs[rid] = fut
         try:
             chat = self.chat
             t = chat.normalizer(text, True, True, None)             # what Chat._infer does with do_text_normalization / homophones
             ids, attn, tmask = chat.code_prompt([t], params)
             emb = chat.prompt_embedding(ids, tmask, params, chat.tokenizer.spk_emb_ids)
             keep = attn[0].bool()
-            self.pool.submit(rid, ids[0][keep], tmask[0][keep], max_new_token=params.max_new_token, params=params, emb=emb[0][keep.to(emb.device)])
+            self.pool.submit(rid, ids[0][keep], tmask[0][keep], max_new_token=params.max_new_token, params=params, emb=emb[0][keep.to(emb.device)],
+                             **kw)
             self.admissions += 1
         except Exception as e:        # this request's error, not the worker's
             self._fail(rid, e)
@@ -508,7 +694,47 @@ class SpeechBatcher:
                 return False
             block = False
             with self.lock:
-                self._take(item)
+                if isinstance(item, _Cancel):
+                    self._cancel(item.rid)
+                else:
+                    self._take(item)
+
+    def _cancel(self, rid) -> None:
+        h = self._streams.pop(rid, None)
+        if h is not None:
+            self.cancelled += 1
+            self.pool.cancel(rid)
+            h._q.put(None)
+
+    def _serve_chunks(self, ev: StreamEvents) -> None:
+        """the chunks of one poll: ONE window decode, every piece to its own stream's queue"""
+        live = [c for c in ev.chunks if c[0] in self._streams]
+        if not live:
+            return
+        try:
+            if any(c[4] > c[3] for c in live):
+                self.stream_decode_calls += 1
+                self.max_stream_group = max(self.max_stream_group, len(live))
+            self.stream_chunks += len(live)
+            pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live])
+        except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
+            for rid in {c[0] for c in live}:
+                self.pool.cancel(rid)
+                self._fail(rid, e)
+            return
+        for c, pcm in zip(live, pieces):
+            self._streams[c[0]]._q.put(pcm)
+
+    def _end_stream(self, rid, hid) -> None:
+        h = self._streams.pop(rid, None)
+        if h is None:
+            return
+        if hid.shape[0] == 0:
+            self.failed += 1
+            h._q.put(RuntimeError("the engine returned no audio (the first token was EOS)"))
+        else:
+            self.completed += 1
+            h._q.put(None)
 
     def _between(self):
         self.max_coresident = max(self.max_coresident, len(self.pool.active))
@@ -559,7 +785,10 @@ class SpeechBatcher:
                 continue
             self.lock.acquire()
             try:
-                it = self.pool.run(between=self._between, grouped=True) if self.ragged_decode else self.pool.run(between=self._between)
+                if self.streams:
+                    it = self.pool.run(between=self._between, grouped=self.ragged_decode, events=True)
+                else:
+                    it = self.pool.run(between=self._between, grouped=True) if self.ragged_decode else self.pool.run(between=self._between)
                 while True:
                     try:
                         got = next(it)
@@ -567,13 +796,18 @@ class SpeechBatcher:
                         break
                     except Exception as e:     # the pool itself failed: the requests in it fail, a fresh pool serves the next ones
                         self.log.error("slot pool failed: %s", e)
-                        for r in list(self._futs):
+                        for r in [*self._futs, *self._streams]:
                             self._fail(r, e)
                         close = getattr(self.pool, "close", None)
                         if close is not None:
                             close()
                         self.pool = self._make_pool()
                         break
+                    if isinstance(got, StreamEvents):
+                        self._serve_chunks(got)
+                        continue
+                    for rid, _, hid in (got if self.ragged_decode else [got]):     # a stream's result: its chunks went out already
+                        self._end_stream(rid, hid)
                     if self.ragged_decode:
                         group = [(rid, hid) for rid, _, hid in got if rid in self._futs]
                         try:

@@ -354,6 +354,31 @@ int ctts_vocos_decode_ragged(ctts_codec* c, const float* mel, const int32_t* tok
 int ctts_float_to_int16_ragged(const float* wav, int16_t* pcm, uint8_t* keep_bits, const int64_t* off_dev, const int64_t* off_host,
                                int32_t n_seg, int32_t product, float keep_thr, uint32_t* peak, void* stream);
 
+/* Window decode: the chunks of many streamed utterances that are due at one poll, in ONE ragged pass, each at its own position.
+ * hid: a hidden-state store [n_slots][hid_cap][768] float32 (a slot pool's; slot_stride / row_stride in floats, multiples of 4, rows 16-byte
+ * aligned).  A window is token rows [t_lo, t_hi) of one slot; it is decoded as one ragged segment -- its edges are sequence edges -- and
+ * samples [c_lo, c_hi) of that decode, counted from the window's first sample (sample 512 t_lo of the slot's own decode), are emitted.
+ *   out_type 0: float32 (the crop alone); 1: int16, ctts_float_to_int16's arithmetic (`product` as there) with ONE peak per window, taken
+ *   over the cropped samples only.
+ * out: window i's c_hi - c_lo samples from element out_off[i] = sum_{j<i} ceil8(c_hi_j - c_lo_j) on (every window starts on a multiple of 8
+ * samples; the pad samples are zeros), so one copy of sum_i ceil8(n_i) elements delivers every chunk.  keep_bits (may be NULL when no window
+ * sets .keep): for a window with .keep != 0 -- a stream's last chunk -- its mask |x| > keep_thr in np.packbits order from byte out_off[i] / 8
+ * on (the layout of ctts_float_to_int16_ragged's masks); other windows' bytes are not written.
+ * win_dev / win_host: the same n_win entries on the device (read by the kernels) and on the host (sizes and the checks: an empty window, a
+ * slot outside the store, t_hi beyond hid_cap, an empty crop or one outside the window's 256 (2 (t_hi - t_lo) - 1) samples are refused before
+ * anything is launched).  Stream-ordered on `stream`: one gather launch, the ragged DVAE and Vocos stages, one crop / conversion launch. */
+typedef struct {
+  int32_t slot;          /* slot of the store */
+  int32_t t_lo, t_hi;    /* token rows [t_lo, t_hi) of that slot */
+  int32_t c_lo, c_hi;    /* samples to emit, relative to the window's first sample */
+  int32_t keep;          /* != 0: also write this window's keep mask */
+  int32_t reserved[2];
+} ctts_window;           /* 32 bytes */
+size_t ctts_codec_windows_workspace_bytes(int32_t n_win, int32_t total_tokens);   /* 0 when n_win < 1 or total_tokens < n_win */
+int ctts_codec_decode_windows(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots, int32_t hid_cap,
+                              const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win, int32_t out_type, void* out,
+                              uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Full DVAE (asset/DVAE.safetensors): audio -> 4 x T codes and codes -> mel through the GFSQ codebook.
  * Replaces `self.dvae(wav, "encode")` of `Chat.sample_audio_speaker` (ChatTTS/core.py:179-180 ->

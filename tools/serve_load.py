@@ -2,7 +2,12 @@
 batching (`create_app(..., batch_slots=S)`) and once without, plus the sampling kernel's cost in a per-request pool vs a plain pool.
 Prints one JSON line.  Not a bench.py leg.
 
-    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode]
+    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R]]
+
+--stream: instead, N concurrent STREAMED requests against the batching app with `batch_streams` off (streams served one after the
+other, each a batch of one) and on (streams share the slot pool, the chunks due at one poll come from one window decode): per request
+the time to the first audio byte and the total time, p50 / p95, and audio-s/s; then one streamed request alone on both (--repeat runs
+each, off and on alternating: the single-stream time to first byte and its run-to-run spread).  --ragged-decode composes.
 
 --ragged-decode: also the batched burst with `create_app(..., ragged_decode=True)` (the requests that finish in one poll decoded in one
 ragged pass) -- an A/B against the default batched burst (one decode per request), with both runs' decode-call counts.
@@ -71,6 +76,76 @@ def burst(chat, voices, n, batch_slots, ragged_decode=False, counts=False):
     return out
 
 
+def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app=None):
+    """n concurrent streamed requests, driven through the ASGI interface on one event loop (a test client would hand the body over only
+    once it is complete): the clock of a request stops at its first body message that carries audio, and at its last message"""
+    import asyncio
+    own = app is None
+    if own:
+        app = server.create_app(chat, voices, batch_slots=slots, ragged_decode=ragged_decode, batch_streams=batch_streams)
+    names = sorted(voices)
+
+    async def one(i, text, out):
+        body = json.dumps({"input": text, "voice": names[i % len(names)], "response_format": "pcm", "stream": True}).encode()
+        scope = dict(type="http", asgi={"version": "3.0"}, http_version="1.1", method="POST", path="/v1/audio/speech", raw_path=b"/v1/audio/speech",
+                     query_string=b"", root_path="", scheme="http", server=("load", 80), client=("load", 1),
+                     headers=[(b"content-type", b"application/json"), (b"content-length", str(len(body)).encode())])
+        sent = [False]
+
+        async def receive():
+            if not sent[0]:
+                sent[0] = True
+                return {"type": "http.request", "body": body, "more_body": False}
+            await asyncio.sleep(3600)
+            return {"type": "http.disconnect"}
+        t0 = time.perf_counter()
+
+        async def send(msg):
+            if msg["type"] == "http.response.start":
+                out["status"] = msg["status"]
+            elif msg["type"] == "http.response.body" and msg.get("body"):
+                out.setdefault("first_s", time.perf_counter() - t0)
+                out["bytes"] = out.get("bytes", 0) + len(msg["body"])
+        await app(scope, receive, send)
+        out["total_s"] = time.perf_counter() - t0
+
+    async def run(texts):
+        outs = [dict() for _ in texts]
+        t0 = time.perf_counter()
+        await asyncio.gather(*[one(i, t, outs[i]) for i, t in enumerate(texts)])
+        return outs, time.perf_counter() - t0
+    asyncio.run(run(["Warm up."]))                                 # first-call costs out of the burst
+    outs, wall = asyncio.run(run([TEXTS[i % len(TEXTS)] for i in range(n)]))
+    pool = app.state.batcher.occupancy() if app.state.batcher is not None else {}
+    if own and app.state.batcher is not None:
+        app.state.batcher.close()
+    first = [o.get("first_s", float("nan")) for o in outs]
+    total = [o["total_s"] for o in outs]
+    audio = sum(o.get("bytes", 0) for o in outs) / 2 / server.SAMPLE_RATE
+    pct = lambda v, q: round(float(np.percentile(v, q)), 4)
+    out = dict(failed=sum(o.get("status") != 200 or "first_s" not in o for o in outs), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3),
+               audio_s=round(audio, 2), first_byte_p50_s=pct(first, 50), first_byte_p95_s=pct(first, 95), total_p50_s=pct(total, 50),
+               total_p95_s=pct(total, 95))
+    for k in ("max_coresident", "stream_decode_calls", "stream_chunks", "max_stream_group", "decode_calls"):
+        if k in pool:
+            out[k] = pool[k]
+    return out
+
+
+def stream_main(chat, voices, a):
+    off = stream_burst(chat, voices, a.n, a.slots, False, a.ragged_decode)
+    on = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode)
+    single = {"off": [], "on": []}
+    for _ in range(a.repeat):                                      # one stream alone, the two legs alternating
+        for name, flag in (("off", False), ("on", True)):
+            single[name].append(stream_burst(chat, voices, 1, a.slots, flag, a.ragged_decode)["first_byte_p50_s"])
+    print(json.dumps(dict(metric="serve_load_stream", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, ragged_decode=a.ragged_decode,
+                          batch_streams_off=off, batch_streams_on=on,
+                          first_byte_p50_ratio=round(off["first_byte_p50_s"] / on["first_byte_p50_s"], 2),
+                          audio_rate_ratio=round(on["audio_s_per_s"] / off["audio_s_per_s"], 2),
+                          single_stream_first_byte_s=single)))
+
+
 def sample_k_ms(eng, per_request, slots, steps=64):
     """mean sample_k time (profile tag 9) over `steps` eager decode steps of a full pool of identical requests"""
     pool = SlotPool(eng, slots=slots, cap=512, hid_cap=256, manual_seed=42, per_request=per_request)
@@ -98,6 +173,8 @@ def main():
     ap.add_argument("--max-new", type=int, default=256)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--ragged-decode", action="store_true", help="A/B: also the batched burst with one ragged decode per poll")
+    ap.add_argument("--stream", action="store_true", help="streamed requests: batch_streams off vs on")
+    ap.add_argument("--repeat", type=int, default=5, help="--stream: single-stream runs per leg (run-to-run spread)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     gold = os.path.join(ROOT, "tests", "golden")
@@ -109,6 +186,8 @@ def main():
     voices = {"default": chat.sample_random_speaker(), "alloy": chat.sample_random_speaker(), "echo": chat.sample_random_speaker()}
     orig = chat.InferCodeParams
     chat.InferCodeParams = lambda **kw: orig(**{**kw, "max_new_token": a.max_new})
+    if a.stream:
+        return stream_main(chat, voices, a)
     serial = burst(chat, voices, a.n, None)
     batched = burst(chat, voices, a.n, a.slots, counts=a.ragged_decode)
     extra = {}
