@@ -456,11 +456,23 @@ class Chat:
 
     def _refine_text(self, text, device, params: RefineTextParams) -> GenerationOutputs:
         """core.py:665-751"""
+        ids, attn, tmask = self.refine_prompt(text, params)
+        return self.refine_text_ids(ids, attn, tmask, self.tokenizer.eos_token, params, num_code=self.tokenizer.len)
+
+    def refine_prompt(self, text, params: RefineTextParams):
+        """decorate -> tokenise of ALREADY NORMALISED texts for the refine-text pass (the head of `_refine_text`): (input_ids [B,T,4], attention_mask
+        [B,T], text_mask [B,T]).  `Chat.infer` and the batched server's refine stage (serving.SpeechBatcher) both build their prompts here."""
         self._need_tokenizer()
         if not isinstance(text, list):
             text = [text]
-        ids, attn, tmask = self.tokenizer.encode(Speaker.decorate_text_prompts(text, params.prompt), GPT.n_vq)
-        return self.refine_text_ids(ids, attn, tmask, self.tokenizer.eos_token, params, num_code=self.tokenizer.len)
+        return self.tokenizer.encode(Speaker.decorate_text_prompts(text, params.prompt), GPT.n_vq)
+
+    def refined_text(self, rows) -> List[str]:
+        """refined token rows -> the texts of the code pass (what `_infer` does with them): control tokens >= [break_0] dropped, then decoded.  Shared
+        by `_infer` and the batched server's hand-off from the text pool to the code pool."""
+        self._need_tokenizer()
+        tokens = [row[row.less(self.tokenizer.break_0_ids)] for row in rows]
+        return self.tokenizer.decode(tokens)
 
     def infer(self, text, stream=False, lang=None, skip_refine_text=False, refine_text_only=False, use_decoder=True,
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
@@ -512,8 +524,7 @@ class Chat:
         text = [self.normalizer(t, do_text_normalization, do_homophone_replacement, lang) for t in text]
         if not skip_refine_text:
             refined = self._refine_text(text, self.device, params_refine_text)
-            tokens = [row[row.less(self.tokenizer.break_0_ids)] for row in refined.ids]   # control tokens >= [break_0] dropped
-            text = self.tokenizer.decode(tokens)
+            text = self.refined_text(refined.ids)     # control tokens >= [break_0] dropped, decoded
             refined.destroy()
             if refine_text_only:
                 yield "\n".join(text) if (split_text and isinstance(text, list)) else text

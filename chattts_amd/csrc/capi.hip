@@ -277,8 +277,6 @@ static int check_state(const ctts_gpt* g, const ctts_gen_state* s, int ws_T = 0)
   if (s->workspace_bytes < ctts_gpt_workspace_bytes(s->B, ws_T > 0 ? ws_T : s->T)) return fail("workspace too small");
   if (!s->rng_device && (s->nq <= 0 || !s->q)) return fail("q draws missing");
   if (s->rng_device && !s->rng_seed && !s->row_sampling) return fail("rng_device needs the rng_seed device scalar (or row_sampling)");
-  if (s->row_sampling && s->infer_text) return fail("row_sampling serves the code mode only");
-  if (s->rng_device && s->infer_text) return fail("the device generator serves the code mode only (refine-text samples from `q`)");
   if (g->w.weight_dtype == CTTS_BF16 && g->w.kv_dtype != CTTS_BF16) return fail("perf mode needs a bf16 KV cache");
   if (s->infer_text) {
     if (!g->w.emb_text || !g->w.head_text || g->w.n_text <= 0 || g->w.n_text > NTEXT_MAX) return fail("text head/embedding not loaded");

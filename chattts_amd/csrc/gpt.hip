@@ -2032,7 +2032,34 @@ __global__ __launch_bounds__(TEXT_NT) void sample_text_k(SampleArgs a, int V) {
   }
   const int gen = len - (a.prompt_len ? a.prompt_len[b] : a.T);
   const float* lrow = a.logits + (size_t)m * V;
-  const float temp = a.temperature[0];
+  // sampling parameters: call-wide, or this utterance slot's row of the per-slot table (ctts_gen_state.row_sampling), read like sample_k
+  // reads it: through the constant address space with a block-uniform slot index, so the scalars arrive by s_load in this first load
+  // round, next to the logits loads; with rows == null (a uniform kernel argument) the table is never touched.  The text mode has no
+  // repetition penalty: use_penalty / pow_table of a row are not read (the host refuses a row that sets them).
+  float temp, thr;
+  int use_top_p, top_k, use_top_k, min_new, per_step;
+  unsigned long long seed;
+  bool nonce;
+  if (a.rows != nullptr) {
+    const int bu = __builtin_amdgcn_readfirstlane(b);
+    const __attribute__((address_space(4))) SamplingRow* r = (const __attribute__((address_space(4))) SamplingRow*)(a.rows + bu);
+    temp = r->temperature[0];
+    thr = r->top_p_thr; use_top_p = r->use_top_p; top_k = r->top_k; use_top_k = r->use_top_k; min_new = r->min_new;
+    per_step = r->rng_per_step;
+    seed = a.rng_device ? r->rng_seed : 0ull;
+    nonce = per_step != 0 && a.rng_nonce != nullptr;   // unseeded row: the per-admission fourth word; seeded row: the constant word
+  } else {
+    temp = a.temperature[0];
+    thr = a.top_p_thr; use_top_p = a.use_top_p; top_k = a.top_k; use_top_k = a.use_top_k; min_new = a.min_new;
+    per_step = a.rng_per_step;
+    seed = a.rng_device ? *a.rng_seed : 0ull;
+    nonce = a.rng_nonce != nullptr;
+  }
+  // global sampling row: ONE per utterance in this mode (gpt.py:439-440); the device generator is keyed on it, the host draws stay
+  // indexed by slot
+  const int grow = a.row_base != nullptr ? a.row_base[b] : a.row_offset + b;
+  const uint32_t w3 = (a.rng_device && nonce) ? a.rng_nonce[b] : CTTS_RNG_WORD3;
+  const int dstep = per_step ? gen : 0;     // device generator: the step word (a seeded row draws the same tensor every step)
   const bool cert = a.margin != nullptr;
   TSTAMP(1);   // row known
 
@@ -2061,16 +2088,15 @@ __global__ __launch_bounds__(TEXT_NT) void sample_text_k(SampleArgs a, int V) {
   sall = block_sumNd(sall, red, wave, lane);
   TSTAMP(3);   // softmax statistics
 
-  const int kk = a.use_top_k ? min(max(a.top_k, 3), V) : V;
-  const float thr = a.top_p_thr;
-  const bool any_filter = a.use_top_p || a.use_top_k;
+  const int kk = use_top_k ? min(max(top_k, 3), V) : V;
+  const bool any_filter = use_top_p || use_top_k;
   float v_last = INFINITY; int i_last = -1, n_kept = 0;
   float c_cut = INFINITY, c_p = INFINITY;
   bool done = !any_filter;
   bool fast = false;                     // the kept set was found on the candidate list: (cand_rank, cand_val, cand_idx) of this thread's candidate
   int cand_rank = 0x7fffffff, cand_idx = 0x7fffffff;
   float cand_val = -INFINITY;
-  if (any_filter && a.use_top_k && kk <= 64) {
+  if (any_filter && use_top_k && kk <= 64) {
     // threshold: the kk-th largest of the 64 COLUMN maxima (column l = lane l of every wave, 16 x 21 elements).  kk columns hold an
     // element >= t, so {x >= t} contains the prefix -- and only ~1.2 kk candidates survive (the kk-th largest thread maximum of ONE wave,
     // a 1/16 sample of the row, left ~370 of them, and ranking those by counting was 38 of the kernel's 50 us: profiles/r6g_text_phase.log)
@@ -2126,16 +2152,16 @@ __global__ __launch_bounds__(TEXT_NT) void sample_text_k(SampleArgs a, int V) {
       __syncthreads();
       const float kth_val = sh_f[0];
       const float cum = (float)(sall - mass_above);   // ascending cumulative probability including itself
-      const bool ok_p = !(a.use_top_p && rank >= 3 && cum <= thr);
+      const bool ok_p = !(use_top_p && rank >= 3 && cum <= thr);
       const bool ok_k = rank < kk || cv == kth_val;   // ties with the k-th largest value survive
       const int n = block_minNi((act && !(ok_p && ok_k)) ? rank : C, red, wave, lane);   // >= 3 (min_tokens_to_keep)
       if (act && rank == n - 1) {
         sh_f[1] = cv; sh_i[0] = ci;
-        if (a.use_top_p && rank >= 3) sh_f[3] = fabsf(__logf(fmaxf(cum, 1e-38f) / thr));
+        if (use_top_p && rank >= 3) sh_f[3] = fabsf(__logf(fmaxf(cum, 1e-38f) / thr));
       }
       if (act && rank == n) {
         sh_f[2] = cv;
-        if (a.use_top_p && rank >= 3 && !ok_p) sh_f[4] = fabsf(__logf(fmaxf(cum, 1e-38f) / thr));
+        if (use_top_p && rank >= 3 && !ok_p) sh_f[4] = fabsf(__logf(fmaxf(cum, 1e-38f) / thr));
       }
       float bm = -INFINITY;   // every candidate kept: the first dropped value is the largest non-candidate
       if (cert && n == C) {
@@ -2171,11 +2197,11 @@ __global__ __launch_bounds__(TEXT_NT) void sample_text_k(SampleArgs a, int V) {
       float wv; int wi;
       block_argmaxN(bv, bi, red, wave, lane, wv, wi);
       float cum = INFINITY;
-      if (a.use_top_p && n >= 3) {
+      if (use_top_p && n >= 3) {
         cum = (float)(sall - mass_above);
         if (cum <= thr) { nxt = wv; cum_drop = cum; break; }
       }
-      if (a.use_top_k && n >= kk && !(wv == kth_val)) { nxt = wv; break; }
+      if (use_top_k && n >= kk && !(wv == kth_val)) { nxt = wv; break; }
       cum_last = cum;
       mass_above += (double)(expf(wv - mx) * rz);
       if ((wi & (TEXT_NT - 1)) == tid) taken |= 1u << (wi / TEXT_NT);
@@ -2185,19 +2211,20 @@ __global__ __launch_bounds__(TEXT_NT) void sample_text_k(SampleArgs a, int V) {
     }
     n_kept = n;
     if (cert) {
-      c_cut = (a.use_top_k && n > kk) ? 0.f : v_last - nxt;
+      c_cut = (use_top_k && n > kk) ? 0.f : v_last - nxt;
       if (cum_last < INFINITY) c_p = fabsf(__logf(fmaxf(cum_last, 1e-38f) / thr));
       if (cum_drop >= 0.f) c_p = fminf(c_p, fabsf(__logf(fmaxf(cum_drop, 1e-38f) / thr)));
     }
   }
 
-  bool mask_eos = gen < a.min_new;
+  bool mask_eos = gen < min_new;
   bool force_eos = false;
   if (a.stop_at != nullptr) {
     const int sa = a.stop_at[b];
     if (sa >= 0) { mask_eos = mask_eos || (gen < sa); force_eos = gen >= sa; }
   }
-  const float* qrow = a.q + ((size_t)(gen % a.nq) * a.q_rows + b) * V;
+  // host generator: this slot's row of the step's slab of `q`; device generator: no `q` memory is read at all
+  const float* qrow = a.rng_device ? nullptr : a.q + ((size_t)(gen % a.nq) * a.q_rows + b) * V;
   float wv; int wi;
   float c_arg = INFINITY;
   TSTAMP(4);   // kept set known
@@ -2208,7 +2235,14 @@ __global__ __launch_bounds__(TEXT_NT) void sample_text_k(SampleArgs a, int V) {
     // 40 of the kernel's 57 us, profiles/r6e_kernel_stats_text.csv).  Every other token has p = 0, hence p / q = 0 for any draw: it can only
     // win when every kept token's p / q underflowed to 0 too, and then the lowest index of the row (0) wins, as in the row-wide argmax.
     const bool live = cand_rank < n_kept && !(mask_eos && cand_idx == a.eos);
-    const float qj = live ? qrow[cand_idx] : 1.f;
+    float qj = 1.f;
+    if (live && a.rng_device != 0) {   // the draw of this thread's own candidate only: one Philox per kept candidate, not one per token of the row
+      float q4[4];
+      device_exp_draws4(seed, grow, dstep, cand_idx >> 2, q4, w3);
+      qj = q4[cand_idx & 3];
+    } else if (live) {
+      qj = qrow[cand_idx];
+    }
     const float m2 = block_maxN(live ? cand_val : -INFINITY, red, wave, lane);
     const float z2 = block_sumN(live ? expf(cand_val - m2) : 0.f, red, wave, lane);
     const float rz2 = 1.0f / z2;
@@ -2222,7 +2256,16 @@ __global__ __launch_bounds__(TEXT_NT) void sample_text_k(SampleArgs a, int V) {
   } else {
     float qv[TEXT_PER];
 #pragma unroll
-    for (int i = 0; i < TEXT_PER; ++i) { const int v = tid + TEXT_NT * i; qv[i] = (v < V) ? qrow[v] : 1.f; }   // one round trip
+    for (int i = 0; i < TEXT_PER; ++i) {
+      const int v = tid + TEXT_NT * i;
+      if (a.rng_device != 0) {   // the draws of this thread's 21 tokens, generated in registers (token v sits in group v / 4)
+        float q4[4];
+        device_exp_draws4(seed, grow, dstep, v >> 2, q4, w3);
+        qv[i] = (v < V) ? q4[v & 3] : 1.f;
+      } else {
+        qv[i] = (v < V) ? qrow[v] : 1.f;   // one round trip
+      }
+    }
 #define TEXT_LIVE(x_, v_) ((v_) < V && (!any_filter || (n_kept > 0 && ((x_) > v_last || ((x_) == v_last && (v_) <= i_last)))) && !(mask_eos && (v_) == a.eos))
     float m2 = -INFINITY;
 #pragma unroll

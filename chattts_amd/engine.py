@@ -452,7 +452,8 @@ class GptEngine:
                  profile_stride: int = 1, lanes: Optional[int] = None,
                  teacher_ids: Optional[torch.Tensor] = None, prefill_chunk: Optional[int] = None,
                  return_sampled: bool = False, rng: Optional[str] = None, rng_seed: Optional[int] = None,
-                 rng_nonce=None, row_ids: Optional[torch.Tensor] = None, exact: bool = False) -> Iterator[GenerationOutputs]:
+                 rng_nonce=None, row_ids: Optional[torch.Tensor] = None, exact: bool = False,
+                 text_rng: Optional[str] = None) -> Iterator[GenerationOutputs]:
         """Drop-in for `GPT.generate` (gpt.py:316-337), code mode.  Extra keyword-only arguments:
         `use_graph` (hipGraph replay of the decode step), `stop_at` ([B] int32 forced output lengths,
         benchmark hook), `row_offset`/`total_rows` (this shard's position inside a data-parallel batch:
@@ -471,7 +472,10 @@ class GptEngine:
         CPU generator call, uploaded (rng.py).  "device" draws them inside the sampling kernel (Philox4x32-10, counter = token / global
         row / step; the reference on a GPU device draws from the device generator too, gpt.py:39): with `manual_seed=None` -- the
         reference's DEFAULT -- that removes the ~2 ms per-step host draw + upload; the key is `rng_seed` or, if None, one draw from
-        torch's global CPU generator (so `torch.manual_seed` still makes a run repeatable).  Code mode only.  `rng_nonce` (device generator
+        torch's global CPU generator (so `torch.manual_seed` still makes a run repeatable).  Code mode only: a refine-text call
+        (`infer_text=True`) keeps the host stream whatever `rng` / `self.rng` say, unless `text_rng="device"` opts THAT call in (one
+        sampling row per utterance, a seeded call draws with step word 0 as in code mode; what a text-mode slot pool with the device
+        generator draws, serving.SlotPool(infer_text=True)).  `rng_nonce` (device generator
         only; an int or one int per utterance): the fourth word of the generator's counter instead of its constant -- a slot pool gives
         every admission its own (serving.SlotPool), and passing a request's number here reproduces that request in isolation.
         `row_ids` ([B] ints, with `total_rows`): the GLOBAL utterance index of every row of this call when they are not the contiguous
@@ -519,7 +523,10 @@ class GptEngine:
         rng_mode = rng or self.rng
         if rng_mode not in ("host", "device"):
             raise ValueError("rng must be 'host' or 'device'")
-        device_rng = rng_mode == "device" and not infer_text     # refine-text keeps the host stream
+        if text_rng not in (None, "host", "device"):
+            raise ValueError("text_rng must be 'host' or 'device'")
+        # refine-text keeps the host stream unless the call opts in
+        device_rng = (text_rng == "device") if infer_text else rng_mode == "device"
         dkey = (total_rows if total_rows is not None else B * nrow, V, manual_seed, row_offset, B * nrow, None if rid is None else tuple(rid.tolist()))
         if device_rng:
             draws = None
@@ -885,7 +892,7 @@ class GptEngine:
                                          use_graph=use_graph, stop_at=stop_at, row_offset=row_offset, total_rows=total_rows,
                                          profile_tag=profile_tag, profile_stride=profile_stride, lanes=lanes,
                                          teacher_ids=teacher_ids, prefill_chunk=prefill_chunk, return_sampled=return_sampled,
-                                         rng=rng, rng_seed=None, rng_nonce=rng_nonce, row_ids=row_ids, exact=exact)
+                                         rng=rng, rng_seed=None, rng_nonce=rng_nonce, row_ids=row_ids, exact=exact, text_rng=text_rng)
             return  # gpt.py:570: the seeded case yields nothing
 
         graph_ok = use_graph and max_new > 1
@@ -1004,12 +1011,12 @@ class GptEngine:
                     final = self._rerun_exact(final, unsafe, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token,
                                               logits_processors, infer_text, return_hidden, stream_batch, manual_seed, context, use_graph, stop_at,
                                               row_offset // nrow, (total_rows if total_rows is not None else B * nrow), prefill_chunk, rng,
-                                              seed_val if device_rng else None, rng_nonce, rid, rng_state0)
+                                              seed_val if device_rng else None, rng_nonce, rid, rng_state0, text_rng)
         yield final
 
     def _rerun_exact(self, final, rows, emb, inputs_ids, temperature, eos_token, attention_mask, max_new_token, min_new_token,
                      logits_processors, infer_text, return_hidden, stream_batch, manual_seed, context, use_graph, stop_at, first_row,
-                     total_rows, prefill_chunk, rng, rng_seed, rng_nonce, rid, rng_state0):
+                     total_rows, prefill_chunk, rng, rng_seed, rng_nonce, rid, rng_state0, text_rng=None):
         """The exact fallback of the certificate: utterances `rows` of the call once more, as a sub-batch with the same padded prompt
         geometry, on the f32 MFMA decode kernels, with the draws of their own global rows -- what the "f32" engine gives for them (utterances
         never interact) -- spliced over their rows of `final`."""
@@ -1030,7 +1037,7 @@ class GptEngine:
                                      None if attention_mask is None else attention_mask[sel.to(attention_mask.device)], max_new_token, min_new_token,
                                      logits_processors, infer_text, False, return_hidden, False, False, False, stream_batch, manual_seed, context,
                                      use_graph=use_graph, stop_at=None if stop_at is None else stop_at[sel.to(stop_at.device)], total_rows=total_rows,
-                                     lanes=1, prefill_chunk=prefill_chunk, rng=rng, rng_seed=rng_seed, rng_nonce=nz, row_ids=gid, exact=True):
+                                     lanes=1, prefill_chunk=prefill_chunk, rng=rng, rng_seed=rng_seed, rng_nonce=nz, row_ids=gid, exact=True, text_rng=text_rng):
                 pass
         finally:
             # where the global generator is left: the reference draws once per step of its loop, which ends when the LAST utterance

@@ -79,7 +79,8 @@ def _have_av() -> bool:
 
 
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
-               batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False):
+               batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
+               batch_refine: bool = False, refine_params=None):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -88,7 +89,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     instead of one decode per request (SpeechBatcher(ragged_decode=True)).  `batch_streams` (batching only; off: every path is as
     without it): a request with `"stream": true` joins the pool too (SpeechBatcher.submit_stream) instead of taking `model_lock` and
     running as a batch of one -- concurrent streams advance together, the chunks that are due at one poll come from one decoder pass,
-    and a client that goes away cancels its request."""
+    and a client that goes away cancels its request.  `batch_refine` (batching only; off: every path is as without it): a request body
+    may carry `"refine_text": true` -- the reference's default two-stage call: its text goes through the batcher's text-mode pool first
+    (SpeechBatcher(refine=True)), with `refine_params` (a `RefineTextParams`, or a callable returning one; default
+    `RefineTextParams(show_tqdm=False, manual_seed=42)`, a fixed seed like the code stage's), and the refined text is what is
+    synthesised.  It applies to the requests the pool serves (non-streamed ones, streamed ones with `batch_streams`); without
+    `batch_refine` the key is ignored with the "unsupported parameters" warning, like any unknown key."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -103,11 +109,21 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     gpu_lock = threading.Lock()                      # batching: the worker's chunks / decodes vs the streamed path's chunks
     if batcher is None and batch_slots is not None:
         from .serving import SpeechBatcher
-        batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode, streams=bool(batch_streams))
+        batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode, streams=bool(batch_streams),
+                                **({"refine": True} if batch_refine else {}))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
     pool_streams = bool(batch_streams) and batcher is not None and bool(getattr(batcher, "streams", False))
+    pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
+    allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set())
+
+    def refine_of(request_data):         # the refine stage's parameters of a request that asks for it, or None
+        if not (pool_refine and bool(request_data.get("refine_text", False))):
+            return None
+        if refine_params is None:
+            return chat.RefineTextParams(show_tqdm=False, manual_seed=42)
+        return refine_params() if callable(refine_params) else refine_params
 
     def locked_chunks(gen):
         """one chunk of a streamed response at a time under the GPU lock (batching on): the worker's chunks interleave with these"""
@@ -147,7 +163,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
     @app.post("/v1/audio/speech")
     async def speech(request_data: Dict):
-        unknown = set(request_data) - ALLOWED_PARAMS                                 # openai_api.py:130-138
+        unknown = set(request_data) - allowed                                 # openai_api.py:130-138
         if unknown:
             log.warning("ignoring unsupported parameters: %s", sorted(unknown))
         data = {k: request_data[k] for k in ALLOWED_PARAMS if k in request_data}
@@ -160,6 +176,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         if fmt not in formats:
             hint = " (mp3 / ogg need PyAV, which is not installed here)" if fmt in ("mp3", "ogg") else ""
             raise HTTPException(400, detail=f"Unsupported audio format: {fmt}, supported formats: {', '.join(sorted(formats))}{hint}")
+        refine = refine_of(request_data)
+        rkw = {} if refine is None else {"refine": refine}
+        if refine is not None and req.stream and not pool_streams:
+            log.warning("refine_text is served by the batched path only: ignored for a serially streamed request")
         media = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "ogg": "audio/ogg"}[fmt]
 
         def encode(pcm: np.ndarray, header: bool) -> bytes:
@@ -172,7 +192,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
         if req.stream and pool_streams:
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
-                chunks = batcher.submit_stream(req.input, code_params(req.voice))
+                chunks = batcher.submit_stream(req.input, code_params(req.voice), **rkw)
                 try:
                     first = True
                     async for chunk in iterate_in_threadpool(chunks):
@@ -205,7 +225,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
         if batcher is not None:
             try:
-                wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice)))]
+                wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:

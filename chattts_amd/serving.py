@@ -64,19 +64,39 @@ _PARAM_DEFAULTS = dict(temperature=0.3, top_P=0.7, top_K=20, repetition_penalty=
                        ensure_non_empty=True)
 
 
+# RefineTextParams' sampling fields and their defaults (core.py:33-44)
+_TEXT_PARAM_DEFAULTS = dict(temperature=0.7, top_P=0.7, top_K=20, repetition_penalty=1.0, min_new_token=0, manual_seed=None,
+                            ensure_non_empty=True)
+
+
 @dataclass
 class RequestParams:
-    """the sampling parameters of one pooled request, validated: `temperature` has one entry per codebook"""
+    """the sampling parameters of one pooled request, validated: `temperature` has one entry per codebook (text mode: one entry)"""
     temperature: Tuple[float, ...]
     plan: object             # engine.SamplingPlan
     min_new_token: int
     manual_seed: Optional[int]
     ensure_non_empty: bool
+    infer_text: bool = False
 
 
-def request_params(params=None) -> RequestParams:
+def request_params(params=None, infer_text: bool = False, num_code: int = GPT.n_text) -> RequestParams:
     """`params`: an `InferCodeParams`, a dict of its fields, or None (the defaults).  Validated the way `GptEngine.generate` validates
-    them (gen_logits -> plan_from_processors), so a pool refuses exactly what a plain call refuses."""
+    them (gen_logits -> plan_from_processors), so a pool refuses exactly what a plain call refuses.
+    `infer_text=True`: `params` is a `RefineTextParams` (or a dict of its fields) -- ONE temperature (the text mode has one sampling row per
+    utterance, core.py refine_text_ids), `gen_logits(num_code, ...)`, `plan_from_processors(..., infer_text=True)`: a text pool refuses
+    what `Chat.refine_text_ids` refuses (a repetition penalty other than 1 above all)."""
+    if infer_text:
+        get = ((lambda k: params.get(k, _TEXT_PARAM_DEFAULTS[k])) if isinstance(params, dict)
+               else (lambda k: getattr(params, k, _TEXT_PARAM_DEFAULTS[k])))
+        t = get("temperature")
+        temp = tuple(float(x) for x in t) if isinstance(t, (list, tuple)) else (float(t),)
+        if len(temp) != 1:
+            raise ValueError("refine-text mode takes one temperature (a scalar)")
+        warpers, procs = gen_logits(int(num_code), get("top_P"), get("top_K"), get("repetition_penalty"))
+        plan = plan_from_processors((*procs, *warpers), infer_text=True)
+        seed = get("manual_seed")
+        return RequestParams(temp, plan, int(get("min_new_token")), None if seed is None else int(seed), bool(get("ensure_non_empty")), True)
     get = (lambda k: params.get(k, _PARAM_DEFAULTS[k])) if isinstance(params, dict) else (lambda k: getattr(params, k, _PARAM_DEFAULTS[k]))
     t = get("temperature")
     temp = tuple(float(x) for x in t) if isinstance(t, (list, tuple)) else (float(t),) * GPT.n_vq   # core.py:558-561
@@ -90,6 +110,8 @@ def request_params(params=None) -> RequestParams:
 
 def sampling_row(p: RequestParams, rng_seed: int = 0, rng_per_step: bool = False) -> _lib.SamplingRow:
     """the ctts_sampling_row of one request: the values `GptEngine.generate` puts into the call-wide fields for the same parameters"""
+    if p.infer_text and p.plan.penalty is not None:     # (the sampling kernel's text mode never reads use_penalty / pow_table)
+        raise NotImplementedError("refine-text mode supports repetition_penalty = 1.0 only (reference default)")
     r = _lib.SamplingRow()
     for i, t in enumerate(p.temperature):
         r.temperature[i] = float(np.float32(t))
@@ -188,8 +210,8 @@ class SlotPool:
 
     def __init__(self, engine: GptEngine, slots: int = 64, cap: int = 1536, hid_cap: int = 1024, *, temperature=(0.3,) * 4,
                  top_P: Optional[float] = 0.7, top_K: Optional[int] = 20, repetition_penalty: float = 1.05, manual_seed: int = 42,
-                 min_new_token: int = 0, eos_token: int = GPT.n_audio - 1, rng: str = "host", rng_seed: Optional[int] = None,
-                 per_request: bool = False):
+                 min_new_token: int = 0, eos_token: Optional[int] = None, rng: str = "host", rng_seed: Optional[int] = None,
+                 per_request: bool = False, infer_text: bool = False):
         """`per_request=True`: the sampling keywords above are not used; every request brings its own (`submit(params=...)`), with
         the host generator each its own `manual_seed`; with the device generator seeded and unseeded requests share the pool (unseeded
         ones draw from `rng_seed` -- random if None -- with a fresh counter word per admission, `nonce_of[rid]`).
@@ -200,6 +222,20 @@ class SlotPool:
         if rng not in ("host", "device"):
             raise ValueError("rng must be 'host' or 'device'")
         self.per_request = bool(per_request)
+        # infer_text=True: a REFINE-TEXT pool (the generator in text mode, core.py refine_text_ids): prompts are [T, 4] text ids
+        # (replicated), requests bring `RefineTextParams`-shaped parameters, a sampling row is ONE per utterance (`row_offset` /
+        # `total_rows` count those), `eos_token` is the tokenizer's [Ebreak] and must be given, results are (rid, ids [n] int64, empty).
+        # No hidden states are kept: `hid_cap` is not used (the store is the one row per slot the C side writes through its bound check).
+        self.infer_text = bool(infer_text)
+        if self.infer_text:
+            if not self.per_request:
+                raise ValueError("a text-mode pool is a per-request pool: SlotPool(per_request=True, infer_text=True)")
+            if eos_token is None:
+                raise ValueError("a text-mode pool needs eos_token (tokenizer.eos_token, [Ebreak])")
+            hid_cap = 1
+        eos_token = GPT.n_audio - 1 if eos_token is None else int(eos_token)
+        self.nrow = 1 if self.infer_text else GPT.n_vq          # sampling rows per utterance (gpt.py:459-464 vs :439-440)
+        self.V = GPT.n_text if self.infer_text else GPT.n_audio
         if manual_seed is None and rng != "device" and not self.per_request:
             raise NotImplementedError("SlotPool with the host generator needs manual_seed (one constant Exp(1) draw per session); "
                                       "use rng='device' for unseeded sampling")
@@ -208,8 +244,11 @@ class SlotPool:
         self.eng, self.S, self.cap, self.hid_cap = engine, slots, cap, hid_cap
         self.lib = engine.lib
         dev = self.dev = engine.device
-        warpers, procs = gen_logits(GPT.n_audio - 1, top_P, top_K, repetition_penalty)
-        plan = plan_from_processors((*procs, *warpers))
+        if self.infer_text:
+            plan = plan_from_processors(())       # (per request: the call-wide fields are not read)
+        else:
+            warpers, procs = gen_logits(GPT.n_audio - 1, top_P, top_K, repetition_penalty)
+            plan = plan_from_processors((*procs, *warpers))
         h = C.c_void_p()
         _lib.check(self.lib.ctts_gpt_create(C.byref(h), C.byref(engine._w)), "ctts_gpt_create")
         self.handle = h
@@ -239,7 +278,7 @@ class SlotPool:
                 self.rows = torch.zeros((slots, C.sizeof(_lib.SamplingRow)), dtype=torch.uint8, device=dev)
                 self.row_base = torch.zeros((slots,), dtype=torch.int32, device=dev)
                 self.q = (torch.zeros((1,), dtype=torch.float32, device=dev) if self.device_rng else
-                          torch.ones((1, slots * nvq, GPT.n_audio), dtype=torch.float32, device=dev))   # host: each slot's rows at admission
+                          torch.ones((1, slots * self.nrow, self.V), dtype=torch.float32, device=dev))   # host: each slot's rows at admission
                 self.rng_seed = None
                 self.pool_seed = int(rng_seed) if rng_seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
                 self.rng_nonce = torch.zeros((slots,), dtype=torch.int32, device=dev) if self.device_rng else None
@@ -266,6 +305,8 @@ class SlotPool:
         self.dec = self._state(B=slots, T=1, workspace=self.ws, row_map=None, n_active=self.n_active)
         self.st.synchronize()
         _lib.check(self.lib.ctts_gpt_graph_build(self.handle, C.byref(self.dec), self.st.cuda_stream), "ctts_gpt_graph_build")
+        self._pending: Deque = deque()        # snapshots enqueued, not read yet (launch / poll)
+        self._ready: Deque = deque()          # (event behind the result copies, results) of the previous poll
         self.free: List[int] = list(range(slots))
         self.active: dict = {}                 # slot -> (_Req, Tg, first snapshot sequence number that reflects this request)
         self.queue: Deque[_Req] = deque()
@@ -303,7 +344,7 @@ class SlotPool:
         s.row_map, s.n_active = _lib.ptr(row_map), _lib.ptr(n_active)
         s.cap, s.hid_cap, s.kv_batch, s.q_batch = self.cap, self.hid_cap, self.S, self.S
         s.prompt_len = self.prompt_len.data_ptr()
-        s.infer_text = 0
+        s.infer_text = int(self.infer_text)
         s.rng_device, s.rng_per_step, s.rng_seed = int(self.device_rng), int(self.rng_per_step), _lib.ptr(self.rng_seed)
         s.rng_nonce = _lib.ptr(getattr(self, "rng_nonce", None))
         if self.per_request:
@@ -313,7 +354,7 @@ class SlotPool:
 
     # -- request intake ---------------------------------------------------------------------------------------
     def submit(self, rid, input_ids, text_mask=None, max_new_token: int = 512, stop_at: int = -1, *, params=None, row_offset: int = 0,
-               total_rows: int = GPT.n_vq, emb: Optional[torch.Tensor] = None, stream: Optional[StreamSpec] = None) -> None:
+               total_rows: Optional[int] = None, emb: Optional[torch.Tensor] = None, stream: Optional[StreamSpec] = None) -> None:
         """Queues one request.  Per-request pools only: `params` (an `InferCodeParams` or a dict of its sampling fields: temperature,
         top_P, top_K, repetition_penalty, min_new_token, manual_seed, ensure_non_empty), `row_offset` / `total_rows` (the request's
         sampling rows inside the batch whose tokens it must reproduce -- (0, 4): alone at batch 1, what `Chat.infer` does for one text),
@@ -321,20 +362,26 @@ class SlotPool:
         The request then yields exactly the tokens `GptEngine.generate` yields for it alone with those arguments.  Step 0 follows
         generate's rule (gpt.py:527-570): a request whose first token is EOS yields no tokens (an empty result) -- unless it is unseeded
         with `ensure_non_empty`, then it is generated again with a fresh draw.
-        `stream` (any pool): the request is streamed -- `run(events=True)` also yields its chunk events (StreamEvents)."""
+        `stream` (any pool): the request is streamed -- `run(events=True)` also yields its chunk events (StreamEvents).
+        Text-mode pools: `input_ids` are [T, 4] text ids (replicated), `params` a `RefineTextParams` (or a dict of its sampling fields),
+        `row_offset` / `total_rows` count one sampling row per utterance ((0, 1): alone at batch 1), the request yields the tokens
+        `GptEngine.generate(infer_text=True)` yields for it alone; no `emb`, no `stream` (a text row has no audio)."""
+        total_rows = self.nrow if total_rows is None else total_rows
         ids = torch.as_tensor(input_ids).to(torch.int64)
         assert ids.dim() == 2 and ids.shape[1] == GPT.n_vq
         tm = torch.ones(ids.shape[0], dtype=torch.bool) if text_mask is None else torch.as_tensor(text_mask).bool()
         # 2 * POLL positions of slack: a request that ends by max_new_token (no EOS) is retired by the HOST, up to two chunks late
-        if ids.shape[0] + max_new_token + 1 + 2 * self.POLL > self.cap or max_new_token > self.hid_cap:
+        if ids.shape[0] + max_new_token + 1 + 2 * self.POLL > self.cap or (max_new_token > self.hid_cap and not self.infer_text):
             raise ValueError("request does not fit a slot (prompt + max_new_token + 2 * POLL vs cap, max_new_token vs hid_cap)")
         p = None
         if self.per_request:
-            p = request_params(params)
+            p = request_params(params, infer_text=True) if self.infer_text else request_params(params)
+            if self.infer_text and (emb is not None or stream is not None):
+                raise ValueError("a text-mode pool takes token ids only (no emb, no stream)")
             if p.manual_seed is None and not self.device_rng:
                 raise NotImplementedError("a request without manual_seed needs a pool with the device generator (rng='device')")
-            if not (0 <= int(row_offset) and int(row_offset) + GPT.n_vq <= int(total_rows)):
-                raise ValueError("row_offset / total_rows: the request's 4 sampling rows must lie inside the batch")
+            if not (0 <= int(row_offset) and int(row_offset) + self.nrow <= int(total_rows)):
+                raise ValueError("row_offset / total_rows: the request's sampling rows (4, text mode: 1) must lie inside the batch")
             if emb is not None and tuple(emb.shape) != (ids.shape[0], GPT.hidden):
                 raise ValueError("emb must be [T, 768] for a [T, 4] prompt")
         elif params is not None or row_offset != 0 or total_rows != GPT.n_vq or emb is not None:
@@ -358,7 +405,7 @@ class SlotPool:
 
     def _admit_rows(self, slots: List[int], reqs: List[_Req], sl: torch.Tensor) -> None:
         """per-request pools: the admitted slots' sampling table entries, global sampling rows and Exp(1) rows (stream-ordered)"""
-        dev, nvq = self.dev, GPT.n_vq
+        dev, nvq = self.dev, self.nrow
         tab = []
         for r in reqs:
             seeded = r.params.manual_seed is not None
@@ -369,7 +416,7 @@ class SlotPool:
         self.row_base[sl] = torch.tensor([r.row_offset for r in reqs], dtype=torch.int32, device=dev)
         if not self.device_rng:
             for s_, r in zip(slots, reqs):    # the request's rows of the draw of a total_rows batch (what generate uploads for it)
-                q = ExpDraws(r.total_rows, GPT.n_audio, r.params.manual_seed, row_begin=r.row_offset, row_end=r.row_offset + nvq).step(0)
+                q = ExpDraws(r.total_rows, self.V, r.params.manual_seed, row_begin=r.row_offset, row_end=r.row_offset + nvq).step(0)
                 self.q[0, s_ * nvq: (s_ + 1) * nvq] = q.to(dev)
 
     def _admit(self) -> None:
@@ -454,74 +501,99 @@ class SlotPool:
         first -- at once, not one chunk later like the results: the consumer decodes the chunks from `self.hiddens` while the generator
         is suspended, so a finished slot's rows are still its own (the slot is freed, and re-admitted, only after the generator resumes;
         the device meanwhile runs the chunk that was enqueued ahead)."""
-        pending: Deque = deque()
-        ready: Deque = deque()      # (event behind the result copies, results) of the previous poll
-        while self.queue or self.active or pending:
+        while self.busy():
             if between is not None:
                 between()
-            self._admit()
-            if self.active:
-                _lib.check(self.lib.ctts_gpt_graph_launch(self.handle, self.POLL, self.st.cuda_stream), "ctts_gpt_graph_launch")
-                self.steps += self.POLL
-                pending.append(self._snapshot())
-            while ready:          # the copies were enqueued in front of the chunk launched just now: the device stays busy while we wait
-                ev_out, outs = ready.popleft()
-                wait_event(ev_out)
-                yield from self._hand_out(outs, grouped)
-            if len(pending) < 2 and self.active:
-                continue          # keep one chunk running ahead of the snapshot the host is about to read
-            if not pending:
-                continue
-            seq, blk, ev = pending.popleft()
-            wait_event(ev)        # polled, not an interrupt wait (chattts_amd/_sync.py)
-            fin = blk[: self.S]
-            end = blk[self._Sp:].view(torch.int32)[: self.S]
-            gone = [s for s, (r, _, _) in self.active.items() if r.cancelled]
-            if gone:                  # cancel(rid): the slot stops computing and is free for the next admission
-                with torch.cuda.stream(self.st):
-                    for s in gone:
-                        self.active.pop(s)
-                        self.finish[s] = 1
-                self.free.extend(gone)
-                self.free.sort()
-            done = [s for s, (r, _, since) in self.active.items() if seq >= since and (bool(fin[s]) or int(end[s]) >= r.max_new)]
-            if events:
-                chunks = []
-                for s, (r, _, since) in self.active.items():
-                    if r.cursor is None or seq < since:
-                        continue
-                    n = min(int(end[s]), r.max_new)
-                    due = r.cursor.finish(n, bool(fin[s]) and int(end[s]) < r.max_new) if s in done else r.cursor.advance(n)
-                    chunks += [(r.rid, s, *c) for c in due]
-                if chunks:
-                    yield StreamEvents(chunks)
-            if not done:
-                continue
-            outs = []
-            with torch.cuda.stream(self.st):
-                for s in done:
-                    r, Tg, _ = self.active.pop(s)
-                    n = min(int(end[s]), r.max_new)
-                    if self.per_request and n == 0 and bool(fin[s]) and r.stop_at < 0 and r.max_new > 0:
-                        # step 0 drew EOS: generate's rule (engine.py, gpt.py:527-570) -- an unseeded request with ensure_non_empty is
-                        # generated again (fresh admission number / draw), any other yields nothing
-                        self.finish[s] = 1
-                        if r.params.manual_seed is None and r.params.ensure_non_empty:
-                            self.queue.appendleft(r)
-                            continue
-                        outs.append((r.rid, self.ids_buf[s, :0].clone(), self.hiddens[s, :0].clone()))
-                        continue
-                    outs.append((r.rid, self.ids_buf[s, Tg: Tg + n].clone(), self.hiddens[s, :n].clone()))
-                    self.finish[s] = 1      # a request cut at max_new_token stops costing attention bandwidth
-                ev_out = torch.cuda.Event()
-                ev_out.record(self.st)
-            ready.append((ev_out, outs))    # handed out after the next chunk has been enqueued; the slots are free now (re-admission
-            self.free.extend(done)          # writes are stream-ordered behind the copies)
-            self.free.sort()
-        while ready:
-            ev_out, outs = ready.popleft()
+            yield from self.tick(grouped, events)
+
+    # The loop body of run() in three pieces, so that ONE worker can drive several pools (SpeechBatcher(refine=True): the text pool and
+    # the code pool): `launch()` of every pool first -- one chunk of each enqueued on its own stream -- and only then the waits.
+    def busy(self) -> bool:
+        """requests queued or resident, a snapshot not read yet, or results not handed out yet"""
+        return bool(self.queue or self.active or self._pending or self._ready)
+
+    def tick(self, grouped: bool = False, events: bool = False) -> Iterator:
+        """one iteration of run(): admit + enqueue a chunk, hand out the previous poll's results, read the oldest snapshot"""
+        self.launch()
+        yield from self.results(grouped)
+        yield from self.poll(events)
+
+    def launch(self) -> bool:
+        """admits queued requests into free slots and enqueues one POLL-step chunk + its snapshot when slots are live (True then)"""
+        self._admit()
+        if not self.active:
+            return False
+        _lib.check(self.lib.ctts_gpt_graph_launch(self.handle, self.POLL, self.st.cuda_stream), "ctts_gpt_graph_launch")
+        self.steps += self.POLL
+        self._pending.append(self._snapshot())
+        return True
+
+    def results(self, grouped: bool = False) -> Iterator:
+        """the results of the previous poll: their copies were enqueued in front of the chunk launched last, so the device stays busy
+        while the host waits for them"""
+        while self._ready:
+            ev_out, outs = self._ready.popleft()
             wait_event(ev_out)
             yield from self._hand_out(outs, grouped)
+
+    def poll(self, events: bool = False) -> Iterator:
+        """reads the oldest snapshot once a second chunk runs ahead of it (or nothing is live any more): retires cancelled and finished
+        slots, yields the due StreamEvents at once, queues the finished requests' results for the next `results()`"""
+        pending, ready = self._pending, self._ready
+        if len(pending) < 2 and self.active:
+            return            # keep one chunk running ahead of the snapshot the host is about to read
+        if not pending:
+            return
+        seq, blk, ev = pending.popleft()
+        wait_event(ev)        # polled, not an interrupt wait (chattts_amd/_sync.py)
+        fin = blk[: self.S]
+        end = blk[self._Sp:].view(torch.int32)[: self.S]
+        gone = [s for s, (r, _, _) in self.active.items() if r.cancelled]
+        if gone:                  # cancel(rid): the slot stops computing and is free for the next admission
+            with torch.cuda.stream(self.st):
+                for s in gone:
+                    self.active.pop(s)
+                    self.finish[s] = 1
+            self.free.extend(gone)
+            self.free.sort()
+        done = [s for s, (r, _, since) in self.active.items() if seq >= since and (bool(fin[s]) or int(end[s]) >= r.max_new)]
+        if events:
+            chunks = []
+            for s, (r, _, since) in self.active.items():
+                if r.cursor is None or seq < since:
+                    continue
+                n = min(int(end[s]), r.max_new)
+                due = r.cursor.finish(n, bool(fin[s]) and int(end[s]) < r.max_new) if s in done else r.cursor.advance(n)
+                chunks += [(r.rid, s, *c) for c in due]
+            if chunks:
+                yield StreamEvents(chunks)
+        if not done:
+            return
+        outs = []
+        with torch.cuda.stream(self.st):
+            for s in done:
+                r, Tg, _ = self.active.pop(s)
+                n = min(int(end[s]), r.max_new)
+                if self.per_request and n == 0 and bool(fin[s]) and r.stop_at < 0 and r.max_new > 0:
+                    # step 0 drew EOS: generate's rule (engine.py, gpt.py:527-570) -- an unseeded request with ensure_non_empty is
+                    # generated again (fresh admission number / draw), any other yields nothing
+                    self.finish[s] = 1
+                    if r.params.manual_seed is None and r.params.ensure_non_empty:
+                        self.queue.appendleft(r)
+                        continue
+                    outs.append((r.rid, self.ids_buf[s, :0, 0].clone() if self.infer_text else self.ids_buf[s, :0].clone(),
+                                 self.hiddens[s, :0].clone()))
+                    continue
+                if self.infer_text:     # gpt.py:300-301: the text row is slot 0 of the replicated ids; no hidden states are kept
+                    outs.append((r.rid, self.ids_buf[s, Tg: Tg + n, 0].clone(), self.hiddens[s, :0].clone()))
+                else:
+                    outs.append((r.rid, self.ids_buf[s, Tg: Tg + n].clone(), self.hiddens[s, :n].clone()))
+                self.finish[s] = 1      # a request cut at max_new_token stops costing attention bandwidth
+            ev_out = torch.cuda.Event()
+            ev_out.record(self.st)
+        ready.append((ev_out, outs))    # handed out after the next chunk has been enqueued; the slots are free now (re-admission
+        self.free.extend(done)          # writes are stream-ordered behind the copies)
+        self.free.sort()
 
     @staticmethod
     def _hand_out(outs: list, grouped: bool):
@@ -581,11 +653,26 @@ class SpeechBatcher:
     `CodecEngine.decode_windows`), each what the serial streamed path yields for that request; `stream_decode_calls` counts those
     decodes, `stream_chunks` the chunks they served, `max_stream_group` the most one decode served.
 
-    `make_pool` (tests: a fake) builds the pool; by default a per-request SlotPool on `chat.gpt` with the engine's generator mode,
+    `refine=True`: requests may ask for the reference's DEFAULT behaviour, the refine-text pass in front of the code pass
+    (`submit(text, params, refine=RefineTextParams(...))`).  A second, TEXT-mode per-request pool (SlotPool(infer_text=True), its own
+    handle and stream, `text_cap` positions per slot: the endpoint's 2048-character inputs + 384 new tokens by default) serves that stage:
+    the request is admitted there first; when its text row completes the worker turns it into the code-stage text with the helpers
+    `Chat._infer` uses (`Chat.refined_text`, then `Chat.code_prompt` / `Chat.prompt_embedding`) and submits it to the code pool, as a
+    stream if it was one.  The result is what `Chat.infer([text], skip_refine_text=False, params_refine_text=refine,
+    params_infer_code=params, pcm16=True[, stream=True])` returns for the request alone.  ONE worker owns both pools: every iteration
+    enqueues one chunk of every pool that has work -- on their two streams, so the text chain overlaps the code chain on the device --
+    before it waits for any snapshot.  The text pool draws from the HOST generator (`refine_rng="host"`: what the serial refine pass
+    draws from whatever the engine's `rng` is -- seeded requests only); `refine_rng="device"` serves unseeded refine requests too, from
+    the sampling kernel's generator (`GptEngine.generate(text_rng="device")` is that request alone).  `occupancy()["refine"]` counts
+    text admissions, the most co-resident text requests, text steps, hand-offs, and the polls at which both pools had live slots.
+    A request without `refine` takes the code pool directly, as without the option.
+
+    `make_pool` / `make_text_pool` (tests: fakes) build the pools; by default a per-request SlotPool on `chat.gpt` with the engine's generator mode,
     `cap` = the engine's position limit (the longest accepted prompt + max_new_token 2048 + slack), `hid_cap` 2048."""
 
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
-                 logger=None, ragged_decode: bool = False, streams: bool = False):
+                 logger=None, ragged_decode: bool = False, streams: bool = False, refine: bool = False, make_text_pool=None,
+                 text_cap: Optional[int] = None, refine_rng: str = "host"):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
@@ -613,29 +700,64 @@ class SpeechBatcher:
                 return SlotPool(eng, slots=self.S, cap=cap if cap is not None else eng.max_pos, hid_cap=hid_cap,
                                 rng=getattr(eng, "rng", "host"), per_request=True)
         self._make_pool = make_pool
+        self.refine = bool(refine)
+        self.text_pool = None
+        self._stage1: dict = {}          # request id -> its request, while it is in the text pool
+        self.refine_admissions = 0       # requests admitted into the text pool
+        self.refine_max_coresident = 0   # most requests resident in the text pool at once
+        self.handed = 0                  # requests handed from the text pool to the code pool
+        self.both_live_polls = 0         # worker iterations at which both pools had live slots
+        if self.refine and make_text_pool is None:
+            def make_text_pool():
+                eng = chat.gpt
+                # the endpoint accepts 2048 characters (<= 2048 text tokens + the prompt's decoration) and refines with max_new_token 384
+                tc = text_cap if text_cap is not None else min(eng.max_pos, 2048 + 64 + 384 + 1 + 2 * SlotPool.POLL)
+                return SlotPool(eng, slots=self.S, cap=tc, rng=refine_rng, per_request=True, infer_text=True,
+                                eos_token=chat.tokenizer.eos_token)
+        self._make_text_pool = make_text_pool
         with self.lock:
             self.pool = make_pool()
-        self._thread = threading.Thread(target=self._loop, name="speech-batcher", daemon=True)
+            if self.refine:
+                self.text_pool = make_text_pool()
+        self._thread = threading.Thread(target=self._loop2 if self.refine else self._loop, name="speech-batcher", daemon=True)
         self._thread.start()
 
     # -- public -------------------------------------------------------------------------------------------------------------
-    def submit(self, text: str, params) -> Future:
+    def submit(self, text: str, params, refine=None) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
-        int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return."""
+        int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
+        `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
+        result is that of `Chat.infer([text], skip_refine_text=False, params_refine_text=refine, ...)`."""
+        self._check_refine(refine)
         fut: Future = Future()
-        self._in.put((next(self._ids), text, params, fut))
+        self._in.put((next(self._ids), text, params, fut, refine))
         return fut
 
-    def submit_stream(self, text: str, params) -> SpeechStream:
+    def submit_stream(self, text: str, params, refine=None) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
-        params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request."""
+        params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
+        whichever pool it is.  `refine`: as in `submit`."""
         if not self.streams:
             raise RuntimeError("this SpeechBatcher was built without streams=True")
+        self._check_refine(refine)
         h = SpeechStream(self, next(self._ids))
-        self._in.put((h.rid, text, params, h))
+        self._in.put((h.rid, text, params, h, refine))
         return h
 
+    def _check_refine(self, refine) -> None:
+        if refine is not None and not self.refine:
+            raise RuntimeError("this SpeechBatcher was built without refine=True")
+
     def occupancy(self) -> dict:
+        if self.refine:
+            tp = self.text_pool
+            return {**self._occupancy_streams(), "refine": {
+                "active": len(getattr(tp, "active", {})), "queued": len(getattr(tp, "queue", ())), "admissions": self.refine_admissions,
+                "max_coresident": self.refine_max_coresident, "steps": int(getattr(tp, "steps", 0)), "handed": self.handed,
+                "both_live_polls": self.both_live_polls}}
+        return self._occupancy_streams()
+
+    def _occupancy_streams(self) -> dict:
         if self.streams:
             return {**self._occupancy(), "streams": len(self._streams), "stream_decode_calls": self.stream_decode_calls,
                     "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled}
@@ -655,6 +777,7 @@ class SpeechBatcher:
     # -- worker -------------------------------------------------------------------------------------------------------------
     def _fail(self, rid, e: BaseException):
         self.failed += 1
+        self._stage1.pop(rid, None)
         fut = self._futs.pop(rid, None)
         if fut is not None and not fut.done():
             fut.set_exception(e)
@@ -664,16 +787,48 @@ class SpeechBatcher:
 
     def _take(self, item) -> None:
         """prompt of one request -> pool.submit (worker thread, GPU lock held)"""
-        rid, text, params, fut = item
-        kw = {}
+        rid, text, params, fut = item[:4]
+        refine = item[4] if len(item) > 4 else None
         if isinstance(fut, SpeechStream):
             self._streams[rid] = fut
-            kw["stream"] = StreamSpec(int(params.stream_batch), int(params.stream_speed), int(params.pass_first_n_batches))
         else:
             self._futs[rid] = fut
         try:
+            t = self.chat.normalizer(text, True, True, None)        # what Chat._infer does with do_text_normalization / homophones
+            if refine is not None:       # stage 1: the refine-text pass, in the text pool (Chat._refine_text's prompt)
+                ids, attn, _ = self.chat.refine_prompt([t], refine)
+                self.text_pool.submit(rid, ids[0][attn[0].bool()], max_new_token=refine.max_new_token, params=refine)
+                self._stage1[rid] = (rid, t, params, fut, refine)
+                self.refine_admissions += 1
+                return
+        except Exception as e:        # this request's error, not the worker's
+            self._fail(rid, e)
+            return
+        self._to_code(rid, t, params, fut)
+
+    def _refined(self, rid, row: torch.Tensor) -> None:
+        """a request's text row completed: hand it to the code pool (exactly once), as the text `Chat._infer` would synthesise"""
+        item = self._stage1.pop(rid, None)
+        if item is None or (rid not in self._futs and rid not in self._streams):
+            return                        # cancelled or failed meanwhile
+        _, _, params, fut, _ = item
+        try:
+            if row.shape[0] == 0:         # the serial path's refine pass yields nothing there (gpt.py:570)
+                raise RuntimeError("the refine-text pass returned no tokens (the first token was EOS)")
+            t = self.chat.refined_text([row.cpu()])[0]
+        except Exception as e:
+            self._fail(rid, e)
+            return
+        self.handed += 1
+        self._to_code(rid, t, params, fut)
+
+    def _to_code(self, rid, t: str, params, fut) -> None:
+        """the code-stage prompt of one normalised (or refined) text -> pool.submit"""
+        kw = {}
+        if isinstance(fut, SpeechStream):
+            kw["stream"] = StreamSpec(int(params.stream_batch), int(params.stream_speed), int(params.pass_first_n_batches))
+        try:
             chat = self.chat
-            t = chat.normalizer(text, True, True, None)             # what Chat._infer does with do_text_normalization / homophones
             ids, attn, tmask = chat.code_prompt([t], params)
             emb = chat.prompt_embedding(ids, tmask, params, chat.tokenizer.spk_emb_ids)
             keep = attn[0].bool()
@@ -703,7 +858,10 @@ class SpeechBatcher:
         h = self._streams.pop(rid, None)
         if h is not None:
             self.cancelled += 1
-            self.pool.cancel(rid)
+            if self._stage1.pop(rid, None) is not None:
+                self.text_pool.cancel(rid)
+            else:
+                self.pool.cancel(rid)
             h._q.put(None)
 
     def _serve_chunks(self, ev: StreamEvents) -> None:
@@ -803,27 +961,75 @@ class SpeechBatcher:
                             close()
                         self.pool = self._make_pool()
                         break
-                    if isinstance(got, StreamEvents):
-                        self._serve_chunks(got)
-                        continue
-                    for rid, _, hid in (got if self.ragged_decode else [got]):     # a stream's result: its chunks went out already
-                        self._end_stream(rid, hid)
-                    if self.ragged_decode:
-                        group = [(rid, hid) for rid, _, hid in got if rid in self._futs]
-                        try:
-                            results = self.finish_group([h for _, h in group])
-                        except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
-                            results = [e] * len(group)
-                        for (rid, _), r in zip(group, results):
-                            self._deliver(rid, r)
-                        continue
-                    rid, ids, hid = got
-                    if rid not in self._futs:
-                        continue
-                    try:
-                        pcm = self.finish(hid)
-                    except Exception as e:
-                        pcm = e
-                    self._deliver(rid, pcm)
+                    self._handle(got)
             finally:
                 self.lock.release()
+
+    def _handle(self, got) -> None:
+        """one item of the code pool's output: the due chunks of a poll, or finished requests (one, or the group of a poll)"""
+        if isinstance(got, StreamEvents):
+            self._serve_chunks(got)
+            return
+        for rid, _, hid in (got if self.ragged_decode else [got]):     # a stream's result: its chunks went out already
+            self._end_stream(rid, hid)
+        if self.ragged_decode:
+            group = [(rid, hid) for rid, _, hid in got if rid in self._futs]
+            try:
+                results = self.finish_group([h for _, h in group])
+            except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
+                results = [e] * len(group)
+            for (rid, _), r in zip(group, results):
+                self._deliver(rid, r)
+            return
+        rid, ids, hid = got
+        if rid not in self._futs:
+            return
+        try:
+            pcm = self.finish(hid)
+        except Exception as e:
+            pcm = e
+        self._deliver(rid, pcm)
+
+    def _loop2(self):
+        """refine=True: ONE worker over the text pool and the code pool.  Every iteration: let other GPU users in and take arrived
+        requests (`_between`), then enqueue one chunk of EVERY pool that has work -- each on its own stream -- and only then wait:
+        for the previous poll's results, then for the oldest snapshot of each.  A finished text row goes to the code pool at once
+        and is admitted there at the next iteration."""
+        def busy():
+            return self.text_pool.busy() or self.pool.busy()
+        while self._drain(block=True) or busy():
+            if not busy():
+                continue
+            self.lock.acquire()
+            try:
+                while busy():
+                    self._between()
+                    try:
+                        live = [p for p in (self.text_pool, self.pool) if p.busy()]      # only the pools that have work
+                        n_live = sum(bool(p.launch()) for p in live)
+                        self.both_live_polls += int(n_live == 2)
+                        self.refine_max_coresident = max(self.refine_max_coresident, len(self.text_pool.active))
+                        for p in live:
+                            for got in p.results(self.ragged_decode and p is self.pool):
+                                self._route(p, got)
+                        for p in live:
+                            for got in p.poll(self.streams and p is self.pool):
+                                self._route(p, got)
+                    except Exception as e:     # a pool itself failed: the requests in flight fail, fresh pools serve the next ones
+                        self.log.error("slot pool failed: %s", e)
+                        for r in [*self._futs, *self._streams]:
+                            self._fail(r, e)
+                        for p in (self.text_pool, self.pool):
+                            close = getattr(p, "close", None)
+                            if close is not None:
+                                close()
+                        self.pool, self.text_pool = self._make_pool(), self._make_text_pool()
+                        break
+            finally:
+                self.lock.release()
+
+    def _route(self, pool, got) -> None:
+        if pool is self.text_pool:
+            self._refined(got[0], got[1])
+        else:
+            self._handle(got)

@@ -170,7 +170,8 @@ typedef struct {
                                       is 0.  The host passes the utterances by descending context (the contexts of a batch differ
                                       only by the static valid prompt length), so the attention grid starts its longest
                                       (utterance, head) units first.  NULL = ascending slot.  No result depends on it. */
-  /* Opt-in DEVICE generator for the Exp(1) draws of the multinomial (code mode only).  The reference draws them from
+  /* Opt-in DEVICE generator for the Exp(1) draws of the multinomial (both modes; the text mode has ONE sampling row per utterance:
+   * global row = row_base[b] or row_offset + b).  The reference draws them from
    * `torch.Generator(device=device)` (gpt.py:39,501-508): on its CPU path that is torch's CPU stream -- the parity contract, served
    * by `q` above -- and on a GPU device its device stream.  With rng_device = 1 `q` is not read: the sampling kernel draws
    * q = -log(u) itself from Philox4x32-10 keyed on rng_seed with counter (token / 4, global sampling row, step), so the default
@@ -190,7 +191,8 @@ typedef struct {
    * margin / 2 cannot change any sampled token of that utterance: the split-fp16 parity arithmetic (wqkv_x3 ...) is certified per call
    * against its measured logit error bound instead of by sample (chattts_amd/engine.py GptEngine.certify).  NULL: nothing is computed. */
   float* margin;
-  /* [B] or NULL: global index of sampling row 0 of utterance b (b_global * 4 in code mode) -- replaces row_offset + 4 b when a shard holds a
+  /* [B] or NULL: global index of sampling row 0 of utterance b (b_global * 4 in code mode, b_global in text mode) -- replaces
+   * row_offset + 4 b (text mode: row_offset + b) when a shard holds a
    * NON-contiguous set of the caller's utterances (length-balanced data-parallel shards, chattts_amd/dist.py; the exact re-run of the
    * utterances a parity certificate flagged).  Keys the rows >= 625 repetition-penalty quirk (processors.py:24-27) and the device
    * generator's counter; `q` stays indexed by the local slot (the host uploads the selected rows of the CPU draw). */
@@ -203,12 +205,15 @@ typedef struct {
    * known to the host.  > 0: the prompt pass runs over those rows only instead of over all B * T left-padded rows (the reference computes
    * the pad rows and never consumes them, gpt.py:234-241).  0: every row.  Same KV cache contents for the valid slots, same token. */
   int32_t prefill_valid_rows;
-  /* [slots] or NULL, code mode only: per-utterance-slot sampling parameters (ctts_sampling_row above).  When set, the sampling of utterance
+  /* [slots] or NULL: per-utterance-slot sampling parameters (ctts_sampling_row above).  When set, the sampling of utterance
    * slot b -- decode steps (eager and graph replay), the prefill's step-0 sample, ctts_k_sample -- reads temperature, pow_table,
    * top_p_thr / use_top_p, top_k / use_top_k, min_new, and (device generator) rng_seed / rng_per_step from row_sampling[b] instead of
    * the call-wide fields above, which are then not read (temperature / pow_table / rng_seed may be NULL).  Where the slot's draws come from
    * is unchanged: row_base[b] (or row_offset + 4 b) is its global sampling row (the rows >= 625 penalty quirk, the device generator's
-   * counter), q[b] holds its own Exp(1) rows.  The parity certificate (margin) uses the row's own values.  NULL: the call-wide fields. */
+   * counter), q[b] holds its own Exp(1) rows.  The parity certificate (margin) uses the row's own values.  NULL: the call-wide fields.
+   * Text mode (infer_text = 1, sample_text_k / ctts_k_sample_text): temperature[0], top_p_thr / use_top_p, top_k / use_top_k, min_new,
+   * rng_seed / rng_per_step are read; the mode has no repetition penalty, so use_penalty / pow_table are NOT read there (the host refuses
+   * a request that would set them, serving.sampling_row); the global sampling row is row_base[b] (or row_offset + b). */
   const ctts_sampling_row* row_sampling;
 } ctts_gen_state;
 

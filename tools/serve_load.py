@@ -3,6 +3,12 @@ batching (`create_app(..., batch_slots=S)`) and once without, plus the sampling 
 Prints one JSON line.  Not a bench.py leg.
 
     python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R]]
+    python tools/serve_load.py --refine [--refine-max-new 64] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
+
+--refine: the same N concurrent requests WITH the refine-text pass (the reference's default two-stage call), in one process: (a) through
+`Chat.infer(skip_refine_text=False)` one at a time under a lock, (b) through the two-pool batcher (`SpeechBatcher(refine=True,
+streams=True)`: a text-mode pool feeding the code pool).  Non-streamed: audio-s/s, p50 / p95 latency; then the same requests streamed:
+additionally the time to the first audio chunk.
 
 --stream: instead, N concurrent STREAMED requests against the batching app with `batch_streams` off (streams served one after the
 other, each a batch of one) and on (streams share the slot pool, the chunks due at one poll come from one window decode): per request
@@ -146,6 +152,77 @@ def stream_main(chat, voices, a):
                           single_stream_first_byte_s=single)))
 
 
+def refine_main(chat, voices, a):
+    from chattts_amd.serving import SpeechBatcher
+    names = sorted(voices)
+    refine = chat.RefineTextParams(show_tqdm=False, manual_seed=42, max_new_token=a.refine_max_new)
+
+    def code_params(i):
+        return chat.InferCodeParams(prompt="[speed_5]", top_P=0.5, top_K=10, temperature=0.1, repetition_penalty=1.1, max_new_token=2048,
+                                    show_tqdm=False, manual_seed=42, spk_emb=voices[names[i % len(names)]])
+
+    def leg(call, n, stream):
+        """n threads, `call(i)` -> the waveform, or an iterator of chunks"""
+        lat, first, samples = [0.0] * n, [float("nan")] * n, [0] * n
+
+        def one(i):
+            t0 = time.perf_counter()
+            try:
+                got = call(i)
+                for c in (got if stream else [got]):
+                    if np.asarray(c).size and first[i] != first[i]:
+                        first[i] = time.perf_counter() - t0
+                    samples[i] += int(np.asarray(c).size)
+            except Exception as e:
+                print(f"request {i}: {e}", file=sys.stderr)
+            lat[i] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        ths = [threading.Thread(target=one, args=(i,)) for i in range(n)]
+        for th in ths:
+            th.start()
+        for th in ths:
+            th.join()
+        wall = time.perf_counter() - t0
+        audio = sum(samples) / server.SAMPLE_RATE
+        pct = lambda v, q: round(float(np.nanpercentile(v, q)), 4)
+        out = dict(failed=sum(x == 0 for x in samples), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3), audio_s=round(audio, 2),
+                   p50_s=pct(lat, 50), p95_s=pct(lat, 95))
+        if stream:
+            out.update(first_chunk_p50_s=pct(first, 50), first_chunk_p95_s=pct(first, 95))
+        return out
+    lock = threading.Lock()
+    res = {}
+    for stream in (False, True):
+        def serial(i):
+            def call():
+                return chat.infer([TEXTS[i % len(TEXTS)]], stream=stream, skip_refine_text=False, params_refine_text=refine,
+                                  params_infer_code=code_params(i), pcm16=True)
+            if not stream:
+                with lock:
+                    return call()[0]
+
+            def chunks():          # the lock is held for the stream's whole life, like the serial endpoint's model_lock
+                with lock:
+                    yield from call()
+            return chunks()
+        leg(serial, 1, stream)                                           # first-call costs out of the burst
+        res["serial_stream" if stream else "serial"] = leg(serial, a.n, stream)
+        b = SpeechBatcher(chat, a.slots, threading.Lock(), refine=True, streams=True)
+        try:
+            def pooled(i):
+                if stream:
+                    return b.submit_stream(TEXTS[i % len(TEXTS)], code_params(i), refine=refine)
+                return b.submit(TEXTS[i % len(TEXTS)], code_params(i), refine=refine).result()
+            leg(pooled, 1, stream)
+            res["pooled_stream" if stream else "pooled"] = {**leg(pooled, a.n, stream), "refine": b.occupancy()["refine"],
+                                                             "max_coresident": b.occupancy()["max_coresident"]}
+        finally:
+            b.close()
+    print(json.dumps(dict(metric="serve_load_refine", n=a.n, slots=a.slots, max_new=a.max_new, refine_max_new=a.refine_max_new, dtype=a.dtype,
+                          **res, speedup=round(res["pooled"]["audio_s_per_s"] / res["serial"]["audio_s_per_s"], 2),
+                          stream_speedup=round(res["pooled_stream"]["audio_s_per_s"] / res["serial_stream"]["audio_s_per_s"], 2))))
+
+
 def sample_k_ms(eng, per_request, slots, steps=64):
     """mean sample_k time (profile tag 9) over `steps` eager decode steps of a full pool of identical requests"""
     pool = SlotPool(eng, slots=slots, cap=512, hid_cap=256, manual_seed=42, per_request=per_request)
@@ -175,6 +252,8 @@ def main():
     ap.add_argument("--ragged-decode", action="store_true", help="A/B: also the batched burst with one ragged decode per poll")
     ap.add_argument("--stream", action="store_true", help="streamed requests: batch_streams off vs on")
     ap.add_argument("--repeat", type=int, default=5, help="--stream: single-stream runs per leg (run-to-run spread)")
+    ap.add_argument("--refine", action="store_true", help="two-stage requests: Chat.infer serially vs the two-pool batcher")
+    ap.add_argument("--refine-max-new", type=int, default=64, help="--refine: max_new_token of the refine-text pass")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     gold = os.path.join(ROOT, "tests", "golden")
@@ -186,6 +265,8 @@ def main():
     voices = {"default": chat.sample_random_speaker(), "alloy": chat.sample_random_speaker(), "echo": chat.sample_random_speaker()}
     orig = chat.InferCodeParams
     chat.InferCodeParams = lambda **kw: orig(**{**kw, "max_new_token": a.max_new})
+    if a.refine:
+        return refine_main(chat, voices, a)
     if a.stream:
         return stream_main(chat, voices, a)
     serial = burst(chat, voices, a.n, None)
