@@ -64,6 +64,14 @@ class InferCodeParams:            # core.py:195-206 (+ the RefineTextParams fiel
     pass_first_n_batches: int = 2
 
 
+def split_sentences(text: str) -> List[str]:
+    """how `Chat.infer(text: str, split_text=True)` cuts its input (core.py:225-233): at newlines when there are any, else after every CJK
+    full stop and after every ". ".  `Chat.infer` and the batched server (serving.SpeechBatcher.submit(split_text=True)) both cut here."""
+    if "\n" in text:
+        return text.split("\n")
+    return [t for t in re.split(r"(?<=\u3002)|(?<=\.\s)", text) if t]     # sentence ends: after a CJK full stop, or after ". "
+
+
 class Chat:
     RefineTextParams = RefineTextParams      # the reference nests the two dataclasses in `Chat` (core.py:182-206)
     InferCodeParams = InferCodeParams
@@ -192,6 +200,19 @@ class Chat:
             raise RuntimeError("full DVAE not loaded (asset/DVAE.safetensors, or state_dicts['dvae'])")
         return Speaker.encode_prompt(self.dvae.sample_audio(wav))
 
+    def refer_speaker(self, rows, use_decoder: bool = True, *, on_device: bool = False, release=None) -> str:
+        """core.py:435-453: the refer sentence's result (its one row, decoded alone) -> the `spk_smp` prompt of the other sentences of a
+        split_text call.  `release`: called once the rows have been decoded (`_infer` frees the generator's result there).
+        `on_device` (the batched server's stage A, decoder path): the waveform goes from the decoder to the DVAE encoder without
+        visiting the host -- the same samples, hence the same string."""
+        if on_device:
+            wavs = self.codec.decode_to_wavs(rows)
+        else:
+            wavs = self.decode_to_wavs(rows, use_decoder)
+        if release is not None:
+            release()
+        return self.sample_audio_speaker(wavs[0])
+
     def interrupt(self):            # core.py:272-273
         self.context.set(True)
 
@@ -310,6 +331,25 @@ class Chat:
             return pieces
         keep_h = host[2 * n: 2 * n + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
+
+    def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64") -> List[np.ndarray]:
+        """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
+        hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
+        grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
+        device) and ONE device-to-host copy.  Request g's result equals
+        `float_to_int16(np.concatenate([w[np.abs(w) > 1e-5] for w in its sentences' alone decodes]))` bit for bit."""
+        assert self.has_loaded()
+        groups = [list(g) for g in groups]
+        if len(groups) == 0:
+            return []
+        if any(len(g) == 0 for g in groups):
+            raise ValueError("decode_split_to_pcm16: every request needs at least one sentence")
+        grp = np.zeros(len(groups) + 1, np.int32)
+        np.cumsum([len(g) for g in groups], out=grp[1:])
+        codec = self.codec
+        wav, off = codec.decode_ragged([h for g in groups for h in g])
+        blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None)
+        return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts)]
 
     def decode_windows_pcm16(self, store: torch.Tensor, windows) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
@@ -492,20 +532,25 @@ class Chat:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         self.context.set(False)
         if split_text and isinstance(text, str):
-            if "\n" in text:
-                text = text.split("\n")
-            else:                                  # sentence ends: after a CJK full stop, or after ". "
-                text = [t for t in re.split(r"(?<=\u3002)|(?<=\.\s)", text) if t]
+            text = split_sentences(text)
             self.logger.info("split text into %d parts", len(text))
         if len(text) == 0:
             return []
+        # split_text + pcm16 + ragged_decode: the hidden states of every split batch are collected and the whole request is decoded,
+        # stripped, converted under its one peak and compacted on the device (decode_split_to_pcm16) -- the bytes of the host lines below
+        split_dev = bool(split_text and pcm16 and ragged_decode and not stream and not refine_text_only)
         res_gen = self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
-                              pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode)
+                              pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev)
         if stream:
             return res_gen
         if refine_text_only:
             return next(res_gen)
+        if split_dev:
+            rows = [h for hids in res_gen for h in hids]
+            if rows:
+                return self.decode_split_to_pcm16([rows])
+            res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
         thr = np.float32(1e-5)
@@ -516,8 +561,8 @@ class Chat:
 
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
-               ragged: bool = False):
-        """core.py:395-503 (generator)."""
+               ragged: bool = False, raw: bool = False):
+        """core.py:395-503 (generator).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
             text = [text]
@@ -533,9 +578,7 @@ class Chat:
             # core.py:435-453: the first sentence is synthesised alone and its audio becomes the speaker prompt of the rest
             refer_text = text[0]
             result = next(self._infer_code(refer_text, False, self.device, use_decoder, params_infer_code))
-            wavs = self.decode_to_wavs(result.hiddens if use_decoder else result.ids, use_decoder)
-            result.destroy()
-            params_infer_code.spk_smp = self.sample_audio_speaker(wavs[0])
+            params_infer_code.spk_smp = self.refer_speaker(result.hiddens if use_decoder else result.ids, use_decoder, release=result.destroy)
             params_infer_code.txt_smp = refer_text
         length = 0
         pass_batch_count = 0
@@ -548,6 +591,11 @@ class Chat:
             for result in self._infer_code(batch, stream, self.device, use_decoder, params_infer_code):
                 if not stream:
                     src = result.hiddens if use_decoder else result.ids
+                    if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
+                        rows = [h.clone() for h in src]
+                        result.destroy()
+                        yield rows
+                        continue
                     if ragged:      # every utterance as if alone (Chat.infer's ragged_decode)
                         wavs = self.decode_to_pcm16(src, ragged=True) if pcm16 else self.decode_to_wavs(src, ragged=True)
                     else:

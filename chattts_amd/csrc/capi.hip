@@ -1349,6 +1349,47 @@ extern "C" int ctts_float_to_int16_ragged(const float* wav, int16_t* pcm, uint8_
   CK(launch_float_to_int16_ragged(wav, (const long long*)off_dev, n_seg, n_max, product, keep_thr, peak, pcm, keep_bits, (hipStream_t)stream));
   return 0;
 }
+// tiles of 2048 samples (codec.hip, GT) of the longest group, per group: the size of the grouped conversion's count scratch
+static long long groups_scratch_words(const int64_t* off_host, const int32_t* grp_host, int32_t n_grp, long long* n_max_out) {
+  long long n_max = 0;
+  for (int g = 0; g < n_grp; ++g) n_max = std::max(n_max, (long long)(off_host[grp_host[g + 1]] - off_host[grp_host[g]]));
+  if (n_max_out) *n_max_out = n_max;
+  return (long long)n_grp * ((n_max + 2047) / 2048);
+}
+static int groups_check(const char* who, const int64_t* off_host, int32_t n_seg, const int32_t* grp_host, int32_t n_grp) {
+  if (!off_host || !grp_host) return fail("%s: bad arguments", who);
+  if (n_grp < 1 || n_grp > 65535) return fail("%s: need 1 <= n_grp <= 65535 (got %d)", who, n_grp);
+  if (n_seg < n_grp) return fail("%s: %d groups need at least as many segments (got %d)", who, n_grp, n_seg);
+  if (off_host[0] != 0) return fail("%s: the first sample offset must be 0", who);
+  for (int i = 0; i < n_seg; ++i)
+    if (off_host[i + 1] <= off_host[i]) return fail("%s: segment %d is empty or the offsets do not ascend", who, i);
+  if (grp_host[0] != 0 || grp_host[n_grp] != n_seg) return fail("%s: the group table must run from 0 to n_seg", who);
+  for (int g = 0; g < n_grp; ++g) {
+    if (grp_host[g + 1] <= grp_host[g]) return fail("%s: group %d is empty or the group table does not ascend", who, g);
+    if (off_host[grp_host[g + 1]] - off_host[grp_host[g]] >= (1ll << 31)) return fail("%s: group %d holds 2^31 samples or more", who, g);
+  }
+  return 0;
+}
+extern "C" size_t ctts_float_to_int16_groups_scratch_bytes(const int64_t* off_host, int32_t n_seg, const int32_t* grp_host, int32_t n_grp) {
+  if (groups_check("ctts_float_to_int16_groups_scratch_bytes", off_host, n_seg, grp_host, n_grp)) return 0;
+  return (size_t)groups_scratch_words(off_host, grp_host, n_grp, nullptr) * sizeof(uint32_t);
+}
+extern "C" int ctts_float_to_int16_groups(const float* wav, int16_t* pcm, int64_t* n_kept, const int64_t* off_dev, const int64_t* off_host,
+                                          int32_t n_seg, const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp, int32_t product,
+                                          float keep_thr, uint32_t* peak, void* scratch, size_t scratch_bytes, void* stream) {
+  const char* who = "ctts_float_to_int16_groups";
+  if (!wav || !pcm || !off_dev || !grp_dev || (product != 0 && product != 1)) return fail("%s: bad arguments", who);
+  if (!peak || !n_kept) return fail("%s: the peak and count buffers must not be null", who);
+  if (groups_check(who, off_host, n_seg, grp_host, n_grp)) return -1;
+  if (((uintptr_t)pcm & 15) || ((uintptr_t)n_kept & 7)) return fail("%s: pcm must be 16-byte aligned, n_kept 8-byte aligned", who);
+  long long n_max = 0;
+  const long long words = groups_scratch_words(off_host, grp_host, n_grp, &n_max);
+  if (!scratch || scratch_bytes < (size_t)words * sizeof(uint32_t)) return fail("%s: scratch too small (%zu bytes, need %lld)", who, scratch_bytes, words * 4);
+  CttsDeviceGuard dg(stream);
+  CK(launch_float_to_int16_groups(wav, (const long long*)off_dev, grp_dev, n_grp, n_max, product, keep_thr, peak, (unsigned*)scratch, pcm,
+                                  (long long*)n_kept, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_copy_bytes(void* dst, const void* src, size_t bytes, void* stream) {
   if (!dst || !src || (bytes & 15) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return fail("ctts_copy_bytes: pointers and size must be 16-byte aligned");
   CttsDeviceGuard dg(stream);

@@ -578,6 +578,155 @@ hipError_t launch_float_to_int16_ragged(const float* wav, const long long* off, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Grouped strip + convert + compact (ctts_float_to_int16_groups): the last step of a split_text request (Chat.infer, core.py: ONE
+// concatenated waveform, hence one peak over all sentences) for many requests at once.  Segments grp[g] .. grp[g+1]-1 are request g's
+// sentences; packed segments are contiguous, so a group is the sample range [off[grp[g]], off[grp[g+1]]).  One peak and one scale per
+// group; the group's kept samples (|x| > keep_thr) go out contiguously, in order, from element gs[g] = sum_{h<g} ceil8(n_h) of the
+// output (n_h: group h's unstripped length -- for every real decode, whose segments are multiples of 256 samples, that is
+// ceil8(off[grp[g]]) = off[grp[g]]), the kept count to n_kept[g].  Three stream-ordered launches, no workgroup waits on another:
+//   grp_peak_count_k : a workgroup per tile of GT samples of a group -- the group's peak (atomicMax) and the tile's kept count
+//   grp_scan_k       : a workgroup per group -- exclusive scan of its tiles' counts in place, the total to n_kept[g]
+//   grp_pcm16_k      : a workgroup per tile -- converts, compacts its kept samples in LDS (a lane's position from the wave's ballots)
+//                      and writes the run out, 16 bytes per lane wherever the run covers a whole 16-byte chunk of the output
+// A thread owns 8 consecutive samples: two 16-byte loads where the tile starts on a 16-byte boundary.
+// ------------------------------------------------------------------------------------------------
+#define GT 2048   // samples per workgroup: 256 threads x 8
+// the thread's 8 samples of a tile of m samples at xt (zeros behind the tile's end) -> bit e of the result: sample e exists and is kept
+__device__ __forceinline__ unsigned grp_load8(const float* __restrict__ xt, int m, float keep_thr, float (&v)[8]) {
+  const int j0 = (int)threadIdx.x * 8;
+  if ((reinterpret_cast<uintptr_t>(xt) & 15) == 0 && j0 + 8 <= m) {
+    const float4 a = reinterpret_cast<const float4*>(xt + j0)[0], b = reinterpret_cast<const float4*>(xt + j0)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = j0 + e < m ? xt[j0 + e] : 0.0f;
+  }
+  unsigned bits = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (j0 + e < m && fabsf(v[e]) > keep_thr) bits |= 1u << e;
+  return bits;
+}
+__global__ __launch_bounds__(256) void grp_peak_count_k(const float* __restrict__ x, const long long* __restrict__ off, const int32_t* __restrict__ grp,
+                                                        float keep_thr, unsigned* __restrict__ peak, unsigned* __restrict__ blk) {
+  __shared__ unsigned red[4];
+  const int g = blockIdx.y;
+  const long long a = off[grp[g]], n = off[grp[g + 1]] - a, t0 = (long long)blockIdx.x * GT;
+  if (t0 >= n) return;                                   // workgroup-uniform: this group has fewer tiles than the longest one
+  float v[8];
+  const unsigned bits = grp_load8(x + a + t0, (int)min((long long)GT, n - t0), keep_thr, v);
+  unsigned m = 0, c = __popc(bits);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) m = max(m, __float_as_uint(v[e]) & 0x7fffffffu);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    c += (unsigned)__shfl_xor((int)c, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (m != 0) atomicMax(peak + g, m);
+    red[threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) blk[(size_t)g * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+__global__ __launch_bounds__(256) void grp_scan_k(const long long* __restrict__ off, const int32_t* __restrict__ grp, unsigned* __restrict__ blk,
+                                                  int tiles_max, long long* __restrict__ n_kept) {
+  __shared__ unsigned wsum[4];
+  const int g = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long n = off[grp[g + 1]] - off[grp[g]];
+  const int nt = (int)((n + GT - 1) / GT);
+  unsigned* c = blk + (size_t)g * tiles_max;
+  unsigned long long carry = 0;
+  for (int base = 0; base < nt; base += 256) {          // workgroup-uniform
+    const int i = base + (int)threadIdx.x;
+    const unsigned val = i < nt ? c[i] : 0u;
+    unsigned inc = val;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned t = (unsigned)__shfl_up((int)inc, o, 64);
+      if (lane >= o) inc += t;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    unsigned pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { if (k < wave) pre += wsum[k]; tot += wsum[k]; }
+    if (i < nt) c[i] = (unsigned)carry + pre + inc - val;   // a group holds fewer than 2^31 samples (checked on the host)
+    carry += tot;
+    __syncthreads();                                     // wsum is written again in the next round
+  }
+  if (threadIdx.x == 0) n_kept[g] = (long long)carry;
+}
+__global__ __launch_bounds__(256) void grp_pcm16_k(const float* __restrict__ x, const long long* __restrict__ off, const int32_t* __restrict__ grp,
+                                                   int product, float keep_thr, const unsigned* __restrict__ peak, const unsigned* __restrict__ blk,
+                                                   int16_t* __restrict__ out) {
+  __shared__ unsigned wcnt[4];
+  __shared__ __attribute__((aligned(16))) int16_t stg[GT + 8];
+  const int g = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long a = off[grp[g]], n = off[grp[g + 1]] - a, t0 = (long long)blockIdx.x * GT;
+  if (t0 >= n) return;                                   // workgroup-uniform
+  long long gs = 0;                                      // the group's first output element (wave-uniform: scalar loads)
+  for (int h = 0; h < g; ++h) gs += (off[grp[h + 1]] - off[grp[h]] + 7) & ~7ll;
+  const long long am = pcm16_scale(__uint_as_float(peak[g]));
+  float v[8];
+  const unsigned bits = grp_load8(x + a + t0, (int)min((long long)GT, n - t0), keep_thr, v);
+  // kept samples of the lower lanes of this wave: one ballot per sample position, counted below this lane
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned pre = 0, wtot = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const unsigned long long b = __ballot((bits >> e) & 1u);
+    pre += (unsigned)__popcll(b & below);
+    wtot += (unsigned)__popcll(b);
+  }
+  if (lane == 0) wcnt[wave] = wtot;
+  __syncthreads();
+  unsigned cnt = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { if (k < wave) pre += wcnt[k]; cnt += wcnt[k]; }
+  // stg[sh + j] is the tile's j-th kept sample, output element d0 + j: with sh = d0 & 7 a 16-byte chunk of the output is one of stg
+  const long long d0 = gs + blk[(size_t)g * gridDim.x + blockIdx.x];
+  const int sh = (int)(d0 & 7);
+  int pos = sh + (int)pre;
+  if (bits == 0xffu && (pos & 7) == 0) {
+    union { u128 q; int16_t s[8]; } p;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) p.s[e] = pcm16_sample(v[e], am, product);
+    *reinterpret_cast<u128*>(stg + pos) = p.q;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if ((bits >> e) & 1u) stg[pos++] = pcm16_sample(v[e], am, product);
+  }
+  __syncthreads();
+  int16_t* ob = out + (d0 - sh);                         // 16-byte aligned: gs and the output base are
+  const int lo = sh, hi = sh + (int)cnt;                 // the run, in stg's coordinates
+  for (int ch = threadIdx.x; ch * 8 < hi; ch += 256) {
+    const int q0 = ch * 8;
+    if (q0 >= lo && q0 + 8 <= hi) {
+      reinterpret_cast<u128*>(ob)[ch] = *reinterpret_cast<const u128*>(stg + q0);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (q0 + e >= lo && q0 + e < hi) ob[q0 + e] = stg[q0 + e];
+    }
+  }
+}
+hipError_t launch_float_to_int16_groups(const float* wav, const long long* off, const int32_t* grp, int n_grp, long long n_max, int product,
+                                        float keep_thr, unsigned* peak, unsigned* blk, int16_t* pcm, long long* n_kept, hipStream_t st) {
+  if (n_grp < 1 || n_max < 1) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(peak, 0, sizeof(unsigned) * n_grp, st);
+  if (e != hipSuccess) return e;
+  const int tiles = (int)((n_max + GT - 1) / GT);
+  hipLaunchKernelGGL(grp_peak_count_k, dim3(tiles, n_grp), dim3(256), 0, st, wav, off, grp, keep_thr, peak, blk);
+  hipLaunchKernelGGL(grp_scan_k, dim3(n_grp), dim3(256), 0, st, off, grp, blk, tiles, n_kept);
+  hipLaunchKernelGGL(grp_pcm16_k, dim3(tiles, n_grp), dim3(256), 0, st, wav, off, grp, product, keep_thr, (const unsigned*)peak,
+                     (const unsigned*)blk, pcm);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // Window decode (ctts_codec_decode_windows): the chunks of many streamed utterances that are due at one poll, each at its own position.
 // A window = token rows [t_lo, t_hi) of one slot of a hidden-state store [slots][hid_cap][768]; it is decoded as one ragged segment and
 // samples [c_lo, c_hi) of its decode (relative to the window's first sample) are emitted.

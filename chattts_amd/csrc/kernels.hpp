@@ -456,6 +456,11 @@ hipError_t launch_float_to_int16(const float* wav, long long n, long long ld, in
 // sum_{j<i} ceil(n_j / 8) on (every segment starts on a byte boundary).  n_max: the longest segment (grid size)
 hipError_t launch_float_to_int16_ragged(const float* wav, const long long* off, int n_seg, long long n_max, int product, float keep_thr,
                                         unsigned* peak, int16_t* pcm, uint8_t* keep, hipStream_t st);
+// grouped strip + convert + compact: segments grp[g] .. grp[g+1]-1 (packed, contiguous) are group g -- one peak each; its kept samples
+// (|x| > keep_thr) go out contiguously from element sum_{h<g} ceil8(n_h) of pcm, the kept count to n_kept[g].  n_max: the longest group (grid
+// size); blk: n_grp * ceil(n_max / 2048) words of device scratch (the tiles' kept counts, then their scan); peak: [n_grp] device scratch
+hipError_t launch_float_to_int16_groups(const float* wav, const long long* off, const int32_t* grp, int n_grp, long long n_max, int product,
+                                        float keep_thr, unsigned* peak, unsigned* blk, int16_t* pcm, long long* n_kept, hipStream_t st);
 // ctts_window (include/chattts_amd.h), field for field (capi.hip asserts the layout): token rows [t_lo, t_hi) of one slot of a hidden-state
 // store, decoded as one ragged segment; samples [c_lo, c_hi) of that decode (relative to its first sample) are emitted
 struct CodecWindow {

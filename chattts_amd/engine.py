@@ -1153,6 +1153,15 @@ def keep_offsets(off) -> np.ndarray:
     return k
 
 
+def group_starts(off, grp) -> np.ndarray:
+    """first output element of every group of `CodecEngine.float_to_int16_groups` (+ the total as the last entry): the running sum of the
+    groups' unstripped lengths, each rounded up to 8 samples -- for a decode's offsets (multiples of 256) simply off[grp[g]]"""
+    off, grp = np.asarray(off, dtype=np.int64), np.asarray(grp, dtype=np.int64)
+    s = np.zeros(len(grp), np.int64)
+    np.cumsum((np.diff(off[grp]) + 7) // 8 * 8, out=s[1:])
+    return s
+
+
 def ragged_views(flat, off) -> list:
     """the per-utterance pieces [off[i], off[i+1]) of a packed 1-D array or tensor (CodecEngine.decode_ragged): views, no copies"""
     return [flat[int(off[i]): int(off[i + 1])] for i in range(len(off) - 1)]
@@ -1420,6 +1429,46 @@ class CodecEngine:
                    "ctts_float_to_int16_ragged")
         off_d.record_stream(st)
         return pcm, keep, keep_off
+
+    def float_to_int16_groups(self, wav: torch.Tensor, off, grp, product: str = "f64", keep_thr: Optional[float] = 1e-5):
+        """The last step of split_text requests on the device (ctts_float_to_int16_groups): segments grp[g] .. grp[g+1]-1 of a packed
+        waveform (`decode_ragged`'s output) are request g's sentences.  ONE peak per group; the group's samples with |x| > keep_thr
+        are converted and written contiguously, in order (keep_thr None: nothing is stripped, a plain concatenation under one peak).
+        Returns (blob, starts): ONE uint8 device tensor -- a header of the groups' kept counts (int64 [n_grp], padded to 16 bytes), then
+        the int16 samples, group g's from element starts[g] = sum_{h<g} ceil8(n_h) on (for a decode: off[grp[g]]) -- so that a single
+        copy brings counts and bytes to the host; `unpack_groups(host_blob, starts)` cuts it.  Group g's result equals
+        `audio.float_to_int16(np.concatenate([w[np.abs(w) > keep_thr] for w in its segments]))` bit for bit."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        grp = np.ascontiguousarray(grp, dtype=np.int32)
+        assert wav.dim() == 1 and wav.dtype == torch.float32 and wav.is_cuda and wav.is_contiguous() and wav.numel() == int(off[-1])
+        n_seg, n_grp = len(off) - 1, len(grp) - 1
+        off_p, grp_p = off.ctypes.data_as(C.c_void_p), grp.ctypes.data_as(C.c_void_p)
+        sb = int(self.lib.ctts_float_to_int16_groups_scratch_bytes(off_p, n_seg, grp_p, n_grp))
+        if sb == 0:
+            _lib.check(-1, "ctts_float_to_int16_groups")      # the tables were refused: the library's message says why
+        starts = group_starts(off, grp)
+        hdr = (8 * n_grp + 15) // 16 * 16
+        dev = wav.device
+        blob = torch.empty((hdr + 2 * int(starts[-1]),), dtype=torch.uint8, device=dev)
+        tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), grp.view(np.uint8)])).to(dev)      # one upload: offsets, then groups
+        work = torch.empty((4 * n_grp + sb,), dtype=torch.uint8, device=dev)                            # peaks, then the tile counts
+        st = torch.cuda.current_stream(dev)
+        _lib.check(self.lib.ctts_float_to_int16_groups(wav.data_ptr(), blob.data_ptr() + hdr, blob.data_ptr(), tabs.data_ptr(), off_p, n_seg,
+                                                       tabs.data_ptr() + off.nbytes, grp_p, n_grp, {"f64": 0, "f32": 1}[product],
+                                                       -1.0 if keep_thr is None else float(keep_thr), work.data_ptr(),
+                                                       work.data_ptr() + 4 * n_grp, sb, st.cuda_stream), "ctts_float_to_int16_groups")
+        tabs.record_stream(st)
+        work.record_stream(st)
+        return blob, starts
+
+    @staticmethod
+    def unpack_groups(host_blob: np.ndarray, starts) -> List[np.ndarray]:
+        """`float_to_int16_groups`'s blob on the host -> one int16 array per group (views of the blob)"""
+        n_grp = len(starts) - 1
+        hdr = (8 * n_grp + 15) // 16 * 16
+        n_kept = host_blob[: 8 * n_grp].view(np.int64)
+        pcm = host_blob[hdr:].view(np.int16)
+        return [pcm[int(starts[g]): int(starts[g]) + int(n_kept[g])] for g in range(n_grp)]
 
     HALO_FRAMES = HALO_FRAMES
 

@@ -80,7 +80,7 @@ def _have_av() -> bool:
 
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
-               batch_refine: bool = False, refine_params=None):
+               batch_refine: bool = False, refine_params=None, batch_split: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -94,7 +94,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     (SpeechBatcher(refine=True)), with `refine_params` (a `RefineTextParams`, or a callable returning one; default
     `RefineTextParams(show_tqdm=False, manual_seed=42)`, a fixed seed like the code stage's), and the refined text is what is
     synthesised.  It applies to the requests the pool serves (non-streamed ones, streamed ones with `batch_streams`); without
-    `batch_refine` the key is ignored with the "unsupported parameters" warning, like any unknown key."""
+    `batch_refine` the key is ignored with the "unsupported parameters" warning, like any unknown key.  `batch_split` (batching only; off:
+    every path is as without it): a non-streamed request body may carry `"split_text": true` -- the reference's default handling of a long
+    input: the text is cut into sentences that run side by side in the pool under one voice (SpeechBatcher.submit(split_text=True));
+    with `"stream": true` the key is ignored with a warning.  A `voices` value may also be a dict `{"spk_emb"?, "spk_smp"?, "txt_smp"?}`
+    (a plain string means `spk_emb`): a cloned voice -- with it a split request needs no refer sentence."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -116,7 +120,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     app.state.batcher = batcher
     pool_streams = bool(batch_streams) and batcher is not None and bool(getattr(batcher, "streams", False))
     pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
-    allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set())
+    pool_split = bool(batch_split) and batcher is not None
+    allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
 
     def refine_of(request_data):         # the refine stage's parameters of a request that asks for it, or None
         if not (pool_refine and bool(request_data.get("refine_text", False))):
@@ -151,9 +156,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         return JSONResponse(status_code=getattr(exc, "status_code", 500), content={"error": {"message": str(exc), "type": exc.__class__.__name__}})
 
     def code_params(voice: Optional[str]):           # openai_api.py:185-205, field for field
+        v = voices.get(voice, voices.get("default"))
+        v = v if isinstance(v, dict) else {"spk_emb": v}      # a plain string: the speaker embedding; a dict: a cloned voice's fields too
         return chat.InferCodeParams(prompt="[speed_5]", top_P=0.5, top_K=10, temperature=0.1, repetition_penalty=1.1, max_new_token=2048,
                                     min_new_token=0, show_tqdm=False, ensure_non_empty=True, manual_seed=42,
-                                    spk_emb=voices.get(voice, voices.get("default")), spk_smp=None, txt_smp=None, stream_batch=24,
+                                    spk_emb=v.get("spk_emb"), spk_smp=v.get("spk_smp"), txt_smp=v.get("txt_smp"), stream_batch=24,
                                     stream_speed=12000, pass_first_n_batches=2)
 
     def infer(req: "SpeechRequest"):                 # openai_api.py:168-183,207-222
@@ -180,6 +187,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         rkw = {} if refine is None else {"refine": refine}
         if refine is not None and req.stream and not pool_streams:
             log.warning("refine_text is served by the batched path only: ignored for a serially streamed request")
+        if pool_split and bool(request_data.get("split_text", False)):
+            if req.stream:
+                log.warning("split_text is served for non-streamed requests only: ignored for a streamed request")
+            else:
+                rkw = {**rkw, "split_text": True}
         media = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "ogg": "audio/ogg"}[fmt]
 
         def encode(pcm: np.ndarray, header: bool) -> bytes:

@@ -23,14 +23,16 @@ parameters, `row_offset` and `total_rows` -- whatever runs beside it and whichev
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
+import dataclasses
 import itertools
 import queue
 import threading
 import time
 from collections import deque
 from concurrent.futures import Future
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Deque, Iterator, List, Optional, Tuple
 
 import numpy as np
@@ -636,6 +638,34 @@ class SpeechStream:
             self._b._in.put(_Cancel(self.rid))
 
 
+def split_rows(n: int, max_split_batch: int) -> List[Tuple[int, int]]:
+    """(row_offset, total_rows) of every sentence of an n-sentence split_text call: `Chat._infer` generates the sentences in batches of
+    `max_split_batch`, so sentence i holds sampling rows 4 (i % max_split_batch) .. + 3 of a batch of 4 * (its batch's size) rows"""
+    m = int(max_split_batch)
+    if m < 1:
+        raise ValueError("max_split_batch must be positive")
+    return [(GPT.n_vq * (i % m), GPT.n_vq * min(m, n - (i - i % m))) for i in range(n)]
+
+
+@dataclass(eq=False)
+class _SplitReq:
+    """one split_text request in flight (SpeechBatcher.submit(split_text=True)).  Its pool requests carry tuple ids: (rid, "r", i) sentence
+    i in the text pool, (rid, "A") the refer sentence alone (stage A), (rid, i) sentence i of stage B."""
+    rid: object
+    params: object                 # the caller's object until stage A ends, then a COPY with spk_smp / txt_smp filled
+    msb: int
+    texts: list                    # per sentence: its normalised (refine: refined) text, None while it is in the text pool
+    hids: list                     # per sentence: its hidden states, None until stage B delivered them
+    need_a: bool
+    keys: set = field(default_factory=set)     # its pool requests that are queued or resident
+    a_started: bool = False
+    a_done: bool = False
+    b_started: bool = False
+
+
+_NO_AUDIO = "the engine returned no audio (the first token was EOS)"
+
+
 class SpeechBatcher:
     """Serves many non-streamed speech requests from ONE per-request slot pool (continuous batching behind `server.create_app(...,
     batch_slots=N)`).  A single worker thread owns the pool and all GPU work of pooled requests: requests arrive through a thread-safe
@@ -667,6 +697,17 @@ class SpeechBatcher:
     text admissions, the most co-resident text requests, text steps, hand-offs, and the polls at which both pools had live slots.
     A request without `refine` takes the code pool directly, as without the option.
 
+    `submit(..., split_text=True)`: the reference's default handling of a long input (`Chat.infer(text: str, split_text=True)`), with the
+    request's sentences side by side in the slots.  The worker cuts the text with `core.split_sentences`; one sentence is an ordinary
+    request.  Otherwise: stage A (only without `params.spk_smp`) -- sentence 0 alone, its decode through the DVAE encoder on the device
+    (`Chat.refer_speaker`) becomes the `spk_smp` prompt of a COPY of the parameters; stage B -- every sentence (sentence 0 again) with the
+    sampling rows it has in the serial call's batches of `max_split_batch` (`split_rows`), in as many slots as are free, other requests
+    interleaving; when the last one is done the request is decoded by `Chat.decode_split_to_pcm16` -- with `ragged_decode`, together
+    with everything else that finished at that poll.  With `refine` the sentences pass the text pool first, as rows i of n; stage A
+    starts when sentence 0's text is back.  A sentence whose first token is EOS, one that does not fit a slot, or any other error fails
+    that request alone and frees all its slots; `cancel(future)` drops every sentence.  `occupancy()["split"]`: split requests,
+    stage-B sentences, the most sentences of one request co-resident.
+
     `make_pool` / `make_text_pool` (tests: fakes) build the pools; by default a per-request SlotPool on `chat.gpt` with the engine's generator mode,
     `cap` = the engine's position limit (the longest accepted prompt + max_new_token 2048 + slack), `hid_cap` 2048."""
 
@@ -694,6 +735,11 @@ class SpeechBatcher:
         self.completed = 0
         self.failed = 0
         self._stop = False
+        self._splits: dict = {}          # request id -> its _SplitReq
+        self._sub: dict = {}             # pool request id (a tuple) -> the _SplitReq it belongs to
+        self.split_requests = 0          # split_text requests of more than one sentence
+        self.split_sentences = 0         # sentences submitted to stage B
+        self.split_max_coresident = 0    # most stage-B sentences of ONE request resident at once
         if make_pool is None:
             def make_pool():
                 eng = chat.gpt
@@ -723,20 +769,34 @@ class SpeechBatcher:
         self._thread.start()
 
     # -- public -------------------------------------------------------------------------------------------------------------
-    def submit(self, text: str, params, refine=None) -> Future:
+    def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
-        result is that of `Chat.infer([text], skip_refine_text=False, params_refine_text=refine, ...)`."""
+        result is that of `Chat.infer([text], skip_refine_text=False, params_refine_text=refine, ...)`.
+        `split_text=True`: the result is that of `Chat.infer(text, split_text=True, max_split_batch=..., ragged_decode=True,
+        pcm16=True, ...)[0]` -- the same tokens per sentence, ONE waveform under one peak (see the class text).  `params` is never
+        modified (the serial call writes the speaker prompt into it)."""
         self._check_refine(refine)
+        if split_text and int(max_split_batch) < 1:
+            raise ValueError("max_split_batch must be positive")
         fut: Future = Future()
-        self._in.put((next(self._ids), text, params, fut, refine))
+        fut.rid = next(self._ids)
+        self._in.put((fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None))
         return fut
 
-    def submit_stream(self, text: str, params, refine=None) -> SpeechStream:
+    def cancel(self, fut: Future) -> None:
+        """drops a non-streamed request (every sentence of a split one, in whichever pool): its slots are retired at the next poll and
+        the Future is cancelled.  Nothing happens when it has completed already."""
+        self._in.put(_Cancel(fut.rid))
+
+    def submit_stream(self, text: str, params, refine=None, split_text: bool = False) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
-        whichever pool it is.  `refine`: as in `submit`."""
+        whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
+        is not served from the pool."""
+        if split_text:
+            raise ValueError("split_text is served for non-streamed requests only")
         if not self.streams:
             raise RuntimeError("this SpeechBatcher was built without streams=True")
         self._check_refine(refine)
@@ -764,6 +824,10 @@ class SpeechBatcher:
         return self._occupancy()
 
     def _occupancy(self) -> dict:
+        return {**self._occupancy_base(), "split": {"requests": self.split_requests, "sentences": self.split_sentences,
+                                                    "max_coresident": self.split_max_coresident}}
+
+    def _occupancy_base(self) -> dict:
         return {"slots": self.S, "active": len(getattr(self.pool, "active", {})), "queued": self._in.qsize() + len(getattr(self.pool, "queue", ())),
                 "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed,
                 "ragged_decode": self.ragged_decode, "decode_calls": self.decode_calls, "decoded": self.decoded,
@@ -778,6 +842,10 @@ class SpeechBatcher:
     def _fail(self, rid, e: BaseException):
         self.failed += 1
         self._stage1.pop(rid, None)
+        sp = self._splits.pop(rid, None)
+        if sp is not None:
+            for k in sp.keys:
+                self._sub.pop(k, None)
         fut = self._futs.pop(rid, None)
         if fut is not None and not fut.done():
             fut.set_exception(e)
@@ -789,10 +857,24 @@ class SpeechBatcher:
         """prompt of one request -> pool.submit (worker thread, GPU lock held)"""
         rid, text, params, fut = item[:4]
         refine = item[4] if len(item) > 4 else None
+        msb = item[5] if len(item) > 5 else None
         if isinstance(fut, SpeechStream):
             self._streams[rid] = fut
         else:
             self._futs[rid] = fut
+        if msb is not None:
+            try:
+                from .core import split_sentences
+                sents = split_sentences(text)
+                if len(sents) == 0:
+                    raise ValueError("split_text: the input holds no sentence")
+            except Exception as e:
+                self._fail(rid, e)
+                return
+            if len(sents) > 1:
+                self._take_split(rid, sents, params, refine, msb)
+                return
+            text = sents[0]               # one sentence: an ordinary request
         try:
             t = self.chat.normalizer(text, True, True, None)        # what Chat._infer does with do_text_normalization / homophones
             if refine is not None:       # stage 1: the refine-text pass, in the text pool (Chat._refine_text's prompt)
@@ -808,6 +890,9 @@ class SpeechBatcher:
 
     def _refined(self, rid, row: torch.Tensor) -> None:
         """a request's text row completed: hand it to the code pool (exactly once), as the text `Chat._infer` would synthesise"""
+        if rid in self._sub:
+            self._sentence_refined(rid, row)
+            return
         item = self._stage1.pop(rid, None)
         if item is None or (rid not in self._futs and rid not in self._streams):
             return                        # cancelled or failed meanwhile
@@ -828,15 +913,125 @@ class SpeechBatcher:
         if isinstance(fut, SpeechStream):
             kw["stream"] = StreamSpec(int(params.stream_batch), int(params.stream_speed), int(params.pass_first_n_batches))
         try:
-            chat = self.chat
-            ids, attn, tmask = chat.code_prompt([t], params)
-            emb = chat.prompt_embedding(ids, tmask, params, chat.tokenizer.spk_emb_ids)
-            keep = attn[0].bool()
-            self.pool.submit(rid, ids[0][keep], tmask[0][keep], max_new_token=params.max_new_token, params=params, emb=emb[0][keep.to(emb.device)],
-                             **kw)
-            self.admissions += 1
+            self._code_submit(rid, t, params, **kw)
         except Exception as e:        # this request's error, not the worker's
             self._fail(rid, e)
+
+    def _code_submit(self, key, t: str, params, **kw) -> None:
+        chat = self.chat
+        ids, attn, tmask = chat.code_prompt([t], params)
+        emb = chat.prompt_embedding(ids, tmask, params, chat.tokenizer.spk_emb_ids)
+        keep = attn[0].bool()
+        self.pool.submit(key, ids[0][keep], tmask[0][keep], max_new_token=params.max_new_token, params=params, emb=emb[0][keep.to(emb.device)],
+                         **kw)
+        self.admissions += 1
+
+    # -- split_text requests ------------------------------------------------------------------------------------------------
+    def _take_split(self, rid, sents: list, params, refine, msb: int) -> None:
+        """a request of several sentences: normalise them like `Chat._infer`, then the text pool (refine) or stage A / B"""
+        n = len(sents)
+        sp = _SplitReq(rid, params, int(msb), [None] * n, [None] * n, need_a=getattr(params, "spk_smp", None) is None)
+        self._splits[rid] = sp
+        self.split_requests += 1
+        try:
+            ts = [self.chat.normalizer(s_, True, True, None) for s_ in sents]
+            if refine is None:
+                sp.texts = ts
+                self._split_advance(sp)
+                return
+            for i, t in enumerate(ts):      # the serial call refines the sentences as ONE batch: row i of n
+                ids, attn, _ = self.chat.refine_prompt([t], refine)
+                key = (rid, "r", i)
+                self.text_pool.submit(key, ids[0][attn[0].bool()], max_new_token=refine.max_new_token, params=refine, row_offset=i, total_rows=n)
+                self._sub[key] = sp
+                sp.keys.add(key)
+                self.refine_admissions += 1
+        except Exception as e:
+            self._fail_split(sp, e)
+
+    def _split_advance(self, sp: _SplitReq) -> None:
+        """submits what has become possible: stage A once sentence 0's text is there, stage B once every text and the speaker prompt are.
+        Raises what the prompt builder or the pool raises (a sentence that does not fit a slot): the caller fails the request."""
+        if sp.need_a and not sp.a_started and sp.texts[0] is not None:
+            sp.a_started = True
+            self._split_submit(sp, (sp.rid, "A"), sp.texts[0], 0, GPT.n_vq)      # alone: a batch of one
+        if not sp.b_started and (sp.a_done or not sp.need_a) and all(t is not None for t in sp.texts):
+            sp.b_started = True
+            for i, ((ro, tr), t) in enumerate(zip(split_rows(len(sp.texts), sp.msb), sp.texts)):
+                self._split_submit(sp, (sp.rid, i), t, ro, tr)
+                self.split_sentences += 1
+
+    def _split_submit(self, sp: _SplitReq, key, t: str, row_offset: int, total_rows: int) -> None:
+        self._code_submit(key, t, sp.params, row_offset=row_offset, total_rows=total_rows)
+        self._sub[key] = sp
+        sp.keys.add(key)
+
+    def _fail_split(self, sp: _SplitReq, e: BaseException) -> None:
+        """fails ONE split request: every sentence of it leaves its pool (queued ones at once, resident ones at the next poll)"""
+        self._drop_split(sp)
+        self._fail(sp.rid, e)
+
+    def _drop_split(self, sp: _SplitReq) -> None:
+        for k in list(sp.keys):
+            self._sub.pop(k, None)
+            (self.text_pool if len(k) == 3 else self.pool).cancel(k)
+        sp.keys.clear()
+        self._splits.pop(sp.rid, None)
+
+    def _sentence_refined(self, key, row: torch.Tensor) -> None:
+        sp = self._sub.pop(key)
+        sp.keys.discard(key)
+        try:
+            if row.shape[0] == 0:
+                raise RuntimeError("the refine-text pass returned no tokens (the first token was EOS)")
+            sp.texts[key[2]] = self.chat.refined_text([row.cpu()])[0]
+            if all(t is not None for t in sp.texts):
+                self.handed += 1
+            self._split_advance(sp)
+        except Exception as e:
+            self._fail_split(sp, e)
+
+    def _sentence_done(self, key, hid: torch.Tensor) -> Optional[_SplitReq]:
+        """a stage-A / stage-B pool request completed -> the split request, once ALL its sentences are generated"""
+        sp = self._sub.pop(key)
+        sp.keys.discard(key)
+        try:
+            if hid.shape[0] == 0:       # (the serial call drops the whole split batch silently there)
+                raise RuntimeError(_NO_AUDIO)
+            if key[1] == "A":           # core.py:435-453: the refer sentence's audio becomes the speaker prompt of all sentences
+                smp = self.chat.refer_speaker([hid], on_device=True)
+                new = dict(spk_smp=smp, txt_smp=sp.texts[0])
+                if dataclasses.is_dataclass(sp.params):
+                    sp.params = dataclasses.replace(sp.params, **new)
+                else:
+                    sp.params = copy.copy(sp.params)
+                    for k, v in new.items():
+                        setattr(sp.params, k, v)
+                sp.a_done = True
+                self._split_advance(sp)
+                return None
+            sp.hids[key[1]] = hid
+        except Exception as e:
+            self._fail_split(sp, e)
+            return None
+        return sp if all(h is not None for h in sp.hids) else None
+
+    def _finish_splits(self, ready: list, plain: list = ()) -> None:
+        """ONE decode for the split requests that completed at this poll (+ `plain`: (rid, hid) of the ordinary requests of the same
+        poll, each a group of one sentence): Chat.decode_split_to_pcm16"""
+        for sp in ready:
+            self._splits.pop(sp.rid, None)
+        live = [(rid, [hid]) for rid, hid in plain if hid.shape[0] > 0] + [(sp.rid, sp.hids) for sp in ready]
+        for rid, hid in plain:
+            if hid.shape[0] == 0:
+                self._deliver(rid, RuntimeError(_NO_AUDIO))
+        try:
+            self._count_decode(len(live))
+            results = self.chat.decode_split_to_pcm16([g for _, g in live])
+        except Exception as e:         # the decode failed: its requests fail, the worker goes on
+            results = [e] * len(live)
+        for (rid, _), r in zip(live, results):
+            self._deliver(rid, r)
 
     def _drain(self, block: bool) -> bool:
         """moves arrived requests into the pool; False once close() was called"""
@@ -855,6 +1050,17 @@ class SpeechBatcher:
                     self._take(item)
 
     def _cancel(self, rid) -> None:
+        fut = self._futs.pop(rid, None)
+        if fut is not None:           # cancel(future): a non-streamed request, every sentence of a split one
+            sp = self._splits.get(rid)
+            if sp is not None:
+                self._drop_split(sp)
+            elif self._stage1.pop(rid, None) is not None:
+                self.text_pool.cancel(rid)
+            else:
+                self.pool.cancel(rid)
+            fut.cancel()
+            return
         h = self._streams.pop(rid, None)
         if h is not None:
             self.cancelled += 1
@@ -896,6 +1102,13 @@ class SpeechBatcher:
 
     def _between(self):
         self.max_coresident = max(self.max_coresident, len(self.pool.active))
+        if self._splits:
+            per: dict = {}
+            for v in self.pool.active.values():
+                k = getattr(v[0], "rid", v[0])
+                if isinstance(k, tuple) and len(k) == 2 and k[1] != "A" and k in self._sub:
+                    per[k[0]] = per.get(k[0], 0) + 1
+            self.split_max_coresident = max([self.split_max_coresident, *per.values()])
         self.lock.release()           # one decode chunk done: a streamed request may take the GPU now
         time.sleep(0)
         self._drain(block=False)
@@ -970,6 +1183,25 @@ class SpeechBatcher:
         if isinstance(got, StreamEvents):
             self._serve_chunks(got)
             return
+        if self._sub:                  # sentences of split requests: collected until their request is complete
+            items, ready = [], []
+            for it in (got if self.ragged_decode else [got]):
+                if it[0] in self._sub:
+                    sp = self._sentence_done(it[0], it[2])
+                    if sp is not None:
+                        ready.append(sp)
+                else:
+                    items.append(it)
+            if ready and self.ragged_decode:      # one decode for everything that finished at this poll
+                for rid, _, hid in items:
+                    self._end_stream(rid, hid)
+                self._finish_splits(ready, [(rid, hid) for rid, _, hid in items if rid in self._futs])
+                return
+            if ready:
+                self._finish_splits(ready)
+            if not items:
+                return
+            got = items if self.ragged_decode else items[0]
         for rid, _, hid in (got if self.ragged_decode else [got]):     # a stream's result: its chunks went out already
             self._end_stream(rid, hid)
         if self.ragged_decode:

@@ -359,6 +359,24 @@ int ctts_vocos_decode_ragged(ctts_codec* c, const float* mel, const int32_t* tok
 int ctts_float_to_int16_ragged(const float* wav, int16_t* pcm, uint8_t* keep_bits, const int64_t* off_dev, const int64_t* off_host,
                                int32_t n_seg, int32_t product, float keep_thr, uint32_t* peak, void* stream);
 
+/* Grouped strip, convert and compact: the last step of a split_text request (one concatenated waveform, one peak over all its sentences)
+ * for many requests in one call.  wav / off as in ctts_float_to_int16_ragged; grp [n_grp + 1] (int32, on the device and the host, the two
+ * must agree): segment indices, ascending, grp[0] = 0, grp[n_grp] = n_seg -- segments grp[g] .. grp[g+1]-1 are request g's sentences, in
+ * order.  ONE peak and scale per group (`product` as in ctts_float_to_int16).  Group g's kept samples (|x| > keep_thr) are written
+ * contiguously, in order, from element gs[g] = sum_{h<g} ceil8(n_h) of pcm (n_h: group h's unstripped sample count) and their number to
+ * n_kept[g]; elements behind a group's kept samples are unspecified.  Where every group starts on a multiple of 8 samples -- any decode:
+ * a segment holds 256 (2 T - 1) samples -- gs[g] = ceil8(off[grp[g]]) = off[grp[g]], the group's unstripped start; for other offsets
+ * ceil8(off[grp[g]]) + n_g could pass ceil8(off[grp[g+1]]), so the padded running sum is the rule.  pcm: sum_g ceil8(n_g) int16, 16-byte
+ * aligned.  keep_thr < 0: nothing is stripped -- a plain concatenation under one peak (n_kept[g] = n_g).  An all-zero group converts to
+ * zeros.  peak: [n_grp] uint32 device scratch; scratch: ctts_float_to_int16_groups_scratch_bytes(...) bytes of device scratch (per-tile
+ * kept counts).  Refused before anything is launched: n_grp < 1, an empty group, a group table that does not run 0 .. n_seg ascending,
+ * empty segments / non-ascending offsets, a null peak or count buffer, a group of 2^31 samples or more.  Stream-ordered: a memset and three
+ * launches (group peaks + tile counts, a scan per group, convert + scatter); no workgroup waits on another. */
+size_t ctts_float_to_int16_groups_scratch_bytes(const int64_t* off_host, int32_t n_seg, const int32_t* grp_host, int32_t n_grp);   /* 0: bad tables */
+int ctts_float_to_int16_groups(const float* wav, int16_t* pcm, int64_t* n_kept, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                               const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp, int32_t product, float keep_thr, uint32_t* peak,
+                               void* scratch, size_t scratch_bytes, void* stream);
+
 /* Window decode: the chunks of many streamed utterances that are due at one poll, in ONE ragged pass, each at its own position.
  * hid: a hidden-state store [n_slots][hid_cap][768] float32 (a slot pool's; slot_stride / row_stride in floats, multiples of 4, rows 16-byte
  * aligned).  A window is token rows [t_lo, t_hi) of one slot; it is decoded as one ragged segment -- its edges are sequence edges -- and

@@ -4,6 +4,12 @@ Prints one JSON line.  Not a bench.py leg.
 
     python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R]]
     python tools/serve_load.py --refine [--refine-max-new 64] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
+    python tools/serve_load.py --split [--split-sentences 6] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
+
+--split: N concurrent MULTI-SENTENCE requests (the reference's default `split_text` handling of a long input), in one process: (a) through
+`Chat.infer(text, split_text=True, ragged_decode=True, pcm16=True)` one by one under a lock, (b) through the batcher
+(`SpeechBatcher.submit(text, params, split_text=True)`, ragged_decode on: a request's sentences side by side in the slots).  Audio-s/s,
+p50 / p95 latency, acoustic-decoder calls (stage A's included) and the batcher's `split` occupancy.
 
 --refine: the same N concurrent requests WITH the refine-text pass (the reference's default two-stage call), in one process: (a) through
 `Chat.infer(skip_refine_text=False)` one at a time under a lock, (b) through the two-pool batcher (`SpeechBatcher(refine=True,
@@ -152,6 +158,37 @@ def stream_main(chat, voices, a):
                           single_stream_first_byte_s=single)))
 
 
+def leg(call, n, stream=False):
+    """n threads, `call(i)` -> the waveform, or an iterator of chunks"""
+    lat, first, samples = [0.0] * n, [float("nan")] * n, [0] * n
+
+    def one(i):
+        t0 = time.perf_counter()
+        try:
+            got = call(i)
+            for c in (got if stream else [got]):
+                if np.asarray(c).size and first[i] != first[i]:
+                    first[i] = time.perf_counter() - t0
+                samples[i] += int(np.asarray(c).size)
+        except Exception as e:
+            print(f"request {i}: {e}", file=sys.stderr)
+        lat[i] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    ths = [threading.Thread(target=one, args=(i,)) for i in range(n)]
+    for th in ths:
+        th.start()
+    for th in ths:
+        th.join()
+    wall = time.perf_counter() - t0
+    audio = sum(samples) / server.SAMPLE_RATE
+    pct = lambda v, q: round(float(np.nanpercentile(v, q)), 4)
+    out = dict(failed=sum(x == 0 for x in samples), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3), audio_s=round(audio, 2),
+               p50_s=pct(lat, 50), p95_s=pct(lat, 95))
+    if stream:
+        out.update(first_chunk_p50_s=pct(first, 50), first_chunk_p95_s=pct(first, 95))
+    return out
+
+
 def refine_main(chat, voices, a):
     from chattts_amd.serving import SpeechBatcher
     names = sorted(voices)
@@ -161,35 +198,6 @@ def refine_main(chat, voices, a):
         return chat.InferCodeParams(prompt="[speed_5]", top_P=0.5, top_K=10, temperature=0.1, repetition_penalty=1.1, max_new_token=2048,
                                     show_tqdm=False, manual_seed=42, spk_emb=voices[names[i % len(names)]])
 
-    def leg(call, n, stream):
-        """n threads, `call(i)` -> the waveform, or an iterator of chunks"""
-        lat, first, samples = [0.0] * n, [float("nan")] * n, [0] * n
-
-        def one(i):
-            t0 = time.perf_counter()
-            try:
-                got = call(i)
-                for c in (got if stream else [got]):
-                    if np.asarray(c).size and first[i] != first[i]:
-                        first[i] = time.perf_counter() - t0
-                    samples[i] += int(np.asarray(c).size)
-            except Exception as e:
-                print(f"request {i}: {e}", file=sys.stderr)
-            lat[i] = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        ths = [threading.Thread(target=one, args=(i,)) for i in range(n)]
-        for th in ths:
-            th.start()
-        for th in ths:
-            th.join()
-        wall = time.perf_counter() - t0
-        audio = sum(samples) / server.SAMPLE_RATE
-        pct = lambda v, q: round(float(np.nanpercentile(v, q)), 4)
-        out = dict(failed=sum(x == 0 for x in samples), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3), audio_s=round(audio, 2),
-                   p50_s=pct(lat, 50), p95_s=pct(lat, 95))
-        if stream:
-            out.update(first_chunk_p50_s=pct(first, 50), first_chunk_p95_s=pct(first, 95))
-        return out
     lock = threading.Lock()
     res = {}
     for stream in (False, True):
@@ -223,6 +231,50 @@ def refine_main(chat, voices, a):
                           stream_speedup=round(res["pooled_stream"]["audio_s_per_s"] / res["serial_stream"]["audio_s_per_s"], 2))))
 
 
+def split_main(chat, voices, a):
+    """N concurrent multi-sentence requests: `Chat.infer(text, split_text=True, ragged_decode=True, pcm16=True)` one by one under a lock
+    against `SpeechBatcher.submit(text, params, split_text=True)` (ragged_decode on), in one process"""
+    from chattts_amd.serving import SpeechBatcher
+    names = sorted(voices)
+    texts = ["\n".join(TEXTS[(i + j) % len(TEXTS)] for j in range(a.split_sentences)) for i in range(a.n)]
+
+    def code_params(i):
+        return chat.InferCodeParams(prompt="[speed_5]", top_P=0.5, top_K=10, temperature=0.1, repetition_penalty=1.1, max_new_token=2048,
+                                    show_tqdm=False, manual_seed=42, spk_emb=voices[names[i % len(names)]])
+    lock = threading.Lock()
+    decodes = [0]
+    ragged, alone = chat.codec.decode_ragged, chat.codec.decode_to_wavs
+
+    def counted(fn):
+        def wrap(*args, **kw):
+            decodes[0] += 1
+            return fn(*args, **kw)
+        return wrap
+
+    def serial(i):
+        with lock:
+            return chat.infer(texts[i], skip_refine_text=True, split_text=True, ragged_decode=True, pcm16=True, params_infer_code=code_params(i))[0]
+    leg(serial, 1)                                                       # first-call costs out of the burst
+    chat.codec.decode_ragged, chat.codec.decode_to_wavs = counted(ragged), counted(alone)
+    try:
+        res = {"serial": {**leg(serial, a.n), "decode_calls": decodes[0]}}
+        decodes[0] = 0
+        b = SpeechBatcher(chat, a.slots, threading.Lock(), ragged_decode=True)
+        try:
+            def pooled(i):
+                return b.submit(texts[i], code_params(i), split_text=True).result()
+            leg(pooled, 1)
+            decodes[0] = 0
+            res["pooled"] = {**leg(pooled, a.n), "decode_calls": decodes[0], "split": b.occupancy()["split"],
+                             "max_coresident": b.occupancy()["max_coresident"]}
+        finally:
+            b.close()
+    finally:
+        del chat.codec.decode_ragged, chat.codec.decode_to_wavs
+    print(json.dumps(dict(metric="serve_load_split", n=a.n, slots=a.slots, max_new=a.max_new, sentences=a.split_sentences, dtype=a.dtype, **res,
+                          speedup=round(res["pooled"]["audio_s_per_s"] / res["serial"]["audio_s_per_s"], 2))))
+
+
 def sample_k_ms(eng, per_request, slots, steps=64):
     """mean sample_k time (profile tag 9) over `steps` eager decode steps of a full pool of identical requests"""
     pool = SlotPool(eng, slots=slots, cap=512, hid_cap=256, manual_seed=42, per_request=per_request)
@@ -254,17 +306,25 @@ def main():
     ap.add_argument("--repeat", type=int, default=5, help="--stream: single-stream runs per leg (run-to-run spread)")
     ap.add_argument("--refine", action="store_true", help="two-stage requests: Chat.infer serially vs the two-pool batcher")
     ap.add_argument("--refine-max-new", type=int, default=64, help="--refine: max_new_token of the refine-text pass")
+    ap.add_argument("--split", action="store_true", help="multi-sentence requests: Chat.infer(split_text=True) serially vs the batcher's split path")
+    ap.add_argument("--split-sentences", type=int, default=6, help="--split: sentences per request")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     gold = os.path.join(ROOT, "tests", "golden")
     with open(os.path.join(gold, "spk_stat.txt"), encoding="utf-8") as f:
         spk_stat = f.read()
     chat = Chat()
-    assert chat.load(state_dicts=synthetic_all(), device=dev, dtype=a.dtype, tokenizer=os.path.join(gold, "tokenizer"), spk_stat=spk_stat)
+    sds = synthetic_all()
+    if a.split:       # the refer sentence's audio goes through the full DVAE's encoder
+        from chattts_amd.weights import synthetic_dvae
+        sds = {**sds, "dvae": synthetic_dvae()}
+    assert chat.load(state_dicts=sds, device=dev, dtype=a.dtype, tokenizer=os.path.join(gold, "tokenizer"), spk_stat=spk_stat)
     torch.manual_seed(5)
     voices = {"default": chat.sample_random_speaker(), "alloy": chat.sample_random_speaker(), "echo": chat.sample_random_speaker()}
     orig = chat.InferCodeParams
     chat.InferCodeParams = lambda **kw: orig(**{**kw, "max_new_token": a.max_new})
+    if a.split:
+        return split_main(chat, voices, a)
     if a.refine:
         return refine_main(chat, voices, a)
     if a.stream:
