@@ -126,6 +126,8 @@ SIGNATURES = {
     "ctts_float_to_int16_ragged": (C.c_int, [P, P, P, P, P, I32, I32, F, P, P]),
     "ctts_float_to_int16_groups_scratch_bytes": (SZ, [P, I32, P, I32]),
     "ctts_float_to_int16_groups": (C.c_int, [P, P, P, P, P, I32, P, P, I32, I32, F, P, P, SZ, P]),
+    "ctts_resample_supported": (I32, [I32, I32, I32]),
+    "ctts_resample_ragged": (C.c_int, [P, P, P, P, P, P, I32, P, P, I32, P, I32, I32, I32, P]),
     "ctts_codec_windows_workspace_bytes": (SZ, [I32, I32]),
     "ctts_codec_decode_windows": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, I32, P, P, I32, F, P, SZ, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),

@@ -41,3 +41,29 @@ def pcm_to_wav_bytes(wav: np.ndarray, sample_rate: int = 24000) -> bytes:
         wf.setframerate(sample_rate)
         wf.writeframes(float_to_int16(np.asarray(wav, dtype=np.float32).reshape(-1)).astype("<i2").tobytes())
     return buf.getvalue()
+
+
+def load_wav(data: bytes):
+    """RIFF/WAVE bytes -> (float32 mono samples in [-1, 1), sample rate): the front door of voice cloning from an uploaded clip
+    (`Chat.sample_audio_speaker(wav, rate)`, the endpoint's POST /v1/audio/voices).  Integer PCM of 8 (unsigned), 16 or 32 bits, any
+    number of channels (averaged to mono), read with the stdlib `wave` module.  Anything else -- a float or compressed WAVE, 24-bit
+    samples, no RIFF at all, no frames -- raises ValueError naming what was found."""
+    try:
+        with wave.open(BytesIO(bytes(data)), "rb") as wf:
+            ch, width, rate, n = wf.getnchannels(), wf.getsampwidth(), wf.getframerate(), wf.getnframes()
+            raw = wf.readframes(n)
+    except (wave.Error, EOFError) as e:     # `wave` reads integer PCM only: "unknown format: 3" is a float file, 85 an mp3 in a RIFF
+        raise ValueError(f"not an integer-PCM WAV file: {e or 'truncated or empty input'}") from None
+    if width not in (1, 2, 4):
+        raise ValueError(f"unsupported WAV sample width: {8 * width} bits (8-, 16- and 32-bit PCM are supported)")
+    if ch < 1 or rate <= 0:
+        raise ValueError(f"bad WAV header: {ch} channels at {rate} Hz")
+    frames = len(raw) // (width * ch)
+    if frames == 0:
+        raise ValueError("the WAV file holds no samples")
+    raw = raw[: frames * width * ch]
+    if width == 1:
+        x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float64) - 128.0) / 128.0
+    else:
+        x = np.frombuffer(raw, dtype="<i2" if width == 2 else "<i4").astype(np.float64) / float(1 << (8 * width - 1))
+    return x.reshape(frames, ch).mean(axis=1).astype(np.float32), int(rate)

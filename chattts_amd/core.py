@@ -194,10 +194,20 @@ class Chat:
             raise RuntimeError("speaker statistics not loaded: pass spk_stat= to Chat.load")
         return self.speaker.sample_random()
 
-    def sample_audio_speaker(self, wav) -> str:
-        """24 kHz waveform -> `spk_smp` string: DVAE encode to [4,T] codes, packed like `Speaker.encode_prompt`"""
+    def sample_audio_speaker(self, wav, sample_rate: Optional[int] = None) -> str:
+        """waveform -> `spk_smp` string: DVAE encode to [4,T] codes, packed like `Speaker.encode_prompt`.  `sample_rate`: the clip's rate;
+        None or 24000: the clip is encoded as it is (the reference's callers resample with `load_audio(path, 24000)` first,
+        examples/web/funcs.py:121-122); any other rate: the clip is uploaded and resampled to 24 kHz on the device
+        (CodecEngine.resample) and goes to the encoder from there."""
         if self.dvae is None:
             raise RuntimeError("full DVAE not loaded (asset/DVAE.safetensors, or state_dicts['dvae'])")
+        if sample_rate is not None and int(sample_rate) != CodecEngine.SAMPLE_RATE:
+            if self.codec is None:
+                raise RuntimeError("resampling a clip needs the acoustic decoder's engine (Chat.load)")
+            if isinstance(wav, np.ndarray):
+                wav = torch.from_numpy(np.ascontiguousarray(wav))
+            wav = wav.reshape(-1).to(torch.float32).contiguous().to(self.codec.device)
+            wav = self.codec.resample(wav, int(sample_rate), CodecEngine.SAMPLE_RATE)
         return Speaker.encode_prompt(self.dvae.sample_audio(wav))
 
     def refer_speaker(self, rows, use_decoder: bool = True, *, on_device: bool = False, release=None) -> str:
@@ -265,12 +275,13 @@ class Chat:
             24, params.manual_seed, self.context, **kw))
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None, *,
-                       ragged: bool = False):
+                       ragged: bool = False, sample_rate=None):
         """`Chat._decode_to_wavs` (core.py:513-539) -> np.float32 [B, n]: per-row hidden states [T_b,768] through the
         decoder, or (use_decoder=False) per-row token ids [T_b,4] through the full DVAE's codebook; then Vocos.
         `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded).
         `ragged=True` (not the reference's batch semantics): every row decoded as if alone, in one pass (CodecEngine.decode_ragged)
-        -> List[np.ndarray], row b's 256 (2 T_b - 1) samples; the decoder path only."""
+        -> List[np.ndarray], row b's 256 (2 T_b - 1) samples; the decoder path only.
+        `sample_rate` (None: 24000; with `ragged` also one per row): the waveforms are resampled on the device behind the ISTFT."""
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
@@ -279,29 +290,34 @@ class Chat:
                 raise ValueError("ragged decoding decodes every row at its own length: pad_to does not apply")
             if len(result_list) == 0:
                 return []
-            wav, off = self.codec.decode_ragged(list(result_list))
+            wav, off = self.codec.decode_ragged(list(result_list), sample_rate=sample_rate)
             return ragged_views(self.codec.to_host(wav), off)
         if len(result_list) == 0:
             return np.array([], dtype=np.float32)
         if use_decoder:
-            return self.codec.to_host(self.codec.decode_to_wavs(result_list, pad_to=pad_to))
-        return self.codec.to_host(self.codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to)))
+            return self.codec.to_host(self.codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate))
+        wav = self.codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to))
+        return self.codec.to_host(wav if sample_rate is None else self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate)))
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
-                        product: str = "f64", *, ragged: bool = False) -> List[np.ndarray]:
+                        product: str = "f64", *, ragged: bool = False, sample_rate=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
         Returns one int16 array per utterance, equal to `float_to_int16(wav[np.abs(wav) > 1e-5])` bit for bit (the strip only removes
-        samples that are far below one count, so the peak -- hence the scale -- is that of the unstripped row)."""
+        samples that are far below one count, so the peak -- hence the scale -- is that of the unstripped row).
+        `sample_rate` (None: 24000; with `ragged` also one per row): `wav` above is the waveform resampled on the device directly
+        behind the ISTFT; strip and conversion are the same kernels, fed the resampled samples."""
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
         if ragged:
-            return self._decode_to_pcm16_ragged(result_list, strip, product)
+            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate)
         if len(result_list) == 0:
             return []
         wav = self.codec.decode_to_wavs(result_list) if use_decoder else self.codec.vocos_decode(self.dvae.decode_codes(result_list))
+        if sample_rate is not None:
+            wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
         pcm, keep = self.codec.float_to_int16(wav, per_row=True, product=product, keep_thr=1e-5 if strip else None)
         pcm_h = self.codec.to_host(pcm)
         if not strip:
@@ -310,14 +326,14 @@ class Chat:
         n = pcm_h.shape[1]
         return [pcm_h[b][np.unpackbits(keep_h[b])[:n].astype(bool)] for b in range(pcm_h.shape[0])]
 
-    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str) -> List[np.ndarray]:
+    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None) -> List[np.ndarray]:
         """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
         PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's result equals
         `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w."""
         if len(result_list) == 0:
             return []
         codec = self.codec
-        wav, off = codec.decode_ragged(list(result_list))
+        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate)
         n = wav.numel()
         kb = int(keep_offsets(off)[-1]) if strip else 0
         blob = torch.empty(((2 * n + kb + 15) // 16 * 16,), dtype=torch.uint8, device=wav.device)
@@ -332,12 +348,14 @@ class Chat:
         keep_h = host[2 * n: 2 * n + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
-    def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64") -> List[np.ndarray]:
+    def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
         device) and ONE device-to-host copy.  Request g's result equals
-        `float_to_int16(np.concatenate([w[np.abs(w) > 1e-5] for w in its sentences' alone decodes]))` bit for bit."""
+        `float_to_int16(np.concatenate([w[np.abs(w) > 1e-5] for w in its sentences' alone decodes]))` bit for bit.
+        `sample_rate` (None: 24000; or one per request): every sentence is resampled alone, on the device, behind the ISTFT; the
+        grouped conversion then works on offsets that are no multiples of 8."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -347,7 +365,11 @@ class Chat:
         grp = np.zeros(len(groups) + 1, np.int32)
         np.cumsum([len(g) for g in groups], out=grp[1:])
         codec = self.codec
-        wav, off = codec.decode_ragged([h for g in groups for h in g])
+        if sample_rate is not None and np.ndim(sample_rate) != 0:
+            if len(sample_rate) != len(groups):
+                raise ValueError("decode_split_to_pcm16: one sample rate per request, or one for all")
+            sample_rate = [int(r) for r, g in zip(sample_rate, groups) for _ in g]
+        wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate)
         blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None)
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts)]
 
@@ -517,7 +539,7 @@ class Chat:
     def infer(self, text, stream=False, lang=None, skip_refine_text=False, refine_text_only=False, use_decoder=True,
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
-              *, pcm16: bool = False, ragged_decode: bool = False):
+              *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -525,7 +547,16 @@ class Chat:
         device so that half the bytes cross PCIe: `infer(t, pcm16=True)[i] == float_to_int16(infer(t)[i])` bit for bit.
         `ragged_decode=True` (keyword-only, non-streamed only; NOT the reference's batch semantics): every utterance of a batch is
         decoded as if alone (CodecEngine.decode_ragged) instead of as a row of the reference's zero-padded batch, so a shorter
-        utterance's last second no longer depends on the longer ones it was batched with."""
+        utterance's last second no longer depends on the longer ones it was batched with.
+        `sample_rate` (keyword-only, non-streamed only): the rate of the returned audio.  Every decoded waveform is resampled on the
+        device directly behind the ISTFT (CodecEngine.resample); the silence strip, the 16-bit conversion and the concatenation of a
+        split request work on the resampled samples.  The refer sentence's audio that becomes `spk_smp` of a split request stays at
+        24 kHz.  A streamed call at another rate raises: carrying the filter's state across chunks is separate work."""
+        sample_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        if stream and sample_rate != CodecEngine.SAMPLE_RATE:
+            raise ValueError("sample_rate applies to non-streamed inference only (a stream's chunks would need the filter's state carried "
+                             "across them, which is not implemented)")
+        rate = None if sample_rate == CodecEngine.SAMPLE_RATE else sample_rate
         if ragged_decode and stream:
             raise ValueError("ragged_decode applies to non-streamed inference only")
         if ragged_decode and not use_decoder:
@@ -541,7 +572,8 @@ class Chat:
         split_dev = bool(split_text and pcm16 and ragged_decode and not stream and not refine_text_only)
         res_gen = self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
-                              pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev)
+                              pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
+                              sample_rate=rate)
         if stream:
             return res_gen
         if refine_text_only:
@@ -549,7 +581,7 @@ class Chat:
         if split_dev:
             rows = [h for hids in res_gen for h in hids]
             if rows:
-                return self.decode_split_to_pcm16([rows])
+                return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}))
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
@@ -561,7 +593,7 @@ class Chat:
 
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
-               ragged: bool = False, raw: bool = False):
+               ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None):
         """core.py:395-503 (generator).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -591,15 +623,16 @@ class Chat:
             for result in self._infer_code(batch, stream, self.device, use_decoder, params_infer_code):
                 if not stream:
                     src = result.hiddens if use_decoder else result.ids
+                    rkw = {} if sample_rate is None else {"sample_rate": sample_rate}      # 24 kHz: today's call, argument for argument
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
                         rows = [h.clone() for h in src]
                         result.destroy()
                         yield rows
                         continue
                     if ragged:      # every utterance as if alone (Chat.infer's ragged_decode)
-                        wavs = self.decode_to_pcm16(src, ragged=True) if pcm16 else self.decode_to_wavs(src, ragged=True)
+                        wavs = self.decode_to_pcm16(src, ragged=True, **rkw) if pcm16 else self.decode_to_wavs(src, ragged=True, **rkw)
                     else:
-                        wavs = self.decode_to_pcm16(src, use_decoder) if pcm16 else self.decode_to_wavs(src, use_decoder)
+                        wavs = self.decode_to_pcm16(src, use_decoder, **rkw) if pcm16 else self.decode_to_wavs(src, use_decoder, **rkw)
                     result.destroy()
                     yield wavs
                     continue

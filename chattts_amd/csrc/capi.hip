@@ -1390,7 +1390,39 @@ extern "C" int ctts_float_to_int16_groups(const float* wav, int16_t* pcm, int64_
                                   (long long*)n_kept, (hipStream_t)stream));
   return 0;
 }
-extern "C" int ctts_copy_bytes(void* dst, const void* src, size_t bytes, void* stream) {
+extern "C" int32_t ctts_resample_supported(int32_t L, int32_t M, int32_t K) { return resample_mode(L, M, K); }
+extern "C" int ctts_resample_ragged(const float* x, const int64_t* off_in_dev, const int64_t* off_in_host, float* y, const int64_t* off_out_dev,
+                                    const int64_t* off_out_host, int32_t n_seg, const int32_t* sel_dev, const int32_t* sel_host, int32_t n_sel,
+                                    const float* taps, int32_t L, int32_t M, int32_t K, void* stream) {
+  const char* who = "ctts_resample_ragged";
+  if (!x || !y || !off_in_dev || !off_in_host || !off_out_dev || !off_out_host || !taps || n_seg < 1) return fail("%s: bad arguments", who);
+  if ((sel_dev == nullptr) != (sel_host == nullptr)) return fail("%s: the segment selection must be given on the device and the host, or on neither", who);
+  if (L < 1 || M < 1 || L == M) return fail("%s: need L != M, both positive (got %d/%d)", who, L, M);
+  if (resample_mode(L, M, K) == 0)
+    return fail("%s: conversion %d/%d with %d taps is not supported (K = 2 width + M; a tile's input span within %d floats, the table within %d)",
+                who, L, M, K, RS_LDS_FLOATS, RS_TAB_MAX);
+  if (off_in_host[0] != 0 || off_out_host[0] != 0) return fail("%s: the first offsets must be 0", who);
+  for (int i = 0; i < n_seg; ++i) {
+    if (off_in_host[i + 1] <= off_in_host[i]) return fail("%s: segment %d is empty or the input offsets do not ascend", who, i);
+    if (off_out_host[i + 1] <= off_out_host[i]) return fail("%s: segment %d's output is empty or the output offsets do not ascend", who, i);
+  }
+  if (off_out_host[n_seg] >= (1ll << 31)) return fail("%s: the output holds 2^31 samples or more", who);
+  const int n_launch = sel_host ? n_sel : n_seg;
+  if (n_launch < 1 || n_launch > 65535) return fail("%s: need 1 <= converted segments <= 65535 (got %d)", who, n_launch);
+  long long n_out_max = 0;
+  for (int q = 0; q < n_launch; ++q) {
+    const int i = sel_host ? sel_host[q] : q;
+    if (i < 0 || i >= n_seg) return fail("%s: selected segment %d is outside the pack", who, i);
+    const long long n = off_in_host[i + 1] - off_in_host[i], no = off_out_host[i + 1] - off_out_host[i];
+    if (n >= (1ll << 31) || no != (n * L + M - 1) / M) return fail("%s: segment %d: %lld samples in need ceil(n L / M) out, got %lld", who, i, n, no);
+    n_out_max = std::max(n_out_max, no);
+  }
+  CttsDeviceGuard dg(stream);
+  CK(launch_resample_ragged(x, (const long long*)off_in_dev, y, (const long long*)off_out_dev, sel_dev, n_launch, n_out_max, taps, L, M, K,
+                            (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ctts_copy_bytes(void* dst,const void* src, size_t bytes, void* stream) {
   if (!dst || !src || (bytes & 15) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return fail("ctts_copy_bytes: pointers and size must be 16-byte aligned");
   CttsDeviceGuard dg(stream);
   CK(launch_copy16(src, dst, bytes, (hipStream_t)stream));

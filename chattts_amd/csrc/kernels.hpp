@@ -476,6 +476,17 @@ hipError_t launch_crop_pcm16_windows(const float* wav, const CodecWindow* win, i
                                      uint8_t* keep, hipStream_t st);
 hipError_t launch_copy16(const void* src, void* dst, size_t bytes, hipStream_t st);   // shader copy (dst may be pinned host memory)
 
+// ---- sample-rate conversion (resample.hip) -----------------------------------------------------
+#define RS_TILE 2048          // output samples per workgroup
+#define RS_LDS_FLOATS 16384   // 64 KiB of LDS per workgroup: a tile's input span, plus the filter table where both fit
+#define RS_TAB_MAX (1 << 20)  // floats: the largest [L][K] table (read through L2 beyond the LDS)
+long long rs_span_max(int L, int M, int K);
+int resample_mode(int L, int M, int K);   // 0 unsupported, 1 table through L2, 2 table in LDS
+// packed segments by L/M: segment s = x[off_in[s], off_in[s+1]) -> y[off_out[s], off_out[s+1]) (ceil(n_s L / M) samples), each as if alone;
+// sel (or null: segments 0 .. n_launch-1): the n_launch segment indices this call converts; n_out_max: their longest output (grid size)
+hipError_t launch_resample_ragged(const float* x, const long long* off_in, float* y, const long long* off_out, const int32_t* sel, int n_launch,
+                                  long long n_out_max, const float* taps, int L, int M, int K, hipStream_t st);
+
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------
 // |STFT| of one waveform: center=True reflect padding, frame f = padded[256 f, 256 f + 1024) * window, 1024-point FFT,
 // mag [F][516] (bins 0..512, then 3 zeros so that the mel projection's K is a multiple of 4)

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import resample as RS
 from ._sync import wait_event, wait_stream
 from .config import DVAE, GPT, VOCOS
 from .rng import ExpDraws, penalty_table
@@ -1366,8 +1367,96 @@ class CodecEngine:
                    "ctts_float_to_int16")
         return pcm, keep
 
+    # -- sample-rate conversion (csrc/resample.hip) ----------------------------------------------------------------------------------
+    SAMPLE_RATE = 24000      # what the acoustic decoder produces and the DVAE encoder expects
+
+    def _resample_taps(self, orig: int, new: int) -> torch.Tensor:
+        """the float32 [L, K] polyphase table of a rate pair on the device, built once (resample.taps, float64 on the host)"""
+        cache = self.__dict__.setdefault("_rs_taps", {})
+        key = (int(orig), int(new))
+        if key not in cache:
+            cache[key] = torch.from_numpy(np.ascontiguousarray(RS.taps(*key), dtype=np.float32)).to(self.device)
+        return cache[key]
+
+    def _resample_launch(self, x: torch.Tensor, off: np.ndarray, y: torch.Tensor, off_out: np.ndarray, sel, orig: int, new: int) -> None:
+        """ctts_resample_ragged over segments `sel` (None: all) of the pack x / off into y / off_out"""
+        L, M = RS.ratio(orig, new)
+        _, K = RS.geometry(L, M)
+        taps = self._resample_taps(orig, new)
+        n_seg = len(off) - 1
+        sel_h = None if sel is None else np.ascontiguousarray(sel, dtype=np.int32)
+        parts = [off.view(np.uint8), off_out.view(np.uint8)] + ([] if sel_h is None else [sel_h.view(np.uint8)])
+        tabs = torch.from_numpy(np.concatenate(parts)).to(x.device)       # one upload: input offsets, output offsets, the selection
+        st = torch.cuda.current_stream(x.device)
+        base = tabs.data_ptr()
+        _lib.check(self.lib.ctts_resample_ragged(
+            x.data_ptr(), base, off.ctypes.data_as(C.c_void_p), y.data_ptr(), base + off.nbytes, off_out.ctypes.data_as(C.c_void_p), n_seg,
+            None if sel_h is None else base + off.nbytes + off_out.nbytes, None if sel_h is None else sel_h.ctypes.data_as(C.c_void_p),
+            0 if sel_h is None else len(sel_h), taps.data_ptr(), L, M, K, st.cuda_stream), "ctts_resample_ragged")
+        tabs.record_stream(st)
+
+    def resample(self, wav: torch.Tensor, orig: int, new: int, offsets=None):
+        """Windowed-sinc polyphase conversion orig -> new Hz of a float32 device tensor (ctts_resample_ragged; the filter of
+        resample.py): 1-D (one signal), [B, n] (rows, each alone -> [B, ceil(n L / M)]), or 1-D packed with `offsets` (n_seg + 1 sample
+        offsets, the ragged decoder's layout; every segment as if alone) -> (tensor, new offsets).  `orig == new` returns the input
+        untouched.  ValueError before any launch: an unsupported rate pair, an empty segment, non-ascending offsets, 2^31 samples out."""
+        if int(orig) == int(new):
+            return wav if offsets is None else (wav, offsets)
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
+            raise ValueError("resample: a float32 device tensor, 1-D or [B, n]")
+        if offsets is not None and wav.dim() != 1:
+            raise ValueError("resample: offsets go with a packed 1-D tensor")
+        if wav.dim() == 2:
+            B, n = int(wav.shape[0]), int(wav.shape[1])
+            off = np.arange(B + 1, dtype=np.int64) * n
+        else:
+            off = np.ascontiguousarray(offsets, dtype=np.int64) if offsets is not None else np.array([0, wav.numel()], dtype=np.int64)
+        if len(off) < 2:
+            raise ValueError("resample: nothing to convert")
+        _, _, _, off_out = RS.plan(orig, new, off)
+        if int(off[-1]) != wav.numel():
+            raise ValueError("resample: the offsets do not cover the tensor")
+        x = wav.contiguous()
+        y = torch.empty((int(off_out[-1]),), dtype=torch.float32, device=wav.device)
+        self._resample_launch(x.view(-1), off, y, off_out, None, int(orig), int(new))
+        if wav.dim() == 2:
+            return y.view(wav.shape[0], -1)
+        return (y, off_out) if offsets is not None else y
+
+    def resample_segments(self, wav: torch.Tensor, off, rates, orig: int = SAMPLE_RATE):
+        """packed segments to ONE RATE EACH (`rates[i]` for segment i): requests that were decoded together and want different rates.
+        One launch per distinct rate over that rate's segments, all into one packed output; segments that stay at `orig` are copied.
+        -> (tensor, offsets).  A segment's samples are those of `resample` on it alone, bit for bit."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        rates = [int(r) for r in rates]
+        if len(rates) != len(off) - 1:
+            raise ValueError("resample_segments: one rate per segment")
+        distinct = sorted(set(rates))
+        if len(distinct) == 1:
+            return self.resample(wav, orig, distinct[0], off)
+        for r in distinct:
+            if r != orig:
+                RS.plan(orig, r, off)       # every refusal, before the first launch
+        lens = [int(n) if r == orig else RS.out_len(int(n), *RS.ratio(orig, r)) for n, r in zip(np.diff(off), rates)]
+        off_out = np.zeros(len(off), np.int64)
+        np.cumsum(lens, out=off_out[1:])
+        if int(off_out[-1]) >= 1 << 31:
+            raise ValueError("resample: the output would hold 2^31 samples or more")
+        if int(off[-1]) != wav.numel() or wav.dim() != 1:
+            raise ValueError("resample_segments: a packed 1-D tensor covered by its offsets")
+        x = wav.contiguous()
+        y = torch.empty((int(off_out[-1]),), dtype=torch.float32, device=wav.device)
+        for r in distinct:
+            idx = [i for i, q in enumerate(rates) if q == r]
+            if r == orig:
+                for i in idx:
+                    y[int(off_out[i]): int(off_out[i + 1])].copy_(x[int(off[i]): int(off[i + 1])])
+            else:
+                self._resample_launch(x, off, y, off_out, idx, orig, r)
+        return y, off_out
+
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
-    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False):
+    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None):
         """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
         packed frames (ctts_dvae_decode_ragged / ctts_vocos_decode_ragged): each utterance gets zero padding at its own edges in every
         convolution, so its audio does not depend on what else is in the call -- unlike `decode_to_wavs`, whose zero-padded [B, Tmax]
@@ -1377,9 +1466,19 @@ class CodecEngine:
         third element when `return_mel`.  With gemm "f32" or "bf16x3", every utterance's mel and waveform are bit-identical to its B = 1
         decode at any packed size.  With "f16", a pack of at least CTTS_X3P_MIN_ROWS (default 1024) frames runs the point-wise pairs
         on fp16 planes: an utterance of at least that many frames takes them alone too and is bit-identical, a shorter one takes
-        split-bf16 tiles alone and is within 2e-5 RMS."""
+        split-bf16 tiles alone and is within 2e-5 RMS.
+        `sample_rate` (None: 24000): the rate of the returned samples -- one value, or one per row (requests that finish together at
+        different rates share the decode).  The waveform is resampled on the device directly behind the ISTFT (`resample_segments`),
+        every row as if alone; `off` then holds the resampled rows' offsets."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
+        if sample_rate is not None:
+            rates = [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
+            if len(rates) != len(rows):
+                raise ValueError("decode_ragged: one sample rate per row, or one for all")
+            out = self.decode_ragged(rows, return_mel)
+            wav, off = self.resample_segments(out[0], out[1], rates)
+            return (wav, off, out[2]) if return_mel else (wav, off)
         lens = [int(r.size(0)) for r in rows]
         if min(lens) < 1:
             raise ValueError("decode_ragged: every row needs at least one token")
@@ -1661,13 +1760,16 @@ class CodecEngine:
             list(pool.map(lambda i: np.copyto(flat_o[i * step: (i + 1) * step], flat_s[i * step: (i + 1) * step]), range(4)))
         return out
 
-    def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None) -> torch.Tensor:
+    def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None, sample_rate: Optional[int] = None) -> torch.Tensor:
         """`Chat._decode_to_wavs` (core.py:513-539): zero-pad the per-row [T_b,768] hidden lists to the
         longest row, DVAE decode, Vocos decode -> [B, 256(2Tmax-1)] float32 on the device.  `pad_to`: pad to that many tokens instead
         (>= the longest row): a data-parallel shard decodes its rows as part of the GLOBAL batch (dist.infer_sharded) -- the reference
-        decodes a shorter row's tail from zero hidden states and returns it."""
+        decodes a shorter row's tail from zero hidden states and returns it.  `sample_rate` (None: 24000): the rows are resampled to
+        that rate on the device, directly behind the ISTFT (`resample`) -> [B, ceil(n * new / 24000)]."""
         if len(result_list) == 0:
             return torch.empty((0,), dtype=torch.float32)
+        if sample_rate is not None and int(sample_rate) != self.SAMPLE_RATE:
+            return self.resample(self.decode_to_wavs(result_list, pad_to), self.SAMPLE_RATE, int(sample_rate))
         longest = max(int(r.size(0)) for r in result_list)
         if pad_to is not None and int(pad_to) < longest:
             raise ValueError("pad_to is shorter than the longest row")

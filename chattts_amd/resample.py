@@ -1,0 +1,88 @@
+"""Host side of the device resampler (csrc/resample.hip, `CodecEngine.resample`): the rational ratio of a rate pair, the polyphase
+filter table and the packed-segment arithmetic, all in Python integers / float64.  Nothing here touches the GPU.
+
+The filter is the Hann-windowed sinc that `torchaudio.functional.resample` documents as its default (6 zero crossings, roll-off 0.99).
+With orig = M and new = L (the rates divided by their gcd):
+    base  = min(orig, new) * 0.99            width = ceil(6 * orig / base)            K = 2 * width + orig
+    t_i[k] = clamp(((k - width) / orig - i / new) * base, -6, 6)
+    h[i][k] = (base / orig) * cos^2(pi t / 12) * sinc(t)
+    y[j * new + i] = sum_k h[i][k] * x[j * orig + k - width]            (x = 0 outside the segment)
+"""
+from __future__ import annotations
+
+import math
+from typing import Tuple
+
+import numpy as np
+
+ZEROS = 6            # zero crossings of the sinc either side
+ROLLOFF = 0.99
+TILE = 2048          # csrc/kernels.hpp RS_TILE: output samples per workgroup
+LDS_FLOATS = 16384   # RS_LDS_FLOATS: a tile's input span (+ the table, where both fit) in LDS
+TAB_MAX = 1 << 20    # RS_TAB_MAX: the largest table, in floats
+
+
+def ratio(orig: int, new: int) -> Tuple[int, int]:
+    """(L, M) = (new, orig) / gcd"""
+    orig, new = int(orig), int(new)
+    if orig <= 0 or new <= 0:
+        raise ValueError(f"sample rates must be positive (got {orig} -> {new})")
+    g = math.gcd(orig, new)
+    return new // g, orig // g
+
+
+def geometry(L: int, M: int) -> Tuple[int, int]:
+    """(width, K) of the table for the reduced pair"""
+    width = int(math.ceil(ZEROS * M / (min(L, M) * ROLLOFF)))      # float64, as the formula is stated
+    return width, 2 * width + M
+
+
+def taps(orig: int, new: int) -> np.ndarray:
+    """float64 [L, K] polyphase table of the conversion orig -> new"""
+    L, M = ratio(orig, new)
+    width, K = geometry(L, M)
+    base = min(L, M) * ROLLOFF
+    idx = (np.arange(K, dtype=np.float64) - width) / M
+    t = (idx[None, :] - np.arange(L, dtype=np.float64)[:, None] / L) * base
+    t = np.clip(t, -ZEROS, ZEROS)
+    win = np.cos(t * (math.pi / (2 * ZEROS))) ** 2
+    return (base / M) * win * np.sinc(t)          # np.sinc(t) = sin(pi t) / (pi t), 1 at 0
+
+
+def mode(L: int, M: int, K: int) -> int:
+    """what the kernel makes of a table (ctts_resample_supported): 0 = refused, 1 = table through L2, 2 = table in LDS"""
+    if L < 1 or M < 1 or L == M or K <= M or (K - M) % 2:
+        return 0
+    span, tab = ((TILE - 1) // L + 1) * M + K, L * K
+    if span > LDS_FLOATS or tab > TAB_MAX:
+        return 0
+    return 2 if tab + span <= LDS_FLOATS else 1
+
+
+def out_len(n: int, L: int, M: int) -> int:
+    """ceil(n L / M), in Python integers"""
+    return -(-int(n) * int(L) // int(M))
+
+
+def plan(orig: int, new: int, off) -> Tuple[int, int, int, np.ndarray]:
+    """(L, M, K, off_out) of converting the packed segments at `off` (n_seg + 1 sample offsets) from `orig` to `new`; raises
+    ValueError for everything the kernel must not be launched with"""
+    L, M = ratio(orig, new)
+    if L == M:
+        raise ValueError("resample: the rates are equal, there is nothing to convert")
+    _, K = geometry(L, M)
+    if mode(L, M, K) == 0:
+        raise ValueError(f"resample: {orig} -> {new} Hz reduces to {L}/{M} with {K} taps per phase, beyond what the kernel supports "
+                         f"(a tile's input span within {LDS_FLOATS} floats, the table within {TAB_MAX})")
+    off = [int(v) for v in off]
+    if len(off) < 2 or off[0] != 0:
+        raise ValueError("resample: offsets must start at 0 and hold at least one segment")
+    out = [0]
+    for i in range(len(off) - 1):
+        n = off[i + 1] - off[i]
+        if n <= 0:
+            raise ValueError(f"resample: segment {i} is empty or the offsets do not ascend")
+        out.append(out[-1] + out_len(n, L, M))
+    if out[-1] >= 1 << 31:
+        raise ValueError("resample: the output would hold 2^31 samples or more")
+    return L, M, K, np.asarray(out, dtype=np.int64)

@@ -32,6 +32,11 @@ from typing import Dict, Optional
 
 import numpy as np
 
+try:        # the upload route's parameter type: annotations of this module are resolved against its globals
+    from starlette.requests import Request
+except ImportError:      # create_app raises on its own fastapi import
+    Request = None
+
 ALLOWED_PARAMS = {"model", "input", "voice", "response_format", "speed", "stream", "output_format"}    # openai_api.py:97-105
 SAMPLE_RATE = 24000
 
@@ -56,13 +61,13 @@ def pcm16_to_wav_bytes(pcm: np.ndarray, sample_rate: int = SAMPLE_RATE) -> bytes
     return buf.getvalue()
 
 
-def _av_encode(pcm: np.ndarray, fmt: str) -> bytes:
+def _av_encode(pcm: np.ndarray, fmt: str, sample_rate: int = SAMPLE_RATE) -> bytes:
     """tools/audio/av.py: WAV bytes -> mp3 / ogg through PyAV (absent in the build container: only reached where `av` imports)"""
     import av
-    src = av.open(io.BytesIO(pcm16_to_wav_bytes(pcm)), "r")
+    src = av.open(io.BytesIO(pcm16_to_wav_bytes(pcm, sample_rate)), "r")
     out_buf = io.BytesIO()
     out = av.open(out_buf, "w", format=fmt)
-    stream = out.add_stream({"mp3": "mp3", "ogg": "libvorbis"}[fmt], rate=SAMPLE_RATE)
+    stream = out.add_stream({"mp3": "mp3", "ogg": "libvorbis"}[fmt], rate=sample_rate)
     for frame in src.decode(audio=0):
         for p in stream.encode(frame):
             out.mux(p)
@@ -80,7 +85,7 @@ def _have_av() -> bool:
 
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
-               batch_refine: bool = False, refine_params=None, batch_split: bool = False):
+               batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -98,7 +103,14 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     every path is as without it): a non-streamed request body may carry `"split_text": true` -- the reference's default handling of a long
     input: the text is cut into sentences that run side by side in the pool under one voice (SpeechBatcher.submit(split_text=True));
     with `"stream": true` the key is ignored with a warning.  A `voices` value may also be a dict `{"spk_emb"?, "spk_smp"?, "txt_smp"?}`
-    (a plain string means `spk_emb`): a cloned voice -- with it a split request needs no refer sentence."""
+    (a plain string means `spk_emb`): a cloned voice -- with it a split request needs no refer sentence.  `sample_rates` (default None:
+    every path is as without it, a `"sample_rate"` key is ignored with the "unsupported parameters" warning): the rates a non-streamed
+    request body may ask for with `"sample_rate"`, e.g. (8000, 16000, 24000, 44100, 48000) -- the audio is resampled on the device
+    (Chat.infer(sample_rate=) / SpeechBatcher.submit(sample_rate=)) and the WAV header carries the rate; another rate, or a rate other
+    than 24000 with `"stream": true` (the filter's state is not carried across chunks), gets a 400.  `voice_upload=True` adds
+    `POST /v1/audio/voices?name=NAME[&text=TRANSCRIPT]`, whose body is a WAV file (8/16/32-bit PCM, any rate, any channel count): the clip
+    is resampled to 24 kHz on the device and encoded (Chat.sample_audio_speaker(wav, rate)) under the GPU lock, and NAME becomes a cloned
+    voice of this app."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -122,6 +134,19 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
     pool_split = bool(batch_split) and batcher is not None
     allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
+    rates_ok = None if sample_rates is None else {int(r) for r in sample_rates}
+    if rates_ok is not None:
+        allowed = allowed | {"sample_rate"}
+
+    def voice_token_room():
+        """how many audio-prompt tokens of a cloned voice fit a pool slot beside a prompt: the pool admits a request when prompt +
+        max_new_token + 1 + 2 POLL <= cap (SlotPool.submit); 64 tokens are left for a short text and its decoration.  None without a
+        pool (the serial path has no slot)."""
+        pool = getattr(batcher, "pool", None)
+        cap = getattr(pool, "cap", None)
+        if cap is None:
+            return None
+        return max(0, int(cap) - int(code_params(None).max_new_token) - 1 - 2 * int(getattr(pool, "POLL", 0)) - 64)
 
     def refine_of(request_data):         # the refine stage's parameters of a request that asks for it, or None
         if not (pool_refine and bool(request_data.get("refine_text", False))):
@@ -163,10 +188,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     spk_emb=v.get("spk_emb"), spk_smp=v.get("spk_smp"), txt_smp=v.get("txt_smp"), stream_batch=24,
                                     stream_speed=12000, pass_first_n_batches=2)
 
-    def infer(req: "SpeechRequest"):                 # openai_api.py:168-183,207-222
+    def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE):                 # openai_api.py:168-183,207-222
+        kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
         return chat.infer(text=[req.input], stream=bool(req.stream), lang=None, skip_refine_text=True, refine_text_only=False,
                           use_decoder=True, do_text_normalization=True, do_homophone_replacement=True,
-                          params_infer_code=code_params(req.voice), pcm16=True, **extra)
+                          params_infer_code=code_params(req.voice), pcm16=True, **kw)
 
     @app.post("/v1/audio/speech")
     async def speech(request_data: Dict):
@@ -183,6 +209,18 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         if fmt not in formats:
             hint = " (mp3 / ogg need PyAV, which is not installed here)" if fmt in ("mp3", "ogg") else ""
             raise HTTPException(400, detail=f"Unsupported audio format: {fmt}, supported formats: {', '.join(sorted(formats))}{hint}")
+        rate = SAMPLE_RATE
+        if rates_ok is not None and request_data.get("sample_rate") is not None:
+            try:
+                rate = int(request_data["sample_rate"])
+            except (TypeError, ValueError):
+                rate = -1
+            if rate not in rates_ok:
+                raise HTTPException(400, detail=f"Unsupported sample_rate: {request_data['sample_rate']}, supported: "
+                                                f"{', '.join(str(r) for r in sorted(rates_ok))}")
+            if req.stream and rate != SAMPLE_RATE:
+                raise HTTPException(400, detail=f"sample_rate {rate} is served for non-streamed requests only: a stream's chunks are "
+                                                f"produced at {SAMPLE_RATE} Hz (the resampling filter's state is not carried across chunks)")
         refine = refine_of(request_data)
         rkw = {} if refine is None else {"refine": refine}
         if refine is not None and req.stream and not pool_streams:
@@ -197,10 +235,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         def encode(pcm: np.ndarray, header: bool) -> bytes:
             pcm = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype="<i2")
             if fmt == "wav":
-                return pcm16_to_wav_bytes(pcm) if header else pcm.tobytes()        # pcm.py:84-93
+                return pcm16_to_wav_bytes(pcm, rate) if header else pcm.tobytes()        # pcm.py:84-93
             if fmt == "pcm":
                 return pcm.tobytes()
-            return _av_encode(pcm, fmt)
+            return _av_encode(pcm, fmt, rate)
 
         if req.stream and pool_streams:
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
@@ -237,19 +275,51 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
         if batcher is not None:
             try:
+                if rate != SAMPLE_RATE:
+                    rkw = {**rkw, "sample_rate": rate}
                 wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:
             async with app.state.model_lock:
                 try:
-                    wavs = await run_in_threadpool(infer, req)
+                    wavs = await run_in_threadpool(infer, req, rate)
                 except Exception as e:
                     raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         if len(wavs) == 0:
             raise HTTPException(500, detail="Speech synthesis failed: the engine returned no audio")
         body = encode(wavs[0], header=True)                                           # openai_api.py:277-288
         return Response(content=body, media_type=media, headers={"Content-Disposition": f"attachment; filename=output.{fmt}"})
+
+    if voice_upload:
+        from .audio import load_wav
+        from .frontend import Speaker
+
+        def clone(wav, clip_rate: int) -> str:
+            with gpu_lock:
+                return chat.sample_audio_speaker(wav, clip_rate)
+
+        @app.post("/v1/audio/voices")
+        async def add_voice(request: Request, name: str, text: Optional[str] = None):
+            if not name or name == "default":
+                raise HTTPException(400, detail='a voice needs a name other than "default"')
+            try:
+                wav, clip_rate = load_wav(await request.body())
+            except ValueError as e:
+                raise HTTPException(400, detail=f"bad WAV upload: {e}")
+            async with app.state.model_lock:
+                try:
+                    smp = await run_in_threadpool(clone, wav, clip_rate)
+                except ValueError as e:                # a rate pair the resampler refuses
+                    raise HTTPException(400, detail=str(e))
+            tokens = int(Speaker.decode_prompt(smp).shape[-1])
+            if tokens == 0:
+                raise HTTPException(400, detail="the clip is too short: it encodes to no audio token")
+            room = voice_token_room()
+            if room is not None and tokens > room:
+                raise HTTPException(400, detail=f"the clip encodes to {tokens} audio tokens; a pool slot holds at most {room} beside a prompt")
+            voices[name] = {"spk_smp": smp, **({"txt_smp": text} if text else {})}
+            return {"name": name, "seconds": wav.shape[0] / clip_rate, "sample_rate": clip_rate, "tokens": tokens}
 
     @app.get("/health")
     async def health():                                                               # openai_api.py:291-294

@@ -769,19 +769,22 @@ class SpeechBatcher:
         self._thread.start()
 
     # -- public -------------------------------------------------------------------------------------------------------------
-    def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4) -> Future:
+    def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
         result is that of `Chat.infer([text], skip_refine_text=False, params_refine_text=refine, ...)`.
         `split_text=True`: the result is that of `Chat.infer(text, split_text=True, max_split_batch=..., ragged_decode=True,
         pcm16=True, ...)[0]` -- the same tokens per sentence, ONE waveform under one peak (see the class text).  `params` is never
-        modified (the serial call writes the speaker prompt into it)."""
+        modified (the serial call writes the speaker prompt into it).  `sample_rate` (None: 24000): the rate of the returned audio, the
+        serial call's `sample_rate=`; requests that finish together at different rates are decoded together and resampled in one
+        launch per distinct rate (CodecEngine.resample_segments)."""
         self._check_refine(refine)
         if split_text and int(max_split_batch) < 1:
             raise ValueError("max_split_batch must be positive")
         fut: Future = Future()
         fut.rid = next(self._ids)
+        fut.sample_rate = None if sample_rate is None or int(sample_rate) == 24000 else int(sample_rate)
         self._in.put((fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None))
         return fut
 
@@ -1027,7 +1030,7 @@ class SpeechBatcher:
                 self._deliver(rid, RuntimeError(_NO_AUDIO))
         try:
             self._count_decode(len(live))
-            results = self.chat.decode_split_to_pcm16([g for _, g in live])
+            results = self.chat.decode_split_to_pcm16([g for _, g in live], **self._rate_kw([rid for rid, _ in live]))
         except Exception as e:         # the decode failed: its requests fail, the worker goes on
             results = [e] * len(live)
         for (rid, _), r in zip(live, results):
@@ -1114,23 +1117,31 @@ class SpeechBatcher:
         self._drain(block=False)
         self.lock.acquire()
 
-    def finish(self, hid: torch.Tensor) -> np.ndarray:
+    def _rate_kw(self, rids) -> dict:
+        """the `sample_rate=` keyword of the decode of the requests `rids` (nothing when all of them want 24 kHz: today's call)"""
+        rates = [getattr(self._futs.get(r), "sample_rate", None) for r in rids]
+        if all(r is None for r in rates):
+            return {}
+        return {"sample_rate": [24000 if r is None else r for r in rates]}
+
+    def finish(self, hid: torch.Tensor, sample_rate=None) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
             raise RuntimeError("the engine returned no audio (the first token was EOS)")
         self._count_decode(1)
-        wav = self.chat.decode_to_wavs([hid])[0]
+        wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}))[0]
         return float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
 
-    def finish_group(self, hids: List[torch.Tensor]) -> list:
+    def finish_group(self, hids: List[torch.Tensor], sample_rates=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
-        returns for it) or the exception that fails it alone (an empty result)"""
+        returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000)"""
         out: list = [RuntimeError("the engine returned no audio (the first token was EOS)") if h.shape[0] == 0 else None for h in hids]
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
             self._count_decode(len(live))
-            for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True)):
+            kw = {} if sample_rates is None else {"sample_rate": [int(sample_rates[i]) for i in live]}
+            for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out
 
@@ -1207,7 +1218,8 @@ class SpeechBatcher:
         if self.ragged_decode:
             group = [(rid, hid) for rid, _, hid in got if rid in self._futs]
             try:
-                results = self.finish_group([h for _, h in group])
+                rkw = self._rate_kw([rid for rid, _ in group])
+                results = self.finish_group([h for _, h in group], **({"sample_rates": rkw["sample_rate"]} if rkw else {}))
             except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
                 results = [e] * len(group)
             for (rid, _), r in zip(group, results):
@@ -1217,7 +1229,8 @@ class SpeechBatcher:
         if rid not in self._futs:
             return
         try:
-            pcm = self.finish(hid)
+            rate = getattr(self._futs.get(rid), "sample_rate", None)
+            pcm = self.finish(hid, **({} if rate is None else {"sample_rate": rate}))
         except Exception as e:
             pcm = e
         self._deliver(rid, pcm)

@@ -377,6 +377,20 @@ int ctts_float_to_int16_groups(const float* wav, int16_t* pcm, int64_t* n_kept, 
                                const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp, int32_t product, float keep_thr, uint32_t* peak,
                                void* scratch, size_t scratch_bytes, void* stream);
 
+/* Sample-rate conversion by L/M (new / old rate, reduced) over packed segments: x[off_in[s], off_in[s+1]) -> y[off_out[s], off_out[s+1]),
+ * ceil(n_s L / M) samples, every segment as if alone (input outside its own samples reads as zero).  taps: the float32 [L][K] polyphase
+ * table on the device, K = 2 width + M:  y[j L + i] = sum_k taps[i][k] x[j M + k - width], one accumulator, k ascending -- a sample does
+ * not depend on what it is packed with.  The offsets (int64, first 0, strictly ascending) are given on the device and the host (the two
+ * must agree).  sel_dev / sel_host (both NULL: every segment): the n_sel segment indices this call converts -- segments of one pack that
+ * go to different rates share off_in / off_out / y, one call per rate.  Refused before anything is launched: L == M, a pair
+ * ctts_resample_supported refuses, an empty segment, non-ascending offsets, an output length other than ceil(n L / M), an output of 2^31
+ * samples or more.  ctts_resample_supported: 0 = no (a tile's input span or the table is too large), 1 = table read through L2, 2 = table
+ * staged in LDS. */
+int32_t ctts_resample_supported(int32_t L, int32_t M, int32_t K);
+int ctts_resample_ragged(const float* x, const int64_t* off_in_dev, const int64_t* off_in_host, float* y, const int64_t* off_out_dev,
+                         const int64_t* off_out_host, int32_t n_seg, const int32_t* sel_dev, const int32_t* sel_host, int32_t n_sel,
+                         const float* taps, int32_t L, int32_t M, int32_t K, void* stream);
+
 /* Window decode: the chunks of many streamed utterances that are due at one poll, in ONE ragged pass, each at its own position.
  * hid: a hidden-state store [n_slots][hid_cap][768] float32 (a slot pool's; slot_stride / row_stride in floats, multiples of 4, rows 16-byte
  * aligned).  A window is token rows [t_lo, t_hi) of one slot; it is decoded as one ragged segment -- its edges are sequence edges -- and
