@@ -5,6 +5,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 import torch  # noqa: F401  -- MUST precede the dlopen below: torch bundles its own libamdhip64; loading ours first
 #                  would bind libchattts_amd.so to a second HIP runtime that cannot see torch's device context
 
@@ -45,6 +47,16 @@ class GenState(C.Structure):
         ("margin", P), ("row_base", P), ("proj_exact", C.c_int32), ("prefill_valid_rows", C.c_int32),
         ("row_sampling", P),
     ]
+
+
+# ctts_rs_window (64 bytes): in_off, n_in, origin, total, o_lo, o_hi, out_off int64; rate, pad int32
+RS_WINDOW = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("origin", "<i8"), ("total", "<i8"), ("o_lo", "<i8"), ("o_hi", "<i8"),
+                      ("out_off", "<i8"), ("rate", "<i4"), ("pad", "<i4")])
+
+
+class Rate(C.Structure):
+    """ctts_rate: one conversion of ctts_codec_decode_windows_rate"""
+    _fields_ = [("taps", P), ("L", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SamplingRow(C.Structure):
@@ -130,6 +142,10 @@ SIGNATURES = {
     "ctts_resample_ragged": (C.c_int, [P, P, P, P, P, P, I32, P, P, I32, P, I32, I32, I32, P]),
     "ctts_codec_windows_workspace_bytes": (SZ, [I32, I32]),
     "ctts_codec_decode_windows": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, I32, P, P, I32, F, P, SZ, P]),
+    "ctts_resample_windows": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P, I32, I32, I32, P]),
+    "ctts_codec_windows_rate_workspace_bytes": (SZ, [I32, I32, C.c_int64]),
+    "ctts_codec_decode_windows_rate": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, P, P, P, P, I32, P, I32, I32, P, P, I32, F, P,
+                                                 SZ, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),
     "ctts_dvae_destroy": (None, [P]),
     "ctts_dvae_code_frames": (I32, [I32]),

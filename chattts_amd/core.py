@@ -22,6 +22,7 @@ from typing import Iterator, List, Optional, Union
 import numpy as np
 import torch
 
+from . import resample as RS
 from . import weights as W
 from .audio import float_to_int16
 from .config import GPT
@@ -373,11 +374,13 @@ class Chat:
         blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None)
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts)]
 
-    def decode_windows_pcm16(self, store: torch.Tensor, windows) -> List[np.ndarray]:
+    def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
         (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream)"""
-        return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5)
+        if sample_rates is None:
+            return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5)
+        return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, sample_rates=sample_rates)
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
         """non-stream `Chat._infer` body for one batch (core.py:469-481, split_text=False, skip_refine_text=True),
@@ -408,31 +411,44 @@ class Chat:
         for p in pending:
             yield np.zeros((0,), np.float32) if p is None else p.result()
 
-    def _stream_piece(self, hiddens, a: int, b: Optional[int], use_decoder: bool = True, pcm16: bool = False) -> np.ndarray:
+    def _stream_piece(self, hiddens, a: int, b: Optional[int], use_decoder: bool = True, pcm16: bool = False,
+                      rate: Optional[int] = None) -> np.ndarray:
         """samples [a, b) (b=None: to the end) of the decode of the current prefix (core.py:482-497), from a token window with
         halos instead of the whole prefix (`CodecEngine.decode_window`); `incremental_stream=False` restores the reference's
-        full re-decode per yield"""
+        full re-decode per yield.  `rate` (None: 24 kHz): [a, b) stay 24 kHz samples and the piece is outputs
+        [ceil(a L / M), ceil(b L / M)) of the prefix's decode resampled as one signal -- from the widened window
+        (`decode_window(sample_rate=)`), or, `incremental_stream=False`, sliced out of the whole prefix resampled whole."""
         Tn = max(int(r.size(0)) for r in hiddens)
         total = 256 * (2 * Tn - 1) if use_decoder else None
         if not use_decoder or not self.incremental_stream:
+            if rate is not None:
+                n24 = max(0, 256 * (2 * Tn - 1))      # the decode's width at 24 kHz, on both decode paths
+                L, M = RS.ratio(CodecEngine.SAMPLE_RATE, rate)
+                o_lo, o_hi = (RS.out_len(min(v, n24), L, M) for v in (a, n24 if b is None else b))
+                piece = self.decode_to_wavs(hiddens, use_decoder, sample_rate=rate)[:, o_lo: max(o_lo, o_hi)]
+                return np.stack([float_to_int16(r) for r in piece]) if (pcm16 and piece.shape[1]) else piece
             wavs = self.decode_to_wavs(hiddens, use_decoder)
             piece = wavs[:, a: wavs.shape[1] if b is None else min(b, wavs.shape[1])]
             return np.stack([float_to_int16(r) for r in piece]) if (pcm16 and piece.shape[1]) else piece
         hi = total if b is None else min(b, total)
         if hi <= a:     # a window that starts past the end of this prefix (a later split batch, see `_infer`): nothing to decode
             return np.zeros((len(hiddens), 0), np.int16 if pcm16 else np.float32)
-        win = self.codec.decode_window(hiddens, a, hi)
+        win = self.codec.decode_window(hiddens, a, hi) if rate is None else self.codec.decode_window(hiddens, a, hi, sample_rate=rate)
         if pcm16 and win.shape[1] > 0:     # every row by its own peak -- float_to_int16(chunk[b]), examples/web/funcs.py:203-206 -- on the device
             return self.codec.to_host(self.codec.float_to_int16(win, per_row=True)[0])
         return self.codec.to_host(win)
 
-    def infer_ids_stream(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw):
+    def infer_ids_stream(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), *,
+                         sample_rate: Optional[int] = None, **kw):
         """stream=True body of `Chat._infer` for one batch (core.py:455-503): every `stream_batch` live steps the
         generator yields the cumulative result and the next `stream_speed` samples of the decode of that prefix are
         emitted; the first `pass_first_n_batches` yields are dropped (core.py:488-490); the tail is emitted with all-silent
         columns removed (core.py:500-503).  The reference decodes the WHOLE prefix at every yield (O(n^2), App. D-10);
         here only the token window those samples depend on is decoded (same samples, O(n) in total), on the caller's
-        stream while the generator's own stream already runs the next chunk."""
+        stream while the generator's own stream already runs the next chunk.
+        `sample_rate` (None or 24000: as above): every piece is its range of the prefix's decode resampled as one signal
+        (`_stream_piece`); the schedule -- `length` -- stays in 24 kHz samples."""
+        rate = None if sample_rate is None or int(sample_rate) == CodecEngine.SAMPLE_RATE else int(sample_rate)
         length = 0
         pass_batch_count = 0
         result = None
@@ -440,11 +456,16 @@ class Chat:
             pass_batch_count += 1
             if pass_batch_count <= params.pass_first_n_batches:
                 continue
-            piece = self._stream_piece(result.hiddens, length, length + params.stream_speed)
-            length += piece.shape[1]
+            if rate is None:
+                piece = self._stream_piece(result.hiddens, length, length + params.stream_speed)
+                length += piece.shape[1]
+            else:      # the 24 kHz count of the range, not the resampled piece's length
+                piece = self._stream_piece(result.hiddens, length, length + params.stream_speed, rate=rate)
+                total = 256 * (2 * max(int(r.size(0)) for r in result.hiddens) - 1)
+                length += max(0, min(length + params.stream_speed, total) - length)
             yield piece
         if result is not None:
-            new_wavs = self._stream_piece(result.hiddens, length, None)
+            new_wavs = self._stream_piece(result.hiddens, length, None, **({} if rate is None else {"rate": rate}))
             keep_cols = np.sum(np.abs(new_wavs) > 1e-5, axis=0) > 0
             yield new_wavs[:, keep_cols]
 
@@ -539,7 +560,7 @@ class Chat:
     def infer(self, text, stream=False, lang=None, skip_refine_text=False, refine_text_only=False, use_decoder=True,
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
-              *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000):
+              *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -551,11 +572,20 @@ class Chat:
         `sample_rate` (keyword-only, non-streamed only): the rate of the returned audio.  Every decoded waveform is resampled on the
         device directly behind the ISTFT (CodecEngine.resample); the silence strip, the 16-bit conversion and the concatenation of a
         split request work on the resampled samples.  The refer sentence's audio that becomes `spk_smp` of a split request stays at
-        24 kHz.  A streamed call at another rate raises: carrying the filter's state across chunks is separate work."""
+        24 kHz.  A streamed call at another rate raises unless `stream_resample=True` (keyword-only): then every chunk is its range
+        of the prefix's decode resampled as one signal -- the chunk the 24 kHz schedule defines as samples [s_lo, s_hi) becomes outputs
+        [ceil(s_lo L / M), ceil(s_hi L / M)), so the chunks tile the resampled stream; the schedule itself (stream_speed,
+        pass_first_n_batches, ...) stays in 24 kHz samples; each chunk's 16-bit peak and the tail's silence strip are taken on the
+        resampled samples.  No filter state is carried: a chunk is converted from a token window widened by the filter's reach
+        (CodecEngine.decode_window).  A `split_text` stream at another rate raises."""
         sample_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if stream and sample_rate != CodecEngine.SAMPLE_RATE:
-            raise ValueError("sample_rate applies to non-streamed inference only (a stream's chunks would need the filter's state carried "
-                             "across them, which is not implemented)")
+            if not stream_resample:
+                raise ValueError("sample_rate applies to non-streamed inference only (a stream's chunks would need the filter's state carried "
+                                 "across them, which is not implemented)")
+            if split_text:
+                raise ValueError("a streamed split_text request is served at 24000 Hz only")
+            RS.plan(CodecEngine.SAMPLE_RATE, sample_rate, [0, 1])      # an unsupported pair is refused here, not at the first chunk
         rate = None if sample_rate == CodecEngine.SAMPLE_RATE else sample_rate
         if ragged_decode and stream:
             raise ValueError("ragged_decode applies to non-streamed inference only")
@@ -643,7 +673,8 @@ class Chat:
                 if pass_batch_count <= params_infer_code.pass_first_n_batches:
                     continue     # the reference decodes these yields and drops the audio (core.py:482-490)
                 src = result.hiddens if use_decoder else result.ids
-                piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16)
+                skw = {"rate": sample_rate} if sample_rate is not None else {}      # 24 kHz: today's call, argument for argument
+                piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
                 # that is BELOW `a`: `length` and `pass_batch_count` are not reset between split batches, so the first yields of a
                 # later batch (a short prefix again) are empty and pull `length` back (tests/test_host_flow.py, stream_split_batches)
@@ -651,7 +682,8 @@ class Chat:
                 length = min(length + params_infer_code.stream_speed, max(0, 256 * (2 * max(int(r.size(0)) for r in src) - 1)))
                 yield piece
             if stream and last is not None:
-                new_wavs = self._stream_piece(last.hiddens if use_decoder else last.ids, length, None, use_decoder)
+                skw = {"rate": sample_rate} if sample_rate is not None else {}
+                new_wavs = self._stream_piece(last.hiddens if use_decoder else last.ids, length, None, use_decoder, **skw)
                 last.destroy()
                 keep_cols = np.sum(np.abs(new_wavs) > 1e-5, axis=0) > 0
                 tail = new_wavs[:, keep_cols]

@@ -1084,6 +1084,145 @@ extern "C" int ctts_codec_decode_windows(ctts_codec* c, const float* hid, int64_
   return 0;
 }
 
+// ---- window decode at other sample rates: the windows' chunks are outputs [o_lo, o_hi) of the resampled prefix ------------------------
+static_assert(sizeof(ctts_rs_window) == 64 && sizeof(RsWindow) == 64 && offsetof(ctts_rs_window, out_off) == offsetof(RsWindow, out_off) &&
+              offsetof(ctts_rs_window, rate) == offsetof(RsWindow, rate) && offsetof(ctts_rs_window, pad) == offsetof(RsWindow, pad),
+              "ctts_rs_window layout");
+// the inputs inside [0, total) that outputs [o_lo, o_hi) read (resample.py, window_inputs) must lie in the window; everything in the host
+// mirror that a launch would trust.  o_lo == o_hi (an empty chunk) reads nothing
+static int check_rs_window(const char* who, int i, const ctts_rs_window& w, int L, int M, int K) {
+  if (w.o_lo < 0 || w.o_hi < w.o_lo) return fail("%s: window %d wants outputs %lld -> %lld", who, i, (long long)w.o_lo, (long long)w.o_hi);
+  if (w.n_in < 1 || w.in_off < 0 || w.origin < 0 || w.total < 1 || w.origin + w.n_in > w.total || w.total >= (1ll << 31))
+    return fail("%s: window %d holds samples %lld + %lld of a signal of %lld", who, i, (long long)w.origin, (long long)w.n_in, (long long)w.total);
+  if (w.o_hi > (w.total * L + M - 1) / M)
+    return fail("%s: window %d ends at output %lld beyond the signal's ceil(total L / M)", who, i, (long long)w.o_hi);
+  if (w.out_off < 0 || w.pad < 0 || w.pad > 255) return fail("%s: window %d: bad output offset or pad", who, i);
+  if (w.o_hi == w.o_lo) return 0;
+  const long long width = (K - M) / 2;
+  const long long a = std::max(0ll, (long long)(w.o_lo / L) * M - width), b = std::min((long long)w.total, (long long)((w.o_hi - 1) / L) * M + width + M);
+  if (a < b && (w.origin > a || w.origin + w.n_in < b))
+    return fail("%s: window %d holds samples [%lld, %lld) but its outputs read [%lld, %lld)", who, i, (long long)w.origin,
+                (long long)(w.origin + w.n_in), a, b);
+  return 0;
+}
+static int check_rs_pair(const char* who, const float* taps, int L, int M, int K) {
+  if (!taps) return fail("%s: the filter table is null", who);
+  if (L < 1 || M < 1 || L == M) return fail("%s: need L != M, both positive (got %d/%d)", who, L, M);
+  if (resample_mode(L, M, K) == 0)
+    return fail("%s: conversion %d/%d with %d taps is not supported (K = 2 width + M; a tile's input span within %d floats, the table within %d)",
+                who, L, M, K, RS_LDS_FLOATS, RS_TAB_MAX);
+  return 0;
+}
+extern "C" int ctts_resample_windows(const float* x, int64_t n_x, const ctts_rs_window* win_dev, const ctts_rs_window* win_host, int32_t n_win,
+                                     float* y, int64_t n_y, const int32_t* sel_dev, const int32_t* sel_host, int32_t n_sel, const float* taps,
+                                     int32_t L, int32_t M, int32_t K, void* stream) {
+  const char* who = "ctts_resample_windows";
+  if (!x || !y || !win_dev || !win_host) return fail("%s: bad arguments", who);
+  if (n_win < 1 || n_win > 1024) return fail("%s: need 1 <= n_win <= 1024 (got %d)", who, n_win);
+  if ((sel_dev == nullptr) != (sel_host == nullptr)) return fail("%s: the window selection must be given on the device and the host, or on neither", who);
+  if (check_rs_pair(who, taps, L, M, K)) return -1;
+  const int n_launch = sel_host ? n_sel : n_win;
+  if (n_launch < 1 || n_launch > 1024) return fail("%s: need 1 <= converted windows <= 1024 (got %d)", who, n_launch);
+  long long n_out_max = 0;
+  for (int q = 0; q < n_launch; ++q) {
+    const int i = sel_host ? sel_host[q] : q;
+    if (i < 0 || i >= n_win) return fail("%s: selected window %d is outside the table", who, i);
+    const ctts_rs_window& w = win_host[i];
+    if (check_rs_window(who, i, w, L, M, K)) return -1;
+    if (w.in_off + w.n_in > n_x || w.out_off + (w.o_hi - w.o_lo) + w.pad > n_y)
+      return fail("%s: window %d lies outside the input (%lld floats) or the output (%lld floats)", who, i, (long long)n_x, (long long)n_y);
+    n_out_max = std::max(n_out_max, (long long)(w.o_hi - w.o_lo));
+  }
+  CttsDeviceGuard dg(stream);
+  CK(launch_resample_windows(x, (const RsWindow*)win_dev, y, sel_dev, n_launch, n_out_max, taps, L, M, K, (hipStream_t)stream));
+  return 0;
+}
+
+// workspace = the window-decode workspace | the resampled chunks, chunk_floats of them (sum of ceil8(o_hi - o_lo) over the resampled windows)
+extern "C" size_t ctts_codec_windows_rate_workspace_bytes(int32_t n_win, int32_t total_tokens, int64_t chunk_floats) {
+  const size_t base = ctts_codec_windows_workspace_bytes(n_win, total_tokens);
+  if (base == 0 || chunk_floats < 0 || chunk_floats >= (1ll << 31)) return 0;
+  return base + align_up((size_t)chunk_floats * 4);
+}
+extern "C" int ctts_codec_decode_windows_rate(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots,
+                                              int32_t hid_cap, const ctts_window* win_dev, const ctts_window* win_host,
+                                              const ctts_rs_window* rs_dev, const ctts_rs_window* rs_host, const int32_t* sel_dev, const int32_t* sel_host,
+                                              int32_t n_win,
+                                              const ctts_rate* rates, int32_t n_rates, int32_t out_type, void* out, uint8_t* keep_bits,
+                                              int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
+  const char* who = "ctts_codec_decode_windows_rate";
+  if (!c || !hid || !win_dev || !win_host || !rs_dev || !rs_host || !sel_dev || !sel_host || !out) return fail("%s: bad arguments", who);
+  if (n_win < 1 || n_win > 1024) return fail("%s: need 1 <= n_win <= 1024 (got %d)", who, n_win);
+  if (n_rates < 0 || n_rates > n_win || (n_rates > 0 && !rates)) return fail("%s: need 0 <= n_rates <= n_win and the rate table", who);
+  if ((out_type != 0 && out_type != 1) || (product != 0 && product != 1)) return fail("%s: out_type and product must be 0 or 1", who);
+  if (n_slots < 1 || hid_cap < 1 || row_stride < 768 || slot_stride < (int64_t)hid_cap * row_stride || (row_stride & 3) || (slot_stride & 3) ||
+      ((uintptr_t)hid & 15) || ((uintptr_t)out & 15))
+    return fail("%s: the store must be [n_slots][hid_cap][768] floats with 16-byte aligned rows, the output 16-byte aligned", who);
+  for (int r = 0; r < n_rates; ++r)
+    if (check_rs_pair(who, rates[r].taps, rates[r].L, rates[r].M, rates[r].K)) return -1;
+  std::vector<int32_t> tok(n_win + 1, 0);
+  std::vector<int> per_rate(n_rates, 0);
+  std::vector<long long> longest(n_rates, 0);
+  long long chunk_floats = 0;
+  for (int i = 0; i < n_win; ++i) {
+    const ctts_window& w = win_host[i];
+    const ctts_rs_window& r = rs_host[i];
+    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: window %d names slot %d of %d", who, i, w.slot, n_slots);
+    if (w.t_lo < 0 || w.t_hi <= w.t_lo) return fail("%s: window %d is empty (tokens %d -> %d)", who, i, w.t_lo, w.t_hi);
+    if (w.t_hi > hid_cap) return fail("%s: window %d ends at token %d beyond the slot's capacity %d", who, i, w.t_hi, hid_cap);
+    const int64_t n_samples = 256 * (2 * (int64_t)(w.t_hi - w.t_lo) - 1);
+    if (w.c_lo < 0 || w.c_hi <= w.c_lo || w.c_hi > n_samples)
+      return fail("%s: window %d crops samples %d -> %d outside its %lld samples", who, i, w.c_lo, w.c_hi, (long long)n_samples);
+    if (w.keep && !keep_bits) return fail("%s: window %d asks for a keep mask but keep_bits is null", who, i);
+    const int64_t start = 256 * (2 * (int64_t)tok[i] - i);       // the window's first sample in the packed decode
+    if (r.rate >= n_rates) return fail("%s: window %d names rate %d of %d", who, i, r.rate, n_rates);
+    if (r.rate < 0) {                                            // stays at 24 kHz: the crop itself
+      if (r.in_off != start + w.c_lo || r.n_in != w.c_hi - w.c_lo) return fail("%s: window %d: the 24 kHz chunk is not the window's crop", who, i);
+    } else {
+      // the resampler reads the crop alone: samples [origin, origin + n_in) = [512 t_lo + c_lo, 512 t_lo + c_hi) of the prefix
+      if (r.in_off != start + w.c_lo || r.n_in != w.c_hi - w.c_lo || r.origin != 512 * (int64_t)w.t_lo + w.c_lo)
+        return fail("%s: window %d: the resampler's input is not the window's crop at its place in the prefix", who, i);
+      if (r.o_hi <= r.o_lo) return fail("%s: window %d wants outputs %lld -> %lld", who, i, (long long)r.o_lo, (long long)r.o_hi);
+      if (check_rs_window(who, i, r, rates[r.rate].L, rates[r.rate].M, rates[r.rate].K)) return -1;
+      const long long n = r.o_hi - r.o_lo;
+      if (r.out_off != chunk_floats || r.pad != (int)(((n + 7) & ~7ll) - n)) return fail("%s: window %d: chunks start on multiples of 8 floats, zero padded", who, i);
+      chunk_floats += n + r.pad;
+      ++per_rate[r.rate];
+      longest[r.rate] = std::max(longest[r.rate], n);
+    }
+    tok[i + 1] = tok[i] + (w.t_hi - w.t_lo);
+    if (tok[i + 1] > (1 << 28)) return fail("%s: too many tokens", who);
+  }
+  // sel lists the resampled windows rate by rate, each once: one launch per distinct rate converts its run of the list
+  for (int r = 0, q = 0; r < n_rates; ++r)
+    for (int k = 0; k < per_rate[r]; ++k, ++q) {
+      const int i = sel_host[q];
+      if (i < 0 || i >= n_win || rs_host[i].rate != r || (k > 0 && i <= sel_host[q - 1]))
+        return fail("%s: the selection must list the resampled windows rate by rate, ascending within a rate", who);
+    }
+  const int T = tok[n_win];
+  if (!workspace || ws_bytes < ctts_codec_windows_rate_workspace_bytes(n_win, T, chunk_floats) || chunk_floats >= (1ll << 31))
+    return fail("codec workspace too small");
+  WindowsWs ws = carve_windows(workspace, n_win, T);
+  float* chunks = (float*)((char*)workspace + ws.bytes);
+  {
+    CttsDeviceGuard dg(stream);
+    CK(launch_gather_windows(hid, slot_stride, row_stride, (const CodecWindow*)win_dev, n_win, T, ws.hid, ws.tok_off, (hipStream_t)stream));
+  }
+  if (ctts_dvae_decode_ragged(c, ws.hid, ws.tok_off, tok.data(), n_win, ws.mel, workspace, ws.ragged_bytes, stream)) return -1;
+  if (ctts_vocos_decode_ragged(c, ws.mel, ws.tok_off, tok.data(), n_win, ws.wav, workspace, ws.ragged_bytes, stream)) return -1;
+  CttsDeviceGuard dg(stream);
+  int done = 0;
+  for (int r = 0; r < n_rates; ++r) {
+    CK(launch_resample_windows(ws.wav, (const RsWindow*)rs_dev, chunks, sel_dev + done, per_rate[r], longest[r], rates[r].taps, rates[r].L,
+                               rates[r].M, rates[r].K, (hipStream_t)stream));
+    done += per_rate[r];
+  }
+  CK(launch_chunks_pcm16(ws.wav, chunks, (const CodecWindow*)win_dev, (const RsWindow*)rs_dev, n_win, out_type == 0 ? 1 : 0, product, keep_thr,
+                         out, keep_bits, (hipStream_t)stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // single-kernel entry points
 // ------------------------------------------------------------------------------------------------

@@ -839,3 +839,75 @@ hipError_t launch_crop_pcm16_windows(const float* wav, const CodecWindow* win, i
   hipLaunchKernelGGL(crop_pcm16_windows_k, dim3(n_win), dim3(1024), 0, st, wav, win, out_f32, product, keep_thr, out, keep);
   return hipGetLastError();
 }
+
+// crop_pcm16_windows_k with the chunk addressed through a second table (ctts_codec_decode_windows_rate): window w's samples are the resampled
+// chunk at chunks + rs[w].out_off (rs[w].rate >= 0; rs[w].o_hi - rs[w].o_lo of them) or the 24 kHz crop at wav + rs[w].in_off (rate < 0;
+// rs[w].n_in).  Everything else -- the output layout, one peak per window over its own samples, pcm16_scale / pcm16_sample, the keep
+// mask -- is that kernel's, so a 24 kHz window among resampled ones gets the bytes it gets there.
+__global__ __launch_bounds__(1024) void chunks_pcm16_k(const float* __restrict__ wav, const float* __restrict__ chunks,
+                                                       const CodecWindow* __restrict__ win, const RsWindow* __restrict__ rs, int out_f32,
+                                                       int product, float keep_thr, void* __restrict__ out, uint8_t* __restrict__ keep) {
+  __shared__ unsigned red[16];
+  const int w = blockIdx.x;
+  auto len = [&](int j) { return rs[j].rate >= 0 ? rs[j].o_hi - rs[j].o_lo : rs[j].n_in; };
+  long long oo = 0;
+  for (int j = 0; j < w; ++j) oo += (len(j) + 7) & ~7ll;      // wave-uniform: scalar loads
+  const int n = (int)len(w);
+  const float* x = rs[w].rate >= 0 ? chunks + rs[w].out_off : wav + rs[w].in_off;
+  const int groups = (n + 7) >> 3;
+  const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  auto load8 = [&](int g, float (&v)[8]) {
+    if (vec && g * 8 + 8 <= n) {
+      const float4 a = reinterpret_cast<const float4*>(x)[2 * g], b = reinterpret_cast<const float4*>(x)[2 * g + 1];
+      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = g * 8 + e < n ? x[g * 8 + e] : 0.0f;
+    }
+  };
+  long long am = 0;
+  if (!out_f32) {
+    unsigned m = 0;
+    for (int g = threadIdx.x; g < groups; g += 1024) {
+      float v[8];
+      load8(g, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) m = max(m, __float_as_uint(v[e]) & 0x7fffffffu);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m = max(m, red[k]);
+    am = pcm16_scale(__uint_as_float(m));
+  }
+  const bool mask = keep != nullptr && win[w].keep != 0;
+  for (int g = threadIdx.x; g < groups; g += 1024) {
+    float v[8];
+    load8(g, v);
+    if (out_f32) {
+      float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + oo) + 2 * g;
+      o[0] = make_float4(v[0], v[1], v[2], v[3]);
+      o[1] = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+      union { u128 q; int16_t s[8]; } p;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) p.s[e] = pcm16_sample(v[e], am, product);
+      reinterpret_cast<u128*>(reinterpret_cast<int16_t*>(out) + oo)[g] = p.q;
+    }
+    if (mask) {
+      unsigned bits = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (g * 8 + e < n && fabsf(v[e]) > keep_thr) bits |= 0x80u >> e;
+      keep[(oo >> 3) + g] = (uint8_t)bits;
+    }
+  }
+}
+hipError_t launch_chunks_pcm16(const float* wav, const float* chunks, const CodecWindow* win, const RsWindow* rs, int n_win, int out_f32,
+                               int product, float keep_thr, void* out, uint8_t* keep, hipStream_t st) {
+  if (n_win < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(chunks_pcm16_k, dim3(n_win), dim3(1024), 0, st, wav, chunks, win, rs, out_f32, product, keep_thr, out, keep);
+  return hipGetLastError();
+}

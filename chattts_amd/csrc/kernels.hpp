@@ -486,6 +486,21 @@ int resample_mode(int L, int M, int K);   // 0 unsupported, 1 table through L2, 
 // sel (or null: segments 0 .. n_launch-1): the n_launch segment indices this call converts; n_out_max: their longest output (grid size)
 hipError_t launch_resample_ragged(const float* x, const long long* off_in, float* y, const long long* off_out, const int32_t* sel, int n_launch,
                                   long long n_out_max, const float* taps, int L, int M, int K, hipStream_t st);
+// ctts_rs_window (include/chattts_amd.h), field for field (capi.hip asserts the layout): a window x[in_off, in_off + n_in) holds samples
+// [origin, origin + n_in) of a signal of `total` samples; outputs [o_lo, o_hi) of that signal's conversion go to y[out_off ..], followed by
+// `pad` zeros (< 256).  `rate`, `total`: the host's (which table converts the window; the checks)
+struct RsWindow {
+  long long in_off, n_in, origin, total, o_lo, o_hi, out_off;
+  int32_t rate, pad;
+};
+// windows sel[0 .. n_launch-1] (or null: 0 .. n_launch-1) of the table, all by the same L/M; n_out_max: their longest chunk (grid size)
+hipError_t launch_resample_windows(const float* x, const RsWindow* win, float* y, const int32_t* sel, int n_launch, long long n_out_max,
+                                   const float* taps, int L, int M, int K, hipStream_t st);
+// the conversion behind ctts_codec_decode_windows_rate: window i's chunk is rs[i].o_hi - rs[i].o_lo floats at chunks + rs[i].out_off
+// (rs[i].rate >= 0: resampled) or rs[i].n_in floats at wav + rs[i].in_off (rate < 0: the 24 kHz crop); the output layout, the peak, the
+// conversion and the keep masks (win[i].keep) are launch_crop_pcm16_windows's
+hipError_t launch_chunks_pcm16(const float* wav, const float* chunks, const CodecWindow* win, const RsWindow* rs, int n_win, int out_f32,
+                               int product, float keep_thr, void* out, uint8_t* keep, hipStream_t st);
 
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------
 // |STFT| of one waveform: center=True reflect padding, frame f = padded[256 f, 256 f + 1024) * window, 1024-point FFT,

@@ -1455,6 +1455,39 @@ class CodecEngine:
                 self._resample_launch(x, off, y, off_out, idx, orig, r)
         return y, off_out
 
+    def resample_window(self, wav: torch.Tensor, origin: int, total: int, o_lo: int, o_hi: int, orig: int, new: int) -> torch.Tensor:
+        """Outputs [o_lo, o_hi) of `resample(signal, orig, new)` from a WINDOW of the signal (ctts_resample_windows, resample_win_k):
+        `wav`, 1-D or [B, n] float32 on the device, holds samples [origin, origin + n) of a signal of `total` samples (every row of its
+        own signal, all at the same place) -> [.., o_hi - o_lo], bit for bit the slice of the whole signal's conversion.  The window
+        must hold the inputs those outputs read (`resample.window_inputs`); samples outside the signal read as zero.  ValueError before
+        any launch otherwise, and for what `resample` refuses."""
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
+            raise ValueError("resample_window: a float32 device tensor, 1-D or [B, n]")
+        L, M, K, _ = RS.plan(orig, new, [0, 1])
+        origin, total, o_lo, o_hi = int(origin), int(total), int(o_lo), int(o_hi)
+        B, n = (1, int(wav.shape[0])) if wav.dim() == 1 else (int(wav.shape[0]), int(wav.shape[1]))
+        a, b = RS.window_inputs(L, M, K, o_lo, o_hi, total)
+        if origin < 0 or n < 1 or origin + n > total or total >= 1 << 31:
+            raise ValueError(f"resample_window: samples [{origin}, {origin + n}) are no window of a signal of {total}")
+        if a < b and (origin > a or origin + n < b):
+            raise ValueError(f"resample_window: outputs [{o_lo}, {o_hi}) read samples [{a}, {b}), the window holds [{origin}, {origin + n})")
+        if not 1 <= B <= 1024:
+            raise ValueError("resample_window: 1 to 1024 rows")
+        m = o_hi - o_lo
+        y = torch.empty((B, m), dtype=torch.float32, device=wav.device)
+        if m > 0:
+            x = wav.contiguous()
+            tab = np.zeros(B, _lib.RS_WINDOW)
+            tab["in_off"], tab["n_in"], tab["origin"], tab["total"] = np.arange(B, dtype=np.int64) * n, n, origin, total
+            tab["o_lo"], tab["o_hi"], tab["out_off"] = o_lo, o_hi, np.arange(B, dtype=np.int64) * m
+            tab_d = torch.from_numpy(tab.view(np.uint8)).to(wav.device)
+            st = torch.cuda.current_stream(wav.device)
+            _lib.check(self.lib.ctts_resample_windows(x.data_ptr(), x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), B, y.data_ptr(),
+                                                      y.numel(), None, None, 0, self._resample_taps(orig, new).data_ptr(), L, M, K,
+                                                      st.cuda_stream), "ctts_resample_windows")
+            tab_d.record_stream(st)
+        return y[0] if wav.dim() == 1 else y
+
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
     def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None):
         """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
@@ -1571,13 +1604,26 @@ class CodecEngine:
 
     HALO_FRAMES = HALO_FRAMES
 
-    def decode_window(self, result_list: List[torch.Tensor], s_lo: int, s_hi: int) -> torch.Tensor:
+    def decode_window(self, result_list: List[torch.Tensor], s_lo: int, s_hi: int, sample_rate: Optional[int] = None) -> torch.Tensor:
         """Samples [s_lo, s_hi) of `decode_to_wavs(result_list)` WITHOUT decoding the whole batch: the acoustic decoder is a
         stack of short symmetric convolutions, so those samples depend only on the tokens within HALO_FRAMES mel frames
         (+ the 4 overlapping ISTFT frames) of them.  Only that token window (zero padded like core.py:525-533) goes
         through DVAE + Vocos; at the true ends of the sequence the window is the sequence's own edge, so the result equals
         the full decode up to summation order.  This is what makes streaming O(n): the reference re-decodes the entire
-        prefix at every yield (core.py:482-497) to hand out the next `stream_speed` samples of it."""
+        prefix at every yield (core.py:482-497) to hand out the next `stream_speed` samples of it.
+        `sample_rate` (None or 24000: the path above, bit for bit): the same range of the decode RESAMPLED AS ONE SIGNAL -- outputs
+        [ceil(s_lo L / M), ceil(s_hi L / M)) of `resample(decode_to_wavs(result_list))`, so consecutive ranges tile the resampled
+        signal.  The window of `resample.window_inputs` is decoded as above and converted by `resample_window`: no filter state."""
+        if sample_rate is not None and int(sample_rate) != self.SAMPLE_RATE:
+            Tn = max(int(r.size(0)) for r in result_list)
+            total = VOCOS.hop * (2 * Tn - 1)
+            L, M, K, _ = RS.plan(self.SAMPLE_RATE, int(sample_rate), [0, 1])
+            lo, hi = min(max(0, int(s_lo)), max(total, 0)), min(max(total, 0), int(s_hi))
+            o_lo, o_hi = RS.out_len(lo, L, M), RS.out_len(max(lo, hi), L, M)
+            if o_hi <= o_lo:
+                return torch.empty((len(result_list), 0), dtype=torch.float32, device=self.device)
+            a, b = RS.window_inputs(L, M, K, o_lo, o_hi, total)
+            return self.resample_window(self.decode_window(result_list, a, b), a, total, o_lo, o_hi, self.SAMPLE_RATE, int(sample_rate))
         win = window_for_samples(max(int(r.size(0)) for r in result_list), s_lo, s_hi)
         if win is None:
             return torch.empty((len(result_list), 0), dtype=torch.float32, device=self.device)
@@ -1590,7 +1636,8 @@ class CodecEngine:
         wav = self.vocos_decode(self.dvae_decode(batch))
         return wav[:, c_lo: c_hi]
 
-    def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64"):
+    def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
+                       sample_rates=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -1600,7 +1647,16 @@ class CodecEngine:
         float32.  With `keep_thr`, a window marked `tail` comes back with its samples |x| <= keep_thr removed -- the serial path's
         last chunk (core.py, `_infer`): the mask is taken from the float samples on the device, the conversion uses the peak over
         the whole crop (the removed samples are all below the threshold, so that is the peak of the kept ones whenever any is kept).
-        One table upload, one pass, one device-to-host copy whatever the number of windows."""
+        One table upload, one pass, one device-to-host copy whatever the number of windows.
+        `sample_rates` (None, or all 24000: the call above, argument for argument): one rate per window.  A window at rate r yields
+        outputs [ceil(s_lo L / M), ceil(s_hi L / M)) of the resampled decode of its prefix -- `decode_window(.., sample_rate=r)` --
+        with the peak, the conversion and a tail's strip taken on the resampled samples (ctts_codec_decode_windows_rate: the same
+        pass, one resampler launch per distinct rate, one conversion launch)."""
+        if sample_rates is not None:
+            if len(sample_rates) != len(windows):
+                raise ValueError("decode_windows: one sample rate per window")
+            if any(int(r) != self.SAMPLE_RATE for r in sample_rates):
+                return self._decode_windows_rate(store, windows, [int(r) for r in sample_rates], pcm16, keep_thr, product)
         assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
         S, cap = int(store.size(0)), int(store.size(1))
         dt = np.int16 if pcm16 else np.float32
@@ -1636,6 +1692,89 @@ class CodecEngine:
                                                       {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws,
                                                       cur.cuda_stream), "ctts_codec_decode_windows")
         tab_d.record_stream(cur)
+        host = self.to_host(buf)
+        vals = host[:n_out].view(dt)
+        for k, i in enumerate(live):
+            a = vals[int(off[k]): int(off[k]) + int(n[k])]
+            if tab[k, 5]:
+                kb = n_out + int(off[k]) // 8
+                a = a[np.unpackbits(host[kb: kb + (int(n[k]) + 7) // 8])[: int(n[k])].astype(bool)]
+            out[i] = a
+        return out
+
+    def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str):
+        """`decode_windows` with at least one window at another rate than 24 kHz"""
+        assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
+        S, cap = int(store.size(0)), int(store.size(1))
+        dt = np.int16 if pcm16 else np.float32
+        out: list = [None] * len(windows)
+        plans, pairs = {}, {}              # rate -> (L, M, K); rate -> (index, L, M, K) once a window at it has samples
+        rows, res, live = [], [], []
+        for i, (w, r) in enumerate(zip(windows, rates)):
+            slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
+            tail = len(w) > 4 and bool(w[4]) and keep_thr is not None
+            if not (0 <= slot < S and 0 <= Tn <= cap):
+                raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
+            total = VOCOS.hop * (2 * Tn - 1)
+            hi = total if s_hi is None else int(s_hi)
+            if r == self.SAMPLE_RATE:
+                win, rs = window_for_samples(Tn, s_lo, hi), None
+            else:
+                if r not in plans:
+                    plans[r] = RS.plan(self.SAMPLE_RATE, r, [0, 1])[:3]        # every refusal before the launch
+                L, M, K = plans[r]
+                lo, hi = max(0, int(s_lo)), min(total, hi)
+                o_lo, o_hi = (RS.out_len(lo, L, M), RS.out_len(hi, L, M)) if hi > lo else (0, 0)
+                win = None
+                if o_hi > o_lo:
+                    a, b = RS.window_inputs(L, M, K, o_lo, o_hi, total)
+                    q = pairs.setdefault(r, (len(pairs), L, M, K))[0]
+                    win, rs = window_for_samples(Tn, a, b), (q, a, total, o_lo, o_hi)
+            if win is None:
+                out[i] = np.zeros((0,), dt)
+                continue
+            rows.append((slot, *win, int(tail), 0, 0))
+            res.append(rs)
+            live.append(i)
+        if not live:
+            return out
+        tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]
+        tok = np.zeros(len(live) + 1, np.int64)
+        np.cumsum(tab[:, 2] - tab[:, 1], out=tok[1:])
+        rtab = np.zeros(len(live), _lib.RS_WINDOW)                           # ctts_rs_window[n]
+        rtab["in_off"] = VOCOS.hop * (2 * tok[:-1] - np.arange(len(live))) + tab[:, 3]
+        rtab["n_in"] = tab[:, 4] - tab[:, 3]
+        rtab["rate"] = -1
+        chunk = 0
+        for k, rs in enumerate(res):
+            if rs is not None:
+                q, a, total, o_lo, o_hi = rs
+                m = o_hi - o_lo
+                rtab[k] = (rtab["in_off"][k], rtab["n_in"][k], a, total, o_lo, o_hi, chunk, q, -m % 8)
+                chunk += m + (-m % 8)
+        sel = np.array([k for q in range(len(pairs)) for k, rs in enumerate(res) if rs is not None and rs[0] == q], dtype=np.int32)
+        n = np.where(rtab["rate"] >= 0, rtab["o_hi"] - rtab["o_lo"], rtab["n_in"]).astype(np.int64)
+        off = np.zeros(len(live) + 1, np.int64)
+        np.cumsum((n + 7) // 8 * 8, out=off[1:])                             # every window starts on a multiple of 8 samples
+        esz = 2 if pcm16 else 4
+        n_out, any_keep = int(off[-1]) * esz, bool(tab[:, 5].any())
+        n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if any_keep else 0
+        cur = torch.cuda.current_stream(self.device)
+        buf = torch.empty((n_out + n_keep,), dtype=torch.uint8, device=self.device)      # samples | keep masks: one copy brings both
+        blob = np.concatenate([tab.view(np.uint8).reshape(-1), rtab.view(np.uint8), sel.view(np.uint8)])
+        blob_d = torch.from_numpy(blob).to(self.device)                      # one upload: both tables and the selection
+        by_q = sorted(pairs.items(), key=lambda kv: kv[1][0])
+        rate_tab = (_lib.Rate * max(1, len(by_q)))()
+        for r, (q, L, M, K) in by_q:
+            rate_tab[q].taps, rate_tab[q].L, rate_tab[q].M, rate_tab[q].K = self._resample_taps(self.SAMPLE_RATE, r).data_ptr(), L, M, K
+        ws, nws = self._ws_bytes(self.lib.ctts_codec_windows_rate_workspace_bytes(len(live), int(tok[-1]), chunk))
+        base = blob_d.data_ptr()
+        _lib.check(self.lib.ctts_codec_decode_windows_rate(
+            self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap, base, tab.ctypes.data_as(C.c_void_p),
+            base + tab.nbytes, rtab.ctypes.data_as(C.c_void_p), base + tab.nbytes + rtab.nbytes, sel.ctypes.data_as(C.c_void_p), len(live),
+            C.cast(rate_tab, C.c_void_p), len(by_q), 1 if pcm16 else 0, buf.data_ptr(), buf.data_ptr() + n_out if any_keep else None,
+            {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws, cur.cuda_stream), "ctts_codec_decode_windows_rate")
+        blob_d.record_stream(cur)
         host = self.to_host(buf)
         vals = host[:n_out].view(dt)
         for k, i in enumerate(live):

@@ -86,3 +86,22 @@ def plan(orig: int, new: int, off) -> Tuple[int, int, int, np.ndarray]:
     if out[-1] >= 1 << 31:
         raise ValueError("resample: the output would hold 2^31 samples or more")
     return L, M, K, np.asarray(out, dtype=np.int64)
+
+
+def window_inputs(L: int, M: int, K: int, o_lo: int, o_hi: int, total: int) -> Tuple[int, int]:
+    """[a, b): the inputs inside [0, total) that outputs [o_lo, o_hi) of the conversion of a `total`-sample signal read -- output
+    o = j L + i reads inputs j M + k - width, k = 0 .. K-1, so a = (o_lo // L) M - width and b = ((o_hi - 1) // L) M + width + M,
+    clipped (inputs outside the signal read as zero).  What a streamed chunk's window must hold (csrc/resample.hip, resample_win_k).
+    An empty range of outputs reads nothing: (a, a).  ValueError: o_lo < 0, o_hi < o_lo, o_hi beyond ceil(total L / M)."""
+    L, M, K, o_lo, o_hi, total = int(L), int(M), int(K), int(o_lo), int(o_hi), int(total)
+    if L < 1 or M < 1 or K <= M or (K - M) % 2 or total < 0:
+        raise ValueError(f"resample: no table has L = {L}, M = {M}, K = {K} (K = 2 width + M), and a signal holds 0 samples or more")
+    if o_lo < 0 or o_hi < o_lo:
+        raise ValueError(f"resample: outputs [{o_lo}, {o_hi}) are not a range")
+    if o_hi > out_len(total, L, M):
+        raise ValueError(f"resample: output {o_hi} lies beyond the {out_len(total, L, M)} outputs of {total} samples")
+    width = (K - M) // 2
+    a = min(max((o_lo // L) * M - width, 0), total)
+    if o_hi == o_lo:
+        return a, a
+    return a, max(a, min(((o_hi - 1) // L) * M + width + M, total))

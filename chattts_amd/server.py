@@ -85,7 +85,8 @@ def _have_av() -> bool:
 
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
-               batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False):
+               batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
+               stream_sample_rates=None):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -107,7 +108,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     every path is as without it, a `"sample_rate"` key is ignored with the "unsupported parameters" warning): the rates a non-streamed
     request body may ask for with `"sample_rate"`, e.g. (8000, 16000, 24000, 44100, 48000) -- the audio is resampled on the device
     (Chat.infer(sample_rate=) / SpeechBatcher.submit(sample_rate=)) and the WAV header carries the rate; another rate, or a rate other
-    than 24000 with `"stream": true` (the filter's state is not carried across chunks), gets a 400.  `voice_upload=True` adds
+    than 24000 with `"stream": true`, gets a 400 -- unless `stream_sample_rates` (default None: every path is as without it) holds it: the
+    rates a STREAMED request body may ask for.  Such a stream's chunks are their ranges of the resampled decode (Chat.infer(stream=True,
+    sample_rate=, stream_resample=True); with `batch_streams` SpeechBatcher.submit_stream(sample_rate=), the chunks of streams at
+    different rates still share one decoder pass) and the open-ended WAV header carries the rate.  `voice_upload=True` adds
     `POST /v1/audio/voices?name=NAME[&text=TRANSCRIPT]`, whose body is a WAV file (8/16/32-bit PCM, any rate, any channel count): the clip
     is resampled to 24 kHz on the device and encoded (Chat.sample_audio_speaker(wav, rate)) under the GPU lock, and NAME becomes a cloned
     voice of this app."""
@@ -135,7 +139,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     pool_split = bool(batch_split) and batcher is not None
     allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
     rates_ok = None if sample_rates is None else {int(r) for r in sample_rates}
-    if rates_ok is not None:
+    stream_rates_ok = None if stream_sample_rates is None else {int(r) for r in stream_sample_rates}
+    if rates_ok is not None or stream_rates_ok is not None:
         allowed = allowed | {"sample_rate"}
 
     def voice_token_room():
@@ -190,6 +195,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
     def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE):                 # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if req.stream and rate != SAMPLE_RATE:       # one text: split_text changes nothing but is refused for a stream at another rate
+            kw = {**kw, "stream_resample": True, "split_text": False}
         return chat.infer(text=[req.input], stream=bool(req.stream), lang=None, skip_refine_text=True, refine_text_only=False,
                           use_decoder=True, do_text_normalization=True, do_homophone_replacement=True,
                           params_infer_code=code_params(req.voice), pcm16=True, **kw)
@@ -210,15 +217,20 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             hint = " (mp3 / ogg need PyAV, which is not installed here)" if fmt in ("mp3", "ogg") else ""
             raise HTTPException(400, detail=f"Unsupported audio format: {fmt}, supported formats: {', '.join(sorted(formats))}{hint}")
         rate = SAMPLE_RATE
-        if rates_ok is not None and request_data.get("sample_rate") is not None:
+        if (rates_ok is not None or stream_rates_ok is not None) and request_data.get("sample_rate") is not None:
             try:
                 rate = int(request_data["sample_rate"])
             except (TypeError, ValueError):
                 rate = -1
-            if rate not in rates_ok:
+            if req.stream and stream_rates_ok is not None and rate in stream_rates_ok:
+                pass                                 # a stream at this rate is served
+            elif rates_ok is None and not req.stream:
+                log.warning("ignoring unsupported parameters: ['sample_rate']")       # only streams were given rates: as without the key
+                rate = SAMPLE_RATE
+            elif rates_ok is not None and rate not in rates_ok:
                 raise HTTPException(400, detail=f"Unsupported sample_rate: {request_data['sample_rate']}, supported: "
                                                 f"{', '.join(str(r) for r in sorted(rates_ok))}")
-            if req.stream and rate != SAMPLE_RATE:
+            elif req.stream and rate != SAMPLE_RATE:
                 raise HTTPException(400, detail=f"sample_rate {rate} is served for non-streamed requests only: a stream's chunks are "
                                                 f"produced at {SAMPLE_RATE} Hz (the resampling filter's state is not carried across chunks)")
         refine = refine_of(request_data)
@@ -242,12 +254,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
         if req.stream and pool_streams:
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
-                chunks = batcher.submit_stream(req.input, code_params(req.voice), **rkw)
+                skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
+                chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw)
                 try:
                     first = True
                     async for chunk in iterate_in_threadpool(chunks):
                         if fmt == "wav" and first:
-                            yield wav_stream_header()
+                            yield wav_stream_header(rate)
                         first = False
                         if np.asarray(chunk).size:
                             yield encode(chunk, header=False)
@@ -262,10 +275,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        gen = infer(req)
+                        gen = infer(req, rate)
                         async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
                             if fmt == "wav" and first:
-                                yield wav_stream_header()
+                                yield wav_stream_header(rate)
                             first = False
                             if np.asarray(chunk).size:
                                 yield encode(chunk, header=False)

@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import resample as RS
 from ._sync import wait_event, wait_stream
 from .config import GPT
 from .engine import GptEngine, gen_logits, plan_from_processors
@@ -723,6 +724,7 @@ class SpeechBatcher:
         self.streams = bool(streams)
         self.stream_decode_calls = 0  # window decodes over the due chunks of streamed requests
         self.stream_chunks = 0        # chunks those decodes served (empty chunks included)
+        self.stream_resampled_chunks = 0   # those of them at another rate than 24 kHz
         self.max_stream_group = 0     # most chunks one window decode served
         self.cancelled = 0            # streams closed by their consumer before the end
         self._streams: dict = {}      # request id -> SpeechStream
@@ -793,17 +795,23 @@ class SpeechBatcher:
         the Future is cancelled.  Nothing happens when it has completed already."""
         self._in.put(_Cancel(fut.rid))
 
-    def submit_stream(self, text: str, params, refine=None, split_text: bool = False) -> SpeechStream:
+    def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
-        is not served from the pool."""
+        is not served from the pool.  `sample_rate` (None: 24000): the serial call's `sample_rate=` with `stream_resample=True` --
+        every chunk is its range of the prefix's decode resampled as one signal; the chunks of streams at different rates that are
+        due at one poll still come from one decoder pass (CodecEngine.decode_windows(sample_rates=))."""
         if split_text:
             raise ValueError("split_text is served for non-streamed requests only")
         if not self.streams:
             raise RuntimeError("this SpeechBatcher was built without streams=True")
         self._check_refine(refine)
+        rate = None if sample_rate is None or int(sample_rate) == 24000 else int(sample_rate)
+        if rate is not None:
+            RS.plan(24000, rate, [0, 1])       # an unsupported pair is refused here, not at the first chunk
         h = SpeechStream(self, next(self._ids))
+        h.sample_rate = rate
         self._in.put((h.rid, text, params, h, refine))
         return h
 
@@ -823,7 +831,8 @@ class SpeechBatcher:
     def _occupancy_streams(self) -> dict:
         if self.streams:
             return {**self._occupancy(), "streams": len(self._streams), "stream_decode_calls": self.stream_decode_calls,
-                    "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled}
+                    "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled,
+                    "stream_resampled_chunks": self.stream_resampled_chunks}
         return self._occupancy()
 
     def _occupancy(self) -> dict:
@@ -1083,7 +1092,10 @@ class SpeechBatcher:
                 self.stream_decode_calls += 1
                 self.max_stream_group = max(self.max_stream_group, len(live))
             self.stream_chunks += len(live)
-            pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live])
+            rates = [getattr(self._streams[c[0]], "sample_rate", None) for c in live]
+            self.stream_resampled_chunks += sum(r is not None for r in rates)
+            rkw = {"sample_rates": [24000 if r is None else r for r in rates]} if any(r is not None for r in rates) else {}
+            pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **rkw)     # 24 kHz only: today's call
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for rid in {c[0] for c in live}:
                 self.pool.cancel(rid)

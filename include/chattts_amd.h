@@ -416,6 +416,53 @@ int ctts_codec_decode_windows(ctts_codec* c, const float* hid, int64_t slot_stri
                               const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win, int32_t out_type, void* out,
                               uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream);
 
+/* Streamed chunks at another sample rate.  A chunk at rate r is outputs [o_lo, o_hi) of the conversion of a whole signal of `total` samples
+ * (for a stream: the decode of a token prefix, resampled as one segment alone); those outputs read inputs
+ *   [(o_lo / L) M - width, ((o_hi - 1) / L) M + width + M)  clipped to [0, total)            (resample.py, window_inputs)
+ * so a WINDOW of the signal that holds them is enough: x[in_off, in_off + n_in) = samples [origin, origin + n_in) of the signal.  Positions
+ * outside the window read as zero -- which the checks below make samples outside the signal only, the segment-alone rule.  Given the same
+ * samples, a chunk equals outputs [o_lo, o_hi) of ctts_resample_ragged over the whole signal bit for bit (the same accumulation; a tile starts
+ * at o_lo, at any phase).  The chunk goes to y[out_off, out_off + o_hi - o_lo), followed by `pad` zeros (0 .. 255).
+ * ctts_resample_windows: the kernel alone over packed float windows, all by one L/M.  sel_dev / sel_host (both NULL: every window): the n_sel
+ * windows this call converts, so windows of one pack that go to different rates take one call per rate.  n_x / n_y: the floats behind x / y.
+ * Refused before anything is launched: a null table, a pair ctts_resample_supported refuses, o_lo < 0, o_hi < o_lo (o_hi == o_lo converts
+ * nothing), o_hi beyond ceil(total L / M), a window outside [0, total), a window that does not hold the inputs above, windows outside x or y,
+ * more than 1024 windows. */
+typedef struct {
+  int64_t in_off, n_in;   /* the window's samples in x */
+  int64_t origin;         /* position of its first sample in the signal */
+  int64_t total;          /* length of the signal */
+  int64_t o_lo, o_hi;     /* outputs of the signal's conversion to produce */
+  int64_t out_off;        /* first output element */
+  int32_t rate;           /* ctts_codec_decode_windows_rate: index into `rates`, < 0: the window stays at 24 kHz; ignored otherwise */
+  int32_t pad;            /* zeros written behind the chunk */
+} ctts_rs_window;         /* 64 bytes */
+int ctts_resample_windows(const float* x, int64_t n_x, const ctts_rs_window* win_dev, const ctts_rs_window* win_host, int32_t n_win, float* y,
+                          int64_t n_y, const int32_t* sel_dev, const int32_t* sel_host, int32_t n_sel, const float* taps, int32_t L, int32_t M,
+                          int32_t K, void* stream);
+
+/* ctts_codec_decode_windows with one sample rate per window: gather and the ragged DVAE / Vocos stages as there, then the windows that leave
+ * 24 kHz are resampled (one launch per distinct rate) into float chunks in the workspace, then ONE conversion launch writes every window's
+ * chunk -- the 24 kHz crop, or the resampled chunk -- in ctts_codec_decode_windows's output layout (window i's n_i samples from element
+ * sum_{j<i} ceil8(n_j) on, n_i = o_hi - o_lo or c_hi - c_lo; one peak per window over the chunk's own samples; keep masks as there, taken on
+ * the chunk's floats).  win: as there; [c_lo, c_hi) of a resampled window is the range the resampler reads.  rs (device and host): entry i
+ * describes window i: in_off / n_in = the crop in the packed decode (256 (2 tok_off[i] - i) + c_lo, c_hi - c_lo); rate < 0 and nothing else
+ * for a 24 kHz window; else origin = 512 t_lo + c_lo, total = the prefix's 256 (2 Tn - 1) samples, [o_lo, o_hi) non-empty, out_off = the
+ * running sum of ceil8(o_hi - o_lo) over the resampled windows before it, pad = the rest to that multiple of 8.  sel (device and host): the
+ * resampled windows rate by rate, ascending within a rate.  Refused before anything is launched: everything ctts_codec_decode_windows and
+ * ctts_resample_windows refuse (a null table, an unsupported pair, o_hi <= o_lo, a crop that does not hold the inputs the outputs read, more
+ * than 1024 windows) and tables that do not agree with each other. */
+typedef struct {
+  const float* taps;      /* [L][K] float32 on the device */
+  int32_t L, M, K, reserved;
+} ctts_rate;
+size_t ctts_codec_windows_rate_workspace_bytes(int32_t n_win, int32_t total_tokens, int64_t chunk_floats);   /* 0: bad arguments */
+int ctts_codec_decode_windows_rate(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots, int32_t hid_cap,
+                                   const ctts_window* win_dev, const ctts_window* win_host, const ctts_rs_window* rs_dev,
+                                   const ctts_rs_window* rs_host, const int32_t* sel_dev, const int32_t* sel_host, int32_t n_win,
+                                   const ctts_rate* rates, int32_t n_rates, int32_t out_type, void* out, uint8_t* keep_bits, int32_t product,
+                                   float keep_thr, void* workspace, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Full DVAE (asset/DVAE.safetensors): audio -> 4 x T codes and codes -> mel through the GFSQ codebook.
  * Replaces `self.dvae(wav, "encode")` of `Chat.sample_audio_speaker` (ChatTTS/core.py:179-180 ->

@@ -2,7 +2,7 @@
 batching (`create_app(..., batch_slots=S)`) and once without, plus the sampling kernel's cost in a per-request pool vs a plain pool.
 Prints one JSON line.  Not a bench.py leg.
 
-    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R]]
+    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R] [--sample-rate HZ]]
     python tools/serve_load.py --refine [--refine-max-new 64] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
     python tools/serve_load.py --split [--split-sentences 6] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
 
@@ -20,6 +20,8 @@ additionally the time to the first audio chunk.
 other, each a batch of one) and on (streams share the slot pool, the chunks due at one poll come from one window decode): per request
 the time to the first audio byte and the total time, p50 / p95, and audio-s/s; then one streamed request alone on both (--repeat runs
 each, off and on alternating: the single-stream time to first byte and its run-to-run spread).  --ragged-decode composes.
+--stream --sample-rate HZ: instead, the pooled streams (`batch_streams` on) at 24 kHz and asking for HZ (`stream_sample_rates`: every chunk
+resampled on the device) in one process, the same figures, and one stream alone on both, alternating.
 
 --ragged-decode: also the batched burst with `create_app(..., ragged_decode=True)` (the requests that finish in one poll decoded in one
 ragged pass) -- an A/B against the default batched burst (one decode per request), with both runs' decode-call counts.
@@ -88,17 +90,20 @@ def burst(chat, voices, n, batch_slots, ragged_decode=False, counts=False):
     return out
 
 
-def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app=None):
+def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app=None, rate=None):
     """n concurrent streamed requests, driven through the ASGI interface on one event loop (a test client would hand the body over only
-    once it is complete): the clock of a request stops at its first body message that carries audio, and at its last message"""
+    once it is complete): the clock of a request stops at its first body message that carries audio, and at its last message.
+    `rate`: the streams ask for that sample rate (`stream_sample_rates`; None: 24 kHz, the body carries no rate)"""
     import asyncio
     own = app is None
     if own:
-        app = server.create_app(chat, voices, batch_slots=slots, ragged_decode=ragged_decode, batch_streams=batch_streams)
+        app = server.create_app(chat, voices, batch_slots=slots, ragged_decode=ragged_decode, batch_streams=batch_streams,
+                                **({} if rate is None else {"stream_sample_rates": (int(rate),)}))
     names = sorted(voices)
+    more = {} if rate is None else {"sample_rate": int(rate)}
 
     async def one(i, text, out):
-        body = json.dumps({"input": text, "voice": names[i % len(names)], "response_format": "pcm", "stream": True}).encode()
+        body = json.dumps({"input": text, "voice": names[i % len(names)], "response_format": "pcm", "stream": True, **more}).encode()
         scope = dict(type="http", asgi={"version": "3.0"}, http_version="1.1", method="POST", path="/v1/audio/speech", raw_path=b"/v1/audio/speech",
                      query_string=b"", root_path="", scheme="http", server=("load", 80), client=("load", 1),
                      headers=[(b"content-type", b"application/json"), (b"content-length", str(len(body)).encode())])
@@ -133,18 +138,33 @@ def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app
         app.state.batcher.close()
     first = [o.get("first_s", float("nan")) for o in outs]
     total = [o["total_s"] for o in outs]
-    audio = sum(o.get("bytes", 0) for o in outs) / 2 / server.SAMPLE_RATE
+    audio = sum(o.get("bytes", 0) for o in outs) / 2 / (server.SAMPLE_RATE if rate is None else int(rate))
     pct = lambda v, q: round(float(np.percentile(v, q)), 4)
     out = dict(failed=sum(o.get("status") != 200 or "first_s" not in o for o in outs), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3),
                audio_s=round(audio, 2), first_byte_p50_s=pct(first, 50), first_byte_p95_s=pct(first, 95), total_p50_s=pct(total, 50),
                total_p95_s=pct(total, 95))
-    for k in ("max_coresident", "stream_decode_calls", "stream_chunks", "max_stream_group", "decode_calls"):
+    for k in ("max_coresident", "stream_decode_calls", "stream_chunks", "max_stream_group", "decode_calls", "stream_resampled_chunks"):
         if k in pool:
             out[k] = pool[k]
     return out
 
 
+def stream_rate_main(chat, voices, a):
+    """--stream --sample-rate R: the pooled streams at 24 kHz and at R Hz in one process, then one stream alone on both, alternating"""
+    base = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode)
+    at = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode, rate=a.sample_rate)
+    single = {"24000": [], str(a.sample_rate): []}
+    for _ in range(a.repeat):
+        for rate in (None, a.sample_rate):
+            single[str(rate or 24000)].append(stream_burst(chat, voices, 1, a.slots, True, a.ragged_decode, rate=rate)["first_byte_p50_s"])
+    print(json.dumps(dict(metric="serve_load_stream_rate", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, sample_rate=a.sample_rate,
+                          at_24000=base, at_rate=at, first_byte_p50_delta_s=round(at["first_byte_p50_s"] - base["first_byte_p50_s"], 4),
+                          single_stream_first_byte_s=single)))
+
+
 def stream_main(chat, voices, a):
+    if a.sample_rate is not None and int(a.sample_rate) != server.SAMPLE_RATE:
+        return stream_rate_main(chat, voices, a)
     off = stream_burst(chat, voices, a.n, a.slots, False, a.ragged_decode)
     on = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode)
     single = {"off": [], "on": []}
@@ -303,6 +323,7 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--ragged-decode", action="store_true", help="A/B: also the batched burst with one ragged decode per poll")
     ap.add_argument("--stream", action="store_true", help="streamed requests: batch_streams off vs on")
+    ap.add_argument("--sample-rate", type=int, default=None, help="--stream: the pooled streams at 24 kHz vs at this rate (resampled chunks)")
     ap.add_argument("--repeat", type=int, default=5, help="--stream: single-stream runs per leg (run-to-run spread)")
     ap.add_argument("--refine", action="store_true", help="two-stage requests: Chat.infer serially vs the two-pool batcher")
     ap.add_argument("--refine-max-new", type=int, default=64, help="--refine: max_new_token of the refine-text pass")
