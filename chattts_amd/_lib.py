@@ -54,6 +54,10 @@ RS_WINDOW = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("origin", "<i8"), ("t
                       ("out_off", "<i8"), ("rate", "<i4"), ("pad", "<i4")])
 
 
+# ctts_g711_range (32 bytes): start, n int64; law int32 (0 mu-law, 1 A-law, -1 skip); pad
+G711_RANGE = np.dtype([("start", "<i8"), ("n", "<i8"), ("law", "<i4"), ("pad0", "<i4"), ("pad1", "<i8")])
+
+
 class Rate(C.Structure):
     """ctts_rate: one conversion of ctts_codec_decode_windows_rate"""
     _fields_ = [("taps", P), ("L", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("reserved", C.c_int32)]
@@ -146,6 +150,7 @@ SIGNATURES = {
     "ctts_codec_windows_rate_workspace_bytes": (SZ, [I32, I32, C.c_int64]),
     "ctts_codec_decode_windows_rate": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, P, P, P, P, I32, P, I32, I32, P, P, I32, F, P,
                                                  SZ, P]),
+    "ctts_g711_encode_ranges": (C.c_int, [P, P, P, P, I32, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),
     "ctts_dvae_destroy": (None, [P]),
     "ctts_dvae_code_frames": (I32, [I32]),

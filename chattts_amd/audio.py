@@ -6,6 +6,7 @@ mp3 / ogg go through PyAV in the reference (tools/audio/av.py), which is not par
 from __future__ import annotations
 
 import math
+import struct
 import wave
 from io import BytesIO
 
@@ -43,11 +44,72 @@ def pcm_to_wav_bytes(wav: np.ndarray, sample_rate: int = 24000) -> bytes:
     return buf.getvalue()
 
 
-def load_wav(data: bytes):
+WAVE_FORMAT_ALAW, WAVE_FORMAT_MULAW = 6, 7
+
+
+def g711_wav_header(law, sample_rate: int, n_samples=None) -> bytes:
+    """everything in front of the samples of a mono G.711 RIFF/WAVE file: format tag 7 (mu-law) / 6 (A-law), 8 bits, block align 1, an
+    18-byte `fmt ` chunk with cbSize = 0, a `fact` chunk holding the sample count, the `data` chunk's header.  `n_samples` None: the
+    open-ended form of a stream -- 0xFFFFFFFF in the RIFF, `fact` and `data` lengths, like `server.wav_stream_header`."""
+    from .g711 import law_of
+    tag = (WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW)[law_of(law)]
+    if n_samples is None:
+        riff = fact = data = 0xFFFFFFFF
+    else:
+        fact = data = int(n_samples)
+        riff = 4 + (8 + 18) + (8 + 4) + 8 + data + (data & 1)
+    return (b"RIFF" + struct.pack("<I", riff) + b"WAVEfmt " + struct.pack("<IHHIIHHH", 18, tag, 1, int(sample_rate), int(sample_rate), 1, 8, 0)
+            + b"fact" + struct.pack("<II", 4, fact) + b"data" + struct.pack("<I", data))
+
+
+def g711_to_wav_bytes(codes: np.ndarray, law, sample_rate: int = 8000) -> bytes:
+    """G.711 codes (uint8, `g711.encode`'s or the device's) -> a mono WAVE_FORMAT_MULAW / WAVE_FORMAT_ALAW file; an odd-length `data` chunk
+    is followed by one pad byte (RIFF chunks are word aligned)"""
+    codes = np.ascontiguousarray(np.asarray(codes).reshape(-1))
+    if codes.dtype != np.uint8:
+        raise ValueError(f"g711_to_wav_bytes takes uint8 codes, got {codes.dtype}")
+    return g711_wav_header(law, sample_rate, codes.size) + codes.tobytes() + (b"\0" if codes.size & 1 else b"")
+
+
+def _load_g711_wav(data: bytes):
+    """a WAVE_FORMAT_MULAW / WAVE_FORMAT_ALAW file parsed chunk by chunk (stdlib `wave` refuses the tags) -> (float32 mono, rate), or None
+    when the bytes are no RIFF/WAVE with one of those two tags -- then `load_wav` goes on as without the option"""
+    from .g711 import expand
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        return None
+    pos, fmt, body = 12, None, None
+    while pos + 8 <= len(data) and (fmt is None or body is None):
+        cid, size = data[pos: pos + 4], struct.unpack_from("<I", data, pos + 4)[0]
+        if cid == b"fmt " and size >= 16 and pos + 8 + 16 <= len(data):
+            fmt = struct.unpack_from("<HHIIHH", data, pos + 8)
+        elif cid == b"data":
+            body = data[pos + 8: pos + 8 + size]       # an open-ended stream's 0xFFFFFFFF: everything that follows
+        pos += 8 + size + (size & 1)
+    if fmt is None or fmt[0] not in (WAVE_FORMAT_ALAW, WAVE_FORMAT_MULAW):
+        return None
+    tag, ch, rate, _, _, bits = fmt
+    if bits != 8:
+        raise ValueError(f"a G.711 WAV file holds 8-bit samples, this one says {bits}")
+    if ch < 1 or rate <= 0:
+        raise ValueError(f"bad WAV header: {ch} channels at {rate} Hz")
+    frames = len(body or b"") // ch
+    if frames == 0:
+        raise ValueError("the WAV file holds no samples")
+    x = expand(np.frombuffer(body[: frames * ch], dtype=np.uint8), 0 if tag == WAVE_FORMAT_MULAW else 1).astype(np.float64) / 32768.0
+    return x.reshape(frames, ch).mean(axis=1).astype(np.float32), int(rate)
+
+
+def load_wav(data: bytes, *, g711: bool = False):
     """RIFF/WAVE bytes -> (float32 mono samples in [-1, 1), sample rate): the front door of voice cloning from an uploaded clip
     (`Chat.sample_audio_speaker(wav, rate)`, the endpoint's POST /v1/audio/voices).  Integer PCM of 8 (unsigned), 16 or 32 bits, any
     number of channels (averaged to mono), read with the stdlib `wave` module.  Anything else -- a float or compressed WAVE, 24-bit
-    samples, no RIFF at all, no frames -- raises ValueError naming what was found."""
+    samples, no RIFF at all, no frames -- raises ValueError naming what was found.  `g711=True` (keyword-only; the default refuses them
+    like any compressed file): mu-law and A-law files (format tags 7 / 6, 8 bits, any channel count, any rate) -- telephone recordings --
+    are parsed from the RIFF chunks by hand and expanded through `g711.expand`'s tables to int16 / 32768."""
+    if g711:
+        got = _load_g711_wav(bytes(data))
+        if got is not None:
+            return got
     try:
         with wave.open(BytesIO(bytes(data)), "rb") as wf:
             ch, width, rate, n = wf.getnchannels(), wf.getsampwidth(), wf.getframerate(), wf.getnframes()

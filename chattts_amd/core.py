@@ -22,6 +22,7 @@ from typing import Iterator, List, Optional, Union
 import numpy as np
 import torch
 
+from . import g711 as G711
 from . import resample as RS
 from . import weights as W
 from .audio import float_to_int16
@@ -301,25 +302,43 @@ class Chat:
         return self.codec.to_host(wav if sample_rate is None else self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate)))
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
-                        product: str = "f64", *, ragged: bool = False, sample_rate=None) -> List[np.ndarray]:
+                        product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
         Returns one int16 array per utterance, equal to `float_to_int16(wav[np.abs(wav) > 1e-5])` bit for bit (the strip only removes
         samples that are far below one count, so the peak -- hence the scale -- is that of the unstripped row).
         `sample_rate` (None: 24000; with `ragged` also one per row): `wav` above is the waveform resampled on the device directly
-        behind the ISTFT; strip and conversion are the same kernels, fed the resampled samples."""
+        behind the ISTFT; strip and conversion are the same kernels, fed the resampled samples.
+        `encoding` (None: the call above; "ulaw" / "alaw"; with `ragged` also one per row): G.711 companding on the device, strictly
+        behind the conversion (CodecEngine.g711_encode) -- row b comes back as uint8, `g711.encode` of the int16 array above."""
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
         if ragged:
-            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate)
+            if encoding is None:
+                return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate)
+            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding)
+        G711.check_encoding(encoding)
         if len(result_list) == 0:
             return []
         wav = self.codec.decode_to_wavs(result_list) if use_decoder else self.codec.vocos_decode(self.dvae.decode_codes(result_list))
         if sample_rate is not None:
             wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
         pcm, keep = self.codec.float_to_int16(wav, per_row=True, product=product, keep_thr=1e-5 if strip else None)
+        if encoding is not None:       # codes | keep masks in one buffer: one copy
+            B, n = int(pcm.shape[0]), int(pcm.shape[1])
+            nc, kb = (B * n + 15) // 16 * 16, (keep.numel() + 15) // 16 * 16 if strip else 0
+            buf = torch.empty((nc + kb,), dtype=torch.uint8, device=pcm.device)
+            self.codec.g711_encode(pcm.view(-1), [(0, B * n, encoding)], out=buf[:nc])
+            if strip:
+                buf[nc: nc + keep.numel()].copy_(keep.view(-1))
+            host = self.codec.to_host(buf)
+            codes = host[: B * n].reshape(B, n)
+            if not strip:
+                return [codes[b] for b in range(B)]
+            keep_h = host[nc: nc + keep.numel()].reshape(B, -1)
+            return [codes[b][np.unpackbits(keep_h[b])[:n].astype(bool)] for b in range(B)]
         pcm_h = self.codec.to_host(pcm)
         if not strip:
             return [pcm_h[b] for b in range(pcm_h.shape[0])]
@@ -327,13 +346,21 @@ class Chat:
         n = pcm_h.shape[1]
         return [pcm_h[b][np.unpackbits(keep_h[b])[:n].astype(bool)] for b in range(pcm_h.shape[0])]
 
-    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None) -> List[np.ndarray]:
+    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None) -> List[np.ndarray]:
         """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
         PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's result equals
-        `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w."""
+        `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w.  `encoding` (one, or one per row; None entries stay int16): the
+        companded rows are converted by one launch behind the conversion, and the codes travel with the keep masks in the one copy
+        (the PCM16 samples too when some row stays int16)."""
         if len(result_list) == 0:
             return []
         codec = self.codec
+        if encoding is not None:
+            encs = [encoding] * len(result_list) if isinstance(encoding, str) else list(encoding)
+            if len(encs) != len(result_list):
+                raise ValueError("decode_to_pcm16: one encoding per row, or one for all")
+            if any(G711.check_encoding(e) is not None for e in encs):
+                return self._decode_to_g711_ragged(result_list, strip, product, sample_rate, encs)
         wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate)
         n = wav.numel()
         kb = int(keep_offsets(off)[-1]) if strip else 0
@@ -349,14 +376,51 @@ class Chat:
         keep_h = host[2 * n: 2 * n + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
-    def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None) -> List[np.ndarray]:
+    def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs) -> List[np.ndarray]:
+        """`_decode_to_pcm16_ragged` with at least one companded row.  The device buffer is int16 samples | codes | keep masks; rows
+        that share a law and follow each other make one range.  A range starts on a multiple of 8 elements: rows resampled to
+        another rate sit at arbitrary offsets, so a call that mixes laws over such rows goes through the grouped conversion instead
+        (one group per row: the same bytes, slots that start on multiples of 8)."""
+        codec = self.codec
+        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate)
+        runs = []                     # [first row, one past the last, encoding]
+        for i, e in enumerate(encs):
+            if runs and runs[-1][2] == e:
+                runs[-1][1] = i + 1
+            else:
+                runs.append([i, i + 1, e])
+        if any(int(off[a]) % 8 for a, _, e in runs if e is not None):
+            grp = np.arange(len(encs) + 1, dtype=np.int32)
+            blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None, encodings=encs)
+            return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts, encs)]
+        n = wav.numel()
+        kb = int(keep_offsets(off)[-1]) if strip else 0
+        n2, nc = (2 * n + 15) // 16 * 16, (n + 15) // 16 * 16
+        blob = torch.empty((n2 + nc + (kb + 15) // 16 * 16,), dtype=torch.uint8, device=wav.device)
+        pcm_d = blob[: 2 * n].view(torch.int16)
+        keep_d = blob[n2 + nc: n2 + nc + kb] if strip else None
+        _, _, keep_off = codec.float_to_int16_ragged(wav, off, product=product, keep_thr=1e-5 if strip else None, out=(pcm_d, keep_d))
+        codec.g711_encode(pcm_d, [(int(off[a]), int(off[b] - off[a]), e) for a, b, e in runs if e is not None], out=blob[n2: n2 + nc])
+        base = n2 if all(e is not None for e in encs) else 0
+        host = codec.to_host(blob[base:] if base else blob)
+        codes = ragged_views(host[n2 - base: n2 - base + n], off)
+        pieces = codes if base else [c if e is not None else p for c, p, e in zip(codes, ragged_views(host[: 2 * n].view(np.int16), off), encs)]
+        if not strip:
+            return pieces
+        keep_h = host[n2 - base + nc: n2 - base + nc + kb]
+        return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
+
+    def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
         device) and ONE device-to-host copy.  Request g's result equals
         `float_to_int16(np.concatenate([w[np.abs(w) > 1e-5] for w in its sentences' alone decodes]))` bit for bit.
         `sample_rate` (None: 24000; or one per request): every sentence is resampled alone, on the device, behind the ISTFT; the
-        grouped conversion then works on offsets that are no multiples of 8."""
+        grouped conversion then works on offsets that are no multiples of 8.
+        `encoding` (None: the call above; "ulaw" / "alaw"; or one per request, None entries stay int16): the companded requests come
+        back as uint8, `g711.encode` of the int16 array above (CodecEngine.float_to_int16_groups(encodings=): one launch behind the
+        grouped conversion, still one copy)."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -371,13 +435,24 @@ class Chat:
                 raise ValueError("decode_split_to_pcm16: one sample rate per request, or one for all")
             sample_rate = [int(r) for r, g in zip(sample_rate, groups) for _ in g]
         wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate)
+        if encoding is not None:
+            encs = [encoding] * len(groups) if isinstance(encoding, str) else list(encoding)
+            if len(encs) != len(groups):
+                raise ValueError("decode_split_to_pcm16: one encoding per request, or one for all")
+            if any(G711.check_encoding(e) is not None for e in encs):
+                blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None, encodings=encs)
+                return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts, encs)]
         blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None)
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts)]
 
-    def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None) -> List[np.ndarray]:
+    def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
-        (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream)"""
+        (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream).  `encodings`: one per window, None / "ulaw" / "alaw" -- a
+        companded window's piece is uint8, `g711.encode` of the int16 piece"""
+        if encodings is not None:
+            return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, encodings=encodings,
+                                             **({} if sample_rates is None else {"sample_rates": sample_rates}))
         if sample_rates is None:
             return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5)
         return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, sample_rates=sample_rates)
@@ -412,12 +487,27 @@ class Chat:
             yield np.zeros((0,), np.float32) if p is None else p.result()
 
     def _stream_piece(self, hiddens, a: int, b: Optional[int], use_decoder: bool = True, pcm16: bool = False,
-                      rate: Optional[int] = None) -> np.ndarray:
+                      rate: Optional[int] = None, encoding=None) -> np.ndarray:
         """samples [a, b) (b=None: to the end) of the decode of the current prefix (core.py:482-497), from a token window with
         halos instead of the whole prefix (`CodecEngine.decode_window`); `incremental_stream=False` restores the reference's
         full re-decode per yield.  `rate` (None: 24 kHz): [a, b) stay 24 kHz samples and the piece is outputs
         [ceil(a L / M), ceil(b L / M)) of the prefix's decode resampled as one signal -- from the widened window
-        (`decode_window(sample_rate=)`), or, `incremental_stream=False`, sliced out of the whole prefix resampled whole."""
+        (`decode_window(sample_rate=)`), or, `incremental_stream=False`, sliced out of the whole prefix resampled whole.
+        `encoding` ("ulaw" / "alaw", with `pcm16`): the int16 piece companded -- on the device where the conversion ran there, by the
+        host twin where it ran on the host."""
+        if encoding is not None:
+            if not pcm16:
+                raise ValueError("encoding needs pcm16=True")
+            Tn = max(int(r.size(0)) for r in hiddens)
+            hi = 256 * (2 * Tn - 1) if b is None else min(b, 256 * (2 * Tn - 1))
+            if use_decoder and self.incremental_stream and hi > a:
+                win = self.codec.decode_window(hiddens, a, hi) if rate is None else self.codec.decode_window(hiddens, a, hi, sample_rate=rate)
+                if win.shape[1] > 0:
+                    pcm = self.codec.float_to_int16(win, per_row=True)[0]
+                    codes = self.codec.g711_encode(pcm.view(-1), [(0, pcm.numel(), encoding)])
+                    return self.codec.to_host(codes)[: pcm.numel()].reshape(tuple(pcm.shape))
+            piece = self._stream_piece(hiddens, a, b, use_decoder, pcm16, **({} if rate is None else {"rate": rate}))
+            return G711.encode(piece, encoding) if piece.dtype == np.int16 else piece.astype(np.uint8)
         Tn = max(int(r.size(0)) for r in hiddens)
         total = 256 * (2 * Tn - 1) if use_decoder else None
         if not use_decoder or not self.incremental_stream:
@@ -560,7 +650,8 @@ class Chat:
     def infer(self, text, stream=False, lang=None, skip_refine_text=False, refine_text_only=False, use_decoder=True,
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
-              *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False):
+              *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
+              encoding: Optional[str] = None):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -577,7 +668,13 @@ class Chat:
         [ceil(s_lo L / M), ceil(s_hi L / M)), so the chunks tile the resampled stream; the schedule itself (stream_speed,
         pass_first_n_batches, ...) stays in 24 kHz samples; each chunk's 16-bit peak and the tail's silence strip are taken on the
         resampled samples.  No filter state is carried: a chunk is converted from a token window widened by the filter's reach
-        (CodecEngine.decode_window).  A `split_text` stream at another rate raises."""
+        (CodecEngine.decode_window).  A `split_text` stream at another rate raises.
+        `encoding` (keyword-only; None: 16-bit PCM, the call above): "ulaw" / "alaw" -- G.711, one byte per sample, what telephone
+        bridges take (usually with sample_rate=8000).  Needs `pcm16=True` (ValueError otherwise).  Every result is `g711.encode` of the
+        int16 array the same call returns without it, element for element: the companding comes strictly behind the 16-bit conversion
+        and runs on the device wherever that does (CodecEngine.g711_encode)."""
+        if G711.check_encoding(encoding) is not None and not pcm16:
+            raise ValueError("encoding applies to 16-bit output: pass pcm16=True")
         sample_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if stream and sample_rate != CodecEngine.SAMPLE_RATE:
             if not stream_resample:
@@ -603,7 +700,7 @@ class Chat:
         res_gen = self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
-                              sample_rate=rate)
+                              sample_rate=rate, **({} if encoding is None else {"encoding": encoding}))
         if stream:
             return res_gen
         if refine_text_only:
@@ -611,19 +708,21 @@ class Chat:
         if split_dev:
             rows = [h for hids in res_gen for h in hids]
             if rows:
-                return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}))
+                return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}),
+                                                  **({} if encoding is None else {"encoding": encoding}))
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
         thr = np.float32(1e-5)
         stripped = [wav[np.abs(wav) > thr] for wavs in res_gen for wav in wavs]   # sample-level strip, also mid-utterance
         if pcm16:      # split_text: ONE concatenated waveform, hence one peak over all sentences -- converted on the host
-            return [float_to_int16(np.concatenate(stripped))]
+            one = float_to_int16(np.concatenate(stripped))
+            return [one if encoding is None else G711.encode(one, encoding)]
         return [np.concatenate(stripped)] if split_text else stripped
 
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
-               ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None):
+               ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None):
         """core.py:395-503 (generator).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -654,6 +753,8 @@ class Chat:
                 if not stream:
                     src = result.hiddens if use_decoder else result.ids
                     rkw = {} if sample_rate is None else {"sample_rate": sample_rate}      # 24 kHz: today's call, argument for argument
+                    if encoding is not None and pcm16:
+                        rkw["encoding"] = encoding
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
                         rows = [h.clone() for h in src]
                         result.destroy()
@@ -674,6 +775,8 @@ class Chat:
                     continue     # the reference decodes these yields and drops the audio (core.py:482-490)
                 src = result.hiddens if use_decoder else result.ids
                 skw = {"rate": sample_rate} if sample_rate is not None else {}      # 24 kHz: today's call, argument for argument
+                if encoding is not None and pcm16:
+                    skw["encoding"] = encoding
                 piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
                 # that is BELOW `a`: `length` and `pass_batch_count` are not reset between split batches, so the first yields of a
@@ -690,4 +793,6 @@ class Chat:
                 # the last chunk is filtered by columns on the float samples first (core.py:500-503): converted on the host, row by row
                 if pcm16:     # int16 like every other chunk of the stream, also when nothing survives the column filter
                     tail = np.stack([float_to_int16(r) for r in tail]) if tail.shape[1] else tail.astype(np.int16)
+                    if encoding is not None:      # companded by the host twin, like the conversion in front of it
+                        tail = G711.encode(tail, encoding)
                 yield tail

@@ -1567,6 +1567,34 @@ extern "C" int ctts_copy_bytes(void* dst,const void* src, size_t bytes, void* st
   CK(launch_copy16(src, dst, bytes, (hipStream_t)stream));
   return 0;
 }
+static_assert(sizeof(ctts_g711_range) == 32 && sizeof(G711Range) == 32 && offsetof(ctts_g711_range, law) == offsetof(G711Range, law) &&
+              offsetof(ctts_g711_range, n) == offsetof(G711Range, n), "ctts_g711_range layout");
+extern "C" int ctts_g711_encode_ranges(const int16_t* pcm, uint8_t* out, const ctts_g711_range* rng_dev, const ctts_g711_range* rng_host,
+                                       int32_t n_rng, void* stream) {
+  const char* who = "ctts_g711_encode_ranges";
+  if (!pcm || !out || !rng_dev || !rng_host) return fail("%s: a null pointer (pcm, out and both range tables are needed)", who);
+  if (n_rng < 1 || n_rng > 1024) return fail("%s: need 1 <= n_rng <= 1024 (got %d)", who, n_rng);
+  if (((uintptr_t)pcm & 15) || ((uintptr_t)out & 15)) return fail("%s: pcm and out must be 16-byte aligned", who);
+  long long end = 0, n_max = 0;
+  for (int i = 0; i < n_rng; ++i) {
+    const ctts_g711_range& r = rng_host[i];
+    if (r.law < -1 || r.law > 1) return fail("%s: range %d: law %d is none of -1 (skip), 0 (mu-law), 1 (A-law)", who, i, r.law);
+    if (r.start < 0 || (r.start & 7)) return fail("%s: range %d starts at element %lld: starts are multiples of 8", who, i, (long long)r.start);
+    if (r.n < 0) return fail("%s: range %d has a negative length (%lld)", who, i, (long long)r.n);
+    if (r.start >= (1ll << 46) || r.n >= (1ll << 40)) return fail("%s: range %d lies beyond what a launch can address", who, i);
+    if (r.start < end) return fail("%s: range %d starts at element %lld, before the end %lld of the ranges in front of it (overlapping or descending)", who,
+                                   i, (long long)r.start, end);
+    end = r.start + r.n;
+    if (r.law >= 0) n_max = std::max(n_max, (long long)r.n);
+  }
+  const uintptr_t p0 = (uintptr_t)pcm, o0 = (uintptr_t)out;
+  if (p0 == o0 || (p0 < o0 + (uintptr_t)end && o0 < p0 + 2 * (uintptr_t)end))
+    return fail("%s: out aliases pcm (the conversion is not in place)", who);
+  if (n_max == 0) return 0;                      // nothing but skipped or empty ranges
+  CttsDeviceGuard dg(stream);
+  CK(launch_g711_ranges(pcm, out, (const G711Range*)rng_dev, n_rng, n_max, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_k_exp_draws(uint64_t seed, int32_t step, int32_t row0, int32_t rows, int32_t V, float* out, void* stream) {
   if (!out || rows <= 0 || V <= 0) return fail("ctts_k_exp_draws: bad arguments");
   CK(launch_exp_draws(seed, step, row0, rows, V, out, (hipStream_t)stream));

@@ -502,6 +502,18 @@ hipError_t launch_resample_windows(const float* x, const RsWindow* win, float* y
 hipError_t launch_chunks_pcm16(const float* wav, const float* chunks, const CodecWindow* win, const RsWindow* rs, int n_win, int out_f32,
                                int product, float keep_thr, void* out, uint8_t* keep, hipStream_t st);
 
+// ---- G.711 companding (g711.hip) ----------------------------------------------------------------
+#define G711_TILE 4096        // samples per workgroup: 256 threads, 16 consecutive samples each
+// ctts_g711_range (include/chattts_amd.h), field for field (capi.hip asserts the layout): elements [start, start + n) of the int16 input
+// become bytes [start, start + n) of the output under `law` (0 mu, 1 A, < 0: the range is skipped)
+struct G711Range {
+  long long start, n;
+  int32_t law, pad0;
+  long long pad1;
+};
+// n_max: the longest range (grid size)
+hipError_t launch_g711_ranges(const int16_t* pcm, uint8_t* out, const G711Range* rng, int n_rng, long long n_max, hipStream_t st);
+
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------
 // |STFT| of one waveform: center=True reflect padding, frame f = padded[256 f, 256 f + 1024) * window, 1024-point FFT,
 // mag [F][516] (bins 0..512, then 3 zeros so that the mel projection's K is a multiple of 4)

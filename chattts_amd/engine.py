@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import g711 as G711
 from . import resample as RS
 from ._sync import wait_event, wait_stream
 from .config import DVAE, GPT, VOCOS
@@ -1562,16 +1563,26 @@ class CodecEngine:
         off_d.record_stream(st)
         return pcm, keep, keep_off
 
-    def float_to_int16_groups(self, wav: torch.Tensor, off, grp, product: str = "f64", keep_thr: Optional[float] = 1e-5):
+    def float_to_int16_groups(self, wav: torch.Tensor, off, grp, product: str = "f64", keep_thr: Optional[float] = 1e-5, encodings=None):
         """The last step of split_text requests on the device (ctts_float_to_int16_groups): segments grp[g] .. grp[g+1]-1 of a packed
         waveform (`decode_ragged`'s output) are request g's sentences.  ONE peak per group; the group's samples with |x| > keep_thr
         are converted and written contiguously, in order (keep_thr None: nothing is stripped, a plain concatenation under one peak).
         Returns (blob, starts): ONE uint8 device tensor -- a header of the groups' kept counts (int64 [n_grp], padded to 16 bytes), then
         the int16 samples, group g's from element starts[g] = sum_{h<g} ceil8(n_h) on (for a decode: off[grp[g]]) -- so that a single
         copy brings counts and bytes to the host; `unpack_groups(host_blob, starts)` cuts it.  Group g's result equals
-        `audio.float_to_int16(np.concatenate([w[np.abs(w) > keep_thr] for w in its segments]))` bit for bit."""
+        `audio.float_to_int16(np.concatenate([w[np.abs(w) > keep_thr] for w in its segments]))` bit for bit.
+        `encodings` (None, or all None: the call above): one entry per group, None / "ulaw" / "alaw".  A companded group's slot
+        [starts[g], starts[g+1]) is converted whole by ONE ctts_g711_encode_ranges launch behind the conversion (its kept count is
+        known on the device only; the bytes behind it are never handed out).  The device buffer is then int16 samples | count header
+        | companded bytes, and the blob returned is the part the host needs: header | bytes when every group is companded, the whole
+        buffer otherwise -- one copy either way; `unpack_groups(host_blob, starts, encodings)` cuts it."""
         off = np.ascontiguousarray(off, dtype=np.int64)
         grp = np.ascontiguousarray(grp, dtype=np.int32)
+        if encodings is not None:
+            if len(encodings) != len(grp) - 1:
+                raise ValueError("float_to_int16_groups: one encoding per group")
+            if all(G711.check_encoding(e) is None for e in encodings):
+                encodings = None
         assert wav.dim() == 1 and wav.dtype == torch.float32 and wav.is_cuda and wav.is_contiguous() and wav.numel() == int(off[-1])
         n_seg, n_grp = len(off) - 1, len(grp) - 1
         off_p, grp_p = off.ctypes.data_as(C.c_void_p), grp.ctypes.data_as(C.c_void_p)
@@ -1581,23 +1592,42 @@ class CodecEngine:
         starts = group_starts(off, grp)
         hdr = (8 * n_grp + 15) // 16 * 16
         dev = wav.device
-        blob = torch.empty((hdr + 2 * int(starts[-1]),), dtype=torch.uint8, device=dev)
+        E = int(starts[-1])                                                                              # a multiple of 8
+        if encodings is None:
+            blob = torch.empty((hdr + 2 * E,), dtype=torch.uint8, device=dev)
+            cnt_p, pcm_p = blob.data_ptr(), blob.data_ptr() + hdr
+        else:                                                                                           # samples | header | companded bytes
+            blob = torch.empty((2 * E + hdr + (E + 15) // 16 * 16,), dtype=torch.uint8, device=dev)
+            cnt_p, pcm_p = blob.data_ptr() + 2 * E, blob.data_ptr()
         tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), grp.view(np.uint8)])).to(dev)      # one upload: offsets, then groups
         work = torch.empty((4 * n_grp + sb,), dtype=torch.uint8, device=dev)                            # peaks, then the tile counts
         st = torch.cuda.current_stream(dev)
-        _lib.check(self.lib.ctts_float_to_int16_groups(wav.data_ptr(), blob.data_ptr() + hdr, blob.data_ptr(), tabs.data_ptr(), off_p, n_seg,
+        _lib.check(self.lib.ctts_float_to_int16_groups(wav.data_ptr(), pcm_p, cnt_p, tabs.data_ptr(), off_p, n_seg,
                                                        tabs.data_ptr() + off.nbytes, grp_p, n_grp, {"f64": 0, "f32": 1}[product],
                                                        -1.0 if keep_thr is None else float(keep_thr), work.data_ptr(),
                                                        work.data_ptr() + 4 * n_grp, sb, st.cuda_stream), "ctts_float_to_int16_groups")
         tabs.record_stream(st)
         work.record_stream(st)
+        if encodings is not None:
+            self.g711_encode(blob[: 2 * E].view(torch.int16), [(int(starts[g]), int(starts[g + 1] - starts[g]), encodings[g]) for g in range(n_grp)],
+                             out=blob[2 * E + hdr:])
+            if all(e is not None for e in encodings):
+                return blob[2 * E:], starts
         return blob, starts
 
     @staticmethod
-    def unpack_groups(host_blob: np.ndarray, starts) -> List[np.ndarray]:
-        """`float_to_int16_groups`'s blob on the host -> one int16 array per group (views of the blob)"""
+    def unpack_groups(host_blob: np.ndarray, starts, encodings=None) -> List[np.ndarray]:
+        """`float_to_int16_groups`'s blob on the host -> one int16 array per group (views of the blob); with `encodings` (those of the
+        call) a companded group's uint8 codes instead"""
         n_grp = len(starts) - 1
         hdr = (8 * n_grp + 15) // 16 * 16
+        if encodings is not None and any(e is not None for e in encodings):
+            E = int(starts[-1])
+            base = 0 if all(e is not None for e in encodings) else 2 * E       # where the count header sits
+            n_kept = host_blob[base: base + 8 * n_grp].view(np.int64)
+            codes = host_blob[base + hdr:]
+            pcm = host_blob[: 2 * E].view(np.int16) if base else None
+            return [(pcm if e is None else codes)[int(starts[g]): int(starts[g]) + int(n_kept[g])] for g, e in enumerate(encodings)]
         n_kept = host_blob[: 8 * n_grp].view(np.int64)
         pcm = host_blob[hdr:].view(np.int16)
         return [pcm[int(starts[g]): int(starts[g]) + int(n_kept[g])] for g in range(n_grp)]
@@ -1637,7 +1667,7 @@ class CodecEngine:
         return wav[:, c_lo: c_hi]
 
     def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
-                       sample_rates=None):
+                       sample_rates=None, encodings=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -1651,12 +1681,25 @@ class CodecEngine:
         `sample_rates` (None, or all 24000: the call above, argument for argument): one rate per window.  A window at rate r yields
         outputs [ceil(s_lo L / M), ceil(s_hi L / M)) of the resampled decode of its prefix -- `decode_window(.., sample_rate=r)` --
         with the peak, the conversion and a tail's strip taken on the resampled samples (ctts_codec_decode_windows_rate: the same
-        pass, one resampler launch per distinct rate, one conversion launch)."""
+        pass, one resampler launch per distinct rate, one conversion launch).
+        `encodings` (None, or all None: the call above, argument for argument; needs `pcm16`): one entry per window, None / "ulaw" /
+        "alaw".  A companded window comes back as uint8, `g711.encode` of the int16 array it would come back as -- strictly behind the
+        conversion, a tail's strip included (ONE ctts_g711_encode_ranges launch over the windows' own element offsets; the codes and
+        the keep masks sit side by side in the output buffer, so one copy brings both; a call that mixes PCM16 and companded windows
+        copies the PCM16 samples with them, still in one copy)."""
+        laws = None
+        if encodings is not None:
+            if len(encodings) != len(windows):
+                raise ValueError("decode_windows: one encoding per window")
+            if any(G711.check_encoding(e) is not None for e in encodings):
+                if not pcm16:
+                    raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
+                laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
         if sample_rates is not None:
             if len(sample_rates) != len(windows):
                 raise ValueError("decode_windows: one sample rate per window")
             if any(int(r) != self.SAMPLE_RATE for r in sample_rates):
-                return self._decode_windows_rate(store, windows, [int(r) for r in sample_rates], pcm16, keep_thr, product)
+                return self._decode_windows_rate(store, windows, [int(r) for r in sample_rates], pcm16, keep_thr, product, laws)
         assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
         S, cap = int(store.size(0)), int(store.size(1))
         dt = np.int16 if pcm16 else np.float32
@@ -1669,7 +1712,7 @@ class CodecEngine:
                 raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
             win = window_for_samples(Tn, s_lo, VOCOS.hop * (2 * Tn - 1) if s_hi is None else s_hi)
             if win is None:
-                out[i] = np.zeros((0,), dt)
+                out[i] = np.zeros((0,), np.uint8 if laws is not None and laws[i] >= 0 else dt)
                 continue
             rows.append((slot, *win, int(tail), 0, 0))
             live.append(i)
@@ -1682,27 +1725,70 @@ class CodecEngine:
         esz = 2 if pcm16 else 4
         n_out, any_keep = int(off[-1]) * esz, bool(tab[:, 5].any())
         n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if any_keep else 0
+        n_g = (int(off[-1]) + 15) // 16 * 16 if laws is not None else 0
         cur = torch.cuda.current_stream(self.device)
-        buf = torch.empty((n_out + n_keep,), dtype=torch.uint8, device=self.device)      # samples | keep masks: one copy brings both
+        buf = torch.empty((n_out + n_g + n_keep,), dtype=torch.uint8, device=self.device)      # samples | (companded bytes) | keep masks: one copy
         tab_d = torch.from_numpy(tab).to(self.device)
         ws, nws = self._ws_bytes(self.lib.ctts_codec_windows_workspace_bytes(len(live), int((tab[:, 2] - tab[:, 1]).sum())))
         _lib.check(self.lib.ctts_codec_decode_windows(self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap,
                                                       tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(live), 1 if pcm16 else 0,
-                                                      buf.data_ptr(), buf.data_ptr() + n_out if any_keep else None,
+                                                      buf.data_ptr(), buf.data_ptr() + n_out + n_g if any_keep else None,
                                                       {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws,
                                                       cur.cuda_stream), "ctts_codec_decode_windows")
         tab_d.record_stream(cur)
-        host = self.to_host(buf)
-        vals = host[:n_out].view(dt)
+        return self._windows_to_host(buf, n_out, n_g, off, n, tab[:, 5], live, None if laws is None else [laws[i] for i in live], dt, out)
+
+    def _windows_to_host(self, buf: torch.Tensor, n_out: int, n_g: int, off, n, keep, live, laws, dt, out: list) -> list:
+        """the end of `decode_windows`: `buf` = samples (n_out bytes) | companded bytes (n_g, 0 without `laws`) | keep masks.  The
+        companded windows (laws[k] >= 0) are converted by one launch over their own element offsets `off`; ONE copy to the host -- of
+        the codes and the masks when every window is companded, of the whole buffer otherwise -- and live window k becomes out[live[k]]"""
+        base = 0
+        if laws is not None:
+            self.g711_encode(buf[:n_out].view(torch.int16), [(int(off[k]), int(n[k]), laws[k]) for k in range(len(live))],
+                             out=buf[n_out: n_out + n_g])
+            if all(l >= 0 for l in laws):
+                base = n_out
+        host = self.to_host(buf[base:] if base else buf)
+        vals = host[: n_out - base].view(dt) if base == 0 else None
+        codes = host[n_out - base: n_out - base + n_g]
         for k, i in enumerate(live):
-            a = vals[int(off[k]): int(off[k]) + int(n[k])]
-            if tab[k, 5]:
-                kb = n_out + int(off[k]) // 8
+            if laws is not None and laws[k] >= 0:
+                a = codes[int(off[k]): int(off[k]) + int(n[k])]
+            else:
+                a = vals[int(off[k]): int(off[k]) + int(n[k])]
+            if keep[k]:
+                kb = n_out - base + n_g + int(off[k]) // 8
                 a = a[np.unpackbits(host[kb: kb + (int(n[k]) + 7) // 8])[: int(n[k])].astype(bool)]
             out[i] = a
         return out
 
-    def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str):
+    def g711_encode(self, pcm: torch.Tensor, ranges, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """G.711 companding on the device (ctts_g711_encode_ranges, csrc/g711.hip): `pcm`, a contiguous int16 device tensor, taken as
+        flat; `ranges`: up to 1024 (start, n, law) in ascending order -- elements [start, start + n) become BYTES [start, start + n)
+        of the result under law 0 / "ulaw", 1 / "alaw"; -1 / None: the range is skipped.  Starts are multiples of 8.  Returns a flat
+        uint8 device tensor of pcm.numel() bytes (rounded up to 16; `out`: write into this one instead); bytes outside the ranges
+        and those of skipped ranges are left as they were.  One launch whatever the number of ranges; equal to `g711.encode` byte
+        for byte.  The library refuses bad tables before anything is launched (EngineError)."""
+        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()):
+            raise ValueError("g711_encode: a contiguous int16 device tensor")
+        n_el = pcm.numel()
+        if out is None:
+            out = torch.empty(((n_el + 15) // 16 * 16,), dtype=torch.uint8, device=pcm.device)
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n_el):
+            raise ValueError("g711_encode: `out` must be a contiguous uint8 device tensor of at least pcm.numel() bytes")
+        tab = np.zeros(len(ranges), _lib.G711_RANGE)
+        for k, (start, n, law) in enumerate(ranges):
+            tab[k] = (int(start), int(n), -1 if law is None or law == -1 else G711.law_of(law), 0, 0)
+        if len(tab) and int((tab["start"] + np.maximum(tab["n"], 0)).max()) > n_el:
+            raise ValueError(f"g711_encode: a range ends beyond the {n_el} samples")
+        tab_d = torch.from_numpy(tab.view(np.uint8)).to(pcm.device)
+        st = torch.cuda.current_stream(pcm.device)
+        _lib.check(self.lib.ctts_g711_encode_ranges(pcm.data_ptr(), out.data_ptr(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(tab),
+                                                    st.cuda_stream), "ctts_g711_encode_ranges")
+        tab_d.record_stream(st)
+        return out
+
+    def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str, laws=None):
         """`decode_windows` with at least one window at another rate than 24 kHz"""
         assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
         S, cap = int(store.size(0)), int(store.size(1))
@@ -1731,7 +1817,7 @@ class CodecEngine:
                     q = pairs.setdefault(r, (len(pairs), L, M, K))[0]
                     win, rs = window_for_samples(Tn, a, b), (q, a, total, o_lo, o_hi)
             if win is None:
-                out[i] = np.zeros((0,), dt)
+                out[i] = np.zeros((0,), np.uint8 if laws is not None and laws[i] >= 0 else dt)
                 continue
             rows.append((slot, *win, int(tail), 0, 0))
             res.append(rs)
@@ -1759,8 +1845,9 @@ class CodecEngine:
         esz = 2 if pcm16 else 4
         n_out, any_keep = int(off[-1]) * esz, bool(tab[:, 5].any())
         n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if any_keep else 0
+        n_g = (int(off[-1]) + 15) // 16 * 16 if laws is not None else 0
         cur = torch.cuda.current_stream(self.device)
-        buf = torch.empty((n_out + n_keep,), dtype=torch.uint8, device=self.device)      # samples | keep masks: one copy brings both
+        buf = torch.empty((n_out + n_g + n_keep,), dtype=torch.uint8, device=self.device)      # samples | (companded bytes) | keep masks: one copy
         blob = np.concatenate([tab.view(np.uint8).reshape(-1), rtab.view(np.uint8), sel.view(np.uint8)])
         blob_d = torch.from_numpy(blob).to(self.device)                      # one upload: both tables and the selection
         by_q = sorted(pairs.items(), key=lambda kv: kv[1][0])
@@ -1772,18 +1859,10 @@ class CodecEngine:
         _lib.check(self.lib.ctts_codec_decode_windows_rate(
             self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap, base, tab.ctypes.data_as(C.c_void_p),
             base + tab.nbytes, rtab.ctypes.data_as(C.c_void_p), base + tab.nbytes + rtab.nbytes, sel.ctypes.data_as(C.c_void_p), len(live),
-            C.cast(rate_tab, C.c_void_p), len(by_q), 1 if pcm16 else 0, buf.data_ptr(), buf.data_ptr() + n_out if any_keep else None,
+            C.cast(rate_tab, C.c_void_p), len(by_q), 1 if pcm16 else 0, buf.data_ptr(), buf.data_ptr() + n_out + n_g if any_keep else None,
             {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws, cur.cuda_stream), "ctts_codec_decode_windows_rate")
         blob_d.record_stream(cur)
-        host = self.to_host(buf)
-        vals = host[:n_out].view(dt)
-        for k, i in enumerate(live):
-            a = vals[int(off[k]): int(off[k]) + int(n[k])]
-            if tab[k, 5]:
-                kb = n_out + int(off[k]) // 8
-                a = a[np.unpackbits(host[kb: kb + (int(n[k]) + 7) // 8])[: int(n[k])].astype(bool)]
-            out[i] = a
-        return out
+        return self._windows_to_host(buf, n_out, n_g, off, n, tab[:, 5], live, None if laws is None else [laws[i] for i in live], dt, out)
 
     def to_host(self, t: torch.Tensor) -> np.ndarray:
         """device tensor -> numpy, the `.cpu().numpy()` that ends the reference path (core.py:508-510), through a cached PINNED

@@ -32,6 +32,8 @@ from typing import Dict, Optional
 
 import numpy as np
 
+from .audio import g711_to_wav_bytes
+
 try:        # the upload route's parameter type: annotations of this module are resolved against its globals
     from starlette.requests import Request
 except ImportError:      # create_app raises on its own fastapi import
@@ -48,6 +50,13 @@ def wav_stream_header(sample_rate: int = SAMPLE_RATE, bits_per_sample: int = 16,
     return (b"RIFF" + b"\xff\xff\xff\xff" + b"WAVEfmt " + (16).to_bytes(4, "little") + (1).to_bytes(2, "little")
             + channels.to_bytes(2, "little") + sample_rate.to_bytes(4, "little") + byte_rate.to_bytes(4, "little")
             + block_align.to_bytes(2, "little") + bits_per_sample.to_bytes(2, "little") + b"data" + b"\xff\xff\xff\xff")
+
+
+def g711_wav_stream_header(law, sample_rate: int = 8000) -> bytes:
+    """`wav_stream_header` for a G.711 stream: WAVE_FORMAT_MULAW / WAVE_FORMAT_ALAW, mono, 8 bits, an 18-byte `fmt ` chunk and a `fact` chunk, with
+    0xFFFFFFFF in the RIFF, `fact` and `data` lengths (audio.g711_wav_header)"""
+    from .audio import g711_wav_header
+    return g711_wav_header(law, sample_rate, None)
 
 
 def pcm16_to_wav_bytes(pcm: np.ndarray, sample_rate: int = SAMPLE_RATE) -> bytes:
@@ -86,7 +95,7 @@ def _have_av() -> bool:
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
-               stream_sample_rates=None):
+               stream_sample_rates=None, g711: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -114,7 +123,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     different rates still share one decoder pass) and the open-ended WAV header carries the rate.  `voice_upload=True` adds
     `POST /v1/audio/voices?name=NAME[&text=TRANSCRIPT]`, whose body is a WAV file (8/16/32-bit PCM, any rate, any channel count): the clip
     is resampled to 24 kHz on the device and encoded (Chat.sample_audio_speaker(wav, rate)) under the GPU lock, and NAME becomes a cloned
-    voice of this app."""
+    voice of this app.  `g711=True` (default off: every response, status and warning is as without it): telephony output.
+    `response_format` "ulaw" / "alaw" returns raw headerless G.711 bytes, one per sample, like "pcm" (media types audio/PCMU /
+    audio/PCMA); "wav" with a body key `"encoding": "ulaw" | "alaw"` returns a WAVE_FORMAT_MULAW / WAVE_FORMAT_ALAW file (a stream: its
+    open-ended form); another `"encoding"` value gets a 400.  The companding runs on the device behind the 16-bit conversion
+    (Chat.infer(encoding=) / SpeechBatcher.submit(encoding=) / submit_stream(encoding=)); the rate is whatever `sample_rates` /
+    `stream_sample_rates` allow -- 8000 is the telephone's.  With `voice_upload`, mu-law / A-law WAV clips are accepted too
+    (audio.load_wav(g711=True))."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -169,7 +184,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 except StopIteration:
                     return
             yield chunk
-    formats = {"wav", "pcm"} | ({"mp3", "ogg"} if _have_av() else set())
+    formats = {"wav", "pcm"} | ({"mp3", "ogg"} if _have_av() else set()) | ({"ulaw", "alaw"} if g711 else set())
+    if g711:
+        allowed = allowed | {"encoding"}
 
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
         model: str = "tts-1"
@@ -193,8 +210,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     spk_emb=v.get("spk_emb"), spk_smp=v.get("spk_smp"), txt_smp=v.get("txt_smp"), stream_batch=24,
                                     stream_speed=12000, pass_first_n_batches=2)
 
-    def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE):                 # openai_api.py:168-183,207-222
+    def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None):   # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if law is not None:
+            kw = {**kw, "encoding": law}
         if req.stream and rate != SAMPLE_RATE:       # one text: split_text changes nothing but is refused for a stream at another rate
             kw = {**kw, "stream_resample": True, "split_text": False}
         return chat.infer(text=[req.input], stream=bool(req.stream), lang=None, skip_refine_text=True, refine_text_only=False,
@@ -242,9 +261,24 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 log.warning("split_text is served for non-streamed requests only: ignored for a streamed request")
             else:
                 rkw = {**rkw, "split_text": True}
-        media = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "ogg": "audio/ogg"}[fmt]
+        law = None                                   # G.711: the engine hands out uint8 codes
+        if g711:
+            law = fmt if fmt in ("ulaw", "alaw") else None
+            enc = request_data.get("encoding")
+            if enc is not None:
+                if enc not in ("ulaw", "alaw") or (law is not None and enc != law):
+                    raise HTTPException(400, detail=f"Unsupported encoding: {enc}, supported: alaw, ulaw")
+                if fmt not in ("wav", "ulaw", "alaw"):
+                    raise HTTPException(400, detail=f"encoding {enc} goes with response_format wav, ulaw or alaw, not {fmt}")
+                law = enc
+        media = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "ogg": "audio/ogg", "ulaw": "audio/PCMU", "alaw": "audio/PCMA"}[fmt]
+        ekw = {} if law is None else {"encoding": law}
+        stream_header = wav_stream_header if law is None else (lambda r: g711_wav_stream_header(law, r))
 
         def encode(pcm: np.ndarray, header: bool) -> bytes:
+            if law is not None:
+                codes = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype=np.uint8)
+                return g711_to_wav_bytes(codes, law, rate) if (fmt == "wav" and header) else codes.tobytes()
             pcm = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype="<i2")
             if fmt == "wav":
                 return pcm16_to_wav_bytes(pcm, rate) if header else pcm.tobytes()        # pcm.py:84-93
@@ -255,12 +289,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         if req.stream and pool_streams:
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
                 skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
-                chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw)
+                chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw, **ekw)
                 try:
                     first = True
                     async for chunk in iterate_in_threadpool(chunks):
                         if fmt == "wav" and first:
-                            yield wav_stream_header(rate)
+                            yield stream_header(rate)
                         first = False
                         if np.asarray(chunk).size:
                             yield encode(chunk, header=False)
@@ -275,10 +309,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        gen = infer(req, rate)
+                        gen = infer(req, rate) if law is None else infer(req, rate, law)
                         async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
                             if fmt == "wav" and first:
-                                yield wav_stream_header(rate)
+                                yield stream_header(rate)
                             first = False
                             if np.asarray(chunk).size:
                                 yield encode(chunk, header=False)
@@ -290,13 +324,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             try:
                 if rate != SAMPLE_RATE:
                     rkw = {**rkw, "sample_rate": rate}
-                wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw))]
+                wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw, **ekw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:
             async with app.state.model_lock:
                 try:
-                    wavs = await run_in_threadpool(infer, req, rate)
+                    wavs = await run_in_threadpool(infer, req, rate, *(() if law is None else (law,)))
                 except Exception as e:
                     raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         if len(wavs) == 0:
@@ -317,7 +351,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             if not name or name == "default":
                 raise HTTPException(400, detail='a voice needs a name other than "default"')
             try:
-                wav, clip_rate = load_wav(await request.body())
+                wav, clip_rate = load_wav(await request.body(), **({"g711": True} if g711 else {}))
             except ValueError as e:
                 raise HTTPException(400, detail=f"bad WAV upload: {e}")
             async with app.state.model_lock:

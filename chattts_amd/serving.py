@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import g711 as G711
 from . import resample as RS
 from ._sync import wait_event, wait_stream
 from .config import GPT
@@ -725,6 +726,7 @@ class SpeechBatcher:
         self.stream_decode_calls = 0  # window decodes over the due chunks of streamed requests
         self.stream_chunks = 0        # chunks those decodes served (empty chunks included)
         self.stream_resampled_chunks = 0   # those of them at another rate than 24 kHz
+        self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.max_stream_group = 0     # most chunks one window decode served
         self.cancelled = 0            # streams closed by their consumer before the end
         self._streams: dict = {}      # request id -> SpeechStream
@@ -771,7 +773,8 @@ class SpeechBatcher:
         self._thread.start()
 
     # -- public -------------------------------------------------------------------------------------------------------------
-    def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None) -> Future:
+    def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None,
+               encoding=None) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
@@ -780,13 +783,17 @@ class SpeechBatcher:
         pcm16=True, ...)[0]` -- the same tokens per sentence, ONE waveform under one peak (see the class text).  `params` is never
         modified (the serial call writes the speaker prompt into it).  `sample_rate` (None: 24000): the rate of the returned audio, the
         serial call's `sample_rate=`; requests that finish together at different rates are decoded together and resampled in one
-        launch per distinct rate (CodecEngine.resample_segments)."""
+        launch per distinct rate (CodecEngine.resample_segments).  `encoding` (None: int16; "ulaw" / "alaw"): the serial call's
+        `encoding=` -- the Future resolves to the uint8 G.711 codes of that waveform; requests that finish together with different
+        encodings still share the one decode, and one companding launch (ctts_g711_encode_ranges)."""
+        G711.check_encoding(encoding)
         self._check_refine(refine)
         if split_text and int(max_split_batch) < 1:
             raise ValueError("max_split_batch must be positive")
         fut: Future = Future()
         fut.rid = next(self._ids)
         fut.sample_rate = None if sample_rate is None or int(sample_rate) == 24000 else int(sample_rate)
+        fut.encoding = encoding
         self._in.put((fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None))
         return fut
 
@@ -795,13 +802,16 @@ class SpeechBatcher:
         the Future is cancelled.  Nothing happens when it has completed already."""
         self._in.put(_Cancel(fut.rid))
 
-    def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None) -> SpeechStream:
+    def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
         is not served from the pool.  `sample_rate` (None: 24000): the serial call's `sample_rate=` with `stream_resample=True` --
         every chunk is its range of the prefix's decode resampled as one signal; the chunks of streams at different rates that are
-        due at one poll still come from one decoder pass (CodecEngine.decode_windows(sample_rates=))."""
+        due at one poll still come from one decoder pass (CodecEngine.decode_windows(sample_rates=)).  `encoding` (None: int16;
+        "ulaw" / "alaw"): the serial call's `encoding=` -- the chunks are uint8 G.711 codes; the chunks of one poll share the decoder
+        pass and ONE companding launch whatever their encodings (CodecEngine.decode_windows(encodings=))."""
+        G711.check_encoding(encoding)
         if split_text:
             raise ValueError("split_text is served for non-streamed requests only")
         if not self.streams:
@@ -812,6 +822,7 @@ class SpeechBatcher:
             RS.plan(24000, rate, [0, 1])       # an unsupported pair is refused here, not at the first chunk
         h = SpeechStream(self, next(self._ids))
         h.sample_rate = rate
+        h.encoding = encoding
         self._in.put((h.rid, text, params, h, refine))
         return h
 
@@ -843,7 +854,7 @@ class SpeechBatcher:
         return {"slots": self.S, "active": len(getattr(self.pool, "active", {})), "queued": self._in.qsize() + len(getattr(self.pool, "queue", ())),
                 "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed,
                 "ragged_decode": self.ragged_decode, "decode_calls": self.decode_calls, "decoded": self.decoded,
-                "max_decode_group": self.max_decode_group}
+                "max_decode_group": self.max_decode_group, "companded": self.companded}
 
     def close(self):
         self._stop = True
@@ -1039,7 +1050,8 @@ class SpeechBatcher:
                 self._deliver(rid, RuntimeError(_NO_AUDIO))
         try:
             self._count_decode(len(live))
-            results = self.chat.decode_split_to_pcm16([g for _, g in live], **self._rate_kw([rid for rid, _ in live]))
+            results = self.chat.decode_split_to_pcm16([g for _, g in live], **self._rate_kw([rid for rid, _ in live]),
+                                                      **self._enc_kw([rid for rid, _ in live]))
         except Exception as e:         # the decode failed: its requests fail, the worker goes on
             results = [e] * len(live)
         for (rid, _), r in zip(live, results):
@@ -1095,6 +1107,10 @@ class SpeechBatcher:
             rates = [getattr(self._streams[c[0]], "sample_rate", None) for c in live]
             self.stream_resampled_chunks += sum(r is not None for r in rates)
             rkw = {"sample_rates": [24000 if r is None else r for r in rates]} if any(r is not None for r in rates) else {}
+            encs = [getattr(self._streams[c[0]], "encoding", None) for c in live]
+            if any(e is not None for e in encs):
+                rkw = {**rkw, "encodings": encs}
+                self.companded += sum(e is not None for e in encs)
             pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **rkw)     # 24 kHz only: today's call
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for rid in {c[0] for c in live}:
@@ -1136,16 +1152,25 @@ class SpeechBatcher:
             return {}
         return {"sample_rate": [24000 if r is None else r for r in rates]}
 
-    def finish(self, hid: torch.Tensor, sample_rate=None) -> np.ndarray:
+    def _enc_kw(self, rids) -> dict:
+        """the `encoding=` keyword of the decode of the requests `rids` (nothing when none of them is companded: today's call)"""
+        encs = [getattr(self._futs.get(r), "encoding", None) for r in rids]
+        if all(e is None for e in encs):
+            return {}
+        self.companded += sum(e is not None for e in encs)
+        return {"encoding": encs}
+
+    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
             raise RuntimeError("the engine returned no audio (the first token was EOS)")
         self._count_decode(1)
         wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}))[0]
-        return float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
+        pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
+        return pcm if encoding is None else G711.encode(pcm, encoding)      # converted on the host, companded by the host twin
 
-    def finish_group(self, hids: List[torch.Tensor], sample_rates=None) -> list:
+    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
         returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000)"""
         out: list = [RuntimeError("the engine returned no audio (the first token was EOS)") if h.shape[0] == 0 else None for h in hids]
@@ -1153,6 +1178,8 @@ class SpeechBatcher:
         if live:
             self._count_decode(len(live))
             kw = {} if sample_rates is None else {"sample_rate": [int(sample_rates[i]) for i in live]}
+            if encodings is not None and any(encodings[i] is not None for i in live):
+                kw["encoding"] = [encodings[i] for i in live]
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out
@@ -1231,7 +1258,9 @@ class SpeechBatcher:
             group = [(rid, hid) for rid, _, hid in got if rid in self._futs]
             try:
                 rkw = self._rate_kw([rid for rid, _ in group])
-                results = self.finish_group([h for _, h in group], **({"sample_rates": rkw["sample_rate"]} if rkw else {}))
+                ekw = self._enc_kw([rid for rid, _ in group])
+                results = self.finish_group([h for _, h in group], **({"sample_rates": rkw["sample_rate"]} if rkw else {}),
+                                            **({"encodings": ekw["encoding"]} if ekw else {}))
             except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
                 results = [e] * len(group)
             for (rid, _), r in zip(group, results):
@@ -1242,7 +1271,8 @@ class SpeechBatcher:
             return
         try:
             rate = getattr(self._futs.get(rid), "sample_rate", None)
-            pcm = self.finish(hid, **({} if rate is None else {"sample_rate": rate}))
+            ekw = self._enc_kw([rid])
+            pcm = self.finish(hid, **({} if rate is None else {"sample_rate": rate}), **({"encoding": ekw["encoding"][0]} if ekw else {}))
         except Exception as e:
             pcm = e
         self._deliver(rid, pcm)

@@ -463,6 +463,26 @@ int ctts_codec_decode_windows_rate(ctts_codec* c, const float* hid, int64_t slot
                                    const ctts_rate* rates, int32_t n_rates, int32_t out_type, void* out, uint8_t* keep_bits, int32_t product,
                                    float keep_thr, void* workspace, size_t ws_bytes, void* stream);
 
+/* G.711 companding behind the PCM16 conversion: 16-bit PCM -> one byte per sample, mu-law (law 0) or A-law (law 1), the ITU-T G.191 map
+ * (a negative sample is companded from its ones' complement, so G(~x) == G(x) ^ 0x80; chattts_amd/g711.py is the NumPy twin):
+ *   mu: a = min((mag >> 2) + 33, 0x1FFF), seg = 1 + bits(a >> 6), code = ((8 - seg) << 4) | (0xF - ((a >> seg) & 0xF)), | 0x80 when lin >= 0
+ *   A:  ix = mag >> 4; if ix > 15 { e = 1; while ix > 31 { ix >>= 1; e++ }; ix = ix - 16 + (e << 4) }; | 0x80 when lin >= 0; ^ 0x55
+ * Range r: elements [start, start + n) of `pcm` become BYTES [start, start + n) of `out` -- element offsets carry over with item size 1, so
+ * the offset tables of every PCM16 layout (windows, ragged rows, groups) address the companded output too.  Bytes outside every range, and
+ * every byte of a skipped range (law -1), are not written.  One launch (g711_ranges_k) whatever the number of ranges; rng_dev / rng_host:
+ * the same table on the device (read by the kernel) and on the host (grid size and the checks).  Refused on the host table before anything
+ * is launched: a null pointer, n_rng < 1 or > 1024, a start that is negative or no multiple of 8, a negative n, ranges that overlap or
+ * descend, a law outside {-1, 0, 1}, pcm or out not 16-byte aligned, `out` aliasing `pcm`. */
+typedef struct {
+  int64_t start;          /* first element: of the int16 input and of the uint8 output; a multiple of 8 */
+  int64_t n;              /* samples */
+  int32_t law;            /* 0 mu-law, 1 A-law, -1 the range is skipped */
+  int32_t reserved0;
+  int64_t reserved1;
+} ctts_g711_range;        /* 32 bytes */
+int ctts_g711_encode_ranges(const int16_t* pcm, uint8_t* out, const ctts_g711_range* rng_dev, const ctts_g711_range* rng_host, int32_t n_rng,
+                            void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Full DVAE (asset/DVAE.safetensors): audio -> 4 x T codes and codes -> mel through the GFSQ codebook.
  * Replaces `self.dvae(wav, "encode")` of `Chat.sample_audio_speaker` (ChatTTS/core.py:179-180 ->

@@ -2,7 +2,7 @@
 batching (`create_app(..., batch_slots=S)`) and once without, plus the sampling kernel's cost in a per-request pool vs a plain pool.
 Prints one JSON line.  Not a bench.py leg.
 
-    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R] [--sample-rate HZ]]
+    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R] [--sample-rate HZ [--encoding ulaw|alaw]]]
     python tools/serve_load.py --refine [--refine-max-new 64] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
     python tools/serve_load.py --split [--split-sentences 6] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
 
@@ -22,6 +22,9 @@ the time to the first audio byte and the total time, p50 / p95, and audio-s/s; t
 each, off and on alternating: the single-stream time to first byte and its run-to-run spread).  --ragged-decode composes.
 --stream --sample-rate HZ: instead, the pooled streams (`batch_streams` on) at 24 kHz and asking for HZ (`stream_sample_rates`: every chunk
 resampled on the device) in one process, the same figures, and one stream alone on both, alternating.
+--stream --sample-rate HZ --encoding ulaw|alaw: instead, the pooled streams at HZ as 16-bit PCM and at HZ as G.711 (`g711=True`: every chunk
+companded on the device behind the conversion) in one process, the same figures, and one stream alone on both legs, alternating: the
+G.711 leg's first-byte p50 beside the PCM16 leg's, and the PCM16 leg's own run-to-run spread to judge the difference against.
 
 --ragged-decode: also the batched burst with `create_app(..., ragged_decode=True)` (the requests that finish in one poll decoded in one
 ragged pass) -- an A/B against the default batched burst (one decode per request), with both runs' decode-call counts.
@@ -90,20 +93,21 @@ def burst(chat, voices, n, batch_slots, ragged_decode=False, counts=False):
     return out
 
 
-def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app=None, rate=None):
+def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app=None, rate=None, encoding=None):
     """n concurrent streamed requests, driven through the ASGI interface on one event loop (a test client would hand the body over only
     once it is complete): the clock of a request stops at its first body message that carries audio, and at its last message.
-    `rate`: the streams ask for that sample rate (`stream_sample_rates`; None: 24 kHz, the body carries no rate)"""
+    `rate`: the streams ask for that sample rate (`stream_sample_rates`; None: 24 kHz, the body carries no rate).  `encoding`: the streams
+    ask for raw G.711 ("ulaw" / "alaw": `g711=True`, one byte per sample)"""
     import asyncio
     own = app is None
     if own:
         app = server.create_app(chat, voices, batch_slots=slots, ragged_decode=ragged_decode, batch_streams=batch_streams,
-                                **({} if rate is None else {"stream_sample_rates": (int(rate),)}))
+                                **({} if rate is None else {"stream_sample_rates": (int(rate),)}), **({} if encoding is None else {"g711": True}))
     names = sorted(voices)
     more = {} if rate is None else {"sample_rate": int(rate)}
 
     async def one(i, text, out):
-        body = json.dumps({"input": text, "voice": names[i % len(names)], "response_format": "pcm", "stream": True, **more}).encode()
+        body = json.dumps({"input": text, "voice": names[i % len(names)], "response_format": encoding or "pcm", "stream": True, **more}).encode()
         scope = dict(type="http", asgi={"version": "3.0"}, http_version="1.1", method="POST", path="/v1/audio/speech", raw_path=b"/v1/audio/speech",
                      query_string=b"", root_path="", scheme="http", server=("load", 80), client=("load", 1),
                      headers=[(b"content-type", b"application/json"), (b"content-length", str(len(body)).encode())])
@@ -138,12 +142,12 @@ def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app
         app.state.batcher.close()
     first = [o.get("first_s", float("nan")) for o in outs]
     total = [o["total_s"] for o in outs]
-    audio = sum(o.get("bytes", 0) for o in outs) / 2 / (server.SAMPLE_RATE if rate is None else int(rate))
+    audio = sum(o.get("bytes", 0) for o in outs) / (2 if encoding is None else 1) / (server.SAMPLE_RATE if rate is None else int(rate))
     pct = lambda v, q: round(float(np.percentile(v, q)), 4)
     out = dict(failed=sum(o.get("status") != 200 or "first_s" not in o for o in outs), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3),
                audio_s=round(audio, 2), first_byte_p50_s=pct(first, 50), first_byte_p95_s=pct(first, 95), total_p50_s=pct(total, 50),
                total_p95_s=pct(total, 95))
-    for k in ("max_coresident", "stream_decode_calls", "stream_chunks", "max_stream_group", "decode_calls", "stream_resampled_chunks"):
+    for k in ("max_coresident", "stream_decode_calls", "stream_chunks", "max_stream_group", "decode_calls", "stream_resampled_chunks", "companded"):
         if k in pool:
             out[k] = pool[k]
     return out
@@ -162,7 +166,25 @@ def stream_rate_main(chat, voices, a):
                           single_stream_first_byte_s=single)))
 
 
+def stream_encoding_main(chat, voices, a):
+    """--stream --sample-rate R --encoding E: the pooled streams at R Hz as PCM16 and as G.711 in one process, then one stream alone on both"""
+    rate = None if a.sample_rate is None or int(a.sample_rate) == server.SAMPLE_RATE else int(a.sample_rate)
+    base = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode, rate=rate)
+    at = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode, rate=rate, encoding=a.encoding)
+    single = {"pcm16": [], a.encoding: []}
+    for _ in range(a.repeat):
+        for enc in (None, a.encoding):
+            single[enc or "pcm16"].append(stream_burst(chat, voices, 1, a.slots, True, a.ragged_decode, rate=rate, encoding=enc)["first_byte_p50_s"])
+    p50 = {k: round(float(np.percentile(v, 50)), 4) for k, v in single.items()}
+    print(json.dumps(dict(metric="serve_load_stream_encoding", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, sample_rate=rate or 24000,
+                          encoding=a.encoding, pcm16=base, g711=at, single_stream_first_byte_s=single, single_stream_first_byte_p50_s=p50,
+                          single_stream_p50_delta_s=round(p50[a.encoding] - p50["pcm16"], 4),
+                          pcm16_spread_s=round(max(single["pcm16"]) - min(single["pcm16"]), 4))))
+
+
 def stream_main(chat, voices, a):
+    if a.encoding is not None:
+        return stream_encoding_main(chat, voices, a)
     if a.sample_rate is not None and int(a.sample_rate) != server.SAMPLE_RATE:
         return stream_rate_main(chat, voices, a)
     off = stream_burst(chat, voices, a.n, a.slots, False, a.ragged_decode)
@@ -324,6 +346,8 @@ def main():
     ap.add_argument("--ragged-decode", action="store_true", help="A/B: also the batched burst with one ragged decode per poll")
     ap.add_argument("--stream", action="store_true", help="streamed requests: batch_streams off vs on")
     ap.add_argument("--sample-rate", type=int, default=None, help="--stream: the pooled streams at 24 kHz vs at this rate (resampled chunks)")
+    ap.add_argument("--encoding", choices=("ulaw", "alaw"), default=None,
+                    help="--stream: the pooled streams as 16-bit PCM vs as G.711 at --sample-rate (8000: the telephone's)")
     ap.add_argument("--repeat", type=int, default=5, help="--stream: single-stream runs per leg (run-to-run spread)")
     ap.add_argument("--refine", action="store_true", help="two-stage requests: Chat.infer serially vs the two-pool batcher")
     ap.add_argument("--refine-max-new", type=int, default=64, help="--refine: max_new_token of the refine-text pass")
