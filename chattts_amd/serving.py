@@ -90,26 +90,17 @@ def request_params(params=None, infer_text: bool = False, num_code: int = GPT.n_
     `infer_text=True`: `params` is a `RefineTextParams` (or a dict of its fields) -- ONE temperature (the text mode has one sampling row per
     utterance, core.py refine_text_ids), `gen_logits(num_code, ...)`, `plan_from_processors(..., infer_text=True)`: a text pool refuses
     what `Chat.refine_text_ids` refuses (a repetition penalty other than 1 above all)."""
-    if infer_text:
-        get = ((lambda k: params.get(k, _TEXT_PARAM_DEFAULTS[k])) if isinstance(params, dict)
-               else (lambda k: getattr(params, k, _TEXT_PARAM_DEFAULTS[k])))
-        t = get("temperature")
-        temp = tuple(float(x) for x in t) if isinstance(t, (list, tuple)) else (float(t),)
-        if len(temp) != 1:
-            raise ValueError("refine-text mode takes one temperature (a scalar)")
-        warpers, procs = gen_logits(int(num_code), get("top_P"), get("top_K"), get("repetition_penalty"))
-        plan = plan_from_processors((*procs, *warpers), infer_text=True)
-        seed = get("manual_seed")
-        return RequestParams(temp, plan, int(get("min_new_token")), None if seed is None else int(seed), bool(get("ensure_non_empty")), True)
-    get = (lambda k: params.get(k, _PARAM_DEFAULTS[k])) if isinstance(params, dict) else (lambda k: getattr(params, k, _PARAM_DEFAULTS[k]))
+    defaults, n_temp, wrong, codes = ((_TEXT_PARAM_DEFAULTS, 1, "refine-text mode takes one temperature (a scalar)", int(num_code)) if infer_text else
+                                      (_PARAM_DEFAULTS, GPT.n_vq, "temperature must be a scalar or one value per codebook", GPT.n_audio - 1))
+    get = (lambda k: params.get(k, defaults[k])) if isinstance(params, dict) else (lambda k: getattr(params, k, defaults[k]))
     t = get("temperature")
-    temp = tuple(float(x) for x in t) if isinstance(t, (list, tuple)) else (float(t),) * GPT.n_vq   # core.py:558-561
-    if len(temp) != GPT.n_vq:
-        raise ValueError("temperature must be a scalar or one value per codebook")
-    warpers, procs = gen_logits(GPT.n_audio - 1, get("top_P"), get("top_K"), get("repetition_penalty"))
-    plan = plan_from_processors((*procs, *warpers))
+    temp = tuple(float(x) for x in t) if isinstance(t, (list, tuple)) else (float(t),) * n_temp   # core.py:558-561
+    if len(temp) != n_temp:
+        raise ValueError(wrong)
+    warpers, procs = gen_logits(codes, get("top_P"), get("top_K"), get("repetition_penalty"))
+    plan = plan_from_processors((*procs, *warpers), infer_text=bool(infer_text))
     seed = get("manual_seed")
-    return RequestParams(temp, plan, int(get("min_new_token")), None if seed is None else int(seed), bool(get("ensure_non_empty")))
+    return RequestParams(temp, plan, int(get("min_new_token")), None if seed is None else int(seed), bool(get("ensure_non_empty")), bool(infer_text))
 
 
 def sampling_row(p: RequestParams, rng_seed: int = 0, rng_per_step: bool = False) -> _lib.SamplingRow:
@@ -309,6 +300,10 @@ class SlotPool:
         self.dec = self._state(B=slots, T=1, workspace=self.ws, row_map=None, n_active=self.n_active)
         self.st.synchronize()
         _lib.check(self.lib.ctts_gpt_graph_build(self.handle, C.byref(self.dec), self.st.cuda_stream), "ctts_gpt_graph_build")
+        # a poll's target: two pinned blocks (state_blk's size) used in turn, each with the event behind its copy (_snapshot)
+        self._snaps = [(torch.empty((5 * self._Sp,), dtype=torch.uint8).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        self._snap_seq = 0                    # snapshots enqueued so far
+        self._admit_no = 0                    # admissions numbered so far (rng_nonce)
         self._pending: Deque = deque()        # snapshots enqueued, not read yet (launch / poll)
         self._ready: Deque = deque()          # (event behind the result copies, results) of the previous poll
         self.free: List[int] = list(range(slots))
@@ -350,7 +345,7 @@ class SlotPool:
         s.prompt_len = self.prompt_len.data_ptr()
         s.infer_text = int(self.infer_text)
         s.rng_device, s.rng_per_step, s.rng_seed = int(self.device_rng), int(self.rng_per_step), _lib.ptr(self.rng_seed)
-        s.rng_nonce = _lib.ptr(getattr(self, "rng_nonce", None))
+        s.rng_nonce = _lib.ptr(self.rng_nonce)
         if self.per_request:
             s.temperature, s.pow_table = None, None
             s.row_sampling, s.row_base = self.rows.data_ptr(), self.row_base.data_ptr()
@@ -464,8 +459,8 @@ class SlotPool:
             self.finish[sl] = 0
             self.end_idx[sl] = 0
             self.stop_at[sl] = torch.tensor([r.stop_at for r in reqs], dtype=torch.int32, device=dev)
-            if getattr(self, "rng_nonce", None) is not None:   # (per-request pools: every admission; only unseeded rows read it)
-                self._admit_no = getattr(self, "_admit_no", 0) + n
+            if self.rng_nonce is not None:   # (per-request pools: every admission; only unseeded rows read it)
+                self._admit_no += n
                 # globally unique admission numbers (never the constant word of a plain generate() call)
                 self.rng_nonce[sl] = torch.arange(self._admit_no - n + 1, self._admit_no + 1, dtype=torch.int32, device=dev)
                 for i, r in enumerate(reqs):
@@ -475,7 +470,7 @@ class SlotPool:
             pre = self._state(B=n, T=Tg, workspace=ws, row_map=rmap, n_active=None)
             _lib.check(self.lib.ctts_gpt_prefill(self.handle, C.byref(pre), emb.data_ptr(), self.st.cuda_stream), "ctts_gpt_prefill")
             self._keep = (ws, emb, rmap, sl)  # stream-ordered: stay alive until the next poll's sync, no extra sync here
-        since = getattr(self, "_snap_seq", 0)      # snapshots enqueued before this admission still show the previous occupant
+        since = self._snap_seq      # snapshots enqueued before this admission still show the previous occupant
         for s_, r in zip(slots, reqs):
             r.cursor = StreamCursor(r.stream) if r.stream is not None else None
             self.active[s_] = (r, Tg, since)
@@ -484,9 +479,6 @@ class SlotPool:
     # -- main loop --------------------------------------------------------------------------------------------
     def _snapshot(self):
         """stream-ordered shader copy of the finish flags + end_idx into one of two pinned blocks, and the event behind it"""
-        if not hasattr(self, "_snaps"):
-            self._snaps = [(torch.empty((5 * self._Sp,), dtype=torch.uint8).pin_memory(), torch.cuda.Event()) for _ in range(2)]
-            self._snap_seq = 0
         blk, ev = self._snaps[self._snap_seq % 2]
         _lib.check(self.lib.ctts_copy_bytes(blk.data_ptr(), self.state_blk.data_ptr(), blk.numel(), self.st.cuda_stream), "ctts_copy_bytes")
         ev.record(self.st)
@@ -650,12 +642,35 @@ def split_rows(n: int, max_split_batch: int) -> List[Tuple[int, int]]:
 
 
 @dataclass(eq=False)
+class _Job:
+    """one request of a SpeechBatcher, from `submit` / `submit_stream` to its resolution: what travels on the worker's queue and what
+    `SpeechBatcher._jobs` holds while the request is wanted"""
+    rid: object
+    text: str                              # as the endpoint received it
+    params: object                         # its InferCodeParams (never modified)
+    sink: object                           # the caller's end: a Future, or a SpeechStream
+    refine: object = None                  # its RefineTextParams: the refine-text pass runs first
+    max_split_batch: Optional[int] = None  # None unless the request is split_text
+    sample_rate: Optional[int] = None      # None: 24 kHz
+    encoding: Optional[str] = None         # None: int16
+    code_text: Optional[str] = None        # the text of the code stage: normalised, with `refine` then refined
+    in_text_pool: bool = False             # the refine-text pass of an unsplit request is queued or resident
+
+    @property
+    def is_stream(self) -> bool:
+        return isinstance(self.sink, SpeechStream)
+
+    def __getitem__(self, i):
+        """the queue item was a tuple that began (rid, text, params, sink): wrappers of `_take` that index it keep working"""
+        return (self.rid, self.text, self.params, self.sink)[i]
+
+
+@dataclass(eq=False)
 class _SplitReq:
     """one split_text request in flight (SpeechBatcher.submit(split_text=True)).  Its pool requests carry tuple ids: (rid, "r", i) sentence
     i in the text pool, (rid, "A") the refer sentence alone (stage A), (rid, i) sentence i of stage B."""
-    rid: object
+    job: _Job
     params: object                 # the caller's object until stage A ends, then a COPY with spk_smp / txt_smp filled
-    msb: int
     texts: list                    # per sentence: its normalised (refine: refined) text, None while it is in the text pool
     hids: list                     # per sentence: its hidden states, None until stage B delivered them
     need_a: bool
@@ -666,6 +681,18 @@ class _SplitReq:
 
 
 _NO_AUDIO = "the engine returned no audio (the first token was EOS)"
+_NO_TEXT = "the refine-text pass returned no tokens (the first token was EOS)"
+
+
+def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding") -> dict:
+    """the output-format keywords of ONE decode that serves `jobs`, one list entry per job.  Nothing when every job wants 24 kHz int16:
+    the collaborator is then called exactly as it was before it knew rates and encodings (the host fakes pin that)."""
+    kw = {}
+    if any(j.sample_rate is not None for j in jobs):
+        kw[rate_kw] = [24000 if j.sample_rate is None else j.sample_rate for j in jobs]
+    if any(j.encoding is not None for j in jobs):
+        kw[encoding_kw] = [j.encoding for j in jobs]
+    return kw
 
 
 class SpeechBatcher:
@@ -729,10 +756,9 @@ class SpeechBatcher:
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.max_stream_group = 0     # most chunks one window decode served
         self.cancelled = 0            # streams closed by their consumer before the end
-        self._streams: dict = {}      # request id -> SpeechStream
         self.log = logger or logging.getLogger("chattts_amd.serving")
-        self._in: "queue.Queue" = queue.Queue()
-        self._futs: dict = {}
+        self._in: "queue.Queue" = queue.Queue()      # _Job | _Cancel | None (close)
+        self._jobs: dict = {}        # request id -> its _Job, from `_take` until `_resolve`: the requests that are still wanted
         self._ids = itertools.count()
         self.admissions = 0          # requests admitted into the pool
         self.max_coresident = 0      # most requests resident in the pool at once
@@ -752,7 +778,6 @@ class SpeechBatcher:
         self._make_pool = make_pool
         self.refine = bool(refine)
         self.text_pool = None
-        self._stage1: dict = {}          # request id -> its request, while it is in the text pool
         self.refine_admissions = 0       # requests admitted into the text pool
         self.refine_max_coresident = 0   # most requests resident in the text pool at once
         self.handed = 0                  # requests handed from the text pool to the code pool
@@ -792,9 +817,7 @@ class SpeechBatcher:
             raise ValueError("max_split_batch must be positive")
         fut: Future = Future()
         fut.rid = next(self._ids)
-        fut.sample_rate = None if sample_rate is None or int(sample_rate) == 24000 else int(sample_rate)
-        fut.encoding = encoding
-        self._in.put((fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None))
+        self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding))
         return fut
 
     def cancel(self, fut: Future) -> None:
@@ -817,44 +840,37 @@ class SpeechBatcher:
         if not self.streams:
             raise RuntimeError("this SpeechBatcher was built without streams=True")
         self._check_refine(refine)
-        rate = None if sample_rate is None or int(sample_rate) == 24000 else int(sample_rate)
+        rate = self._rate(sample_rate)
         if rate is not None:
             RS.plan(24000, rate, [0, 1])       # an unsupported pair is refused here, not at the first chunk
         h = SpeechStream(self, next(self._ids))
-        h.sample_rate = rate
-        h.encoding = encoding
-        self._in.put((h.rid, text, params, h, refine))
+        self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding))
         return h
 
     def _check_refine(self, refine) -> None:
         if refine is not None and not self.refine:
             raise RuntimeError("this SpeechBatcher was built without refine=True")
 
+    @staticmethod
+    def _rate(sample_rate) -> Optional[int]:
+        return None if sample_rate is None or int(sample_rate) == 24000 else int(sample_rate)
+
     def occupancy(self) -> dict:
+        pool, tp = self.pool, self.text_pool
+        occ = {"slots": self.S, "active": len(getattr(pool, "active", {})), "queued": self._in.qsize() + len(getattr(pool, "queue", ())),
+               "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed,
+               "ragged_decode": self.ragged_decode, "decode_calls": self.decode_calls, "decoded": self.decoded,
+               "max_decode_group": self.max_decode_group, "companded": self.companded,
+               "split": {"requests": self.split_requests, "sentences": self.split_sentences, "max_coresident": self.split_max_coresident}}
+        if self.streams:      # (list(): the worker changes the registry meanwhile)
+            occ.update({"streams": sum(j.is_stream for j in list(self._jobs.values())), "stream_decode_calls": self.stream_decode_calls,
+                        "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled,
+                        "stream_resampled_chunks": self.stream_resampled_chunks})
         if self.refine:
-            tp = self.text_pool
-            return {**self._occupancy_streams(), "refine": {
-                "active": len(getattr(tp, "active", {})), "queued": len(getattr(tp, "queue", ())), "admissions": self.refine_admissions,
-                "max_coresident": self.refine_max_coresident, "steps": int(getattr(tp, "steps", 0)), "handed": self.handed,
-                "both_live_polls": self.both_live_polls}}
-        return self._occupancy_streams()
-
-    def _occupancy_streams(self) -> dict:
-        if self.streams:
-            return {**self._occupancy(), "streams": len(self._streams), "stream_decode_calls": self.stream_decode_calls,
-                    "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled,
-                    "stream_resampled_chunks": self.stream_resampled_chunks}
-        return self._occupancy()
-
-    def _occupancy(self) -> dict:
-        return {**self._occupancy_base(), "split": {"requests": self.split_requests, "sentences": self.split_sentences,
-                                                    "max_coresident": self.split_max_coresident}}
-
-    def _occupancy_base(self) -> dict:
-        return {"slots": self.S, "active": len(getattr(self.pool, "active", {})), "queued": self._in.qsize() + len(getattr(self.pool, "queue", ())),
-                "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed,
-                "ragged_decode": self.ragged_decode, "decode_calls": self.decode_calls, "decoded": self.decoded,
-                "max_decode_group": self.max_decode_group, "companded": self.companded}
+            occ["refine"] = {"active": len(getattr(tp, "active", {})), "queued": len(getattr(tp, "queue", ())),
+                             "admissions": self.refine_admissions, "max_coresident": self.refine_max_coresident,
+                             "steps": int(getattr(tp, "steps", 0)), "handed": self.handed, "both_live_polls": self.both_live_polls}
+        return occ
 
     def close(self):
         self._stop = True
@@ -862,83 +878,92 @@ class SpeechBatcher:
         self._thread.join(timeout=60)
 
     # -- worker -------------------------------------------------------------------------------------------------------------
-    def _fail(self, rid, e: BaseException):
-        self.failed += 1
-        self._stage1.pop(rid, None)
-        sp = self._splits.pop(rid, None)
+    def _resolve(self, job: _Job, result=None, cancelled: bool = False) -> None:
+        """The ONE exit of a request.  `result`: its waveform, or the exception that fails it; a stream: None, its end (its chunks went
+        out already).  `cancelled`: its consumer dropped it.  A request that is not wanted any more (resolved already) is left alone."""
+        sp = self._splits.pop(job.rid, None)
         if sp is not None:
             for k in sp.keys:
                 self._sub.pop(k, None)
-        fut = self._futs.pop(rid, None)
-        if fut is not None and not fut.done():
-            fut.set_exception(e)
-        h = self._streams.pop(rid, None)
-        if h is not None:
-            h._q.put(e)
-
-    def _take(self, item) -> None:
-        """prompt of one request -> pool.submit (worker thread, GPU lock held)"""
-        rid, text, params, fut = item[:4]
-        refine = item[4] if len(item) > 4 else None
-        msb = item[5] if len(item) > 5 else None
-        if isinstance(fut, SpeechStream):
-            self._streams[rid] = fut
+        if self._jobs.pop(job.rid, None) is None:
+            return
+        failed = isinstance(result, BaseException)
+        if cancelled:
+            self.cancelled += job.is_stream
+        elif failed:
+            self.failed += 1
         else:
-            self._futs[rid] = fut
-        if msb is not None:
+            self.completed += 1
+            self.companded += not job.is_stream and job.encoding is not None      # (a stream's chunks are counted as they go out)
+        if job.is_stream:
+            job.sink._q.put(None if cancelled else result)
+        elif cancelled:
+            job.sink.cancel()
+        elif job.sink.done():
+            pass                       # the caller cancelled the Future itself
+        elif failed:
+            job.sink.set_exception(result)
+        else:
+            job.sink.set_result(result)
+
+    def _take(self, job: _Job) -> None:
+        """prompt of one request -> pool.submit (worker thread, GPU lock held)"""
+        self._jobs[job.rid] = job
+        text = job.text
+        if job.max_split_batch is not None:
             try:
                 from .core import split_sentences
                 sents = split_sentences(text)
                 if len(sents) == 0:
                     raise ValueError("split_text: the input holds no sentence")
             except Exception as e:
-                self._fail(rid, e)
+                self._resolve(job, e)
                 return
             if len(sents) > 1:
-                self._take_split(rid, sents, params, refine, msb)
+                self._take_split(job, sents)
                 return
             text = sents[0]               # one sentence: an ordinary request
         try:
-            t = self.chat.normalizer(text, True, True, None)        # what Chat._infer does with do_text_normalization / homophones
-            if refine is not None:       # stage 1: the refine-text pass, in the text pool (Chat._refine_text's prompt)
-                ids, attn, _ = self.chat.refine_prompt([t], refine)
-                self.text_pool.submit(rid, ids[0][attn[0].bool()], max_new_token=refine.max_new_token, params=refine)
-                self._stage1[rid] = (rid, t, params, fut, refine)
+            job.code_text = self.chat.normalizer(text, True, True, None)        # what Chat._infer does with do_text_normalization / homophones
+            if job.refine is not None:       # stage 1: the refine-text pass, in the text pool (Chat._refine_text's prompt)
+                ids, attn, _ = self.chat.refine_prompt([job.code_text], job.refine)
+                self.text_pool.submit(job.rid, ids[0][attn[0].bool()], max_new_token=job.refine.max_new_token, params=job.refine)
+                job.in_text_pool = True
                 self.refine_admissions += 1
                 return
         except Exception as e:        # this request's error, not the worker's
-            self._fail(rid, e)
+            self._resolve(job, e)
             return
-        self._to_code(rid, t, params, fut)
+        self._to_code(job)
 
     def _refined(self, rid, row: torch.Tensor) -> None:
         """a request's text row completed: hand it to the code pool (exactly once), as the text `Chat._infer` would synthesise"""
         if rid in self._sub:
             self._sentence_refined(rid, row)
             return
-        item = self._stage1.pop(rid, None)
-        if item is None or (rid not in self._futs and rid not in self._streams):
+        job = self._jobs.get(rid)
+        if job is None or not job.in_text_pool:
             return                        # cancelled or failed meanwhile
-        _, _, params, fut, _ = item
+        job.in_text_pool = False
         try:
             if row.shape[0] == 0:         # the serial path's refine pass yields nothing there (gpt.py:570)
-                raise RuntimeError("the refine-text pass returned no tokens (the first token was EOS)")
-            t = self.chat.refined_text([row.cpu()])[0]
+                raise RuntimeError(_NO_TEXT)
+            job.code_text = self.chat.refined_text([row.cpu()])[0]
         except Exception as e:
-            self._fail(rid, e)
+            self._resolve(job, e)
             return
         self.handed += 1
-        self._to_code(rid, t, params, fut)
+        self._to_code(job)
 
-    def _to_code(self, rid, t: str, params, fut) -> None:
+    def _to_code(self, job: _Job) -> None:
         """the code-stage prompt of one normalised (or refined) text -> pool.submit"""
-        kw = {}
-        if isinstance(fut, SpeechStream):
-            kw["stream"] = StreamSpec(int(params.stream_batch), int(params.stream_speed), int(params.pass_first_n_batches))
+        kw, p = {}, job.params
+        if job.is_stream:
+            kw["stream"] = StreamSpec(int(p.stream_batch), int(p.stream_speed), int(p.pass_first_n_batches))
         try:
-            self._code_submit(rid, t, params, **kw)
+            self._code_submit(job.rid, job.code_text, p, **kw)
         except Exception as e:        # this request's error, not the worker's
-            self._fail(rid, e)
+            self._resolve(job, e)
 
     def _code_submit(self, key, t: str, params, **kw) -> None:
         chat = self.chat
@@ -950,11 +975,11 @@ class SpeechBatcher:
         self.admissions += 1
 
     # -- split_text requests ------------------------------------------------------------------------------------------------
-    def _take_split(self, rid, sents: list, params, refine, msb: int) -> None:
+    def _take_split(self, job: _Job, sents: list) -> None:
         """a request of several sentences: normalise them like `Chat._infer`, then the text pool (refine) or stage A / B"""
-        n = len(sents)
-        sp = _SplitReq(rid, params, int(msb), [None] * n, [None] * n, need_a=getattr(params, "spk_smp", None) is None)
-        self._splits[rid] = sp
+        n, refine = len(sents), job.refine
+        sp = _SplitReq(job, job.params, [None] * n, [None] * n, need_a=getattr(job.params, "spk_smp", None) is None)
+        self._splits[job.rid] = sp
         self.split_requests += 1
         try:
             ts = [self.chat.normalizer(s_, True, True, None) for s_ in sents]
@@ -964,7 +989,7 @@ class SpeechBatcher:
                 return
             for i, t in enumerate(ts):      # the serial call refines the sentences as ONE batch: row i of n
                 ids, attn, _ = self.chat.refine_prompt([t], refine)
-                key = (rid, "r", i)
+                key = (job.rid, "r", i)
                 self.text_pool.submit(key, ids[0][attn[0].bool()], max_new_token=refine.max_new_token, params=refine, row_offset=i, total_rows=n)
                 self._sub[key] = sp
                 sp.keys.add(key)
@@ -975,13 +1000,14 @@ class SpeechBatcher:
     def _split_advance(self, sp: _SplitReq) -> None:
         """submits what has become possible: stage A once sentence 0's text is there, stage B once every text and the speaker prompt are.
         Raises what the prompt builder or the pool raises (a sentence that does not fit a slot): the caller fails the request."""
+        rid = sp.job.rid
         if sp.need_a and not sp.a_started and sp.texts[0] is not None:
             sp.a_started = True
-            self._split_submit(sp, (sp.rid, "A"), sp.texts[0], 0, GPT.n_vq)      # alone: a batch of one
+            self._split_submit(sp, (rid, "A"), sp.texts[0], 0, GPT.n_vq)      # alone: a batch of one
         if not sp.b_started and (sp.a_done or not sp.need_a) and all(t is not None for t in sp.texts):
             sp.b_started = True
-            for i, ((ro, tr), t) in enumerate(zip(split_rows(len(sp.texts), sp.msb), sp.texts)):
-                self._split_submit(sp, (sp.rid, i), t, ro, tr)
+            for i, ((ro, tr), t) in enumerate(zip(split_rows(len(sp.texts), sp.job.max_split_batch), sp.texts)):
+                self._split_submit(sp, (rid, i), t, ro, tr)
                 self.split_sentences += 1
 
     def _split_submit(self, sp: _SplitReq, key, t: str, row_offset: int, total_rows: int) -> None:
@@ -992,21 +1018,21 @@ class SpeechBatcher:
     def _fail_split(self, sp: _SplitReq, e: BaseException) -> None:
         """fails ONE split request: every sentence of it leaves its pool (queued ones at once, resident ones at the next poll)"""
         self._drop_split(sp)
-        self._fail(sp.rid, e)
+        self._resolve(sp.job, e)
 
     def _drop_split(self, sp: _SplitReq) -> None:
         for k in list(sp.keys):
             self._sub.pop(k, None)
             (self.text_pool if len(k) == 3 else self.pool).cancel(k)
         sp.keys.clear()
-        self._splits.pop(sp.rid, None)
+        self._splits.pop(sp.job.rid, None)
 
     def _sentence_refined(self, key, row: torch.Tensor) -> None:
         sp = self._sub.pop(key)
         sp.keys.discard(key)
         try:
             if row.shape[0] == 0:
-                raise RuntimeError("the refine-text pass returned no tokens (the first token was EOS)")
+                raise RuntimeError(_NO_TEXT)
             sp.texts[key[2]] = self.chat.refined_text([row.cpu()])[0]
             if all(t is not None for t in sp.texts):
                 self.handed += 1
@@ -1040,22 +1066,19 @@ class SpeechBatcher:
         return sp if all(h is not None for h in sp.hids) else None
 
     def _finish_splits(self, ready: list, plain: list = ()) -> None:
-        """ONE decode for the split requests that completed at this poll (+ `plain`: (rid, hid) of the ordinary requests of the same
+        """ONE decode for the split requests that completed at this poll (+ `plain`: (job, hid) of the ordinary requests of the same
         poll, each a group of one sentence): Chat.decode_split_to_pcm16"""
-        for sp in ready:
-            self._splits.pop(sp.rid, None)
-        live = [(rid, [hid]) for rid, hid in plain if hid.shape[0] > 0] + [(sp.rid, sp.hids) for sp in ready]
-        for rid, hid in plain:
+        live = [(job, [hid]) for job, hid in plain if hid.shape[0] > 0] + [(sp.job, sp.hids) for sp in ready]
+        for job, hid in plain:
             if hid.shape[0] == 0:
-                self._deliver(rid, RuntimeError(_NO_AUDIO))
+                self._resolve(job, RuntimeError(_NO_AUDIO))
         try:
             self._count_decode(len(live))
-            results = self.chat.decode_split_to_pcm16([g for _, g in live], **self._rate_kw([rid for rid, _ in live]),
-                                                      **self._enc_kw([rid for rid, _ in live]))
+            results = self.chat.decode_split_to_pcm16([g for _, g in live], **_format_kw([job for job, _ in live]))
         except Exception as e:         # the decode failed: its requests fail, the worker goes on
             results = [e] * len(live)
-        for (rid, _), r in zip(live, results):
-            self._deliver(rid, r)
+        for (job, _), r in zip(live, results):
+            self._resolve(job, r)
 
     def _drain(self, block: bool) -> bool:
         """moves arrived requests into the pool; False once close() was called"""
@@ -1074,62 +1097,38 @@ class SpeechBatcher:
                     self._take(item)
 
     def _cancel(self, rid) -> None:
-        fut = self._futs.pop(rid, None)
-        if fut is not None:           # cancel(future): a non-streamed request, every sentence of a split one
-            sp = self._splits.get(rid)
-            if sp is not None:
-                self._drop_split(sp)
-            elif self._stage1.pop(rid, None) is not None:
-                self.text_pool.cancel(rid)
-            else:
-                self.pool.cancel(rid)
-            fut.cancel()
+        """cancel(future) / SpeechStream.close(): the request leaves whichever pool it is in (every sentence of a split one)"""
+        job = self._jobs.get(rid)
+        if job is None:
             return
-        h = self._streams.pop(rid, None)
-        if h is not None:
-            self.cancelled += 1
-            if self._stage1.pop(rid, None) is not None:
-                self.text_pool.cancel(rid)
-            else:
-                self.pool.cancel(rid)
-            h._q.put(None)
+        sp = self._splits.get(rid)
+        if sp is not None:
+            self._drop_split(sp)
+        else:
+            (self.text_pool if job.in_text_pool else self.pool).cancel(rid)
+        self._resolve(job, cancelled=True)
 
     def _serve_chunks(self, ev: StreamEvents) -> None:
         """the chunks of one poll: ONE window decode, every piece to its own stream's queue"""
-        live = [c for c in ev.chunks if c[0] in self._streams]
+        live = [c for c in ev.chunks if c[0] in self._jobs]
         if not live:
             return
+        jobs = [self._jobs[c[0]] for c in live]
         try:
             if any(c[4] > c[3] for c in live):
                 self.stream_decode_calls += 1
                 self.max_stream_group = max(self.max_stream_group, len(live))
             self.stream_chunks += len(live)
-            rates = [getattr(self._streams[c[0]], "sample_rate", None) for c in live]
-            self.stream_resampled_chunks += sum(r is not None for r in rates)
-            rkw = {"sample_rates": [24000 if r is None else r for r in rates]} if any(r is not None for r in rates) else {}
-            encs = [getattr(self._streams[c[0]], "encoding", None) for c in live]
-            if any(e is not None for e in encs):
-                rkw = {**rkw, "encodings": encs}
-                self.companded += sum(e is not None for e in encs)
-            pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **rkw)     # 24 kHz only: today's call
+            self.stream_resampled_chunks += sum(j.sample_rate is not None for j in jobs)
+            self.companded += sum(j.encoding is not None for j in jobs)
+            pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **_format_kw(jobs, "sample_rates", "encodings"))
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
-            for rid in {c[0] for c in live}:
-                self.pool.cancel(rid)
-                self._fail(rid, e)
+            for job in dict.fromkeys(jobs):
+                self.pool.cancel(job.rid)
+                self._resolve(job, e)
             return
-        for c, pcm in zip(live, pieces):
-            self._streams[c[0]]._q.put(pcm)
-
-    def _end_stream(self, rid, hid) -> None:
-        h = self._streams.pop(rid, None)
-        if h is None:
-            return
-        if hid.shape[0] == 0:
-            self.failed += 1
-            h._q.put(RuntimeError("the engine returned no audio (the first token was EOS)"))
-        else:
-            self.completed += 1
-            h._q.put(None)
+        for job, pcm in zip(jobs, pieces):
+            job.sink._q.put(pcm)
 
     def _between(self):
         self.max_coresident = max(self.max_coresident, len(self.pool.active))
@@ -1145,26 +1144,11 @@ class SpeechBatcher:
         self._drain(block=False)
         self.lock.acquire()
 
-    def _rate_kw(self, rids) -> dict:
-        """the `sample_rate=` keyword of the decode of the requests `rids` (nothing when all of them want 24 kHz: today's call)"""
-        rates = [getattr(self._futs.get(r), "sample_rate", None) for r in rids]
-        if all(r is None for r in rates):
-            return {}
-        return {"sample_rate": [24000 if r is None else r for r in rates]}
-
-    def _enc_kw(self, rids) -> dict:
-        """the `encoding=` keyword of the decode of the requests `rids` (nothing when none of them is companded: today's call)"""
-        encs = [getattr(self._futs.get(r), "encoding", None) for r in rids]
-        if all(e is None for e in encs):
-            return {}
-        self.companded += sum(e is not None for e in encs)
-        return {"encoding": encs}
-
     def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
-            raise RuntimeError("the engine returned no audio (the first token was EOS)")
+            raise RuntimeError(_NO_AUDIO)
         self._count_decode(1)
         wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}))[0]
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
@@ -1173,7 +1157,7 @@ class SpeechBatcher:
     def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
         returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000)"""
-        out: list = [RuntimeError("the engine returned no audio (the first token was EOS)") if h.shape[0] == 0 else None for h in hids]
+        out: list = [RuntimeError(_NO_AUDIO) if h.shape[0] == 0 else None for h in hids]
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
             self._count_decode(len(live))
@@ -1189,16 +1173,18 @@ class SpeechBatcher:
         self.decoded += n
         self.max_decode_group = max(self.max_decode_group, n)
 
-    def _deliver(self, rid, result) -> None:
-        fut = self._futs.pop(rid, None)
-        if fut is None:
-            return
-        if isinstance(result, BaseException):
-            self.failed += 1
-            fut.set_exception(result)
-        else:
-            self.completed += 1
-            fut.set_result(result)
+    def _pools_failed(self, e: BaseException) -> None:
+        """a pool itself failed: the requests in flight fail, fresh pools serve the next ones"""
+        self.log.error("slot pool failed: %s", e)
+        for job in list(self._jobs.values()):
+            self._resolve(job, e)
+        for p in (self.text_pool, self.pool):
+            close = getattr(p, "close", None)
+            if close is not None:
+                close()
+        self.pool = self._make_pool()
+        if self.refine:
+            self.text_pool = self._make_text_pool()
 
     def _loop(self):
         while self._drain(block=True) or self.pool.queue:
@@ -1215,14 +1201,8 @@ class SpeechBatcher:
                         got = next(it)
                     except StopIteration:
                         break
-                    except Exception as e:     # the pool itself failed: the requests in it fail, a fresh pool serves the next ones
-                        self.log.error("slot pool failed: %s", e)
-                        for r in [*self._futs, *self._streams]:
-                            self._fail(r, e)
-                        close = getattr(self.pool, "close", None)
-                        if close is not None:
-                            close()
-                        self.pool = self._make_pool()
+                    except Exception as e:
+                        self._pools_failed(e)
                         break
                     self._handle(got)
             finally:
@@ -1233,49 +1213,38 @@ class SpeechBatcher:
         if isinstance(got, StreamEvents):
             self._serve_chunks(got)
             return
-        if self._sub:                  # sentences of split requests: collected until their request is complete
-            items, ready = [], []
-            for it in (got if self.ragged_decode else [got]):
-                if it[0] in self._sub:
-                    sp = self._sentence_done(it[0], it[2])
-                    if sp is not None:
-                        ready.append(sp)
-                else:
-                    items.append(it)
-            if ready and self.ragged_decode:      # one decode for everything that finished at this poll
-                for rid, _, hid in items:
-                    self._end_stream(rid, hid)
-                self._finish_splits(ready, [(rid, hid) for rid, _, hid in items if rid in self._futs])
-                return
+        ready, plain = [], []          # split requests that became complete; (job, hidden states) of the ordinary finished requests
+        for rid, _, hid in (got if self.ragged_decode else [got]):
+            if rid in self._sub:       # a sentence of a split request: collected until its request is complete
+                sp = self._sentence_done(rid, hid)
+                if sp is not None:
+                    ready.append(sp)
+                continue
+            job = self._jobs.get(rid)
+            if job is None:
+                continue               # cancelled or failed meanwhile
+            if job.is_stream:          # a stream's result: its chunks went out already
+                self._resolve(job, RuntimeError(_NO_AUDIO) if hid.shape[0] == 0 else None)
+            else:
+                plain.append((job, hid))
+        if not self.ragged_decode:     # every request alone
+            for job, hid in plain:
+                try:
+                    pcm = self.finish(hid, **{k: v[0] for k, v in _format_kw([job]).items()})
+                except Exception as e:
+                    pcm = e
+                self._resolve(job, pcm)
             if ready:
                 self._finish_splits(ready)
-            if not items:
-                return
-            got = items if self.ragged_decode else items[0]
-        for rid, _, hid in (got if self.ragged_decode else [got]):     # a stream's result: its chunks went out already
-            self._end_stream(rid, hid)
-        if self.ragged_decode:
-            group = [(rid, hid) for rid, _, hid in got if rid in self._futs]
+        elif ready:                    # one decode for everything that finished at this poll
+            self._finish_splits(ready, plain)
+        elif plain:
             try:
-                rkw = self._rate_kw([rid for rid, _ in group])
-                ekw = self._enc_kw([rid for rid, _ in group])
-                results = self.finish_group([h for _, h in group], **({"sample_rates": rkw["sample_rate"]} if rkw else {}),
-                                            **({"encodings": ekw["encoding"]} if ekw else {}))
+                results = self.finish_group([hid for _, hid in plain], **_format_kw([job for job, _ in plain], "sample_rates", "encodings"))
             except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
-                results = [e] * len(group)
-            for (rid, _), r in zip(group, results):
-                self._deliver(rid, r)
-            return
-        rid, ids, hid = got
-        if rid not in self._futs:
-            return
-        try:
-            rate = getattr(self._futs.get(rid), "sample_rate", None)
-            ekw = self._enc_kw([rid])
-            pcm = self.finish(hid, **({} if rate is None else {"sample_rate": rate}), **({"encoding": ekw["encoding"][0]} if ekw else {}))
-        except Exception as e:
-            pcm = e
-        self._deliver(rid, pcm)
+                results = [e] * len(plain)
+            for (job, _), r in zip(plain, results):
+                self._resolve(job, r)
 
     def _loop2(self):
         """refine=True: ONE worker over the text pool and the code pool.  Every iteration: let other GPU users in and take arrived
@@ -1302,15 +1271,8 @@ class SpeechBatcher:
                         for p in live:
                             for got in p.poll(self.streams and p is self.pool):
                                 self._route(p, got)
-                    except Exception as e:     # a pool itself failed: the requests in flight fail, fresh pools serve the next ones
-                        self.log.error("slot pool failed: %s", e)
-                        for r in [*self._futs, *self._streams]:
-                            self._fail(r, e)
-                        for p in (self.text_pool, self.pool):
-                            close = getattr(p, "close", None)
-                            if close is not None:
-                                close()
-                        self.pool, self.text_pool = self._make_pool(), self._make_text_pool()
+                    except Exception as e:
+                        self._pools_failed(e)
                         break
             finally:
                 self.lock.release()

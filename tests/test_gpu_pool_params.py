@@ -204,7 +204,7 @@ def test_batched_endpoint_matches_the_serial_endpoint(weights):
 
     class Recording(SpeechBatcher):
         def _take(self, item):
-            self.texts[item[0]] = (item[1], item[2].spk_emb)
+            self.texts[item.rid] = (item.text, item.params.spk_emb)
             super()._take(item)
 
     def pcm_of(r):
