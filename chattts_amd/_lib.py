@@ -144,6 +144,7 @@ SIGNATURES = {
     "ctts_float_to_int16_groups": (C.c_int, [P, P, P, P, P, I32, P, P, I32, I32, F, P, P, SZ, P]),
     "ctts_resample_supported": (I32, [I32, I32, I32]),
     "ctts_resample_ragged": (C.c_int, [P, P, P, P, P, P, I32, P, P, I32, P, I32, I32, I32, P]),
+    "ctts_time_scale_ragged": (C.c_int, [P, P, P, P, P, P, P, P, P, I32, P, I32, I32, P]),
     "ctts_codec_windows_workspace_bytes": (SZ, [I32, I32]),
     "ctts_codec_decode_windows": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, I32, P, P, I32, F, P, SZ, P]),
     "ctts_resample_windows": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P, I32, I32, I32, P]),

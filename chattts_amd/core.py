@@ -24,6 +24,7 @@ import torch
 
 from . import g711 as G711
 from . import resample as RS
+from . import timescale as TS
 from . import weights as W
 from .audio import float_to_int16
 from .config import GPT
@@ -64,6 +65,17 @@ class InferCodeParams:            # core.py:195-206 (+ the RefineTextParams fiel
     stream_batch: int = 24
     stream_speed: int = 12000
     pass_first_n_batches: int = 2
+
+
+def _speed_kw(speed) -> dict:
+    """the decode calls' `speed=` argument: nothing for None or 1.0 everywhere (today's call, argument for argument); ValueError for a
+    speed outside 0.5 .. 2.0"""
+    if speed is None:
+        return {}
+    one = [speed] if np.ndim(speed) == 0 else list(speed)
+    if all(TS.quantize(v)[0] == TS.DEN for v in one):
+        return {}
+    return {"speed": float(speed) if np.ndim(speed) == 0 else [float(v) for v in speed]}
 
 
 def split_sentences(text: str) -> List[str]:
@@ -277,13 +289,16 @@ class Chat:
             24, params.manual_seed, self.context, **kw))
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None, *,
-                       ragged: bool = False, sample_rate=None):
+                       ragged: bool = False, sample_rate=None, speed=None):
         """`Chat._decode_to_wavs` (core.py:513-539) -> np.float32 [B, n]: per-row hidden states [T_b,768] through the
         decoder, or (use_decoder=False) per-row token ids [T_b,4] through the full DVAE's codebook; then Vocos.
         `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded).
         `ragged=True` (not the reference's batch semantics): every row decoded as if alone, in one pass (CodecEngine.decode_ragged)
         -> List[np.ndarray], row b's 256 (2 T_b - 1) samples; the decoder path only.
-        `sample_rate` (None: 24000; with `ragged` also one per row): the waveforms are resampled on the device behind the ISTFT."""
+        `sample_rate` (None: 24000; with `ragged` also one per row): the waveforms are resampled on the device behind the ISTFT.
+        `speed` (None: 1.0; with `ragged` also one per row): pitch-preserving time scaling on the device (CodecEngine.time_scale), at
+        24 kHz, behind the ISTFT and in front of the resampler."""
+        skw = _speed_kw(speed)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
@@ -292,17 +307,19 @@ class Chat:
                 raise ValueError("ragged decoding decodes every row at its own length: pad_to does not apply")
             if len(result_list) == 0:
                 return []
-            wav, off = self.codec.decode_ragged(list(result_list), sample_rate=sample_rate)
+            wav, off = self.codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw)
             return ragged_views(self.codec.to_host(wav), off)
         if len(result_list) == 0:
             return np.array([], dtype=np.float32)
         if use_decoder:
-            return self.codec.to_host(self.codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate))
+            return self.codec.to_host(self.codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate, **skw))
         wav = self.codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to))
+        if skw:
+            wav = self.codec.time_scale(wav, skw["speed"])
         return self.codec.to_host(wav if sample_rate is None else self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate)))
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
-                        product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None) -> List[np.ndarray]:
+                        product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
@@ -311,18 +328,23 @@ class Chat:
         `sample_rate` (None: 24000; with `ragged` also one per row): `wav` above is the waveform resampled on the device directly
         behind the ISTFT; strip and conversion are the same kernels, fed the resampled samples.
         `encoding` (None: the call above; "ulaw" / "alaw"; with `ragged` also one per row): G.711 companding on the device, strictly
-        behind the conversion (CodecEngine.g711_encode) -- row b comes back as uint8, `g711.encode` of the int16 array above."""
+        behind the conversion (CodecEngine.g711_encode) -- row b comes back as uint8, `g711.encode` of the int16 array above.
+        `speed` (None: 1.0; with `ragged` also one per row): `wav` above is the waveform time-scaled on the device
+        (CodecEngine.time_scale) at 24 kHz, in front of the resampler; rows at speed 1 are not touched."""
+        skw = _speed_kw(speed)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
         if ragged:
             if encoding is None:
-                return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate)
-            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding)
+                return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, **skw)
+            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding, **skw)
         G711.check_encoding(encoding)
         if len(result_list) == 0:
             return []
         wav = self.codec.decode_to_wavs(result_list) if use_decoder else self.codec.vocos_decode(self.dvae.decode_codes(result_list))
+        if skw:
+            wav = self.codec.time_scale(wav, skw["speed"])
         if sample_rate is not None:
             wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
         pcm, keep = self.codec.float_to_int16(wav, per_row=True, product=product, keep_thr=1e-5 if strip else None)
@@ -346,22 +368,23 @@ class Chat:
         n = pcm_h.shape[1]
         return [pcm_h[b][np.unpackbits(keep_h[b])[:n].astype(bool)] for b in range(pcm_h.shape[0])]
 
-    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None) -> List[np.ndarray]:
+    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None, speed=None) -> List[np.ndarray]:
         """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
         PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's result equals
         `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w.  `encoding` (one, or one per row; None entries stay int16): the
         companded rows are converted by one launch behind the conversion, and the codes travel with the keep masks in the one copy
-        (the PCM16 samples too when some row stays int16)."""
+        (the PCM16 samples too when some row stays int16).  `speed` (one, or one per row) goes to the ragged decode."""
         if len(result_list) == 0:
             return []
         codec = self.codec
+        skw = {} if speed is None else {"speed": speed}
         if encoding is not None:
             encs = [encoding] * len(result_list) if isinstance(encoding, str) else list(encoding)
             if len(encs) != len(result_list):
                 raise ValueError("decode_to_pcm16: one encoding per row, or one for all")
             if any(G711.check_encoding(e) is not None for e in encs):
-                return self._decode_to_g711_ragged(result_list, strip, product, sample_rate, encs)
-        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate)
+                return self._decode_to_g711_ragged(result_list, strip, product, sample_rate, encs, **skw)
+        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw)
         n = wav.numel()
         kb = int(keep_offsets(off)[-1]) if strip else 0
         blob = torch.empty(((2 * n + kb + 15) // 16 * 16,), dtype=torch.uint8, device=wav.device)
@@ -376,13 +399,13 @@ class Chat:
         keep_h = host[2 * n: 2 * n + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
-    def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs) -> List[np.ndarray]:
+    def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs, speed=None) -> List[np.ndarray]:
         """`_decode_to_pcm16_ragged` with at least one companded row.  The device buffer is int16 samples | codes | keep masks; rows
         that share a law and follow each other make one range.  A range starts on a multiple of 8 elements: rows resampled to
         another rate sit at arbitrary offsets, so a call that mixes laws over such rows goes through the grouped conversion instead
         (one group per row: the same bytes, slots that start on multiples of 8)."""
         codec = self.codec
-        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate)
+        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **({} if speed is None else {"speed": speed}))
         runs = []                     # [first row, one past the last, encoding]
         for i, e in enumerate(encs):
             if runs and runs[-1][2] == e:
@@ -410,7 +433,8 @@ class Chat:
         keep_h = host[n2 - base + nc: n2 - base + nc + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
-    def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None) -> List[np.ndarray]:
+    def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None,
+                              speed=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
@@ -420,7 +444,9 @@ class Chat:
         grouped conversion then works on offsets that are no multiples of 8.
         `encoding` (None: the call above; "ulaw" / "alaw"; or one per request, None entries stay int16): the companded requests come
         back as uint8, `g711.encode` of the int16 array above (CodecEngine.float_to_int16_groups(encodings=): one launch behind the
-        grouped conversion, still one copy)."""
+        grouped conversion, still one copy).
+        `speed` (None: 1.0; or one per request): every sentence is time-scaled alone, on the device, at 24 kHz -- in front of the
+        resampler, hence in front of the group's strip and concatenation."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -434,7 +460,12 @@ class Chat:
             if len(sample_rate) != len(groups):
                 raise ValueError("decode_split_to_pcm16: one sample rate per request, or one for all")
             sample_rate = [int(r) for r, g in zip(sample_rate, groups) for _ in g]
-        wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate)
+        skw = _speed_kw(speed)
+        if skw and np.ndim(speed) != 0:
+            if len(speed) != len(groups):
+                raise ValueError("decode_split_to_pcm16: one speed per request, or one for all")
+            skw = {"speed": [float(v) for v, g in zip(speed, groups) for _ in g]}
+        wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate, **skw)
         if encoding is not None:
             encs = [encoding] * len(groups) if isinstance(encoding, str) else list(encoding)
             if len(encs) != len(groups):
@@ -651,7 +682,7 @@ class Chat:
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
-              encoding: Optional[str] = None):
+              encoding: Optional[str] = None, speed: float = 1.0):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -672,9 +703,19 @@ class Chat:
         `encoding` (keyword-only; None: 16-bit PCM, the call above): "ulaw" / "alaw" -- G.711, one byte per sample, what telephone
         bridges take (usually with sample_rate=8000).  Needs `pcm16=True` (ValueError otherwise).  Every result is `g711.encode` of the
         int16 array the same call returns without it, element for element: the companding comes strictly behind the 16-bit conversion
-        and runs on the device wherever that does (CodecEngine.g711_encode)."""
+        and runs on the device wherever that does (CodecEngine.g711_encode).
+        `speed` (keyword-only, non-streamed only; 0.5 .. 2.0, taken in hundredths): the same utterance at the same pitch, `speed` times
+        as fast -- the generator samples exactly what it samples at 1.0, and every decoded waveform is time-scaled on the device at
+        24 kHz (CodecEngine.time_scale: waveform-similarity overlap-add) directly behind the ISTFT, in front of the resampler, the
+        silence strip, the 16-bit conversion and the companding; the sentences of a split request are scaled one by one.  The refer
+        sentence's audio that becomes `spk_smp` of a split request stays at speed 1.  A streamed call at another speed raises: a
+        chunk's frames depend on the path the search took through everything before it, which is not carried across chunks."""
         if G711.check_encoding(encoding) is not None and not pcm16:
             raise ValueError("encoding applies to 16-bit output: pass pcm16=True")
+        skw = _speed_kw(speed)
+        if stream and skw:
+            raise ValueError("speed applies to non-streamed inference only (a chunk's frames depend on the path of everything before it; "
+                             "carrying the path across chunks is not implemented)")
         sample_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if stream and sample_rate != CodecEngine.SAMPLE_RATE:
             if not stream_resample:
@@ -700,7 +741,7 @@ class Chat:
         res_gen = self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
-                              sample_rate=rate, **({} if encoding is None else {"encoding": encoding}))
+                              sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw)
         if stream:
             return res_gen
         if refine_text_only:
@@ -709,7 +750,7 @@ class Chat:
             rows = [h for hids in res_gen for h in hids]
             if rows:
                 return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}),
-                                                  **({} if encoding is None else {"encoding": encoding}))
+                                                  **({} if encoding is None else {"encoding": encoding}), **skw)
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
@@ -722,7 +763,8 @@ class Chat:
 
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
-               ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None):
+               ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
+               speed: Optional[float] = None):
         """core.py:395-503 (generator).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -755,6 +797,8 @@ class Chat:
                     rkw = {} if sample_rate is None else {"sample_rate": sample_rate}      # 24 kHz: today's call, argument for argument
                     if encoding is not None and pcm16:
                         rkw["encoding"] = encoding
+                    if speed is not None:
+                        rkw["speed"] = speed
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
                         rows = [h.clone() for h in src]
                         result.destroy()

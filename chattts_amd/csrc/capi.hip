@@ -1561,6 +1561,35 @@ extern "C" int ctts_resample_ragged(const float* x, const int64_t* off_in_dev, c
                             (hipStream_t)stream));
   return 0;
 }
+extern "C" int ctts_time_scale_ragged(const float* x, const int64_t* off_in_dev, const int64_t* off_in_host, float* y, const int64_t* off_out_dev,
+                                      const int64_t* off_out_host, int32_t* path, const int64_t* path_off_dev, const int64_t* path_off_host,
+                                      int32_t n_seg, const float* window, int32_t num, int32_t den, void* stream) {
+  const char* who = "ctts_time_scale_ragged";
+  if (!x || !y || !path || !window || !off_in_dev || !off_in_host || !off_out_dev || !off_out_host || !path_off_dev || !path_off_host)
+    return fail("%s: a null pointer (x, y, path, the window and the three offset tables on the device and the host are needed)", who);
+  if (n_seg < 1 || n_seg > 65535) return fail("%s: need 1 <= n_seg <= 65535 (got %d)", who, n_seg);
+  if (den != 100 || num < 50 || num > 200) return fail("%s: the speed is num / 100 with 50 <= num <= 200 (got %d/%d)", who, num, den);
+  if (num == den) return fail("%s: speed 1 (%d/%d): there is nothing to scale", who, num, den);
+  if (off_in_host[0] != 0 || off_out_host[0] != 0 || path_off_host[0] != 0) return fail("%s: the first offsets must be 0", who);
+  long long n_out_max = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    const long long n = off_in_host[i + 1] - off_in_host[i], no = off_out_host[i + 1] - off_out_host[i];
+    if (n <= 0) return fail("%s: segment %d is empty or the input offsets do not ascend", who, i);
+    if (no <= 0) return fail("%s: segment %d's output is empty or the output offsets do not ascend", who, i);
+    // a frame reaches up to N + D samples past the end and the path is int32: keep every position below 2^31
+    if (off_in_host[i + 1] >= (1ll << 31) - 4096) return fail("%s: the input holds 2^31 samples or more (less the 4096 a frame may reach past it)", who);
+    if (no != (n * den + num - 1) / num) return fail("%s: segment %d: %lld samples in need ceil(n den / num) out, got %lld", who, i, n, no);
+    if (path_off_host[i + 1] - path_off_host[i] != (no + TS_HS - 1) / TS_HS + 1)
+      return fail("%s: segment %d: %lld samples out are ceil(n_out / %d) + 1 frames of path, got %lld", who, i, no, TS_HS,
+                  (long long)(path_off_host[i + 1] - path_off_host[i]));
+    n_out_max = std::max(n_out_max, no);
+  }
+  if (off_out_host[n_seg] >= (1ll << 31)) return fail("%s: the output holds 2^31 samples or more", who);
+  CttsDeviceGuard dg(stream);
+  CK(launch_time_scale_ragged(x, (const long long*)off_in_dev, y, (const long long*)off_out_dev, path, (const long long*)path_off_dev, n_seg,
+                              n_out_max, window, num, den, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_copy_bytes(void* dst,const void* src, size_t bytes, void* stream) {
   if (!dst || !src || (bytes & 15) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return fail("ctts_copy_bytes: pointers and size must be 16-byte aligned");
   CttsDeviceGuard dg(stream);

@@ -502,6 +502,18 @@ hipError_t launch_resample_windows(const float* x, const RsWindow* win, float* y
 hipError_t launch_chunks_pcm16(const float* wav, const float* chunks, const CodecWindow* win, const RsWindow* rs, int n_win, int out_f32,
                                int product, float keep_thr, void* out, uint8_t* keep, hipStream_t st);
 
+// ---- pitch-preserving time scaling, WSOLA (timescale.hip) ----------------------------------------
+#define TS_N 1024             // window
+#define TS_HS 512             // synthesis hop
+#define TS_D 256              // search radius: candidates -D .. D-1
+#define TS_TILE 1024          // output samples per workgroup of the overlap-add: 256 threads, 4 consecutive samples each
+// packed segments at speed num / den: x[off_in[s], off_in[s+1]) -> y[off_out[s], off_out[s+1]) (ceil(n_s den / num) samples), each as if
+// alone; path[path_off[s] + k] = s_k, the first input sample of frame k (ceil(n_out_s / HS) + 1 frames); window: the float32 [N] periodic
+// Hann table; n_out_max: the longest output (grid size).  Two launches: the search (one workgroup per segment), the overlap-add.
+hipError_t launch_time_scale_ragged(const float* x, const long long* off_in, float* y, const long long* off_out, int32_t* path,
+                                    const long long* path_off, int n_seg, long long n_out_max, const float* window, int num, int den,
+                                    hipStream_t st);
+
 // ---- G.711 companding (g711.hip) ----------------------------------------------------------------
 #define G711_TILE 4096        // samples per workgroup: 256 threads, 16 consecutive samples each
 // ctts_g711_range (include/chattts_amd.h), field for field (capi.hip asserts the layout): elements [start, start + n) of the int16 input

@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from . import g711 as G711
 from . import resample as RS
+from . import timescale as TS
 from ._sync import wait_event, wait_stream
 from .config import DVAE, GPT, VOCOS
 from .rng import ExpDraws, penalty_table
@@ -1489,8 +1490,103 @@ class CodecEngine:
             tab_d.record_stream(st)
         return y[0] if wav.dim() == 1 else y
 
+    # -- pitch-preserving time scaling (csrc/timescale.hip) ----------------------------------------------------------------------------
+    def _time_scale_window(self) -> torch.Tensor:
+        """the float32 [N] periodic Hann table on the device, built once (timescale.window, float64 on the host)"""
+        w = self.__dict__.get("_ts_window")
+        if w is None:
+            w = self._ts_window = torch.from_numpy(np.ascontiguousarray(TS.window(), dtype=np.float32)).to(self.device)
+        return w
+
+    def _time_scale_launch(self, x: torch.Tensor, off: np.ndarray, y: torch.Tensor, path: torch.Tensor, off_out: np.ndarray,
+                           path_off: np.ndarray, num: int, den: int) -> None:
+        """ctts_time_scale_ragged over the pack x / off into y / off_out and path / path_off (views at a run of a larger pack allowed)"""
+        tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), off_out.view(np.uint8), path_off.view(np.uint8)])).to(x.device)   # one upload
+        st = torch.cuda.current_stream(x.device)
+        base = tabs.data_ptr()
+        _lib.check(self.lib.ctts_time_scale_ragged(
+            x.data_ptr(), base, off.ctypes.data_as(C.c_void_p), y.data_ptr(), base + off.nbytes, off_out.ctypes.data_as(C.c_void_p),
+            path.data_ptr(), base + off.nbytes + off_out.nbytes, path_off.ctypes.data_as(C.c_void_p), len(off) - 1,
+            self._time_scale_window().data_ptr(), num, den, st.cuda_stream), "ctts_time_scale_ragged")
+        tabs.record_stream(st)
+
+    def time_scale(self, wav: torch.Tensor, speed: float, offsets=None, return_path: bool = False):
+        """The same audio at the same pitch, `speed` times as fast: waveform-similarity overlap-add at 24 kHz (ctts_time_scale_ragged;
+        the constants and formulas of timescale.py) of a float32 device tensor: 1-D (one signal), [B, n] (rows, each alone ->
+        [B, ceil(n / speed)]), or 1-D packed with `offsets` (n_seg + 1 sample offsets, the ragged decoder's layout; every segment as if
+        alone) -> (tensor, new offsets).  The speed is taken in hundredths; 1.0 returns the input untouched, with no launch.
+        `return_path`: also the frame starts s_k the search chose -- an int32 device tensor ([B, F] for rows; packed, with its offsets,
+        for a pack: (tensor, offsets, path, path offsets)).  ValueError before any launch: a speed outside 0.5 .. 2.0, an empty segment,
+        non-ascending offsets, 2^31 samples."""
+        num, den = TS.quantize(speed)
+        if num == den:
+            if return_path:
+                raise ValueError("time_scale: speed 1 has no path")
+            return wav if offsets is None else (wav, offsets)
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
+            raise ValueError("time_scale: a float32 device tensor, 1-D or [B, n]")
+        if offsets is not None and wav.dim() != 1:
+            raise ValueError("time_scale: offsets go with a packed 1-D tensor")
+        if wav.dim() == 2:
+            B, n = int(wav.shape[0]), int(wav.shape[1])
+            off = np.arange(B + 1, dtype=np.int64) * n
+        else:
+            off = np.ascontiguousarray(offsets, dtype=np.int64) if offsets is not None else np.array([0, wav.numel()], dtype=np.int64)
+        if len(off) < 2:
+            raise ValueError("time_scale: nothing to scale")
+        _, _, off_out, path_off = TS.plan(speed, off)
+        if int(off[-1]) != wav.numel():
+            raise ValueError("time_scale: the offsets do not cover the tensor")
+        x = wav.contiguous()
+        y = torch.empty((int(off_out[-1]),), dtype=torch.float32, device=wav.device)
+        path = torch.empty((int(path_off[-1]),), dtype=torch.int32, device=wav.device)
+        self._time_scale_launch(x.view(-1), off, y, path, off_out, path_off, num, den)
+        if wav.dim() == 2:
+            return (y.view(wav.shape[0], -1), path.view(wav.shape[0], -1)) if return_path else y.view(wav.shape[0], -1)
+        if offsets is not None:
+            return (y, off_out, path, path_off) if return_path else (y, off_out)
+        return (y, path) if return_path else y
+
+    def time_scale_segments(self, wav: torch.Tensor, off, speeds):
+        """packed segments at ONE SPEED EACH (`speeds[i]` for segment i): requests that were decoded together and want different speeds.
+        One call per run of neighbouring segments at one speed, all into one packed output; segments at speed 1 are copied, not
+        processed.  -> (tensor, offsets).  A segment's samples are those of `time_scale` on it alone, bit for bit."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        q = [TS.quantize(v) for v in speeds]
+        if len(q) != len(off) - 1:
+            raise ValueError("time_scale_segments: one speed per segment")
+        if len(set(q)) == 1:
+            return self.time_scale(wav, q[0][0] / q[0][1], off)
+        if wav.dim() != 1 or int(off[-1]) != wav.numel() or off[0] != 0 or np.any(np.diff(off) <= 0):
+            raise ValueError("time_scale_segments: a packed 1-D tensor covered by ascending offsets")
+        runs = []                     # [first segment, one past the last, (num, den)]
+        for i, v in enumerate(q):
+            if runs and runs[-1][2] == v:
+                runs[-1][1] = i + 1
+            else:
+                runs.append([i, i + 1, v])
+        plans = [None if v[0] == v[1] else TS.plan(v[0] / v[1], off[a: b + 1] - off[a]) for a, b, v in runs]   # every refusal, before the first launch
+        lens = np.diff(off).copy()
+        for (a, b, _), p in zip(runs, plans):
+            if p is not None:
+                lens[a:b] = np.diff(p[2])
+        off_out = np.zeros(len(off), np.int64)
+        np.cumsum(lens, out=off_out[1:])
+        if int(off_out[-1]) >= 1 << 31:
+            raise ValueError("time_scale: the pack would hold 2^31 samples or more")
+        x = wav.contiguous()
+        y = torch.empty((int(off_out[-1]),), dtype=torch.float32, device=wav.device)
+        for (a, b, v), p in zip(runs, plans):
+            xi, yi = x[int(off[a]): int(off[b])], y[int(off_out[a]): int(off_out[b])]
+            if p is None:
+                yi.copy_(xi)
+            else:
+                path = torch.empty((int(p[3][-1]),), dtype=torch.int32, device=wav.device)
+                self._time_scale_launch(xi, np.ascontiguousarray(off[a: b + 1] - off[a]), yi, path, p[2], p[3], v[0], v[1])
+        return y, off_out
+
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
-    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None):
+    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None):
         """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
         packed frames (ctts_dvae_decode_ragged / ctts_vocos_decode_ragged): each utterance gets zero padding at its own edges in every
         convolution, so its audio does not depend on what else is in the call -- unlike `decode_to_wavs`, whose zero-padded [B, Tmax]
@@ -1503,9 +1599,24 @@ class CodecEngine:
         split-bf16 tiles alone and is within 2e-5 RMS.
         `sample_rate` (None: 24000): the rate of the returned samples -- one value, or one per row (requests that finish together at
         different rates share the decode).  The waveform is resampled on the device directly behind the ISTFT (`resample_segments`),
-        every row as if alone; `off` then holds the resampled rows' offsets."""
+        every row as if alone; `off` then holds the resampled rows' offsets.
+        `speed` (None: 1.0): pitch-preserving time scaling -- one value, or one per row (`time_scale_segments`: rows at speed 1 are
+        copied through).  It runs at 24 kHz, behind the ISTFT and in front of the resampler, every row as if alone."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
+        if speed is not None:
+            speeds = [float(speed)] * len(rows) if np.ndim(speed) == 0 else [float(v) for v in speed]
+            if len(speeds) != len(rows):
+                raise ValueError("decode_ragged: one speed per row, or one for all")
+            if any(TS.quantize(v)[0] != TS.DEN for v in speeds):
+                out = self.decode_ragged(rows, return_mel)
+                wav, off = self.time_scale_segments(out[0], out[1], speeds)
+                if sample_rate is not None:
+                    rates = [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
+                    if len(rates) != len(rows):
+                        raise ValueError("decode_ragged: one sample rate per row, or one for all")
+                    wav, off = self.resample_segments(wav, off, rates)
+                return (wav, off, out[2]) if return_mel else (wav, off)
         if sample_rate is not None:
             rates = [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
             if len(rates) != len(rows):
@@ -1978,14 +2089,19 @@ class CodecEngine:
             list(pool.map(lambda i: np.copyto(flat_o[i * step: (i + 1) * step], flat_s[i * step: (i + 1) * step]), range(4)))
         return out
 
-    def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None, sample_rate: Optional[int] = None) -> torch.Tensor:
+    def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None, sample_rate: Optional[int] = None,
+                       speed: Optional[float] = None) -> torch.Tensor:
         """`Chat._decode_to_wavs` (core.py:513-539): zero-pad the per-row [T_b,768] hidden lists to the
         longest row, DVAE decode, Vocos decode -> [B, 256(2Tmax-1)] float32 on the device.  `pad_to`: pad to that many tokens instead
         (>= the longest row): a data-parallel shard decodes its rows as part of the GLOBAL batch (dist.infer_sharded) -- the reference
         decodes a shorter row's tail from zero hidden states and returns it.  `sample_rate` (None: 24000): the rows are resampled to
-        that rate on the device, directly behind the ISTFT (`resample`) -> [B, ceil(n * new / 24000)]."""
+        that rate on the device, directly behind the ISTFT (`resample`) -> [B, ceil(n * new / 24000)].  `speed` (None: 1.0): the rows
+        are time-scaled at 24 kHz (`time_scale`), each alone, behind the ISTFT and in front of the resampler."""
         if len(result_list) == 0:
             return torch.empty((0,), dtype=torch.float32)
+        if speed is not None and TS.quantize(speed)[0] != TS.DEN:
+            wav = self.time_scale(self.decode_to_wavs(result_list, pad_to), speed)
+            return wav if sample_rate is None else self.resample(wav, self.SAMPLE_RATE, int(sample_rate))
         if sample_rate is not None and int(sample_rate) != self.SAMPLE_RATE:
             return self.resample(self.decode_to_wavs(result_list, pad_to), self.SAMPLE_RATE, int(sample_rate))
         longest = max(int(r.size(0)) for r in result_list)

@@ -95,7 +95,7 @@ def _have_av() -> bool:
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
-               stream_sample_rates=None, g711: bool = False):
+               stream_sample_rates=None, g711: bool = False, speed: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -129,7 +129,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     open-ended form); another `"encoding"` value gets a 400.  The companding runs on the device behind the 16-bit conversion
     (Chat.infer(encoding=) / SpeechBatcher.submit(encoding=) / submit_stream(encoding=)); the rate is whatever `sample_rates` /
     `stream_sample_rates` allow -- 8000 is the telephone's.  With `voice_upload`, mu-law / A-law WAV clips are accepted too
-    (audio.load_wav(g711=True))."""
+    (audio.load_wav(g711=True)).  `speed=True` (default off: the body's `"speed"` is validated to lie in 0.5 .. 2.0 and then ignored, like
+    the reference does): a non-streamed request is served at its `"speed"` -- the same utterance at the same pitch, time-scaled on the
+    device behind the decode (Chat.infer(speed=) / SpeechBatcher.submit(speed=)); a speed other than 1.0 with `"stream": true` gets a 400."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -210,8 +212,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     spk_emb=v.get("spk_emb"), spk_smp=v.get("spk_smp"), txt_smp=v.get("txt_smp"), stream_batch=24,
                                     stream_speed=12000, pass_first_n_batches=2)
 
-    def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None):   # openai_api.py:168-183,207-222
+    def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None):   # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if spd is not None:
+            kw = {**kw, "speed": spd}
         if law is not None:
             kw = {**kw, "encoding": law}
         if req.stream and rate != SAMPLE_RATE:       # one text: split_text changes nothing but is refused for a stream at another rate
@@ -252,6 +256,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             elif req.stream and rate != SAMPLE_RATE:
                 raise HTTPException(400, detail=f"sample_rate {rate} is served for non-streamed requests only: a stream's chunks are "
                                                 f"produced at {SAMPLE_RATE} Hz (the resampling filter's state is not carried across chunks)")
+        spd = None                                   # the request's speed where it is honoured and is not 1.0
+        if speed and req.speed is not None and int(round(100.0 * req.speed)) != 100:
+            if req.stream:
+                raise HTTPException(400, detail=f"speed {req.speed} is served for non-streamed requests only: a stream's chunks are "
+                                                f"produced at speed 1.0 (the time scaler's path is not carried across chunks)")
+            spd = int(round(100.0 * req.speed)) / 100
         refine = refine_of(request_data)
         rkw = {} if refine is None else {"refine": refine}
         if refine is not None and req.stream and not pool_streams:
@@ -324,13 +334,16 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             try:
                 if rate != SAMPLE_RATE:
                     rkw = {**rkw, "sample_rate": rate}
+                if spd is not None:
+                    rkw = {**rkw, "speed": spd}
                 wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw, **ekw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:
             async with app.state.model_lock:
                 try:
-                    wavs = await run_in_threadpool(infer, req, rate, *(() if law is None else (law,)))
+                    wavs = await run_in_threadpool(infer, req, rate, *(() if law is None and spd is None else (law,)),
+                                                   *(() if spd is None else (spd,)))
                 except Exception as e:
                     raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         if len(wavs) == 0:

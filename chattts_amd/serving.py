@@ -41,6 +41,7 @@ import torch
 from . import _lib
 from . import g711 as G711
 from . import resample as RS
+from . import timescale as TS
 from ._sync import wait_event, wait_stream
 from .config import GPT
 from .engine import GptEngine, gen_logits, plan_from_processors
@@ -655,6 +656,7 @@ class _Job:
     encoding: Optional[str] = None         # None: int16
     code_text: Optional[str] = None        # the text of the code stage: normalised, with `refine` then refined
     in_text_pool: bool = False             # the refine-text pass of an unsplit request is queued or resident
+    speed: Optional[float] = None          # None: 1.0 (never set on a stream)
 
     @property
     def is_stream(self) -> bool:
@@ -684,14 +686,24 @@ _NO_AUDIO = "the engine returned no audio (the first token was EOS)"
 _NO_TEXT = "the refine-text pass returned no tokens (the first token was EOS)"
 
 
-def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding") -> dict:
-    """the output-format keywords of ONE decode that serves `jobs`, one list entry per job.  Nothing when every job wants 24 kHz int16:
-    the collaborator is then called exactly as it was before it knew rates and encodings (the host fakes pin that)."""
+def _job_speed(speed) -> Optional[float]:
+    """a request's speed as its job carries it: in hundredths, None for 1.0; ValueError outside 0.5 .. 2.0"""
+    if speed is None:
+        return None
+    num, den = TS.quantize(speed)
+    return None if num == den else num / den
+
+
+def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding", speed_kw: str = "speed") -> dict:
+    """the output-format keywords of ONE decode that serves `jobs`, one list entry per job.  Nothing when every job wants 24 kHz int16
+    at speed 1: the collaborator is then called exactly as it was before it knew rates, encodings and speeds (the host fakes pin that)."""
     kw = {}
     if any(j.sample_rate is not None for j in jobs):
         kw[rate_kw] = [24000 if j.sample_rate is None else j.sample_rate for j in jobs]
     if any(j.encoding is not None for j in jobs):
         kw[encoding_kw] = [j.encoding for j in jobs]
+    if any(j.speed is not None for j in jobs):
+        kw[speed_kw] = [1.0 if j.speed is None else j.speed for j in jobs]
     return kw
 
 
@@ -799,7 +811,7 @@ class SpeechBatcher:
 
     # -- public -------------------------------------------------------------------------------------------------------------
     def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None,
-               encoding=None) -> Future:
+               encoding=None, speed=None) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
@@ -810,14 +822,18 @@ class SpeechBatcher:
         serial call's `sample_rate=`; requests that finish together at different rates are decoded together and resampled in one
         launch per distinct rate (CodecEngine.resample_segments).  `encoding` (None: int16; "ulaw" / "alaw"): the serial call's
         `encoding=` -- the Future resolves to the uint8 G.711 codes of that waveform; requests that finish together with different
-        encodings still share the one decode, and one companding launch (ctts_g711_encode_ranges)."""
+        encodings still share the one decode, and one companding launch (ctts_g711_encode_ranges).  `speed` (None: 1.0; 0.5 .. 2.0):
+        the serial call's `speed=` -- the same tokens, time-scaled on the device behind the decode; requests that finish together at
+        different speeds still share the one ragged decode (CodecEngine.time_scale_segments: rows at speed 1 are copied through)."""
         G711.check_encoding(encoding)
+        speed = _job_speed(speed)
         self._check_refine(refine)
         if split_text and int(max_split_batch) < 1:
             raise ValueError("max_split_batch must be positive")
         fut: Future = Future()
         fut.rid = next(self._ids)
-        self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding))
+        self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding,
+                          speed=speed))
         return fut
 
     def cancel(self, fut: Future) -> None:
@@ -825,7 +841,8 @@ class SpeechBatcher:
         the Future is cancelled.  Nothing happens when it has completed already."""
         self._in.put(_Cancel(fut.rid))
 
-    def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None) -> SpeechStream:
+    def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None,
+                      speed=None) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
@@ -833,8 +850,11 @@ class SpeechBatcher:
         every chunk is its range of the prefix's decode resampled as one signal; the chunks of streams at different rates that are
         due at one poll still come from one decoder pass (CodecEngine.decode_windows(sample_rates=)).  `encoding` (None: int16;
         "ulaw" / "alaw"): the serial call's `encoding=` -- the chunks are uint8 G.711 codes; the chunks of one poll share the decoder
-        pass and ONE companding launch whatever their encodings (CodecEngine.decode_windows(encodings=))."""
+        pass and ONE companding launch whatever their encodings (CodecEngine.decode_windows(encodings=)).  `speed` other than 1 is
+        refused: a chunk's frames depend on the path of everything before it, which is not carried across chunks."""
         G711.check_encoding(encoding)
+        if _job_speed(speed) is not None:
+            raise ValueError("speed applies to non-streamed requests only (a chunk's frames depend on the path of everything before it)")
         if split_text:
             raise ValueError("split_text is served for non-streamed requests only")
         if not self.streams:
@@ -1144,19 +1164,21 @@ class SpeechBatcher:
         self._drain(block=False)
         self.lock.acquire()
 
-    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None) -> np.ndarray:
+    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
             raise RuntimeError(_NO_AUDIO)
         self._count_decode(1)
-        wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}))[0]
+        wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}),
+                                       **({} if speed is None else {"speed": float(speed)}))[0]
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
         return pcm if encoding is None else G711.encode(pcm, encoding)      # converted on the host, companded by the host twin
 
-    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None) -> list:
+    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
-        returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000)"""
+        returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000);
+        `speeds`: one speed per request (None: 1.0)"""
         out: list = [RuntimeError(_NO_AUDIO) if h.shape[0] == 0 else None for h in hids]
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
@@ -1164,6 +1186,8 @@ class SpeechBatcher:
             kw = {} if sample_rates is None else {"sample_rate": [int(sample_rates[i]) for i in live]}
             if encodings is not None and any(encodings[i] is not None for i in live):
                 kw["encoding"] = [encodings[i] for i in live]
+            if speeds is not None:
+                kw["speed"] = [float(speeds[i]) for i in live]
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out
@@ -1240,7 +1264,7 @@ class SpeechBatcher:
             self._finish_splits(ready, plain)
         elif plain:
             try:
-                results = self.finish_group([hid for _, hid in plain], **_format_kw([job for job, _ in plain], "sample_rates", "encodings"))
+                results = self.finish_group([hid for _, hid in plain], **_format_kw([job for job, _ in plain], "sample_rates", "encodings", "speeds"))
             except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
                 results = [e] * len(plain)
             for (job, _), r in zip(plain, results):

@@ -391,6 +391,24 @@ int ctts_resample_ragged(const float* x, const int64_t* off_in_dev, const int64_
                          const int64_t* off_out_host, int32_t n_seg, const int32_t* sel_dev, const int32_t* sel_host, int32_t n_sel,
                          const float* taps, int32_t L, int32_t M, int32_t K, void* stream);
 
+/* Pitch-preserving time scaling at speed num / den (den = 100, 50 <= num <= 200, num != den) over packed segments: waveform-similarity
+ * overlap-add with window N = 1024, synthesis hop HS = 512 and search radius D = 256, x[off_in[s], off_in[s+1]) -> y[off_out[s], off_out[s+1]),
+ * n_out = ceil(n_s den / num) samples, every segment as if alone (input outside its own samples reads as zero).  Frame k of
+ * F = ceil(n_out / HS) + 1 starts at input sample s_k:  s_0 = -HS;  for k >= 1, a_k = floor(k HS num / den), the template is
+ * t[j] = x[s_{k-1} + HS + j], c(d) = sum_{j<N} t[j] x[a_k - HS + d + j] over d in [-D, D), d_k = the d of the largest c (equal c: the
+ * smallest |d|, then the negative one), s_k = a_k - HS + d_k.  y[(k-1) HS + j] = window[j + HS] x[s_{k-1} + HS + j] + window[j] x[s_k + j],
+ * 0 <= j < HS, each product and the sum rounded to float32.  window: the float32 [N] table 0.5 - 0.5 cos(2 pi j / N) on the device.
+ * path: int32 on the device, s_k of segment s at path[path_off[s] + k] -- written by the search, read by the overlap-add, and what a caller
+ * needs to reproduce the output.  The three offset tables (int64, first 0, strictly ascending) are given on the device and the host (the
+ * two must agree).  The sums run in float32 in a fixed order, so a segment's path and samples do not depend on what it is packed with.
+ * Refused before anything is launched: a null pointer, den != 100, num outside 50 .. 200 or num == den, more than 65535 segments, an
+ * empty segment, non-ascending offsets, an output length other than ceil(n den / num), a path length other than F, 2^31 samples or more
+ * (less the 4096 that a frame may reach past the input: positions are int32).  Stream-ordered: two launches, the search (one workgroup
+ * per segment) and the overlap-add. */
+int ctts_time_scale_ragged(const float* x, const int64_t* off_in_dev, const int64_t* off_in_host, float* y, const int64_t* off_out_dev,
+                           const int64_t* off_out_host, int32_t* path, const int64_t* path_off_dev, const int64_t* path_off_host, int32_t n_seg,
+                           const float* window, int32_t num, int32_t den, void* stream);
+
 /* Window decode: the chunks of many streamed utterances that are due at one poll, in ONE ragged pass, each at its own position.
  * hid: a hidden-state store [n_slots][hid_cap][768] float32 (a slot pool's; slot_stride / row_stride in floats, multiples of 4, rows 16-byte
  * aligned).  A window is token rows [t_lo, t_hi) of one slot; it is decoded as one ragged segment -- its edges are sequence edges -- and

@@ -1,0 +1,107 @@
+"""What the device time scaler costs (csrc/timescale.hip, ctts_time_scale_ragged), beside the decode it follows:
+
+  * launch    : 1, 8 and 64 segments of 10 s (240 000 samples at 24 kHz) at speeds 0.5, 1.25 and 2.0 -- device time of one call (the search
+                and the overlap-add), from events around `--reps` back-to-back calls on pre-uploaded tables, after warm calls; the search
+                walks ceil(n_out / 512) dependent frames per segment, the segments side by side, one workgroup each
+  * decode    : `Chat.decode_to_pcm16(rows, ragged=True)` on 1, 8 and 64 rows of 469 tokens (10 s each) without `speed=` and with it, same
+                rows; wall time including the host side
+
+Synthetic weights, noise input (the kernels' work does not depend on the samples).  Prints one JSON line.  Not a bench.py leg.
+
+    python tools/time_scale_probe.py [--reps 20] [--gemm f16]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from chattts_amd import timescale as TS  # noqa: E402
+from chattts_amd.core import Chat  # noqa: E402
+from chattts_amd.weights import synthetic_all  # noqa: E402
+
+SEG = 240000          # 10 s at 24 kHz
+TOKENS = 469          # 256 (2 T - 1) = 239 872 samples
+
+
+def _launch_ms(codec, n_seg, speed, reps):
+    dev = codec.device
+    off = np.arange(n_seg + 1, dtype=np.int64) * SEG
+    num, den, off_out, path_off = TS.plan(speed, off)
+    x = torch.rand(n_seg * SEG, device=dev) * 2 - 1
+    y = torch.empty(int(off_out[-1]), dtype=torch.float32, device=dev)
+    path = torch.empty(int(path_off[-1]), dtype=torch.int32, device=dev)
+    tabs = [torch.from_numpy(t).to(dev) for t in (off, off_out, path_off)]
+    win = codec._time_scale_window()
+    st = torch.cuda.current_stream(dev).cuda_stream
+
+    def call():
+        rc = codec.lib.ctts_time_scale_ragged(x.data_ptr(), tabs[0].data_ptr(), off.ctypes.data_as(C.c_void_p), y.data_ptr(), tabs[1].data_ptr(),
+                                              off_out.ctypes.data_as(C.c_void_p), path.data_ptr(), tabs[2].data_ptr(),
+                                              path_off.ctypes.data_as(C.c_void_p), n_seg, win.data_ptr(), num, den, st)
+        assert rc == 0
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        call()
+    b.record()
+    b.synchronize()
+    return round(a.elapsed_time(b) / reps, 3), int(path_off[1]) - 1
+
+
+def _wall_ms(fn, reps):
+    fn()
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return round(float(np.median(ts)), 3)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--gemm", default="f16")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("time_scale_probe needs a GPU: nothing here can be timed without one")
+    dev = torch.device("cuda:0")
+    sds = synthetic_all()
+    chat = Chat()
+    assert chat.load(state_dicts={k: sds[k] for k in ("gpt", "embed", "decoder", "vocos")}, device=dev, dtype="f32", codec_gemm=a.gemm)
+    codec = chat.codec
+    out = dict(metric="time_scale_probe", segment_samples=SEG, tokens_per_row=TOKENS, codec_gemm=a.gemm, reps=a.reps, launch_ms={}, frames={},
+               decode_to_pcm16_ms={})
+    for n_seg in (1, 8, 64):
+        for speed in (0.5, 1.25, 2.0):
+            ms, frames = _launch_ms(codec, n_seg, speed, a.reps)
+            out["launch_ms"][f"{n_seg}x@{speed}"] = ms
+            out["frames"][str(speed)] = frames
+    rs = np.random.RandomState(3)
+    for n_rows in (1, 8, 64):
+        rows = [torch.from_numpy(rs.standard_normal((TOKENS, 768)).astype(np.float32) * 0.5).to(dev) for _ in range(n_rows)]
+        r = {"speed_1": _wall_ms(lambda: chat.decode_to_pcm16(rows, ragged=True), max(3, a.reps // 4))}
+        for speed in (0.5, 1.25, 2.0):
+            r[f"speed_{speed}"] = _wall_ms(lambda: chat.decode_to_pcm16(rows, ragged=True, speed=speed), max(3, a.reps // 4))
+        out["decode_to_pcm16_ms"][f"{n_rows}_rows"] = r
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
