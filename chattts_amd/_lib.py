@@ -58,6 +58,12 @@ RS_WINDOW = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("origin", "<i8"), ("t
 G711_RANGE = np.dtype([("start", "<i8"), ("n", "<i8"), ("law", "<i4"), ("pad0", "<i4"), ("pad1", "<i8")])
 
 
+# ctts_ts_stream (80 bytes): in_off, n_in, pos, total, out_off, path_off int64; k_prev, k_now, slot, phase, num, den, n_out, reserved int32
+TS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("out_off", "<i8"), ("path_off", "<i8"),
+                      ("k_prev", "<i4"), ("k_now", "<i4"), ("slot", "<i4"), ("phase", "<i4"), ("num", "<i4"), ("den", "<i4"),
+                      ("n_out", "<i4"), ("reserved", "<i4")])
+
+
 class Rate(C.Structure):
     """ctts_rate: one conversion of ctts_codec_decode_windows_rate"""
     _fields_ = [("taps", P), ("L", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("reserved", C.c_int32)]
@@ -145,12 +151,16 @@ SIGNATURES = {
     "ctts_resample_supported": (I32, [I32, I32, I32]),
     "ctts_resample_ragged": (C.c_int, [P, P, P, P, P, P, I32, P, P, I32, P, I32, I32, I32, P]),
     "ctts_time_scale_ragged": (C.c_int, [P, P, P, P, P, P, P, P, P, I32, P, I32, I32, P]),
+    "ctts_time_scale_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, C.c_int64, P, P, I32, P, P]),
     "ctts_codec_windows_workspace_bytes": (SZ, [I32, I32]),
     "ctts_codec_decode_windows": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, I32, P, P, I32, F, P, SZ, P]),
     "ctts_resample_windows": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P, I32, I32, I32, P]),
     "ctts_codec_windows_rate_workspace_bytes": (SZ, [I32, I32, C.c_int64]),
     "ctts_codec_decode_windows_rate": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, P, P, P, P, I32, P, I32, I32, P, P, I32, F, P,
                                                  SZ, P]),
+    "ctts_codec_windows_speed_workspace_bytes": (SZ, [I32, I32, C.c_int64]),
+    "ctts_codec_decode_windows_speed": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, P, P, P, P, I32, P, P, P, I32, P, P, I32, P,
+                                                  I32, P, P, I32, F, P, SZ, P]),
     "ctts_g711_encode_ranges": (C.c_int, [P, P, P, P, I32, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),
     "ctts_dvae_destroy": (None, [P]),

@@ -476,11 +476,18 @@ class Chat:
         blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None)
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts)]
 
-    def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None) -> List[np.ndarray]:
+    def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
         (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream).  `encodings`: one per window, None / "ulaw" / "alaw" -- a
-        companded window's piece is uint8, `g711.encode` of the int16 piece"""
+        companded window's piece is uint8, `g711.encode` of the int16 piece.  `speeds` with `ts_streams` (one entry per window; a
+        speed other than 1 with the handle of its stream of the time scaler): the window's samples are pushed into that stream and
+        the piece is what the step emits, converted (CodecEngine.decode_windows(speeds=)); without them today's call, argument for
+        argument"""
+        if speeds is not None:
+            return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, speeds=speeds, ts_streams=ts_streams,
+                                             **({} if encodings is None else {"encodings": encodings}),
+                                             **({} if sample_rates is None else {"sample_rates": sample_rates}))
         if encodings is not None:
             return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, encodings=encodings,
                                              **({} if sample_rates is None else {"sample_rates": sample_rates}))
@@ -558,6 +565,35 @@ class Chat:
         if pcm16 and win.shape[1] > 0:     # every row by its own peak -- float_to_int16(chunk[b]), examples/web/funcs.py:203-206 -- on the device
             return self.codec.to_host(self.codec.float_to_int16(win, per_row=True)[0])
         return self.codec.to_host(win)
+
+    def _stream_piece_scaled(self, hiddens, a: int, b: Optional[int], handles, final: bool, pcm16: bool = False, encoding=None) -> np.ndarray:
+        """`_stream_piece` at another speed: samples [a, b) of the decode of the current prefix are PUSHED into the rows' streams of the
+        time scaler (`handles`, one per row; CodecEngine.time_scale_stream_step, all rows in one launch) and the piece is what the step
+        emits -- [B, 512 k] samples, possibly none; every row has had the same number of samples, so the chunk stays rectangular.
+        `final`: the last push (the stream's tail); it comes back as float32 whatever `pcm16` says: the caller filters its columns
+        first.  Otherwise `pcm16` converts every row under its own peak on the device, `encoding` compands behind that."""
+        codec = self.codec
+        Tn = max(int(r.size(0)) for r in hiddens)
+        total = max(0, 256 * (2 * Tn - 1))
+        hi = total if b is None else min(b, total)
+        B, m = len(hiddens), max(0, hi - a)
+        if m > 0 and self.incremental_stream:
+            x = codec.decode_window(hiddens, a, hi).contiguous().view(-1)
+        elif m > 0:
+            x = torch.from_numpy(np.ascontiguousarray(self.decode_to_wavs(hiddens)[:, a: hi], dtype=np.float32)).to(self.device).view(-1)
+        else:
+            x = torch.empty((0,), dtype=torch.float32, device=self.device)
+        y, off = codec.time_scale_stream_step(x, [(h, i * m, m, final) for i, h in enumerate(handles)])
+        y = y.view(B, int(off[1]))
+        if final or not pcm16:
+            return codec.to_host(y)
+        if y.shape[1] == 0:
+            return np.zeros((B, 0), np.int16 if encoding is None else np.uint8)
+        pcm = codec.float_to_int16(y, per_row=True)[0]
+        if encoding is None:
+            return codec.to_host(pcm)
+        codes = codec.g711_encode(pcm.view(-1), [(0, pcm.numel(), encoding)])
+        return codec.to_host(codes)[: pcm.numel()].reshape(tuple(pcm.shape))
 
     def infer_ids_stream(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), *,
                          sample_rate: Optional[int] = None, **kw):
@@ -682,7 +718,7 @@ class Chat:
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
-              encoding: Optional[str] = None, speed: float = 1.0):
+              encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -709,14 +745,32 @@ class Chat:
         24 kHz (CodecEngine.time_scale: waveform-similarity overlap-add) directly behind the ISTFT, in front of the resampler, the
         silence strip, the 16-bit conversion and the companding; the sentences of a split request are scaled one by one.  The refer
         sentence's audio that becomes `spk_smp` of a split request stays at speed 1.  A streamed call at another speed raises: a
-        chunk's frames depend on the path the search took through everything before it, which is not carried across chunks."""
+        chunk's frames depend on the path the search took through everything before it, which is not carried across chunks --
+        unless `stream_time_scale=True` (keyword-only): then every row of the batch gets a stream of the time scaler
+        (CodecEngine.time_scale_stream_step: the path's last entry and a short tail of samples are carried on the device), the
+        24 kHz chunks of the unchanged schedule are pushed into it and each yield hands out what its push made final: the chunks,
+        concatenated, are `time_scale` of the speed-1 stream with its tail not yet stripped; each chunk's 16-bit peak, the tail's
+        column filter and the companding are taken on the scaled samples.  A chunk is a multiple of 512 samples and may be empty;
+        the first one needs ~55-75 ms of audio beyond its frames.  Refused with a streamed speed: a `sample_rate` other than 24000
+        (resampling the scaled stream would need its history and a look-ahead carried too), `split_text` (`length` pulls back
+        between batches) and `use_decoder=False`."""
         if G711.check_encoding(encoding) is not None and not pcm16:
             raise ValueError("encoding applies to 16-bit output: pass pcm16=True")
         skw = _speed_kw(speed)
-        if stream and skw:
+        if stream and skw and not stream_time_scale:
             raise ValueError("speed applies to non-streamed inference only (a chunk's frames depend on the path of everything before it; "
-                             "carrying the path across chunks is not implemented)")
+                             "pass stream_time_scale=True to carry the path across chunks)")
         sample_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        if stream and skw:
+            if sample_rate != CodecEngine.SAMPLE_RATE:
+                raise ValueError("a streamed speed is served at 24000 Hz only (resampling the scaled stream would need its history and a "
+                                 "look-ahead carried too)")
+            if split_text:
+                raise ValueError("a streamed speed does not go with split_text (the schedule's length pulls back between batches)")
+            if not use_decoder:
+                raise ValueError("a streamed speed needs the hidden-state decoder (use_decoder=True)")
+            if np.ndim(speed) != 0:
+                raise ValueError("a streamed speed is one number for the whole batch")
         if stream and sample_rate != CodecEngine.SAMPLE_RATE:
             if not stream_resample:
                 raise ValueError("sample_rate applies to non-streamed inference only (a stream's chunks would need the filter's state carried "
@@ -783,9 +837,19 @@ class Chat:
             result = next(self._infer_code(refer_text, False, self.device, use_decoder, params_infer_code))
             params_infer_code.spk_smp = self.refer_speaker(result.hiddens if use_decoder else result.ids, use_decoder, release=result.destroy)
             params_infer_code.txt_smp = refer_text
+        step = max_split_batch if split_text else len(text)
+        ts = [] if stream and speed is not None else None      # a streamed speed: the rows' streams of the time scaler, opened at the first chunk
+        try:
+            yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
+                                           encoding, speed, ts)
+        finally:
+            for h in ts or ():                                 # also when the consumer drops the generator half way
+                self.codec.time_scale_stream_close(h)
+
+    def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts):
+        """the batch loop of `_infer`"""
         length = 0
         pass_batch_count = 0
-        step = max_split_batch if split_text else len(text)
         for lo in range(0, len(text), step):
             batch = text[lo: lo + step]
             if split_text:
@@ -821,7 +885,13 @@ class Chat:
                 skw = {"rate": sample_rate} if sample_rate is not None else {}      # 24 kHz: today's call, argument for argument
                 if encoding is not None and pcm16:
                     skw["encoding"] = encoding
-                piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw)
+                if ts is not None:
+                    if not ts:
+                        ts.extend(self.codec.time_scale_stream_open(speed) for _ in src)
+                    piece = self._stream_piece_scaled(src, length, length + params_infer_code.stream_speed, ts, False, pcm16,
+                                                      encoding if pcm16 else None)
+                else:
+                    piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
                 # that is BELOW `a`: `length` and `pass_batch_count` are not reset between split batches, so the first yields of a
                 # later batch (a short prefix again) are empty and pull `length` back (tests/test_host_flow.py, stream_split_batches)
@@ -830,7 +900,12 @@ class Chat:
                 yield piece
             if stream and last is not None:
                 skw = {"rate": sample_rate} if sample_rate is not None else {}
-                new_wavs = self._stream_piece(last.hiddens if use_decoder else last.ids, length, None, use_decoder, **skw)
+                if ts is not None:
+                    if not ts:
+                        ts.extend(self.codec.time_scale_stream_open(speed) for _ in last.hiddens)
+                    new_wavs = self._stream_piece_scaled(last.hiddens, length, None, ts, True)
+                else:
+                    new_wavs = self._stream_piece(last.hiddens if use_decoder else last.ids, length, None, use_decoder, **skw)
                 last.destroy()
                 keep_cols = np.sum(np.abs(new_wavs) > 1e-5, axis=0) > 0
                 tail = new_wavs[:, keep_cols]

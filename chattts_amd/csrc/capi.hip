@@ -1223,6 +1223,169 @@ extern "C" int ctts_codec_decode_windows_rate(ctts_codec* c, const float* hid, i
   return 0;
 }
 
+// ---- time scaling of streams: the host's arithmetic (timescale.py: a_of, need, frames_final, base) and every check a launch trusts -------
+static_assert(sizeof(ctts_ts_stream) == 80 && sizeof(TsStream) == 80 && offsetof(ctts_ts_stream, k_prev) == offsetof(TsStream, k_prev) &&
+              offsetof(ctts_ts_stream, slot) == offsetof(TsStream, slot) && offsetof(ctts_ts_stream, n_out) == offsetof(TsStream, n_out) &&
+              CTTS_TS_CARRY == TS_CARRY && CTTS_TS_STATE_INTS == TS_STATE_INTS, "ctts_ts_stream layout");
+static long long ts_a(long long k, long long num) { return k * TS_HS * num / 100; }
+static long long ts_need(long long k, long long num) {
+  return k < 1 ? 0 : std::max(ts_a(k - 1, num) + TS_D + TS_N - 1, ts_a(k, num) - TS_HS + TS_D + TS_N - 1);
+}
+static long long ts_frames_final(long long n_avail, long long num) {
+  long long k = n_avail * 100 / (TS_HS * num) + 2;   // need(k) > k HS num / den: above every frame that may run
+  while (k > 0 && ts_need(k, num) > n_avail) --k;
+  return k;
+}
+static long long ts_base(long long k, long long num) { return std::max(0ll, ts_a(k, num) - TS_HS - TS_D); }
+static long long ts_path_entries(const ctts_ts_stream& w) { return (long long)w.k_now - w.k_prev + (w.k_prev == 0 && w.k_now > 0 ? 1 : 0); }
+// streams [lo, hi) of the host mirror: one launch's worth.  `seen`: n_slots flags, cleared here
+static int check_ts_streams(const char* who, const ctts_ts_stream* tab, int lo, int hi, long long n_x, long long n_y, long long n_path, int n_slots,
+                            std::vector<char>& seen) {
+  std::fill(seen.begin(), seen.end(), 0);
+  for (int i = lo; i < hi; ++i) {
+    const ctts_ts_stream& w = tab[i];
+    if (w.den != 100 || w.num < 50 || w.num > 200) return fail("%s: stream %d: the speed is num / 100 with 50 <= num <= 200 (got %d/%d)", who, i, w.num, w.den);
+    if (w.num == w.den) return fail("%s: stream %d: speed 1 (%d/%d): there is nothing to scale", who, i, w.num, w.den);
+    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: stream %d: slot %d is outside the pool of %d", who, i, w.slot, n_slots);
+    if (seen[w.slot]) return fail("%s: stream %d: slot %d appears twice in one launch", who, i, w.slot);
+    seen[w.slot] = 1;
+    if (w.phase != 0 && w.phase != 1) return fail("%s: stream %d: phase %d is neither 0 nor 1", who, i, w.phase);
+    if (w.n_in < 0 || w.pos < 0 || w.in_off < 0 || w.out_off < 0 || w.path_off < 0) return fail("%s: stream %d: a negative length, position or offset", who, i);
+    if (w.pos >= (1ll << 31) || w.n_in >= (1ll << 31) || w.pos + w.n_in >= (1ll << 31) - 4096)
+      return fail("%s: stream %d would hold 2^31 samples or more (less the 4096 a frame may reach past them)", who, i);
+    if (w.in_off + w.n_in > n_x) return fail("%s: stream %d: the push lies outside the input (%lld floats)", who, i, n_x);
+    const long long end = w.pos + w.n_in;
+    const bool fin = w.total != -1;
+    if (fin && (w.total != end || w.total < 1))
+      return fail("%s: stream %d: a last push ends the stream at pos + n_in = %lld >= 1, got total %lld", who, i, end, (long long)w.total);
+    const long long kp = ts_frames_final(w.pos, w.num);
+    const long long m = (end * w.den + w.num - 1) / w.num;
+    const long long kn = fin ? (m + TS_HS - 1) / TS_HS : ts_frames_final(end, w.num);
+    if (w.k_prev != kp || w.k_now != kn)
+      return fail("%s: stream %d: %lld + %lld samples at %d/%d make frames (%lld, %lld] final, got (%d, %d]", who, i, (long long)w.pos, (long long)w.n_in,
+                  w.num, w.den, kp, kn, w.k_prev, w.k_now);
+    const long long no = fin ? m - TS_HS * kp : TS_HS * (kn - kp);
+    if (w.n_out != no) return fail("%s: stream %d: the step emits %lld samples, got %d", who, i, no, w.n_out);
+    if (w.out_off + no > n_y) return fail("%s: stream %d: the chunk lies outside the output (%lld floats)", who, i, n_y);
+    if (w.path_off + ts_path_entries(w) > n_path) return fail("%s: stream %d: the path entries lie outside the path (%lld entries)", who, i, n_path);
+    const long long c_in = w.pos - ts_base(kp, w.num), c_out = fin ? 0 : end - ts_base(kn, w.num);
+    if (c_in < 0 || c_in > TS_CARRY || c_out < 0 || c_out > TS_CARRY)
+      return fail("%s: stream %d: a carry of %lld samples exceeds the %d a slot keeps", who, i, std::max(c_in, c_out), TS_CARRY);
+  }
+  return 0;
+}
+extern "C" int ctts_time_scale_stream_step(const float* x, int64_t n_x, const ctts_ts_stream* st_dev, const ctts_ts_stream* st_host,
+                                           int32_t n_streams, float* y, int64_t n_y, int32_t* path, int64_t n_path, float* carry, int32_t* state,
+                                           int32_t n_slots, const float* window, void* stream) {
+  const char* who = "ctts_time_scale_stream_step";
+  if (!st_dev || !st_host || !carry || !state || !window)
+    return fail("%s: a null pointer (both descriptor tables, the carry, the state and the window are needed)", who);
+  if (n_x < 0 || n_y < 0 || n_path < 0 || (!x && n_x) || (!y && n_y) || (!path && n_path))
+    return fail("%s: a null pointer (x, y or path) with a length other than 0", who);
+  if (n_streams < 1 || n_streams > 1024) return fail("%s: need 1 <= n_streams <= 1024 (got %d)", who, n_streams);
+  if (n_slots < 1) return fail("%s: the state pool has no slot", who);
+  std::vector<char> seen((size_t)n_slots, 0);
+  if (check_ts_streams(who, st_host, 0, n_streams, n_x, n_y, n_path, n_slots, seen)) return -1;
+  CttsDeviceGuard dg(stream);
+  CK(launch_time_scale_stream(x, (const TsStream*)st_dev, n_streams, y, path, carry, state, window, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- window decode of time-scaled streams: crop -> stream step -> 16-bit conversion, around ONE ragged decoder pass --------------------
+// workspace = the window-decode workspace (n_win >= 1) | the scaled chunks, each from a multiple of 8 floats on | the path entries
+extern "C" size_t ctts_codec_windows_speed_workspace_bytes(int32_t n_win, int32_t total_tokens, int64_t chunk_floats) {
+  if (n_win < 0 || chunk_floats < 0 || chunk_floats >= (1ll << 31)) return 0;
+  const size_t base = n_win ? ctts_codec_windows_workspace_bytes(n_win, total_tokens) : 0;
+  if (n_win && base == 0) return 0;
+  return base + align_up((size_t)chunk_floats * 4 + 16);
+}
+extern "C" int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots,
+                                               int32_t hid_cap, const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win,
+                                               const ctts_window* cwin_dev, const ctts_window* cwin_host, const ctts_rs_window* crs_dev,
+                                               const ctts_rs_window* crs_host, int32_t n_conv, const ctts_ts_stream* ts_dev,
+                                               const ctts_ts_stream* ts_host, const int32_t* round_off, int32_t n_rounds, float* carry,
+                                               int32_t* state, int32_t n_ts_slots, const float* ts_window, int32_t out_type, void* out,
+                                               uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
+  const char* who = "ctts_codec_decode_windows_speed";
+  if (!c || !cwin_dev || !cwin_host || !crs_dev || !crs_host || !ts_dev || !ts_host || !round_off || !carry || !state || !ts_window || !out)
+    return fail("%s: a null pointer", who);
+  if (n_win < 0 || n_win > 1024 || (n_win && (!hid || !win_dev || !win_host))) return fail("%s: need 0 <= n_win <= 1024 and, with windows, the store and their tables", who);
+  if (n_conv < 1 || n_conv > 2048) return fail("%s: need 1 <= n_conv <= 2048 (got %d)", who, n_conv);
+  if (n_rounds < 1 || n_rounds > n_conv || round_off[0] != 0) return fail("%s: need 1 <= n_rounds <= n_conv, the first round at 0", who);
+  for (int r = 0; r < n_rounds; ++r)
+    if (round_off[r + 1] <= round_off[r]) return fail("%s: round %d is empty", who, r);
+  const int n_ts = round_off[n_rounds];
+  if (n_ts > n_conv) return fail("%s: %d stream descriptors for %d chunks", who, n_ts, n_conv);
+  if (n_ts_slots < 1) return fail("%s: the state pool has no slot", who);
+  if ((out_type != 0 && out_type != 1) || (product != 0 && product != 1)) return fail("%s: out_type and product must be 0 or 1", who);
+  if ((uintptr_t)out & 15) return fail("%s: the output must be 16-byte aligned", who);
+  if (n_win && (n_slots < 1 || hid_cap < 1 || row_stride < 768 || slot_stride < (int64_t)hid_cap * row_stride || (row_stride & 3) || (slot_stride & 3) ||
+                ((uintptr_t)hid & 15)))
+    return fail("%s: the store must be [n_slots][hid_cap][768] floats with 16-byte aligned rows", who);
+  std::vector<int32_t> tok(n_win + 1, 0);
+  for (int i = 0; i < n_win; ++i) {
+    const ctts_window& w = win_host[i];
+    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: window %d names slot %d of %d", who, i, w.slot, n_slots);
+    if (w.t_lo < 0 || w.t_hi <= w.t_lo) return fail("%s: window %d is empty (tokens %d -> %d)", who, i, w.t_lo, w.t_hi);
+    if (w.t_hi > hid_cap) return fail("%s: window %d ends at token %d beyond the slot's capacity %d", who, i, w.t_hi, hid_cap);
+    const int64_t n_samples = 256 * (2 * (int64_t)(w.t_hi - w.t_lo) - 1);
+    if (w.c_lo < 0 || w.c_hi <= w.c_lo || w.c_hi > n_samples)
+      return fail("%s: window %d crops samples %d -> %d outside its %lld samples", who, i, w.c_lo, w.c_hi, (long long)n_samples);
+    tok[i + 1] = tok[i] + (w.t_hi - w.t_lo);
+    if (tok[i + 1] > (1 << 28)) return fail("%s: too many tokens", who);
+  }
+  const int T = tok[n_win];
+  const long long n_x = n_win ? 256 * (2 * (long long)T - n_win) : 0;
+  // what chunk e of the output is: a 24 kHz crop of the packed decode (rate < 0), or the chunk of stream descriptor `rate`
+  std::vector<char> used((size_t)n_ts, 0);
+  long long chunk_floats = 0, n_path = 0;
+  for (int e = 0; e < n_conv; ++e) {
+    const ctts_rs_window& r = crs_host[e];
+    if (cwin_host[e].keep && !keep_bits) return fail("%s: chunk %d asks for a keep mask but keep_bits is null", who, e);
+    if (r.rate < 0) {
+      if (r.in_off < 0 || r.n_in < 1 || r.in_off + r.n_in > n_x) return fail("%s: chunk %d: the crop lies outside the packed decode (%lld floats)", who, e, n_x);
+      continue;
+    }
+    if (r.rate >= n_ts || used[r.rate]) return fail("%s: chunk %d names stream descriptor %d of %d, or one that is taken", who, e, r.rate, n_ts);
+    used[r.rate] = 1;
+    const ctts_ts_stream& t = ts_host[r.rate];
+    if (r.o_lo != 0 || r.o_hi != t.n_out || r.o_hi < 0 || r.out_off != chunk_floats || t.out_off != chunk_floats)
+      return fail("%s: chunk %d: the scaled chunks lie one behind the other, each from a multiple of 8 floats on", who, e);
+    if (t.path_off != n_path) return fail("%s: chunk %d: the path entries lie one behind the other", who, e);
+    chunk_floats += ((long long)r.o_hi + 7) & ~7ll;
+    n_path += ts_path_entries(t);
+  }
+  for (int q = 0; q < n_ts; ++q)
+    if (!used[q]) return fail("%s: stream descriptor %d belongs to no chunk", who, q);
+  const long long area = chunk_floats + ((n_path + 7) & ~7ll);
+  const size_t need_ws = area < (1ll << 31) ? ctts_codec_windows_speed_workspace_bytes(n_win, T, area) : 0;
+  if (!workspace || need_ws == 0 || ws_bytes < need_ws) return fail("codec workspace too small");
+  std::vector<char> seen((size_t)n_ts_slots, 0);
+  for (int r = 0; r < n_rounds; ++r)
+    if (check_ts_streams(who, ts_host, round_off[r], round_off[r + 1], n_x, chunk_floats, n_path, n_ts_slots, seen)) return -1;
+  const float* wav = nullptr;
+  float* chunks = (float*)workspace;
+  if (n_win) {
+    WindowsWs ws = carve_windows(workspace, n_win, T);
+    wav = ws.wav;
+    chunks = (float*)((char*)workspace + ws.bytes);
+    {
+      CttsDeviceGuard dg(stream);
+      CK(launch_gather_windows(hid, slot_stride, row_stride, (const CodecWindow*)win_dev, n_win, T, ws.hid, ws.tok_off, (hipStream_t)stream));
+    }
+    if (ctts_dvae_decode_ragged(c, ws.hid, ws.tok_off, tok.data(), n_win, ws.mel, workspace, ws.ragged_bytes, stream)) return -1;
+    if (ctts_vocos_decode_ragged(c, ws.mel, ws.tok_off, tok.data(), n_win, ws.wav, workspace, ws.ragged_bytes, stream)) return -1;
+  }
+  int32_t* path = (int32_t*)(chunks + chunk_floats);
+  CttsDeviceGuard dg(stream);
+  for (int r = 0; r < n_rounds; ++r)      // a stream with several chunks in the call takes them one launch after the other
+    CK(launch_time_scale_stream(wav, (const TsStream*)ts_dev + round_off[r], round_off[r + 1] - round_off[r], chunks, path, carry, state, ts_window,
+                                (hipStream_t)stream));
+  CK(launch_chunks_pcm16(wav, chunks, (const CodecWindow*)cwin_dev, (const RsWindow*)crs_dev, n_conv, out_type == 0 ? 1 : 0, product, keep_thr,
+                         out, keep_bits, (hipStream_t)stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // single-kernel entry points
 // ------------------------------------------------------------------------------------------------

@@ -514,6 +514,20 @@ hipError_t launch_time_scale_ragged(const float* x, const long long* off_in, flo
                                     const long long* path_off, int n_seg, long long n_out_max, const float* window, int num, int den,
                                     hipStream_t st);
 
+#define TS_CARRY 2560         // floats of one carry buffer of a stream slot; a slot has two (a step reads one and writes the other)
+#define TS_STATE_INTS 4       // int32 per slot of the state table: s_K, three reserved
+// ctts_ts_stream (include/chattts_amd.h), field for field (capi.hip asserts the layout): one push of one stream.  x[in_off, in_off + n_in)
+// are samples [pos, pos + n_in) of the stream; total: its length when this push is the last, else -1; the step runs frames k_prev < k <=
+// k_now, writes n_out samples to y[out_off ..] and the frames' path entries (s_0 in front of frame 1's) to path[path_off ..]; slot / phase:
+// the state slot and which of its two carry buffers holds x[base(k_prev), pos)
+struct TsStream {
+  long long in_off, n_in, pos, total, out_off, path_off;
+  int32_t k_prev, k_now, slot, phase, num, den, n_out, reserved;
+};
+// one workgroup per stream; carry [n_slots][2][TS_CARRY] floats, state [n_slots][TS_STATE_INTS] int32.  Every bound is the caller's to check
+hipError_t launch_time_scale_stream(const float* x, const TsStream* tab, int n_streams, float* y, int32_t* path, float* carry, int32_t* state,
+                                    const float* window, hipStream_t st);
+
 // ---- G.711 companding (g711.hip) ----------------------------------------------------------------
 #define G711_TILE 4096        // samples per workgroup: 256 threads, 16 consecutive samples each
 // ctts_g711_range (include/chattts_amd.h), field for field (capi.hip asserts the layout): elements [start, start + n) of the int16 input

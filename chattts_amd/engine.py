@@ -1547,6 +1547,120 @@ class CodecEngine:
             return (y, off_out, path, path_off) if return_path else (y, off_out)
         return (y, path) if return_path else y
 
+    # -- time scaling of streams: per-stream device state (csrc/timescale.hip, timescale_stream_k) ---------------------------------------
+    TS_STREAM_SLOTS = 64      # the state pool's first size; it doubles when every slot is taken
+
+    def _ts_pool(self) -> dict:
+        """the state pool: carry [slots, 2, TS.CARRY] float32 and state [slots, 4] int32 on the device, the free list, and per open
+        stream its host record [num, den, samples pushed, carry phase, done]"""
+        pool = self.__dict__.get("_ts_streams")
+        if pool is None:
+            n = int(self.TS_STREAM_SLOTS)
+            pool = self._ts_streams = dict(carry=torch.zeros((n, 2, TS.CARRY), dtype=torch.float32, device=self.device),
+                                           state=torch.zeros((n, 4), dtype=torch.int32, device=self.device), free=list(range(n - 1, -1, -1)), rec={})
+        return pool
+
+    def time_scale_stream_open(self, speed: float) -> int:
+        """A stream of the time scaler at `speed` (0.5 .. 2.0, not 1): -> its handle, a slot of the engine's state pool.  The slot is
+        fresh by construction -- the first step of a stream reads neither carry nor state -- so nothing is cleared.  ValueError for a
+        speed the scaler does not take."""
+        num, den = TS.quantize(speed)
+        if num == den:
+            raise ValueError("time_scale: the speed is 1, there is nothing to scale")
+        pool = self._ts_pool()
+        if not pool["free"]:
+            n = int(pool["carry"].shape[0])
+            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
+            pool["state"] = torch.cat([pool["state"], torch.zeros_like(pool["state"])])
+            pool["free"] = list(range(2 * n - 1, n - 1, -1))
+        slot = pool["free"].pop()
+        pool["rec"][slot] = [num, den, 0, 0, False]
+        return slot
+
+    def time_scale_stream_close(self, handle: int) -> None:
+        """gives the stream's slot back (any time: finished, or abandoned half way)"""
+        pool = self._ts_pool()
+        if pool["rec"].pop(int(handle), None) is None:
+            raise ValueError(f"time_scale: stream {handle} is not open")
+        pool["free"].append(int(handle))
+
+    def time_scale_streams_in_use(self) -> int:
+        """the streams that are open: slots of the state pool not on its free list"""
+        return len(self._ts_pool()["rec"])
+
+    def time_scale_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
+        """`timescale.stream_plan` of the stream's next push: what a step with `n_in` more samples would run and emit"""
+        rec = self._ts_pool()["rec"].get(int(handle))
+        if rec is None:
+            raise ValueError(f"time_scale: stream {handle} is not open")
+        if rec[4]:
+            raise ValueError(f"time_scale: stream {handle} has had its last push")
+        return TS.stream_plan(rec[0] / rec[1], rec[2], n_in, final)
+
+    def _ts_descriptors(self, pushes):
+        """pushes [(handle, in_off, n_in, final)], in the order given, a stream's pushes in ITS order -> (TS_STREAM table sorted into
+        rounds with out_off / path_off unset, round_off, order: order[q] = the push behind row q, commit: handle -> its new host record).
+        All in Python integers and before anything is launched; the records change only when the caller commits."""
+        recs = self._ts_pool()["rec"]
+        shadow, rounds = {}, []
+        for i, (h, in_off, n_in, final) in enumerate(pushes):
+            h = int(h)
+            if h not in recs:
+                raise ValueError(f"time_scale: stream {h} is not open")
+            num, den, pushed, phase, done, r = shadow.get(h, (*recs[h], 0))
+            if done:
+                raise ValueError(f"time_scale: stream {h} has had its last push")
+            p = TS.stream_plan(num / den, pushed, n_in, final)
+            row = (int(in_off), int(n_in), pushed, p["total"], 0, 0, p["k_prev"], p["k_now"], h, phase, num, den, p["n_out"], 0)
+            if r == len(rounds):
+                rounds.append([])
+            rounds[r].append((i, row, p["n_path"]))
+            shadow[h] = (num, den, pushed + int(n_in), phase ^ 1, bool(final), r + 1)
+        order = [i for rd in rounds for i, _, _ in rd]
+        tab = np.zeros(len(order), _lib.TS_STREAM)
+        for q, (_, row, _) in enumerate(e for rd in rounds for e in rd):
+            tab[q] = row
+        n_path = [n for rd in rounds for _, _, n in rd]
+        round_off = np.zeros(len(rounds) + 1, np.int32)
+        np.cumsum([len(rd) for rd in rounds], out=round_off[1:])
+        return tab, round_off, order, n_path, {h: list(v[:5]) for h, v in shadow.items()}
+
+    def time_scale_stream_step(self, x: torch.Tensor, pushes, return_path: bool = False):
+        """ONE step of many streams (ctts_time_scale_stream_step, one launch): `x`, a 1-D float32 device tensor, holds the new samples
+        of every stream; `pushes` = [(handle, in_off, n_in, final)]: x[in_off, in_off + n_in) continue stream `handle` (n_in 0: nothing
+        new), `final`: they are its last.  -> (y, off): stream i's chunk is y[off[i], off[i+1]) (possibly empty); the chunks of a
+        stream, concatenated, are `time_scale` of its concatenated pushes, bit for bit, however they were cut.  `return_path`: also
+        (path, path_off), the frame starts the step chose (s_0 comes with frame 1's).  A handle may appear once per call.  Every
+        refusal (ValueError here, EngineError from the library) comes before the launch and leaves all streams as they were."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+            raise ValueError("time_scale: a contiguous 1-D float32 device tensor")
+        if len(pushes) < 1:
+            raise ValueError("time_scale: nothing to step")
+        if len({int(p[0]) for p in pushes}) != len(pushes):
+            raise ValueError("time_scale: a stream appears twice in one step")
+        for _, in_off, n_in, _ in pushes:
+            if int(in_off) < 0 or int(n_in) < 0 or int(in_off) + int(n_in) > x.numel():
+                raise ValueError("time_scale: a push lies outside the tensor")
+        tab, _, order, n_path, commit = self._ts_descriptors(pushes)
+        assert order == list(range(len(pushes)))
+        off = np.zeros(len(pushes) + 1, np.int64)
+        np.cumsum(tab["n_out"], out=off[1:])
+        path_off = np.zeros(len(pushes) + 1, np.int64)
+        np.cumsum(n_path, out=path_off[1:])
+        tab["out_off"], tab["path_off"] = off[:-1], path_off[:-1]
+        pool = self._ts_pool()
+        y = torch.empty((int(off[-1]),), dtype=torch.float32, device=x.device)
+        path = torch.empty((int(path_off[-1]),), dtype=torch.int32, device=x.device)
+        tab_d = torch.from_numpy(tab.view(np.uint8)).to(x.device)
+        st = torch.cuda.current_stream(x.device)
+        _lib.check(self.lib.ctts_time_scale_stream_step(
+            x.data_ptr() if x.numel() else None, x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(tab),
+            y.data_ptr() if y.numel() else None, y.numel(), path.data_ptr() if path.numel() else None, path.numel(), pool["carry"].data_ptr(),
+            pool["state"].data_ptr(), int(pool["carry"].shape[0]), self._time_scale_window().data_ptr(), st.cuda_stream), "ctts_time_scale_stream_step")
+        tab_d.record_stream(st)
+        pool["rec"].update(commit)
+        return (y, off, path, path_off) if return_path else (y, off)
+
     def time_scale_segments(self, wav: torch.Tensor, off, speeds):
         """packed segments at ONE SPEED EACH (`speeds[i]` for segment i): requests that were decoded together and want different speeds.
         One call per run of neighbouring segments at one speed, all into one packed output; segments at speed 1 are copied, not
@@ -1778,7 +1892,7 @@ class CodecEngine:
         return wav[:, c_lo: c_hi]
 
     def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
-                       sample_rates=None, encodings=None):
+                       sample_rates=None, encodings=None, speeds=None, ts_streams=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -1797,7 +1911,27 @@ class CodecEngine:
         "alaw".  A companded window comes back as uint8, `g711.encode` of the int16 array it would come back as -- strictly behind the
         conversion, a tail's strip included (ONE ctts_g711_encode_ranges launch over the windows' own element offsets; the codes and
         the keep masks sit side by side in the output buffer, so one copy brings both; a call that mixes PCM16 and companded windows
-        copies the PCM16 samples with them, still in one copy)."""
+        copies the PCM16 samples with them, still in one copy).
+        `speeds` (None, or all 1.0: the call above, argument for argument): one speed per window, with `ts_streams`, one entry per
+        window: the handle of the time scaler's stream (`time_scale_stream_open`) the window continues, None at speed 1.  A window
+        at another speed PUSHES its 24 kHz crop into its stream and yields what that step emits (`time_scale_stream_step`: a
+        multiple of 512 samples, possibly none; a window marked `tail` is the stream's last push and yields the rest) -- crop ->
+        stream step -> conversion on the device (ctts_codec_decode_windows_speed), the peak, the conversion, a tail's strip and the
+        companding taken on the scaled samples; still one decoder pass and one copy.  A window whose crop is empty still steps its
+        stream.  Several windows of one stream are taken in the order given.  Windows at speed 1 return the bytes they return
+        without `speeds`.  A speed together with a rate other than 24000 is refused: resampling the scaled stream would need its
+        history and a look-ahead carried too."""
+        if speeds is not None:
+            if len(speeds) != len(windows):
+                raise ValueError("decode_windows: one speed per window")
+            q = [TS.quantize(v) for v in speeds]
+            if any(n != d for n, d in q):
+                if sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
+                    raise ValueError("decode_windows: a streamed speed goes with 24000 Hz only (resampling the scaled stream would need "
+                                     "its history and a look-ahead carried too)")
+                if ts_streams is None or len(ts_streams) != len(windows):
+                    raise ValueError("decode_windows: speeds need ts_streams, one entry per window")
+                return self._decode_windows_speed(store, windows, q, ts_streams, pcm16, keep_thr, product, encodings)
         laws = None
         if encodings is not None:
             if len(encodings) != len(windows):
@@ -1848,6 +1982,99 @@ class CodecEngine:
                                                       cur.cuda_stream), "ctts_codec_decode_windows")
         tab_d.record_stream(cur)
         return self._windows_to_host(buf, n_out, n_g, off, n, tab[:, 5], live, None if laws is None else [laws[i] for i in live], dt, out)
+
+    def _decode_windows_speed(self, store: torch.Tensor, windows, q, ts_streams, pcm16: bool, keep_thr: Optional[float], product: str,
+                              encodings=None):
+        """`decode_windows` with at least one window at another speed than 1 (q: the windows' (num, den))"""
+        laws = None
+        if encodings is not None:
+            if len(encodings) != len(windows):
+                raise ValueError("decode_windows: one encoding per window")
+            if any(G711.check_encoding(e) is not None for e in encodings):
+                if not pcm16:
+                    raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
+                laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
+        assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
+        S, cap = int(store.size(0)), int(store.size(1))
+        dt = np.int16 if pcm16 else np.float32
+        out: list = [None] * len(windows)
+        recs = self._ts_pool()["rec"]
+        rows, crops, conv, pushes = [], [], [], []     # decode windows; their crops; (window, decode row or None, push or None); stream pushes
+        for i, w in enumerate(windows):
+            slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
+            last = len(w) > 4 and bool(w[4])
+            if not (0 <= slot < S and 0 <= Tn <= cap):
+                raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
+            scaled = q[i][0] != q[i][1]
+            if scaled:
+                h = ts_streams[i]
+                if h is None or int(h) not in recs or tuple(recs[int(h)][:2]) != tuple(q[i]):
+                    raise ValueError(f"decode_windows: window {i} at speed {q[i][0]}/{q[i][1]} needs an open stream of that speed")
+            elif ts_streams[i] is not None:
+                raise ValueError(f"decode_windows: window {i} is at speed 1 but names a stream")
+            win = window_for_samples(Tn, s_lo, VOCOS.hop * (2 * Tn - 1) if s_hi is None else s_hi)
+            if win is None and not scaled:
+                out[i] = np.zeros((0,), np.uint8 if laws is not None and laws[i] >= 0 else dt)
+                continue
+            k = None
+            if win is not None:
+                k = len(rows)
+                rows.append((slot, *win, 0, 0, 0))
+            if scaled:
+                pushes.append([int(ts_streams[i]), k, 0, last])
+            conv.append((i, k, len(pushes) - 1 if scaled else None, int(last and keep_thr is not None)))
+        tab = np.ascontiguousarray(np.array(rows, dtype=np.int32).reshape(-1, 8))       # ctts_window[n_win]: what is decoded
+        tok = np.zeros(len(rows) + 1, np.int64)
+        np.cumsum(tab[:, 2] - tab[:, 1], out=tok[1:])
+        start = VOCOS.hop * (2 * tok[:-1] - np.arange(len(rows))) + tab[:, 3]           # the crops in the packed decode
+        width = (tab[:, 4] - tab[:, 3]).astype(np.int64)
+        for p in pushes:
+            p[1], p[2] = (0, 0) if p[1] is None else (int(start[p[1]]), int(width[p[1]]))
+        ts, round_off, order, n_path, commit = self._ts_descriptors([tuple(p) for p in pushes])
+        rank = {i: r for r, i in enumerate(order)}                                       # push -> its row of the descriptor table
+        ctab = np.zeros((len(conv), 8), np.int32)                                        # ctts_window[n_conv]: only `keep` is read
+        rtab = np.zeros(len(conv), _lib.RS_WINDOW)
+        rtab["rate"] = -1
+        chunk = paths = 0
+        for e, (i, k, pi, keep) in enumerate(conv):
+            ctab[e, 5] = keep
+            if k is not None:
+                rtab["in_off"][e], rtab["n_in"][e] = start[k], width[k]
+            if pi is not None:
+                r = rank[pi]
+                m = int(ts["n_out"][r])
+                ts["out_off"][r], ts["path_off"][r] = chunk, paths
+                rtab["o_hi"][e], rtab["out_off"][e], rtab["rate"][e] = m, chunk, r
+                chunk += (m + 7) // 8 * 8
+                paths += n_path[r]
+        n = np.where(rtab["rate"] >= 0, rtab["o_hi"], rtab["n_in"]).astype(np.int64)
+        off = np.zeros(len(conv) + 1, np.int64)
+        np.cumsum((n + 7) // 8 * 8, out=off[1:])                             # every chunk starts on a multiple of 8 samples
+        esz = 2 if pcm16 else 4
+        n_out, any_keep = int(off[-1]) * esz, bool(ctab[:, 5].any())
+        n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if any_keep else 0
+        n_g = (int(off[-1]) + 15) // 16 * 16 if laws is not None else 0
+        cur = torch.cuda.current_stream(self.device)
+        buf = torch.empty((max(16, n_out + n_g + n_keep),), dtype=torch.uint8, device=self.device)   # samples | (companded bytes) | keep masks: one copy
+        parts = [tab.view(np.uint8).reshape(-1), ctab.view(np.uint8).reshape(-1), rtab.view(np.uint8), ts.view(np.uint8)]
+        blob_d = torch.from_numpy(np.concatenate(parts)).to(self.device)                 # one upload: the four tables
+        p0 = blob_d.data_ptr()
+        p1, p2 = p0 + parts[0].nbytes, p0 + parts[0].nbytes + parts[1].nbytes
+        p3 = p2 + parts[2].nbytes
+        pool = self._ts_pool()
+        ws, nws = self._ws_bytes(self.lib.ctts_codec_windows_speed_workspace_bytes(len(rows), int(tok[-1]), chunk + (paths + 7) // 8 * 8))
+        _lib.check(self.lib.ctts_codec_decode_windows_speed(
+            self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap, p0 if len(rows) else None,
+            tab.ctypes.data_as(C.c_void_p) if len(rows) else None, len(rows), p1, ctab.ctypes.data_as(C.c_void_p), p2, rtab.ctypes.data_as(C.c_void_p),
+            len(conv), p3, ts.ctypes.data_as(C.c_void_p), round_off.ctypes.data_as(C.c_void_p), len(round_off) - 1, pool["carry"].data_ptr(),
+            pool["state"].data_ptr(), int(pool["carry"].shape[0]), self._time_scale_window().data_ptr(), 1 if pcm16 else 0, buf.data_ptr(),
+            buf.data_ptr() + n_out + n_g if any_keep else None, {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws,
+            cur.cuda_stream), "ctts_codec_decode_windows_speed")
+        blob_d.record_stream(cur)
+        pool["rec"].update(commit)
+        live = [c[0] for c in conv]
+        return self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, off, n, ctab[:, 5], live, None if laws is None else [laws[i] for i in live],
+                                     dt, out)
 
     def _windows_to_host(self, buf: torch.Tensor, n_out: int, n_g: int, off, n, keep, live, laws, dt, out: list) -> list:
         """the end of `decode_windows`: `buf` = samples (n_out bytes) | companded bytes (n_g, 0 without `laws`) | keep masks.  The

@@ -95,7 +95,7 @@ def _have_av() -> bool:
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
-               stream_sample_rates=None, g711: bool = False, speed: bool = False):
+               stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -131,7 +131,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     `stream_sample_rates` allow -- 8000 is the telephone's.  With `voice_upload`, mu-law / A-law WAV clips are accepted too
     (audio.load_wav(g711=True)).  `speed=True` (default off: the body's `"speed"` is validated to lie in 0.5 .. 2.0 and then ignored, like
     the reference does): a non-streamed request is served at its `"speed"` -- the same utterance at the same pitch, time-scaled on the
-    device behind the decode (Chat.infer(speed=) / SpeechBatcher.submit(speed=)); a speed other than 1.0 with `"stream": true` gets a 400."""
+    device behind the decode (Chat.infer(speed=) / SpeechBatcher.submit(speed=)); a speed other than 1.0 with `"stream": true` gets a 400
+    -- unless `stream_speed=True` (with `speed`; default off): then a streamed request is served at its speed too, the time scaler's path
+    carried across its chunks on the device -- from the pool with `batch_streams` (SpeechBatcher(stream_speeds=True).submit_stream(speed=)),
+    serially otherwise (Chat.infer(stream=True, speed=, stream_time_scale=True)); a streamed speed at a rate other than 24000 gets a 400."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -147,11 +150,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     if batcher is None and batch_slots is not None:
         from .serving import SpeechBatcher
         batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode, streams=bool(batch_streams),
-                                **({"refine": True} if batch_refine else {}))
+                                **({"refine": True} if batch_refine else {}), **({"stream_speeds": True} if speed and stream_speed else {}))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
     pool_streams = bool(batch_streams) and batcher is not None and bool(getattr(batcher, "streams", False))
+    pool_stream_speeds = pool_streams and bool(speed and stream_speed) and bool(getattr(batcher, "stream_speeds", False))
     pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
     pool_split = bool(batch_split) and batcher is not None
     allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
@@ -220,6 +224,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             kw = {**kw, "encoding": law}
         if req.stream and rate != SAMPLE_RATE:       # one text: split_text changes nothing but is refused for a stream at another rate
             kw = {**kw, "stream_resample": True, "split_text": False}
+        if req.stream and spd is not None:           # likewise for a stream at another speed
+            kw = {**kw, "stream_time_scale": True, "split_text": False}
         return chat.infer(text=[req.input], stream=bool(req.stream), lang=None, skip_refine_text=True, refine_text_only=False,
                           use_decoder=True, do_text_normalization=True, do_homophone_replacement=True,
                           params_infer_code=code_params(req.voice), pcm16=True, **kw)
@@ -258,9 +264,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                                 f"produced at {SAMPLE_RATE} Hz (the resampling filter's state is not carried across chunks)")
         spd = None                                   # the request's speed where it is honoured and is not 1.0
         if speed and req.speed is not None and int(round(100.0 * req.speed)) != 100:
-            if req.stream:
+            if req.stream and not stream_speed:
                 raise HTTPException(400, detail=f"speed {req.speed} is served for non-streamed requests only: a stream's chunks are "
                                                 f"produced at speed 1.0 (the time scaler's path is not carried across chunks)")
+            if req.stream and rate != SAMPLE_RATE:
+                raise HTTPException(400, detail=f"a streamed speed is served at {SAMPLE_RATE} Hz only: speed {req.speed} with sample_rate {rate} "
+                                                f"would need the scaled stream's history and a look-ahead carried into the resampler")
             spd = int(round(100.0 * req.speed)) / 100
         refine = refine_of(request_data)
         rkw = {} if refine is None else {"refine": refine}
@@ -296,9 +305,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 return pcm.tobytes()
             return _av_encode(pcm, fmt, rate)
 
-        if req.stream and pool_streams:
+        if req.stream and pool_streams and (spd is None or pool_stream_speeds):
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
                 skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
+                if spd is not None:
+                    skw = {**skw, "speed": spd}
                 chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw, **ekw)
                 try:
                     first = True
@@ -319,7 +330,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        gen = infer(req, rate) if law is None else infer(req, rate, law)
+                        gen = infer(req, rate, law, spd) if spd is not None else (infer(req, rate) if law is None else infer(req, rate, law))
                         async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
                             if fmt == "wav" and first:
                                 yield stream_header(rate)

@@ -656,7 +656,8 @@ class _Job:
     encoding: Optional[str] = None         # None: int16
     code_text: Optional[str] = None        # the text of the code stage: normalised, with `refine` then refined
     in_text_pool: bool = False             # the refine-text pass of an unsplit request is queued or resident
-    speed: Optional[float] = None          # None: 1.0 (never set on a stream)
+    speed: Optional[float] = None          # None: 1.0 (on a stream only with SpeechBatcher(stream_speeds=True))
+    ts_slot: Optional[int] = None          # a stream at another speed: its stream of the time scaler, opened at its first chunk
 
     @property
     def is_stream(self) -> bool:
@@ -724,6 +725,11 @@ class SpeechBatcher:
     `CodecEngine.decode_windows`), each what the serial streamed path yields for that request; `stream_decode_calls` counts those
     decodes, `stream_chunks` the chunks they served, `max_stream_group` the most one decode served.
 
+    `stream_speeds=True` (with `streams`; off: `submit_stream(speed=)` is refused as before): a streamed request may carry a speed.
+    Its job record holds a stream of the time scaler (`CodecEngine.time_scale_stream_open`, opened at its first chunk, given back
+    in `_resolve` however the request ends); the chunks due at one poll -- at whatever speeds, speed 1 among them -- still come from
+    one window decode (`CodecEngine.decode_windows(speeds=, ts_streams=)`); `occupancy()["stream_scaled_chunks"]` counts them.
+
     `refine=True`: requests may ask for the reference's DEFAULT behaviour, the refine-text pass in front of the code pass
     (`submit(text, params, refine=RefineTextParams(...))`).  A second, TEXT-mode per-request pool (SlotPool(infer_text=True), its own
     handle and stream, `text_cap` positions per slot: the endpoint's 2048-character inputs + 384 new tokens by default) serves that stage:
@@ -754,7 +760,7 @@ class SpeechBatcher:
 
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
                  logger=None, ragged_decode: bool = False, streams: bool = False, refine: bool = False, make_text_pool=None,
-                 text_cap: Optional[int] = None, refine_rng: str = "host"):
+                 text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
@@ -765,6 +771,8 @@ class SpeechBatcher:
         self.stream_decode_calls = 0  # window decodes over the due chunks of streamed requests
         self.stream_chunks = 0        # chunks those decodes served (empty chunks included)
         self.stream_resampled_chunks = 0   # those of them at another rate than 24 kHz
+        self.stream_speeds = bool(stream_speeds)   # submit_stream(speed=) is accepted
+        self.stream_scaled_chunks = 0      # chunks of streams at another speed than 1
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.max_stream_group = 0     # most chunks one window decode served
         self.cancelled = 0            # streams closed by their consumer before the end
@@ -851,10 +859,16 @@ class SpeechBatcher:
         due at one poll still come from one decoder pass (CodecEngine.decode_windows(sample_rates=)).  `encoding` (None: int16;
         "ulaw" / "alaw"): the serial call's `encoding=` -- the chunks are uint8 G.711 codes; the chunks of one poll share the decoder
         pass and ONE companding launch whatever their encodings (CodecEngine.decode_windows(encodings=)).  `speed` other than 1 is
-        refused: a chunk's frames depend on the path of everything before it, which is not carried across chunks."""
+        refused: a chunk's frames depend on the path of everything before it, which is not carried across chunks -- unless the
+        batcher was built with `stream_speeds=True`: then the chunks are those of the serial call with `speed=, stream_time_scale=True`
+        (the path and a tail of samples are carried on the device, per stream), at 24000 Hz only."""
         G711.check_encoding(encoding)
-        if _job_speed(speed) is not None:
+        speed = _job_speed(speed)
+        if speed is not None and not self.stream_speeds:
             raise ValueError("speed applies to non-streamed requests only (a chunk's frames depend on the path of everything before it)")
+        if speed is not None and self._rate(sample_rate) is not None:
+            raise ValueError("a streamed speed is served at 24000 Hz only (resampling the scaled stream would need its history and a "
+                             "look-ahead carried too)")
         if split_text:
             raise ValueError("split_text is served for non-streamed requests only")
         if not self.streams:
@@ -864,7 +878,7 @@ class SpeechBatcher:
         if rate is not None:
             RS.plan(24000, rate, [0, 1])       # an unsupported pair is refused here, not at the first chunk
         h = SpeechStream(self, next(self._ids))
-        self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding))
+        self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed))
         return h
 
     def _check_refine(self, refine) -> None:
@@ -885,7 +899,7 @@ class SpeechBatcher:
         if self.streams:      # (list(): the worker changes the registry meanwhile)
             occ.update({"streams": sum(j.is_stream for j in list(self._jobs.values())), "stream_decode_calls": self.stream_decode_calls,
                         "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled,
-                        "stream_resampled_chunks": self.stream_resampled_chunks})
+                        "stream_resampled_chunks": self.stream_resampled_chunks, "stream_scaled_chunks": self.stream_scaled_chunks})
         if self.refine:
             occ["refine"] = {"active": len(getattr(tp, "active", {})), "queued": len(getattr(tp, "queue", ())),
                              "admissions": self.refine_admissions, "max_coresident": self.refine_max_coresident,
@@ -907,6 +921,9 @@ class SpeechBatcher:
                 self._sub.pop(k, None)
         if self._jobs.pop(job.rid, None) is None:
             return
+        if job.ts_slot is not None:        # finished, failed or cancelled: its stream of the time scaler goes back to the pool
+            slot, job.ts_slot = job.ts_slot, None
+            self.chat.codec.time_scale_stream_close(slot)
         failed = isinstance(result, BaseException)
         if cancelled:
             self.cancelled += job.is_stream
@@ -1141,7 +1158,14 @@ class SpeechBatcher:
             self.stream_chunks += len(live)
             self.stream_resampled_chunks += sum(j.sample_rate is not None for j in jobs)
             self.companded += sum(j.encoding is not None for j in jobs)
-            pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **_format_kw(jobs, "sample_rates", "encodings"))
+            kw = _format_kw(jobs, "sample_rates", "encodings", "speeds")
+            if "speeds" in kw:
+                self.stream_scaled_chunks += sum(j.speed is not None for j in jobs)
+                for j in jobs:
+                    if j.speed is not None and j.ts_slot is None:
+                        j.ts_slot = self.chat.codec.time_scale_stream_open(j.speed)
+                kw["ts_streams"] = [j.ts_slot for j in jobs]
+            pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **kw)
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for job in dict.fromkeys(jobs):
                 self.pool.cancel(job.rid)

@@ -409,6 +409,40 @@ int ctts_time_scale_ragged(const float* x, const int64_t* off_in_dev, const int6
                            const int64_t* off_out_host, int32_t* path, const int64_t* path_off_dev, const int64_t* path_off_host, int32_t n_seg,
                            const float* window, int32_t num, int32_t den, void* stream);
 
+/* Time scaling of streams: the signal of a stream arrives in pushes, its output leaves in chunks, and the concatenation of the chunks (and
+ * of the path entries) is ctts_time_scale_ragged's result on the whole signal, bit for bit, however the signal is cut into pushes.
+ * With n_avail samples in and more to come, frame k >= 1 may run once need(k) = max(a_{k-1} + D + N - 1, a_k - HS + D + N - 1) <= n_avail;
+ * K(n_avail) is the largest such k (0: none).  A push that is not the last runs frames K(pos) < k <= K(pos + n_in) and emits
+ * y[HS K(pos), HS K(pos + n_in)) -- possibly nothing; the last one knows total = pos + n_in, runs the frames up to F - 1 and emits the
+ * rest up to ceil(total den / num).  After K frames nothing below base(K) = max(0, a_K - HS - D) is read again, so a slot of the state
+ * pool keeps x[base(K), n_avail) -- at most CTTS_TS_CARRY floats -- and s_K.
+ * carry: [n_slots][2][CTTS_TS_CARRY] float32 on the device, two buffers per slot: a step reads buffer `phase` and writes the other, so the
+ * caller flips `phase` after every accepted step of a slot.  state: [n_slots][CTTS_TS_STATE_INTS] int32 on the device.  A slot is fresh
+ * by its descriptor alone: at pos == 0 no carry is read, and at k_prev == 0 no state -- a reused slot never sees what it held.
+ * The descriptor table is given on the device and the host (the two must agree).  x, y and path may be null where n_x, n_y, n_path is 0.
+ * Refused before anything is launched, from the host mirror: a null pointer, n_streams outside 1 .. 1024, den != 100, num outside
+ * 50 .. 200 or num == den, a negative length, position or offset, a push outside x, a total that is neither -1 nor pos + n_in (>= 1),
+ * k_prev != K(pos), k_now other than K(pos + n_in) (F - 1 on the last push), n_out other than the plan's or a chunk outside y, path
+ * entries outside path, a phase other than 0 / 1, a carry (in front of or behind the step) above CTTS_TS_CARRY, a slot outside the pool
+ * or named twice in the call, a position within 4096 of 2^31.  Stream-ordered: one launch, one workgroup per stream. */
+#define CTTS_TS_CARRY 2560
+#define CTTS_TS_STATE_INTS 4
+typedef struct {
+  int64_t in_off, n_in;   /* the new samples: x[in_off, in_off + n_in) */
+  int64_t pos;            /* their position in the stream */
+  int64_t total;          /* the stream's length when this push is the last; -1 otherwise */
+  int64_t out_off;        /* first output float in y */
+  int64_t path_off;       /* first path entry: k_now - k_prev entries, one more (s_0, in front) when k_prev == 0 < k_now */
+  int32_t k_prev, k_now;  /* the step runs frames k_prev < k <= k_now */
+  int32_t slot, phase;    /* state slot; which of its two carry buffers holds x[base(k_prev), pos) */
+  int32_t num, den;       /* the stream's speed */
+  int32_t n_out;          /* samples this step emits */
+  int32_t reserved;
+} ctts_ts_stream;         /* 80 bytes */
+int ctts_time_scale_stream_step(const float* x, int64_t n_x, const ctts_ts_stream* st_dev, const ctts_ts_stream* st_host, int32_t n_streams,
+                                float* y, int64_t n_y, int32_t* path, int64_t n_path, float* carry, int32_t* state, int32_t n_slots,
+                                const float* window, void* stream);
+
 /* Window decode: the chunks of many streamed utterances that are due at one poll, in ONE ragged pass, each at its own position.
  * hid: a hidden-state store [n_slots][hid_cap][768] float32 (a slot pool's; slot_stride / row_stride in floats, multiples of 4, rows 16-byte
  * aligned).  A window is token rows [t_lo, t_hi) of one slot; it is decoded as one ragged segment -- its edges are sequence edges -- and
@@ -480,6 +514,26 @@ int ctts_codec_decode_windows_rate(ctts_codec* c, const float* hid, int64_t slot
                                    const ctts_rs_window* rs_host, const int32_t* sel_dev, const int32_t* sel_host, int32_t n_win,
                                    const ctts_rate* rates, int32_t n_rates, int32_t out_type, void* out, uint8_t* keep_bits, int32_t product,
                                    float keep_thr, void* workspace, size_t ws_bytes, void* stream);
+
+/* Window decode of time-scaled streams: crop -> stream step (ctts_time_scale_stream_step's kernel) -> 16-bit conversion around ONE ragged
+ * decoder pass.  win: the n_win windows to decode, as in ctts_codec_decode_windows (n_win may be 0: nothing is decoded, streams are only
+ * flushed or stepped with empty pushes).  The call emits n_conv chunks in the layout of ctts_codec_decode_windows (chunk e from element
+ * sum_{f<e} ceil8(len_f) on, its keep mask when cwin[e].keep -- of cwin only `keep` is read): crs[e].rate < 0: the 24 kHz samples
+ * [in_off, in_off + n_in) of the packed decode (window i's first sample is 256 (2 tok_i - i), tok_i the tokens of the windows in front of
+ * it); crs[e].rate >= 0: the chunk of stream descriptor ts[rate], with o_lo = 0, o_hi = its n_out (0 allowed: the push made no frame
+ * final) and out_off = its out_off: the scaled chunks lie one behind the other in chunk order, each from a multiple of 8 floats on, the path
+ * entries likewise (they stay in the workspace).  A descriptor's push x[in_off, in_off + n_in) addresses the packed decode.  The descriptors
+ * are sorted into rounds (round_off: n_rounds + 1 ascending indices, host): a stream with several chunks in the call takes them in
+ * successive rounds, one launch per round; within a round a slot appears once.  Everything ctts_codec_decode_windows and
+ * ctts_time_scale_stream_step refuse is refused here, before any launch.
+ * Workspace: ctts_codec_windows_speed_workspace_bytes(n_win, total_tokens, sum ceil8(n_out) + ceil8(path entries)); 0: bad arguments. */
+size_t ctts_codec_windows_speed_workspace_bytes(int32_t n_win, int32_t total_tokens, int64_t chunk_floats);
+int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots, int32_t hid_cap,
+                                    const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win, const ctts_window* cwin_dev,
+                                    const ctts_window* cwin_host, const ctts_rs_window* crs_dev, const ctts_rs_window* crs_host, int32_t n_conv,
+                                    const ctts_ts_stream* ts_dev, const ctts_ts_stream* ts_host, const int32_t* round_off, int32_t n_rounds,
+                                    float* carry, int32_t* state, int32_t n_ts_slots, const float* ts_window, int32_t out_type, void* out,
+                                    uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream);
 
 /* G.711 companding behind the PCM16 conversion: 16-bit PCM -> one byte per sample, mu-law (law 0) or A-law (law 1), the ITU-T G.191 map
  * (a negative sample is companded from its ones' complement, so G(~x) == G(x) ^ 0x80; chattts_amd/g711.py is the NumPy twin):

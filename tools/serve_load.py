@@ -2,7 +2,7 @@
 batching (`create_app(..., batch_slots=S)`) and once without, plus the sampling kernel's cost in a per-request pool vs a plain pool.
 Prints one JSON line.  Not a bench.py leg.
 
-    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R] [--sample-rate HZ [--encoding ulaw|alaw]]]
+    python tools/serve_load.py [--n 16] [--slots 8] [--max-new 256] [--dtype bf16] [--ragged-decode] [--stream [--repeat R] [--sample-rate HZ [--encoding ulaw|alaw]] [--speed V]]
     python tools/serve_load.py --refine [--refine-max-new 64] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
     python tools/serve_load.py --split [--split-sentences 6] [--n 16] [--slots 8] [--max-new 256] [--dtype bf16]
 
@@ -26,6 +26,8 @@ resampled on the device) in one process, the same figures, and one stream alone 
 companded on the device behind the conversion) in one process, the same figures, and one stream alone on both legs, alternating: the
 G.711 leg's first-byte p50 beside the PCM16 leg's, and the PCM16 leg's own run-to-run spread to judge the difference against.
 
+--stream --speed V: instead, the pooled streams (`batch_streams` on) at speed 1 and at V (`speed=True, stream_speed=True`: every chunk is what its
+push into the request's stream of the time scaler made final), then one stream alone on both legs, alternating, --repeat times.
 --ragged-decode: also the batched burst with `create_app(..., ragged_decode=True)` (the requests that finish in one poll decoded in one
 ragged pass) -- an A/B against the default batched burst (one decode per request), with both runs' decode-call counts.
 
@@ -93,18 +95,20 @@ def burst(chat, voices, n, batch_slots, ragged_decode=False, counts=False):
     return out
 
 
-def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app=None, rate=None, encoding=None):
+def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app=None, rate=None, encoding=None, speed=None):
     """n concurrent streamed requests, driven through the ASGI interface on one event loop (a test client would hand the body over only
     once it is complete): the clock of a request stops at its first body message that carries audio, and at its last message.
     `rate`: the streams ask for that sample rate (`stream_sample_rates`; None: 24 kHz, the body carries no rate).  `encoding`: the streams
-    ask for raw G.711 ("ulaw" / "alaw": `g711=True`, one byte per sample)"""
+    ask for raw G.711 ("ulaw" / "alaw": `g711=True`, one byte per sample).  `speed`: the streams carry that speed (`speed=True,
+    stream_speed=True`: the time scaler's path carried across their chunks); the audio seconds counted are those of the scaled stream"""
     import asyncio
     own = app is None
     if own:
         app = server.create_app(chat, voices, batch_slots=slots, ragged_decode=ragged_decode, batch_streams=batch_streams,
-                                **({} if rate is None else {"stream_sample_rates": (int(rate),)}), **({} if encoding is None else {"g711": True}))
+                                **({} if rate is None else {"stream_sample_rates": (int(rate),)}), **({} if encoding is None else {"g711": True}),
+                                **({} if speed is None else {"speed": True, "stream_speed": True}))
     names = sorted(voices)
-    more = {} if rate is None else {"sample_rate": int(rate)}
+    more = {**({} if rate is None else {"sample_rate": int(rate)}), **({} if speed is None else {"speed": float(speed)})}
 
     async def one(i, text, out):
         body = json.dumps({"input": text, "voice": names[i % len(names)], "response_format": encoding or "pcm", "stream": True, **more}).encode()
@@ -147,7 +151,8 @@ def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app
     out = dict(failed=sum(o.get("status") != 200 or "first_s" not in o for o in outs), audio_s_per_s=round(audio / wall, 2), wall_s=round(wall, 3),
                audio_s=round(audio, 2), first_byte_p50_s=pct(first, 50), first_byte_p95_s=pct(first, 95), total_p50_s=pct(total, 50),
                total_p95_s=pct(total, 95))
-    for k in ("max_coresident", "stream_decode_calls", "stream_chunks", "max_stream_group", "decode_calls", "stream_resampled_chunks", "companded"):
+    for k in ("max_coresident", "stream_decode_calls", "stream_chunks", "max_stream_group", "decode_calls", "stream_resampled_chunks", "companded",
+              "stream_scaled_chunks"):
         if k in pool:
             out[k] = pool[k]
     return out
@@ -164,6 +169,21 @@ def stream_rate_main(chat, voices, a):
     print(json.dumps(dict(metric="serve_load_stream_rate", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, sample_rate=a.sample_rate,
                           at_24000=base, at_rate=at, first_byte_p50_delta_s=round(at["first_byte_p50_s"] - base["first_byte_p50_s"], 4),
                           single_stream_first_byte_s=single)))
+
+
+def stream_speed_main(chat, voices, a):
+    """--stream --speed V: the pooled streams at speed 1 and at V in one process, then one stream alone on both, alternating"""
+    base = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode)
+    at = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode, speed=a.speed)
+    single = {"1.0": [], str(a.speed): []}
+    for _ in range(a.repeat):
+        for v in (None, a.speed):
+            single[str(v or 1.0)].append(stream_burst(chat, voices, 1, a.slots, True, a.ragged_decode, speed=v)["first_byte_p50_s"])
+    p50 = {k: round(float(np.percentile(v, 50)), 4) for k, v in single.items()}
+    print(json.dumps(dict(metric="serve_load_stream_speed", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, speed=a.speed, at_1=base,
+                          at_speed=at, single_stream_first_byte_s=single, single_stream_first_byte_p50_s=p50,
+                          single_stream_p50_delta_s=round(p50[str(a.speed)] - p50["1.0"], 4),
+                          speed_1_spread_s=round(max(single["1.0"]) - min(single["1.0"]), 4))))
 
 
 def stream_encoding_main(chat, voices, a):
@@ -183,6 +203,8 @@ def stream_encoding_main(chat, voices, a):
 
 
 def stream_main(chat, voices, a):
+    if a.speed is not None and int(round(100 * a.speed)) != 100:
+        return stream_speed_main(chat, voices, a)
     if a.encoding is not None:
         return stream_encoding_main(chat, voices, a)
     if a.sample_rate is not None and int(a.sample_rate) != server.SAMPLE_RATE:
@@ -348,6 +370,7 @@ def main():
     ap.add_argument("--sample-rate", type=int, default=None, help="--stream: the pooled streams at 24 kHz vs at this rate (resampled chunks)")
     ap.add_argument("--encoding", choices=("ulaw", "alaw"), default=None,
                     help="--stream: the pooled streams as 16-bit PCM vs as G.711 at --sample-rate (8000: the telephone's)")
+    ap.add_argument("--speed", type=float, default=None, help="--stream: the pooled streams at speed 1 vs at this speed (the scaler's path carried across chunks)")
     ap.add_argument("--repeat", type=int, default=5, help="--stream: single-stream runs per leg (run-to-run spread)")
     ap.add_argument("--refine", action="store_true", help="two-stage requests: Chat.infer serially vs the two-pool batcher")
     ap.add_argument("--refine-max-new", type=int, default=64, help="--refine: max_new_token of the refine-text pass")

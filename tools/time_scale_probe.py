@@ -6,9 +6,13 @@
   * decode    : `Chat.decode_to_pcm16(rows, ragged=True)` on 1, 8 and 64 rows of 469 tokens (10 s each) without `speed=` and with it, same
                 rows; wall time including the host side
 
+  * --stream  : instead, the streamed scaler (ctts_time_scale_stream_step, one launch): 1, 8 and 64 streams in their steady state, each
+                pushed 12 000 samples per step, at speeds 0.5, 1.25 and 2.0 -- device time of one step from events around `--reps`
+                back-to-back steps on pre-uploaded descriptor tables, after warm steps, and the frames a step runs
+
 Synthetic weights, noise input (the kernels' work does not depend on the samples).  Prints one JSON line.  Not a bench.py leg.
 
-    python tools/time_scale_probe.py [--reps 20] [--gemm f16]
+    python tools/time_scale_probe.py [--reps 20] [--gemm f16] [--stream]
 """
 from __future__ import annotations
 
@@ -61,6 +65,45 @@ def _launch_ms(codec, n_seg, speed, reps):
     return round(a.elapsed_time(b) / reps, 3), int(path_off[1]) - 1
 
 
+def _stream_step_ms(codec, n_streams, speed, reps, push=12000, warm=3):
+    """device time of one step of `n_streams` streams, each pushed `push` samples, and the frames it runs per stream"""
+    from chattts_amd import _lib
+    dev = codec.device
+    pool = codec._ts_pool()
+    assert n_streams <= int(pool["carry"].shape[0])
+    x = torch.rand(n_streams * push, device=dev) * 2 - 1
+    tabs, frames, n_out = [], [], 0
+    for r in range(warm + reps):
+        p = TS.stream_plan(speed, r * push, push, False)
+        tab = np.zeros(n_streams, _lib.TS_STREAM)
+        for i in range(n_streams):
+            tab[i] = (i * push, push, r * push, -1, i * p["n_out"], i * p["n_path"], p["k_prev"], p["k_now"], i, r & 1, p["num"], p["den"], p["n_out"], 0)
+        tabs.append((tab, torch.from_numpy(tab.view(np.uint8)).to(dev)))
+        frames.append(p["k_now"] - p["k_prev"])
+        n_out = max(n_out, n_streams * p["n_out"])
+    y = torch.empty(n_out, dtype=torch.float32, device=dev)
+    path = torch.empty(n_streams * (max(frames) + 1), dtype=torch.int32, device=dev)
+    win = codec._time_scale_window()
+    st = torch.cuda.current_stream(dev).cuda_stream
+
+    def call(r):
+        tab, tab_d = tabs[r]
+        rc = codec.lib.ctts_time_scale_stream_step(x.data_ptr(), x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), n_streams, y.data_ptr(),
+                                                   y.numel(), path.data_ptr(), path.numel(), pool["carry"].data_ptr(), pool["state"].data_ptr(),
+                                                   int(pool["carry"].shape[0]), win.data_ptr(), st)
+        assert rc == 0, codec.lib.ctts_last_error()
+    for r in range(warm):
+        call(r)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for r in range(warm, warm + reps):
+        call(r)
+    b.record()
+    b.synchronize()
+    return round(a.elapsed_time(b) / reps, 4), round(float(np.mean(frames[warm:])), 2)
+
+
 def _wall_ms(fn, reps):
     fn()
     fn()
@@ -78,11 +121,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--gemm", default="f16")
+    ap.add_argument("--stream", action="store_true", help="the streamed scaler's step instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_scale_probe needs a GPU: nothing here can be timed without one")
     dev = torch.device("cuda:0")
     sds = synthetic_all()
+    if a.stream:
+        from chattts_amd.engine import CodecEngine
+        codec = CodecEngine(sds["decoder"], sds["vocos"], dev)
+        out = dict(metric="time_scale_stream_probe", push_samples=12000, reps=a.reps, step_ms={}, frames_per_step={}, us_per_frame={})
+        for n in (1, 8, 64):
+            for speed in (0.5, 1.25, 2.0):
+                ms, frames = _stream_step_ms(codec, n, speed, a.reps)
+                out["step_ms"][f"{n}x@{speed}"] = ms
+                out["frames_per_step"][str(speed)] = frames
+                out["us_per_frame"][f"{n}x@{speed}"] = round(1e3 * ms / frames, 2)
+        print(json.dumps(out))
+        return
     chat = Chat()
     assert chat.load(state_dicts={k: sds[k] for k in ("gpt", "embed", "decoder", "vocos")}, device=dev, dtype="f32", codec_gemm=a.gemm)
     codec = chat.codec
