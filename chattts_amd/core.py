@@ -484,16 +484,10 @@ class Chat:
         speed other than 1 with the handle of its stream of the time scaler): the window's samples are pushed into that stream and
         the piece is what the step emits, converted (CodecEngine.decode_windows(speeds=)); without them today's call, argument for
         argument"""
+        kw = {k: v for k, v in (("sample_rates", sample_rates), ("encodings", encodings), ("speeds", speeds)) if v is not None}
         if speeds is not None:
-            return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, speeds=speeds, ts_streams=ts_streams,
-                                             **({} if encodings is None else {"encodings": encodings}),
-                                             **({} if sample_rates is None else {"sample_rates": sample_rates}))
-        if encodings is not None:
-            return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, encodings=encodings,
-                                             **({} if sample_rates is None else {"sample_rates": sample_rates}))
-        if sample_rates is None:
-            return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5)
-        return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, sample_rates=sample_rates)
+            kw["ts_streams"] = ts_streams
+        return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, **kw)
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
         """non-stream `Chat._infer` body for one batch (core.py:469-481, split_text=False, skip_refine_text=True),

@@ -1045,17 +1045,22 @@ extern "C" size_t ctts_codec_windows_workspace_bytes(int32_t n_win, int32_t tota
   if (n_win < 1 || total_tokens < n_win || ctts_codec_ragged_workspace_bytes(n_win, total_tokens) == 0) return 0;
   return carve_windows(nullptr, n_win, total_tokens).bytes;
 }
-extern "C" int ctts_codec_decode_windows(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots, int32_t hid_cap,
-                                         const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win, int32_t out_type, void* out,
-                                         uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
-  const char* who = "ctts_codec_decode_windows";
-  if (!c || !hid || !win_dev || !win_host || !out) return fail("%s: bad arguments", who);
-  if (n_win < 1 || n_win > 1024) return fail("%s: need 1 <= n_win <= 1024 (got %d)", who, n_win);
+// -- what the three entries below share: the checks of the host mirror and the front half, up to the packed waveforms -------------------
+static int check_out_format(const char* who, int out_type, int product, const void* out) {
   if ((out_type != 0 && out_type != 1) || (product != 0 && product != 1)) return fail("%s: out_type and product must be 0 or 1", who);
+  if ((uintptr_t)out & 15) return fail("%s: the output must be 16-byte aligned", who);
+  return 0;
+}
+static int check_store(const char* who, const float* hid, int64_t slot_stride, int64_t row_stride, int n_slots, int hid_cap) {
   if (n_slots < 1 || hid_cap < 1 || row_stride < 768 || slot_stride < (int64_t)hid_cap * row_stride || (row_stride & 3) || (slot_stride & 3) ||
-      ((uintptr_t)hid & 15) || ((uintptr_t)out & 15))
-    return fail("%s: the store must be [n_slots][hid_cap][768] floats with 16-byte aligned rows, the output 16-byte aligned", who);
-  std::vector<int32_t> tok(n_win + 1, 0);
+      ((uintptr_t)hid & 15))
+    return fail("%s: the store must be [n_slots][hid_cap][768] floats with 16-byte aligned rows", who);
+  return 0;
+}
+// the windows of the host mirror: slot, token range, capacity, crop -- everything the gather and the crop trust.  Fills tok[0 .. n_win],
+// the windows' token offsets in the packed decode
+static int check_windows(const char* who, const ctts_window* win_host, int n_win, int n_slots, int hid_cap, std::vector<int32_t>& tok) {
+  tok.assign(n_win + 1, 0);
   for (int i = 0; i < n_win; ++i) {
     const ctts_window& w = win_host[i];
     if (w.slot < 0 || w.slot >= n_slots) return fail("%s: window %d names slot %d of %d", who, i, w.slot, n_slots);
@@ -1064,20 +1069,37 @@ extern "C" int ctts_codec_decode_windows(ctts_codec* c, const float* hid, int64_
     const int64_t n_samples = 256 * (2 * (int64_t)(w.t_hi - w.t_lo) - 1);
     if (w.c_lo < 0 || w.c_hi <= w.c_lo || w.c_hi > n_samples)
       return fail("%s: window %d crops samples %d -> %d outside its %lld samples", who, i, w.c_lo, w.c_hi, (long long)n_samples);
-    if (w.keep && !keep_bits) return fail("%s: window %d asks for a keep mask but keep_bits is null", who, i);
     tok[i + 1] = tok[i] + (w.t_hi - w.t_lo);
     if (tok[i + 1] > (1 << 28)) return fail("%s: too many tokens", who);
   }
+  return 0;
+}
+// gather -> DVAE -> Vocos over the checked table: every window is a ragged segment, its edges are sequence edges.  Leaves ws.wav filled
+static int decode_windows_front(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, const ctts_window* win_dev, int n_win,
+                                const std::vector<int32_t>& tok, const WindowsWs& ws, void* workspace, void* stream) {
+  {
+    CttsDeviceGuard dg(stream);
+    CK(launch_gather_windows(hid, slot_stride, row_stride, (const CodecWindow*)win_dev, n_win, tok[n_win], ws.hid, ws.tok_off, (hipStream_t)stream));
+  }
+  if (ctts_dvae_decode_ragged(c, ws.hid, ws.tok_off, tok.data(), n_win, ws.mel, workspace, ws.ragged_bytes, stream)) return -1;
+  return ctts_vocos_decode_ragged(c, ws.mel, ws.tok_off, tok.data(), n_win, ws.wav, workspace, ws.ragged_bytes, stream);
+}
+
+extern "C" int ctts_codec_decode_windows(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots, int32_t hid_cap,
+                                         const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win, int32_t out_type, void* out,
+                                         uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
+  const char* who = "ctts_codec_decode_windows";
+  if (!c || !hid || !win_dev || !win_host || !out) return fail("%s: bad arguments", who);
+  if (n_win < 1 || n_win > 1024) return fail("%s: need 1 <= n_win <= 1024 (got %d)", who, n_win);
+  if (check_out_format(who, out_type, product, out) || check_store(who, hid, slot_stride, row_stride, n_slots, hid_cap)) return -1;
+  std::vector<int32_t> tok;
+  if (check_windows(who, win_host, n_win, n_slots, hid_cap, tok)) return -1;
+  for (int i = 0; i < n_win; ++i)
+    if (win_host[i].keep && !keep_bits) return fail("%s: window %d asks for a keep mask but keep_bits is null", who, i);
   const int T = tok[n_win];
   if (!workspace || ws_bytes < ctts_codec_windows_workspace_bytes(n_win, T)) return fail("codec workspace too small");
   WindowsWs ws = carve_windows(workspace, n_win, T);
-  {
-    CttsDeviceGuard dg(stream);
-    CK(launch_gather_windows(hid, slot_stride, row_stride, (const CodecWindow*)win_dev, n_win, T, ws.hid, ws.tok_off, (hipStream_t)stream));
-  }
-  // the ragged stages, unchanged: every window is a segment, its edges are sequence edges
-  if (ctts_dvae_decode_ragged(c, ws.hid, ws.tok_off, tok.data(), n_win, ws.mel, workspace, ws.ragged_bytes, stream)) return -1;
-  if (ctts_vocos_decode_ragged(c, ws.mel, ws.tok_off, tok.data(), n_win, ws.wav, workspace, ws.ragged_bytes, stream)) return -1;
+  if (decode_windows_front(c, hid, slot_stride, row_stride, win_dev, n_win, tok, ws, workspace, stream)) return -1;
   CttsDeviceGuard dg(stream);
   CK(launch_crop_pcm16_windows(ws.wav, (const CodecWindow*)win_dev, n_win, out_type == 0 ? 1 : 0, product, keep_thr, out, keep_bits,
                                (hipStream_t)stream));
@@ -1154,25 +1176,17 @@ extern "C" int ctts_codec_decode_windows_rate(ctts_codec* c, const float* hid, i
   if (!c || !hid || !win_dev || !win_host || !rs_dev || !rs_host || !sel_dev || !sel_host || !out) return fail("%s: bad arguments", who);
   if (n_win < 1 || n_win > 1024) return fail("%s: need 1 <= n_win <= 1024 (got %d)", who, n_win);
   if (n_rates < 0 || n_rates > n_win || (n_rates > 0 && !rates)) return fail("%s: need 0 <= n_rates <= n_win and the rate table", who);
-  if ((out_type != 0 && out_type != 1) || (product != 0 && product != 1)) return fail("%s: out_type and product must be 0 or 1", who);
-  if (n_slots < 1 || hid_cap < 1 || row_stride < 768 || slot_stride < (int64_t)hid_cap * row_stride || (row_stride & 3) || (slot_stride & 3) ||
-      ((uintptr_t)hid & 15) || ((uintptr_t)out & 15))
-    return fail("%s: the store must be [n_slots][hid_cap][768] floats with 16-byte aligned rows, the output 16-byte aligned", who);
+  if (check_out_format(who, out_type, product, out) || check_store(who, hid, slot_stride, row_stride, n_slots, hid_cap)) return -1;
   for (int r = 0; r < n_rates; ++r)
     if (check_rs_pair(who, rates[r].taps, rates[r].L, rates[r].M, rates[r].K)) return -1;
-  std::vector<int32_t> tok(n_win + 1, 0);
+  std::vector<int32_t> tok;
+  if (check_windows(who, win_host, n_win, n_slots, hid_cap, tok)) return -1;
   std::vector<int> per_rate(n_rates, 0);
   std::vector<long long> longest(n_rates, 0);
   long long chunk_floats = 0;
   for (int i = 0; i < n_win; ++i) {
     const ctts_window& w = win_host[i];
     const ctts_rs_window& r = rs_host[i];
-    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: window %d names slot %d of %d", who, i, w.slot, n_slots);
-    if (w.t_lo < 0 || w.t_hi <= w.t_lo) return fail("%s: window %d is empty (tokens %d -> %d)", who, i, w.t_lo, w.t_hi);
-    if (w.t_hi > hid_cap) return fail("%s: window %d ends at token %d beyond the slot's capacity %d", who, i, w.t_hi, hid_cap);
-    const int64_t n_samples = 256 * (2 * (int64_t)(w.t_hi - w.t_lo) - 1);
-    if (w.c_lo < 0 || w.c_hi <= w.c_lo || w.c_hi > n_samples)
-      return fail("%s: window %d crops samples %d -> %d outside its %lld samples", who, i, w.c_lo, w.c_hi, (long long)n_samples);
     if (w.keep && !keep_bits) return fail("%s: window %d asks for a keep mask but keep_bits is null", who, i);
     const int64_t start = 256 * (2 * (int64_t)tok[i] - i);       // the window's first sample in the packed decode
     if (r.rate >= n_rates) return fail("%s: window %d names rate %d of %d", who, i, r.rate, n_rates);
@@ -1190,8 +1204,6 @@ extern "C" int ctts_codec_decode_windows_rate(ctts_codec* c, const float* hid, i
       ++per_rate[r.rate];
       longest[r.rate] = std::max(longest[r.rate], n);
     }
-    tok[i + 1] = tok[i] + (w.t_hi - w.t_lo);
-    if (tok[i + 1] > (1 << 28)) return fail("%s: too many tokens", who);
   }
   // sel lists the resampled windows rate by rate, each once: one launch per distinct rate converts its run of the list
   for (int r = 0, q = 0; r < n_rates; ++r)
@@ -1205,12 +1217,7 @@ extern "C" int ctts_codec_decode_windows_rate(ctts_codec* c, const float* hid, i
     return fail("codec workspace too small");
   WindowsWs ws = carve_windows(workspace, n_win, T);
   float* chunks = (float*)((char*)workspace + ws.bytes);
-  {
-    CttsDeviceGuard dg(stream);
-    CK(launch_gather_windows(hid, slot_stride, row_stride, (const CodecWindow*)win_dev, n_win, T, ws.hid, ws.tok_off, (hipStream_t)stream));
-  }
-  if (ctts_dvae_decode_ragged(c, ws.hid, ws.tok_off, tok.data(), n_win, ws.mel, workspace, ws.ragged_bytes, stream)) return -1;
-  if (ctts_vocos_decode_ragged(c, ws.mel, ws.tok_off, tok.data(), n_win, ws.wav, workspace, ws.ragged_bytes, stream)) return -1;
+  if (decode_windows_front(c, hid, slot_stride, row_stride, win_dev, n_win, tok, ws, workspace, stream)) return -1;
   CttsDeviceGuard dg(stream);
   int done = 0;
   for (int r = 0; r < n_rates; ++r) {
@@ -1317,23 +1324,9 @@ extern "C" int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, 
   const int n_ts = round_off[n_rounds];
   if (n_ts > n_conv) return fail("%s: %d stream descriptors for %d chunks", who, n_ts, n_conv);
   if (n_ts_slots < 1) return fail("%s: the state pool has no slot", who);
-  if ((out_type != 0 && out_type != 1) || (product != 0 && product != 1)) return fail("%s: out_type and product must be 0 or 1", who);
-  if ((uintptr_t)out & 15) return fail("%s: the output must be 16-byte aligned", who);
-  if (n_win && (n_slots < 1 || hid_cap < 1 || row_stride < 768 || slot_stride < (int64_t)hid_cap * row_stride || (row_stride & 3) || (slot_stride & 3) ||
-                ((uintptr_t)hid & 15)))
-    return fail("%s: the store must be [n_slots][hid_cap][768] floats with 16-byte aligned rows", who);
-  std::vector<int32_t> tok(n_win + 1, 0);
-  for (int i = 0; i < n_win; ++i) {
-    const ctts_window& w = win_host[i];
-    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: window %d names slot %d of %d", who, i, w.slot, n_slots);
-    if (w.t_lo < 0 || w.t_hi <= w.t_lo) return fail("%s: window %d is empty (tokens %d -> %d)", who, i, w.t_lo, w.t_hi);
-    if (w.t_hi > hid_cap) return fail("%s: window %d ends at token %d beyond the slot's capacity %d", who, i, w.t_hi, hid_cap);
-    const int64_t n_samples = 256 * (2 * (int64_t)(w.t_hi - w.t_lo) - 1);
-    if (w.c_lo < 0 || w.c_hi <= w.c_lo || w.c_hi > n_samples)
-      return fail("%s: window %d crops samples %d -> %d outside its %lld samples", who, i, w.c_lo, w.c_hi, (long long)n_samples);
-    tok[i + 1] = tok[i] + (w.t_hi - w.t_lo);
-    if (tok[i + 1] > (1 << 28)) return fail("%s: too many tokens", who);
-  }
+  if (check_out_format(who, out_type, product, out) || (n_win && check_store(who, hid, slot_stride, row_stride, n_slots, hid_cap))) return -1;
+  std::vector<int32_t> tok;
+  if (check_windows(who, win_host, n_win, n_slots, hid_cap, tok)) return -1;
   const int T = tok[n_win];
   const long long n_x = n_win ? 256 * (2 * (long long)T - n_win) : 0;
   // what chunk e of the output is: a 24 kHz crop of the packed decode (rate < 0), or the chunk of stream descriptor `rate`
@@ -1369,12 +1362,7 @@ extern "C" int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, 
     WindowsWs ws = carve_windows(workspace, n_win, T);
     wav = ws.wav;
     chunks = (float*)((char*)workspace + ws.bytes);
-    {
-      CttsDeviceGuard dg(stream);
-      CK(launch_gather_windows(hid, slot_stride, row_stride, (const CodecWindow*)win_dev, n_win, T, ws.hid, ws.tok_off, (hipStream_t)stream));
-    }
-    if (ctts_dvae_decode_ragged(c, ws.hid, ws.tok_off, tok.data(), n_win, ws.mel, workspace, ws.ragged_bytes, stream)) return -1;
-    if (ctts_vocos_decode_ragged(c, ws.mel, ws.tok_off, tok.data(), n_win, ws.wav, workspace, ws.ragged_bytes, stream)) return -1;
+    if (decode_windows_front(c, hid, slot_stride, row_stride, win_dev, n_win, tok, ws, workspace, stream)) return -1;
   }
   int32_t* path = (int32_t*)(chunks + chunk_floats);
   CttsDeviceGuard dg(stream);

@@ -766,22 +766,14 @@ hipError_t launch_gather_windows(const float* hid, long long slot_stride, long l
   return hipGetLastError();
 }
 
-// One workgroup per window: the peak over the CROPPED samples only, then the conversion of ctts_float_to_int16 (per_row) -- or, out_f32, the
-// crop alone.  Window i's samples go to element out_off[i] = sum_{j<i} ceil8(c_hi_j - c_lo_j) of the output (every window starts on a
-// 16-byte boundary of the int16 output; the pad samples are written as zeros) and, when win[i].keep, its mask |x| > keep_thr to byte
-// out_off[i] / 8 of keep (np.packbits order) -- the layout of float_to_int16_ragged's masks.  A thread converts 8 samples: two 16-byte
-// loads where the crop starts on a 16-byte boundary (every chunk of the streaming schedule does), one 16-byte store.
-__global__ __launch_bounds__(1024) void crop_pcm16_windows_k(const float* __restrict__ wav, const CodecWindow* __restrict__ win, int out_f32,
-                                                             int product, float keep_thr, void* __restrict__ out, uint8_t* __restrict__ keep) {
+// The conversion both window kernels end in: one workgroup's chunk, n floats at x, goes to element oo (a multiple of 8) of the output --
+// int16 through pcm16_scale / pcm16_sample under ONE peak over the chunk's own samples, or, out_f32, the floats themselves; the pad up to
+// the next multiple of 8 is written as zeros.  With keep_flag (and a mask buffer) the chunk's mask |x| > keep_thr goes to byte oo / 8 of
+// keep (np.packbits order) -- the layout of float_to_int16_ragged's masks.  A thread converts 8 samples: two 16-byte loads where the
+// chunk starts on a 16-byte boundary (every chunk of the streaming schedule does), one 16-byte store.  1024 threads.
+__device__ __forceinline__ void chunk_pcm16_body(const float* __restrict__ x, int n, long long oo, int keep_flag, int out_f32, int product,
+                                                 float keep_thr, void* __restrict__ out, uint8_t* __restrict__ keep) {
   __shared__ unsigned red[16];
-  const int w = blockIdx.x;
-  long long tok = 0, oo = 0;
-  for (int j = 0; j < w; ++j) {      // wave-uniform: scalar loads
-    tok += win[j].t_hi - win[j].t_lo;
-    oo += (long long)((win[j].c_hi - win[j].c_lo + 7) & ~7);
-  }
-  const int n = win[w].c_hi - win[w].c_lo;
-  const float* x = wav + HOP * (2 * tok - w) + win[w].c_lo;
   const int groups = (n + 7) >> 3;
   const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   auto load8 = [&](int g, float (&v)[8]) {
@@ -810,7 +802,7 @@ __global__ __launch_bounds__(1024) void crop_pcm16_windows_k(const float* __rest
     for (int k = 0; k < 16; ++k) m = max(m, red[k]);
     am = pcm16_scale(__uint_as_float(m));
   }
-  const bool mask = keep != nullptr && win[w].keep != 0;
+  const bool mask = keep != nullptr && keep_flag != 0;
   for (int g = threadIdx.x; g < groups; g += 1024) {
     float v[8];
     load8(g, v);
@@ -832,6 +824,22 @@ __global__ __launch_bounds__(1024) void crop_pcm16_windows_k(const float* __rest
       keep[(oo >> 3) + g] = (uint8_t)bits;
     }
   }
+}
+
+// One workgroup per window: the peak over the CROPPED samples only, then the conversion of ctts_float_to_int16 (per_row) -- or, out_f32, the
+// crop alone (chunk_pcm16_body).  Window i's samples go to element out_off[i] = sum_{j<i} ceil8(c_hi_j - c_lo_j) of the output (every
+// window starts on a 16-byte boundary of the int16 output) and, when win[i].keep, its mask to byte out_off[i] / 8 of keep.
+__global__ __launch_bounds__(1024) void crop_pcm16_windows_k(const float* __restrict__ wav, const CodecWindow* __restrict__ win, int out_f32,
+                                                             int product, float keep_thr, void* __restrict__ out, uint8_t* __restrict__ keep) {
+  const int w = blockIdx.x;
+  long long tok = 0, oo = 0;
+  for (int j = 0; j < w; ++j) {      // wave-uniform: scalar loads
+    tok += win[j].t_hi - win[j].t_lo;
+    oo += (long long)((win[j].c_hi - win[j].c_lo + 7) & ~7);
+  }
+  const int n = win[w].c_hi - win[w].c_lo;
+  const float* x = wav + HOP * (2 * tok - w) + win[w].c_lo;
+  chunk_pcm16_body(x, n, oo, win[w].keep, out_f32, product, keep_thr, out, keep);
 }
 hipError_t launch_crop_pcm16_windows(const float* wav, const CodecWindow* win, int n_win, int out_f32, int product, float keep_thr, void* out,
                                      uint8_t* keep, hipStream_t st) {
@@ -842,68 +850,17 @@ hipError_t launch_crop_pcm16_windows(const float* wav, const CodecWindow* win, i
 
 // crop_pcm16_windows_k with the chunk addressed through a second table (ctts_codec_decode_windows_rate): window w's samples are the resampled
 // chunk at chunks + rs[w].out_off (rs[w].rate >= 0; rs[w].o_hi - rs[w].o_lo of them) or the 24 kHz crop at wav + rs[w].in_off (rate < 0;
-// rs[w].n_in).  Everything else -- the output layout, one peak per window over its own samples, pcm16_scale / pcm16_sample, the keep
-// mask -- is that kernel's, so a 24 kHz window among resampled ones gets the bytes it gets there.
+// rs[w].n_in).  Everything else is chunk_pcm16_body too, so a 24 kHz window among resampled ones gets the bytes it gets there.
 __global__ __launch_bounds__(1024) void chunks_pcm16_k(const float* __restrict__ wav, const float* __restrict__ chunks,
                                                        const CodecWindow* __restrict__ win, const RsWindow* __restrict__ rs, int out_f32,
                                                        int product, float keep_thr, void* __restrict__ out, uint8_t* __restrict__ keep) {
-  __shared__ unsigned red[16];
   const int w = blockIdx.x;
   auto len = [&](int j) { return rs[j].rate >= 0 ? rs[j].o_hi - rs[j].o_lo : rs[j].n_in; };
   long long oo = 0;
   for (int j = 0; j < w; ++j) oo += (len(j) + 7) & ~7ll;      // wave-uniform: scalar loads
   const int n = (int)len(w);
   const float* x = rs[w].rate >= 0 ? chunks + rs[w].out_off : wav + rs[w].in_off;
-  const int groups = (n + 7) >> 3;
-  const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  auto load8 = [&](int g, float (&v)[8]) {
-    if (vec && g * 8 + 8 <= n) {
-      const float4 a = reinterpret_cast<const float4*>(x)[2 * g], b = reinterpret_cast<const float4*>(x)[2 * g + 1];
-      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = g * 8 + e < n ? x[g * 8 + e] : 0.0f;
-    }
-  };
-  long long am = 0;
-  if (!out_f32) {
-    unsigned m = 0;
-    for (int g = threadIdx.x; g < groups; g += 1024) {
-      float v[8];
-      load8(g, v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) m = max(m, __float_as_uint(v[e]) & 0x7fffffffu);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) m = max(m, red[k]);
-    am = pcm16_scale(__uint_as_float(m));
-  }
-  const bool mask = keep != nullptr && win[w].keep != 0;
-  for (int g = threadIdx.x; g < groups; g += 1024) {
-    float v[8];
-    load8(g, v);
-    if (out_f32) {
-      float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + oo) + 2 * g;
-      o[0] = make_float4(v[0], v[1], v[2], v[3]);
-      o[1] = make_float4(v[4], v[5], v[6], v[7]);
-    } else {
-      union { u128 q; int16_t s[8]; } p;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) p.s[e] = pcm16_sample(v[e], am, product);
-      reinterpret_cast<u128*>(reinterpret_cast<int16_t*>(out) + oo)[g] = p.q;
-    }
-    if (mask) {
-      unsigned bits = 0;
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if (g * 8 + e < n && fabsf(v[e]) > keep_thr) bits |= 0x80u >> e;
-      keep[(oo >> 3) + g] = (uint8_t)bits;
-    }
-  }
+  chunk_pcm16_body(x, n, oo, win[w].keep, out_f32, product, keep_thr, out, keep);
 }
 hipError_t launch_chunks_pcm16(const float* wav, const float* chunks, const CodecWindow* win, const RsWindow* rs, int n_win, int out_f32,
                                int product, float keep_thr, void* out, uint8_t* keep, hipStream_t st) {

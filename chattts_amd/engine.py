@@ -1921,17 +1921,18 @@ class CodecEngine:
         stream.  Several windows of one stream are taken in the order given.  Windows at speed 1 return the bytes they return
         without `speeds`.  A speed together with a rate other than 24000 is refused: resampling the scaled stream would need its
         history and a look-ahead carried too."""
+        q = None
         if speeds is not None:
             if len(speeds) != len(windows):
                 raise ValueError("decode_windows: one speed per window")
             q = [TS.quantize(v) for v in speeds]
-            if any(n != d for n, d in q):
-                if sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
-                    raise ValueError("decode_windows: a streamed speed goes with 24000 Hz only (resampling the scaled stream would need "
-                                     "its history and a look-ahead carried too)")
-                if ts_streams is None or len(ts_streams) != len(windows):
-                    raise ValueError("decode_windows: speeds need ts_streams, one entry per window")
-                return self._decode_windows_speed(store, windows, q, ts_streams, pcm16, keep_thr, product, encodings)
+            if all(n == d for n, d in q):
+                q = None
+            elif sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
+                raise ValueError("decode_windows: a streamed speed goes with 24000 Hz only (resampling the scaled stream would need "
+                                 "its history and a look-ahead carried too)")
+            elif ts_streams is None or len(ts_streams) != len(windows):
+                raise ValueError("decode_windows: speeds need ts_streams, one entry per window")
         laws = None
         if encodings is not None:
             if len(encodings) != len(windows):
@@ -1940,24 +1941,21 @@ class CodecEngine:
                 if not pcm16:
                     raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
                 laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
+        if q is not None:
+            return self._decode_windows_speed(store, windows, q, ts_streams, pcm16, keep_thr, product, laws)
         if sample_rates is not None:
             if len(sample_rates) != len(windows):
                 raise ValueError("decode_windows: one sample rate per window")
             if any(int(r) != self.SAMPLE_RATE for r in sample_rates):
                 return self._decode_windows_rate(store, windows, [int(r) for r in sample_rates], pcm16, keep_thr, product, laws)
-        assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
-        S, cap = int(store.size(0)), int(store.size(1))
-        dt = np.int16 if pcm16 else np.float32
+        S, cap = self._windows_store(store)
         out: list = [None] * len(windows)
         rows, live = [], []
         for i, w in enumerate(windows):
-            slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
-            tail = len(w) > 4 and bool(w[4]) and keep_thr is not None
-            if not (0 <= slot < S and 0 <= Tn <= cap):
-                raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
-            win = window_for_samples(Tn, s_lo, VOCOS.hop * (2 * Tn - 1) if s_hi is None else s_hi)
+            slot, Tn, s_lo, hi, tail = self._window_fields(i, w, S, cap, keep_thr)
+            win = window_for_samples(Tn, s_lo, hi)
             if win is None:
-                out[i] = np.zeros((0,), np.uint8 if laws is not None and laws[i] >= 0 else dt)
+                out[i] = self._empty_window(i, pcm16, laws)
                 continue
             rows.append((slot, *win, int(tail), 0, 0))
             live.append(i)
@@ -1965,46 +1963,78 @@ class CodecEngine:
             return out
         tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]: slot, t_lo, t_hi, c_lo, c_hi, keep, 0, 0
         n = (tab[:, 4] - tab[:, 3]).astype(np.int64)
-        off = np.zeros(len(live) + 1, np.int64)
-        np.cumsum((n + 7) // 8 * 8, out=off[1:])                             # every window starts on a multiple of 8 samples
-        esz = 2 if pcm16 else 4
-        n_out, any_keep = int(off[-1]) * esz, bool(tab[:, 5].any())
-        n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if any_keep else 0
-        n_g = (int(off[-1]) + 15) // 16 * 16 if laws is not None else 0
-        cur = torch.cuda.current_stream(self.device)
-        buf = torch.empty((n_out + n_g + n_keep,), dtype=torch.uint8, device=self.device)      # samples | (companded bytes) | keep masks: one copy
+        lay = self._windows_layout(n, tab[:, 5], pcm16, laws)
         tab_d = torch.from_numpy(tab).to(self.device)
-        ws, nws = self._ws_bytes(self.lib.ctts_codec_windows_workspace_bytes(len(live), int((tab[:, 2] - tab[:, 1]).sum())))
+        cur, tail_args = self._windows_call_tail(lay, tab[:, 5], pcm16, product, keep_thr,
+                                                 self.lib.ctts_codec_windows_workspace_bytes(len(live), int((tab[:, 2] - tab[:, 1]).sum())))
         _lib.check(self.lib.ctts_codec_decode_windows(self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap,
-                                                      tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(live), 1 if pcm16 else 0,
-                                                      buf.data_ptr(), buf.data_ptr() + n_out + n_g if any_keep else None,
-                                                      {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws,
-                                                      cur.cuda_stream), "ctts_codec_decode_windows")
+                                                      tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(live), *tail_args),
+                   "ctts_codec_decode_windows")
         tab_d.record_stream(cur)
-        return self._windows_to_host(buf, n_out, n_g, off, n, tab[:, 5], live, None if laws is None else [laws[i] for i in live], dt, out)
+        return self._windows_finish(lay, n, tab[:, 5], live, laws, pcm16, out)
+
+    # -- what the three paths of `decode_windows` share: the prologue (store, one window's fields, an empty result, the crops' places in the
+    # packed decode), the output layout, the tail of the C call and the epilogue.  A further variant builds its own tables between them
+    @staticmethod
+    def _windows_store(store: torch.Tensor):
+        assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
+        return int(store.size(0)), int(store.size(1))
+
+    @staticmethod
+    def _window_fields(i: int, w, S: int, cap: int, keep_thr: Optional[float]):
+        """window i of the list -> slot, Tn, s_lo, hi (s_hi, or the end of the prefix's decode), tail (marked as one AND a `keep_thr`
+        given: the window is stripped)"""
+        slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
+        if not (0 <= slot < S and 0 <= Tn <= cap):
+            raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
+        return slot, Tn, s_lo, VOCOS.hop * (2 * Tn - 1) if s_hi is None else int(s_hi), len(w) > 4 and bool(w[4]) and keep_thr is not None
+
+    @staticmethod
+    def _empty_window(i: int, pcm16: bool, laws):
+        return np.zeros((0,), np.uint8 if laws is not None and laws[i] >= 0 else np.int16 if pcm16 else np.float32)
+
+    @staticmethod
+    def _packed_crops(tab: np.ndarray):
+        """ctts_window rows -> (tok, start): the windows' token offsets [n + 1] in the packed decode, each crop's first sample in it"""
+        tok = np.zeros(len(tab) + 1, np.int64)
+        np.cumsum(tab[:, 2] - tab[:, 1], out=tok[1:])
+        return tok, VOCOS.hop * (2 * tok[:-1] - np.arange(len(tab))) + tab[:, 3]
+
+    def _windows_layout(self, n, keep, pcm16: bool, laws):
+        """the output of one call from its chunks' lengths `n` and keep flags -> (off, n_out, n_g, n_keep, buf): every chunk starts on a
+        multiple of 8 samples (`off`, in elements); `buf` = samples (n_out bytes) | companded bytes (n_g, with `laws`) | keep masks
+        (n_keep, when any chunk is stripped), so ONE copy brings all of it; at least 16 bytes (a call whose chunks are all empty)"""
+        off = np.zeros(len(n) + 1, np.int64)
+        np.cumsum((n + 7) // 8 * 8, out=off[1:])
+        n_out = int(off[-1]) * (2 if pcm16 else 4)
+        n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if keep.any() else 0
+        n_g = (int(off[-1]) + 15) // 16 * 16 if laws is not None else 0
+        return off, n_out, n_g, n_keep, torch.empty((max(16, n_out + n_g + n_keep),), dtype=torch.uint8, device=self.device)
+
+    def _windows_call_tail(self, lay, keep, pcm16: bool, product: str, keep_thr: Optional[float], ws_bytes: int):
+        """the current stream and the arguments every window entry ends in: out_type, out, keep_bits, product, keep_thr, workspace, its
+        size, stream"""
+        _, n_out, n_g, _, buf = lay
+        ws, nws = self._ws_bytes(ws_bytes)
+        cur = torch.cuda.current_stream(self.device)
+        return cur, (1 if pcm16 else 0, buf.data_ptr(), buf.data_ptr() + n_out + n_g if keep.any() else None, {"f64": 0, "f32": 1}[product],
+                     float(keep_thr or 0.0), ws.data_ptr(), nws, cur.cuda_stream)
+
+    def _windows_finish(self, lay, n, keep, live, laws, pcm16: bool, out: list) -> list:
+        off, n_out, n_g, n_keep, buf = lay
+        return self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, off, n, keep, live, None if laws is None else [laws[i] for i in live],
+                                     np.int16 if pcm16 else np.float32, out)
 
     def _decode_windows_speed(self, store: torch.Tensor, windows, q, ts_streams, pcm16: bool, keep_thr: Optional[float], product: str,
-                              encodings=None):
+                              laws=None):
         """`decode_windows` with at least one window at another speed than 1 (q: the windows' (num, den))"""
-        laws = None
-        if encodings is not None:
-            if len(encodings) != len(windows):
-                raise ValueError("decode_windows: one encoding per window")
-            if any(G711.check_encoding(e) is not None for e in encodings):
-                if not pcm16:
-                    raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
-                laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
-        assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
-        S, cap = int(store.size(0)), int(store.size(1))
-        dt = np.int16 if pcm16 else np.float32
+        S, cap = self._windows_store(store)
         out: list = [None] * len(windows)
         recs = self._ts_pool()["rec"]
-        rows, crops, conv, pushes = [], [], [], []     # decode windows; their crops; (window, decode row or None, push or None); stream pushes
+        rows, conv, pushes = [], [], []     # decode windows; (window, decode row or None, push or None, keep); stream pushes
         for i, w in enumerate(windows):
-            slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
-            last = len(w) > 4 and bool(w[4])
-            if not (0 <= slot < S and 0 <= Tn <= cap):
-                raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
+            slot, Tn, s_lo, hi, keep = self._window_fields(i, w, S, cap, keep_thr)
+            last = len(w) > 4 and bool(w[4])               # ends the stream, with or without a `keep_thr`
             scaled = q[i][0] != q[i][1]
             if scaled:
                 h = ts_streams[i]
@@ -2012,9 +2042,9 @@ class CodecEngine:
                     raise ValueError(f"decode_windows: window {i} at speed {q[i][0]}/{q[i][1]} needs an open stream of that speed")
             elif ts_streams[i] is not None:
                 raise ValueError(f"decode_windows: window {i} is at speed 1 but names a stream")
-            win = window_for_samples(Tn, s_lo, VOCOS.hop * (2 * Tn - 1) if s_hi is None else s_hi)
+            win = window_for_samples(Tn, s_lo, hi)
             if win is None and not scaled:
-                out[i] = np.zeros((0,), np.uint8 if laws is not None and laws[i] >= 0 else dt)
+                out[i] = self._empty_window(i, pcm16, laws)
                 continue
             k = None
             if win is not None:
@@ -2022,11 +2052,9 @@ class CodecEngine:
                 rows.append((slot, *win, 0, 0, 0))
             if scaled:
                 pushes.append([int(ts_streams[i]), k, 0, last])
-            conv.append((i, k, len(pushes) - 1 if scaled else None, int(last and keep_thr is not None)))
+            conv.append((i, k, len(pushes) - 1 if scaled else None, int(keep)))
         tab = np.ascontiguousarray(np.array(rows, dtype=np.int32).reshape(-1, 8))       # ctts_window[n_win]: what is decoded
-        tok = np.zeros(len(rows) + 1, np.int64)
-        np.cumsum(tab[:, 2] - tab[:, 1], out=tok[1:])
-        start = VOCOS.hop * (2 * tok[:-1] - np.arange(len(rows))) + tab[:, 3]           # the crops in the packed decode
+        tok, start = self._packed_crops(tab)
         width = (tab[:, 4] - tab[:, 3]).astype(np.int64)
         for p in pushes:
             p[1], p[2] = (0, 0) if p[1] is None else (int(start[p[1]]), int(width[p[1]]))
@@ -2048,33 +2076,24 @@ class CodecEngine:
                 chunk += (m + 7) // 8 * 8
                 paths += n_path[r]
         n = np.where(rtab["rate"] >= 0, rtab["o_hi"], rtab["n_in"]).astype(np.int64)
-        off = np.zeros(len(conv) + 1, np.int64)
-        np.cumsum((n + 7) // 8 * 8, out=off[1:])                             # every chunk starts on a multiple of 8 samples
-        esz = 2 if pcm16 else 4
-        n_out, any_keep = int(off[-1]) * esz, bool(ctab[:, 5].any())
-        n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if any_keep else 0
-        n_g = (int(off[-1]) + 15) // 16 * 16 if laws is not None else 0
-        cur = torch.cuda.current_stream(self.device)
-        buf = torch.empty((max(16, n_out + n_g + n_keep),), dtype=torch.uint8, device=self.device)   # samples | (companded bytes) | keep masks: one copy
+        lay = self._windows_layout(n, ctab[:, 5], pcm16, laws)
         parts = [tab.view(np.uint8).reshape(-1), ctab.view(np.uint8).reshape(-1), rtab.view(np.uint8), ts.view(np.uint8)]
         blob_d = torch.from_numpy(np.concatenate(parts)).to(self.device)                 # one upload: the four tables
         p0 = blob_d.data_ptr()
         p1, p2 = p0 + parts[0].nbytes, p0 + parts[0].nbytes + parts[1].nbytes
         p3 = p2 + parts[2].nbytes
         pool = self._ts_pool()
-        ws, nws = self._ws_bytes(self.lib.ctts_codec_windows_speed_workspace_bytes(len(rows), int(tok[-1]), chunk + (paths + 7) // 8 * 8))
+        cur, tail_args = self._windows_call_tail(lay, ctab[:, 5], pcm16, product, keep_thr, self.lib.ctts_codec_windows_speed_workspace_bytes(
+            len(rows), int(tok[-1]), chunk + (paths + 7) // 8 * 8))
         _lib.check(self.lib.ctts_codec_decode_windows_speed(
             self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap, p0 if len(rows) else None,
             tab.ctypes.data_as(C.c_void_p) if len(rows) else None, len(rows), p1, ctab.ctypes.data_as(C.c_void_p), p2, rtab.ctypes.data_as(C.c_void_p),
             len(conv), p3, ts.ctypes.data_as(C.c_void_p), round_off.ctypes.data_as(C.c_void_p), len(round_off) - 1, pool["carry"].data_ptr(),
-            pool["state"].data_ptr(), int(pool["carry"].shape[0]), self._time_scale_window().data_ptr(), 1 if pcm16 else 0, buf.data_ptr(),
-            buf.data_ptr() + n_out + n_g if any_keep else None, {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws,
-            cur.cuda_stream), "ctts_codec_decode_windows_speed")
+            pool["state"].data_ptr(), int(pool["carry"].shape[0]), self._time_scale_window().data_ptr(), *tail_args),
+            "ctts_codec_decode_windows_speed")
         blob_d.record_stream(cur)
         pool["rec"].update(commit)
-        live = [c[0] for c in conv]
-        return self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, off, n, ctab[:, 5], live, None if laws is None else [laws[i] for i in live],
-                                     dt, out)
+        return self._windows_finish(lay, n, ctab[:, 5], [c[0] for c in conv], laws, pcm16, out)
 
     def _windows_to_host(self, buf: torch.Tensor, n_out: int, n_g: int, off, n, keep, live, laws, dt, out: list) -> list:
         """the end of `decode_windows`: `buf` = samples (n_out bytes) | companded bytes (n_g, 0 without `laws`) | keep masks.  The
@@ -2128,19 +2147,13 @@ class CodecEngine:
 
     def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str, laws=None):
         """`decode_windows` with at least one window at another rate than 24 kHz"""
-        assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
-        S, cap = int(store.size(0)), int(store.size(1))
-        dt = np.int16 if pcm16 else np.float32
+        S, cap = self._windows_store(store)
         out: list = [None] * len(windows)
         plans, pairs = {}, {}              # rate -> (L, M, K); rate -> (index, L, M, K) once a window at it has samples
         rows, res, live = [], [], []
         for i, (w, r) in enumerate(zip(windows, rates)):
-            slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
-            tail = len(w) > 4 and bool(w[4]) and keep_thr is not None
-            if not (0 <= slot < S and 0 <= Tn <= cap):
-                raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
+            slot, Tn, s_lo, hi, tail = self._window_fields(i, w, S, cap, keep_thr)
             total = VOCOS.hop * (2 * Tn - 1)
-            hi = total if s_hi is None else int(s_hi)
             if r == self.SAMPLE_RATE:
                 win, rs = window_for_samples(Tn, s_lo, hi), None
             else:
@@ -2155,7 +2168,7 @@ class CodecEngine:
                     q = pairs.setdefault(r, (len(pairs), L, M, K))[0]
                     win, rs = window_for_samples(Tn, a, b), (q, a, total, o_lo, o_hi)
             if win is None:
-                out[i] = np.zeros((0,), np.uint8 if laws is not None and laws[i] >= 0 else dt)
+                out[i] = self._empty_window(i, pcm16, laws)
                 continue
             rows.append((slot, *win, int(tail), 0, 0))
             res.append(rs)
@@ -2163,10 +2176,9 @@ class CodecEngine:
         if not live:
             return out
         tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]
-        tok = np.zeros(len(live) + 1, np.int64)
-        np.cumsum(tab[:, 2] - tab[:, 1], out=tok[1:])
+        tok, start = self._packed_crops(tab)
         rtab = np.zeros(len(live), _lib.RS_WINDOW)                           # ctts_rs_window[n]
-        rtab["in_off"] = VOCOS.hop * (2 * tok[:-1] - np.arange(len(live))) + tab[:, 3]
+        rtab["in_off"] = start
         rtab["n_in"] = tab[:, 4] - tab[:, 3]
         rtab["rate"] = -1
         chunk = 0
@@ -2178,29 +2190,22 @@ class CodecEngine:
                 chunk += m + (-m % 8)
         sel = np.array([k for q in range(len(pairs)) for k, rs in enumerate(res) if rs is not None and rs[0] == q], dtype=np.int32)
         n = np.where(rtab["rate"] >= 0, rtab["o_hi"] - rtab["o_lo"], rtab["n_in"]).astype(np.int64)
-        off = np.zeros(len(live) + 1, np.int64)
-        np.cumsum((n + 7) // 8 * 8, out=off[1:])                             # every window starts on a multiple of 8 samples
-        esz = 2 if pcm16 else 4
-        n_out, any_keep = int(off[-1]) * esz, bool(tab[:, 5].any())
-        n_keep = (int(off[-1]) // 8 + 15) // 16 * 16 if any_keep else 0
-        n_g = (int(off[-1]) + 15) // 16 * 16 if laws is not None else 0
-        cur = torch.cuda.current_stream(self.device)
-        buf = torch.empty((n_out + n_g + n_keep,), dtype=torch.uint8, device=self.device)      # samples | (companded bytes) | keep masks: one copy
+        lay = self._windows_layout(n, tab[:, 5], pcm16, laws)
         blob = np.concatenate([tab.view(np.uint8).reshape(-1), rtab.view(np.uint8), sel.view(np.uint8)])
         blob_d = torch.from_numpy(blob).to(self.device)                      # one upload: both tables and the selection
         by_q = sorted(pairs.items(), key=lambda kv: kv[1][0])
         rate_tab = (_lib.Rate * max(1, len(by_q)))()
         for r, (q, L, M, K) in by_q:
             rate_tab[q].taps, rate_tab[q].L, rate_tab[q].M, rate_tab[q].K = self._resample_taps(self.SAMPLE_RATE, r).data_ptr(), L, M, K
-        ws, nws = self._ws_bytes(self.lib.ctts_codec_windows_rate_workspace_bytes(len(live), int(tok[-1]), chunk))
+        cur, tail_args = self._windows_call_tail(lay, tab[:, 5], pcm16, product, keep_thr,
+                                                 self.lib.ctts_codec_windows_rate_workspace_bytes(len(live), int(tok[-1]), chunk))
         base = blob_d.data_ptr()
         _lib.check(self.lib.ctts_codec_decode_windows_rate(
             self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap, base, tab.ctypes.data_as(C.c_void_p),
             base + tab.nbytes, rtab.ctypes.data_as(C.c_void_p), base + tab.nbytes + rtab.nbytes, sel.ctypes.data_as(C.c_void_p), len(live),
-            C.cast(rate_tab, C.c_void_p), len(by_q), 1 if pcm16 else 0, buf.data_ptr(), buf.data_ptr() + n_out + n_g if any_keep else None,
-            {"f64": 0, "f32": 1}[product], float(keep_thr or 0.0), ws.data_ptr(), nws, cur.cuda_stream), "ctts_codec_decode_windows_rate")
+            C.cast(rate_tab, C.c_void_p), len(by_q), *tail_args), "ctts_codec_decode_windows_rate")
         blob_d.record_stream(cur)
-        return self._windows_to_host(buf, n_out, n_g, off, n, tab[:, 5], live, None if laws is None else [laws[i] for i in live], dt, out)
+        return self._windows_finish(lay, n, tab[:, 5], live, laws, pcm16, out)
 
     def to_host(self, t: torch.Tensor) -> np.ndarray:
         """device tensor -> numpy, the `.cpu().numpy()` that ends the reference path (core.py:508-510), through a cached PINNED
