@@ -18,7 +18,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libchattts_amd.so")
 SOURCES = ["gemm.hip", "decode.hip", "decode32.hip", "decode32x.hip", "prefill.hip", "prefill32.hip", "prefill32x.hip", "gpt.hip", "codec.hip", "resample.hip", "timescale.hip", "g711.hip", "codec_gemm.hip", "dvae.hip", "capi.hip"]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
+# -amdgpu-kernarg-preload-count: the dispatcher places a kernel's leading plain (pointer / integer) parameters in user SGPRs, so the
+# step kernels address their first loads without a scalar fetch of the argument segment (a by-value struct is never
+# preloaded, which is why those kernels take what their first loads need as leading parameters IN FRONT of their struct)
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "kernels.hpp"), os.path.join(CSRC, "decode_dev.hpp"),
            os.path.join(HERE, "..", "include", "chattts_amd.h")]
 

@@ -26,11 +26,29 @@
 #include "kernels.hpp"
 #include "decode_dev.hpp"
 
+// Leading arguments preloaded: what the first requests need -- the probe pointer tested at entry, the weight and
+// activation tiles, the switches in front of them, the live-row count -- leads as plain parameters in user SGPRs; the struct follows
+// and everything else reads from it as before.  DEC_LEAD is the ONE list the kernel's parameter list, the copy back into the struct and
+// the launch (dec_launch) expand, so host and device cannot disagree.
+#define DEC_LEAD(F) F(long long*, dbg) F(const uint16_t*, Wp) F(const uint16_t*, Ap) F(int, N) F(int, K) F(int, w_nt) F(int, a_early) F(const int32_t*, n_active) F(int, M)
+#define DEC_LEAD_PARAM(T, f) T lead_##f,
+#define DEC_LEAD_PUT(T, f) a.f = lead_##f;
+#define DEC_LEAD_ARG(T, f) a.f,
+
 template <int MBT, int NW, bool SCALE, int EPI, int U = DEC_U>
 __global__ __launch_bounds__(64 * (NW + (EPI == FEPI_QKV_ROPE ? 1 : 0)))
-void gemm_dec_k(DecGemmArgs a) {
+void gemm_dec_k(DEC_LEAD(DEC_LEAD_PARAM) int lead_grid_x, DecGemmArgs a_rest) {
   CTTS_PROBE_RETURN();
-  gemm_dec_wg<MBT, NW, SCALE, EPI, false, U>(a, blockIdx.x, blockIdx.y * MBT, gridDim.y, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+  DecGemmArgs a = a_rest;
+  DEC_LEAD(DEC_LEAD_PUT)
+  // row groups = 1: whether one row group reads the weights is folded into w_nt by the launch (gridDim sits in the argument segment too)
+  gemm_dec_wg<MBT, NW, SCALE, EPI, false, U>(a, blockIdx.x, blockIdx.y * MBT, 1, blockIdx.y * lead_grid_x + blockIdx.x, lead_grid_x * gridDim.y);
+}
+
+template <class Kern>
+static inline void dec_launch(Kern kern, dim3 grid, dim3 block, hipStream_t st, DecGemmArgs a) {
+  a.w_nt = a.w_nt && grid.y == 1;   // non-temporal only when a single row group reads the weights
+  CTTS_LAUNCH(kern, grid, block, st, DEC_LEAD(DEC_LEAD_ARG) (int)grid.x, a);
 }
 
 // Waves per workgroup of the K = 768 launches.  Rounds 2-4 ran all of them on 4 waves (6 chunks of 32 each, one round).  Round 5 (the
@@ -61,13 +79,13 @@ static hipError_t dec_dispatch_k768(const DecGemmArgs& a, hipStream_t st) {
   dim3 grid(a.N / 16, (mt + MBT - 1) / MBT);
   const bool scale = a.ssq_in != nullptr;
   if (a.K != 768) {   // K = 1536 (probes): the 4-wave shape
-    if (a.epi == FEPI_SILU && scale) CTTS_LAUNCH((gemm_dec_k<MBT, 4, true, FEPI_SILU>), grid, dim3(256), st, a);
+    if (a.epi == FEPI_SILU && scale) dec_launch(gemm_dec_k<MBT, 4, true, FEPI_SILU>, grid, dim3(256), st, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
   }
-  if (a.epi == FEPI_QKV_ROPE && scale) CTTS_LAUNCH((gemm_dec_k<MBT, NQ, true, FEPI_QKV_ROPE, 24 / NQ>), grid, dim3(64 * NQ + 64), st, a);
-  else if (a.epi == FEPI_SILU && scale) CTTS_LAUNCH((gemm_dec_k<MBT, NS, true, FEPI_SILU, 24 / NS>), grid, dim3(64 * NS), st, a);
-  else if (a.epi == FEPI_RES && !scale) CTTS_LAUNCH((gemm_dec_k<MBT, NO, false, FEPI_RES, 24 / NO>), grid, dim3(64 * NO), st, a);
+  if (a.epi == FEPI_QKV_ROPE && scale) dec_launch(gemm_dec_k<MBT, NQ, true, FEPI_QKV_ROPE, 24 / NQ>, grid, dim3(64 * NQ + 64), st, a);
+  else if (a.epi == FEPI_SILU && scale) dec_launch(gemm_dec_k<MBT, NS, true, FEPI_SILU, 24 / NS>, grid, dim3(64 * NS), st, a);
+  else if (a.epi == FEPI_RES && !scale) dec_launch(gemm_dec_k<MBT, NO, false, FEPI_RES, 24 / NO>, grid, dim3(64 * NO), st, a);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
@@ -75,7 +93,7 @@ template <int MBT, int NW>
 static hipError_t dec_dispatch_k3072(const DecGemmArgs& a, hipStream_t st) {
   const int mt = (a.M + 15) / 16;
   dim3 grid(a.N / 16, (mt + MBT - 1) / MBT);
-  if (a.epi == FEPI_RES && a.ssq_in == nullptr) CTTS_LAUNCH((gemm_dec_k<MBT, NW, false, FEPI_RES>), grid, dim3(64 * NW), st, a);
+  if (a.epi == FEPI_RES && a.ssq_in == nullptr) dec_launch(gemm_dec_k<MBT, NW, false, FEPI_RES>, grid, dim3(64 * NW), st, a);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

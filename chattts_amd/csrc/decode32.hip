@@ -114,7 +114,7 @@ __device__ __forceinline__ void dec32_body(const Dec32Args& a, const int M, cons
   const u128* wp = reinterpret_cast<const u128*>(a.Wp) + ((size_t)tile * KCH + wave) * 64 + lane;
   const u128* wp2 = wp + (size_t)(N >> 4) * KCH * 64;  // SILU_MUL: the "up" tile of the same columns
   const u128* ap = reinterpret_cast<const u128*>(a.Ap) + ((size_t)mt0 * KCH + wave) * 64 + lane;
-  const bool w_once = a.w_nt && gridDim.y == 1;  // a single row group reads W: stream it past the caches
+  const bool w_once = a.w_nt != 0;  // a single row group reads W: stream it past the caches
   u128 af[NMB][U];
   float4 nw[U];
   auto load_a = [&](const int i) {
@@ -255,8 +255,19 @@ __device__ __forceinline__ void dec32_body(const Dec32Args& a, const int M, cons
   }
 }
 
+// Leading arguments preloaded: what the first requests of the four kernels below need -- the weight and activation
+// tiles, N (the grid's x extent is rounded up), the non-temporal switch, the norm's gain, the live-row count -- leads as plain parameters
+// in user SGPRs; the struct follows and everything else reads from it as before.  D32_LEAD is the ONE list the kernels' parameter
+// lists, the copy back into the struct and the launch (dec32_launch) expand, so host and device cannot disagree.
+#define D32_LEAD(F) F(const float*, Wp) F(const float*, Ap) F(int, N) F(int, w_nt) F(const float*, norm_w) F(const int32_t*, n_active) F(int, M) F(int, K)
+#define D32_LEAD_PARAM(T, f) T lead_##f,
+#define D32_LEAD_PUT(T, f) a.f = lead_##f;
+#define D32_LEAD_ARG(T, f) a.f,
+
 template <int MBT, bool RMS, int EPI>
-__global__ __launch_bounds__(256) void gemm_dec32_k(Dec32Args a) {
+__global__ __launch_bounds__(256) void gemm_dec32_k(D32_LEAD(D32_LEAD_PARAM) Dec32Args a_rest) {
+  Dec32Args a = a_rest;
+  D32_LEAD(D32_LEAD_PUT)
   constexpr int NACC = (EPI == EPI_SILU_MUL) ? 2 : 1;
   __shared__ __attribute__((aligned(16))) float red[4][NACC][MBT][64][4];
   __shared__ float rstd_s[16 * MBT];
@@ -269,7 +280,7 @@ __global__ __launch_bounds__(256) void gemm_dec32_k(Dec32Args a) {
     const int KCH = a.K >> 4, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const u128* wp = reinterpret_cast<const u128*>(a.Wp) + ((size_t)tile * KCH + wave) * 64 + lane;
     const u128* wp2 = wp + (size_t)(a.N >> 4) * KCH * 64;
-    const bool w_once = a.w_nt && gridDim.y == 1;
+    const bool w_once = a.w_nt != 0;
     if (w_once) {
 #pragma unroll
       for (int j = 0; j < D32_U; ++j) {
@@ -306,7 +317,9 @@ __global__ __launch_bounds__(256) void gemm_dec32_k(Dec32Args a) {
 // double-buffered (stage r+1 requested before stage r is multiplied).  Same operation order per output element as above.
 // (With an RMSNorm prologue this shape was SLOWER than the generic body -- 200+ VGPRs, profiles/r2s_* -- see gemm_dec32_rms16_k.)
 template <int KT, int EPI>
-__global__ __launch_bounds__(256) void gemm_dec32_m16_k(Dec32Args a) {
+__global__ __launch_bounds__(256) void gemm_dec32_m16_k(D32_LEAD(D32_LEAD_PARAM) Dec32Args a_rest) {
+  Dec32Args a = a_rest;
+  D32_LEAD(D32_LEAD_PUT)
   constexpr int NACC = 1;
   constexpr int KCH = KT / 16, NPER = KCH / 4;   // chunks per wave: 12 / 48
   constexpr int U = (KT == 768) ? 12 : 6;         // chunks per stage
@@ -324,7 +337,7 @@ __global__ __launch_bounds__(256) void gemm_dec32_m16_k(Dec32Args a) {
   const u128* wp = reinterpret_cast<const u128*>(a.Wp) + ((size_t)tile * KCH + wave) * 64 + lane;   // wave w owns chunks 4 i + w
   const u128* wp2 = wp + (size_t)(a.N >> 4) * KCH * 64;
   const u128* ap = reinterpret_cast<const u128*>(a.Ap) + ((size_t)mt0 * KCH + wave) * 64 + lane;
-  const bool w_once = a.w_nt && gridDim.y == 1;
+  const bool w_once = a.w_nt != 0;
   auto load_stage = [&](Stage& s, const int r) {
     if (w_once) {
 #pragma unroll
@@ -407,7 +420,9 @@ __global__ __launch_bounds__(256) void gemm_dec32_m16_k(Dec32Args a) {
 // lane ^ 16).  Same operands, same association, same bits -- and the launch moves 25 % less through the L2s and loses a
 // dependent memory round trip.  Weights come in rounds of 6 (gate/up: 4) chunks (VGPR budget: 3 workgroups per CU).
 template <int EPI>
-__global__ __launch_bounds__(256, 3) void gemm_dec32_rms16_k(Dec32Args a) {
+__global__ __launch_bounds__(256, 3) void gemm_dec32_rms16_k(D32_LEAD(D32_LEAD_PARAM) Dec32Args a_rest) {
+  Dec32Args a = a_rest;
+  D32_LEAD(D32_LEAD_PUT)
   constexpr int NACC = (EPI == EPI_SILU_MUL) ? 2 : 1;
   constexpr int KCH = 48, NPER = 12;
   constexpr int WU = (NACC == 2) ? 4 : 6;          // weight chunks per round (VGPR budget: 3 workgroups per CU)
@@ -421,7 +436,7 @@ __global__ __launch_bounds__(256, 3) void gemm_dec32_rms16_k(Dec32Args a) {
   const u128* wp = reinterpret_cast<const u128*>(a.Wp) + ((size_t)tile * KCH + wave) * 64 + lane;   // wave w owns chunks 4 i + w
   const u128* wp2 = wp + (size_t)(a.N >> 4) * KCH * 64;
   const u128* ap = reinterpret_cast<const u128*>(a.Ap) + ((size_t)mt0 * KCH + wave) * 64 + lane;
-  const bool w_once = a.w_nt && gridDim.y == 1;
+  const bool w_once = a.w_nt != 0;
   // Round 4: the weight chunks of a round live in TWO half buffers (HU chunks each, the same registers as one WU-chunk round before);
   // a half is refilled with the chunks of the round after next as soon as its MFMAs are issued, so the next request is in flight while the
   // other half is multiplied (before: every round's loads were issued right in front of its own MFMAs -- one exposed L2 round trip per
@@ -549,7 +564,9 @@ __global__ __launch_bounds__(256, 3) void gemm_dec32_rms16_k(Dec32Args a) {
 // between the lane's own four partials of a block (i ^ 2, then i ^ 1), levels 8 and 4 adds across the four waves (w ^ 2, then w ^ 1,
 // through LDS), levels 2 and 1 adds across lane groups (lane ^ 32, then lane ^ 16).  Same operands, same association, same bits as
 // final_norm_k; the scaled fragment g[k] * (x * rstd) IS the hidden state, and the workgroups of weight tile 0 store it.
-__global__ __launch_bounds__(256, 3) void gemm_dec32_fnorm16_k(Dec32Args a) {
+__global__ __launch_bounds__(256, 3) void gemm_dec32_fnorm16_k(D32_LEAD(D32_LEAD_PARAM) Dec32Args a_rest) {
+  Dec32Args a = a_rest;
+  D32_LEAD(D32_LEAD_PUT)
   constexpr int KCH = 48, NPER = 12, WU = 6;
   __shared__ __attribute__((aligned(16))) float red[4][64][4];
   __shared__ float bs[3][4][64];
@@ -562,7 +579,7 @@ __global__ __launch_bounds__(256, 3) void gemm_dec32_fnorm16_k(Dec32Args a) {
   const int n0 = tile * 16, m0 = mt0 * 16;
   const u128* wp = reinterpret_cast<const u128*>(a.Wp) + ((size_t)tile * KCH + wave) * 64 + lane;   // wave w owns chunks 4 i + w
   const u128* ap = reinterpret_cast<const u128*>(a.Ap) + ((size_t)mt0 * KCH + wave) * 64 + lane;
-  const bool w_once = a.w_nt && gridDim.y == 1;
+  const bool w_once = a.w_nt != 0;
   u128 wf[WU], af[NPER];
   float4 nw[WU];
   auto load_w = [&](const int i0) {
@@ -642,6 +659,13 @@ __global__ __launch_bounds__(256, 3) void gemm_dec32_fnorm16_k(Dec32Args a) {
   if (row < M && col < a.n_cols) a.C[(size_t)row * a.ldc + col] = v;
 }
 
+template <class Kern>
+static inline void dec32_launch(Kern kern, dim3 grid, dim3 block, size_t smem, hipStream_t st, Dec32Args a) {
+  a.w_nt = a.w_nt && grid.y == 1;   // non-temporal only when a single row group reads the weights: decided here, so that the kernels'
+                                    // first requests wait for no scalar load (gridDim sits in the argument segment too)
+  CTTS_LAUNCH_SMEM(kern, grid, block, smem, st, D32_LEAD(D32_LEAD_ARG) a);
+}
+
 template <int KT>
 static hipError_t dec32_dispatch_m16(const Dec32Args& a, hipStream_t st) {
   // x extent a multiple of 8: workgroup (tile, row tile) then runs on XCD tile % 8 for EVERY row tile, so a weight tile is fetched
@@ -649,8 +673,8 @@ static hipError_t dec32_dispatch_m16(const Dec32Args& a, hipStream_t st) {
   // launch against 8.2 MB of weights); 48 / 144 / 192 tiles are multiples of 8 already.
   dim3 grid((a.N / 16 + 7) / 8 * 8, (a.M + 15) / 16), block(256);
   if (a.norm_w != nullptr) return hipErrorInvalidValue;
-  if (a.epi == EPI_STORE) CTTS_LAUNCH((gemm_dec32_m16_k<KT, EPI_STORE>), grid, block, st, a);
-  else if (a.epi == EPI_RES) CTTS_LAUNCH((gemm_dec32_m16_k<KT, EPI_RES>), grid, block, st, a);
+  if (a.epi == EPI_STORE) dec32_launch(gemm_dec32_m16_k<KT, EPI_STORE>, grid, block, 0, st, a);
+  else if (a.epi == EPI_RES) dec32_launch(gemm_dec32_m16_k<KT, EPI_RES>, grid, block, 0, st, a);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
@@ -665,11 +689,11 @@ static hipError_t dec32_dispatch(const Dec32Args& a, hipStream_t st) {
   const int mt = (a.M + 15) / 16;
   dim3 grid(a.N / 16, (mt + MBT - 1) / MBT), block(256);
   const bool rms = a.norm_w != nullptr;
-  if (a.epi == EPI_STORE && rms) CTTS_LAUNCH((gemm_dec32_k<MBT, true, EPI_STORE>), grid, block, st, a);
-  else if (a.epi == EPI_STORE) CTTS_LAUNCH((gemm_dec32_k<MBT, false, EPI_STORE>), grid, block, st, a);
-  else if (a.epi == EPI_RES && !rms) CTTS_LAUNCH((gemm_dec32_k<MBT, false, EPI_RES>), grid, block, st, a);
-  else if (a.epi == EPI_SILU_MUL && rms) CTTS_LAUNCH((gemm_dec32_k<MBT, true, EPI_SILU_MUL>), grid, block, st, a);
-  else if (a.epi == D32_EPI_QKV_ROPE && rms) CTTS_LAUNCH((gemm_dec32_k<MBT, true, D32_EPI_QKV_ROPE>), grid, block, st, a);
+  if (a.epi == EPI_STORE && rms) dec32_launch(gemm_dec32_k<MBT, true, EPI_STORE>, grid, block, 0, st, a);
+  else if (a.epi == EPI_STORE) dec32_launch(gemm_dec32_k<MBT, false, EPI_STORE>, grid, block, 0, st, a);
+  else if (a.epi == EPI_RES && !rms) dec32_launch(gemm_dec32_k<MBT, false, EPI_RES>, grid, block, 0, st, a);
+  else if (a.epi == EPI_SILU_MUL && rms) dec32_launch(gemm_dec32_k<MBT, true, EPI_SILU_MUL>, grid, block, 0, st, a);
+  else if (a.epi == D32_EPI_QKV_ROPE && rms) dec32_launch(gemm_dec32_k<MBT, true, D32_EPI_QKV_ROPE>, grid, block, 0, st, a);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
@@ -704,7 +728,7 @@ hipError_t launch_gemm_dec32(const Dec32Args& a_in, hipStream_t st) {
     if (a.norm_w == nullptr || a.K != 768 || a.epi != EPI_STORE || (a.hid != nullptr && a.desc == nullptr)) return hipErrorInvalidValue;
     g_d32_variant = "fnorm16";
     dim3 grid((a.N / 16 + 7) / 8 * 8, (a.M + 15) / 16), block(256);
-    CTTS_LAUNCH(gemm_dec32_fnorm16_k, grid, block, st, a);
+    dec32_launch(gemm_dec32_fnorm16_k, grid, block, 0, st, a);
     return hipGetLastError();
   }
   // 16-row RMSNorm launches (QKV, gate/up): statistics from the fragments, no re-read of the residual rows
@@ -723,9 +747,9 @@ hipError_t launch_gemm_dec32(const Dec32Args& a_in, hipStream_t st) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dec32_rms16_k<D32_EPI_QKV_ROPE>), hipFuncAttributeMaxDynamicSharedMemorySize, d32_lds);
       }
     }
-    if (a.epi == EPI_SILU_MUL) CTTS_LAUNCH_SMEM((gemm_dec32_rms16_k<EPI_SILU_MUL>), grid, block, d32_lds, st, a);
-    else if (a.epi == D32_EPI_QKV_ROPE) CTTS_LAUNCH_SMEM((gemm_dec32_rms16_k<D32_EPI_QKV_ROPE>), grid, block, d32_lds, st, a);
-    else if (a.epi == EPI_STORE) CTTS_LAUNCH((gemm_dec32_rms16_k<EPI_STORE>), grid, block, st, a);
+    if (a.epi == EPI_SILU_MUL) dec32_launch(gemm_dec32_rms16_k<EPI_SILU_MUL>, grid, block, d32_lds, st, a);
+    else if (a.epi == D32_EPI_QKV_ROPE) dec32_launch(gemm_dec32_rms16_k<D32_EPI_QKV_ROPE>, grid, block, d32_lds, st, a);
+    else if (a.epi == EPI_STORE) dec32_launch(gemm_dec32_rms16_k<EPI_STORE>, grid, block, 0, st, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
   }

@@ -75,7 +75,7 @@ __device__ __forceinline__ void dec32x_body(const Dec32xArgs& a, const int M, co
   const u128* wp2 = wp + (size_t)(N >> 4) * KCH * 64;  // SILU_MUL: the "up" tile of the same columns
   const u128* ap = reinterpret_cast<const u128*>(a.Ap) + ((size_t)mt0 * KCH + wave * nper) * 64 + lane;
   const size_t wpl = a.w_plane >> 3, apl = a.a_plane >> 3;   // plane strides in 16-byte units
-  const bool w_once = a.w_nt && gridDim.y == 1;
+  const bool w_once = a.w_nt != 0;   // (the launch clears w_nt when more than one row tile reads the weights)
   u128 ah[NMB][U], al[NMB][U];
   auto load_a = [&](const int i) {
 #pragma unroll
@@ -263,8 +263,19 @@ __device__ __forceinline__ void dec32x_body(const Dec32xArgs& a, const int M, co
   }
 }
 
+// Leading arguments preloaded: what the first loads need -- the weight planes, the live-row count, the activation
+// planes -- arrives in user SGPRs as plain leading parameters, in order of first use; the struct follows and everything else reads from
+// it as before.  DEC32X_LEAD is the ONE place that says which fields lead and in which order: the kernel's parameter list, the copy
+// back into its struct and the launch (dec32x_launch) are all expansions of it, so host and device cannot disagree.
+#define DEC32X_LEAD(F) F(const uint16_t*, Wp) F(size_t, w_plane) F(int, N) F(int, w_nt) F(const int32_t*, n_active) F(const uint16_t*, Ap) F(size_t, a_plane) F(int, M)
+#define DEC32X_LEAD_PARAM(T, f) T lead_##f,
+#define DEC32X_LEAD_PUT(T, f) a.f = lead_##f;
+#define DEC32X_LEAD_ARG(T, f) a.f,
+
 template <int MBT, int KT, bool RMS, int EPI, int NW>
-__global__ __launch_bounds__(64 * NW) void gemm_dec32x_k(Dec32xArgs a) {
+__global__ __launch_bounds__(64 * NW) void gemm_dec32x_k(DEC32X_LEAD(DEC32X_LEAD_PARAM) Dec32xArgs a_rest) {
+  Dec32xArgs a = a_rest;
+  DEC32X_LEAD(DEC32X_LEAD_PUT)
   constexpr int NACC = (EPI == EPI_SILU_MUL) ? 2 : 1;
   constexpr int U = DxU<MBT, KT, NW>::v;
   __shared__ __attribute__((aligned(16))) float red[NW][NACC][MBT][64][4];
@@ -281,7 +292,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_dec32x_k(Dec32xArgs a) {
     const u128* wp = reinterpret_cast<const u128*>(a.Wp) + ((size_t)tile * KCH + wave * nper) * 64 + lane;
     const u128* wp2 = wp + (size_t)(a.N >> 4) * KCH * 64;
     const size_t wpl = a.w_plane >> 3;
-    if (a.w_nt && gridDim.y == 1) {
+    if (a.w_nt) {
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         wh[0][j] = load16_nt(wp + (size_t)j * 64); wl[0][j] = load16_nt(wp + wpl + (size_t)j * 64);
@@ -316,14 +327,21 @@ static int env_i(const char* name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
+template <class Kern>
+static inline void dec32x_launch(Kern kern, dim3 grid, dim3 block, hipStream_t st, Dec32xArgs a) {
+  a.w_nt = a.w_nt && grid.y == 1;   // non-temporal only when every weight fragment is read once: decided here, so that the kernel's first
+                                    // request waits for no scalar load at all (gridDim sits in the argument segment too)
+  CTTS_LAUNCH(kern, grid, block, st, DEC32X_LEAD(DEC32X_LEAD_ARG) a);
+}
+
 template <int MBT, int NW>
 static hipError_t dec32x_dispatch(const Dec32xArgs& a, hipStream_t st) {
   const int mt = (a.M + 15) / 16;
   dim3 grid(a.N / 16, (mt + MBT - 1) / MBT), block(64 * NW);
-  if (a.epi == EPI_RES && !a.rms && a.K == 768) CTTS_LAUNCH((gemm_dec32x_k<MBT, 768, false, EPI_RES, NW>), grid, block, st, a);
-  else if (a.epi == EPI_RES && !a.rms && a.K == 3072) CTTS_LAUNCH((gemm_dec32x_k<MBT, 3072, false, EPI_RES, NW>), grid, block, st, a);
-  else if (a.epi == EPI_SILU_MUL && a.rms && a.K == 768) CTTS_LAUNCH((gemm_dec32x_k<MBT, 768, true, EPI_SILU_MUL, NW>), grid, block, st, a);
-  else if (a.epi == D32_EPI_QKV_ROPE && a.rms && a.K == 768) CTTS_LAUNCH((gemm_dec32x_k<MBT, 768, true, D32_EPI_QKV_ROPE, NW>), grid, block, st, a);
+  if (a.epi == EPI_RES && !a.rms && a.K == 768) dec32x_launch(gemm_dec32x_k<MBT, 768, false, EPI_RES, NW>, grid, block, st, a);
+  else if (a.epi == EPI_RES && !a.rms && a.K == 3072) dec32x_launch(gemm_dec32x_k<MBT, 3072, false, EPI_RES, NW>, grid, block, st, a);
+  else if (a.epi == EPI_SILU_MUL && a.rms && a.K == 768) dec32x_launch(gemm_dec32x_k<MBT, 768, true, EPI_SILU_MUL, NW>, grid, block, st, a);
+  else if (a.epi == D32_EPI_QKV_ROPE && a.rms && a.K == 768) dec32x_launch(gemm_dec32x_k<MBT, 768, true, D32_EPI_QKV_ROPE, NW>, grid, block, st, a);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
@@ -356,7 +374,7 @@ hipError_t launch_gemm_dec32x(const Dec32xArgs& a_in, hipStream_t st) {
   if (a.force_mb) { mb = a.force_mb & 7; nw = (a.force_mb & 16) ? 16 : (a.force_mb & 8) ? 8 : 4; }   // tests: rows per workgroup in the low bits, +8 = eight waves, +16 = sixteen (down_proj, 16 rows)
   if (nw == 16 && a.epi == EPI_RES && !a.rms && a.K == 3072 && mb == 1) {   // down_proj only: 16 waves x 6 chunks, as the perf mode's down_proj
     dim3 grid(a.N / 16, (a.M + 15) / 16), block(1024);
-    CTTS_LAUNCH((gemm_dec32x_k<1, 3072, false, EPI_RES, 16>), grid, block, st, a);
+    dec32x_launch(gemm_dec32x_k<1, 3072, false, EPI_RES, 16>, grid, block, st, a);
     return hipGetLastError();
   }
   if (nw >= 8) {

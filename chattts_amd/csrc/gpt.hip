@@ -114,12 +114,22 @@ __device__ __forceinline__ uint16_t* xb_row_ptr(uint16_t* xb, int m, int t, int 
   return packed ? xb + pk_off(m, 4 * t, HID / 32) - 4 * t : xb + (size_t)m * HID;
 }
 
-__global__ __launch_bounds__(192) void embed_codes_k(const float* __restrict__ emb, const int64_t* __restrict__ ids_buf,
-                                                     int tcap, const int32_t* __restrict__ len, float* __restrict__ x,
-                                                     uint16_t* __restrict__ xb, float* __restrict__ ssq,
-                                                     const int32_t* __restrict__ row_map, const int32_t* __restrict__ n_active,
-                                                     StepPrep sp) {
+// Leading arguments preloaded: what the kernel's first loads need -- the words to zero, the compaction's inputs, or
+// the live-row count, the row map and the lengths -- leads as plain parameters; the two EMBED_LEAD lists are the one place the
+// parameter list, the copy back into StepPrep and the launch expand.
+#define EMBED_LEAD_SP(F) F(int32_t*, zero_p) F(int32_t*, row_map_out) F(const uint8_t*, finish) F(const int32_t*, order)
+#define EMBED_LEAD(F) F(const int32_t* __restrict__, n_active) F(const int32_t* __restrict__, row_map) F(const int32_t* __restrict__, len)
+#define EMBED_LEAD_SP_PARAM(T, f) T lead_##f,
+#define EMBED_LEAD_SP_PUT(T, f) sp.f = lead_##f;
+#define EMBED_LEAD_SP_ARG(T, f) sp.f,
+#define EMBED_LEAD_PARAM(T, f) T f,
+#define EMBED_LEAD_ARG(T, f) f,
+__global__ __launch_bounds__(192) void embed_codes_k(EMBED_LEAD_SP(EMBED_LEAD_SP_PARAM) EMBED_LEAD(EMBED_LEAD_PARAM)
+                                                     const float* __restrict__ emb, const int64_t* __restrict__ ids_buf, int tcap,
+                                                     float* __restrict__ x, uint16_t* __restrict__ xb, float* __restrict__ ssq, StepPrep sp_rest) {
   CTTS_PROBE_RETURN();
+  StepPrep sp = sp_rest;
+  EMBED_LEAD_SP(EMBED_LEAD_SP_PUT)
   step_zero(sp);
   const int m = blockIdx.x, t = threadIdx.x;
   int b;
@@ -160,7 +170,8 @@ static StepPrep prep_or_none(const StepPrep* p) {
 
 hipError_t launch_embed_codes(const float* emb_code, const int64_t* ids_buf, int tcap, const int32_t* len, float* x, uint16_t* xb,
                               float* ssq, int B, const int32_t* row_map, const int32_t* n_active, hipStream_t st, const StepPrep* prep) {
-  CTTS_LAUNCH(embed_codes_k, dim3(B), dim3(192), st, emb_code, ids_buf, tcap, len, x, xb, ssq, row_map, n_active, prep_or_none(prep));
+  const StepPrep sp = prep_or_none(prep);
+  CTTS_LAUNCH(embed_codes_k, dim3(B), dim3(192), st, EMBED_LEAD_SP(EMBED_LEAD_SP_ARG) EMBED_LEAD(EMBED_LEAD_ARG) emb_code, ids_buf, tcap, x, xb, ssq, sp);
   return hipGetLastError();
 }
 
@@ -841,11 +852,31 @@ __device__ __forceinline__ void attention_body(const float* __restrict__ qkv, co
 #undef ASTAMP
 }
 
+// Leading arguments preloaded: the row's descriptor is the kernel's first request, and what addresses it -- the
+// probe pointer tested at entry, the live-row count, desc, the two switches in front of them -- arrives in user SGPRs as plain leading
+// parameters, followed by what addresses the first KV block; q is requested behind that block and `out` is used last: those two do
+// not fit the 14 preloaded dwords and are fetched while the descriptor is on its way.  The two ATT_LEAD lists are the
+// ONE place that says what leads and in which order: the kernel's parameter list, the copy back into GptRowMap and the launch
+// (att_launch) are all expansions of them, so host and device cannot disagree.
+#define ATT_LEAD_RM(F) F(long long*, dbg) F(const int32_t*, n_active) F(const RowDesc*, desc) F(int, q_per_b) F(int, desc_covers_all)
+#define ATT_LEAD_PTR(F) F(const KT* __restrict__, kc) F(const KT* __restrict__, vc) F(int, cmax) F(int, grid_x) F(const float* __restrict__, qkv) F(OT* __restrict__, out)
+#define ATT_LEAD_PARAM(T, f) T lead_##f,
+#define ATT_LEAD_PUT(T, f) rm.f = lead_##f;
+#define ATT_LEAD_RM_ARG(T, f) rm.f,
+#define ATT_LEAD_ARG(T, f) f,
+
 template <typename KT, int NW, typename OT, bool PKO = false, bool SPLIT = false, bool PF = false, int NBUF = 2, bool OPJ = false>
-__global__ __launch_bounds__(64 * NW + (PF ? 64 : 0)) void attention_k(const float* __restrict__ qkv, const KT* __restrict__ kc,
-                                                       const KT* __restrict__ vc, int cmax, OT* __restrict__ out, GptRowMap rm) {
+__global__ __launch_bounds__(64 * NW + (PF ? 64 : 0)) void attention_k(ATT_LEAD_RM(ATT_LEAD_PARAM) ATT_LEAD_PTR(ATT_LEAD_PARAM) GptRowMap rm_rest) {
   if (NW > 1) CTTS_PROBE_RETURN();
-  attention_body<KT, NW, OT, PKO, SPLIT, PF, NBUF, OPJ, false>(qkv, kc, vc, cmax, out, rm, blockIdx.x, blockIdx.y, blockIdx.y * gridDim.x + blockIdx.x);
+  GptRowMap rm = rm_rest;
+  ATT_LEAD_RM(ATT_LEAD_PUT)
+  const float* __restrict__ qkv = lead_qkv;
+  const KT* __restrict__ kc = lead_kc;
+  const KT* __restrict__ vc = lead_vc;
+  const int cmax = lead_cmax;
+  OT* __restrict__ out = lead_out;
+  // (gridDim sits in the argument segment as well: the launch hands grid.x over with the leading arguments)
+  attention_body<KT, NW, OT, PKO, SPLIT, PF, NBUF, OPJ, false>(qkv, kc, vc, cmax, out, rm, blockIdx.x, blockIdx.y, blockIdx.y * lead_grid_x + blockIdx.x);
 }
 
 // HPW heads of one utterance per workgroup (round 5 A/B, CTTS_ATT_HPW=2|3|4; ctts_k_attention_heads_per_wg): the SAME 4-wave unit,
@@ -1259,6 +1290,14 @@ void attention_persist_override(int persist, int g, int d) {
   if (d > 0) att_cfg_[2] = d;
 }
 
+
+template <typename KT, typename OT, class Kern>
+static inline void att_launch(Kern kern, dim3 grid, dim3 block, size_t smem, hipStream_t st, const float* qkv, const KT* kc, const KT* vc, int cmax, OT* out,
+                              const GptRowMap& rm) {
+  const int grid_x = (int)grid.x;
+  CTTS_LAUNCH_SMEM(kern, grid, block, smem, st, ATT_LEAD_RM(ATT_LEAD_RM_ARG) ATT_LEAD_PTR(ATT_LEAD_ARG) rm);
+}
+
 hipError_t launch_attention(const float* qkv, const void* kcache, const void* vcache, int kv_wt, int cmax, void* out, int out_bf16,
                             GptRowMap rm, int M, hipStream_t st) {
   dim3 grid(NHEAD, M);
@@ -1325,53 +1364,53 @@ hipError_t launch_attention(const float* qkv, const void* kcache, const void* vc
   if (out_bf16 == 2) {   // decode, perf mode: bf16 output in the fragment-packed order the o_proj kernel of decode.hip reads
     if (!decode || kv_wt != WT_BF16) return hipErrorInvalidValue;
     if (rm.sp_cus > 0 && rm.sp_part != nullptr && rm.sp_cnt != nullptr)
-      CTTS_LAUNCH((attention_k<bf16_t, 4, bf16_t, true, true>), dim3(NHEAD * M + rm.sp_cus), dim3(256), st, qkv, (const bf16_t*)kcache,
+      att_launch((attention_k<bf16_t, 4, bf16_t, true, true>), dim3(NHEAD * M + rm.sp_cus), dim3(256), 0, st, qkv, (const bf16_t*)kcache,
                   (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
     else if (M <= att_small_m)
       // A/B knob, OFF by default (CTTS_ATT_SMALL_M=<rows>): 16 waves per unit for tiny batches (BASELINE C2: batch 1 = 12 units on
       // 256 CUs), so a long context is in flight in one round trip.  MEASURED at batch 1 (profiles/r3b_c2_ab.log): 0.482 ms per
       // step with it, 0.478 without -- the 16-way LDS merge costs what the shorter stream saves -- and it would make a row's
       // perf-mode bits depend on the batch size.
-      CTTS_LAUNCH((attention_k<bf16_t, 16, bf16_t, true>), grid, dim3(1024), st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
+      att_launch((attention_k<bf16_t, 16, bf16_t, true>), grid, dim3(1024), 0, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
 #ifdef CTTS_PF_BUILD
     else if (rm.pf.base != nullptr)
-      CTTS_LAUNCH_SMEM((attention_k<bf16_t, 4, bf16_t, true, false, true>), grid, dim3(320), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
+      att_launch((attention_k<bf16_t, 4, bf16_t, true, false, true>), grid, dim3(320), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
 #endif
     else if (nw_packed == 2)
-      CTTS_LAUNCH_SMEM((attention_k<bf16_t, 2, bf16_t, true>), grid, dim3(128), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
+      att_launch((attention_k<bf16_t, 2, bf16_t, true>), grid, dim3(128), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
     else if (nw_packed == 8)
-      CTTS_LAUNCH_SMEM((attention_k<bf16_t, 8, bf16_t, true>), grid, dim3(512), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
+      att_launch((attention_k<bf16_t, 8, bf16_t, true>), grid, dim3(512), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
     else if (nw_packed == 16)
-      CTTS_LAUNCH_SMEM((attention_k<bf16_t, 16, bf16_t, true>), grid, dim3(1024), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
+      att_launch((attention_k<bf16_t, 16, bf16_t, true>), grid, dim3(1024), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
     else if (att_nbuf == 3)
-      CTTS_LAUNCH_SMEM((attention_k<bf16_t, 4, bf16_t, true, false, false, 3>), grid, dim3(256), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
+      att_launch((attention_k<bf16_t, 4, bf16_t, true, false, false, 3>), grid, dim3(256), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
     else
-      CTTS_LAUNCH_SMEM((attention_k<bf16_t, 4, bf16_t, true>), grid, dim3(256), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
+      att_launch((attention_k<bf16_t, 4, bf16_t, true>), grid, dim3(256), att_lds, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
     return hipGetLastError();
   }
   if (out_bf16 == 3 && !decode) {   // prefill, f32 parity mode: one wave per (row, head), output in the packed f32 order
     if (kv_wt == WT_BF16) return hipErrorInvalidValue;
-    CTTS_LAUNCH((attention_k<float, 1, float, true>), grid, dim3(64), st, qkv, (const float*)kcache, (const float*)vcache, cmax, (float*)out, rm);
+    att_launch((attention_k<float, 1, float, true>), grid, dim3(64), 0, st, qkv, (const float*)kcache, (const float*)vcache, cmax, (float*)out, rm);
     return hipGetLastError();
   }
   if (out_bf16 == 4) {   // decode, split-bf16 parity mode: f32 KV cache, output as hi / lo bf16 planes in decode.hip's fragment order
     if (!decode || kv_wt == WT_BF16 || rm.x3_plane == 0) return hipErrorInvalidValue;
-    CTTS_LAUNCH_SMEM((attention_k<float, 4, x3p_t, true>), grid, dim3(256), att_lds, st, qkv, (const float*)kcache, (const float*)vcache, cmax, (x3p_t*)out, rm);
+    att_launch((attention_k<float, 4, x3p_t, true>), grid, dim3(256), att_lds, st, qkv, (const float*)kcache, (const float*)vcache, cmax, (x3p_t*)out, rm);
     return hipGetLastError();
   }
   if (out_bf16 == 3) {   // decode, f32 parity mode: f32 output in the fragment-packed order o_proj of decode32.hip reads
     if (!decode || kv_wt == WT_BF16) return hipErrorInvalidValue;
     if (att_nbuf == 3)
-      CTTS_LAUNCH_SMEM((attention_k<float, 4, float, true, false, false, 3>), grid, dim3(256), att_lds, st, qkv, (const float*)kcache, (const float*)vcache, cmax, (float*)out, rm);
+      att_launch((attention_k<float, 4, float, true, false, false, 3>), grid, dim3(256), att_lds, st, qkv, (const float*)kcache, (const float*)vcache, cmax, (float*)out, rm);
     else
-      CTTS_LAUNCH_SMEM((attention_k<float, 4, float, true>), grid, dim3(256), att_lds, st, qkv, (const float*)kcache, (const float*)vcache, cmax, (float*)out, rm);
+      att_launch((attention_k<float, 4, float, true>), grid, dim3(256), att_lds, st, qkv, (const float*)kcache, (const float*)vcache, cmax, (float*)out, rm);
     return hipGetLastError();
   }
   if (decode && nw8 && kv_wt == WT_BF16 && out_bf16) {
-    CTTS_LAUNCH((attention_k<bf16_t, 8, bf16_t>), grid, dim3(512), st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
+    att_launch((attention_k<bf16_t, 8, bf16_t>), grid, dim3(512), 0, st, qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, cmax, (bf16_t*)out, rm);
     return hipGetLastError();
   }
-#define ATT(KT, NW, OT) CTTS_LAUNCH((attention_k<KT, NW, OT>), grid, dim3(64 * NW), st, qkv, (const KT*)kcache, (const KT*)vcache, cmax, (OT*)out, rm)
+#define ATT(KT, NW, OT) att_launch((attention_k<KT, NW, OT>), grid, dim3(64 * NW), 0, st, qkv, (const KT*)kcache, (const KT*)vcache, cmax, (OT*)out, rm)
   if (kv_wt == WT_BF16) {
     if (out_bf16) { if (decode) ATT(bf16_t, 4, bf16_t); else ATT(bf16_t, 1, bf16_t); }
     else { if (decode) ATT(bf16_t, 4, float); else ATT(bf16_t, 1, float); }
@@ -1403,7 +1442,7 @@ hipError_t launch_qkv_attention(const DecGemmArgs& d_in, const void* kcache, con
 hipError_t launch_attention_oproj(const float* qkv, const void* kcache, const void* vcache, int cmax, GptRowMap rm, int M, hipStream_t st) {
   if (rm.q_per_b != 1 || rm.desc == nullptr || !rm.wo_h || !rm.op_part || !rm.op_cnt || !rm.x32 || !rm.xp || !rm.ssq) return hipErrorInvalidValue;
   rm.sp_cus = 0; rm.sp_part = nullptr; rm.sp_cnt = nullptr;   // no remainder splitting on this path
-  CTTS_LAUNCH((attention_k<bf16_t, 4, bf16_t, true, false, false, 2, true>), dim3(NHEAD, M), dim3(256), st, qkv, (const bf16_t*)kcache,
+  att_launch((attention_k<bf16_t, 4, bf16_t, true, false, false, 2, true>), dim3(NHEAD, M), dim3(256), 0, st, qkv, (const bf16_t*)kcache,
               (const bf16_t*)vcache, cmax, (bf16_t*)nullptr, rm);
   return hipGetLastError();
 }
@@ -1524,7 +1563,15 @@ __device__ __forceinline__ float wave_minf_dpp(float v) { return -wave_max_dpp(-
 //   largest factor the repetition penalty applies to a perturbation (alpha for negative, 1 / alpha for positive scores).
 // Moving every tempered logit by less than half of min(c_arg, c_cut, c_p) changes neither the kept set nor the argmax: p / q moves by a
 // factor e^(+-2 eps) between any two tokens, a cumulative probability by e^(+-2 eps), a value gap by 2 eps.
-__global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
+// Leading arguments preloaded: what finds the row and its length -- the kernel's first loads -- leads as plain
+// parameters in order of first use; SAMPLE_LEAD is the one list the parameter list, the copy back into the struct and the launch expand.
+#define SAMPLE_LEAD(F) F(long long*, dbg) F(const RowDesc*, desc) F(const int32_t*, n_active) F(const int32_t*, row_map) F(int32_t*, len) F(int, tcap) F(int, T) F(const int32_t*, prompt_len)
+#define SAMPLE_LEAD_PARAM(T_, f) T_ lead_##f,
+#define SAMPLE_LEAD_PUT(T_, f) a.f = lead_##f;
+#define SAMPLE_LEAD_ARG(T_, f) a.f,
+__global__ __launch_bounds__(256) void sample_k(SAMPLE_LEAD(SAMPLE_LEAD_PARAM) SampleArgs a_rest) {
+  SampleArgs a = a_rest;
+  SAMPLE_LEAD(SAMPLE_LEAD_PUT)
   __shared__ int tok_s[NVQ];
   __shared__ float marg_s[NVQ];
   __shared__ int fin_s;
@@ -1888,7 +1935,7 @@ __global__ __launch_bounds__(256) void sample_k(SampleArgs a) {
 }
 
 hipError_t launch_sample(const SampleArgs& a, hipStream_t st) {
-  CTTS_LAUNCH(sample_k, dim3(a.B), dim3(256), st, a);
+  CTTS_LAUNCH(sample_k, dim3(a.B), dim3(256), st, SAMPLE_LEAD(SAMPLE_LEAD_ARG) a);
   return hipGetLastError();
 }
 
