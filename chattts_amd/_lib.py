@@ -64,6 +64,12 @@ TS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("tota
                       ("n_out", "<i4"), ("reserved", "<i4")])
 
 
+# ctts_rs_stream (80 bytes): in_off, n_in, pos, total, o_lo, n_out, out_off int64; slot, phase, c_in, c_out, pad, reserved int32
+RS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("o_lo", "<i8"), ("n_out", "<i8"),
+                      ("out_off", "<i8"), ("slot", "<i4"), ("phase", "<i4"), ("c_in", "<i4"), ("c_out", "<i4"), ("pad", "<i4"),
+                      ("reserved", "<i4")])
+
+
 class Rate(C.Structure):
     """ctts_rate: one conversion of ctts_codec_decode_windows_rate"""
     _fields_ = [("taps", P), ("L", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("reserved", C.c_int32)]
@@ -161,6 +167,10 @@ SIGNATURES = {
     "ctts_codec_windows_speed_workspace_bytes": (SZ, [I32, I32, C.c_int64]),
     "ctts_codec_decode_windows_speed": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, P, P, P, P, I32, P, P, P, I32, P, P, I32, P,
                                                   I32, P, P, I32, F, P, SZ, P]),
+    "ctts_resample_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, I32, P, I32, I32, I32, P]),
+    "ctts_codec_windows_speed_rate_workspace_bytes": (SZ, [I32, I32, C.c_int64]),
+    "ctts_codec_decode_windows_speed_rate": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, P, P, P, P, I32, P, P, P, I32, P, P, I32,
+                                                       P, P, P, P, P, P, I32, P, I32, P, I32, I32, P, P, I32, F, P, SZ, P]),
     "ctts_g711_encode_ranges": (C.c_int, [P, P, P, P, I32, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),
     "ctts_dvae_destroy": (None, [P]),

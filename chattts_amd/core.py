@@ -476,17 +476,21 @@ class Chat:
         blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None)
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts)]
 
-    def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None) -> List[np.ndarray]:
+    def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None,
+                             rs_streams=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
         (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream).  `encodings`: one per window, None / "ulaw" / "alaw" -- a
         companded window's piece is uint8, `g711.encode` of the int16 piece.  `speeds` with `ts_streams` (one entry per window; a
         speed other than 1 with the handle of its stream of the time scaler): the window's samples are pushed into that stream and
-        the piece is what the step emits, converted (CodecEngine.decode_windows(speeds=)); without them today's call, argument for
-        argument"""
+        the piece is what the step emits, converted (CodecEngine.decode_windows(speeds=)); `rs_streams` (with `speeds` and
+        `sample_rates`): the handle of the resampler's stream of a window at another speed AND rate, None otherwise; without them
+        today's call, argument for argument"""
         kw = {k: v for k, v in (("sample_rates", sample_rates), ("encodings", encodings), ("speeds", speeds)) if v is not None}
         if speeds is not None:
             kw["ts_streams"] = ts_streams
+            if rs_streams is not None:
+                kw["rs_streams"] = rs_streams
         return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, **kw)
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
@@ -560,12 +564,15 @@ class Chat:
             return self.codec.to_host(self.codec.float_to_int16(win, per_row=True)[0])
         return self.codec.to_host(win)
 
-    def _stream_piece_scaled(self, hiddens, a: int, b: Optional[int], handles, final: bool, pcm16: bool = False, encoding=None) -> np.ndarray:
+    def _stream_piece_scaled(self, hiddens, a: int, b: Optional[int], handles, final: bool, pcm16: bool = False, encoding=None,
+                             rs_handles=None) -> np.ndarray:
         """`_stream_piece` at another speed: samples [a, b) of the decode of the current prefix are PUSHED into the rows' streams of the
         time scaler (`handles`, one per row; CodecEngine.time_scale_stream_step, all rows in one launch) and the piece is what the step
         emits -- [B, 512 k] samples, possibly none; every row has had the same number of samples, so the chunk stays rectangular.
         `final`: the last push (the stream's tail); it comes back as float32 whatever `pcm16` says: the caller filters its columns
-        first.  Otherwise `pcm16` converts every row under its own peak on the device, `encoding` compands behind that."""
+        first.  Otherwise `pcm16` converts every row under its own peak on the device, `encoding` compands behind that.
+        `rs_handles` (one resampler stream per row, 24000 -> the request's rate): what the scaler's step emits is pushed on into them
+        (CodecEngine.resample_stream_step, all rows in one launch) and the piece is what THAT step emits."""
         codec = self.codec
         Tn = max(int(r.size(0)) for r in hiddens)
         total = max(0, 256 * (2 * Tn - 1))
@@ -578,6 +585,8 @@ class Chat:
         else:
             x = torch.empty((0,), dtype=torch.float32, device=self.device)
         y, off = codec.time_scale_stream_step(x, [(h, i * m, m, final) for i, h in enumerate(handles)])
+        if rs_handles:
+            y, off = codec.resample_stream_step(y, [(h, int(off[i]), int(off[i + 1] - off[i]), final) for i, h in enumerate(rs_handles)])
         y = y.view(B, int(off[1]))
         if final or not pcm16:
             return codec.to_host(y)
@@ -712,7 +721,7 @@ class Chat:
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
-              encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False):
+              encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -747,7 +756,13 @@ class Chat:
         column filter and the companding are taken on the scaled samples.  A chunk is a multiple of 512 samples and may be empty;
         the first one needs ~55-75 ms of audio beyond its frames.  Refused with a streamed speed: a `sample_rate` other than 24000
         (resampling the scaled stream would need its history and a look-ahead carried too), `split_text` (`length` pulls back
-        between batches) and `use_decoder=False`."""
+        between batches) and `use_decoder=False`.
+        `stream_scaled_resample=True` (keyword-only; with `stream_time_scale` and `stream_resample`) carries that history and
+        look-ahead: every row also gets a stream of the resampler (CodecEngine.resample_stream_step: at most K - 1 scaled samples are
+        kept on the device), the scaler's chunks are pushed into it and each yield hands out the outputs whose inputs have all
+        arrived: the chunks, concatenated, are `resample(time_scale(speed-1 stream), 24000, sample_rate)`; the 16-bit peak, the
+        tail's column filter and the companding are taken on those samples.  The first output needs width + M scaled samples
+        beyond its frame (22 at 8000 Hz: under 1 ms on top of the scaler's own)."""
         if G711.check_encoding(encoding) is not None and not pcm16:
             raise ValueError("encoding applies to 16-bit output: pass pcm16=True")
         skw = _speed_kw(speed)
@@ -756,7 +771,7 @@ class Chat:
                              "pass stream_time_scale=True to carry the path across chunks)")
         sample_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
         if stream and skw:
-            if sample_rate != CodecEngine.SAMPLE_RATE:
+            if sample_rate != CodecEngine.SAMPLE_RATE and not stream_scaled_resample:
                 raise ValueError("a streamed speed is served at 24000 Hz only (resampling the scaled stream would need its history and a "
                                  "look-ahead carried too)")
             if split_text:
@@ -771,7 +786,9 @@ class Chat:
                                  "across them, which is not implemented)")
             if split_text:
                 raise ValueError("a streamed split_text request is served at 24000 Hz only")
-            RS.plan(CodecEngine.SAMPLE_RATE, sample_rate, [0, 1])      # an unsupported pair is refused here, not at the first chunk
+            K = RS.plan(CodecEngine.SAMPLE_RATE, sample_rate, [0, 1])[2]      # an unsupported pair is refused here, not at the first chunk
+            if skw and K - 1 > RS.CARRY:
+                raise ValueError(f"a streamed speed at {sample_rate} Hz would carry up to {K - 1} samples, a resampler stream keeps {RS.CARRY}")
         rate = None if sample_rate == CodecEngine.SAMPLE_RATE else sample_rate
         if ragged_decode and stream:
             raise ValueError("ragged_decode applies to non-streamed inference only")
@@ -833,15 +850,24 @@ class Chat:
             params_infer_code.txt_smp = refer_text
         step = max_split_batch if split_text else len(text)
         ts = [] if stream and speed is not None else None      # a streamed speed: the rows' streams of the time scaler, opened at the first chunk
+        rs = [] if ts is not None and sample_rate is not None else None      # ... at another rate: and their streams of the resampler
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
-                                           encoding, speed, ts)
+                                           encoding, speed, ts, rs)
         finally:
             for h in ts or ():                                 # also when the consumer drops the generator half way
                 self.codec.time_scale_stream_close(h)
+            for h in rs or ():
+                self.codec.resample_stream_close(h)
 
-    def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts):
+    def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
+                       rs=None):
         """the batch loop of `_infer`"""
+        def open_streams(rows):
+            ts.extend(self.codec.time_scale_stream_open(speed) for _ in rows)
+            if rs is not None:
+                rs.extend(self.codec.resample_stream_open(CodecEngine.SAMPLE_RATE, sample_rate) for _ in rows)
+        rkw_s = {} if rs is None else {"rs_handles": rs}
         length = 0
         pass_batch_count = 0
         for lo in range(0, len(text), step):
@@ -881,9 +907,9 @@ class Chat:
                     skw["encoding"] = encoding
                 if ts is not None:
                     if not ts:
-                        ts.extend(self.codec.time_scale_stream_open(speed) for _ in src)
+                        open_streams(src)
                     piece = self._stream_piece_scaled(src, length, length + params_infer_code.stream_speed, ts, False, pcm16,
-                                                      encoding if pcm16 else None)
+                                                      encoding if pcm16 else None, **rkw_s)
                 else:
                     piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
@@ -896,8 +922,8 @@ class Chat:
                 skw = {"rate": sample_rate} if sample_rate is not None else {}
                 if ts is not None:
                     if not ts:
-                        ts.extend(self.codec.time_scale_stream_open(speed) for _ in last.hiddens)
-                    new_wavs = self._stream_piece_scaled(last.hiddens, length, None, ts, True)
+                        open_streams(last.hiddens)
+                    new_wavs = self._stream_piece_scaled(last.hiddens, length, None, ts, True, **rkw_s)
                 else:
                     new_wavs = self._stream_piece(last.hiddens if use_decoder else last.ids, length, None, use_decoder, **skw)
                 last.destroy()

@@ -1298,6 +1298,66 @@ extern "C" int ctts_time_scale_stream_step(const float* x, int64_t n_x, const ct
   return 0;
 }
 
+// ---- sample-rate conversion of streams: the host's arithmetic (resample.py: stream_plan) and every check a launch trusts ---------------
+static_assert(sizeof(ctts_rs_stream) == 80 && sizeof(RsStream) == 80 && offsetof(ctts_rs_stream, n_out) == offsetof(RsStream, n_out) &&
+              offsetof(ctts_rs_stream, slot) == offsetof(RsStream, slot) && offsetof(ctts_rs_stream, c_out) == offsetof(RsStream, c_out) &&
+              offsetof(ctts_rs_stream, pad) == offsetof(RsStream, pad) && CTTS_RS_CARRY == RS_CARRY, "ctts_rs_stream layout");
+// the frames j whose inputs [j M - width, j M + width + M) lie within the first p samples
+static long long rs_frames_final(long long p, long long M, long long width) { return p >= width + M ? (p - width - M) / M + 1 : 0; }
+// descriptors [lo, hi) of the host mirror: one launch's worth, all by L/M/K.  `seen`: n_slots flags, cleared here; *n_out_max: the longest chunk
+static int check_rs_streams(const char* who, const ctts_rs_stream* tab, int lo, int hi, long long n_x, long long n_y, int n_slots, int L, int M,
+                            int K, std::vector<char>& seen, long long* n_out_max) {
+  std::fill(seen.begin(), seen.end(), 0);
+  const long long width = (K - M) / 2;
+  *n_out_max = 0;
+  for (int i = lo; i < hi; ++i) {
+    const ctts_rs_stream& w = tab[i];
+    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: resampler stream %d: slot %d is outside the pool of %d", who, i, w.slot, n_slots);
+    if (seen[w.slot]) return fail("%s: resampler stream %d: slot %d appears twice in one launch", who, i, w.slot);
+    seen[w.slot] = 1;
+    if (w.phase != 0 && w.phase != 1) return fail("%s: resampler stream %d: phase %d is neither 0 nor 1", who, i, w.phase);
+    if (w.n_in < 0 || w.pos < 0 || w.in_off < 0 || w.out_off < 0 || w.o_lo < 0 || w.n_out < 0)
+      return fail("%s: resampler stream %d: a negative length, position or offset", who, i);
+    if (w.pad < 0 || w.pad > 255) return fail("%s: resampler stream %d: a pad of %d is outside 0 .. 255", who, i, w.pad);
+    if (w.pos >= (1ll << 31) || w.n_in >= (1ll << 31) || w.pos + w.n_in >= (1ll << 31))
+      return fail("%s: resampler stream %d would hold 2^31 samples or more", who, i);
+    if (w.in_off + w.n_in > n_x) return fail("%s: resampler stream %d: the push lies outside the input (%lld floats)", who, i, n_x);
+    const long long end = w.pos + w.n_in;
+    const bool fin = w.total != -1;
+    if (fin && (w.total != end || w.total < 1))
+      return fail("%s: resampler stream %d: a last push ends the stream at pos + n_in = %lld >= 1, got total %lld", who, i, end, (long long)w.total);
+    const long long e0 = rs_frames_final(w.pos, M, width) * L;
+    if (w.o_lo != e0) return fail("%s: resampler stream %d: %lld samples have emitted %lld outputs, got o_lo %lld", who, i, (long long)w.pos, e0, (long long)w.o_lo);
+    const long long e1 = fin ? (end * L + M - 1) / M : std::max(e0, rs_frames_final(end, M, width) * L);
+    if (e1 >= (1ll << 31)) return fail("%s: resampler stream %d would emit 2^31 samples or more", who, i);
+    if (w.n_out != e1 - e0) return fail("%s: resampler stream %d: the step emits %lld samples, got %lld", who, i, e1 - e0, (long long)w.n_out);
+    if (w.out_off + w.n_out + w.pad > n_y) return fail("%s: resampler stream %d: the chunk lies outside the output (%lld floats)", who, i, n_y);
+    const long long c_in = w.pos - std::max(0ll, (e0 / L) * M - width), c_out = fin ? 0 : end - std::max(0ll, (e1 / L) * M - width);
+    if (c_in > RS_CARRY || c_out > RS_CARRY)
+      return fail("%s: resampler stream %d: a carry of %lld samples exceeds the %d a slot keeps", who, i, std::max(c_in, c_out), RS_CARRY);
+    if (w.c_in != c_in || w.c_out != c_out)
+      return fail("%s: resampler stream %d: the step carries %lld samples in and %lld out, got %d and %d", who, i, c_in, c_out, w.c_in, w.c_out);
+    *n_out_max = std::max(*n_out_max, (long long)w.n_out);
+  }
+  return 0;
+}
+extern "C" int ctts_resample_stream_step(const float* x, int64_t n_x, const ctts_rs_stream* st_dev, const ctts_rs_stream* st_host,
+                                         int32_t n_streams, float* y, int64_t n_y, float* carry, int32_t n_slots, const float* taps, int32_t L,
+                                         int32_t M, int32_t K, void* stream) {
+  const char* who = "ctts_resample_stream_step";
+  if (!st_dev || !st_host || !carry) return fail("%s: a null pointer (both descriptor tables and the carry are needed)", who);
+  if (n_x < 0 || n_y < 0 || (!x && n_x) || (!y && n_y)) return fail("%s: a null pointer (x or y) with a length other than 0", who);
+  if (n_streams < 1 || n_streams > 1024) return fail("%s: need 1 <= n_streams <= 1024 (got %d)", who, n_streams);
+  if (n_slots < 1) return fail("%s: the state pool has no slot", who);
+  if (check_rs_pair(who, taps, L, M, K)) return -1;
+  std::vector<char> seen((size_t)n_slots, 0);
+  long long n_out_max = 0;
+  if (check_rs_streams(who, st_host, 0, n_streams, n_x, n_y, n_slots, L, M, K, seen, &n_out_max)) return -1;
+  CttsDeviceGuard dg(stream);
+  CK(launch_resample_stream(x, (const RsStream*)st_dev, n_streams, n_out_max, y, carry, taps, L, M, K, (hipStream_t)stream));
+  return 0;
+}
+
 // ---- window decode of time-scaled streams: crop -> stream step -> 16-bit conversion, around ONE ragged decoder pass --------------------
 // workspace = the window-decode workspace (n_win >= 1) | the scaled chunks, each from a multiple of 8 floats on | the path entries
 extern "C" size_t ctts_codec_windows_speed_workspace_bytes(int32_t n_win, int32_t total_tokens, int64_t chunk_floats) {
@@ -1306,14 +1366,23 @@ extern "C" size_t ctts_codec_windows_speed_workspace_bytes(int32_t n_win, int32_
   if (n_win && base == 0) return 0;
   return base + align_up((size_t)chunk_floats * 4 + 16);
 }
-extern "C" int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots,
-                                               int32_t hid_cap, const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win,
-                                               const ctts_window* cwin_dev, const ctts_window* cwin_host, const ctts_rs_window* crs_dev,
-                                               const ctts_rs_window* crs_host, int32_t n_conv, const ctts_ts_stream* ts_dev,
-                                               const ctts_ts_stream* ts_host, const int32_t* round_off, int32_t n_rounds, float* carry,
-                                               int32_t* state, int32_t n_ts_slots, const float* ts_window, int32_t out_type, void* out,
-                                               uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
-  const char* who = "ctts_codec_decode_windows_speed";
+// the resampler stage behind the time scaler (ctts_codec_decode_windows_speed_rate); null: there is none
+struct RsStage {
+  const ctts_rs_stream *dev, *host;
+  const int32_t *of_ts, *grp_off, *grp_rate;
+  int n_grp;
+  const ctts_rate* rates;
+  int n_rates;
+  float* carry;
+  int n_slots;
+};
+static int decode_windows_speed_body(const char* who, ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots,
+                                     int32_t hid_cap, const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win,
+                                     const ctts_window* cwin_dev, const ctts_window* cwin_host, const ctts_rs_window* crs_dev,
+                                     const ctts_rs_window* crs_host, int32_t n_conv, const ctts_ts_stream* ts_dev,
+                                     const ctts_ts_stream* ts_host, const int32_t* round_off, int32_t n_rounds, float* carry,
+                                     int32_t* state, int32_t n_ts_slots, const float* ts_window, const RsStage* rs, int32_t out_type, void* out,
+                                     uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
   if (!c || !cwin_dev || !cwin_host || !crs_dev || !crs_host || !ts_dev || !ts_host || !round_off || !carry || !state || !ts_window || !out)
     return fail("%s: a null pointer", who);
   if (n_win < 0 || n_win > 1024 || (n_win && (!hid || !win_dev || !win_host))) return fail("%s: need 0 <= n_win <= 1024 and, with windows, the store and their tables", who);
@@ -1342,20 +1411,52 @@ extern "C" int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, 
     if (r.rate >= n_ts || used[r.rate]) return fail("%s: chunk %d names stream descriptor %d of %d, or one that is taken", who, e, r.rate, n_ts);
     used[r.rate] = 1;
     const ctts_ts_stream& t = ts_host[r.rate];
-    if (r.o_lo != 0 || r.o_hi != t.n_out || r.o_hi < 0 || r.out_off != chunk_floats || t.out_off != chunk_floats)
+    const bool resampled = rs && rs->of_ts[r.rate] >= 0;       // the entry then describes the resampled chunk: checked below
+    if (t.n_out < 0 || t.out_off != chunk_floats || (!resampled && (r.o_lo != 0 || r.o_hi != t.n_out || r.out_off != chunk_floats)))
       return fail("%s: chunk %d: the scaled chunks lie one behind the other, each from a multiple of 8 floats on", who, e);
     if (t.path_off != n_path) return fail("%s: chunk %d: the path entries lie one behind the other", who, e);
-    chunk_floats += ((long long)r.o_hi + 7) & ~7ll;
+    chunk_floats += ((long long)t.n_out + 7) & ~7ll;
     n_path += ts_path_entries(t);
   }
   for (int q = 0; q < n_ts; ++q)
     if (!used[q]) return fail("%s: stream descriptor %d belongs to no chunk", who, q);
+  const long long ts_floats = chunk_floats;                    // the scaled chunks: what the resampler stage reads
+  const int n_rs = rs ? rs->grp_off[rs->n_grp] : 0;
+  if (rs) {
+    std::vector<char> taken((size_t)n_rs, 0);
+    for (int e = 0; e < n_conv; ++e) {
+      const ctts_rs_window& r = crs_host[e];
+      if (r.rate < 0 || rs->of_ts[r.rate] < 0) continue;
+      const int q = rs->of_ts[r.rate];
+      if (q >= n_rs || taken[q]) return fail("%s: chunk %d names resampler descriptor %d of %d, or one that is taken", who, e, q, n_rs);
+      taken[q] = 1;
+      const ctts_ts_stream& t = ts_host[r.rate];
+      const ctts_rs_stream& w = rs->host[q];
+      if (w.in_off != t.out_off || w.n_in != t.n_out) return fail("%s: chunk %d: the resampler's push is not the scaled chunk", who, e);
+      if (w.n_out < 0 || w.out_off != chunk_floats || w.pad != (int)(((w.n_out + 7) & ~7ll) - w.n_out) || r.o_lo != 0 || r.o_hi != w.n_out ||
+          r.out_off != w.out_off)
+        return fail("%s: chunk %d: the resampled chunks lie behind the scaled ones, one behind the other, each from a multiple of 8 floats on", who, e);
+      chunk_floats += w.n_out + w.pad;
+    }
+    for (int q = 0; q < n_rs; ++q)
+      if (!taken[q]) return fail("%s: resampler descriptor %d belongs to no chunk", who, q);
+  }
   const long long area = chunk_floats + ((n_path + 7) & ~7ll);
   const size_t need_ws = area < (1ll << 31) ? ctts_codec_windows_speed_workspace_bytes(n_win, T, area) : 0;
   if (!workspace || need_ws == 0 || ws_bytes < need_ws) return fail("codec workspace too small");
   std::vector<char> seen((size_t)n_ts_slots, 0);
   for (int r = 0; r < n_rounds; ++r)
-    if (check_ts_streams(who, ts_host, round_off[r], round_off[r + 1], n_x, chunk_floats, n_path, n_ts_slots, seen)) return -1;
+    if (check_ts_streams(who, ts_host, round_off[r], round_off[r + 1], n_x, ts_floats, n_path, n_ts_slots, seen)) return -1;
+  std::vector<long long> rs_longest((size_t)(rs ? rs->n_grp : 0), 0);
+  if (rs) {
+    std::vector<char> rs_seen((size_t)rs->n_slots, 0);
+    for (int g = 0; g < rs->n_grp; ++g) {
+      const ctts_rate& p = rs->rates[rs->grp_rate[g]];
+      if (check_rs_streams(who, rs->host, rs->grp_off[g], rs->grp_off[g + 1], ts_floats, chunk_floats, rs->n_slots, p.L, p.M, p.K, rs_seen,
+                           &rs_longest[g]))
+        return -1;
+    }
+  }
   const float* wav = nullptr;
   float* chunks = (float*)workspace;
   if (n_win) {
@@ -1369,9 +1470,58 @@ extern "C" int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, 
   for (int r = 0; r < n_rounds; ++r)      // a stream with several chunks in the call takes them one launch after the other
     CK(launch_time_scale_stream(wav, (const TsStream*)ts_dev + round_off[r], round_off[r + 1] - round_off[r], chunks, path, carry, state, ts_window,
                                 (hipStream_t)stream));
+  if (rs)                                 // behind every round of the scaler: one launch per group (a round's descriptors at one rate)
+    for (int g = 0; g < rs->n_grp; ++g) {
+      const ctts_rate& p = rs->rates[rs->grp_rate[g]];
+      CK(launch_resample_stream(chunks, (const RsStream*)rs->dev + rs->grp_off[g], rs->grp_off[g + 1] - rs->grp_off[g], rs_longest[g], chunks,
+                                rs->carry, p.taps, p.L, p.M, p.K, (hipStream_t)stream));
+    }
   CK(launch_chunks_pcm16(wav, chunks, (const CodecWindow*)cwin_dev, (const RsWindow*)crs_dev, n_conv, out_type == 0 ? 1 : 0, product, keep_thr,
                          out, keep_bits, (hipStream_t)stream));
   return 0;
+}
+extern "C" int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots,
+                                               int32_t hid_cap, const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win,
+                                               const ctts_window* cwin_dev, const ctts_window* cwin_host, const ctts_rs_window* crs_dev,
+                                               const ctts_rs_window* crs_host, int32_t n_conv, const ctts_ts_stream* ts_dev,
+                                               const ctts_ts_stream* ts_host, const int32_t* round_off, int32_t n_rounds, float* carry,
+                                               int32_t* state, int32_t n_ts_slots, const float* ts_window, int32_t out_type, void* out,
+                                               uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
+  return decode_windows_speed_body("ctts_codec_decode_windows_speed", c, hid, slot_stride, row_stride, n_slots, hid_cap, win_dev, win_host, n_win,
+                                   cwin_dev, cwin_host, crs_dev, crs_host, n_conv, ts_dev, ts_host, round_off, n_rounds, carry, state, n_ts_slots,
+                                   ts_window, nullptr, out_type, out, keep_bits, product, keep_thr, workspace, ws_bytes, stream);
+}
+
+// ---- the same with the resampler stage: crop -> time scaler's stream step -> resampler's stream step -> 16-bit conversion --------------
+extern "C" size_t ctts_codec_windows_speed_rate_workspace_bytes(int32_t n_win, int32_t total_tokens, int64_t chunk_floats) {
+  return ctts_codec_windows_speed_workspace_bytes(n_win, total_tokens, chunk_floats);
+}
+extern "C" int ctts_codec_decode_windows_speed_rate(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots,
+                                                    int32_t hid_cap, const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win,
+                                                    const ctts_window* cwin_dev, const ctts_window* cwin_host, const ctts_rs_window* crs_dev,
+                                                    const ctts_rs_window* crs_host, int32_t n_conv, const ctts_ts_stream* ts_dev,
+                                                    const ctts_ts_stream* ts_host, const int32_t* round_off, int32_t n_rounds, float* carry,
+                                                    int32_t* state, int32_t n_ts_slots, const float* ts_window, const ctts_rs_stream* rs_dev,
+                                                    const ctts_rs_stream* rs_host, const int32_t* rs_of_ts, const int32_t* grp_off,
+                                                    const int32_t* grp_rate, int32_t n_grp, const ctts_rate* rates, int32_t n_rates,
+                                                    float* rs_carry, int32_t n_rs_slots, int32_t out_type, void* out, uint8_t* keep_bits,
+                                                    int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream) {
+  const char* who = "ctts_codec_decode_windows_speed_rate";
+  if (!rs_of_ts || !grp_off) return fail("%s: a null pointer (the chunks' resampler descriptors and the group offsets are needed)", who);
+  if (n_grp < 0 || n_grp > 2048 || grp_off[0] != 0) return fail("%s: need 0 <= n_grp <= 2048, the first group at 0", who);
+  if (n_grp && (!rs_dev || !rs_host || !grp_rate || !rates || !rs_carry)) return fail("%s: a null pointer (the resampler stage's tables and carry)", who);
+  if (n_grp && n_rs_slots < 1) return fail("%s: the resampler's state pool has no slot", who);
+  if (n_rates < 0 || n_rates > 2048) return fail("%s: need 0 <= n_rates <= 2048", who);
+  for (int r = 0; r < n_rates; ++r)
+    if (check_rs_pair(who, rates[r].taps, rates[r].L, rates[r].M, rates[r].K)) return -1;
+  for (int g = 0; g < n_grp; ++g) {
+    if (grp_off[g + 1] <= grp_off[g] || grp_off[g + 1] > 2048) return fail("%s: resampler group %d is empty, or the table holds more than 2048", who, g);
+    if (grp_rate[g] < 0 || grp_rate[g] >= n_rates) return fail("%s: resampler group %d names rate %d of %d", who, g, grp_rate[g], n_rates);
+  }
+  const RsStage rs{rs_dev, rs_host, rs_of_ts, grp_off, grp_rate, n_grp, rates, n_rates, rs_carry, n_rs_slots};
+  return decode_windows_speed_body(who, c, hid, slot_stride, row_stride, n_slots, hid_cap, win_dev, win_host, n_win, cwin_dev, cwin_host, crs_dev,
+                                   crs_host, n_conv, ts_dev, ts_host, round_off, n_rounds, carry, state, n_ts_slots, ts_window, &rs, out_type, out,
+                                   keep_bits, product, keep_thr, workspace, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

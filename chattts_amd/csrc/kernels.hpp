@@ -496,6 +496,19 @@ struct RsWindow {
 // windows sel[0 .. n_launch-1] (or null: 0 .. n_launch-1) of the table, all by the same L/M; n_out_max: their longest chunk (grid size)
 hipError_t launch_resample_windows(const float* x, const RsWindow* win, float* y, const int32_t* sel, int n_launch, long long n_out_max,
                                    const float* taps, int L, int M, int K, hipStream_t st);
+#define RS_CARRY 512           // floats of one carry buffer of a resampler stream slot (a pair keeps at most K - 1); a slot has two
+// ctts_rs_stream (include/chattts_amd.h), field for field (capi.hip asserts the layout): one push of one resampler stream.
+// x[in_off, in_off + n_in) are samples [pos, pos + n_in) of the stream; total: its length when this push is the last, else -1; the step
+// emits outputs [o_lo, o_lo + n_out) of the stream's conversion to y[out_off ..], followed by `pad` zeros (< 256); slot / phase: the state
+// slot and which of its two carry buffers holds samples [pos - c_in, pos); c_out: the samples [pos + n_in - c_out, pos + n_in) it keeps
+struct RsStream {
+  long long in_off, n_in, pos, total, o_lo, n_out, out_off;
+  int32_t slot, phase, c_in, c_out, pad, reserved;
+};
+// descriptors 0 .. n_streams-1 of the table, all by the same L/M; n_out_max: their longest chunk (grid size; 0: only the carries move);
+// carry [n_slots][2][RS_CARRY] floats.  Every bound is the caller's to check
+hipError_t launch_resample_stream(const float* x, const RsStream* tab, int n_streams, long long n_out_max, float* y, float* carry,
+                                  const float* taps, int L, int M, int K, hipStream_t st);
 // the conversion behind ctts_codec_decode_windows_rate: window i's chunk is rs[i].o_hi - rs[i].o_lo floats at chunks + rs[i].out_off
 // (rs[i].rate >= 0: resampled) or rs[i].n_in floats at wav + rs[i].in_off (rate < 0: the 24 kHz crop); the output layout, the peak, the
 // conversion and the keep masks (win[i].keep) are launch_crop_pcm16_windows's

@@ -1661,6 +1661,126 @@ class CodecEngine:
         pool["rec"].update(commit)
         return (y, off, path, path_off) if return_path else (y, off)
 
+    # -- sample-rate conversion of streams: per-stream device state (csrc/resample.hip, resample_stream_k) --------------------------------
+    RS_STREAM_SLOTS = 64      # the state pool's first size; it doubles when every slot is taken
+
+    def _rs_pool(self) -> dict:
+        """the state pool: carry [slots, 2, RS.CARRY] float32 on the device, the free list, and per open stream its host record
+        [orig, new, samples pushed, outputs emitted, carry phase, done]"""
+        pool = self.__dict__.get("_rs_streams")
+        if pool is None:
+            n = int(self.RS_STREAM_SLOTS)
+            pool = self._rs_streams = dict(carry=torch.zeros((n, 2, RS.CARRY), dtype=torch.float32, device=self.device),
+                                           free=list(range(n - 1, -1, -1)), rec={})
+        return pool
+
+    def resample_stream_open(self, orig: int, new: int) -> int:
+        """A stream of the resampler from `orig` to `new` Hz: -> its handle, a slot of the engine's state pool.  The slot is fresh by
+        construction -- the first step of a stream reads no carry -- so nothing is cleared.  ValueError for a pair `resample` refuses,
+        and for one whose filter (K taps per phase) would carry more than RS.CARRY samples."""
+        L, M, K, _ = RS.plan(orig, new, [0, 1])
+        if K - 1 > RS.CARRY:
+            raise ValueError(f"resample: a stream {orig} -> {new} Hz would carry up to {K - 1} samples, a slot keeps {RS.CARRY}")
+        pool = self._rs_pool()
+        if not pool["free"]:
+            n = int(pool["carry"].shape[0])
+            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
+            pool["free"] = list(range(2 * n - 1, n - 1, -1))
+        slot = pool["free"].pop()
+        pool["rec"][slot] = [int(orig), int(new), 0, 0, 0, False]
+        return slot
+
+    def resample_stream_close(self, handle: int) -> None:
+        """gives the stream's slot back (any time: finished, or abandoned half way)"""
+        pool = self._rs_pool()
+        if pool["rec"].pop(int(handle), None) is None:
+            raise ValueError(f"resample: stream {handle} is not open")
+        pool["free"].append(int(handle))
+
+    def resample_streams_in_use(self) -> int:
+        """the streams that are open: slots of the state pool not on its free list"""
+        return len(self._rs_pool()["rec"])
+
+    def resample_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
+        """`resample.stream_plan` of the stream's next push: what a step with `n_in` more samples would emit and keep"""
+        rec = self._rs_pool()["rec"].get(int(handle))
+        if rec is None:
+            raise ValueError(f"resample: stream {handle} is not open")
+        if rec[5]:
+            raise ValueError(f"resample: stream {handle} has had its last push")
+        L, M = RS.ratio(rec[0], rec[1])
+        return RS.stream_plan(L, M, RS.geometry(L, M)[1], rec[2], rec[3], n_in, final)
+
+    def _rs_descriptors(self, pushes):
+        """pushes [(handle, in_off, n_in, final)], a stream's pushes in ITS order -> (RS_STREAM table with out_off / pad unset, sorted
+        into groups, groups: [round, (orig, new), first row, end row] -- a stream's r-th push of the call lies in round r, a round's rows
+        at one rate pair make one launch --, order: order[q] = the push behind row q, commit: handle -> its new host record).  All in
+        Python integers and before anything is launched; the records change only when the caller commits."""
+        recs = self._rs_pool()["rec"]
+        shadow, rows = {}, []
+        for i, (h, in_off, n_in, final) in enumerate(pushes):
+            h = int(h)
+            if h not in recs:
+                raise ValueError(f"resample: stream {h} is not open")
+            orig, new, pushed, emitted, phase, done, r = shadow.get(h, (*recs[h], 0))
+            if done:
+                raise ValueError(f"resample: stream {h} has had its last push")
+            L, M = RS.ratio(orig, new)
+            p = RS.stream_plan(L, M, RS.geometry(L, M)[1], pushed, emitted, n_in, final)
+            rows.append((r, (orig, new), i, (int(in_off), int(n_in), pushed, p["total"], emitted, p["n_out"], 0, h, phase, p["carry_in"],
+                                             p["carry_out"], 0, 0)))
+            shadow[h] = (orig, new, pushed + int(n_in), p["emitted"], phase ^ 1, bool(final), r + 1)
+        rows.sort(key=lambda e: e[:3])
+        tab = np.zeros(len(rows), _lib.RS_STREAM)
+        groups: list = []
+        for q, (r, pair, _, row) in enumerate(rows):
+            tab[q] = row
+            if groups and groups[-1][:2] == [r, pair]:
+                groups[-1][3] = q + 1
+            else:
+                groups.append([r, pair, q, q + 1])
+        return tab, groups, [e[2] for e in rows], {h: list(v[:6]) for h, v in shadow.items()}
+
+    def resample_stream_step(self, x: torch.Tensor, pushes):
+        """ONE step of many streams (ctts_resample_stream_step, one launch per distinct rate pair): `x`, a 1-D float32 device tensor,
+        holds the new samples of every stream; `pushes` = [(handle, in_off, n_in, final)]: x[in_off, in_off + n_in) continue stream
+        `handle` (n_in 0: nothing new), `final`: they are its last.  -> (y, off): stream i's chunk is y[off[i], off[i+1]) (possibly
+        empty; `resample_stream_plan`'s n_out); the chunks of a stream, concatenated, are `resample` of its concatenated pushes, bit
+        for bit, however they were cut.  A handle may appear once per call.  Every refusal (ValueError here, EngineError from the
+        library) comes before the first launch and leaves all streams as they were."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+            raise ValueError("resample: a contiguous 1-D float32 device tensor")
+        if len(pushes) < 1:
+            raise ValueError("resample: nothing to step")
+        if len({int(p[0]) for p in pushes}) != len(pushes):
+            raise ValueError("resample: a stream appears twice in one step")
+        for _, in_off, n_in, _ in pushes:
+            if int(in_off) < 0 or int(n_in) < 0 or int(in_off) + int(n_in) > x.numel():
+                raise ValueError("resample: a push lies outside the tensor")
+        tab, groups, order, commit = self._rs_descriptors(pushes)
+        if len(tab) > 1024:
+            raise ValueError("resample: at most 1024 streams in one step")
+        n_out = np.zeros(len(pushes), np.int64)
+        n_out[order] = tab["n_out"]
+        off = np.zeros(len(pushes) + 1, np.int64)
+        np.cumsum(n_out, out=off[1:])
+        if int(off[-1]) >= 1 << 31:
+            raise ValueError("resample: the output would hold 2^31 samples or more")
+        tab["out_off"] = off[:-1][order]
+        pool = self._rs_pool()
+        y = torch.empty((int(off[-1]),), dtype=torch.float32, device=x.device)
+        tab_d = torch.from_numpy(tab.view(np.uint8)).to(x.device)
+        st = torch.cuda.current_stream(x.device)
+        for _, (orig, new), lo, hi in groups:
+            L, M = RS.ratio(orig, new)
+            _lib.check(self.lib.ctts_resample_stream_step(
+                x.data_ptr() if x.numel() else None, x.numel(), tab_d.data_ptr() + lo * tab.itemsize, tab[lo:hi].ctypes.data_as(C.c_void_p),
+                hi - lo, y.data_ptr() if y.numel() else None, y.numel(), pool["carry"].data_ptr(), int(pool["carry"].shape[0]),
+                self._resample_taps(orig, new).data_ptr(), L, M, RS.geometry(L, M)[1], st.cuda_stream), "ctts_resample_stream_step")
+        tab_d.record_stream(st)
+        pool["rec"].update(commit)
+        return y, off
+
     def time_scale_segments(self, wav: torch.Tensor, off, speeds):
         """packed segments at ONE SPEED EACH (`speeds[i]` for segment i): requests that were decoded together and want different speeds.
         One call per run of neighbouring segments at one speed, all into one packed output; segments at speed 1 are copied, not
@@ -1892,7 +2012,7 @@ class CodecEngine:
         return wav[:, c_lo: c_hi]
 
     def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
-                       sample_rates=None, encodings=None, speeds=None, ts_streams=None):
+                       sample_rates=None, encodings=None, speeds=None, ts_streams=None, rs_streams=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -1919,8 +2039,16 @@ class CodecEngine:
         stream step -> conversion on the device (ctts_codec_decode_windows_speed), the peak, the conversion, a tail's strip and the
         companding taken on the scaled samples; still one decoder pass and one copy.  A window whose crop is empty still steps its
         stream.  Several windows of one stream are taken in the order given.  Windows at speed 1 return the bytes they return
-        without `speeds`.  A speed together with a rate other than 24000 is refused: resampling the scaled stream would need its
-        history and a look-ahead carried too."""
+        without `speeds`.  A speed together with a rate other than 24000 is refused (resampling the scaled stream needs its history
+        and a look-ahead carried too) unless `rs_streams` carries them: one entry per window, the handle of the resampler's stream
+        (`resample_stream_open(24000, rate)`) the window continues, None for a window at speed 1 or at 24000 Hz.  A window at
+        another speed AND another rate pushes its crop into its time-scale stream and the chunk that step emits into its resampler
+        stream, and yields what that second step emits (`resample_stream_step`; ctts_codec_decode_windows_speed_rate: behind the
+        scaler's rounds one resampler launch per distinct rate per round, then the one conversion launch); the peak, the
+        conversion, a tail's strip and the companding are taken on those samples.  A `tail` window is the last push of both
+        streams; several windows of one stream go to successive rounds in both stages.  Windows at speed 1 and another rate keep
+        the stateless window path of `sample_rates` and return its bytes; in a call that also holds windows at another speed they
+        take a decoder pass of their own."""
         q = None
         if speeds is not None:
             if len(speeds) != len(windows):
@@ -1928,7 +2056,7 @@ class CodecEngine:
             q = [TS.quantize(v) for v in speeds]
             if all(n == d for n, d in q):
                 q = None
-            elif sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
+            elif rs_streams is None and sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
                 raise ValueError("decode_windows: a streamed speed goes with 24000 Hz only (resampling the scaled stream would need "
                                  "its history and a look-ahead carried too)")
             elif ts_streams is None or len(ts_streams) != len(windows):
@@ -1942,7 +2070,28 @@ class CodecEngine:
                     raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
                 laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
         if q is not None:
-            return self._decode_windows_speed(store, windows, q, ts_streams, pcm16, keep_thr, product, laws)
+            rates = None
+            if sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
+                if len(sample_rates) != len(windows) or len(rs_streams) != len(windows):
+                    raise ValueError("decode_windows: one sample rate and one rs_streams entry per window")
+                rates = [int(r) for r in sample_rates]
+                alone = [i for i in range(len(windows)) if q[i][0] == q[i][1] and rates[i] != self.SAMPLE_RATE]
+                if alone:         # speed 1 at another rate: the stateless window path, in a pass of its own
+                    for i in alone:
+                        if ts_streams[i] is not None or rs_streams[i] is not None:
+                            raise ValueError(f"decode_windows: window {i} is at speed 1 but names a stream")
+                    rest = [i for i in range(len(windows)) if i not in set(alone)]
+                    pick = lambda v, idx: None if v is None else [v[i] for i in idx]
+                    out: list = [None] * len(windows)
+                    got = self._decode_windows_speed(store, pick(windows, rest), pick(q, rest), pick(ts_streams, rest), pcm16, keep_thr,
+                                                     product, pick(laws, rest), pick(rates, rest), pick(rs_streams, rest))
+                    for i, a in zip(alone, self._decode_windows_rate(store, pick(windows, alone), pick(rates, alone), pcm16, keep_thr,
+                                                                     product, pick(laws, alone))):
+                        out[i] = a
+                    for i, a in zip(rest, got):
+                        out[i] = a
+                    return out
+            return self._decode_windows_speed(store, windows, q, ts_streams, pcm16, keep_thr, product, laws, rates, rs_streams)
         if sample_rates is not None:
             if len(sample_rates) != len(windows):
                 raise ValueError("decode_windows: one sample rate per window")
@@ -2026,12 +2175,15 @@ class CodecEngine:
                                      np.int16 if pcm16 else np.float32, out)
 
     def _decode_windows_speed(self, store: torch.Tensor, windows, q, ts_streams, pcm16: bool, keep_thr: Optional[float], product: str,
-                              laws=None):
-        """`decode_windows` with at least one window at another speed than 1 (q: the windows' (num, den))"""
+                              laws=None, rates=None, rs_streams=None):
+        """`decode_windows` with at least one window at another speed than 1 (q: the windows' (num, den)).  `rates` (None: all 24000)
+        with `rs_streams`: the scaled windows that also leave 24 kHz, each with its resampler stream"""
         S, cap = self._windows_store(store)
         out: list = [None] * len(windows)
         recs = self._ts_pool()["rec"]
+        rs_recs = self._rs_pool()["rec"] if rates is not None else {}
         rows, conv, pushes = [], [], []     # decode windows; (window, decode row or None, push or None, keep); stream pushes
+        push_rs = []                        # per push: the resampler stream its chunk goes on into, or None
         for i, w in enumerate(windows):
             slot, Tn, s_lo, hi, keep = self._window_fields(i, w, S, cap, keep_thr)
             last = len(w) > 4 and bool(w[4])               # ends the stream, with or without a `keep_thr`
@@ -2040,8 +2192,18 @@ class CodecEngine:
                 h = ts_streams[i]
                 if h is None or int(h) not in recs or tuple(recs[int(h)][:2]) != tuple(q[i]):
                     raise ValueError(f"decode_windows: window {i} at speed {q[i][0]}/{q[i][1]} needs an open stream of that speed")
-            elif ts_streams[i] is not None:
+            elif ts_streams[i] is not None or (rates is not None and rs_streams[i] is not None):
                 raise ValueError(f"decode_windows: window {i} is at speed 1 but names a stream")
+            hr = None
+            if rates is not None and scaled and rates[i] != self.SAMPLE_RATE:
+                hr = rs_streams[i]
+                if hr is None or int(hr) not in rs_recs or tuple(rs_recs[int(hr)][:2]) != (self.SAMPLE_RATE, rates[i]):
+                    raise ValueError(f"decode_windows: window {i} at {rates[i]} Hz needs an open resampler stream {self.SAMPLE_RATE} -> {rates[i]}")
+                hr = int(hr)
+            elif rates is not None and rs_streams[i] is not None:
+                raise ValueError(f"decode_windows: window {i} stays at {self.SAMPLE_RATE} Hz but names a resampler stream")
+            elif rates is not None and rates[i] != self.SAMPLE_RATE:
+                raise ValueError(f"decode_windows: window {i} at speed 1 and {rates[i]} Hz takes the stateless window path")
             win = window_for_samples(Tn, s_lo, hi)
             if win is None and not scaled:
                 out[i] = self._empty_window(i, pcm16, laws)
@@ -2052,6 +2214,7 @@ class CodecEngine:
                 rows.append((slot, *win, 0, 0, 0))
             if scaled:
                 pushes.append([int(ts_streams[i]), k, 0, last])
+                push_rs.append(hr)
             conv.append((i, k, len(pushes) - 1 if scaled else None, int(keep)))
         tab = np.ascontiguousarray(np.array(rows, dtype=np.int32).reshape(-1, 8))       # ctts_window[n_win]: what is decoded
         tok, start = self._packed_crops(tab)
@@ -2075,24 +2238,58 @@ class CodecEngine:
                 rtab["o_hi"][e], rtab["out_off"][e], rtab["rate"][e] = m, chunk, r
                 chunk += (m + 7) // 8 * 8
                 paths += n_path[r]
+        # the resampler stage: every scaled chunk that leaves 24 kHz is the push of its resampler stream; the resampled chunks lie behind
+        # all scaled ones, in chunk order, and the output entry then names the resampled chunk
+        staged = [(e, pi) for e, (_, _, pi, _) in enumerate(conv) if pi is not None and push_rs[pi] is not None]
+        rs = groups = rs_commit = None
+        if staged:
+            rs, groups, rs_order, rs_commit = self._rs_descriptors(
+                [(push_rs[pi], int(ts["out_off"][rank[pi]]), int(ts["n_out"][rank[pi]]), pushes[pi][3]) for _, pi in staged])
+            rs_rank = {k: r for r, k in enumerate(rs_order)}
+            rs_of_ts = np.full(len(ts), -1, np.int32)
+            for k, (e, pi) in enumerate(staged):
+                r = rs_rank[k]
+                m = int(rs["n_out"][r])
+                rs["out_off"][r], rs["pad"][r] = chunk, -m % 8
+                rtab["o_hi"][e], rtab["out_off"][e] = m, chunk
+                rs_of_ts[rank[pi]] = r
+                chunk += m + (-m % 8)
         n = np.where(rtab["rate"] >= 0, rtab["o_hi"], rtab["n_in"]).astype(np.int64)
         lay = self._windows_layout(n, ctab[:, 5], pcm16, laws)
         parts = [tab.view(np.uint8).reshape(-1), ctab.view(np.uint8).reshape(-1), rtab.view(np.uint8), ts.view(np.uint8)]
-        blob_d = torch.from_numpy(np.concatenate(parts)).to(self.device)                 # one upload: the four tables
+        if staged:
+            parts.append(rs.view(np.uint8))
+        blob_d = torch.from_numpy(np.concatenate(parts)).to(self.device)                 # one upload: the tables
         p0 = blob_d.data_ptr()
         p1, p2 = p0 + parts[0].nbytes, p0 + parts[0].nbytes + parts[1].nbytes
         p3 = p2 + parts[2].nbytes
         pool = self._ts_pool()
         cur, tail_args = self._windows_call_tail(lay, ctab[:, 5], pcm16, product, keep_thr, self.lib.ctts_codec_windows_speed_workspace_bytes(
             len(rows), int(tok[-1]), chunk + (paths + 7) // 8 * 8))
-        _lib.check(self.lib.ctts_codec_decode_windows_speed(
-            self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap, p0 if len(rows) else None,
-            tab.ctypes.data_as(C.c_void_p) if len(rows) else None, len(rows), p1, ctab.ctypes.data_as(C.c_void_p), p2, rtab.ctypes.data_as(C.c_void_p),
-            len(conv), p3, ts.ctypes.data_as(C.c_void_p), round_off.ctypes.data_as(C.c_void_p), len(round_off) - 1, pool["carry"].data_ptr(),
-            pool["state"].data_ptr(), int(pool["carry"].shape[0]), self._time_scale_window().data_ptr(), *tail_args),
-            "ctts_codec_decode_windows_speed")
+        front = (self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap, p0 if len(rows) else None,
+                 tab.ctypes.data_as(C.c_void_p) if len(rows) else None, len(rows), p1, ctab.ctypes.data_as(C.c_void_p), p2,
+                 rtab.ctypes.data_as(C.c_void_p), len(conv), p3, ts.ctypes.data_as(C.c_void_p), round_off.ctypes.data_as(C.c_void_p),
+                 len(round_off) - 1, pool["carry"].data_ptr(), pool["state"].data_ptr(), int(pool["carry"].shape[0]),
+                 self._time_scale_window().data_ptr())
+        if staged:
+            pairs = sorted({g[1] for g in groups})
+            rate_tab = (_lib.Rate * len(pairs))()
+            for k, (orig, new) in enumerate(pairs):
+                L, M = RS.ratio(orig, new)
+                rate_tab[k].taps, rate_tab[k].L, rate_tab[k].M, rate_tab[k].K = self._resample_taps(orig, new).data_ptr(), L, M, RS.geometry(L, M)[1]
+            grp_off = np.array([g[2] for g in groups] + [groups[-1][3]], dtype=np.int32)
+            grp_rate = np.array([pairs.index(g[1]) for g in groups], dtype=np.int32)
+            rs_pool = self._rs_pool()
+            _lib.check(self.lib.ctts_codec_decode_windows_speed_rate(
+                *front, p3 + parts[3].nbytes, rs.ctypes.data_as(C.c_void_p), rs_of_ts.ctypes.data_as(C.c_void_p),
+                grp_off.ctypes.data_as(C.c_void_p), grp_rate.ctypes.data_as(C.c_void_p), len(groups), C.cast(rate_tab, C.c_void_p), len(pairs),
+                rs_pool["carry"].data_ptr(), int(rs_pool["carry"].shape[0]), *tail_args), "ctts_codec_decode_windows_speed_rate")
+        else:
+            _lib.check(self.lib.ctts_codec_decode_windows_speed(*front, *tail_args), "ctts_codec_decode_windows_speed")
         blob_d.record_stream(cur)
         pool["rec"].update(commit)
+        if staged:
+            rs_pool["rec"].update(rs_commit)
         return self._windows_finish(lay, n, ctab[:, 5], [c[0] for c in conv], laws, pcm16, out)
 
     def _windows_to_host(self, buf: torch.Tensor, n_out: int, n_g: int, off, n, keep, live, laws, dt, out: list) -> list:

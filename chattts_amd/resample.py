@@ -7,6 +7,12 @@ With orig = M and new = L (the rates divided by their gcd):
     t_i[k] = clamp(((k - width) / orig - i / new) * base, -6, 6)
     h[i][k] = (base / orig) * cos^2(pi t / 12) * sinc(t)
     y[j * new + i] = sum_k h[i][k] * x[j * orig + k - width]            (x = 0 outside the segment)
+
+Streams (`CodecEngine.resample_stream_step`, ctts_resample_stream_step): the signal arrives in pushes and its conversion leaves in chunks
+whose concatenation is the one-shot result.  Output o = j L + i reads inputs [j M - width, j M + width + M); with P' samples pushed and
+more to come, J(P') = (P' - width - M) // M + 1 frames j are complete (0 while P' < width + M) and the stream has emitted E' = J L
+outputs; the last push, which knows the total, emits the rest up to ceil(P' L / M).  Nothing below c' = max(0, (E' // L) M - width) is read
+again: the stream keeps samples [c', P'), at most K - 1 of them since J > (P' - width - M) / M (`stream_plan`, in Python integers).
 """
 from __future__ import annotations
 
@@ -20,6 +26,8 @@ ROLLOFF = 0.99
 TILE = 2048          # csrc/kernels.hpp RS_TILE: output samples per workgroup
 LDS_FLOATS = 16384   # RS_LDS_FLOATS: a tile's input span (+ the table, where both fit) in LDS
 TAB_MAX = 1 << 20    # RS_TAB_MAX: the largest table, in floats
+CARRY = 512          # RS_CARRY: floats of a stream's carry.  A stream keeps at most K - 1 samples (`stream_plan`); 24000 -> 11025 Hz, the
+#                      longest filter among the common telephony and audio rates, has K = 348
 
 
 def ratio(orig: int, new: int) -> Tuple[int, int]:
@@ -105,3 +113,37 @@ def window_inputs(L: int, M: int, K: int, o_lo: int, o_hi: int, total: int) -> T
     if o_hi == o_lo:
         return a, a
     return a, max(a, min(((o_hi - 1) // L) * M + width + M, total))
+
+
+def frames_final(p: int, M: int, width: int) -> int:
+    """J(p): the frames j whose inputs [j M - width, j M + width + M) lie within the first p samples; monotone in p"""
+    return (int(p) - width - M) // M + 1 if int(p) >= width + M else 0
+
+
+def stream_plan(L: int, M: int, K: int, pushed: int, emitted: int, n_in: int, final: bool) -> dict:
+    """One push of a stream in Python integers: `pushed` samples are in and `emitted` outputs out, `n_in` samples arrive, `final` says
+    they are the last.  -> o_lo (= emitted), n_out (the outputs the step emits: [emitted, E')), emitted (E'), carry_in / carry_out (the
+    samples kept in front of and behind the step: [c, pushed) and [c', pushed + n_in), 0 behind the last), total (-1 while not final).
+    ValueError for everything the library must not be launched with."""
+    L, M, K, pushed, emitted, n_in = int(L), int(M), int(K), int(pushed), int(emitted), int(n_in)
+    if L < 1 or M < 1 or K <= M or (K - M) % 2:
+        raise ValueError(f"resample: no table has L = {L}, M = {M}, K = {K} (K = 2 width + M)")
+    if pushed < 0 or n_in < 0 or emitted < 0:
+        raise ValueError("resample: a stream's position, output count and push cannot be negative")
+    width = (K - M) // 2
+    if emitted != frames_final(pushed, M, width) * L:
+        raise ValueError(f"resample: a stream of {pushed} samples has emitted {frames_final(pushed, M, width) * L} outputs, not {emitted}")
+    end = pushed + n_in
+    if end >= 1 << 31 or out_len(end, L, M) >= 1 << 31:
+        raise ValueError("resample: the stream would hold 2^31 samples or more")
+    if final:
+        if end < 1:
+            raise ValueError("resample: an empty stream")
+        e1 = out_len(end, L, M)
+    else:
+        e1 = max(emitted, frames_final(end, M, width) * L)
+    carry_in = pushed - max(0, (emitted // L) * M - width)
+    carry_out = 0 if final else end - max(0, (e1 // L) * M - width)
+    if carry_in > CARRY or carry_out > CARRY:
+        raise ValueError(f"resample: a carry of {max(carry_in, carry_out)} samples exceeds the {CARRY} a stream keeps")
+    return dict(o_lo=emitted, n_out=e1 - emitted, emitted=e1, carry_in=carry_in, carry_out=carry_out, total=end if final else -1)

@@ -95,7 +95,8 @@ def _have_av() -> bool:
 def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[logging.Logger] = None, infer_kwargs: Optional[dict] = None,
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
-               stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False):
+               stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
+               stream_speed_rates: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -134,7 +135,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     device behind the decode (Chat.infer(speed=) / SpeechBatcher.submit(speed=)); a speed other than 1.0 with `"stream": true` gets a 400
     -- unless `stream_speed=True` (with `speed`; default off): then a streamed request is served at its speed too, the time scaler's path
     carried across its chunks on the device -- from the pool with `batch_streams` (SpeechBatcher(stream_speeds=True).submit_stream(speed=)),
-    serially otherwise (Chat.infer(stream=True, speed=, stream_time_scale=True)); a streamed speed at a rate other than 24000 gets a 400."""
+    serially otherwise (Chat.infer(stream=True, speed=, stream_time_scale=True)); a streamed speed at a rate other than 24000 gets a 400 -- unless
+    `stream_speed_rates=True` (with `speed`, `stream_speed` and the rate in `stream_sample_rates`; default off): then such a request is
+    served, the scaled stream resampled with the filter's history and look-ahead carried on the device -- from the pool when it can take
+    it (SpeechBatcher(stream_speeds=True, stream_speed_rates=True).submit_stream(speed=, sample_rate=)), serially otherwise
+    (Chat.infer(..., stream_time_scale=True, stream_resample=True, stream_scaled_resample=True)); with `g711`, companded too."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -150,12 +155,15 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     if batcher is None and batch_slots is not None:
         from .serving import SpeechBatcher
         batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode, streams=bool(batch_streams),
-                                **({"refine": True} if batch_refine else {}), **({"stream_speeds": True} if speed and stream_speed else {}))
+                                **({"refine": True} if batch_refine else {}), **({"stream_speeds": True} if speed and stream_speed else {}),
+                                **({"stream_speed_rates": True} if speed and stream_speed and stream_speed_rates else {}))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
     pool_streams = bool(batch_streams) and batcher is not None and bool(getattr(batcher, "streams", False))
     pool_stream_speeds = pool_streams and bool(speed and stream_speed) and bool(getattr(batcher, "stream_speeds", False))
+    speed_rates = bool(speed and stream_speed and stream_speed_rates)
+    pool_stream_speed_rates = pool_stream_speeds and speed_rates and bool(getattr(batcher, "stream_speed_rates", False))
     pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
     pool_split = bool(batch_split) and batcher is not None
     allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
@@ -226,6 +234,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             kw = {**kw, "stream_resample": True, "split_text": False}
         if req.stream and spd is not None:           # likewise for a stream at another speed
             kw = {**kw, "stream_time_scale": True, "split_text": False}
+            if rate != SAMPLE_RATE:                  # ... and another rate: the resampler's history and look-ahead are carried
+                kw = {**kw, "stream_scaled_resample": True}
         return chat.infer(text=[req.input], stream=bool(req.stream), lang=None, skip_refine_text=True, refine_text_only=False,
                           use_decoder=True, do_text_normalization=True, do_homophone_replacement=True,
                           params_infer_code=code_params(req.voice), pcm16=True, **kw)
@@ -267,7 +277,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             if req.stream and not stream_speed:
                 raise HTTPException(400, detail=f"speed {req.speed} is served for non-streamed requests only: a stream's chunks are "
                                                 f"produced at speed 1.0 (the time scaler's path is not carried across chunks)")
-            if req.stream and rate != SAMPLE_RATE:
+            if req.stream and rate != SAMPLE_RATE and not speed_rates:
                 raise HTTPException(400, detail=f"a streamed speed is served at {SAMPLE_RATE} Hz only: speed {req.speed} with sample_rate {rate} "
                                                 f"would need the scaled stream's history and a look-ahead carried into the resampler")
             spd = int(round(100.0 * req.speed)) / 100
@@ -305,7 +315,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 return pcm.tobytes()
             return _av_encode(pcm, fmt, rate)
 
-        if req.stream and pool_streams and (spd is None or pool_stream_speeds):
+        if req.stream and pool_streams and (spd is None or (pool_stream_speeds and (rate == SAMPLE_RATE or pool_stream_speed_rates))):
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
                 skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
                 if spd is not None:

@@ -658,6 +658,7 @@ class _Job:
     in_text_pool: bool = False             # the refine-text pass of an unsplit request is queued or resident
     speed: Optional[float] = None          # None: 1.0 (on a stream only with SpeechBatcher(stream_speeds=True))
     ts_slot: Optional[int] = None          # a stream at another speed: its stream of the time scaler, opened at its first chunk
+    rs_slot: Optional[int] = None          # ... and at another rate: its stream of the resampler, opened with it
 
     @property
     def is_stream(self) -> bool:
@@ -729,6 +730,10 @@ class SpeechBatcher:
     Its job record holds a stream of the time scaler (`CodecEngine.time_scale_stream_open`, opened at its first chunk, given back
     in `_resolve` however the request ends); the chunks due at one poll -- at whatever speeds, speed 1 among them -- still come from
     one window decode (`CodecEngine.decode_windows(speeds=, ts_streams=)`); `occupancy()["stream_scaled_chunks"]` counts them.
+    `stream_speed_rates=True` (with `stream_speeds`; off: a streamed speed at another rate than 24000 is refused as before): such a
+    request's job also holds a stream of the resampler (`CodecEngine.resample_stream_open(24000, rate)`, opened and given back where
+    the time scaler's is) and its chunks are the scaler's chunks resampled with the filter's history and look-ahead carried
+    (`decode_windows(..., rs_streams=)`): those of the serial call with `stream_scaled_resample=True`.
 
     `refine=True`: requests may ask for the reference's DEFAULT behaviour, the refine-text pass in front of the code pass
     (`submit(text, params, refine=RefineTextParams(...))`).  A second, TEXT-mode per-request pool (SlotPool(infer_text=True), its own
@@ -760,7 +765,7 @@ class SpeechBatcher:
 
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
                  logger=None, ragged_decode: bool = False, streams: bool = False, refine: bool = False, make_text_pool=None,
-                 text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False):
+                 text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False, stream_speed_rates: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
@@ -772,6 +777,7 @@ class SpeechBatcher:
         self.stream_chunks = 0        # chunks those decodes served (empty chunks included)
         self.stream_resampled_chunks = 0   # those of them at another rate than 24 kHz
         self.stream_speeds = bool(stream_speeds)   # submit_stream(speed=) is accepted
+        self.stream_speed_rates = bool(stream_speeds and stream_speed_rates)   # ... at another rate than 24000 too
         self.stream_scaled_chunks = 0      # chunks of streams at another speed than 1
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.max_stream_group = 0     # most chunks one window decode served
@@ -861,12 +867,13 @@ class SpeechBatcher:
         pass and ONE companding launch whatever their encodings (CodecEngine.decode_windows(encodings=)).  `speed` other than 1 is
         refused: a chunk's frames depend on the path of everything before it, which is not carried across chunks -- unless the
         batcher was built with `stream_speeds=True`: then the chunks are those of the serial call with `speed=, stream_time_scale=True`
-        (the path and a tail of samples are carried on the device, per stream), at 24000 Hz only."""
+        (the path and a tail of samples are carried on the device, per stream), at 24000 Hz only -- unless it was also built with
+        `stream_speed_rates=True`: then `speed` goes with `sample_rate`, the serial call's `stream_scaled_resample=True`."""
         G711.check_encoding(encoding)
         speed = _job_speed(speed)
         if speed is not None and not self.stream_speeds:
             raise ValueError("speed applies to non-streamed requests only (a chunk's frames depend on the path of everything before it)")
-        if speed is not None and self._rate(sample_rate) is not None:
+        if speed is not None and self._rate(sample_rate) is not None and not self.stream_speed_rates:
             raise ValueError("a streamed speed is served at 24000 Hz only (resampling the scaled stream would need its history and a "
                              "look-ahead carried too)")
         if split_text:
@@ -876,7 +883,9 @@ class SpeechBatcher:
         self._check_refine(refine)
         rate = self._rate(sample_rate)
         if rate is not None:
-            RS.plan(24000, rate, [0, 1])       # an unsupported pair is refused here, not at the first chunk
+            K = RS.plan(24000, rate, [0, 1])[2]       # an unsupported pair is refused here, not at the first chunk
+            if speed is not None and K - 1 > RS.CARRY:
+                raise ValueError(f"a streamed speed at {rate} Hz would carry up to {K - 1} samples, a resampler stream keeps {RS.CARRY}")
         h = SpeechStream(self, next(self._ids))
         self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed))
         return h
@@ -924,6 +933,9 @@ class SpeechBatcher:
         if job.ts_slot is not None:        # finished, failed or cancelled: its stream of the time scaler goes back to the pool
             slot, job.ts_slot = job.ts_slot, None
             self.chat.codec.time_scale_stream_close(slot)
+        if job.rs_slot is not None:        # ... and its stream of the resampler
+            slot, job.rs_slot = job.rs_slot, None
+            self.chat.codec.resample_stream_close(slot)
         failed = isinstance(result, BaseException)
         if cancelled:
             self.cancelled += job.is_stream
@@ -1164,7 +1176,11 @@ class SpeechBatcher:
                 for j in jobs:
                     if j.speed is not None and j.ts_slot is None:
                         j.ts_slot = self.chat.codec.time_scale_stream_open(j.speed)
+                    if j.speed is not None and j.sample_rate is not None and j.rs_slot is None:
+                        j.rs_slot = self.chat.codec.resample_stream_open(24000, j.sample_rate)
                 kw["ts_streams"] = [j.ts_slot for j in jobs]
+                if any(j.rs_slot is not None for j in jobs):
+                    kw["rs_streams"] = [j.rs_slot for j in jobs]
             pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **kw)
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for job in dict.fromkeys(jobs):

@@ -535,6 +535,59 @@ int ctts_codec_decode_windows_speed(ctts_codec* c, const float* hid, int64_t slo
                                     float* carry, int32_t* state, int32_t n_ts_slots, const float* ts_window, int32_t out_type, void* out,
                                     uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes, void* stream);
 
+/* Sample-rate conversion of streams: the signal of a stream arrives in pushes -- it exists nowhere as a whole, like the time scaler's
+ * stream -- its conversion leaves in chunks, and the concatenation of the chunks is ctts_resample_ragged's result on the whole signal, bit
+ * for bit, however the signal is cut.  Output o = j L + i reads inputs [j M - width, j M + width + M), width = (K - M) / 2.  With
+ * P' = pos + n_in samples in and more to come, J(P') = (P' - width - M) / M + 1 frames j are complete (0 while P' < width + M): the step
+ * emits outputs [o_lo, E'), o_lo = J(pos) L, E' = J(P') L -- possibly nothing; the last push knows total = P' and emits the rest up to
+ * ceil(total L / M), inputs at or beyond total reading as zero.  Afterwards nothing below c' = max(0, (E' / L) M - width) is read again: a
+ * slot keeps samples [c', P'), at most K - 1 of them (J > (P' - width - M) / M), within CTTS_RS_CARRY floats.
+ * carry: [n_slots][2][CTTS_RS_CARRY] float32 on the device, two buffers per slot: a step reads buffer `phase` and writes the other, so the
+ * caller flips `phase` after every accepted step of a slot.  A slot is fresh by its descriptor alone: at pos == 0 no carry is read.
+ * One launch over descriptors that share one L/M; the table is given on the device and the host (the two must agree).  x and y may be null
+ * where n_x, n_y is 0.  Refused before anything is launched, from the host mirror: a null pointer, a pair ctts_resample_supported refuses,
+ * n_streams outside 1 .. 1024, a negative length, position or offset, a pad outside 0 .. 255, 2^31 samples, a push outside x, a total that
+ * is neither -1 nor pos + n_in (>= 1), o_lo other than J(pos) L, n_out other than the plan's, a chunk (with its pad) outside y, c_in / c_out
+ * other than the plan's or above CTTS_RS_CARRY, a phase other than 0 / 1, a slot outside the pool or named twice in the call. */
+#define CTTS_RS_CARRY 512
+typedef struct {
+  int64_t in_off, n_in;   /* the new samples: x[in_off, in_off + n_in) */
+  int64_t pos;            /* samples pushed before them */
+  int64_t total;          /* the stream's length when this push is the last; -1 otherwise */
+  int64_t o_lo;           /* outputs emitted before this step */
+  int64_t n_out;          /* outputs this step emits */
+  int64_t out_off;        /* first output float in y */
+  int32_t slot, phase;    /* state slot; which of its two carry buffers holds samples [pos - c_in, pos) */
+  int32_t c_in, c_out;    /* samples of carry in front of the step; samples [pos + n_in - c_out, pos + n_in) kept behind it (0 on the last push) */
+  int32_t pad;            /* zeros written behind the chunk */
+  int32_t reserved;
+} ctts_rs_stream;         /* 80 bytes */
+int ctts_resample_stream_step(const float* x, int64_t n_x, const ctts_rs_stream* st_dev, const ctts_rs_stream* st_host, int32_t n_streams,
+                              float* y, int64_t n_y, float* carry, int32_t n_slots, const float* taps, int32_t L, int32_t M, int32_t K,
+                              void* stream);
+
+/* ctts_codec_decode_windows_speed with the resampler stage behind the time scaler: a chunk may also be a scaled AND resampled one.
+ * Everything up to the time scaler's rounds is as there.  rs_of_ts (host, one entry per time-scale descriptor): -1, or the resampler stream
+ * descriptor rs[q] the scaled chunk is pushed into, each named once.  Then rs[q].in_off / n_in = that descriptor's out_off / n_out (the
+ * scaled chunk in the workspace), and the output entry of the chunk has o_lo = 0, o_hi = rs[q].n_out, out_off = rs[q].out_off: the resampled
+ * chunks lie behind ALL scaled chunks, one behind the other in chunk order, each from a multiple of 8 floats on (pad = the rest to it).
+ * The resampler descriptors are sorted into groups (grp_off: n_grp + 1 ascending indices, grp_rate: the group's entry of `rates`; host):
+ * one launch per group after the time scaler's rounds, in the order given -- a stream with several chunks in the call takes them in
+ * successive groups; within a group a slot appears once.  n_rs = grp_off[n_grp] may be 0 (n_grp 0): the call is
+ * ctts_codec_decode_windows_speed.  Everything that call and ctts_resample_stream_step refuse is refused here, before any launch.
+ * Workspace: ..._workspace_bytes(n_win, total_tokens, sum ceil8(scaled n_out) + sum ceil8(resampled n_out) + ceil8(path entries)). */
+size_t ctts_codec_windows_speed_rate_workspace_bytes(int32_t n_win, int32_t total_tokens, int64_t chunk_floats);
+int ctts_codec_decode_windows_speed_rate(ctts_codec* c, const float* hid, int64_t slot_stride, int64_t row_stride, int32_t n_slots,
+                                         int32_t hid_cap, const ctts_window* win_dev, const ctts_window* win_host, int32_t n_win,
+                                         const ctts_window* cwin_dev, const ctts_window* cwin_host, const ctts_rs_window* crs_dev,
+                                         const ctts_rs_window* crs_host, int32_t n_conv, const ctts_ts_stream* ts_dev,
+                                         const ctts_ts_stream* ts_host, const int32_t* round_off, int32_t n_rounds, float* carry, int32_t* state,
+                                         int32_t n_ts_slots, const float* ts_window, const ctts_rs_stream* rs_dev, const ctts_rs_stream* rs_host,
+                                         const int32_t* rs_of_ts, const int32_t* grp_off, const int32_t* grp_rate, int32_t n_grp,
+                                         const ctts_rate* rates, int32_t n_rates, float* rs_carry, int32_t n_rs_slots, int32_t out_type,
+                                         void* out, uint8_t* keep_bits, int32_t product, float keep_thr, void* workspace, size_t ws_bytes,
+                                         void* stream);
+
 /* G.711 companding behind the PCM16 conversion: 16-bit PCM -> one byte per sample, mu-law (law 0) or A-law (law 1), the ITU-T G.191 map
  * (a negative sample is companded from its ones' complement, so G(~x) == G(x) ^ 0x80; chattts_amd/g711.py is the NumPy twin):
  *   mu: a = min((mag >> 2) + 33, 0x1FFF), seg = 1 + bits(a >> 6), code = ((8 - seg) << 4) | (0xF - ((a >> seg) & 0xF)), | 0x80 when lin >= 0

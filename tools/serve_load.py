@@ -26,7 +26,7 @@ resampled on the device) in one process, the same figures, and one stream alone 
 companded on the device behind the conversion) in one process, the same figures, and one stream alone on both legs, alternating: the
 G.711 leg's first-byte p50 beside the PCM16 leg's, and the PCM16 leg's own run-to-run spread to judge the difference against.
 
---stream --speed V: instead, the pooled streams (`batch_streams` on) at speed 1 and at V (`speed=True, stream_speed=True`: every chunk is what its
+--stream --speed V [--sample-rate HZ [--encoding ulaw|alaw]]: instead, the pooled streams (`batch_streams` on) at speed 1 and at V (`speed=True, stream_speed=True`: every chunk is what its
 push into the request's stream of the time scaler made final), then one stream alone on both legs, alternating, --repeat times.
 --ragged-decode: also the batched burst with `create_app(..., ragged_decode=True)` (the requests that finish in one poll decoded in one
 ragged pass) -- an A/B against the default batched burst (one decode per request), with both runs' decode-call counts.
@@ -100,13 +100,15 @@ def stream_burst(chat, voices, n, slots, batch_streams, ragged_decode=False, app
     once it is complete): the clock of a request stops at its first body message that carries audio, and at its last message.
     `rate`: the streams ask for that sample rate (`stream_sample_rates`; None: 24 kHz, the body carries no rate).  `encoding`: the streams
     ask for raw G.711 ("ulaw" / "alaw": `g711=True`, one byte per sample).  `speed`: the streams carry that speed (`speed=True,
-    stream_speed=True`: the time scaler's path carried across their chunks); the audio seconds counted are those of the scaled stream"""
+    stream_speed=True`: the time scaler's path carried across their chunks; with `rate` also `stream_speed_rates=True`: the scaled stream
+    resampled with the filter's history carried); the audio seconds counted are those of the scaled stream"""
     import asyncio
     own = app is None
     if own:
         app = server.create_app(chat, voices, batch_slots=slots, ragged_decode=ragged_decode, batch_streams=batch_streams,
                                 **({} if rate is None else {"stream_sample_rates": (int(rate),)}), **({} if encoding is None else {"g711": True}),
-                                **({} if speed is None else {"speed": True, "stream_speed": True}))
+                                **({} if speed is None else {"speed": True, "stream_speed": True}),
+                                **({"stream_speed_rates": True} if speed is not None and rate is not None else {}))
     names = sorted(voices)
     more = {**({} if rate is None else {"sample_rate": int(rate)}), **({} if speed is None else {"speed": float(speed)})}
 
@@ -172,15 +174,19 @@ def stream_rate_main(chat, voices, a):
 
 
 def stream_speed_main(chat, voices, a):
-    """--stream --speed V: the pooled streams at speed 1 and at V in one process, then one stream alone on both, alternating"""
-    base = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode)
-    at = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode, speed=a.speed)
+    """--stream --speed V [--sample-rate R [--encoding E]]: the pooled streams at speed 1 and at V (both at R Hz, as E, when given) in one
+    process, then one stream alone on both, alternating"""
+    rate = None if a.sample_rate is None or int(a.sample_rate) == server.SAMPLE_RATE else int(a.sample_rate)
+    fmt = dict(rate=rate, encoding=a.encoding)
+    base = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode, **fmt)
+    at = stream_burst(chat, voices, a.n, a.slots, True, a.ragged_decode, speed=a.speed, **fmt)
     single = {"1.0": [], str(a.speed): []}
     for _ in range(a.repeat):
         for v in (None, a.speed):
-            single[str(v or 1.0)].append(stream_burst(chat, voices, 1, a.slots, True, a.ragged_decode, speed=v)["first_byte_p50_s"])
+            single[str(v or 1.0)].append(stream_burst(chat, voices, 1, a.slots, True, a.ragged_decode, speed=v, **fmt)["first_byte_p50_s"])
     p50 = {k: round(float(np.percentile(v, 50)), 4) for k, v in single.items()}
-    print(json.dumps(dict(metric="serve_load_stream_speed", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, speed=a.speed, at_1=base,
+    print(json.dumps(dict(metric="serve_load_stream_speed", n=a.n, slots=a.slots, max_new=a.max_new, dtype=a.dtype, speed=a.speed, sample_rate=rate or 24000,
+                          encoding=a.encoding, at_1=base,
                           at_speed=at, single_stream_first_byte_s=single, single_stream_first_byte_p50_s=p50,
                           single_stream_p50_delta_s=round(p50[str(a.speed)] - p50["1.0"], 4),
                           speed_1_spread_s=round(max(single["1.0"]) - min(single["1.0"]), 4))))

@@ -9,10 +9,12 @@
   * --stream  : instead, the streamed scaler (ctts_time_scale_stream_step, one launch): 1, 8 and 64 streams in their steady state, each
                 pushed 12 000 samples per step, at speeds 0.5, 1.25 and 2.0 -- device time of one step from events around `--reps`
                 back-to-back steps on pre-uploaded descriptor tables, after warm steps, and the frames a step runs
+  * --stream --sample-rate HZ : also the streamed resampler behind it (ctts_resample_stream_step, one launch): the same streams, each
+                pushed what the scaler's step emits for 12 000 samples, converted 24000 -> HZ -- device time of one step, the same way
 
 Synthetic weights, noise input (the kernels' work does not depend on the samples).  Prints one JSON line.  Not a bench.py leg.
 
-    python tools/time_scale_probe.py [--reps 20] [--gemm f16] [--stream]
+    python tools/time_scale_probe.py [--reps 20] [--gemm f16] [--stream [--sample-rate 8000]]
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from chattts_amd import timescale as TS  # noqa: E402
+from chattts_amd import resample as RS, timescale as TS  # noqa: E402
 from chattts_amd.core import Chat  # noqa: E402
 from chattts_amd.weights import synthetic_all  # noqa: E402
 
@@ -104,6 +106,50 @@ def _stream_step_ms(codec, n_streams, speed, reps, push=12000, warm=3):
     return round(a.elapsed_time(b) / reps, 4), round(float(np.mean(frames[warm:])), 2)
 
 
+def _resample_step_ms(codec, n_streams, speed, rate, reps, push=12000, warm=3):
+    """device time of one step of `n_streams` resampler streams 24000 -> `rate`, each pushed the chunk the scaler's step at `speed` emits
+    for `push` samples, and the samples a step emits per stream"""
+    from chattts_amd import _lib
+    dev = codec.device
+    pool = codec._rs_pool()
+    assert n_streams <= int(pool["carry"].shape[0])
+    L, M = RS.ratio(24000, rate)
+    K = RS.geometry(L, M)[1]
+    taps = codec._resample_taps(24000, rate)
+    plans, pushed, emitted = [], 0, 0
+    for r in range(warm + reps):
+        n_in = TS.stream_plan(speed, r * push, push, False)["n_out"]
+        p = RS.stream_plan(L, M, K, pushed, emitted, n_in, False)
+        plans.append((n_in, pushed, p))
+        pushed, emitted = pushed + n_in, p["emitted"]
+    n_max, o_max = max(n for n, _, _ in plans), max(p["n_out"] for _, _, p in plans)
+    x = torch.rand(n_streams * n_max, device=dev) * 2 - 1
+    y = torch.empty(max(1, n_streams * o_max), dtype=torch.float32, device=dev)
+    tabs = []
+    for r, (n_in, pos, p) in enumerate(plans):
+        tab = np.zeros(n_streams, _lib.RS_STREAM)
+        for i in range(n_streams):
+            tab[i] = (i * n_max, n_in, pos, -1, p["o_lo"], p["n_out"], i * o_max, i, r & 1, p["carry_in"], p["carry_out"], 0, 0)
+        tabs.append((tab, torch.from_numpy(tab.view(np.uint8)).to(dev)))
+    st = torch.cuda.current_stream(dev).cuda_stream
+
+    def call(r):
+        tab, tab_d = tabs[r]
+        rc = codec.lib.ctts_resample_stream_step(x.data_ptr(), x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), n_streams, y.data_ptr(),
+                                                 y.numel(), pool["carry"].data_ptr(), int(pool["carry"].shape[0]), taps.data_ptr(), L, M, K, st)
+        assert rc == 0, codec.lib.ctts_last_error()
+    for r in range(warm):
+        call(r)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for r in range(warm, warm + reps):
+        call(r)
+    b.record()
+    b.synchronize()
+    return round(a.elapsed_time(b) / reps, 4), round(float(np.mean([p["n_out"] for _, _, p in plans[warm:]])), 1)
+
+
 def _wall_ms(fn, reps):
     fn()
     fn()
@@ -122,6 +168,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--gemm", default="f16")
     ap.add_argument("--stream", action="store_true", help="the streamed scaler's step instead")
+    ap.add_argument("--sample-rate", type=int, default=None, help="--stream: also the streamed resampler's step behind it, 24000 -> this rate")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_scale_probe needs a GPU: nothing here can be timed without one")
@@ -137,6 +184,11 @@ def main():
                 out["step_ms"][f"{n}x@{speed}"] = ms
                 out["frames_per_step"][str(speed)] = frames
                 out["us_per_frame"][f"{n}x@{speed}"] = round(1e3 * ms / frames, 2)
+                if a.sample_rate is not None and a.sample_rate != 24000:
+                    ms, n_out = _resample_step_ms(codec, n, speed, a.sample_rate, a.reps)
+                    out.setdefault("sample_rate", a.sample_rate)
+                    out.setdefault("resample_step_ms", {})[f"{n}x@{speed}"] = ms
+                    out.setdefault("resampled_per_step", {})[str(speed)] = n_out
         print(json.dumps(out))
         return
     chat = Chat()
