@@ -1932,7 +1932,15 @@ extern "C" int ctts_k_exp_draws(uint64_t seed, int32_t step, int32_t row0, int32
 }
 extern "C" int ctts_k_dwconv_ln(const float* x, const float* w, const float* b, const float* ln_w, const float* ln_b, float eps,
                                 int32_t dil, float* y, int32_t B, int32_t F, void* stream) {
-  CK(launch_dwconv_ln(x, w, b, ln_w, ln_b, eps, dil, y, B, F, 512, (hipStream_t)stream));
+  return ctts_k_dwconv_ln_ex(x, w, b, ln_w, ln_b, eps, dil, y, B, F, 512, nullptr, 0, nullptr, stream);
+}
+extern "C" int ctts_k_dwconv_ln_ex(const float* x, const float* w, const float* b, const float* ln_w, const float* ln_b, float eps,
+                                   int32_t dil, float* y, int32_t B, int32_t F, int32_t C, uint16_t* yp, int32_t plane_f16,
+                                   const int32_t* seg, void* stream) {
+  const hipError_t e = launch_dwconv_ln(x, w, b, ln_w, ln_b, eps, dil, y, B, F, C, (hipStream_t)stream, yp, plane_f16, (const int2*)seg);
+  if (e != hipSuccess)
+    return fail("ctts_k_dwconv_ln_ex: launch_dwconv_ln refused B %d, F %d, C %d, dil %d, planes %s, seg %s: %s", B, F, C, dil,
+                yp ? (plane_f16 ? "fp16" : "bf16 hi/lo") : "none", seg ? "yes" : "no", hipGetErrorString(e));
   return 0;
 }
 extern "C" int ctts_k_layernorm(const float* x, const float* w, const float* b, float eps, float* y, int32_t rows, void* stream) {

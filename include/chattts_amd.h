@@ -778,6 +778,12 @@ int ctts_k_sample_text(const ctts_gen_state* s, const float* logits, int32_t n_t
 int ctts_k_exp_draws(uint64_t seed, int32_t step, int32_t row0, int32_t rows, int32_t V, float* out, void* stream);
 int ctts_k_dwconv_ln(const float* x, const float* w, const float* b, const float* ln_w, const float* ln_b, float eps, int32_t dil,
                      float* y, int32_t B, int32_t F, void* stream);
+/* the whole depthwise conv + LayerNorm launcher (kernel tests): C = 512 | 256; yp != NULL: the normalised rows go out as planes in the
+ * codec GEMMs' fragment order instead of to y (C = 512 only) -- hi | lo bf16 planes [rows/32][C/16][2][64][8], or with plane_f16 ONE
+ * fp16 plane [rows/32][C/16][64][8]; seg != NULL: B = 1 and the F frames are packed segments, seg = device int32 [F][2], frame f's
+ * segment [lo, hi) (C = 512 only).  Returns -1 with a message when the launcher refuses the combination; nothing is launched then. */
+int ctts_k_dwconv_ln_ex(const float* x, const float* w, const float* b, const float* ln_w, const float* ln_b, float eps, int32_t dil,
+                        float* y, int32_t B, int32_t F, int32_t C, uint16_t* yp, int32_t plane_f16, const int32_t* seg, void* stream);
 int ctts_k_layernorm(const float* x, const float* w, const float* b, float eps, float* y, int32_t rows, void* stream);
 int ctts_k_istft(const float* head, const float* window, const float* twiddle, float* frames, float* wav, int32_t B, int32_t F, void* stream);
 

@@ -320,12 +320,22 @@ def test_a_failure_fails_that_request_only_and_frees_its_slots():
 
 def test_cancel_covers_every_sentence():
     b, chat, pools, lock = _batcher(slots=2)
+    pool = pools.setdefault("code", _Pool(2, lock))          # the pool the batcher's make_pool hands out
+    resident, queued, poll = threading.Event(), threading.Event(), pool.poll
+
+    def gated_poll(events=False):
+        # the worker stops with sentences b and c resident until the cancel is queued (it takes it at its next `_between`): the test
+        # thread does not have to catch the 500 polls of a sentence, which a loaded machine runs through between two of its looks
+        if len(pool.active) >= 2:
+            resident.set()
+            queued.wait(10)
+        return poll(events)
+    pool.poll = gated_poll
     try:
         fut = b.submit("a#4000\nb#4000\nc#4000", _Params(spk_smp="V", max_new=40), split_text=True)
-        deadline = time.time() + 10
-        while len(pools.get("code", _Pool(1, lock)).active) < 2 and time.time() < deadline:
-            time.sleep(0.01)
+        assert resident.wait(10), "sentences b and c never became resident"
         b.cancel(fut)
+        queued.set()
         with pytest.raises(CancelledError):
             fut.result(timeout=30)
         _wait_idle(pools)
