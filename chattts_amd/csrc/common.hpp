@@ -143,6 +143,42 @@ __device__ __forceinline__ u128 load16_sc1(const void* p) {
   r.x = (uint32_t)a; r.y = (uint32_t)(a >> 32); r.z = (uint32_t)b; r.w = (uint32_t)(b >> 32);
   return r;
 }
+// ---- publishing stores: results of a decode-step kernel that a LATER launch reads -------------------------------------------------
+// A plain store leaves its line dirty in the L2 of the XCD it ran on, and the release at the end of the launch has to write every such
+// line back before the next launch of the chain may start.  These store WRITE-THROUGH (`sc1`, never `nt`): the bytes leave while the
+// kernel still runs and the release finds a clean L2 ("results published write-through"; MI355X guide, Guideline 16
+// R1 for the forms).  Same value, same address, same width as the plain store each replaces; readers are later launches behind their
+// acquire and load as before.  publishN stores the N bytes of `v` at `p` (N-byte aligned, as the plain store it replaces required).
+// -DCTTS_PLAIN_PUBLISH=1 (python -m chattts_amd.build --variant plainpub -DCTTS_PLAIN_PUBLISH=1) turns them back into plain stores:
+// the A/B build of profiles/r9B, selected through CTTS_LIB.
+#ifndef CTTS_PLAIN_PUBLISH
+#define CTTS_PLAIN_PUBLISH 0
+#endif
+template <typename U, typename T>
+__device__ __forceinline__ void publish_small(void* p, const T& v) {
+  static_assert(sizeof(T) == sizeof(U), "publishN stores exactly N bytes");
+#if CTTS_PLAIN_PUBLISH
+  *reinterpret_cast<T*>(p) = v;
+#else
+  __hip_atomic_store(reinterpret_cast<U*>(p), __builtin_bit_cast(U, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // global_store_* ... sc1
+#endif
+}
+template <typename T> __device__ __forceinline__ void publish1(void* p, const T& v) { publish_small<uint8_t>(p, v); }
+template <typename T> __device__ __forceinline__ void publish2(void* p, const T& v) { publish_small<uint16_t>(p, v); }
+template <typename T> __device__ __forceinline__ void publish4(void* p, const T& v) { publish_small<uint32_t>(p, v); }
+template <typename T> __device__ __forceinline__ void publish8(void* p, const T& v) { publish_small<unsigned long long>(p, v); }
+// 16 bytes: no builtin lowers to a 16-byte sc1 store of a per-lane address, so the instruction is written out.  It reads registers only
+// (no "memory" clobber: nothing in the kernel reads the bytes back, and loads may still be scheduled across it); the trailing s_nop keeps
+// the compiler's next instruction off the data registers until the store has read them.
+template <typename T> __device__ __forceinline__ void publish16(void* p, const T& v) {
+  static_assert(sizeof(T) == 16, "publish16 stores exactly 16 bytes");
+#if CTTS_PLAIN_PUBLISH || !defined(__HIP_DEVICE_COMPILE__)
+  *reinterpret_cast<T*>(p) = v;
+#else
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(__builtin_bit_cast(u32x4_t, v)));
+#endif
+}
+
 // the XCD this wave runs on (0..7); used for speed only (which copy of a flag to poll), never for correctness
 __device__ __forceinline__ unsigned xcc_id() {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -50,8 +50,8 @@ template <int MBT, int KT, int NW> struct DxU { static constexpr int v = (MBT > 
 __device__ __forceinline__ void x3_store(uint16_t* __restrict__ hi_at, const size_t plane, const float v) {
   uint16_t h, l;
   x3_split(v, h, l);   // split-fp16 (common.hpp)
-  hi_at[0] = h;
-  hi_at[plane] = l;
+  publish2(hi_at, h);
+  publish2(hi_at + plane, l);
 }
 
 template <int NMB, int MBT, int KT, bool RMS, int EPI, int NW>
@@ -242,9 +242,10 @@ __device__ __forceinline__ void dec32x_body(const Dec32xArgs& a, const int M, co
       const int d = dlo + (hi ? 32 : 0);
       if (row < M && rd[q].b >= 0) {
         const size_t cbase = (((size_t)rd[q].b * 12 + head) * a.cmax + rd[q].slot) * 64;
-        if (sect == 0) a.C[(size_t)row * a.ldc + head * 64 + d] = roped;
-        else if (sect == 1) a.kc[cbase + d] = roped;
-        else a.vc[cbase + (hcol & 63) + li] = v;
+        // (every result of the three epilogues leaves through a publishing store, common.hpp: the next launch reads it)
+        if (sect == 0) publish4(a.C + (size_t)row * a.ldc + head * 64 + d, roped);
+        else if (sect == 1) publish4(a.kc + cbase + d, roped);
+        else publish4(a.vc + cbase + (hcol & 63) + li, v);
       }
       continue;
     }
@@ -254,12 +255,12 @@ __device__ __forceinline__ void dec32x_body(const Dec32xArgs& a, const int M, co
       sq += __shfl_xor(sq, 2, 64);
       sq += __shfl_xor(sq, 4, 64);
       sq += __shfl_xor(sq, 8, 64);
-      if (li == 0 && row < M) a.ssq_out[(size_t)row * SSQ_PARTS + tile] = sq;
+      if (li == 0 && row < M) publish4(a.ssq_out + (size_t)row * SSQ_PARTS + tile, sq);
     }
     if (row >= M) continue;
-    if (EPI == EPI_RES) a.C[(size_t)row * a.ldc + col] = v;
+    if (EPI == EPI_RES) publish4(a.C + (size_t)row * a.ldc + col, v);
     if (a.Cp != nullptr) x3_store(a.Cp + pk_off(row, col, a.kch_out), a.c_plane, v);
-    if (EPI == EPI_RES && a.Cp32 != nullptr) a.Cp32[pk32_off(row, col, a.kch32_out)] = v;
+    if (EPI == EPI_RES && a.Cp32 != nullptr) publish4(a.Cp32 + pk32_off(row, col, a.kch32_out), v);
   }
 }
 

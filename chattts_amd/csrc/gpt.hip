@@ -31,28 +31,37 @@ __device__ __forceinline__ bool row_absent(const int32_t* n_active, int m) { ret
 // G1  x[b] = sum_k emb_code[k][ids_buf[b, len[b]-1, k]]     (gpt.py:403-415; k-ordered f32 adds
 //     like torch.stack(code_emb, 3).sum(3))
 // ------------------------------------------------------------------------------------------------
+// A thread's share of a row's sum of squares, pinned to what hipcc made of `(x*x + y*y) + (z*z + w*w)` when the goldens were established
+// -- per pair one rounded product and one fma -- so that the bits do not follow the optimiser's mood when the code around it changes.
+__device__ __forceinline__ float row_ssq4(const float4 s) {
+#pragma clang fp contract(off)
+  const float yy = s.y * s.y, ww = s.w * s.w;
+  return __builtin_fmaf(s.x, s.x, yy) + __builtin_fmaf(s.z, s.z, ww);
+}
 // emit one residual-stream row: f32, optional bf16 copy, optional 48 partial sums of squares
 // (thread t owns columns 4t..4t+3; a partial covers 16 columns = 4 consecutive threads)
 __device__ __forceinline__ void emit_row(float4 s, int t, float* __restrict__ x_row, uint16_t* __restrict__ xb_row,
                                          float* __restrict__ ssq_row, float* __restrict__ xp32_at = nullptr, size_t lo_plane = 0) {
-  if (x_row) *reinterpret_cast<float4*>(x_row + t * 4) = s;
-  if (xp32_at) *reinterpret_cast<float4*>(xp32_at) = s;   // columns 4t..4t+3 are one lane's 16 bytes of the packed f32 order
+  // (every store of a row is a publishing store, common.hpp: the next launch reads it)
+  if (x_row) publish16(x_row + t * 4, s);
+  if (xp32_at) publish16(xp32_at, s);   // columns 4t..4t+3 are one lane's 16 bytes of the packed f32 order
   if (xb_row) {
-    ushort4 o;
-    o.x = f32_to_bf16(s.x); o.y = f32_to_bf16(s.y); o.z = f32_to_bf16(s.z); o.w = f32_to_bf16(s.w);
-    *reinterpret_cast<ushort4*>(xb_row + t * 4) = o;   // columns 4t..4t+3 share one 8-column group in either layout
     if (lo_plane) {   // "f32x3" parity mode (decode32x.hip): BOTH planes in the split-fp16 format (common.hpp x3_split), lo_plane elements apart
       ushort4 h, l;
       x3_split(s.x, h.x, l.x); x3_split(s.y, h.y, l.y); x3_split(s.z, h.z, l.z); x3_split(s.w, h.w, l.w);
-      *reinterpret_cast<ushort4*>(xb_row + t * 4) = h;
-      *reinterpret_cast<ushort4*>(xb_row + lo_plane + t * 4) = l;
+      publish8(xb_row + t * 4, h);
+      publish8(xb_row + lo_plane + t * 4, l);
+    } else {
+      ushort4 o;
+      o.x = f32_to_bf16(s.x); o.y = f32_to_bf16(s.y); o.z = f32_to_bf16(s.z); o.w = f32_to_bf16(s.w);
+      publish8(xb_row + t * 4, o);   // columns 4t..4t+3 share one 8-column group in either layout
     }
   }
   if (ssq_row) {
-    float q = (s.x * s.x + s.y * s.y) + (s.z * s.z + s.w * s.w);
+    float q = row_ssq4(s);
     q += __shfl_xor(q, 1, 64);
     q += __shfl_xor(q, 2, 64);
-    if ((t & 3) == 0) ssq_row[t >> 2] = q;
+    if ((t & 3) == 0) publish4(ssq_row + (t >> 2), q);
   }
 }
 
@@ -64,7 +73,7 @@ __device__ __forceinline__ void write_rope_cs(const StepPrep& sp, int m, int b, 
   if (sp.rope_cs == nullptr || t >= 64) return;
   const int ks = sp.kv_start[b];
   const int pos = slot - ks < 0 ? 1 : slot - ks;   // as write_desc
-  sp.rope_cs[(size_t)m * 64 + t] = t < 32 ? sp.cos_t[pos * 32 + t] : sp.sin_t[pos * 32 + t - 32];
+  publish4(sp.rope_cs + (size_t)m * 64 + t, t < 32 ? sp.cos_t[pos * 32 + t] : sp.sin_t[pos * 32 + t - 32]);
 }
 __device__ __forceinline__ void write_desc(const StepPrep& sp, int m, int b, int slot) {
   RowDesc d;
@@ -73,7 +82,7 @@ __device__ __forceinline__ void write_desc(const StepPrep& sp, int m, int b, int
   d.slot = slot;
   d.pos = slot - ks < 0 ? 1 : slot - ks;   // pad slots get position 1 (gpt.py:234-241)
   d.jlo = ks > slot ? slot : ks;
-  sp.desc[m] = d;
+  publish16(sp.desc + m, d);
 }
 // Device-side compaction: which utterance is compact row m, and how many rows are live.  Every wave of the workgroup
 // evaluates this itself (the finish bytes are one load for B <= 64; no barrier).  Returns -1 when row m does not exist.
@@ -136,12 +145,12 @@ __global__ __launch_bounds__(192) void embed_codes_k(EMBED_LEAD_SP(EMBED_LEAD_SP
   if (sp.row_map_out != nullptr) {   // device-side compaction: this step's row order comes from the finish flags
     int total;
     b = nth_unfinished(sp.finish, sp.order, gridDim.x, m, total);
-    if (m == 0 && t == 0) *sp.n_active_out = total;
+    if (m == 0 && t == 0) publish4(sp.n_active_out, total);
     if (b < 0) {   // row m does not exist this step: say so in its descriptor (the attention kernel reads nothing else)
-      if (sp.desc != nullptr && t == 0) sp.desc[m] = RowDesc{-1, 0, 0, 0};
+      if (sp.desc != nullptr && t == 0) publish16(sp.desc + m, RowDesc{-1, 0, 0, 0});
       return;
     }
-    if (t == 0) sp.row_map_out[m] = b;
+    if (t == 0) publish4(sp.row_map_out + m, b);
   } else {
     if (row_absent(n_active, m)) return;
     b = row_map ? row_map[m] : m;
@@ -333,8 +342,8 @@ template <> __device__ __forceinline__ void store_pko<x3p_t>(x3p_t* out, int m, 
   uint16_t* p = reinterpret_cast<uint16_t*>(out) + pk_off(m, c, HID / 32);
   uint16_t h, l;
   x3_split(v, h, l);
-  p[0] = h;
-  p[plane] = l;
+  publish2(p, h);   // publishing stores (common.hpp): o_proj is the next launch
+  publish2(p + plane, l);
 }
 template <> __device__ __forceinline__ void store_out<float>(float* p, float v) { *p = v; }
 template <> __device__ __forceinline__ void store_out<bf16_t>(bf16_t* p, float v) { *p = f32_to_bf16(v); }
@@ -1889,6 +1898,8 @@ __global__ __launch_bounds__(256) void sample_k(SAMPLE_LEAD(SAMPLE_LEAD_PARAM) S
   }
   if (force_eos) wi = a.eos;
   SSTAMP(6);   // token drawn
+  // (plain stores on purpose: as publishing stores (common.hpp) they made this kernel 2.1 us slower -- the write-through drops the
+  // lines of finish / end_idx / len / margin from the L2, and thread 0 reads them back one step later -- profiles/r9C)
   if (a.sampled != nullptr && gen < a.teacher_stride && lane == 0) a.sampled[((size_t)b * a.teacher_stride + gen) * NVQ + k] = (int64_t)wi;
   if (forced_t) wi = (int)teach;
   if (lane == 0) {
@@ -1955,12 +1966,12 @@ __global__ __launch_bounds__(192) void embed_text_k(const float* __restrict__ em
   if (sp.row_map_out != nullptr) {   // device-side compaction (see embed_codes_k)
     int total;
     b = nth_unfinished(sp.finish, sp.order, gridDim.x, m, total);
-    if (m == 0 && t == 0) *sp.n_active_out = total;
+    if (m == 0 && t == 0) publish4(sp.n_active_out, total);
     if (b < 0) {   // row m does not exist this step: say so in its descriptor (the attention kernel reads nothing else)
-      if (sp.desc != nullptr && t == 0) sp.desc[m] = RowDesc{-1, 0, 0, 0};
+      if (sp.desc != nullptr && t == 0) publish16(sp.desc + m, RowDesc{-1, 0, 0, 0});
       return;
     }
-    if (t == 0) sp.row_map_out[m] = b;
+    if (t == 0) publish4(sp.row_map_out + m, b);
   } else {
     if (row_absent(n_active, m)) return;
     b = row_map ? row_map[m] : m;

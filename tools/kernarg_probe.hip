@@ -1,4 +1,5 @@
-// Micro-benchmarks of the kernel-argument fetch at the head of a short dependent kernel on MI355X.  Two parts, own main, no Python.
+// Micro-benchmarks of the fixed cost of a short dependent kernel on MI355X: the kernel-argument fetch at its head (parts "size" and
+// "preload") and the write-back of its results at its end (part "publish").  Own main, no Python.
 //
 // "size"    (round 3: growing DecGemmArgs by 32 bytes made the 5 us o_proj launch 1 us slower.)  Does the SIZE of a by-value
 //           argument struct matter?  A chain of 104 graph-captured launches; each kernel reads a pointer from the FIRST or the LAST
@@ -19,8 +20,16 @@
 //           Four cells, three repeats each, us per launch.  The final values of the chain are checked (one increment per hop).
 //           Read the preload length the compiler granted with:  hipcc ... --cuda-device-only -S, .amdhsa_user_sgpr_kernarg_preload_length
 //
+// "publish" Does it pay to store a launch's results write-through (sc1), so that the release at the end of the launch finds the L2 of
+//           each XCD clean, instead of plain stores whose dirty lines that release has to write back?  The "preload" chain (104
+//           captured launches, 24 KB of cold weights per workgroup, the previous hop's value read from a workgroup on another XCD),
+//           but every workgroup stores 4 KB (16 bytes per lane), 192 and 768 workgroups = 0.79 and 3.1 MB dirtied per launch:
+//             plain    global_store_dwordx4
+//             sc1      the same store through a buffer resource with the write-through bit (aux 16)
+//           alternating, three repeats each, us per launch; the chain's values are checked.
+//
 //   hipcc --offload-arch=gfx950 -O3 -mllvm -amdgpu-kernarg-preload-count=16 tools/kernarg_probe.hip -o /tmp/kernarg_probe
-//   /tmp/kernarg_probe [size|preload]        (default: both)
+//   /tmp/kernarg_probe [size|preload|publish]        (default: size and preload)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -195,9 +204,91 @@ static int part_preload(hipStream_t st) {
   return bad ? 1 : 0;
 }
 
+// ---- part "publish" ----------------------------------------------------------------------------------------------------------
+static const int PUB_MAX_WG = 768;
+
+// out / in: n_elem 16-byte vectors (one per thread of the grid); the vector's four words all hold the hop count
+template <bool WT>
+__global__ __launch_bounds__(256) void k_hop_pub(const u4* w, const int* n_live, const u4* in, u4* out, unsigned n_elem) {
+  const int tid = threadIdx.x, wg = blockIdx.x;
+  u4 wv[6];
+  const u4* wp = w + (size_t)wg * 1536 + tid;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) wv[j] = __builtin_nontemporal_load(wp + j * 256);
+  __builtin_amdgcn_sched_barrier(0);
+  const unsigned live = (unsigned)*n_live;
+  const unsigned i = (unsigned)wg * 256u + (unsigned)tid;        // < n_elem: the grid is n_elem / 256 workgroups
+  const u4 x = in[(i + live * 19u * 256u) % n_elem];
+  unsigned s = 0;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) s ^= wv[j].x ^ wv[j].y ^ wv[j].z ^ wv[j].w;
+  const u4 y = {x.x + 1u + s, x.y + 1u + s, x.z + 1u + s, x.w + 1u + s};
+  if (WT) {
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, (int)(n_elem * 16u), 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(y, rs, (int)(i * 16u), 0, 16);   // aux 16 = sc1
+  } else {
+    out[i] = y;
+  }
+}
+
+static int pub_graph(const PBufs& b, u4* o0, u4* o1, hipStream_t st, int n_wg, bool wt, hipGraphExec_t* ge) {
+  hipGraph_t g;
+  CK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+  for (int i = 0; i < CHAIN; ++i) {
+    const u4* w = (const u4*)((const char*)b.w + (size_t)i * PUB_MAX_WG * 24576);
+    const u4* in = (i & 1) ? o1 : o0; u4* out = (i & 1) ? o0 : o1;
+    if (wt) hipLaunchKernelGGL(k_hop_pub<true>, dim3(n_wg), dim3(256), 0, st, w, (const int*)b.n_live, in, out, (unsigned)n_wg * 256u);
+    else hipLaunchKernelGGL(k_hop_pub<false>, dim3(n_wg), dim3(256), 0, st, w, (const int*)b.n_live, in, out, (unsigned)n_wg * 256u);
+  }
+  CK(hipStreamEndCapture(st, &g));
+  CK(hipGraphInstantiate(ge, g, nullptr, nullptr, 0));
+  CK(hipGraphDestroy(g));
+  return 0;
+}
+
+static int part_publish(hipStream_t st) {
+  PBufs b;
+  const size_t n_max = (size_t)PUB_MAX_WG * 256;
+  u4 *o0, *o1;
+  CK(hipMalloc(&b.w, (size_t)CHAIN * PUB_MAX_WG * 24576)); CK(hipMemset(b.w, 0, (size_t)CHAIN * PUB_MAX_WG * 24576));
+  CK(hipMalloc(&o0, n_max * 16)); CK(hipMalloc(&o1, n_max * 16));
+  const int one = 1;
+  CK(hipMalloc(&b.n_live, 4)); CK(hipMemcpy(b.n_live, &one, 4, hipMemcpyHostToDevice));
+  hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  printf("chain of %d captured launches, 24 KB of cold weights and 4 KB of results per workgroup, %d replays per figure; us per launch\n", CHAIN, REPLAYS);
+  int rc = 0;
+  for (int n_wg : {192, 768}) {
+    CK(hipMemset(o0, 0, n_max * 16)); CK(hipMemset(o1, 0, n_max * 16));
+    hipGraphExec_t ge[2];
+    for (int v = 0; v < 2; ++v) if (pub_graph(b, o0, o1, st, n_wg, v == 1, &ge[v])) return 1;
+    unsigned hops = 0;
+    double lo[2] = {1e30, 1e30}, hi[2] = {0, 0};
+    for (int rep = 0; rep < REPEATS; ++rep)
+      for (int v = 0; v < 2; ++v) {
+        double t;
+        if (time_graph(ge[v], st, e0, e1, &t)) return 1;
+        hops += (unsigned)(REPLAYS + 1) * CHAIN;
+        t /= CHAIN;
+        lo[v] = t < lo[v] ? t : lo[v]; hi[v] = t > hi[v] ? t : hi[v];
+        printf("%3d workgroups, repeat %d: %s %.3f us per launch\n", n_wg, rep, v ? "sc1  " : "plain", t);
+        fflush(stdout);
+      }
+    std::vector<unsigned> h((size_t)n_wg * 256 * 4);
+    CK(hipMemcpy(h.data(), o0, h.size() * 4, hipMemcpyDeviceToHost));
+    size_t bad = 0;
+    for (unsigned x : h) bad += x != hops;
+    printf("%3d workgroups: plain %.3f-%.3f, sc1 %.3f-%.3f us per launch; chain values %s (%zu of %zu wrong, expect %u, first %u)\n", n_wg, lo[0], hi[0], lo[1],
+           hi[1], bad ? "WRONG" : "ok", bad, h.size(), hops, h[0]);
+    for (int v = 0; v < 2; ++v) CK(hipGraphExecDestroy(ge[v]));
+    rc |= bad != 0;
+  }
+  return rc;
+}
+
 int main(int argc, char** argv) {
   const char* part = argc > 1 ? argv[1] : "both";
   hipStream_t st; CK(hipStreamCreate(&st));
+  if (!strcmp(part, "publish")) return part_publish(st);
   if (strcmp(part, "preload") != 0 && part_size(st)) return 1;
   if (strcmp(part, "size") != 0 && part_preload(st)) return 1;
   return 0;
