@@ -207,6 +207,11 @@ SIGNATURES = {
     "ctts_k_attention_oproj": (C.c_int, [P, P, P, I32, P, P, P, I32, P, P, P, P, P, P]),
     "ctts_k_device_guard_probe": (C.c_int, [P, P, P, P, P]),
     "ctts_k_embed_codes": (C.c_int, [P, P, I32, P, P, I32, P]),
+    "ctts_k_step_prep": (C.c_int, [P, I32, P, I32, P, P, P, P, I32, P, P, P, P, P, I32, P, C.c_int64, P, P, P, P, P, P, P, I32, I32, P]),
+    "ctts_k_prefill_prep32": (C.c_int, [P, P, P, I32, I32, P, P, I32, P]),
+    "ctts_k_prefill_compact": (C.c_int, [P, P, P, P, I32, I32, P, P]),
+    "ctts_k_gemm_pre32": (C.c_int, [P, P, I32, I32, I32, P, I32, P, F, P, I32, P, I32, P, I32, P, I32, P, P, P, P, P, I32, P]),
+    "ctts_k_qkv_rope32": (C.c_int, [I32, P, C.c_int64, P, C.c_int64, I32, P, P, I32, P, P, F, P, P, P, P, P, P, P, I32, I32, P]),
     "ctts_k_final_norm": (C.c_int, [P, I32, P, F, P, P, I32, P, I32, I32, P]),
     "ctts_k_sample": (C.c_int, [C.POINTER(GenState), P, P]),
     "ctts_k_sample_text": (C.c_int, [C.POINTER(GenState), P, I32, P]),

@@ -1725,6 +1725,85 @@ extern "C" int ctts_k_embed_codes(const float* emb_code, const int64_t* ids_buf,
   CK(launch_embed_codes(emb_code, ids_buf, tcap, len, x, nullptr, nullptr, B, nullptr, nullptr, (hipStream_t)stream));
   return 0;
 }
+// ---- the row-descriptor contract, kernel by kernel (tests/test_gpu_step_front.py, tests/test_gpu_parity_qkv.py) ----------------------
+// the step's first kernel with a caller-filled StepPrep: embed_codes_k, or embed_text_k when n_text > 0
+extern "C" int ctts_k_step_prep(const float* emb, int32_t n_text, const int64_t* ids_buf, int32_t tcap, const int32_t* len, float* x,
+                                uint16_t* xb, float* ssq, int32_t B, const int32_t* row_map, const int32_t* n_active, int32_t* desc,
+                                const int32_t* kv_start, const uint8_t* finish, int32_t xb_packed, float* xp32, int64_t xb_lo_plane,
+                                int32_t* row_map_out, int32_t* n_active_out, const int32_t* order, float* rope_cs, const float* cos_tab,
+                                const float* sin_tab, int32_t* zero_p, int32_t zero_n, int32_t zero_stride, void* stream) {
+  const char* who = "ctts_k_step_prep";
+  if (!emb || !ids_buf || !len || !x || B <= 0 || tcap <= 0 || n_text < 0) return fail("%s: bad arguments", who);
+  if ((desc || rope_cs) && !kv_start) return fail("%s: descriptors and RoPE rows need kv_start", who);
+  if (rope_cs && (!cos_tab || !sin_tab)) return fail("%s: rope_cs needs the cos / sin tables", who);
+  if (row_map_out && (!finish || !n_active_out)) return fail("%s: device-side compaction needs finish and n_active_out", who);
+  if (xb_lo_plane < 0 || (xb_lo_plane & 7) || (xb_lo_plane && (!xb || !xb_packed))) return fail("%s: the lo plane needs a packed xb, a multiple of 8 elements behind it", who);
+  if (zero_p && (zero_n < 0 || zero_stride < 1)) return fail("%s: bad zero_n / zero_stride", who);
+  StepPrep sp{reinterpret_cast<RowDesc*>(desc), kv_start, finish, xb_packed ? 1 : 0, xp32, row_map_out, n_active_out, order, rope_cs, cos_tab, sin_tab,
+              zero_p, zero_n, zero_stride, (size_t)xb_lo_plane};
+  if (n_text > 0) CK(launch_embed_text(emb, n_text, ids_buf, tcap, len, x, xb, ssq, B, row_map, n_active, (hipStream_t)stream, &sp));
+  else CK(launch_embed_codes(emb, ids_buf, tcap, len, x, xb, ssq, B, row_map, n_active, (hipStream_t)stream, &sp));
+  return 0;
+}
+extern "C" int ctts_k_prefill_prep32(const float* x, float* xp32, int32_t* desc, int32_t q_per_b, int32_t slot0, const int32_t* kv_start,
+                                     const int32_t* row_map, int32_t M, void* stream) {
+  if (!x || !xp32 || !desc || !kv_start || q_per_b <= 0 || slot0 < 0 || M <= 0) return fail("ctts_k_prefill_prep32: bad arguments");
+  CK(launch_prefill_prep32(x, xp32, reinterpret_cast<RowDesc*>(desc), q_per_b, slot0, kv_start, row_map, M, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ctts_k_prefill_compact(const float* emb, float* x, int32_t* desc, int32_t* last_row, int32_t B, int32_t T, const int32_t* kv_start,
+                                      void* stream) {
+  if (!emb || !x || !desc || !last_row || !kv_start || B <= 0 || T <= 0) return fail("ctts_k_prefill_compact: bad arguments");
+  CK(launch_prefill_compact(emb, x, reinterpret_cast<RowDesc*>(desc), last_row, B, T, kv_start, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ctts_k_gemm_pre32(const float* Ap, const float* Wp, int32_t M, int32_t N, int32_t K, const float* X, int32_t ldx, const float* norm_w,
+                                 float eps, float* rstd, int32_t epi, float* C, int32_t ldc, const float* res, int32_t ldr, float* Cp,
+                                 int32_t kch_out, const int32_t* desc, const float* cos_tab, const float* sin_tab, float* kcache, float* vcache,
+                                 int32_t cmax, void* stream) {
+  const char* who = "ctts_k_gemm_pre32";
+  if (!Ap || !Wp) return fail("%s: bad arguments", who);
+  if (norm_w && (!X || !rstd || K != HID)) return fail("%s: the RMSNorm prologue needs X, rstd and K = 768 (launch_rows_rstd32)", who);
+  if (epi == D32_EPI_QKV_ROPE && (!C || !cos_tab || !sin_tab || cmax <= 0)) return fail("%s: the QKV epilogue needs C, the tables and cmax", who);
+  Dec32Args d;
+  memset(&d, 0, sizeof(d));
+  d.Ap = Ap; d.Wp = Wp; d.M = M; d.N = N; d.K = K; d.X = X; d.ldx = ldx; d.norm_w = norm_w; d.eps = eps; d.epi = epi; d.C = C; d.ldc = ldc;
+  d.res = res; d.ldr = ldr; d.Cp = Cp; d.kch_out = kch_out; d.desc = reinterpret_cast<const RowDesc*>(desc); d.cos_t = cos_tab; d.sin_t = sin_tab;
+  d.kc = kcache; d.vc = vcache; d.cmax = cmax;
+  if (norm_w) CK(launch_rows_rstd32(X, ldx, M, eps, rstd, (hipStream_t)stream));
+  CK(launch_gemm_pre32(d, norm_w ? rstd : nullptr, (hipStream_t)stream));
+  return 0;
+}
+// the D32_EPI_QKV_ROPE launch of the decode step, given descriptors: x3 = 0: launch_gemm_dec32 (Ap / Wp packed f32, X + norm_w the RMSNorm
+// prologue); x3 = 1: launch_gemm_dec32x (Ap / Wp hi planes, the lo planes a_plane / w_plane elements behind, gain folded into W, 1 / rms
+// from ssq_in or else from X; rope_cs optional)
+extern "C" int ctts_k_qkv_rope32(int32_t x3, const void* Ap, int64_t a_plane, const void* Wp, int64_t w_plane, int32_t M, const int32_t* n_active,
+                                 const float* X, int32_t ldx, const float* norm_w, const float* ssq_in, float eps, float* qkv,
+                                 const int32_t* desc, const float* rope_cs, const float* cos_tab, const float* sin_tab, float* kcache,
+                                 float* vcache, int32_t cmax, int32_t force_mb, void* stream) {
+  const char* who = "ctts_k_qkv_rope32";
+  if (!Ap || !Wp || !qkv || !desc || !kcache || !vcache || M <= 0 || cmax <= 0) return fail("%s: bad arguments", who);
+  if ((x3 == 0 || !rope_cs) && (!cos_tab || !sin_tab)) return fail("%s: needs the cos / sin tables", who);
+  if (x3) {
+    if (a_plane <= 0 || w_plane <= 0 || (!X && !ssq_in)) return fail("%s: the split launch needs both plane strides and X or ssq_in", who);
+    Dec32xArgs d;
+    memset(&d, 0, sizeof(d));
+    d.Ap = (const uint16_t*)Ap; d.a_plane = (size_t)a_plane; d.Wp = (const uint16_t*)Wp; d.w_plane = (size_t)w_plane; d.M = M; d.N = 3 * HID; d.K = HID;
+    d.n_active = n_active; d.rms = 1; d.X = X; d.ldx = ldx; d.eps = eps; d.ssq_in = ssq_in; d.rope_cs = rope_cs; d.epi = D32_EPI_QKV_ROPE;
+    d.C = qkv; d.ldc = 3 * HID; d.desc = reinterpret_cast<const RowDesc*>(desc); d.cos_t = cos_tab; d.sin_t = sin_tab; d.kc = kcache; d.vc = vcache;
+    d.cmax = cmax; d.force_mb = force_mb;
+    CK(launch_gemm_dec32x(d, (hipStream_t)stream));
+    return 0;
+  }
+  if (!X || !norm_w || rope_cs) return fail("%s: the f32 launch needs X and norm_w and reads no rope_cs", who);
+  Dec32Args d;
+  memset(&d, 0, sizeof(d));
+  d.Ap = (const float*)Ap; d.Wp = (const float*)Wp; d.M = M; d.N = 3 * HID; d.K = HID; d.n_active = n_active; d.X = X; d.ldx = ldx; d.norm_w = norm_w;
+  d.eps = eps; d.epi = D32_EPI_QKV_ROPE; d.C = qkv; d.ldc = 3 * HID; d.desc = reinterpret_cast<const RowDesc*>(desc); d.cos_t = cos_tab;
+  d.sin_t = sin_tab; d.kc = kcache; d.vc = vcache; d.cmax = cmax; d.force_mb = force_mb;
+  CK(launch_gemm_dec32(d, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_k_final_norm(const float* x, int32_t q_per_b, const float* w, float eps, float* hfin, float* hiddens,
                                  int32_t max_new, const int32_t* len, int32_t T, int32_t B, void* stream) {
   CK(launch_final_norm(x, q_per_b, w, eps, hfin, hiddens, max_new, len, T, B, nullptr, nullptr, nullptr, (hipStream_t)stream));

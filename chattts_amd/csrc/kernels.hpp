@@ -292,7 +292,8 @@ struct StepPrep {
   float* rope_cs; const float* cos_t; const float* sin_t;   // [rows][64] out (cos[32] | sin[32] of the row's position) from the [max_pos][32] tables, or null
   int32_t* zero_p; int zero_n; int zero_stride;   // zero_n words, zero_stride ints apart, that the step's first kernel zeroes (arrival words
                                                   // of the fused QKV + attention launches), or null
-  size_t xb_lo_plane;       // split-bf16 parity mode: with a packed `xb`, ALSO write the lo plane (x - bf16(x)) this many elements behind it; 0 = no
+  size_t xb_lo_plane;       // split-fp16 parity mode: the packed `xb` is the hi plane of x3_split (common.hpp: fp16(x)); ALSO write its lo plane,
+                            // fp16((x - hi) * 2^11), this many elements behind it; 0 = no (`xb` is plain bf16)
 };
 hipError_t launch_embed_codes(const float* emb_code /*[4,626,768]*/, const int64_t* ids_buf, int ids_row_stride /*Tcap*/,
                               const int32_t* len, float* x, uint16_t* xb /*null ok*/, float* ssq /*null ok*/, int B,

@@ -767,6 +767,40 @@ int ctts_k_attention_oproj(const float* qkv, const uint16_t* kcache, const uint1
  * current inside the guard, whether it switched; fails if the previous device is not restored */
 int ctts_k_device_guard_probe(void* stream, int32_t* before, int32_t* stream_dev, int32_t* inside, int32_t* switched);
 int ctts_k_embed_codes(const float* emb_code, const int64_t* ids_buf, int32_t tcap, const int32_t* len, float* x, int32_t B, void* stream);
+/* The first kernel of a decode step with everything it can produce (csrc/gpt.hip embed_codes_k; n_text > 0: embed_text_k over emb [n_text, 768]):
+ * the residual rows x [B, 768], their 16-bit copy xb (row-major bf16; xb_packed: the fragment-packed order of csrc/decode.hip; with
+ * xb_lo_plane > 0: hi | lo' fp16 planes of the split-fp16 format, the lo plane xb_lo_plane elements behind), ssq [B, 48] partial sums of
+ * squares, xp32 (packed f32 order of csrc/decode32.hip), and per compact row m: desc [B][4] int32 = {utterance (-1: finished), KV slot, RoPE
+ * position, first visible key}, rope_cs [B][64] = cos[32] | sin[32] of the row's position out of the [max_pos][32] tables.  Rows: row_map_out
+ * != NULL: device-side compaction -- row m is the m-th utterance (in `order`, or ascending) whose finish byte is 0, written to row_map_out[m],
+ * the live count to *n_active_out; else the host's row_map (NULL: identity) and *n_active (NULL: B).  zero_p: zero_n words, zero_stride ints
+ * apart, set to 0.  Every output pointer may be NULL except x. */
+int ctts_k_step_prep(const float* emb, int32_t n_text, const int64_t* ids_buf, int32_t tcap, const int32_t* len, float* x, uint16_t* xb, float* ssq,
+                     int32_t B, const int32_t* row_map, const int32_t* n_active, int32_t* desc, const int32_t* kv_start, const uint8_t* finish,
+                     int32_t xb_packed, float* xp32, int64_t xb_lo_plane, int32_t* row_map_out, int32_t* n_active_out, const int32_t* order,
+                     float* rope_cs, const float* cos_tab, const float* sin_tab, int32_t* zero_p, int32_t zero_n, int32_t zero_stride,
+                     void* stream);
+/* parity-mode prompt pass: x [M, 768] -> xp32 (packed f32 order) and desc [M][4] of prompt row m: utterance row_map ? row_map[m / q_per_b]
+ * : m / q_per_b, KV slot slot0 + m % q_per_b (csrc/gpt.hip prefill_prep32_k) */
+int ctts_k_prefill_prep32(const float* x, float* xp32, int32_t* desc, int32_t q_per_b, int32_t slot0, const int32_t* kv_start,
+                          const int32_t* row_map, int32_t M, void* stream);
+/* prompt pass over the valid tokens only: emb [B, T, 768] -> consecutive rows of x (utterance b's slots kv_start[b] .. T-1), their desc, and
+ * last_row [B] (csrc/gpt.hip prefill_compact_k).  Every utterance needs at least one valid token: kv_start[b] < T. */
+int ctts_k_prefill_compact(const float* emb, float* x, int32_t* desc, int32_t* last_row, int32_t B, int32_t T, const int32_t* kv_start,
+                           void* stream);
+/* prompt-pass projection of the f32 parity mode (csrc/prefill32.hip), operands as ctts_k_gemm_dec32: epi 1 = C = res + acc and Cp, 2 =
+ * SiLU(gate)*up -> Cp, 100 = RoPE + KV append from desc [M][4] into float32 caches [slots, 12, cmax, 64] (N = 2304, K = 768, q/k weight rows
+ * in engine.py `rope_row_perm` order; q -> C).  norm_w != NULL (K = 768): RMSNorm prologue, 1 / rms of the rows of X goes through rstd [M]. */
+int ctts_k_gemm_pre32(const float* Ap, const float* Wp, int32_t M, int32_t N, int32_t K, const float* X, int32_t ldx, const float* norm_w,
+                      float eps, float* rstd, int32_t epi, float* C, int32_t ldc, const float* res, int32_t ldr, float* Cp, int32_t kch_out,
+                      const int32_t* desc, const float* cos_tab, const float* sin_tab, float* kcache, float* vcache, int32_t cmax, void* stream);
+/* the fused RMSNorm + QKV + RoPE + KV append launch of the parity decode step, given descriptors: x3 = 0: csrc/decode32.hip (Ap / Wp packed
+ * f32, X + norm_w the RMSNorm prologue; bit-identical to ctts_k_gemm + ctts_k_rope_append); x3 = 1: csrc/decode32x.hip (Ap / Wp hi planes, the
+ * lo planes a_plane / w_plane elements behind, gain folded into W, 1 / rms from ssq_in or else from X; rope_cs [M][64] replaces the tables) */
+int ctts_k_qkv_rope32(int32_t x3, const void* Ap, int64_t a_plane, const void* Wp, int64_t w_plane, int32_t M, const int32_t* n_active,
+                      const float* X, int32_t ldx, const float* norm_w, const float* ssq_in, float eps, float* qkv, const int32_t* desc,
+                      const float* rope_cs, const float* cos_tab, const float* sin_tab, float* kcache, float* vcache, int32_t cmax,
+                      int32_t force_mb, void* stream);
 int ctts_k_final_norm(const float* x, int32_t q_per_b, const float* w, float eps, float* hfin, float* hiddens, int32_t max_new,
                       const int32_t* len, int32_t T, int32_t B, void* stream);
 int ctts_k_sample(const ctts_gen_state* s, const float* logits, void* stream);

@@ -55,6 +55,24 @@ def relerr(got: np.ndarray, ref: np.ndarray) -> float:
     return float(np.abs(got.astype(np.float64) - ref.astype(np.float64)).max() / max(1e-30, np.abs(ref).max()))
 
 
+# ---- row descriptors (csrc/kernels.hpp RowDesc) ---------------------------------------------------------------------------------
+DESC_ABSENT = (-1, 0, 0, 0)      # what the step's first kernel writes for a compact row that does not exist this step
+CANARY32 = 0x5A5A5A5A            # int32 pattern of an output word no kernel may write
+CANARY16 = 0x5A5A
+
+
+def row_desc(b: int, slot: int, ks: int, finished: bool = False):
+    """numpy restatement of write_desc (csrc/gpt.hip): {utterance or -1, KV slot, RoPE position, first visible key}; a slot in front
+    of the utterance's first valid one (ks > slot) is a pad row: position 1, and it sees itself only"""
+    return (-1 if finished else int(b), int(slot), 1 if slot - ks < 0 else int(slot - ks), int(slot) if ks > slot else int(ks))
+
+
+def live_rows(finish: np.ndarray, order=None):
+    """numpy restatement of the device-side compaction (nth_unfinished): the utterances with finish == 0 in visiting order"""
+    seq = np.arange(len(finish)) if order is None else np.asarray(order)
+    return [int(s) for s in seq if finish[s] == 0]
+
+
 # ---- ragged decode: packed layouts whose segment boundaries fall where the codec kernels switch, tile and run -------------------
 EDGE_MODS = (32, 36, 48, 64, 128, 256)   # GEMM row tiles 32 / 64 / 128 / 256; dwconv runs of 36 frames (dilation 1) and 48 (seq, dilation 2)
 EDGE_SHORTS = (1, 2, 3, 4, 7)            # tokens: 2 - 14 frames, inside the k7 conv's reach, the dilation-2 dwconv's 13-frame span, one run
