@@ -58,6 +58,10 @@ RS_WINDOW = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("origin", "<i8"), ("t
 G711_RANGE = np.dtype([("start", "<i8"), ("n", "<i8"), ("law", "<i4"), ("pad0", "<i4"), ("pad1", "<i8")])
 
 
+# ctts_flac_range (32 bytes): start, n int64; rate (0 skip), count_idx (-1: n is the length) int32; frame0 int64
+FLAC_RANGE = np.dtype([("start", "<i8"), ("n", "<i8"), ("rate", "<i4"), ("count_idx", "<i4"), ("frame0", "<i8")])
+
+
 # ctts_ts_stream (80 bytes): in_off, n_in, pos, total, out_off, path_off int64; k_prev, k_now, slot, phase, num, den, n_out, reserved int32
 TS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("out_off", "<i8"), ("path_off", "<i8"),
                       ("k_prev", "<i4"), ("k_now", "<i4"), ("slot", "<i4"), ("phase", "<i4"), ("num", "<i4"), ("den", "<i4"),
@@ -172,6 +176,8 @@ SIGNATURES = {
     "ctts_codec_decode_windows_speed_rate": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, P, P, P, P, I32, P, P, P, I32, P, P, I32,
                                                        P, P, P, P, P, P, I32, P, I32, P, I32, I32, P, P, I32, F, P, SZ, P]),
     "ctts_g711_encode_ranges": (C.c_int, [P, P, P, P, I32, P]),
+    "ctts_flac_encode_sizes": (C.c_int, [P, I32, P]),
+    "ctts_flac_encode_ranges": (C.c_int, [P, P, P, P, I32, P, SZ, P, SZ, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),
     "ctts_dvae_destroy": (None, [P]),
     "ctts_dvae_code_frames": (I32, [I32]),

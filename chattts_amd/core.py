@@ -22,6 +22,7 @@ from typing import Iterator, List, Optional, Union
 import numpy as np
 import torch
 
+from . import flac as FLAC
 from . import g711 as G711
 from . import resample as RS
 from . import timescale as TS
@@ -319,7 +320,8 @@ class Chat:
         return self.codec.to_host(wav if sample_rate is None else self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate)))
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
-                        product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None) -> List[np.ndarray]:
+                        product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None,
+                        flac=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
@@ -330,11 +332,17 @@ class Chat:
         `encoding` (None: the call above; "ulaw" / "alaw"; with `ragged` also one per row): G.711 companding on the device, strictly
         behind the conversion (CodecEngine.g711_encode) -- row b comes back as uint8, `g711.encode` of the int16 array above.
         `speed` (None: 1.0; with `ragged` also one per row): `wav` above is the waveform time-scaled on the device
-        (CodecEngine.time_scale) at 24 kHz, in front of the resampler; rows at speed 1 are not touched."""
+        (CodecEngine.time_scale) at 24 kHz, in front of the resampler; rows at speed 1 are not touched.
+        `flac` (None / False: the call above; True; with `ragged` also one flag per row): a flagged row comes back as a uint8 array, the
+        complete FLAC file (chattts_amd/flac.py) of exactly the int16 samples above at the row's rate, encoded on the device behind the
+        conversion (CodecEngine.float_to_int16_groups_flac: the stripped length is known there only); not together with `encoding`."""
         skw = _speed_kw(speed)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
+        flags = self._flac_flags(flac, len(result_list), encoding, per_row=ragged, who="decode_to_pcm16")
+        if flags is not None:
+            return self._decode_to_flac(result_list, use_decoder, strip, product, ragged, sample_rate, flags, skw, encoding)
         if ragged:
             if encoding is None:
                 return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, **skw)
@@ -367,6 +375,53 @@ class Chat:
         keep_h = self.codec.to_host(keep)
         n = pcm_h.shape[1]
         return [pcm_h[b][np.unpackbits(keep_h[b])[:n].astype(bool)] for b in range(pcm_h.shape[0])]
+
+    @staticmethod
+    def _flac_flags(flac, n: int, encoding, per_row: bool, who: str):
+        """the `flac=` option of the decode calls -> one bool per row, or None when no row asks for it (today's call)"""
+        if flac is None or flac is False:
+            return None
+        if isinstance(flac, (bool, np.bool_)):
+            flags = [bool(flac)] * n
+        else:
+            if not per_row:
+                raise ValueError(f"{who}: one flac flag for the whole call (one per row goes with ragged=True)")
+            flags = [bool(f) for f in flac]
+            if len(flags) != n:
+                raise ValueError(f"{who}: one flac flag per row, or one for all")
+        if not any(flags):
+            return None
+        encs = None if encoding is None else ([encoding] * n if isinstance(encoding, str) else list(encoding))
+        if encs is not None and (len(encs) != n or any(f and e is not None for f, e in zip(flags, encs))):
+            raise ValueError(f"{who}: flac does not go with an encoding (a FLAC file holds the 16-bit samples; one entry per row)")
+        return flags
+
+    def _decode_to_flac(self, result_list, use_decoder: bool, strip: bool, product: str, ragged: bool, sample_rate, flags, skw,
+                        encoding=None) -> List[np.ndarray]:
+        """`decode_to_pcm16` with at least one row as a FLAC file: the decode of the plain call, then the grouped conversion with one
+        group per row (the same samples; slots that start on multiples of 8 and a count header on the device) and the encoder behind it"""
+        B = len(result_list)
+        if B == 0:
+            return []
+        codec = self.codec
+        if ragged:
+            wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw)
+            rates = [CodecEngine.SAMPLE_RATE] * B if sample_rate is None else ([int(sample_rate)] * B if np.ndim(sample_rate) == 0 else
+                                                                                [int(r) for r in sample_rate])
+        else:
+            wav = codec.decode_to_wavs(result_list) if use_decoder else codec.vocos_decode(self.dvae.decode_codes(result_list))
+            if skw:
+                wav = codec.time_scale(wav, skw["speed"])
+            if sample_rate is not None:
+                wav = codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
+            wav = wav.contiguous()
+            off = np.arange(B + 1, dtype=np.int64) * int(wav.shape[1])
+            wav = wav.view(-1)
+            rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * B
+        encs = None if encoding is None else ([encoding] * B if isinstance(encoding, str) else list(encoding))
+        out = codec.float_to_int16_groups_flac(wav, off, np.arange(B + 1, dtype=np.int32), [r if f else None for r, f in zip(rates, flags)],
+                                               product=product, keep_thr=1e-5 if strip else None, encodings=encs)
+        return [p if p.dtype == np.uint8 else p.copy() for p in out]
 
     def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None, speed=None) -> List[np.ndarray]:
         """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
@@ -434,7 +489,7 @@ class Chat:
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None,
-                              speed=None) -> List[np.ndarray]:
+                              speed=None, flac=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
@@ -446,7 +501,10 @@ class Chat:
         back as uint8, `g711.encode` of the int16 array above (CodecEngine.float_to_int16_groups(encodings=): one launch behind the
         grouped conversion, still one copy).
         `speed` (None: 1.0; or one per request): every sentence is time-scaled alone, on the device, at 24 kHz -- in front of the
-        resampler, hence in front of the group's strip and concatenation."""
+        resampler, hence in front of the group's strip and concatenation.
+        `flac` (None / False: the call above; True; or one flag per request): a flagged request comes back as a uint8 array, the
+        complete FLAC file of exactly the int16 samples above at the request's rate, encoded on the device straight from the grouped
+        slots and their count header (CodecEngine.float_to_int16_groups_flac); not together with `encoding`."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -456,9 +514,12 @@ class Chat:
         grp = np.zeros(len(groups) + 1, np.int32)
         np.cumsum([len(g) for g in groups], out=grp[1:])
         codec = self.codec
+        flags = self._flac_flags(flac, len(groups), encoding, per_row=True, who="decode_split_to_pcm16")
+        rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * len(groups) if np.ndim(sample_rate) == 0 else None
         if sample_rate is not None and np.ndim(sample_rate) != 0:
             if len(sample_rate) != len(groups):
                 raise ValueError("decode_split_to_pcm16: one sample rate per request, or one for all")
+            rates = [int(r) for r in sample_rate]
             sample_rate = [int(r) for r, g in zip(sample_rate, groups) for _ in g]
         skw = _speed_kw(speed)
         if skw and np.ndim(speed) != 0:
@@ -466,6 +527,11 @@ class Chat:
                 raise ValueError("decode_split_to_pcm16: one speed per request, or one for all")
             skw = {"speed": [float(v) for v, g in zip(speed, groups) for _ in g]}
         wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate, **skw)
+        if flags is not None:
+            encs = None if encoding is None else ([encoding] * len(groups) if isinstance(encoding, str) else list(encoding))
+            out = codec.float_to_int16_groups_flac(wav, off, grp, [r if f else None for r, f in zip(rates, flags)], product=product,
+                                                   keep_thr=1e-5 if strip else None, encodings=encs)
+            return [p if p.dtype == np.uint8 else p.copy() for p in out]
         if encoding is not None:
             encs = [encoding] * len(groups) if isinstance(encoding, str) else list(encoding)
             if len(encs) != len(groups):
@@ -721,7 +787,8 @@ class Chat:
               do_text_normalization=True, do_homophone_replacement=True, split_text=True, max_split_batch=4,
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
-              encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False):
+              encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
+              flac: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -762,9 +829,23 @@ class Chat:
         kept on the device), the scaler's chunks are pushed into it and each yield hands out the outputs whose inputs have all
         arrived: the chunks, concatenated, are `resample(time_scale(speed-1 stream), 24000, sample_rate)`; the 16-bit peak, the
         tail's column filter and the companding are taken on those samples.  The first output needs width + M scaled samples
-        beyond its frame (22 at 8000 Hz: under 1 ms on top of the scaler's own)."""
+        beyond its frame (22 at 8000 Hz: under 1 ms on top of the scaler's own).
+        `flac=True` (keyword-only, non-streamed only; needs `pcm16=True`, not together with `encoding`: ValueError otherwise): every
+        result is a uint8 array holding the complete FLAC file (chattts_amd/flac.py: mono, 16 bits, at `sample_rate`) of exactly the
+        int16 samples the same call returns without it -- lossless, encoded on the device behind the conversion
+        (CodecEngine.flac_encode), so that the compressed bytes are what cross PCIe.  A streamed FLAC would need a variable-block-size
+        stream and carried sample numbers: it raises."""
         if G711.check_encoding(encoding) is not None and not pcm16:
             raise ValueError("encoding applies to 16-bit output: pass pcm16=True")
+        if flac:
+            if not pcm16:
+                raise ValueError("flac applies to 16-bit output: pass pcm16=True")
+            if encoding is not None:
+                raise ValueError("flac does not go with an encoding (a FLAC file holds the 16-bit samples)")
+            if stream:
+                raise ValueError("flac applies to non-streamed inference only (a streamed FLAC needs a variable-block-size stream and "
+                                 "carried sample numbers, which is not implemented)")
+            FLAC.rate_code(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         skw = _speed_kw(speed)
         if stream and skw and not stream_time_scale:
             raise ValueError("speed applies to non-streamed inference only (a chunk's frames depend on the path of everything before it; "
@@ -806,7 +887,7 @@ class Chat:
         res_gen = self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
-                              sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw)
+                              sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}))
         if stream:
             return res_gen
         if refine_text_only:
@@ -815,7 +896,8 @@ class Chat:
             rows = [h for hids in res_gen for h in hids]
             if rows:
                 return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}),
-                                                  **({} if encoding is None else {"encoding": encoding}), **skw)
+                                                  **({} if encoding is None else {"encoding": encoding}), **skw,
+                                                  **({"flac": True} if flac else {}))
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
@@ -823,13 +905,15 @@ class Chat:
         stripped = [wav[np.abs(wav) > thr] for wavs in res_gen for wav in wavs]   # sample-level strip, also mid-utterance
         if pcm16:      # split_text: ONE concatenated waveform, hence one peak over all sentences -- converted on the host
             one = float_to_int16(np.concatenate(stripped))
+            if flac:      # a split request concatenated on the host: encoded by the host twin, like the conversion in front of it
+                return [np.frombuffer(FLAC.encode(one, sample_rate), np.uint8)]
             return [one if encoding is None else G711.encode(one, encoding)]
         return [np.concatenate(stripped)] if split_text else stripped
 
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-               speed: Optional[float] = None):
+               speed: Optional[float] = None, flac: bool = False):
         """core.py:395-503 (generator).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -853,7 +937,7 @@ class Chat:
         rs = [] if ts is not None and sample_rate is not None else None      # ... at another rate: and their streams of the resampler
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
-                                           encoding, speed, ts, rs)
+                                           encoding, speed, ts, rs, **({"flac": True} if flac else {}))
         finally:
             for h in ts or ():                                 # also when the consumer drops the generator half way
                 self.codec.time_scale_stream_close(h)
@@ -861,7 +945,7 @@ class Chat:
                 self.codec.resample_stream_close(h)
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None):
+                       rs=None, flac: bool = False):
         """the batch loop of `_infer`"""
         def open_streams(rows):
             ts.extend(self.codec.time_scale_stream_open(speed) for _ in rows)
@@ -883,6 +967,8 @@ class Chat:
                         rkw["encoding"] = encoding
                     if speed is not None:
                         rkw["speed"] = speed
+                    if flac and pcm16:
+                        rkw["flac"] = True
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
                         rows = [h.clone() for h in src]
                         result.destroy()

@@ -2004,6 +2004,82 @@ extern "C" int ctts_g711_encode_ranges(const int16_t* pcm, uint8_t* out, const c
   CK(launch_g711_ranges(pcm, out, (const G711Range*)rng_dev, n_rng, n_max, (hipStream_t)stream));
   return 0;
 }
+static_assert(sizeof(ctts_flac_range) == 32 && sizeof(FlacRange) == 32 && offsetof(ctts_flac_range, rate) == offsetof(FlacRange, rate) &&
+              offsetof(ctts_flac_range, count_idx) == offsetof(FlacRange, count_idx) &&
+              offsetof(ctts_flac_range, frame0) == offsetof(FlacRange, frame0) && sizeof(FlacFrame) == 96, "ctts_flac_range layout");
+static bool flac_rate_ok(int32_t rate) {
+  switch (rate) {
+    case 88200: case 176400: case 192000: case 96000: return true;
+  }
+  return rate >= 1 && rate <= 65535;
+}
+// the checks of a host table; sizes: n_frames, out bytes, work bytes, the most slots of one range, the end of the last range (elements)
+static int flac_check_table(const char* who, const ctts_flac_range* rng_host, int32_t n_rng, long long sizes[5], bool* wants_counts) {
+  if (!rng_host) return fail("%s: a null pointer (the host range table is needed)", who);
+  if (n_rng < 1 || n_rng > 1024) return fail("%s: need 1 <= n_rng <= 1024 (got %d)", who, n_rng);
+  long long end = 0, frames = 0, frames_max = 0, out_bytes = 0;
+  *wants_counts = false;
+  for (int i = 0; i < n_rng; ++i) {
+    const ctts_flac_range& r = rng_host[i];
+    if (r.rate != 0 && !flac_rate_ok(r.rate))
+      return fail("%s: range %d: a rate of %d Hz cannot be coded (0 skips the range; else a rate of the format's table or 1 .. 65535)", who, i, r.rate);
+    if (r.start < 0 || (r.start & 7)) return fail("%s: range %d starts at element %lld: starts are multiples of 8", who, i, (long long)r.start);
+    if (r.n < 0) return fail("%s: range %d has a negative length (%lld)", who, i, (long long)r.n);
+    if (r.start >= (1ll << 46) || r.n >= (1ll << 31)) return fail("%s: range %d lies beyond what a launch can address (n < 2^31)", who, i);
+    if (r.start < end) return fail("%s: range %d starts at element %lld, before the end %lld of the ranges in front of it (overlapping or descending)", who,
+                                   i, (long long)r.start, end);
+    if (r.count_idx < -1 || r.count_idx > 65535) return fail("%s: range %d: count_idx %d is neither -1 nor in 0 .. 65535", who, i, r.count_idx);
+    end = r.start + r.n;
+    if (r.frame0 != frames) return fail("%s: range %d: frame0 is %lld, the ranges in front of it own %lld frame slots", who, i, (long long)r.frame0, frames);
+    if (r.rate == 0) continue;
+    if (r.count_idx >= 0) *wants_counts = true;
+    const long long fr = (r.n + FLAC_BLOCK - 1) / FLAC_BLOCK;
+    frames += fr;
+    frames_max = std::max(frames_max, fr);
+    out_bytes += 2 * r.n + 16 * fr;
+  }
+  sizes[0] = frames;
+  sizes[1] = out_bytes;
+  sizes[2] = ((frames + 1 + n_rng) * 8 + frames * (long long)sizeof(FlacFrame) + 15) / 16 * 16;
+  sizes[3] = frames_max;
+  sizes[4] = end;
+  return 0;
+}
+extern "C" int ctts_flac_encode_sizes(const ctts_flac_range* rng_host, int32_t n_rng, int64_t* sizes) {
+  const char* who = "ctts_flac_encode_sizes";
+  if (!sizes) return fail("%s: a null pointer (sizes[3] is needed)", who);
+  long long s[5];
+  bool wants_counts;
+  if (flac_check_table(who, rng_host, n_rng, s, &wants_counts)) return -1;
+  sizes[0] = s[0];
+  sizes[1] = s[1];
+  sizes[2] = s[2];
+  return 0;
+}
+extern "C" int ctts_flac_encode_ranges(const int16_t* pcm, const int64_t* counts, const ctts_flac_range* rng_dev, const ctts_flac_range* rng_host,
+                                       int32_t n_rng, uint8_t* out, size_t out_bytes, void* work, size_t work_bytes, void* stream) {
+  const char* who = "ctts_flac_encode_ranges";
+  if (!pcm || !out || !rng_dev || !rng_host || !work) return fail("%s: a null pointer (pcm, out, work and both range tables are needed)", who);
+  long long s[5];
+  bool wants_counts;
+  if (flac_check_table(who, rng_host, n_rng, s, &wants_counts)) return -1;
+  if (wants_counts && !counts) return fail("%s: a null pointer (a range has a count_idx, so counts is needed)", who);
+  if (((uintptr_t)pcm & 15) || ((uintptr_t)out & 15) || ((uintptr_t)work & 15) || ((uintptr_t)counts & 7))
+    return fail("%s: pcm, out and work must be 16-byte aligned, counts 8-byte aligned", who);
+  if ((long long)out_bytes < s[1] || out_bytes >= (1ull << 62))
+    return fail("%s: out holds %zu bytes, the ranges may need %lld (out of capacity)", who, out_bytes, s[1]);
+  if ((long long)work_bytes < s[2] || work_bytes >= (1ull << 62))
+    return fail("%s: work holds %zu bytes, %lld are needed (out of capacity)", who, work_bytes, s[2]);
+  const uintptr_t p0 = (uintptr_t)pcm, o0 = (uintptr_t)out;
+  if (p0 == o0 || (p0 < o0 + (uintptr_t)out_bytes && o0 < p0 + 2 * (uintptr_t)s[4]))
+    return fail("%s: out aliases pcm (the encoding is not in place)", who);
+  if (s[0] == 0) return 0;                       // nothing but skipped or empty ranges
+  CttsDeviceGuard dg(stream);
+  long long* meta = (long long*)work;
+  CK(launch_flac_encode(pcm, (const long long*)counts, (const FlacRange*)rng_dev, n_rng, s[3], s[0], out, meta,
+                        (FlacFrame*)(meta + s[0] + 1 + n_rng), (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_k_exp_draws(uint64_t seed, int32_t step, int32_t row0, int32_t rows, int32_t V, float* out, void* stream) {
   if (!out || rows <= 0 || V <= 0) return fail("ctts_k_exp_draws: bad arguments");
   CK(launch_exp_draws(seed, step, row0, rows, V, out, (hipStream_t)stream));

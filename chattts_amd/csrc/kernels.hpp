@@ -554,6 +554,32 @@ struct G711Range {
 // n_max: the longest range (grid size)
 hipError_t launch_g711_ranges(const int16_t* pcm, uint8_t* out, const G711Range* rng, int n_rng, long long n_max, hipStream_t st);
 
+// ---- FLAC encoding (flac.hip) ----------------------------------------------------------------------
+#define FLAC_BLOCK 4096       // samples per frame (the stream's fixed block size) and per workgroup
+// ctts_flac_range (include/chattts_amd.h), field for field (capi.hip asserts the layout): elements [start, start + n) of the int16 input
+// are one signal at `rate` Hz (0: the range is skipped); count_idx >= 0: its length is min(counts[count_idx], n), read on the device;
+// the range owns the frame slots [frame0, frame0 + ceil(n / FLAC_BLOCK))
+struct FlacRange {
+  long long start, n;
+  int32_t rate, count_idx;
+  long long frame0;
+};
+// what flac_analyse_k decides for one frame slot and flac_pack_k writes out; len 0: the slot holds no frame
+struct FlacFrame {
+  int32_t len;                // bytes of the frame, CRC-16 included
+  int32_t kind;               // 0 CONSTANT, 1 VERBATIM, 2 FIXED
+  int32_t order, part;        // FIXED: the predictor order and the Rice partition order
+  int32_t bits;               // of the subframe
+  int32_t n;                  // samples of the block
+  int32_t hdr;                // bytes of the frame header, CRC-8 included
+  int32_t number;             // the frame number
+  uint8_t k[64];              // the Rice parameter of each partition
+};
+// meta: int64 [n_frames + 1 + n_rng] -- the slots' exclusive byte offsets, the total, then each range's signal length; rec: [n_frames];
+// frames_max: the most slots of one range (grid size).  Every bound is the caller's to check
+hipError_t launch_flac_encode(const int16_t* pcm, const long long* counts, const FlacRange* rng, int n_rng, long long frames_max,
+                              long long n_frames, uint8_t* out, long long* meta, FlacFrame* rec, hipStream_t st);
+
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------
 // |STFT| of one waveform: center=True reflect padding, frame f = padded[256 f, 256 f + 1024) * window, 1024-point FFT,
 // mag [F][516] (bins 0..512, then 3 zeros so that the mel projection's K is a multiple of 4)

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import flac as FLAC
 from . import g711 as G711
 from . import resample as RS
 from . import timescale as TS
@@ -1960,6 +1961,34 @@ class CodecEngine:
                 return blob[2 * E:], starts
         return blob, starts
 
+    def float_to_int16_groups_flac(self, wav: torch.Tensor, off, grp, rates, product: str = "f64", keep_thr: Optional[float] = 1e-5,
+                                   encodings=None) -> list:
+        """`float_to_int16_groups` with FLAC behind it: `rates`, one entry per group -- None: the group comes back as
+        `unpack_groups` hands it out (int16 samples, or with `encodings` its G.711 codes); a rate in Hz: as the complete FLAC file (a
+        uint8 array) of exactly its int16 samples.  The grouped slots and the count header on the device go straight into
+        `flac_encode` (a group's stripped length is known on the device only); when every group is encoded the samples never cross
+        the bus.  A group has a rate or an encoding, not both."""
+        n_grp = len(grp) - 1
+        if len(rates) != n_grp or (encodings is not None and len(encodings) != n_grp):
+            raise ValueError("float_to_int16_groups_flac: one rate (or None) and one encoding (or None) per group")
+        for g, r in enumerate(rates):
+            if r is not None:
+                FLAC.rate_code(r)
+                if encodings is not None and encodings[g] is not None:
+                    raise ValueError("float_to_int16_groups_flac: a group is FLAC or companded, not both")
+        if encodings is not None and all(G711.check_encoding(e) is None for e in encodings):
+            encodings = None
+        blob, starts = self.float_to_int16_groups(wav, off, grp, product, keep_thr, encodings=encodings)
+        if all(r is None for r in rates):
+            return self.unpack_groups(self.to_host(blob), starts, encodings)
+        hdr, E = (8 * n_grp + 15) // 16 * 16, int(starts[-1])
+        pcm_at, cnt_at = (hdr, 0) if encodings is None else (0, 2 * E)           # header | samples, or samples | header | codes
+        enc = self.flac_encode(blob[pcm_at: pcm_at + 2 * E].view(torch.int16),
+                               [(int(starts[g]), int(starts[g + 1] - starts[g]), rates[g], g) for g in range(n_grp)],
+                               counts=blob[cnt_at: cnt_at + 8 * n_grp].view(torch.int64), info=True)
+        plain = self.unpack_groups(self.to_host(blob), starts, encodings) if any(r is None for r in rates) else None
+        return [plain[g] if rates[g] is None else FLAC.file_bytes(enc[g][0], enc[g][1], enc[g][2], rates[g]) for g in range(n_grp)]
+
     @staticmethod
     def unpack_groups(host_blob: np.ndarray, starts, encodings=None) -> List[np.ndarray]:
         """`float_to_int16_groups`'s blob on the host -> one int16 array per group (views of the blob); with `encodings` (those of the
@@ -2341,6 +2370,62 @@ class CodecEngine:
                                                     st.cuda_stream), "ctts_g711_encode_ranges")
         tab_d.record_stream(st)
         return out
+
+    def flac_encode(self, pcm: torch.Tensor, ranges, counts: Optional[torch.Tensor] = None, info: bool = False) -> list:
+        """FLAC on the device (ctts_flac_encode_ranges, csrc/flac.hip): `pcm`, a contiguous int16 device tensor, taken as flat;
+        `ranges`: up to 1024 (start, n, rate) or (start, n, rate, count_idx) in ascending order -- elements [start, start + n) are one
+        signal at `rate` Hz (None / 0: the range is skipped); with a count_idx the signal's length is min(counts[count_idx], n), read on
+        the device (`counts`: an int64 device tensor, e.g. float_to_int16_groups' count header).  Starts are multiples of 8.  Returns
+        one uint8 array per range, its frames back to back (`flac.frames` byte for byte; None for a skipped range); `info`: (frames,
+        frame lengths, samples) instead -- what `flac.file_bytes` needs.  Three launches whatever the number of ranges, then one small
+        copy (the frame offsets, the total and the sample counts) and one copy of exactly the bytes used: the compressed bytes are what
+        cross the bus.  The library refuses bad tables before anything is launched (EngineError)."""
+        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()):
+            raise ValueError("flac_encode: a contiguous int16 device tensor")
+        if counts is not None and not (counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()):
+            raise ValueError("flac_encode: `counts` must be a contiguous int64 device tensor")
+        n_el, n_rng = pcm.numel(), len(ranges)
+        tab = np.zeros(n_rng, _lib.FLAC_RANGE)
+        slots = 0
+        for k, r in enumerate(ranges):
+            rate = int(r[2] or 0)
+            ci = int(r[3]) if len(r) > 3 and r[3] is not None else -1
+            if ci >= 0 and (counts is None or ci >= counts.numel()):
+                raise ValueError(f"flac_encode: range {k} reads count {ci}, beyond `counts`")
+            tab[k] = (int(r[0]), int(r[1]), rate, ci, slots)
+            slots += (max(int(r[1]), 0) + FLAC.BLOCK - 1) // FLAC.BLOCK if rate else 0
+        if n_rng and int((tab["start"] + np.maximum(tab["n"], 0)).max()) > n_el:
+            raise ValueError(f"flac_encode: a range ends beyond the {n_el} samples")
+        sizes = (C.c_int64 * 3)()
+        _lib.check(self.lib.ctts_flac_encode_sizes(tab.ctypes.data_as(C.c_void_p), n_rng, sizes), "ctts_flac_encode_sizes")
+        n_frames, out_bytes, work_bytes = (int(v) for v in sizes)
+        empty = np.zeros((0,), np.uint8)
+        if n_frames == 0:
+            res = [(None if not tab["rate"][k] else empty) for k in range(n_rng)]
+            return [None if b is None else (b, np.zeros((0,), np.int64), 0) for b in res] if info else res
+        dev = pcm.device
+        out = torch.empty(((out_bytes + 15) // 16 * 16,), dtype=torch.uint8, device=dev)
+        work = torch.empty((work_bytes,), dtype=torch.uint8, device=dev)
+        tab_d = torch.from_numpy(tab.view(np.uint8)).to(dev)
+        st = torch.cuda.current_stream(dev)
+        _lib.check(self.lib.ctts_flac_encode_ranges(pcm.data_ptr(), _lib.ptr(counts), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), n_rng,
+                                                    out.data_ptr(), out.numel(), work.data_ptr(), work.numel(), st.cuda_stream),
+                   "ctts_flac_encode_ranges")
+        tab_d.record_stream(st)
+        meta = self.to_host(work[: (8 * (n_frames + 1 + n_rng) + 15) // 16 * 16]).view(np.int64)     # offsets, total, sample counts
+        total = int(meta[n_frames])
+        blob = self.to_host(out[: (total + 15) // 16 * 16])[:total] if total else empty
+        res = []
+        for k in range(n_rng):
+            if not tab["rate"][k]:
+                res.append(None)
+                continue
+            f0 = int(tab["frame0"][k])
+            offs = meta[f0: f0 + (int(tab["n"][k]) + FLAC.BLOCK - 1) // FLAC.BLOCK + 1]
+            lens = np.diff(offs)
+            frames = blob[int(offs[0]): int(offs[-1])]
+            res.append((frames, lens[lens > 0], int(meta[n_frames + 1 + k])) if info else frames)
+        return res
 
     def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str, laws=None):
         """`decode_windows` with at least one window at another rate than 24 kHz"""

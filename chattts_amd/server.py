@@ -96,7 +96,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
-               stream_speed_rates: bool = False):
+               stream_speed_rates: bool = False, flac: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -139,7 +139,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     `stream_speed_rates=True` (with `speed`, `stream_speed` and the rate in `stream_sample_rates`; default off): then such a request is
     served, the scaled stream resampled with the filter's history and look-ahead carried on the device -- from the pool when it can take
     it (SpeechBatcher(stream_speeds=True, stream_speed_rates=True).submit_stream(speed=, sample_rate=)), serially otherwise
-    (Chat.infer(..., stream_time_scale=True, stream_resample=True, stream_scaled_resample=True)); with `g711`, companded too."""
+    (Chat.infer(..., stream_time_scale=True, stream_resample=True, stream_scaled_resample=True)); with `g711`, companded too.
+    `flac=True` (default off: every response, status, warning and /health list is as without it): `response_format` "flac" returns the
+    request's 16-bit samples as a FLAC file (audio/flac; lossless: the samples of the "wav" response, bit for bit), encoded on the device
+    behind the 16-bit conversion (Chat.infer(flac=True) / SpeechBatcher.submit(flac=True)), at whatever rate and speed `sample_rates` /
+    `speed` allow.  `"stream": true` with it gets a 400 (a streamed FLAC needs a variable-block-size stream and carried sample numbers),
+    an `"encoding"` key with it too."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -201,6 +206,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     formats = {"wav", "pcm"} | ({"mp3", "ogg"} if _have_av() else set()) | ({"ulaw", "alaw"} if g711 else set())
     if g711:
         allowed = allowed | {"encoding"}
+    if flac:
+        from . import flac as FLAC
+        formats = formats | {"flac"}
 
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
         model: str = "tts-1"
@@ -224,8 +232,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     spk_emb=v.get("spk_emb"), spk_smp=v.get("spk_smp"), txt_smp=v.get("txt_smp"), stream_batch=24,
                                     stream_speed=12000, pass_first_n_batches=2)
 
-    def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None):   # openai_api.py:168-183,207-222
+    def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None,
+              as_flac: bool = False):                # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if as_flac:
+            kw = {**kw, "flac": True}
         if spd is not None:
             kw = {**kw, "speed": spd}
         if law is not None:
@@ -300,11 +311,26 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 if fmt not in ("wav", "ulaw", "alaw"):
                     raise HTTPException(400, detail=f"encoding {enc} goes with response_format wav, ulaw or alaw, not {fmt}")
                 law = enc
-        media = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "ogg": "audio/ogg", "ulaw": "audio/PCMU", "alaw": "audio/PCMA"}[fmt]
-        ekw = {} if law is None else {"encoding": law}
+        as_flac = bool(flac) and fmt == "flac"       # the engine hands out the file
+        if as_flac:
+            if req.stream:
+                raise HTTPException(400, detail="flac is served for non-streamed requests only: a streamed FLAC needs a variable-block-size "
+                                                "stream and carried sample numbers")
+            if request_data.get("encoding") is not None:
+                raise HTTPException(400, detail=f"encoding {request_data['encoding']} does not go with response_format flac (a FLAC file "
+                                                f"holds the 16-bit samples)")
+            try:
+                FLAC.rate_code(rate)
+            except ValueError as e:
+                raise HTTPException(400, detail=str(e))
+        media = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "ogg": "audio/ogg", "ulaw": "audio/PCMU", "alaw": "audio/PCMA",
+                 "flac": "audio/flac"}[fmt]
+        ekw = ({} if law is None else {"encoding": law}) if not as_flac else {"flac": True}
         stream_header = wav_stream_header if law is None else (lambda r: g711_wav_stream_header(law, r))
 
         def encode(pcm: np.ndarray, header: bool) -> bytes:
+            if as_flac:
+                return np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype=np.uint8).tobytes()
             if law is not None:
                 codes = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype=np.uint8)
                 return g711_to_wav_bytes(codes, law, rate) if (fmt == "wav" and header) else codes.tobytes()
@@ -363,8 +389,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         else:
             async with app.state.model_lock:
                 try:
-                    wavs = await run_in_threadpool(infer, req, rate, *(() if law is None and spd is None else (law,)),
-                                                   *(() if spd is None else (spd,)))
+                    if as_flac:
+                        wavs = await run_in_threadpool(infer, req, rate, None, spd, True)
+                    else:
+                        wavs = await run_in_threadpool(infer, req, rate, *(() if law is None and spd is None else (law,)),
+                                                       *(() if spd is None else (spd,)))
                 except Exception as e:
                     raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         if len(wavs) == 0:

@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import flac as FLAC
 from . import g711 as G711
 from . import resample as RS
 from . import timescale as TS
@@ -659,6 +660,7 @@ class _Job:
     speed: Optional[float] = None          # None: 1.0 (on a stream only with SpeechBatcher(stream_speeds=True))
     ts_slot: Optional[int] = None          # a stream at another speed: its stream of the time scaler, opened at its first chunk
     rs_slot: Optional[int] = None          # ... and at another rate: its stream of the resampler, opened with it
+    flac: bool = False                     # the result is the FLAC file of the int16 waveform (non-streamed only)
 
     @property
     def is_stream(self) -> bool:
@@ -706,6 +708,8 @@ def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding"
         kw[encoding_kw] = [j.encoding for j in jobs]
     if any(j.speed is not None for j in jobs):
         kw[speed_kw] = [1.0 if j.speed is None else j.speed for j in jobs]
+    if any(j.flac for j in jobs):
+        kw["flac"] = [j.flac for j in jobs]
     return kw
 
 
@@ -780,6 +784,7 @@ class SpeechBatcher:
         self.stream_speed_rates = bool(stream_speeds and stream_speed_rates)   # ... at another rate than 24000 too
         self.stream_scaled_chunks = 0      # chunks of streams at another speed than 1
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
+        self.flac_encoded = 0              # results handed out as FLAC files
         self.max_stream_group = 0     # most chunks one window decode served
         self.cancelled = 0            # streams closed by their consumer before the end
         self.log = logger or logging.getLogger("chattts_amd.serving")
@@ -825,7 +830,7 @@ class SpeechBatcher:
 
     # -- public -------------------------------------------------------------------------------------------------------------
     def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None,
-               encoding=None, speed=None) -> Future:
+               encoding=None, speed=None, flac: bool = False) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
@@ -838,8 +843,15 @@ class SpeechBatcher:
         `encoding=` -- the Future resolves to the uint8 G.711 codes of that waveform; requests that finish together with different
         encodings still share the one decode, and one companding launch (ctts_g711_encode_ranges).  `speed` (None: 1.0; 0.5 .. 2.0):
         the serial call's `speed=` -- the same tokens, time-scaled on the device behind the decode; requests that finish together at
-        different speeds still share the one ragged decode (CodecEngine.time_scale_segments: rows at speed 1 are copied through)."""
+        different speeds still share the one ragged decode (CodecEngine.time_scale_segments: rows at speed 1 are copied through).
+        `flac=True`: the serial call's `flac=` -- the Future resolves to a uint8 array, the complete FLAC file of that int16 waveform
+        at its rate; not together with `encoding`.  Requests that finish together, with and without it, still share the one decode;
+        the encoder runs on the device behind the grouped conversion (CodecEngine.flac_encode), in `finish` by the host twin."""
         G711.check_encoding(encoding)
+        if flac:
+            if encoding is not None:
+                raise ValueError("flac does not go with an encoding (a FLAC file holds the 16-bit samples)")
+            FLAC.rate_code(24000 if sample_rate is None else sample_rate)
         speed = _job_speed(speed)
         self._check_refine(refine)
         if split_text and int(max_split_batch) < 1:
@@ -847,7 +859,7 @@ class SpeechBatcher:
         fut: Future = Future()
         fut.rid = next(self._ids)
         self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding,
-                          speed=speed))
+                          speed=speed, flac=bool(flac)))
         return fut
 
     def cancel(self, fut: Future) -> None:
@@ -856,7 +868,7 @@ class SpeechBatcher:
         self._in.put(_Cancel(fut.rid))
 
     def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None,
-                      speed=None) -> SpeechStream:
+                      speed=None, flac: bool = False) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
@@ -868,7 +880,11 @@ class SpeechBatcher:
         refused: a chunk's frames depend on the path of everything before it, which is not carried across chunks -- unless the
         batcher was built with `stream_speeds=True`: then the chunks are those of the serial call with `speed=, stream_time_scale=True`
         (the path and a tail of samples are carried on the device, per stream), at 24000 Hz only -- unless it was also built with
-        `stream_speed_rates=True`: then `speed` goes with `sample_rate`, the serial call's `stream_scaled_resample=True`."""
+        `stream_speed_rates=True`: then `speed` goes with `sample_rate`, the serial call's `stream_scaled_resample=True`.  `flac` is
+        refused: a streamed FLAC needs a variable-block-size stream and carried sample numbers."""
+        if flac:
+            raise ValueError("flac is served for non-streamed requests only (a streamed FLAC needs a variable-block-size stream and "
+                             "carried sample numbers)")
         G711.check_encoding(encoding)
         speed = _job_speed(speed)
         if speed is not None and not self.stream_speeds:
@@ -903,7 +919,7 @@ class SpeechBatcher:
         occ = {"slots": self.S, "active": len(getattr(pool, "active", {})), "queued": self._in.qsize() + len(getattr(pool, "queue", ())),
                "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed,
                "ragged_decode": self.ragged_decode, "decode_calls": self.decode_calls, "decoded": self.decoded,
-               "max_decode_group": self.max_decode_group, "companded": self.companded,
+               "max_decode_group": self.max_decode_group, "companded": self.companded, "flac_encoded": self.flac_encoded,
                "split": {"requests": self.split_requests, "sentences": self.split_sentences, "max_coresident": self.split_max_coresident}}
         if self.streams:      # (list(): the worker changes the registry meanwhile)
             occ.update({"streams": sum(j.is_stream for j in list(self._jobs.values())), "stream_decode_calls": self.stream_decode_calls,
@@ -943,6 +959,7 @@ class SpeechBatcher:
             self.failed += 1
         else:
             self.completed += 1
+            self.flac_encoded += job.flac
             self.companded += not job.is_stream and job.encoding is not None      # (a stream's chunks are counted as they go out)
         if job.is_stream:
             job.sink._q.put(None if cancelled else result)
@@ -1204,7 +1221,7 @@ class SpeechBatcher:
         self._drain(block=False)
         self.lock.acquire()
 
-    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None) -> np.ndarray:
+    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None, flac: bool = False) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
@@ -1213,9 +1230,11 @@ class SpeechBatcher:
         wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}),
                                        **({} if speed is None else {"speed": float(speed)}))[0]
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
+        if flac:                                                            # converted on the host, encoded by the host twin
+            return np.frombuffer(FLAC.encode(pcm, 24000 if sample_rate is None else int(sample_rate)), np.uint8)
         return pcm if encoding is None else G711.encode(pcm, encoding)      # converted on the host, companded by the host twin
 
-    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None) -> list:
+    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None, flac=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
         returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000);
         `speeds`: one speed per request (None: 1.0)"""
@@ -1228,6 +1247,8 @@ class SpeechBatcher:
                 kw["encoding"] = [encodings[i] for i in live]
             if speeds is not None:
                 kw["speed"] = [float(speeds[i]) for i in live]
+            if flac is not None and any(flac[i] for i in live):
+                kw["flac"] = [bool(flac[i]) for i in live]
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out

@@ -608,6 +608,35 @@ typedef struct {
 int ctts_g711_encode_ranges(const int16_t* pcm, uint8_t* out, const ctts_g711_range* rng_dev, const ctts_g711_range* rng_host, int32_t n_rng,
                             void* stream);
 
+/* FLAC behind the PCM16 conversion: 16-bit mono PCM -> FLAC frames, losslessly (chattts_amd/flac.py is the NumPy twin, byte for byte).
+ * The subset: fixed block size 4096 (frames start FF F8; a shorter last block carries n - 1 in 16 bits), the rate by its table code or in
+ * Hz (16 bits), one subframe per frame: CONSTANT when all samples are equal, else FIXED order o in 0 .. min(4, n - 1) with 4-bit Rice
+ * parameters k in 0 .. 14 over 2^p partitions, p in 0 .. min(6, ctz(n)), (n >> p) > o, when STRICTLY smaller than VERBATIM.  The choice is
+ * exact: the smallest subframe in bits over every (o, p, k per partition), ties to the lowest o, then p, then k -- so a frame is at most
+ * 16 + 2 n bytes.  CRC-8 (0x07) over the header, CRC-16 (0x8005) over the frame.
+ * Range r: elements [start, start + n) of `pcm` are one signal at `rate` Hz; rate 0: the range is skipped.  count_idx >= 0: the signal's
+ * length is min(counts[count_idx], n), read ON THE DEVICE (the kept counts of ctts_float_to_int16_groups; the caller vouches for the
+ * index); -1: it is n.  The range owns the frame slots [frame0, frame0 + ceil(n / 4096)), frame0 = the slots of the ranges in front of
+ * it (skipped ranges own none).  The frames of all ranges are written back to back from out[0] on, in slot order, so that a range's
+ * frames form one slice; bytes behind the total are not written.  `work` receives, from its first byte on, int64 [n_frames + 1] the
+ * exclusive byte offset of every slot (an unused slot has length 0) and the total, then int64 [n_rng] each range's signal length: what
+ * the host copies before it copies exactly the bytes used.  Three launches (flac_analyse_k, flac_scan_k, flac_pack_k) whatever the
+ * number of ranges.  ctts_flac_encode_sizes checks a host table and gives sizes[3] = {n_frames, the bytes `out` must hold
+ * (sum of 2 n + 16 ceil(n / 4096)), the bytes `work` must hold}.  Refused on the host table before anything is launched: a null pointer
+ * (counts may be null when no range has a count_idx), n_rng < 1 or > 1024, a start that is negative or no multiple of 8, n negative or
+ * >= 2^31, ranges that overlap or descend, a rate that is negative or neither in the format's table nor < 65536, a count_idx < -1
+ * or > 65535, a frame0 other than the running sum, out_bytes or work_bytes too small, pointers not 16-byte aligned, `out` aliasing `pcm`. */
+typedef struct {
+  int64_t start;          /* first element of the int16 input; a multiple of 8 */
+  int64_t n;              /* samples (with count_idx >= 0: the capacity) */
+  int32_t rate;           /* Hz; 0: the range is skipped */
+  int32_t count_idx;      /* index into counts, or -1 */
+  int64_t frame0;         /* the range's first frame slot */
+} ctts_flac_range;        /* 32 bytes */
+int ctts_flac_encode_sizes(const ctts_flac_range* rng_host, int32_t n_rng, int64_t* sizes);
+int ctts_flac_encode_ranges(const int16_t* pcm, const int64_t* counts, const ctts_flac_range* rng_dev, const ctts_flac_range* rng_host,
+                            int32_t n_rng, uint8_t* out, size_t out_bytes, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Full DVAE (asset/DVAE.safetensors): audio -> 4 x T codes and codes -> mel through the GFSQ codebook.
  * Replaces `self.dvae(wav, "encode")` of `Chat.sample_audio_speaker` (ChatTTS/core.py:179-180 ->
