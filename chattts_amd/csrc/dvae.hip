@@ -299,3 +299,21 @@ extern "C" int ctts_dvae_decode_codes(ctts_dvae* c, const int64_t* codes, float*
   CK(launch_gemm_tiled(oc, st));
   return 0;
 }
+
+// ---- single-kernel entry points (unit parity tests) ----------------------------------------------------------------------------
+extern "C" int ctts_k_stft_mag(const float* wav, int32_t n, const float* window, const float* twiddle, float* mag, int32_t F, void* stream) {
+  if (!wav || !window || !twiddle || !mag) return ctts_fail("ctts_k_stft_mag: bad arguments");
+  CK(launch_stft_mag(wav, n, window, twiddle, mag, F, (hipStream_t)stream));
+  return 0;
+}
+// the quantiser pair takes the engine: GfsqArgs as ctts_dvae_create marshalled them are part of what is under test
+extern "C" int ctts_k_gfsq_encode(ctts_dvae* c, const float* feat, int32_t* codes, int32_t rows, void* stream) {
+  if (!c || !feat || !codes || rows < 1) return ctts_fail("ctts_k_gfsq_encode: bad arguments");
+  CK(launch_gfsq_encode(c->q, feat, codes, rows, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ctts_k_gfsq_embed(ctts_dvae* c, const int64_t* codes, float* feat, int32_t rows, void* stream) {
+  if (!c || !codes || !feat || rows < 1) return ctts_fail("ctts_k_gfsq_embed: bad arguments");
+  CK(launch_gfsq_embed(c->q, codes, feat, rows, (hipStream_t)stream));
+  return 0;
+}

@@ -279,7 +279,10 @@ __global__ __launch_bounds__(256) void gemm_tiled_f32_k(GemmArgs a) {
         else if (EPI == EPI_BIAS_SCALE_RES) v = rv[r] + gam * (v + bias);
         else if (EPI == EPI_RES) v = rv[r] + v;
         else if (EPI == EPI_SCALE) v = v * gam;
-        else if (EPI == EPI_LOG_DIV) v = logf(fmaxf(v, 1e-5f)) / gam;
+        // the device's logf is ~1.4 ulp off at log(1e-5) (v_log_f32 is 1 ulp of log2 = -16.6, a wider binade than ln = -11.5), which the
+        // division by coef can stretch past 2 ulps of the result -- and log(1e-5) / coef is what EVERY band of a silent frame holds.
+        // The log in double, rounded once: F x 100 elements per clip, off the hot path
+        else if (EPI == EPI_LOG_DIV) v = (float)log((double)fmaxf(v, 1e-5f)) / gam;
         a.C[(size_t)row * a.ldc + col] = v;
       }
     }

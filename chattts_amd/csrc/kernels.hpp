@@ -57,7 +57,7 @@ enum GemmEpi {
   EPI_BIAS_GELU = 4,   // C = gelu(acc + bias[n])
   EPI_BIAS_SCALE_RES = 5,  // C = res + gamma[n] * (acc + bias[n])    (ConvNeXt pwconv2)
   EPI_SCALE = 6,       // C = acc * scale[n]                          (DVAE out_conv * coef)
-  EPI_LOG_DIV = 7,     // C = log(max(acc, 1e-5)) / gamma[n]          (log-mel / coef, DVAE encode; f32 tiles only)
+  EPI_LOG_DIV = 7,     // C = log(max(acc, 1e-5)) / gamma[n]          (log-mel / coef, DVAE encode; f32 tiles only; the log in double)
 };
 
 struct GemmArgs {

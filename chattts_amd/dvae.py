@@ -19,6 +19,15 @@ import torch
 from . import _lib
 
 
+def pair_repack_k4s2(w4: torch.Tensor) -> torch.Tensor:
+    """Conv1d(C, Cout, 4, stride 2, pad 1) over frames == Conv1d(2C, Cout, 3, pad 1) over frame PAIRS:
+    out[t] = W0 x[2t-1] + W1 x[2t] + W2 x[2t+1] + W3 x[2t+2]  ->  taps {[0,W0], [W1,W2], [W3,0]} on (x[2u], x[2u+1]).
+    w4 [Cout, C, 4] (torch layout) -> float32 [Cout, 3, 2C], tap-major as the conv GEMM reads its weight rows."""
+    w4 = w4.to(torch.float32)
+    z = torch.zeros_like(w4[:, :, 0])
+    return torch.stack([torch.cat([z, w4[:, :, 0]], 1), torch.cat([w4[:, :, 1], w4[:, :, 2]], 1), torch.cat([w4[:, :, 3], z], 1)], 1)
+
+
 class DvaeEngine:
     LEVELS, G, R = (5, 5, 5, 5), 2, 2          # config.py:23-28
 
@@ -71,12 +80,8 @@ class DvaeEngine:
         trunk(w.encoder, "encoder.")
         trunk(w.decoder, "decoder.")
         w.ds0_w, w.ds0_b = P(convw(sd["downsample_conv.0.weight"])), P(f(sd["downsample_conv.0.bias"]))
-        # Conv1d(512,512,4,stride 2,pad 1) over frames == Conv1d(1024,512,3,pad 1) over frame PAIRS:
-        # out[t] = W0 x[2t-1] + W1 x[2t] + W2 x[2t+1] + W3 x[2t+2]  ->  taps {[0,W0], [W1,W2], [W3,0]} on (x[2u], x[2u+1])
-        w4 = sd["downsample_conv.2.weight"].to(torch.float32)             # [512, 512, 4]
-        z = torch.zeros_like(w4[:, :, 0])
-        pair = torch.stack([torch.cat([z, w4[:, :, 0]], 1), torch.cat([w4[:, :, 1], w4[:, :, 2]], 1), torch.cat([w4[:, :, 3], z], 1)], 1)
-        w.ds1_w, w.ds1_b = P(f(pair.reshape(512, -1))), P(f(sd["downsample_conv.2.bias"]))
+        pair = pair_repack_k4s2(sd["downsample_conv.2.weight"])           # [512, 3, 1024]
+        w.ds1_w, w.ds1_b = P(f(pair.reshape(pair.shape[0], -1))), P(f(sd["downsample_conv.2.bias"]))
         w.out_conv_w = P(convw(sd["out_conv.weight"]))
         w.coef = P(f(sd["coef"].reshape(-1)))
         q = lambda g, n: sd[f"vq_layer.quantizer.rvqs.{g}.{n}"]

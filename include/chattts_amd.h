@@ -849,6 +849,13 @@ int ctts_k_dwconv_ln_ex(const float* x, const float* w, const float* b, const fl
                         float* y, int32_t B, int32_t F, int32_t C, uint16_t* yp, int32_t plane_f16, const int32_t* seg, void* stream);
 int ctts_k_layernorm(const float* x, const float* w, const float* b, float eps, float* y, int32_t rows, void* stream);
 int ctts_k_istft(const float* head, const float* window, const float* twiddle, float* frames, float* wav, int32_t B, int32_t F, void* stream);
+/* The full DVAE's own kernels alone (csrc/dvae.hip).  stft_mag: wav [n] -> mag [F][516] (513 bins of |stft(center, reflect, hann)|, then
+ * 3 zero columns), window [1024], twiddle [512][2] as ctts_dvae_weights; refused, with nothing launched, unless n > 512 and
+ * F == 1 + n / 256.  gfsq_encode: feat [rows][1024] -> codes [rows][4] int32; gfsq_embed: codes [rows][4] int64 -> feat [rows][1024];
+ * both read the quantiser's weights and levels as ctts_dvae_create marshalled them into the engine `c`. */
+int ctts_k_stft_mag(const float* wav, int32_t n, const float* window, const float* twiddle, float* mag, int32_t F, void* stream);
+int ctts_k_gfsq_encode(ctts_dvae* c, const float* feat, int32_t* codes, int32_t rows, void* stream);
+int ctts_k_gfsq_embed(ctts_dvae* c, const int64_t* codes, float* feat, int32_t rows, void* stream);
 
 #ifdef __cplusplus
 }
