@@ -24,6 +24,7 @@ import torch
 
 from . import flac as FLAC
 from . import g711 as G711
+from . import loudness as LN
 from . import resample as RS
 from . import timescale as TS
 from . import weights as W
@@ -77,6 +78,17 @@ def _speed_kw(speed) -> dict:
     if all(TS.quantize(v)[0] == TS.DEN for v in one):
         return {}
     return {"speed": float(speed) if np.ndim(speed) == 0 else [float(v) for v in speed]}
+
+
+def _loudness_kw(loudness) -> dict:
+    """the decode calls' `loudness=` argument: nothing for None, alone or everywhere (today's call, argument for argument); ValueError
+    for a target outside -40 .. -5 LUFS"""
+    if loudness is None:
+        return {}
+    vals = [LN.check_target(v) for v in ([loudness] if np.ndim(loudness) == 0 else list(loudness))]
+    if all(v is None for v in vals):
+        return {}
+    return {"loudness": vals[0] if np.ndim(loudness) == 0 else vals}
 
 
 def split_sentences(text: str) -> List[str]:
@@ -290,7 +302,7 @@ class Chat:
             24, params.manual_seed, self.context, **kw))
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None, *,
-                       ragged: bool = False, sample_rate=None, speed=None):
+                       ragged: bool = False, sample_rate=None, speed=None, loudness=None):
         """`Chat._decode_to_wavs` (core.py:513-539) -> np.float32 [B, n]: per-row hidden states [T_b,768] through the
         decoder, or (use_decoder=False) per-row token ids [T_b,4] through the full DVAE's codebook; then Vocos.
         `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded).
@@ -298,8 +310,12 @@ class Chat:
         -> List[np.ndarray], row b's 256 (2 T_b - 1) samples; the decoder path only.
         `sample_rate` (None: 24000; with `ragged` also one per row): the waveforms are resampled on the device behind the ISTFT.
         `speed` (None: 1.0; with `ragged` also one per row): pitch-preserving time scaling on the device (CodecEngine.time_scale), at
-        24 kHz, behind the ISTFT and in front of the resampler."""
+        24 kHz, behind the ISTFT and in front of the resampler.
+        `loudness` (None: untouched; a target in LUFS, -40 .. -5, also one per row, None entries left alone): every row is brought to
+        that BS.1770 integrated loudness on the device (CodecEngine.loudness_normalize), under the +30 dB cap and the -1 dBFS ceiling:
+        the last float32 stage, behind the time scaler and the resampler."""
         skw = _speed_kw(speed)
+        lkw = _loudness_kw(loudness)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
@@ -308,20 +324,24 @@ class Chat:
                 raise ValueError("ragged decoding decodes every row at its own length: pad_to does not apply")
             if len(result_list) == 0:
                 return []
-            wav, off = self.codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw)
+            wav, off = self.codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw)
             return ragged_views(self.codec.to_host(wav), off)
         if len(result_list) == 0:
             return np.array([], dtype=np.float32)
         if use_decoder:
-            return self.codec.to_host(self.codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate, **skw))
+            return self.codec.to_host(self.codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate, **skw, **lkw))
         wav = self.codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to))
         if skw:
             wav = self.codec.time_scale(wav, skw["speed"])
-        return self.codec.to_host(wav if sample_rate is None else self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate)))
+        if sample_rate is not None:
+            wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
+        if lkw:
+            wav = self.codec.loudness_normalize(wav, lkw["loudness"], rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+        return self.codec.to_host(wav)
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
                         product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None,
-                        flac=None) -> List[np.ndarray]:
+                        flac=None, loudness=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
@@ -335,18 +355,23 @@ class Chat:
         (CodecEngine.time_scale) at 24 kHz, in front of the resampler; rows at speed 1 are not touched.
         `flac` (None / False: the call above; True; with `ragged` also one flag per row): a flagged row comes back as a uint8 array, the
         complete FLAC file (chattts_amd/flac.py) of exactly the int16 samples above at the row's rate, encoded on the device behind the
-        conversion (CodecEngine.float_to_int16_groups_flac: the stripped length is known there only); not together with `encoding`."""
+        conversion (CodecEngine.float_to_int16_groups_flac: the stripped length is known there only); not together with `encoding`.
+        `loudness` (None: untouched; a target in LUFS, also one per row, None entries left alone): `wav` above is the waveform
+        normalised on the device (CodecEngine.loudness_normalize) at the rate it is returned at -- behind the time scaler and the
+        resampler, in front of the strip, the conversion, the companding and FLAC, so the -1 dBFS ceiling holds on exactly the samples
+        that are converted."""
         skw = _speed_kw(speed)
+        lkw = _loudness_kw(loudness)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
         flags = self._flac_flags(flac, len(result_list), encoding, per_row=ragged, who="decode_to_pcm16")
         if flags is not None:
-            return self._decode_to_flac(result_list, use_decoder, strip, product, ragged, sample_rate, flags, skw, encoding)
+            return self._decode_to_flac(result_list, use_decoder, strip, product, ragged, sample_rate, flags, skw, encoding, **lkw)
         if ragged:
             if encoding is None:
-                return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, **skw)
-            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding, **skw)
+                return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, **skw, **lkw)
+            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding, **skw, **lkw)
         G711.check_encoding(encoding)
         if len(result_list) == 0:
             return []
@@ -355,6 +380,8 @@ class Chat:
             wav = self.codec.time_scale(wav, skw["speed"])
         if sample_rate is not None:
             wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
+        if lkw:
+            wav = self.codec.loudness_normalize(wav, lkw["loudness"], rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         pcm, keep = self.codec.float_to_int16(wav, per_row=True, product=product, keep_thr=1e-5 if strip else None)
         if encoding is not None:       # codes | keep masks in one buffer: one copy
             B, n = int(pcm.shape[0]), int(pcm.shape[1])
@@ -397,15 +424,16 @@ class Chat:
         return flags
 
     def _decode_to_flac(self, result_list, use_decoder: bool, strip: bool, product: str, ragged: bool, sample_rate, flags, skw,
-                        encoding=None) -> List[np.ndarray]:
+                        encoding=None, loudness=None) -> List[np.ndarray]:
         """`decode_to_pcm16` with at least one row as a FLAC file: the decode of the plain call, then the grouped conversion with one
         group per row (the same samples; slots that start on multiples of 8 and a count header on the device) and the encoder behind it"""
         B = len(result_list)
         if B == 0:
             return []
         codec = self.codec
+        lkw = {} if loudness is None else {"loudness": loudness}
         if ragged:
-            wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw)
+            wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw)
             rates = [CodecEngine.SAMPLE_RATE] * B if sample_rate is None else ([int(sample_rate)] * B if np.ndim(sample_rate) == 0 else
                                                                                 [int(r) for r in sample_rate])
         else:
@@ -415,24 +443,27 @@ class Chat:
             if sample_rate is not None:
                 wav = codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
             wav = wav.contiguous()
+            rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * B
+            if lkw:
+                wav = codec.loudness_normalize(wav, loudness, rates=rates[0])
             off = np.arange(B + 1, dtype=np.int64) * int(wav.shape[1])
             wav = wav.view(-1)
-            rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * B
         encs = None if encoding is None else ([encoding] * B if isinstance(encoding, str) else list(encoding))
         out = codec.float_to_int16_groups_flac(wav, off, np.arange(B + 1, dtype=np.int32), [r if f else None for r, f in zip(rates, flags)],
                                                product=product, keep_thr=1e-5 if strip else None, encodings=encs)
         return [p if p.dtype == np.uint8 else p.copy() for p in out]
 
-    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None, speed=None) -> List[np.ndarray]:
+    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None, speed=None,
+                                loudness=None) -> List[np.ndarray]:
         """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
         PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's result equals
         `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w.  `encoding` (one, or one per row; None entries stay int16): the
         companded rows are converted by one launch behind the conversion, and the codes travel with the keep masks in the one copy
-        (the PCM16 samples too when some row stays int16).  `speed` (one, or one per row) goes to the ragged decode."""
+        (the PCM16 samples too when some row stays int16).  `speed` and `loudness` (one, or one per row) go to the ragged decode."""
         if len(result_list) == 0:
             return []
         codec = self.codec
-        skw = {} if speed is None else {"speed": speed}
+        skw = {**({} if speed is None else {"speed": speed}), **({} if loudness is None else {"loudness": loudness})}
         if encoding is not None:
             encs = [encoding] * len(result_list) if isinstance(encoding, str) else list(encoding)
             if len(encs) != len(result_list):
@@ -454,13 +485,14 @@ class Chat:
         keep_h = host[2 * n: 2 * n + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
-    def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs, speed=None) -> List[np.ndarray]:
+    def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs, speed=None, loudness=None) -> List[np.ndarray]:
         """`_decode_to_pcm16_ragged` with at least one companded row.  The device buffer is int16 samples | codes | keep masks; rows
         that share a law and follow each other make one range.  A range starts on a multiple of 8 elements: rows resampled to
         another rate sit at arbitrary offsets, so a call that mixes laws over such rows goes through the grouped conversion instead
         (one group per row: the same bytes, slots that start on multiples of 8)."""
         codec = self.codec
-        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **({} if speed is None else {"speed": speed}))
+        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **({} if speed is None else {"speed": speed}),
+                                       **({} if loudness is None else {"loudness": loudness}))
         runs = []                     # [first row, one past the last, encoding]
         for i, e in enumerate(encs):
             if runs and runs[-1][2] == e:
@@ -489,7 +521,7 @@ class Chat:
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None,
-                              speed=None, flac=None) -> List[np.ndarray]:
+                              speed=None, flac=None, loudness=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
@@ -504,7 +536,10 @@ class Chat:
         resampler, hence in front of the group's strip and concatenation.
         `flac` (None / False: the call above; True; or one flag per request): a flagged request comes back as a uint8 array, the
         complete FLAC file of exactly the int16 samples above at the request's rate, encoded on the device straight from the grouped
-        slots and their count header (CodecEngine.float_to_int16_groups_flac); not together with `encoding`."""
+        slots and their count header (CodecEngine.float_to_int16_groups_flac); not together with `encoding`.
+        `loudness` (None: untouched; a target in LUFS, or one per request, None entries left alone): a request gets ONE loudness and
+        ONE gain over its sentences (CodecEngine.loudness_normalize with the group table of the conversion behind it): every sentence
+        is filtered alone, the gates run over all of the request's blocks, the peak is the request's."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -526,7 +561,13 @@ class Chat:
             if len(speed) != len(groups):
                 raise ValueError("decode_split_to_pcm16: one speed per request, or one for all")
             skw = {"speed": [float(v) for v, g in zip(speed, groups) for _ in g]}
+        lkw = _loudness_kw(loudness)
+        if lkw and np.ndim(loudness) != 0 and len(loudness) != len(groups):
+            raise ValueError("decode_split_to_pcm16: one loudness target per request, or one for all")
         wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate, **skw)
+        if lkw:
+            wav = codec.loudness_normalize(wav, lkw["loudness"], offsets=off, groups=grp, out=wav,
+                                           rates=[r for r, g in zip(rates, groups) for _ in g])
         if flags is not None:
             encs = None if encoding is None else ([encoding] * len(groups) if isinstance(encoding, str) else list(encoding))
             out = codec.float_to_int16_groups_flac(wav, off, grp, [r if f else None for r, f in zip(rates, flags)], product=product,
@@ -788,7 +829,7 @@ class Chat:
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
-              flac: bool = False):
+              flac: bool = False, loudness=None):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -834,7 +875,20 @@ class Chat:
         result is a uint8 array holding the complete FLAC file (chattts_amd/flac.py: mono, 16 bits, at `sample_rate`) of exactly the
         int16 samples the same call returns without it -- lossless, encoded on the device behind the conversion
         (CodecEngine.flac_encode), so that the compressed bytes are what cross PCIe.  A streamed FLAC would need a variable-block-size
-        stream and carried sample numbers: it raises."""
+        stream and carried sample numbers: it raises.
+        `loudness` (keyword-only, non-streamed only; None: untouched): a target in LUFS, -40 .. -5 -- one number, or one per text.
+        Every utterance is brought to that ITU-R BS.1770-4 integrated loudness on the device (CodecEngine.loudness_normalize) by one
+        gain, capped at +30 dB and at a -1 dBFS sample peak: the last float32 stage, behind the time scaler and the resampler and in
+        front of the silence strip, the 16-bit conversion, the companding and FLAC.  A split request gets ONE gain over its sentences
+        (one target only).  A streamed call with a target raises: an integrated loudness needs the whole utterance."""
+        lkw = _loudness_kw(loudness)
+        if lkw and stream:
+            raise ValueError("loudness applies to non-streamed inference only (an integrated loudness needs the whole utterance; a "
+                             "stream would need a running measure)")
+        if lkw and split_text and np.ndim(loudness) != 0:
+            raise ValueError("a split_text request is one waveform: it takes one loudness target")
+        if lkw:
+            LN.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         if G711.check_encoding(encoding) is not None and not pcm16:
             raise ValueError("encoding applies to 16-bit output: pass pcm16=True")
         if flac:
@@ -884,10 +938,12 @@ class Chat:
         # split_text + pcm16 + ragged_decode: the hidden states of every split batch are collected and the whole request is decoded,
         # stripped, converted under its one peak and compacted on the device (decode_split_to_pcm16) -- the bytes of the host lines below
         split_dev = bool(split_text and pcm16 and ragged_decode and not stream and not refine_text_only)
+        split_host = bool(lkw and split_text and not split_dev and not refine_text_only)      # one gain over the sentences: applied below
         res_gen = self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
-                              sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}))
+                              sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}),
+                              **({} if split_host else lkw))
         if stream:
             return res_gen
         if refine_text_only:
@@ -897,11 +953,13 @@ class Chat:
             if rows:
                 return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}),
                                                   **({} if encoding is None else {"encoding": encoding}), **skw,
-                                                  **({"flac": True} if flac else {}))
+                                                  **({"flac": True} if flac else {}), **lkw)
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
         thr = np.float32(1e-5)
+        if split_host:
+            res_gen = [self._normalize_request([w for wavs in res_gen for w in wavs], lkw["loudness"], sample_rate)]
         stripped = [wav[np.abs(wav) > thr] for wavs in res_gen for wav in wavs]   # sample-level strip, also mid-utterance
         if pcm16:      # split_text: ONE concatenated waveform, hence one peak over all sentences -- converted on the host
             one = float_to_int16(np.concatenate(stripped))
@@ -910,10 +968,21 @@ class Chat:
             return [one if encoding is None else G711.encode(one, encoding)]
         return [np.concatenate(stripped)] if split_text else stripped
 
+    def _normalize_request(self, wavs, target: float, rate: int) -> List[np.ndarray]:
+        """the sentences of a split request that is concatenated on the host: ONE loudness and ONE gain over all of them, on the
+        device (the waveforms go there and back as one pack; every sentence is filtered alone)"""
+        if len(wavs) == 0:
+            return []
+        off = np.zeros(len(wavs) + 1, np.int64)
+        np.cumsum([len(w) for w in wavs], out=off[1:])
+        pack = torch.from_numpy(np.concatenate([np.asarray(w, dtype=np.float32) for w in wavs])).to(self.device)
+        out = self.codec.loudness_normalize(pack, target, offsets=off, groups=np.array([0, len(wavs)], np.int32), rates=rate, out=pack)
+        return ragged_views(self.codec.to_host(out), off)
+
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-               speed: Optional[float] = None, flac: bool = False):
+               speed: Optional[float] = None, flac: bool = False, loudness=None):
         """core.py:395-503 (generator).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -937,7 +1006,8 @@ class Chat:
         rs = [] if ts is not None and sample_rate is not None else None      # ... at another rate: and their streams of the resampler
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
-                                           encoding, speed, ts, rs, **({"flac": True} if flac else {}))
+                                           encoding, speed, ts, rs, **({"flac": True} if flac else {}),
+                                           **({} if loudness is None else {"loudness": loudness}))
         finally:
             for h in ts or ():                                 # also when the consumer drops the generator half way
                 self.codec.time_scale_stream_close(h)
@@ -945,7 +1015,7 @@ class Chat:
                 self.codec.resample_stream_close(h)
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None, flac: bool = False):
+                       rs=None, flac: bool = False, loudness=None):
         """the batch loop of `_infer`"""
         def open_streams(rows):
             ts.extend(self.codec.time_scale_stream_open(speed) for _ in rows)
@@ -969,6 +1039,8 @@ class Chat:
                         rkw["speed"] = speed
                     if flac and pcm16:
                         rkw["flac"] = True
+                    if loudness is not None and not raw:
+                        rkw["loudness"] = loudness
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
                         rows = [h.clone() for h in src]
                         result.destroy()

@@ -1970,6 +1970,61 @@ extern "C" int ctts_time_scale_ragged(const float* x, const int64_t* off_in_dev,
                               n_out_max, window, num, den, (hipStream_t)stream));
   return 0;
 }
+// the sample offsets of a loudness call: 0 when they pass
+static int loudness_offsets_check(const char* who, const int64_t* off_host, int32_t n_seg) {
+  if (!off_host) return fail("%s: the host offsets are null", who);
+  if (n_seg < 1 || n_seg > 65535) return fail("%s: need 1 <= n_seg <= 65535 (got %d)", who, n_seg);
+  if (off_host[0] != 0) return fail("%s: the first sample offset must be 0", who);
+  for (int i = 0; i < n_seg; ++i)
+    if (off_host[i + 1] <= off_host[i]) return fail("%s: segment %d is empty or the offsets do not ascend", who, i);
+  if (off_host[n_seg] >= (1ll << 31) - 4096) return fail("%s: the pack holds 2^31 - 4096 samples or more", who);
+  return 0;
+}
+extern "C" size_t ctts_loudness_normalize_ragged_scratch_bytes(const int64_t* off_host, int32_t n_seg) {
+  if (loudness_offsets_check("ctts_loudness_normalize_ragged_scratch_bytes", off_host, n_seg)) return 0;
+  return (size_t)loudness_records(off_host[n_seg], n_seg) * LN_REC * sizeof(double) + (size_t)(n_seg + 3) / 4 * 16;
+}
+extern "C" int ctts_loudness_normalize_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                              const int32_t* rate_dev, const int32_t* rate_host, const double* coef_dev, const double* coef_host,
+                                              int32_t n_rates, const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp,
+                                              const double* target_dev, const double* target_host, void* stats, void* scratch,
+                                              size_t scratch_bytes, void* stream) {
+  const char* who = "ctts_loudness_normalize_ragged";
+  if (!x || !y || !off_dev || !rate_dev || !rate_host || !coef_dev || !coef_host || !grp_dev || !grp_host || !target_dev || !target_host || !stats)
+    return fail("%s: a null pointer (x, y, the stats and the offset, rate, coefficient, group and target tables on the device and the host are needed)", who);
+  if (loudness_offsets_check(who, off_host, n_seg)) return -1;
+  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)stats & 7)) return fail("%s: x and y must be 16-byte aligned, the stats 8-byte aligned", who);
+  if (x != y && x < y + off_host[n_seg] && y < x + off_host[n_seg]) return fail("%s: y must be x itself or not overlap it", who);
+  if (n_rates < 1) return fail("%s: the coefficient table is empty", who);
+  for (int r = 0; r < n_rates; ++r) {
+    const double H = coef_host[(size_t)r * LN_ROW], c = coef_host[(size_t)r * LN_ROW + 1];
+    if (!(H >= LN_HMIN && H <= LN_HMAX) || H != (double)(int)H)
+      return fail("%s: rate row %d: a sub-block of %g samples (the rate is a multiple of 10 Hz in %d .. %d)", who, r, H, 10 * LN_HMIN, 10 * LN_HMAX);
+    if (c != (double)((((int)H + 63) / 64) | 1)) return fail("%s: rate row %d: the chunk is ceil(H / 64) | 1 samples (got %g for H = %g)", who, r, c, H);
+  }
+  long long n_max = 0, tiles_max = 0, h_max = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    if (rate_host[i] < 0 || rate_host[i] >= n_rates) return fail("%s: segment %d: rate row %d is outside the table of %d", who, i, rate_host[i], n_rates);
+    const long long n = off_host[i + 1] - off_host[i], H = (long long)coef_host[(size_t)rate_host[i] * LN_ROW];
+    n_max = std::max(n_max, n);
+    tiles_max = std::max(tiles_max, (n + H - 1) / H);
+    h_max = std::max(h_max, H);
+  }
+  if (n_grp < 1 || n_grp > n_seg) return fail("%s: need 1 <= n_grp <= n_seg (got %d groups, %d segments)", who, n_grp, n_seg);
+  if (grp_host[0] != 0 || grp_host[n_grp] != n_seg) return fail("%s: the group table must run from 0 to n_seg", who);
+  for (int g = 0; g < n_grp; ++g) {
+    if (grp_host[g + 1] <= grp_host[g]) return fail("%s: group %d is empty or the group table does not ascend", who, g);
+    const double t = target_host[g];
+    if (t == t && !(t >= -40.0 && t <= -5.0)) return fail("%s: group %d: the target is -40 .. -5 LUFS, or NaN for none (got %g)", who, g, t);
+  }
+  const size_t rec_bytes = (size_t)loudness_records(off_host[n_seg], n_seg) * LN_REC * sizeof(double);
+  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < rec_bytes + (size_t)(n_seg + 3) / 4 * 16)
+    return fail("%s: scratch missing, not 16-byte aligned or too small (%zu bytes, need %zu)", who, scratch_bytes, rec_bytes + (size_t)(n_seg + 3) / 4 * 16);
+  CttsDeviceGuard dg(stream);
+  CK(launch_loudness_normalize_ragged(x, y, (const long long*)off_dev, n_seg, n_max, tiles_max, (int)h_max, rate_dev, coef_dev, grp_dev, n_grp, target_dev,
+                                      stats, (double*)scratch, (float*)((char*)scratch + rec_bytes), (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_copy_bytes(void* dst,const void* src, size_t bytes, void* stream) {
   if (!dst || !src || (bytes & 15) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return fail("ctts_copy_bytes: pointers and size must be 16-byte aligned");
   CttsDeviceGuard dg(stream);

@@ -528,6 +528,21 @@ hipError_t launch_time_scale_ragged(const float* x, const long long* off_in, flo
                                     const long long* path_off, int n_seg, long long n_out_max, const float* window, int num, int den,
                                     hipStream_t st);
 
+// ---- loudness normalisation, BS.1770-4 (loudness.hip) ---------------------------------------------
+#define LN_HMIN 800           // a tile is H = fs / 10 samples: 8 kHz ..
+#define LN_HMAX 4800          // .. 48 kHz
+#define LN_WAVES 4            // tiles (waves) per workgroup of the tile pass: 4 * h_max floats of LDS (2 where that passes 64 KB)
+#define LN_REC 20             // float64 per tile record: z[4], e, v[4], M[10], peak
+#define LN_ROW 1072           // float64 per rate of the coefficient table (loudness.rate_row)
+// tile records a pack of `total` samples in n_seg segments needs: segment s's tiles start at record off[s] / LN_HMIN + s
+static inline long long loudness_records(long long total, int n_seg) { return total / LN_HMIN + n_seg + 1; }
+// packed segments x[off[s], off[s+1]) at rate row rate[s] of coef; segments grp[g] .. grp[g+1]-1 are group g with target[g] LUFS (NaN:
+// measured, gain 1): y = g32 * x (y may be x), stats[g] the group's 32-byte record.  n_max: the longest segment, tiles_max: the most
+// tiles ceil(n_s / H_s) of a segment (grid sizes), h_max: the largest H of a segment (the tile pass's LDS); rec: loudness_records(..) * LN_REC float64, seg_gain: [n_seg] float32 of device scratch.
+hipError_t launch_loudness_normalize_ragged(const float* x, float* y, const long long* off, int n_seg, long long n_max, long long tiles_max,
+                                            int h_max, const int32_t* rate, const double* coef, const int32_t* grp, int n_grp, const double* target,
+                                            void* stats, double* rec, float* seg_gain, hipStream_t st);
+
 #define TS_CARRY 2560         // floats of one carry buffer of a stream slot; a slot has two (a step reads one and writes the other)
 #define TS_STATE_INTS 4       // int32 per slot of the state table: s_K, three reserved
 // ctts_ts_stream (include/chattts_amd.h), field for field (capi.hip asserts the layout): one push of one stream.  x[in_off, in_off + n_in)

@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from . import flac as FLAC
 from . import g711 as G711
+from . import loudness as LN
 from . import resample as RS
 from . import timescale as TS
 from ._sync import wait_event, wait_stream
@@ -1820,8 +1821,80 @@ class CodecEngine:
                 self._time_scale_launch(xi, np.ascontiguousarray(off[a: b + 1] - off[a]), yi, path, p[2], p[3], v[0], v[1])
         return y, off_out
 
+    # -- loudness normalisation (csrc/loudness.hip) -----------------------------------------------------------------------------------
+    def _loudness_coef(self, rates):
+        """the coefficient table of a call's distinct rates on the device, built once per set of rates -> (device, host, {rate: row})"""
+        cache = self.__dict__.setdefault("_ln_coef", {})
+        key = tuple(sorted(set(rates)))
+        if key not in cache:
+            host, index = LN.coef_table(key)
+            cache[key] = (torch.from_numpy(host).to(self.device), host, index)
+        return cache[key]
+
+    def loudness_normalize(self, wav: torch.Tensor, target, offsets=None, groups=None, rates=None, return_stats: bool = False, out=None):
+        """ITU-R BS.1770-4 integrated loudness of a float32 device tensor and ONE gain per group that brings it to `target` LUFS
+        (ctts_loudness_normalize_ragged; the definition, the +30 dB cap and the -1 dBFS ceiling of loudness.py): 1-D (one signal),
+        [B, n] (rows, each alone), or 1-D packed with `offsets` (n_seg + 1 sample offsets, the ragged decoder's layout; every segment
+        filtered as if alone).  `groups`: the table `float_to_int16_groups` takes -- segments groups[g] .. groups[g+1]-1 share one
+        loudness, one peak and one gain; without it every segment is its own group.  `target`: one number of LUFS in -40 .. -5 or one
+        per group; None leaves that group alone (bit for bit), and with every target None and no `return_stats` the input comes back
+        untouched, with no launch.  `rates`: the segments' sample rates in Hz (one, or one per segment; default 24000), multiples of 10
+        in 8000 .. 48000.  Returns a tensor of the input's shape (`out`, when given: a float32 device tensor of that shape, possibly
+        `wav` itself), and with `return_stats` also the groups' records (a NumPy array of loudness.STATS: L, peak, g32, the block
+        counts, the term that bound).  A group's record and samples do not depend on what it is packed with.  ValueError before any
+        launch: a rate or target out of range, an empty segment, non-ascending offsets, a bad group table, 2^31 - 4096 samples."""
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
+            raise ValueError("loudness_normalize: a float32 device tensor, 1-D or [B, n]")
+        if offsets is not None and wav.dim() != 1:
+            raise ValueError("loudness_normalize: offsets go with a packed 1-D tensor")
+        if wav.numel() == 0:
+            raise ValueError("loudness_normalize: nothing to normalise")
+        if wav.dim() == 2:
+            offsets = np.arange(wav.shape[0] + 1, dtype=np.int64) * int(wav.shape[1])
+        off, grp, rates, tg = LN.tables(wav.numel(), offsets, groups, rates, target)
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == wav.shape
+                                    and out.is_contiguous()):
+            raise ValueError("loudness_normalize: out is a contiguous float32 device tensor of the input's shape")
+        if all(t is None for t in tg) and not return_stats:
+            if out is None or out is wav:
+                return wav
+            out.copy_(wav)
+            return out
+        x = wav.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()
+        y = out if out is not None and out.data_ptr() % 16 == 0 else torch.empty_like(x)
+        n_seg, n_grp = len(off) - 1, len(grp) - 1
+        coef_d, coef_h, index = self._loudness_coef(rates)
+        ridx = np.array([index[r] for r in rates], dtype=np.int32)
+        tgt = np.array([math.nan if t is None else t for t in tg], dtype=np.float64)
+        off_p = off.ctypes.data_as(C.c_void_p)
+        sb = int(self.lib.ctts_loudness_normalize_ragged_scratch_bytes(off_p, n_seg))
+        if sb == 0:
+            _lib.check(-1, "ctts_loudness_normalize_ragged")      # the offsets were refused: the library's message says why
+        dev = wav.device
+        tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), tgt.view(np.uint8), ridx.view(np.uint8), grp.view(np.uint8)])).to(dev)   # one upload
+        work = torch.empty((LN.STATS.itemsize * n_grp + sb,), dtype=torch.uint8, device=dev)             # the records, then the scratch
+        st = torch.cuda.current_stream(dev)
+        base = tabs.data_ptr()
+        _lib.check(self.lib.ctts_loudness_normalize_ragged(
+            x.data_ptr(), y.data_ptr(), base, off_p, n_seg, base + off.nbytes + tgt.nbytes, ridx.ctypes.data_as(C.c_void_p),
+            coef_d.data_ptr(), coef_h.ctypes.data_as(C.c_void_p), int(coef_h.shape[0]),
+            base + off.nbytes + tgt.nbytes + ridx.nbytes, grp.ctypes.data_as(C.c_void_p), n_grp, base + off.nbytes,
+            tgt.ctypes.data_as(C.c_void_p), work.data_ptr(), work.data_ptr() + LN.STATS.itemsize * n_grp, sb, st.cuda_stream),
+            "ctts_loudness_normalize_ragged")
+        tabs.record_stream(st)
+        work.record_stream(st)
+        if out is not None and y is not out:
+            out.copy_(y)
+            y = out
+        y = y.view(wav.shape)
+        if return_stats:
+            return y, work[: LN.STATS.itemsize * n_grp].cpu().numpy().view(LN.STATS)
+        return y
+
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
-    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None):
+    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None, loudness=None):
         """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
         packed frames (ctts_dvae_decode_ragged / ctts_vocos_decode_ragged): each utterance gets zero padding at its own edges in every
         convolution, so its audio does not depend on what else is in the call -- unlike `decode_to_wavs`, whose zero-padded [B, Tmax]
@@ -1836,9 +1909,23 @@ class CodecEngine:
         different rates share the decode).  The waveform is resampled on the device directly behind the ISTFT (`resample_segments`),
         every row as if alone; `off` then holds the resampled rows' offsets.
         `speed` (None: 1.0): pitch-preserving time scaling -- one value, or one per row (`time_scale_segments`: rows at speed 1 are
-        copied through).  It runs at 24 kHz, behind the ISTFT and in front of the resampler, every row as if alone."""
+        copied through).  It runs at 24 kHz, behind the ISTFT and in front of the resampler, every row as if alone.
+        `loudness` (None: untouched): a target in LUFS -- one value, or one per row, None entries left alone.  The rows are
+        normalised in place (`loudness_normalize`), each as a group of its own at its own rate: the last float32 stage, behind the
+        time scaler and the resampler."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
+        targets = LN.per_row(loudness, len(rows), "decode_ragged")
+        if targets is not None:
+            rates = [self.SAMPLE_RATE] * len(rows) if sample_rate is None else \
+                [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
+            if len(rates) != len(rows):
+                raise ValueError("decode_ragged: one sample rate per row, or one for all")
+            for r in rates:
+                LN.check_rate(r)                                  # every refusal, before the decode
+            out = self.decode_ragged(rows, return_mel, sample_rate, speed)
+            self.loudness_normalize(out[0], targets, offsets=out[1], rates=rates, out=out[0])
+            return out
         if speed is not None:
             speeds = [float(speed)] * len(rows) if np.ndim(speed) == 0 else [float(v) for v in speed]
             if len(speeds) != len(rows):
@@ -2604,15 +2691,22 @@ class CodecEngine:
         return out
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None, sample_rate: Optional[int] = None,
-                       speed: Optional[float] = None) -> torch.Tensor:
+                       speed: Optional[float] = None, loudness=None) -> torch.Tensor:
         """`Chat._decode_to_wavs` (core.py:513-539): zero-pad the per-row [T_b,768] hidden lists to the
         longest row, DVAE decode, Vocos decode -> [B, 256(2Tmax-1)] float32 on the device.  `pad_to`: pad to that many tokens instead
         (>= the longest row): a data-parallel shard decodes its rows as part of the GLOBAL batch (dist.infer_sharded) -- the reference
         decodes a shorter row's tail from zero hidden states and returns it.  `sample_rate` (None: 24000): the rows are resampled to
         that rate on the device, directly behind the ISTFT (`resample`) -> [B, ceil(n * new / 24000)].  `speed` (None: 1.0): the rows
-        are time-scaled at 24 kHz (`time_scale`), each alone, behind the ISTFT and in front of the resampler."""
+        are time-scaled at 24 kHz (`time_scale`), each alone, behind the ISTFT and in front of the resampler.  `loudness` (None:
+        untouched): a target in LUFS, one value or one per row (None entries left alone) -- every row, padding and all, is normalised
+        alone (`loudness_normalize`) at the returned rate, the last float32 stage."""
         if len(result_list) == 0:
             return torch.empty((0,), dtype=torch.float32)
+        targets = LN.per_row(loudness, len(result_list), "decode_to_wavs")
+        if targets is not None:
+            rate = LN.check_rate(self.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+            wav = self.decode_to_wavs(result_list, pad_to, sample_rate, speed).contiguous()
+            return self.loudness_normalize(wav, targets, rates=rate, out=wav)
         if speed is not None and TS.quantize(speed)[0] != TS.DEN:
             wav = self.time_scale(self.decode_to_wavs(result_list, pad_to), speed)
             return wav if sample_rate is None else self.resample(wav, self.SAMPLE_RATE, int(sample_rate))

@@ -96,7 +96,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
-               stream_speed_rates: bool = False, flac: bool = False):
+               stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -144,7 +144,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     request's 16-bit samples as a FLAC file (audio/flac; lossless: the samples of the "wav" response, bit for bit), encoded on the device
     behind the 16-bit conversion (Chat.infer(flac=True) / SpeechBatcher.submit(flac=True)), at whatever rate and speed `sample_rates` /
     `speed` allow.  `"stream": true` with it gets a 400 (a streamed FLAC needs a variable-block-size stream and carried sample numbers),
-    an `"encoding"` key with it too."""
+    an `"encoding"` key with it too.  `loudness=True` (default off: every response, status and warning is as without it, a `"loudness"`
+    key is ignored with the "unsupported parameters" warning): a non-streamed request body may carry `"loudness"`, a target in LUFS
+    (-40 .. -5) -- the utterance is brought to that ITU-R BS.1770-4 integrated loudness on the device, under a +30 dB cap and a -1 dBFS
+    ceiling, in front of the 16-bit conversion (Chat.infer(loudness=) / SpeechBatcher.submit(loudness=)), in whatever format, rate and
+    speed the other options allow; a value that is no number or out of range gets a 400, `"stream": true` with it too (an integrated
+    loudness needs the whole utterance), and /health carries `"loudness": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -209,6 +214,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     if flac:
         from . import flac as FLAC
         formats = formats | {"flac"}
+    if loudness:
+        from . import loudness as LN
+        allowed = allowed | {"loudness"}
 
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
         model: str = "tts-1"
@@ -233,8 +241,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     stream_speed=12000, pass_first_n_batches=2)
 
     def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None,
-              as_flac: bool = False):                # openai_api.py:168-183,207-222
+              as_flac: bool = False, lufs: Optional[float] = None):                # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if lufs is not None:
+            kw = {**kw, "loudness": lufs}
         if as_flac:
             kw = {**kw, "flac": True}
         if spd is not None:
@@ -292,6 +302,16 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 raise HTTPException(400, detail=f"a streamed speed is served at {SAMPLE_RATE} Hz only: speed {req.speed} with sample_rate {rate} "
                                                 f"would need the scaled stream's history and a look-ahead carried into the resampler")
             spd = int(round(100.0 * req.speed)) / 100
+        lufs = None                                  # the request's loudness target where it is honoured
+        if loudness and request_data.get("loudness") is not None:
+            try:
+                lufs = LN.check_target(request_data["loudness"])
+                LN.check_rate(rate)
+            except ValueError as e:
+                raise HTTPException(400, detail=str(e))
+            if req.stream:
+                raise HTTPException(400, detail=f"loudness {lufs} is served for non-streamed requests only: an integrated loudness needs "
+                                                f"the whole utterance (a stream would need a running measure)")
         refine = refine_of(request_data)
         rkw = {} if refine is None else {"refine": refine}
         if refine is not None and req.stream and not pool_streams:
@@ -383,13 +403,17 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     rkw = {**rkw, "sample_rate": rate}
                 if spd is not None:
                     rkw = {**rkw, "speed": spd}
+                if lufs is not None:
+                    rkw = {**rkw, "loudness": lufs}
                 wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw, **ekw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:
             async with app.state.model_lock:
                 try:
-                    if as_flac:
+                    if lufs is not None:
+                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs)
+                    elif as_flac:
                         wavs = await run_in_threadpool(infer, req, rate, None, spd, True)
                     else:
                         wavs = await run_in_threadpool(infer, req, rate, *(() if law is None and spd is None else (law,)),
@@ -437,6 +461,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         out = {"status": "healthy" if loaded else "loading", "model_loaded": loaded, "formats": sorted(formats)}
         if batcher is not None:
             out["pool"] = batcher.occupancy()
+        if loudness:
+            out["loudness"] = True
         return out
 
     return app

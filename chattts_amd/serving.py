@@ -41,6 +41,7 @@ import torch
 from . import _lib
 from . import flac as FLAC
 from . import g711 as G711
+from . import loudness as LN
 from . import resample as RS
 from . import timescale as TS
 from ._sync import wait_event, wait_stream
@@ -661,6 +662,7 @@ class _Job:
     ts_slot: Optional[int] = None          # a stream at another speed: its stream of the time scaler, opened at its first chunk
     rs_slot: Optional[int] = None          # ... and at another rate: its stream of the resampler, opened with it
     flac: bool = False                     # the result is the FLAC file of the int16 waveform (non-streamed only)
+    loudness: Optional[float] = None       # a target in LUFS (non-streamed only); None: the level is left alone
 
     @property
     def is_stream(self) -> bool:
@@ -710,6 +712,8 @@ def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding"
         kw[speed_kw] = [1.0 if j.speed is None else j.speed for j in jobs]
     if any(j.flac for j in jobs):
         kw["flac"] = [j.flac for j in jobs]
+    if any(j.loudness is not None for j in jobs):
+        kw["loudness"] = [j.loudness for j in jobs]
     return kw
 
 
@@ -830,7 +834,7 @@ class SpeechBatcher:
 
     # -- public -------------------------------------------------------------------------------------------------------------
     def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None,
-               encoding=None, speed=None, flac: bool = False) -> Future:
+               encoding=None, speed=None, flac: bool = False, loudness=None) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
@@ -846,7 +850,14 @@ class SpeechBatcher:
         different speeds still share the one ragged decode (CodecEngine.time_scale_segments: rows at speed 1 are copied through).
         `flac=True`: the serial call's `flac=` -- the Future resolves to a uint8 array, the complete FLAC file of that int16 waveform
         at its rate; not together with `encoding`.  Requests that finish together, with and without it, still share the one decode;
-        the encoder runs on the device behind the grouped conversion (CodecEngine.flac_encode), in `finish` by the host twin."""
+        the encoder runs on the device behind the grouped conversion (CodecEngine.flac_encode), in `finish` by the host twin.
+        `loudness` (None: untouched; a target in LUFS, -40 .. -5): the serial call's `loudness=` -- the waveform is brought to that
+        BS.1770 integrated loudness on the device, in front of the strip and the conversion; requests that finish together with
+        different targets, or none, still share the one ragged decode and ONE normalisation call (a split request is one group of
+        it: one gain over its sentences)."""
+        loudness = LN.check_target(loudness)
+        if loudness is not None:
+            LN.check_rate(24000 if sample_rate is None else sample_rate)
         G711.check_encoding(encoding)
         if flac:
             if encoding is not None:
@@ -859,7 +870,7 @@ class SpeechBatcher:
         fut: Future = Future()
         fut.rid = next(self._ids)
         self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding,
-                          speed=speed, flac=bool(flac)))
+                          speed=speed, flac=bool(flac), loudness=loudness))
         return fut
 
     def cancel(self, fut: Future) -> None:
@@ -868,7 +879,7 @@ class SpeechBatcher:
         self._in.put(_Cancel(fut.rid))
 
     def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None,
-                      speed=None, flac: bool = False) -> SpeechStream:
+                      speed=None, flac: bool = False, loudness=None) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
@@ -881,7 +892,11 @@ class SpeechBatcher:
         batcher was built with `stream_speeds=True`: then the chunks are those of the serial call with `speed=, stream_time_scale=True`
         (the path and a tail of samples are carried on the device, per stream), at 24000 Hz only -- unless it was also built with
         `stream_speed_rates=True`: then `speed` goes with `sample_rate`, the serial call's `stream_scaled_resample=True`.  `flac` is
-        refused: a streamed FLAC needs a variable-block-size stream and carried sample numbers."""
+        refused: a streamed FLAC needs a variable-block-size stream and carried sample numbers.  `loudness` is refused: an integrated
+        loudness needs the whole utterance."""
+        if LN.check_target(loudness) is not None:
+            raise ValueError("loudness applies to non-streamed requests only (an integrated loudness needs the whole utterance; a stream "
+                             "would need a running measure)")
         if flac:
             raise ValueError("flac is served for non-streamed requests only (a streamed FLAC needs a variable-block-size stream and "
                              "carried sample numbers)")
@@ -1221,23 +1236,24 @@ class SpeechBatcher:
         self._drain(block=False)
         self.lock.acquire()
 
-    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None, flac: bool = False) -> np.ndarray:
+    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None, flac: bool = False, loudness=None) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
             raise RuntimeError(_NO_AUDIO)
         self._count_decode(1)
         wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}),
-                                       **({} if speed is None else {"speed": float(speed)}))[0]
+                                       **({} if speed is None else {"speed": float(speed)}),
+                                       **({} if loudness is None else {"loudness": float(loudness)}))[0]
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
         if flac:                                                            # converted on the host, encoded by the host twin
             return np.frombuffer(FLAC.encode(pcm, 24000 if sample_rate is None else int(sample_rate)), np.uint8)
         return pcm if encoding is None else G711.encode(pcm, encoding)      # converted on the host, companded by the host twin
 
-    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None, flac=None) -> list:
+    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None, flac=None, loudness=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
         returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000);
-        `speeds`: one speed per request (None: 1.0)"""
+        `speeds`: one speed per request (None: 1.0); `loudness`: one target per request (None entries: left alone)"""
         out: list = [RuntimeError(_NO_AUDIO) if h.shape[0] == 0 else None for h in hids]
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
@@ -1249,6 +1265,8 @@ class SpeechBatcher:
                 kw["speed"] = [float(speeds[i]) for i in live]
             if flac is not None and any(flac[i] for i in live):
                 kw["flac"] = [bool(flac[i]) for i in live]
+            if loudness is not None and any(loudness[i] is not None for i in live):
+                kw["loudness"] = [loudness[i] for i in live]
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out

@@ -409,6 +409,33 @@ int ctts_time_scale_ragged(const float* x, const int64_t* off_in_dev, const int6
                            const int64_t* off_out_host, int32_t* path, const int64_t* path_off_dev, const int64_t* path_off_host, int32_t n_seg,
                            const float* window, int32_t num, int32_t den, void* stream);
 
+/* Loudness normalisation: ITU-R BS.1770-4 integrated loudness of packed float32 segments x[off[s], off[s+1]), every segment K-weighted as
+ * if alone (two biquads, zero initial state), and y = g32 * x with ONE float32 gain per group of segments; y may be x (otherwise the two
+ * do not overlap), both 16-byte aligned.  Segment s is at rate row rate[s] of the coefficient table coef: n_rates rows of 1072 float64
+ * that the host computes per rate fs (a multiple of 10 Hz, 8000 .. 48000) -- [0] H = fs / 10, the 100 ms sub-block and the tile;
+ * [1] c = ceil(H / 64) | 1, a lane's chunk (odd); [2, 12) b0 b1 b2 a1 a2 of the shelf, then of the high-pass; [16, 32) A^H, row-major, A the 4 x 4
+ * state matrix of the cascade in transposed direct form II; [32, 42) the upper triangle of M = sum_{i<H} h_i h_i^T, h_i = C A^i;
+ * [48, 1072) A^(l c), l = 0 .. 63.  Sub-block energies e_j (complete sub-blocks only), gating blocks z_i = (e_i + .. + e_{i+3}) / (4 H),
+ * l_i = -0.691 + 10 log10 z_i; a segment with fewer than 4 complete sub-blocks is ONE block, its mean square.  Group g is segments
+ * grp[g] .. grp[g+1]-1 (the table of the grouped 16-bit conversion): its blocks pass the absolute gate (l_i > -70) and the relative gate
+ * (10 LU under the mean of those), L is -0.691 + 10 log10 of the mean of what passed both, its peak is max |x|, and
+ * g = min(10^((target[g] - L) / 20), 10^(30 / 20), 10^(-1 / 20) / peak) in float64, rounded once to float32.  No block past the
+ * absolute gate: L = -inf and g = 1.  A NaN target: the group is measured, g = 1.  stats: [n_grp] records of 32 bytes on the device --
+ * float64 L; float32 peak, g32; int32 blocks, blocks past the absolute gate, blocks past both, the term that bound (0 target, 1 the
+ * +30 dB cap, 2 the -1 dBFS ceiling, -1 none).  All float64; the sums run in a fixed order, so a group's record and samples do not depend
+ * on what it is packed with.  Every table is given on the device and the host (the two must agree).  Refused before anything is
+ * launched: a null pointer, offsets that do not ascend from 0, an empty segment, a pack of 2^31 - 4096 samples or more, more than 65535
+ * segments, a rate row outside the table or a row whose H or c is out of range, a group table that does not run 0 .. n_seg ascending,
+ * a target outside -40 .. -5, misaligned buffers, scratch under the companion function's size (0: the offsets were refused).
+ * Stream-ordered, three launches: the tiles from zero state (one wave each), one workgroup per group (the state chain, the energies'
+ * closed-form correction, the gates, the gain), the scale pass. */
+size_t ctts_loudness_normalize_ragged_scratch_bytes(const int64_t* off_host, int32_t n_seg);
+int ctts_loudness_normalize_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                   const int32_t* rate_dev, const int32_t* rate_host, const double* coef_dev, const double* coef_host,
+                                   int32_t n_rates, const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp,
+                                   const double* target_dev, const double* target_host, void* stats, void* scratch, size_t scratch_bytes,
+                                   void* stream);
+
 /* Time scaling of streams: the signal of a stream arrives in pushes, its output leaves in chunks, and the concatenation of the chunks (and
  * of the path entries) is ctts_time_scale_ragged's result on the whole signal, bit for bit, however the signal is cut into pushes.
  * With n_avail samples in and more to come, frame k >= 1 may run once need(k) = max(a_{k-1} + D + N - 1, a_k - HS + D + N - 1) <= n_avail;
