@@ -584,20 +584,24 @@ class Chat:
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts)]
 
     def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None,
-                             rs_streams=None) -> List[np.ndarray]:
+                             rs_streams=None, flac=None, flac_streams=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
         (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream).  `encodings`: one per window, None / "ulaw" / "alaw" -- a
         companded window's piece is uint8, `g711.encode` of the int16 piece.  `speeds` with `ts_streams` (one entry per window; a
         speed other than 1 with the handle of its stream of the time scaler): the window's samples are pushed into that stream and
         the piece is what the step emits, converted (CodecEngine.decode_windows(speeds=)); `rs_streams` (with `speeds` and
-        `sample_rates`): the handle of the resampler's stream of a window at another speed AND rate, None otherwise; without them
-        today's call, argument for argument"""
+        `sample_rates`): the handle of the resampler's stream of a window at another speed AND rate, None otherwise.  `flac` with
+        `flac_streams` (one flag and one entry per window; a flagged window with the handle of its FLAC stream): the window's int16
+        samples are pushed into that stream and the piece is uint8, the frames the push completes
+        (CodecEngine.decode_windows(flac=)); without them today's call, argument for argument"""
         kw = {k: v for k, v in (("sample_rates", sample_rates), ("encodings", encodings), ("speeds", speeds)) if v is not None}
         if speeds is not None:
             kw["ts_streams"] = ts_streams
             if rs_streams is not None:
                 kw["rs_streams"] = rs_streams
+        if flac is not None:
+            kw["flac"], kw["flac_streams"] = flac, flac_streams
         return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, **kw)
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
@@ -630,14 +634,15 @@ class Chat:
             yield np.zeros((0,), np.float32) if p is None else p.result()
 
     def _stream_piece(self, hiddens, a: int, b: Optional[int], use_decoder: bool = True, pcm16: bool = False,
-                      rate: Optional[int] = None, encoding=None) -> np.ndarray:
+                      rate: Optional[int] = None, encoding=None, on_device: bool = False) -> np.ndarray:
         """samples [a, b) (b=None: to the end) of the decode of the current prefix (core.py:482-497), from a token window with
         halos instead of the whole prefix (`CodecEngine.decode_window`); `incremental_stream=False` restores the reference's
         full re-decode per yield.  `rate` (None: 24 kHz): [a, b) stay 24 kHz samples and the piece is outputs
         [ceil(a L / M), ceil(b L / M)) of the prefix's decode resampled as one signal -- from the widened window
         (`decode_window(sample_rate=)`), or, `incremental_stream=False`, sliced out of the whole prefix resampled whole.
         `encoding` ("ulaw" / "alaw", with `pcm16`): the int16 piece companded -- on the device where the conversion ran there, by the
-        host twin where it ran on the host."""
+        host twin where it ran on the host.  `on_device` (with `pcm16`, without `encoding`): a piece that was converted on the device
+        stays there, as an int16 tensor (a streamed FLAC pushes it on)."""
         if encoding is not None:
             if not pcm16:
                 raise ValueError("encoding needs pcm16=True")
@@ -668,11 +673,12 @@ class Chat:
             return np.zeros((len(hiddens), 0), np.int16 if pcm16 else np.float32)
         win = self.codec.decode_window(hiddens, a, hi) if rate is None else self.codec.decode_window(hiddens, a, hi, sample_rate=rate)
         if pcm16 and win.shape[1] > 0:     # every row by its own peak -- float_to_int16(chunk[b]), examples/web/funcs.py:203-206 -- on the device
-            return self.codec.to_host(self.codec.float_to_int16(win, per_row=True)[0])
+            pcm = self.codec.float_to_int16(win, per_row=True)[0]
+            return pcm if on_device else self.codec.to_host(pcm)
         return self.codec.to_host(win)
 
     def _stream_piece_scaled(self, hiddens, a: int, b: Optional[int], handles, final: bool, pcm16: bool = False, encoding=None,
-                             rs_handles=None) -> np.ndarray:
+                             rs_handles=None, on_device: bool = False) -> np.ndarray:
         """`_stream_piece` at another speed: samples [a, b) of the decode of the current prefix are PUSHED into the rows' streams of the
         time scaler (`handles`, one per row; CodecEngine.time_scale_stream_step, all rows in one launch) and the piece is what the step
         emits -- [B, 512 k] samples, possibly none; every row has had the same number of samples, so the chunk stays rectangular.
@@ -701,7 +707,7 @@ class Chat:
             return np.zeros((B, 0), np.int16 if encoding is None else np.uint8)
         pcm = codec.float_to_int16(y, per_row=True)[0]
         if encoding is None:
-            return codec.to_host(pcm)
+            return pcm if on_device else codec.to_host(pcm)          # (`on_device`: a streamed FLAC pushes the tensor on)
         codes = codec.g711_encode(pcm.view(-1), [(0, pcm.numel(), encoding)])
         return codec.to_host(codes)[: pcm.numel()].reshape(tuple(pcm.shape))
 
@@ -829,7 +835,7 @@ class Chat:
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
-              flac: bool = False, loudness=None):
+              flac: bool = False, loudness=None, stream_flac: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -874,7 +880,17 @@ class Chat:
         `flac=True` (keyword-only, non-streamed only; needs `pcm16=True`, not together with `encoding`: ValueError otherwise): every
         result is a uint8 array holding the complete FLAC file (chattts_amd/flac.py: mono, 16 bits, at `sample_rate`) of exactly the
         int16 samples the same call returns without it -- lossless, encoded on the device behind the conversion
-        (CodecEngine.flac_encode), so that the compressed bytes are what cross PCIe.  A streamed FLAC would need a variable-block-size
+        (CodecEngine.flac_encode), so that the compressed bytes are what cross PCIe.  A streamed call raises unless
+        `stream_flac=True` (keyword-only): then every row of the batch gets a FLAC stream (variable-block-size frames that carry the
+        number of their first sample; chattts_amd/flac.py, StreamEncoder) and every yield is a list with one uint8 array per row: the
+        frames that chunk completes -- an empty array when it completes none (up to 15 samples wait for the next chunk; the last
+        chunk brings them).  The frames of a row behind `flac.stream_header(sample_rate)` are a FLAC stream that decodes to exactly
+        the int16 chunks the call yields without `flac`, concatenated.  The chunks are pushed on the device
+        (CodecEngine.flac_stream_step; a chunk that was converted on the host, like the last one, is uploaded for its push); with
+        `incremental_stream=False` or without the decoder every chunk is converted on the host and the host twin encodes the
+        stream.  It combines with `sample_rate` / `stream_resample`, `speed` / `stream_time_scale` and `stream_scaled_resample`; not
+        with `split_text` (every split batch would end the stream).  The streams' slots are given back when the generator ends or
+        is dropped.  Without `stream_flac` a streamed FLAC is refused: it needs a variable-block-size
         stream and carried sample numbers: it raises.
         `loudness` (keyword-only, non-streamed only; None: untouched): a target in LUFS, -40 .. -5 -- one number, or one per text.
         Every utterance is brought to that ITU-R BS.1770-4 integrated loudness on the device (CodecEngine.loudness_normalize) by one
@@ -896,9 +912,11 @@ class Chat:
                 raise ValueError("flac applies to 16-bit output: pass pcm16=True")
             if encoding is not None:
                 raise ValueError("flac does not go with an encoding (a FLAC file holds the 16-bit samples)")
-            if stream:
+            if stream and not stream_flac:
                 raise ValueError("flac applies to non-streamed inference only (a streamed FLAC needs a variable-block-size stream and "
                                  "carried sample numbers, which is not implemented)")
+            if stream and split_text:
+                raise ValueError("a streamed FLAC does not go with split_text (every split batch would end the stream)")
             FLAC.rate_code(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         skw = _speed_kw(speed)
         if stream and skw and not stream_time_scale:
@@ -983,7 +1001,7 @@ class Chat:
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                speed: Optional[float] = None, flac: bool = False, loudness=None):
-        """core.py:395-503 (generator).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
+        """core.py:395-503 (generator).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
             text = [text]
@@ -1004,19 +1022,47 @@ class Chat:
         step = max_split_batch if split_text else len(text)
         ts = [] if stream and speed is not None else None      # a streamed speed: the rows' streams of the time scaler, opened at the first chunk
         rs = [] if ts is not None and sample_rate is not None else None      # ... at another rate: and their streams of the resampler
+        fs = [] if stream and flac and pcm16 else None         # a streamed FLAC: the rows' FLAC streams, opened at the first chunk
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
                                            encoding, speed, ts, rs, **({"flac": True} if flac else {}),
-                                           **({} if loudness is None else {"loudness": loudness}))
+                                           **({} if loudness is None else {"loudness": loudness}), **({} if fs is None else {"fs": fs}))
         finally:
+            for h in fs or ():
+                if not isinstance(h, FLAC.StreamEncoder):
+                    self.codec.flac_stream_close(h)
             for h in ts or ():                                 # also when the consumer drops the generator half way
                 self.codec.time_scale_stream_close(h)
             for h in rs or ():
                 self.codec.resample_stream_close(h)
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None, flac: bool = False, loudness=None):
+                       rs=None, flac: bool = False, loudness=None, fs=None):
         """the batch loop of `_infer`"""
+        def flac_chunks(piece, final):
+            """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' FLAC
+            streams `fs` -> one uint8 array per row"""
+            B = int(piece.shape[0])
+            if not fs:             # opened at the first chunk: on the device, or the host twin where every chunk is converted on the host
+                rate = CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate
+                on_device = use_decoder and self.incremental_stream
+                fs.extend(self.codec.flac_stream_open(rate) if on_device else FLAC.StreamEncoder(rate) for _ in range(B))
+            n = int(piece.shape[1])
+            if isinstance(fs[0], FLAC.StreamEncoder):
+                piece = np.asarray(piece).astype(np.int16, copy=False)
+                return [np.frombuffer(e.push(np.ascontiguousarray(r), final), np.uint8) for e, r in zip(fs, piece)]
+            if not isinstance(piece, torch.Tensor):
+                piece = torch.from_numpy(np.ascontiguousarray(piece, dtype=np.int16)).to(self.device)
+            if n == 0:
+                piece = torch.zeros((B, 8), dtype=torch.int16, device=self.device)
+            elif n % 8 and B > 1:  # every row starts on a multiple of 8 samples
+                piece = torch.nn.functional.pad(piece, (0, -n % 8))
+            row = int(piece.shape[1])
+            piece = piece.contiguous()
+            if piece.data_ptr() % 16:          # a view into the conversion's buffer: the encoder reads 16-byte units
+                piece = piece.clone()
+            return self.codec.flac_stream_step(piece.view(-1), [(h, i * row, n, final) for i, h in enumerate(fs)])
+        dkw = {} if fs is None else {"on_device": True}
         def open_streams(rows):
             ts.extend(self.codec.time_scale_stream_open(speed) for _ in rows)
             if rs is not None:
@@ -1067,9 +1113,11 @@ class Chat:
                     if not ts:
                         open_streams(src)
                     piece = self._stream_piece_scaled(src, length, length + params_infer_code.stream_speed, ts, False, pcm16,
-                                                      encoding if pcm16 else None, **rkw_s)
+                                                      encoding if pcm16 else None, **rkw_s, **dkw)
                 else:
-                    piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw)
+                    piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw, **dkw)
+                if fs is not None:
+                    piece = flac_chunks(piece, False)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
                 # that is BELOW `a`: `length` and `pass_batch_count` are not reset between split batches, so the first yields of a
                 # later batch (a short prefix again) are empty and pull `length` back (tests/test_host_flow.py, stream_split_batches)
@@ -1092,4 +1140,6 @@ class Chat:
                     tail = np.stack([float_to_int16(r) for r in tail]) if tail.shape[1] else tail.astype(np.int16)
                     if encoding is not None:      # companded by the host twin, like the conversion in front of it
                         tail = G711.encode(tail, encoding)
+                    if fs is not None:            # the streams' last push: what they held leaves with it
+                        tail = flac_chunks(tail, True)
                 yield tail

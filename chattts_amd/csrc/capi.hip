@@ -2135,6 +2135,98 @@ extern "C" int ctts_flac_encode_ranges(const int16_t* pcm, const int64_t* counts
                         (FlacFrame*)(meta + s[0] + 1 + n_rng), (hipStream_t)stream));
   return 0;
 }
+static_assert(sizeof(ctts_flac_push) == 64 && sizeof(FlacPush) == 64 && offsetof(ctts_flac_push, sample) == offsetof(FlacPush, sample) &&
+              offsetof(ctts_flac_push, stage) == offsetof(FlacPush, stage) && offsetof(ctts_flac_push, frame0) == offsetof(FlacPush, frame0) &&
+              offsetof(ctts_flac_push, rate) == offsetof(FlacPush, rate) && offsetof(ctts_flac_push, slot) == offsetof(FlacPush, slot) &&
+              offsetof(ctts_flac_push, carry) == offsetof(FlacPush, carry) && offsetof(ctts_flac_push, flags) == offsetof(FlacPush, flags) &&
+              offsetof(ctts_flac_push, count_idx) == offsetof(FlacPush, count_idx), "ctts_flac_push layout");
+// the checks of a host push table; sizes: n_frames, out bytes, work bytes, staging elements, the most slots of one push
+static int flac_check_pushes(const char* who, const ctts_flac_push* push_host, int32_t n_push, int32_t n_slots, long long n_pcm,
+                             long long sizes[5], bool* wants_counts, bool* wants_mask) {
+  if (!push_host) return fail("%s: a null pointer (the host push table is needed)", who);
+  if (n_push < 1 || n_push > 1024) return fail("%s: need 1 <= n_push <= 1024 (got %d)", who, n_push);
+  if (n_slots < 1) return fail("%s: the state pool has %d slots", who, n_slots);
+  if (n_pcm < 0) return fail("%s: n_pcm is negative (%lld)", who, n_pcm);
+  long long stage = 0, frames = 0, frames_max = 0, out_bytes = 0;
+  *wants_counts = *wants_mask = false;
+  for (int i = 0; i < n_push; ++i) {
+    const ctts_flac_push& p = push_host[i];
+    if (!flac_rate_ok(p.rate))
+      return fail("%s: push %d: a rate of %d Hz cannot be coded (a rate of the format's table or 1 .. 65535)", who, i, p.rate);
+    if (p.slot < 0 || p.slot >= n_slots) return fail("%s: push %d: slot %d lies outside the pool of %d", who, i, p.slot, n_slots);
+    for (int j = 0; j < i; ++j)
+      if (push_host[j].slot == p.slot) return fail("%s: pushes %d and %d name slot %d: a stream appears twice in one step", who, j, i, p.slot);
+    if (p.start < 0 || (p.start & 7)) return fail("%s: push %d starts at element %lld: starts are multiples of 8", who, i, (long long)p.start);
+    if (p.n < 0) return fail("%s: push %d has a negative length (%lld)", who, i, (long long)p.n);
+    if (p.n >= (1ll << 31)) return fail("%s: push %d lies beyond what a launch can address (n < 2^31)", who, i);
+    if (p.start > n_pcm || p.n > n_pcm - p.start)
+      return fail("%s: push %d ends at element %lld, beyond the %lld of pcm", who, i, (long long)(p.start + p.n), n_pcm);
+    if (p.carry < 0 || p.carry >= FLAC_MIN_BLOCK) return fail("%s: push %d: a stream carries 0 .. 15 samples (got %d)", who, i, p.carry);
+    if (p.flags & ~3) return fail("%s: push %d: unknown flag bits (%d)", who, i, p.flags);
+    if (p.count_idx < -1 || p.count_idx > 65535) return fail("%s: push %d: count_idx %d is neither -1 nor in 0 .. 65535", who, i, p.count_idx);
+    if (!(p.flags & 1) && p.count_idx >= 0)
+      return fail("%s: push %d has a count_idx but is not final (only a stream's last push may leave its length to the device)", who, i);
+    if (!(p.flags & 1) && (p.flags & 2))
+      return fail("%s: push %d has a keep mask but is not final (only a stream's last push may leave its length to the device)", who, i);
+    if (p.sample < 0 || p.sample >= (1ll << 36) || p.sample + p.carry + p.n >= (1ll << 36))
+      return fail("%s: push %d would take the stream's sample number to 2^36 (sample %lld, %lld more)", who, i, (long long)p.sample,
+                  (long long)(p.carry + p.n));
+    if (p.stage != stage) return fail("%s: push %d: stage is %lld, the pushes in front of it own %lld staging elements", who, i, (long long)p.stage, stage);
+    if (p.frame0 != frames) return fail("%s: push %d: frame0 is %lld, the pushes in front of it own %lld frame slots", who, i, (long long)p.frame0, frames);
+    if (p.count_idx >= 0) *wants_counts = true;
+    if (p.flags & 2) *wants_mask = true;
+    const long long cap = p.carry + p.n, fr = (cap + FLAC_BLOCK - 1) / FLAC_BLOCK;
+    stage += (cap + 7) / 8 * 8;
+    frames += fr;
+    frames_max = std::max(frames_max, fr);
+    out_bytes += 2 * cap + 19 * fr;
+  }
+  sizes[0] = frames;
+  sizes[1] = out_bytes;
+  // int64: offsets, total, emitted [n_push] | staged [n_push] | base [n_push]; FlacRange [n_push]; FlacFrame [frames]; the staging buffer
+  sizes[2] = ((frames + 1 + 3ll * n_push) * 8 + n_push * (long long)sizeof(FlacRange) + frames * (long long)sizeof(FlacFrame) + 15) / 16 * 16 + 2 * stage;
+  sizes[3] = stage;
+  sizes[4] = frames_max;
+  return 0;
+}
+extern "C" int ctts_flac_stream_sizes(const ctts_flac_push* push_host, int32_t n_push, int32_t n_slots, int64_t n_pcm, int64_t* sizes) {
+  const char* who = "ctts_flac_stream_sizes";
+  if (!sizes) return fail("%s: a null pointer (sizes[4] is needed)", who);
+  long long s[5];
+  bool wants_counts, wants_mask;
+  if (flac_check_pushes(who, push_host, n_push, n_slots, n_pcm, s, &wants_counts, &wants_mask)) return -1;
+  for (int i = 0; i < 4; ++i) sizes[i] = s[i];
+  return 0;
+}
+extern "C" int ctts_flac_stream_step(const int16_t* pcm, int64_t n_pcm, const uint8_t* mask, const int64_t* counts, const ctts_flac_push* push_dev,
+                                     const ctts_flac_push* push_host, int32_t n_push, int16_t* state, int32_t n_slots, uint8_t* out,
+                                     size_t out_bytes, void* work, size_t work_bytes, void* stream) {
+  const char* who = "ctts_flac_stream_step";
+  if (!pcm || !out || !push_dev || !push_host || !work || !state)
+    return fail("%s: a null pointer (pcm, out, work, state and both push tables are needed)", who);
+  long long s[5];
+  bool wants_counts, wants_mask;
+  if (flac_check_pushes(who, push_host, n_push, n_slots, n_pcm, s, &wants_counts, &wants_mask)) return -1;
+  if (wants_counts && !counts) return fail("%s: a null pointer (a push has a count_idx, so counts is needed)", who);
+  if (wants_mask && !mask) return fail("%s: a null pointer (a push has a keep mask, so mask is needed)", who);
+  if (((uintptr_t)pcm & 15) || ((uintptr_t)out & 15) || ((uintptr_t)work & 15) || ((uintptr_t)counts & 7) || ((uintptr_t)state & 1))
+    return fail("%s: pcm, out and work must be 16-byte aligned, counts 8-byte aligned", who);
+  if ((long long)out_bytes < s[1] || out_bytes >= (1ull << 62))
+    return fail("%s: out holds %zu bytes, the pushes may need %lld (out of capacity)", who, out_bytes, s[1]);
+  if ((long long)work_bytes < s[2] || work_bytes >= (1ull << 62))
+    return fail("%s: work holds %zu bytes, %lld are needed (out of capacity)", who, work_bytes, s[2]);
+  if (s[0] == 0) return 0;                       // no push holds a sample: nothing is emitted and no slot changes
+  CttsDeviceGuard dg(stream);
+  long long* meta = (long long*)work;
+  long long* staged = meta + s[0] + 1 + n_push;
+  long long* base = staged + n_push;
+  FlacRange* rng = (FlacRange*)(base + n_push);
+  FlacFrame* rec = (FlacFrame*)(rng + n_push);
+  int16_t* stage = (int16_t*)((char*)work + s[2] - 2 * s[3]);
+  CK(launch_flac_stream(pcm, mask, (const long long*)counts, (const FlacPush*)push_dev, n_push, state, s[4], s[0], out, meta, staged, base,
+                        rng, rec, stage, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_k_exp_draws(uint64_t seed, int32_t step, int32_t row0, int32_t rows, int32_t V, float* out, void* stream) {
   if (!out || rows <= 0 || V <= 0) return fail("ctts_k_exp_draws: bad arguments");
   CK(launch_exp_draws(seed, step, row0, rows, V, out, (hipStream_t)stream));

@@ -17,13 +17,17 @@
 //      per-thread pieces (CRC with initial value 0 is linear: piece t is advanced by x^(8 * bytes behind it) mod the polynomial), then
 //      16-byte stores to the final position (bytes where a 16-byte unit of the destination is not wholly the frame's).
 // Bytes of `out` outside [0, off[n_frames]) are not written.  Plain vector stores and LDS atomics only.
+// Streams (ctts_flac_stream_step, the end of this file): flac_stage_k in front of the same three kernels, which then take the number of
+// each range's first sample (`base`) and write variable-block-size frames (FF F9) numbered by their first sample, in up to 36 bits.
 #include "common.hpp"
 #include "kernels.hpp"
 
 #define FLAC_MAX_ORDER 4
 #define FLAC_MAX_PART 6
 #define FLAC_RICE 15                     // parameters 0 .. 14
-#define FLAC_WORDS (FLAC_BLOCK / 2 + 8)  // a frame is at most 16 + 2 * 4096 bytes; two words of slack for the unaligned reads of the store loop
+// a frame is at most 19 + 2 * 4096 bytes (a stream's header: up to 16 bytes, never all of them at 4096 samples); the store loop's
+// unaligned reads and the CRC's second word reach one word further: 2053 words at the most
+#define FLAC_WORDS (FLAC_BLOCK / 2 + 8)
 
 typedef uint32_t flac_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long flac_u64;
@@ -45,8 +49,14 @@ __device__ __forceinline__ int flac_rate_code(int rate) {
   return 13;                             // Hz in 16 bits (the host refused every rate that fits neither form)
 }
 
-__device__ __forceinline__ int flac_number_bytes(uint32_t f) {   // the UTF-8-like coding of the frame number
-  return f < 0x80u ? 1 : f < 0x800u ? 2 : f < 0x10000u ? 3 : f < 0x200000u ? 4 : f < 0x4000000u ? 5 : 6;
+// the UTF-8-like coding of a frame's number: the frame's index (fixed block size), or its first sample's number in up to 36 bits (a stream)
+__device__ __forceinline__ int flac_number_bytes(flac_u64 f) {
+  return f < 0x80ull ? 1 : f < 0x800ull ? 2 : f < 0x10000ull ? 3 : f < 0x200000ull ? 4 : f < 0x4000000ull ? 5 : f < 0x80000000ull ? 6 : 7;
+}
+
+// the number frame slot f of range r carries: f itself, or in a stream (base given) the number of its first sample, base[r] + 4096 f
+__device__ __forceinline__ flac_u64 flac_frame_number(const long long* __restrict__ base, int r, long long f) {
+  return base ? (flac_u64)(base[r] + f * (long long)FLAC_BLOCK) : (flac_u64)f;
 }
 
 __device__ __forceinline__ uint32_t flac_zigzag(int r) { return ((uint32_t)r << 1) ^ (uint32_t)(r >> 31); }
@@ -80,7 +90,7 @@ __device__ __forceinline__ void flac_load_block(const int16_t* __restrict__ src,
 
 __global__ __launch_bounds__(256) void flac_analyse_k(const int16_t* __restrict__ pcm, const long long* __restrict__ counts,
                                                       const FlacRange* __restrict__ rng, FlacFrame* __restrict__ rec,
-                                                      long long* __restrict__ n_act) {
+                                                      long long* __restrict__ n_act, const long long* __restrict__ base) {
   __shared__ int s_x[FLAC_BLOCK + 4];
   __shared__ flac_u64 s_sum[FLAC_MAX_ORDER + 1][FLAC_RICE][1 << FLAC_MAX_PART];
   __shared__ flac_u64 s_tot[FLAC_MAX_ORDER + 1][FLAC_MAX_PART + 1];
@@ -185,7 +195,7 @@ __global__ __launch_bounds__(256) void flac_analyse_k(const int16_t* __restrict_
         if (bits < best) { best = bits; kind = 2; bo = o; bp = p; }
       }
     if (!s_differs) { kind = 0; best = 24; bo = 0; bp = 0; }
-    const int hdr = 4 + flac_number_bytes((uint32_t)f) + (n != FLAC_BLOCK ? 2 : 0) + (flac_rate_code(R.rate) == 13 ? 2 : 0) + 1;
+    const int hdr = 4 + flac_number_bytes(flac_frame_number(base, blockIdx.y, f)) + (n != FLAC_BLOCK ? 2 : 0) + (flac_rate_code(R.rate) == 13 ? 2 : 0) + 1;
     fr->kind = kind;
     fr->order = bo;
     fr->part = bp;
@@ -248,7 +258,7 @@ __device__ __forceinline__ uint32_t flac_mulmod16(uint32_t a, uint32_t b) {   //
 
 __global__ __launch_bounds__(256) void flac_pack_k(const int16_t* __restrict__ pcm, const FlacRange* __restrict__ rng,
                                                    const FlacFrame* __restrict__ rec, const long long* __restrict__ off,
-                                                   uint8_t* __restrict__ out) {
+                                                   uint8_t* __restrict__ out, const long long* __restrict__ base) {
   __shared__ int s_x[FLAC_BLOCK + 4];
   __shared__ uint32_t s_w[FLAC_WORDS];
   __shared__ uint32_t s_scan[2][256];
@@ -273,15 +283,15 @@ __global__ __launch_bounds__(256) void flac_pack_k(const int16_t* __restrict__ p
     int m = 0;
     const int rc = flac_rate_code(R.rate);
     h[m++] = 0xFF;
-    h[m++] = 0xF8;
+    h[m++] = base ? 0xF9 : 0xF8;                       // a stream's frames: variable block size, numbered by their first sample
     h[m++] = (uint8_t)(((n == FLAC_BLOCK ? 0xC : 0x7) << 4) | rc);
     h[m++] = 0x08;                                     // mono, 16 bits per sample
-    const uint32_t fn = (uint32_t)f;
+    const flac_u64 fn = flac_frame_number(base, blockIdx.y, f);
     const int nb = flac_number_bytes(fn);
     if (nb == 1) h[m++] = (uint8_t)fn;
     else {
-      h[m++] = (uint8_t)(((0xFF << (8 - nb)) & 0xFF) | (fn >> (6 * (nb - 1))));
-      for (int i = nb - 2; i >= 0; --i) h[m++] = (uint8_t)(0x80 | ((fn >> (6 * i)) & 0x3F));
+      h[m++] = (uint8_t)(((0xFF << (8 - nb)) & 0xFF) | (uint32_t)(fn >> (6 * (nb - 1))));
+      for (int i = nb - 2; i >= 0; --i) h[m++] = (uint8_t)(0x80 | ((uint32_t)(fn >> (6 * i)) & 0x3F));
     }
     if (n != FLAC_BLOCK) { h[m++] = (uint8_t)((n - 1) >> 8); h[m++] = (uint8_t)((n - 1) & 0xFF); }
     if (rc == 13) { h[m++] = (uint8_t)(R.rate >> 8); h[m++] = (uint8_t)(R.rate & 0xFF); }
@@ -379,12 +389,131 @@ hipError_t launch_flac_encode(const int16_t* pcm, const long long* counts, const
                               long long n_frames, uint8_t* out, long long* meta, FlacFrame* rec, hipStream_t st) {
   if (n_rng <= 0 || frames_max <= 0 || n_frames <= 0) return hipSuccess;
   const dim3 grid((unsigned)frames_max, (unsigned)n_rng);
-  hipLaunchKernelGGL(flac_analyse_k, grid, dim3(256), 0, st, pcm, counts, rng, rec, meta + n_frames + 1);
+  hipLaunchKernelGGL(flac_analyse_k, grid, dim3(256), 0, st, pcm, counts, rng, rec, meta + n_frames + 1, (const long long*)nullptr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(flac_scan_k, dim3(1), dim3(1024), 0, st, (const FlacFrame*)rec, n_frames, meta);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(flac_pack_k, grid, dim3(256), 0, st, pcm, rng, (const FlacFrame*)rec, (const long long*)meta, out);
+  hipLaunchKernelGGL(flac_pack_k, grid, dim3(256), 0, st, pcm, rng, (const FlacFrame*)rec, (const long long*)meta, out,
+                     (const long long*)nullptr);
+  return hipGetLastError();
+}
+
+// ---- streams (ctts_flac_stream_step) -----------------------------------------------------------------------------------------------
+// One workgroup per push: [the stream's carried samples | the push's samples, a final push's compacted by its keep mask] go to the
+// push's 16-byte-aligned staging range, so that flac_load_block's aligned path serves the frames cut from it.  The cutting rule of
+// chattts_amd/flac.py (stream_plan): blocks of 4096 from the front, a rest of 16 or more is one more block, a rest of 1 .. 15 waits in
+// the stream's slot (state [slots][16] int16) unless the push is final.  The slot is read into LDS before the barrier and written
+// behind it, by this workgroup alone (the host refuses a slot named twice).  A keep mask is MSB first and starts at byte start / 8.
+// Thread 0 writes what the three encoder kernels read: the push's FlacRange over its staging range (its length the count written
+// here), and the number of its first staged sample.
+__global__ __launch_bounds__(1024) void flac_stage_k(const int16_t* __restrict__ pcm, const uint8_t* __restrict__ mask,
+                                                     const long long* __restrict__ counts, const FlacPush* __restrict__ push,
+                                                     int16_t* __restrict__ state, int16_t* __restrict__ stage, FlacRange* __restrict__ rng,
+                                                     long long* __restrict__ base, long long* __restrict__ staged) {
+  __shared__ int16_t s_c[FLAC_MIN_BLOCK];
+  __shared__ int s_v[2][1024];
+  __shared__ long long s_run;
+  const FlacPush P = push[blockIdx.x];
+  const int t = threadIdx.x;
+  const int c = P.carry;
+  const bool last = P.flags & 1, masked = P.flags & 2;
+  int16_t* slot = state + (long long)P.slot * FLAC_MIN_BLOCK;
+  if (t < FLAC_MIN_BLOCK) s_c[t] = t < c ? slot[t] : (int16_t)0;
+  if (t == 0) s_run = 0;
+  long long L = P.n;
+  if (P.count_idx >= 0) {
+    const long long k = counts[P.count_idx];
+    L = k < 0 ? 0 : (k < L ? k : L);
+  }
+  __syncthreads();
+  // a push that is not final has neither a count nor a mask: what it holds and emits is known before a sample is read
+  const long long avail = c + L, r = avail & (FLAC_BLOCK - 1);
+  const long long emit = last ? (1ll << 62) : avail < FLAC_MIN_BLOCK ? 0 : r < FLAC_MIN_BLOCK ? avail - r : avail;
+  int16_t* dst = stage + P.stage;
+  const int16_t* src = pcm + P.start;
+  if (t < c) {
+    dst[t] = s_c[t];
+    if (t >= emit) slot[t - emit] = s_c[t];
+  }
+  for (long long tile = 0; tile < L; tile += 8 * 1024) {
+    const long long i0 = tile + 8 * t;
+    uint32_t bits = 0;
+    if (i0 < L) {
+      bits = masked ? mask[(P.start + i0) >> 3] : 0xFFu;
+      if (L - i0 < 8) bits &= (0xFFu << (8 - (int)(L - i0))) & 0xFFu;
+    }
+    const int cnt = __popc(bits);
+    long long pos = i0;
+    if (masked) {
+      int cur = 0;
+      s_v[0][t] = cnt;
+      __syncthreads();
+      for (int d = 1; d < 1024; d <<= 1) {
+        s_v[cur ^ 1][t] = s_v[cur][t] + (t >= d ? s_v[cur][t - d] : 0);
+        cur ^= 1;
+        __syncthreads();
+      }
+      const long long run = s_run;
+      pos = run + s_v[cur][t] - cnt;
+      __syncthreads();
+      if (t == 1023) s_run = run + s_v[cur][t];
+    }
+    if (bits) {
+      int16_t x[8];
+      if (i0 + 8 <= L) {                 // pcm is 16-byte aligned and starts are multiples of 8 elements
+        const int4 a = *reinterpret_cast<const int4*>(src + i0);
+        const int w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          x[2 * j] = (int16_t)(w[j] & 0xFFFF);
+          x[2 * j + 1] = (int16_t)(w[j] >> 16);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = i0 + j < L ? src[i0 + j] : (int16_t)0;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (bits & (0x80u >> j)) {
+          const long long d = c + pos++;
+          dst[d] = x[j];
+          if (d >= emit) slot[d - emit] = x[j];
+        }
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    const long long held = c + (masked ? s_run : L);
+    FlacRange R;
+    R.start = P.stage;
+    R.n = c + P.n;
+    R.rate = P.rate;
+    R.count_idx = (int32_t)blockIdx.x;
+    R.frame0 = P.frame0;
+    rng[blockIdx.x] = R;
+    base[blockIdx.x] = P.sample;
+    staged[blockIdx.x] = last ? held : emit;
+  }
+}
+
+hipError_t launch_flac_stream(const int16_t* pcm, const uint8_t* mask, const long long* counts, const FlacPush* push, int n_push,
+                              int16_t* state, long long frames_max, long long n_frames, uint8_t* out, long long* meta, long long* staged,
+                              long long* base, FlacRange* rng, FlacFrame* rec, int16_t* stage, hipStream_t st) {
+  if (n_push <= 0 || frames_max <= 0 || n_frames <= 0) return hipSuccess;
+  hipLaunchKernelGGL(flac_stage_k, dim3((unsigned)n_push), dim3(1024), 0, st, pcm, mask, counts, push, state, stage, rng, base, staged);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 grid((unsigned)frames_max, (unsigned)n_push);
+  hipLaunchKernelGGL(flac_analyse_k, grid, dim3(256), 0, st, (const int16_t*)stage, (const long long*)staged, (const FlacRange*)rng, rec,
+                     meta + n_frames + 1, (const long long*)base);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(flac_scan_k, dim3(1), dim3(1024), 0, st, (const FlacFrame*)rec, n_frames, meta);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(flac_pack_k, grid, dim3(256), 0, st, (const int16_t*)stage, (const FlacRange*)rng, (const FlacFrame*)rec,
+                     (const long long*)meta, out, (const long long*)base);
   return hipGetLastError();
 }

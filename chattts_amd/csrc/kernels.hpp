@@ -594,6 +594,26 @@ struct FlacFrame {
 // frames_max: the most slots of one range (grid size).  Every bound is the caller's to check
 hipError_t launch_flac_encode(const int16_t* pcm, const long long* counts, const FlacRange* rng, int n_rng, long long frames_max,
                               long long n_frames, uint8_t* out, long long* meta, FlacFrame* rec, hipStream_t st);
+// streams: variable-block-size frames numbered by their first sample; a stream holds back up to FLAC_MIN_BLOCK - 1 samples between pushes
+#define FLAC_MIN_BLOCK 16
+// ctts_flac_push (include/chattts_amd.h), field for field (capi.hip asserts the layout): n samples from element `start` of the int16
+// input continue the stream in state slot `slot`, which holds `carry` samples, the first of them sample `sample` of the stream
+struct FlacPush {
+  long long start, n;
+  long long sample;           // the number of the first sample staged: the first carried one, or the push's first
+  long long stage;            // the push's first element in the staging buffer (a multiple of 8); it owns carry + n, rounded up to 8
+  long long frame0;           // its first frame slot; it owns ceil((carry + n) / FLAC_BLOCK)
+  int32_t rate, slot, carry;
+  int32_t flags;              // 1: the stream's last push; 2: compacted by the keep mask (bit 7 - (e & 7) of byte (start + e) / 8)
+  int32_t count_idx;          // >= 0: only the first min(counts[count_idx], n) samples count
+  int32_t reserved;
+};
+// One step of many streams: the staging launch, then the three of launch_flac_encode in their stream form.  meta: int64 [n_frames + 1 +
+// n_push] -- the slots' exclusive byte offsets, the total, then the samples each push emitted; staged, base: int64 [n_push]; rng:
+// [n_push]; rec: [n_frames]; stage: 16-byte aligned.  Every bound is the caller's to check
+hipError_t launch_flac_stream(const int16_t* pcm, const uint8_t* mask, const long long* counts, const FlacPush* push, int n_push,
+                              int16_t* state, long long frames_max, long long n_frames, uint8_t* out, long long* meta, long long* staged,
+                              long long* base, FlacRange* rng, FlacFrame* rec, int16_t* stage, hipStream_t st);
 
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------
 // |STFT| of one waveform: center=True reflect padding, frame f = padded[256 f, 256 f + 1024) * window, 1024-point FFT,

@@ -2128,7 +2128,7 @@ class CodecEngine:
         return wav[:, c_lo: c_hi]
 
     def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
-                       sample_rates=None, encodings=None, speeds=None, ts_streams=None, rs_streams=None):
+                       sample_rates=None, encodings=None, speeds=None, ts_streams=None, rs_streams=None, flac=None, flac_streams=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -2164,7 +2164,34 @@ class CodecEngine:
         conversion, a tail's strip and the companding are taken on those samples.  A `tail` window is the last push of both
         streams; several windows of one stream go to successive rounds in both stages.  Windows at speed 1 and another rate keep
         the stateless window path of `sample_rates` and return its bytes; in a call that also holds windows at another speed they
-        take a decoder pass of their own."""
+        take a decoder pass of their own.
+        `flac` (None, or all False: the call above, argument for argument; needs `pcm16`) with `flac_streams`: one flag and one entry
+        per window, the handle of the FLAC stream (`flac_stream_open`, at the window's rate) a flagged window continues.  A flagged
+        window PUSHES the int16 samples it would come back as into its stream and comes back as uint8, the frames that push completes
+        (possibly none; `flac.StreamEncoder.push` byte for byte) -- strictly behind the conversion, on every path above; a window
+        marked `tail` is the stream's last push, and with `keep_thr` it is stripped on the device by the conversion's keep mask.  ONE
+        `flac_stream_step` for the whole call (four launches), one small copy of the frame offsets and one of the bytes used: a flagged
+        window's samples never cross the bus (a call whose windows are all flagged copies no samples at all).  A flagged window whose
+        crop is empty still steps its stream; several windows of one stream are taken in the order given, each in a step of its own
+        round.  A flag together with an encoding is refused."""
+        fl = None
+        if flac is not None and any(bool(f) for f in flac):
+            if len(flac) != len(windows) or flac_streams is None or len(flac_streams) != len(windows):
+                raise ValueError("decode_windows: one flac flag and one flac_streams entry per window")
+            if not pcm16:
+                raise ValueError("decode_windows: FLAC comes behind the 16-bit conversion (pcm16=True)")
+            if encodings is not None and any(f and e is not None for f, e in zip(flac, encodings)):
+                raise ValueError("decode_windows: flac does not go with an encoding (a FLAC stream holds the 16-bit samples)")
+            for i, (f, h) in enumerate(zip(flac, flac_streams)):
+                if f:
+                    want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
+                    if h is None or self._flac_rec(h)[0] != want:
+                        raise ValueError(f"decode_windows: window {i} needs an open FLAC stream at {want} Hz")
+                elif h is not None:
+                    raise ValueError(f"decode_windows: window {i} has no flac flag but names a FLAC stream")
+            fl = ([int(h) if f else None for f, h in zip(flac, flac_streams)], [len(w) > 4 and bool(w[4]) for w in windows])
+        elif flac_streams is not None and any(h is not None for h in flac_streams):
+            raise ValueError("decode_windows: flac_streams without a flac flag")
         q = None
         if speeds is not None:
             if len(speeds) != len(windows):
@@ -2198,21 +2225,22 @@ class CodecEngine:
                             raise ValueError(f"decode_windows: window {i} is at speed 1 but names a stream")
                     rest = [i for i in range(len(windows)) if i not in set(alone)]
                     pick = lambda v, idx: None if v is None else [v[i] for i in idx]
+                    pick2 = lambda v, idx: None if v is None else (pick(v[0], idx), pick(v[1], idx))
                     out: list = [None] * len(windows)
                     got = self._decode_windows_speed(store, pick(windows, rest), pick(q, rest), pick(ts_streams, rest), pcm16, keep_thr,
-                                                     product, pick(laws, rest), pick(rates, rest), pick(rs_streams, rest))
+                                                     product, pick(laws, rest), pick(rates, rest), pick(rs_streams, rest), pick2(fl, rest))
                     for i, a in zip(alone, self._decode_windows_rate(store, pick(windows, alone), pick(rates, alone), pcm16, keep_thr,
-                                                                     product, pick(laws, alone))):
+                                                                     product, pick(laws, alone), pick2(fl, alone))):
                         out[i] = a
                     for i, a in zip(rest, got):
                         out[i] = a
                     return out
-            return self._decode_windows_speed(store, windows, q, ts_streams, pcm16, keep_thr, product, laws, rates, rs_streams)
+            return self._decode_windows_speed(store, windows, q, ts_streams, pcm16, keep_thr, product, laws, rates, rs_streams, fl)
         if sample_rates is not None:
             if len(sample_rates) != len(windows):
                 raise ValueError("decode_windows: one sample rate per window")
             if any(int(r) != self.SAMPLE_RATE for r in sample_rates):
-                return self._decode_windows_rate(store, windows, [int(r) for r in sample_rates], pcm16, keep_thr, product, laws)
+                return self._decode_windows_rate(store, windows, [int(r) for r in sample_rates], pcm16, keep_thr, product, laws, fl)
         S, cap = self._windows_store(store)
         out: list = [None] * len(windows)
         rows, live = [], []
@@ -2225,7 +2253,7 @@ class CodecEngine:
             rows.append((slot, *win, int(tail), 0, 0))
             live.append(i)
         if not live:
-            return out
+            return self._windows_flac_idle(fl, out)
         tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]: slot, t_lo, t_hi, c_lo, c_hi, keep, 0, 0
         n = (tab[:, 4] - tab[:, 3]).astype(np.int64)
         lay = self._windows_layout(n, tab[:, 5], pcm16, laws)
@@ -2236,7 +2264,7 @@ class CodecEngine:
                                                       tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(live), *tail_args),
                    "ctts_codec_decode_windows")
         tab_d.record_stream(cur)
-        return self._windows_finish(lay, n, tab[:, 5], live, laws, pcm16, out)
+        return self._windows_finish(lay, n, tab[:, 5], live, laws, pcm16, out, fl)
 
     # -- what the three paths of `decode_windows` share: the prologue (store, one window's fields, an empty result, the crops' places in the
     # packed decode), the output layout, the tail of the C call and the epilogue.  A further variant builds its own tables between them
@@ -2285,13 +2313,36 @@ class CodecEngine:
         return cur, (1 if pcm16 else 0, buf.data_ptr(), buf.data_ptr() + n_out + n_g if keep.any() else None, {"f64": 0, "f32": 1}[product],
                      float(keep_thr or 0.0), ws.data_ptr(), nws, cur.cuda_stream)
 
-    def _windows_finish(self, lay, n, keep, live, laws, pcm16: bool, out: list) -> list:
+    def _windows_finish(self, lay, n, keep, live, laws, pcm16: bool, out: list, fl=None) -> list:
         off, n_out, n_g, n_keep, buf = lay
         return self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, off, n, keep, live, None if laws is None else [laws[i] for i in live],
-                                     np.int16 if pcm16 else np.float32, out)
+                                     np.int16 if pcm16 else np.float32, out, fl)
+
+    def _windows_flac_idle(self, fl, out: list) -> list:
+        """a call none of whose windows has a sample: the flagged ones still step their streams (a tail ends its stream and brings
+        what the stream held)"""
+        if fl is not None:
+            idle = [i for i, h in enumerate(fl[0]) if h is not None]
+            out[:] = [a for a in self._flac_rounds(torch.zeros((8,), dtype=torch.int16, device=self.device), None, idle,
+                                                   [(fl[0][i], 0, 0, fl[1][i]) for i in idle], out)]
+        return out
+
+    def _flac_rounds(self, pcm: torch.Tensor, masks, idx, pushes, out: list) -> list:
+        """pushes[j] is window idx[j]'s: ONE `flac_stream_step` when no stream is named twice, else the r-th push of a stream goes to
+        step r, in the order given; -> `out` with the windows' chunks in place"""
+        out, seen, rounds = list(out), {}, []
+        for i, p in zip(idx, pushes):
+            r = seen[p[0]] = seen.get(p[0], -1) + 1
+            if r == len(rounds):
+                rounds.append([])
+            rounds[r].append((i, p))
+        for rnd in rounds:
+            for (i, _), c in zip(rnd, self.flac_stream_step(pcm, [p for _, p in rnd], None, masks)):
+                out[i] = c
+        return out
 
     def _decode_windows_speed(self, store: torch.Tensor, windows, q, ts_streams, pcm16: bool, keep_thr: Optional[float], product: str,
-                              laws=None, rates=None, rs_streams=None):
+                              laws=None, rates=None, rs_streams=None, fl=None):
         """`decode_windows` with at least one window at another speed than 1 (q: the windows' (num, den)).  `rates` (None: all 24000)
         with `rs_streams`: the scaled windows that also leave 24 kHz, each with its resampler stream"""
         S, cap = self._windows_store(store)
@@ -2406,12 +2457,27 @@ class CodecEngine:
         pool["rec"].update(commit)
         if staged:
             rs_pool["rec"].update(rs_commit)
-        return self._windows_finish(lay, n, ctab[:, 5], [c[0] for c in conv], laws, pcm16, out)
+        return self._windows_finish(lay, n, ctab[:, 5], [c[0] for c in conv], laws, pcm16, out, fl)
 
-    def _windows_to_host(self, buf: torch.Tensor, n_out: int, n_g: int, off, n, keep, live, laws, dt, out: list) -> list:
+    def _windows_to_host(self, buf: torch.Tensor, n_out: int, n_g: int, off, n, keep, live, laws, dt, out: list, fl=None) -> list:
         """the end of `decode_windows`: `buf` = samples (n_out bytes) | companded bytes (n_g, 0 without `laws`) | keep masks.  The
         companded windows (laws[k] >= 0) are converted by one launch over their own element offsets `off`; ONE copy to the host -- of
-        the codes and the masks when every window is companded, of the whole buffer otherwise -- and live window k becomes out[live[k]]"""
+        the codes and the masks when every window is companded, of the whole buffer otherwise -- and live window k becomes out[live[k]].
+        `fl` = (FLAC stream or None per window, tail flag per window): the flagged windows, live or not, are the pushes of ONE
+        `flac_stream_step` over the int16 samples and the keep masks where they lie; their samples are not copied, and when every
+        live window is flagged nothing of `buf` is"""
+        chunks = {}
+        if fl is not None:
+            row = {i: k for k, i in enumerate(live)}
+            idx = [i for i, h in enumerate(fl[0]) if h is not None]
+            pushes = [(fl[0][i], int(off[row[i]]), int(n[row[i]]), fl[1][i], None, bool(keep[row[i]])) if i in row else (fl[0][i], 0, 0, fl[1][i])
+                      for i in idx]
+            masks = buf[n_out + n_g:] if any(len(p) > 4 and p[5] for p in pushes) else None
+            done = self._flac_rounds(buf[:n_out].view(torch.int16), masks, idx, pushes, out)
+            chunks = {i: done[i] for i in idx}
+            if all(i in chunks for i in live):
+                out[:] = done
+                return out
         base = 0
         if laws is not None:
             self.g711_encode(buf[:n_out].view(torch.int16), [(int(off[k]), int(n[k]), laws[k]) for k in range(len(live))],
@@ -2430,6 +2496,8 @@ class CodecEngine:
                 kb = n_out - base + n_g + int(off[k]) // 8
                 a = a[np.unpackbits(host[kb: kb + (int(n[k]) + 7) // 8])[: int(n[k])].astype(bool)]
             out[i] = a
+        for i, c in chunks.items():
+            out[i] = c
         return out
 
     def g711_encode(self, pcm: torch.Tensor, ranges, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -2514,7 +2582,140 @@ class CodecEngine:
             res.append((frames, lens[lens > 0], int(meta[n_frames + 1 + k])) if info else frames)
         return res
 
-    def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str, laws=None):
+    # -- FLAC for streams: per-stream device state (csrc/flac.hip, flac_stage_k) ---------------------------------------------------------
+    FLAC_STREAM_SLOTS = 64    # the state pool's first size; it doubles when every slot is taken
+
+    def _flac_pool(self) -> dict:
+        """the state pool: carry [slots, 16] int16 on the device, the free list, and per open stream its host record [rate, the number
+        of the first sample it holds, samples held (0 .. 15), done]"""
+        pool = self.__dict__.get("_flac_streams")
+        if pool is None:
+            n = int(self.FLAC_STREAM_SLOTS)
+            pool = self._flac_streams = dict(carry=torch.zeros((n, FLAC.MIN_BLOCK), dtype=torch.int16, device=self.device),
+                                             free=list(range(n - 1, -1, -1)), rec={})
+        return pool
+
+    def flac_stream_open(self, rate: int, first_sample: int = 0) -> int:
+        """A FLAC stream at `rate` Hz whose first sample has the number `first_sample`: -> its handle, a slot of the engine's state
+        pool.  The slot is fresh by construction -- a stream that holds no samples reads none -- so nothing is cleared.  ValueError for
+        a rate the format cannot code and a sample number beyond 36 bits."""
+        FLAC.rate_code(rate)
+        if not 0 <= int(first_sample) < FLAC.MAX_SAMPLES:
+            raise ValueError(f"flac: sample number {first_sample} does not fit 36 bits")
+        pool = self._flac_pool()
+        if not pool["free"]:
+            n = int(pool["carry"].shape[0])
+            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
+            pool["free"] = list(range(2 * n - 1, n - 1, -1))
+        slot = pool["free"].pop()
+        pool["rec"][slot] = [int(rate), int(first_sample), 0, False]
+        return slot
+
+    def flac_stream_close(self, handle: int) -> None:
+        """gives the stream's slot back (any time: finished, or abandoned half way)"""
+        pool = self._flac_pool()
+        if pool["rec"].pop(int(handle), None) is None:
+            raise ValueError(f"flac: stream {handle} is not open")
+        pool["free"].append(int(handle))
+
+    def flac_streams_in_use(self) -> int:
+        """the streams that are open: slots of the state pool not on its free list"""
+        return len(self._flac_pool()["rec"])
+
+    def _flac_rec(self, handle: int):
+        rec = self._flac_pool()["rec"].get(int(handle))
+        if rec is None:
+            raise ValueError(f"flac: stream {handle} is not open")
+        if rec[3]:
+            raise ValueError(f"flac: stream {handle} has had its last push")
+        return rec
+
+    def flac_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
+        """`flac.stream_plan` of the stream's next push: the blocks a step with `n_in` more samples would emit, the number of the first
+        of them, the samples the stream would hold afterwards, and the most bytes the push can emit"""
+        rate, sample, carry, _ = self._flac_rec(handle)
+        blocks, held = FLAC.stream_plan(carry, n_in, final)
+        return dict(rate=rate, sample=sample, blocks=blocks, carry=held, bound=FLAC.stream_bound(n_in))
+
+    def flac_stream_step(self, pcm: torch.Tensor, pushes, counts: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None) -> list:
+        """ONE step of many FLAC streams (ctts_flac_stream_step: four launches whatever their number): `pcm`, a contiguous int16 device
+        tensor taken as flat, holds the new samples of every stream; `pushes` = [(handle, start, n, final)] or [(handle, start, n,
+        final, count_idx, masked)]: pcm[start, start + n) continue stream `handle` (n 0: nothing new; starts are multiples of 8),
+        `final`: they are its last.  A final push may leave its length to the device: with a count_idx only the first
+        min(counts[count_idx], n) samples count (`counts`: an int64 device tensor), and `masked` keeps only the samples whose bit is
+        set in `masks` (a uint8 device tensor, MSB first, the bit of element e of `pcm` in byte e / 8: `decode_windows`' keep masks).
+        -> one uint8 array per push: the frames that push completes (possibly none), `flac.StreamEncoder.push` byte for byte; behind
+        `flac.stream_header(rate)` a stream's chunks are a FLAC stream of its pushes, concatenated, however they were cut.  A handle may
+        appear once per call.  One small copy (the frame offsets and the total) and one copy of exactly the bytes used come to the host;
+        the samples stay on the device.  Every refusal (ValueError here, EngineError from the library) comes before the first launch
+        and leaves all streams as they were."""
+        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()):
+            raise ValueError("flac: a contiguous int16 device tensor")
+        if counts is not None and not (counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()):
+            raise ValueError("flac: `counts` must be a contiguous int64 device tensor")
+        if masks is not None and not (masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous()):
+            raise ValueError("flac: `masks` must be a contiguous uint8 device tensor")
+        if len(pushes) < 1:
+            raise ValueError("flac: nothing to step")
+        if len(pushes) > 1024:
+            raise ValueError("flac: at most 1024 streams in one step")
+        if len({int(p[0]) for p in pushes}) != len(pushes):
+            raise ValueError("flac: a stream appears twice in one step")
+        pool = self._flac_pool()
+        n_el, n_push = pcm.numel(), len(pushes)
+        tab = np.zeros(n_push, _lib.FLAC_PUSH)
+        stage = slots = 0
+        commit = {}
+        for k, p in enumerate(pushes):
+            h, start, n, final = int(p[0]), int(p[1]), int(p[2]), bool(p[3])
+            ci = int(p[4]) if len(p) > 4 and p[4] is not None else -1
+            masked = len(p) > 5 and bool(p[5])
+            rate, sample, carry, _ = self._flac_rec(h)
+            if n < 0 or start < 0 or start + n > n_el:
+                raise ValueError("flac: a push lies outside the tensor")
+            if ci >= 0 and (counts is None or ci >= counts.numel()):
+                raise ValueError(f"flac: push {k} reads count {ci}, beyond `counts`")
+            if masked and (masks is None or masks.numel() * 8 < start + n):
+                raise ValueError(f"flac: push {k} is masked, and `masks` does not reach its end")
+            if (ci >= 0 or masked) and not final:
+                raise ValueError(f"flac: push {k} leaves its length to the device but is not final")
+            if sample + carry + n >= FLAC.MAX_SAMPLES:
+                raise ValueError(f"flac: push {k} would take the stream's sample number to 2^36")
+            tab[k] = (start, n, sample, stage, slots, rate, h, carry, int(final) | 2 * int(masked), ci, 0)
+            blocks, held = FLAC.stream_plan(carry, n, final)                     # a final push's own count only shortens its last blocks
+            commit[h] = [rate, sample + sum(blocks), held, final]
+            stage += (carry + n + 7) // 8 * 8
+            slots += (carry + n + FLAC.BLOCK - 1) // FLAC.BLOCK
+        n_slots = int(pool["carry"].shape[0])
+        sizes = (C.c_int64 * 4)()
+        _lib.check(self.lib.ctts_flac_stream_sizes(tab.ctypes.data_as(C.c_void_p), n_push, n_slots, n_el, sizes), "ctts_flac_stream_sizes")
+        n_frames, out_bytes, work_bytes, _ = (int(v) for v in sizes)
+        empty = np.zeros((0,), np.uint8)
+        if n_frames == 0:                                                        # no stream holds or gets a sample
+            pool["rec"].update(commit)
+            return [empty for _ in pushes]
+        dev = pcm.device
+        out = torch.empty(((out_bytes + 15) // 16 * 16,), dtype=torch.uint8, device=dev)
+        work = torch.empty((work_bytes,), dtype=torch.uint8, device=dev)
+        tab_d = torch.from_numpy(tab.view(np.uint8)).to(dev)
+        st = torch.cuda.current_stream(dev)
+        _lib.check(self.lib.ctts_flac_stream_step(pcm.data_ptr(), n_el, _lib.ptr(masks), _lib.ptr(counts), tab_d.data_ptr(),
+                                                  tab.ctypes.data_as(C.c_void_p), n_push, pool["carry"].data_ptr(), n_slots, out.data_ptr(),
+                                                  out.numel(), work.data_ptr(), work.numel(), st.cuda_stream), "ctts_flac_stream_step")
+        tab_d.record_stream(st)
+        pool["rec"].update(commit)
+        meta = self.to_host(work[: (8 * (n_frames + 1) + 15) // 16 * 16]).view(np.int64)              # the slots' offsets and the total
+        total = int(meta[n_frames])
+        blob = self.to_host(out[: (total + 15) // 16 * 16])[:total] if total else empty
+        res = []
+        for k in range(n_push):
+            f0 = int(tab["frame0"][k])
+            f1 = f0 + (int(tab["carry"][k]) + int(tab["n"][k]) + FLAC.BLOCK - 1) // FLAC.BLOCK
+            res.append(blob[int(meta[f0]): int(meta[f1])])
+        return res
+
+    def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str, laws=None,
+                             fl=None):
         """`decode_windows` with at least one window at another rate than 24 kHz"""
         S, cap = self._windows_store(store)
         out: list = [None] * len(windows)
@@ -2543,7 +2744,7 @@ class CodecEngine:
             res.append(rs)
             live.append(i)
         if not live:
-            return out
+            return self._windows_flac_idle(fl, out)
         tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]
         tok, start = self._packed_crops(tab)
         rtab = np.zeros(len(live), _lib.RS_WINDOW)                           # ctts_rs_window[n]
@@ -2574,7 +2775,7 @@ class CodecEngine:
             base + tab.nbytes, rtab.ctypes.data_as(C.c_void_p), base + tab.nbytes + rtab.nbytes, sel.ctypes.data_as(C.c_void_p), len(live),
             C.cast(rate_tab, C.c_void_p), len(by_q), *tail_args), "ctts_codec_decode_windows_rate")
         blob_d.record_stream(cur)
-        return self._windows_finish(lay, n, tab[:, 5], live, laws, pcm16, out)
+        return self._windows_finish(lay, n, tab[:, 5], live, laws, pcm16, out, fl)
 
     def to_host(self, t: torch.Tensor) -> np.ndarray:
         """device tensor -> numpy, the `.cpu().numpy()` that ends the reference path (core.py:508-510), through a cached PINNED

@@ -9,7 +9,11 @@ lowest k.  So a frame never exceeds its VERBATIM size, 16 + 2 n bytes, which giv
 are 64-bit too.  The file is `fLaC`, one STREAMINFO block (MD5 all zero: "not computed", the samples never reach the host) and the frames.
 
 The device encodes whole results; this form serves the odd pieces that are converted on the host (SpeechBatcher.finish, a split request
-concatenated on the host) and the tests."""
+concatenated on the host) and the tests.
+
+Streams (the second half of this file; ctts_flac_stream_step) arrive in pushes and leave as variable-block-size frames (FF F9) that carry
+the number of their first sample: `stream_header`, `frame_header_variable`, `stream_plan` (the cutting rule), `stream_bound`,
+`StreamEncoder`."""
 from __future__ import annotations
 
 import numpy as np
@@ -222,3 +226,102 @@ def encode(pcm, rate) -> bytes:
     """int16 samples -> the whole FLAC file"""
     body, lens = frames(pcm, rate)
     return stream_info(len(pcm), rate, lens) + body
+
+
+# ---- streams: variable-block-size frames (sync FF F9) that carry the number of their first sample ------------------------------------
+# A stream is cut where its pushes end, so its blocks have 16 .. 4096 samples (the last: 1 .. 4096) and a frame says where it starts.  Up
+# to 15 samples wait for the next push (a block under 16 samples may only end a stream).  The subframes are the file encoder's, search
+# and all; the bytes depend on the cut, the decoded samples do not.  csrc/flac.hip (ctts_flac_stream_step) agrees byte for byte.
+MIN_BLOCK = 16
+MAX_SAMPLES = 1 << 36
+
+
+def stream_header(rate) -> bytes:
+    """`fLaC` and STREAMINFO of a stream whose end is not known: blocks of 16 .. 4096 samples, frame sizes, total and MD5 unknown (0)"""
+    rate_code(rate)
+    v = (int(rate) << 44) | (0 << 41) | (15 << 36)
+    return b"fLaC\x80\x00\x00\x22" + MIN_BLOCK.to_bytes(2, "big") + BLOCK.to_bytes(2, "big") + bytes(6) + v.to_bytes(8, "big") + bytes(16)
+
+
+def frame_header_variable(sample: int, n: int, rate: int) -> bytes:
+    """the header of the block of n samples whose first is sample `sample` of the stream (up to 36 bits: 1 .. 7 bytes), with its CRC-8"""
+    sample, n = int(sample), int(n)
+    if not 0 <= sample < MAX_SAMPLES:
+        raise ValueError(f"flac: sample number {sample} does not fit 36 bits")
+    if not 1 <= n <= BLOCK:
+        raise ValueError(f"flac: a block of {n} samples")
+    rc = rate_code(rate)
+    h = bytearray([0xFF, 0xF9, ((0x0C if n == BLOCK else 0x07) << 4) | rc, 0x08])
+    h += _frame_number(sample)
+    if n != BLOCK:
+        h += bytes([(n - 1) >> 8, (n - 1) & 0xFF])
+    if rc == 13:
+        h += bytes([int(rate) >> 8, int(rate) & 0xFF])
+    h.append(crc8(h))
+    return bytes(h)
+
+
+def stream_plan(carry: int, n_in: int, final: bool):
+    """the cutting rule: a stream that holds `carry` samples (0 .. 15) gets n_in more -> (the lengths of the blocks it emits, the samples
+    it holds afterwards).  Blocks of 4096 from the front; a rest of 16 or more is one more block; a rest of 1 .. 15 waits, unless the
+    push is the last, which emits it."""
+    carry, n_in = int(carry), int(n_in)
+    if not 0 <= carry < MIN_BLOCK or n_in < 0:
+        raise ValueError(f"flac: a stream carries 0 .. 15 samples and is pushed 0 or more (got {carry}, {n_in})")
+    avail = carry + n_in
+    blocks = [BLOCK] * (avail // BLOCK)
+    r = avail % BLOCK
+    if not final and (avail < MIN_BLOCK or 0 < r < MIN_BLOCK):
+        return (blocks if avail >= MIN_BLOCK else []), (r if avail >= MIN_BLOCK else avail)
+    if r:
+        blocks.append(r)
+    return blocks, 0
+
+
+def stream_bound(n_in: int) -> int:
+    """the most bytes one push of n_in samples emits: with the carry up to n_in + 15 samples in at most (n_in + 15) // 4096 + 1 frames,
+    each at most its VERBATIM form -- a header of up to 16 bytes (7 of them the sample number), the subframe's byte, 2 n, the CRC-16"""
+    n = int(n_in) + MIN_BLOCK - 1
+    return 2 * n + 19 * (n // BLOCK + 1)
+
+
+def stream_frames(pcm, rate, sample: int, blocks) -> bytes:
+    """the frames of consecutive blocks (their lengths in `blocks`) of int16 samples, the first of which is sample `sample`"""
+    x = np.asarray(pcm).astype(np.int64)
+    out, at = [], 0
+    for n in blocks:
+        X = x[at: at + n].reshape(1, n)
+        order, part, ks, nbits = _analyse(X)
+        body = frame_header_variable(sample + at, n, int(rate)) + _subframe(X[0], int(order[0]), int(part[0]), ks[0], int(nbits[0]))
+        out.append(body + crc16(body).to_bytes(2, "big"))
+        at += n
+    assert at == len(x)
+    return b"".join(out)
+
+
+class StreamEncoder:
+    """One stream on the host: push(pcm, final=False) -> the bytes of the frames that push completes (possibly none).  The frames of all
+    pushes behind `stream_header(rate)` are a FLAC stream whose samples are the pushes, concatenated."""
+
+    def __init__(self, rate, first_sample: int = 0):
+        rate_code(rate)
+        if not 0 <= int(first_sample) < MAX_SAMPLES:
+            raise ValueError(f"flac: sample number {first_sample} does not fit 36 bits")
+        self.rate, self.sample, self.done = int(rate), int(first_sample), False        # sample: the number of the first sample held
+        self.held = np.zeros((0,), np.int16)
+
+    def push(self, pcm, final: bool = False) -> bytes:
+        pcm = np.asarray(pcm)
+        if pcm.dtype != np.int16 or pcm.ndim != 1:
+            raise ValueError(f"flac takes a 1-D int16 array, got {pcm.dtype} {pcm.shape}")
+        if self.done:
+            raise ValueError("flac: the stream has had its last push")
+        if self.sample + len(self.held) + len(pcm) >= MAX_SAMPLES:
+            raise ValueError("flac: the push would take the stream's sample number to 2^36")
+        blocks, carry = stream_plan(len(self.held), len(pcm), final)
+        x = np.concatenate([self.held, pcm])
+        n = sum(blocks)
+        out = stream_frames(x[:n], self.rate, self.sample, blocks)
+        self.held, self.sample, self.done = x[n:].copy(), self.sample + n, bool(final)
+        assert len(self.held) == carry
+        return out

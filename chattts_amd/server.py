@@ -96,7 +96,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
-               stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False):
+               stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -144,7 +144,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     request's 16-bit samples as a FLAC file (audio/flac; lossless: the samples of the "wav" response, bit for bit), encoded on the device
     behind the 16-bit conversion (Chat.infer(flac=True) / SpeechBatcher.submit(flac=True)), at whatever rate and speed `sample_rates` /
     `speed` allow.  `"stream": true` with it gets a 400 (a streamed FLAC needs a variable-block-size stream and carried sample numbers),
-    an `"encoding"` key with it too.  `loudness=True` (default off: every response, status and warning is as without it, a `"loudness"`
+    an `"encoding"` key with it too -- unless `stream_flac=True` (with `flac`; default off): then a streamed request with
+    `response_format` "flac" is served as audio/flac: `flac.stream_header(rate)` (STREAMINFO with blocks of 16 .. 4096 samples, the total
+    unknown) in front of the first chunk, then every chunk's frames as they are completed -- variable-block-size frames that carry the
+    number of their first sample, at most 15 samples behind the PCM stream of the same request, whose samples they decode to bit for
+    bit; from the pool with `batch_streams` (SpeechBatcher(stream_flac=True).submit_stream(flac=True)), serially otherwise
+    (Chat.infer(stream=True, flac=True, stream_flac=True)), at whatever streamed rate and speed the other options allow, and /health
+    carries `"stream_flac": true`.  `loudness=True` (default off: every response, status and warning is as without it, a `"loudness"`
     key is ignored with the "unsupported parameters" warning): a non-streamed request body may carry `"loudness"`, a target in LUFS
     (-40 .. -5) -- the utterance is brought to that ITU-R BS.1770-4 integrated loudness on the device, under a +30 dB cap and a -1 dBFS
     ceiling, in front of the 16-bit conversion (Chat.infer(loudness=) / SpeechBatcher.submit(loudness=)), in whatever format, rate and
@@ -166,7 +172,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         from .serving import SpeechBatcher
         batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode, streams=bool(batch_streams),
                                 **({"refine": True} if batch_refine else {}), **({"stream_speeds": True} if speed and stream_speed else {}),
-                                **({"stream_speed_rates": True} if speed and stream_speed and stream_speed_rates else {}))
+                                **({"stream_speed_rates": True} if speed and stream_speed and stream_speed_rates else {}),
+                                **({"stream_flac": True} if flac and stream_flac else {}))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
@@ -174,6 +181,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     pool_stream_speeds = pool_streams and bool(speed and stream_speed) and bool(getattr(batcher, "stream_speeds", False))
     speed_rates = bool(speed and stream_speed and stream_speed_rates)
     pool_stream_speed_rates = pool_stream_speeds and speed_rates and bool(getattr(batcher, "stream_speed_rates", False))
+    flac_streams = bool(flac and stream_flac)
+    pool_stream_flac = pool_streams and flac_streams and bool(getattr(batcher, "stream_flac", False))
     pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
     pool_split = bool(batch_split) and batcher is not None
     allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
@@ -253,6 +262,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             kw = {**kw, "encoding": law}
         if req.stream and rate != SAMPLE_RATE:       # one text: split_text changes nothing but is refused for a stream at another rate
             kw = {**kw, "stream_resample": True, "split_text": False}
+        if req.stream and as_flac:                   # likewise for a streamed FLAC
+            kw = {**kw, "stream_flac": True, "split_text": False}
         if req.stream and spd is not None:           # likewise for a stream at another speed
             kw = {**kw, "stream_time_scale": True, "split_text": False}
             if rate != SAMPLE_RATE:                  # ... and another rate: the resampler's history and look-ahead are carried
@@ -333,7 +344,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 law = enc
         as_flac = bool(flac) and fmt == "flac"       # the engine hands out the file
         if as_flac:
-            if req.stream:
+            if req.stream and not flac_streams:
                 raise HTTPException(400, detail="flac is served for non-streamed requests only: a streamed FLAC needs a variable-block-size "
                                                 "stream and carried sample numbers")
             if request_data.get("encoding") is not None:
@@ -361,7 +372,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 return pcm.tobytes()
             return _av_encode(pcm, fmt, rate)
 
-        if req.stream and pool_streams and (spd is None or (pool_stream_speeds and (rate == SAMPLE_RATE or pool_stream_speed_rates))):
+        if req.stream and pool_streams and (spd is None or (pool_stream_speeds and (rate == SAMPLE_RATE or pool_stream_speed_rates))) \
+                and (not as_flac or pool_stream_flac):
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
                 skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
                 if spd is not None:
@@ -372,6 +384,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     async for chunk in iterate_in_threadpool(chunks):
                         if fmt == "wav" and first:
                             yield stream_header(rate)
+                        if as_flac and first:
+                            yield FLAC.stream_header(rate)
                         first = False
                         if np.asarray(chunk).size:
                             yield encode(chunk, header=False)
@@ -386,10 +400,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        gen = infer(req, rate, law, spd) if spd is not None else (infer(req, rate) if law is None else infer(req, rate, law))
+                        gen = infer(req, rate, law, spd, True) if as_flac else \
+                            infer(req, rate, law, spd) if spd is not None else (infer(req, rate) if law is None else infer(req, rate, law))
                         async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
                             if fmt == "wav" and first:
                                 yield stream_header(rate)
+                            if as_flac and first:
+                                yield FLAC.stream_header(rate)
                             first = False
                             if np.asarray(chunk).size:
                                 yield encode(chunk, header=False)
@@ -463,6 +480,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["pool"] = batcher.occupancy()
         if loudness:
             out["loudness"] = True
+        if flac_streams:
+            out["stream_flac"] = True
         return out
 
     return app

@@ -661,7 +661,8 @@ class _Job:
     speed: Optional[float] = None          # None: 1.0 (on a stream only with SpeechBatcher(stream_speeds=True))
     ts_slot: Optional[int] = None          # a stream at another speed: its stream of the time scaler, opened at its first chunk
     rs_slot: Optional[int] = None          # ... and at another rate: its stream of the resampler, opened with it
-    flac: bool = False                     # the result is the FLAC file of the int16 waveform (non-streamed only)
+    flac: bool = False                     # the result is the FLAC file of the int16 waveform; a stream: its chunks are FLAC frames
+    flac_slot: Optional[int] = None        # a FLAC stream: its stream of the encoder, opened at its first chunk
     loudness: Optional[float] = None       # a target in LUFS (non-streamed only); None: the level is left alone
 
     @property
@@ -742,6 +743,10 @@ class SpeechBatcher:
     request's job also holds a stream of the resampler (`CodecEngine.resample_stream_open(24000, rate)`, opened and given back where
     the time scaler's is) and its chunks are the scaler's chunks resampled with the filter's history and look-ahead carried
     (`decode_windows(..., rs_streams=)`): those of the serial call with `stream_scaled_resample=True`.
+    `stream_flac=True` (with `streams`; off: `submit_stream(flac=True)` is refused as before): a streamed request may ask for FLAC.
+    Its job holds a stream of the encoder (`CodecEngine.flac_stream_open(rate)`, opened at its first chunk, given back in `_resolve`
+    however the request ends); the chunks of all FLAC streams due at one poll are the pushes of ONE encoder step behind the one
+    window decode (`decode_windows(flac=, flac_streams=)`); `occupancy()["stream_flac_chunks"]` counts them.
 
     `refine=True`: requests may ask for the reference's DEFAULT behaviour, the refine-text pass in front of the code pass
     (`submit(text, params, refine=RefineTextParams(...))`).  A second, TEXT-mode per-request pool (SlotPool(infer_text=True), its own
@@ -773,7 +778,8 @@ class SpeechBatcher:
 
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
                  logger=None, ragged_decode: bool = False, streams: bool = False, refine: bool = False, make_text_pool=None,
-                 text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False, stream_speed_rates: bool = False):
+                 text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False, stream_speed_rates: bool = False,
+                 stream_flac: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
@@ -787,6 +793,8 @@ class SpeechBatcher:
         self.stream_speeds = bool(stream_speeds)   # submit_stream(speed=) is accepted
         self.stream_speed_rates = bool(stream_speeds and stream_speed_rates)   # ... at another rate than 24000 too
         self.stream_scaled_chunks = 0      # chunks of streams at another speed than 1
+        self.stream_flac = bool(stream_flac)       # submit_stream(flac=True) is accepted
+        self.stream_flac_chunks = 0        # chunks handed out as FLAC frames (empty ones included)
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.flac_encoded = 0              # results handed out as FLAC files
         self.max_stream_group = 0     # most chunks one window decode served
@@ -892,14 +900,22 @@ class SpeechBatcher:
         batcher was built with `stream_speeds=True`: then the chunks are those of the serial call with `speed=, stream_time_scale=True`
         (the path and a tail of samples are carried on the device, per stream), at 24000 Hz only -- unless it was also built with
         `stream_speed_rates=True`: then `speed` goes with `sample_rate`, the serial call's `stream_scaled_resample=True`.  `flac` is
-        refused: a streamed FLAC needs a variable-block-size stream and carried sample numbers.  `loudness` is refused: an integrated
-        loudness needs the whole utterance."""
+        refused: a streamed FLAC needs a variable-block-size stream and carried sample numbers -- unless the batcher was built with
+        `stream_flac=True`: then the chunks are uint8, the FLAC frames each chunk completes (possibly none: up to 15 samples wait for
+        the next chunk), the serial call's `flac=True, stream_flac=True`; behind `flac.stream_header(rate)` they decode to the int16
+        chunks of the same request without `flac`.  The chunks of all FLAC streams due at one poll share ONE encoder step behind the
+        one decoder pass (CodecEngine.decode_windows(flac=)); it combines with `sample_rate` and `speed` as far as the batcher serves
+        those, not with `encoding`.  `loudness` is refused: an integrated loudness needs the whole utterance."""
         if LN.check_target(loudness) is not None:
             raise ValueError("loudness applies to non-streamed requests only (an integrated loudness needs the whole utterance; a stream "
                              "would need a running measure)")
-        if flac:
+        if flac and not self.stream_flac:
             raise ValueError("flac is served for non-streamed requests only (a streamed FLAC needs a variable-block-size stream and "
                              "carried sample numbers)")
+        if flac:
+            if encoding is not None:
+                raise ValueError("flac does not go with an encoding (a FLAC stream holds the 16-bit samples)")
+            FLAC.rate_code(24000 if sample_rate is None else sample_rate)
         G711.check_encoding(encoding)
         speed = _job_speed(speed)
         if speed is not None and not self.stream_speeds:
@@ -918,7 +934,7 @@ class SpeechBatcher:
             if speed is not None and K - 1 > RS.CARRY:
                 raise ValueError(f"a streamed speed at {rate} Hz would carry up to {K - 1} samples, a resampler stream keeps {RS.CARRY}")
         h = SpeechStream(self, next(self._ids))
-        self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed))
+        self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed, flac=bool(flac)))
         return h
 
     def _check_refine(self, refine) -> None:
@@ -940,6 +956,8 @@ class SpeechBatcher:
             occ.update({"streams": sum(j.is_stream for j in list(self._jobs.values())), "stream_decode_calls": self.stream_decode_calls,
                         "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled,
                         "stream_resampled_chunks": self.stream_resampled_chunks, "stream_scaled_chunks": self.stream_scaled_chunks})
+            if self.stream_flac:
+                occ["stream_flac_chunks"] = self.stream_flac_chunks
         if self.refine:
             occ["refine"] = {"active": len(getattr(tp, "active", {})), "queued": len(getattr(tp, "queue", ())),
                              "admissions": self.refine_admissions, "max_coresident": self.refine_max_coresident,
@@ -967,6 +985,9 @@ class SpeechBatcher:
         if job.rs_slot is not None:        # ... and its stream of the resampler
             slot, job.rs_slot = job.rs_slot, None
             self.chat.codec.resample_stream_close(slot)
+        if job.flac_slot is not None:      # ... and its stream of the FLAC encoder
+            slot, job.flac_slot = job.flac_slot, None
+            self.chat.codec.flac_stream_close(slot)
         failed = isinstance(result, BaseException)
         if cancelled:
             self.cancelled += job.is_stream
@@ -974,7 +995,7 @@ class SpeechBatcher:
             self.failed += 1
         else:
             self.completed += 1
-            self.flac_encoded += job.flac
+            self.flac_encoded += job.flac and not job.is_stream                  # (a stream's chunks are counted as they go out)
             self.companded += not job.is_stream and job.encoding is not None      # (a stream's chunks are counted as they go out)
         if job.is_stream:
             job.sink._q.put(None if cancelled else result)
@@ -1213,6 +1234,12 @@ class SpeechBatcher:
                 kw["ts_streams"] = [j.ts_slot for j in jobs]
                 if any(j.rs_slot is not None for j in jobs):
                     kw["rs_streams"] = [j.rs_slot for j in jobs]
+            if "flac" in kw:              # the FLAC streams due at this poll: one encoder step behind the one decode
+                self.stream_flac_chunks += sum(j.flac for j in jobs)
+                for j in jobs:
+                    if j.flac and j.flac_slot is None:
+                        j.flac_slot = self.chat.codec.flac_stream_open(24000 if j.sample_rate is None else j.sample_rate)
+                kw["flac_streams"] = [j.flac_slot for j in jobs]
             pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **kw)
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for job in dict.fromkeys(jobs):

@@ -664,6 +664,47 @@ int ctts_flac_encode_sizes(const ctts_flac_range* rng_host, int32_t n_rng, int64
 int ctts_flac_encode_ranges(const int16_t* pcm, const int64_t* counts, const ctts_flac_range* rng_dev, const ctts_flac_range* rng_host,
                             int32_t n_rng, uint8_t* out, size_t out_bytes, void* work, size_t work_bytes, void* stream);
 
+/* FLAC for STREAMS: the signal arrives in pushes and leaves as variable-block-size frames (sync FF F9) whose header carries the number of
+ * the block's first sample, in up to 36 bits (1 .. 7 bytes).  chattts_amd/flac.py (StreamEncoder) is the NumPy twin, byte for byte; the
+ * subframes and their exact search are those above.  The cutting rule: a stream holds `carry` samples (0 .. 15) from its last push in its
+ * state slot (`state`: int16 [n_slots][16] on the device); with the push's samples that makes `avail`.  Blocks of 4096 leave from the
+ * front; a rest of 16 or more is one more block; a rest of 1 .. 15 stays in the slot -- unless the push is final (flags & 1), which emits
+ * it as the stream's last block.  A push with avail < 16 that is not final emits nothing.  So every block but a stream's last has
+ * 16 .. 4096 samples, and a frame is at most 19 + 2 n bytes.
+ * Push i: elements [start, start + n) of `pcm` continue the stream in `slot`; `sample` is the number of the first staged sample (the
+ * first carried one).  A FINAL push may leave its length to the device: count_idx >= 0 takes min(counts[count_idx], n) samples, and
+ * flags & 2 keeps only the samples whose bit is set in `mask` (MSB first; the push's bits start at byte start / 8: the keep masks of
+ * ctts_codec_decode_windows).  The push owns staging elements [stage, stage + carry + n rounded up to 8) and the frame slots
+ * [frame0, frame0 + ceil((carry + n) / 4096)), both the running sums over the pushes in front of it.  The caller keeps carry and sample
+ * of every stream (a push that is not final is planned in integers: the rule above) and reads, from the first byte of `work` on, int64
+ * [n_frames + 1] the exclusive byte offset of every slot and the total, then int64 [n_push] the samples each push emitted.  The frames of
+ * all pushes lie back to back from out[0] on, in slot order.  Four launches (flac_stage_k, flac_analyse_k, flac_scan_k, flac_pack_k)
+ * whatever the number of pushes; no launch when no push holds a sample.  ctts_flac_stream_sizes checks a host table and gives sizes[4] =
+ * {n_frames, the bytes `out` must hold (sum of 2 (carry + n) + 19 slots), the bytes `work` must hold, the staging elements}.
+ * Refused on the host table before anything is launched, all streams left as they were: a null pointer (mask / counts may be null when
+ * no push uses them), n_push < 1 or > 1024, a slot outside [0, n_slots) or named twice, a start that is negative or no multiple of 8, a
+ * push that ends beyond n_pcm, n negative or >= 2^31, a carry outside 0 .. 15, a rate that is neither in the format's table nor
+ * 1 .. 65535, unknown flag bits, a count_idx < -1 or > 65535, a count_idx or a mask on a push that is not final, a negative sample
+ * number or one that the push would take to 2^36 (sample + carry + n >= 2^36), a stage or frame0 other than the running sum, out_bytes
+ * or work_bytes too small, pointers not 16-byte aligned (counts: 8). */
+typedef struct {
+  int64_t start;          /* first element of the int16 input; a multiple of 8 */
+  int64_t n;              /* samples pushed (with a count_idx or a mask: at most) */
+  int64_t sample;         /* the number of the first staged sample */
+  int64_t stage;          /* the push's first staging element */
+  int64_t frame0;         /* the push's first frame slot */
+  int32_t rate;           /* Hz */
+  int32_t slot;           /* the stream's state slot */
+  int32_t carry;          /* samples the slot holds, 0 .. 15 */
+  int32_t flags;          /* 1: final; 2: compact by the keep mask */
+  int32_t count_idx;      /* index into counts, or -1 */
+  int32_t reserved;
+} ctts_flac_push;         /* 64 bytes */
+int ctts_flac_stream_sizes(const ctts_flac_push* push_host, int32_t n_push, int32_t n_slots, int64_t n_pcm, int64_t* sizes);
+int ctts_flac_stream_step(const int16_t* pcm, int64_t n_pcm, const uint8_t* mask, const int64_t* counts, const ctts_flac_push* push_dev,
+                          const ctts_flac_push* push_host, int32_t n_push, int16_t* state, int32_t n_slots, uint8_t* out, size_t out_bytes,
+                          void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Full DVAE (asset/DVAE.safetensors): audio -> 4 x T codes and codes -> mel through the GFSQ codebook.
  * Replaces `self.dvae(wav, "encode")` of `Chat.sample_audio_speaker` (ChatTTS/core.py:179-180 ->

@@ -8,9 +8,16 @@
                 launches) from events around `--reps` back-to-back calls on pre-uploaded tables, for a speech-like signal (a noise-driven
                 resonance, tests/flac_cases.py's "ar2" recipe) and for full-scale noise (every frame VERBATIM), with the ratio of each
 
-Every file is checked against `flac.bound(n)`.  Prints one JSON line.  Not a bench.py leg.
+  * --stream  : streamed FLAC instead (ctts_flac_stream_step behind `CodecEngine.decode_windows(flac=)`):
+                poll  -- one poll of 1, 8 and 32 streams, each due a 24-token chunk (12,000 samples of a 48-token prefix), through
+                         `decode_windows` without `flac=` and with it, the two alternating call by call: the median wall time of each and
+                         the spread (min .. max) of the calls, and the bytes `to_host` brought back per call either way
+                size  -- one speech-like utterance of 10 s pushed in 12,000-sample chunks (the server's) and in 3,000-sample chunks: the
+                         stream's bytes, header included, against `flac.encode` of the same samples (fixed blocks of 4096)
 
-    python tools/flac_probe.py [--reps 20] [--gemm f16]
+Every file is checked against `flac.bound(n)`, every pushed chunk against `flac.stream_bound(n)`.  Prints one JSON line.  Not a bench.py leg.
+
+    python tools/flac_probe.py [--reps 20] [--gemm f16] [--stream]
 """
 from __future__ import annotations
 
@@ -90,10 +97,64 @@ def _wall_ms(fn, reps: int):
     return round(float(np.median(ts)), 3), res
 
 
+def _stream_probe(codec, reps: int) -> dict:
+    dev = codec.device
+    out = dict(poll={}, size={})
+    g = torch.Generator(device=dev).manual_seed(3)
+    store = torch.randn((32, 64, 768), device=dev, generator=g) * 0.5
+    copied = [0]
+    to_host = codec.to_host
+
+    def counting(t):
+        copied[0] += t.numel() * t.element_size()
+        return to_host(t)
+    codec.to_host = counting
+    try:
+        for S in (1, 8, 32):
+            wins = [(s, 48, 12000, 24000, False) for s in range(S)]
+            hs = [codec.flac_stream_open(24000) for _ in range(S)]
+            calls = {"pcm16": lambda: codec.decode_windows(store, wins, pcm16=True, keep_thr=1e-5),
+                     "flac": lambda: codec.decode_windows(store, wins, pcm16=True, keep_thr=1e-5, flac=[True] * S, flac_streams=hs)}
+            for _ in range(3):
+                for fn in calls.values():
+                    res = fn()
+            torch.cuda.synchronize()
+            ts, nbytes = {k: [] for k in calls}, {}
+            for _ in range(reps):
+                for k, fn in calls.items():                    # alternating: both see the same neighbours on the machine
+                    copied[0] = 0
+                    t0 = time.perf_counter()
+                    res = fn()
+                    ts[k].append((time.perf_counter() - t0) * 1e3)
+                    nbytes[k] = copied[0]
+                    if k == "flac":
+                        assert all(r.dtype == np.uint8 and r.size <= flac.stream_bound(12000) for r in res)
+            for h in hs:
+                codec.flac_stream_close(h)
+            out["poll"][f"streams{S}"] = {k: dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3),
+                                                 to_host_bytes=nbytes[k]) for k, v in ts.items()}
+    finally:
+        codec.to_host = to_host
+    sig = _speech_like(SEG, 7)
+    file_bytes = len(flac.encode(sig, 24000))
+    pcm = torch.from_numpy(sig).to(dev)
+    for chunk in (12000, 3000):
+        h = codec.flac_stream_open(24000)
+        total = flac.HEADER_BYTES
+        for lo in range(0, SEG, chunk):
+            n = min(chunk, SEG - lo)
+            total += codec.flac_stream_step(pcm, [(h, lo, n, lo + n == SEG)])[0].size
+        codec.flac_stream_close(h)
+        out["size"][f"chunks_of_{chunk}"] = dict(stream_bytes=total, file_bytes=file_bytes, pcm16_bytes=2 * SEG,
+                                                 stream_over_file=round(total / file_bytes, 4))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--gemm", default="f16")
+    ap.add_argument("--stream", action="store_true", help="streamed FLAC: one poll with and without it, and the stream's size")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("flac_probe needs a GPU: nothing here can be timed without one")
@@ -102,6 +163,9 @@ def main():
     chat = Chat()
     assert chat.load(state_dicts={k: sds[k] for k in ("gpt", "embed", "decoder", "vocos")}, device=dev, dtype="f32", codec_gemm=a.gemm)
     codec = chat.codec
+    if a.stream:
+        print(json.dumps(dict(metric="flac_stream_probe", codec_gemm=a.gemm, reps=a.reps, **_stream_probe(codec, a.reps))))
+        return
     out = dict(metric="flac_probe", segment_samples=SEG, tokens_per_row=TOKENS, codec_gemm=a.gemm, reps=a.reps, decode={}, encode={})
     g = torch.Generator(device=dev).manual_seed(3)
     for B in (1, 8):
