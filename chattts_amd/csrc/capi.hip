@@ -1757,6 +1757,69 @@ extern "C" int ctts_k_prefill_compact(const float* emb, float* x, int32_t* desc,
   CK(launch_prefill_compact(emb, x, reinterpret_cast<RowDesc*>(desc), last_row, B, T, kv_start, (hipStream_t)stream));
   return 0;
 }
+// ---- ... and its readers at the end of the step (tests/test_gpu_step_back.py) --------------------------------------------------------
+// final_norm_k with every argument of launch_final_norm
+extern "C" int ctts_k_final_norm_rows(const float* x, int32_t q_per_b, const float* w, float eps, float* hfin, float* hiddens, int32_t max_new,
+                                      const int32_t* len, int32_t T, int32_t B, const int32_t* row_map, const int32_t* n_active,
+                                      const int32_t* prompt_len, float* hfin_packed, const int32_t* last_row, void* stream) {
+  const char* who = "ctts_k_final_norm_rows";
+  if (!x || !w || !hfin || !len || B <= 0 || q_per_b <= 0 || T < 0) return fail("%s: bad arguments", who);
+  if (hiddens && max_new <= 0) return fail("%s: hiddens needs max_new > 0", who);
+  if (n_active && q_per_b != 1) return fail("%s: n_active belongs to the decode layout (q_per_b = 1)", who);
+  if (last_row && n_active) return fail("%s: last_row belongs to the prompt pass, n_active to the decode step", who);
+  CK(launch_final_norm(x, q_per_b, w, eps, hfin, hiddens, max_new, len, T, B, row_map, n_active, prompt_len, (hipStream_t)stream, hfin_packed,
+                       last_row));
+  return 0;
+}
+// the decode step's one-launch final RMSNorm + hidden capture + heads (decode32.hip gemm_dec32_fnorm16_k): launch_gemm_dec32 with fnorm = 1,
+// K = 768, EPI_STORE
+extern "C" int ctts_k_fnorm_heads(const float* Ap, const float* Wp, int32_t M, int32_t N, int32_t n_cols, const int32_t* n_active,
+                                  const float* norm_w, float eps, float* C, int32_t ldc, const int32_t* desc, float* hid, int32_t hid_cap,
+                                  int32_t T, const int32_t* prompt_len, void* stream) {
+  const char* who = "ctts_k_fnorm_heads";
+  if (!Ap || !Wp || !norm_w || !C || M <= 0) return fail("%s: bad arguments", who);
+  if (N <= 0 || (N & 15) || n_cols <= 0 || n_cols > N || ldc < n_cols) return fail("%s: N is a multiple of 16, 0 < n_cols <= N, ldc >= n_cols", who);
+  if (hid && (!desc || hid_cap <= 0)) return fail("%s: the hidden capture needs desc and hid_cap > 0", who);
+  if (prompt_len && !hid) return fail("%s: prompt_len is read by the hidden capture only", who);
+  Dec32Args d;
+  memset(&d, 0, sizeof(d));
+  d.Ap = Ap; d.Wp = Wp; d.M = M; d.N = N; d.K = HID; d.n_active = n_active; d.epi = EPI_STORE; d.C = C; d.ldc = ldc; d.n_cols = n_cols;
+  d.fnorm = 1; d.norm_w = norm_w; d.eps = eps; d.desc = reinterpret_cast<const RowDesc*>(desc); d.hid = hid; d.hid_cap = hid_cap; d.T = T;
+  d.prompt_len = prompt_len;
+  CK(launch_gemm_dec32(d, (hipStream_t)stream));
+  return 0;
+}
+// the sampler on compact rows: launch_sample (n_text > 0: launch_sample_text) over a grid of `rows` logits rows, the state as in
+// ctts_k_sample, the rows from desc or from row_map + n_active; x != NULL: with the next step's first kernel folded in (EmbedNext) -- its
+// StepPrep as ctts_k_step_prep takes it, host compaction only
+extern "C" int ctts_k_sample_rows(const ctts_gen_state* s, const float* logits, int32_t n_text, int32_t rows, const int32_t* row_map,
+                                  const int32_t* n_active, const int32_t* desc, const float* emb_code, float* x, uint16_t* xb, float* ssq,
+                                  int32_t* desc_out, const int32_t* kv_start, int32_t xb_packed, float* xp32, int64_t xb_lo_plane,
+                                  float* rope_cs, const float* cos_tab, const float* sin_tab, void* stream) {
+  const char* who = "ctts_k_sample_rows";
+  if (!s || !logits || rows <= 0 || n_text < 0 || n_text > NTEXT_MAX) return fail("%s: bad arguments", who);
+  if (rows > s->B) return fail("%s: more rows (%d) than utterance slots (%d)", who, rows, s->B);
+  if (!s->ids_buf || !s->len || !s->finish || !s->end_idx) return fail("%s: ids_buf, len, finish and end_idx are needed", who);
+  if (!s->rng_device && (s->nq <= 0 || !s->q)) return fail("%s: q draws missing", who);
+  if (n_text > 0 && desc) return fail("%s: the text sampler reads no descriptors", who);
+  if (!x && (emb_code || xb || ssq || desc_out || xp32 || rope_cs)) return fail("%s: outputs of the fold without x", who);
+  SampleArgs a = make_sample_args(s, logits);
+  a.B = rows; a.row_map = row_map; a.n_active = n_active; a.desc = reinterpret_cast<const RowDesc*>(desc);
+  if (x) {
+    if (n_text > 0) return fail("%s: the text sampler has no fold", who);
+    if (!emb_code) return fail("%s: the fold needs emb_code", who);
+    if (!desc || !desc_out) return fail("%s: the fold needs descriptors in and out", who);
+    if (!kv_start) return fail("%s: the fold needs kv_start", who);
+    if (rope_cs && (!cos_tab || !sin_tab)) return fail("%s: rope_cs needs the cos / sin tables", who);
+    if (xb_lo_plane < 0 || (xb_lo_plane & 7) || (xb_lo_plane && (!xb || !xb_packed))) return fail("%s: the lo plane needs a packed xb, a multiple of 8 elements behind it", who);
+    a.next.emb_code = emb_code; a.next.x = x; a.next.xb = xb; a.next.ssq = ssq;
+    a.next.sp = StepPrep{reinterpret_cast<RowDesc*>(desc_out), kv_start, nullptr, xb_packed ? 1 : 0, xp32, nullptr, nullptr, nullptr, rope_cs, cos_tab, sin_tab,
+                         nullptr, 0, 1, (size_t)xb_lo_plane};
+  }
+  if (n_text > 0) CK(launch_sample_text(a, n_text, (hipStream_t)stream));
+  else CK(launch_sample(a, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_k_gemm_pre32(const float* Ap, const float* Wp, int32_t M, int32_t N, int32_t K, const float* X, int32_t ldx, const float* norm_w,
                                  float eps, float* rstd, int32_t epi, float* C, int32_t ldc, const float* res, int32_t ldr, float* Cp,
                                  int32_t kch_out, const int32_t* desc, const float* cos_tab, const float* sin_tab, float* kcache, float* vcache,

@@ -822,7 +822,8 @@ int ctts_k_gemm_dec32x(const uint16_t* Ap, int64_t a_plane, const uint16_t* Wp, 
  * N % 128 == 0 (epi 2: % 64).  Reference ops: HF Llama projections, examples/onnx/modeling_llama.py:259-295,455-505. */
 int ctts_k_gemm_pre_x3(const float* A, int32_t lda, const float* W, float* C, int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t epi,
                        const float* norm_w, const float* rstd, const float* res, int32_t ldr, void* stream);
-/* which decode32 kernel the calling thread's last ctts_k_gemm_dec32 / decode step picked: "rms16" | "m16" | "generic" (all bit-identical) */
+/* which decode32 kernel the calling thread's last ctts_k_gemm_dec32 / decode step picked: "rms16" | "m16" | "generic" (all bit-identical), or "fnorm16"
+ * (the fused final norm + heads launch) */
 const char* ctts_k_dec32_last_variant(void);
 int ctts_k_rows_prep(const float* x32, uint16_t* xb, float* ssq, int32_t M, void* stream);
 int ctts_k_rope_append(float* qkv, void* kcache, void* vcache, int32_t kv_dtype, int32_t cmax, const float* cos_tab, const float* sin_tab,
@@ -904,6 +905,28 @@ int ctts_k_sample(const ctts_gen_state* s, const float* logits, void* stream);
 /* the refine-text sampler alone (sample_text_k, gpt.py:439-440,477-525): logits [B, n_text], q [nq, B, n_text], temperature[0], ONE
  * sampling row per utterance, the token replicated over the 4 slots; no repetition penalty */
 int ctts_k_sample_text(const ctts_gen_state* s, const float* logits, int32_t n_text, void* stream);
+/* The readers of the row descriptors at the end of a decode step, kernel by kernel (tests/test_gpu_step_back.py).
+ * ctts_k_final_norm_rows: ctts_k_final_norm with the rest of final_norm_k's arguments -- row_map (compact row -> utterance, NULL: identity),
+ * n_active (device scalar, q_per_b = 1 only; NULL: B rows), prompt_len [slots] (NULL: T for all), hfin_packed (the same rows in the packed
+ * f32 order of csrc/decode32.hip, or NULL), last_row [B] (row of utterance m's last prompt token after ctts_k_prefill_compact, or NULL). */
+int ctts_k_final_norm_rows(const float* x, int32_t q_per_b, const float* w, float eps, float* hfin, float* hiddens, int32_t max_new,
+                           const int32_t* len, int32_t T, int32_t B, const int32_t* row_map, const int32_t* n_active, const int32_t* prompt_len,
+                           float* hfin_packed, const int32_t* last_row, void* stream);
+/* final RMSNorm + hidden capture + heads as the decode step launches them (csrc/decode32.hip gemm_dec32_fnorm16_k, K = 768): Ap = the
+ * UN-normalised rows, Wp = the heads, both in the packed f32 order (N padded to a multiple of 16, n_cols columns exist); C [M, ldc] row-major;
+ * hid [slots, hid_cap, 768] != NULL: row m's normalised row also goes to hid[desc[m].b][desc[m].slot + 1 - (prompt_len ? prompt_len[b] : T)]
+ * when desc[m].b >= 0 and that index is in [0, hid_cap).  ctts_k_dec32_last_variant() says "fnorm16" afterwards. */
+int ctts_k_fnorm_heads(const float* Ap, const float* Wp, int32_t M, int32_t N, int32_t n_cols, const int32_t* n_active, const float* norm_w,
+                       float eps, float* C, int32_t ldc, const int32_t* desc, float* hid, int32_t hid_cap, int32_t T, const int32_t* prompt_len,
+                       void* stream);
+/* ctts_k_sample (n_text > 0: ctts_k_sample_text) on COMPACT rows: a grid of `rows` <= s->B logits rows; row m samples utterance desc[m].b at
+ * length desc[m].slot + 1 (b = -1: the row does not exist), or without desc utterance row_map[m] (NULL: m) while m < *n_active (NULL: rows).
+ * x != NULL (codes only, needs desc, desc_out and kv_start): the next step's first kernel folded into the launch (csrc/kernels.hpp
+ * EmbedNext) -- emb_code [4, 626, 768] and the outputs x, xb, ssq, desc_out, xb_packed, xp32, xb_lo_plane, rope_cs as ctts_k_step_prep. */
+int ctts_k_sample_rows(const ctts_gen_state* s, const float* logits, int32_t n_text, int32_t rows, const int32_t* row_map, const int32_t* n_active,
+                       const int32_t* desc, const float* emb_code, float* x, uint16_t* xb, float* ssq, int32_t* desc_out, const int32_t* kv_start,
+                       int32_t xb_packed, float* xp32, int64_t xb_lo_plane, float* rope_cs, const float* cos_tab, const float* sin_tab,
+                       void* stream);
 /* the device generator's Exp(1) draws (ctts_gen_state.rng_device) of sampling rows row0 .. row0+rows-1 at generation step `step`
  * as a [rows, V] float32 tensor -- distribution tests */
 int ctts_k_exp_draws(uint64_t seed, int32_t step, int32_t row0, int32_t rows, int32_t V, float* out, void* stream);

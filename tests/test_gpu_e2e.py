@@ -1764,6 +1764,26 @@ def test_fused_final_norm_heads_is_bit_identical(weights, golden, monkeypatch, d
         assert x.shape == y.shape and torch.equal(x, y)
 
 
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_embed_fold_is_bit_identical(weights, golden, monkeypatch, dtype):
+    """multi-step graphs with the next step's first kernel folded into sample_k's tail (CTTS_EMBED_FOLD=1: steps 2 .. 8 of a group take
+    their input rows and descriptors from the previous step's sampling launch, kernels.hpp EmbedNext) vs the default, where every step
+    launches embed_codes_k: token ids AND the captured hidden states are bit-identical, in both numeric modes (rows finishing at
+    different steps -- inside a group their compact rows go dead instead of being re-ranked -- and left padding)."""
+    c = cases.GEN_CASES["b8"]
+    plain = E.GptEngine(weights["gpt"], weights["embed"], DEV, dtype=dtype)
+    a, _ = run_case(plain, c, use_graph=True)
+    monkeypatch.setenv("CTTS_EMBED_FOLD", "1")
+    fold = E.GptEngine(weights["gpt"], weights["embed"], DEV, dtype=dtype)
+    monkeypatch.delenv("CTTS_EMBED_FOLD")
+    b, _ = run_case(fold, c, use_graph=True)
+    assert len(a[-1].ids) == len(b[-1].ids) == 8
+    for x, y in zip(a[-1].ids, b[-1].ids):
+        assert torch.equal(x, y)
+    for x, y in zip(a[-1].hiddens, b[-1].hiddens):
+        assert x.shape == y.shape and torch.equal(x, y)
+
+
 def test_pipelined_batches_equal_sequential(weights):
     """`Chat.infer_ids_pipelined` (acoustic decode + D2H of batch i on the codec engine's side stream while batch i+1 is generated,
     `CodecEngine.decode_to_wavs_async`) yields, per batch and in order, exactly what `Chat.infer_ids` returns for that batch --

@@ -7,8 +7,8 @@ The reference is a numpy restatement of the contract (tests/gpu_util.py `row_des
 sums of squares have a bound.  Every output buffer starts as NaN or a sentinel word: a slot the kernel must not write is compared
 with that, a slot it skipped cannot pass.
 
-Not covered here: the `EmbedNext` fold in `sample_k`'s tail (CTTS_EMBED_FOLD, off by default) -- the one remaining writer of
-descriptors without a kernel test."""
+The readers of the descriptors at the end of the step -- `final_norm_k`, the fused final norm + heads, the samplers -- and the one
+remaining writer, the `EmbedNext` fold in `sample_k`'s tail (CTTS_EMBED_FOLD), are in tests/test_gpu_step_back.py."""
 import functools
 
 import numpy as np
