@@ -25,6 +25,7 @@ import torch
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
+from . import pauses as PA
 from . import resample as RS
 from . import timescale as TS
 from . import weights as W
@@ -89,6 +90,17 @@ def _loudness_kw(loudness) -> dict:
     if all(v is None for v in vals):
         return {}
     return {"loudness": vals[0] if np.ndim(loudness) == 0 else vals}
+
+
+def _pauses_kw(pauses) -> dict:
+    """the decode calls' `pauses=` argument: nothing for None, alone or everywhere (today's call, argument for argument); ValueError
+    for a bad spec (pauses.check)"""
+    if pauses is None:
+        return {}
+    vals = [PA.check(v) for v in (list(pauses) if isinstance(pauses, (list, tuple)) else [pauses])]
+    if all(v is None for v in vals):
+        return {}
+    return {"pauses": vals if isinstance(pauses, (list, tuple)) else vals[0]}
 
 
 def split_sentences(text: str) -> List[str]:
@@ -302,7 +314,7 @@ class Chat:
             24, params.manual_seed, self.context, **kw))
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None, *,
-                       ragged: bool = False, sample_rate=None, speed=None, loudness=None):
+                       ragged: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None):
         """`Chat._decode_to_wavs` (core.py:513-539) -> np.float32 [B, n]: per-row hidden states [T_b,768] through the
         decoder, or (use_decoder=False) per-row token ids [T_b,4] through the full DVAE's codebook; then Vocos.
         `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded).
@@ -313,9 +325,14 @@ class Chat:
         24 kHz, behind the ISTFT and in front of the resampler.
         `loudness` (None: untouched; a target in LUFS, -40 .. -5, also one per row, None entries left alone): every row is brought to
         that BS.1770 integrated loudness on the device (CodecEngine.loudness_normalize), under the +30 dB cap and the -1 dBFS ceiling:
-        the last float32 stage, behind the time scaler and the resampler."""
+        the last float32 stage, behind the time scaler and the resampler.
+        `pauses` (None: untouched; True, a pauses.PauseSpec or a dict of its fields, also a list with one per row, None entries copied
+        through): every row loses the silence at its edges and the middle of its long pauses on the device
+        (CodecEngine.trim_pauses), behind the resampler and in front of the loudness stage.  The rows' lengths then differ: the
+        result is a List[np.ndarray] also without `ragged`."""
         skw = _speed_kw(speed)
         lkw = _loudness_kw(loudness)
+        pkw = _pauses_kw(pauses)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
@@ -324,10 +341,13 @@ class Chat:
                 raise ValueError("ragged decoding decodes every row at its own length: pad_to does not apply")
             if len(result_list) == 0:
                 return []
-            wav, off = self.codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw)
+            wav, off = self.codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw, **pkw)
             return ragged_views(self.codec.to_host(wav), off)
         if len(result_list) == 0:
             return np.array([], dtype=np.float32)
+        if pkw:
+            wav, off = self._decode_batch_trimmed(result_list, use_decoder, pad_to, sample_rate, skw, lkw, pkw["pauses"])
+            return ragged_views(self.codec.to_host(wav), off)
         if use_decoder:
             return self.codec.to_host(self.codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate, **skw, **lkw))
         wav = self.codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to))
@@ -339,9 +359,26 @@ class Chat:
             wav = self.codec.loudness_normalize(wav, lkw["loudness"], rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         return self.codec.to_host(wav)
 
+    def _decode_batch_trimmed(self, result_list, use_decoder: bool, pad_to, sample_rate, skw: dict, lkw: dict, pauses):
+        """the zero-padded batch decode of the plain calls with the pause stage behind it: time scaler, resampler, `trim_pauses` (every
+        row alone), loudness -> (packed float32 device tensor, host offsets), the ragged decoder's layout"""
+        codec = self.codec
+        if use_decoder:
+            return codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate, **skw, **lkw, pauses=pauses)
+        wav = codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to))
+        if skw:
+            wav = codec.time_scale(wav, skw["speed"])
+        if sample_rate is not None:
+            wav = codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
+        rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
+        wav, off = codec.trim_pauses(wav, pauses, rates=rate)
+        if lkw:
+            wav = codec.loudness_normalize(wav, lkw["loudness"], offsets=off, rates=rate, out=wav)
+        return wav, off
+
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
                         product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None,
-                        flac=None, loudness=None) -> List[np.ndarray]:
+                        flac=None, loudness=None, pauses=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
@@ -359,22 +396,30 @@ class Chat:
         `loudness` (None: untouched; a target in LUFS, also one per row, None entries left alone): `wav` above is the waveform
         normalised on the device (CodecEngine.loudness_normalize) at the rate it is returned at -- behind the time scaler and the
         resampler, in front of the strip, the conversion, the companding and FLAC, so the -1 dBFS ceiling holds on exactly the samples
-        that are converted."""
+        that are converted.
+        `pauses` (None: untouched; True, a pauses.PauseSpec or a dict of its fields, also a list with one per row, None entries copied
+        through): `wav` above is the waveform with its edge silence trimmed and its long pauses capped on the device
+        (CodecEngine.trim_pauses), every row alone -- behind the resampler, in front of the loudness stage and everything behind it.
+        Without `ragged` the trimmed rows of the batch go on as a pack, through the ragged calls' conversion."""
         skw = _speed_kw(speed)
         lkw = _loudness_kw(loudness)
+        pkw = _pauses_kw(pauses)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
         flags = self._flac_flags(flac, len(result_list), encoding, per_row=ragged, who="decode_to_pcm16")
         if flags is not None:
-            return self._decode_to_flac(result_list, use_decoder, strip, product, ragged, sample_rate, flags, skw, encoding, **lkw)
+            return self._decode_to_flac(result_list, use_decoder, strip, product, ragged, sample_rate, flags, skw, encoding, **lkw, **pkw)
         if ragged:
             if encoding is None:
-                return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, **skw, **lkw)
-            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding, **skw, **lkw)
+                return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, **skw, **lkw, **pkw)
+            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding, **skw, **lkw, **pkw)
         G711.check_encoding(encoding)
         if len(result_list) == 0:
             return []
+        if pkw:
+            decoded = self._decode_batch_trimmed(result_list, use_decoder, None, sample_rate, skw, lkw, pkw["pauses"])
+            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding, decoded=decoded)
         wav = self.codec.decode_to_wavs(result_list) if use_decoder else self.codec.vocos_decode(self.dvae.decode_codes(result_list))
         if skw:
             wav = self.codec.time_scale(wav, skw["speed"])
@@ -424,7 +469,7 @@ class Chat:
         return flags
 
     def _decode_to_flac(self, result_list, use_decoder: bool, strip: bool, product: str, ragged: bool, sample_rate, flags, skw,
-                        encoding=None, loudness=None) -> List[np.ndarray]:
+                        encoding=None, loudness=None, pauses=None) -> List[np.ndarray]:
         """`decode_to_pcm16` with at least one row as a FLAC file: the decode of the plain call, then the grouped conversion with one
         group per row (the same samples; slots that start on multiples of 8 and a count header on the device) and the encoder behind it"""
         B = len(result_list)
@@ -433,9 +478,12 @@ class Chat:
         codec = self.codec
         lkw = {} if loudness is None else {"loudness": loudness}
         if ragged:
-            wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw)
+            wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw, **({} if pauses is None else {"pauses": pauses}))
             rates = [CodecEngine.SAMPLE_RATE] * B if sample_rate is None else ([int(sample_rate)] * B if np.ndim(sample_rate) == 0 else
                                                                                 [int(r) for r in sample_rate])
+        elif pauses is not None:
+            wav, off = self._decode_batch_trimmed(result_list, use_decoder, None, sample_rate, skw, lkw, pauses)
+            rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * B
         else:
             wav = codec.decode_to_wavs(result_list) if use_decoder else codec.vocos_decode(self.dvae.decode_codes(result_list))
             if skw:
@@ -454,23 +502,25 @@ class Chat:
         return [p if p.dtype == np.uint8 else p.copy() for p in out]
 
     def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None, speed=None,
-                                loudness=None) -> List[np.ndarray]:
+                                loudness=None, pauses=None, decoded=None) -> List[np.ndarray]:
         """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
         PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's result equals
         `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w.  `encoding` (one, or one per row; None entries stay int16): the
         companded rows are converted by one launch behind the conversion, and the codes travel with the keep masks in the one copy
-        (the PCM16 samples too when some row stays int16).  `speed` and `loudness` (one, or one per row) go to the ragged decode."""
+        (the PCM16 samples too when some row stays int16).  `speed`, `loudness` and `pauses` (one, or one per row) go to the ragged decode;
+        `decoded`: the (packed, offsets) of a decode that has run already (the trimmed rows of a zero-padded batch)."""
         if len(result_list) == 0:
             return []
         codec = self.codec
-        skw = {**({} if speed is None else {"speed": speed}), **({} if loudness is None else {"loudness": loudness})}
+        skw = {**({} if speed is None else {"speed": speed}), **({} if loudness is None else {"loudness": loudness}),
+               **({} if pauses is None else {"pauses": pauses}), **({} if decoded is None else {"decoded": decoded})}
         if encoding is not None:
             encs = [encoding] * len(result_list) if isinstance(encoding, str) else list(encoding)
             if len(encs) != len(result_list):
                 raise ValueError("decode_to_pcm16: one encoding per row, or one for all")
             if any(G711.check_encoding(e) is not None for e in encs):
                 return self._decode_to_g711_ragged(result_list, strip, product, sample_rate, encs, **skw)
-        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw)
+        wav, off = decoded if decoded is not None else codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw)
         n = wav.numel()
         kb = int(keep_offsets(off)[-1]) if strip else 0
         blob = torch.empty(((2 * n + kb + 15) // 16 * 16,), dtype=torch.uint8, device=wav.device)
@@ -485,14 +535,16 @@ class Chat:
         keep_h = host[2 * n: 2 * n + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
-    def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs, speed=None, loudness=None) -> List[np.ndarray]:
+    def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs, speed=None, loudness=None, pauses=None,
+                               decoded=None) -> List[np.ndarray]:
         """`_decode_to_pcm16_ragged` with at least one companded row.  The device buffer is int16 samples | codes | keep masks; rows
         that share a law and follow each other make one range.  A range starts on a multiple of 8 elements: rows resampled to
         another rate sit at arbitrary offsets, so a call that mixes laws over such rows goes through the grouped conversion instead
         (one group per row: the same bytes, slots that start on multiples of 8)."""
         codec = self.codec
-        wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **({} if speed is None else {"speed": speed}),
-                                       **({} if loudness is None else {"loudness": loudness}))
+        wav, off = decoded if decoded is not None else codec.decode_ragged(
+            list(result_list), sample_rate=sample_rate, **({} if speed is None else {"speed": speed}),
+            **({} if loudness is None else {"loudness": loudness}), **({} if pauses is None else {"pauses": pauses}))
         runs = []                     # [first row, one past the last, encoding]
         for i, e in enumerate(encs):
             if runs and runs[-1][2] == e:
@@ -521,7 +573,7 @@ class Chat:
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None,
-                              speed=None, flac=None, loudness=None) -> List[np.ndarray]:
+                              speed=None, flac=None, loudness=None, pauses=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
@@ -539,7 +591,10 @@ class Chat:
         slots and their count header (CodecEngine.float_to_int16_groups_flac); not together with `encoding`.
         `loudness` (None: untouched; a target in LUFS, or one per request, None entries left alone): a request gets ONE loudness and
         ONE gain over its sentences (CodecEngine.loudness_normalize with the group table of the conversion behind it): every sentence
-        is filtered alone, the gates run over all of the request's blocks, the peak is the request's."""
+        is filtered alone, the gates run over all of the request's blocks, the peak is the request's.
+        `pauses` (None: untouched; a pause spec, or a list with one per request, None entries copied through): every SENTENCE is
+        trimmed alone (CodecEngine.trim_pauses) behind the resampler, so the gap at a join is at most tail + lead; the request's one
+        gain is then computed over its trimmed sentences."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -564,7 +619,12 @@ class Chat:
         lkw = _loudness_kw(loudness)
         if lkw and np.ndim(loudness) != 0 and len(loudness) != len(groups):
             raise ValueError("decode_split_to_pcm16: one loudness target per request, or one for all")
-        wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate, **skw)
+        pkw = _pauses_kw(pauses)
+        if pkw and isinstance(pauses, (list, tuple)):
+            if len(pauses) != len(groups):
+                raise ValueError("decode_split_to_pcm16: one pause spec per request, or one for all")
+            pkw = {"pauses": [v for v, g in zip(pkw["pauses"], groups) for _ in g]}
+        wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate, **skw, **pkw)
         if lkw:
             wav = codec.loudness_normalize(wav, lkw["loudness"], offsets=off, groups=grp, out=wav,
                                            rates=[r for r, g in zip(rates, groups) for _ in g])
@@ -835,7 +895,7 @@ class Chat:
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
-              flac: bool = False, loudness=None, stream_flac: bool = False):
+              flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -896,7 +956,22 @@ class Chat:
         Every utterance is brought to that ITU-R BS.1770-4 integrated loudness on the device (CodecEngine.loudness_normalize) by one
         gain, capped at +30 dB and at a -1 dBFS sample peak: the last float32 stage, behind the time scaler and the resampler and in
         front of the silence strip, the 16-bit conversion, the companding and FLAC.  A split request gets ONE gain over its sentences
-        (one target only).  A streamed call with a target raises: an integrated loudness needs the whole utterance."""
+        (one target only).  A streamed call with a target raises: an integrated loudness needs the whole utterance.
+        `pauses` (keyword-only, non-streamed only; None: untouched): True (the defaults), a pauses.PauseSpec or a dict of its fields
+        (max_pause_ms, lead_ms, tail_ms, threshold_db, pad_ms) -- one, or a list with one per text.  Every utterance loses the
+        near-silence in front of and behind it down to lead_ms / tail_ms, and an inner pause longer than max_pause_ms keeps its two
+        ends, crossfaded (CodecEngine.trim_pauses, on the device): behind the time scaler and the resampler, so the milliseconds are
+        those of what is heard, and in front of the loudness stage, the silence strip, the 16-bit conversion, the companding and
+        FLAC.  Every sentence of a split request is trimmed alone (one spec only), so the gap at a join is at most tail + lead; with
+        `loudness` the request still gets ONE gain, over its trimmed sentences.  A streamed call with it raises: the run state would
+        have to be carried across chunks."""
+        pkw = _pauses_kw(pauses)
+        if pkw and stream:
+            raise ValueError("pauses applies to non-streamed inference only (a stream would need the run state carried across chunks)")
+        if pkw and split_text and isinstance(pauses, (list, tuple)):
+            raise ValueError("a split_text request is one waveform: it takes one pause spec")
+        if pkw:
+            PA.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         lkw = _loudness_kw(loudness)
         if lkw and stream:
             raise ValueError("loudness applies to non-streamed inference only (an integrated loudness needs the whole utterance; a "
@@ -961,7 +1036,7 @@ class Chat:
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
                               sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}),
-                              **({} if split_host else lkw))
+                              **({} if split_host else lkw), **pkw)
         if stream:
             return res_gen
         if refine_text_only:
@@ -971,7 +1046,7 @@ class Chat:
             if rows:
                 return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}),
                                                   **({} if encoding is None else {"encoding": encoding}), **skw,
-                                                  **({"flac": True} if flac else {}), **lkw)
+                                                  **({"flac": True} if flac else {}), **lkw, **pkw)
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
@@ -1000,7 +1075,7 @@ class Chat:
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-               speed: Optional[float] = None, flac: bool = False, loudness=None):
+               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None):
         """core.py:395-503 (generator).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -1026,7 +1101,8 @@ class Chat:
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
                                            encoding, speed, ts, rs, **({"flac": True} if flac else {}),
-                                           **({} if loudness is None else {"loudness": loudness}), **({} if fs is None else {"fs": fs}))
+                                           **({} if loudness is None else {"loudness": loudness}), **({} if fs is None else {"fs": fs}),
+                                           **({} if pauses is None else {"pauses": pauses}))
         finally:
             for h in fs or ():
                 if not isinstance(h, FLAC.StreamEncoder):
@@ -1037,7 +1113,7 @@ class Chat:
                 self.codec.resample_stream_close(h)
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None, flac: bool = False, loudness=None, fs=None):
+                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None):
         """the batch loop of `_infer`"""
         def flac_chunks(piece, final):
             """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' FLAC
@@ -1087,6 +1163,8 @@ class Chat:
                         rkw["flac"] = True
                     if loudness is not None and not raw:
                         rkw["loudness"] = loudness
+                    if pauses is not None and not raw:
+                        rkw["pauses"] = pauses[lo: lo + step] if isinstance(pauses, list) else pauses
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
                         rows = [h.clone() for h in src]
                         result.destroy()

@@ -2088,6 +2088,50 @@ extern "C" int ctts_loudness_normalize_ragged(const float* x, float* y, const in
                                       stats, (double*)scratch, (float*)((char*)scratch + rec_bytes), (hipStream_t)stream));
   return 0;
 }
+extern "C" size_t ctts_trim_pauses_ragged_scratch_bytes(int64_t frames, int32_t n_seg) {
+  if (frames < 1 || frames >= (1ll << 31) || n_seg < 1 || n_seg > 65535) return 0;
+  return pause_scratch_bytes(frames, n_seg);
+}
+extern "C" int ctts_trim_pauses_ragged(const float* in, float* out, const int64_t* off_dev, const int64_t* off_host, const int64_t* fbase_dev,
+                                       const int64_t* fbase_host, const int32_t* rows_dev, const int32_t* rows_host, int32_t n_seg,
+                                       const float* fade_dev, int32_t n_fade, int64_t* off_out, int32_t* records, void* scratch,
+                                       size_t scratch_bytes, void* stream) {
+  const char* who = "ctts_trim_pauses_ragged";
+  if (!in || !out || !off_dev || !off_host || !fbase_dev || !fbase_host || !rows_dev || !rows_host || !fade_dev || !off_out || !records || !scratch)
+    return fail("%s: a null pointer (in, out, the offset, frame base and row tables on the device and the host, the fade table, off_out, the records and the scratch are needed)", who);
+  if (loudness_offsets_check(who, off_host, n_seg)) return -1;
+  const long long total = off_host[n_seg];
+  if (((uintptr_t)in & 15) || ((uintptr_t)out & 15) || ((uintptr_t)off_out & 7) || ((uintptr_t)records & 3) || ((uintptr_t)scratch & 15))
+    return fail("%s: in, out and the scratch must be 16-byte aligned, off_out 8-byte, the records 4-byte", who);
+  if (in < out + total && out < in + total) return fail("%s: out must not overlap in", who);
+  if (n_fade < 0) return fail("%s: the fade table's length is negative", who);
+  if (fbase_host[0] != 0) return fail("%s: the first frame base must be 0", who);
+  long long frames_max = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    const int32_t* r = rows_host + (size_t)i * PA_ROW;
+    const long long n = off_host[i + 1] - off_host[i];
+    if (r[0] < PA_FMIN || r[0] > PA_FMAX) return fail("%s: segment %d: a frame of %d samples (the rate is %d .. %d Hz)", who, i, r[0], 100 * PA_FMIN, 100 * PA_FMAX);
+    if (r[4] < 0 || r[4] > 1000 || r[1] < 0 || r[1] > 100 || r[2] < 0 || r[2] > 1000 || r[3] < 0 || r[3] > 1000)
+      return fail("%s: segment %d: pad 0 .. 100, lead and tail 0 .. 1000, P 0 (copy) .. 1000 frames (got %d, %d, %d, %d)", who, i, r[1], r[2], r[3], r[4]);
+    if (r[4] != 0) {
+      float thr;
+      memcpy(&thr, r + 5, 4);
+      if (!(thr >= 9e-6f && thr <= 1.0f)) return fail("%s: segment %d: the threshold is -100 .. 0 dB (got an amplitude of %g)", who, i, (double)thr);
+      if (r[6] < 0 || (long long)r[6] + r[0] > n_fade) return fail("%s: segment %d: its fade table [%d, %d) lies outside the %d floats given", who, i, r[6], r[6] + r[0], n_fade);
+    }
+    const long long nf = (n + r[0] - 1) / r[0];
+    if (fbase_host[i + 1] - fbase_host[i] != nf)
+      return fail("%s: segment %d: %lld samples in frames of %d are %lld frames, the frame bases say %lld", who, i, n, r[0], nf, (long long)(fbase_host[i + 1] - fbase_host[i]));
+    frames_max = std::max(frames_max, nf);
+  }
+  const long long frames = fbase_host[n_seg];
+  if (scratch_bytes < pause_scratch_bytes(frames, n_seg))
+    return fail("%s: scratch too small (%zu bytes, need %zu)", who, scratch_bytes, pause_scratch_bytes(frames, n_seg));
+  CttsDeviceGuard dg(stream);
+  CK(launch_trim_pauses_ragged(in, out, (const long long*)off_dev, (const long long*)fbase_dev, rows_dev, n_seg, frames_max, frames, fade_dev,
+                               (long long*)off_out, records, scratch, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_copy_bytes(void* dst,const void* src, size_t bytes, void* stream) {
   if (!dst || !src || (bytes & 15) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return fail("ctts_copy_bytes: pointers and size must be 16-byte aligned");
   CttsDeviceGuard dg(stream);

@@ -543,6 +543,26 @@ hipError_t launch_loudness_normalize_ragged(const float* x, float* y, const long
                                             int h_max, const int32_t* rate, const double* coef, const int32_t* grp, int n_grp, const double* target,
                                             void* stats, double* rec, float* seg_gain, hipStream_t st);
 
+// ---- pause control (pauses.hip) -------------------------------------------------------------------
+#define PA_FMIN 80            // a frame is F = fs / 100 samples (integer division): 8 kHz ..
+#define PA_FMAX 480           // .. 48 kHz
+#define PA_ROW 8              // int32 per segment row: F, pad, lead, tail, P (0: the segment is copied through), thr (float32 bits), fade offset, 0
+#define PA_REC 8              // int32 per segment record (pauses.RECORD)
+#define PA_FPW 8              // frames a wave of the activity pass reads as one span
+#define PA_FPB 16             // frames a workgroup of the copy pass handles, four per wave
+static inline size_t pause_r16(size_t b) { return (b + 15) & ~(size_t)15; }
+// device scratch of a call with `frames` frames in all: dst int32 [frames], mix int32 [frames], act uint8 [frames], len int32 [n_seg],
+// each region rounded up to 16 bytes (pauses.scratch_bytes)
+static inline size_t pause_scratch_bytes(long long frames, int n_seg) {
+  return 2 * pause_r16((size_t)frames * 4) + pause_r16((size_t)frames) + pause_r16((size_t)n_seg * 4);
+}
+// packed segments x[off[s], off[s+1]) with frame base fbase[s] (fbase[s+1] - fbase[s] = ceil(n_s / F_s)) and row rows[s] -> the kept frames
+// in order at y[off_out[s], off_out[s+1]), off_out and the records written on the device.  frames_max: the most frames of a segment (grid
+// sizes).  Four launches: activity, plan (one workgroup per segment), offsets (one workgroup), copy.  Every bound is the caller's to check
+hipError_t launch_trim_pauses_ragged(const float* x, float* y, const long long* off, const long long* fbase, const int32_t* rows, int n_seg,
+                                     long long frames_max, long long frames, const float* fade, long long* off_out, int32_t* records,
+                                     void* scratch, hipStream_t st);
+
 #define TS_CARRY 2560         // floats of one carry buffer of a stream slot; a slot has two (a step reads one and writes the other)
 #define TS_STATE_INTS 4       // int32 per slot of the state table: s_K, three reserved
 // ctts_ts_stream (include/chattts_amd.h), field for field (capi.hip asserts the layout): one push of one stream.  x[in_off, in_off + n_in)

@@ -22,6 +22,7 @@ from . import _lib
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
+from . import pauses as PA
 from . import resample as RS
 from . import timescale as TS
 from ._sync import wait_event, wait_stream
@@ -1893,8 +1894,62 @@ class CodecEngine:
             return y, work[: LN.STATS.itemsize * n_grp].cpu().numpy().view(LN.STATS)
         return y
 
+    # -- pause control (csrc/pauses.hip) ------------------------------------------------------------------------------------------------
+    def trim_pauses(self, wav: torch.Tensor, spec, offsets=None, rates=None, return_stats: bool = False):
+        """Trims the silence at every segment's edges and caps its inner pauses (ctts_trim_pauses_ragged; the definition of
+        pauses.py): 1-D (one signal) -> a tensor; [B, n] (rows, each alone) -> (packed, offsets); 1-D packed with `offsets` (n_seg + 1
+        sample offsets, the ragged decoder's layout) -> (packed, offsets), `offsets` a host int64 array.  `spec`: None, True (the
+        defaults), a `pauses.PauseSpec` or a dict of its fields -- one for all, or a list with one per segment; a segment whose spec is
+        None is copied through bit for bit, and with every spec None and no `return_stats` the input comes back untouched, with no
+        launch.  `rates`: the segments' sample rates in Hz (one, or one per segment; default 24000), 8000 .. 48000.  With
+        `return_stats` the segments' records follow (int32 [n_seg, 8], `pauses.RECORD`).  The output's length depends on the samples:
+        the call ends in ONE device-to-host copy of the new offsets and the records, its only synchronisation, however many segments
+        there are.  A segment's samples and record do not depend on what it is packed with.  ValueError before any launch: a bad spec,
+        a rate out of range, an empty segment, non-ascending offsets, 2^31 - 4096 samples, more than 65535 segments."""
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
+            raise ValueError("trim_pauses: a float32 device tensor, 1-D or [B, n]")
+        if offsets is not None and wav.dim() != 1:
+            raise ValueError("trim_pauses: offsets go with a packed 1-D tensor")
+        if wav.numel() == 0:
+            raise ValueError("trim_pauses: nothing to trim")
+        single = wav.dim() == 1 and offsets is None
+        if wav.dim() == 2:
+            offsets = np.arange(wav.shape[0] + 1, dtype=np.int64) * int(wav.shape[1])
+        tb = PA.tables(np.array([0, wav.numel()], dtype=np.int64) if offsets is None else offsets, rates, spec)
+        off, rows, fbase, fade = tb["off"], tb["rows"], tb["fbase"], tb["fade"]
+        if int(off[-1]) != wav.numel():
+            raise ValueError("trim_pauses: the offsets do not cover the tensor")
+        n_seg = len(off) - 1
+        if all(s is None for s in tb["specs"]) and not return_stats:
+            flat = wav.reshape(-1)
+            return flat if single else (flat, off)
+        x = wav.contiguous().view(-1)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        dev = wav.device
+        y = torch.empty_like(x)
+        tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), fbase.view(np.uint8), rows.reshape(-1).view(np.uint8), fade.view(np.uint8)])).to(dev)   # one upload
+        res_bytes = 8 * (n_seg + 1) + 4 * PA.REC * n_seg                                                  # off_out, then the records
+        work = torch.empty((-(-res_bytes // 16) * 16 + tb["scratch"],), dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev)
+        base, wp = tabs.data_ptr(), work.data_ptr()
+        _lib.check(self.lib.ctts_trim_pauses_ragged(
+            x.data_ptr(), y.data_ptr(), base, off.ctypes.data_as(C.c_void_p), base + off.nbytes, fbase.ctypes.data_as(C.c_void_p),
+            base + off.nbytes + fbase.nbytes, rows.ctypes.data_as(C.c_void_p), n_seg, base + off.nbytes + fbase.nbytes + rows.nbytes,
+            int(fade.size), wp, wp + 8 * (n_seg + 1), wp + -(-res_bytes // 16) * 16, tb["scratch"], st.cuda_stream), "ctts_trim_pauses_ragged")
+        tabs.record_stream(st)
+        work.record_stream(st)
+        x.record_stream(st)
+        res = work[:res_bytes].cpu().numpy()                                                              # the one copy, and the one wait
+        off_out = res[: 8 * (n_seg + 1)].view(np.int64).copy()
+        y = y[: int(off_out[-1])]
+        out = (y,) if single else (y, off_out)
+        if return_stats:
+            out = (*out, res[8 * (n_seg + 1):].view(np.int32).reshape(n_seg, PA.REC).copy())
+        return out[0] if len(out) == 1 else out
+
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
-    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None, loudness=None):
+    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None):
         """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
         packed frames (ctts_dvae_decode_ragged / ctts_vocos_decode_ragged): each utterance gets zero padding at its own edges in every
         convolution, so its audio does not depend on what else is in the call -- unlike `decode_to_wavs`, whose zero-padded [B, Tmax]
@@ -1912,9 +1967,29 @@ class CodecEngine:
         copied through).  It runs at 24 kHz, behind the ISTFT and in front of the resampler, every row as if alone.
         `loudness` (None: untouched): a target in LUFS -- one value, or one per row, None entries left alone.  The rows are
         normalised in place (`loudness_normalize`), each as a group of its own at its own rate: the last float32 stage, behind the
-        time scaler and the resampler."""
+        time scaler and the resampler.
+        `pauses` (None: untouched): a pause spec -- one, or a list with one per row, None entries copied through (`trim_pauses`, every
+        row alone at its own rate).  It runs behind the time scaler and the resampler and in front of the loudness stage, so the
+        milliseconds are those of what is heard and the gain is computed on what is delivered; `off` then holds the trimmed rows'
+        offsets, read back from the device in the call's one extra copy."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
+        specs = PA.per_row(pauses, len(rows), "decode_ragged")
+        if specs is not None:
+            rates = [self.SAMPLE_RATE] * len(rows) if sample_rate is None else \
+                [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
+            if len(rates) != len(rows):
+                raise ValueError("decode_ragged: one sample rate per row, or one for all")
+            targets = LN.per_row(loudness, len(rows), "decode_ragged")
+            for r in rates:                                           # every refusal, before the decode
+                PA.check_rate(r)
+                if targets is not None:
+                    LN.check_rate(r)
+            out = self.decode_ragged(rows, return_mel, sample_rate, speed)
+            wav, off = self.trim_pauses(out[0], specs, offsets=out[1], rates=rates)
+            if targets is not None:
+                self.loudness_normalize(wav, targets, offsets=off, rates=rates, out=wav)
+            return (wav, off, out[2]) if return_mel else (wav, off)
         targets = LN.per_row(loudness, len(rows), "decode_ragged")
         if targets is not None:
             rates = [self.SAMPLE_RATE] * len(rows) if sample_rate is None else \
@@ -2892,7 +2967,7 @@ class CodecEngine:
         return out
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None, sample_rate: Optional[int] = None,
-                       speed: Optional[float] = None, loudness=None) -> torch.Tensor:
+                       speed: Optional[float] = None, loudness=None, pauses=None) -> torch.Tensor:
         """`Chat._decode_to_wavs` (core.py:513-539): zero-pad the per-row [T_b,768] hidden lists to the
         longest row, DVAE decode, Vocos decode -> [B, 256(2Tmax-1)] float32 on the device.  `pad_to`: pad to that many tokens instead
         (>= the longest row): a data-parallel shard decodes its rows as part of the GLOBAL batch (dist.infer_sharded) -- the reference
@@ -2900,9 +2975,22 @@ class CodecEngine:
         that rate on the device, directly behind the ISTFT (`resample`) -> [B, ceil(n * new / 24000)].  `speed` (None: 1.0): the rows
         are time-scaled at 24 kHz (`time_scale`), each alone, behind the ISTFT and in front of the resampler.  `loudness` (None:
         untouched): a target in LUFS, one value or one per row (None entries left alone) -- every row, padding and all, is normalised
-        alone (`loudness_normalize`) at the returned rate, the last float32 stage."""
+        alone (`loudness_normalize`) at the returned rate, the last float32 stage.  `pauses` (None: untouched): a pause spec, one or
+        a list with one per row (None entries copied through) -- every row, padding and all, is trimmed alone (`trim_pauses`) at the
+        returned rate, behind the resampler and in front of the loudness stage, and the result is then (packed, offsets) instead of
+        [B, n]: the rows' lengths differ."""
         if len(result_list) == 0:
             return torch.empty((0,), dtype=torch.float32)
+        specs = PA.per_row(pauses, len(result_list), "decode_to_wavs")
+        if specs is not None:
+            rate = PA.check_rate(self.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+            targets = LN.per_row(loudness, len(result_list), "decode_to_wavs")
+            if targets is not None:
+                LN.check_rate(rate)                                   # every refusal, before the decode
+            wav, off = self.trim_pauses(self.decode_to_wavs(result_list, pad_to, sample_rate, speed), specs, rates=rate)
+            if targets is not None:
+                self.loudness_normalize(wav, targets, offsets=off, rates=rate, out=wav)
+            return wav, off
         targets = LN.per_row(loudness, len(result_list), "decode_to_wavs")
         if targets is not None:
             rate = LN.check_rate(self.SAMPLE_RATE if sample_rate is None else int(sample_rate))

@@ -96,7 +96,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                batch_slots: Optional[int] = None, batcher=None, ragged_decode: bool = False, batch_streams: bool = False,
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
-               stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False):
+               stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
+               pauses: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -155,7 +156,14 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     (-40 .. -5) -- the utterance is brought to that ITU-R BS.1770-4 integrated loudness on the device, under a +30 dB cap and a -1 dBFS
     ceiling, in front of the 16-bit conversion (Chat.infer(loudness=) / SpeechBatcher.submit(loudness=)), in whatever format, rate and
     speed the other options allow; a value that is no number or out of range gets a 400, `"stream": true` with it too (an integrated
-    loudness needs the whole utterance), and /health carries `"loudness": true`."""
+    loudness needs the whole utterance), and /health carries `"loudness": true`.  `pauses=True` (default off: every response, status,
+    warning and /health list is as without it, a `"pauses"` key is ignored with the "unsupported parameters" warning): a non-streamed
+    request body may carry `"pauses"`: true (the defaults) or an object with any of `max_pause_ms`, `lead_ms`, `tail_ms`,
+    `threshold_db`, `pad_ms` (chattts_amd/pauses.py) -- the silence in front of and behind the utterance is trimmed and its long pauses
+    are capped on the device, in front of the loudness stage and the 16-bit conversion (Chat.infer(pauses=) /
+    SpeechBatcher.submit(pauses=)), in whatever format, rate and speed the other options allow; false or null leaves the audio alone;
+    a wrong type, an unknown field or a value out of range gets a 400, `"stream": true` with it too (the run state is not carried
+    across chunks), and /health carries `"pauses": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -226,6 +234,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     if loudness:
         from . import loudness as LN
         allowed = allowed | {"loudness"}
+    if pauses:
+        from . import pauses as PA
+        allowed = allowed | {"pauses"}
 
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
         model: str = "tts-1"
@@ -250,8 +261,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     stream_speed=12000, pass_first_n_batches=2)
 
     def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None,
-              as_flac: bool = False, lufs: Optional[float] = None):                # openai_api.py:168-183,207-222
+              as_flac: bool = False, lufs: Optional[float] = None, trim=None):     # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if trim is not None:
+            kw = {**kw, "pauses": trim}
         if lufs is not None:
             kw = {**kw, "loudness": lufs}
         if as_flac:
@@ -323,6 +336,19 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             if req.stream:
                 raise HTTPException(400, detail=f"loudness {lufs} is served for non-streamed requests only: an integrated loudness needs "
                                                 f"the whole utterance (a stream would need a running measure)")
+        trim = None                                  # the request's pause spec where it is honoured
+        if pauses and request_data.get("pauses") is not None and request_data["pauses"] is not False:
+            spec = request_data["pauses"]
+            if spec is not True and not isinstance(spec, dict):
+                raise HTTPException(400, detail=f"pauses is true or an object with any of {', '.join(PA.RANGES)} (got {spec!r})")
+            try:
+                trim = PA.check(spec)
+                PA.check_rate(rate)
+            except ValueError as e:
+                raise HTTPException(400, detail=str(e))
+            if req.stream:
+                raise HTTPException(400, detail="pauses is served for non-streamed requests only: a stream would need the run state "
+                                                "carried across chunks")
         refine = refine_of(request_data)
         rkw = {} if refine is None else {"refine": refine}
         if refine is not None and req.stream and not pool_streams:
@@ -422,13 +448,17 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     rkw = {**rkw, "speed": spd}
                 if lufs is not None:
                     rkw = {**rkw, "loudness": lufs}
+                if trim is not None:
+                    rkw = {**rkw, "pauses": trim}
                 wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw, **ekw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:
             async with app.state.model_lock:
                 try:
-                    if lufs is not None:
+                    if trim is not None:
+                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim)
+                    elif lufs is not None:
                         wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs)
                     elif as_flac:
                         wavs = await run_in_threadpool(infer, req, rate, None, spd, True)
@@ -482,6 +512,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["loudness"] = True
         if flac_streams:
             out["stream_flac"] = True
+        if pauses:
+            out["pauses"] = True
         return out
 
     return app

@@ -42,6 +42,7 @@ from . import _lib
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
+from . import pauses as PA
 from . import resample as RS
 from . import timescale as TS
 from ._sync import wait_event, wait_stream
@@ -664,6 +665,7 @@ class _Job:
     flac: bool = False                     # the result is the FLAC file of the int16 waveform; a stream: its chunks are FLAC frames
     flac_slot: Optional[int] = None        # a FLAC stream: its stream of the encoder, opened at its first chunk
     loudness: Optional[float] = None       # a target in LUFS (non-streamed only); None: the level is left alone
+    pauses: object = None                  # a pauses.PauseSpec (non-streamed only); None: the silence is left alone
 
     @property
     def is_stream(self) -> bool:
@@ -715,6 +717,8 @@ def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding"
         kw["flac"] = [j.flac for j in jobs]
     if any(j.loudness is not None for j in jobs):
         kw["loudness"] = [j.loudness for j in jobs]
+    if any(j.pauses is not None for j in jobs):
+        kw["pauses"] = [j.pauses for j in jobs]
     return kw
 
 
@@ -797,6 +801,7 @@ class SpeechBatcher:
         self.stream_flac_chunks = 0        # chunks handed out as FLAC frames (empty ones included)
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.flac_encoded = 0              # results handed out as FLAC files
+        self.trimmed = 0                   # results handed out with their pauses trimmed
         self.max_stream_group = 0     # most chunks one window decode served
         self.cancelled = 0            # streams closed by their consumer before the end
         self.log = logger or logging.getLogger("chattts_amd.serving")
@@ -842,7 +847,7 @@ class SpeechBatcher:
 
     # -- public -------------------------------------------------------------------------------------------------------------
     def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None,
-               encoding=None, speed=None, flac: bool = False, loudness=None) -> Future:
+               encoding=None, speed=None, flac: bool = False, loudness=None, pauses=None) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
@@ -862,7 +867,14 @@ class SpeechBatcher:
         `loudness` (None: untouched; a target in LUFS, -40 .. -5): the serial call's `loudness=` -- the waveform is brought to that
         BS.1770 integrated loudness on the device, in front of the strip and the conversion; requests that finish together with
         different targets, or none, still share the one ragged decode and ONE normalisation call (a split request is one group of
-        it: one gain over its sentences)."""
+        it: one gain over its sentences).
+        `pauses` (None: untouched; True, a pauses.PauseSpec or a dict of its fields): the serial call's `pauses=` -- edge silence
+        trimmed and long pauses capped on the device, behind the resampler and in front of the loudness stage; requests that finish
+        together with different specs, or none, still share the one ragged decode and ONE `CodecEngine.trim_pauses` call (a request
+        without a spec is copied through it; every sentence of a split request is trimmed alone)."""
+        pauses = PA.check(pauses)
+        if pauses is not None:
+            PA.check_rate(24000 if sample_rate is None else sample_rate)
         loudness = LN.check_target(loudness)
         if loudness is not None:
             LN.check_rate(24000 if sample_rate is None else sample_rate)
@@ -878,7 +890,7 @@ class SpeechBatcher:
         fut: Future = Future()
         fut.rid = next(self._ids)
         self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding,
-                          speed=speed, flac=bool(flac), loudness=loudness))
+                          speed=speed, flac=bool(flac), loudness=loudness, pauses=pauses))
         return fut
 
     def cancel(self, fut: Future) -> None:
@@ -887,7 +899,7 @@ class SpeechBatcher:
         self._in.put(_Cancel(fut.rid))
 
     def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None,
-                      speed=None, flac: bool = False, loudness=None) -> SpeechStream:
+                      speed=None, flac: bool = False, loudness=None, pauses=None) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
@@ -905,7 +917,10 @@ class SpeechBatcher:
         the next chunk), the serial call's `flac=True, stream_flac=True`; behind `flac.stream_header(rate)` they decode to the int16
         chunks of the same request without `flac`.  The chunks of all FLAC streams due at one poll share ONE encoder step behind the
         one decoder pass (CodecEngine.decode_windows(flac=)); it combines with `sample_rate` and `speed` as far as the batcher serves
-        those, not with `encoding`.  `loudness` is refused: an integrated loudness needs the whole utterance."""
+        those, not with `encoding`.  `loudness` is refused: an integrated loudness needs the whole utterance.  `pauses` is refused: the
+        run state would have to be carried across chunks."""
+        if PA.check(pauses) is not None:
+            raise ValueError("pauses applies to non-streamed requests only (a stream would need the run state carried across chunks)")
         if LN.check_target(loudness) is not None:
             raise ValueError("loudness applies to non-streamed requests only (an integrated loudness needs the whole utterance; a stream "
                              "would need a running measure)")
@@ -951,6 +966,7 @@ class SpeechBatcher:
                "admissions": self.admissions, "max_coresident": self.max_coresident, "completed": self.completed, "failed": self.failed,
                "ragged_decode": self.ragged_decode, "decode_calls": self.decode_calls, "decoded": self.decoded,
                "max_decode_group": self.max_decode_group, "companded": self.companded, "flac_encoded": self.flac_encoded,
+               "trimmed": self.trimmed,
                "split": {"requests": self.split_requests, "sentences": self.split_sentences, "max_coresident": self.split_max_coresident}}
         if self.streams:      # (list(): the worker changes the registry meanwhile)
             occ.update({"streams": sum(j.is_stream for j in list(self._jobs.values())), "stream_decode_calls": self.stream_decode_calls,
@@ -996,6 +1012,7 @@ class SpeechBatcher:
         else:
             self.completed += 1
             self.flac_encoded += job.flac and not job.is_stream                  # (a stream's chunks are counted as they go out)
+            self.trimmed += job.pauses is not None and not job.is_stream
             self.companded += not job.is_stream and job.encoding is not None      # (a stream's chunks are counted as they go out)
         if job.is_stream:
             job.sink._q.put(None if cancelled else result)
@@ -1263,7 +1280,8 @@ class SpeechBatcher:
         self._drain(block=False)
         self.lock.acquire()
 
-    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None, flac: bool = False, loudness=None) -> np.ndarray:
+    def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None, flac: bool = False, loudness=None,
+               pauses=None) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
@@ -1271,16 +1289,19 @@ class SpeechBatcher:
         self._count_decode(1)
         wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}),
                                        **({} if speed is None else {"speed": float(speed)}),
-                                       **({} if loudness is None else {"loudness": float(loudness)}))[0]
+                                       **({} if loudness is None else {"loudness": float(loudness)}),
+                                       **({} if pauses is None else {"pauses": pauses}))[0]
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
         if flac:                                                            # converted on the host, encoded by the host twin
             return np.frombuffer(FLAC.encode(pcm, 24000 if sample_rate is None else int(sample_rate)), np.uint8)
         return pcm if encoding is None else G711.encode(pcm, encoding)      # converted on the host, companded by the host twin
 
-    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None, flac=None, loudness=None) -> list:
+    def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None, flac=None, loudness=None,
+                     pauses=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
         returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000);
-        `speeds`: one speed per request (None: 1.0); `loudness`: one target per request (None entries: left alone)"""
+        `speeds`: one speed per request (None: 1.0); `loudness`: one target per request (None entries: left alone); `pauses`: one spec
+        per request (None entries: copied through the one `trim_pauses` call)"""
         out: list = [RuntimeError(_NO_AUDIO) if h.shape[0] == 0 else None for h in hids]
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
@@ -1294,6 +1315,8 @@ class SpeechBatcher:
                 kw["flac"] = [bool(flac[i]) for i in live]
             if loudness is not None and any(loudness[i] is not None for i in live):
                 kw["loudness"] = [loudness[i] for i in live]
+            if pauses is not None and any(pauses[i] is not None for i in live):
+                kw["pauses"] = [pauses[i] for i in live]
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out

@@ -436,6 +436,26 @@ int ctts_loudness_normalize_ragged(const float* x, float* y, const int64_t* off_
                                    const double* target_dev, const double* target_host, void* stats, void* scratch, size_t scratch_bytes,
                                    void* stream);
 
+/* Pause control: packed float32 segments in[off[s], off[s+1]) lose edge silence and long inner pauses, frame by frame (the definition,
+ * once, is chattts_amd/pauses.py).  Segment s has the row rows[8 s ..]: F (samples per 10 ms frame, 80 .. 480), pad, lead, tail, P (frames;
+ * P = 0: the segment is copied through), thr (float32 bits, a frame is active when some sample has !(|x| < thr)), the offset of its
+ * crossfade table w_in[F] in `fade`, and 0.  fbase[s] is the number of frames in front of segment s (ceil(n / F) frames each).  The kept
+ * frames go, in order, to out[off_out[s], off_out[s+1]); off_out (n_seg + 1 int64) and records (8 int32 per segment: frames, active, speech,
+ * lead frames removed, tail frames removed, inner runs shortened, inner frames removed, output samples) are written ON THE DEVICE -- the
+ * output length depends on the samples.  `out` holds as many samples as `in` (an upper bound) and must not overlap it; both are 16-byte
+ * aligned.  A kept sample is a bit-for-bit copy, except one frame per shortened inner run, which is a raised-cosine crossfade
+ * (fadd_rn(fmul_rn(w_in[F-1-i], a[i]), fmul_rn(w_in[i], b[i])), no fused multiply-add).  A segment's samples and record do not depend on
+ * what it is packed with.  The offset, frame base and row tables are given on the device and the host (the two must agree).  Refused
+ * before anything is launched: a null pointer, offsets that do not ascend from 0, an empty segment, a pack of 2^31 - 4096 samples or
+ * more, more than 65535 segments, a row out of range, a fade offset outside the table, a frame base table that disagrees with the
+ * offsets, misaligned or overlapping buffers, scratch under ctts_trim_pauses_ragged_scratch_bytes(frames, n_seg).  Stream-ordered,
+ * four launches: the frames' activity, the plan (one workgroup per segment), the output offsets (one workgroup), the copy. */
+size_t ctts_trim_pauses_ragged_scratch_bytes(int64_t frames, int32_t n_seg);
+int ctts_trim_pauses_ragged(const float* in, float* out, const int64_t* off_dev, const int64_t* off_host, const int64_t* fbase_dev,
+                            const int64_t* fbase_host, const int32_t* rows_dev, const int32_t* rows_host, int32_t n_seg,
+                            const float* fade_dev, int32_t n_fade, int64_t* off_out, int32_t* records, void* scratch, size_t scratch_bytes,
+                            void* stream);
+
 /* Time scaling of streams: the signal of a stream arrives in pushes, its output leaves in chunks, and the concatenation of the chunks (and
  * of the path entries) is ctts_time_scale_ragged's result on the whole signal, bit for bit, however the signal is cut into pushes.
  * With n_avail samples in and more to come, frame k >= 1 may run once need(k) = max(a_{k-1} + D + N - 1, a_k - HS + D + N - 1) <= n_avail;
