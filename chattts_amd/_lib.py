@@ -240,6 +240,10 @@ SIGNATURES = {
     "ctts_k_dwconv_ln_ex": (C.c_int, [P, P, P, P, P, F, I32, P, I32, I32, I32, P, I32, P, P]),
     "ctts_k_layernorm": (C.c_int, [P, P, P, F, P, I32, P]),
     "ctts_k_istft": (C.c_int, [P, P, P, P, P, I32, I32, P]),
+    "ctts_k_istft_ragged": (C.c_int, [P, P, P, P, P, P, I32, I32, I32, P]),
+    "ctts_k_gather_windows": (C.c_int, [P, C.c_int64, C.c_int64, P, I32, I32, P, P, P]),
+    "ctts_k_crop_pcm16_windows": (C.c_int, [P, P, I32, I32, I32, F, P, P, P]),
+    "ctts_k_chunks_pcm16": (C.c_int, [P, P, P, P, I32, I32, I32, F, P, P, P]),
     "ctts_k_stft_mag": (C.c_int, [P, I32, P, P, P, I32, P]),
     "ctts_k_gfsq_encode": (C.c_int, [P, P, P, I32, P]),
     "ctts_k_gfsq_embed": (C.c_int, [P, P, P, I32, P]),

@@ -2361,6 +2361,32 @@ extern "C" int ctts_k_istft(const float* head, const float* window, const float*
   CK(launch_istft(head, window, twiddle, frames, wav, B, F, (hipStream_t)stream));
   return 0;
 }
+// the Vocos tail's launchers alone (kernel tests): no checks beyond null pointers -- every bound is the caller's
+extern "C" int ctts_k_istft_ragged(const float* head, const float* window, const float* twiddle, float* frames, float* wav,
+                                   const int32_t* tok_off, int32_t n_seg, int32_t F_total, int32_t F_max, void* stream) {
+  if (!head || !window || !twiddle || !frames || !wav || !tok_off) return fail("ctts_k_istft_ragged: bad arguments");
+  CK(launch_istft_ragged(head, window, twiddle, frames, wav, tok_off, n_seg, F_total, F_max, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ctts_k_gather_windows(const float* hid, int64_t slot_stride, int64_t row_stride, const ctts_window* win, int32_t n_win,
+                                     int32_t total_rows, float* packed, int32_t* tok_off, void* stream) {
+  if (!hid || !win || !packed || !tok_off) return fail("ctts_k_gather_windows: bad arguments");
+  CK(launch_gather_windows(hid, slot_stride, row_stride, (const CodecWindow*)win, n_win, total_rows, packed, tok_off, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ctts_k_crop_pcm16_windows(const float* wav, const ctts_window* win, int32_t n_win, int32_t out_f32, int32_t product,
+                                         float keep_thr, void* out, uint8_t* keep, void* stream) {
+  if (!wav || !win || !out) return fail("ctts_k_crop_pcm16_windows: bad arguments");
+  CK(launch_crop_pcm16_windows(wav, (const CodecWindow*)win, n_win, out_f32, product, keep_thr, out, keep, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int ctts_k_chunks_pcm16(const float* wav, const float* chunks, const ctts_window* win, const ctts_rs_window* rs, int32_t n_win,
+                                   int32_t out_f32, int32_t product, float keep_thr, void* out, uint8_t* keep, void* stream) {
+  if (!wav || !chunks || !win || !rs || !out) return fail("ctts_k_chunks_pcm16: bad arguments");
+  CK(launch_chunks_pcm16(wav, chunks, (const CodecWindow*)win, (const RsWindow*)rs, n_win, out_f32, product, keep_thr, out, keep,
+                         (hipStream_t)stream));
+  return 0;
+}
 
 
 // ------------------------------------------------------------------------------------------------

@@ -512,9 +512,13 @@ __global__ __launch_bounds__(256) void absmax_rows_k(const float* __restrict__ x
 // the scale of a row whose peak |x| is pk, and one converted sample (shared by every PCM16 kernel of this file)
 __device__ __forceinline__ long long pcm16_scale(float pk) {
   // a non-finite sample makes the peak Inf / NaN (the bit pattern of |x| orders above every finite value): the cast would be undefined
-  // behaviour -- such a row gets scale 0, i.e. zeros (the reference's numpy path yields garbage there)
-  const long long c = (pk < 3.0e38f) ? (long long)ceilf(pk) : 0;
-  return c > 0 ? (32767ll * 32768ll) / (c * 32768ll) : 0;
+  // behaviour -- such a row gets scale 0, i.e. zeros (the reference's numpy path yields garbage there).  So does every finite peak whose
+  // ceiling exceeds 32767: the integer quotient is 0 there (audio.pcm_scale), while (long long)ceilf(pk) is undefined from 2^63 on and
+  // c * 32768 wraps from c = 2^48 on (a zero divisor at 2^49) -- hence the test on the float, before any cast.  For 1 <= c <= 32767
+  // 32767 / c == (32767 * 32768) / (c * 32768), the reference's expression.  The comparison is false for NaN.
+  const float cf = ceilf(pk);
+  if (!(cf >= 1.0f && cf <= 32767.0f)) return 0;
+  return 32767ll / (long long)cf;
 }
 __device__ __forceinline__ int16_t pcm16_sample(float v, long long am, int product) {
   const int q = product == 0 ? (int)((double)v * (double)am) : (int)(v * (float)am);

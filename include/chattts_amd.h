@@ -960,6 +960,20 @@ int ctts_k_dwconv_ln_ex(const float* x, const float* w, const float* b, const fl
                         float* y, int32_t B, int32_t F, int32_t C, uint16_t* yp, int32_t plane_f16, const int32_t* seg, void* stream);
 int ctts_k_layernorm(const float* x, const float* w, const float* b, float eps, float* y, int32_t rows, void* stream);
 int ctts_k_istft(const float* head, const float* window, const float* twiddle, float* frames, float* wav, int32_t B, int32_t F, void* stream);
+/* The Vocos tail's launchers alone (csrc/kernels.hpp: launch_istft_ragged, launch_gather_windows, launch_crop_pcm16_windows,
+ * launch_chunks_pcm16), with their arguments in their order and NO checks beyond null pointers: every bound is the caller's.
+ * istft_ragged: head [F_total][1026] of packed segments, tok_off [n_seg + 1] device token offsets (2 frames per token), segment i's
+ * waveform at wav + 256 (2 tok_off[i] - i), frames [F_total][1024] scratch.  gather_windows: the rows of `win` (device) out of the store
+ * into packed [total_rows][768], tok_off [n_win + 1].  crop_pcm16_windows / chunks_pcm16: the last launch of ctts_codec_decode_windows /
+ * ctts_codec_decode_windows_rate over a given waveform -- `out` int16 or (out_f32) float32, sum ceil8(n_i) elements; `keep` may be NULL. */
+int ctts_k_istft_ragged(const float* head, const float* window, const float* twiddle, float* frames, float* wav, const int32_t* tok_off,
+                        int32_t n_seg, int32_t F_total, int32_t F_max, void* stream);
+int ctts_k_gather_windows(const float* hid, int64_t slot_stride, int64_t row_stride, const ctts_window* win, int32_t n_win, int32_t total_rows,
+                          float* packed, int32_t* tok_off, void* stream);
+int ctts_k_crop_pcm16_windows(const float* wav, const ctts_window* win, int32_t n_win, int32_t out_f32, int32_t product, float keep_thr,
+                              void* out, uint8_t* keep, void* stream);
+int ctts_k_chunks_pcm16(const float* wav, const float* chunks, const ctts_window* win, const ctts_rs_window* rs, int32_t n_win, int32_t out_f32,
+                        int32_t product, float keep_thr, void* out, uint8_t* keep, void* stream);
 /* The full DVAE's own kernels alone (csrc/dvae.hip).  stft_mag: wav [n] -> mag [F][516] (513 bins of |stft(center, reflect, hann)|, then
  * 3 zero columns), window [1024], twiddle [512][2] as ctts_dvae_weights; refused, with nothing launched, unless n > 512 and
  * F == 1 + n / 256.  gfsq_encode: feat [rows][1024] -> codes [rows][4] int32; gfsq_embed: codes [rows][4] int64 -> feat [rows][1024];
