@@ -25,6 +25,7 @@ import torch
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
+from . import limiter as LM
 from . import pauses as PA
 from . import resample as RS
 from . import timescale as TS
@@ -90,6 +91,27 @@ def _loudness_kw(loudness) -> dict:
     if all(v is None for v in vals):
         return {}
     return {"loudness": vals[0] if np.ndim(loudness) == 0 else vals}
+
+
+def _limiter_kw(limiter) -> dict:
+    """the decode calls' `limiter=` argument: nothing for None or False, alone or everywhere (today's call, argument for argument);
+    ValueError for anything but bools"""
+    if limiter is None:
+        return {}
+    vals = [LM.check_flag(v) for v in ([limiter] if np.ndim(limiter) == 0 else list(limiter))]
+    if not any(vals):
+        return {}
+    return {"limiter": True if np.ndim(limiter) == 0 else vals}
+
+
+def _level_kw(loudness, limiter) -> dict:
+    """both arguments of the last float32 stage (CodecEngine.loudness_normalize and the peak limiter behind it)"""
+    return {**_loudness_kw(loudness), **_limiter_kw(limiter)}
+
+
+def _lim(lkw: dict) -> dict:
+    """the `limiter=` argument of a CodecEngine.loudness_normalize call: nothing where it is not asked for"""
+    return {"limiter": lkw["limiter"]} if "limiter" in lkw else {}
 
 
 def _pauses_kw(pauses) -> dict:
@@ -314,7 +336,7 @@ class Chat:
             24, params.manual_seed, self.context, **kw))
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None, *,
-                       ragged: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None):
+                       ragged: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None, limiter=None):
         """`Chat._decode_to_wavs` (core.py:513-539) -> np.float32 [B, n]: per-row hidden states [T_b,768] through the
         decoder, or (use_decoder=False) per-row token ids [T_b,4] through the full DVAE's codebook; then Vocos.
         `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded).
@@ -329,9 +351,13 @@ class Chat:
         `pauses` (None: untouched; True, a pauses.PauseSpec or a dict of its fields, also a list with one per row, None entries copied
         through): every row loses the silence at its edges and the middle of its long pauses on the device
         (CodecEngine.trim_pauses), behind the resampler and in front of the loudness stage.  The rows' lengths then differ: the
-        result is a List[np.ndarray] also without `ragged`."""
+        result is a List[np.ndarray] also without `ragged`.
+        `limiter` (None / False: off; True, also one flag per row): every flagged row goes through the look-ahead peak limiter on the
+        device (CodecEngine.peak_limit; the definition of limiter.py) where the loudness stage is, behind its gain: that gain then
+        drops the -1 dBFS ceiling term, and the limiter holds the ceiling sample by sample.  Without `loudness` it runs at unity
+        gain."""
         skw = _speed_kw(speed)
-        lkw = _loudness_kw(loudness)
+        lkw = _level_kw(loudness, limiter)
         pkw = _pauses_kw(pauses)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
@@ -356,7 +382,8 @@ class Chat:
         if sample_rate is not None:
             wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
         if lkw:
-            wav = self.codec.loudness_normalize(wav, lkw["loudness"], rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+            wav = self.codec.loudness_normalize(wav, lkw.get("loudness"), rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate),
+                                                **_lim(lkw))
         return self.codec.to_host(wav)
 
     def _decode_batch_trimmed(self, result_list, use_decoder: bool, pad_to, sample_rate, skw: dict, lkw: dict, pauses):
@@ -373,12 +400,12 @@ class Chat:
         rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
         wav, off = codec.trim_pauses(wav, pauses, rates=rate)
         if lkw:
-            wav = codec.loudness_normalize(wav, lkw["loudness"], offsets=off, rates=rate, out=wav)
+            wav = codec.loudness_normalize(wav, lkw.get("loudness"), offsets=off, rates=rate, out=wav, **_lim(lkw))
         return wav, off
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
                         product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None,
-                        flac=None, loudness=None, pauses=None) -> List[np.ndarray]:
+                        flac=None, loudness=None, pauses=None, limiter=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
@@ -400,9 +427,12 @@ class Chat:
         `pauses` (None: untouched; True, a pauses.PauseSpec or a dict of its fields, also a list with one per row, None entries copied
         through): `wav` above is the waveform with its edge silence trimmed and its long pauses capped on the device
         (CodecEngine.trim_pauses), every row alone -- behind the resampler, in front of the loudness stage and everything behind it.
-        Without `ragged` the trimmed rows of the batch go on as a pack, through the ragged calls' conversion."""
+        Without `ragged` the trimmed rows of the batch go on as a pack, through the ragged calls' conversion.
+        `limiter` (None / False: off; True, also one flag per row): `wav` above is the waveform behind the look-ahead peak limiter
+        (CodecEngine.peak_limit), which runs where the loudness stage is, at its gain without the ceiling term (unity without
+        `loudness`): no sample that is converted exceeds -1 dBFS, and a peak above full scale is limited instead of clipped."""
         skw = _speed_kw(speed)
-        lkw = _loudness_kw(loudness)
+        lkw = _level_kw(loudness, limiter)
         pkw = _pauses_kw(pauses)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
@@ -426,7 +456,8 @@ class Chat:
         if sample_rate is not None:
             wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
         if lkw:
-            wav = self.codec.loudness_normalize(wav, lkw["loudness"], rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+            wav = self.codec.loudness_normalize(wav, lkw.get("loudness"), rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate),
+                                                **_lim(lkw))
         pcm, keep = self.codec.float_to_int16(wav, per_row=True, product=product, keep_thr=1e-5 if strip else None)
         if encoding is not None:       # codes | keep masks in one buffer: one copy
             B, n = int(pcm.shape[0]), int(pcm.shape[1])
@@ -469,14 +500,14 @@ class Chat:
         return flags
 
     def _decode_to_flac(self, result_list, use_decoder: bool, strip: bool, product: str, ragged: bool, sample_rate, flags, skw,
-                        encoding=None, loudness=None, pauses=None) -> List[np.ndarray]:
+                        encoding=None, loudness=None, pauses=None, limiter=None) -> List[np.ndarray]:
         """`decode_to_pcm16` with at least one row as a FLAC file: the decode of the plain call, then the grouped conversion with one
         group per row (the same samples; slots that start on multiples of 8 and a count header on the device) and the encoder behind it"""
         B = len(result_list)
         if B == 0:
             return []
         codec = self.codec
-        lkw = {} if loudness is None else {"loudness": loudness}
+        lkw = {**({} if loudness is None else {"loudness": loudness}), **({} if limiter is None else {"limiter": limiter})}
         if ragged:
             wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw, **({} if pauses is None else {"pauses": pauses}))
             rates = [CodecEngine.SAMPLE_RATE] * B if sample_rate is None else ([int(sample_rate)] * B if np.ndim(sample_rate) == 0 else
@@ -493,7 +524,7 @@ class Chat:
             wav = wav.contiguous()
             rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * B
             if lkw:
-                wav = codec.loudness_normalize(wav, loudness, rates=rates[0])
+                wav = codec.loudness_normalize(wav, loudness, rates=rates[0], **_lim(lkw))
             off = np.arange(B + 1, dtype=np.int64) * int(wav.shape[1])
             wav = wav.view(-1)
         encs = None if encoding is None else ([encoding] * B if isinstance(encoding, str) else list(encoding))
@@ -502,18 +533,19 @@ class Chat:
         return [p if p.dtype == np.uint8 else p.copy() for p in out]
 
     def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None, speed=None,
-                                loudness=None, pauses=None, decoded=None) -> List[np.ndarray]:
+                                loudness=None, pauses=None, decoded=None, limiter=None) -> List[np.ndarray]:
         """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
         PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's result equals
         `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w.  `encoding` (one, or one per row; None entries stay int16): the
         companded rows are converted by one launch behind the conversion, and the codes travel with the keep masks in the one copy
-        (the PCM16 samples too when some row stays int16).  `speed`, `loudness` and `pauses` (one, or one per row) go to the ragged decode;
+        (the PCM16 samples too when some row stays int16).  `speed`, `loudness`, `limiter` and `pauses` (one, or one per row) go to the ragged decode;
         `decoded`: the (packed, offsets) of a decode that has run already (the trimmed rows of a zero-padded batch)."""
         if len(result_list) == 0:
             return []
         codec = self.codec
         skw = {**({} if speed is None else {"speed": speed}), **({} if loudness is None else {"loudness": loudness}),
-               **({} if pauses is None else {"pauses": pauses}), **({} if decoded is None else {"decoded": decoded})}
+               **({} if pauses is None else {"pauses": pauses}), **({} if decoded is None else {"decoded": decoded}),
+               **({} if limiter is None else {"limiter": limiter})}
         if encoding is not None:
             encs = [encoding] * len(result_list) if isinstance(encoding, str) else list(encoding)
             if len(encs) != len(result_list):
@@ -536,7 +568,7 @@ class Chat:
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs, speed=None, loudness=None, pauses=None,
-                               decoded=None) -> List[np.ndarray]:
+                               decoded=None, limiter=None) -> List[np.ndarray]:
         """`_decode_to_pcm16_ragged` with at least one companded row.  The device buffer is int16 samples | codes | keep masks; rows
         that share a law and follow each other make one range.  A range starts on a multiple of 8 elements: rows resampled to
         another rate sit at arbitrary offsets, so a call that mixes laws over such rows goes through the grouped conversion instead
@@ -544,7 +576,8 @@ class Chat:
         codec = self.codec
         wav, off = decoded if decoded is not None else codec.decode_ragged(
             list(result_list), sample_rate=sample_rate, **({} if speed is None else {"speed": speed}),
-            **({} if loudness is None else {"loudness": loudness}), **({} if pauses is None else {"pauses": pauses}))
+            **({} if loudness is None else {"loudness": loudness}), **({} if pauses is None else {"pauses": pauses}),
+            **({} if limiter is None else {"limiter": limiter}))
         runs = []                     # [first row, one past the last, encoding]
         for i, e in enumerate(encs):
             if runs and runs[-1][2] == e:
@@ -573,7 +606,7 @@ class Chat:
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None,
-                              speed=None, flac=None, loudness=None, pauses=None) -> List[np.ndarray]:
+                              speed=None, flac=None, loudness=None, pauses=None, limiter=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
@@ -594,7 +627,10 @@ class Chat:
         is filtered alone, the gates run over all of the request's blocks, the peak is the request's.
         `pauses` (None: untouched; a pause spec, or a list with one per request, None entries copied through): every SENTENCE is
         trimmed alone (CodecEngine.trim_pauses) behind the resampler, so the gap at a join is at most tail + lead; the request's one
-        gain is then computed over its trimmed sentences."""
+        gain is then computed over its trimmed sentences.
+        `limiter` (None / False: off; True, or one flag per request): a flagged request's ONE gain drops the ceiling term and the
+        look-ahead peak limiter (CodecEngine.peak_limit) runs behind it over every sentence alone: its windows never span two
+        sentences.  Without `loudness` it runs at unity gain."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -616,9 +652,11 @@ class Chat:
             if len(speed) != len(groups):
                 raise ValueError("decode_split_to_pcm16: one speed per request, or one for all")
             skw = {"speed": [float(v) for v, g in zip(speed, groups) for _ in g]}
-        lkw = _loudness_kw(loudness)
-        if lkw and np.ndim(loudness) != 0 and len(loudness) != len(groups):
+        lkw = _level_kw(loudness, limiter)
+        if "loudness" in lkw and np.ndim(loudness) != 0 and len(loudness) != len(groups):
             raise ValueError("decode_split_to_pcm16: one loudness target per request, or one for all")
+        if "limiter" in lkw and np.ndim(limiter) != 0 and len(limiter) != len(groups):
+            raise ValueError("decode_split_to_pcm16: one limiter flag per request, or one for all")
         pkw = _pauses_kw(pauses)
         if pkw and isinstance(pauses, (list, tuple)):
             if len(pauses) != len(groups):
@@ -626,8 +664,8 @@ class Chat:
             pkw = {"pauses": [v for v, g in zip(pkw["pauses"], groups) for _ in g]}
         wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate, **skw, **pkw)
         if lkw:
-            wav = codec.loudness_normalize(wav, lkw["loudness"], offsets=off, groups=grp, out=wav,
-                                           rates=[r for r, g in zip(rates, groups) for _ in g])
+            wav = codec.loudness_normalize(wav, lkw.get("loudness"), offsets=off, groups=grp, out=wav,
+                                           rates=[r for r, g in zip(rates, groups) for _ in g], **_lim(lkw))
         if flags is not None:
             encs = None if encoding is None else ([encoding] * len(groups) if isinstance(encoding, str) else list(encoding))
             out = codec.float_to_int16_groups_flac(wav, off, grp, [r if f else None for r, f in zip(rates, flags)], product=product,
@@ -895,7 +933,7 @@ class Chat:
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
-              flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None):
+              flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -964,7 +1002,22 @@ class Chat:
         those of what is heard, and in front of the loudness stage, the silence strip, the 16-bit conversion, the companding and
         FLAC.  Every sentence of a split request is trimmed alone (one spec only), so the gap at a join is at most tail + lead; with
         `loudness` the request still gets ONE gain, over its trimmed sentences.  A streamed call with it raises: the run state would
-        have to be carried across chunks."""
+        have to be carried across chunks.
+        `limiter` (keyword-only, non-streamed only; None / False: off): True -- or one flag per text -- puts the look-ahead peak
+        limiter (CodecEngine.peak_limit; the definition of limiter.py: 10 ms of look-ahead, 10 ms of smoothing, a -1 dBFS ceiling
+        held sample by sample) behind the loudness stage's gain, which then drops its ceiling term: one loud plosive no longer
+        decides the level of the whole utterance.  Without `loudness` it runs at unity gain, so a decoded peak above full scale is
+        limited instead of clipped by the 16-bit conversion.  It sits where the loudness stage does: behind the time scaler, the
+        resampler and `pauses`, in front of the silence strip, the 16-bit conversion, the companding and FLAC.  The sentences of a
+        split request (one flag only) are limited one by one under the request's ONE gain.  A streamed call with it raises: the
+        look-ahead is not carried across chunks."""
+        mkw = _limiter_kw(limiter)
+        if mkw and stream:
+            raise ValueError("limiter applies to non-streamed inference only (the look-ahead is not carried across chunks)")
+        if mkw and split_text and np.ndim(limiter) != 0:
+            raise ValueError("a split_text request is one waveform: it takes one limiter flag")
+        if mkw:
+            LN.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         pkw = _pauses_kw(pauses)
         if pkw and stream:
             raise ValueError("pauses applies to non-streamed inference only (a stream would need the run state carried across chunks)")
@@ -1031,6 +1084,7 @@ class Chat:
         # split_text + pcm16 + ragged_decode: the hidden states of every split batch are collected and the whole request is decoded,
         # stripped, converted under its one peak and compacted on the device (decode_split_to_pcm16) -- the bytes of the host lines below
         split_dev = bool(split_text and pcm16 and ragged_decode and not stream and not refine_text_only)
+        lkw = {**lkw, **mkw}
         split_host = bool(lkw and split_text and not split_dev and not refine_text_only)      # one gain over the sentences: applied below
         res_gen = self._infer(text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
@@ -1052,7 +1106,7 @@ class Chat:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
         thr = np.float32(1e-5)
         if split_host:
-            res_gen = [self._normalize_request([w for wavs in res_gen for w in wavs], lkw["loudness"], sample_rate)]
+            res_gen = [self._normalize_request([w for wavs in res_gen for w in wavs], lkw.get("loudness"), sample_rate, **_lim(lkw))]
         stripped = [wav[np.abs(wav) > thr] for wavs in res_gen for wav in wavs]   # sample-level strip, also mid-utterance
         if pcm16:      # split_text: ONE concatenated waveform, hence one peak over all sentences -- converted on the host
             one = float_to_int16(np.concatenate(stripped))
@@ -1061,21 +1115,21 @@ class Chat:
             return [one if encoding is None else G711.encode(one, encoding)]
         return [np.concatenate(stripped)] if split_text else stripped
 
-    def _normalize_request(self, wavs, target: float, rate: int) -> List[np.ndarray]:
+    def _normalize_request(self, wavs, target, rate: int, **lim) -> List[np.ndarray]:
         """the sentences of a split request that is concatenated on the host: ONE loudness and ONE gain over all of them, on the
-        device (the waveforms go there and back as one pack; every sentence is filtered alone)"""
+        device (the waveforms go there and back as one pack; every sentence is filtered alone, and with `limiter` limited alone)"""
         if len(wavs) == 0:
             return []
         off = np.zeros(len(wavs) + 1, np.int64)
         np.cumsum([len(w) for w in wavs], out=off[1:])
         pack = torch.from_numpy(np.concatenate([np.asarray(w, dtype=np.float32) for w in wavs])).to(self.device)
-        out = self.codec.loudness_normalize(pack, target, offsets=off, groups=np.array([0, len(wavs)], np.int32), rates=rate, out=pack)
+        out = self.codec.loudness_normalize(pack, target, offsets=off, groups=np.array([0, len(wavs)], np.int32), rates=rate, out=pack, **lim)
         return ragged_views(self.codec.to_host(out), off)
 
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None):
+               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None):
         """core.py:395-503 (generator).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -1102,7 +1156,8 @@ class Chat:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
                                            encoding, speed, ts, rs, **({"flac": True} if flac else {}),
                                            **({} if loudness is None else {"loudness": loudness}), **({} if fs is None else {"fs": fs}),
-                                           **({} if pauses is None else {"pauses": pauses}))
+                                           **({} if pauses is None else {"pauses": pauses}),
+                                           **({} if limiter is None else {"limiter": limiter}))
         finally:
             for h in fs or ():
                 if not isinstance(h, FLAC.StreamEncoder):
@@ -1113,7 +1168,7 @@ class Chat:
                 self.codec.resample_stream_close(h)
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None):
+                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None):
         """the batch loop of `_infer`"""
         def flac_chunks(piece, final):
             """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' FLAC
@@ -1163,6 +1218,8 @@ class Chat:
                         rkw["flac"] = True
                     if loudness is not None and not raw:
                         rkw["loudness"] = loudness
+                    if limiter is not None and not raw:
+                        rkw["limiter"] = limiter
                     if pauses is not None and not raw:
                         rkw["pauses"] = pauses[lo: lo + step] if isinstance(pauses, list) else pauses
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)

@@ -2047,12 +2047,12 @@ extern "C" size_t ctts_loudness_normalize_ragged_scratch_bytes(const int64_t* of
   if (loudness_offsets_check("ctts_loudness_normalize_ragged_scratch_bytes", off_host, n_seg)) return 0;
   return (size_t)loudness_records(off_host[n_seg], n_seg) * LN_REC * sizeof(double) + (size_t)(n_seg + 3) / 4 * 16;
 }
-extern "C" int ctts_loudness_normalize_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
-                                              const int32_t* rate_dev, const int32_t* rate_host, const double* coef_dev, const double* coef_host,
-                                              int32_t n_rates, const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp,
-                                              const double* target_dev, const double* target_host, void* stats, void* scratch,
-                                              size_t scratch_bytes, void* stream) {
-  const char* who = "ctts_loudness_normalize_ragged";
+// both loudness entries; lim_dev / gain_out null: ctts_loudness_normalize_ragged
+static int loudness_normalize_impl(const char* who, const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                   const int32_t* rate_dev, const int32_t* rate_host, const double* coef_dev, const double* coef_host,
+                                   int32_t n_rates, const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp,
+                                   const double* target_dev, const double* target_host, const int32_t* lim_dev, float* gain_out, void* stats,
+                                   void* scratch, size_t scratch_bytes, void* stream) {
   if (!x || !y || !off_dev || !rate_dev || !rate_host || !coef_dev || !coef_host || !grp_dev || !grp_host || !target_dev || !target_host || !stats)
     return fail("%s: a null pointer (x, y, the stats and the offset, rate, coefficient, group and target tables on the device and the host are needed)", who);
   if (loudness_offsets_check(who, off_host, n_seg)) return -1;
@@ -2085,7 +2085,59 @@ extern "C" int ctts_loudness_normalize_ragged(const float* x, float* y, const in
     return fail("%s: scratch missing, not 16-byte aligned or too small (%zu bytes, need %zu)", who, scratch_bytes, rec_bytes + (size_t)(n_seg + 3) / 4 * 16);
   CttsDeviceGuard dg(stream);
   CK(launch_loudness_normalize_ragged(x, y, (const long long*)off_dev, n_seg, n_max, tiles_max, (int)h_max, rate_dev, coef_dev, grp_dev, n_grp, target_dev,
-                                      stats, (double*)scratch, (float*)((char*)scratch + rec_bytes), (hipStream_t)stream));
+                                      stats, (double*)scratch, (float*)((char*)scratch + rec_bytes), (hipStream_t)stream, lim_dev, gain_out));
+  return 0;
+}
+extern "C" int ctts_loudness_normalize_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                              const int32_t* rate_dev, const int32_t* rate_host, const double* coef_dev, const double* coef_host,
+                                              int32_t n_rates, const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp,
+                                              const double* target_dev, const double* target_host, void* stats, void* scratch,
+                                              size_t scratch_bytes, void* stream) {
+  return loudness_normalize_impl("ctts_loudness_normalize_ragged", x, y, off_dev, off_host, n_seg, rate_dev, rate_host, coef_dev, coef_host, n_rates,
+                                 grp_dev, grp_host, n_grp, target_dev, target_host, nullptr, nullptr, stats, scratch, scratch_bytes, stream);
+}
+extern "C" int ctts_loudness_limited_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                            const int32_t* rate_dev, const int32_t* rate_host, const double* coef_dev, const double* coef_host,
+                                            int32_t n_rates, const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp,
+                                            const double* target_dev, const double* target_host, const int32_t* lim_dev, const int32_t* lim_host,
+                                            float* gain_out, void* stats, void* scratch, size_t scratch_bytes, void* stream) {
+  const char* who = "ctts_loudness_limited_ragged";
+  if (!lim_dev || !lim_host || !gain_out) return fail("%s: a null pointer (the limiter table on the device and the host and the gains are needed)", who);
+  if ((uintptr_t)gain_out & 3) return fail("%s: the gains must be 4-byte aligned", who);
+  if (n_grp >= 1 && n_grp <= 65535)
+    for (int g = 0; g < n_grp; ++g)
+      if (lim_host[g] != 0 && lim_host[g] != 1) return fail("%s: group %d: the limiter flag is 0 or 1 (got %d)", who, g, lim_host[g]);
+  return loudness_normalize_impl(who, x, y, off_dev, off_host, n_seg, rate_dev, rate_host, coef_dev, coef_host, n_rates, grp_dev, grp_host, n_grp,
+                                 target_dev, target_host, lim_dev, gain_out, stats, scratch, scratch_bytes, stream);
+}
+extern "C" size_t ctts_peak_limit_ragged_scratch_bytes(const int64_t* off_host, int32_t n_seg) {
+  if (loudness_offsets_check("ctts_peak_limit_ragged_scratch_bytes", off_host, n_seg)) return 0;
+  return ((size_t)off_host[n_seg] * sizeof(float) + 15) / 16 * 16 + ((size_t)limiter_tiles(off_host[n_seg], n_seg) * sizeof(int32_t) + 15) / 16 * 16;
+}
+extern "C" int ctts_peak_limit_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                      const int32_t* rate_dev, const int32_t* rate_host, const float* gain_dev, void* stats, void* scratch,
+                                      size_t scratch_bytes, void* stream) {
+  const char* who = "ctts_peak_limit_ragged";
+  if (!x || !y || !off_dev || !rate_dev || !rate_host || !gain_dev || !stats)
+    return fail("%s: a null pointer (x, y, the gains, the stats and the offset and rate tables on the device and the host are needed)", who);
+  if (loudness_offsets_check(who, off_host, n_seg)) return -1;
+  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)stats & 3) || ((uintptr_t)gain_dev & 3))
+    return fail("%s: x and y must be 16-byte aligned, the gains and the stats 4-byte aligned", who);
+  if (x != y && x < y + off_host[n_seg] && y < x + off_host[n_seg]) return fail("%s: y must be x itself or not overlap it", who);
+  long long n_max = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    const int32_t fs = rate_host[i];
+    if (fs < 100 * LM_WMIN || fs > 100 * LM_WMAX || fs % 10 != 0)
+      return fail("%s: segment %d: the rate is a multiple of 10 Hz in %d .. %d (got %d)", who, i, 100 * LM_WMIN, 100 * LM_WMAX, fs);
+    n_max = std::max(n_max, (long long)(off_host[i + 1] - off_host[i]));
+  }
+  const size_t curve_bytes = ((size_t)off_host[n_seg] * sizeof(float) + 15) / 16 * 16;
+  const size_t need = curve_bytes + ((size_t)limiter_tiles(off_host[n_seg], n_seg) * sizeof(int32_t) + 15) / 16 * 16;
+  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < need)
+    return fail("%s: scratch missing, not 16-byte aligned or too small (%zu bytes, need %zu)", who, scratch_bytes, need);
+  CttsDeviceGuard dg(stream);
+  CK(launch_peak_limit_ragged(x, y, (const long long*)off_dev, n_seg, n_max, rate_dev, gain_dev, stats, (float*)scratch,
+                              (int32_t*)((char*)scratch + curve_bytes), (hipStream_t)stream));
   return 0;
 }
 extern "C" size_t ctts_trim_pauses_ragged_scratch_bytes(int64_t frames, int32_t n_seg) {

@@ -539,9 +539,23 @@ static inline long long loudness_records(long long total, int n_seg) { return to
 // packed segments x[off[s], off[s+1]) at rate row rate[s] of coef; segments grp[g] .. grp[g+1]-1 are group g with target[g] LUFS (NaN:
 // measured, gain 1): y = g32 * x (y may be x), stats[g] the group's 32-byte record.  n_max: the longest segment, tiles_max: the most
 // tiles ceil(n_s / H_s) of a segment (grid sizes), h_max: the largest H of a segment (the tile pass's LDS); rec: loudness_records(..) * LN_REC float64, seg_gain: [n_seg] float32 of device scratch.
+// lim != null: a group with lim[g] != 0 goes through the peak limiter behind this stage -- its gain drops the ceiling term and its
+// segments are not scaled here (copied where y is not x); gain_out != null: [n_seg] float32, every segment's group gain, for that call.
 hipError_t launch_loudness_normalize_ragged(const float* x, float* y, const long long* off, int n_seg, long long n_max, long long tiles_max,
                                             int h_max, const int32_t* rate, const double* coef, const int32_t* grp, int n_grp, const double* target,
-                                            void* stats, double* rec, float* seg_gain, hipStream_t st);
+                                            void* stats, double* rec, float* seg_gain, hipStream_t st, const int32_t* lim = nullptr,
+                                            float* gain_out = nullptr);
+
+// ---- look-ahead peak limiter (limiter.hip) -----------------------------------------------------------
+#define LM_TILE 2048          // samples of one segment per workgroup; a halo is 2 W <= 960 of them on each side
+#define LM_WMIN 80            // W = fs / 100: 8 kHz ..
+#define LM_WMAX 480           // .. 48 kHz
+// tile flags a pack of `total` samples in n_seg segments needs: segment s's tiles start at flag off[s] / LM_TILE + s
+static inline long long limiter_tiles(long long total, int n_seg) { return total / LM_TILE + n_seg + 1; }
+// packed segments x[off[s], off[s+1]) at rate[s] Hz with the pre-gain gain[s]: y = s (g x) (y may be x), stats[s] the segment's 16-byte
+// record.  n_max: the longest segment (grid sizes); curve: one float32 per sample of the pack, flags: limiter_tiles(..) int32 of scratch.
+hipError_t launch_peak_limit_ragged(const float* x, float* y, const long long* off, int n_seg, long long n_max, const int32_t* rate,
+                                    const float* gain, void* stats, float* curve, int32_t* flags, hipStream_t st);
 
 // ---- pause control (pauses.hip) -------------------------------------------------------------------
 #define PA_FMIN 80            // a frame is F = fs / 100 samples (integer division): 8 kHz ..

@@ -20,6 +20,8 @@
 //    the gain and the record; the group's gain goes to every one of its segments.
 //  * loudness_scale_k -- y = g32 * x over the pack, one rounding per sample: 16-byte loads and stores at the pack's own alignment, single
 //    samples at a segment's ragged edges.  y may be x.
+// With a limiter table (ctts_loudness_limited_ragged) a flagged group's gain drops the ceiling term -- the peak limiter behind this stage
+// (limiter.hip) enforces it -- its segments are left unscaled, and every segment's gain goes where that call reads it.
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -186,7 +188,8 @@ __device__ __forceinline__ void ln_for_blocks(const long long* off, const int32_
 __global__ __launch_bounds__(256) void loudness_group_k(const long long* __restrict__ off, const int32_t* __restrict__ rate,
                                                         const double* __restrict__ coef, const int32_t* __restrict__ grp,
                                                         const double* __restrict__ target, double* rec, float* __restrict__ seg_gain,
-                                                        LnStats* __restrict__ stats) {
+                                                        LnStats* __restrict__ stats, const int32_t* __restrict__ lim,
+                                                        float* __restrict__ gain_out) {
   __shared__ double zs[256][4];
   __shared__ double red[256];
   __shared__ float gsh;
@@ -255,6 +258,7 @@ __global__ __launch_bounds__(256) void loudness_group_k(const long long* __restr
     if (tid < m) red[tid] = fmax(red[tid], red[tid + m]);
     __syncthreads();
   }
+  const bool limited = lim && lim[g] != 0;                        // the limiter behind this stage enforces the ceiling
   if (tid == 0) {
     const float peak = (float)red[0];
     const double t = target[g];
@@ -267,7 +271,7 @@ __global__ __launch_bounds__(256) void loudness_group_k(const long long* __restr
         bound = 0;
         if (LN_MAX_GAIN < gain) { gain = LN_MAX_GAIN; bound = 1; }
         const double ceil_g = LN_CEILING / (double)peak;
-        if (ceil_g < gain) { gain = ceil_g; bound = 2; }
+        if (!limited && ceil_g < gain) { gain = ceil_g; bound = 2; }
       }
     }
     LnStats st;
@@ -278,16 +282,20 @@ __global__ __launch_bounds__(256) void loudness_group_k(const long long* __restr
   }
   __syncthreads();
   const float g32 = gsh;
-  for (int s = sa + tid; s < sb; s += 256) seg_gain[s] = g32;
+  for (int s = sa + tid; s < sb; s += 256) {
+    seg_gain[s] = limited ? 1.0f : g32;                           // the limiter applies the gain itself: the scale pass leaves x as it is
+    if (gain_out) gain_out[s] = g32;
+  }
 }
 
 __global__ __launch_bounds__(256) void loudness_scale_k(const float* x, float* y, const long long* __restrict__ off,
-                                                        const float* __restrict__ seg_gain) {
+                                                        const float* __restrict__ seg_gain, int skip_unity) {
   const int s = blockIdx.y;
   const long long lo = off[s], hi = off[s + 1];
   const long long p = (lo & ~3ll) + ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (p >= hi) return;
   const float g = seg_gain[s];
+  if (skip_unity && g == 1.0f && x == y) return;                  // a segment that waits for the limiter, in place: nothing to do
   if (p >= lo && p + 4 <= hi) {
     const float4 v = *reinterpret_cast<const float4*>(x + p);
     *reinterpret_cast<float4*>(y + p) = make_float4(__fmul_rn(g, v.x), __fmul_rn(g, v.y), __fmul_rn(g, v.z), __fmul_rn(g, v.w));
@@ -298,7 +306,7 @@ __global__ __launch_bounds__(256) void loudness_scale_k(const float* x, float* y
 
 hipError_t launch_loudness_normalize_ragged(const float* x, float* y, const long long* off, int n_seg, long long n_max, long long tiles_max,
                                             int h_max, const int32_t* rate, const double* coef, const int32_t* grp, int n_grp, const double* target,
-                                            void* stats, double* rec, float* seg_gain, hipStream_t st) {
+                                            void* stats, double* rec, float* seg_gain, hipStream_t st, const int32_t* lim, float* gain_out) {
   if (n_seg <= 0 || n_grp <= 0 || n_max <= 0 || h_max < LN_HMIN || h_max > LN_HMAX) return hipSuccess;
   // LN_WAVES tiles per workgroup where they fit the 64 KB of LDS a launch gets without asking for more (H <= 4096), else half as many
   const int waves = (size_t)LN_WAVES * h_max * sizeof(float) <= 65536 ? LN_WAVES : LN_WAVES / 2;
@@ -306,10 +314,11 @@ hipError_t launch_loudness_normalize_ragged(const float* x, float* y, const long
   hipLaunchKernelGGL(loudness_tile_k, g1, dim3(64 * waves), (size_t)waves * h_max * sizeof(float), st, x, off, rate, coef, rec, h_max);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(loudness_group_k, dim3((unsigned)n_grp), dim3(256), 0, st, off, rate, coef, grp, target, rec, seg_gain, (LnStats*)stats);
+  hipLaunchKernelGGL(loudness_group_k, dim3((unsigned)n_grp), dim3(256), 0, st, off, rate, coef, grp, target, rec, seg_gain, (LnStats*)stats, lim,
+                     gain_out);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const dim3 g3((unsigned)((n_max + 3 + 1023) / 1024), (unsigned)n_seg);
-  hipLaunchKernelGGL(loudness_scale_k, g3, dim3(256), 0, st, x, y, off, seg_gain);
+  hipLaunchKernelGGL(loudness_scale_k, g3, dim3(256), 0, st, x, y, off, seg_gain, lim ? 1 : 0);
   return hipGetLastError();
 }

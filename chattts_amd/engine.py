@@ -22,6 +22,7 @@ from . import _lib
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
+from . import limiter as LM
 from . import pauses as PA
 from . import resample as RS
 from . import timescale as TS
@@ -1832,7 +1833,8 @@ class CodecEngine:
             cache[key] = (torch.from_numpy(host).to(self.device), host, index)
         return cache[key]
 
-    def loudness_normalize(self, wav: torch.Tensor, target, offsets=None, groups=None, rates=None, return_stats: bool = False, out=None):
+    def loudness_normalize(self, wav: torch.Tensor, target, offsets=None, groups=None, rates=None, return_stats: bool = False, out=None,
+                           limiter=None):
         """ITU-R BS.1770-4 integrated loudness of a float32 device tensor and ONE gain per group that brings it to `target` LUFS
         (ctts_loudness_normalize_ragged; the definition, the +30 dB cap and the -1 dBFS ceiling of loudness.py): 1-D (one signal),
         [B, n] (rows, each alone), or 1-D packed with `offsets` (n_seg + 1 sample offsets, the ragged decoder's layout; every segment
@@ -1843,7 +1845,12 @@ class CodecEngine:
         in 8000 .. 48000.  Returns a tensor of the input's shape (`out`, when given: a float32 device tensor of that shape, possibly
         `wav` itself), and with `return_stats` also the groups' records (a NumPy array of loudness.STATS: L, peak, g32, the block
         counts, the term that bound).  A group's record and samples do not depend on what it is packed with.  ValueError before any
-        launch: a rate or target out of range, an empty segment, non-ascending offsets, a bad group table, 2^31 - 4096 samples."""
+        launch: a rate or target out of range, an empty segment, non-ascending offsets, a bad group table, 2^31 - 4096 samples.
+        `limiter` (None: off; one bool, or one per group): a flagged group's gain is min(target term, +30 dB cap) -- the ceiling term
+        is dropped, its record's bound is 0 or 1 -- and each of its segments goes through the look-ahead peak limiter alone at that
+        gain (`peak_limit`, ctts_loudness_limited_ragged in front of it: no host round trip in between), also where the gain is 1
+        (no target, a silent group).  With `return_stats` the limiter's records follow as a third element (limiter.STATS per
+        segment; zeros for a segment outside a flagged group)."""
         if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
             raise ValueError("loudness_normalize: a float32 device tensor, 1-D or [B, n]")
         if offsets is not None and wav.dim() != 1:
@@ -1856,7 +1863,10 @@ class CodecEngine:
         if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == wav.shape
                                     and out.is_contiguous()):
             raise ValueError("loudness_normalize: out is a contiguous float32 device tensor of the input's shape")
+        lim = LM.per_row(limiter, len(grp) - 1, "loudness_normalize")
         if all(t is None for t in tg) and not return_stats:
+            if lim is not None:                                   # nothing to measure: the limiter at unity gain
+                return self._peak_limit_runs(wav, off, rates, np.repeat(lim, np.diff(grp)), None, out)[0]
             if out is None or out is wav:
                 return wav
             out.copy_(wav)
@@ -1866,6 +1876,8 @@ class CodecEngine:
             x = x.clone()
         y = out if out is not None and out.data_ptr() % 16 == 0 else torch.empty_like(x)
         n_seg, n_grp = len(off) - 1, len(grp) - 1
+        if lim is not None:
+            return self._loudness_limited(wav, x, y, out, off, grp, rates, tg, lim, return_stats)
         coef_d, coef_h, index = self._loudness_coef(rates)
         ridx = np.array([index[r] for r in rates], dtype=np.int32)
         tgt = np.array([math.nan if t is None else t for t in tg], dtype=np.float64)
@@ -1892,6 +1904,131 @@ class CodecEngine:
         y = y.view(wav.shape)
         if return_stats:
             return y, work[: LN.STATS.itemsize * n_grp].cpu().numpy().view(LN.STATS)
+        return y
+
+    def _loudness_limited(self, wav, x, y, out, off, grp, rates, tg, lim, return_stats):
+        """`loudness_normalize` with a limiter table: ctts_loudness_limited_ragged (the flagged groups' gains without the ceiling
+        term, their segments left unscaled in y, every segment's gain in a device table), then the limiter over the flagged
+        segments in place in y, reading that table"""
+        n_seg, n_grp = len(off) - 1, len(grp) - 1
+        coef_d, coef_h, index = self._loudness_coef(rates)
+        ridx = np.array([index[r] for r in rates], dtype=np.int32)
+        tgt = np.array([math.nan if t is None else t for t in tg], dtype=np.float64)
+        lmt = np.array(lim, dtype=np.int32)
+        off_p = off.ctypes.data_as(C.c_void_p)
+        sb = int(self.lib.ctts_loudness_normalize_ragged_scratch_bytes(off_p, n_seg))
+        if sb == 0:
+            _lib.check(-1, "ctts_loudness_limited_ragged")
+        dev = wav.device
+        tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), tgt.view(np.uint8), ridx.view(np.uint8), grp.view(np.uint8), lmt.view(np.uint8)])).to(dev)
+        work = torch.empty((LN.STATS.itemsize * n_grp + sb,), dtype=torch.uint8, device=dev)             # the records, then the scratch
+        gains = torch.empty((n_seg,), dtype=torch.float32, device=dev)
+        st = torch.cuda.current_stream(dev)
+        base = tabs.data_ptr()
+        p_tgt, p_ridx = base + off.nbytes, base + off.nbytes + tgt.nbytes
+        p_grp = p_ridx + ridx.nbytes
+        _lib.check(self.lib.ctts_loudness_limited_ragged(
+            x.data_ptr(), y.data_ptr(), base, off_p, n_seg, p_ridx, ridx.ctypes.data_as(C.c_void_p),
+            coef_d.data_ptr(), coef_h.ctypes.data_as(C.c_void_p), int(coef_h.shape[0]),
+            p_grp, grp.ctypes.data_as(C.c_void_p), n_grp, p_tgt, tgt.ctypes.data_as(C.c_void_p),
+            p_grp + grp.nbytes, lmt.ctypes.data_as(C.c_void_p), gains.data_ptr(),
+            work.data_ptr(), work.data_ptr() + LN.STATS.itemsize * n_grp, sb, st.cuda_stream), "ctts_loudness_limited_ragged")
+        tabs.record_stream(st)
+        work.record_stream(st)
+        x.record_stream(st)
+        yv = y.view(-1)
+        lstats = self._peak_limit_runs(yv, off, rates, np.repeat(lim, np.diff(grp)), gains, yv, return_stats)[1]
+        if out is not None and y is not out:
+            out.copy_(y)
+            y = out
+        y = y.view(wav.shape)
+        if return_stats:
+            return y, work[: LN.STATS.itemsize * n_grp].cpu().numpy().view(LN.STATS), lstats
+        return y
+
+    # -- look-ahead peak limiter (csrc/limiter.hip) ------------------------------------------------------------------------------------
+    def _peak_limit_runs(self, wav, off, rates, flags, gains, out, return_stats: bool = False):
+        """the limiter over the flagged segments of a pack, run of neighbours by run (one call where every segment is flagged);
+        `gains`: None (unity) or a float32 device tensor with one gain per segment -> (tensor of wav's shape, records or None)"""
+        flat = wav.contiguous().view(-1)
+        if out is wav:
+            y = flat                                              # in place
+        else:
+            y = torch.empty_like(flat) if out is None else out.view(-1)
+            y.copy_(flat)
+        recs = np.zeros(len(off) - 1, dtype=LM.STATS) if return_stats else None
+        a = 0
+        while a < len(flags):
+            if not flags[a]:
+                a += 1
+                continue
+            b = a
+            while b < len(flags) and flags[b]:
+                b += 1
+            sub = y[int(off[a]): int(off[b])]
+            res = self.peak_limit(sub, offsets=off[a: b + 1] - off[a], rates=[int(r) for r in rates[a:b]],
+                                  gains=None if gains is None else gains[a:b], return_stats=return_stats, out=sub)
+            if return_stats:
+                recs[a:b] = res[1]
+            a = b
+        return y.view(wav.shape), recs
+
+    def peak_limit(self, wav: torch.Tensor, offsets=None, rates=None, gains=None, return_stats: bool = False, out=None):
+        """The look-ahead peak limiter on a float32 device tensor (ctts_peak_limit_ragged; the definition of limiter.py): 1-D (one
+        signal), [B, n] (rows, each alone), or 1-D packed with `offsets` (n_seg + 1 sample offsets, the ragged decoder's layout;
+        every segment limited as if alone, its windows never reach a neighbour).  `gains`: the float32 pre-gain -- None (1), one
+        number, one per segment, or a float32 device tensor with one per segment (the loudness stage's).  `rates`: the segments'
+        sample rates in Hz (one, or one per segment; default 24000), multiples of 10 in 8000 .. 48000: the look-ahead and the
+        smoothing are 10 ms each.  No sample of the result exceeds float32(10^(-1/20)) in magnitude, and a segment with no sample
+        over the threshold comes back as gain * x bit for bit.  Returns a tensor of the input's shape (`out`, when given: a float32
+        device tensor of that shape, possibly `wav` itself), and with `return_stats` also the segments' records (a NumPy array of
+        limiter.STATS: the pre-gain, the smallest gain, the samples over the threshold, the samples touched).  A segment's samples
+        and record do not depend on what it is packed with.  ValueError before any launch: a rate or gain out of range, an empty
+        segment, non-ascending offsets, 2^31 - 4096 samples, more than 65535 segments."""
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
+            raise ValueError("peak_limit: a float32 device tensor, 1-D or [B, n]")
+        if offsets is not None and wav.dim() != 1:
+            raise ValueError("peak_limit: offsets go with a packed 1-D tensor")
+        if wav.numel() == 0:
+            raise ValueError("peak_limit: nothing to limit")
+        if wav.dim() == 2:
+            offsets = np.arange(wav.shape[0] + 1, dtype=np.int64) * int(wav.shape[1])
+        on_dev = isinstance(gains, torch.Tensor)
+        off, rt, g = LM.tables(wav.numel(), offsets, rates, None if on_dev else gains)
+        n_seg = len(off) - 1
+        if on_dev and not (gains.is_cuda and gains.dtype == torch.float32 and gains.dim() == 1 and gains.numel() == n_seg and gains.is_contiguous()):
+            raise ValueError("peak_limit: gains on the device are a contiguous float32 tensor with one per segment")
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == wav.shape
+                                    and out.is_contiguous()):
+            raise ValueError("peak_limit: out is a contiguous float32 device tensor of the input's shape")
+        x = wav.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()
+        y = out if out is not None and out.data_ptr() % 16 == 0 else torch.empty_like(x)
+        off_p = off.ctypes.data_as(C.c_void_p)
+        sb = int(self.lib.ctts_peak_limit_ragged_scratch_bytes(off_p, n_seg))
+        if sb == 0:
+            _lib.check(-1, "ctts_peak_limit_ragged")              # the offsets were refused: the library's message says why
+        dev = wav.device
+        tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), rt.view(np.uint8), g.view(np.uint8)])).to(dev)   # one upload
+        work = torch.empty((-(-LM.STATS.itemsize * n_seg // 16) * 16 + sb,), dtype=torch.uint8, device=dev)          # the records, then the scratch
+        st = torch.cuda.current_stream(dev)
+        base = tabs.data_ptr()
+        _lib.check(self.lib.ctts_peak_limit_ragged(
+            x.data_ptr(), y.data_ptr(), base, off_p, n_seg, base + off.nbytes, rt.ctypes.data_as(C.c_void_p),
+            gains.data_ptr() if on_dev else base + off.nbytes + rt.nbytes, work.data_ptr(),
+            work.data_ptr() + -(-LM.STATS.itemsize * n_seg // 16) * 16, sb, st.cuda_stream), "ctts_peak_limit_ragged")
+        tabs.record_stream(st)
+        work.record_stream(st)
+        x.record_stream(st)
+        if on_dev:
+            gains.record_stream(st)
+        if out is not None and y is not out:
+            out.copy_(y.view(out.shape))
+            y = out
+        y = y.view(wav.shape)
+        if return_stats:
+            return y, work[: LM.STATS.itemsize * n_seg].cpu().numpy().view(LM.STATS)
         return y
 
     # -- pause control (csrc/pauses.hip) ------------------------------------------------------------------------------------------------
@@ -1949,7 +2086,8 @@ class CodecEngine:
         return out[0] if len(out) == 1 else out
 
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
-    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None):
+    def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None,
+                      limiter=None):
         """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
         packed frames (ctts_dvae_decode_ragged / ctts_vocos_decode_ragged): each utterance gets zero padding at its own edges in every
         convolution, so its audio does not depend on what else is in the call -- unlike `decode_to_wavs`, whose zero-padded [B, Tmax]
@@ -1971,9 +2109,24 @@ class CodecEngine:
         `pauses` (None: untouched): a pause spec -- one, or a list with one per row, None entries copied through (`trim_pauses`, every
         row alone at its own rate).  It runs behind the time scaler and the resampler and in front of the loudness stage, so the
         milliseconds are those of what is heard and the gain is computed on what is delivered; `off` then holds the trimmed rows'
-        offsets, read back from the device in the call's one extra copy."""
+        offsets, read back from the device in the call's one extra copy.
+        `limiter` (None: off; one bool, or one per row): a flagged row goes through the look-ahead peak limiter (`peak_limit`) behind
+        the loudness stage's gain, which then drops its ceiling term (`loudness_normalize(limiter=)`); without `loudness` at unity
+        gain.  The rows that do not ask for it are not touched by it."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
+        lims = LM.per_row(limiter, len(rows), "decode_ragged")
+        if lims is not None:
+            rates = [self.SAMPLE_RATE] * len(rows) if sample_rate is None else \
+                [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
+            if len(rates) != len(rows):
+                raise ValueError("decode_ragged: one sample rate per row, or one for all")
+            targets = LN.per_row(loudness, len(rows), "decode_ragged")
+            for r in rates:
+                LN.check_rate(r)                                  # every refusal, before the decode
+            out = self.decode_ragged(rows, return_mel, sample_rate, speed, pauses=pauses)
+            self.loudness_normalize(out[0], targets, offsets=out[1], rates=rates, out=out[0], limiter=lims)
+            return out
         specs = PA.per_row(pauses, len(rows), "decode_ragged")
         if specs is not None:
             rates = [self.SAMPLE_RATE] * len(rows) if sample_rate is None else \
@@ -2967,7 +3120,7 @@ class CodecEngine:
         return out
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None, sample_rate: Optional[int] = None,
-                       speed: Optional[float] = None, loudness=None, pauses=None) -> torch.Tensor:
+                       speed: Optional[float] = None, loudness=None, pauses=None, limiter=None) -> torch.Tensor:
         """`Chat._decode_to_wavs` (core.py:513-539): zero-pad the per-row [T_b,768] hidden lists to the
         longest row, DVAE decode, Vocos decode -> [B, 256(2Tmax-1)] float32 on the device.  `pad_to`: pad to that many tokens instead
         (>= the longest row): a data-parallel shard decodes its rows as part of the GLOBAL batch (dist.infer_sharded) -- the reference
@@ -2978,9 +3131,21 @@ class CodecEngine:
         alone (`loudness_normalize`) at the returned rate, the last float32 stage.  `pauses` (None: untouched): a pause spec, one or
         a list with one per row (None entries copied through) -- every row, padding and all, is trimmed alone (`trim_pauses`) at the
         returned rate, behind the resampler and in front of the loudness stage, and the result is then (packed, offsets) instead of
-        [B, n]: the rows' lengths differ."""
+        [B, n]: the rows' lengths differ.  `limiter` (None: off; one bool, or one per row): a flagged row, padding and all, goes
+        through the look-ahead peak limiter (`peak_limit`) behind the loudness stage's gain, which then drops its ceiling term
+        (`loudness_normalize(limiter=)`); without `loudness` at unity gain."""
         if len(result_list) == 0:
             return torch.empty((0,), dtype=torch.float32)
+        lims = LM.per_row(limiter, len(result_list), "decode_to_wavs")
+        if lims is not None:
+            rate = LN.check_rate(self.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+            targets = LN.per_row(loudness, len(result_list), "decode_to_wavs")
+            res = self.decode_to_wavs(result_list, pad_to, sample_rate, speed, pauses=pauses)
+            if isinstance(res, tuple):                                # trimmed rows: (packed, offsets)
+                self.loudness_normalize(res[0], targets, offsets=res[1], rates=rate, out=res[0], limiter=lims)
+                return res
+            wav = res.contiguous()
+            return self.loudness_normalize(wav, targets, rates=rate, out=wav, limiter=lims)
         specs = PA.per_row(pauses, len(result_list), "decode_to_wavs")
         if specs is not None:
             rate = PA.check_rate(self.SAMPLE_RATE if sample_rate is None else int(sample_rate))

@@ -11,7 +11,8 @@
   groups       segments grp[g] .. grp[g+1]-1 (a split_text request's sentences) get ONE loudness and ONE gain: each sentence is filtered
                alone, blocks never span sentences, the gates run over the union of the group's blocks, the peak is the group's peak.
   gain         g = min(10^((target - L) / 20), 10^(MAX_GAIN_DB / 20), CEILING / peak) in float64, rounded once to float32;
-               y = float32(g) * x, one rounding per sample.  No dither, no limiter curve.
+               y = float32(g) * x, one rounding per sample.  No dither.  A group that goes through the look-ahead peak limiter
+               (limiter.py) drops the ceiling term: the limiter runs behind the gain and holds the ceiling sample by sample.
 
 The recurrence is computed exactly and in parallel.  The cascade is the linear system s' = A s + B x, y = C s + D x (`step` is its one
 sample, transposed direct form II, and `homogeneous` probes A^i and h_i = C A^i from it), so a tile of one sub-block runs from zero state
@@ -205,11 +206,12 @@ def gate(z: np.ndarray):
     return OFFSET + 10.0 * math.log10(z[keep2].mean()), len(z), int(keep.sum()), int(keep2.sum())
 
 
-def gain(L: float, peak: float, target):
-    """(float32 gain, which term bound): target None or a silent group -> (1, BOUND_NONE)"""
+def gain(L: float, peak: float, target, limiter: bool = False):
+    """(float32 gain, which term bound): target None or a silent group -> (1, BOUND_NONE).  `limiter`: the group goes through the
+    peak limiter behind this stage (limiter.py), which enforces the ceiling, so the ceiling term is dropped: bound is 0 or 1"""
     if target is None or L == -math.inf:
         return np.float32(1.0), BOUND_NONE
-    terms = [10.0 ** ((target - L) / 20.0), 10.0 ** (MAX_GAIN_DB / 20.0), CEILING / float(peak)]
+    terms = [10.0 ** ((target - L) / 20.0), 10.0 ** (MAX_GAIN_DB / 20.0)] + ([] if limiter else [CEILING / float(peak)])
     b = int(np.argmin(terms))
     return np.float32(terms[b]), b
 
@@ -244,19 +246,30 @@ def tables(n_total: int, offsets=None, groups=None, rates=None, targets=None):
     return off, grp, rates, [check_target(t) for t in tg]
 
 
-def normalize(x: np.ndarray, target, offsets=None, groups=None, rates=None):
-    """the NumPy twin of CodecEngine.loudness_normalize on a host array -> (y float32, stats STATS [n_grp])"""
+def normalize(x: np.ndarray, target, offsets=None, groups=None, rates=None, limiter=None):
+    """the NumPy twin of CodecEngine.loudness_normalize on a host array -> (y float32, stats STATS [n_grp]); with `limiter` (one
+    bool, or one per group) also the limiter's records (limiter.STATS [n_seg]; a segment outside a flagged group has g32 = 0 there):
+    a flagged group's gain drops the ceiling term and every one of its segments goes through limiter.limit_segment alone at it"""
     x = np.ascontiguousarray(x, dtype=np.float32)
     off, grp, rates, tg = tables(len(x), offsets, groups, rates, target)
     y = np.empty_like(x)
     stats = np.zeros(len(grp) - 1, dtype=STATS)
+    lim = lstats = None
+    if limiter is not None:
+        from . import limiter as LM
+        lim = LM.per_row(limiter, len(grp) - 1, "loudness") or [False] * (len(grp) - 1)
+        lstats = np.zeros(len(off) - 1, dtype=LM.STATS)
     for g in range(len(grp) - 1):
         a, b = int(grp[g]), int(grp[g + 1])
         z = np.concatenate([blocks(x[off[s]: off[s + 1]], rates[s]) for s in range(a, b)])
         L, nb, na, nr = gate(z)
         xs = x[off[a]: off[b]]
         peak = np.abs(xs).max()
-        g32, bound = gain(L, peak, tg[g])
-        y[off[a]: off[b]] = g32 * xs
+        g32, bound = gain(L, peak, tg[g], bool(lim and lim[g]))
         stats[g] = (L, peak, g32, nb, na, nr, bound)
-    return y, stats
+        if lim and lim[g]:
+            for s in range(a, b):
+                y[off[s]: off[s + 1]], lstats[s] = LM.limit_segment(x[off[s]: off[s + 1]], rates[s], g32)
+        else:
+            y[off[a]: off[b]] = g32 * xs
+    return (y, stats) if limiter is None else (y, stats, lstats)

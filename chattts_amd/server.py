@@ -97,7 +97,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
                stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
-               pauses: bool = False):
+               pauses: bool = False, limiter: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -163,7 +163,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     are capped on the device, in front of the loudness stage and the 16-bit conversion (Chat.infer(pauses=) /
     SpeechBatcher.submit(pauses=)), in whatever format, rate and speed the other options allow; false or null leaves the audio alone;
     a wrong type, an unknown field or a value out of range gets a 400, `"stream": true` with it too (the run state is not carried
-    across chunks), and /health carries `"pauses": true`."""
+    across chunks), and /health carries `"pauses": true`.  `limiter=True` (default off: every response, status, warning and /health
+    body is as without it, a `"limiter"` key is ignored with the "unsupported parameters" warning): a non-streamed request body may
+    carry `"limiter": true`, with or without `"loudness"` -- the look-ahead peak limiter (chattts_amd/limiter.py) runs on the device
+    behind the loudness stage's gain, which then drops its ceiling term, or at unity gain (Chat.infer(limiter=) /
+    SpeechBatcher.submit(limiter=)): no sample exceeds -1 dBFS and one loud peak no longer decides the level; false or null leaves
+    the audio alone; a value that is no boolean gets a 400, `"stream": true` with it too (the look-ahead is not carried across
+    chunks), and /health carries `"limiter": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -237,6 +243,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     if pauses:
         from . import pauses as PA
         allowed = allowed | {"pauses"}
+    if limiter:
+        from . import loudness as LN
+        allowed = allowed | {"limiter"}
 
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
         model: str = "tts-1"
@@ -261,8 +270,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     stream_speed=12000, pass_first_n_batches=2)
 
     def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None,
-              as_flac: bool = False, lufs: Optional[float] = None, trim=None):     # openai_api.py:168-183,207-222
+              as_flac: bool = False, lufs: Optional[float] = None, trim=None, lim: bool = False):     # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if lim:
+            kw = {**kw, "limiter": True}
         if trim is not None:
             kw = {**kw, "pauses": trim}
         if lufs is not None:
@@ -349,6 +360,19 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             if req.stream:
                 raise HTTPException(400, detail="pauses is served for non-streamed requests only: a stream would need the run state "
                                                 "carried across chunks")
+        lim = False                                  # the request's limiter flag where it is honoured
+        if limiter and request_data.get("limiter") is not None:
+            if not isinstance(request_data["limiter"], bool):
+                raise HTTPException(400, detail=f"limiter is true or false (got {request_data['limiter']!r})")
+            lim = request_data["limiter"]
+            if lim:
+                try:
+                    LN.check_rate(rate)
+                except ValueError as e:
+                    raise HTTPException(400, detail=str(e))
+                if req.stream:
+                    raise HTTPException(400, detail="limiter is served for non-streamed requests only: the look-ahead is not carried "
+                                                    "across chunks")
         refine = refine_of(request_data)
         rkw = {} if refine is None else {"refine": refine}
         if refine is not None and req.stream and not pool_streams:
@@ -450,13 +474,17 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     rkw = {**rkw, "loudness": lufs}
                 if trim is not None:
                     rkw = {**rkw, "pauses": trim}
+                if lim:
+                    rkw = {**rkw, "limiter": True}
                 wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw, **ekw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:
             async with app.state.model_lock:
                 try:
-                    if trim is not None:
+                    if lim:
+                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, True)
+                    elif trim is not None:
                         wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim)
                     elif lufs is not None:
                         wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs)
@@ -514,6 +542,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["stream_flac"] = True
         if pauses:
             out["pauses"] = True
+        if limiter:
+            out["limiter"] = True
         return out
 
     return app

@@ -42,6 +42,7 @@ from . import _lib
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
+from . import limiter as LM
 from . import pauses as PA
 from . import resample as RS
 from . import timescale as TS
@@ -666,6 +667,7 @@ class _Job:
     flac_slot: Optional[int] = None        # a FLAC stream: its stream of the encoder, opened at its first chunk
     loudness: Optional[float] = None       # a target in LUFS (non-streamed only); None: the level is left alone
     pauses: object = None                  # a pauses.PauseSpec (non-streamed only); None: the silence is left alone
+    limiter: bool = False                  # the look-ahead peak limiter behind the loudness stage's gain (non-streamed only)
 
     @property
     def is_stream(self) -> bool:
@@ -719,6 +721,8 @@ def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding"
         kw["loudness"] = [j.loudness for j in jobs]
     if any(j.pauses is not None for j in jobs):
         kw["pauses"] = [j.pauses for j in jobs]
+    if any(j.limiter for j in jobs):
+        kw["limiter"] = [j.limiter for j in jobs]
     return kw
 
 
@@ -847,7 +851,7 @@ class SpeechBatcher:
 
     # -- public -------------------------------------------------------------------------------------------------------------
     def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None,
-               encoding=None, speed=None, flac: bool = False, loudness=None, pauses=None) -> Future:
+               encoding=None, speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
@@ -871,7 +875,13 @@ class SpeechBatcher:
         `pauses` (None: untouched; True, a pauses.PauseSpec or a dict of its fields): the serial call's `pauses=` -- edge silence
         trimmed and long pauses capped on the device, behind the resampler and in front of the loudness stage; requests that finish
         together with different specs, or none, still share the one ragged decode and ONE `CodecEngine.trim_pauses` call (a request
-        without a spec is copied through it; every sentence of a split request is trimmed alone)."""
+        without a spec is copied through it; every sentence of a split request is trimmed alone).
+        `limiter=True`: the serial call's `limiter=` -- the look-ahead peak limiter behind the loudness stage's gain, which then drops
+        its ceiling term (at unity gain without `loudness`); requests that finish together, with and without it, still share the one
+        decode, and the ones without it are not touched by it (every sentence of a split request is limited alone)."""
+        limiter = LM.check_flag(limiter, "submit")
+        if limiter:
+            LN.check_rate(24000 if sample_rate is None else sample_rate)
         pauses = PA.check(pauses)
         if pauses is not None:
             PA.check_rate(24000 if sample_rate is None else sample_rate)
@@ -890,7 +900,7 @@ class SpeechBatcher:
         fut: Future = Future()
         fut.rid = next(self._ids)
         self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding,
-                          speed=speed, flac=bool(flac), loudness=loudness, pauses=pauses))
+                          speed=speed, flac=bool(flac), loudness=loudness, pauses=pauses, limiter=limiter))
         return fut
 
     def cancel(self, fut: Future) -> None:
@@ -899,7 +909,7 @@ class SpeechBatcher:
         self._in.put(_Cancel(fut.rid))
 
     def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None,
-                      speed=None, flac: bool = False, loudness=None, pauses=None) -> SpeechStream:
+                      speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
@@ -918,7 +928,9 @@ class SpeechBatcher:
         chunks of the same request without `flac`.  The chunks of all FLAC streams due at one poll share ONE encoder step behind the
         one decoder pass (CodecEngine.decode_windows(flac=)); it combines with `sample_rate` and `speed` as far as the batcher serves
         those, not with `encoding`.  `loudness` is refused: an integrated loudness needs the whole utterance.  `pauses` is refused: the
-        run state would have to be carried across chunks."""
+        run state would have to be carried across chunks.  `limiter` is refused: the look-ahead is not carried across chunks."""
+        if LM.check_flag(limiter, "submit_stream"):
+            raise ValueError("limiter applies to non-streamed requests only (the look-ahead is not carried across chunks)")
         if PA.check(pauses) is not None:
             raise ValueError("pauses applies to non-streamed requests only (a stream would need the run state carried across chunks)")
         if LN.check_target(loudness) is not None:
@@ -1281,7 +1293,7 @@ class SpeechBatcher:
         self.lock.acquire()
 
     def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None, flac: bool = False, loudness=None,
-               pauses=None) -> np.ndarray:
+               pauses=None, limiter: bool = False) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
@@ -1290,18 +1302,19 @@ class SpeechBatcher:
         wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}),
                                        **({} if speed is None else {"speed": float(speed)}),
                                        **({} if loudness is None else {"loudness": float(loudness)}),
-                                       **({} if pauses is None else {"pauses": pauses}))[0]
+                                       **({} if pauses is None else {"pauses": pauses}),
+                                       **({"limiter": True} if limiter else {}))[0]
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
         if flac:                                                            # converted on the host, encoded by the host twin
             return np.frombuffer(FLAC.encode(pcm, 24000 if sample_rate is None else int(sample_rate)), np.uint8)
         return pcm if encoding is None else G711.encode(pcm, encoding)      # converted on the host, companded by the host twin
 
     def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None, flac=None, loudness=None,
-                     pauses=None) -> list:
+                     pauses=None, limiter=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
         returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000);
         `speeds`: one speed per request (None: 1.0); `loudness`: one target per request (None entries: left alone); `pauses`: one spec
-        per request (None entries: copied through the one `trim_pauses` call)"""
+        per request (None entries: copied through the one `trim_pauses` call); `limiter`: one flag per request"""
         out: list = [RuntimeError(_NO_AUDIO) if h.shape[0] == 0 else None for h in hids]
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
@@ -1317,6 +1330,8 @@ class SpeechBatcher:
                 kw["loudness"] = [loudness[i] for i in live]
             if pauses is not None and any(pauses[i] is not None for i in live):
                 kw["pauses"] = [pauses[i] for i in live]
+            if limiter is not None and any(limiter[i] for i in live):
+                kw["limiter"] = [bool(limiter[i]) for i in live]
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out

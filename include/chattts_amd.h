@@ -436,6 +436,37 @@ int ctts_loudness_normalize_ragged(const float* x, float* y, const int64_t* off_
                                    const double* target_dev, const double* target_host, void* stats, void* scratch, size_t scratch_bytes,
                                    void* stream);
 
+/* ctts_loudness_normalize_ragged in front of the peak limiter: the same call and the same refusals, with lim (int32 per group, 0 or 1,
+ * on the device and the host) and gain_out (float32 [n_seg] on the device).  A group with lim[g] = 1 gets
+ * g = min(10^((target[g] - L) / 20), 10^(30 / 20)) -- the ceiling term is dropped, the limiter enforces it, so its record's bound is 0
+ * or 1 -- and its segments are NOT scaled here: they are copied where y is not x and left alone where it is.  Every segment's group
+ * gain is written to gain_out, where a ctts_peak_limit_ragged call on the same stream reads it: measurement and limiter are
+ * stream-ordered with no host round trip.  A group with lim[g] = 0 is treated as by ctts_loudness_normalize_ragged (in place, a gain
+ * of exactly 1 writes nothing).  Scratch: ctts_loudness_normalize_ragged_scratch_bytes. */
+int ctts_loudness_limited_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                 const int32_t* rate_dev, const int32_t* rate_host, const double* coef_dev, const double* coef_host,
+                                 int32_t n_rates, const int32_t* grp_dev, const int32_t* grp_host, int32_t n_grp,
+                                 const double* target_dev, const double* target_host, const int32_t* lim_dev, const int32_t* lim_host,
+                                 float* gain_out, void* stats, void* scratch, size_t scratch_bytes, void* stream);
+
+/* The look-ahead peak limiter (the definition, once, is chattts_amd/limiter.py): packed float32 segments x[off[s], off[s+1]) at rate[s] Hz
+ * (a multiple of 10 in 8000 .. 48000; W = rate / 100 samples is 10 ms) with the float32 pre-gain gain[s] (on the device; it may be the
+ * gain_out of ctts_loudness_limited_ragged), every segment as if alone: u = gain x; r = 1 where |u| <= T, else T / |u|, with
+ * T = float32(C32 (1 - 2^-22)) and C32 = float32(10^(-1 / 20)); m the minimum of r over |k - j| <= W (1 outside the segment); s the mean
+ * of m over |j - i| <= W, a float64 sum and division rounded once to float32; y = s u.  So |y| <= C32, a segment with no sample over T
+ * comes out as gain x bit for bit, and a NaN passes through.  y may be x (otherwise the two do not overlap), both 16-byte aligned.  The
+ * float64 sum is exact, and with it the result independent of the order of summation, while every r >= 2^-19 (gain |x| up to about 4e5).
+ * stats: [n_seg] records of 16 bytes on the device -- float32 the pre-gain, min s; int32 the samples with |u| > T, the samples with
+ * s < 1.  A segment's samples and record do not depend on what it is packed with.  The offset and rate tables are given on the device
+ * and the host (the two must agree).  Refused before anything is launched: a null pointer, offsets that do not ascend from 0, an empty
+ * segment, a pack of 2^31 - 4096 samples or more, more than 65535 segments, a rate outside the range or not a multiple of 10,
+ * misaligned buffers, y overlapping x in part, scratch under the companion function's size (0: the offsets were refused).
+ * Stream-ordered, four launches: the records, the count of samples over T per tile of 2048, the gain curve of the tiles that have
+ * such a sample in or next to them (the others leave at once), and y. */
+size_t ctts_peak_limit_ragged_scratch_bytes(const int64_t* off_host, int32_t n_seg);
+int ctts_peak_limit_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg, const int32_t* rate_dev,
+                           const int32_t* rate_host, const float* gain_dev, void* stats, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Pause control: packed float32 segments in[off[s], off[s+1]) lose edge silence and long inner pauses, frame by frame (the definition,
  * once, is chattts_amd/pauses.py).  Segment s has the row rows[8 s ..]: F (samples per 10 ms frame, 80 .. 480), pad, lead, tail, P (frames;
  * P = 0: the segment is copied through), thr (float32 bits, a frame is active when some sample has !(|x| < thr)), the offset of its
