@@ -25,16 +25,16 @@ import torch
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
-from . import limiter as LM
+from . import outchain
 from . import pauses as PA
 from . import resample as RS
-from . import timescale as TS
 from . import weights as W
 from .audio import float_to_int16
 from .config import GPT
 from .dvae import DvaeEngine
 from .engine import CodecEngine, Context, GenerationOutputs, GptEngine, gen_logits, keep_offsets, ragged_views
 from .frontend import Normalizer, Speaker, Tokenizer, apply_speaker
+from .outchain import Plan
 
 
 @dataclass(repr=False, eq=False)
@@ -69,60 +69,6 @@ class InferCodeParams:            # core.py:195-206 (+ the RefineTextParams fiel
     stream_batch: int = 24
     stream_speed: int = 12000
     pass_first_n_batches: int = 2
-
-
-def _speed_kw(speed) -> dict:
-    """the decode calls' `speed=` argument: nothing for None or 1.0 everywhere (today's call, argument for argument); ValueError for a
-    speed outside 0.5 .. 2.0"""
-    if speed is None:
-        return {}
-    one = [speed] if np.ndim(speed) == 0 else list(speed)
-    if all(TS.quantize(v)[0] == TS.DEN for v in one):
-        return {}
-    return {"speed": float(speed) if np.ndim(speed) == 0 else [float(v) for v in speed]}
-
-
-def _loudness_kw(loudness) -> dict:
-    """the decode calls' `loudness=` argument: nothing for None, alone or everywhere (today's call, argument for argument); ValueError
-    for a target outside -40 .. -5 LUFS"""
-    if loudness is None:
-        return {}
-    vals = [LN.check_target(v) for v in ([loudness] if np.ndim(loudness) == 0 else list(loudness))]
-    if all(v is None for v in vals):
-        return {}
-    return {"loudness": vals[0] if np.ndim(loudness) == 0 else vals}
-
-
-def _limiter_kw(limiter) -> dict:
-    """the decode calls' `limiter=` argument: nothing for None or False, alone or everywhere (today's call, argument for argument);
-    ValueError for anything but bools"""
-    if limiter is None:
-        return {}
-    vals = [LM.check_flag(v) for v in ([limiter] if np.ndim(limiter) == 0 else list(limiter))]
-    if not any(vals):
-        return {}
-    return {"limiter": True if np.ndim(limiter) == 0 else vals}
-
-
-def _level_kw(loudness, limiter) -> dict:
-    """both arguments of the last float32 stage (CodecEngine.loudness_normalize and the peak limiter behind it)"""
-    return {**_loudness_kw(loudness), **_limiter_kw(limiter)}
-
-
-def _lim(lkw: dict) -> dict:
-    """the `limiter=` argument of a CodecEngine.loudness_normalize call: nothing where it is not asked for"""
-    return {"limiter": lkw["limiter"]} if "limiter" in lkw else {}
-
-
-def _pauses_kw(pauses) -> dict:
-    """the decode calls' `pauses=` argument: nothing for None, alone or everywhere (today's call, argument for argument); ValueError
-    for a bad spec (pauses.check)"""
-    if pauses is None:
-        return {}
-    vals = [PA.check(v) for v in (list(pauses) if isinstance(pauses, (list, tuple)) else [pauses])]
-    if all(v is None for v in vals):
-        return {}
-    return {"pauses": vals if isinstance(pauses, (list, tuple)) else vals[0]}
 
 
 def split_sentences(text: str) -> List[str]:
@@ -356,52 +302,33 @@ class Chat:
         device (CodecEngine.peak_limit; the definition of limiter.py) where the loudness stage is, behind its gain: that gain then
         drops the -1 dBFS ceiling term, and the limiter holds the ceiling sample by sample.  Without `loudness` it runs at unity
         gain."""
-        skw = _speed_kw(speed)
-        lkw = _level_kw(loudness, limiter)
-        pkw = _pauses_kw(pauses)
+        plan = Plan.given("decode_to_wavs", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
-        if ragged:
-            if pad_to is not None:
-                raise ValueError("ragged decoding decodes every row at its own length: pad_to does not apply")
-            if len(result_list) == 0:
-                return []
-            wav, off = self.codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw, **pkw)
-            return ragged_views(self.codec.to_host(wav), off)
+        if ragged and pad_to is not None:
+            raise ValueError("ragged decoding decodes every row at its own length: pad_to does not apply")
         if len(result_list) == 0:
-            return np.array([], dtype=np.float32)
-        if pkw:
-            wav, off = self._decode_batch_trimmed(result_list, use_decoder, pad_to, sample_rate, skw, lkw, pkw["pauses"])
-            return ragged_views(self.codec.to_host(wav), off)
-        if use_decoder:
-            return self.codec.to_host(self.codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate, **skw, **lkw))
-        wav = self.codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to))
-        if skw:
-            wav = self.codec.time_scale(wav, skw["speed"])
-        if sample_rate is not None:
-            wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
-        if lkw:
-            wav = self.codec.loudness_normalize(wav, lkw.get("loudness"), rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate),
-                                                **_lim(lkw))
-        return self.codec.to_host(wav)
+            return [] if ragged else np.array([], dtype=np.float32)
+        wav, off = self._decode_float(result_list, use_decoder, ragged, pad_to, plan)
+        host = self.codec.to_host(wav)
+        return host if off is None else ragged_views(host, off)
 
-    def _decode_batch_trimmed(self, result_list, use_decoder: bool, pad_to, sample_rate, skw: dict, lkw: dict, pauses):
-        """the zero-padded batch decode of the plain calls with the pause stage behind it: time scaler, resampler, `trim_pauses` (every
-        row alone), loudness -> (packed float32 device tensor, host offsets), the ragged decoder's layout"""
+    def _decode_float(self, result_list, use_decoder: bool, ragged: bool, pad_to, plan: Plan, own_chain: bool = False):
+        """the front half of the decode calls: the rows through the acoustic decoder and the output chain of `plan` ("The
+        output chain") -> (float32 device waveform, host offsets), offsets None for a [B, n] batch.  The engine's decode calls take
+        the options and run the chain; Chat runs it (outchain.run) on the DVAE-codes path and, with `own_chain`, behind the plain
+        zero-padded decode of decode_to_pcm16 (the last stage then writes a tensor of its own, not the decode's).  Rows that the
+        pause stage trims leave either path as a pack."""
         codec = self.codec
-        if use_decoder:
-            return codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=sample_rate, **skw, **lkw, pauses=pauses)
-        wav = codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to))
-        if skw:
-            wav = codec.time_scale(wav, skw["speed"])
-        if sample_rate is not None:
-            wav = codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
-        rate = CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)
-        wav, off = codec.trim_pauses(wav, pauses, rates=rate)
-        if lkw:
-            wav = codec.loudness_normalize(wav, lkw.get("loudness"), offsets=off, rates=rate, out=wav, **_lim(lkw))
-        return wav, off
+        if ragged:
+            return codec.decode_ragged(list(result_list), sample_rate=plan.sample_rate, **plan.kwargs())
+        if use_decoder and (plan.pauses is not None or not own_chain):
+            res = codec.decode_to_wavs(result_list, pad_to=pad_to, sample_rate=plan.sample_rate, **plan.kwargs())
+        else:
+            wav = codec.decode_to_wavs(result_list) if use_decoder else codec.vocos_decode(self.dvae.decode_codes(result_list, pad_to=pad_to))
+            res = outchain.run(codec, wav, plan)
+        return res if isinstance(res, tuple) else (res, None)
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
                         product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None,
@@ -431,33 +358,19 @@ class Chat:
         `limiter` (None / False: off; True, also one flag per row): `wav` above is the waveform behind the look-ahead peak limiter
         (CodecEngine.peak_limit), which runs where the loudness stage is, at its gain without the ceiling term (unity without
         `loudness`): no sample that is converted exceeds -1 dBFS, and a peak above full scale is limited instead of clipped."""
-        skw = _speed_kw(speed)
-        lkw = _level_kw(loudness, limiter)
-        pkw = _pauses_kw(pauses)
+        plan = Plan.given("decode_to_pcm16", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
-        flags = self._flac_flags(flac, len(result_list), encoding, per_row=ragged, who="decode_to_pcm16")
-        if flags is not None:
-            return self._decode_to_flac(result_list, use_decoder, strip, product, ragged, sample_rate, flags, skw, encoding, **lkw, **pkw)
-        if ragged:
-            if encoding is None:
-                return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, **skw, **lkw, **pkw)
-            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding, **skw, **lkw, **pkw)
-        G711.check_encoding(encoding)
+        encs, flags = self._formats(encoding, flac, len(result_list), per_row=ragged, who="decode_to_pcm16")
         if len(result_list) == 0:
             return []
-        if pkw:
-            decoded = self._decode_batch_trimmed(result_list, use_decoder, None, sample_rate, skw, lkw, pkw["pauses"])
-            return self._decode_to_pcm16_ragged(result_list, strip, product, sample_rate, encoding, decoded=decoded)
-        wav = self.codec.decode_to_wavs(result_list) if use_decoder else self.codec.vocos_decode(self.dvae.decode_codes(result_list))
-        if skw:
-            wav = self.codec.time_scale(wav, skw["speed"])
-        if sample_rate is not None:
-            wav = self.codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
-        if lkw:
-            wav = self.codec.loudness_normalize(wav, lkw.get("loudness"), rates=CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate),
-                                                **_lim(lkw))
+        wav, off = self._decode_float(result_list, use_decoder, ragged, None, plan, own_chain=True)
+        if flags is not None:
+            return self._decode_to_flac(wav, off, plan.row_rates(len(result_list)), flags, strip, product, encs)
+        if off is not None:
+            return self._decode_to_pcm16_ragged(wav, off, strip, product, encs)
+        encoding = None if encs is None else encs[0]
         pcm, keep = self.codec.float_to_int16(wav, per_row=True, product=product, keep_thr=1e-5 if strip else None)
         if encoding is not None:       # codes | keep masks in one buffer: one copy
             B, n = int(pcm.shape[0]), int(pcm.shape[1])
@@ -499,60 +412,45 @@ class Chat:
             raise ValueError(f"{who}: flac does not go with an encoding (a FLAC file holds the 16-bit samples; one entry per row)")
         return flags
 
-    def _decode_to_flac(self, result_list, use_decoder: bool, strip: bool, product: str, ragged: bool, sample_rate, flags, skw,
-                        encoding=None, loudness=None, pauses=None, limiter=None) -> List[np.ndarray]:
-        """`decode_to_pcm16` with at least one row as a FLAC file: the decode of the plain call, then the grouped conversion with one
-        group per row (the same samples; slots that start on multiples of 8 and a count header on the device) and the encoder behind it"""
-        B = len(result_list)
-        if B == 0:
-            return []
-        codec = self.codec
-        lkw = {**({} if loudness is None else {"loudness": loudness}), **({} if limiter is None else {"limiter": limiter})}
-        if ragged:
-            wav, off = codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw, **lkw, **({} if pauses is None else {"pauses": pauses}))
-            rates = [CodecEngine.SAMPLE_RATE] * B if sample_rate is None else ([int(sample_rate)] * B if np.ndim(sample_rate) == 0 else
-                                                                                [int(r) for r in sample_rate])
-        elif pauses is not None:
-            wav, off = self._decode_batch_trimmed(result_list, use_decoder, None, sample_rate, skw, lkw, pauses)
-            rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * B
-        else:
-            wav = codec.decode_to_wavs(result_list) if use_decoder else codec.vocos_decode(self.dvae.decode_codes(result_list))
-            if skw:
-                wav = codec.time_scale(wav, skw["speed"])
-            if sample_rate is not None:
-                wav = codec.resample(wav, CodecEngine.SAMPLE_RATE, int(sample_rate))
+    @staticmethod
+    def _formats(encoding, flac, n: int, per_row: bool, who: str, unit: str = "row"):
+        """the `encoding=` and `flac=` options of the 16-bit calls, once for every path and before the decode -> (encs, flags): one
+        encoding per row, None unless a row is companded or some row is a FLAC file; one flac flag per row, None when none is set
+        (`_flac_flags`, which also refuses a row that asks for both)"""
+        flags = Chat._flac_flags(flac, n, encoding, per_row, who)
+        if not per_row:
+            G711.check_encoding(encoding)
+        if encoding is None or n == 0:
+            return None, flags
+        encs = [encoding] * n if isinstance(encoding, str) else list(encoding)
+        if flags is not None:
+            return encs, flags
+        if len(encs) != n:
+            raise ValueError(f"{who}: one encoding per {unit}, or one for all")
+        return (encs if any(G711.check_encoding(e) is not None for e in encs) else None), None
+
+    def _decode_to_flac(self, wav, off, rates, flags, strip: bool, product: str, encs=None, grp=None) -> List[np.ndarray]:
+        """a decoded waveform -- [B, n], or packed with `off` -- with at least one row (with `grp`: one request, its sentences) as a
+        FLAC file at its entry of `rates`: the grouped conversion with one group per row (the same samples; slots that start on
+        multiples of 8 and a count header on the device) and the encoder behind it"""
+        if off is None:
             wav = wav.contiguous()
-            rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * B
-            if lkw:
-                wav = codec.loudness_normalize(wav, loudness, rates=rates[0], **_lim(lkw))
-            off = np.arange(B + 1, dtype=np.int64) * int(wav.shape[1])
+            off = np.arange(wav.shape[0] + 1, dtype=np.int64) * int(wav.shape[1])
             wav = wav.view(-1)
-        encs = None if encoding is None else ([encoding] * B if isinstance(encoding, str) else list(encoding))
-        out = codec.float_to_int16_groups_flac(wav, off, np.arange(B + 1, dtype=np.int32), [r if f else None for r, f in zip(rates, flags)],
-                                               product=product, keep_thr=1e-5 if strip else None, encodings=encs)
+        grp = np.arange(len(flags) + 1, dtype=np.int32) if grp is None else grp
+        out = self.codec.float_to_int16_groups_flac(wav, off, grp, [r if f else None for r, f in zip(rates, flags)], product=product,
+                                                    keep_thr=1e-5 if strip else None, encodings=encs)
         return [p if p.dtype == np.uint8 else p.copy() for p in out]
 
-    def _decode_to_pcm16_ragged(self, result_list, strip: bool, product: str, sample_rate=None, encoding=None, speed=None,
-                                loudness=None, pauses=None, decoded=None, limiter=None) -> List[np.ndarray]:
-        """decode_to_pcm16(..., ragged=True): every row decoded as if alone (CodecEngine.decode_ragged), one peak per row, and the
-        PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's result equals
-        `float_to_int16(w[np.abs(w) > 1e-5])` of its alone decode w.  `encoding` (one, or one per row; None entries stay int16): the
-        companded rows are converted by one launch behind the conversion, and the codes travel with the keep masks in the one copy
-        (the PCM16 samples too when some row stays int16).  `speed`, `loudness`, `limiter` and `pauses` (one, or one per row) go to the ragged decode;
-        `decoded`: the (packed, offsets) of a decode that has run already (the trimmed rows of a zero-padded batch)."""
-        if len(result_list) == 0:
-            return []
+    def _decode_to_pcm16_ragged(self, wav, off, strip: bool, product: str, encs=None) -> List[np.ndarray]:
+        """the back half of decode_to_pcm16 for a pack (the ragged decode's rows, or the trimmed rows of a zero-padded batch): one
+        peak per row, and the PCM + keep masks of the whole group cross PCIe in ONE copy (both live in one device buffer).  Row b's
+        result equals `float_to_int16(w[np.abs(w) > 1e-5])` of its waveform w.  `encs` (one per row, None entries stay int16; None:
+        no row is companded): the companded rows are converted by one launch behind the conversion, and the codes travel with the
+        keep masks in the one copy (the PCM16 samples too when some row stays int16)."""
         codec = self.codec
-        skw = {**({} if speed is None else {"speed": speed}), **({} if loudness is None else {"loudness": loudness}),
-               **({} if pauses is None else {"pauses": pauses}), **({} if decoded is None else {"decoded": decoded}),
-               **({} if limiter is None else {"limiter": limiter})}
-        if encoding is not None:
-            encs = [encoding] * len(result_list) if isinstance(encoding, str) else list(encoding)
-            if len(encs) != len(result_list):
-                raise ValueError("decode_to_pcm16: one encoding per row, or one for all")
-            if any(G711.check_encoding(e) is not None for e in encs):
-                return self._decode_to_g711_ragged(result_list, strip, product, sample_rate, encs, **skw)
-        wav, off = decoded if decoded is not None else codec.decode_ragged(list(result_list), sample_rate=sample_rate, **skw)
+        if encs is not None:
+            return self._decode_to_g711_ragged(wav, off, strip, product, encs)
         n = wav.numel()
         kb = int(keep_offsets(off)[-1]) if strip else 0
         blob = torch.empty(((2 * n + kb + 15) // 16 * 16,), dtype=torch.uint8, device=wav.device)
@@ -567,17 +465,12 @@ class Chat:
         keep_h = host[2 * n: 2 * n + kb]
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
-    def _decode_to_g711_ragged(self, result_list, strip: bool, product: str, sample_rate, encs, speed=None, loudness=None, pauses=None,
-                               decoded=None, limiter=None) -> List[np.ndarray]:
+    def _decode_to_g711_ragged(self, wav, off, strip: bool, product: str, encs) -> List[np.ndarray]:
         """`_decode_to_pcm16_ragged` with at least one companded row.  The device buffer is int16 samples | codes | keep masks; rows
         that share a law and follow each other make one range.  A range starts on a multiple of 8 elements: rows resampled to
         another rate sit at arbitrary offsets, so a call that mixes laws over such rows goes through the grouped conversion instead
         (one group per row: the same bytes, slots that start on multiples of 8)."""
         codec = self.codec
-        wav, off = decoded if decoded is not None else codec.decode_ragged(
-            list(result_list), sample_rate=sample_rate, **({} if speed is None else {"speed": speed}),
-            **({} if loudness is None else {"loudness": loudness}), **({} if pauses is None else {"pauses": pauses}),
-            **({} if limiter is None else {"limiter": limiter}))
         runs = []                     # [first row, one past the last, encoding]
         for i, e in enumerate(encs):
             if runs and runs[-1][2] == e:
@@ -640,46 +533,20 @@ class Chat:
         grp = np.zeros(len(groups) + 1, np.int32)
         np.cumsum([len(g) for g in groups], out=grp[1:])
         codec = self.codec
-        flags = self._flac_flags(flac, len(groups), encoding, per_row=True, who="decode_split_to_pcm16")
-        rates = [CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)] * len(groups) if np.ndim(sample_rate) == 0 else None
-        if sample_rate is not None and np.ndim(sample_rate) != 0:
-            if len(sample_rate) != len(groups):
-                raise ValueError("decode_split_to_pcm16: one sample rate per request, or one for all")
-            rates = [int(r) for r in sample_rate]
-            sample_rate = [int(r) for r, g in zip(sample_rate, groups) for _ in g]
-        skw = _speed_kw(speed)
-        if skw and np.ndim(speed) != 0:
-            if len(speed) != len(groups):
-                raise ValueError("decode_split_to_pcm16: one speed per request, or one for all")
-            skw = {"speed": [float(v) for v, g in zip(speed, groups) for _ in g]}
-        lkw = _level_kw(loudness, limiter)
-        if "loudness" in lkw and np.ndim(loudness) != 0 and len(loudness) != len(groups):
-            raise ValueError("decode_split_to_pcm16: one loudness target per request, or one for all")
-        if "limiter" in lkw and np.ndim(limiter) != 0 and len(limiter) != len(groups):
-            raise ValueError("decode_split_to_pcm16: one limiter flag per request, or one for all")
-        pkw = _pauses_kw(pauses)
-        if pkw and isinstance(pauses, (list, tuple)):
-            if len(pauses) != len(groups):
-                raise ValueError("decode_split_to_pcm16: one pause spec per request, or one for all")
-            pkw = {"pauses": [v for v, g in zip(pkw["pauses"], groups) for _ in g]}
-        wav, off = codec.decode_ragged([h for g in groups for h in g], sample_rate=sample_rate, **skw, **pkw)
-        if lkw:
-            wav = codec.loudness_normalize(wav, lkw.get("loudness"), offsets=off, groups=grp, out=wav,
-                                           rates=[r for r, g in zip(rates, groups) for _ in g], **_lim(lkw))
+        encs, flags = self._formats(encoding, flac, len(groups), per_row=True, who="decode_split_to_pcm16", unit="request")
+        plan = Plan.given("decode_split_to_pcm16", sample_rate, speed, loudness, pauses, limiter)
+        rates = plan.row_rates(len(groups))
+        plan = plan.per_sentence(groups)
+        rows = [h for g in groups for h in g]
+        wav, off = codec.decode_ragged(rows, sample_rate=plan.sample_rate, **plan.kwargs("speed", "pauses"))
+        if plan.levels:                                               # ONE gain per request: the stage runs here, over the group table
+            wav = codec.loudness_normalize(wav, plan.loudness, offsets=off, groups=grp, out=wav, rates=plan.row_rates(len(rows)),
+                                           **plan.kwargs("limiter"))
         if flags is not None:
-            encs = None if encoding is None else ([encoding] * len(groups) if isinstance(encoding, str) else list(encoding))
-            out = codec.float_to_int16_groups_flac(wav, off, grp, [r if f else None for r, f in zip(rates, flags)], product=product,
-                                                   keep_thr=1e-5 if strip else None, encodings=encs)
-            return [p if p.dtype == np.uint8 else p.copy() for p in out]
-        if encoding is not None:
-            encs = [encoding] * len(groups) if isinstance(encoding, str) else list(encoding)
-            if len(encs) != len(groups):
-                raise ValueError("decode_split_to_pcm16: one encoding per request, or one for all")
-            if any(G711.check_encoding(e) is not None for e in encs):
-                blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None, encodings=encs)
-                return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts, encs)]
-        blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None)
-        return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts)]
+            return self._decode_to_flac(wav, off, rates, flags, strip, product, encs, grp=grp)
+        blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None,
+                                                   **({} if encs is None else {"encodings": encs}))
+        return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts, *(() if encs is None else (encs,)))]
 
     def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None,
                              rs_streams=None, flac=None, flac_streams=None) -> List[np.ndarray]:
@@ -1011,21 +878,21 @@ class Chat:
         resampler and `pauses`, in front of the silence strip, the 16-bit conversion, the companding and FLAC.  The sentences of a
         split request (one flag only) are limited one by one under the request's ONE gain.  A streamed call with it raises: the
         look-ahead is not carried across chunks."""
-        mkw = _limiter_kw(limiter)
+        mkw = Plan.given("infer", limiter=limiter).kwargs()
         if mkw and stream:
             raise ValueError("limiter applies to non-streamed inference only (the look-ahead is not carried across chunks)")
         if mkw and split_text and np.ndim(limiter) != 0:
             raise ValueError("a split_text request is one waveform: it takes one limiter flag")
         if mkw:
             LN.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
-        pkw = _pauses_kw(pauses)
+        pkw = Plan.given("infer", pauses=pauses).kwargs()
         if pkw and stream:
             raise ValueError("pauses applies to non-streamed inference only (a stream would need the run state carried across chunks)")
         if pkw and split_text and isinstance(pauses, (list, tuple)):
             raise ValueError("a split_text request is one waveform: it takes one pause spec")
         if pkw:
             PA.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
-        lkw = _loudness_kw(loudness)
+        lkw = Plan.given("infer", loudness=loudness).kwargs()
         if lkw and stream:
             raise ValueError("loudness applies to non-streamed inference only (an integrated loudness needs the whole utterance; a "
                              "stream would need a running measure)")
@@ -1046,7 +913,7 @@ class Chat:
             if stream and split_text:
                 raise ValueError("a streamed FLAC does not go with split_text (every split batch would end the stream)")
             FLAC.rate_code(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
-        skw = _speed_kw(speed)
+        skw = Plan.given("infer", speed=speed).kwargs()
         if stream and skw and not stream_time_scale:
             raise ValueError("speed applies to non-streamed inference only (a chunk's frames depend on the path of everything before it; "
                              "pass stream_time_scale=True to carry the path across chunks)")
@@ -1106,7 +973,7 @@ class Chat:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
         thr = np.float32(1e-5)
         if split_host:
-            res_gen = [self._normalize_request([w for wavs in res_gen for w in wavs], lkw.get("loudness"), sample_rate, **_lim(lkw))]
+            res_gen = [self._normalize_request([w for wavs in res_gen for w in wavs], lkw.get("loudness"), sample_rate, **mkw)]
         stripped = [wav[np.abs(wav) > thr] for wavs in res_gen for wav in wavs]   # sample-level strip, also mid-utterance
         if pcm16:      # split_text: ONE concatenated waveform, hence one peak over all sentences -- converted on the host
             one = float_to_int16(np.concatenate(stripped))

@@ -23,6 +23,7 @@ from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
 from . import limiter as LM
+from . import outchain as OC
 from . import pauses as PA
 from . import resample as RS
 from . import timescale as TS
@@ -2115,65 +2116,10 @@ class CodecEngine:
         gain.  The rows that do not ask for it are not touched by it."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
-        lims = LM.per_row(limiter, len(rows), "decode_ragged")
-        if lims is not None:
-            rates = [self.SAMPLE_RATE] * len(rows) if sample_rate is None else \
-                [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
-            if len(rates) != len(rows):
-                raise ValueError("decode_ragged: one sample rate per row, or one for all")
-            targets = LN.per_row(loudness, len(rows), "decode_ragged")
-            for r in rates:
-                LN.check_rate(r)                                  # every refusal, before the decode
-            out = self.decode_ragged(rows, return_mel, sample_rate, speed, pauses=pauses)
-            self.loudness_normalize(out[0], targets, offsets=out[1], rates=rates, out=out[0], limiter=lims)
-            return out
-        specs = PA.per_row(pauses, len(rows), "decode_ragged")
-        if specs is not None:
-            rates = [self.SAMPLE_RATE] * len(rows) if sample_rate is None else \
-                [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
-            if len(rates) != len(rows):
-                raise ValueError("decode_ragged: one sample rate per row, or one for all")
-            targets = LN.per_row(loudness, len(rows), "decode_ragged")
-            for r in rates:                                           # every refusal, before the decode
-                PA.check_rate(r)
-                if targets is not None:
-                    LN.check_rate(r)
-            out = self.decode_ragged(rows, return_mel, sample_rate, speed)
-            wav, off = self.trim_pauses(out[0], specs, offsets=out[1], rates=rates)
-            if targets is not None:
-                self.loudness_normalize(wav, targets, offsets=off, rates=rates, out=wav)
-            return (wav, off, out[2]) if return_mel else (wav, off)
-        targets = LN.per_row(loudness, len(rows), "decode_ragged")
-        if targets is not None:
-            rates = [self.SAMPLE_RATE] * len(rows) if sample_rate is None else \
-                [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
-            if len(rates) != len(rows):
-                raise ValueError("decode_ragged: one sample rate per row, or one for all")
-            for r in rates:
-                LN.check_rate(r)                                  # every refusal, before the decode
-            out = self.decode_ragged(rows, return_mel, sample_rate, speed)
-            self.loudness_normalize(out[0], targets, offsets=out[1], rates=rates, out=out[0])
-            return out
-        if speed is not None:
-            speeds = [float(speed)] * len(rows) if np.ndim(speed) == 0 else [float(v) for v in speed]
-            if len(speeds) != len(rows):
-                raise ValueError("decode_ragged: one speed per row, or one for all")
-            if any(TS.quantize(v)[0] != TS.DEN for v in speeds):
-                out = self.decode_ragged(rows, return_mel)
-                wav, off = self.time_scale_segments(out[0], out[1], speeds)
-                if sample_rate is not None:
-                    rates = [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
-                    if len(rates) != len(rows):
-                        raise ValueError("decode_ragged: one sample rate per row, or one for all")
-                    wav, off = self.resample_segments(wav, off, rates)
-                return (wav, off, out[2]) if return_mel else (wav, off)
-        if sample_rate is not None:
-            rates = [int(sample_rate)] * len(rows) if np.ndim(sample_rate) == 0 else [int(r) for r in sample_rate]
-            if len(rates) != len(rows):
-                raise ValueError("decode_ragged: one sample rate per row, or one for all")
-            out = self.decode_ragged(rows, return_mel)
-            wav, off = self.resample_segments(out[0], out[1], rates)
-            return (wav, off, out[2]) if return_mel else (wav, off)
+        plan = OC.Plan.rows("decode_ragged", len(rows), sample_rate, speed, loudness, pauses, limiter)     # every refusal, before the decode
+        if plan.on:
+            out = self.decode_ragged(rows, return_mel)                # the plain decode, through the public method
+            return (*OC.run(self, out[0], plan, offsets=out[1], in_place=True), *out[2:])
         lens = [int(r.size(0)) for r in rows]
         if min(lens) < 1:
             raise ValueError("decode_ragged: every row needs at least one token")
@@ -3136,36 +3082,9 @@ class CodecEngine:
         (`loudness_normalize(limiter=)`); without `loudness` at unity gain."""
         if len(result_list) == 0:
             return torch.empty((0,), dtype=torch.float32)
-        lims = LM.per_row(limiter, len(result_list), "decode_to_wavs")
-        if lims is not None:
-            rate = LN.check_rate(self.SAMPLE_RATE if sample_rate is None else int(sample_rate))
-            targets = LN.per_row(loudness, len(result_list), "decode_to_wavs")
-            res = self.decode_to_wavs(result_list, pad_to, sample_rate, speed, pauses=pauses)
-            if isinstance(res, tuple):                                # trimmed rows: (packed, offsets)
-                self.loudness_normalize(res[0], targets, offsets=res[1], rates=rate, out=res[0], limiter=lims)
-                return res
-            wav = res.contiguous()
-            return self.loudness_normalize(wav, targets, rates=rate, out=wav, limiter=lims)
-        specs = PA.per_row(pauses, len(result_list), "decode_to_wavs")
-        if specs is not None:
-            rate = PA.check_rate(self.SAMPLE_RATE if sample_rate is None else int(sample_rate))
-            targets = LN.per_row(loudness, len(result_list), "decode_to_wavs")
-            if targets is not None:
-                LN.check_rate(rate)                                   # every refusal, before the decode
-            wav, off = self.trim_pauses(self.decode_to_wavs(result_list, pad_to, sample_rate, speed), specs, rates=rate)
-            if targets is not None:
-                self.loudness_normalize(wav, targets, offsets=off, rates=rate, out=wav)
-            return wav, off
-        targets = LN.per_row(loudness, len(result_list), "decode_to_wavs")
-        if targets is not None:
-            rate = LN.check_rate(self.SAMPLE_RATE if sample_rate is None else int(sample_rate))
-            wav = self.decode_to_wavs(result_list, pad_to, sample_rate, speed).contiguous()
-            return self.loudness_normalize(wav, targets, rates=rate, out=wav)
-        if speed is not None and TS.quantize(speed)[0] != TS.DEN:
-            wav = self.time_scale(self.decode_to_wavs(result_list, pad_to), speed)
-            return wav if sample_rate is None else self.resample(wav, self.SAMPLE_RATE, int(sample_rate))
-        if sample_rate is not None and int(sample_rate) != self.SAMPLE_RATE:
-            return self.resample(self.decode_to_wavs(result_list, pad_to), self.SAMPLE_RATE, int(sample_rate))
+        plan = OC.Plan.batch("decode_to_wavs", len(result_list), sample_rate, speed, loudness, pauses, limiter)   # every refusal, before the decode
+        if plan.on:
+            return OC.run(self, self.decode_to_wavs(result_list, pad_to), plan, in_place=True)   # the plain decode, through the public method
         longest = max(int(r.size(0)) for r in result_list)
         if pad_to is not None and int(pad_to) < longest:
             raise ValueError("pad_to is shorter than the longest row")

@@ -49,6 +49,7 @@ from . import timescale as TS
 from ._sync import wait_event, wait_stream
 from .config import GPT
 from .engine import GptEngine, gen_logits, plan_from_processors
+from .outchain import option_kw
 from .rng import ExpDraws, penalty_table
 
 
@@ -708,21 +709,13 @@ def _job_speed(speed) -> Optional[float]:
 def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding", speed_kw: str = "speed") -> dict:
     """the output-format keywords of ONE decode that serves `jobs`, one list entry per job.  Nothing when every job wants 24 kHz int16
     at speed 1: the collaborator is then called exactly as it was before it knew rates, encodings and speeds (the host fakes pin that)."""
-    kw = {}
-    if any(j.sample_rate is not None for j in jobs):
-        kw[rate_kw] = [24000 if j.sample_rate is None else j.sample_rate for j in jobs]
-    if any(j.encoding is not None for j in jobs):
-        kw[encoding_kw] = [j.encoding for j in jobs]
-    if any(j.speed is not None for j in jobs):
-        kw[speed_kw] = [1.0 if j.speed is None else j.speed for j in jobs]
-    if any(j.flac for j in jobs):
-        kw["flac"] = [j.flac for j in jobs]
-    if any(j.loudness is not None for j in jobs):
-        kw["loudness"] = [j.loudness for j in jobs]
-    if any(j.pauses is not None for j in jobs):
-        kw["pauses"] = [j.pauses for j in jobs]
-    if any(j.limiter for j in jobs):
-        kw["limiter"] = [j.limiter for j in jobs]
+    kw = option_kw({rate_kw: [j.sample_rate for j in jobs], encoding_kw: [j.encoding for j in jobs], speed_kw: [j.speed for j in jobs],
+                    "flac": [j.flac for j in jobs], "loudness": [j.loudness for j in jobs], "pauses": [j.pauses for j in jobs],
+                    "limiter": [j.limiter for j in jobs]})
+    if rate_kw in kw:
+        kw[rate_kw] = [24000 if r is None else r for r in kw[rate_kw]]
+    if speed_kw in kw:
+        kw[speed_kw] = [1.0 if v is None else v for v in kw[speed_kw]]
     return kw
 
 
@@ -1299,11 +1292,8 @@ class SpeechBatcher:
         if hid.shape[0] == 0:
             raise RuntimeError(_NO_AUDIO)
         self._count_decode(1)
-        wav = self.chat.decode_to_wavs([hid], **({} if sample_rate is None else {"sample_rate": int(sample_rate)}),
-                                       **({} if speed is None else {"speed": float(speed)}),
-                                       **({} if loudness is None else {"loudness": float(loudness)}),
-                                       **({} if pauses is None else {"pauses": pauses}),
-                                       **({"limiter": True} if limiter else {}))[0]
+        kw = option_kw({"sample_rate": [sample_rate], "speed": [speed], "loudness": [loudness], "pauses": [pauses], "limiter": [bool(limiter)]})
+        wav = self.chat.decode_to_wavs([hid], **{k: v[0] for k, v in kw.items()})[0]
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
         if flac:                                                            # converted on the host, encoded by the host twin
             return np.frombuffer(FLAC.encode(pcm, 24000 if sample_rate is None else int(sample_rate)), np.uint8)
@@ -1319,19 +1309,8 @@ class SpeechBatcher:
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
             self._count_decode(len(live))
-            kw = {} if sample_rates is None else {"sample_rate": [int(sample_rates[i]) for i in live]}
-            if encodings is not None and any(encodings[i] is not None for i in live):
-                kw["encoding"] = [encodings[i] for i in live]
-            if speeds is not None:
-                kw["speed"] = [float(speeds[i]) for i in live]
-            if flac is not None and any(flac[i] for i in live):
-                kw["flac"] = [bool(flac[i]) for i in live]
-            if loudness is not None and any(loudness[i] is not None for i in live):
-                kw["loudness"] = [loudness[i] for i in live]
-            if pauses is not None and any(pauses[i] is not None for i in live):
-                kw["pauses"] = [pauses[i] for i in live]
-            if limiter is not None and any(limiter[i] for i in live):
-                kw["limiter"] = [bool(limiter[i]) for i in live]
+            kw = option_kw({"sample_rate": sample_rates, "encoding": encodings, "speed": speeds, "flac": flac, "loudness": loudness,
+                            "pauses": pauses, "limiter": limiter}, rows=live)
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out
