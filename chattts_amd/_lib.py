@@ -73,6 +73,12 @@ TS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("tota
                       ("n_out", "<i4"), ("reserved", "<i4")])
 
 
+# ctts_lm_stream (80 bytes): in_off, n_in, pos, total, e_lo, n_out, out_off int64; slot, phase, c_in, c_out, rate int32; gain float32
+LM_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("e_lo", "<i8"), ("n_out", "<i8"),
+                      ("out_off", "<i8"), ("slot", "<i4"), ("phase", "<i4"), ("c_in", "<i4"), ("c_out", "<i4"), ("rate", "<i4"),
+                      ("gain", "<f4")])
+
+
 # ctts_rs_stream (80 bytes): in_off, n_in, pos, total, o_lo, n_out, out_off int64; slot, phase, c_in, c_out, pad, reserved int32
 RS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("o_lo", "<i8"), ("n_out", "<i8"),
                       ("out_off", "<i8"), ("slot", "<i4"), ("phase", "<i4"), ("c_in", "<i4"), ("c_out", "<i4"), ("pad", "<i4"),
@@ -171,6 +177,7 @@ SIGNATURES = {
     "ctts_loudness_limited_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, I32, P, P, I32, P, P, P, P, P, P, P, SZ, P]),
     "ctts_peak_limit_ragged_scratch_bytes": (SZ, [P, I32]),
     "ctts_peak_limit_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, P, SZ, P]),
+    "ctts_peak_limit_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P]),
     "ctts_trim_pauses_ragged_scratch_bytes": (SZ, [C.c_int64, I32]),
     "ctts_trim_pauses_ragged": (C.c_int, [P, P, P, P, P, P, P, P, I32, P, I32, P, P, P, SZ, P]),
     "ctts_time_scale_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, C.c_int64, P, P, I32, P, P]),

@@ -24,6 +24,7 @@ import torch
 
 from . import flac as FLAC
 from . import g711 as G711
+from . import limiter as LM
 from . import loudness as LN
 from . import outchain
 from . import pauses as PA
@@ -549,7 +550,7 @@ class Chat:
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts, *(() if encs is None else (encs,)))]
 
     def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None,
-                             rs_streams=None, flac=None, flac_streams=None) -> List[np.ndarray]:
+                             rs_streams=None, flac=None, flac_streams=None, limiter=None, lm_streams=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
         (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream).  `encodings`: one per window, None / "ulaw" / "alaw" -- a
@@ -559,7 +560,9 @@ class Chat:
         `sample_rates`): the handle of the resampler's stream of a window at another speed AND rate, None otherwise.  `flac` with
         `flac_streams` (one flag and one entry per window; a flagged window with the handle of its FLAC stream): the window's int16
         samples are pushed into that stream and the piece is uint8, the frames the push completes
-        (CodecEngine.decode_windows(flac=)); without them today's call, argument for argument"""
+        (CodecEngine.decode_windows(flac=)); `limiter` with `lm_streams` (one flag and one entry per window; a flagged window with the
+        handle of its limiter stream): the window's float samples are pushed into that stream and the piece is what the step emits,
+        converted (CodecEngine.decode_windows(limiter=)); without them today's call, argument for argument"""
         kw = {k: v for k, v in (("sample_rates", sample_rates), ("encodings", encodings), ("speeds", speeds)) if v is not None}
         if speeds is not None:
             kw["ts_streams"] = ts_streams
@@ -567,6 +570,8 @@ class Chat:
                 kw["rs_streams"] = rs_streams
         if flac is not None:
             kw["flac"], kw["flac_streams"] = flac, flac_streams
+        if limiter is not None:
+            kw["limiter"], kw["lm_streams"] = limiter, lm_streams
         return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, **kw)
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
@@ -599,7 +604,7 @@ class Chat:
             yield np.zeros((0,), np.float32) if p is None else p.result()
 
     def _stream_piece(self, hiddens, a: int, b: Optional[int], use_decoder: bool = True, pcm16: bool = False,
-                      rate: Optional[int] = None, encoding=None, on_device: bool = False) -> np.ndarray:
+                      rate: Optional[int] = None, encoding=None, on_device: bool = False, lm_handles=None, final: bool = False) -> np.ndarray:
         """samples [a, b) (b=None: to the end) of the decode of the current prefix (core.py:482-497), from a token window with
         halos instead of the whole prefix (`CodecEngine.decode_window`); `incremental_stream=False` restores the reference's
         full re-decode per yield.  `rate` (None: 24 kHz): [a, b) stay 24 kHz samples and the piece is outputs
@@ -607,7 +612,25 @@ class Chat:
         (`decode_window(sample_rate=)`), or, `incremental_stream=False`, sliced out of the whole prefix resampled whole.
         `encoding` ("ulaw" / "alaw", with `pcm16`): the int16 piece companded -- on the device where the conversion ran there, by the
         host twin where it ran on the host.  `on_device` (with `pcm16`, without `encoding`): a piece that was converted on the device
-        stays there, as an int16 tensor (a streamed FLAC pushes it on)."""
+        stays there, as an int16 tensor (a streamed FLAC pushes it on).  `lm_handles` (one limiter stream per row, at the piece's
+        rate; the decoder path): the float samples are PUSHED into the rows' streams (CodecEngine.peak_limit_stream_step, all rows in
+        one launch) and the piece is what the step emits -- the conversion and the companding act on the limited samples; `final`:
+        the streams' last push, which comes back as float32 whatever `pcm16` says (the caller filters its columns first)."""
+        if lm_handles:
+            Tn = max(int(r.size(0)) for r in hiddens)
+            total = max(0, 256 * (2 * Tn - 1))
+            hi = total if b is None else min(b, total)
+            rkw = {} if rate is None else {"sample_rate": rate}
+            if hi > a and self.incremental_stream:
+                x = self.codec.decode_window(hiddens, a, hi, **rkw).contiguous()
+            elif hi > a:        # decoded whole on the host path: the piece goes back to the device for the limiter
+                x = torch.from_numpy(np.ascontiguousarray(self._stream_piece(hiddens, a, b, True, False, **({} if rate is None else {"rate": rate})),
+                                                          dtype=np.float32)).to(self.device)
+            else:               # nothing new: the streams are stepped all the same (the last push brings what they held)
+                x = torch.empty((len(hiddens), 0), dtype=torch.float32, device=self.device)
+            m = int(x.shape[1])
+            y, off = self.codec.peak_limit_stream_step(x.view(-1), [(h, i * m, m, final) for i, h in enumerate(lm_handles)])
+            return self._finish_piece(y.view(len(hiddens), int(off[1])), final, pcm16, encoding, on_device)
         if encoding is not None:
             if not pcm16:
                 raise ValueError("encoding needs pcm16=True")
@@ -643,14 +666,15 @@ class Chat:
         return self.codec.to_host(win)
 
     def _stream_piece_scaled(self, hiddens, a: int, b: Optional[int], handles, final: bool, pcm16: bool = False, encoding=None,
-                             rs_handles=None, on_device: bool = False) -> np.ndarray:
+                             rs_handles=None, on_device: bool = False, lm_handles=None) -> np.ndarray:
         """`_stream_piece` at another speed: samples [a, b) of the decode of the current prefix are PUSHED into the rows' streams of the
         time scaler (`handles`, one per row; CodecEngine.time_scale_stream_step, all rows in one launch) and the piece is what the step
         emits -- [B, 512 k] samples, possibly none; every row has had the same number of samples, so the chunk stays rectangular.
         `final`: the last push (the stream's tail); it comes back as float32 whatever `pcm16` says: the caller filters its columns
         first.  Otherwise `pcm16` converts every row under its own peak on the device, `encoding` compands behind that.
         `rs_handles` (one resampler stream per row, 24000 -> the request's rate): what the scaler's step emits is pushed on into them
-        (CodecEngine.resample_stream_step, all rows in one launch) and the piece is what THAT step emits."""
+        (CodecEngine.resample_stream_step, all rows in one launch) and the piece is what THAT step emits.  `lm_handles` (one limiter
+        stream per row, at the piece's rate): the last float stage's chunk is pushed on into them in the same way."""
         codec = self.codec
         Tn = max(int(r.size(0)) for r in hiddens)
         total = max(0, 256 * (2 * Tn - 1))
@@ -665,7 +689,14 @@ class Chat:
         y, off = codec.time_scale_stream_step(x, [(h, i * m, m, final) for i, h in enumerate(handles)])
         if rs_handles:
             y, off = codec.resample_stream_step(y, [(h, int(off[i]), int(off[i + 1] - off[i]), final) for i, h in enumerate(rs_handles)])
-        y = y.view(B, int(off[1]))
+        if lm_handles:
+            y, off = codec.peak_limit_stream_step(y, [(h, int(off[i]), int(off[i + 1] - off[i]), final) for i, h in enumerate(lm_handles)])
+        return self._finish_piece(y.view(B, int(off[1])), final, pcm16, encoding, on_device)
+
+    def _finish_piece(self, y: torch.Tensor, final: bool, pcm16: bool, encoding, on_device: bool):
+        """what a stream step emitted, [B, n] float32 on the device -> the piece: float32 on the host (`final`, or not `pcm16`), else
+        converted row by row under its own peak on the device, companded behind that"""
+        codec, B = self.codec, int(y.shape[0])
         if final or not pcm16:
             return codec.to_host(y)
         if y.shape[1] == 0:
@@ -800,7 +831,8 @@ class Chat:
               params_refine_text: RefineTextParams = RefineTextParams(), params_infer_code: InferCodeParams = InferCodeParams(),
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
-              flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None):
+              flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None,
+              stream_limiter: bool = False, gain_db=None):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -877,10 +909,36 @@ class Chat:
         limited instead of clipped by the 16-bit conversion.  It sits where the loudness stage does: behind the time scaler, the
         resampler and `pauses`, in front of the silence strip, the 16-bit conversion, the companding and FLAC.  The sentences of a
         split request (one flag only) are limited one by one under the request's ONE gain.  A streamed call with it raises: the
-        look-ahead is not carried across chunks."""
+        look-ahead is not carried across chunks -- unless
+        `stream_limiter=True` (keyword-only): then every row of a streamed batch gets a limiter stream (CodecEngine.peak_limit_stream_*,
+        opened at the first chunk, closed when the generator ends or is dropped) between the last float stage -- the crop, the
+        resampled window, the time scaler's or the scaled resampler's stream -- and the 16-bit conversion, so every chunk is converted,
+        companded and FLAC-encoded from limited samples.  The stream lags by 20 ms (rate // 50 samples: a sample's gain needs the 20 ms
+        behind it); its chunks, end to end, are the limiter of the whole float stream bit for bit, and the last chunk brings the rest.
+        One flag for the whole batch; refused with `split_text` and without the decoder.
+        `gain_db` (keyword-only; with `stream=True, limiter=True, stream_limiter=True` only): a fixed make-up gain in dB, -30 .. +30, one
+        for the whole batch, applied in front of the limiter as its float32 pre-gain 10 ** (gain_db / 20).  A non-streamed call has
+        `loudness` for its level and refuses it."""
         mkw = Plan.given("infer", limiter=limiter).kwargs()
-        if mkw and stream:
+        if gain_db is not None and np.ndim(gain_db) != 0:
+            raise ValueError("gain_db is one make-up gain for the whole batch")
+        g32 = LM.check_gain_db(gain_db)
+        if g32 is not None and not mkw:
+            raise ValueError("gain_db is the make-up gain in front of the limiter: it needs limiter=True")
+        if g32 is not None and not stream:
+            raise ValueError("gain_db applies to a limited stream only (a non-streamed call sets its level with loudness)")
+        if mkw and stream and not stream_limiter:
             raise ValueError("limiter applies to non-streamed inference only (the look-ahead is not carried across chunks)")
+        smkw = {}
+        if mkw and stream:
+            if np.ndim(limiter) != 0:
+                raise ValueError("a limited stream takes one limiter flag for the whole batch")
+            if split_text:
+                raise ValueError("a limited stream does not go with split_text (every split batch would end the stream)")
+            if not use_decoder:
+                raise ValueError("a limited stream needs the hidden-state decoder (use_decoder=True)")
+            LN.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+            smkw, mkw = {"lm_gain": np.float32(1.0) if g32 is None else g32}, {}
         if mkw and split_text and np.ndim(limiter) != 0:
             raise ValueError("a split_text request is one waveform: it takes one limiter flag")
         if mkw:
@@ -957,7 +1015,7 @@ class Chat:
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
                               sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}),
-                              **({} if split_host else lkw), **pkw)
+                              **({} if split_host else lkw), **pkw, **smkw)
         if stream:
             return res_gen
         if refine_text_only:
@@ -996,8 +1054,8 @@ class Chat:
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None):
-        """core.py:395-503 (generator).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
+               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None):
+        """core.py:395-503 (generator).  `lm_gain` with `stream`: the rows' limiter streams and their pre-gain (Chat.infer's `stream_limiter`).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
             text = [text]
@@ -1019,13 +1077,17 @@ class Chat:
         ts = [] if stream and speed is not None else None      # a streamed speed: the rows' streams of the time scaler, opened at the first chunk
         rs = [] if ts is not None and sample_rate is not None else None      # ... at another rate: and their streams of the resampler
         fs = [] if stream and flac and pcm16 else None         # a streamed FLAC: the rows' FLAC streams, opened at the first chunk
+        lm = [] if stream and lm_gain is not None else None    # a limited stream: the rows' limiter streams, opened at the first chunk
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
                                            encoding, speed, ts, rs, **({"flac": True} if flac else {}),
                                            **({} if loudness is None else {"loudness": loudness}), **({} if fs is None else {"fs": fs}),
                                            **({} if pauses is None else {"pauses": pauses}),
-                                           **({} if limiter is None else {"limiter": limiter}))
+                                           **({} if limiter is None else {"limiter": limiter}),
+                                           **({} if lm is None else {"lm": lm, "lm_gain": lm_gain}))
         finally:
+            for h in lm or ():
+                self.codec.peak_limit_stream_close(h)
             for h in fs or ():
                 if not isinstance(h, FLAC.StreamEncoder):
                     self.codec.flac_stream_close(h)
@@ -1035,7 +1097,7 @@ class Chat:
                 self.codec.resample_stream_close(h)
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None):
+                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None):
         """the batch loop of `_infer`"""
         def flac_chunks(piece, final):
             """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' FLAC
@@ -1066,6 +1128,13 @@ class Chat:
             if rs is not None:
                 rs.extend(self.codec.resample_stream_open(CodecEngine.SAMPLE_RATE, sample_rate) for _ in rows)
         rkw_s = {} if rs is None else {"rs_handles": rs}
+        def limited(rows):
+            """the rows' limiter streams, opened at the first chunk at the stream's output rate -> the keyword of the piece calls"""
+            if lm is None:
+                return {}
+            if not lm:
+                lm.extend(self.codec.peak_limit_stream_open(CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate, lm_gain) for _ in rows)
+            return {"lm_handles": lm}
         length = 0
         pass_batch_count = 0
         for lo in range(0, len(text), step):
@@ -1115,9 +1184,9 @@ class Chat:
                     if not ts:
                         open_streams(src)
                     piece = self._stream_piece_scaled(src, length, length + params_infer_code.stream_speed, ts, False, pcm16,
-                                                      encoding if pcm16 else None, **rkw_s, **dkw)
+                                                      encoding if pcm16 else None, **rkw_s, **dkw, **limited(src))
                 else:
-                    piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw, **dkw)
+                    piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw, **dkw, **limited(src))
                 if fs is not None:
                     piece = flac_chunks(piece, False)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
@@ -1131,9 +1200,10 @@ class Chat:
                 if ts is not None:
                     if not ts:
                         open_streams(last.hiddens)
-                    new_wavs = self._stream_piece_scaled(last.hiddens, length, None, ts, True, **rkw_s)
+                    new_wavs = self._stream_piece_scaled(last.hiddens, length, None, ts, True, **rkw_s, **limited(last.hiddens))
                 else:
-                    new_wavs = self._stream_piece(last.hiddens if use_decoder else last.ids, length, None, use_decoder, **skw)
+                    new_wavs = self._stream_piece(last.hiddens if use_decoder else last.ids, length, None, use_decoder, **skw,
+                                                  **({} if lm is None else {**limited(last.hiddens), "final": True}))
                 last.destroy()
                 keep_cols = np.sum(np.abs(new_wavs) > 1e-5, axis=0) > 0
                 tail = new_wavs[:, keep_cols]

@@ -2140,6 +2140,56 @@ extern "C" int ctts_peak_limit_ragged(const float* x, float* y, const int64_t* o
                               (int32_t*)((char*)scratch + curve_bytes), (hipStream_t)stream));
   return 0;
 }
+// ---- the limiter of streams: the host's arithmetic (limiter.py: stream_plan) and every check the launch trusts --------------------------
+static_assert(sizeof(ctts_lm_stream) == 80 && sizeof(LmStream) == 80 && offsetof(ctts_lm_stream, n_out) == offsetof(LmStream, n_out) &&
+              offsetof(ctts_lm_stream, slot) == offsetof(LmStream, slot) && offsetof(ctts_lm_stream, c_out) == offsetof(LmStream, c_out) &&
+              offsetof(ctts_lm_stream, rate) == offsetof(LmStream, rate) && offsetof(ctts_lm_stream, gain) == offsetof(LmStream, gain) &&
+              CTTS_LM_CARRY == LM_CARRY, "ctts_lm_stream layout");
+extern "C" int ctts_peak_limit_stream_step(const float* x, int64_t n_x, const ctts_lm_stream* st_dev, const ctts_lm_stream* st_host,
+                                           int32_t n_streams, float* y, int64_t n_y, float* carry, void* stats, int32_t n_slots, void* stream) {
+  const char* who = "ctts_peak_limit_stream_step";
+  if (!st_dev || !st_host || !carry || !stats) return fail("%s: a null pointer (both descriptor tables, the carry and the stats are needed)", who);
+  if (n_x < 0 || n_y < 0 || (!x && n_x) || (!y && n_y)) return fail("%s: a null pointer (x or y) with a length other than 0", who);
+  if (n_streams < 1 || n_streams > 1024) return fail("%s: need 1 <= n_streams <= 1024 (got %d)", who, n_streams);
+  if (n_slots < 1) return fail("%s: the state pool has no slot", who);
+  if (((uintptr_t)x & 3) || ((uintptr_t)y & 3) || ((uintptr_t)carry & 3) || ((uintptr_t)stats & 3))
+    return fail("%s: x, y, the carry and the stats must be 4-byte aligned", who);
+  if (n_x && n_y && x < y + n_y && y < x + n_x) return fail("%s: y must not overlap x (a stream is never limited in place)", who);
+  std::vector<char> seen((size_t)n_slots, 0);
+  long long n_out_max = 0;
+  int reset = 0;
+  for (int i = 0; i < n_streams; ++i) {
+    const ctts_lm_stream& w = st_host[i];
+    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: limiter stream %d: slot %d is outside the pool of %d", who, i, w.slot, n_slots);
+    if (seen[w.slot]) return fail("%s: limiter stream %d: slot %d appears twice in one launch", who, i, w.slot);
+    seen[w.slot] = 1;
+    if (w.phase != 0 && w.phase != 1) return fail("%s: limiter stream %d: phase %d is neither 0 nor 1", who, i, w.phase);
+    if (w.rate < 100 * LM_WMIN || w.rate > 100 * LM_WMAX || w.rate % 10 != 0)
+      return fail("%s: limiter stream %d: the rate is a multiple of 10 Hz in %d .. %d (got %d)", who, i, 100 * LM_WMIN, 100 * LM_WMAX, w.rate);
+    if (!(w.gain > 0.0f) || !std::isfinite(w.gain)) return fail("%s: limiter stream %d: the pre-gain is a positive finite number", who, i);
+    if (w.n_in < 0 || w.pos < 0 || w.in_off < 0 || w.out_off < 0 || w.e_lo < 0 || w.n_out < 0)
+      return fail("%s: limiter stream %d: a negative length, position or offset", who, i);
+    if (w.pos >= (1ll << 31) || w.n_in >= (1ll << 31) || w.pos + w.n_in >= (1ll << 31))
+      return fail("%s: limiter stream %d would hold 2^31 samples or more", who, i);
+    if (w.in_off + w.n_in > n_x) return fail("%s: limiter stream %d: the push lies outside the input (%lld floats)", who, i, (long long)n_x);
+    const long long W = w.rate / 100, end = w.pos + w.n_in;
+    const bool fin = w.total != -1;
+    if (fin && w.total != end)
+      return fail("%s: limiter stream %d: a last push ends the stream at pos + n_in = %lld, got total %lld", who, i, end, (long long)w.total);
+    const long long e0 = std::max(0ll, w.pos - 2 * W), e1 = fin ? end : std::max(0ll, end - 2 * W);
+    if (w.e_lo != e0) return fail("%s: limiter stream %d: %lld samples have emitted %lld, got e_lo %lld", who, i, (long long)w.pos, e0, (long long)w.e_lo);
+    if (w.n_out != e1 - e0) return fail("%s: limiter stream %d: the step emits %lld samples, got %lld", who, i, e1 - e0, (long long)w.n_out);
+    if (w.out_off + w.n_out > n_y) return fail("%s: limiter stream %d: the chunk lies outside the output (%lld floats)", who, i, (long long)n_y);
+    const long long c_in = std::min((long long)w.pos, 4 * W), c_out = fin ? 0 : std::min(end, 4 * W);
+    if (w.c_in != c_in || w.c_out != c_out)
+      return fail("%s: limiter stream %d: the step carries %lld samples in and %lld out, got %d and %d", who, i, c_in, c_out, w.c_in, w.c_out);
+    n_out_max = std::max(n_out_max, (long long)w.n_out);
+    reset |= w.pos == 0;
+  }
+  CttsDeviceGuard dg(stream);
+  CK(launch_peak_limit_stream(x, (const LmStream*)st_dev, n_streams, n_out_max, y, carry, stats, reset, (hipStream_t)stream));
+  return 0;
+}
 extern "C" size_t ctts_trim_pauses_ragged_scratch_bytes(int64_t frames, int32_t n_seg) {
   if (frames < 1 || frames >= (1ll << 31) || n_seg < 1 || n_seg > 65535) return 0;
   return pause_scratch_bytes(frames, n_seg);

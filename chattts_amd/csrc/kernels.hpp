@@ -556,6 +556,21 @@ static inline long long limiter_tiles(long long total, int n_seg) { return total
 // record.  n_max: the longest segment (grid sizes); curve: one float32 per sample of the pack, flags: limiter_tiles(..) int32 of scratch.
 hipError_t launch_peak_limit_ragged(const float* x, float* y, const long long* off, int n_seg, long long n_max, const int32_t* rate,
                                     const float* gain, void* stats, float* curve, int32_t* flags, hipStream_t st);
+#define LM_CARRY (4 * LM_WMAX) // floats of one carry buffer of a limiter stream slot (its last 4 W raw samples); a slot has two
+// ctts_lm_stream (include/chattts_amd.h), field for field (capi.hip asserts the layout): one push of one limiter stream.
+// x[in_off, in_off + n_in) are samples [pos, pos + n_in) of the stream; total: its length when this push is the last, else -1; the step
+// writes samples [e_lo, e_lo + n_out) of the limited stream to y[out_off ..]; slot / phase: the state slot and which of its two carry
+// buffers holds the raw samples [pos - c_in, pos); c_out: the samples [pos + n_in - c_out, pos + n_in) it keeps; rate, gain: fs and g32
+struct LmStream {
+  long long in_off, n_in, pos, total, e_lo, n_out, out_off;
+  int32_t slot, phase, c_in, c_out, rate;
+  float gain;
+};
+// descriptors 0 .. n_streams-1 of the table; n_out_max: their longest chunk (grid size; 0: only the carries move); carry
+// [n_slots][2][LM_CARRY] floats, stats [n_slots] 16-byte records; reset != 0: some descriptor has pos == 0, and the records of those are
+// reset by a launch of their own in front of the step.  Every bound is the caller's to check
+hipError_t launch_peak_limit_stream(const float* x, const LmStream* tab, int n_streams, long long n_out_max, float* y, float* carry,
+                                    void* stats, int reset, hipStream_t st);
 
 // ---- pause control (pauses.hip) -------------------------------------------------------------------
 #define PA_FMIN 80            // a frame is F = fs / 100 samples (integer division): 8 kHz ..

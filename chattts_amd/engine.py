@@ -2032,6 +2032,140 @@ class CodecEngine:
             return y, work[: LM.STATS.itemsize * n_seg].cpu().numpy().view(LM.STATS)
         return y
 
+    # -- the limiter of streams: per-stream device state (csrc/limiter.hip, limiter_stream_k) ---------------------------------------------
+    LM_STREAM_SLOTS = 64      # the state pool's first size; it doubles when every slot is taken
+
+    def _lm_pool(self) -> dict:
+        """the state pool: carry [slots, 2, LM.CARRY] float32 and stats [slots, 4] int32 (one limiter.STATS record per slot) on the
+        device, the free list, and per open stream its host record [rate, pre-gain, samples pushed, samples emitted, carry phase, done]"""
+        pool = self.__dict__.get("_lm_streams")
+        if pool is None:
+            n = int(self.LM_STREAM_SLOTS)
+            pool = self._lm_streams = dict(carry=torch.zeros((n, 2, LM.CARRY), dtype=torch.float32, device=self.device),
+                                           stats=torch.zeros((n, 4), dtype=torch.int32, device=self.device),
+                                           free=list(range(n - 1, -1, -1)), rec={})
+        return pool
+
+    def peak_limit_stream_open(self, rate: int, gain=1.0) -> int:
+        """A stream of the limiter at `rate` Hz with the float32 pre-gain `gain` (any positive finite float32): -> its handle, a slot
+        of the engine's state pool.  The slot is fresh by construction -- the first step of a stream reads no carry, and the step
+        that carries a stream's first push resets the slot's record on the device in front of its own atomics -- so nothing is
+        cleared here.  ValueError for a rate or gain `peak_limit` refuses."""
+        rate = LN.check_rate(rate)
+        g = np.float32(gain)
+        if not (np.isfinite(g) and g > 0):
+            raise ValueError("limiter: a pre-gain is a positive finite number")
+        pool = self._lm_pool()
+        if not pool["free"]:
+            n = int(pool["carry"].shape[0])
+            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
+            pool["stats"] = torch.cat([pool["stats"], torch.zeros_like(pool["stats"])])
+            pool["free"] = list(range(2 * n - 1, n - 1, -1))
+        slot = pool["free"].pop()
+        pool["rec"][slot] = [rate, g, 0, 0, 0, False]
+        return slot
+
+    def peak_limit_stream_close(self, handle: int) -> None:
+        """gives the stream's slot back (any time: finished, or abandoned half way)"""
+        pool = self._lm_pool()
+        if pool["rec"].pop(int(handle), None) is None:
+            raise ValueError(f"limiter: stream {handle} is not open")
+        pool["free"].append(int(handle))
+
+    def peak_limit_streams_in_use(self) -> int:
+        """the streams that are open: slots of the state pool not on its free list"""
+        return len(self._lm_pool()["rec"])
+
+    def peak_limit_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
+        """`limiter.stream_plan` of the stream's next push: what a step with `n_in` more samples would emit and keep"""
+        rec = self._lm_pool()["rec"].get(int(handle))
+        if rec is None:
+            raise ValueError(f"limiter: stream {handle} is not open")
+        if rec[5]:
+            raise ValueError(f"limiter: stream {handle} has had its last push")
+        return LM.stream_plan(rec[0] // 100, rec[2], rec[3], n_in, final)
+
+    def peak_limit_stream_stats(self, handle: int) -> np.ndarray:
+        """the stream's limiter.STATS record, counted over the samples emitted so far (a device read: it waits for the steps so far);
+        after the last push it is `peak_limit`'s record of the whole signal.  Before the first push nothing has been counted."""
+        pool = self._lm_pool()
+        rec = pool["rec"].get(int(handle))
+        if rec is None:
+            raise ValueError(f"limiter: stream {handle} is not open")
+        out = np.zeros((), dtype=LM.STATS)
+        if rec[2] == 0:                                           # the slot's record is reset by the step of the first push
+            out["g32"], out["min_gain"] = rec[1], 1.0
+            return out
+        return pool["stats"][int(handle)].cpu().numpy().view(LM.STATS)[0]
+
+    def _lm_descriptors(self, pushes):
+        """pushes [(handle, in_off, n_in, final)], one per stream -> (LM_STREAM table with out_off unset, in the pushes' order,
+        commit: handle -> its new host record).  All in Python integers and before anything is launched; the records change only
+        when the caller commits."""
+        recs = self._lm_pool()["rec"]
+        tab = np.zeros(len(pushes), _lib.LM_STREAM)
+        commit = {}
+        for i, (h, in_off, n_in, final) in enumerate(pushes):
+            h = int(h)
+            if h not in recs:
+                raise ValueError(f"limiter: stream {h} is not open")
+            if h in commit:
+                raise ValueError("limiter: a stream appears twice in one step")
+            rate, g, pushed, emitted, phase, done = recs[h]
+            if done:
+                raise ValueError(f"limiter: stream {h} has had its last push")
+            p = LM.stream_plan(rate // 100, pushed, emitted, n_in, final)
+            tab[i] = (int(in_off), int(n_in), pushed, p["total"] if final else -1, emitted, p["n_out"], 0, h, phase, p["carry_in"],
+                      p["carry_out"], rate, g)
+            commit[h] = [rate, g, p["total"], p["emitted"], phase ^ 1, bool(final)]
+        return tab, commit
+
+    def peak_limit_stream_step(self, x: torch.Tensor, pushes, out: Optional[torch.Tensor] = None, out_off=None):
+        """ONE step of many streams (ctts_peak_limit_stream_step, one launch whatever their rates and gains): `x`, a 1-D float32
+        device tensor, holds the new samples of every stream; `pushes` = [(handle, in_off, n_in, final)]: x[in_off, in_off + n_in)
+        continue stream `handle` (n_in 0: nothing new), `final`: they are its last.  -> (y, off): stream i's chunk is
+        y[off[i], off[i+1]) (possibly empty; `peak_limit_stream_plan`'s n_out), a tensor of its own -- x is never written.  A stream
+        lags by 2 W = rate // 50 samples; the chunks of a stream, concatenated, are `peak_limit` of its concatenated pushes with the
+        stream's gain, bit for bit, however they were cut, and after the last push `peak_limit_stream_stats` is that call's record.
+        A handle may appear once per call.  `out` with `out_off`: a contiguous 1-D float32 device tensor of the caller's (not x) and
+        one offset per push -- stream i's chunk is written to out[out_off[i] ..] instead, and (out, out_off) comes back.  Every
+        refusal (ValueError here, EngineError from the library) comes before the first launch and leaves all streams as they were."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+            raise ValueError("limiter: a contiguous 1-D float32 device tensor")
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 1
+                                    and out.is_contiguous() and out_off is not None and len(out_off) == len(pushes)):
+            raise ValueError("limiter: out is a contiguous 1-D float32 device tensor, with one offset per push")
+        if len(pushes) < 1:
+            raise ValueError("limiter: nothing to step")
+        if len(pushes) > 1024:
+            raise ValueError("limiter: at most 1024 streams in one step")
+        for _, in_off, n_in, _ in pushes:
+            if int(in_off) < 0 or int(n_in) < 0 or int(in_off) + int(n_in) > x.numel():
+                raise ValueError("limiter: a push lies outside the tensor")
+        tab, commit = self._lm_descriptors(pushes)
+        off = np.zeros(len(pushes) + 1, np.int64)
+        np.cumsum(tab["n_out"], out=off[1:])
+        if int(off[-1]) >= 1 << 31:
+            raise ValueError("limiter: the output would hold 2^31 samples or more")
+        if out is None:
+            tab["out_off"] = off[:-1]
+            y = torch.empty((int(off[-1]),), dtype=torch.float32, device=x.device)
+        else:
+            off = np.array([int(v) for v in out_off], dtype=np.int64)
+            if np.any(off < 0) or np.any(off + tab["n_out"] > out.numel()):
+                raise ValueError("limiter: a chunk lies outside `out`")
+            tab["out_off"], y = off, out
+        pool = self._lm_pool()
+        tab_d = torch.from_numpy(tab.view(np.uint8)).to(x.device)
+        st = torch.cuda.current_stream(x.device)
+        _lib.check(self.lib.ctts_peak_limit_stream_step(
+            x.data_ptr() if x.numel() else None, x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(tab),
+            y.data_ptr() if y.numel() else None, y.numel(), pool["carry"].data_ptr(), pool["stats"].data_ptr(), int(pool["carry"].shape[0]),
+            st.cuda_stream), "ctts_peak_limit_stream_step")
+        tab_d.record_stream(st)
+        pool["rec"].update(commit)
+        return y, off
+
     # -- pause control (csrc/pauses.hip) ------------------------------------------------------------------------------------------------
     def trim_pauses(self, wav: torch.Tensor, spec, offsets=None, rates=None, return_stats: bool = False):
         """Trims the silence at every segment's edges and caps its inner pauses (ctts_trim_pauses_ragged; the definition of
@@ -2302,7 +2436,8 @@ class CodecEngine:
         return wav[:, c_lo: c_hi]
 
     def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
-                       sample_rates=None, encodings=None, speeds=None, ts_streams=None, rs_streams=None, flac=None, flac_streams=None):
+                       sample_rates=None, encodings=None, speeds=None, ts_streams=None, rs_streams=None, flac=None, flac_streams=None,
+                       limiter=None, lm_streams=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -2347,7 +2482,37 @@ class CodecEngine:
         `flac_stream_step` for the whole call (four launches), one small copy of the frame offsets and one of the bytes used: a flagged
         window's samples never cross the bus (a call whose windows are all flagged copies no samples at all).  A flagged window whose
         crop is empty still steps its stream; several windows of one stream are taken in the order given, each in a step of its own
-        round.  A flag together with an encoding is refused."""
+        round.  A flag together with an encoding is refused.
+        `limiter` (None, or all False: the call above, argument for argument) with `lm_streams`: one flag and one entry per window,
+        the handle of the limiter stream (`peak_limit_stream_open`, at the window's output rate) a flagged window continues.  A
+        flagged window PUSHES the float32 samples it would otherwise convert -- behind the plain crop, the stateless rate path, the
+        time-scale stream or the time-scale and resampler streams -- into its limiter stream and yields what that step emits
+        (`peak_limit_stream_step`: the stream lags by rate // 50 samples; a window marked `tail` is the stream's last push and yields
+        the rest): the peak, the 16-bit conversion, a tail's strip, the companding and a FLAC push all act on the limited samples,
+        the non-streamed order.  The float chunks stay on the device: the flagged windows take a decoder pass of their own (two
+        where some are at another speed and some are not), one limiter step per round -- several windows of one stream go to
+        successive rounds, in the order given --, ONE ctts_float_to_int16_ragged launch, and the epilogue of every other path (one
+        copy).  A flagged window whose crop is empty still steps its stream.  Unflagged windows return the bytes they return
+        without `limiter`."""
+        lm = None
+        if limiter is not None and any(bool(f) for f in limiter):
+            if len(limiter) != len(windows) or lm_streams is None or len(lm_streams) != len(windows):
+                raise ValueError("decode_windows: one limiter flag and one lm_streams entry per window")
+            lm_recs, ended = self._lm_pool()["rec"], set()
+            for i, (f, h) in enumerate(zip(limiter, lm_streams)):
+                if LM.check_flag(f, "decode_windows"):
+                    want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
+                    if h is None or int(h) not in lm_recs or lm_recs[int(h)][0] != want:
+                        raise ValueError(f"decode_windows: window {i} needs an open limiter stream at {want} Hz")
+                    if lm_recs[int(h)][5] or int(h) in ended:
+                        raise ValueError(f"decode_windows: window {i}: limiter stream {int(h)} has had its last push")
+                    if len(windows[i]) > 4 and bool(windows[i][4]):
+                        ended.add(int(h))
+                elif h is not None:
+                    raise ValueError(f"decode_windows: window {i} has no limiter flag but names a limiter stream")
+            lm = [int(h) if f else None for f, h in zip(limiter, lm_streams)]
+        elif lm_streams is not None and any(h is not None for h in lm_streams):
+            raise ValueError("decode_windows: lm_streams without a limiter flag")
         fl = None
         if flac is not None and any(bool(f) for f in flac):
             if len(flac) != len(windows) or flac_streams is None or len(flac_streams) != len(windows):
@@ -2386,6 +2551,10 @@ class CodecEngine:
                 if not pcm16:
                     raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
                 laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
+        if lm is not None:
+            return self._decode_windows_limited(store, windows, lm, q, laws, fl, pcm16, keep_thr, product, dict(
+                sample_rates=sample_rates, encodings=encodings, speeds=speeds, ts_streams=ts_streams, rs_streams=rs_streams, flac=flac,
+                flac_streams=flac_streams))
         if q is not None:
             rates = None
             if sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
@@ -2489,8 +2658,85 @@ class CodecEngine:
 
     def _windows_finish(self, lay, n, keep, live, laws, pcm16: bool, out: list, fl=None) -> list:
         off, n_out, n_g, n_keep, buf = lay
+        sink = self.__dict__.get("_lm_sink")
+        if sink is not None:          # `_decode_windows_limited` takes the float chunks where they lie: nothing is converted or copied
+            sink.append((buf[:n_out].view(torch.float32), off, n, list(live)))
+            return out
         return self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, off, n, keep, live, None if laws is None else [laws[i] for i in live],
                                      np.int16 if pcm16 else np.float32, out, fl)
+
+    def _decode_windows_limited(self, store: torch.Tensor, windows, lm, q, laws, fl, pcm16: bool, keep_thr: Optional[float], product: str,
+                                per_window: dict) -> list:
+        """`decode_windows` with at least one window behind a limiter stream (lm: the windows' handles or None; q, laws, fl: the
+        call's checked speeds, laws and FLAC streams; per_window: its per-window arguments, to be cut for the passes)"""
+        pick = lambda v, ix: None if v is None else [v[i] for i in ix]
+        idx = [i for i, h in enumerate(lm) if h is not None]
+        rest = [i for i, h in enumerate(lm) if h is None]
+        out: list = [None] * len(windows)
+        if rest:                                                   # the unflagged windows: the call without the limiter
+            for i, a in zip(rest, self.decode_windows(store, pick(windows, rest), pcm16, keep_thr, product,
+                                                      **{k: pick(v, rest) for k, v in per_window.items()})):
+                out[i] = a
+        # the float chunks of the flagged windows, left on the device: the scaled windows in one pass, the others in another
+        scaled = [i for i in idx if q is not None and q[i][0] != q[i][1]]
+        plain = [i for i in idx if i not in set(scaled)]
+        src, bufs, base = {}, [], 0                                # window -> (first sample, samples) in the passes' chunks, end to end
+        sink = self._lm_sink = []
+        try:
+            for ix in (scaled, plain):
+                if not ix:
+                    continue
+                del sink[:]
+                self.decode_windows(store, pick(windows, ix), False, None, product, sample_rates=pick(per_window["sample_rates"], ix),
+                                    speeds=pick(per_window["speeds"], ix), ts_streams=pick(per_window["ts_streams"], ix),
+                                    rs_streams=pick(per_window["rs_streams"], ix))
+                if sink:                                           # none: no window of the pass had a sample
+                    fbuf, off, n, live = sink[0]
+                    for k, j in enumerate(live):
+                        src[ix[j]] = (base + int(off[k]), int(n[k]))
+                    bufs.append(fbuf)
+                    base += fbuf.numel()
+        finally:
+            del self._lm_sink
+        x = torch.cat(bufs) if len(bufs) > 1 else bufs[0] if bufs else torch.zeros((8,), dtype=torch.float32, device=self.device)
+        # the limiter's steps: the r-th window of a stream in round r; the limited chunks start on multiples of 8 samples, zeros between
+        recs, shadow, rounds = self._lm_pool()["rec"], {}, []
+        tails = [len(windows[i]) > 4 and bool(windows[i][4]) for i in idx]
+        n = np.zeros(len(idx), np.int64)
+        for k, i in enumerate(idx):
+            pushed, emitted, r = shadow.get(lm[i], (recs[lm[i]][2], recs[lm[i]][3], 0))
+            p = LM.stream_plan(recs[lm[i]][0] // 100, pushed, emitted, src.get(i, (0, 0))[1], tails[k])
+            n[k] = p["n_out"]
+            shadow[lm[i]] = (p["total"], p["emitted"], r + 1)
+            if r == len(rounds):
+                rounds.append([])
+            rounds[r].append(k)
+        keep = np.array([t and keep_thr is not None for t in tails], dtype=bool)
+        off = np.zeros(len(idx) + 1, np.int64)
+        np.cumsum((n + 7) // 8 * 8, out=off[1:])
+        lim = torch.zeros((max(8, int(off[-1])),), dtype=torch.float32, device=self.device)
+        for rnd in rounds:
+            self.peak_limit_stream_step(x, [(lm[idx[k]], *src.get(idx[k], (0, 0)), tails[k]) for k in rnd], out=lim, out_off=[int(off[k]) for k in rnd])
+        live = [k for k in range(len(idx)) if n[k] > 0]
+        for k in range(len(idx)):
+            if n[k] == 0:
+                out[idx[k]] = self._empty_window(idx[k], pcm16, laws)
+        fl_sub = None if fl is None else ([h if i in set(idx) else None for i, h in enumerate(fl[0])], fl[1])
+        if not pcm16:
+            host = self.to_host(lim)
+            for k in live:
+                a = host[int(off[k]): int(off[k]) + int(n[k])]
+                out[idx[k]] = a[np.abs(a) > keep_thr] if keep[k] else a
+            return out
+        if not live:
+            return self._windows_flac_idle(fl_sub, out)
+        # the conversion: every limited chunk with its zero pad is a segment of ctts_float_to_int16_ragged -- the pad changes no peak, and
+        # the segments' samples, codes and keep masks then lie where `_windows_to_host` expects those of a window entry
+        n_l, keep_l, laws_l = n[live], keep[live], None if laws is None else [laws[idx[k]] for k in live]
+        o, n_out, n_g, n_keep, buf = self._windows_layout(n_l, keep_l, True, laws)
+        masks = buf[n_out + n_g: n_out + n_g + int(o[-1]) // 8] if keep_l.any() else None
+        self.float_to_int16_ragged(lim[: int(o[-1])], o, product, keep_thr if keep_l.any() else None, out=(buf[:n_out].view(torch.int16), masks))
+        return self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, o, n_l, keep_l, [idx[k] for k in live], laws_l, np.int16, out, fl_sub)
 
     def _windows_flac_idle(self, fl, out: list) -> list:
         """a call none of whose windows has a sample: the flagged ones still step their streams (a tail ends its stream and brings

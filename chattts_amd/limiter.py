@@ -21,7 +21,13 @@ depend on the order of summation: a direct sum, a sliding sum and sums of partia
 condition the twin and the device may differ in s's last bit; the peak bound still holds.
 
 One record per segment (`STATS`, 16 bytes, written on the device): the pre-gain, min s, the samples with |u| > T, the samples with
-s < 1.  A segment's samples and record do not depend on what it is packed with."""
+s < 1.  A segment's samples and record do not depend on what it is packed with.
+
+A STREAM (`stream_plan`, `StreamLimiter`, ctts_peak_limit_stream_step): the segment arrives in pushes.  y[i] depends on x[i - 2 W .. i + 2 W],
+so with P samples pushed and more to come the samples [0, P - 2 W) are decided: a stream lags by 2 W samples (20 ms), and its last push
+emits the rest.  The chunks of a stream, concatenated, are `limit_segment` of the concatenated pushes -- bit for bit under THE CONDITION,
+however the signal was cut -- and after the last push its record is the segment's.  A stream keeps its last min(P, 4 W) raw samples:
+sample P - 2 W, the first the next push decides, needs r from P - 4 W on."""
 from __future__ import annotations
 
 import numpy as np
@@ -32,6 +38,9 @@ C32 = np.float32(LN.CEILING)
 T = np.float32(C32 * np.float32(1.0 - 2.0 ** -22))
 R_MIN = 2.0 ** -19                              # THE CONDITION: min r of every segment stays at or above this
 TILE = 2048                                     # samples per workgroup of csrc/limiter.hip (LM_TILE): the tests put segments at its edges
+
+CARRY = 4 * 480                                 # floats of one carry buffer of a stream (4 W at 48 kHz; csrc/kernels.hpp LM_CARRY)
+GAIN_DB_MAX = 30.0                              # the public make-up gain of a stream lies in -30 .. +30 dB
 
 # one record per segment (16 bytes, csrc/limiter.hip LmStats)
 STATS = np.dtype([("g32", "<f4"), ("min_gain", "<f4"), ("n_over", "<i4"), ("n_touched", "<i4")])
@@ -152,3 +161,73 @@ def limit(x: np.ndarray, offsets=None, rates=None, gains=None):
     for s in range(len(off) - 1):
         y[off[s]: off[s + 1]], stats[s] = limit_segment(x[off[s]: off[s + 1]], int(rates[s]), g[s])
     return y, stats
+
+
+# ---- streams ----------------------------------------------------------------------------------------------------------------------------
+def check_gain_db(v, who: str = "gain_db"):
+    """the make-up gain of a limited stream, in dB in front of the limiter: None -> None; a finite number in -30 .. +30 -> the
+    float32 pre-gain g32 = float32(10 ** (v / 20)); anything else (a bool, a string, NaN, beyond the range) is refused"""
+    if v is None:
+        return None
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) \
+            or not -GAIN_DB_MAX <= float(v) <= GAIN_DB_MAX:
+        raise ValueError(f"{who}: the make-up gain is a finite number of dB in -30 .. +30 (got {v!r})")
+    return np.float32(10.0 ** (float(v) / 20.0))
+
+
+def stream_plan(W: int, pushed: int, emitted: int, n_in: int, final: bool) -> dict:
+    """One push of a stream in Python integers: `pushed` samples are in and `emitted` out, `n_in` arrive, `final` says they are the
+    last (a stream may end empty: it emits nothing).  -> total (= pushed + n_in), e_lo (= emitted), n_out (the step emits samples [emitted, E')), emitted (E': total on the last
+    push, else max(0, total - 2 W)), carry_in / carry_out (the raw samples kept in front of and behind the step: [pushed - carry_in,
+    pushed) and [total - carry_out, total); min(., 4 W), 0 behind the last).  ValueError for what the library must not be launched with."""
+    W, pushed, emitted, n_in = int(W), int(pushed), int(emitted), int(n_in)
+    if not 80 <= W <= 480:
+        raise ValueError(f"limiter: W = fs // 100 lies in 80 .. 480 (got {W})")
+    if pushed < 0 or n_in < 0 or emitted < 0:
+        raise ValueError("limiter: a stream's position, output count and push cannot be negative")
+    if emitted != max(0, pushed - 2 * W):
+        raise ValueError(f"limiter: a stream of {pushed} samples has emitted {max(0, pushed - 2 * W)}, not {emitted}")
+    total = pushed + n_in
+    if total >= 1 << 31:
+        raise ValueError("limiter: the stream would hold 2^31 samples or more")
+    e1 = total if final else max(0, total - 2 * W)
+    return dict(total=total, e_lo=emitted, n_out=e1 - emitted, emitted=e1, carry_in=min(pushed, 4 * W),
+                carry_out=0 if final else min(total, 4 * W))
+
+
+class StreamLimiter:
+    """the NumPy twin of one limiter stream at rate fs with the float32 pre-gain g32: `push(x, final) -> y` float32, `stats` the STATS
+    record counted over the samples emitted so far.  The gain curve is computed on carry ++ x: an emitted sample lies 2 W or more
+    from either end of that buffer unless the end is the signal's own, so the silence assumed outside it reaches no emitted sample."""
+
+    def __init__(self, fs: int, g32=1.0):
+        self.fs, self.W, self.g32 = LN.check_rate(fs), LN.check_rate(fs) // 100, np.float32(g32)
+        if not (np.isfinite(self.g32) and self.g32 > 0):
+            raise ValueError("limiter: a pre-gain is a positive finite number")
+        self.pushed = self.emitted = 0
+        self.done = False
+        self.carry = np.zeros(0, dtype=np.float32)
+        self.stats = np.zeros((), dtype=STATS)
+        self.stats["g32"], self.stats["min_gain"] = self.g32, 1.0
+
+    def push(self, x, final: bool = False) -> np.ndarray:
+        if self.done:
+            raise ValueError("limiter: the stream has had its last push")
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        p = stream_plan(self.W, self.pushed, self.emitted, len(x), final)
+        assert p["carry_in"] == len(self.carry)
+        buf = np.concatenate([self.carry, x])
+        base = self.pushed - len(self.carry)                          # the signal position of buf[0]
+        lo, hi = self.emitted - base, p["emitted"] - base
+        if hi > lo:
+            u, _, s = gain_curve(buf, self.fs, self.g32)
+            u, s = u[lo:hi], s[lo:hi]
+            y = s * u
+            self.stats["min_gain"] = min(self.stats["min_gain"], s.min())
+            self.stats["n_over"] += int((np.abs(u) > T).sum())
+            self.stats["n_touched"] += int((s < 1).sum())
+        else:
+            y = np.zeros(0, dtype=np.float32)
+        self.carry = buf[len(buf) - p["carry_out"]:].copy()
+        self.pushed, self.emitted, self.done = p["total"], p["emitted"], bool(final)
+        return y

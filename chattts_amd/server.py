@@ -97,7 +97,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
                stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
-               pauses: bool = False, limiter: bool = False):
+               pauses: bool = False, limiter: bool = False, stream_limiter: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -169,7 +169,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     behind the loudness stage's gain, which then drops its ceiling term, or at unity gain (Chat.infer(limiter=) /
     SpeechBatcher.submit(limiter=)): no sample exceeds -1 dBFS and one loud peak no longer decides the level; false or null leaves
     the audio alone; a value that is no boolean gets a 400, `"stream": true` with it too (the look-ahead is not carried across
-    chunks), and /health carries `"limiter": true`."""
+    chunks), and /health carries `"limiter": true` -- unless `stream_limiter=True` (with `limiter`; default off): then a body with
+    `"stream": true, "limiter": true` is served, every chunk converted from samples that went through the request's limiter stream, 20 ms
+    behind (chattts_amd/limiter.py, the stream) -- from the pool with `batch_streams` when it can take it
+    (SpeechBatcher(stream_limiter=True).submit_stream(limiter=True)), serially otherwise (Chat.infer(stream=True, limiter=True,
+    stream_limiter=True)), with whatever streamed rate, speed and format the other options allow; such a body may also carry
+    `"gain_db"`, a fixed make-up gain of -30 .. +30 dB in front of the limiter (a bad value, or the key without `"stream": true` and
+    `"limiter": true`, gets a 400), and /health carries `"stream_limiter": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -187,7 +193,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         batcher = SpeechBatcher(chat, int(batch_slots), gpu_lock, logger=log, ragged_decode=ragged_decode, streams=bool(batch_streams),
                                 **({"refine": True} if batch_refine else {}), **({"stream_speeds": True} if speed and stream_speed else {}),
                                 **({"stream_speed_rates": True} if speed and stream_speed and stream_speed_rates else {}),
-                                **({"stream_flac": True} if flac and stream_flac else {}))
+                                **({"stream_flac": True} if flac and stream_flac else {}),
+                                **({"stream_limiter": True} if limiter and stream_limiter else {}))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
@@ -197,6 +204,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     pool_stream_speed_rates = pool_stream_speeds and speed_rates and bool(getattr(batcher, "stream_speed_rates", False))
     flac_streams = bool(flac and stream_flac)
     pool_stream_flac = pool_streams and flac_streams and bool(getattr(batcher, "stream_flac", False))
+    limiter_streams = bool(limiter and stream_limiter)
+    pool_stream_limiter = pool_streams and limiter_streams and bool(getattr(batcher, "stream_limiter", False))
     pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
     pool_split = bool(batch_split) and batcher is not None
     allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
@@ -246,6 +255,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     if limiter:
         from . import loudness as LN
         allowed = allowed | {"limiter"}
+    if limiter_streams:
+        from . import limiter as LM
+        allowed = allowed | {"gain_db"}
 
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
         model: str = "tts-1"
@@ -270,7 +282,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     stream_speed=12000, pass_first_n_batches=2)
 
     def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None,
-              as_flac: bool = False, lufs: Optional[float] = None, trim=None, lim: bool = False):     # openai_api.py:168-183,207-222
+              as_flac: bool = False, lufs: Optional[float] = None, trim=None, lim: bool = False, gdb=None):     # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
         if lim:
             kw = {**kw, "limiter": True}
@@ -292,6 +304,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             kw = {**kw, "stream_time_scale": True, "split_text": False}
             if rate != SAMPLE_RATE:                  # ... and another rate: the resampler's history and look-ahead are carried
                 kw = {**kw, "stream_scaled_resample": True}
+        if req.stream and lim:                       # likewise for a limited stream
+            kw = {**kw, "stream_limiter": True, "split_text": False, **({} if gdb is None else {"gain_db": gdb})}
         return chat.infer(text=[req.input], stream=bool(req.stream), lang=None, skip_refine_text=True, refine_text_only=False,
                           use_decoder=True, do_text_normalization=True, do_homophone_replacement=True,
                           params_infer_code=code_params(req.voice), pcm16=True, **kw)
@@ -370,9 +384,18 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     LN.check_rate(rate)
                 except ValueError as e:
                     raise HTTPException(400, detail=str(e))
-                if req.stream:
+                if req.stream and not limiter_streams:
                     raise HTTPException(400, detail="limiter is served for non-streamed requests only: the look-ahead is not carried "
                                                     "across chunks")
+        gdb = None                                   # the request's make-up gain in dB where it is honoured
+        if limiter_streams and request_data.get("gain_db") is not None:
+            if not (lim and req.stream):
+                raise HTTPException(400, detail='gain_db is the make-up gain of a limited stream: it goes with "stream": true and "limiter": true')
+            try:
+                LM.check_gain_db(request_data["gain_db"])
+            except ValueError as e:
+                raise HTTPException(400, detail=str(e))
+            gdb = float(request_data["gain_db"])
         refine = refine_of(request_data)
         rkw = {} if refine is None else {"refine": refine}
         if refine is not None and req.stream and not pool_streams:
@@ -423,11 +446,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             return _av_encode(pcm, fmt, rate)
 
         if req.stream and pool_streams and (spd is None or (pool_stream_speeds and (rate == SAMPLE_RATE or pool_stream_speed_rates))) \
-                and (not as_flac or pool_stream_flac):
+                and (not as_flac or pool_stream_flac) and (not lim or pool_stream_limiter):
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
                 skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
                 if spd is not None:
                     skw = {**skw, "speed": spd}
+                if lim:
+                    skw = {**skw, "limiter": True, **({} if gdb is None else {"gain_db": gdb})}
                 chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw, **ekw)
                 try:
                     first = True
@@ -450,7 +475,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        gen = infer(req, rate, law, spd, True) if as_flac else \
+                        gen = infer(req, rate, law, spd, as_flac, None, None, True, gdb) if lim else infer(req, rate, law, spd, True) if as_flac else \
                             infer(req, rate, law, spd) if spd is not None else (infer(req, rate) if law is None else infer(req, rate, law))
                         async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
                             if fmt == "wav" and first:
@@ -544,6 +569,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["pauses"] = True
         if limiter:
             out["limiter"] = True
+        if limiter_streams:
+            out["stream_limiter"] = True
         return out
 
     return app

@@ -668,7 +668,9 @@ class _Job:
     flac_slot: Optional[int] = None        # a FLAC stream: its stream of the encoder, opened at its first chunk
     loudness: Optional[float] = None       # a target in LUFS (non-streamed only); None: the level is left alone
     pauses: object = None                  # a pauses.PauseSpec (non-streamed only); None: the silence is left alone
-    limiter: bool = False                  # the look-ahead peak limiter behind the loudness stage's gain (non-streamed only)
+    limiter: bool = False                  # the look-ahead peak limiter behind the loudness stage's gain; a stream: in front of the conversion
+    lm_slot: Optional[int] = None          # a limited stream: its stream of the limiter, opened at its first chunk
+    lm_gain: Optional[float] = None        # ... and the float32 pre-gain of its `gain_db` (None: 1)
 
     @property
     def is_stream(self) -> bool:
@@ -780,7 +782,7 @@ class SpeechBatcher:
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
                  logger=None, ragged_decode: bool = False, streams: bool = False, refine: bool = False, make_text_pool=None,
                  text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False, stream_speed_rates: bool = False,
-                 stream_flac: bool = False):
+                 stream_flac: bool = False, stream_limiter: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
@@ -796,6 +798,8 @@ class SpeechBatcher:
         self.stream_scaled_chunks = 0      # chunks of streams at another speed than 1
         self.stream_flac = bool(stream_flac)       # submit_stream(flac=True) is accepted
         self.stream_flac_chunks = 0        # chunks handed out as FLAC frames (empty ones included)
+        self.stream_limiter = bool(stream_limiter)   # submit_stream(limiter=True) is accepted
+        self.stream_limited_chunks = 0     # chunks that came out of a limiter stream (empty ones included)
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.flac_encoded = 0              # results handed out as FLAC files
         self.trimmed = 0                   # results handed out with their pauses trimmed
@@ -902,7 +906,7 @@ class SpeechBatcher:
         self._in.put(_Cancel(fut.rid))
 
     def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None,
-                      speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False) -> SpeechStream:
+                      speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False, gain_db=None) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
@@ -921,9 +925,20 @@ class SpeechBatcher:
         chunks of the same request without `flac`.  The chunks of all FLAC streams due at one poll share ONE encoder step behind the
         one decoder pass (CodecEngine.decode_windows(flac=)); it combines with `sample_rate` and `speed` as far as the batcher serves
         those, not with `encoding`.  `loudness` is refused: an integrated loudness needs the whole utterance.  `pauses` is refused: the
-        run state would have to be carried across chunks.  `limiter` is refused: the look-ahead is not carried across chunks."""
-        if LM.check_flag(limiter, "submit_stream"):
+        run state would have to be carried across chunks.  `limiter` is refused: the look-ahead is not carried across chunks -- unless
+        the batcher was built with `stream_limiter=True`: then the request gets a limiter stream (opened at its first chunk, given back
+        where its other streams are) and its chunks are those of the serial call with `limiter=True, stream_limiter=True`: converted,
+        companded or FLAC-encoded from limited samples, 20 ms behind.  The limiter streams due at one poll share one step per round
+        behind their decoder pass (CodecEngine.decode_windows(limiter=)).  `gain_db` (with `limiter` only): the serial call's fixed
+        make-up gain in front of the limiter, -30 .. +30 dB."""
+        limiter = LM.check_flag(limiter, "submit_stream")
+        if limiter and not self.stream_limiter:
             raise ValueError("limiter applies to non-streamed requests only (the look-ahead is not carried across chunks)")
+        g32 = LM.check_gain_db(gain_db)
+        if g32 is not None and not limiter:
+            raise ValueError("gain_db is the make-up gain in front of the limiter: it needs limiter=True")
+        if limiter:
+            LN.check_rate(24000 if sample_rate is None else sample_rate)
         if PA.check(pauses) is not None:
             raise ValueError("pauses applies to non-streamed requests only (a stream would need the run state carried across chunks)")
         if LN.check_target(loudness) is not None:
@@ -954,7 +969,8 @@ class SpeechBatcher:
             if speed is not None and K - 1 > RS.CARRY:
                 raise ValueError(f"a streamed speed at {rate} Hz would carry up to {K - 1} samples, a resampler stream keeps {RS.CARRY}")
         h = SpeechStream(self, next(self._ids))
-        self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed, flac=bool(flac)))
+        self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed, flac=bool(flac),
+                          **({"limiter": True, "lm_gain": g32} if limiter else {})))
         return h
 
     def _check_refine(self, refine) -> None:
@@ -979,6 +995,8 @@ class SpeechBatcher:
                         "stream_resampled_chunks": self.stream_resampled_chunks, "stream_scaled_chunks": self.stream_scaled_chunks})
             if self.stream_flac:
                 occ["stream_flac_chunks"] = self.stream_flac_chunks
+            if self.stream_limiter:
+                occ["stream_limited_chunks"] = self.stream_limited_chunks
         if self.refine:
             occ["refine"] = {"active": len(getattr(tp, "active", {})), "queued": len(getattr(tp, "queue", ())),
                              "admissions": self.refine_admissions, "max_coresident": self.refine_max_coresident,
@@ -1009,6 +1027,9 @@ class SpeechBatcher:
         if job.flac_slot is not None:      # ... and its stream of the FLAC encoder
             slot, job.flac_slot = job.flac_slot, None
             self.chat.codec.flac_stream_close(slot)
+        if job.lm_slot is not None:        # ... and its stream of the limiter
+            slot, job.lm_slot = job.lm_slot, None
+            self.chat.codec.peak_limit_stream_close(slot)
         failed = isinstance(result, BaseException)
         if cancelled:
             self.cancelled += job.is_stream
@@ -1262,6 +1283,13 @@ class SpeechBatcher:
                     if j.flac and j.flac_slot is None:
                         j.flac_slot = self.chat.codec.flac_stream_open(24000 if j.sample_rate is None else j.sample_rate)
                 kw["flac_streams"] = [j.flac_slot for j in jobs]
+            if "limiter" in kw:           # the limiter streams due at this poll: one step per round behind their decode
+                self.stream_limited_chunks += sum(j.limiter for j in jobs)
+                for j in jobs:
+                    if j.limiter and j.lm_slot is None:
+                        j.lm_slot = self.chat.codec.peak_limit_stream_open(24000 if j.sample_rate is None else j.sample_rate,
+                                                                           1.0 if j.lm_gain is None else j.lm_gain)
+                kw["lm_streams"] = [j.lm_slot for j in jobs]
             pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **kw)
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for job in dict.fromkeys(jobs):

@@ -467,6 +467,41 @@ size_t ctts_peak_limit_ragged_scratch_bytes(const int64_t* off_host, int32_t n_s
 int ctts_peak_limit_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg, const int32_t* rate_dev,
                            const int32_t* rate_host, const float* gain_dev, void* stats, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The limiter of STREAMS: the segment exists nowhere as a whole, it arrives in pushes, and each step returns the samples the pushes so
+ * far decide.  y[i] depends on x[i - 2 W .. i + 2 W], so with pos samples in and more to come, samples [0, pos - 2 W) are out: a stream
+ * lags by 2 W samples (20 ms).  One step of one stream: x[in_off, in_off + n_in) are samples [pos, pos + n_in); it writes samples
+ * [e_lo, e_lo + n_out) of the limited stream to y[out_off ..], with e_lo = max(0, pos - 2 W) and e_lo + n_out = max(0, pos + n_in - 2 W),
+ * or pos + n_in = total on the last push (0: the stream ends empty); positions before sample 0 and from total on are silence.  The chunks of a stream,
+ * concatenated, are ctts_peak_limit_ragged of its concatenated pushes bit for bit (under the same condition on the float64 sums), however
+ * the signal was cut.  y is a buffer of its own and does not overlap x: nothing is limited in place.
+ * carry: [n_slots][2][CTTS_LM_CARRY] float32 on the device, two buffers per slot: a slot keeps its last min(pos, 4 W) RAW samples, a step
+ * reads buffer `phase` and writes the other, so the caller flips `phase` after every accepted step of a slot.
+ * stats: [n_slots] records of 16 bytes on the device, laid out as ctts_peak_limit_ragged's, accumulated over the samples EMITTED so far
+ * by integer atomics (the counts) and an atomic minimum on the bits (min s); after the last push a slot's record is the one-shot record.
+ * A slot is fresh by its descriptor alone: at pos == 0 no carry is read, and the records of the descriptors with pos == 0 are reset to
+ * {gain, 1, 0, 0} by a launch of its own in front of the step's, so the reset is ordered before the step's atomics by the kernel boundary
+ * (nothing has been emitted while pos == 0, so an empty first push resets nothing that counts).
+ * One launch over up to 1024 descriptors of any rates and gains; the table is given on the device and the host (the two must agree).  x
+ * and y may be null where n_x, n_y is 0.  A step with n_in == 0 or n_out == 0 still moves the carry.  Refused before anything is launched,
+ * from the host mirror: a null pointer, n_streams outside 1 .. 1024, a pool without a slot, y overlapping x, a negative length, position
+ * or offset, 2^31 samples, a push outside x, a chunk outside y, a rate that is no multiple of 10 Hz in 8000 .. 48000, a gain that is not
+ * positive and finite, a total that is neither -1 nor pos + n_in, e_lo, n_out, c_in = min(pos, 4 W) or c_out = min(pos + n_in, 4 W)
+ * (0 on the last push) other than these, a phase other than 0 / 1, a slot outside the pool or named twice in the call. */
+#define CTTS_LM_CARRY 1920
+typedef struct {
+  int64_t in_off, n_in;   /* the new samples: x[in_off, in_off + n_in) */
+  int64_t pos;            /* samples pushed before them */
+  int64_t total;          /* the stream's length when this push is its last, else -1 */
+  int64_t e_lo, n_out;    /* the step emits samples [e_lo, e_lo + n_out) of the limited stream */
+  int64_t out_off;        /* .. to y[out_off ..] */
+  int32_t slot, phase;    /* the state slot; which of its two carry buffers holds samples [pos - c_in, pos) */
+  int32_t c_in, c_out;    /* raw samples kept in front of the step; samples [pos + n_in - c_out, pos + n_in) kept behind it (0 on the last push) */
+  int32_t rate;           /* Hz */
+  float gain;             /* the float32 pre-gain g32 */
+} ctts_lm_stream;         /* 80 bytes (limiter stream) */
+int ctts_peak_limit_stream_step(const float* x, int64_t n_x, const ctts_lm_stream* st_dev, const ctts_lm_stream* st_host, int32_t n_streams,
+                                float* y, int64_t n_y, float* carry, void* stats, int32_t n_slots, void* stream);
+
 /* Pause control: packed float32 segments in[off[s], off[s+1]) lose edge silence and long inner pauses, frame by frame (the definition,
  * once, is chattts_amd/pauses.py).  Segment s has the row rows[8 s ..]: F (samples per 10 ms frame, 80 .. 480), pad, lead, tail, P (frames;
  * P = 0: the segment is copied through), thr (float32 bits, a frame is active when some sample has !(|x| < thr)), the offset of its
@@ -499,7 +534,7 @@ int ctts_trim_pauses_ragged(const float* in, float* out, const int64_t* off_dev,
  * by its descriptor alone: at pos == 0 no carry is read, and at k_prev == 0 no state -- a reused slot never sees what it held.
  * The descriptor table is given on the device and the host (the two must agree).  x, y and path may be null where n_x, n_y, n_path is 0.
  * Refused before anything is launched, from the host mirror: a null pointer, n_streams outside 1 .. 1024, den != 100, num outside
- * 50 .. 200 or num == den, a negative length, position or offset, a push outside x, a total that is neither -1 nor pos + n_in (>= 1),
+ * 50 .. 200 or num == den, a negative length, position or offset, a push outside x, a total that is neither -1 nor pos + n_in,
  * k_prev != K(pos), k_now other than K(pos + n_in) (F - 1 on the last push), n_out other than the plan's or a chunk outside y, path
  * entries outside path, a phase other than 0 / 1, a carry (in front of or behind the step) above CTTS_TS_CARRY, a slot outside the pool
  * or named twice in the call, a position within 4096 of 2^31.  Stream-ordered: one launch, one workgroup per stream. */

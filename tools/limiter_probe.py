@@ -13,9 +13,16 @@ ctts_loudness_limited_ragged):
                 pair towards -5 LUFS on a pack of sine bursts, out of place: every tile computes its gain curve.  The limiter call
                 alone on both packs as well.
 
+  * --stream  : the limiter of STREAMS (ctts_peak_limit_stream_step) instead: 1 / 8 / 64 streams, each pushed 12 000 samples per step
+                (half a second at 24 kHz, a served stream's chunk), `quiet` (noise under 0.3: every tile leaves early) and `loud` (the
+                same noise at 4x: every tile computes its curve).  The descriptors of `--reps` consecutive steps are uploaded first;
+                device time of one step from events around those steps, median (min .. max) of `--rounds` rounds, alternated with the
+                one-shot ctts_peak_limit_ragged on the same samples (as many segments of 12 000) and with the window decode the step
+                rides behind (`decode_windows` of as many 12 000-sample chunks, 16 bit).  Writes a markdown table to `--out`.
+
 Noise under a stepped envelope; synthetic weights.  Prints one JSON line.  Not a bench.py leg.
 
-    python tools/limiter_probe.py [--reps 20] [--rounds 7]
+    python tools/limiter_probe.py [--reps 20] [--rounds 7] [--stream --out profiles/limiter_stream_probe.md]
 """
 from __future__ import annotations
 
@@ -146,11 +153,115 @@ def _stage(codec, reps, rounds):
     return dict(segments=N_SEG, segment_samples=SEG, records=recs, call_ms=ms)
 
 
+CHUNK = 12000         # samples per push of the stream probe
+
+
+def _stream(codec, reps, rounds):
+    """step time of 1 / 8 / 64 limiter streams, quiet and loud, against the one-shot limiter on the same samples and the window decode"""
+    from chattts_amd import _lib
+    dev = codec.device
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    r = np.random.default_rng(5)
+    out = {}
+    for B in (1, 8, 64):
+        env = np.repeat(r.choice([0.003, 0.05, 0.3], size=B * CHUNK // 1200), 1200)
+        x = torch.from_numpy((r.uniform(-1, 1, B * CHUNK) * env).astype(np.float32)).to(dev)
+        y = torch.empty_like(x)
+        hs = [codec.peak_limit_stream_open(24000) for _ in range(B)]
+        pool = codec._lm_pool()
+        W = 240
+        # step k of every stream: the same B x CHUNK samples again, at position k * CHUNK (k = 0 emits 2 W fewer: it is the warm-up)
+        tabs = []
+        for k in range(reps + 1):
+            tab = np.zeros(B, _lib.LM_STREAM)
+            for i, h in enumerate(hs):
+                p = LM.stream_plan(W, k * CHUNK, max(0, k * CHUNK - 2 * W), CHUNK, False)
+                tab[i] = (i * CHUNK, CHUNK, k * CHUNK, -1, p["e_lo"], p["n_out"], i * CHUNK, h, k & 1, p["carry_in"], p["carry_out"], 24000, 1.0)
+            tabs.append(tab)
+        tabs_d = [torch.from_numpy(t.view(np.uint8)).to(dev) for t in tabs]
+        off = np.arange(B + 1, dtype=np.int64) * CHUNK
+        hz = np.full(B, 24000, np.int32)
+        off_d, hz_d = torch.from_numpy(off).to(dev), torch.from_numpy(hz).to(dev)
+        gains = torch.ones(B, dtype=torch.float32, device=dev)
+        sb = int(codec.lib.ctts_peak_limit_ragged_scratch_bytes(vp(off), B))
+        scr = torch.empty(sb, dtype=torch.uint8, device=dev)
+        lstats = torch.empty(LM.STATS.itemsize * B, dtype=torch.uint8, device=dev)
+        store = torch.from_numpy(np.random.RandomState(3).standard_normal((B, 64, 768)).astype(np.float32) * 0.5).to(dev)
+        wins = [(i, 48, 0, CHUNK, False) for i in range(B)]
+
+        def steps(gain):
+            for k in range(reps + 1):
+                tabs[k]["gain"] = gain
+            for t, td in zip(tabs, tabs_d):
+                td.copy_(torch.from_numpy(t.view(np.uint8)))
+
+            def run(lo=1):
+                for k in range(lo, reps + 1):
+                    rc = codec.lib.ctts_peak_limit_stream_step(x.data_ptr(), x.numel(), tabs_d[k].data_ptr(), vp(tabs[k]), B, y.data_ptr(), y.numel(),
+                                                               pool["carry"].data_ptr(), pool["stats"].data_ptr(), int(pool["carry"].shape[0]), st)
+                    assert rc == 0, codec.lib.ctts_last_error()
+            return run
+
+        def one_shot(gain):
+            def run():
+                for _ in range(reps):
+                    rc = codec.lib.ctts_peak_limit_ragged(x.data_ptr(), y.data_ptr(), off_d.data_ptr(), vp(off), B, hz_d.data_ptr(), vp(hz), gains.data_ptr(),
+                                                          lstats.data_ptr(), scr.data_ptr(), sb, st)
+                    assert rc == 0, codec.lib.ctts_last_error()
+            return run
+
+        def decode():
+            for _ in range(reps):
+                codec.decode_windows(store, wins)
+        res = {}
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for name, gain in (("quiet", 1.0), ("loud", 4.0)):
+            run_s, run_o = steps(np.float32(gain)), one_shot(gain)
+            gains.fill_(gain)
+            run_s(0)                                       # warm: step 0 included, it resets the records
+            run_o()
+            decode()
+            torch.cuda.synchronize()
+            rec = pool["stats"][hs].cpu().numpy().view(LM.STATS).reshape(-1)
+            times = {"stream_step": [], "one_shot": [], "window_decode": []}
+            for _ in range(rounds):
+                for key, fn in (("stream_step", run_s), ("one_shot", run_o), ("window_decode", decode)):
+                    torch.cuda.synchronize()
+                    a.record()
+                    fn()
+                    b.record()
+                    b.synchronize()
+                    times[key].append(a.elapsed_time(b) / reps)
+            res[name] = dict(n_over=int(rec["n_over"].sum()), n_touched=int(rec["n_touched"].sum()),
+                             **{k: dict(median=round(float(np.median(v)), 4), min=round(float(np.min(v)), 4), max=round(float(np.max(v)), 4))
+                                for k, v in times.items()})
+        for h in hs:
+            codec.peak_limit_stream_close(h)
+        out[str(B)] = res
+    return out
+
+
+def _stream_markdown(res, reps, rounds, gemm) -> str:
+    rows = ["# The limiter of streams: step time (tools/limiter_probe.py --stream)", "",
+            f"MI355X, device events around {reps} back-to-back calls, median (min .. max) of {rounds} rounds, the three calls alternated; chunks of "
+            f"{CHUNK} samples at 24 kHz per stream; `window_decode` is `decode_windows` of as many {CHUNK}-sample chunks (codec GEMM {gemm}, synthetic weights).", "",
+            "| streams | signal | samples over T | stream step, ms | one-shot limiter, ms | window decode, ms | step / decode |", "|---|---|---|---|---|---|---|"]
+    f = lambda d: f"{d['median']:.4f} ({d['min']:.4f} .. {d['max']:.4f})"
+    for B, by in res.items():
+        for name, d in by.items():
+            rows.append(f"| {B} | {name} | {d['n_over']} | {f(d['stream_step'])} | {f(d['one_shot'])} | {f(d['window_decode'])} | "
+                        f"{100.0 * d['stream_step']['median'] / d['window_decode']['median']:.1f} % |")
+    return "\n".join(rows) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--gemm", default="f16")
+    ap.add_argument("--stream", action="store_true", help="time the limiter of streams instead")
+    ap.add_argument("--out", default=None, help="with --stream: the markdown table goes here")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("limiter_probe needs a GPU: nothing here can be timed without one")
@@ -161,6 +272,13 @@ def main():
     chat = Chat()
     assert chat.load(state_dicts={k: sds[k] for k in ("gpt", "embed", "decoder", "vocos")}, device=dev, dtype="f32", codec_gemm=a.gemm)
     codec = chat.codec
+    if a.stream:
+        res = _stream(codec, a.reps, a.rounds)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(_stream_markdown(res, a.reps, a.rounds, a.gemm))
+        print(json.dumps(dict(metric="limiter_stream_probe", reps=a.reps, rounds=a.rounds, codec_gemm=a.gemm, chunk=CHUNK, streams=res)))
+        return
     out = dict(metric="limiter_probe", target=TARGET, reps=a.reps, rounds=a.rounds, codec_gemm=a.gemm, fixtures={}, batch={})
     sig = [s for s in LC.signals() if s[0] not in ("zeros", "silent")]
     for fs in (8000, 24000):
