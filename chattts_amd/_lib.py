@@ -214,6 +214,7 @@ SIGNATURES = {
     "ctts_k_mlp_fused": (C.c_int, [P, P, P, I32, I32, P, P, P, P, I32, P]),
     "ctts_k_gemm_fast": (C.c_int, [P, I32, P, I32, I32, I32, P, F, I32, P, I32, P, I32, P, P]),
     "ctts_k_qkv_rope": (C.c_int, [P, P, I32, P, F, P, P, P, I32, P, P, I32, P, P, I32, P]),
+    "ctts_k_qkv_rope_ex": (C.c_int, [P, P, I32, P, F, P, P, P, I32, P, P, I32, P, P, I32, P, I32, P]),
     "ctts_k_gemm_dec": (C.c_int, [P, P, I32, I32, I32, P, P, F, I32, P, I32, P, I32, P, I32, P]),
     "ctts_k_gemm_dec32x": (C.c_int, [P, C.c_int64, P, C.c_int64, I32, I32, I32, P, P, I32, F, I32, P, I32, P, I32, P, C.c_int64, I32, P, I32, P, P, P]),
     "ctts_k_gemm_pre_x3": (C.c_int, [P, I32, P, P, I32, I32, I32, I32, I32, P, P, P, I32, P]),
@@ -223,6 +224,7 @@ SIGNATURES = {
     "ctts_k_rope_append": (C.c_int, [P, P, P, I32, I32, P, P, I32, P, P, I32, P]),
     "ctts_k_attention": (C.c_int, [P, P, P, I32, I32, P, I32, P, P, I32, P]),
     "ctts_k_attention_prefill": (C.c_int, [P, P, P, I32, P, I32, I32, P, I32, P]),
+    "ctts_k_attention_prefill_ex": (C.c_int, [P, P, P, I32, P, I32, I32, I32, P, P, I32, P]),
     "ctts_k_attention_dec": (C.c_int, [P, P, P, I32, P, P, P, I32, P, P, I32, P]),
     "ctts_k_attention_dec2": (C.c_int, [P, P, P, I32, I32, P, P, P, I32, I32, P]),
     "ctts_k_attention_cfg": (C.c_int, [I32, I32, I32]),

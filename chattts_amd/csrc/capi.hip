@@ -1621,6 +1621,24 @@ extern "C" int ctts_k_qkv_rope(const uint16_t* A, const uint16_t* W, int32_t M, 
   CK(launch_gemm_fast(f, (hipStream_t)stream));
   return 0;
 }
+// the same with the prompt chunk's first slot and the slot-pool row_map that run_step passes (tests)
+extern "C" int ctts_k_qkv_rope_ex(const uint16_t* A, const uint16_t* W, int32_t M, const float* ssq_in, float eps, float* qkv, uint16_t* kcache,
+                                  uint16_t* vcache, int32_t cmax, const float* cos_tab, const float* sin_tab, int32_t q_per_b,
+                                  const int32_t* len, const int32_t* kv_start, int32_t slot0, const int32_t* row_map, int32_t force_mb,
+                                  void* stream) {
+  const char* who = "ctts_k_qkv_rope_ex";
+  if (!A || !W || !ssq_in || !qkv || !kcache || !vcache || !cos_tab || !sin_tab || !kv_start) return fail("%s: null pointer", who);
+  if (q_per_b < 1 || M <= 0 || (q_per_b == 1 && !len)) return fail("%s: bad q_per_b / M (q_per_b == 1 is a decode launch and needs len)", who);
+  if (q_per_b > 1 && (M % q_per_b != 0 || slot0 < 0 || slot0 + q_per_b > cmax))
+    return fail("%s: M must be a multiple of q_per_b and slots [slot0, slot0 + q_per_b) must lie inside the cache rows", who);
+  FastGemmArgs f;
+  memset(&f, 0, sizeof(f));
+  f.A = A; f.lda = HID; f.W = W; f.M = M; f.N = 3 * HID; f.K = HID; f.ssq_in = ssq_in; f.eps = eps; f.epi = FEPI_QKV_ROPE; f.C32 = qkv;
+  f.ldc = 3 * HID; f.q_per_b = q_per_b; f.len = len; f.kv_start = kv_start; f.cos_t = cos_tab; f.sin_t = sin_tab; f.kc = kcache;
+  f.vc = vcache; f.cmax = cmax; f.force_mb = force_mb; f.slot0 = slot0; f.row_map = row_map;
+  CK(launch_gemm_fast(f, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_k_gemm_dec(const uint16_t* Ap, const uint16_t* Wp, int32_t M, int32_t N, int32_t K, const int32_t* n_active,
                                const float* ssq_in, float eps, int32_t epi, float* C32, int32_t ldc, uint16_t* Cp, int32_t kch_out,
                                float* ssq_out, int32_t force_mb, void* stream) {
@@ -1679,6 +1697,20 @@ extern "C" int ctts_k_attention_prefill(const float* qkv, const uint16_t* kcache
                                         int32_t slot0, const int32_t* kv_start, int32_t M, void* stream) {
   GptRowMap rm{q_per_b, nullptr, kv_start, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, slot0, 0};
   CK(launch_attention(qkv, kcache, vcache, WT_BF16, cmax, out, 0, rm, M, (hipStream_t)stream));
+  return 0;
+}
+// the prompt pass's attention as run_step launches it (tests): the shipped bf16-output instantiations and the slot-pool row_map
+extern "C" int ctts_k_attention_prefill_ex(const float* qkv, const uint16_t* kcache, const uint16_t* vcache, int32_t cmax, void* out, int32_t out_bf16,
+                                           int32_t q_per_b, int32_t slot0, const int32_t* kv_start, const int32_t* row_map, int32_t M,
+                                           void* stream) {
+  const char* who = "ctts_k_attention_prefill_ex";
+  if (!qkv || !kcache || !vcache || !out || !kv_start) return fail("%s: null pointer", who);
+  if (out_bf16 != 0 && out_bf16 != 1) return fail("%s: out_bf16 is 0 (f32) or 1 (bf16)", who);
+  // q_per_b == 1 is the decode convention of GptRowMap (slot = len[b] - 1): not a prompt pass, and there is no `len` here
+  if (q_per_b < 2 || M <= 0 || M % q_per_b != 0) return fail("%s: M must be a positive multiple of q_per_b >= 2", who);
+  if (slot0 < 0 || slot0 + q_per_b > cmax) return fail("%s: slots [slot0, slot0 + q_per_b) must lie inside the cache rows", who);
+  GptRowMap rm{q_per_b, nullptr, kv_start, row_map, nullptr, nullptr, nullptr, nullptr, nullptr, 0, slot0, 0};
+  CK(launch_attention(qkv, kcache, vcache, WT_BF16, cmax, out, out_bf16, rm, M, (hipStream_t)stream));
   return 0;
 }
 extern "C" int ctts_k_attention_dec(const float* qkv, const uint16_t* kcache, const uint16_t* vcache, int32_t cmax, uint16_t* out_packed,

@@ -877,6 +877,12 @@ int ctts_k_gemm_fast(const uint16_t* A, int32_t lda, const uint16_t* W, int32_t 
 int ctts_k_qkv_rope(const uint16_t* A, const uint16_t* W, int32_t M, const float* ssq_in, float eps, float* qkv, uint16_t* kcache,
                     uint16_t* vcache, int32_t cmax, const float* cos_tab, const float* sin_tab, int32_t q_per_b, const int32_t* len,
                     const int32_t* kv_start, int32_t force_mb, void* stream);
+/* the same as the prompt pass launches it: row m of a q_per_b > 1 launch appends at KV slot slot0 + m % q_per_b of utterance
+ * row_map[m / q_per_b] (row_map NULL: m / q_per_b) -- a later chunk of a prompt, a row group admitted into a slot pool; kv_start is indexed
+ * by the utterance.  Refuses null pointers and a chunk that does not fit the cmax cache rows. */
+int ctts_k_qkv_rope_ex(const uint16_t* A, const uint16_t* W, int32_t M, const float* ssq_in, float eps, float* qkv, uint16_t* kcache,
+                       uint16_t* vcache, int32_t cmax, const float* cos_tab, const float* sin_tab, int32_t q_per_b, const int32_t* len,
+                       const int32_t* kv_start, int32_t slot0, const int32_t* row_map, int32_t force_mb, void* stream);
 /* decode-step projection on fragment-packed operands (csrc/decode.hip): Ap [ceil(M/16)][K/32][64][8] bf16, Wp packed likewise
  * (epi 2: gate tiles then up tiles); epi 1 = residual add (C32 in place, Cp packed bf16 copy with kch_out = N/32, ssq_out),
  * 2 = SiLU(gate)*up -> Cp packed (kch_out = N/32).  n_active: device scalar or NULL.  force_mb: rows/16 per workgroup (0 = default) */
@@ -921,6 +927,11 @@ int ctts_k_attention(const float* qkv, const void* kcache, const void* vcache, i
  * flash-style MFMA kernel runs (csrc/gpt.hip attention_prefill_mfma_k), the per-row kernel below that */
 int ctts_k_attention_prefill(const float* qkv, const uint16_t* kcache, const uint16_t* vcache, int32_t cmax, float* out, int32_t q_per_b,
                              int32_t slot0, const int32_t* kv_start, int32_t M, void* stream);
+/* the same with the output type and the slot-pool map of the prompt pass: out_bf16 0 = f32 [M,768], 1 = bf16 [M,768] row-major (what the
+ * perf mode's o_proj reads); row_map [M / q_per_b] or NULL: row group -> utterance slot of the cache, kv_start indexed by that slot.
+ * Refuses null pointers, out_bf16 outside {0, 1}, q_per_b < 2 (q_per_b == 1 is a decode launch) and a chunk beyond the cmax cache rows. */
+int ctts_k_attention_prefill_ex(const float* qkv, const uint16_t* kcache, const uint16_t* vcache, int32_t cmax, void* out, int32_t out_bf16,
+                                int32_t q_per_b, int32_t slot0, const int32_t* kv_start, const int32_t* row_map, int32_t M, void* stream);
 /* decode attention of the perf mode: one query row per utterance, bf16 KV cache [slots,12,cmax,64], output bf16 in the fragment-packed
  * order of csrc/decode.hip; desc [M][4] int32 = {utterance slot (-1: skip), KV slot of the query, RoPE position (unused here), first
  * visible key}; n_active: device scalar or NULL (M).  n_cu > 0 with part ([n_cu][8][66] f32) and cnt ([n_cu] int32, zeroed) turns on
