@@ -73,6 +73,13 @@ TS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("tota
                       ("n_out", "<i4"), ("reserved", "<i4")])
 
 
+# ctts_pa_stream (96 bytes): in_off, n_in, pos, out_off, fr_off, list_off int64; slot, phase, need, fin, F, pad, lead, tail, P int32; thr float32;
+# fade, n_list int32
+PA_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("out_off", "<i8"), ("fr_off", "<i8"), ("list_off", "<i8"),
+                      ("slot", "<i4"), ("phase", "<i4"), ("need", "<i4"), ("fin", "<i4"), ("F", "<i4"), ("pad", "<i4"), ("lead", "<i4"),
+                      ("tail", "<i4"), ("P", "<i4"), ("thr", "<f4"), ("fade", "<i4"), ("n_list", "<i4")])
+
+
 # ctts_lm_stream (80 bytes): in_off, n_in, pos, total, e_lo, n_out, out_off int64; slot, phase, c_in, c_out, rate int32; gain float32
 LM_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("e_lo", "<i8"), ("n_out", "<i8"),
                       ("out_off", "<i8"), ("slot", "<i4"), ("phase", "<i4"), ("c_in", "<i4"), ("c_out", "<i4"), ("rate", "<i4"),
@@ -180,6 +187,8 @@ SIGNATURES = {
     "ctts_peak_limit_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P]),
     "ctts_trim_pauses_ragged_scratch_bytes": (SZ, [C.c_int64, I32]),
     "ctts_trim_pauses_ragged": (C.c_int, [P, P, P, P, P, P, P, P, I32, P, I32, P, P, P, SZ, P]),
+    "ctts_trim_pauses_stream_scratch_bytes": (SZ, [C.c_int64, C.c_int64]),
+    "ctts_trim_pauses_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P, I32, P, P, SZ, P]),
     "ctts_time_scale_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, C.c_int64, P, P, I32, P, P]),
     "ctts_codec_windows_workspace_bytes": (SZ, [I32, I32]),
     "ctts_codec_decode_windows": (C.c_int, [P, P, C.c_int64, C.c_int64, I32, I32, P, P, I32, I32, P, P, I32, F, P, SZ, P]),

@@ -550,7 +550,8 @@ class Chat:
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts, *(() if encs is None else (encs,)))]
 
     def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None,
-                             rs_streams=None, flac=None, flac_streams=None, limiter=None, lm_streams=None) -> List[np.ndarray]:
+                             rs_streams=None, flac=None, flac_streams=None, limiter=None, lm_streams=None, pauses=None,
+                             pa_streams=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
         (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream).  `encodings`: one per window, None / "ulaw" / "alaw" -- a
@@ -572,6 +573,8 @@ class Chat:
             kw["flac"], kw["flac_streams"] = flac, flac_streams
         if limiter is not None:
             kw["limiter"], kw["lm_streams"] = limiter, lm_streams
+        if pauses is not None:          # a flagged window goes through its pause stream in front of all that (CodecEngine.decode_windows(pauses=))
+            kw["pauses"], kw["pa_streams"] = pauses, pa_streams
         return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, **kw)
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
@@ -692,6 +695,73 @@ class Chat:
         if lm_handles:
             y, off = codec.peak_limit_stream_step(y, [(h, int(off[i]), int(off[i + 1] - off[i]), final) for i, h in enumerate(lm_handles)])
         return self._finish_piece(y.view(B, int(off[1])), final, pcm16, encoding, on_device)
+
+    def _stream_rows_paused(self, hiddens, a: int, b: Optional[int], final: bool, pa_handles, rate: Optional[int] = None, ts_handles=None,
+                            rs_handles=None, lm_handles=None, pcm16: bool = False, encoding=None, fs_handles=None) -> list:
+        """One chunk of a PAUSED stream (Chat.infer's `stream_pauses`): samples [a, b) of the decode of the current prefix go through
+        the rows' float stages as in `_stream_piece` / `_stream_piece_scaled` (the resampled window at `rate`, or the time scaler's
+        streams `ts_handles` and behind them the resampler's `rs_handles`), then into the rows' pause streams `pa_handles`
+        (CodecEngine.trim_pauses_stream_step, all rows in one step) -- the one-shot chain's order: behind the last float stage, in front
+        of the limiter streams `lm_handles`, the 16-bit conversion (one peak per row over the samples that come out), G.711 and the
+        FLAC streams `fs_handles`.  The rows emit different numbers of samples, so the chunk is a list with one array per row,
+        possibly empty.  `final`: the streams' last push; every row's own samples with |x| <= 1e-5 are removed (the reference's tail
+        filter, core.py:500-503, read for one row) and the rest is converted on the host, as a limited stream's last chunk is."""
+        codec, B = self.codec, len(hiddens)
+        Tn = max(int(r.size(0)) for r in hiddens)
+        total = max(0, 256 * (2 * Tn - 1))
+        hi = total if b is None else min(b, total)
+        m = max(0, hi - a)
+        rkw = {} if rate is None or ts_handles is not None else {"sample_rate": rate}
+        if m > 0 and self.incremental_stream:
+            x = codec.decode_window(hiddens, a, hi, **rkw).contiguous()
+        elif m > 0:            # decoded whole on the host path: the piece goes back to the device for the streams
+            skw = {} if not rkw else {"rate": rate}
+            x = torch.from_numpy(np.ascontiguousarray(self._stream_piece(hiddens, a, b, True, False, **skw), dtype=np.float32)).to(self.device)
+        else:
+            x = torch.empty((B, 0), dtype=torch.float32, device=self.device)
+        w = int(x.shape[1])
+        y, off = x.view(-1), np.arange(B + 1, dtype=np.int64) * w
+        step = lambda fn, hs: fn(y, [(h, int(off[i]), int(off[i + 1] - off[i]), final) for i, h in enumerate(hs)])
+        if ts_handles is not None:
+            y, off = step(codec.time_scale_stream_step, ts_handles)
+            if rs_handles:
+                y, off = step(codec.resample_stream_step, rs_handles)
+        y, off = step(codec.trim_pauses_stream_step, pa_handles)
+        if lm_handles:
+            y, off = step(codec.peak_limit_stream_step, lm_handles)
+        off = np.asarray(off, dtype=np.int64)
+        n = np.diff(off)
+        if final or not pcm16:
+            host = codec.to_host(y.contiguous())
+            rows = [host[off[i]: off[i + 1]] for i in range(B)]
+            if not final:
+                return rows
+            rows = [r[np.abs(r) > 1e-5] for r in rows]
+            if not pcm16:
+                return rows
+            rows = [float_to_int16(r) if r.size else r.astype(np.int16) for r in rows]
+            if encoding is not None:
+                return [G711.encode(r, encoding) for r in rows]
+            if fs_handles is None:
+                return rows
+            pcm = torch.from_numpy(np.concatenate(rows) if int(sum(r.size for r in rows)) else np.zeros(0, np.int16)).to(self.device)
+            n = np.array([r.size for r in rows], dtype=np.int64)
+            off = np.concatenate([[0], np.cumsum(n)])
+        elif int(off[-1]) == 0:
+            pcm = torch.zeros((0,), dtype=torch.int16, device=self.device)
+        else:                  # every row under its own peak, on the device; empty rows are no segments
+            seg = np.concatenate([[0], off[1:][n > 0]])
+            pcm = codec.float_to_int16_ragged(y.contiguous(), seg)[0]
+        if fs_handles is not None:      # every row's push starts on a multiple of 8 samples
+            start = np.concatenate([[0], np.cumsum((n + 7) // 8 * 8)])
+            buf = torch.zeros((max(8, int(start[-1])),), dtype=torch.int16, device=self.device)
+            for i in range(B):
+                if n[i]:
+                    buf[int(start[i]): int(start[i]) + int(n[i])] = pcm[int(off[i]): int(off[i + 1])]
+            return codec.flac_stream_step(buf, [(h, int(start[i]), int(n[i]), final) for i, h in enumerate(fs_handles)])
+        host = codec.to_host(pcm)
+        rows = [host[off[i]: off[i + 1]] for i in range(B)]
+        return rows if encoding is None else [G711.encode(r, encoding) if r.size else r.astype(np.uint8) for r in rows]
 
     def _finish_piece(self, y: torch.Tensor, final: bool, pcm16: bool, encoding, on_device: bool):
         """what a stream step emitted, [B, n] float32 on the device -> the piece: float32 on the host (`final`, or not `pcm16`), else
@@ -832,7 +902,7 @@ class Chat:
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
               flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None,
-              stream_limiter: bool = False, gain_db=None):
+              stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -916,6 +986,12 @@ class Chat:
         companded and FLAC-encoded from limited samples.  The stream lags by 20 ms (rate // 50 samples: a sample's gain needs the 20 ms
         behind it); its chunks, end to end, are the limiter of the whole float stream bit for bit, and the last chunk brings the rest.
         One flag for the whole batch; refused with `split_text` and without the decoder.
+        `stream_pauses=True` (keyword-only): then `pauses` goes with `stream=True` -- one spec for the whole batch; every row gets a pause
+        stream (CodecEngine.trim_pauses_stream_*), opened at the first chunk and closed when the generator ends or is dropped, behind the
+        last float stage and in front of the limiter stream and the conversion.  The rows emit different numbers of samples, so every
+        yield is a list with one array per row, possibly empty, as a streamed FLAC yields; per row the chunks, end to end, are the
+        one-shot `pauses` result of that row's stream.  Refused with `split_text`, without the decoder, and for a spec whose
+        `pauses.stream_need` exceeds `pauses.STREAM_FRAMES`.  Without the switch the refusal above stays.
         `gain_db` (keyword-only; with `stream=True, limiter=True, stream_limiter=True` only): a fixed make-up gain in dB, -30 .. +30, one
         for the whole batch, applied in front of the limiter as its float32 pre-gain 10 ** (gain_db / 20).  A non-streamed call has
         `loudness` for its level and refuses it."""
@@ -944,8 +1020,18 @@ class Chat:
         if mkw:
             LN.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         pkw = Plan.given("infer", pauses=pauses).kwargs()
-        if pkw and stream:
+        if pkw and stream and not stream_pauses:
             raise ValueError("pauses applies to non-streamed inference only (a stream would need the run state carried across chunks)")
+        spkw = {}
+        if pkw and stream:
+            if isinstance(pauses, (list, tuple)):
+                raise ValueError("a paused stream takes one pause spec for the whole batch")
+            if split_text:
+                raise ValueError("a paused stream does not go with split_text (every split batch would end the stream)")
+            if not use_decoder:
+                raise ValueError("a paused stream needs the hidden-state decoder (use_decoder=True)")
+            spkw = {"pa_spec": PA.check_stream(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate), pauses, "infer")[1]}
+            pkw = {}
         if pkw and split_text and isinstance(pauses, (list, tuple)):
             raise ValueError("a split_text request is one waveform: it takes one pause spec")
         if pkw:
@@ -1015,7 +1101,7 @@ class Chat:
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
                               sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}),
-                              **({} if split_host else lkw), **pkw, **smkw)
+                              **({} if split_host else lkw), **pkw, **smkw, **spkw)
         if stream:
             return res_gen
         if refine_text_only:
@@ -1054,8 +1140,8 @@ class Chat:
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None):
-        """core.py:395-503 (generator).  `lm_gain` with `stream`: the rows' limiter streams and their pre-gain (Chat.infer's `stream_limiter`).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
+               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None, pa_spec=None):
+        """core.py:395-503 (generator).  `pa_spec` with `stream`: the rows' pause streams and their spec (Chat.infer's `stream_pauses`).  `lm_gain` with `stream`: the rows' limiter streams and their pre-gain (Chat.infer's `stream_limiter`).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
             text = [text]
@@ -1078,14 +1164,18 @@ class Chat:
         rs = [] if ts is not None and sample_rate is not None else None      # ... at another rate: and their streams of the resampler
         fs = [] if stream and flac and pcm16 else None         # a streamed FLAC: the rows' FLAC streams, opened at the first chunk
         lm = [] if stream and lm_gain is not None else None    # a limited stream: the rows' limiter streams, opened at the first chunk
+        pa = [] if stream and pa_spec is not None else None    # a paused stream: the rows' pause streams, opened at the first chunk
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
                                            encoding, speed, ts, rs, **({"flac": True} if flac else {}),
                                            **({} if loudness is None else {"loudness": loudness}), **({} if fs is None else {"fs": fs}),
                                            **({} if pauses is None else {"pauses": pauses}),
                                            **({} if limiter is None else {"limiter": limiter}),
-                                           **({} if lm is None else {"lm": lm, "lm_gain": lm_gain}))
+                                           **({} if lm is None else {"lm": lm, "lm_gain": lm_gain}),
+                                           **({} if pa is None else {"pa": pa, "pa_spec": pa_spec}))
         finally:
+            for h in pa or ():
+                self.codec.trim_pauses_stream_close(h)
             for h in lm or ():
                 self.codec.peak_limit_stream_close(h)
             for h in fs or ():
@@ -1097,7 +1187,7 @@ class Chat:
                 self.codec.resample_stream_close(h)
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None):
+                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None, pa=None, pa_spec=None):
         """the batch loop of `_infer`"""
         def flac_chunks(piece, final):
             """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' FLAC
@@ -1135,6 +1225,17 @@ class Chat:
             if not lm:
                 lm.extend(self.codec.peak_limit_stream_open(CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate, lm_gain) for _ in rows)
             return {"lm_handles": lm}
+        def paused(rows, a, b, final):
+            """one chunk of a paused stream: a list with one array per row (`_stream_rows_paused`); every stream is opened at the first"""
+            out_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate
+            if not pa:
+                pa.extend(self.codec.trim_pauses_stream_open(out_rate, pa_spec) for _ in rows)
+            if ts is not None and not ts:
+                open_streams(rows)
+            if fs is not None and not fs:
+                fs.extend(self.codec.flac_stream_open(out_rate) for _ in rows)
+            return self._stream_rows_paused(rows, a, b, final, pa, sample_rate, ts, rs, limited(rows).get("lm_handles"), pcm16,
+                                            encoding if pcm16 else None, fs)
         length = 0
         pass_batch_count = 0
         for lo in range(0, len(text), step):
@@ -1180,14 +1281,16 @@ class Chat:
                 skw = {"rate": sample_rate} if sample_rate is not None else {}      # 24 kHz: today's call, argument for argument
                 if encoding is not None and pcm16:
                     skw["encoding"] = encoding
-                if ts is not None:
+                if pa is not None:
+                    piece = paused(src, length, length + params_infer_code.stream_speed, False)
+                elif ts is not None:
                     if not ts:
                         open_streams(src)
                     piece = self._stream_piece_scaled(src, length, length + params_infer_code.stream_speed, ts, False, pcm16,
                                                       encoding if pcm16 else None, **rkw_s, **dkw, **limited(src))
                 else:
                     piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw, **dkw, **limited(src))
-                if fs is not None:
+                if fs is not None and pa is None:
                     piece = flac_chunks(piece, False)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
                 # that is BELOW `a`: `length` and `pass_batch_count` are not reset between split batches, so the first yields of a
@@ -1195,6 +1298,11 @@ class Chat:
                 # (the decode width of a T-token prefix is 256 (2 T - 1) samples on both decode paths; never negative for an empty yield)
                 length = min(length + params_infer_code.stream_speed, max(0, 256 * (2 * max(int(r.size(0)) for r in src) - 1)))
                 yield piece
+            if stream and last is not None and pa is not None:      # rows of different lengths: filtered and converted row by row
+                tail = paused(last.hiddens, length, None, True)
+                last.destroy()
+                yield tail
+                continue
             if stream and last is not None:
                 skw = {"rate": sample_rate} if sample_rate is not None else {}
                 if ts is not None:

@@ -2266,6 +2266,85 @@ extern "C" int ctts_trim_pauses_ragged(const float* in, float* out, const int64_
                                (long long*)off_out, records, scratch, (hipStream_t)stream));
   return 0;
 }
+// ---- pause control of streams: the host's arithmetic (pauses.py: stream_need and the step's layout) and every check the launches trust ----
+static_assert(sizeof(ctts_pa_stream) == 96 && sizeof(PaStream) == 96 && offsetof(ctts_pa_stream, list_off) == offsetof(PaStream, list_off) &&
+              offsetof(ctts_pa_stream, slot) == offsetof(PaStream, slot) && offsetof(ctts_pa_stream, fin) == offsetof(PaStream, fin) &&
+              offsetof(ctts_pa_stream, P) == offsetof(PaStream, P) && offsetof(ctts_pa_stream, thr) == offsetof(PaStream, thr) &&
+              offsetof(ctts_pa_stream, n_list) == offsetof(PaStream, n_list) && CTTS_PA_STREAM_FRAMES == PA_SCAP &&
+              CTTS_PA_STREAM_CARRY == PA_SCARRY && CTTS_PA_STREAM_STATE == PA_STATE && CTTS_PA_STREAM_RES == PA_RES, "ctts_pa_stream layout");
+// pauses.stream_need in frames
+static long long pause_stream_need(long long P, long long lead, long long tail, long long pad) {
+  const long long h = (P + 1) / 2, t = P - h, k0 = std::min(h - 1, tail);
+  return std::max(std::max(std::max(1ll, lead + tail) + lead + pad, P + pad - k0), std::max(h, tail) - k0 + t + 1 + pad);
+}
+extern "C" size_t ctts_trim_pauses_stream_scratch_bytes(int64_t frames, int64_t entries) {
+  if (frames < 0 || frames >= (1ll << 31) || entries < 1 || entries >= (1ll << 31)) return 0;
+  return pause_stream_scratch_bytes(frames, entries);
+}
+extern "C" int ctts_trim_pauses_stream_step(const float* x, int64_t n_x, const ctts_pa_stream* st_dev, const ctts_pa_stream* st_host,
+                                            int32_t n_streams, float* y, int64_t n_y, float* carry, int32_t* state, int32_t n_slots,
+                                            const float* fade_dev, int32_t n_fade, int32_t* res, void* scratch, size_t scratch_bytes,
+                                            void* stream) {
+  const char* who = "ctts_trim_pauses_stream_step";
+  if (!st_dev || !st_host || !carry || !state || !fade_dev || !res || !scratch)
+    return fail("%s: a null pointer (both descriptor tables, the carry, the state, the fade table, the results and the scratch are needed)", who);
+  if (n_x < 0 || n_y < 0 || (!x && n_x) || (!y && n_y)) return fail("%s: a null pointer (x or y) with a length other than 0", who);
+  if (n_streams < 1 || n_streams > 1024) return fail("%s: need 1 <= n_streams <= 1024 (got %d)", who, n_streams);
+  if (n_slots < 1) return fail("%s: the state pool has no slot", who);
+  if (((uintptr_t)x & 3) || ((uintptr_t)y & 3) || ((uintptr_t)carry & 3) || ((uintptr_t)state & 3) || ((uintptr_t)fade_dev & 3) || ((uintptr_t)res & 3) ||
+      ((uintptr_t)scratch & 15))
+    return fail("%s: x, y, the carry, the state, the fade table and the results must be 4-byte aligned, the scratch 16-byte", who);
+  if (n_x && n_y && x < y + n_y && y < x + n_x) return fail("%s: y must not overlap x (a stream is never trimmed in place)", who);
+  if (n_fade < 0) return fail("%s: the fade table's length is negative", who);
+  std::vector<char> seen((size_t)n_slots, 0);
+  long long frames = 0, entries = 0, nf_max = 0, list_max = 0;
+  for (int i = 0; i < n_streams; ++i) {
+    const ctts_pa_stream& w = st_host[i];
+    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: pause stream %d: slot %d is outside the pool of %d", who, i, w.slot, n_slots);
+    if (seen[w.slot]) return fail("%s: pause stream %d: slot %d appears twice in one launch", who, i, w.slot);
+    seen[w.slot] = 1;
+    if (w.phase != 0 && w.phase != 1) return fail("%s: pause stream %d: phase %d is neither 0 nor 1", who, i, w.phase);
+    if (w.fin != 0 && w.fin != 1) return fail("%s: pause stream %d: the last-push flag is 0 or 1 (got %d)", who, i, w.fin);
+    if (w.F < PA_FMIN || w.F > PA_FMAX) return fail("%s: pause stream %d: a frame of %d samples (the rate is %d .. %d Hz)", who, i, w.F, 100 * PA_FMIN, 100 * PA_FMAX);
+    if (w.P < 1 || w.P > 1000 || w.pad < 0 || w.pad > 100 || w.lead < 0 || w.lead > 1000 || w.tail < 0 || w.tail > 1000)
+      return fail("%s: pause stream %d: pad 0 .. 100, lead and tail 0 .. 1000, P 1 .. 1000 frames (got %d, %d, %d, %d)", who, i, w.pad, w.lead, w.tail, w.P);
+    if (!(w.thr >= 9e-6f && w.thr <= 1.0f)) return fail("%s: pause stream %d: the threshold is -100 .. 0 dB (got an amplitude of %g)", who, i, (double)w.thr);
+    if (w.fade < 0 || (long long)w.fade + w.F > n_fade)
+      return fail("%s: pause stream %d: its fade table [%d, %d) lies outside the %d floats given", who, i, w.fade, w.fade + w.F, n_fade);
+    const long long need = pause_stream_need(w.P, w.lead, w.tail, w.pad);
+    if (need > PA_SCAP) return fail("%s: pause stream %d: this spec makes a stream hold %lld frames, a slot holds %d", who, i, need, PA_SCAP);
+    if (w.need != need) return fail("%s: pause stream %d: this spec needs %lld frames, got %d", who, i, need, w.need);
+    if (w.n_in < 0 || w.pos < 0 || w.in_off < 0 || w.out_off < 0) return fail("%s: pause stream %d: a negative length, position or offset", who, i);
+    if (w.pos >= (1ll << 31) || w.n_in >= (1ll << 31) || w.pos + w.n_in >= (1ll << 31))
+      return fail("%s: pause stream %d would hold 2^31 samples or more", who, i);
+    if (w.in_off + w.n_in > n_x) return fail("%s: pause stream %d: the push lies outside the input (%lld floats)", who, i, (long long)n_x);
+    const long long avail = w.pos % w.F + w.n_in, nf = avail / w.F + (w.fin && avail % w.F ? 1 : 0), room = need * w.F + avail;
+    if (room >= (1ll << 31)) return fail("%s: pause stream %d: the chunk could hold 2^31 samples or more", who, i);
+    if (w.out_off + room > n_y)
+      return fail("%s: pause stream %d: the chunk's room (%lld floats: what may wait and what arrives) lies outside the output (%lld floats)", who, i, room, (long long)n_y);
+    const long long nl = 2 * need + nf + 1;
+    if (w.fr_off != frames || w.list_off != entries || w.n_list != nl)
+      return fail("%s: pause stream %d: its new frames start at %lld and its copy list is [%lld, +%lld), got %lld and [%lld, +%d)", who, i, frames, entries, nl,
+                  (long long)w.fr_off, (long long)w.list_off, w.n_list);
+    frames += nf;
+    entries += nl;
+    nf_max = std::max(nf_max, nf);
+    list_max = std::max(list_max, nl);
+  }
+  if (frames >= (1ll << 31) || entries >= (1ll << 31)) return fail("%s: 2^31 frames or copy-list entries in one step", who);
+  for (int i = 0; i < n_streams; ++i)                             // chunks may not share room: a step's output length is known only on the device
+    for (int k = 0; k < i; ++k) {
+      const ctts_pa_stream &a = st_host[i], &b = st_host[k];
+      const long long ra = (long long)a.need * a.F + a.pos % a.F + a.n_in, rb = (long long)b.need * b.F + b.pos % b.F + b.n_in;
+      if (a.out_off < b.out_off + rb && b.out_off < a.out_off + ra) return fail("%s: pause streams %d and %d: the chunks' rooms overlap", who, k, i);
+    }
+  if (scratch_bytes < pause_stream_scratch_bytes(frames, entries))
+    return fail("%s: scratch too small (%zu bytes, need %zu)", who, scratch_bytes, pause_stream_scratch_bytes(frames, entries));
+  CttsDeviceGuard dg(stream);
+  CK(launch_trim_pauses_stream(x, (const PaStream*)st_dev, n_streams, nf_max, list_max, frames, y, carry, state, fade_dev, res, scratch,
+                               (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_copy_bytes(void* dst,const void* src, size_t bytes, void* stream) {
   if (!dst || !src || (bytes & 15) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return fail("ctts_copy_bytes: pointers and size must be 16-byte aligned");
   CttsDeviceGuard dg(stream);

@@ -592,6 +592,36 @@ hipError_t launch_trim_pauses_ragged(const float* x, float* y, const long long* 
                                      long long frames_max, long long frames, const float* fade, long long* off_out, int32_t* records,
                                      void* scratch, hipStream_t st);
 
+// A STREAM of pause control (ctts_trim_pauses_stream_step; the schedule and the held ranges are in chattts_amd/pauses.py)
+#define PA_SCAP 112           // frames a slot's carry holds (pauses.STREAM_FRAMES), besides the partial frame
+#define PA_SCARRY ((PA_SCAP + 1) * PA_FMAX)   // floats of one carry buffer: the held frames, F apart, and at PA_SCAP * PA_FMAX the partial frame; a slot has two
+#define PA_STATE 16           // int32 per slot of the state table: mode (0: no active frame yet), frames seen, pa, the RECORD, 5 reserved
+#define PA_RES 4              // int32 per stream a step reports: samples emitted, frames held behind it, copy-list entries, 0
+// ctts_pa_stream (include/chattts_amd.h), field for field (capi.hip asserts the layout): one push of one stream.  x[in_off, in_off + n_in)
+// are samples [pos, pos + n_in) of the stream; the chunk goes to y[out_off ..] (room for need F + pos % F + n_in samples); fr_off: the
+// stream's first entry in the step's activity bytes, list_off / n_list: its part of the copy list; slot / phase: the state slot and which of
+// its two carry buffers holds the waiting frames (`need` at the most: pauses.stream_need) and the pos % F samples of the partial frame; fin: the
+// push is the stream's last
+struct PaStream {
+  long long in_off, n_in, pos, out_off, fr_off, list_off;
+  int32_t slot, phase, need, fin, F, pad, lead, tail, P;
+  float thr;
+  int32_t fade, n_list;
+};
+// one entry of the copy list: src / mix < PA_SCAP: a frame of the old carry, else PA_SCAP + q: frame q of (partial ++ push); mix < 0: a plain
+// copy; dst >= 0: to the chunk, dst < 0: to float -1 - dst of the new carry
+struct PaCopy {
+  int32_t src, mix, dst, len;
+};
+static inline size_t pause_stream_scratch_bytes(long long frames, long long entries) {
+  return pause_r16((size_t)frames) + (size_t)entries * sizeof(PaCopy);
+}
+// descriptors 0 .. n_streams-1; nf_max: the most new frames of a stream, list_max: the longest copy list (grid sizes); carry
+// [n_slots][2][PA_SCARRY] floats, state [n_slots][PA_STATE] int32, res [n_streams][PA_RES] int32; scratch: the activity bytes of all new
+// frames, then the copy lists.  Three launches: activity, walk (one wave per stream), copy.  Every bound is the caller's to check
+hipError_t launch_trim_pauses_stream(const float* x, const PaStream* tab, int n_streams, long long nf_max, long long list_max, long long frames,
+                                     float* y, float* carry, int32_t* state, const float* fade, int32_t* res, void* scratch, hipStream_t st);
+
 #define TS_CARRY 2560         // floats of one carry buffer of a stream slot; a slot has two (a step reads one and writes the other)
 #define TS_STATE_INTS 4       // int32 per slot of the state table: s_K, three reserved
 // ctts_ts_stream (include/chattts_amd.h), field for field (capi.hip asserts the layout): one push of one stream.  x[in_off, in_off + n_in)

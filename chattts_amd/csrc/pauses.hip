@@ -15,6 +15,17 @@
 //  * pause_copy_k -- a wave per kept frame copies it to out + off_out[s] + dst[j] with the widest access both alignments allow (16, 8 or
 //    4 bytes), or crossfades it with its partner: the fade table w_in[F] comes through LDS (w_out[i] = w_in[F - 1 - i]), products and sum
 //    rounded separately (__fmul_rn / __fadd_rn: no fused multiply-add, so float32 NumPy reproduces it).
+//
+// A STREAM (ctts_trim_pauses_stream_step): the segment arrives in pushes and the kept frames leave as soon as the rules decide them
+// (pauses.py: schedule, state).  A slot's carry holds the frames that wait, two ranges of the current run and a function of (mode, frames
+// seen, pa) alone, and the samples of the incomplete frame; a step reads buffer `phase` and writes the other.  Three launches:
+//  * pause_stream_act_k  -- a wave per newly completed frame of (partial ++ push): one wave-wide reduction of !(|x| < thr) per frame.
+//  * pause_stream_walk_k -- a wave per stream walks its new frames in order, 64 activity bits per ballot, every lane holding the same few
+//    integers of state; what a frame decides goes to the stream's copy list, ranges of frames written by the lanes side by side.  Behind
+//    the frames it lists the next carry, writes the slot's state and record, and reports (samples out, frames held, entries).
+//  * pause_stream_copy_k -- a wave per entry of the copy lists, grid-wide: a frame to the chunk or to the new carry, sample by sample
+//    across the lanes (F = 110, 220 put no frame start on 16 bytes, and a frame may begin in the carry and end in the push), or the
+//    crossfade of two frames by pa_fade.
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -243,6 +254,224 @@ __global__ __launch_bounds__(256) void pause_copy_k(const float* __restrict__ x,
       for (int i = l; i < len; i += 64) y[yi + i] = x[xi + i];
     }
   }
+}
+
+// ---- streams --------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(PaStream) == 96 && sizeof(PaCopy) == 16 && PA_STATE >= 3 + PA_REC, "pause stream tables");
+
+struct PaConsts {
+  int P, lead, tail, pad, h, t, k0, A1, A2, H, L;
+};
+__device__ __forceinline__ PaConsts pa_consts(const PaStream& D) {
+  PaConsts c;
+  c.P = D.P; c.lead = D.lead; c.tail = D.tail; c.pad = D.pad;
+  c.h = (c.P + 1) >> 1; c.t = c.P - c.h; c.k0 = min(c.h - 1, c.tail);
+  c.A1 = max(1, c.lead + c.tail); c.A2 = c.lead + c.pad; c.H = max(c.h, c.tail); c.L = c.t + 1 + c.pad;
+  return c;
+}
+// pauses.stream_held: the run starts at frame r0; its frames k in [lo, a) and [b, m) wait, in this order
+struct PaHeld {
+  int r0, lo, a, b, m;
+};
+__device__ __forceinline__ PaHeld pa_held(const PaConsts& c, int mode, int nfr, int pa) {
+  PaHeld o;
+  if (mode == 0) {
+    o.r0 = 0; o.lo = 0; o.m = nfr; o.a = min(o.m, c.A1); o.b = max(o.a, o.m - c.A2);
+    return o;
+  }
+  o.r0 = pa + c.pad + 1; o.lo = c.k0; o.m = max(nfr - o.r0, c.k0);
+  if (o.m - c.pad <= c.P) { o.a = o.m; o.b = o.m; }
+  else { o.a = min(o.m, c.H); o.b = max(o.a, o.m - c.L); }
+  return o;
+}
+// sample i of the frame a copy-list code names: a frame of the old carry, or frame q of (partial ++ push)
+struct PaSrc {
+  const float* cold;   // the slot's old carry buffer
+  const float* xin;    // the push
+  int F, pn;           // pn: samples of the partial frame in the old carry
+};
+__device__ __forceinline__ float pa_read(const PaSrc& S, int code, int i) {
+  if (code < PA_SCAP) return S.cold[code * S.F + i];
+  const long long p = (long long)(code - PA_SCAP) * S.F + i;
+  return p < S.pn ? S.cold[PA_SCAP * PA_FMAX + p] : S.xin[p - S.pn];
+}
+
+__global__ __launch_bounds__(256) void pause_stream_act_k(const float* __restrict__ x, const PaStream* __restrict__ tab,
+                                                          const float* __restrict__ carry, uint8_t* __restrict__ act) {
+  const PaStream& D = tab[blockIdx.y];
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, F = D.F, pn = (int)(D.pos % F);
+  const long long avail = pn + D.n_in, nf = avail / F + (D.fin && avail % F ? 1 : 0), q = (long long)blockIdx.x * 4 + w;
+  if (q >= nf) return;                                            // the whole wave
+  const float* part = carry + ((long long)D.slot * 2 + D.phase) * PA_SCARRY + PA_SCAP * PA_FMAX;
+  const float* xin = x + D.in_off;
+  const long long a = q * F, b = min(avail, a + F);
+  const float thr = D.thr;
+  int hit = 0;
+  for (long long p = a + l; p < b; p += 64) {
+    const float v = p < pn ? part[p] : xin[p - pn];
+    hit |= !(fabsf(v) < thr);
+  }
+  hit = __any(hit);
+  if (l == 0) act[D.fr_off + q] = (uint8_t)(hit != 0);
+}
+
+__global__ __launch_bounds__(64) void pause_stream_walk_k(const PaStream* __restrict__ tab, const uint8_t* __restrict__ act,
+                                                          int32_t* __restrict__ state, PaCopy* __restrict__ list, int32_t* __restrict__ res) {
+  const PaStream& D = tab[blockIdx.x];
+  const int l = threadIdx.x, F = D.F, pn = (int)(D.pos % F);
+  const PaConsts c = pa_consts(D);
+  const long long avail = pn + D.n_in;
+  const int nfull = (int)(avail / F), plen = (int)(avail - (long long)nfull * F), nf = nfull + (D.fin && plen ? 1 : 0);
+  int32_t* st = state + (long long)D.slot * PA_STATE;
+  int mode = 0, nfr = 0, pa = 0, rec[PA_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (D.pos != 0) {                                               // at pos == 0 the slot is fresh by its descriptor alone
+    mode = st[0]; nfr = st[1]; pa = st[2];
+#pragma unroll
+    for (int i = 0; i < PA_REC; ++i) rec[i] = st[3 + i];
+  }
+  const PaHeld o = pa_held(c, mode, nfr, pa);
+  const int nfr0 = nfr, jpart = D.fin && plen ? nfr0 + nfull : -1;
+  auto src = [&](int j) {
+    if (j >= nfr0) return PA_SCAP + (j - nfr0);
+    const int k = j - o.r0;
+    return k < o.a ? k - o.lo : (o.a - o.lo) + (k - o.b);
+  };
+  PaCopy* L = list + D.list_off;
+  int ne = 0, n_out = 0;
+  auto emit = [&](int j0, int j1) {                               // frames [j0, j1), copied: an entry per lane
+    const int cnt = j1 - j0;
+    if (cnt <= 0) return;
+    for (int i = l; i < cnt; i += 64) {
+      PaCopy e;
+      e.src = src(j0 + i); e.mix = -1; e.dst = n_out + i * F; e.len = j0 + i == jpart ? plen : F;
+      L[ne + i] = e;
+    }
+    n_out += cnt * F - (jpart >= j0 && jpart < j1 ? F - plen : 0);
+    ne += cnt;
+  };
+  const uint8_t* A = act + D.fr_off;
+  for (int base = 0; base < nf; base += 64) {
+    const unsigned long long bits = __ballot(base + l < nf && A[base + l] != 0);
+    const int top = min(64, nf - base);
+    for (int q = 0; q < top; ++q) {
+      const int j = nfr++;
+      if ((bits >> q) & 1ull) {
+        ++rec[1];
+        if (mode == 0) {
+          const int first = max(0, j - c.pad - c.lead);
+          emit(first, j);
+          rec[3] += first;
+          rec[2] += min(j, c.pad) + 1;
+          mode = 1;
+        } else {
+          const int r0 = pa + c.pad + 1, m = j - r0, R = m - c.pad;
+          rec[2] += min(j - pa - 1, 2 * c.pad) + 1;
+          if (R <= c.P) {
+            emit(r0 + c.k0, r0 + m);
+          } else {
+            emit(r0 + c.k0, r0 + c.h - 1);
+            if (l == 0) {                                         // both frames are full: they lie in front of an active frame
+              PaCopy e;
+              e.src = src(r0 + c.h - 1); e.mix = src(r0 + R - c.t - 1); e.dst = n_out; e.len = F;
+              L[ne] = e;
+            }
+            ++ne;
+            n_out += F;
+            emit(r0 + R - c.t, r0 + m);
+            ++rec[5];
+            rec[6] += R - c.P;
+          }
+        }
+        emit(j, j + 1);
+        pa = j;
+      } else if (mode == 1 && (j - pa <= c.pad || j - pa - c.pad - 1 < c.k0)) {
+        emit(j, j + 1);
+      }
+    }
+  }
+  int held = 0;
+  if (D.fin) {
+    if (mode == 0) {
+      const int keep = min(nfr, c.A1);
+      emit(0, keep);
+      rec[4] += nfr - keep;
+    } else {
+      const int r0 = pa + c.pad + 1, R = nfr - r0;
+      rec[2] += min(nfr - 1 - pa, c.pad);
+      if (R > 0) {
+        emit(r0 + c.k0, r0 + min(c.tail, R));
+        rec[4] += max(0, R - c.tail);
+      }
+    }
+    rec[0] = nfr;
+  } else {                                                        // the next carry: the frames that wait, then the partial frame
+    const PaHeld n = pa_held(c, mode, nfr, pa);
+    const int n1 = n.a - n.lo;
+    held = n1 + (n.m - n.b);
+    for (int i = l; i < held; i += 64) {
+      PaCopy e;
+      e.src = src(n.r0 + (i < n1 ? n.lo + i : n.b + (i - n1))); e.mix = -1; e.dst = -1 - i * F; e.len = F;
+      L[ne + i] = e;
+    }
+    ne += held;
+    if (plen) {
+      if (l == 0) {
+        PaCopy e;
+        e.src = PA_SCAP + nfull; e.mix = -1; e.dst = -1 - PA_SCAP * PA_FMAX; e.len = plen;
+        L[ne] = e;
+      }
+      ++ne;
+    }
+  }
+  rec[7] += n_out;
+  if (l == 0) {
+    st[0] = mode; st[1] = nfr; st[2] = pa;
+#pragma unroll
+    for (int i = 0; i < PA_REC; ++i) st[3 + i] = rec[i];
+    int32_t* r = res + (long long)blockIdx.x * PA_RES;
+    r[0] = n_out; r[1] = held; r[2] = ne; r[3] = 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void pause_stream_copy_k(const float* __restrict__ x, const PaStream* __restrict__ tab,
+                                                           const PaCopy* __restrict__ list, const int32_t* __restrict__ res,
+                                                           float* __restrict__ y, float* carry, const float* __restrict__ fade) {
+  const PaStream& D = tab[blockIdx.y];
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const long long e = (long long)blockIdx.x * 4 + w;
+  if (e >= res[(long long)blockIdx.y * PA_RES + 2]) return;       // the whole wave
+  const PaCopy cp = list[D.list_off + e];
+  PaSrc S;
+  S.F = D.F; S.pn = (int)(D.pos % D.F);
+  S.cold = carry + ((long long)D.slot * 2 + D.phase) * PA_SCARRY;
+  S.xin = x + D.in_off;
+  float* dst = cp.dst >= 0 ? y + D.out_off + cp.dst : carry + ((long long)D.slot * 2 + (D.phase ^ 1)) * PA_SCARRY + (-1 - cp.dst);
+  if (cp.mix >= 0) {
+    const float* win = fade + D.fade;
+    for (int i = l; i < S.F; i += 64) dst[i] = pa_fade(win[S.F - 1 - i], pa_read(S, cp.src, i), win[i], pa_read(S, cp.mix, i));
+  } else {
+    for (int i = l; i < cp.len; i += 64) dst[i] = pa_read(S, cp.src, i);
+  }
+}
+
+hipError_t launch_trim_pauses_stream(const float* x, const PaStream* tab, int n_streams, long long nf_max, long long list_max, long long frames,
+                                     float* y, float* carry, int32_t* state, const float* fade, int32_t* res, void* scratch, hipStream_t st) {
+  if (n_streams <= 0) return hipSuccess;
+  uint8_t* act = (uint8_t*)scratch;
+  PaCopy* list = (PaCopy*)((char*)scratch + pause_r16((size_t)frames));
+  hipError_t e;
+  if (nf_max > 0) {
+    hipLaunchKernelGGL(pause_stream_act_k, dim3((unsigned)((nf_max + 3) / 4), (unsigned)n_streams), dim3(256), 0, st, x, tab, (const float*)carry, act);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(pause_stream_walk_k, dim3((unsigned)n_streams), dim3(64), 0, st, tab, (const uint8_t*)act, state, list, res);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (list_max > 0)
+    hipLaunchKernelGGL(pause_stream_copy_k, dim3((unsigned)((list_max + 3) / 4), (unsigned)n_streams), dim3(256), 0, st, x, tab,
+                       (const PaCopy*)list, (const int32_t*)res, y, carry, fade);
+  return hipGetLastError();
 }
 
 hipError_t launch_trim_pauses_ragged(const float* x, float* y, const long long* off, const long long* fbase, const int32_t* rows, int n_seg,

@@ -2220,6 +2220,140 @@ class CodecEngine:
             out = (*out, res[8 * (n_seg + 1):].view(np.int32).reshape(n_seg, PA.REC).copy())
         return out[0] if len(out) == 1 else out
 
+    # -- pause control of streams: per-stream device state (csrc/pauses.hip, pause_stream_walk_k) -----------------------------------------
+    PA_STREAM_SLOTS = 16      # the state pool's first size; it doubles when every slot is taken
+
+    def _pa_pool(self) -> dict:
+        """the state pool: carry [slots, 2, (PA.STREAM_FRAMES + 1) * 480] float32 and state [slots, PA.STATE] int32 on the device, the
+        free list, and per open stream its host record [rate, spec, samples pushed, carry phase, done, frames held, samples emitted]"""
+        pool = self.__dict__.get("_pa_streams")
+        if pool is None:
+            n = int(self.PA_STREAM_SLOTS)
+            pool = self._pa_streams = dict(carry=torch.zeros((n, 2, (PA.STREAM_FRAMES + 1) * 480), dtype=torch.float32, device=self.device),
+                                           state=torch.zeros((n, PA.STATE), dtype=torch.int32, device=self.device),
+                                           free=list(range(n - 1, -1, -1)), rec={})
+        return pool
+
+    def trim_pauses_stream_open(self, rate: int, spec=True) -> int:
+        """A pause stream at `rate` Hz with `spec` (True: the defaults, a `pauses.PauseSpec` or a dict of its fields): -> its handle, a
+        slot of the engine's state pool.  The slot is fresh by construction -- the step that carries a stream's first sample reads
+        neither state nor carry -- so nothing is cleared here.  ValueError: a bad rate or spec, no spec, a spec that makes a stream
+        hold more than `pauses.STREAM_FRAMES` frames."""
+        rate, spec = PA.check_stream(rate, spec)
+        pool = self._pa_pool()
+        if not pool["free"]:
+            n = int(pool["carry"].shape[0])
+            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
+            pool["state"] = torch.cat([pool["state"], torch.zeros_like(pool["state"])])
+            pool["free"] = list(range(2 * n - 1, n - 1, -1))
+        slot = pool["free"].pop()
+        pool["rec"][slot] = [rate, spec, 0, 0, False, 0, 0]
+        return slot
+
+    def trim_pauses_stream_close(self, handle: int) -> None:
+        """gives the stream's slot back (any time: finished, or abandoned half way)"""
+        pool = self._pa_pool()
+        if pool["rec"].pop(int(handle), None) is None:
+            raise ValueError(f"pauses: stream {handle} is not open")
+        pool["free"].append(int(handle))
+
+    def trim_pauses_streams_in_use(self) -> int:
+        """the streams that are open: slots of the state pool not on its free list"""
+        return len(self._pa_pool()["rec"])
+
+    def trim_pauses_stream_stats(self, handle: int) -> dict:
+        """the stream so far: `record` (int32 [8], `pauses.RECORD`, a device read that waits for the steps so far; after the last push
+        it is `trim_pauses`' record of the whole signal, all zero for a stream that ended empty), `pushed` and `emitted` samples,
+        `held` frames that wait, `done`"""
+        pool = self._pa_pool()
+        rec = pool["rec"].get(int(handle))
+        if rec is None:
+            raise ValueError(f"pauses: stream {handle} is not open")
+        record = np.zeros(PA.REC, dtype=np.int32) if rec[2] == 0 else pool["state"][int(handle), 3: 3 + PA.REC].cpu().numpy()
+        return dict(record=record, pushed=rec[2], emitted=rec[6], held=rec[5], done=rec[4])
+
+    def _pa_descriptors(self, pushes):
+        """pushes [(handle, in_off, n_in, final)], one per stream -> (PA_STREAM table, the distinct frames' fade tables one behind the
+        other, commit: handle -> [samples pushed, carry phase, done] behind the step).  All in Python integers and before anything is
+        launched; the records change only when the caller commits.  A stream's chunk gets room for what may wait and what arrives."""
+        recs = self._pa_pool()["rec"]
+        tab = np.zeros(len(pushes), _lib.PA_STREAM)
+        commit, fade_off, parts = {}, {}, []
+        out = fr = ls = 0
+        for i, (h, in_off, n_in, final) in enumerate(pushes):
+            h, in_off, n_in = int(h), int(in_off), int(n_in)
+            if h not in recs:
+                raise ValueError(f"pauses: stream {h} is not open")
+            if h in commit:
+                raise ValueError("pauses: a stream appears twice in one step")
+            rate, spec, pushed, phase, done = recs[h][:5]
+            if done:
+                raise ValueError(f"pauses: stream {h} has had its last push")
+            if n_in < 0 or in_off < 0:
+                raise ValueError("pauses: a push cannot be negative")
+            if pushed + n_in >= 1 << 31:
+                raise ValueError("pauses: the stream would hold 2^31 samples or more")
+            F, pad, lead, tail, P, thr = PA.stream_row(rate, spec)
+            if F not in fade_off:
+                fade_off[F] = sum(len(p) for p in parts)
+                parts.append(PA.fade_table(F))
+            need, avail = PA.stream_need(spec), pushed % F + n_in
+            nf = avail // F + (1 if final and avail % F else 0)
+            n_list = 2 * need + nf + 1
+            tab[i] = (in_off, n_in, pushed, out, fr, ls, h, phase, need, int(bool(final)), F, pad, lead, tail, P, thr, fade_off[F], n_list)
+            out, fr, ls = out + need * F + avail, fr + nf, ls + n_list
+            commit[h] = [pushed + n_in, phase ^ 1, bool(final)]
+        if out >= 1 << 31:
+            raise ValueError("pauses: the output would hold 2^31 samples or more")
+        return tab, np.ascontiguousarray(np.concatenate(parts)), commit
+
+    def trim_pauses_stream_step(self, x: torch.Tensor, pushes):
+        """ONE step of many pause streams (ctts_trim_pauses_stream_step: three launches whatever their number, rates and specs): `x`, a
+        1-D float32 device tensor, holds the new samples of every stream; `pushes` = [(handle, in_off, n_in, final)]: x[in_off, in_off
+        + n_in) continue stream `handle` (n_in 0: nothing new), `final`: they are its last.  -> (y, off): stream i's chunk is
+        y[off[i], off[i+1]) (possibly empty), a tensor of its own -- x is never written.  The chunks of a stream, concatenated, are
+        `trim_pauses` of its concatenated pushes bit for bit, however they were cut (`pauses.py`: what a push emits, and the lags).
+        A chunk's length depends on the samples: the step ends in ONE device-to-host copy of the streams' counts, its only
+        synchronisation.  A handle may appear once per call.  Every refusal (ValueError here, EngineError from the library) comes
+        before the first launch and leaves all streams as they were."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+            raise ValueError("pauses: a contiguous 1-D float32 device tensor")
+        if len(pushes) < 1:
+            raise ValueError("pauses: nothing to step")
+        if len(pushes) > 1024:
+            raise ValueError("pauses: at most 1024 streams in one step")
+        for _, in_off, n_in, _ in pushes:
+            if int(in_off) < 0 or int(n_in) < 0 or int(in_off) + int(n_in) > x.numel():
+                raise ValueError("pauses: a push lies outside the tensor")
+        tab, fade, commit = self._pa_descriptors(pushes)
+        n, dev = len(tab), x.device
+        room = int(tab["out_off"][-1]) + int(tab["need"][-1]) * int(tab["F"][-1]) + int(tab["pos"][-1]) % int(tab["F"][-1]) + int(tab["n_in"][-1])
+        frames, entries = int(tab["fr_off"][-1]) + int(tab["n_list"][-1]) - 2 * int(tab["need"][-1]) - 1, int(tab["list_off"][-1]) + int(tab["n_list"][-1])
+        y = torch.empty((room,), dtype=torch.float32, device=dev)
+        up = torch.from_numpy(np.concatenate([tab.view(np.uint8), fade.view(np.uint8)])).to(dev)              # one upload
+        scratch = int(self.lib.ctts_trim_pauses_stream_scratch_bytes(frames, entries))
+        res_bytes = -(-4 * 4 * n // 16) * 16
+        work = torch.empty((res_bytes + scratch,), dtype=torch.uint8, device=dev)
+        pool = self._pa_pool()
+        st = torch.cuda.current_stream(dev)
+        _lib.check(self.lib.ctts_trim_pauses_stream_step(
+            x.data_ptr() if x.numel() else None, x.numel(), up.data_ptr(), tab.ctypes.data_as(C.c_void_p), n, y.data_ptr() if room else None, room,
+            pool["carry"].data_ptr(), pool["state"].data_ptr(), int(pool["carry"].shape[0]), up.data_ptr() + tab.nbytes, int(fade.size),
+            work.data_ptr(), work.data_ptr() + res_bytes, scratch, st.cuda_stream), "ctts_trim_pauses_stream_step")
+        up.record_stream(st)
+        work.record_stream(st)
+        x.record_stream(st)
+        res = work[: 16 * n].cpu().numpy().view(np.int32).reshape(n, 4)                                       # the one copy, and the one wait
+        for i, (h, _, _, _) in enumerate(pushes):
+            rec = pool["rec"][int(h)]
+            rec[2:5] = commit[int(h)]
+            rec[5], rec[6] = int(res[i, 1]), rec[6] + int(res[i, 0])
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(res[:, 0], out=off[1:])
+        if n == 1:
+            return y[: int(off[1])], off
+        return torch.cat([y[int(tab["out_off"][i]): int(tab["out_off"][i]) + int(res[i, 0])] for i in range(n)]), off
+
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
     def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None,
                       limiter=None):
@@ -2437,7 +2571,7 @@ class CodecEngine:
 
     def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
                        sample_rates=None, encodings=None, speeds=None, ts_streams=None, rs_streams=None, flac=None, flac_streams=None,
-                       limiter=None, lm_streams=None):
+                       limiter=None, lm_streams=None, pauses=None, pa_streams=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -2493,7 +2627,34 @@ class CodecEngine:
         where some are at another speed and some are not), one limiter step per round -- several windows of one stream go to
         successive rounds, in the order given --, ONE ctts_float_to_int16_ragged launch, and the epilogue of every other path (one
         copy).  A flagged window whose crop is empty still steps its stream.  Unflagged windows return the bytes they return
-        without `limiter`."""
+        without `limiter`.
+        `pauses` (None, or all None / False: the call above, argument for argument, with no extra copy) with `pa_streams`: one flag
+        and one entry per window, the handle of the pause stream (`trim_pauses_stream_open`, at the window's output rate; the stream
+        holds the spec) a flagged window continues.  A flagged window PUSHES its float32 samples -- behind the same float stages as
+        the limiter's -- into its pause stream and goes on with what that step emits (`trim_pauses_stream_step`; a window marked
+        `tail` is the stream's last push): in front of the limiter stream, the conversion (one peak per window over the samples that
+        come out), a tail's strip (`keep_thr` acts on what the last push emits), G.711 and the FLAC push, the non-streamed order.
+        One pause step per round, each with its one small copy of the counts; the chunks then start on multiples of 8 samples again,
+        as the FLAC step needs them."""
+        pa = None
+        if pauses is not None and any(f is not None and f is not False for f in pauses):
+            if len(pauses) != len(windows) or pa_streams is None or len(pa_streams) != len(windows):
+                raise ValueError("decode_windows: one pauses flag and one pa_streams entry per window")
+            pa_recs, ended = self._pa_pool()["rec"], set()
+            for i, (f, h) in enumerate(zip(pauses, pa_streams)):
+                if f is not None and f is not False:
+                    want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
+                    if h is None or int(h) not in pa_recs or pa_recs[int(h)][0] != want:
+                        raise ValueError(f"decode_windows: window {i} needs an open pause stream at {want} Hz")
+                    if pa_recs[int(h)][4] or int(h) in ended:
+                        raise ValueError(f"decode_windows: window {i}: pause stream {int(h)} has had its last push")
+                    if len(windows[i]) > 4 and bool(windows[i][4]):
+                        ended.add(int(h))
+                elif h is not None:
+                    raise ValueError(f"decode_windows: window {i} has no pauses flag but names a pause stream")
+            pa = [int(h) if (f is not None and f is not False) else None for f, h in zip(pauses, pa_streams)]
+        elif pa_streams is not None and any(h is not None for h in pa_streams):
+            raise ValueError("decode_windows: pa_streams without a pauses flag")
         lm = None
         if limiter is not None and any(bool(f) for f in limiter):
             if len(limiter) != len(windows) or lm_streams is None or len(lm_streams) != len(windows):
@@ -2551,10 +2712,10 @@ class CodecEngine:
                 if not pcm16:
                     raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
                 laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
-        if lm is not None:
-            return self._decode_windows_limited(store, windows, lm, q, laws, fl, pcm16, keep_thr, product, dict(
-                sample_rates=sample_rates, encodings=encodings, speeds=speeds, ts_streams=ts_streams, rs_streams=rs_streams, flac=flac,
-                flac_streams=flac_streams))
+        if lm is not None or pa is not None:
+            return self._decode_windows_limited(store, windows, [None] * len(windows) if lm is None else lm, q, laws, fl, pcm16, keep_thr, product,
+                                                dict(sample_rates=sample_rates, encodings=encodings, speeds=speeds, ts_streams=ts_streams,
+                                                     rs_streams=rs_streams, flac=flac, flac_streams=flac_streams), pa)
         if q is not None:
             rates = None
             if sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
@@ -2666,12 +2827,14 @@ class CodecEngine:
                                      np.int16 if pcm16 else np.float32, out, fl)
 
     def _decode_windows_limited(self, store: torch.Tensor, windows, lm, q, laws, fl, pcm16: bool, keep_thr: Optional[float], product: str,
-                                per_window: dict) -> list:
-        """`decode_windows` with at least one window behind a limiter stream (lm: the windows' handles or None; q, laws, fl: the
-        call's checked speeds, laws and FLAC streams; per_window: its per-window arguments, to be cut for the passes)"""
+                                per_window: dict, pa=None) -> list:
+        """`decode_windows` with at least one window behind a limiter stream or a pause stream (lm, pa: the windows' handles or
+        None; q, laws, fl: the call's checked speeds, laws and FLAC streams; per_window: its per-window arguments, to be cut for the
+        passes)"""
         pick = lambda v, ix: None if v is None else [v[i] for i in ix]
-        idx = [i for i, h in enumerate(lm) if h is not None]
-        rest = [i for i, h in enumerate(lm) if h is None]
+        pa = [None] * len(windows) if pa is None else pa
+        idx = [i for i in range(len(windows)) if lm[i] is not None or pa[i] is not None]
+        rest = [i for i in range(len(windows)) if lm[i] is None and pa[i] is None]
         out: list = [None] * len(windows)
         if rest:                                                   # the unflagged windows: the call without the limiter
             for i, a in zip(rest, self.decode_windows(store, pick(windows, rest), pcm16, keep_thr, product,
@@ -2699,11 +2862,31 @@ class CodecEngine:
         finally:
             del self._lm_sink
         x = torch.cat(bufs) if len(bufs) > 1 else bufs[0] if bufs else torch.zeros((8,), dtype=torch.float32, device=self.device)
+        tails = [len(windows[i]) > 4 and bool(windows[i][4]) for i in idx]
+        # the pause streams' steps, in front of the limiter's: the r-th window of a stream in round r; what a step emits lies behind x
+        seen, prounds = {}, []
+        for k, i in enumerate(idx):
+            if pa[i] is not None:
+                r = seen[pa[i]] = seen.get(pa[i], -1) + 1
+                if r == len(prounds):
+                    prounds.append([])
+                prounds[r].append(k)
+        if prounds:
+            parts, base = [x], x.numel()
+            for rnd in prounds:
+                y, o = self.trim_pauses_stream_step(x, [(pa[idx[k]], *src.get(idx[k], (0, 0)), tails[k]) for k in rnd])
+                for j, k in enumerate(rnd):
+                    src[idx[k]] = (base + int(o[j]), int(o[j + 1] - o[j]))
+                parts.append(y)
+                base += y.numel()
+            x = torch.cat(parts)
         # the limiter's steps: the r-th window of a stream in round r; the limited chunks start on multiples of 8 samples, zeros between
         recs, shadow, rounds = self._lm_pool()["rec"], {}, []
-        tails = [len(windows[i]) > 4 and bool(windows[i][4]) for i in idx]
         n = np.zeros(len(idx), np.int64)
         for k, i in enumerate(idx):
+            if lm[i] is None:                                      # paused only: the chunk goes on as it came out
+                n[k] = src.get(i, (0, 0))[1]
+                continue
             pushed, emitted, r = shadow.get(lm[i], (recs[lm[i]][2], recs[lm[i]][3], 0))
             p = LM.stream_plan(recs[lm[i]][0] // 100, pushed, emitted, src.get(i, (0, 0))[1], tails[k])
             n[k] = p["n_out"]
@@ -2717,6 +2900,9 @@ class CodecEngine:
         lim = torch.zeros((max(8, int(off[-1])),), dtype=torch.float32, device=self.device)
         for rnd in rounds:
             self.peak_limit_stream_step(x, [(lm[idx[k]], *src.get(idx[k], (0, 0)), tails[k]) for k in rnd], out=lim, out_off=[int(off[k]) for k in rnd])
+        for k, i in enumerate(idx):
+            if lm[i] is None and n[k]:
+                lim[int(off[k]): int(off[k]) + int(n[k])] = x[src[i][0]: src[i][0] + int(n[k])]
         live = [k for k in range(len(idx)) if n[k] > 0]
         for k in range(len(idx)):
             if n[k] == 0:

@@ -18,7 +18,29 @@ nothing here touches the GPU).  The definition, once, for a segment of n >= 1 fl
   record     RECORD, eight int32: frames, active frames, speech frames, lead frames removed, tail frames removed, inner runs shortened,
              inner frames removed, output samples.  A segment that is copied through (spec None) reports (frames, 0, 0, 0, 0, 0, 0, n).
 
-`apply` is the NumPy twin of the kernels, vectorised from these formulas; `tables` builds what ctts_trim_pauses_ragged takes."""
+`apply` is the NumPy twin of the kernels, vectorised from these formulas; `tables` builds what ctts_trim_pauses_ragged takes.
+
+A STREAM (`StreamPauses`, `stream_walk`, ctts_trim_pauses_stream_step) is opened with a rate fs and a checked spec; samples arrive in pushes
+of any size, 0 included, and the last push is marked final.  With X the concatenation of the pushes and n its length:
+
+  result     for n >= 1 the chunks the pushes emit, end to end, are apply(X, fs, spec)[0] bit for bit, however X was cut, and after the
+             final push the stream's record is apply's RECORD.  A stream closed with n = 0 emits nothing and reports an all-zero record.
+  schedule   a non-final push considers complete frames only (a partial frame waits: at most F - 1 samples) and emits frames in order up
+             to the first that is not decided.  With pa the last active frame <= j among the frames seen:  (1) an active frame decides
+             every frame up to itself by the rules above -- a leading run or an inner run, crossfade included;  (2) before the first
+             active frame nothing is decided (a leading run, or no active frame at all);  (3) j - pa <= pad: speech, emitted as it is;
+             (4) else, with k = j - (pa + pad + 1) and k0 = min(h - 1, tail): k < k0 is emitted as it is -- it is kept unmixed whether the
+             run turns out short, long or trailing, or speech resumes within pad -- and k >= k0 waits for an active frame or the end.
+             The final push decides what is left, the last and possibly partial frame included.
+  lags       through speech less than one frame (10 ms); inside a pause the first k0 frames of the run go out (100 ms with the defaults,
+             behind the 30 ms of pad) and then nothing until speech resumes or the stream ends; nothing before the first active frame.
+  state      what waits is two ranges of the current run's frames, a function of the run's length m so far (frames k < m seen) alone:
+             before the first active frame  [0, min(m, A1)) and [max(A1, m - A2), m),  A1 = max(1, lead + tail), A2 = lead + pad;  behind
+             speech  [k0, m) while m - pad <= P (the run may still be short), afterwards  [k0, min(m, H)) and [max(H, m - L), m),
+             H = max(h, tail), L = t + 1 + pad  (the frames a long or trailing run keeps at its front; the crossfade partner, the kept
+             tail and the pad at its back).  `stream_need` is the most frames that ever wait, max(A1 + A2, P + pad - k0, H - k0 + L):
+             it depends on the spec, not on how long a pause lasts.  A device slot holds STREAM_FRAMES frames and a partial one; a spec
+             that needs more is refused when the stream is opened."""
 from __future__ import annotations
 
 import math
@@ -224,3 +246,167 @@ def trim(x: np.ndarray, spec, offsets=None, rates=None):
     off_out = np.zeros(len(off), dtype=np.int64)
     np.cumsum([len(y) for y, _ in out], out=off_out[1:])
     return np.concatenate([y for y, _ in out]), off_out, np.stack([r for _, r in out])
+
+
+# ---- streams ----------------------------------------------------------------------------------------------------------------------------
+STREAM_FRAMES = 112                              # frames a device slot holds (csrc/kernels.hpp PA_SCAP), besides the partial frame
+STATE = 16                                       # int32 per slot of the device state (PA_STATE): mode, frames seen, pa, RECORD, 5 reserved
+
+
+def stream_consts(spec: PauseSpec) -> dict:
+    """the frame counts a stream works with: P, lead, tail, pad, h, t, k0, A1, A2, H, L (the module's docstring)"""
+    P, lead, tail, pad = spec.frames()
+    h = -(-P // 2)
+    t = P - h
+    return dict(P=P, lead=lead, tail=tail, pad=pad, h=h, t=t, k0=min(h - 1, tail), A1=max(1, lead + tail), A2=lead + pad, H=max(h, tail),
+                L=t + 1 + pad)
+
+
+def stream_need(spec) -> int:
+    """the most frames a stream with this spec ever holds between two pushes (the partial frame not counted)"""
+    c = stream_consts(check(spec) or PauseSpec())
+    return max(c["A1"] + c["A2"], c["P"] + c["pad"] - c["k0"], c["H"] - c["k0"] + c["L"])
+
+
+def check_stream(fs, spec, who: str = "pauses"):
+    """(fs, spec) of a stream, checked -> (fs, PauseSpec).  ValueError: a bad rate or spec, no spec at all, a spec that needs more
+    frames than a slot holds"""
+    fs = check_rate(fs)
+    spec = check(spec)
+    if spec is None:
+        raise ValueError(f"{who}: a pause stream needs a spec")
+    need = stream_need(spec)
+    if need > STREAM_FRAMES:
+        raise ValueError(f"{who}: this spec makes a stream hold {need} frames, a slot holds {STREAM_FRAMES} "
+                         "(max_pause_ms <= 1000, lead_ms and tail_ms <= 250, pad_ms <= 100 always fit)")
+    return fs, spec
+
+
+def stream_row(fs: int, spec: PauseSpec):
+    """the spec part of a stream's table entry (ctts_pa_stream: F, pad, lead, tail, P, thr)"""
+    P, lead, tail, pad = spec.frames()
+    return fs // 100, pad, lead, tail, P, spec.thr()
+
+
+def stream_held(c: dict, mode: int, nfr: int, pa: int):
+    """the frames that wait when `nfr` frames are seen: (r0, lo, a, b, m) -- the run starts at frame r0, and its frames k in [lo, a) and
+    [b, m) are held, in this order (a stream's carry); mode 0: no active frame yet, 1: the last active frame is pa"""
+    if mode == 0:
+        m = nfr
+        a = min(m, c["A1"])
+        return 0, 0, a, max(a, m - c["A2"]), m
+    r0, k0 = pa + c["pad"] + 1, c["k0"]
+    m = max(nfr - r0, k0)
+    if m - c["pad"] <= c["P"]:
+        return r0, k0, m, m, m
+    a = min(m, c["H"])
+    return r0, k0, a, max(a, m - c["L"]), m
+
+
+def stream_walk(c: dict, state, acts, final: bool):
+    """One push of one stream in integers, the walk of pause_stream_walk_k.  state = (mode, frames seen, pa, record list of 8); acts:
+    the activity of the newly completed frames (on the final push the partial last frame is one of them).  -> (emit, state'): emit a
+    list of (frame, partner or -1) in output order, frames by their absolute index.  n_out of the record is the caller's to add."""
+    mode, nfr, pa, rec = state[0], state[1], state[2], list(state[3])
+    P, lead, tail, pad, h, t, k0 = c["P"], c["lead"], c["tail"], c["pad"], c["h"], c["t"], c["k0"]
+    emit = []
+    for act in acts:
+        j = nfr
+        nfr += 1
+        if act:
+            rec[1] += 1
+            if mode == 0:
+                first = max(0, j - pad - lead)
+                emit.extend((i, -1) for i in range(first, j))
+                rec[3] += first
+                rec[2] += min(j, pad) + 1
+                mode = 1
+            else:
+                r0 = pa + pad + 1
+                m, R = j - r0, j - pad - r0
+                rec[2] += min(j - pa - 1, 2 * pad) + 1
+                if R <= P:
+                    emit.extend((r0 + k, -1) for k in range(k0, m))
+                else:
+                    emit.extend((r0 + k, -1) for k in range(k0, h - 1))
+                    emit.append((r0 + h - 1, r0 + R - t - 1))
+                    emit.extend((r0 + k, -1) for k in range(R - t, m))
+                    rec[5] += 1
+                    rec[6] += R - P
+            emit.append((j, -1))
+            pa = j
+        elif mode == 1 and (j - pa <= pad or j - pa - pad - 1 < k0):
+            emit.append((j, -1))
+    if final:
+        if mode == 0:
+            keep = min(nfr, c["A1"])
+            emit.extend((i, -1) for i in range(keep))
+            rec[4] += nfr - keep
+        else:
+            r0 = pa + pad + 1
+            R = nfr - r0
+            rec[2] += min(nfr - 1 - pa, pad)
+            if R > 0:
+                emit.extend((r0 + k, -1) for k in range(k0, min(tail, R)))
+                rec[4] += max(0, R - tail)
+        rec[0] = nfr
+    return emit, (mode, nfr, pa, rec)
+
+
+class StreamPauses:
+    """the NumPy twin of one pause stream at rate fs: `push(x, final) -> y` float32, `record` the RECORD so far (apply's after the final
+    push), `held` the frames that wait (never more than stream_need(spec)), `partial` the samples of the incomplete frame.  It keeps
+    the frames `stream_held` names, in the device carry's order, and nothing else of the signal."""
+
+    def __init__(self, fs: int, spec=True):
+        self.fs, self.spec = check_stream(fs, spec)
+        self.F = self.fs // 100
+        self.c = stream_consts(self.spec)
+        self.need = stream_need(self.spec)
+        self.state = (0, 0, 0, [0] * REC)
+        self.carry = []                                               # the held frames, float32 [F] each
+        self.partial = np.zeros(0, dtype=np.float32)
+        self.pushed = 0
+        self.done = False
+
+    @property
+    def held(self) -> int:
+        return len(self.carry)
+
+    @property
+    def record(self) -> np.ndarray:
+        return np.array(self.state[3], dtype=np.int32)
+
+    def push(self, x, final: bool = False) -> np.ndarray:
+        if self.done:
+            raise ValueError("pauses: the stream has had its last push")
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        if self.pushed + len(x) >= 1 << 31:
+            raise ValueError("pauses: the stream would hold 2^31 samples or more")
+        F, c = self.F, self.c
+        new = np.concatenate([self.partial, x])
+        nf = len(new) // F + (1 if final and len(new) % F else 0)     # on the final push the partial frame is a frame
+        acts = activity(new[: nf * F], F, self.spec.thr()) if nf else np.zeros(0, dtype=bool)
+        mode0, nfr0, pa0, _ = self.state
+        r0o, loo, ao, bo, _ = stream_held(c, mode0, nfr0, pa0)
+
+        def frame(j):                                                 # a held frame of the old carry, or a new one
+            if j >= nfr0:
+                return new[(j - nfr0) * F: (j - nfr0 + 1) * F]
+            k = j - r0o
+            assert loo <= k < ao or bo <= k, "a frame the stream no longer holds"
+            return self.carry[k - loo if k < ao else (ao - loo) + (k - bo)]
+        emit, state = stream_walk(c, self.state, acts, final)
+        w_in = fade_table(F)
+        parts = [frame(j) if b < 0 else (w_in[::-1] * frame(j)) + (w_in * frame(b)) for j, b in emit]
+        y = np.concatenate(parts).astype(np.float32, copy=False) if parts else np.zeros(0, dtype=np.float32)
+        state[3][7] += len(y)
+        if final:
+            self.carry, self.partial = [], np.zeros(0, dtype=np.float32)
+        else:
+            r0, lo, a, b, m = stream_held(c, state[0], state[1], state[2])
+            self.carry = [frame(r0 + k).copy() for k in [*range(lo, a), *range(b, m)]]
+            self.partial = new[nf * F:].copy()
+            assert len(self.carry) <= self.need <= STREAM_FRAMES
+        self.state, self.pushed, self.done = state, self.pushed + len(x), bool(final)
+        return y

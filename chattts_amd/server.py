@@ -97,7 +97,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
                stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
-               pauses: bool = False, limiter: bool = False, stream_limiter: bool = False):
+               pauses: bool = False, limiter: bool = False, stream_limiter: bool = False, stream_pauses: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -175,7 +175,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     (SpeechBatcher(stream_limiter=True).submit_stream(limiter=True)), serially otherwise (Chat.infer(stream=True, limiter=True,
     stream_limiter=True)), with whatever streamed rate, speed and format the other options allow; such a body may also carry
     `"gain_db"`, a fixed make-up gain of -30 .. +30 dB in front of the limiter (a bad value, or the key without `"stream": true` and
-    `"limiter": true`, gets a 400), and /health carries `"stream_limiter": true`."""
+    `"limiter": true`, gets a 400), and /health carries `"stream_limiter": true`.  `stream_pauses=True` (with `pauses`; default off): a
+    body with `"stream": true` and `"pauses"` is served too -- every stream gets a pause stream on the device that carries the run
+    state across chunks (chattts_amd/pauses.py: the schedule and the lags), from the pool where the batcher was built with
+    `stream_pauses=True`, serially otherwise (Chat.infer(stream=True, pauses=, stream_pauses=True)); a spec that would make a stream
+    hold more frames than a slot has gets a 400, chunks that come out empty are not written, and /health carries
+    `"stream_pauses": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -194,7 +199,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                 **({"refine": True} if batch_refine else {}), **({"stream_speeds": True} if speed and stream_speed else {}),
                                 **({"stream_speed_rates": True} if speed and stream_speed and stream_speed_rates else {}),
                                 **({"stream_flac": True} if flac and stream_flac else {}),
-                                **({"stream_limiter": True} if limiter and stream_limiter else {}))
+                                **({"stream_limiter": True} if limiter and stream_limiter else {}),
+                                **({"stream_pauses": True} if pauses and stream_pauses else {}))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
@@ -206,6 +212,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     pool_stream_flac = pool_streams and flac_streams and bool(getattr(batcher, "stream_flac", False))
     limiter_streams = bool(limiter and stream_limiter)
     pool_stream_limiter = pool_streams and limiter_streams and bool(getattr(batcher, "stream_limiter", False))
+    pause_streams = bool(pauses and stream_pauses)
+    pool_stream_pauses = pool_streams and pause_streams and bool(getattr(batcher, "stream_pauses", False))
     pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
     pool_split = bool(batch_split) and batcher is not None
     allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
@@ -306,6 +314,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 kw = {**kw, "stream_scaled_resample": True}
         if req.stream and lim:                       # likewise for a limited stream
             kw = {**kw, "stream_limiter": True, "split_text": False, **({} if gdb is None else {"gain_db": gdb})}
+        if req.stream and trim is not None:          # likewise for a paused stream
+            kw = {**kw, "stream_pauses": True, "split_text": False}
         return chat.infer(text=[req.input], stream=bool(req.stream), lang=None, skip_refine_text=True, refine_text_only=False,
                           use_decoder=True, do_text_normalization=True, do_homophone_replacement=True,
                           params_infer_code=code_params(req.voice), pcm16=True, **kw)
@@ -371,9 +381,14 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 PA.check_rate(rate)
             except ValueError as e:
                 raise HTTPException(400, detail=str(e))
-            if req.stream:
+            if req.stream and not pause_streams:
                 raise HTTPException(400, detail="pauses is served for non-streamed requests only: a stream would need the run state "
                                                 "carried across chunks")
+            if req.stream:
+                try:
+                    PA.check_stream(rate, trim)
+                except ValueError as e:
+                    raise HTTPException(400, detail=str(e))
         lim = False                                  # the request's limiter flag where it is honoured
         if limiter and request_data.get("limiter") is not None:
             if not isinstance(request_data["limiter"], bool):
@@ -446,13 +461,15 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             return _av_encode(pcm, fmt, rate)
 
         if req.stream and pool_streams and (spd is None or (pool_stream_speeds and (rate == SAMPLE_RATE or pool_stream_speed_rates))) \
-                and (not as_flac or pool_stream_flac) and (not lim or pool_stream_limiter):
+                and (not as_flac or pool_stream_flac) and (not lim or pool_stream_limiter) and (trim is None or pool_stream_pauses):
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
                 skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
                 if spd is not None:
                     skw = {**skw, "speed": spd}
                 if lim:
                     skw = {**skw, "limiter": True, **({} if gdb is None else {"gain_db": gdb})}
+                if trim is not None:
+                    skw = {**skw, "pauses": trim}
                 chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw, **ekw)
                 try:
                     first = True
@@ -475,7 +492,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        gen = infer(req, rate, law, spd, as_flac, None, None, True, gdb) if lim else infer(req, rate, law, spd, True) if as_flac else \
+                        gen = infer(req, rate, law, spd, as_flac, None, trim, lim, gdb) if trim is not None else \
+                            infer(req, rate, law, spd, as_flac, None, None, True, gdb) if lim else infer(req, rate, law, spd, True) if as_flac else \
                             infer(req, rate, law, spd) if spd is not None else (infer(req, rate) if law is None else infer(req, rate, law))
                         async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
                             if fmt == "wav" and first:
@@ -571,6 +589,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["limiter"] = True
         if limiter_streams:
             out["stream_limiter"] = True
+        if pause_streams:
+            out["stream_pauses"] = True
         return out
 
     return app

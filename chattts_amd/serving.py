@@ -670,6 +670,7 @@ class _Job:
     pauses: object = None                  # a pauses.PauseSpec (non-streamed only); None: the silence is left alone
     limiter: bool = False                  # the look-ahead peak limiter behind the loudness stage's gain; a stream: in front of the conversion
     lm_slot: Optional[int] = None          # a limited stream: its stream of the limiter, opened at its first chunk
+    pa_slot: Optional[int] = None          # a paused stream: its pause stream, opened at its first chunk
     lm_gain: Optional[float] = None        # ... and the float32 pre-gain of its `gain_db` (None: 1)
 
     @property
@@ -782,7 +783,7 @@ class SpeechBatcher:
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
                  logger=None, ragged_decode: bool = False, streams: bool = False, refine: bool = False, make_text_pool=None,
                  text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False, stream_speed_rates: bool = False,
-                 stream_flac: bool = False, stream_limiter: bool = False):
+                 stream_flac: bool = False, stream_limiter: bool = False, stream_pauses: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
@@ -800,6 +801,8 @@ class SpeechBatcher:
         self.stream_flac_chunks = 0        # chunks handed out as FLAC frames (empty ones included)
         self.stream_limiter = bool(stream_limiter)   # submit_stream(limiter=True) is accepted
         self.stream_limited_chunks = 0     # chunks that came out of a limiter stream (empty ones included)
+        self.stream_pauses = bool(stream_pauses)     # submit_stream(pauses=) is accepted
+        self.stream_paused_chunks = 0      # chunks that came out of a pause stream (empty ones included)
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.flac_encoded = 0              # results handed out as FLAC files
         self.trimmed = 0                   # results handed out with their pauses trimmed
@@ -925,7 +928,10 @@ class SpeechBatcher:
         chunks of the same request without `flac`.  The chunks of all FLAC streams due at one poll share ONE encoder step behind the
         one decoder pass (CodecEngine.decode_windows(flac=)); it combines with `sample_rate` and `speed` as far as the batcher serves
         those, not with `encoding`.  `loudness` is refused: an integrated loudness needs the whole utterance.  `pauses` is refused: the
-        run state would have to be carried across chunks.  `limiter` is refused: the look-ahead is not carried across chunks -- unless
+        run state would have to be carried across chunks -- unless the batcher was built with `stream_pauses=True`: then the request
+        gets a pause stream (opened at its first chunk, given back where its other streams are) and its chunks are those of the serial
+        call with `pauses=, stream_pauses=True`, possibly empty (CodecEngine.decode_windows(pauses=); a spec that would make a stream
+        hold more than `pauses.STREAM_FRAMES` frames is refused here).  `limiter` is refused: the look-ahead is not carried across chunks -- unless
         the batcher was built with `stream_limiter=True`: then the request gets a limiter stream (opened at its first chunk, given back
         where its other streams are) and its chunks are those of the serial call with `limiter=True, stream_limiter=True`: converted,
         companded or FLAC-encoded from limited samples, 20 ms behind.  The limiter streams due at one poll share one step per round
@@ -939,8 +945,11 @@ class SpeechBatcher:
             raise ValueError("gain_db is the make-up gain in front of the limiter: it needs limiter=True")
         if limiter:
             LN.check_rate(24000 if sample_rate is None else sample_rate)
-        if PA.check(pauses) is not None:
+        pauses = PA.check(pauses)
+        if pauses is not None and not self.stream_pauses:
             raise ValueError("pauses applies to non-streamed requests only (a stream would need the run state carried across chunks)")
+        if pauses is not None:
+            PA.check_stream(24000 if sample_rate is None else sample_rate, pauses, "submit_stream")
         if LN.check_target(loudness) is not None:
             raise ValueError("loudness applies to non-streamed requests only (an integrated loudness needs the whole utterance; a stream "
                              "would need a running measure)")
@@ -970,7 +979,7 @@ class SpeechBatcher:
                 raise ValueError(f"a streamed speed at {rate} Hz would carry up to {K - 1} samples, a resampler stream keeps {RS.CARRY}")
         h = SpeechStream(self, next(self._ids))
         self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed, flac=bool(flac),
-                          **({"limiter": True, "lm_gain": g32} if limiter else {})))
+                          **({"limiter": True, "lm_gain": g32} if limiter else {}), **({} if pauses is None else {"pauses": pauses})))
         return h
 
     def _check_refine(self, refine) -> None:
@@ -997,6 +1006,8 @@ class SpeechBatcher:
                 occ["stream_flac_chunks"] = self.stream_flac_chunks
             if self.stream_limiter:
                 occ["stream_limited_chunks"] = self.stream_limited_chunks
+            if self.stream_pauses:
+                occ["stream_paused_chunks"] = self.stream_paused_chunks
         if self.refine:
             occ["refine"] = {"active": len(getattr(tp, "active", {})), "queued": len(getattr(tp, "queue", ())),
                              "admissions": self.refine_admissions, "max_coresident": self.refine_max_coresident,
@@ -1030,6 +1041,9 @@ class SpeechBatcher:
         if job.lm_slot is not None:        # ... and its stream of the limiter
             slot, job.lm_slot = job.lm_slot, None
             self.chat.codec.peak_limit_stream_close(slot)
+        if job.pa_slot is not None:        # ... and its pause stream
+            slot, job.pa_slot = job.pa_slot, None
+            self.chat.codec.trim_pauses_stream_close(slot)
         failed = isinstance(result, BaseException)
         if cancelled:
             self.cancelled += job.is_stream
@@ -1290,6 +1304,12 @@ class SpeechBatcher:
                         j.lm_slot = self.chat.codec.peak_limit_stream_open(24000 if j.sample_rate is None else j.sample_rate,
                                                                            1.0 if j.lm_gain is None else j.lm_gain)
                 kw["lm_streams"] = [j.lm_slot for j in jobs]
+            if "pauses" in kw:            # the pause streams due at this poll: one step per round in front of the limiter's
+                self.stream_paused_chunks += sum(j.pauses is not None for j in jobs)
+                for j in jobs:
+                    if j.pauses is not None and j.pa_slot is None:
+                        j.pa_slot = self.chat.codec.trim_pauses_stream_open(24000 if j.sample_rate is None else j.sample_rate, j.pauses)
+                kw["pa_streams"] = [j.pa_slot for j in jobs]
             pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **kw)
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for job in dict.fromkeys(jobs):

@@ -522,6 +522,49 @@ int ctts_trim_pauses_ragged(const float* in, float* out, const int64_t* off_dev,
                             const float* fade_dev, int32_t n_fade, int64_t* off_out, int32_t* records, void* scratch, size_t scratch_bytes,
                             void* stream);
 
+/* Pause control of STREAMS: a segment arrives in pushes, and the frames ctts_trim_pauses_ragged would keep leave as soon as the rules decide
+ * them (chattts_amd/pauses.py: schedule, lags, state).  The chunks of a stream, concatenated, are ctts_trim_pauses_ragged of its concatenated
+ * pushes bit for bit, however the signal was cut, and after the last push the slot's record is that call's record (all zero for a stream
+ * that ends empty).  One step of one stream: x[in_off, in_off + n_in) are samples [pos, pos + n_in); the chunk is written from y[out_off] on.
+ * Its length depends on the samples: res[4 i ..] = (samples written, frames that wait behind the step, copy-list entries, 0) on the device,
+ * for the caller to read back in one copy.  y keeps room for `need` F + pos % F + n_in samples from out_off on -- what may wait and what
+ * arrives -- and the rooms of a step's streams do not overlap; y does not overlap x.
+ * carry: [n_slots][2][CTTS_PA_STREAM_CARRY] float32 on the device, two buffers per slot: the frames that wait (at most `need` =
+ * pauses.stream_need of the spec <= CTTS_PA_STREAM_FRAMES, F samples apart) and, at CTTS_PA_STREAM_FRAMES * 480, the pos % F samples of the
+ * incomplete frame; a step reads buffer `phase` and writes the other, so the caller flips `phase` after every accepted step of a slot.
+ * state: [n_slots][CTTS_PA_STREAM_STATE] int32 on the device, written by the steps only: mode, frames seen, the last active frame, the
+ * record (8 int32, pauses.RECORD).  A slot is fresh by its descriptor alone: at pos == 0 neither state nor carry is read.
+ * A fixed number of launches (activity of the new frames, a walk of one wave per stream, the copy) over up to 1024 descriptors of any rates
+ * and specs; the table is given on the device and the host (the two must agree).  fr_off and list_off are running sums over the
+ * descriptors: of nf = (pos % F + n_in) / F new frames (one more for the partial frame of a last push) and of n_list = 2 need + nf + 1
+ * entries; scratch holds ctts_trim_pauses_stream_scratch_bytes(sum nf, sum n_list).  Refused before anything is launched, from the host
+ * mirror: a null pointer, n_streams outside 1 .. 1024, a pool without a slot, misaligned buffers, y overlapping x, a frame outside 80 .. 480,
+ * a spec out of range or needing more than CTTS_PA_STREAM_FRAMES frames, `need`, fr_off, list_off or n_list other than the above, a fade
+ * offset outside the table, a negative length, position or offset, 2^31 samples, a push outside x, a room outside y or overlapping
+ * another, a phase or last-push flag other than 0 / 1, a slot outside the pool or named twice in the call, scratch too small. */
+#define CTTS_PA_STREAM_FRAMES 112
+#define CTTS_PA_STREAM_CARRY 54240
+#define CTTS_PA_STREAM_STATE 16
+#define CTTS_PA_STREAM_RES 4
+typedef struct {
+  int64_t in_off, n_in;       /* the new samples: x[in_off, in_off + n_in) */
+  int64_t pos;                /* samples pushed before them */
+  int64_t out_off;            /* the chunk starts at y[out_off] */
+  int64_t fr_off;             /* the stream's first new frame among the step's */
+  int64_t list_off;           /* the stream's first copy-list entry among the step's */
+  int32_t slot, phase;        /* the state slot; which of its two carry buffers the step reads */
+  int32_t need;               /* frames the spec can make wait (pauses.stream_need) */
+  int32_t fin;                /* 1: the stream's last push */
+  int32_t F, pad, lead, tail, P;   /* samples per frame; the spec in frames */
+  float thr;                  /* a frame is active when some sample has !(|x| < thr) */
+  int32_t fade;               /* the offset of the crossfade table w_in[F] in fade_dev */
+  int32_t n_list;             /* copy-list entries kept for the stream */
+} ctts_pa_stream;             /* 96 bytes (pause stream) */
+size_t ctts_trim_pauses_stream_scratch_bytes(int64_t frames, int64_t entries);
+int ctts_trim_pauses_stream_step(const float* x, int64_t n_x, const ctts_pa_stream* st_dev, const ctts_pa_stream* st_host, int32_t n_streams,
+                                 float* y, int64_t n_y, float* carry, int32_t* state, int32_t n_slots, const float* fade_dev, int32_t n_fade,
+                                 int32_t* res, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Time scaling of streams: the signal of a stream arrives in pushes, its output leaves in chunks, and the concatenation of the chunks (and
  * of the path entries) is ctts_time_scale_ragged's result on the whole signal, bit for bit, however the signal is cut into pushes.
  * With n_avail samples in and more to come, frame k >= 1 may run once need(k) = max(a_{k-1} + D + N - 1, a_k - HS + D + N - 1) <= n_avail;

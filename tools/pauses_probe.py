@@ -12,10 +12,17 @@
                 wall time including the host side.  `--root DIR` imports the package from another checkout (the parent commit, built
                 there), so that the two trees can be timed alternately in one session
 
+  * --stream  : the pause STREAMS (ctts_trim_pauses_stream_step) instead: 1 / 8 / 64 streams at 24 kHz under the default spec, each
+                pushed 12 000 samples per step (half a second, a served stream's chunk) of the same stepped signal, 20 steps.  Wall
+                time of `CodecEngine.trim_pauses_stream_step` -- the upload of the table, the three launches and the one copy of the
+                counts it waits for -- and the device time between events around it; stream 0's chunks are checked against the
+                NumPy twin, bit for bit.  `--out FILE`: the table as markdown
+
 Synthetic weights, noise input under a stepped envelope: quiet steps at -70 dBFS, about half of the frames, in runs of 0.1 .. 1.5 s.
 Prints one JSON line.  Not a bench.py leg.
 
     python tools/pauses_probe.py [--reps 20] [--gemm f16] [--trace] [--root DIR] [--decode-only]
+    python tools/pauses_probe.py --stream [--rounds 5] [--out profiles/pauses_stream_probe.md]
 """
 from __future__ import annotations
 
@@ -106,6 +113,59 @@ def _wall_ms(fn, reps):
     return round(float(np.median(ts)), 3), round(float(np.min(ts)), 3), round(float(np.max(ts)), 3)
 
 
+CHUNK, STEPS = 12000, 20          # samples per push of the stream probe; pushes per stream
+
+
+def _stream(codec, PA, rounds):
+    """step time of 1 / 8 / 64 pause streams: per B the wall and device times of a step in ms (median, min, max over steps and rounds)"""
+    dev = codec.device
+    res = {}
+    for B in (1, 8, 64):
+        host = _signal(B)[: B * SEG].reshape(B, SEG)
+        x = torch.from_numpy(np.ascontiguousarray(host[:, : CHUNK * STEPS])).to(dev)
+        wall, devt, out_n, held = [], [], 0, 0
+        for r in range(rounds + 1):                     # round 0 warms up
+            hs = [codec.trim_pauses_stream_open(24000, True) for _ in range(B)]
+            tw = PA.StreamPauses(24000, True) if r == 0 else None
+            try:
+                for k in range(STEPS):
+                    pushes = [(h, i * CHUNK * STEPS + k * CHUNK, CHUNK, k == STEPS - 1) for i, h in enumerate(hs)]
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    a.record()
+                    y, off = codec.trim_pauses_stream_step(x.view(-1), pushes)
+                    b.record()
+                    b.synchronize()
+                    t1 = time.perf_counter()
+                    if r:
+                        wall.append((t1 - t0) * 1e3)
+                        devt.append(a.elapsed_time(b))
+                        out_n += int(off[-1])
+                        held = max(held, max(codec.trim_pauses_stream_stats(h)["held"] for h in hs) if k < STEPS - 1 else 0)
+                    else:
+                        want = tw.push(host[0, k * CHUNK: (k + 1) * CHUNK], k == STEPS - 1)
+                        assert y[: int(off[1])].cpu().numpy().tobytes() == want.tobytes(), (B, k)
+            finally:
+                for h in hs:
+                    codec.trim_pauses_stream_close(h)
+        f = lambda v: dict(median=round(float(np.median(v)), 4), min=round(float(np.min(v)), 4), max=round(float(np.max(v)), 4))
+        res[B] = dict(wall_ms=f(wall), device_ms=f(devt), samples_in=B * CHUNK * STEPS, samples_out=out_n // rounds, held_max=held)
+    return res
+
+
+def _stream_markdown(res, rounds) -> str:
+    rows = ["# Pause streams: step time (tools/pauses_probe.py --stream)", "",
+            f"{CHUNK} samples at 24 kHz per stream and step, {STEPS} steps, default spec; median (min .. max) over the steps of {rounds} rounds. "
+            "`wall` is `CodecEngine.trim_pauses_stream_step` as a caller sees it (table upload, three launches, the one copy of the counts and "
+            "its wait); `device` is the time between events around it.", "",
+            "| streams | wall, ms | device, ms | samples in | samples out | most frames held |", "|---|---|---|---|---|---|"]
+    f = lambda d: f"{d['median']:.3f} ({d['min']:.3f} .. {d['max']:.3f})"
+    for B, d in res.items():
+        rows.append(f"| {B} | {f(d['wall_ms'])} | {f(d['device_ms'])} | {d['samples_in']} | {d['samples_out']} | {d['held_max']} |")
+    return "\n".join(rows) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -113,6 +173,9 @@ def main():
     ap.add_argument("--trace", action="store_true", help="only the 64-segment calls: the run to put under a kernel trace")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout to import chattts_amd from")
     ap.add_argument("--decode-only", action="store_true", help="only the 64-row decode without the keyword (any checkout has it)")
+    ap.add_argument("--stream", action="store_true", help="time the pause streams instead")
+    ap.add_argument("--rounds", type=int, default=5, help="with --stream: timed rounds of 20 steps")
+    ap.add_argument("--out", default=None, help="with --stream: the markdown table goes here")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("pauses_probe needs a GPU: nothing here can be timed without one")
@@ -120,6 +183,15 @@ def main():
     from chattts_amd.weights import synthetic_all
     dev = torch.device("cuda:0")
     sds = synthetic_all()
+    if a.stream:
+        from chattts_amd import pauses as PA
+        from chattts_amd.engine import CodecEngine
+        res = _stream(CodecEngine(sds["decoder"], sds["vocos"], dev), PA, a.rounds)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(_stream_markdown(res, a.rounds))
+        print(json.dumps(dict(metric="pauses_stream_probe", rounds=a.rounds, chunk=CHUNK, steps=STEPS, streams=res)))
+        return
     if a.trace:
         from chattts_amd import pauses as PA
         from chattts_amd.engine import CodecEngine
