@@ -62,6 +62,11 @@ G711_RANGE = np.dtype([("start", "<i8"), ("n", "<i8"), ("law", "<i4"), ("pad0", 
 FLAC_RANGE = np.dtype([("start", "<i8"), ("n", "<i8"), ("rate", "<i4"), ("count_idx", "<i4"), ("frame0", "<i8")])
 
 
+# ctts_adpcm_range (48 bytes): start, n, block0, byte0 int64; rate (0 skip), count_idx (-1: n is the length) int32; reserved int64
+ADPCM_RANGE = np.dtype([("start", "<i8"), ("n", "<i8"), ("block0", "<i8"), ("byte0", "<i8"), ("rate", "<i4"), ("count_idx", "<i4"),
+                        ("reserved", "<i8")])
+
+
 # ctts_flac_push (64 bytes): start, n, sample, stage, frame0 int64; rate, slot, carry, flags (1 final, 2 keep mask), count_idx, reserved int32
 FLAC_PUSH = np.dtype([("start", "<i8"), ("n", "<i8"), ("sample", "<i8"), ("stage", "<i8"), ("frame0", "<i8"), ("rate", "<i4"),
                       ("slot", "<i4"), ("carry", "<i4"), ("flags", "<i4"), ("count_idx", "<i4"), ("reserved", "<i4")])
@@ -206,6 +211,8 @@ SIGNATURES = {
     "ctts_g711_encode_ranges": (C.c_int, [P, P, P, P, I32, P]),
     "ctts_flac_encode_sizes": (C.c_int, [P, I32, P]),
     "ctts_flac_encode_ranges": (C.c_int, [P, P, P, P, I32, P, SZ, P, SZ, P]),
+    "ctts_adpcm_encode_sizes": (C.c_int, [P, I32, P]),
+    "ctts_adpcm_encode_ranges": (C.c_int, [P, P, P, P, I32, P, SZ, P, SZ, P]),
     "ctts_flac_stream_sizes": (C.c_int, [P, I32, I32, C.c_int64, P]),
     "ctts_flac_stream_step": (C.c_int, [P, C.c_int64, P, P, P, P, I32, P, I32, P, SZ, P, SZ, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),

@@ -99,13 +99,28 @@ def _load_g711_wav(data: bytes):
     return x.reshape(frames, ch).mean(axis=1).astype(np.float32), int(rate)
 
 
-def load_wav(data: bytes, *, g711: bool = False):
+def _load_adpcm_wav(data: bytes):
+    """a mono WAVE_FORMAT_IMA_ADPCM file (`adpcm.parse_wav`) -> (float32 mono, rate), or None when the bytes are no RIFF/WAVE with that tag"""
+    from .adpcm import parse_wav
+    got = parse_wav(data)
+    if got is None:
+        return None
+    return (got[0].astype(np.float64) / 32768.0).astype(np.float32), got[1]
+
+
+def load_wav(data: bytes, *, g711: bool = False, adpcm: bool = False):
     """RIFF/WAVE bytes -> (float32 mono samples in [-1, 1), sample rate): the front door of voice cloning from an uploaded clip
     (`Chat.sample_audio_speaker(wav, rate)`, the endpoint's POST /v1/audio/voices).  Integer PCM of 8 (unsigned), 16 or 32 bits, any
     number of channels (averaged to mono), read with the stdlib `wave` module.  Anything else -- a float or compressed WAVE, 24-bit
     samples, no RIFF at all, no frames -- raises ValueError naming what was found.  `g711=True` (keyword-only; the default refuses them
     like any compressed file): mu-law and A-law files (format tags 7 / 6, 8 bits, any channel count, any rate) -- telephone recordings --
-    are parsed from the RIFF chunks by hand and expanded through `g711.expand`'s tables to int16 / 32768."""
+    are parsed from the RIFF chunks by hand and expanded through `g711.expand`'s tables to int16 / 32768.  `adpcm=True` (keyword-only;
+    the default refuses them likewise): mono IMA ADPCM files (format tag 0x0011, 4 bits, any block size, any rate) are decoded through
+    `adpcm.parse_wav` to int16 / 32768; another channel count, or a `fmt ` chunk that disagrees with its block size, raises ValueError."""
+    if adpcm:
+        got = _load_adpcm_wav(bytes(data))
+        if got is not None:
+            return got
     if g711:
         got = _load_g711_wav(bytes(data))
         if got is not None:

@@ -22,6 +22,7 @@ from typing import Iterator, List, Optional, Union
 import numpy as np
 import torch
 
+from . import adpcm as ADPCM
 from . import flac as FLAC
 from . import g711 as G711
 from . import limiter as LM
@@ -333,7 +334,7 @@ class Chat:
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
                         product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None,
-                        flac=None, loudness=None, pauses=None, limiter=None) -> List[np.ndarray]:
+                        flac=None, loudness=None, pauses=None, limiter=None, adpcm=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
@@ -358,17 +359,26 @@ class Chat:
         Without `ragged` the trimmed rows of the batch go on as a pack, through the ragged calls' conversion.
         `limiter` (None / False: off; True, also one flag per row): `wav` above is the waveform behind the look-ahead peak limiter
         (CodecEngine.peak_limit), which runs where the loudness stage is, at its gain without the ceiling term (unity without
-        `loudness`): no sample that is converted exceeds -1 dBFS, and a peak above full scale is limited instead of clipped."""
+        `loudness`): no sample that is converted exceeds -1 dBFS, and a peak above full scale is limited instead of clipped.
+        `adpcm` (None / False: the call above; True; with `ragged` also one flag per row): a flagged row comes back as a uint8 array, the
+        complete WAVE_FORMAT_IMA_ADPCM file (chattts_amd/adpcm.py: 4 bits per sample) of exactly the int16 samples above at the row's
+        rate, encoded on the device behind the conversion (CodecEngine.float_to_int16_groups_adpcm); not together with `flac`, nor
+        with an `encoding` on the same row."""
         plan = Plan.given("decode_to_pcm16", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
         encs, flags = self._formats(encoding, flac, len(result_list), per_row=ragged, who="decode_to_pcm16")
+        aflags = self._adpcm_flags(adpcm, len(result_list), encoding, flags, ragged, "decode_to_pcm16")
         if len(result_list) == 0:
             return []
+        if aflags is not None:
+            for r in plan.row_rates(len(result_list)):
+                ADPCM.check_rate(r)
         wav, off = self._decode_float(result_list, use_decoder, ragged, None, plan, own_chain=True)
-        if flags is not None:
-            return self._decode_to_flac(wav, off, plan.row_rates(len(result_list)), flags, strip, product, encs)
+        if flags is not None or aflags is not None:
+            return self._decode_to_flac(wav, off, plan.row_rates(len(result_list)), flags or aflags, strip, product, encs,
+                                        **({} if aflags is None else {"adpcm": True}))
         if off is not None:
             return self._decode_to_pcm16_ragged(wav, off, strip, product, encs)
         encoding = None if encs is None else encs[0]
@@ -414,6 +424,29 @@ class Chat:
         return flags
 
     @staticmethod
+    def _adpcm_flags(adpcm, n: int, encoding, flac_flags, per_row: bool, who: str):
+        """the `adpcm=` option of the decode calls -> one bool per row, or None when no row asks for it (today's call); `flac_flags`:
+        what `_flac_flags` made of the same call's `flac=`"""
+        if adpcm is None or adpcm is False:
+            return None
+        if isinstance(adpcm, (bool, np.bool_)):
+            flags = [bool(adpcm)] * n
+        else:
+            if not per_row:
+                raise ValueError(f"{who}: one adpcm flag for the whole call (one per row goes with ragged=True)")
+            flags = [bool(f) for f in adpcm]
+            if len(flags) != n:
+                raise ValueError(f"{who}: one adpcm flag per row, or one for all")
+        if not any(flags):
+            return None
+        if flac_flags is not None:
+            raise ValueError(f"{who}: adpcm does not go with flac (a call hands out one kind of file)")
+        encs = None if encoding is None else ([encoding] * n if isinstance(encoding, str) else list(encoding))
+        if encs is not None and (len(encs) != n or any(f and e is not None for f, e in zip(flags, encs))):
+            raise ValueError(f"{who}: adpcm does not go with an encoding (an ADPCM file is coded from the 16-bit samples; one entry per row)")
+        return flags
+
+    @staticmethod
     def _formats(encoding, flac, n: int, per_row: bool, who: str, unit: str = "row"):
         """the `encoding=` and `flac=` options of the 16-bit calls, once for every path and before the decode -> (encs, flags): one
         encoding per row, None unless a row is companded or some row is a FLAC file; one flac flag per row, None when none is set
@@ -430,17 +463,19 @@ class Chat:
             raise ValueError(f"{who}: one encoding per {unit}, or one for all")
         return (encs if any(G711.check_encoding(e) is not None for e in encs) else None), None
 
-    def _decode_to_flac(self, wav, off, rates, flags, strip: bool, product: str, encs=None, grp=None) -> List[np.ndarray]:
+    def _decode_to_flac(self, wav, off, rates, flags, strip: bool, product: str, encs=None, grp=None, adpcm: bool = False) -> List[np.ndarray]:
         """a decoded waveform -- [B, n], or packed with `off` -- with at least one row (with `grp`: one request, its sentences) as a
         FLAC file at its entry of `rates`: the grouped conversion with one group per row (the same samples; slots that start on
-        multiples of 8 and a count header on the device) and the encoder behind it"""
+        multiples of 8 and a count header on the device) and the encoder behind it.  `adpcm`: the flagged rows are IMA ADPCM WAV files
+        instead (CodecEngine.float_to_int16_groups_adpcm, the same seam)"""
         if off is None:
             wav = wav.contiguous()
             off = np.arange(wav.shape[0] + 1, dtype=np.int64) * int(wav.shape[1])
             wav = wav.view(-1)
         grp = np.arange(len(flags) + 1, dtype=np.int32) if grp is None else grp
-        out = self.codec.float_to_int16_groups_flac(wav, off, grp, [r if f else None for r, f in zip(rates, flags)], product=product,
-                                                    keep_thr=1e-5 if strip else None, encodings=encs)
+        convert = self.codec.float_to_int16_groups_adpcm if adpcm else self.codec.float_to_int16_groups_flac
+        out = convert(wav, off, grp, [r if f else None for r, f in zip(rates, flags)], product=product, keep_thr=1e-5 if strip else None,
+                      encodings=encs)
         return [p if p.dtype == np.uint8 else p.copy() for p in out]
 
     def _decode_to_pcm16_ragged(self, wav, off, strip: bool, product: str, encs=None) -> List[np.ndarray]:
@@ -500,7 +535,7 @@ class Chat:
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None,
-                              speed=None, flac=None, loudness=None, pauses=None, limiter=None) -> List[np.ndarray]:
+                              speed=None, flac=None, loudness=None, pauses=None, limiter=None, adpcm=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
@@ -524,7 +559,10 @@ class Chat:
         gain is then computed over its trimmed sentences.
         `limiter` (None / False: off; True, or one flag per request): a flagged request's ONE gain drops the ceiling term and the
         look-ahead peak limiter (CodecEngine.peak_limit) runs behind it over every sentence alone: its windows never span two
-        sentences.  Without `loudness` it runs at unity gain."""
+        sentences.  Without `loudness` it runs at unity gain.
+        `adpcm` (None / False: the call above; True; or one flag per request): a flagged request comes back as a uint8 array, ONE
+        WAVE_FORMAT_IMA_ADPCM file over its concatenated sentences at the request's rate (CodecEngine.float_to_int16_groups_adpcm);
+        not together with `flac`, nor with an `encoding` on the same request."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -535,16 +573,20 @@ class Chat:
         np.cumsum([len(g) for g in groups], out=grp[1:])
         codec = self.codec
         encs, flags = self._formats(encoding, flac, len(groups), per_row=True, who="decode_split_to_pcm16", unit="request")
+        aflags = self._adpcm_flags(adpcm, len(groups), encoding, flags, True, "decode_split_to_pcm16")
         plan = Plan.given("decode_split_to_pcm16", sample_rate, speed, loudness, pauses, limiter)
         rates = plan.row_rates(len(groups))
+        if aflags is not None:
+            for r in rates:
+                ADPCM.check_rate(r)
         plan = plan.per_sentence(groups)
         rows = [h for g in groups for h in g]
         wav, off = codec.decode_ragged(rows, sample_rate=plan.sample_rate, **plan.kwargs("speed", "pauses"))
         if plan.levels:                                               # ONE gain per request: the stage runs here, over the group table
             wav = codec.loudness_normalize(wav, plan.loudness, offsets=off, groups=grp, out=wav, rates=plan.row_rates(len(rows)),
                                            **plan.kwargs("limiter"))
-        if flags is not None:
-            return self._decode_to_flac(wav, off, rates, flags, strip, product, encs, grp=grp)
+        if flags is not None or aflags is not None:
+            return self._decode_to_flac(wav, off, rates, flags or aflags, strip, product, encs, grp=grp, **({} if aflags is None else {"adpcm": True}))
         blob, starts = codec.float_to_int16_groups(wav, off, grp, product=product, keep_thr=1e-5 if strip else None,
                                                    **({} if encs is None else {"encodings": encs}))
         return [p.copy() for p in codec.unpack_groups(codec.to_host(blob), starts, *(() if encs is None else (encs,)))]
@@ -902,7 +944,7 @@ class Chat:
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
               flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None,
-              stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False):
+              stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False, adpcm: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -994,7 +1036,13 @@ class Chat:
         `pauses.stream_need` exceeds `pauses.STREAM_FRAMES`.  Without the switch the refusal above stays.
         `gain_db` (keyword-only; with `stream=True, limiter=True, stream_limiter=True` only): a fixed make-up gain in dB, -30 .. +30, one
         for the whole batch, applied in front of the limiter as its float32 pre-gain 10 ** (gain_db / 20).  A non-streamed call has
-        `loudness` for its level and refuses it."""
+        `loudness` for its level and refuses it.
+        `adpcm=True` (keyword-only, non-streamed only; needs `pcm16=True`, not together with `encoding` or `flac`: ValueError
+        otherwise): every result is a uint8 array holding the complete WAVE_FORMAT_IMA_ADPCM file (chattts_amd/adpcm.py: mono, 4 bits
+        per sample, blocks of 256 / 512 / 1024 bytes by `sample_rate`) of exactly the int16 samples the same call returns without it
+        -- half of G.711's size, encoded on the device behind the conversion (CodecEngine.adpcm_encode), at whatever rate, speed,
+        pauses, loudness and limiter the call has.  A split request is one file over its concatenated sentences.  A streamed call
+        raises: a stream would have to carry up to a block's samples across chunks."""
         mkw = Plan.given("infer", limiter=limiter).kwargs()
         if gain_db is not None and np.ndim(gain_db) != 0:
             raise ValueError("gain_db is one make-up gain for the whole batch")
@@ -1057,6 +1105,18 @@ class Chat:
             if stream and split_text:
                 raise ValueError("a streamed FLAC does not go with split_text (every split batch would end the stream)")
             FLAC.rate_code(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+        if adpcm:
+            if not pcm16:
+                raise ValueError("adpcm applies to 16-bit output: pass pcm16=True")
+            if encoding is not None:
+                raise ValueError("adpcm does not go with an encoding (an ADPCM file is coded from the 16-bit samples)")
+            if flac:
+                raise ValueError("adpcm does not go with flac (a call hands out one kind of file)")
+            if stream:
+                raise ValueError("adpcm applies to non-streamed inference only (a streamed ADPCM file would carry up to a block's "
+                                 "samples across chunks, which is not implemented)")
+            ADPCM.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+        akw = {"adpcm": True} if adpcm else {}
         skw = Plan.given("infer", speed=speed).kwargs()
         if stream and skw and not stream_time_scale:
             raise ValueError("speed applies to non-streamed inference only (a chunk's frames depend on the path of everything before it; "
@@ -1101,7 +1161,7 @@ class Chat:
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
                               sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}),
-                              **({} if split_host else lkw), **pkw, **smkw, **spkw)
+                              **({} if split_host else lkw), **pkw, **smkw, **spkw, **akw)
         if stream:
             return res_gen
         if refine_text_only:
@@ -1111,7 +1171,7 @@ class Chat:
             if rows:
                 return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}),
                                                   **({} if encoding is None else {"encoding": encoding}), **skw,
-                                                  **({"flac": True} if flac else {}), **lkw, **pkw)
+                                                  **({"flac": True} if flac else {}), **lkw, **pkw, **akw)
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
@@ -1123,6 +1183,8 @@ class Chat:
             one = float_to_int16(np.concatenate(stripped))
             if flac:      # a split request concatenated on the host: encoded by the host twin, like the conversion in front of it
                 return [np.frombuffer(FLAC.encode(one, sample_rate), np.uint8)]
+            if adpcm:
+                return [ADPCM.encode_result(one, sample_rate)]
             return [one if encoding is None else G711.encode(one, encoding)]
         return [np.concatenate(stripped)] if split_text else stripped
 
@@ -1140,7 +1202,8 @@ class Chat:
     def _infer(self, text, stream, lang, skip_refine_text, refine_text_only, use_decoder, do_text_normalization,
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
-               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None, pa_spec=None):
+               speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None, pa_spec=None,
+               adpcm: bool = False):
         """core.py:395-503 (generator).  `pa_spec` with `stream`: the rows' pause streams and their spec (Chat.infer's `stream_pauses`).  `lm_gain` with `stream`: the rows' limiter streams and their pre-gain (Chat.infer's `stream_limiter`).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -1172,7 +1235,7 @@ class Chat:
                                            **({} if pauses is None else {"pauses": pauses}),
                                            **({} if limiter is None else {"limiter": limiter}),
                                            **({} if lm is None else {"lm": lm, "lm_gain": lm_gain}),
-                                           **({} if pa is None else {"pa": pa, "pa_spec": pa_spec}))
+                                           **({} if pa is None else {"pa": pa, "pa_spec": pa_spec}), **({"adpcm": True} if adpcm else {}))
         finally:
             for h in pa or ():
                 self.codec.trim_pauses_stream_close(h)
@@ -1187,7 +1250,8 @@ class Chat:
                 self.codec.resample_stream_close(h)
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None, pa=None, pa_spec=None):
+                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None, pa=None, pa_spec=None,
+                       adpcm: bool = False):
         """the batch loop of `_infer`"""
         def flac_chunks(piece, final):
             """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' FLAC
@@ -1253,6 +1317,8 @@ class Chat:
                         rkw["speed"] = speed
                     if flac and pcm16:
                         rkw["flac"] = True
+                    if adpcm and pcm16:
+                        rkw["adpcm"] = True
                     if loudness is not None and not raw:
                         rkw["loudness"] = loudness
                     if limiter is not None and not raw:

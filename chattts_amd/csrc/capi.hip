@@ -2455,6 +2455,72 @@ extern "C" int ctts_flac_encode_ranges(const int16_t* pcm, const int64_t* counts
                         (FlacFrame*)(meta + s[0] + 1 + n_rng), (hipStream_t)stream));
   return 0;
 }
+static_assert(sizeof(ctts_adpcm_range) == 48 && sizeof(AdpcmRange) == 48 && offsetof(ctts_adpcm_range, block0) == offsetof(AdpcmRange, block0) &&
+              offsetof(ctts_adpcm_range, byte0) == offsetof(AdpcmRange, byte0) && offsetof(ctts_adpcm_range, rate) == offsetof(AdpcmRange, rate) &&
+              offsetof(ctts_adpcm_range, count_idx) == offsetof(AdpcmRange, count_idx), "ctts_adpcm_range layout");
+// the checks of a host table; sizes: the blocks, out bytes, the end of the last range (elements)
+static int adpcm_check_table(const char* who, const ctts_adpcm_range* rng_host, int32_t n_rng, long long sizes[3], bool* wants_counts) {
+  if (!rng_host) return fail("%s: a null pointer (the host range table is needed)", who);
+  if (n_rng < 1 || n_rng > 1024) return fail("%s: need 1 <= n_rng <= 1024 (got %d)", who, n_rng);
+  long long end = 0, blocks = 0, bytes = 0;
+  *wants_counts = false;
+  for (int i = 0; i < n_rng; ++i) {
+    const ctts_adpcm_range& r = rng_host[i];
+    if (r.rate < 0) return fail("%s: range %d: a rate of %d Hz (0 skips the range; else a positive rate)", who, i, r.rate);
+    if (r.start < 0 || (r.start & 7)) return fail("%s: range %d starts at element %lld: starts are multiples of 8", who, i, (long long)r.start);
+    if (r.n < 0) return fail("%s: range %d has a negative length (%lld)", who, i, (long long)r.n);
+    if (r.start >= (1ll << 46) || r.n >= (1ll << 31)) return fail("%s: range %d lies beyond what a launch can address (n < 2^31)", who, i);
+    if (r.start < end) return fail("%s: range %d starts at element %lld, before the end %lld of the ranges in front of it (overlapping or descending)", who,
+                                   i, (long long)r.start, end);
+    if (r.count_idx < -1 || r.count_idx > 65535) return fail("%s: range %d: count_idx %d is neither -1 nor in 0 .. 65535", who, i, r.count_idx);
+    end = r.start + r.n;
+    if (r.block0 != blocks) return fail("%s: range %d: block0 is %lld, the ranges in front of it own %lld blocks", who, i, (long long)r.block0, blocks);
+    if (r.byte0 != bytes) return fail("%s: range %d: byte0 is %lld, the ranges in front of it own %lld bytes", who, i, (long long)r.byte0, bytes);
+    if (r.rate == 0) continue;
+    if (r.count_idx >= 0) *wants_counts = true;
+    const long long align = 256ll * std::max(1, r.rate / 11025), S = 2 * (align - 4) + 1, nb = (r.n + S - 1) / S;
+    blocks += nb;
+    bytes += nb * align;
+  }
+  if (blocks >= (1ll << 31)) return fail("%s: the ranges own %lld blocks, a launch takes fewer than 2^31", who, blocks);
+  sizes[0] = blocks;
+  sizes[1] = bytes;
+  sizes[2] = end;
+  return 0;
+}
+extern "C" int ctts_adpcm_encode_sizes(const ctts_adpcm_range* rng_host, int32_t n_rng, int64_t* sizes) {
+  const char* who = "ctts_adpcm_encode_sizes";
+  if (!sizes) return fail("%s: a null pointer (sizes[3] is needed)", who);
+  long long s[3];
+  bool wants_counts;
+  if (adpcm_check_table(who, rng_host, n_rng, s, &wants_counts)) return -1;
+  sizes[0] = s[0];
+  sizes[1] = s[1];
+  sizes[2] = (8ll * n_rng + 15) / 16 * 16;
+  return 0;
+}
+extern "C" int ctts_adpcm_encode_ranges(const int16_t* pcm, const int64_t* counts, const ctts_adpcm_range* rng_dev, const ctts_adpcm_range* rng_host,
+                                        int32_t n_rng, uint8_t* out, size_t out_bytes, int64_t* used, size_t used_bytes, void* stream) {
+  const char* who = "ctts_adpcm_encode_ranges";
+  if (!pcm || !out || !rng_dev || !rng_host || !used) return fail("%s: a null pointer (pcm, out, used and both range tables are needed)", who);
+  long long s[3];
+  bool wants_counts;
+  if (adpcm_check_table(who, rng_host, n_rng, s, &wants_counts)) return -1;
+  if (wants_counts && !counts) return fail("%s: a null pointer (a range has a count_idx, so counts is needed)", who);
+  if (((uintptr_t)pcm & 15) || ((uintptr_t)out & 15) || ((uintptr_t)rng_dev & 7) || ((uintptr_t)used & 7) || ((uintptr_t)counts & 7))
+    return fail("%s: pcm and out must be 16-byte aligned, counts, used and the device table 8-byte aligned", who);
+  if ((long long)out_bytes < s[1] || out_bytes >= (1ull << 62))
+    return fail("%s: out holds %zu bytes, the ranges own %lld (out of capacity)", who, out_bytes, s[1]);
+  if (used_bytes < 8 * (size_t)n_rng || used_bytes >= (1ull << 62))
+    return fail("%s: used holds %zu bytes, %d are needed (out of capacity)", who, used_bytes, 8 * n_rng);
+  const uintptr_t p0 = (uintptr_t)pcm, o0 = (uintptr_t)out;
+  if (p0 == o0 || (p0 < o0 + (uintptr_t)out_bytes && o0 < p0 + 2 * (uintptr_t)s[2]))
+    return fail("%s: out aliases pcm (the encoding is not in place)", who);
+  if (s[0] == 0) return 0;                       // nothing but skipped or empty ranges
+  CttsDeviceGuard dg(stream);
+  CK(launch_adpcm_encode(pcm, (const long long*)counts, (const AdpcmRange*)rng_dev, n_rng, s[0], out, (long long*)used, (hipStream_t)stream));
+  return 0;
+}
 static_assert(sizeof(ctts_flac_push) == 64 && sizeof(FlacPush) == 64 && offsetof(ctts_flac_push, sample) == offsetof(FlacPush, sample) &&
               offsetof(ctts_flac_push, stage) == offsetof(FlacPush, stage) && offsetof(ctts_flac_push, frame0) == offsetof(FlacPush, frame0) &&
               offsetof(ctts_flac_push, rate) == offsetof(FlacPush, rate) && offsetof(ctts_flac_push, slot) == offsetof(FlacPush, slot) &&

@@ -694,6 +694,23 @@ hipError_t launch_flac_stream(const int16_t* pcm, const uint8_t* mask, const lon
                               int16_t* state, long long frames_max, long long n_frames, uint8_t* out, long long* meta, long long* staged,
                               long long* base, FlacRange* rng, FlacFrame* rec, int16_t* stage, hipStream_t st);
 
+// ---- IMA ADPCM encoding (adpcm.hip) ----------------------------------------------------------------
+#define ADPCM_LANES 64        // blocks per workgroup: one lane each
+// ctts_adpcm_range (include/chattts_amd.h), field for field (capi.hip asserts the layout): elements [start, start + n) of the int16 input
+// are one signal at `rate` Hz (0: the range is skipped); count_idx >= 0: its length is min(counts[count_idx], n), read on the device;
+// with align = 256 * max(1, rate / 11025) and S = 2 * (align - 4) + 1 the range owns the blocks [block0, block0 + ceil(n / S)) of the
+// call and the bytes [byte0, byte0 + align * ceil(n / S)) of the output
+struct AdpcmRange {
+  long long start, n;
+  long long block0, byte0;
+  int32_t rate, count_idx;
+  long long reserved;
+};
+// one launch for all ranges; used: int64 [n_rng], each range's signal length as the device took it; n_blocks: the blocks all ranges own.
+// Every bound is the caller's to check
+hipError_t launch_adpcm_encode(const int16_t* pcm, const long long* counts, const AdpcmRange* rng, int n_rng, long long n_blocks, uint8_t* out,
+                               long long* used, hipStream_t st);
+
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------
 // |STFT| of one waveform: center=True reflect padding, frame f = padded[256 f, 256 f + 1024) * window, 1024-point FFT,
 // mag [F][516] (bins 0..512, then 3 zeros so that the mel projection's K is a multiple of 4)

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import adpcm as ADPCM
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
@@ -3187,6 +3188,90 @@ class CodecEngine:
             frames = blob[int(offs[0]): int(offs[-1])]
             res.append((frames, lens[lens > 0], int(meta[n_frames + 1 + k])) if info else frames)
         return res
+
+    def adpcm_encode(self, pcm: torch.Tensor, ranges, counts: Optional[torch.Tensor] = None, info: bool = False) -> list:
+        """IMA ADPCM on the device (ctts_adpcm_encode_ranges, csrc/adpcm.hip): `pcm`, a contiguous int16 device tensor, taken as flat;
+        `ranges`: up to 1024 (start, n, rate) or (start, n, rate, count_idx) in ascending order -- elements [start, start + n) are one
+        signal at `rate` Hz (None / 0: the range is skipped); with a count_idx the signal's length is min(counts[count_idx], n), read on
+        the device (`counts`: an int64 device tensor, e.g. float_to_int16_groups' count header).  Starts are multiples of 8.  Returns
+        one uint8 array per range, its blocks back to back (`adpcm.encode_blocks` byte for byte; empty for a signal of no samples, None
+        for a skipped range); `info`: (blocks, samples) instead -- what `adpcm.wav_bytes` needs.  One launch whatever the number of
+        ranges, then one small copy (the sample counts) when a range leaves its length to the device, and one copy of the blocks: the
+        4-bit codes are what cross the bus.  The library refuses bad tables before anything is launched (EngineError)."""
+        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()):
+            raise ValueError("adpcm_encode: a contiguous int16 device tensor")
+        if counts is not None and not (counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()):
+            raise ValueError("adpcm_encode: `counts` must be a contiguous int64 device tensor")
+        n_el, n_rng = pcm.numel(), len(ranges)
+        tab = np.zeros(n_rng, _lib.ADPCM_RANGE)
+        blocks = nbytes = 0
+        for k, r in enumerate(ranges):
+            rate = int(r[2] or 0)
+            ci = int(r[3]) if len(r) > 3 and r[3] is not None else -1
+            if ci >= 0 and (counts is None or ci >= counts.numel()):
+                raise ValueError(f"adpcm_encode: range {k} reads count {ci}, beyond `counts`")
+            tab[k] = (int(r[0]), int(r[1]), blocks, nbytes, rate, ci, 0)
+            if rate > 0:
+                nb = ADPCM.n_blocks(int(r[1]), rate)
+                blocks, nbytes = blocks + nb, nbytes + nb * ADPCM.align(rate)
+        if n_rng and int((tab["start"] + np.maximum(tab["n"], 0)).max()) > n_el:
+            raise ValueError(f"adpcm_encode: a range ends beyond the {n_el} samples")
+        sizes = (C.c_int64 * 3)()
+        _lib.check(self.lib.ctts_adpcm_encode_sizes(tab.ctypes.data_as(C.c_void_p), n_rng, sizes), "ctts_adpcm_encode_sizes")
+        n_blocks, out_bytes, used_bytes = (int(v) for v in sizes)
+        empty = np.zeros((0,), np.uint8)
+        if n_blocks == 0:
+            return [None if not tab["rate"][k] else ((empty, 0) if info else empty) for k in range(n_rng)]
+        dev = pcm.device
+        buf = torch.empty((used_bytes + out_bytes,), dtype=torch.uint8, device=dev)      # the sample counts, then the blocks: one copy brings both
+        tab_d = torch.from_numpy(tab.view(np.uint8)).to(dev)
+        st = torch.cuda.current_stream(dev)
+        _lib.check(self.lib.ctts_adpcm_encode_ranges(pcm.data_ptr(), _lib.ptr(counts), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), n_rng,
+                                                     buf.data_ptr() + used_bytes, out_bytes, buf.data_ptr(), used_bytes, st.cuda_stream),
+                   "ctts_adpcm_encode_ranges")
+        tab_d.record_stream(st)
+        host = self.to_host(buf)
+        used, blob = host[: 8 * n_rng].view(np.int64), host[used_bytes:]
+        res = []
+        for k in range(n_rng):
+            rate = int(tab["rate"][k])
+            if not rate:
+                res.append(None)
+                continue
+            m = int(used[k])                                                             # the blocks behind ceil(m / S) were not written
+            b0 = int(tab["byte0"][k])
+            blk = blob[b0: b0 + ADPCM.n_blocks(m, rate) * ADPCM.align(rate)]
+            res.append((blk, m) if info else blk)
+        return res
+
+    def float_to_int16_groups_adpcm(self, wav: torch.Tensor, off, grp, rates, product: str = "f64", keep_thr: Optional[float] = 1e-5,
+                                    encodings=None) -> list:
+        """`float_to_int16_groups` with IMA ADPCM behind it, `float_to_int16_groups_flac`'s form: `rates`, one entry per group -- None:
+        the group comes back as `unpack_groups` hands it out (int16 samples, or with `encodings` its G.711 codes); a rate in Hz: as
+        the complete WAVE_FORMAT_IMA_ADPCM file (a uint8 array; `adpcm.encode` byte for byte) of exactly its int16 samples.  The
+        grouped slots and the count header on the device go straight into `adpcm_encode`; when every group is encoded the samples
+        never cross the bus.  A group has a rate or an encoding, not both.  A group of no samples comes back as the bare 60-byte header
+        (`adpcm.behind_decode`), as FLAC hands out a bare `fLaC` header there."""
+        n_grp = len(grp) - 1
+        if len(rates) != n_grp or (encodings is not None and len(encodings) != n_grp):
+            raise ValueError("float_to_int16_groups_adpcm: one rate (or None) and one encoding (or None) per group")
+        for g, r in enumerate(rates):
+            if r is not None:
+                ADPCM.check_rate(r)
+                if encodings is not None and encodings[g] is not None:
+                    raise ValueError("float_to_int16_groups_adpcm: a group is ADPCM or companded, not both")
+        if encodings is not None and all(G711.check_encoding(e) is None for e in encodings):
+            encodings = None
+        blob, starts = self.float_to_int16_groups(wav, off, grp, product, keep_thr, encodings=encodings)
+        if all(r is None for r in rates):
+            return self.unpack_groups(self.to_host(blob), starts, encodings)
+        hdr, E = (8 * n_grp + 15) // 16 * 16, int(starts[-1])
+        pcm_at, cnt_at = (hdr, 0) if encodings is None else (0, 2 * E)           # header | samples, or samples | header | codes
+        enc = self.adpcm_encode(blob[pcm_at: pcm_at + 2 * E].view(torch.int16),
+                                [(int(starts[g]), int(starts[g + 1] - starts[g]), rates[g], g) for g in range(n_grp)],
+                                counts=blob[cnt_at: cnt_at + 8 * n_grp].view(torch.int64), info=True)
+        plain = self.unpack_groups(self.to_host(blob), starts, encodings) if any(r is None for r in rates) else None
+        return [plain[g] if rates[g] is None else ADPCM.behind_decode(enc[g][0], enc[g][1], rates[g]) for g in range(n_grp)]
 
     # -- FLAC for streams: per-stream device state (csrc/flac.hip, flac_stage_k) ---------------------------------------------------------
     FLAC_STREAM_SLOTS = 64    # the state pool's first size; it doubles when every slot is taken

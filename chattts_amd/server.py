@@ -97,7 +97,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                batch_refine: bool = False, refine_params=None, batch_split: bool = False, sample_rates=None, voice_upload: bool = False,
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
                stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
-               pauses: bool = False, limiter: bool = False, stream_limiter: bool = False, stream_pauses: bool = False):
+               pauses: bool = False, limiter: bool = False, stream_limiter: bool = False, stream_pauses: bool = False,
+               adpcm: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -180,7 +181,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     state across chunks (chattts_amd/pauses.py: the schedule and the lags), from the pool where the batcher was built with
     `stream_pauses=True`, serially otherwise (Chat.infer(stream=True, pauses=, stream_pauses=True)); a spec that would make a stream
     hold more frames than a slot has gets a 400, chunks that come out empty are not written, and /health carries
-    `"stream_pauses": true`."""
+    `"stream_pauses": true`.  `adpcm=True` (default off: every response, status, warning and /health list is as without it):
+    `response_format` "adpcm" returns the request's 16-bit samples as a WAVE_FORMAT_IMA_ADPCM file (audio/wav; 4 bits per sample, mono:
+    half of G.711's size, chattts_amd/adpcm.py), encoded on the device behind the 16-bit conversion (Chat.infer(adpcm=True) /
+    SpeechBatcher.submit(adpcm=True)), at whatever rate, speed, loudness, pauses and limiter the other options allow; `"stream": true`
+    with it gets a 400 (a streamed file would carry up to a block's samples across chunks), an `"encoding"` key with it too.  With
+    `voice_upload`, mono IMA ADPCM WAV clips are accepted too (audio.load_wav(adpcm=True))."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -254,6 +260,9 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     if flac:
         from . import flac as FLAC
         formats = formats | {"flac"}
+    if adpcm:
+        from . import adpcm as ADPCM
+        formats = formats | {"adpcm"}
     if loudness:
         from . import loudness as LN
         allowed = allowed | {"loudness"}
@@ -290,7 +299,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                     stream_speed=12000, pass_first_n_batches=2)
 
     def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None,
-              as_flac: bool = False, lufs: Optional[float] = None, trim=None, lim: bool = False, gdb=None):     # openai_api.py:168-183,207-222
+              as_flac: bool = False, lufs: Optional[float] = None, trim=None, lim: bool = False, gdb=None,
+              as_adpcm: bool = False):                                              # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
         if lim:
             kw = {**kw, "limiter": True}
@@ -300,6 +310,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             kw = {**kw, "loudness": lufs}
         if as_flac:
             kw = {**kw, "flac": True}
+        if as_adpcm:
+            kw = {**kw, "adpcm": True}
         if spd is not None:
             kw = {**kw, "speed": spd}
         if law is not None:
@@ -442,13 +454,26 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 FLAC.rate_code(rate)
             except ValueError as e:
                 raise HTTPException(400, detail=str(e))
+        as_adpcm = bool(adpcm) and fmt == "adpcm"    # likewise
+        if as_adpcm:
+            if req.stream:
+                raise HTTPException(400, detail="adpcm is served for non-streamed requests only: a streamed ADPCM file would carry up to "
+                                                "a block's samples across chunks")
+            if request_data.get("encoding") is not None:
+                raise HTTPException(400, detail=f"encoding {request_data['encoding']} does not go with response_format adpcm (an ADPCM "
+                                                f"file is coded from the 16-bit samples)")
+            try:
+                ADPCM.check_rate(rate)
+            except ValueError as e:
+                raise HTTPException(400, detail=str(e))
+        akw = {"as_adpcm": True} if as_adpcm else {}
         media = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "ogg": "audio/ogg", "ulaw": "audio/PCMU", "alaw": "audio/PCMA",
-                 "flac": "audio/flac"}[fmt]
-        ekw = ({} if law is None else {"encoding": law}) if not as_flac else {"flac": True}
+                 "flac": "audio/flac", "adpcm": "audio/wav"}[fmt]
+        ekw = {"adpcm": True} if as_adpcm else ({} if law is None else {"encoding": law}) if not as_flac else {"flac": True}
         stream_header = wav_stream_header if law is None else (lambda r: g711_wav_stream_header(law, r))
 
         def encode(pcm: np.ndarray, header: bool) -> bytes:
-            if as_flac:
+            if as_flac or as_adpcm:
                 return np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype=np.uint8).tobytes()
             if law is not None:
                 codes = np.ascontiguousarray(np.asarray(pcm).reshape(-1), dtype=np.uint8)
@@ -526,11 +551,13 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             async with app.state.model_lock:
                 try:
                     if lim:
-                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, True)
+                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, True, **akw)
                     elif trim is not None:
-                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim)
+                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, **akw)
                     elif lufs is not None:
-                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs)
+                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, **akw)
+                    elif as_adpcm:
+                        wavs = await run_in_threadpool(infer, req, rate, None, spd, **akw)
                     elif as_flac:
                         wavs = await run_in_threadpool(infer, req, rate, None, spd, True)
                     else:
@@ -541,7 +568,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         if len(wavs) == 0:
             raise HTTPException(500, detail="Speech synthesis failed: the engine returned no audio")
         body = encode(wavs[0], header=True)                                           # openai_api.py:277-288
-        return Response(content=body, media_type=media, headers={"Content-Disposition": f"attachment; filename=output.{fmt}"})
+        return Response(content=body, media_type=media, headers={"Content-Disposition": f"attachment; filename=output.{'wav' if as_adpcm else fmt}"})
 
     if voice_upload:
         from .audio import load_wav
@@ -556,7 +583,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             if not name or name == "default":
                 raise HTTPException(400, detail='a voice needs a name other than "default"')
             try:
-                wav, clip_rate = load_wav(await request.body(), **({"g711": True} if g711 else {}))
+                wav, clip_rate = load_wav(await request.body(), **({"g711": True} if g711 else {}), **({"adpcm": True} if adpcm else {}))
             except ValueError as e:
                 raise HTTPException(400, detail=f"bad WAV upload: {e}")
             async with app.state.model_lock:

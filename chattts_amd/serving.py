@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import adpcm as ADPCM
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
@@ -666,6 +667,7 @@ class _Job:
     rs_slot: Optional[int] = None          # ... and at another rate: its stream of the resampler, opened with it
     flac: bool = False                     # the result is the FLAC file of the int16 waveform; a stream: its chunks are FLAC frames
     flac_slot: Optional[int] = None        # a FLAC stream: its stream of the encoder, opened at its first chunk
+    adpcm: bool = False                    # the result is the IMA ADPCM WAV file of the int16 waveform (non-streamed only)
     loudness: Optional[float] = None       # a target in LUFS (non-streamed only); None: the level is left alone
     pauses: object = None                  # a pauses.PauseSpec (non-streamed only); None: the silence is left alone
     limiter: bool = False                  # the look-ahead peak limiter behind the loudness stage's gain; a stream: in front of the conversion
@@ -714,12 +716,20 @@ def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding"
     at speed 1: the collaborator is then called exactly as it was before it knew rates, encodings and speeds (the host fakes pin that)."""
     kw = option_kw({rate_kw: [j.sample_rate for j in jobs], encoding_kw: [j.encoding for j in jobs], speed_kw: [j.speed for j in jobs],
                     "flac": [j.flac for j in jobs], "loudness": [j.loudness for j in jobs], "pauses": [j.pauses for j in jobs],
-                    "limiter": [j.limiter for j in jobs]})
+                    "limiter": [j.limiter for j in jobs], "adpcm": [j.adpcm for j in jobs]})
     if rate_kw in kw:
         kw[rate_kw] = [24000 if r is None else r for r in kw[rate_kw]]
     if speed_kw in kw:
         kw[speed_kw] = [1.0 if v is None else v for v in kw[speed_kw]]
     return kw
+
+
+def _file_parts(items: list) -> list:
+    """(job, ...) items of one poll -> the lists that are decoded together: one, unless the poll holds FLAC and ADPCM requests -- a
+    decode call hands out one kind of file, so the ADPCM requests then get a decode of their own"""
+    if any(it[0].adpcm for it in items) and any(it[0].flac for it in items):
+        return [[it for it in items if not it[0].adpcm], [it for it in items if it[0].adpcm]]
+    return [items]
 
 
 class SpeechBatcher:
@@ -805,6 +815,8 @@ class SpeechBatcher:
         self.stream_paused_chunks = 0      # chunks that came out of a pause stream (empty ones included)
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.flac_encoded = 0              # results handed out as FLAC files
+        self.adpcm_encoded = 0             # results handed out as IMA ADPCM WAV files
+        self.adpcm_asked = False           # some request has asked for one: only then does occupancy() carry the counter
         self.trimmed = 0                   # results handed out with their pauses trimmed
         self.max_stream_group = 0     # most chunks one window decode served
         self.cancelled = 0            # streams closed by their consumer before the end
@@ -851,7 +863,8 @@ class SpeechBatcher:
 
     # -- public -------------------------------------------------------------------------------------------------------------
     def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None,
-               encoding=None, speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False) -> Future:
+               encoding=None, speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False,
+               adpcm: bool = False) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
@@ -878,7 +891,12 @@ class SpeechBatcher:
         without a spec is copied through it; every sentence of a split request is trimmed alone).
         `limiter=True`: the serial call's `limiter=` -- the look-ahead peak limiter behind the loudness stage's gain, which then drops
         its ceiling term (at unity gain without `loudness`); requests that finish together, with and without it, still share the one
-        decode, and the ones without it are not touched by it (every sentence of a split request is limited alone)."""
+        decode, and the ones without it are not touched by it (every sentence of a split request is limited alone).
+        `adpcm=True`: the serial call's `adpcm=` -- the Future resolves to a uint8 array, the complete WAVE_FORMAT_IMA_ADPCM file
+        (4 bits per sample) of that int16 waveform at its rate; not together with `encoding` or `flac`.  Requests that finish
+        together, with and without it, still share the one decode; the encoder runs on the device behind the grouped conversion
+        (CodecEngine.adpcm_encode), in `finish` by the host twin; `occupancy()["adpcm_encoded"]` counts them from the first such request on.  A poll whose requests ask for FLAC and for ADPCM is decoded in two
+        groups, one per kind of file."""
         limiter = LM.check_flag(limiter, "submit")
         if limiter:
             LN.check_rate(24000 if sample_rate is None else sample_rate)
@@ -893,6 +911,13 @@ class SpeechBatcher:
             if encoding is not None:
                 raise ValueError("flac does not go with an encoding (a FLAC file holds the 16-bit samples)")
             FLAC.rate_code(24000 if sample_rate is None else sample_rate)
+        if adpcm:
+            if encoding is not None:
+                raise ValueError("adpcm does not go with an encoding (an ADPCM file is coded from the 16-bit samples)")
+            if flac:
+                raise ValueError("adpcm does not go with flac (a request is answered with one kind of file)")
+            ADPCM.check_rate(24000 if sample_rate is None else sample_rate)
+            self.adpcm_asked = True
         speed = _job_speed(speed)
         self._check_refine(refine)
         if split_text and int(max_split_batch) < 1:
@@ -900,7 +925,7 @@ class SpeechBatcher:
         fut: Future = Future()
         fut.rid = next(self._ids)
         self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding,
-                          speed=speed, flac=bool(flac), loudness=loudness, pauses=pauses, limiter=limiter))
+                          speed=speed, flac=bool(flac), loudness=loudness, pauses=pauses, limiter=limiter, adpcm=bool(adpcm)))
         return fut
 
     def cancel(self, fut: Future) -> None:
@@ -998,6 +1023,8 @@ class SpeechBatcher:
                "max_decode_group": self.max_decode_group, "companded": self.companded, "flac_encoded": self.flac_encoded,
                "trimmed": self.trimmed,
                "split": {"requests": self.split_requests, "sentences": self.split_sentences, "max_coresident": self.split_max_coresident}}
+        if self.adpcm_asked:  # (a batcher that was never asked for the format reports as it always did)
+            occ["adpcm_encoded"] = self.adpcm_encoded
         if self.streams:      # (list(): the worker changes the registry meanwhile)
             occ.update({"streams": sum(j.is_stream for j in list(self._jobs.values())), "stream_decode_calls": self.stream_decode_calls,
                         "stream_chunks": self.stream_chunks, "max_stream_group": self.max_stream_group, "cancelled": self.cancelled,
@@ -1052,6 +1079,7 @@ class SpeechBatcher:
         else:
             self.completed += 1
             self.flac_encoded += job.flac and not job.is_stream                  # (a stream's chunks are counted as they go out)
+            self.adpcm_encoded += job.adpcm
             self.trimmed += job.pauses is not None and not job.is_stream
             self.companded += not job.is_stream and job.encoding is not None      # (a stream's chunks are counted as they go out)
         if job.is_stream:
@@ -1231,13 +1259,14 @@ class SpeechBatcher:
         for job, hid in plain:
             if hid.shape[0] == 0:
                 self._resolve(job, RuntimeError(_NO_AUDIO))
-        try:
-            self._count_decode(len(live))
-            results = self.chat.decode_split_to_pcm16([g for _, g in live], **_format_kw([job for job, _ in live]))
-        except Exception as e:         # the decode failed: its requests fail, the worker goes on
-            results = [e] * len(live)
-        for (job, _), r in zip(live, results):
-            self._resolve(job, r)
+        for part in _file_parts(live):
+            try:
+                self._count_decode(len(part))
+                results = self.chat.decode_split_to_pcm16([g for _, g in part], **_format_kw([job for job, _ in part]))
+            except Exception as e:     # the decode failed: its requests fail, the worker goes on
+                results = [e] * len(part)
+            for (job, _), r in zip(part, results):
+                self._resolve(job, r)
 
     def _drain(self, block: bool) -> bool:
         """moves arrived requests into the pool; False once close() was called"""
@@ -1334,7 +1363,7 @@ class SpeechBatcher:
         self.lock.acquire()
 
     def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None, flac: bool = False, loudness=None,
-               pauses=None, limiter: bool = False) -> np.ndarray:
+               pauses=None, limiter: bool = False, adpcm: bool = False) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
@@ -1345,20 +1374,22 @@ class SpeechBatcher:
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
         if flac:                                                            # converted on the host, encoded by the host twin
             return np.frombuffer(FLAC.encode(pcm, 24000 if sample_rate is None else int(sample_rate)), np.uint8)
+        if adpcm:                                                           # likewise
+            return ADPCM.encode_result(pcm, 24000 if sample_rate is None else int(sample_rate))
         return pcm if encoding is None else G711.encode(pcm, encoding)      # converted on the host, companded by the host twin
 
     def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None, flac=None, loudness=None,
-                     pauses=None, limiter=None) -> list:
+                     pauses=None, limiter=None, adpcm=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
         returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000);
         `speeds`: one speed per request (None: 1.0); `loudness`: one target per request (None entries: left alone); `pauses`: one spec
-        per request (None entries: copied through the one `trim_pauses` call); `limiter`: one flag per request"""
+        per request (None entries: copied through the one `trim_pauses` call); `limiter`: one flag per request; `flac`, `adpcm`: one flag per request (no request has both)"""
         out: list = [RuntimeError(_NO_AUDIO) if h.shape[0] == 0 else None for h in hids]
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
             self._count_decode(len(live))
             kw = option_kw({"sample_rate": sample_rates, "encoding": encodings, "speed": speeds, "flac": flac, "loudness": loudness,
-                            "pauses": pauses, "limiter": limiter}, rows=live)
+                            "pauses": pauses, "limiter": limiter, "adpcm": adpcm}, rows=live)
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out
@@ -1434,12 +1465,13 @@ class SpeechBatcher:
         elif ready:                    # one decode for everything that finished at this poll
             self._finish_splits(ready, plain)
         elif plain:
-            try:
-                results = self.finish_group([hid for _, hid in plain], **_format_kw([job for job, _ in plain], "sample_rates", "encodings", "speeds"))
-            except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
-                results = [e] * len(plain)
-            for (job, _), r in zip(plain, results):
-                self._resolve(job, r)
+            for part in _file_parts(plain):
+                try:
+                    results = self.finish_group([hid for _, hid in part], **_format_kw([job for job, _ in part], "sample_rates", "encodings", "speeds"))
+                except Exception as e:     # the group's decode failed: its requests fail, the worker goes on
+                    results = [e] * len(part)
+                for (job, _), r in zip(part, results):
+                    self._resolve(job, r)
 
     def _loop2(self):
         """refine=True: ONE worker over the text pool and the code pool.  Every iteration: let other GPU users in and take arrived

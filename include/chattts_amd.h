@@ -793,6 +793,33 @@ int ctts_flac_encode_sizes(const ctts_flac_range* rng_host, int32_t n_rng, int64
 int ctts_flac_encode_ranges(const int16_t* pcm, const int64_t* counts, const ctts_flac_range* rng_dev, const ctts_flac_range* rng_host,
                             int32_t n_rng, uint8_t* out, size_t out_bytes, void* work, size_t work_bytes, void* stream);
 
+/* IMA/DVI ADPCM behind the PCM16 conversion: 16-bit mono PCM -> the 4-bit blocks of a WAVE_FORMAT_IMA_ADPCM (0x0011) file
+ * (chattts_amd/adpcm.py is the NumPy twin, byte for byte, and states the step and the tables).  align = 256 * max(1, rate / 11025) bytes
+ * per block, S = 2 * (align - 4) + 1 samples: bytes 0-1 the block's first sample (little-endian), byte 2 its start index -- the least i
+ * with STEP[i] >= |x[1] - x[0]|, 88 when there is none -- byte 3 zero, byte 4 + j the code of sample 1 + 2j in bits 0-3 and of sample
+ * 2 + 2j in bits 4-7.  A block's bytes depend on its own samples only; the kernel runs one lane per block.
+ * Table-driven: range r says that elements [start, start + n) of `pcm` are one signal at `rate` Hz (0: the range is skipped).  With
+ * count_idx >= 0 its length m is min(counts[count_idx], n), read on the device (ctts_float_to_int16_groups' kept counts), else n.  The
+ * range owns the blocks [block0, block0 + ceil(n / S)) and the bytes of `out` from byte0 on, both the running sums over the ranges in
+ * front of it (skipped ranges own none).  It writes ceil(m / S) whole blocks -- positions at or beyond m read as x[m - 1]; m = 0: none --
+ * and nothing else; `used` (int64 [n_rng] on the device) receives m for every range (0 for a skipped one).  One launch
+ * (adpcm_encode_k) whatever the number of ranges.  ctts_adpcm_encode_sizes checks a host table and gives sizes[3] = {the blocks, the
+ * bytes `out` must hold, the bytes `used` must hold}.  Refused on the host table before anything is launched: a null pointer (counts may
+ * be null when no range has a count_idx), n_rng < 1 or > 1024, a start that is negative or no multiple of 8, n negative or >= 2^31,
+ * ranges that overlap or descend, a negative rate, a count_idx < -1 or > 65535, a block0 or byte0 that is not the running sum, 2^31
+ * blocks or more, pointers that are not 16-byte aligned (counts, used: 8), out or used out of capacity, out aliasing pcm. */
+typedef struct {
+  int64_t start, n;       /* elements of pcm */
+  int64_t block0;         /* the range's first block of the call */
+  int64_t byte0;          /* its first byte of out */
+  int32_t rate;           /* Hz; 0: the range is skipped */
+  int32_t count_idx;      /* index into counts, or -1 */
+  int64_t reserved;
+} ctts_adpcm_range;       /* 48 bytes */
+int ctts_adpcm_encode_sizes(const ctts_adpcm_range* rng_host, int32_t n_rng, int64_t* sizes);
+int ctts_adpcm_encode_ranges(const int16_t* pcm, const int64_t* counts, const ctts_adpcm_range* rng_dev, const ctts_adpcm_range* rng_host,
+                             int32_t n_rng, uint8_t* out, size_t out_bytes, int64_t* used, size_t used_bytes, void* stream);
+
 /* FLAC for STREAMS: the signal arrives in pushes and leaves as variable-block-size frames (sync FF F9) whose header carries the number of
  * the block's first sample, in up to 36 bits (1 .. 7 bytes).  chattts_amd/flac.py (StreamEncoder) is the NumPy twin, byte for byte; the
  * subframes and their exact search are those above.  The cutting rule: a stream holds `carry` samples (0 .. 15) from its last push in its
