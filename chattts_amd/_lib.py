@@ -72,6 +72,11 @@ FLAC_PUSH = np.dtype([("start", "<i8"), ("n", "<i8"), ("sample", "<i8"), ("stage
                       ("slot", "<i4"), ("carry", "<i4"), ("flags", "<i4"), ("count_idx", "<i4"), ("reserved", "<i4")])
 
 
+# ctts_adpcm_push (64 bytes): start, n, stage, block0, byte0 int64; rate, slot, carry, flags (1 final, 2 keep mask), count_idx, reserved int32
+ADPCM_PUSH = np.dtype([("start", "<i8"), ("n", "<i8"), ("stage", "<i8"), ("block0", "<i8"), ("byte0", "<i8"), ("rate", "<i4"),
+                       ("slot", "<i4"), ("carry", "<i4"), ("flags", "<i4"), ("count_idx", "<i4"), ("reserved", "<i4")])
+
+
 # ctts_ts_stream (80 bytes): in_off, n_in, pos, total, out_off, path_off int64; k_prev, k_now, slot, phase, num, den, n_out, reserved int32
 TS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("out_off", "<i8"), ("path_off", "<i8"),
                       ("k_prev", "<i4"), ("k_now", "<i4"), ("slot", "<i4"), ("phase", "<i4"), ("num", "<i4"), ("den", "<i4"),
@@ -215,6 +220,8 @@ SIGNATURES = {
     "ctts_adpcm_encode_ranges": (C.c_int, [P, P, P, P, I32, P, SZ, P, SZ, P]),
     "ctts_flac_stream_sizes": (C.c_int, [P, I32, I32, C.c_int64, P]),
     "ctts_flac_stream_step": (C.c_int, [P, C.c_int64, P, P, P, P, I32, P, I32, P, SZ, P, SZ, P]),
+    "ctts_adpcm_stream_sizes": (C.c_int, [P, I32, I32, C.c_int64, P]),
+    "ctts_adpcm_stream_step": (C.c_int, [P, C.c_int64, P, P, P, P, I32, P, I32, P, SZ, P, SZ, P]),
     "ctts_dvae_create": (C.c_int, [PP, C.POINTER(DvaeWeights)]),
     "ctts_dvae_destroy": (None, [P]),
     "ctts_dvae_code_frames": (I32, [I32]),

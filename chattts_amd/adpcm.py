@@ -20,7 +20,18 @@ which is what makes every block of every signal independent work on the device. 
 choice is a legal one; it is the one place where this encoder differs from a chain carried through the whole signal.
 
 The device encodes whole results; this form serves the odd pieces that are converted on the host (SpeechBatcher.finish, a split request
-concatenated on the host), `audio.load_wav(adpcm=True)` and the tests."""
+concatenated on the host), `audio.load_wav(adpcm=True)` and the tests.
+
+Streams (`stream_plan`, `StreamEncoder`; on the device `CodecEngine.adpcm_stream_step`, csrc/adpcm.hip adpcm_stage_k): because a block's
+bytes depend on its own S samples and the rate only, a stream cut anywhere emits the bytes of the one-shot encoder as long as only whole
+blocks leave and the rest waits.  A stream holds `carry` samples (0 .. S - 1) of its earlier pushes; a push of n samples makes
+avail = carry + n.  Not final: avail // S blocks leave, from the front, and avail % S samples are held.  Final: ceil(avail / S) blocks
+leave, the last one padded as the one-shot encoder pads (positions beyond the end read as the last sample), and none are held; a final
+push with avail = 0 emits nothing.  The pushes of a stream, concatenated, are `encode_blocks` of its samples, however they were cut.  A
+stream's blocks are at most S - 1 samples behind its PCM: 63 ms at 8 kHz, 31.5 ms at 16 kHz, 42.3 ms at 24 kHz, 42.5 ms at 48 kHz.
+`stream_header` is the header of a file whose length is not known yet (0xFFFFFFFF in the RIFF, `fact` and `data` lengths); `parse_wav`
+reads such a file as every whole block that follows.  The consequence: a receiver of an open-ended stream cannot know the true length --
+behind the last real sample it decodes up to S - 1 padded samples, which hold the last value (as closely as the coder follows it)."""
 from __future__ import annotations
 
 import struct
@@ -164,6 +175,55 @@ def wav_header(n, rate, bare: bool = False) -> bytes:
             + b"fact" + struct.pack("<II", 4, n) + b"data" + struct.pack("<I", data))
 
 
+def stream_header(rate) -> bytes:
+    """the 60 bytes in front of a stream's blocks: `wav_header` with 0xFFFFFFFF in the RIFF, `fact` and `data` lengths (the convention of
+    the server's streamed PCM and G.711 headers).  `parse_wav` reads every whole block that follows: up to S - 1 samples more than the
+    stream held, all of them coding the last value."""
+    h = bytearray(wav_header(1, rate))
+    for at in (4, 48, 56):
+        h[at: at + 4] = b"\xFF\xFF\xFF\xFF"
+    return bytes(h)
+
+
+def stream_plan(carry, n, final, rate):
+    """the cutting rule: a stream at `rate` that holds `carry` samples gets n more -> (blocks emitted, samples held afterwards)"""
+    S = samples_per_block(rate)
+    carry, n = int(carry), int(n)
+    if not 0 <= carry < S or n < 0:
+        raise ValueError(f"adpcm: a stream at {rate} Hz carries 0 .. {S - 1} samples and a push has 0 or more (got {carry}, {n})")
+    avail = carry + n
+    return ((avail + S - 1) // S, 0) if final else (avail // S, avail % S)
+
+
+def stream_bound(n, rate) -> int:
+    """the most bytes a push of n samples can emit: a final push onto a carry of S - 1"""
+    S = samples_per_block(rate)
+    return (S - 1 + max(int(n), 0) + S - 1) // S * align(rate)
+
+
+class StreamEncoder:
+    """The NumPy twin of `CodecEngine.adpcm_stream_step` for one stream: `push(x, final)` -> the blocks that push completes (a uint8
+    array, possibly empty).  The concatenated pushes are `encode_blocks` of the concatenated samples."""
+
+    def __init__(self, rate):
+        self.rate = check_rate(rate)
+        self.S = samples_per_block(rate)
+        self.held = np.zeros((0,), np.int16)
+        self.done = False
+
+    def push(self, x, final: bool = False) -> np.ndarray:
+        x = _pcm(x)
+        if self.done:
+            raise ValueError("adpcm: the stream has had its last push")
+        blocks, held = stream_plan(len(self.held), len(x), final, self.rate)
+        buf = np.concatenate([self.held, x])
+        self.held = buf[len(buf) - held:].copy() if held else np.zeros((0,), np.int16)
+        self.done = bool(final)
+        if not blocks:
+            return np.zeros((0,), np.uint8)
+        return encode_blocks(buf[: len(buf) - held], self.rate)
+
+
 def wav_bytes(blocks, n, rate) -> np.ndarray:
     """the complete file around blocks that are already encoded (the device's): a uint8 array"""
     blocks = np.asarray(blocks)
@@ -198,7 +258,8 @@ def encode(pcm, rate) -> bytes:
 def parse_wav(data):
     """a mono WAVE_FORMAT_IMA_ADPCM file -> (int16 samples, rate), or None when the bytes are no RIFF/WAVE with that tag.  Another channel
     count, a `fmt ` chunk that disagrees with its block size (4 bits, samples per block 2 * (align - 4) + 1), no whole block, a `fact`
-    count beyond the blocks: ValueError.  Any block size of 5 bytes or more is read (files of other encoders), not only `align(rate)`."""
+    count beyond the blocks: ValueError -- but a `fact` of 0xFFFFFFFF (`stream_header`: an open-ended file) is read as every whole block
+    that follows, the `data` chunk's 0xFFFFFFFF being cut to the bytes that are there.  Any block size of 5 bytes or more is read (files of other encoders), not only `align(rate)`."""
     data = bytes(data)
     if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
         return None
@@ -225,7 +286,7 @@ def parse_wav(data):
                          f"(4 bits and {2 * (A - 4) + 1} samples per block are expected)")
     S = extra[1]
     nb = len(body or b"") // A
-    n = nb * S if fact is None else int(fact)
+    n = nb * S if fact is None or fact == 0xFFFFFFFF else int(fact)
     if nb == 0 or n == 0:
         raise ValueError("the WAV file holds no samples")
     if n > nb * S:

@@ -593,7 +593,7 @@ class Chat:
 
     def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None,
                              rs_streams=None, flac=None, flac_streams=None, limiter=None, lm_streams=None, pauses=None,
-                             pa_streams=None) -> List[np.ndarray]:
+                             pa_streams=None, adpcm=None, adpcm_streams=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
         (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream).  `encodings`: one per window, None / "ulaw" / "alaw" -- a
@@ -605,7 +605,9 @@ class Chat:
         samples are pushed into that stream and the piece is uint8, the frames the push completes
         (CodecEngine.decode_windows(flac=)); `limiter` with `lm_streams` (one flag and one entry per window; a flagged window with the
         handle of its limiter stream): the window's float samples are pushed into that stream and the piece is what the step emits,
-        converted (CodecEngine.decode_windows(limiter=)); without them today's call, argument for argument"""
+        converted (CodecEngine.decode_windows(limiter=)); `adpcm` with `adpcm_streams`: as `flac` / `flac_streams`, with the handle of
+        the window's IMA ADPCM stream -- the piece is the blocks the push completes (CodecEngine.decode_windows(adpcm=)); without
+        them today's call, argument for argument"""
         kw = {k: v for k, v in (("sample_rates", sample_rates), ("encodings", encodings), ("speeds", speeds)) if v is not None}
         if speeds is not None:
             kw["ts_streams"] = ts_streams
@@ -613,6 +615,8 @@ class Chat:
                 kw["rs_streams"] = rs_streams
         if flac is not None:
             kw["flac"], kw["flac_streams"] = flac, flac_streams
+        if adpcm is not None:
+            kw["adpcm"], kw["adpcm_streams"] = adpcm, adpcm_streams
         if limiter is not None:
             kw["limiter"], kw["lm_streams"] = limiter, lm_streams
         if pauses is not None:          # a flagged window goes through its pause stream in front of all that (CodecEngine.decode_windows(pauses=))
@@ -739,13 +743,13 @@ class Chat:
         return self._finish_piece(y.view(B, int(off[1])), final, pcm16, encoding, on_device)
 
     def _stream_rows_paused(self, hiddens, a: int, b: Optional[int], final: bool, pa_handles, rate: Optional[int] = None, ts_handles=None,
-                            rs_handles=None, lm_handles=None, pcm16: bool = False, encoding=None, fs_handles=None) -> list:
+                            rs_handles=None, lm_handles=None, pcm16: bool = False, encoding=None, fs_handles=None, fs_step=None) -> list:
         """One chunk of a PAUSED stream (Chat.infer's `stream_pauses`): samples [a, b) of the decode of the current prefix go through
         the rows' float stages as in `_stream_piece` / `_stream_piece_scaled` (the resampled window at `rate`, or the time scaler's
         streams `ts_handles` and behind them the resampler's `rs_handles`), then into the rows' pause streams `pa_handles`
         (CodecEngine.trim_pauses_stream_step, all rows in one step) -- the one-shot chain's order: behind the last float stage, in front
         of the limiter streams `lm_handles`, the 16-bit conversion (one peak per row over the samples that come out), G.711 and the
-        FLAC streams `fs_handles`.  The rows emit different numbers of samples, so the chunk is a list with one array per row,
+        FLAC streams `fs_handles` (`fs_step`: another format's step in place of `flac_stream_step`, the ADPCM streams').  The rows emit different numbers of samples, so the chunk is a list with one array per row,
         possibly empty.  `final`: the streams' last push; every row's own samples with |x| <= 1e-5 are removed (the reference's tail
         filter, core.py:500-503, read for one row) and the rest is converted on the host, as a limited stream's last chunk is."""
         codec, B = self.codec, len(hiddens)
@@ -800,7 +804,7 @@ class Chat:
             for i in range(B):
                 if n[i]:
                     buf[int(start[i]): int(start[i]) + int(n[i])] = pcm[int(off[i]): int(off[i + 1])]
-            return codec.flac_stream_step(buf, [(h, int(start[i]), int(n[i]), final) for i, h in enumerate(fs_handles)])
+            return (fs_step or codec.flac_stream_step)(buf, [(h, int(start[i]), int(n[i]), final) for i, h in enumerate(fs_handles)])
         host = codec.to_host(pcm)
         rows = [host[off[i]: off[i + 1]] for i in range(B)]
         return rows if encoding is None else [G711.encode(r, encoding) if r.size else r.astype(np.uint8) for r in rows]
@@ -944,7 +948,7 @@ class Chat:
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
               flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None,
-              stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False, adpcm: bool = False):
+              stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False, adpcm: bool = False, stream_adpcm: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -1042,7 +1046,15 @@ class Chat:
         per sample, blocks of 256 / 512 / 1024 bytes by `sample_rate`) of exactly the int16 samples the same call returns without it
         -- half of G.711's size, encoded on the device behind the conversion (CodecEngine.adpcm_encode), at whatever rate, speed,
         pauses, loudness and limiter the call has.  A split request is one file over its concatenated sentences.  A streamed call
-        raises: a stream would have to carry up to a block's samples across chunks."""
+        raises unless `stream_adpcm=True` (keyword-only): then every row of the batch gets an ADPCM stream at the output rate (opened at
+        the first chunk, closed with the generator) and every yield is a list with one uint8 array per row: the whole blocks that
+        chunk completes, possibly none -- a stream keeps up to S - 1 samples of an open block (chattts_amd/adpcm.py, StreamEncoder),
+        and the last chunk brings them, padded as the file's last block is.  The chunks of a row, concatenated, are
+        `adpcm.encode_blocks` of the int16 chunks the call yields without `adpcm`, concatenated; behind `adpcm.stream_header(rate)`
+        they are an open-ended WAV file, whose reader cannot know the true length and decodes up to S - 1 padded samples behind the
+        last real one.  The chunks are pushed on the device (CodecEngine.adpcm_stream_step; the placement and the host-twin
+        fallback of a streamed FLAC), behind whatever `sample_rate` + `stream_resample`, `speed` + `stream_time_scale`, `limiter` +
+        `stream_limiter` and `pauses` + `stream_pauses` make of the stream.  Not with `split_text`, nor with `use_decoder=False`."""
         mkw = Plan.given("infer", limiter=limiter).kwargs()
         if gain_db is not None and np.ndim(gain_db) != 0:
             raise ValueError("gain_db is one make-up gain for the whole batch")
@@ -1112,10 +1124,17 @@ class Chat:
                 raise ValueError("adpcm does not go with an encoding (an ADPCM file is coded from the 16-bit samples)")
             if flac:
                 raise ValueError("adpcm does not go with flac (a call hands out one kind of file)")
-            if stream:
+            if stream and not stream_adpcm:
                 raise ValueError("adpcm applies to non-streamed inference only (a streamed ADPCM file would carry up to a block's "
                                  "samples across chunks, which is not implemented)")
+            if stream and split_text:
+                raise ValueError("a streamed ADPCM file does not go with split_text (every split batch would end the stream)")
+            if stream and not use_decoder:
+                raise ValueError("a streamed ADPCM file needs the hidden-state decoder (use_decoder=True)")
             ADPCM.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+            if stream and ADPCM.samples_per_block(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)) - 1 > CodecEngine.ADPCM_CARRY:
+                raise ValueError(f"a streamed ADPCM file at {int(sample_rate)} Hz would carry more than a stream keeps ({CodecEngine.ADPCM_CARRY} "
+                                 "samples): streams run below 55125 Hz")
         akw = {"adpcm": True} if adpcm else {}
         skw = Plan.given("infer", speed=speed).kwargs()
         if stream and skw and not stream_time_scale:
@@ -1225,7 +1244,7 @@ class Chat:
         step = max_split_batch if split_text else len(text)
         ts = [] if stream and speed is not None else None      # a streamed speed: the rows' streams of the time scaler, opened at the first chunk
         rs = [] if ts is not None and sample_rate is not None else None      # ... at another rate: and their streams of the resampler
-        fs = [] if stream and flac and pcm16 else None         # a streamed FLAC: the rows' FLAC streams, opened at the first chunk
+        fs = [] if stream and (flac or adpcm) and pcm16 else None      # a streamed FLAC / ADPCM file: the rows' encoder streams, opened at the first chunk
         lm = [] if stream and lm_gain is not None else None    # a limited stream: the rows' limiter streams, opened at the first chunk
         pa = [] if stream and pa_spec is not None else None    # a paused stream: the rows' pause streams, opened at the first chunk
         try:
@@ -1242,8 +1261,8 @@ class Chat:
             for h in lm or ():
                 self.codec.peak_limit_stream_close(h)
             for h in fs or ():
-                if not isinstance(h, FLAC.StreamEncoder):
-                    self.codec.flac_stream_close(h)
+                if not isinstance(h, (FLAC.StreamEncoder, ADPCM.StreamEncoder)):
+                    (self.codec.adpcm_stream_close if adpcm else self.codec.flac_stream_close)(h)
             for h in ts or ():                                 # also when the consumer drops the generator half way
                 self.codec.time_scale_stream_close(h)
             for h in rs or ():
@@ -1253,16 +1272,20 @@ class Chat:
                        rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None, pa=None, pa_spec=None,
                        adpcm: bool = False):
         """the batch loop of `_infer`"""
+        # the rows' encoder streams `fs` are FLAC streams, or with `adpcm` IMA ADPCM streams: the same placement, the same host twin
+        Twin = ADPCM.StreamEncoder if adpcm else FLAC.StreamEncoder
+        fs_open = lambda rate: (self.codec.adpcm_stream_open if adpcm else self.codec.flac_stream_open)(rate)
+        fs_step = lambda pcm, pushes: (self.codec.adpcm_stream_step if adpcm else self.codec.flac_stream_step)(pcm, pushes)
         def flac_chunks(piece, final):
-            """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' FLAC
+            """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' encoder
             streams `fs` -> one uint8 array per row"""
             B = int(piece.shape[0])
             if not fs:             # opened at the first chunk: on the device, or the host twin where every chunk is converted on the host
                 rate = CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate
                 on_device = use_decoder and self.incremental_stream
-                fs.extend(self.codec.flac_stream_open(rate) if on_device else FLAC.StreamEncoder(rate) for _ in range(B))
+                fs.extend(fs_open(rate) if on_device else Twin(rate) for _ in range(B))
             n = int(piece.shape[1])
-            if isinstance(fs[0], FLAC.StreamEncoder):
+            if isinstance(fs[0], Twin):
                 piece = np.asarray(piece).astype(np.int16, copy=False)
                 return [np.frombuffer(e.push(np.ascontiguousarray(r), final), np.uint8) for e, r in zip(fs, piece)]
             if not isinstance(piece, torch.Tensor):
@@ -1275,7 +1298,7 @@ class Chat:
             piece = piece.contiguous()
             if piece.data_ptr() % 16:          # a view into the conversion's buffer: the encoder reads 16-byte units
                 piece = piece.clone()
-            return self.codec.flac_stream_step(piece.view(-1), [(h, i * row, n, final) for i, h in enumerate(fs)])
+            return fs_step(piece.view(-1), [(h, i * row, n, final) for i, h in enumerate(fs)])
         dkw = {} if fs is None else {"on_device": True}
         def open_streams(rows):
             ts.extend(self.codec.time_scale_stream_open(speed) for _ in rows)
@@ -1297,9 +1320,9 @@ class Chat:
             if ts is not None and not ts:
                 open_streams(rows)
             if fs is not None and not fs:
-                fs.extend(self.codec.flac_stream_open(out_rate) for _ in rows)
+                fs.extend(fs_open(out_rate) for _ in rows)
             return self._stream_rows_paused(rows, a, b, final, pa, sample_rate, ts, rs, limited(rows).get("lm_handles"), pcm16,
-                                            encoding if pcm16 else None, fs)
+                                            encoding if pcm16 else None, fs, **({"fs_step": fs_step} if adpcm else {}))
         length = 0
         pass_batch_count = 0
         for lo in range(0, len(text), step):

@@ -17,6 +17,8 @@
 // units (byte0 is a multiple of 256: always aligned, always wholly the block's).  Row strides in LDS are odd numbers of words.  The
 // step table lives in LDS (a lane's index is its own); the step itself is compares and selects.  Nothing outside a range's written
 // blocks is written.  Plain vector stores only.  Positions are 64-bit.
+// Streams (ctts_adpcm_stream_step, the end of this file): adpcm_stage_k in front of the same adpcm_encode_k, which then runs over the
+// staging ranges and takes each range's length from the count that adpcm_stage_k wrote.
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -184,4 +186,113 @@ hipError_t launch_adpcm_encode(const int16_t* pcm, const long long* counts, cons
   hipLaunchKernelGGL(adpcm_encode_k, dim3((unsigned)((n_blocks + ADPCM_LANES - 1) / ADPCM_LANES)), dim3(ADPCM_LANES), 0, st, pcm, counts, rng,
                      n_rng, n_blocks, out, used);
   return hipGetLastError();
+}
+
+// ---- streams (ctts_adpcm_stream_step) ----------------------------------------------------------------------------------------------
+// One workgroup per push: [the stream's carried samples | the push's samples, a final push's shortened by its count and compacted by
+// its keep mask] go to the push's 16-byte-aligned staging range, so that adpcm_encode_k's aligned path serves the blocks cut from it.
+// The cutting rule of chattts_amd/adpcm.py (stream_plan): whole blocks of S samples leave from the front, the rest waits in the
+// stream's slot (state [slots][ADPCM_CARRY] int16) unless the push is final, which emits everything and holds nothing.  The slot is
+// read into LDS before the barrier and written behind it, by this workgroup alone (the host refuses a slot named twice).  A keep mask
+// is MSB first and starts at byte start / 8.  Thread 0 writes what adpcm_encode_k reads: the push's AdpcmRange over its staging range
+// (its length the count written here: `emit` for a push that is not final, what is held for a final one), and the same count to used.
+__global__ __launch_bounds__(1024) void adpcm_stage_k(const int16_t* __restrict__ pcm, const uint8_t* __restrict__ mask,
+                                                      const long long* __restrict__ counts, const AdpcmPush* __restrict__ push,
+                                                      int16_t* __restrict__ state, int16_t* __restrict__ stage, AdpcmRange* __restrict__ rng,
+                                                      long long* __restrict__ staged, long long* __restrict__ used) {
+  __shared__ int16_t s_c[ADPCM_CARRY];
+  __shared__ int s_v[2][1024];
+  __shared__ long long s_run;
+  const AdpcmPush P = push[blockIdx.x];
+  const int t = threadIdx.x;
+  const int c = P.carry;
+  const bool last = P.flags & 1, masked = P.flags & 2;
+  int16_t* slot = state + (long long)P.slot * ADPCM_CARRY;
+  for (int i = t; i < c; i += 1024) s_c[i] = slot[i];
+  if (t == 0) s_run = 0;
+  long long L = P.n;
+  if (P.count_idx >= 0) {
+    const long long k = counts[P.count_idx];
+    L = k < 0 ? 0 : (k < L ? k : L);
+  }
+  __syncthreads();
+  // a push that is not final has neither a count nor a mask: what it holds and emits is known before a sample is read
+  const long long S = 2 * (adpcm_align(P.rate) - 4) + 1;
+  const long long emit = last ? (1ll << 62) : (c + L) / S * S;
+  int16_t* dst = stage + P.stage;
+  const int16_t* src = pcm + P.start;
+  for (int i = t; i < c; i += 1024) {
+    dst[i] = s_c[i];
+    if (i >= emit) slot[i - emit] = s_c[i];
+  }
+  for (long long tile = 0; tile < L; tile += 8 * 1024) {
+    const long long i0 = tile + 8 * t;
+    uint32_t bits = 0;
+    if (i0 < L) {
+      bits = masked ? mask[(P.start + i0) >> 3] : 0xFFu;
+      if (L - i0 < 8) bits &= (0xFFu << (8 - (int)(L - i0))) & 0xFFu;
+    }
+    const int cnt = __popc(bits);
+    long long pos = i0;
+    if (masked) {
+      int cur = 0;
+      s_v[0][t] = cnt;
+      __syncthreads();
+      for (int d = 1; d < 1024; d <<= 1) {
+        s_v[cur ^ 1][t] = s_v[cur][t] + (t >= d ? s_v[cur][t - d] : 0);
+        cur ^= 1;
+        __syncthreads();
+      }
+      const long long run = s_run;
+      pos = run + s_v[cur][t] - cnt;
+      __syncthreads();
+      if (t == 1023) s_run = run + s_v[cur][t];
+    }
+    if (bits) {
+      int16_t x[8];
+      if (i0 + 8 <= L) {                 // pcm is 16-byte aligned and starts are multiples of 8 elements
+        const int4 a = *reinterpret_cast<const int4*>(src + i0);
+        const int w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          x[2 * j] = (int16_t)(w[j] & 0xFFFF);
+          x[2 * j + 1] = (int16_t)(w[j] >> 16);
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = i0 + j < L ? src[i0 + j] : (int16_t)0;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (bits & (0x80u >> j)) {
+          const long long d = c + pos++;
+          dst[d] = x[j];
+          if (d >= emit) slot[d - emit] = x[j];
+        }
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    const long long held = c + (masked ? s_run : L);
+    AdpcmRange R;
+    R.start = P.stage;
+    R.n = last ? c + P.n : emit;
+    R.block0 = P.block0;
+    R.byte0 = P.byte0;
+    R.rate = P.rate;
+    R.count_idx = (int32_t)blockIdx.x;
+    R.reserved = 0;
+    rng[blockIdx.x] = R;
+    staged[blockIdx.x] = used[blockIdx.x] = last ? held : emit;
+  }
+}
+
+hipError_t launch_adpcm_stream(const int16_t* pcm, const uint8_t* mask, const long long* counts, const AdpcmPush* push, int n_push,
+                               int16_t* state, long long n_blocks, uint8_t* out, long long* used, long long* staged, AdpcmRange* rng,
+                               int16_t* stage, hipStream_t st) {
+  if (n_push <= 0) return hipSuccess;
+  hipLaunchKernelGGL(adpcm_stage_k, dim3((unsigned)n_push), dim3(1024), 0, st, pcm, mask, counts, push, state, stage, rng, staged, used);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_adpcm_encode((const int16_t*)stage, (const long long*)staged, (const AdpcmRange*)rng, n_push, n_blocks, out, used, st);
 }

@@ -2613,6 +2613,101 @@ extern "C" int ctts_flac_stream_step(const int16_t* pcm, int64_t n_pcm, const ui
                         rng, rec, stage, (hipStream_t)stream));
   return 0;
 }
+static_assert(sizeof(ctts_adpcm_push) == 64 && sizeof(AdpcmPush) == 64 && offsetof(ctts_adpcm_push, stage) == offsetof(AdpcmPush, stage) &&
+              offsetof(ctts_adpcm_push, block0) == offsetof(AdpcmPush, block0) && offsetof(ctts_adpcm_push, byte0) == offsetof(AdpcmPush, byte0) &&
+              offsetof(ctts_adpcm_push, rate) == offsetof(AdpcmPush, rate) && offsetof(ctts_adpcm_push, slot) == offsetof(AdpcmPush, slot) &&
+              offsetof(ctts_adpcm_push, carry) == offsetof(AdpcmPush, carry) && offsetof(ctts_adpcm_push, flags) == offsetof(AdpcmPush, flags) &&
+              offsetof(ctts_adpcm_push, count_idx) == offsetof(AdpcmPush, count_idx), "ctts_adpcm_push layout");
+// the checks of a host push table; sizes: the blocks, out bytes, work bytes, staging elements, the samples held or pushed
+static int adpcm_check_pushes(const char* who, const ctts_adpcm_push* push_host, int32_t n_push, int32_t n_slots, long long n_pcm,
+                              long long sizes[5], bool* wants_counts, bool* wants_mask) {
+  if (!push_host) return fail("%s: a null pointer (the host push table is needed)", who);
+  if (n_push < 1 || n_push > 1024) return fail("%s: need 1 <= n_push <= 1024 (got %d)", who, n_push);
+  if (n_slots < 1) return fail("%s: the state pool has %d slots", who, n_slots);
+  if (n_pcm < 0) return fail("%s: n_pcm is negative (%lld)", who, n_pcm);
+  long long stage = 0, blocks = 0, bytes = 0, samples = 0;
+  *wants_counts = *wants_mask = false;
+  for (int i = 0; i < n_push; ++i) {
+    const ctts_adpcm_push& p = push_host[i];
+    if (p.rate < 1) return fail("%s: push %d: a rate of %d Hz (a positive rate)", who, i, p.rate);
+    const long long align = 256ll * std::max(1, p.rate / 11025), S = 2 * (align - 4) + 1;
+    if (S - 1 > ADPCM_CARRY)
+      return fail("%s: push %d: a block at %d Hz holds %lld samples, a stream's slot %d (rates below 55125 Hz)", who, i, p.rate, S, ADPCM_CARRY);
+    if (p.slot < 0 || p.slot >= n_slots) return fail("%s: push %d: slot %d lies outside the pool of %d", who, i, p.slot, n_slots);
+    for (int j = 0; j < i; ++j)
+      if (push_host[j].slot == p.slot) return fail("%s: pushes %d and %d name slot %d: a stream appears twice in one step", who, j, i, p.slot);
+    if (p.start < 0 || (p.start & 7)) return fail("%s: push %d starts at element %lld: starts are multiples of 8", who, i, (long long)p.start);
+    if (p.n < 0) return fail("%s: push %d has a negative length (%lld)", who, i, (long long)p.n);
+    if (p.n >= (1ll << 31)) return fail("%s: push %d lies beyond what a launch can address (n < 2^31)", who, i);
+    if (p.start > n_pcm || p.n > n_pcm - p.start)
+      return fail("%s: push %d ends at element %lld, beyond the %lld of pcm", who, i, (long long)(p.start + p.n), n_pcm);
+    if (p.carry < 0 || p.carry >= S) return fail("%s: push %d: a stream at %d Hz carries 0 .. %lld samples (got %d)", who, i, p.rate, S - 1, p.carry);
+    if (p.flags & ~3) return fail("%s: push %d: unknown flag bits (%d)", who, i, p.flags);
+    if (p.count_idx < -1 || p.count_idx > 65535) return fail("%s: push %d: count_idx %d is neither -1 nor in 0 .. 65535", who, i, p.count_idx);
+    if (!(p.flags & 1) && p.count_idx >= 0)
+      return fail("%s: push %d has a count_idx but is not final (only a stream's last push may leave its length to the device)", who, i);
+    if (!(p.flags & 1) && (p.flags & 2))
+      return fail("%s: push %d has a keep mask but is not final (only a stream's last push may leave its length to the device)", who, i);
+    if (p.stage != stage) return fail("%s: push %d: stage is %lld, the pushes in front of it own %lld staging elements", who, i, (long long)p.stage, stage);
+    if (p.block0 != blocks) return fail("%s: push %d: block0 is %lld, the pushes in front of it own %lld blocks", who, i, (long long)p.block0, blocks);
+    if (p.byte0 != bytes) return fail("%s: push %d: byte0 is %lld, the pushes in front of it own %lld bytes", who, i, (long long)p.byte0, bytes);
+    if (p.count_idx >= 0) *wants_counts = true;
+    if (p.flags & 2) *wants_mask = true;
+    const long long cap = p.carry + p.n, nb = (p.flags & 1) ? (cap + S - 1) / S : cap / S;
+    stage += (cap + 7) / 8 * 8;
+    blocks += nb;
+    bytes += nb * align;
+    samples += cap;
+  }
+  if (blocks >= (1ll << 31)) return fail("%s: the pushes own %lld blocks, a launch takes fewer than 2^31", who, blocks);
+  sizes[0] = blocks;
+  sizes[1] = bytes;
+  // int64: used [n_push] | staged [n_push]; AdpcmRange [n_push]; the staging buffer
+  sizes[2] = (16ll * n_push + n_push * (long long)sizeof(AdpcmRange) + 15) / 16 * 16 + 2 * stage;
+  sizes[3] = stage;
+  sizes[4] = samples;
+  return 0;
+}
+extern "C" int ctts_adpcm_stream_sizes(const ctts_adpcm_push* push_host, int32_t n_push, int32_t n_slots, int64_t n_pcm, int64_t* sizes) {
+  const char* who = "ctts_adpcm_stream_sizes";
+  if (!sizes) return fail("%s: a null pointer (sizes[4] is needed)", who);
+  long long s[5];
+  bool wants_counts, wants_mask;
+  if (adpcm_check_pushes(who, push_host, n_push, n_slots, n_pcm, s, &wants_counts, &wants_mask)) return -1;
+  for (int i = 0; i < 4; ++i) sizes[i] = s[i];
+  return 0;
+}
+extern "C" int ctts_adpcm_stream_step(const int16_t* pcm, int64_t n_pcm, const uint8_t* mask, const int64_t* counts,
+                                      const ctts_adpcm_push* push_dev, const ctts_adpcm_push* push_host, int32_t n_push, int16_t* state,
+                                      int32_t n_slots, uint8_t* out, size_t out_bytes, void* work, size_t work_bytes, void* stream) {
+  const char* who = "ctts_adpcm_stream_step";
+  if (!pcm || !out || !push_dev || !push_host || !work || !state)
+    return fail("%s: a null pointer (pcm, out, work, state and both push tables are needed)", who);
+  long long s[5];
+  bool wants_counts, wants_mask;
+  if (adpcm_check_pushes(who, push_host, n_push, n_slots, n_pcm, s, &wants_counts, &wants_mask)) return -1;
+  if (wants_counts && !counts) return fail("%s: a null pointer (a push has a count_idx, so counts is needed)", who);
+  if (wants_mask && !mask) return fail("%s: a null pointer (a push has a keep mask, so mask is needed)", who);
+  if (((uintptr_t)pcm & 15) || ((uintptr_t)out & 15) || ((uintptr_t)work & 15) || ((uintptr_t)push_dev & 7) || ((uintptr_t)counts & 7) ||
+      ((uintptr_t)state & 1))
+    return fail("%s: pcm, out and work must be 16-byte aligned, counts and the device table 8-byte aligned", who);
+  if ((long long)out_bytes < s[1] || out_bytes >= (1ull << 62))
+    return fail("%s: out holds %zu bytes, the pushes own %lld (out of capacity)", who, out_bytes, s[1]);
+  if ((long long)work_bytes < s[2] || work_bytes >= (1ull << 62))
+    return fail("%s: work holds %zu bytes, %lld are needed (out of capacity)", who, work_bytes, s[2]);
+  const uintptr_t p0 = (uintptr_t)pcm, o0 = (uintptr_t)out;
+  if (p0 == o0 || (p0 < o0 + (uintptr_t)out_bytes && o0 < p0 + 2 * (uintptr_t)n_pcm))
+    return fail("%s: out aliases pcm (the encoding is not in place)", who);
+  if (s[4] == 0) return 0;                       // no push holds or gets a sample: nothing is emitted and no slot changes
+  CttsDeviceGuard dg(stream);
+  long long* used = (long long*)work;
+  long long* staged = used + n_push;
+  AdpcmRange* rng = (AdpcmRange*)(staged + n_push);
+  int16_t* stage = (int16_t*)((char*)work + s[2] - 2 * s[3]);
+  CK(launch_adpcm_stream(pcm, mask, (const long long*)counts, (const AdpcmPush*)push_dev, n_push, state, s[0], out, used, staged, rng, stage,
+                         (hipStream_t)stream));
+  return 0;
+}
 extern "C" int ctts_k_exp_draws(uint64_t seed, int32_t step, int32_t row0, int32_t rows, int32_t V, float* out, void* stream) {
   if (!out || rows <= 0 || V <= 0) return fail("ctts_k_exp_draws: bad arguments");
   CK(launch_exp_draws(seed, step, row0, rows, V, out, (hipStream_t)stream));

@@ -710,6 +710,25 @@ struct AdpcmRange {
 // Every bound is the caller's to check
 hipError_t launch_adpcm_encode(const int16_t* pcm, const long long* counts, const AdpcmRange* rng, int n_rng, long long n_blocks, uint8_t* out,
                                long long* used, hipStream_t st);
+// streams: whole blocks leave, a stream holds back up to S - 1 samples between pushes in its slot of ADPCM_CARRY int16 (S - 1 = 2040
+// at 48 kHz; a rate whose block holds more is refused)
+#define ADPCM_CARRY 2048
+// ctts_adpcm_push (include/chattts_amd.h), field for field (capi.hip asserts the layout): n samples from element `start` of the int16
+// input continue the stream in state slot `slot`, which holds `carry` samples
+struct AdpcmPush {
+  long long start, n;
+  long long stage;            // the push's first element in the staging buffer (a multiple of 8); it owns carry + n, rounded up to 8
+  long long block0, byte0;    // its first block of the call and its first byte of the output
+  int32_t rate, slot, carry;
+  int32_t flags;              // 1: the stream's last push; 2: compacted by the keep mask (bit 7 - (e & 7) of byte (start + e) / 8)
+  int32_t count_idx;          // >= 0: only the first min(counts[count_idx], n) samples count
+  int32_t reserved;
+};
+// One step of many streams: the staging launch, then adpcm_encode_k over the staging ranges (not launched when the pushes own no block).
+// used, staged: int64 [n_push]; rng: [n_push]; stage: 16-byte aligned.  Every bound is the caller's to check
+hipError_t launch_adpcm_stream(const int16_t* pcm, const uint8_t* mask, const long long* counts, const AdpcmPush* push, int n_push,
+                               int16_t* state, long long n_blocks, uint8_t* out, long long* used, long long* staged, AdpcmRange* rng,
+                               int16_t* stage, hipStream_t st);
 
 // ---- full DVAE: mel front end + GFSQ (dvae.hip) ------------------------------------------------
 // |STFT| of one waveform: center=True reflect padding, frame f = padded[256 f, 256 f + 1024) * window, 1024-point FFT,

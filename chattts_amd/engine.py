@@ -2572,7 +2572,7 @@ class CodecEngine:
 
     def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
                        sample_rates=None, encodings=None, speeds=None, ts_streams=None, rs_streams=None, flac=None, flac_streams=None,
-                       limiter=None, lm_streams=None, pauses=None, pa_streams=None):
+                       limiter=None, lm_streams=None, pauses=None, pa_streams=None, adpcm=None, adpcm_streams=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -2636,7 +2636,15 @@ class CodecEngine:
         `tail` is the stream's last push): in front of the limiter stream, the conversion (one peak per window over the samples that
         come out), a tail's strip (`keep_thr` acts on what the last push emits), G.711 and the FLAC push, the non-streamed order.
         One pause step per round, each with its one small copy of the counts; the chunks then start on multiples of 8 samples again,
-        as the FLAC step needs them."""
+        as the FLAC step needs them.
+        `adpcm` (None, or all False: the call above, argument for argument; needs `pcm16`) with `adpcm_streams`: `flac` /
+        `flac_streams` for IMA ADPCM -- one flag and one entry per window, the handle of the ADPCM stream (`adpcm_stream_open`, at the
+        window's rate) a flagged window continues.  A flagged window PUSHES the int16 samples it would come back as into its stream and
+        comes back as uint8, the blocks that push completes (possibly none; `adpcm.StreamEncoder.push` byte for byte), on every path
+        and by the rules of a FLAC push: behind the conversion, a `tail` is the last push and is stripped by the keep mask on the
+        device, an empty crop still steps its stream, several windows of one stream go to successive rounds.  ONE `adpcm_stream_step`
+        for the flagged windows of the call (two launches; where no tail is stripped, one copy: the blocks).  A window takes FLAC or
+        ADPCM, not both; neither goes with an encoding."""
         pa = None
         if pauses is not None and any(f is not None and f is not False for f in pauses):
             if len(pauses) != len(windows) or pa_streams is None or len(pa_streams) != len(windows):
@@ -2676,23 +2684,13 @@ class CodecEngine:
         elif lm_streams is not None and any(h is not None for h in lm_streams):
             raise ValueError("decode_windows: lm_streams without a limiter flag")
         fl = None
-        if flac is not None and any(bool(f) for f in flac):
-            if len(flac) != len(windows) or flac_streams is None or len(flac_streams) != len(windows):
-                raise ValueError("decode_windows: one flac flag and one flac_streams entry per window")
-            if not pcm16:
-                raise ValueError("decode_windows: FLAC comes behind the 16-bit conversion (pcm16=True)")
-            if encodings is not None and any(f and e is not None for f, e in zip(flac, encodings)):
-                raise ValueError("decode_windows: flac does not go with an encoding (a FLAC stream holds the 16-bit samples)")
-            for i, (f, h) in enumerate(zip(flac, flac_streams)):
-                if f:
-                    want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
-                    if h is None or self._flac_rec(h)[0] != want:
-                        raise ValueError(f"decode_windows: window {i} needs an open FLAC stream at {want} Hz")
-                elif h is not None:
-                    raise ValueError(f"decode_windows: window {i} has no flac flag but names a FLAC stream")
-            fl = ([int(h) if f else None for f, h in zip(flac, flac_streams)], [len(w) > 4 and bool(w[4]) for w in windows])
-        elif flac_streams is not None and any(h is not None for h in flac_streams):
-            raise ValueError("decode_windows: flac_streams without a flac flag")
+        fl_h = self._window_streams("flac", "FLAC", flac, flac_streams, windows, pcm16, sample_rates, encodings, self._flac_rec)
+        ad_h = self._window_streams("adpcm", "ADPCM", adpcm, adpcm_streams, windows, pcm16, sample_rates, encodings, self._adpcm_rec)
+        if fl_h is not None or ad_h is not None:
+            if fl_h is not None and ad_h is not None and any(f is not None and a is not None for f, a in zip(fl_h, ad_h)):
+                raise ValueError("decode_windows: a window takes FLAC or ADPCM, not both")
+            one = [None] * len(windows)
+            fl = ([f or a for f, a in zip(fl_h or one, ad_h or one)], [len(w) > 4 and bool(w[4]) for w in windows])
         q = None
         if speeds is not None:
             if len(speeds) != len(windows):
@@ -2716,7 +2714,8 @@ class CodecEngine:
         if lm is not None or pa is not None:
             return self._decode_windows_limited(store, windows, [None] * len(windows) if lm is None else lm, q, laws, fl, pcm16, keep_thr, product,
                                                 dict(sample_rates=sample_rates, encodings=encodings, speeds=speeds, ts_streams=ts_streams,
-                                                     rs_streams=rs_streams, flac=flac, flac_streams=flac_streams), pa)
+                                                     rs_streams=rs_streams, flac=flac, flac_streams=flac_streams, adpcm=adpcm,
+                                                     adpcm_streams=adpcm_streams), pa)
         if q is not None:
             rates = None
             if sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
@@ -2934,9 +2933,33 @@ class CodecEngine:
                                                    [(fl[0][i], 0, 0, fl[1][i]) for i in idle], out)]
         return out
 
+    def _window_streams(self, arg: str, name: str, flags, streams, windows, pcm16: bool, sample_rates, encodings, rec):
+        """the flags and streams of one output format of a `decode_windows` call (`arg` / `name`: flac / FLAC, adpcm / ADPCM; `rec`: a
+        handle's open record, its rate first), checked -> per window (arg, handle) or None; None when no window is flagged"""
+        an = "an" if arg[0] == "a" else "a"
+        if flags is not None and any(bool(f) for f in flags):
+            if len(flags) != len(windows) or streams is None or len(streams) != len(windows):
+                raise ValueError(f"decode_windows: one {arg} flag and one {arg}_streams entry per window")
+            if not pcm16:
+                raise ValueError(f"decode_windows: {name} comes behind the 16-bit conversion (pcm16=True)")
+            if encodings is not None and any(f and e is not None for f, e in zip(flags, encodings)):
+                raise ValueError(f"decode_windows: {arg} does not go with an encoding ({an} {name} stream holds the 16-bit samples)")
+            for i, (f, h) in enumerate(zip(flags, streams)):
+                if f:
+                    want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
+                    if h is None or rec(h)[0] != want:
+                        raise ValueError(f"decode_windows: window {i} needs an open {name} stream at {want} Hz")
+                elif h is not None:
+                    raise ValueError(f"decode_windows: window {i} has no {arg} flag but names {an} {name} stream")
+            return [(arg, int(h)) if f else None for f, h in zip(flags, streams)]
+        if streams is not None and any(h is not None for h in streams):
+            raise ValueError(f"decode_windows: {arg}_streams without {an} {arg} flag")
+        return None
+
     def _flac_rounds(self, pcm: torch.Tensor, masks, idx, pushes, out: list) -> list:
-        """pushes[j] is window idx[j]'s: ONE `flac_stream_step` when no stream is named twice, else the r-th push of a stream goes to
-        step r, in the order given; -> `out` with the windows' chunks in place"""
+        """pushes[j] is window idx[j]'s, its stream an (arg, handle) of `_window_streams`: ONE `flac_stream_step` and ONE
+        `adpcm_stream_step` (each for its own windows) when no stream is named twice, else the r-th push of a stream goes to step r,
+        in the order given; -> `out` with the windows' chunks in place"""
         out, seen, rounds = list(out), {}, []
         for i, p in zip(idx, pushes):
             r = seen[p[0]] = seen.get(p[0], -1) + 1
@@ -2944,8 +2967,11 @@ class CodecEngine:
                 rounds.append([])
             rounds[r].append((i, p))
         for rnd in rounds:
-            for (i, _), c in zip(rnd, self.flac_stream_step(pcm, [p for _, p in rnd], None, masks)):
-                out[i] = c
+            for arg, step in (("flac", self.flac_stream_step), ("adpcm", self.adpcm_stream_step)):
+                mine = [(i, p) for i, p in rnd if p[0][0] == arg]
+                if mine:
+                    for (i, _), c in zip(mine, step(pcm, [(p[0][1], *p[1:]) for _, p in mine], None, masks)):
+                        out[i] = c
         return out
 
     def _decode_windows_speed(self, store: torch.Tensor, windows, q, ts_streams, pcm16: bool, keep_thr: Optional[float], product: str,
@@ -3403,6 +3429,143 @@ class CodecEngine:
             f0 = int(tab["frame0"][k])
             f1 = f0 + (int(tab["carry"][k]) + int(tab["n"][k]) + FLAC.BLOCK - 1) // FLAC.BLOCK
             res.append(blob[int(meta[f0]): int(meta[f1])])
+        return res
+
+    # -- IMA ADPCM for streams: per-stream device state (csrc/adpcm.hip, adpcm_stage_k) -------------------------------------------------
+    ADPCM_STREAM_SLOTS = 64   # the state pool's first size; it doubles when every slot is taken
+    ADPCM_CARRY = 2048        # int16 per slot: S - 1 = 2040 at 48 kHz
+
+    def _adpcm_pool(self) -> dict:
+        """the state pool: carry [slots, 2048] int16 on the device, the free list, and per open stream its host record [rate, samples
+        held (0 .. S - 1), done]"""
+        pool = self.__dict__.get("_adpcm_streams")
+        if pool is None:
+            n = int(self.ADPCM_STREAM_SLOTS)
+            pool = self._adpcm_streams = dict(carry=torch.zeros((n, self.ADPCM_CARRY), dtype=torch.int16, device=self.device),
+                                              free=list(range(n - 1, -1, -1)), rec={})
+        return pool
+
+    def adpcm_stream_open(self, rate: int) -> int:
+        """An IMA ADPCM stream at `rate` Hz: -> its handle, a slot of the engine's state pool.  The slot is fresh by construction -- a
+        stream that holds no samples reads none -- so nothing is cleared.  ValueError for a rate that is no rate, or whose block
+        (55125 Hz and above) does not fit a slot."""
+        if ADPCM.samples_per_block(rate) - 1 > self.ADPCM_CARRY:
+            raise ValueError(f"adpcm: a block at {rate} Hz holds {ADPCM.samples_per_block(rate)} samples, more than a stream's slot "
+                             f"({self.ADPCM_CARRY}): streams run below 55125 Hz")
+        pool = self._adpcm_pool()
+        if not pool["free"]:
+            n = int(pool["carry"].shape[0])
+            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
+            pool["free"] = list(range(2 * n - 1, n - 1, -1))
+        slot = pool["free"].pop()
+        pool["rec"][slot] = [int(rate), 0, False]
+        return slot
+
+    def adpcm_stream_close(self, handle: int) -> None:
+        """gives the stream's slot back (any time: finished, or abandoned half way)"""
+        pool = self._adpcm_pool()
+        if pool["rec"].pop(int(handle), None) is None:
+            raise ValueError(f"adpcm: stream {handle} is not open")
+        pool["free"].append(int(handle))
+
+    def adpcm_streams_in_use(self) -> int:
+        """the streams that are open: slots of the state pool not on its free list"""
+        return len(self._adpcm_pool()["rec"])
+
+    def _adpcm_rec(self, handle: int):
+        rec = self._adpcm_pool()["rec"].get(int(handle))
+        if rec is None:
+            raise ValueError(f"adpcm: stream {handle} is not open")
+        if rec[2]:
+            raise ValueError(f"adpcm: stream {handle} has had its last push")
+        return rec
+
+    def adpcm_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
+        """`adpcm.stream_plan` of the stream's next push: the blocks a step with `n_in` more samples would emit, the samples the stream
+        would hold afterwards, and the most bytes the push can emit"""
+        rate, carry, _ = self._adpcm_rec(handle)
+        blocks, held = ADPCM.stream_plan(carry, n_in, final, rate)
+        return dict(rate=rate, blocks=blocks, carry=held, bound=ADPCM.stream_bound(n_in, rate))
+
+    def adpcm_stream_step(self, pcm: torch.Tensor, pushes, counts: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None) -> list:
+        """ONE step of many IMA ADPCM streams (ctts_adpcm_stream_step: two launches whatever their number): `pcm`, a contiguous int16
+        device tensor taken as flat, holds the new samples of every stream; `pushes` = [(handle, start, n, final)] or [(handle, start,
+        n, final, count_idx, masked)]: pcm[start, start + n) continue stream `handle` (n 0: nothing new; starts are multiples of 8),
+        `final`: they are its last.  A final push may leave its length to the device: with a count_idx only the first
+        min(counts[count_idx], n) samples count (`counts`: an int64 device tensor), and `masked` keeps only the samples whose bit is
+        set in `masks` (a uint8 device tensor, MSB first, the bit of element e of `pcm` in byte e / 8: `decode_windows`' keep masks).
+        -> one uint8 array per push: the blocks that push completes (possibly none), `adpcm.StreamEncoder.push` byte for byte; behind
+        `adpcm.stream_header(rate)` a stream's chunks are the blocks of `adpcm.encode_blocks` over its pushes, concatenated, however
+        they were cut.  A handle may appear once per call.  When no push leaves its length to the device the chunk sizes are known
+        here and ONE copy, of the blocks, comes to the host; otherwise one more small copy brings the samples each push encoded.  The
+        samples stay on the device.  Every refusal (ValueError here, EngineError from the library) comes before the first launch and
+        leaves all streams as they were."""
+        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()):
+            raise ValueError("adpcm: a contiguous int16 device tensor")
+        if counts is not None and not (counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()):
+            raise ValueError("adpcm: `counts` must be a contiguous int64 device tensor")
+        if masks is not None and not (masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous()):
+            raise ValueError("adpcm: `masks` must be a contiguous uint8 device tensor")
+        if len(pushes) < 1:
+            raise ValueError("adpcm: nothing to step")
+        if len(pushes) > 1024:
+            raise ValueError("adpcm: at most 1024 streams in one step")
+        if len({int(p[0]) for p in pushes}) != len(pushes):
+            raise ValueError("adpcm: a stream appears twice in one step")
+        pool = self._adpcm_pool()
+        n_el, n_push = pcm.numel(), len(pushes)
+        tab = np.zeros(n_push, _lib.ADPCM_PUSH)
+        stage = blocks = nbytes = samples = 0
+        commit, by_device = {}, False
+        for k, p in enumerate(pushes):
+            h, start, n, final = int(p[0]), int(p[1]), int(p[2]), bool(p[3])
+            ci = int(p[4]) if len(p) > 4 and p[4] is not None else -1
+            masked = len(p) > 5 and bool(p[5])
+            rate, carry, _ = self._adpcm_rec(h)
+            if n < 0 or start < 0 or start + n > n_el:
+                raise ValueError("adpcm: a push lies outside the tensor")
+            if ci >= 0 and (counts is None or ci >= counts.numel()):
+                raise ValueError(f"adpcm: push {k} reads count {ci}, beyond `counts`")
+            if masked and (masks is None or masks.numel() * 8 < start + n):
+                raise ValueError(f"adpcm: push {k} is masked, and `masks` does not reach its end")
+            if (ci >= 0 or masked) and not final:
+                raise ValueError(f"adpcm: push {k} leaves its length to the device but is not final")
+            by_device = by_device or ci >= 0 or masked
+            tab[k] = (start, n, stage, blocks, nbytes, rate, h, carry, int(final) | 2 * int(masked), ci, 0)
+            nb, held = ADPCM.stream_plan(carry, n, final, rate)                  # a final push's own count only lowers its blocks
+            commit[h] = [rate, held, final]
+            stage += (carry + n + 7) // 8 * 8
+            blocks, nbytes, samples = blocks + nb, nbytes + nb * ADPCM.align(rate), samples + carry + n
+        n_slots = int(pool["carry"].shape[0])
+        sizes = (C.c_int64 * 4)()
+        _lib.check(self.lib.ctts_adpcm_stream_sizes(tab.ctypes.data_as(C.c_void_p), n_push, n_slots, n_el, sizes), "ctts_adpcm_stream_sizes")
+        n_blocks, out_bytes, work_bytes, _ = (int(v) for v in sizes)
+        empty = np.zeros((0,), np.uint8)
+        if samples == 0:                                                         # no stream holds or gets a sample
+            pool["rec"].update(commit)
+            return [empty for _ in pushes]
+        dev = pcm.device
+        out = torch.empty((max(out_bytes, 16),), dtype=torch.uint8, device=dev)
+        work = torch.empty((work_bytes,), dtype=torch.uint8, device=dev)
+        tab_d = torch.from_numpy(tab.view(np.uint8)).to(dev)
+        st = torch.cuda.current_stream(dev)
+        _lib.check(self.lib.ctts_adpcm_stream_step(pcm.data_ptr(), n_el, _lib.ptr(masks), _lib.ptr(counts), tab_d.data_ptr(),
+                                                   tab.ctypes.data_as(C.c_void_p), n_push, pool["carry"].data_ptr(), n_slots, out.data_ptr(),
+                                                   out.numel(), work.data_ptr(), work.numel(), st.cuda_stream), "ctts_adpcm_stream_step")
+        tab_d.record_stream(st)
+        pool["rec"].update(commit)
+        if n_blocks == 0:                                                        # samples went to the slots, and no block is complete
+            return [empty for _ in pushes]
+        used = self.to_host(work[: (8 * n_push + 15) // 16 * 16]).view(np.int64) if by_device else None
+        blob = self.to_host(out[:out_bytes])
+        res = []
+        for k in range(n_push):
+            rate, b0 = int(tab["rate"][k]), int(tab["byte0"][k])
+            if used is None:
+                size = ADPCM.stream_plan(int(tab["carry"][k]), int(tab["n"][k]), bool(tab["flags"][k] & 1), rate)[0] * ADPCM.align(rate)
+            else:
+                size = (ADPCM.n_blocks(int(used[k]), rate) if tab["flags"][k] & 1 else int(used[k]) // ADPCM.samples_per_block(rate)) * ADPCM.align(rate)
+            res.append(blob[b0: b0 + size])
         return res
 
     def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str, laws=None,

@@ -98,7 +98,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
                stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
                pauses: bool = False, limiter: bool = False, stream_limiter: bool = False, stream_pauses: bool = False,
-               adpcm: bool = False):
+               adpcm: bool = False, stream_adpcm: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -186,7 +186,14 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     half of G.711's size, chattts_amd/adpcm.py), encoded on the device behind the 16-bit conversion (Chat.infer(adpcm=True) /
     SpeechBatcher.submit(adpcm=True)), at whatever rate, speed, loudness, pauses and limiter the other options allow; `"stream": true`
     with it gets a 400 (a streamed file would carry up to a block's samples across chunks), an `"encoding"` key with it too.  With
-    `voice_upload`, mono IMA ADPCM WAV clips are accepted too (audio.load_wav(adpcm=True))."""
+    `voice_upload`, mono IMA ADPCM WAV clips are accepted too (audio.load_wav(adpcm=True)).  `stream_adpcm=True` (with
+    `adpcm`; default off) lifts that 400: a streamed request with `response_format` "adpcm" is served as audio/wav: `adpcm.stream_header(rate)`
+    (the file's header with 0xFFFFFFFF in the RIFF, `fact` and `data` lengths), then the whole blocks each chunk completes; empty
+    chunks are not written.  The blocks are those of the non-streamed file over the same samples; a reader of the open-ended file
+    cannot know the true length and decodes up to a block's worth of padded samples behind the last real one.  It is served from the
+    pool with `batch_streams` (SpeechBatcher(stream_adpcm=True).submit_stream(adpcm_blocks=True)), serially otherwise
+    (Chat.infer(stream=True, adpcm=True, stream_adpcm=True)), at the rates `stream_sample_rates` allows (below 55125 Hz), and
+    /health carries `"stream_adpcm": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -206,7 +213,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                 **({"stream_speed_rates": True} if speed and stream_speed and stream_speed_rates else {}),
                                 **({"stream_flac": True} if flac and stream_flac else {}),
                                 **({"stream_limiter": True} if limiter and stream_limiter else {}),
-                                **({"stream_pauses": True} if pauses and stream_pauses else {}))
+                                **({"stream_pauses": True} if pauses and stream_pauses else {}),
+                                **({"stream_adpcm": True} if adpcm and stream_adpcm else {}))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
@@ -216,6 +224,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     pool_stream_speed_rates = pool_stream_speeds and speed_rates and bool(getattr(batcher, "stream_speed_rates", False))
     flac_streams = bool(flac and stream_flac)
     pool_stream_flac = pool_streams and flac_streams and bool(getattr(batcher, "stream_flac", False))
+    adpcm_streams = bool(adpcm and stream_adpcm)
+    pool_stream_adpcm = pool_streams and adpcm_streams and bool(getattr(batcher, "stream_adpcm", False))
     limiter_streams = bool(limiter and stream_limiter)
     pool_stream_limiter = pool_streams and limiter_streams and bool(getattr(batcher, "stream_limiter", False))
     pause_streams = bool(pauses and stream_pauses)
@@ -320,6 +330,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             kw = {**kw, "stream_resample": True, "split_text": False}
         if req.stream and as_flac:                   # likewise for a streamed FLAC
             kw = {**kw, "stream_flac": True, "split_text": False}
+        if req.stream and as_adpcm:                  # ... and for a streamed ADPCM file
+            kw = {**kw, "stream_adpcm": True, "split_text": False}
         if req.stream and spd is not None:           # likewise for a stream at another speed
             kw = {**kw, "stream_time_scale": True, "split_text": False}
             if rate != SAMPLE_RATE:                  # ... and another rate: the resampler's history and look-ahead are carried
@@ -456,9 +468,12 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 raise HTTPException(400, detail=str(e))
         as_adpcm = bool(adpcm) and fmt == "adpcm"    # likewise
         if as_adpcm:
-            if req.stream:
+            if req.stream and not adpcm_streams:
                 raise HTTPException(400, detail="adpcm is served for non-streamed requests only: a streamed ADPCM file would carry up to "
                                                 "a block's samples across chunks")
+            if req.stream and rate >= 55125:
+                raise HTTPException(400, detail=f"a streamed ADPCM file is served below 55125 Hz (a stream keeps up to 2048 samples of an "
+                                                f"open block), not at {rate} Hz")
             if request_data.get("encoding") is not None:
                 raise HTTPException(400, detail=f"encoding {request_data['encoding']} does not go with response_format adpcm (an ADPCM "
                                                 f"file is coded from the 16-bit samples)")
@@ -486,7 +501,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             return _av_encode(pcm, fmt, rate)
 
         if req.stream and pool_streams and (spd is None or (pool_stream_speeds and (rate == SAMPLE_RATE or pool_stream_speed_rates))) \
-                and (not as_flac or pool_stream_flac) and (not lim or pool_stream_limiter) and (trim is None or pool_stream_pauses):
+                and (not as_flac or pool_stream_flac) and (not lim or pool_stream_limiter) and (trim is None or pool_stream_pauses) \
+                and (not as_adpcm or pool_stream_adpcm):
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
                 skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
                 if spd is not None:
@@ -495,7 +511,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     skw = {**skw, "limiter": True, **({} if gdb is None else {"gain_db": gdb})}
                 if trim is not None:
                     skw = {**skw, "pauses": trim}
-                chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw, **ekw)
+                chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw, **({"adpcm_blocks": True} if as_adpcm else ekw))
                 try:
                     first = True
                     async for chunk in iterate_in_threadpool(chunks):
@@ -503,6 +519,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                             yield stream_header(rate)
                         if as_flac and first:
                             yield FLAC.stream_header(rate)
+                        if as_adpcm and first:
+                            yield ADPCM.stream_header(rate)
                         first = False
                         if np.asarray(chunk).size:
                             yield encode(chunk, header=False)
@@ -517,14 +535,16 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        gen = infer(req, rate, law, spd, as_flac, None, trim, lim, gdb) if trim is not None else \
-                            infer(req, rate, law, spd, as_flac, None, None, True, gdb) if lim else infer(req, rate, law, spd, True) if as_flac else \
-                            infer(req, rate, law, spd) if spd is not None else (infer(req, rate) if law is None else infer(req, rate, law))
+                        gen = infer(req, rate, law, spd, as_flac, None, trim, lim, gdb, **akw) if trim is not None else \
+                            infer(req, rate, law, spd, as_flac, None, None, True, gdb, **akw) if lim else infer(req, rate, law, spd, True) if as_flac else \
+                            infer(req, rate, None, spd, **akw) if as_adpcm else infer(req, rate, law, spd) if spd is not None else (infer(req, rate) if law is None else infer(req, rate, law))
                         async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
                             if fmt == "wav" and first:
                                 yield stream_header(rate)
                             if as_flac and first:
                                 yield FLAC.stream_header(rate)
+                            if as_adpcm and first:
+                                yield ADPCM.stream_header(rate)
                             first = False
                             if np.asarray(chunk).size:
                                 yield encode(chunk, header=False)
@@ -610,6 +630,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["loudness"] = True
         if flac_streams:
             out["stream_flac"] = True
+        if adpcm_streams:
+            out["stream_adpcm"] = True
         if pauses:
             out["pauses"] = True
         if limiter:

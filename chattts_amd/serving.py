@@ -667,7 +667,8 @@ class _Job:
     rs_slot: Optional[int] = None          # ... and at another rate: its stream of the resampler, opened with it
     flac: bool = False                     # the result is the FLAC file of the int16 waveform; a stream: its chunks are FLAC frames
     flac_slot: Optional[int] = None        # a FLAC stream: its stream of the encoder, opened at its first chunk
-    adpcm: bool = False                    # the result is the IMA ADPCM WAV file of the int16 waveform (non-streamed only)
+    adpcm: bool = False                    # the result is the IMA ADPCM WAV file of the int16 waveform; a stream: its chunks are ADPCM blocks
+    adpcm_slot: Optional[int] = None       # an ADPCM stream: its stream of the encoder, opened at its first chunk
     loudness: Optional[float] = None       # a target in LUFS (non-streamed only); None: the level is left alone
     pauses: object = None                  # a pauses.PauseSpec (non-streamed only); None: the silence is left alone
     limiter: bool = False                  # the look-ahead peak limiter behind the loudness stage's gain; a stream: in front of the conversion
@@ -761,6 +762,9 @@ class SpeechBatcher:
     Its job holds a stream of the encoder (`CodecEngine.flac_stream_open(rate)`, opened at its first chunk, given back in `_resolve`
     however the request ends); the chunks of all FLAC streams due at one poll are the pushes of ONE encoder step behind the one
     window decode (`decode_windows(flac=, flac_streams=)`); `occupancy()["stream_flac_chunks"]` counts them.
+    `stream_adpcm=True` (with `streams`; off: `submit_stream(adpcm_blocks=True)` is refused): likewise for IMA ADPCM -- the job holds
+    a stream of that encoder (`CodecEngine.adpcm_stream_open(rate)`), the chunks of all ADPCM streams due at one poll are the pushes
+    of ONE encoder step (`decode_windows(adpcm=, adpcm_streams=)`), and `occupancy()["stream_adpcm_chunks"]` counts them.
 
     `refine=True`: requests may ask for the reference's DEFAULT behaviour, the refine-text pass in front of the code pass
     (`submit(text, params, refine=RefineTextParams(...))`).  A second, TEXT-mode per-request pool (SlotPool(infer_text=True), its own
@@ -793,7 +797,7 @@ class SpeechBatcher:
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
                  logger=None, ragged_decode: bool = False, streams: bool = False, refine: bool = False, make_text_pool=None,
                  text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False, stream_speed_rates: bool = False,
-                 stream_flac: bool = False, stream_limiter: bool = False, stream_pauses: bool = False):
+                 stream_flac: bool = False, stream_limiter: bool = False, stream_pauses: bool = False, stream_adpcm: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
@@ -809,6 +813,8 @@ class SpeechBatcher:
         self.stream_scaled_chunks = 0      # chunks of streams at another speed than 1
         self.stream_flac = bool(stream_flac)       # submit_stream(flac=True) is accepted
         self.stream_flac_chunks = 0        # chunks handed out as FLAC frames (empty ones included)
+        self.stream_adpcm = bool(stream_adpcm)     # submit_stream(adpcm_blocks=True) is accepted
+        self.stream_adpcm_chunks = 0       # chunks handed out as IMA ADPCM blocks (empty ones included)
         self.stream_limiter = bool(stream_limiter)   # submit_stream(limiter=True) is accepted
         self.stream_limited_chunks = 0     # chunks that came out of a limiter stream (empty ones included)
         self.stream_pauses = bool(stream_pauses)     # submit_stream(pauses=) is accepted
@@ -934,7 +940,8 @@ class SpeechBatcher:
         self._in.put(_Cancel(fut.rid))
 
     def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None,
-                      speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False, gain_db=None) -> SpeechStream:
+                      speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False, gain_db=None,
+                      adpcm_blocks: bool = False) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
@@ -961,7 +968,23 @@ class SpeechBatcher:
         where its other streams are) and its chunks are those of the serial call with `limiter=True, stream_limiter=True`: converted,
         companded or FLAC-encoded from limited samples, 20 ms behind.  The limiter streams due at one poll share one step per round
         behind their decoder pass (CodecEngine.decode_windows(limiter=)).  `gain_db` (with `limiter` only): the serial call's fixed
-        make-up gain in front of the limiter, -30 .. +30 dB."""
+        make-up gain in front of the limiter, -30 .. +30 dB.  `adpcm_blocks` (accepted by a batcher built with `stream_adpcm=True`;
+        refused otherwise, and together with `encoding` or `flac`): the chunks are uint8, the whole IMA ADPCM blocks each chunk
+        completes (possibly none: up to S - 1 samples of an open block wait for the next chunk), the serial call's `adpcm=True,
+        stream_adpcm=True`; concatenated they are `adpcm.encode_blocks` of the int16 chunks of the same request without it, and behind
+        `adpcm.stream_header(rate)` an open-ended WAV file.  The request gets an ADPCM stream (opened at its first chunk, given back
+        where its other streams are); the chunks of all ADPCM streams due at one poll share ONE encoder step behind the one decoder
+        pass (CodecEngine.decode_windows(adpcm=))."""
+        if adpcm_blocks:
+            if not self.stream_adpcm:
+                raise ValueError("adpcm_blocks needs a batcher built with stream_adpcm=True (an ADPCM file is served for non-streamed "
+                                 "requests only otherwise)")
+            if encoding is not None:
+                raise ValueError("adpcm_blocks does not go with an encoding (an ADPCM stream is coded from the 16-bit samples)")
+            if flac:
+                raise ValueError("adpcm_blocks does not go with flac (a stream is answered in one format)")
+            if ADPCM.samples_per_block(24000 if sample_rate is None else sample_rate) - 1 > 2048:
+                raise ValueError(f"a streamed ADPCM file at {sample_rate} Hz would carry more than a stream keeps: streams run below 55125 Hz")
         limiter = LM.check_flag(limiter, "submit_stream")
         if limiter and not self.stream_limiter:
             raise ValueError("limiter applies to non-streamed requests only (the look-ahead is not carried across chunks)")
@@ -1004,7 +1027,8 @@ class SpeechBatcher:
                 raise ValueError(f"a streamed speed at {rate} Hz would carry up to {K - 1} samples, a resampler stream keeps {RS.CARRY}")
         h = SpeechStream(self, next(self._ids))
         self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed, flac=bool(flac),
-                          **({"limiter": True, "lm_gain": g32} if limiter else {}), **({} if pauses is None else {"pauses": pauses})))
+                          **({"limiter": True, "lm_gain": g32} if limiter else {}), **({} if pauses is None else {"pauses": pauses}),
+                          **({"adpcm": True} if adpcm_blocks else {})))
         return h
 
     def _check_refine(self, refine) -> None:
@@ -1031,6 +1055,8 @@ class SpeechBatcher:
                         "stream_resampled_chunks": self.stream_resampled_chunks, "stream_scaled_chunks": self.stream_scaled_chunks})
             if self.stream_flac:
                 occ["stream_flac_chunks"] = self.stream_flac_chunks
+            if self.stream_adpcm:
+                occ["stream_adpcm_chunks"] = self.stream_adpcm_chunks
             if self.stream_limiter:
                 occ["stream_limited_chunks"] = self.stream_limited_chunks
             if self.stream_pauses:
@@ -1065,6 +1091,9 @@ class SpeechBatcher:
         if job.flac_slot is not None:      # ... and its stream of the FLAC encoder
             slot, job.flac_slot = job.flac_slot, None
             self.chat.codec.flac_stream_close(slot)
+        if job.adpcm_slot is not None:     # ... and its stream of the ADPCM encoder
+            slot, job.adpcm_slot = job.adpcm_slot, None
+            self.chat.codec.adpcm_stream_close(slot)
         if job.lm_slot is not None:        # ... and its stream of the limiter
             slot, job.lm_slot = job.lm_slot, None
             self.chat.codec.peak_limit_stream_close(slot)
@@ -1079,7 +1108,7 @@ class SpeechBatcher:
         else:
             self.completed += 1
             self.flac_encoded += job.flac and not job.is_stream                  # (a stream's chunks are counted as they go out)
-            self.adpcm_encoded += job.adpcm
+            self.adpcm_encoded += job.adpcm and not job.is_stream               # (likewise)
             self.trimmed += job.pauses is not None and not job.is_stream
             self.companded += not job.is_stream and job.encoding is not None      # (a stream's chunks are counted as they go out)
         if job.is_stream:
@@ -1326,6 +1355,12 @@ class SpeechBatcher:
                     if j.flac and j.flac_slot is None:
                         j.flac_slot = self.chat.codec.flac_stream_open(24000 if j.sample_rate is None else j.sample_rate)
                 kw["flac_streams"] = [j.flac_slot for j in jobs]
+            if "adpcm" in kw:             # the ADPCM streams due at this poll: likewise
+                self.stream_adpcm_chunks += sum(j.adpcm for j in jobs)
+                for j in jobs:
+                    if j.adpcm and j.adpcm_slot is None:
+                        j.adpcm_slot = self.chat.codec.adpcm_stream_open(24000 if j.sample_rate is None else j.sample_rate)
+                kw["adpcm_streams"] = [j.adpcm_slot for j in jobs]
             if "limiter" in kw:           # the limiter streams due at this poll: one step per round behind their decode
                 self.stream_limited_chunks += sum(j.limiter for j in jobs)
                 for j in jobs:

@@ -861,6 +861,42 @@ int ctts_flac_stream_step(const int16_t* pcm, int64_t n_pcm, const uint8_t* mask
                           const ctts_flac_push* push_host, int32_t n_push, int16_t* state, int32_t n_slots, uint8_t* out, size_t out_bytes,
                           void* work, size_t work_bytes, void* stream);
 
+/* IMA ADPCM for STREAMS: the signal arrives in pushes and leaves as the whole blocks of ctts_adpcm_encode_ranges.  A block's bytes depend
+ * on its own S = 2 * (align - 4) + 1 samples and the rate only, so the pushes of a stream, concatenated, are the bytes of the one-shot
+ * encoder over its samples, however they were cut.  chattts_amd/adpcm.py (StreamEncoder) is the NumPy twin, byte for byte.  The cutting
+ * rule: a stream holds `carry` samples (0 .. S - 1) from its earlier pushes in its state slot (`state`: int16 [n_slots][2048] on the
+ * device); with the push's samples that makes `avail`.  A push that is not final emits avail / S blocks from the front and leaves
+ * avail % S samples in the slot; a final push (flags & 1) emits ceil(avail / S) blocks, the last padded with the last sample, and holds
+ * nothing; with avail = 0 it emits nothing.
+ * Push i: elements [start, start + n) of `pcm` continue the stream in `slot`.  A FINAL push may leave its length to the device:
+ * count_idx >= 0 takes min(counts[count_idx], n) samples, and flags & 2 keeps only the samples whose bit is set in `mask` (MSB first; the
+ * push's bits start at byte start / 8: the keep masks of ctts_codec_decode_windows).  The push owns staging elements [stage, stage +
+ * carry + n rounded up to 8), the blocks [block0, block0 + nb) of the call and the bytes of `out` from byte0 on (nb * align of them),
+ * with nb = (carry + n) / S for a push that is not final and ceil((carry + n) / S) for a final one (an upper bound when its length is
+ * left to the device); all three are the running sums over the pushes in front of it.  The caller keeps the carry of every stream (the
+ * rule above, in integers) and reads, from the first byte of `work` on, int64 [n_push] the samples each push encoded: nb * S for a push
+ * that is not final, everything it held for a final one, which wrote ceil(that / S) blocks.  Two launches (adpcm_stage_k, then
+ * adpcm_encode_k over the staging ranges) whatever the number of pushes, one when the pushes own no block, none -- and `work` is left
+ * as it was -- when no push holds or gets a sample.  ctts_adpcm_stream_sizes checks a host table and gives sizes[4] = {the blocks (an
+ * upper bound), the bytes `out` must hold, the bytes `work` must hold, the staging elements}.
+ * Refused on the host table before anything is launched, all streams left as they were: a null pointer (mask / counts may be null when
+ * no push uses them), n_push < 1 or > 1024, a slot outside [0, n_slots) or named twice, a start that is negative or no multiple of 8, a
+ * push that ends beyond n_pcm, n negative or >= 2^31, a rate below 1 or one whose block does not fit a slot (55125 Hz and above), a
+ * carry outside 0 .. S - 1, unknown flag bits, a count_idx < -1 or > 65535, a count_idx or a mask on a push that is not final, a stage,
+ * block0 or byte0 other than the running sum, out_bytes or work_bytes too small, pointers not 16-byte aligned (counts: 8), out aliasing
+ * pcm. */
+typedef struct {
+  int64_t start, n;       /* elements of the int16 input; start a multiple of 8 */
+  int64_t stage;          /* the push's first staging element */
+  int64_t block0, byte0;  /* its first block of the call, its first byte of out */
+  int32_t rate, slot, carry, flags;   /* flags 1: final; 2: compact by the keep mask */
+  int32_t count_idx, reserved;
+} ctts_adpcm_push;        /* 64 bytes */
+int ctts_adpcm_stream_sizes(const ctts_adpcm_push* push_host, int32_t n_push, int32_t n_slots, int64_t n_pcm, int64_t* sizes);
+int ctts_adpcm_stream_step(const int16_t* pcm, int64_t n_pcm, const uint8_t* mask, const int64_t* counts,
+                           const ctts_adpcm_push* push_dev, const ctts_adpcm_push* push_host, int32_t n_push,
+                           int16_t* state, int32_t n_slots, uint8_t* out, size_t out_bytes, void* work, size_t work_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Full DVAE (asset/DVAE.safetensors): audio -> 4 x T codes and codes -> mel through the GFSQ codebook.
  * Replaces `self.dvae(wav, "encode")` of `Chat.sample_audio_speaker` (ChatTTS/core.py:179-180 ->

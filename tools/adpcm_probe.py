@@ -11,6 +11,16 @@ spread (min .. max) beside it.  The ADPCM bytes are checked against the NumPy tw
 bench.py leg.
 
     python tools/adpcm_probe.py [--reps 20] [--rounds 9]
+
+`--stream`: the streamed form instead (ctts_adpcm_stream_step: adpcm_stage_k, then adpcm_encode_k over the staging ranges -- two
+launches) for 1, 16 and 64 streams that each hold 500 samples and get a chunk of 12000 at 24 kHz, beside one ctts_adpcm_encode_ranges
+call (one launch) over the same chunks as stand-alone signals -- what the step costs over the one-shot encoder for the same samples --,
+and beside that call behind a device copy of the chunks (and the copy alone): the one-shot encoder over samples that a kernel has just
+written, which is how both encoders meet them behind the conversion.
+The same windows, alternating; `--reps` then defaults to 500 (a step is tens of microseconds).  The first stream's blocks are checked
+against the twin.
+
+    python tools/adpcm_probe.py --stream [--reps 500] [--rounds 9]
 """
 from __future__ import annotations
 
@@ -111,15 +121,88 @@ def _entry(lib, dev, rate: int, n_sig: int, reps: int, rounds: int) -> dict:
     return res
 
 
+STREAM_RATE, STREAM_CHUNK, STREAM_CARRY = 24000, 12000, 500
+
+
+def _stream_entry(lib, dev, n_str: int, reps: int, rounds: int) -> dict:
+    rate, n, carry = STREAM_RATE, STREAM_CHUNK, STREAM_CARRY
+    slot = (n + 7) // 8 * 8
+    sig = _speech_like(carry + n, rate, 7)
+    pcm = torch.from_numpy(np.tile(np.concatenate([sig[carry:], np.zeros(slot - n, np.int16)]), n_str)).to(dev)
+    state = torch.zeros((n_str, 2048), dtype=torch.int16, device=dev)
+    state[:, :carry] = torch.from_numpy(sig[:carry].copy()).to(dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    A, S = adpcm.align(rate), adpcm.samples_per_block(rate)
+    nb = (carry + n) // S                                    # a push that is not final: whole blocks leave, the rest goes back to the slot
+    tab = np.zeros(n_str, _lib.ADPCM_PUSH)
+    room = (carry + n + 7) // 8 * 8
+    for k in range(n_str):
+        tab[k] = (k * slot, n, k * room, k * nb, k * nb * A, rate, k, carry, 0, -1, 0)
+    sizes = (C.c_int64 * 4)()
+    _lib.check(lib.ctts_adpcm_stream_sizes(tab.ctypes.data_as(C.c_void_p), n_str, n_str, pcm.numel(), sizes), "ctts_adpcm_stream_sizes")
+    out_s = torch.empty((int(sizes[1]),), dtype=torch.uint8, device=dev)
+    work = torch.empty((int(sizes[2]),), dtype=torch.uint8, device=dev)
+    tab_d = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
+    tab_p = tab.ctypes.data_as(C.c_void_p)
+    keep = state.clone()
+
+    def call_stream():
+        _lib.check(lib.ctts_adpcm_stream_step(pcm.data_ptr(), pcm.numel(), None, None, tab_d.data_ptr(), tab_p, n_str, state.data_ptr(), n_str,
+                                              out_s.data_ptr(), out_s.numel(), work.data_ptr(), work.numel(), st), "ctts_adpcm_stream_step")
+    call_stream()                                            # the check first: the timed calls go on from the carry this one leaves
+    got = out_s[: nb * A].cpu().numpy()
+    assert np.array_equal(got, adpcm.StreamEncoder(rate).push(sig)), "the device's blocks differ from the twin's"
+    assert work[: 8 * n_str].view(torch.int64).cpu().tolist() == [nb * S] * n_str
+    assert np.array_equal(state[0, : (carry + n) % S].cpu().numpy(), sig[nb * S:])
+    state.copy_(keep)
+    # the one-shot encoder over the same chunks
+    nb1 = adpcm.n_blocks(n, rate)
+    rtab = np.zeros(n_str, _lib.ADPCM_RANGE)
+    for k in range(n_str):
+        rtab[k] = (k * slot, n, k * nb1, k * nb1 * A, rate, -1, 0)
+    out_a = torch.empty((n_str * nb1 * A,), dtype=torch.uint8, device=dev)
+    used = torch.empty((n_str,), dtype=torch.int64, device=dev)
+    rtab_d = torch.from_numpy(rtab.view(np.uint8).copy()).to(dev)
+    rtab_p = rtab.ctypes.data_as(C.c_void_p)
+
+    def call_one_shot():
+        _lib.check(lib.ctts_adpcm_encode_ranges(pcm.data_ptr(), None, rtab_d.data_ptr(), rtab_p, n_str, out_a.data_ptr(), out_a.numel(),
+                                                used.data_ptr(), 8 * n_str, st), "ctts_adpcm_encode_ranges")
+    # ... and over chunks that a kernel has just written, as the conversion in front of a real encode leaves them (the buffer above is
+    # read-only and stays in every L2): a device copy of the chunks, then the same call; the copy alone beside it
+    fresh = torch.empty_like(pcm)
+
+    def call_copy():
+        fresh.copy_(pcm)
+
+    def call_fresh():
+        fresh.copy_(pcm)
+        _lib.check(lib.ctts_adpcm_encode_ranges(fresh.data_ptr(), None, rtab_d.data_ptr(), rtab_p, n_str, out_a.data_ptr(), out_a.numel(),
+                                                used.data_ptr(), 8 * n_str, st), "ctts_adpcm_encode_ranges")
+    res = _windows({"stream_step": call_stream, "one_shot": call_one_shot, "copy_then_one_shot": call_fresh, "copy": call_copy}, reps, rounds)
+    res["stream_step"].update(launches=2, blocks=n_str * nb, bytes=int(sizes[1]))
+    res["one_shot"].update(launches=1, blocks=n_str * nb1, bytes=n_str * nb1 * A)
+    res["copy_then_one_shot"].update(launches=2)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=None)
     ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--stream", action="store_true")
     a = ap.parse_args()
+    a.reps = a.reps or (500 if a.stream else 20)
     if not torch.cuda.is_available():
         raise SystemExit("adpcm_probe needs a GPU: nothing here can be timed without one")
     dev = torch.device("cuda:0")
     lib = _lib.lib()
+    if a.stream:
+        out = dict(metric="adpcm_stream_probe", rate=STREAM_RATE, chunk=STREAM_CHUNK, carry=STREAM_CARRY, reps=a.reps, rounds=a.rounds, entries={})
+        for n_str in (1, 16, 64):
+            out["entries"][f"x{n_str}"] = _stream_entry(lib, dev, n_str, a.reps, a.rounds)
+        print(json.dumps(out))
+        return
     out = dict(metric="adpcm_probe", seconds=SECONDS, reps=a.reps, rounds=a.rounds, entries={})
     for rate in (8000, 24000, 48000):
         for n_sig in (1, 8, 64):
