@@ -194,6 +194,8 @@ SIGNATURES = {
     "ctts_loudness_limited_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, I32, P, P, I32, P, P, P, P, P, P, P, SZ, P]),
     "ctts_peak_limit_ragged_scratch_bytes": (SZ, [P, I32]),
     "ctts_peak_limit_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, P, SZ, P]),
+    "ctts_compress_ragged_scratch_bytes": (SZ, [P, I32]),
+    "ctts_compress_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, P, P, I32, P, P, SZ, P]),
     "ctts_peak_limit_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P]),
     "ctts_trim_pauses_ragged_scratch_bytes": (SZ, [C.c_int64, I32]),
     "ctts_trim_pauses_ragged": (C.c_int, [P, P, P, P, P, P, P, P, I32, P, I32, P, P, P, SZ, P]),

@@ -284,7 +284,7 @@ class Chat:
             24, params.manual_seed, self.context, **kw))
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None, *,
-                       ragged: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None, limiter=None):
+                       ragged: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None, limiter=None, compress=None):
         """`Chat._decode_to_wavs` (core.py:513-539) -> np.float32 [B, n]: per-row hidden states [T_b,768] through the
         decoder, or (use_decoder=False) per-row token ids [T_b,4] through the full DVAE's codebook; then Vocos.
         `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded).
@@ -303,8 +303,11 @@ class Chat:
         `limiter` (None / False: off; True, also one flag per row): every flagged row goes through the look-ahead peak limiter on the
         device (CodecEngine.peak_limit; the definition of limiter.py) where the loudness stage is, behind its gain: that gain then
         drops the -1 dBFS ceiling term, and the limiter holds the ceiling sample by sample.  Without `loudness` it runs at unity
-        gain."""
-        plan = Plan.given("decode_to_wavs", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged)
+        gain.
+        `compress` (None / False: off; True or a dict of compressor.RANGES' fields, also a list with one per row, None entries copied
+        through): every row goes through the look-ahead compressor on the device (CodecEngine.compress; the definition of
+        compressor.py), behind `pauses` and in front of the loudness stage."""
+        plan = Plan.given("decode_to_wavs", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged, compress=compress)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
@@ -334,7 +337,7 @@ class Chat:
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
                         product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None,
-                        flac=None, loudness=None, pauses=None, limiter=None, adpcm=None) -> List[np.ndarray]:
+                        flac=None, loudness=None, pauses=None, limiter=None, adpcm=None, compress=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
@@ -363,8 +366,11 @@ class Chat:
         `adpcm` (None / False: the call above; True; with `ragged` also one flag per row): a flagged row comes back as a uint8 array, the
         complete WAVE_FORMAT_IMA_ADPCM file (chattts_amd/adpcm.py: 4 bits per sample) of exactly the int16 samples above at the row's
         rate, encoded on the device behind the conversion (CodecEngine.float_to_int16_groups_adpcm); not together with `flac`, nor
-        with an `encoding` on the same row."""
-        plan = Plan.given("decode_to_pcm16", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged)
+        with an `encoding` on the same row.
+        `compress` (None / False: off; True or a dict of compressor.RANGES' fields, also a list with one per row, None entries copied
+        through): `wav` above is the waveform behind the look-ahead compressor (CodecEngine.compress), every row alone -- behind
+        `pauses`, in front of the loudness stage and everything behind it."""
+        plan = Plan.given("decode_to_pcm16", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged, compress=compress)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
@@ -535,7 +541,7 @@ class Chat:
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None,
-                              speed=None, flac=None, loudness=None, pauses=None, limiter=None, adpcm=None) -> List[np.ndarray]:
+                              speed=None, flac=None, loudness=None, pauses=None, limiter=None, adpcm=None, compress=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
@@ -562,7 +568,10 @@ class Chat:
         sentences.  Without `loudness` it runs at unity gain.
         `adpcm` (None / False: the call above; True; or one flag per request): a flagged request comes back as a uint8 array, ONE
         WAVE_FORMAT_IMA_ADPCM file over its concatenated sentences at the request's rate (CodecEngine.float_to_int16_groups_adpcm);
-        not together with `flac`, nor with an `encoding` on the same request."""
+        not together with `flac`, nor with an `encoding` on the same request.
+        `compress` (None / False: off; a compressor spec, or a list with one per request, None entries copied through): every
+        SENTENCE is compressed alone (CodecEngine.compress) behind `pauses`: no window spans a join; the request's one gain is then
+        computed over its compressed sentences."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -574,14 +583,14 @@ class Chat:
         codec = self.codec
         encs, flags = self._formats(encoding, flac, len(groups), per_row=True, who="decode_split_to_pcm16", unit="request")
         aflags = self._adpcm_flags(adpcm, len(groups), encoding, flags, True, "decode_split_to_pcm16")
-        plan = Plan.given("decode_split_to_pcm16", sample_rate, speed, loudness, pauses, limiter)
+        plan = Plan.given("decode_split_to_pcm16", sample_rate, speed, loudness, pauses, limiter, compress=compress)
         rates = plan.row_rates(len(groups))
         if aflags is not None:
             for r in rates:
                 ADPCM.check_rate(r)
         plan = plan.per_sentence(groups)
         rows = [h for g in groups for h in g]
-        wav, off = codec.decode_ragged(rows, sample_rate=plan.sample_rate, **plan.kwargs("speed", "pauses"))
+        wav, off = codec.decode_ragged(rows, sample_rate=plan.sample_rate, **plan.kwargs("speed", "pauses", "compress"))
         if plan.levels:                                               # ONE gain per request: the stage runs here, over the group table
             wav = codec.loudness_normalize(wav, plan.loudness, offsets=off, groups=grp, out=wav, rates=plan.row_rates(len(rows)),
                                            **plan.kwargs("limiter"))
@@ -948,7 +957,8 @@ class Chat:
               *, pcm16: bool = False, ragged_decode: bool = False, sample_rate: int = 24000, stream_resample: bool = False,
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
               flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None,
-              stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False, adpcm: bool = False, stream_adpcm: bool = False):
+              stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False, adpcm: bool = False, stream_adpcm: bool = False,
+              compress=None):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -1054,7 +1064,15 @@ class Chat:
         they are an open-ended WAV file, whose reader cannot know the true length and decodes up to S - 1 padded samples behind the
         last real one.  The chunks are pushed on the device (CodecEngine.adpcm_stream_step; the placement and the host-twin
         fallback of a streamed FLAC), behind whatever `sample_rate` + `stream_resample`, `speed` + `stream_time_scale`, `limiter` +
-        `stream_limiter` and `pauses` + `stream_pauses` make of the stream.  Not with `split_text`, nor with `use_decoder=False`."""
+        `stream_limiter` and `pauses` + `stream_pauses` make of the stream.  Not with `split_text`, nor with `use_decoder=False`.
+        `compress` (keyword-only, non-streamed only; None / False: off): True (the defaults) or a dict with any of threshold_db, ratio,
+        knee_db, attack_ms, hold_ms (chattts_amd/compressor.py) -- one, or a list with one per text.  Every utterance goes through the
+        feed-forward look-ahead compressor on the device (CodecEngine.compress): levels above the threshold are brought down along a
+        soft-knee curve, block by block of 1 ms, with the gain ramped down ahead of a loud block and held behind it; no sample is
+        raised.  It is stage 3 1/2 of the output chain: behind the time scaler, the resampler and `pauses`, in front of the loudness
+        stage -- so the target is reached on compressed samples -- the limiter, the silence strip, the 16-bit conversion, the
+        companding and the file formats.  Every sentence of a split request is compressed alone (one spec only).  A streamed call
+        with it raises: a compressed stream would need the block state carried across chunks."""
         mkw = Plan.given("infer", limiter=limiter).kwargs()
         if gain_db is not None and np.ndim(gain_db) != 0:
             raise ValueError("gain_db is one make-up gain for the whole batch")
@@ -1096,6 +1114,14 @@ class Chat:
             raise ValueError("a split_text request is one waveform: it takes one pause spec")
         if pkw:
             PA.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+        ckw = Plan.given("infer", compress=compress).kwargs()
+        if ckw and stream:
+            raise ValueError("compress applies to non-streamed inference only (a compressed stream would need the block state carried "
+                             "across chunks)")
+        if ckw and split_text and isinstance(compress, list):
+            raise ValueError("a split_text request is one waveform: it takes one compressor spec")
+        if ckw:
+            LN.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         lkw = Plan.given("infer", loudness=loudness).kwargs()
         if lkw and stream:
             raise ValueError("loudness applies to non-streamed inference only (an integrated loudness needs the whole utterance; a "
@@ -1180,7 +1206,7 @@ class Chat:
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
                               sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}),
-                              **({} if split_host else lkw), **pkw, **smkw, **spkw, **akw)
+                              **({} if split_host else lkw), **pkw, **smkw, **spkw, **akw, **ckw)
         if stream:
             return res_gen
         if refine_text_only:
@@ -1190,7 +1216,7 @@ class Chat:
             if rows:
                 return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}),
                                                   **({} if encoding is None else {"encoding": encoding}), **skw,
-                                                  **({"flac": True} if flac else {}), **lkw, **pkw, **akw)
+                                                  **({"flac": True} if flac else {}), **lkw, **pkw, **akw, **ckw)
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
@@ -1222,7 +1248,7 @@ class Chat:
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None, pa_spec=None,
-               adpcm: bool = False):
+               adpcm: bool = False, compress=None):
         """core.py:395-503 (generator).  `pa_spec` with `stream`: the rows' pause streams and their spec (Chat.infer's `stream_pauses`).  `lm_gain` with `stream`: the rows' limiter streams and their pre-gain (Chat.infer's `stream_limiter`).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -1254,7 +1280,8 @@ class Chat:
                                            **({} if pauses is None else {"pauses": pauses}),
                                            **({} if limiter is None else {"limiter": limiter}),
                                            **({} if lm is None else {"lm": lm, "lm_gain": lm_gain}),
-                                           **({} if pa is None else {"pa": pa, "pa_spec": pa_spec}), **({"adpcm": True} if adpcm else {}))
+                                           **({} if pa is None else {"pa": pa, "pa_spec": pa_spec}), **({"adpcm": True} if adpcm else {}),
+                                           **({} if compress is None else {"compress": compress}))
         finally:
             for h in pa or ():
                 self.codec.trim_pauses_stream_close(h)
@@ -1270,7 +1297,7 @@ class Chat:
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
                        rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None, pa=None, pa_spec=None,
-                       adpcm: bool = False):
+                       adpcm: bool = False, compress=None):
         """the batch loop of `_infer`"""
         # the rows' encoder streams `fs` are FLAC streams, or with `adpcm` IMA ADPCM streams: the same placement, the same host twin
         Twin = ADPCM.StreamEncoder if adpcm else FLAC.StreamEncoder
@@ -1348,6 +1375,8 @@ class Chat:
                         rkw["limiter"] = limiter
                     if pauses is not None and not raw:
                         rkw["pauses"] = pauses[lo: lo + step] if isinstance(pauses, list) else pauses
+                    if compress is not None and not raw:
+                        rkw["compress"] = compress[lo: lo + step] if isinstance(compress, list) else compress
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
                         rows = [h.clone() for h in src]
                         result.destroy()

@@ -2172,6 +2172,48 @@ extern "C" int ctts_peak_limit_ragged(const float* x, float* y, const int64_t* o
                               (int32_t*)((char*)scratch + curve_bytes), (hipStream_t)stream));
   return 0;
 }
+// ---- the dynamic range compressor: every table is checked on its host mirror before the first launch -----------------------------------
+static_assert(sizeof(ctts_cp_stats) == 16 && CTTS_CP_TABLE == CP_TABLE, "ctts_cp_stats layout");
+extern "C" size_t ctts_compress_ragged_scratch_bytes(const int64_t* off_host, int32_t n_seg) {
+  if (loudness_offsets_check("ctts_compress_ragged_scratch_bytes", off_host, n_seg)) return 0;
+  return ((size_t)compress_blocks(off_host[n_seg], n_seg) * sizeof(float) + 15) / 16 * 16;
+}
+extern "C" int ctts_compress_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                    const int32_t* rate_dev, const int32_t* rate_host, const int32_t* par_dev, const int32_t* par_host,
+                                    const float* tab_dev, const float* tab_host, int32_t n_tab, void* stats, void* scratch,
+                                    size_t scratch_bytes, void* stream) {
+  const char* who = "ctts_compress_ragged";
+  if (!x || !y || !off_dev || !rate_dev || !rate_host || !par_dev || !par_host || !tab_dev || !tab_host || !stats)
+    return fail("%s: a null pointer (x, y, the stats and the offset, rate, parameter and gain tables on the device and the host are needed)", who);
+  if (loudness_offsets_check(who, off_host, n_seg)) return -1;
+  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)tab_dev & 15) || ((uintptr_t)stats & 3))
+    return fail("%s: x, y and the gain tables must be 16-byte aligned, the stats 4-byte aligned", who);
+  if (x != y && x < y + off_host[n_seg] && y < x + off_host[n_seg]) return fail("%s: y must be x itself or not overlap it", who);
+  if (n_tab < 1 || n_tab > n_seg) return fail("%s: need 1 <= n_tab <= n_seg gain tables (got %d for %d segments)", who, n_tab, n_seg);
+  for (int t = 0; t < n_tab; ++t)
+    for (int q = 0; q < CP_TABLE; ++q) {
+      const float g = tab_host[(size_t)t * CP_TABLE + q];
+      if (!(g >= 0x1p-18f && g <= 1.0f)) return fail("%s: table %d: entry %d is a gain in 2^-18 .. 1 (got %g)", who, t, q, (double)g);
+    }
+  long long nb_max = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    const int32_t fs = rate_host[i], A = par_host[4 * i], H = par_host[4 * i + 1], ti = par_host[4 * i + 2];
+    if (fs < 1000 * CP_BMIN || fs > 1000 * CP_BMAX || fs % 10 != 0)
+      return fail("%s: segment %d: the rate is a multiple of 10 Hz in %d .. %d (got %d)", who, i, 1000 * CP_BMIN, 1000 * CP_BMAX, fs);
+    if (A < 1 || A > CP_AMAX) return fail("%s: segment %d: the attack is 1 .. %d blocks (got %d)", who, i, CP_AMAX, A);
+    if (H < 0 || H > CP_HMAX) return fail("%s: segment %d: the hold is 0 .. %d blocks (got %d)", who, i, CP_HMAX, H);
+    if (ti < -1 || ti >= n_tab) return fail("%s: segment %d: gain table %d is outside the %d given (-1: the segment is copied through)", who, i, ti, n_tab);
+    const long long B = fs / 1000;
+    nb_max = std::max(nb_max, (long long)(off_host[i + 1] - off_host[i] + B - 1) / B);
+  }
+  const size_t need = ((size_t)compress_blocks(off_host[n_seg], n_seg) * sizeof(float) + 15) / 16 * 16;
+  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < need)
+    return fail("%s: scratch missing, not 16-byte aligned or too small (%zu bytes, need %zu)", who, scratch_bytes, need);
+  CttsDeviceGuard dg(stream);
+  CK(launch_compress_ragged(x, y, (const long long*)off_dev, n_seg, nb_max, rate_dev, par_dev, tab_dev, stats, (float*)scratch,
+                            (hipStream_t)stream));
+  return 0;
+}
 // ---- the limiter of streams: the host's arithmetic (limiter.py: stream_plan) and every check the launch trusts --------------------------
 static_assert(sizeof(ctts_lm_stream) == 80 && sizeof(LmStream) == 80 && offsetof(ctts_lm_stream, n_out) == offsetof(LmStream, n_out) &&
               offsetof(ctts_lm_stream, slot) == offsetof(LmStream, slot) && offsetof(ctts_lm_stream, c_out) == offsetof(LmStream, c_out) &&

@@ -572,6 +572,23 @@ struct LmStream {
 hipError_t launch_peak_limit_stream(const float* x, const LmStream* tab, int n_streams, long long n_out_max, float* y, float* carry,
                                     void* stats, int reset, hipStream_t st);
 
+// ---- dynamic range compressor (compressor.hip) ------------------------------------------------------
+#define CP_TILE 128           // blocks of one segment per workgroup of the apply launch: a sample tile is 128 B samples
+#define CP_PEAK_TILE 512      // blocks of one segment per workgroup of the peak launch, which stages the 4 KiB table
+#define CP_TABLE 1024         // float32 per gain table: 32 bins per octave over 2^-24 <= p < 2^8
+#define CP_Q0 3296            // bits(2^-24) >> 18
+#define CP_BMIN 8             // a block is B = fs / 1000 samples: 8 kHz ..
+#define CP_BMAX 48            // .. 48 kHz
+#define CP_AMAX 20            // the attack is 1 .. 20 blocks,
+#define CP_HMAX 500           // the hold 0 .. 500
+// block gains a pack of `total` samples in n_seg segments needs: segment s's blocks start at float off[s] / CP_BMIN + s
+static inline long long compress_blocks(long long total, int n_seg) { return total / CP_BMIN + n_seg + 1; }
+// packed segments x[off[s], off[s+1]) at rate[s] Hz with par[4 s ..] = A, H, the table (-1: copied through), 0 and tabs[n][CP_TABLE]:
+// y = g x (y may be x), stats[s] the segment's 16-byte record.  nb_max: the most blocks of a segment (grid sizes); cb:
+// compress_blocks(..) float32 of scratch.  A memset node and two launches.  Every bound is the caller's to check
+hipError_t launch_compress_ragged(const float* x, float* y, const long long* off, int n_seg, long long nb_max, const int32_t* rate,
+                                  const int32_t* par, const float* tabs, void* stats, float* cb, hipStream_t st);
+
 // ---- pause control (pauses.hip) -------------------------------------------------------------------
 #define PA_FMIN 80            // a frame is F = fs / 100 samples (integer division): 8 kHz ..
 #define PA_FMAX 480           // .. 48 kHz

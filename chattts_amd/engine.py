@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from . import adpcm as ADPCM
+from . import compressor as CP
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
@@ -2033,6 +2034,64 @@ class CodecEngine:
             return y, work[: LM.STATS.itemsize * n_seg].cpu().numpy().view(LM.STATS)
         return y
 
+    # -- dynamic range compressor (csrc/compressor.hip) ---------------------------------------------------------------------------------
+    def compress(self, wav: torch.Tensor, spec, offsets=None, rates=None, return_stats: bool = False, out=None):
+        """The look-ahead compressor on a float32 device tensor (ctts_compress_ragged; the definition of compressor.py): 1-D (one
+        signal), [B, n] (rows, each alone), or 1-D packed with `offsets` (n_seg + 1 sample offsets, the ragged decoder's layout;
+        every segment compressed as if alone, its windows never reach a neighbour).  `spec`: True (the defaults) or a dict with any
+        of threshold_db, ratio, knee_db, attack_ms, hold_ms -- one for all, or a list with one per segment; a segment whose spec is
+        None or False is copied through.  `rates`: the segments' sample rates in Hz (one, or one per segment; default 24000),
+        multiples of 10 in 8000 .. 48000: a block is 1 ms.  No sample is raised (g <= 1), and a segment whose block peaks all lie
+        under the knee comes back bit for bit.  Returns a tensor of the input's shape (`out`, when given: a float32 device tensor of
+        that shape, possibly `wav` itself), and with `return_stats` also the segments' records (a NumPy array of compressor.STATS:
+        the smallest gain, the blocks under the curve, the samples touched, the largest block peak).  A segment's samples and record
+        do not depend on what it is packed with.  ValueError before any launch: a bad spec, a rate out of range, an empty segment,
+        non-ascending offsets, 2^31 - 4096 samples, more than 65535 segments, no segment that asks for the compressor."""
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
+            raise ValueError("compress: a float32 device tensor, 1-D or [B, n]")
+        if offsets is not None and wav.dim() != 1:
+            raise ValueError("compress: offsets go with a packed 1-D tensor")
+        if wav.numel() == 0:
+            raise ValueError("compress: nothing to compress")
+        if wav.dim() == 2:
+            offsets = np.arange(wav.shape[0] + 1, dtype=np.int64) * int(wav.shape[1])
+        off, rt, par, tabs_h, _ = CP.tables(wav.numel(), spec, offsets, rates)
+        n_seg = len(off) - 1
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == wav.shape
+                                    and out.is_contiguous()):
+            raise ValueError("compress: out is a contiguous float32 device tensor of the input's shape")
+        x = wav.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()
+        y = out if out is not None and out.data_ptr() % 16 == 0 else torch.empty_like(x)
+        off_p = off.ctypes.data_as(C.c_void_p)
+        sb = int(self.lib.ctts_compress_ragged_scratch_bytes(off_p, n_seg))
+        if sb == 0:
+            _lib.check(-1, "ctts_compress_ragged")                # the offsets were refused: the library's message says why
+        dev = wav.device
+        tabs_h = np.ascontiguousarray(tabs_h)
+        host = [tabs_h.view(np.uint8).reshape(-1), off.view(np.uint8), rt.view(np.uint8), par.view(np.uint8).reshape(-1)]   # the gain tables first: 16-byte aligned
+        tabs = torch.from_numpy(np.concatenate(host)).to(dev)                                                              # one upload
+        rec_bytes = -(-CP.STATS.itemsize * n_seg // 16) * 16
+        work = torch.empty((rec_bytes + sb,), dtype=torch.uint8, device=dev)                                               # the records, then the scratch
+        st = torch.cuda.current_stream(dev)
+        base = tabs.data_ptr()
+        p_off = base + tabs_h.nbytes
+        _lib.check(self.lib.ctts_compress_ragged(
+            x.data_ptr(), y.data_ptr(), p_off, off_p, n_seg, p_off + off.nbytes, rt.ctypes.data_as(C.c_void_p),
+            p_off + off.nbytes + rt.nbytes, par.ctypes.data_as(C.c_void_p), base, tabs_h.ctypes.data_as(C.c_void_p), int(tabs_h.shape[0]),
+            work.data_ptr(), work.data_ptr() + rec_bytes, sb, st.cuda_stream), "ctts_compress_ragged")
+        tabs.record_stream(st)
+        work.record_stream(st)
+        x.record_stream(st)
+        if out is not None and y is not out:
+            out.copy_(y.view(out.shape))
+            y = out
+        y = y.view(wav.shape)
+        if return_stats:
+            return y, work[: CP.STATS.itemsize * n_seg].cpu().numpy().view(CP.STATS)
+        return y
+
     # -- the limiter of streams: per-stream device state (csrc/limiter.hip, limiter_stream_k) ---------------------------------------------
     LM_STREAM_SLOTS = 64      # the state pool's first size; it doubles when every slot is taken
 
@@ -2357,7 +2416,7 @@ class CodecEngine:
 
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
     def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None,
-                      limiter=None):
+                      limiter=None, compress=None):
         """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
         packed frames (ctts_dvae_decode_ragged / ctts_vocos_decode_ragged): each utterance gets zero padding at its own edges in every
         convolution, so its audio does not depend on what else is in the call -- unlike `decode_to_wavs`, whose zero-padded [B, Tmax]
@@ -2382,10 +2441,13 @@ class CodecEngine:
         offsets, read back from the device in the call's one extra copy.
         `limiter` (None: off; one bool, or one per row): a flagged row goes through the look-ahead peak limiter (`peak_limit`) behind
         the loudness stage's gain, which then drops its ceiling term (`loudness_normalize(limiter=)`); without `loudness` at unity
-        gain.  The rows that do not ask for it are not touched by it."""
+        gain.  The rows that do not ask for it are not touched by it.
+        `compress` (None: off): a compressor spec (True or a dict, `compressor.check`) -- one, or a list with one per row, None entries
+        copied through (`compress`, every row alone at its own rate, in place): behind `pauses` and in front of the loudness stage, so
+        the target is reached on compressed samples and the limiter still holds the ceiling."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
-        plan = OC.Plan.rows("decode_ragged", len(rows), sample_rate, speed, loudness, pauses, limiter)     # every refusal, before the decode
+        plan = OC.Plan.rows("decode_ragged", len(rows), sample_rate, speed, loudness, pauses, limiter, compress)     # every refusal, before the decode
         if plan.on:
             out = self.decode_ragged(rows, return_mel)                # the plain decode, through the public method
             return (*OC.run(self, out[0], plan, offsets=out[1], in_place=True), *out[2:])
@@ -3746,7 +3808,7 @@ class CodecEngine:
         return out
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None, sample_rate: Optional[int] = None,
-                       speed: Optional[float] = None, loudness=None, pauses=None, limiter=None) -> torch.Tensor:
+                       speed: Optional[float] = None, loudness=None, pauses=None, limiter=None, compress=None) -> torch.Tensor:
         """`Chat._decode_to_wavs` (core.py:513-539): zero-pad the per-row [T_b,768] hidden lists to the
         longest row, DVAE decode, Vocos decode -> [B, 256(2Tmax-1)] float32 on the device.  `pad_to`: pad to that many tokens instead
         (>= the longest row): a data-parallel shard decodes its rows as part of the GLOBAL batch (dist.infer_sharded) -- the reference
@@ -3759,10 +3821,12 @@ class CodecEngine:
         returned rate, behind the resampler and in front of the loudness stage, and the result is then (packed, offsets) instead of
         [B, n]: the rows' lengths differ.  `limiter` (None: off; one bool, or one per row): a flagged row, padding and all, goes
         through the look-ahead peak limiter (`peak_limit`) behind the loudness stage's gain, which then drops its ceiling term
-        (`loudness_normalize(limiter=)`); without `loudness` at unity gain."""
+        (`loudness_normalize(limiter=)`); without `loudness` at unity gain.  `compress` (None: off): a compressor spec, one or a
+        list with one per row (None entries copied through) -- every row, padding and all, is compressed alone (`compress`) at the
+        returned rate, behind `pauses` and in front of the loudness stage."""
         if len(result_list) == 0:
             return torch.empty((0,), dtype=torch.float32)
-        plan = OC.Plan.batch("decode_to_wavs", len(result_list), sample_rate, speed, loudness, pauses, limiter)   # every refusal, before the decode
+        plan = OC.Plan.batch("decode_to_wavs", len(result_list), sample_rate, speed, loudness, pauses, limiter, compress)   # every refusal, before the decode
         if plan.on:
             return OC.run(self, self.decode_to_wavs(result_list, pad_to), plan, in_place=True)   # the plain decode, through the public method
         longest = max(int(r.size(0)) for r in result_list)

@@ -98,7 +98,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
                stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
                pauses: bool = False, limiter: bool = False, stream_limiter: bool = False, stream_pauses: bool = False,
-               adpcm: bool = False, stream_adpcm: bool = False):
+               adpcm: bool = False, stream_adpcm: bool = False, compress: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -193,7 +193,14 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     cannot know the true length and decodes up to a block's worth of padded samples behind the last real one.  It is served from the
     pool with `batch_streams` (SpeechBatcher(stream_adpcm=True).submit_stream(adpcm_blocks=True)), serially otherwise
     (Chat.infer(stream=True, adpcm=True, stream_adpcm=True)), at the rates `stream_sample_rates` allows (below 55125 Hz), and
-    /health carries `"stream_adpcm": true`."""
+    /health carries `"stream_adpcm": true`.  `compress=True` (default off: every response, status, warning and /health list is as
+    without it, a `"compress"` key is ignored with the "unsupported parameters" warning): a non-streamed request body may carry
+    `"compress"`: true (the defaults) or an object with any of `threshold_db`, `ratio`, `knee_db`, `attack_ms`, `hold_ms`
+    (chattts_amd/compressor.py) -- the utterance goes through the look-ahead compressor on the device, behind `pauses` and in front of
+    the loudness stage, the limiter and the 16-bit conversion (Chat.infer(compress=) / SpeechBatcher.submit(compress=)), in whatever
+    format, rate and speed the other options allow; false or null leaves the dynamics alone; a bad spec gets a 400 with the
+    validator's message; `"stream": true` with it gets a 400 (a compressed stream would need the block state carried across chunks),
+    and /health carries `"compress": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -285,6 +292,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     if limiter_streams:
         from . import limiter as LM
         allowed = allowed | {"gain_db"}
+    if compress:
+        from . import compressor as CP
+        from . import loudness as LN
+        allowed = allowed | {"compress"}
 
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
         model: str = "tts-1"
@@ -310,8 +321,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
     def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None,
               as_flac: bool = False, lufs: Optional[float] = None, trim=None, lim: bool = False, gdb=None,
-              as_adpcm: bool = False):                                              # openai_api.py:168-183,207-222
+              as_adpcm: bool = False, comp=None):                                   # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if comp is not None:
+            kw = {**kw, "compress": comp}
         if lim:
             kw = {**kw, "limiter": True}
         if trim is not None:
@@ -413,6 +426,16 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     PA.check_stream(rate, trim)
                 except ValueError as e:
                     raise HTTPException(400, detail=str(e))
+        comp = None                                  # the request's compressor spec where it is honoured
+        if compress and request_data.get("compress") is not None and request_data["compress"] is not False:
+            try:
+                comp = CP.check(request_data["compress"], "compress")
+                LN.check_rate(rate)
+            except ValueError as e:
+                raise HTTPException(400, detail=str(e))
+            if req.stream:
+                raise HTTPException(400, detail="compress is served for non-streamed requests only: a compressed stream would need the "
+                                                "block state carried across chunks")
         lim = False                                  # the request's limiter flag where it is honoured
         if limiter and request_data.get("limiter") is not None:
             if not isinstance(request_data["limiter"], bool):
@@ -564,13 +587,17 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     rkw = {**rkw, "pauses": trim}
                 if lim:
                     rkw = {**rkw, "limiter": True}
+                if comp is not None:
+                    rkw = {**rkw, "compress": comp}
                 wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw, **ekw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:
             async with app.state.model_lock:
                 try:
-                    if lim:
+                    if comp is not None:
+                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, lim, **akw, comp=comp)
+                    elif lim:
                         wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, True, **akw)
                     elif trim is not None:
                         wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, **akw)
@@ -640,6 +667,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["stream_limiter"] = True
         if pause_streams:
             out["stream_pauses"] = True
+        if compress:
+            out["compress"] = True
         return out
 
     return app

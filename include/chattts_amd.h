@@ -467,6 +467,34 @@ size_t ctts_peak_limit_ragged_scratch_bytes(const int64_t* off_host, int32_t n_s
 int ctts_peak_limit_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg, const int32_t* rate_dev,
                            const int32_t* rate_host, const float* gain_dev, void* stats, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The dynamic range compressor (the definition, once, is chattts_amd/compressor.py): packed float32 segments x[off[s], off[s+1]) at
+ * rate[s] Hz (a multiple of 10 in 8000 .. 48000; a block is B = rate / 1000 samples, 1 ms), every segment as if alone.  par holds four
+ * int32 per segment: A (attack, 1 .. 20 blocks), H (hold, 0 .. 500 blocks), the index of its gain table (-1: the segment is copied
+ * through, its record {1, 0, 0, 0}) and 0.  tab holds n_tab tables of CTTS_CP_TABLE float32, the static curve as data: entry q is the
+ * gain at a block peak p with (bits(p) >> 18) - 3296 == q, 32 bins per octave over 2^-24 <= p < 2^8 (below: gain 1; above: the last
+ * entry); every entry lies in 2^-18 .. 1.  p the block's peak (a NaN does not count); c its table entry; m the minimum of c over H
+ * blocks back and A ahead (1 outside the segment); s the mean of m over blocks b - A .. b, a float64 sum and division rounded once to
+ * float32; a[b] = min(s[b-1], s[b]); sample t of block b gets g = a[b] + (a[b+1] - a[b]) (t / B) in float64, each operation rounded once,
+ * no fused multiply-add, rounded once more to float32; y = g x.  So g <= 1, a segment with every block under the knee comes back bit for
+ * bit, and a NaN passes through.  y may be x (otherwise the two do not overlap), both 16-byte aligned, as is tab_dev.
+ * stats: [n_seg] records of 16 bytes on the device (ctts_cp_stats).  A segment's samples and record do not depend on what it is packed
+ * with.  Every table is given on the device and the host (the two must agree).  Refused before anything is launched: a null pointer,
+ * offsets that do not ascend from 0, an empty segment, a pack of 2^31 - 4096 samples or more, more than 65535 segments, a rate outside
+ * the range or not a multiple of 10, A or H out of range, a table index outside -1 .. n_tab - 1, n_tab outside 1 .. n_seg, a table entry
+ * outside 2^-18 .. 1, misaligned buffers, y overlapping x in part, scratch under the companion function's size (0: the offsets were
+ * refused).  Stream-ordered: a memset of the records, the block peaks and their table entries (one float per block), gain and apply. */
+#define CTTS_CP_TABLE 1024
+typedef struct {
+  float min_gain;         /* the smallest g */
+  int32_t n_blocks;       /* blocks with c < 1 */
+  int32_t n_touched;      /* samples with g < 1 */
+  float peak;             /* the largest block peak */
+} ctts_cp_stats;          /* 16 bytes */
+size_t ctts_compress_ragged_scratch_bytes(const int64_t* off_host, int32_t n_seg);
+int ctts_compress_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg, const int32_t* rate_dev,
+                         const int32_t* rate_host, const int32_t* par_dev, const int32_t* par_host, const float* tab_dev,
+                         const float* tab_host, int32_t n_tab, void* stats, void* scratch, size_t scratch_bytes, void* stream);
+
 /* The limiter of STREAMS: the segment exists nowhere as a whole, it arrives in pushes, and each step returns the samples the pushes so
  * far decide.  y[i] depends on x[i - 2 W .. i + 2 W], so with pos samples in and more to come, samples [0, pos - 2 W) are out: a stream
  * lags by 2 W samples (20 ms).  One step of one stream: x[in_off, in_off + n_in) are samples [pos, pos + n_in); it writes samples
