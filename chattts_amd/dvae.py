@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import engine as _engine
 
 
 def pair_repack_k4s2(w4: torch.Tensor) -> torch.Tensor:
@@ -121,7 +122,7 @@ class DvaeEngine:
         T = int(self.lib.ctts_dvae_code_frames(n))
         codes = torch.empty((max(T, 0), self.G * self.R), dtype=torch.int32, device=self.device)
         nb = self.lib.ctts_dvae_encode_workspace_bytes(n)
-        ws = torch.empty((nb,), dtype=torch.uint8, device=self.device)
+        ws = _engine.device_scratch(nb, self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self.lib.ctts_dvae_encode(self.handle, wav.data_ptr(), n, codes.data_ptr(), ws.data_ptr(), nb, st), "ctts_dvae_encode")
         return codes.t().contiguous().cpu()
@@ -142,7 +143,7 @@ class DvaeEngine:
         B, T, _ = ids.shape
         mel = torch.empty((B, 2 * T, 100), dtype=torch.float32, device=self.device)
         nb = self.lib.ctts_dvae_decode_workspace_bytes(B, T)
-        ws = torch.empty((nb,), dtype=torch.uint8, device=self.device)
+        ws = _engine.device_scratch(nb, self.device)
         st = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self.lib.ctts_dvae_decode_codes(self.handle, ids.data_ptr(), mel.data_ptr(), B, T, ws.data_ptr(), nb, st),
                    "ctts_dvae_decode_codes")

@@ -37,6 +37,14 @@ from .weights import fold_weight_norm, gpt_layer_count
 log = logging.getLogger("chattts_amd")
 
 
+def device_scratch(nbytes: int, device) -> torch.Tensor:
+    """The ONE place that allocates memory the library carves itself: every workspace (`ctts_*_workspace_bytes`) and every stage
+    scratch (`ctts_*_scratch_bytes`) of this package comes from here, as `nbytes` uninitialised bytes on `device`.  The library may
+    assume nothing about their contents.  Callers reach it as `engine.device_scratch` (a module attribute looked up per call), so a
+    test can replace it and hand out guarded, pre-filled memory of exactly the declared size (tests/ws_arena.py)."""
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
 # ---------------------------------------------------------------------------------------------
 # logits-processor descriptors (mirror of gen_logits, /root/reference/ChatTTS/model/processors.py:38-58)
 # ---------------------------------------------------------------------------------------------
@@ -605,7 +613,7 @@ class GptEngine:
                     # the decode steps for one row per utterance
                     tc_ws = T if (prefill_chunk is None or int(prefill_chunk) >= T) else max(1, int(prefill_chunk))
                     ln.ws_bytes = max(lib.ctts_gpt_workspace_bytes(Bl, tc_ws), lib.ctts_gpt_workspace_bytes(Bl, 1))
-                    ln.workspace = torch.empty((ln.ws_bytes,), dtype=torch.uint8, device=dev)
+                    ln.workspace = device_scratch(ln.ws_bytes, dev)
                     ln.kv_start = torch.empty((Bl,), dtype=kv_start_all.dtype, device=dev)
                     ln.stop_d = None if stop_at is None else torch.empty((Bl,), dtype=torch.int32, device=dev)
                     ln.q_d = torch.empty((1,) if device_rng else (nq, Bl * nrow, V), dtype=torch.float32, device=dev)
@@ -1329,7 +1337,7 @@ class CodecEngine:
             if buf is not None:
                 buf.record_stream(cur)
             with torch.cuda.stream(cur):
-                self._ws_buf = buf = torch.empty((max(n, 0 if buf is None else buf.numel()),), dtype=torch.uint8, device=self.device)
+                self._ws_buf = buf = device_scratch(max(n, 0 if buf is None else buf.numel()), self.device)
             self._ws_stream = cur.cuda_stream
         return buf, buf.numel()
 
@@ -1890,7 +1898,7 @@ class CodecEngine:
             _lib.check(-1, "ctts_loudness_normalize_ragged")      # the offsets were refused: the library's message says why
         dev = wav.device
         tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), tgt.view(np.uint8), ridx.view(np.uint8), grp.view(np.uint8)])).to(dev)   # one upload
-        work = torch.empty((LN.STATS.itemsize * n_grp + sb,), dtype=torch.uint8, device=dev)             # the records, then the scratch
+        work = device_scratch(LN.STATS.itemsize * n_grp + sb, dev)                                       # the records, then the scratch
         st = torch.cuda.current_stream(dev)
         base = tabs.data_ptr()
         _lib.check(self.lib.ctts_loudness_normalize_ragged(
@@ -1924,7 +1932,7 @@ class CodecEngine:
             _lib.check(-1, "ctts_loudness_limited_ragged")
         dev = wav.device
         tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), tgt.view(np.uint8), ridx.view(np.uint8), grp.view(np.uint8), lmt.view(np.uint8)])).to(dev)
-        work = torch.empty((LN.STATS.itemsize * n_grp + sb,), dtype=torch.uint8, device=dev)             # the records, then the scratch
+        work = device_scratch(LN.STATS.itemsize * n_grp + sb, dev)                                       # the records, then the scratch
         gains = torch.empty((n_seg,), dtype=torch.float32, device=dev)
         st = torch.cuda.current_stream(dev)
         base = tabs.data_ptr()
@@ -2014,7 +2022,7 @@ class CodecEngine:
             _lib.check(-1, "ctts_peak_limit_ragged")              # the offsets were refused: the library's message says why
         dev = wav.device
         tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), rt.view(np.uint8), g.view(np.uint8)])).to(dev)   # one upload
-        work = torch.empty((-(-LM.STATS.itemsize * n_seg // 16) * 16 + sb,), dtype=torch.uint8, device=dev)          # the records, then the scratch
+        work = device_scratch(-(-LM.STATS.itemsize * n_seg // 16) * 16 + sb, dev)                                    # the records, then the scratch
         st = torch.cuda.current_stream(dev)
         base = tabs.data_ptr()
         _lib.check(self.lib.ctts_peak_limit_ragged(
@@ -2073,7 +2081,7 @@ class CodecEngine:
         host = [tabs_h.view(np.uint8).reshape(-1), off.view(np.uint8), rt.view(np.uint8), par.view(np.uint8).reshape(-1)]   # the gain tables first: 16-byte aligned
         tabs = torch.from_numpy(np.concatenate(host)).to(dev)                                                              # one upload
         rec_bytes = -(-CP.STATS.itemsize * n_seg // 16) * 16
-        work = torch.empty((rec_bytes + sb,), dtype=torch.uint8, device=dev)                                               # the records, then the scratch
+        work = device_scratch(rec_bytes + sb, dev)                                                                         # the records, then the scratch
         st = torch.cuda.current_stream(dev)
         base = tabs.data_ptr()
         p_off = base + tabs_h.nbytes
@@ -2262,7 +2270,7 @@ class CodecEngine:
         y = torch.empty_like(x)
         tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), fbase.view(np.uint8), rows.reshape(-1).view(np.uint8), fade.view(np.uint8)])).to(dev)   # one upload
         res_bytes = 8 * (n_seg + 1) + 4 * PA.REC * n_seg                                                  # off_out, then the records
-        work = torch.empty((-(-res_bytes // 16) * 16 + tb["scratch"],), dtype=torch.uint8, device=dev)
+        work = device_scratch(-(-res_bytes // 16) * 16 + tb["scratch"], dev)
         st = torch.cuda.current_stream(dev)
         base, wp = tabs.data_ptr(), work.data_ptr()
         _lib.check(self.lib.ctts_trim_pauses_ragged(
@@ -2393,7 +2401,7 @@ class CodecEngine:
         up = torch.from_numpy(np.concatenate([tab.view(np.uint8), fade.view(np.uint8)])).to(dev)              # one upload
         scratch = int(self.lib.ctts_trim_pauses_stream_scratch_bytes(frames, entries))
         res_bytes = -(-4 * 4 * n // 16) * 16
-        work = torch.empty((res_bytes + scratch,), dtype=torch.uint8, device=dev)
+        work = device_scratch(res_bytes + scratch, dev)
         pool = self._pa_pool()
         st = torch.cuda.current_stream(dev)
         _lib.check(self.lib.ctts_trim_pauses_stream_step(
@@ -2538,7 +2546,7 @@ class CodecEngine:
             blob = torch.empty((2 * E + hdr + (E + 15) // 16 * 16,), dtype=torch.uint8, device=dev)
             cnt_p, pcm_p = blob.data_ptr() + 2 * E, blob.data_ptr()
         tabs = torch.from_numpy(np.concatenate([off.view(np.uint8), grp.view(np.uint8)])).to(dev)      # one upload: offsets, then groups
-        work = torch.empty((4 * n_grp + sb,), dtype=torch.uint8, device=dev)                            # peaks, then the tile counts
+        work = device_scratch(4 * n_grp + sb, dev)                                                      # peaks, then the tile counts
         st = torch.cuda.current_stream(dev)
         _lib.check(self.lib.ctts_float_to_int16_groups(wav.data_ptr(), pcm_p, cnt_p, tabs.data_ptr(), off_p, n_seg,
                                                        tabs.data_ptr() + off.nbytes, grp_p, n_grp, {"f64": 0, "f32": 1}[product],

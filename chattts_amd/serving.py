@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import engine as _engine
 from . import adpcm as ADPCM
 from . import flac as FLAC
 from . import g711 as G711
@@ -303,7 +304,7 @@ class SlotPool:
             ptab = None if self.per_request else penalty_table(plan.penalty)
             self.ptab = None if ptab is None else ptab.to(dev)
             ws_bytes = self.lib.ctts_gpt_workspace_bytes(slots, 1)
-            self.ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+            self.ws = _engine.device_scratch(ws_bytes, dev)
         self.plan, self.min_new, self.eos = plan, int(min_new_token), int(eos_token)
         self.dec = self._state(B=slots, T=1, workspace=self.ws, row_map=None, n_active=self.n_active)
         self.st.synchronize()
@@ -474,7 +475,7 @@ class SlotPool:
                 for i, r in enumerate(reqs):
                     self.nonce_of[r.rid] = self._admit_no - n + 1 + i
             rmap = sl.to(torch.int32)
-            ws = torch.empty((self.lib.ctts_gpt_workspace_bytes(n, Tg),), dtype=torch.uint8, device=dev)
+            ws = _engine.device_scratch(self.lib.ctts_gpt_workspace_bytes(n, Tg), dev)
             pre = self._state(B=n, T=Tg, workspace=ws, row_map=rmap, n_active=None)
             _lib.check(self.lib.ctts_gpt_prefill(self.handle, C.byref(pre), emb.data_ptr(), self.st.cuda_stream), "ctts_gpt_prefill")
             self._keep = (ws, emb, rmap, sl)  # stream-ordered: stay alive until the next poll's sync, no extra sync here
