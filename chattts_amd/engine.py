@@ -28,6 +28,7 @@ from . import limiter as LM
 from . import outchain as OC
 from . import pauses as PA
 from . import resample as RS
+from . import statepool as SP
 from . import timescale as TS
 from ._sync import wait_event, wait_stream
 from .config import DVAE, GPT, VOCOS
@@ -1563,17 +1564,28 @@ class CodecEngine:
         return (y, path) if return_path else y
 
     # -- time scaling of streams: per-stream device state (csrc/timescale.hip, timescale_stream_k) ---------------------------------------
-    TS_STREAM_SLOTS = 64      # the state pool's first size; it doubles when every slot is taken
+    # Every streamed stage keeps its streams in a `statepool.StatePool` of its own, built on first use: label -> (the class attribute
+    # with the pool's first size -- it doubles when every slot is taken --, the device buffers' {name: (tail, dtype)}; the library is
+    # told the slot count and indexes them by slot).  The records are `statepool`'s: TimeScaleRec, ResampleRec, LimiterRec, PauseRec,
+    # FlacRec, AdpcmRec.
+    TS_STREAM_SLOTS = RS_STREAM_SLOTS = LM_STREAM_SLOTS = FLAC_STREAM_SLOTS = ADPCM_STREAM_SLOTS = 64
+    PA_STREAM_SLOTS = 16
+    ADPCM_CARRY = 2048        # int16 per slot: S - 1 = 2040 at 48 kHz
+    POOLS = {
+        "time_scale": ("TS_STREAM_SLOTS", dict(carry=((2, TS.CARRY), torch.float32), state=((4,), torch.int32))),
+        "resample": ("RS_STREAM_SLOTS", dict(carry=((2, RS.CARRY), torch.float32))),
+        "limiter": ("LM_STREAM_SLOTS", dict(carry=((2, LM.CARRY), torch.float32), stats=((4,), torch.int32))),      # one limiter.STATS record per slot
+        "pauses": ("PA_STREAM_SLOTS", dict(carry=((2, (PA.STREAM_FRAMES + 1) * 480), torch.float32), state=((PA.STATE,), torch.int32))),
+        "flac": ("FLAC_STREAM_SLOTS", dict(carry=((FLAC.MIN_BLOCK,), torch.int16))),
+        "adpcm": ("ADPCM_STREAM_SLOTS", dict(carry=((ADPCM_CARRY,), torch.int16))),
+    }
 
-    def _ts_pool(self) -> dict:
-        """the state pool: carry [slots, 2, TS.CARRY] float32 and state [slots, 4] int32 on the device, the free list, and per open
-        stream its host record [num, den, samples pushed, carry phase, done]"""
-        pool = self.__dict__.get("_ts_streams")
-        if pool is None:
-            n = int(self.TS_STREAM_SLOTS)
-            pool = self._ts_streams = dict(carry=torch.zeros((n, 2, TS.CARRY), dtype=torch.float32, device=self.device),
-                                           state=torch.zeros((n, 4), dtype=torch.int32, device=self.device), free=list(range(n - 1, -1, -1)), rec={})
-        return pool
+    def _pool(self, label: str) -> SP.StatePool:
+        pools = self.__dict__.setdefault("_pools", {})
+        if label not in pools:
+            slots, buffers = CodecEngine.POOLS[label]
+            pools[label] = SP.StatePool(label, getattr(self, slots), buffers, self.device)
+        return pools[label]
 
     def time_scale_stream_open(self, speed: float) -> int:
         """A stream of the time scaler at `speed` (0.5 .. 2.0, not 1): -> its handle, a slot of the engine's state pool.  The slot is
@@ -1582,63 +1594,41 @@ class CodecEngine:
         num, den = TS.quantize(speed)
         if num == den:
             raise ValueError("time_scale: the speed is 1, there is nothing to scale")
-        pool = self._ts_pool()
-        if not pool["free"]:
-            n = int(pool["carry"].shape[0])
-            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
-            pool["state"] = torch.cat([pool["state"], torch.zeros_like(pool["state"])])
-            pool["free"] = list(range(2 * n - 1, n - 1, -1))
-        slot = pool["free"].pop()
-        pool["rec"][slot] = [num, den, 0, 0, False]
-        return slot
+        return self._pool("time_scale").open(SP.TimeScaleRec(num, den, 0, 0, False))
 
     def time_scale_stream_close(self, handle: int) -> None:
         """gives the stream's slot back (any time: finished, or abandoned half way)"""
-        pool = self._ts_pool()
-        if pool["rec"].pop(int(handle), None) is None:
-            raise ValueError(f"time_scale: stream {handle} is not open")
-        pool["free"].append(int(handle))
+        self._pool("time_scale").close(handle)
 
     def time_scale_streams_in_use(self) -> int:
         """the streams that are open: slots of the state pool not on its free list"""
-        return len(self._ts_pool()["rec"])
+        return self._pool("time_scale").in_use
 
     def time_scale_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
         """`timescale.stream_plan` of the stream's next push: what a step with `n_in` more samples would run and emit"""
-        rec = self._ts_pool()["rec"].get(int(handle))
-        if rec is None:
-            raise ValueError(f"time_scale: stream {handle} is not open")
-        if rec[4]:
-            raise ValueError(f"time_scale: stream {handle} has had its last push")
-        return TS.stream_plan(rec[0] / rec[1], rec[2], n_in, final)
+        rec = self._pool("time_scale").live(handle)
+        return TS.stream_plan(rec.num / rec.den, rec.pushed, n_in, final)
 
     def _ts_descriptors(self, pushes):
         """pushes [(handle, in_off, n_in, final)], in the order given, a stream's pushes in ITS order -> (TS_STREAM table sorted into
         rounds with out_off / path_off unset, round_off, order: order[q] = the push behind row q, commit: handle -> its new host record).
         All in Python integers and before anything is launched; the records change only when the caller commits."""
-        recs = self._ts_pool()["rec"]
-        shadow, rounds = {}, []
-        for i, (h, in_off, n_in, final) in enumerate(pushes):
+        pool, commit, rows = self._pool("time_scale"), {}, []
+        for h, in_off, n_in, final in pushes:
             h = int(h)
-            if h not in recs:
-                raise ValueError(f"time_scale: stream {h} is not open")
-            num, den, pushed, phase, done, r = shadow.get(h, (*recs[h], 0))
-            if done:
-                raise ValueError(f"time_scale: stream {h} has had its last push")
-            p = TS.stream_plan(num / den, pushed, n_in, final)
-            row = (int(in_off), int(n_in), pushed, p["total"], 0, 0, p["k_prev"], p["k_now"], h, phase, num, den, p["n_out"], 0)
-            if r == len(rounds):
-                rounds.append([])
-            rounds[r].append((i, row, p["n_path"]))
-            shadow[h] = (num, den, pushed + int(n_in), phase ^ 1, bool(final), r + 1)
-        order = [i for rd in rounds for i, _, _ in rd]
+            rec = pool.live(h, commit)
+            p = TS.stream_plan(rec.num / rec.den, rec.pushed, n_in, final)
+            rows.append(((int(in_off), int(n_in), rec.pushed, p["total"], 0, 0, p["k_prev"], p["k_now"], h, rec.phase, rec.num, rec.den, p["n_out"], 0),
+                         p["n_path"]))
+            commit[h] = rec._replace(pushed=rec.pushed + int(n_in), phase=rec.phase ^ 1, done=bool(final))
+        _, members = SP.rounds(int(p[0]) for p in pushes)
+        order = [i for m in members for i in m]
         tab = np.zeros(len(order), _lib.TS_STREAM)
-        for q, (_, row, _) in enumerate(e for rd in rounds for e in rd):
-            tab[q] = row
-        n_path = [n for rd in rounds for _, _, n in rd]
-        round_off = np.zeros(len(rounds) + 1, np.int32)
-        np.cumsum([len(rd) for rd in rounds], out=round_off[1:])
-        return tab, round_off, order, n_path, {h: list(v[:5]) for h, v in shadow.items()}
+        for q, i in enumerate(order):
+            tab[q] = rows[i][0]
+        round_off = np.zeros(len(members) + 1, np.int32)
+        np.cumsum([len(m) for m in members], out=round_off[1:])
+        return tab, round_off, order, [rows[i][1] for i in order], commit
 
     def time_scale_stream_step(self, x: torch.Tensor, pushes, return_path: bool = False):
         """ONE step of many streams (ctts_time_scale_stream_step, one launch): `x`, a 1-D float32 device tensor, holds the new samples
@@ -1649,13 +1639,7 @@ class CodecEngine:
         refusal (ValueError here, EngineError from the library) comes before the launch and leaves all streams as they were."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
             raise ValueError("time_scale: a contiguous 1-D float32 device tensor")
-        if len(pushes) < 1:
-            raise ValueError("time_scale: nothing to step")
-        if len({int(p[0]) for p in pushes}) != len(pushes):
-            raise ValueError("time_scale: a stream appears twice in one step")
-        for _, in_off, n_in, _ in pushes:
-            if int(in_off) < 0 or int(n_in) < 0 or int(in_off) + int(n_in) > x.numel():
-                raise ValueError("time_scale: a push lies outside the tensor")
+        SP.check_pushes("time_scale", pushes, x.numel(), most=None)           # more than 1024: the library refuses
         tab, _, order, n_path, commit = self._ts_descriptors(pushes)
         assert order == list(range(len(pushes)))
         off = np.zeros(len(pushes) + 1, np.int64)
@@ -1663,32 +1647,20 @@ class CodecEngine:
         path_off = np.zeros(len(pushes) + 1, np.int64)
         np.cumsum(n_path, out=path_off[1:])
         tab["out_off"], tab["path_off"] = off[:-1], path_off[:-1]
-        pool = self._ts_pool()
+        pool = self._pool("time_scale")
         y = torch.empty((int(off[-1]),), dtype=torch.float32, device=x.device)
         path = torch.empty((int(path_off[-1]),), dtype=torch.int32, device=x.device)
         tab_d = torch.from_numpy(tab.view(np.uint8)).to(x.device)
         st = torch.cuda.current_stream(x.device)
         _lib.check(self.lib.ctts_time_scale_stream_step(
             x.data_ptr() if x.numel() else None, x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(tab),
-            y.data_ptr() if y.numel() else None, y.numel(), path.data_ptr() if path.numel() else None, path.numel(), pool["carry"].data_ptr(),
-            pool["state"].data_ptr(), int(pool["carry"].shape[0]), self._time_scale_window().data_ptr(), st.cuda_stream), "ctts_time_scale_stream_step")
+            y.data_ptr() if y.numel() else None, y.numel(), path.data_ptr() if path.numel() else None, path.numel(), pool.buf["carry"].data_ptr(),
+            pool.buf["state"].data_ptr(), pool.slots, self._time_scale_window().data_ptr(), st.cuda_stream), "ctts_time_scale_stream_step")
         tab_d.record_stream(st)
-        pool["rec"].update(commit)
+        pool.commit(commit)
         return (y, off, path, path_off) if return_path else (y, off)
 
     # -- sample-rate conversion of streams: per-stream device state (csrc/resample.hip, resample_stream_k) --------------------------------
-    RS_STREAM_SLOTS = 64      # the state pool's first size; it doubles when every slot is taken
-
-    def _rs_pool(self) -> dict:
-        """the state pool: carry [slots, 2, RS.CARRY] float32 on the device, the free list, and per open stream its host record
-        [orig, new, samples pushed, outputs emitted, carry phase, done]"""
-        pool = self.__dict__.get("_rs_streams")
-        if pool is None:
-            n = int(self.RS_STREAM_SLOTS)
-            pool = self._rs_streams = dict(carry=torch.zeros((n, 2, RS.CARRY), dtype=torch.float32, device=self.device),
-                                           free=list(range(n - 1, -1, -1)), rec={})
-        return pool
-
     def resample_stream_open(self, orig: int, new: int) -> int:
         """A stream of the resampler from `orig` to `new` Hz: -> its handle, a slot of the engine's state pool.  The slot is fresh by
         construction -- the first step of a stream reads no carry -- so nothing is cleared.  ValueError for a pair `resample` refuses,
@@ -1696,55 +1668,37 @@ class CodecEngine:
         L, M, K, _ = RS.plan(orig, new, [0, 1])
         if K - 1 > RS.CARRY:
             raise ValueError(f"resample: a stream {orig} -> {new} Hz would carry up to {K - 1} samples, a slot keeps {RS.CARRY}")
-        pool = self._rs_pool()
-        if not pool["free"]:
-            n = int(pool["carry"].shape[0])
-            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
-            pool["free"] = list(range(2 * n - 1, n - 1, -1))
-        slot = pool["free"].pop()
-        pool["rec"][slot] = [int(orig), int(new), 0, 0, 0, False]
-        return slot
+        return self._pool("resample").open(SP.ResampleRec(int(orig), int(new), 0, 0, 0, False))
 
     def resample_stream_close(self, handle: int) -> None:
         """gives the stream's slot back (any time: finished, or abandoned half way)"""
-        pool = self._rs_pool()
-        if pool["rec"].pop(int(handle), None) is None:
-            raise ValueError(f"resample: stream {handle} is not open")
-        pool["free"].append(int(handle))
+        self._pool("resample").close(handle)
 
     def resample_streams_in_use(self) -> int:
         """the streams that are open: slots of the state pool not on its free list"""
-        return len(self._rs_pool()["rec"])
+        return self._pool("resample").in_use
 
     def resample_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
         """`resample.stream_plan` of the stream's next push: what a step with `n_in` more samples would emit and keep"""
-        rec = self._rs_pool()["rec"].get(int(handle))
-        if rec is None:
-            raise ValueError(f"resample: stream {handle} is not open")
-        if rec[5]:
-            raise ValueError(f"resample: stream {handle} has had its last push")
-        L, M = RS.ratio(rec[0], rec[1])
-        return RS.stream_plan(L, M, RS.geometry(L, M)[1], rec[2], rec[3], n_in, final)
+        rec = self._pool("resample").live(handle)
+        L, M = RS.ratio(rec.orig, rec.new)
+        return RS.stream_plan(L, M, RS.geometry(L, M)[1], rec.pushed, rec.emitted, n_in, final)
 
     def _rs_descriptors(self, pushes):
         """pushes [(handle, in_off, n_in, final)], a stream's pushes in ITS order -> (RS_STREAM table with out_off / pad unset, sorted
         into groups, groups: [round, (orig, new), first row, end row] -- a stream's r-th push of the call lies in round r, a round's rows
         at one rate pair make one launch --, order: order[q] = the push behind row q, commit: handle -> its new host record).  All in
         Python integers and before anything is launched; the records change only when the caller commits."""
-        recs = self._rs_pool()["rec"]
-        shadow, rows = {}, []
+        pool, commit, rows = self._pool("resample"), {}, []
+        rnd, _ = SP.rounds(int(p[0]) for p in pushes)
         for i, (h, in_off, n_in, final) in enumerate(pushes):
             h = int(h)
-            if h not in recs:
-                raise ValueError(f"resample: stream {h} is not open")
-            orig, new, pushed, emitted, phase, done, r = shadow.get(h, (*recs[h], 0))
-            if done:
-                raise ValueError(f"resample: stream {h} has had its last push")
-            L, M = RS.ratio(orig, new)
-            p = RS.stream_plan(L, M, RS.geometry(L, M)[1], pushed, emitted, n_in, final)
-            rows.append((r, (orig, new), i, (int(in_off), int(n_in), pushed, p["total"], emitted, p["n_out"], 0, h, phase, p["carry_in"],
-                                             p["carry_out"], 0, 0)))
-            shadow[h] = (orig, new, pushed + int(n_in), p["emitted"], phase ^ 1, bool(final), r + 1)
+            rec = pool.live(h, commit)
+            L, M = RS.ratio(rec.orig, rec.new)
+            p = RS.stream_plan(L, M, RS.geometry(L, M)[1], rec.pushed, rec.emitted, n_in, final)
+            rows.append((rnd[i], (rec.orig, rec.new), i, (int(in_off), int(n_in), rec.pushed, p["total"], rec.emitted, p["n_out"], 0, h, rec.phase,
+                                                          p["carry_in"], p["carry_out"], 0, 0)))
+            commit[h] = rec._replace(pushed=rec.pushed + int(n_in), emitted=p["emitted"], phase=rec.phase ^ 1, done=bool(final))
         rows.sort(key=lambda e: e[:3])
         tab = np.zeros(len(rows), _lib.RS_STREAM)
         groups: list = []
@@ -1754,7 +1708,7 @@ class CodecEngine:
                 groups[-1][3] = q + 1
             else:
                 groups.append([r, pair, q, q + 1])
-        return tab, groups, [e[2] for e in rows], {h: list(v[:6]) for h, v in shadow.items()}
+        return tab, groups, [e[2] for e in rows], commit
 
     def resample_stream_step(self, x: torch.Tensor, pushes):
         """ONE step of many streams (ctts_resample_stream_step, one launch per distinct rate pair): `x`, a 1-D float32 device tensor,
@@ -1765,16 +1719,8 @@ class CodecEngine:
         library) comes before the first launch and leaves all streams as they were."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
             raise ValueError("resample: a contiguous 1-D float32 device tensor")
-        if len(pushes) < 1:
-            raise ValueError("resample: nothing to step")
-        if len({int(p[0]) for p in pushes}) != len(pushes):
-            raise ValueError("resample: a stream appears twice in one step")
-        for _, in_off, n_in, _ in pushes:
-            if int(in_off) < 0 or int(n_in) < 0 or int(in_off) + int(n_in) > x.numel():
-                raise ValueError("resample: a push lies outside the tensor")
+        SP.check_pushes("resample", pushes, x.numel())
         tab, groups, order, commit = self._rs_descriptors(pushes)
-        if len(tab) > 1024:
-            raise ValueError("resample: at most 1024 streams in one step")
         n_out = np.zeros(len(pushes), np.int64)
         n_out[order] = tab["n_out"]
         off = np.zeros(len(pushes) + 1, np.int64)
@@ -1782,7 +1728,7 @@ class CodecEngine:
         if int(off[-1]) >= 1 << 31:
             raise ValueError("resample: the output would hold 2^31 samples or more")
         tab["out_off"] = off[:-1][order]
-        pool = self._rs_pool()
+        pool = self._pool("resample")
         y = torch.empty((int(off[-1]),), dtype=torch.float32, device=x.device)
         tab_d = torch.from_numpy(tab.view(np.uint8)).to(x.device)
         st = torch.cuda.current_stream(x.device)
@@ -1790,10 +1736,10 @@ class CodecEngine:
             L, M = RS.ratio(orig, new)
             _lib.check(self.lib.ctts_resample_stream_step(
                 x.data_ptr() if x.numel() else None, x.numel(), tab_d.data_ptr() + lo * tab.itemsize, tab[lo:hi].ctypes.data_as(C.c_void_p),
-                hi - lo, y.data_ptr() if y.numel() else None, y.numel(), pool["carry"].data_ptr(), int(pool["carry"].shape[0]),
+                hi - lo, y.data_ptr() if y.numel() else None, y.numel(), pool.buf["carry"].data_ptr(), pool.slots,
                 self._resample_taps(orig, new).data_ptr(), L, M, RS.geometry(L, M)[1], st.cuda_stream), "ctts_resample_stream_step")
         tab_d.record_stream(st)
-        pool["rec"].update(commit)
+        pool.commit(commit)
         return y, off
 
     def time_scale_segments(self, wav: torch.Tensor, off, speeds):
@@ -2101,19 +2047,6 @@ class CodecEngine:
         return y
 
     # -- the limiter of streams: per-stream device state (csrc/limiter.hip, limiter_stream_k) ---------------------------------------------
-    LM_STREAM_SLOTS = 64      # the state pool's first size; it doubles when every slot is taken
-
-    def _lm_pool(self) -> dict:
-        """the state pool: carry [slots, 2, LM.CARRY] float32 and stats [slots, 4] int32 (one limiter.STATS record per slot) on the
-        device, the free list, and per open stream its host record [rate, pre-gain, samples pushed, samples emitted, carry phase, done]"""
-        pool = self.__dict__.get("_lm_streams")
-        if pool is None:
-            n = int(self.LM_STREAM_SLOTS)
-            pool = self._lm_streams = dict(carry=torch.zeros((n, 2, LM.CARRY), dtype=torch.float32, device=self.device),
-                                           stats=torch.zeros((n, 4), dtype=torch.int32, device=self.device),
-                                           free=list(range(n - 1, -1, -1)), rec={})
-        return pool
-
     def peak_limit_stream_open(self, rate: int, gain=1.0) -> int:
         """A stream of the limiter at `rate` Hz with the float32 pre-gain `gain` (any positive finite float32): -> its handle, a slot
         of the engine's state pool.  The slot is fresh by construction -- the first step of a stream reads no carry, and the step
@@ -2123,69 +2056,47 @@ class CodecEngine:
         g = np.float32(gain)
         if not (np.isfinite(g) and g > 0):
             raise ValueError("limiter: a pre-gain is a positive finite number")
-        pool = self._lm_pool()
-        if not pool["free"]:
-            n = int(pool["carry"].shape[0])
-            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
-            pool["stats"] = torch.cat([pool["stats"], torch.zeros_like(pool["stats"])])
-            pool["free"] = list(range(2 * n - 1, n - 1, -1))
-        slot = pool["free"].pop()
-        pool["rec"][slot] = [rate, g, 0, 0, 0, False]
-        return slot
+        return self._pool("limiter").open(SP.LimiterRec(rate, g, 0, 0, 0, False))
 
     def peak_limit_stream_close(self, handle: int) -> None:
         """gives the stream's slot back (any time: finished, or abandoned half way)"""
-        pool = self._lm_pool()
-        if pool["rec"].pop(int(handle), None) is None:
-            raise ValueError(f"limiter: stream {handle} is not open")
-        pool["free"].append(int(handle))
+        self._pool("limiter").close(handle)
 
     def peak_limit_streams_in_use(self) -> int:
         """the streams that are open: slots of the state pool not on its free list"""
-        return len(self._lm_pool()["rec"])
+        return self._pool("limiter").in_use
 
     def peak_limit_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
         """`limiter.stream_plan` of the stream's next push: what a step with `n_in` more samples would emit and keep"""
-        rec = self._lm_pool()["rec"].get(int(handle))
-        if rec is None:
-            raise ValueError(f"limiter: stream {handle} is not open")
-        if rec[5]:
-            raise ValueError(f"limiter: stream {handle} has had its last push")
-        return LM.stream_plan(rec[0] // 100, rec[2], rec[3], n_in, final)
+        rec = self._pool("limiter").live(handle)
+        return LM.stream_plan(rec.rate // 100, rec.pushed, rec.emitted, n_in, final)
 
     def peak_limit_stream_stats(self, handle: int) -> np.ndarray:
         """the stream's limiter.STATS record, counted over the samples emitted so far (a device read: it waits for the steps so far);
         after the last push it is `peak_limit`'s record of the whole signal.  Before the first push nothing has been counted."""
-        pool = self._lm_pool()
-        rec = pool["rec"].get(int(handle))
-        if rec is None:
-            raise ValueError(f"limiter: stream {handle} is not open")
+        pool = self._pool("limiter")
+        rec = pool.get(handle)
         out = np.zeros((), dtype=LM.STATS)
-        if rec[2] == 0:                                           # the slot's record is reset by the step of the first push
-            out["g32"], out["min_gain"] = rec[1], 1.0
+        if rec.pushed == 0:                                       # the slot's record is reset by the step of the first push
+            out["g32"], out["min_gain"] = rec.gain, 1.0
             return out
-        return pool["stats"][int(handle)].cpu().numpy().view(LM.STATS)[0]
+        return pool.buf["stats"][int(handle)].cpu().numpy().view(LM.STATS)[0]
 
     def _lm_descriptors(self, pushes):
         """pushes [(handle, in_off, n_in, final)], one per stream -> (LM_STREAM table with out_off unset, in the pushes' order,
         commit: handle -> its new host record).  All in Python integers and before anything is launched; the records change only
         when the caller commits."""
-        recs = self._lm_pool()["rec"]
+        pool, commit = self._pool("limiter"), {}
         tab = np.zeros(len(pushes), _lib.LM_STREAM)
-        commit = {}
         for i, (h, in_off, n_in, final) in enumerate(pushes):
             h = int(h)
-            if h not in recs:
-                raise ValueError(f"limiter: stream {h} is not open")
             if h in commit:
                 raise ValueError("limiter: a stream appears twice in one step")
-            rate, g, pushed, emitted, phase, done = recs[h]
-            if done:
-                raise ValueError(f"limiter: stream {h} has had its last push")
-            p = LM.stream_plan(rate // 100, pushed, emitted, n_in, final)
-            tab[i] = (int(in_off), int(n_in), pushed, p["total"] if final else -1, emitted, p["n_out"], 0, h, phase, p["carry_in"],
-                      p["carry_out"], rate, g)
-            commit[h] = [rate, g, p["total"], p["emitted"], phase ^ 1, bool(final)]
+            rec = pool.live(h)
+            p = LM.stream_plan(rec.rate // 100, rec.pushed, rec.emitted, n_in, final)
+            tab[i] = (int(in_off), int(n_in), rec.pushed, p["total"] if final else -1, rec.emitted, p["n_out"], 0, h, rec.phase, p["carry_in"],
+                      p["carry_out"], rec.rate, rec.gain)
+            commit[h] = rec._replace(pushed=p["total"], emitted=p["emitted"], phase=rec.phase ^ 1, done=bool(final))
         return tab, commit
 
     def peak_limit_stream_step(self, x: torch.Tensor, pushes, out: Optional[torch.Tensor] = None, out_off=None):
@@ -2203,13 +2114,7 @@ class CodecEngine:
         if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 1
                                     and out.is_contiguous() and out_off is not None and len(out_off) == len(pushes)):
             raise ValueError("limiter: out is a contiguous 1-D float32 device tensor, with one offset per push")
-        if len(pushes) < 1:
-            raise ValueError("limiter: nothing to step")
-        if len(pushes) > 1024:
-            raise ValueError("limiter: at most 1024 streams in one step")
-        for _, in_off, n_in, _ in pushes:
-            if int(in_off) < 0 or int(n_in) < 0 or int(in_off) + int(n_in) > x.numel():
-                raise ValueError("limiter: a push lies outside the tensor")
+        SP.check_pushes("limiter", pushes, x.numel(), once=False)             # a stream twice: `_lm_descriptors` refuses
         tab, commit = self._lm_descriptors(pushes)
         off = np.zeros(len(pushes) + 1, np.int64)
         np.cumsum(tab["n_out"], out=off[1:])
@@ -2223,15 +2128,15 @@ class CodecEngine:
             if np.any(off < 0) or np.any(off + tab["n_out"] > out.numel()):
                 raise ValueError("limiter: a chunk lies outside `out`")
             tab["out_off"], y = off, out
-        pool = self._lm_pool()
+        pool = self._pool("limiter")
         tab_d = torch.from_numpy(tab.view(np.uint8)).to(x.device)
         st = torch.cuda.current_stream(x.device)
         _lib.check(self.lib.ctts_peak_limit_stream_step(
             x.data_ptr() if x.numel() else None, x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(tab),
-            y.data_ptr() if y.numel() else None, y.numel(), pool["carry"].data_ptr(), pool["stats"].data_ptr(), int(pool["carry"].shape[0]),
+            y.data_ptr() if y.numel() else None, y.numel(), pool.buf["carry"].data_ptr(), pool.buf["stats"].data_ptr(), pool.slots,
             st.cuda_stream), "ctts_peak_limit_stream_step")
         tab_d.record_stream(st)
-        pool["rec"].update(commit)
+        pool.commit(commit)
         return y, off
 
     # -- pause control (csrc/pauses.hip) ------------------------------------------------------------------------------------------------
@@ -2289,74 +2194,46 @@ class CodecEngine:
         return out[0] if len(out) == 1 else out
 
     # -- pause control of streams: per-stream device state (csrc/pauses.hip, pause_stream_walk_k) -----------------------------------------
-    PA_STREAM_SLOTS = 16      # the state pool's first size; it doubles when every slot is taken
-
-    def _pa_pool(self) -> dict:
-        """the state pool: carry [slots, 2, (PA.STREAM_FRAMES + 1) * 480] float32 and state [slots, PA.STATE] int32 on the device, the
-        free list, and per open stream its host record [rate, spec, samples pushed, carry phase, done, frames held, samples emitted]"""
-        pool = self.__dict__.get("_pa_streams")
-        if pool is None:
-            n = int(self.PA_STREAM_SLOTS)
-            pool = self._pa_streams = dict(carry=torch.zeros((n, 2, (PA.STREAM_FRAMES + 1) * 480), dtype=torch.float32, device=self.device),
-                                           state=torch.zeros((n, PA.STATE), dtype=torch.int32, device=self.device),
-                                           free=list(range(n - 1, -1, -1)), rec={})
-        return pool
-
     def trim_pauses_stream_open(self, rate: int, spec=True) -> int:
         """A pause stream at `rate` Hz with `spec` (True: the defaults, a `pauses.PauseSpec` or a dict of its fields): -> its handle, a
         slot of the engine's state pool.  The slot is fresh by construction -- the step that carries a stream's first sample reads
         neither state nor carry -- so nothing is cleared here.  ValueError: a bad rate or spec, no spec, a spec that makes a stream
         hold more than `pauses.STREAM_FRAMES` frames."""
         rate, spec = PA.check_stream(rate, spec)
-        pool = self._pa_pool()
-        if not pool["free"]:
-            n = int(pool["carry"].shape[0])
-            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
-            pool["state"] = torch.cat([pool["state"], torch.zeros_like(pool["state"])])
-            pool["free"] = list(range(2 * n - 1, n - 1, -1))
-        slot = pool["free"].pop()
-        pool["rec"][slot] = [rate, spec, 0, 0, False, 0, 0]
-        return slot
+        return self._pool("pauses").open(SP.PauseRec(rate, spec, 0, 0, False, 0, 0))
 
     def trim_pauses_stream_close(self, handle: int) -> None:
         """gives the stream's slot back (any time: finished, or abandoned half way)"""
-        pool = self._pa_pool()
-        if pool["rec"].pop(int(handle), None) is None:
-            raise ValueError(f"pauses: stream {handle} is not open")
-        pool["free"].append(int(handle))
+        self._pool("pauses").close(handle)
 
     def trim_pauses_streams_in_use(self) -> int:
         """the streams that are open: slots of the state pool not on its free list"""
-        return len(self._pa_pool()["rec"])
+        return self._pool("pauses").in_use
 
     def trim_pauses_stream_stats(self, handle: int) -> dict:
         """the stream so far: `record` (int32 [8], `pauses.RECORD`, a device read that waits for the steps so far; after the last push
         it is `trim_pauses`' record of the whole signal, all zero for a stream that ended empty), `pushed` and `emitted` samples,
         `held` frames that wait, `done`"""
-        pool = self._pa_pool()
-        rec = pool["rec"].get(int(handle))
-        if rec is None:
-            raise ValueError(f"pauses: stream {handle} is not open")
-        record = np.zeros(PA.REC, dtype=np.int32) if rec[2] == 0 else pool["state"][int(handle), 3: 3 + PA.REC].cpu().numpy()
-        return dict(record=record, pushed=rec[2], emitted=rec[6], held=rec[5], done=rec[4])
+        pool = self._pool("pauses")
+        rec = pool.get(handle)
+        record = np.zeros(PA.REC, dtype=np.int32) if rec.pushed == 0 else pool.buf["state"][int(handle), 3: 3 + PA.REC].cpu().numpy()
+        return dict(record=record, pushed=rec.pushed, emitted=rec.emitted, held=rec.held, done=rec.done)
 
     def _pa_descriptors(self, pushes):
         """pushes [(handle, in_off, n_in, final)], one per stream -> (PA_STREAM table, the distinct frames' fade tables one behind the
-        other, commit: handle -> [samples pushed, carry phase, done] behind the step).  All in Python integers and before anything is
-        launched; the records change only when the caller commits.  A stream's chunk gets room for what may wait and what arrives."""
-        recs = self._pa_pool()["rec"]
+        other, commit: handle -> its host record behind the step, `held` and `emitted` as they were: the step's copy brings those).
+        All in Python integers and before anything is launched; the records change only when the caller commits.  A stream's chunk
+        gets room for what may wait and what arrives."""
+        pool = self._pool("pauses")
         tab = np.zeros(len(pushes), _lib.PA_STREAM)
         commit, fade_off, parts = {}, {}, []
         out = fr = ls = 0
         for i, (h, in_off, n_in, final) in enumerate(pushes):
             h, in_off, n_in = int(h), int(in_off), int(n_in)
-            if h not in recs:
-                raise ValueError(f"pauses: stream {h} is not open")
             if h in commit:
                 raise ValueError("pauses: a stream appears twice in one step")
-            rate, spec, pushed, phase, done = recs[h][:5]
-            if done:
-                raise ValueError(f"pauses: stream {h} has had its last push")
+            rec = pool.live(h)
+            rate, spec, pushed, phase = rec.rate, rec.spec, rec.pushed, rec.phase
             if n_in < 0 or in_off < 0:
                 raise ValueError("pauses: a push cannot be negative")
             if pushed + n_in >= 1 << 31:
@@ -2370,7 +2247,7 @@ class CodecEngine:
             n_list = 2 * need + nf + 1
             tab[i] = (in_off, n_in, pushed, out, fr, ls, h, phase, need, int(bool(final)), F, pad, lead, tail, P, thr, fade_off[F], n_list)
             out, fr, ls = out + need * F + avail, fr + nf, ls + n_list
-            commit[h] = [pushed + n_in, phase ^ 1, bool(final)]
+            commit[h] = rec._replace(pushed=pushed + n_in, phase=phase ^ 1, done=bool(final))
         if out >= 1 << 31:
             raise ValueError("pauses: the output would hold 2^31 samples or more")
         return tab, np.ascontiguousarray(np.concatenate(parts)), commit
@@ -2386,13 +2263,7 @@ class CodecEngine:
         before the first launch and leaves all streams as they were."""
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
             raise ValueError("pauses: a contiguous 1-D float32 device tensor")
-        if len(pushes) < 1:
-            raise ValueError("pauses: nothing to step")
-        if len(pushes) > 1024:
-            raise ValueError("pauses: at most 1024 streams in one step")
-        for _, in_off, n_in, _ in pushes:
-            if int(in_off) < 0 or int(n_in) < 0 or int(in_off) + int(n_in) > x.numel():
-                raise ValueError("pauses: a push lies outside the tensor")
+        SP.check_pushes("pauses", pushes, x.numel(), once=False)              # a stream twice: `_pa_descriptors` refuses
         tab, fade, commit = self._pa_descriptors(pushes)
         n, dev = len(tab), x.device
         room = int(tab["out_off"][-1]) + int(tab["need"][-1]) * int(tab["F"][-1]) + int(tab["pos"][-1]) % int(tab["F"][-1]) + int(tab["n_in"][-1])
@@ -2402,20 +2273,17 @@ class CodecEngine:
         scratch = int(self.lib.ctts_trim_pauses_stream_scratch_bytes(frames, entries))
         res_bytes = -(-4 * 4 * n // 16) * 16
         work = device_scratch(res_bytes + scratch, dev)
-        pool = self._pa_pool()
+        pool = self._pool("pauses")
         st = torch.cuda.current_stream(dev)
         _lib.check(self.lib.ctts_trim_pauses_stream_step(
             x.data_ptr() if x.numel() else None, x.numel(), up.data_ptr(), tab.ctypes.data_as(C.c_void_p), n, y.data_ptr() if room else None, room,
-            pool["carry"].data_ptr(), pool["state"].data_ptr(), int(pool["carry"].shape[0]), up.data_ptr() + tab.nbytes, int(fade.size),
+            pool.buf["carry"].data_ptr(), pool.buf["state"].data_ptr(), pool.slots, up.data_ptr() + tab.nbytes, int(fade.size),
             work.data_ptr(), work.data_ptr() + res_bytes, scratch, st.cuda_stream), "ctts_trim_pauses_stream_step")
         up.record_stream(st)
         work.record_stream(st)
         x.record_stream(st)
         res = work[: 16 * n].cpu().numpy().view(np.int32).reshape(n, 4)                                       # the one copy, and the one wait
-        for i, (h, _, _, _) in enumerate(pushes):
-            rec = pool["rec"][int(h)]
-            rec[2:5] = commit[int(h)]
-            rec[5], rec[6] = int(res[i, 1]), rec[6] + int(res[i, 0])
+        pool.commit({h: rec._replace(held=int(res[i, 1]), emitted=rec.emitted + int(res[i, 0])) for i, (h, rec) in enumerate(commit.items())})  # in push order
         off = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(res[:, 0], out=off[1:])
         if n == 1:
@@ -2715,47 +2583,13 @@ class CodecEngine:
         device, an empty crop still steps its stream, several windows of one stream go to successive rounds.  ONE `adpcm_stream_step`
         for the flagged windows of the call (two launches; where no tail is stripped, one copy: the blocks).  A window takes FLAC or
         ADPCM, not both; neither goes with an encoding."""
-        pa = None
-        if pauses is not None and any(f is not None and f is not False for f in pauses):
-            if len(pauses) != len(windows) or pa_streams is None or len(pa_streams) != len(windows):
-                raise ValueError("decode_windows: one pauses flag and one pa_streams entry per window")
-            pa_recs, ended = self._pa_pool()["rec"], set()
-            for i, (f, h) in enumerate(zip(pauses, pa_streams)):
-                if f is not None and f is not False:
-                    want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
-                    if h is None or int(h) not in pa_recs or pa_recs[int(h)][0] != want:
-                        raise ValueError(f"decode_windows: window {i} needs an open pause stream at {want} Hz")
-                    if pa_recs[int(h)][4] or int(h) in ended:
-                        raise ValueError(f"decode_windows: window {i}: pause stream {int(h)} has had its last push")
-                    if len(windows[i]) > 4 and bool(windows[i][4]):
-                        ended.add(int(h))
-                elif h is not None:
-                    raise ValueError(f"decode_windows: window {i} has no pauses flag but names a pause stream")
-            pa = [int(h) if (f is not None and f is not False) else None for f, h in zip(pauses, pa_streams)]
-        elif pa_streams is not None and any(h is not None for h in pa_streams):
-            raise ValueError("decode_windows: pa_streams without a pauses flag")
-        lm = None
-        if limiter is not None and any(bool(f) for f in limiter):
-            if len(limiter) != len(windows) or lm_streams is None or len(lm_streams) != len(windows):
-                raise ValueError("decode_windows: one limiter flag and one lm_streams entry per window")
-            lm_recs, ended = self._lm_pool()["rec"], set()
-            for i, (f, h) in enumerate(zip(limiter, lm_streams)):
-                if LM.check_flag(f, "decode_windows"):
-                    want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
-                    if h is None or int(h) not in lm_recs or lm_recs[int(h)][0] != want:
-                        raise ValueError(f"decode_windows: window {i} needs an open limiter stream at {want} Hz")
-                    if lm_recs[int(h)][5] or int(h) in ended:
-                        raise ValueError(f"decode_windows: window {i}: limiter stream {int(h)} has had its last push")
-                    if len(windows[i]) > 4 and bool(windows[i][4]):
-                        ended.add(int(h))
-                elif h is not None:
-                    raise ValueError(f"decode_windows: window {i} has no limiter flag but names a limiter stream")
-            lm = [int(h) if f else None for f, h in zip(limiter, lm_streams)]
-        elif lm_streams is not None and any(h is not None for h in lm_streams):
-            raise ValueError("decode_windows: lm_streams without a limiter flag")
+        pa = self._window_streams("pauses", "pa_streams", "pause", pauses, pa_streams, windows, sample_rates,
+                                  flagged=lambda f: f is not None and f is not False)
+        lm = self._window_streams("limiter", "lm_streams", "limiter", limiter, lm_streams, windows, sample_rates,
+                                  flagged=lambda f: LM.check_flag(f, "decode_windows"), any_flag=bool)
         fl = None
-        fl_h = self._window_streams("flac", "FLAC", flac, flac_streams, windows, pcm16, sample_rates, encodings, self._flac_rec)
-        ad_h = self._window_streams("adpcm", "ADPCM", adpcm, adpcm_streams, windows, pcm16, sample_rates, encodings, self._adpcm_rec)
+        fl_h = self._window_codec("flac", "FLAC", flac, flac_streams, windows, pcm16, sample_rates, encodings)
+        ad_h = self._window_codec("adpcm", "ADPCM", adpcm, adpcm_streams, windows, pcm16, sample_rates, encodings)
         if fl_h is not None or ad_h is not None:
             if fl_h is not None and ad_h is not None and any(f is not None and a is not None for f, a in zip(fl_h, ad_h)):
                 raise ValueError("decode_windows: a window takes FLAC or ADPCM, not both")
@@ -2934,13 +2768,7 @@ class CodecEngine:
         x = torch.cat(bufs) if len(bufs) > 1 else bufs[0] if bufs else torch.zeros((8,), dtype=torch.float32, device=self.device)
         tails = [len(windows[i]) > 4 and bool(windows[i][4]) for i in idx]
         # the pause streams' steps, in front of the limiter's: the r-th window of a stream in round r; what a step emits lies behind x
-        seen, prounds = {}, []
-        for k, i in enumerate(idx):
-            if pa[i] is not None:
-                r = seen[pa[i]] = seen.get(pa[i], -1) + 1
-                if r == len(prounds):
-                    prounds.append([])
-                prounds[r].append(k)
+        _, prounds = SP.rounds(pa[i] for i in idx)
         if prounds:
             parts, base = [x], x.numel()
             for rnd in prounds:
@@ -2951,19 +2779,17 @@ class CodecEngine:
                 base += y.numel()
             x = torch.cat(parts)
         # the limiter's steps: the r-th window of a stream in round r; the limited chunks start on multiples of 8 samples, zeros between
-        recs, shadow, rounds = self._lm_pool()["rec"], {}, []
+        recs, shadow = self._pool("limiter").records, {}
+        _, rounds = SP.rounds(lm[i] for i in idx)
         n = np.zeros(len(idx), np.int64)
         for k, i in enumerate(idx):
             if lm[i] is None:                                      # paused only: the chunk goes on as it came out
                 n[k] = src.get(i, (0, 0))[1]
                 continue
-            pushed, emitted, r = shadow.get(lm[i], (recs[lm[i]][2], recs[lm[i]][3], 0))
-            p = LM.stream_plan(recs[lm[i]][0] // 100, pushed, emitted, src.get(i, (0, 0))[1], tails[k])
+            rec = shadow.get(lm[i], recs[lm[i]])
+            p = LM.stream_plan(rec.rate // 100, rec.pushed, rec.emitted, src.get(i, (0, 0))[1], tails[k])
             n[k] = p["n_out"]
-            shadow[lm[i]] = (p["total"], p["emitted"], r + 1)
-            if r == len(rounds):
-                rounds.append([])
-            rounds[r].append(k)
+            shadow[lm[i]] = rec._replace(pushed=p["total"], emitted=p["emitted"])
         keep = np.array([t and keep_thr is not None for t in tails], dtype=bool)
         off = np.zeros(len(idx) + 1, np.int64)
         np.cumsum((n + 7) // 8 * 8, out=off[1:])
@@ -3003,40 +2829,58 @@ class CodecEngine:
                                                    [(fl[0][i], 0, 0, fl[1][i]) for i in idle], out)]
         return out
 
-    def _window_streams(self, arg: str, name: str, flags, streams, windows, pcm16: bool, sample_rates, encodings, rec):
-        """the flags and streams of one output format of a `decode_windows` call (`arg` / `name`: flac / FLAC, adpcm / ADPCM; `rec`: a
-        handle's open record, its rate first), checked -> per window (arg, handle) or None; None when no window is flagged"""
-        an = "an" if arg[0] == "a" else "a"
-        if flags is not None and any(bool(f) for f in flags):
-            if len(flags) != len(windows) or streams is None or len(streams) != len(windows):
-                raise ValueError(f"decode_windows: one {arg} flag and one {arg}_streams entry per window")
+    def _window_streams(self, arg: str, arg_streams: str, name: str, flags, streams, windows, sample_rates, flagged=bool, any_flag=None,
+                        ends: bool = True, also=None):
+        """The flags and streams of one streamed stage of a `decode_windows` call, checked -> per window its stream's handle or None;
+        None when no window is flagged.  `arg` (the stage's pool has that label) / `arg_streams`: the two arguments' names; `name`:
+        what the messages call the stream.  `flagged`: what makes a window flagged (`any_flag`, where it differs: what makes the call
+        look at the flags at all).  `ends`: a stream that has had its last push, before the call or by a tail window earlier in it,
+        is refused here, by window; without it the pool's `live` refuses.  `also`: further checks of a call with a flagged window."""
+        an = lambda s: ("an " if s[0] in "aA" else "a ") + s
+        if flags is None or not any((any_flag or flagged)(f) for f in flags):
+            if streams is not None and any(h is not None for h in streams):
+                raise ValueError(f"decode_windows: {arg_streams} without {an(arg)} flag")
+            return None
+        if len(flags) != len(windows) or streams is None or len(streams) != len(windows):
+            raise ValueError(f"decode_windows: one {arg} flag and one {arg_streams} entry per window")
+        if also is not None:
+            also()
+        pool, ended, out = self._pool(arg), set(), []
+        for i, (f, h) in enumerate(zip(flags, streams)):
+            if not flagged(f):
+                if h is not None:
+                    raise ValueError(f"decode_windows: window {i} has no {arg} flag but names {an(name)} stream")
+                out.append(None)
+                continue
+            want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
+            rec = None if h is None else pool.records.get(int(h)) if ends else pool.live(h)
+            if rec is None or rec.rate != want:
+                raise ValueError(f"decode_windows: window {i} needs an open {name} stream at {want} Hz")
+            if ends:
+                if rec.done or int(h) in ended:
+                    raise ValueError(f"decode_windows: window {i}: {name} stream {int(h)} has had its last push")
+                if len(windows[i]) > 4 and bool(windows[i][4]):
+                    ended.add(int(h))
+            out.append(int(h))
+        return out
+
+    def _window_codec(self, arg: str, name: str, flags, streams, windows, pcm16: bool, sample_rates, encodings):
+        """`_window_streams` for an output format (`arg` / `name`: flac / FLAC, adpcm / ADPCM) -> per window (arg, handle) or None"""
+        def also():
             if not pcm16:
                 raise ValueError(f"decode_windows: {name} comes behind the 16-bit conversion (pcm16=True)")
             if encodings is not None and any(f and e is not None for f, e in zip(flags, encodings)):
-                raise ValueError(f"decode_windows: {arg} does not go with an encoding ({an} {name} stream holds the 16-bit samples)")
-            for i, (f, h) in enumerate(zip(flags, streams)):
-                if f:
-                    want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
-                    if h is None or rec(h)[0] != want:
-                        raise ValueError(f"decode_windows: window {i} needs an open {name} stream at {want} Hz")
-                elif h is not None:
-                    raise ValueError(f"decode_windows: window {i} has no {arg} flag but names {an} {name} stream")
-            return [(arg, int(h)) if f else None for f, h in zip(flags, streams)]
-        if streams is not None and any(h is not None for h in streams):
-            raise ValueError(f"decode_windows: {arg}_streams without {an} {arg} flag")
-        return None
+                raise ValueError(f"decode_windows: {arg} does not go with an encoding ({'an' if arg[0] == 'a' else 'a'} {name} stream holds the 16-bit samples)")
+        got = self._window_streams(arg, arg + "_streams", name, flags, streams, windows, sample_rates, ends=False, also=also)
+        return None if got is None else [None if h is None else (arg, h) for h in got]
 
     def _flac_rounds(self, pcm: torch.Tensor, masks, idx, pushes, out: list) -> list:
-        """pushes[j] is window idx[j]'s, its stream an (arg, handle) of `_window_streams`: ONE `flac_stream_step` and ONE
+        """pushes[j] is window idx[j]'s, its stream an (arg, handle) of `_window_codec`: ONE `flac_stream_step` and ONE
         `adpcm_stream_step` (each for its own windows) when no stream is named twice, else the r-th push of a stream goes to step r,
         in the order given; -> `out` with the windows' chunks in place"""
-        out, seen, rounds = list(out), {}, []
-        for i, p in zip(idx, pushes):
-            r = seen[p[0]] = seen.get(p[0], -1) + 1
-            if r == len(rounds):
-                rounds.append([])
-            rounds[r].append((i, p))
-        for rnd in rounds:
+        out = list(out)
+        for members in SP.rounds(p[0] for p in pushes)[1]:
+            rnd = [(idx[j], pushes[j]) for j in members]
             for arg, step in (("flac", self.flac_stream_step), ("adpcm", self.adpcm_stream_step)):
                 mine = [(i, p) for i, p in rnd if p[0][0] == arg]
                 if mine:
@@ -3050,8 +2894,8 @@ class CodecEngine:
         with `rs_streams`: the scaled windows that also leave 24 kHz, each with its resampler stream"""
         S, cap = self._windows_store(store)
         out: list = [None] * len(windows)
-        recs = self._ts_pool()["rec"]
-        rs_recs = self._rs_pool()["rec"] if rates is not None else {}
+        recs = self._pool("time_scale").records
+        rs_recs = self._pool("resample").records if rates is not None else {}
         rows, conv, pushes = [], [], []     # decode windows; (window, decode row or None, push or None, keep); stream pushes
         push_rs = []                        # per push: the resampler stream its chunk goes on into, or None
         for i, w in enumerate(windows):
@@ -3060,14 +2904,16 @@ class CodecEngine:
             scaled = q[i][0] != q[i][1]
             if scaled:
                 h = ts_streams[i]
-                if h is None or int(h) not in recs or tuple(recs[int(h)][:2]) != tuple(q[i]):
+                rec = None if h is None else recs.get(int(h))
+                if rec is None or (rec.num, rec.den) != tuple(q[i]):
                     raise ValueError(f"decode_windows: window {i} at speed {q[i][0]}/{q[i][1]} needs an open stream of that speed")
             elif ts_streams[i] is not None or (rates is not None and rs_streams[i] is not None):
                 raise ValueError(f"decode_windows: window {i} is at speed 1 but names a stream")
             hr = None
             if rates is not None and scaled and rates[i] != self.SAMPLE_RATE:
                 hr = rs_streams[i]
-                if hr is None or int(hr) not in rs_recs or tuple(rs_recs[int(hr)][:2]) != (self.SAMPLE_RATE, rates[i]):
+                rec = None if hr is None else rs_recs.get(int(hr))
+                if rec is None or (rec.orig, rec.new) != (self.SAMPLE_RATE, rates[i]):
                     raise ValueError(f"decode_windows: window {i} at {rates[i]} Hz needs an open resampler stream {self.SAMPLE_RATE} -> {rates[i]}")
                 hr = int(hr)
             elif rates is not None and rs_streams[i] is not None:
@@ -3133,13 +2979,13 @@ class CodecEngine:
         p0 = blob_d.data_ptr()
         p1, p2 = p0 + parts[0].nbytes, p0 + parts[0].nbytes + parts[1].nbytes
         p3 = p2 + parts[2].nbytes
-        pool = self._ts_pool()
+        pool = self._pool("time_scale")
         cur, tail_args = self._windows_call_tail(lay, ctab[:, 5], pcm16, product, keep_thr, self.lib.ctts_codec_windows_speed_workspace_bytes(
             len(rows), int(tok[-1]), chunk + (paths + 7) // 8 * 8))
         front = (self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap, p0 if len(rows) else None,
                  tab.ctypes.data_as(C.c_void_p) if len(rows) else None, len(rows), p1, ctab.ctypes.data_as(C.c_void_p), p2,
                  rtab.ctypes.data_as(C.c_void_p), len(conv), p3, ts.ctypes.data_as(C.c_void_p), round_off.ctypes.data_as(C.c_void_p),
-                 len(round_off) - 1, pool["carry"].data_ptr(), pool["state"].data_ptr(), int(pool["carry"].shape[0]),
+                 len(round_off) - 1, pool.buf["carry"].data_ptr(), pool.buf["state"].data_ptr(), pool.slots,
                  self._time_scale_window().data_ptr())
         if staged:
             pairs = sorted({g[1] for g in groups})
@@ -3149,17 +2995,17 @@ class CodecEngine:
                 rate_tab[k].taps, rate_tab[k].L, rate_tab[k].M, rate_tab[k].K = self._resample_taps(orig, new).data_ptr(), L, M, RS.geometry(L, M)[1]
             grp_off = np.array([g[2] for g in groups] + [groups[-1][3]], dtype=np.int32)
             grp_rate = np.array([pairs.index(g[1]) for g in groups], dtype=np.int32)
-            rs_pool = self._rs_pool()
+            rs_pool = self._pool("resample")
             _lib.check(self.lib.ctts_codec_decode_windows_speed_rate(
                 *front, p3 + parts[3].nbytes, rs.ctypes.data_as(C.c_void_p), rs_of_ts.ctypes.data_as(C.c_void_p),
                 grp_off.ctypes.data_as(C.c_void_p), grp_rate.ctypes.data_as(C.c_void_p), len(groups), C.cast(rate_tab, C.c_void_p), len(pairs),
-                rs_pool["carry"].data_ptr(), int(rs_pool["carry"].shape[0]), *tail_args), "ctts_codec_decode_windows_speed_rate")
+                rs_pool.buf["carry"].data_ptr(), rs_pool.slots, *tail_args), "ctts_codec_decode_windows_speed_rate")
         else:
             _lib.check(self.lib.ctts_codec_decode_windows_speed(*front, *tail_args), "ctts_codec_decode_windows_speed")
         blob_d.record_stream(cur)
-        pool["rec"].update(commit)
+        pool.commit(commit)
         if staged:
-            rs_pool["rec"].update(rs_commit)
+            rs_pool.commit(rs_commit)
         return self._windows_finish(lay, n, ctab[:, 5], [c[0] for c in conv], laws, pcm16, out, fl)
 
     def _windows_to_host(self, buf: torch.Tensor, n_out: int, n_g: int, off, n, keep, live, laws, dt, out: list, fl=None) -> list:
@@ -3370,17 +3216,13 @@ class CodecEngine:
         return [plain[g] if rates[g] is None else ADPCM.behind_decode(enc[g][0], enc[g][1], rates[g]) for g in range(n_grp)]
 
     # -- FLAC for streams: per-stream device state (csrc/flac.hip, flac_stage_k) ---------------------------------------------------------
-    FLAC_STREAM_SLOTS = 64    # the state pool's first size; it doubles when every slot is taken
+    # `_flac_pool` / `_flac_rec` (and ADPCM's pair below) are all of the pool seam that the stream methods of the two int16 formats use,
+    # so that an object with no more than a library, a device and its `*_STREAM_SLOTS` can borrow them without the decoder's weights
+    def _flac_pool(self) -> SP.StatePool:
+        return CodecEngine._pool(self, "flac")
 
-    def _flac_pool(self) -> dict:
-        """the state pool: carry [slots, 16] int16 on the device, the free list, and per open stream its host record [rate, the number
-        of the first sample it holds, samples held (0 .. 15), done]"""
-        pool = self.__dict__.get("_flac_streams")
-        if pool is None:
-            n = int(self.FLAC_STREAM_SLOTS)
-            pool = self._flac_streams = dict(carry=torch.zeros((n, FLAC.MIN_BLOCK), dtype=torch.int16, device=self.device),
-                                             free=list(range(n - 1, -1, -1)), rec={})
-        return pool
+    def _flac_rec(self, handle: int):
+        return self._flac_pool().live(handle)
 
     def flac_stream_open(self, rate: int, first_sample: int = 0) -> int:
         """A FLAC stream at `rate` Hz whose first sample has the number `first_sample`: -> its handle, a slot of the engine's state
@@ -3389,40 +3231,22 @@ class CodecEngine:
         FLAC.rate_code(rate)
         if not 0 <= int(first_sample) < FLAC.MAX_SAMPLES:
             raise ValueError(f"flac: sample number {first_sample} does not fit 36 bits")
-        pool = self._flac_pool()
-        if not pool["free"]:
-            n = int(pool["carry"].shape[0])
-            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
-            pool["free"] = list(range(2 * n - 1, n - 1, -1))
-        slot = pool["free"].pop()
-        pool["rec"][slot] = [int(rate), int(first_sample), 0, False]
-        return slot
+        return self._flac_pool().open(SP.FlacRec(int(rate), int(first_sample), 0, False))
 
     def flac_stream_close(self, handle: int) -> None:
         """gives the stream's slot back (any time: finished, or abandoned half way)"""
-        pool = self._flac_pool()
-        if pool["rec"].pop(int(handle), None) is None:
-            raise ValueError(f"flac: stream {handle} is not open")
-        pool["free"].append(int(handle))
+        self._flac_pool().close(handle)
 
     def flac_streams_in_use(self) -> int:
         """the streams that are open: slots of the state pool not on its free list"""
-        return len(self._flac_pool()["rec"])
-
-    def _flac_rec(self, handle: int):
-        rec = self._flac_pool()["rec"].get(int(handle))
-        if rec is None:
-            raise ValueError(f"flac: stream {handle} is not open")
-        if rec[3]:
-            raise ValueError(f"flac: stream {handle} has had its last push")
-        return rec
+        return self._flac_pool().in_use
 
     def flac_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
         """`flac.stream_plan` of the stream's next push: the blocks a step with `n_in` more samples would emit, the number of the first
         of them, the samples the stream would hold afterwards, and the most bytes the push can emit"""
-        rate, sample, carry, _ = self._flac_rec(handle)
-        blocks, held = FLAC.stream_plan(carry, n_in, final)
-        return dict(rate=rate, sample=sample, blocks=blocks, carry=held, bound=FLAC.stream_bound(n_in))
+        rec = self._flac_rec(handle)
+        blocks, held = FLAC.stream_plan(rec.carry, n_in, final)
+        return dict(rate=rec.rate, sample=rec.sample, blocks=blocks, carry=held, bound=FLAC.stream_bound(n_in))
 
     def flac_stream_step(self, pcm: torch.Tensor, pushes, counts: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None) -> list:
         """ONE step of many FLAC streams (ctts_flac_stream_step: four launches whatever their number): `pcm`, a contiguous int16 device
@@ -3436,50 +3260,26 @@ class CodecEngine:
         appear once per call.  One small copy (the frame offsets and the total) and one copy of exactly the bytes used come to the host;
         the samples stay on the device.  Every refusal (ValueError here, EngineError from the library) comes before the first launch
         and leaves all streams as they were."""
-        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()):
-            raise ValueError("flac: a contiguous int16 device tensor")
-        if counts is not None and not (counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()):
-            raise ValueError("flac: `counts` must be a contiguous int64 device tensor")
-        if masks is not None and not (masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous()):
-            raise ValueError("flac: `masks` must be a contiguous uint8 device tensor")
-        if len(pushes) < 1:
-            raise ValueError("flac: nothing to step")
-        if len(pushes) > 1024:
-            raise ValueError("flac: at most 1024 streams in one step")
-        if len({int(p[0]) for p in pushes}) != len(pushes):
-            raise ValueError("flac: a stream appears twice in one step")
         pool = self._flac_pool()
-        n_el, n_push = pcm.numel(), len(pushes)
-        tab = np.zeros(n_push, _lib.FLAC_PUSH)
+        tab = np.zeros(len(pushes), _lib.FLAC_PUSH)
         stage = slots = 0
         commit = {}
-        for k, p in enumerate(pushes):
-            h, start, n, final = int(p[0]), int(p[1]), int(p[2]), bool(p[3])
-            ci = int(p[4]) if len(p) > 4 and p[4] is not None else -1
-            masked = len(p) > 5 and bool(p[5])
-            rate, sample, carry, _ = self._flac_rec(h)
-            if n < 0 or start < 0 or start + n > n_el:
-                raise ValueError("flac: a push lies outside the tensor")
-            if ci >= 0 and (counts is None or ci >= counts.numel()):
-                raise ValueError(f"flac: push {k} reads count {ci}, beyond `counts`")
-            if masked and (masks is None or masks.numel() * 8 < start + n):
-                raise ValueError(f"flac: push {k} is masked, and `masks` does not reach its end")
-            if (ci >= 0 or masked) and not final:
-                raise ValueError(f"flac: push {k} leaves its length to the device but is not final")
+        for k, (h, start, n, final, ci, masked, rec) in enumerate(SP.int16_pushes("flac", pcm, pushes, counts, masks, self._flac_rec)):
+            rate, sample, carry = rec.rate, rec.sample, rec.carry
             if sample + carry + n >= FLAC.MAX_SAMPLES:
                 raise ValueError(f"flac: push {k} would take the stream's sample number to 2^36")
             tab[k] = (start, n, sample, stage, slots, rate, h, carry, int(final) | 2 * int(masked), ci, 0)
             blocks, held = FLAC.stream_plan(carry, n, final)                     # a final push's own count only shortens its last blocks
-            commit[h] = [rate, sample + sum(blocks), held, final]
+            commit[h] = SP.FlacRec(rate, sample + sum(blocks), held, final)
             stage += (carry + n + 7) // 8 * 8
             slots += (carry + n + FLAC.BLOCK - 1) // FLAC.BLOCK
-        n_slots = int(pool["carry"].shape[0])
+        n_el, n_push, n_slots = pcm.numel(), len(pushes), pool.slots
         sizes = (C.c_int64 * 4)()
         _lib.check(self.lib.ctts_flac_stream_sizes(tab.ctypes.data_as(C.c_void_p), n_push, n_slots, n_el, sizes), "ctts_flac_stream_sizes")
         n_frames, out_bytes, work_bytes, _ = (int(v) for v in sizes)
         empty = np.zeros((0,), np.uint8)
         if n_frames == 0:                                                        # no stream holds or gets a sample
-            pool["rec"].update(commit)
+            pool.commit(commit)
             return [empty for _ in pushes]
         dev = pcm.device
         out = torch.empty(((out_bytes + 15) // 16 * 16,), dtype=torch.uint8, device=dev)
@@ -3487,10 +3287,10 @@ class CodecEngine:
         tab_d = torch.from_numpy(tab.view(np.uint8)).to(dev)
         st = torch.cuda.current_stream(dev)
         _lib.check(self.lib.ctts_flac_stream_step(pcm.data_ptr(), n_el, _lib.ptr(masks), _lib.ptr(counts), tab_d.data_ptr(),
-                                                  tab.ctypes.data_as(C.c_void_p), n_push, pool["carry"].data_ptr(), n_slots, out.data_ptr(),
+                                                  tab.ctypes.data_as(C.c_void_p), n_push, pool.buf["carry"].data_ptr(), n_slots, out.data_ptr(),
                                                   out.numel(), work.data_ptr(), work.numel(), st.cuda_stream), "ctts_flac_stream_step")
         tab_d.record_stream(st)
-        pool["rec"].update(commit)
+        pool.commit(commit)
         meta = self.to_host(work[: (8 * (n_frames + 1) + 15) // 16 * 16]).view(np.int64)              # the slots' offsets and the total
         total = int(meta[n_frames])
         blob = self.to_host(out[: (total + 15) // 16 * 16])[:total] if total else empty
@@ -3502,18 +3302,11 @@ class CodecEngine:
         return res
 
     # -- IMA ADPCM for streams: per-stream device state (csrc/adpcm.hip, adpcm_stage_k) -------------------------------------------------
-    ADPCM_STREAM_SLOTS = 64   # the state pool's first size; it doubles when every slot is taken
-    ADPCM_CARRY = 2048        # int16 per slot: S - 1 = 2040 at 48 kHz
+    def _adpcm_pool(self) -> SP.StatePool:
+        return CodecEngine._pool(self, "adpcm")
 
-    def _adpcm_pool(self) -> dict:
-        """the state pool: carry [slots, 2048] int16 on the device, the free list, and per open stream its host record [rate, samples
-        held (0 .. S - 1), done]"""
-        pool = self.__dict__.get("_adpcm_streams")
-        if pool is None:
-            n = int(self.ADPCM_STREAM_SLOTS)
-            pool = self._adpcm_streams = dict(carry=torch.zeros((n, self.ADPCM_CARRY), dtype=torch.int16, device=self.device),
-                                              free=list(range(n - 1, -1, -1)), rec={})
-        return pool
+    def _adpcm_rec(self, handle: int):
+        return self._adpcm_pool().live(handle)
 
     def adpcm_stream_open(self, rate: int) -> int:
         """An IMA ADPCM stream at `rate` Hz: -> its handle, a slot of the engine's state pool.  The slot is fresh by construction -- a
@@ -3522,40 +3315,22 @@ class CodecEngine:
         if ADPCM.samples_per_block(rate) - 1 > self.ADPCM_CARRY:
             raise ValueError(f"adpcm: a block at {rate} Hz holds {ADPCM.samples_per_block(rate)} samples, more than a stream's slot "
                              f"({self.ADPCM_CARRY}): streams run below 55125 Hz")
-        pool = self._adpcm_pool()
-        if not pool["free"]:
-            n = int(pool["carry"].shape[0])
-            pool["carry"] = torch.cat([pool["carry"], torch.zeros_like(pool["carry"])])      # stream-ordered behind every step so far
-            pool["free"] = list(range(2 * n - 1, n - 1, -1))
-        slot = pool["free"].pop()
-        pool["rec"][slot] = [int(rate), 0, False]
-        return slot
+        return self._adpcm_pool().open(SP.AdpcmRec(int(rate), 0, False))
 
     def adpcm_stream_close(self, handle: int) -> None:
         """gives the stream's slot back (any time: finished, or abandoned half way)"""
-        pool = self._adpcm_pool()
-        if pool["rec"].pop(int(handle), None) is None:
-            raise ValueError(f"adpcm: stream {handle} is not open")
-        pool["free"].append(int(handle))
+        self._adpcm_pool().close(handle)
 
     def adpcm_streams_in_use(self) -> int:
         """the streams that are open: slots of the state pool not on its free list"""
-        return len(self._adpcm_pool()["rec"])
-
-    def _adpcm_rec(self, handle: int):
-        rec = self._adpcm_pool()["rec"].get(int(handle))
-        if rec is None:
-            raise ValueError(f"adpcm: stream {handle} is not open")
-        if rec[2]:
-            raise ValueError(f"adpcm: stream {handle} has had its last push")
-        return rec
+        return self._adpcm_pool().in_use
 
     def adpcm_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
         """`adpcm.stream_plan` of the stream's next push: the blocks a step with `n_in` more samples would emit, the samples the stream
         would hold afterwards, and the most bytes the push can emit"""
-        rate, carry, _ = self._adpcm_rec(handle)
-        blocks, held = ADPCM.stream_plan(carry, n_in, final, rate)
-        return dict(rate=rate, blocks=blocks, carry=held, bound=ADPCM.stream_bound(n_in, rate))
+        rec = self._adpcm_rec(handle)
+        blocks, held = ADPCM.stream_plan(rec.carry, n_in, final, rec.rate)
+        return dict(rate=rec.rate, blocks=blocks, carry=held, bound=ADPCM.stream_bound(n_in, rec.rate))
 
     def adpcm_stream_step(self, pcm: torch.Tensor, pushes, counts: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None) -> list:
         """ONE step of many IMA ADPCM streams (ctts_adpcm_stream_step: two launches whatever their number): `pcm`, a contiguous int16
@@ -3570,49 +3345,25 @@ class CodecEngine:
         here and ONE copy, of the blocks, comes to the host; otherwise one more small copy brings the samples each push encoded.  The
         samples stay on the device.  Every refusal (ValueError here, EngineError from the library) comes before the first launch and
         leaves all streams as they were."""
-        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()):
-            raise ValueError("adpcm: a contiguous int16 device tensor")
-        if counts is not None and not (counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()):
-            raise ValueError("adpcm: `counts` must be a contiguous int64 device tensor")
-        if masks is not None and not (masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous()):
-            raise ValueError("adpcm: `masks` must be a contiguous uint8 device tensor")
-        if len(pushes) < 1:
-            raise ValueError("adpcm: nothing to step")
-        if len(pushes) > 1024:
-            raise ValueError("adpcm: at most 1024 streams in one step")
-        if len({int(p[0]) for p in pushes}) != len(pushes):
-            raise ValueError("adpcm: a stream appears twice in one step")
         pool = self._adpcm_pool()
-        n_el, n_push = pcm.numel(), len(pushes)
-        tab = np.zeros(n_push, _lib.ADPCM_PUSH)
+        tab = np.zeros(len(pushes), _lib.ADPCM_PUSH)
         stage = blocks = nbytes = samples = 0
         commit, by_device = {}, False
-        for k, p in enumerate(pushes):
-            h, start, n, final = int(p[0]), int(p[1]), int(p[2]), bool(p[3])
-            ci = int(p[4]) if len(p) > 4 and p[4] is not None else -1
-            masked = len(p) > 5 and bool(p[5])
-            rate, carry, _ = self._adpcm_rec(h)
-            if n < 0 or start < 0 or start + n > n_el:
-                raise ValueError("adpcm: a push lies outside the tensor")
-            if ci >= 0 and (counts is None or ci >= counts.numel()):
-                raise ValueError(f"adpcm: push {k} reads count {ci}, beyond `counts`")
-            if masked and (masks is None or masks.numel() * 8 < start + n):
-                raise ValueError(f"adpcm: push {k} is masked, and `masks` does not reach its end")
-            if (ci >= 0 or masked) and not final:
-                raise ValueError(f"adpcm: push {k} leaves its length to the device but is not final")
+        for k, (h, start, n, final, ci, masked, rec) in enumerate(SP.int16_pushes("adpcm", pcm, pushes, counts, masks, self._adpcm_rec)):
+            rate, carry = rec.rate, rec.carry
             by_device = by_device or ci >= 0 or masked
             tab[k] = (start, n, stage, blocks, nbytes, rate, h, carry, int(final) | 2 * int(masked), ci, 0)
             nb, held = ADPCM.stream_plan(carry, n, final, rate)                  # a final push's own count only lowers its blocks
-            commit[h] = [rate, held, final]
+            commit[h] = SP.AdpcmRec(rate, held, final)
             stage += (carry + n + 7) // 8 * 8
             blocks, nbytes, samples = blocks + nb, nbytes + nb * ADPCM.align(rate), samples + carry + n
-        n_slots = int(pool["carry"].shape[0])
+        n_el, n_push, n_slots = pcm.numel(), len(pushes), pool.slots
         sizes = (C.c_int64 * 4)()
         _lib.check(self.lib.ctts_adpcm_stream_sizes(tab.ctypes.data_as(C.c_void_p), n_push, n_slots, n_el, sizes), "ctts_adpcm_stream_sizes")
         n_blocks, out_bytes, work_bytes, _ = (int(v) for v in sizes)
         empty = np.zeros((0,), np.uint8)
         if samples == 0:                                                         # no stream holds or gets a sample
-            pool["rec"].update(commit)
+            pool.commit(commit)
             return [empty for _ in pushes]
         dev = pcm.device
         out = torch.empty((max(out_bytes, 16),), dtype=torch.uint8, device=dev)
@@ -3620,10 +3371,10 @@ class CodecEngine:
         tab_d = torch.from_numpy(tab.view(np.uint8)).to(dev)
         st = torch.cuda.current_stream(dev)
         _lib.check(self.lib.ctts_adpcm_stream_step(pcm.data_ptr(), n_el, _lib.ptr(masks), _lib.ptr(counts), tab_d.data_ptr(),
-                                                   tab.ctypes.data_as(C.c_void_p), n_push, pool["carry"].data_ptr(), n_slots, out.data_ptr(),
+                                                   tab.ctypes.data_as(C.c_void_p), n_push, pool.buf["carry"].data_ptr(), n_slots, out.data_ptr(),
                                                    out.numel(), work.data_ptr(), work.numel(), st.cuda_stream), "ctts_adpcm_stream_step")
         tab_d.record_stream(st)
-        pool["rec"].update(commit)
+        pool.commit(commit)
         if n_blocks == 0:                                                        # samples went to the slots, and no block is complete
             return [empty for _ in pushes]
         used = self.to_host(work[: (8 * n_push + 15) // 16 * 16]).view(np.int64) if by_device else None

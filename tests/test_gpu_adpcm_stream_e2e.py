@@ -127,7 +127,7 @@ def test_a_stream_named_twice_goes_through_rounds_and_flac_sits_beside_it(codec)
                                      adpcm_streams=[h, None, None], flac=[True, False, False], flac_streams=[g, None, None])
         finally:
             codec.flac_stream_close(g)
-        assert codec._adpcm_pool()["rec"][h] == [8000, 0, False]
+        assert codec._pool("adpcm").records[h] == (8000, 0, False)
     finally:
         codec.adpcm_stream_close(h)
         codec.flac_stream_close(f)

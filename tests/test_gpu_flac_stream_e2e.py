@@ -94,7 +94,7 @@ def test_flagged_windows_are_the_twins_pushes_of_the_pcm_windows(codec, rates, f
                    dict(flac=[True, False, False], flac_streams=[h, None, None], sample_rates=[8000] * 3, pcm16=False)):
             with pytest.raises(ValueError):
                 codec.decode_windows(store, POLLS[0], **{"pcm16": True, **kw})
-        assert codec._flac_pool()["rec"][h] == [8000, 0, 0, False]
+        assert codec._pool("flac").records[h] == (8000, 0, 0, False)
     finally:
         codec.flac_stream_close(h)
 

@@ -142,10 +142,10 @@ def _raw_step(codec, xd, pushes, y, mutate=None):
     tab["out_off"] = o[:-1] + 16
     if mutate:
         mutate(tab)
-    pool = codec._lm_pool()
+    pool = codec._pool("limiter")
     tab_d = torch.from_numpy(tab.view(np.uint8)).to(DEV)
     rc = codec.lib.ctts_peak_limit_stream_step(xd.data_ptr(), xd.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(tab), y.data_ptr(),
-                                               y.numel(), pool["carry"].data_ptr(), pool["stats"].data_ptr(), int(pool["carry"].shape[0]), None)
+                                               y.numel(), pool.buf["carry"].data_ptr(), pool.buf["stats"].data_ptr(), int(pool.buf["carry"].shape[0]), None)
     torch.cuda.synchronize()
     return rc, o
 
@@ -183,10 +183,10 @@ def test_a_slot_is_reused_clean_and_the_pool_grows_past_its_first_size(codec):
     fresh = codec.peak_limit_stream_stats(h2)
     assert (fresh["g32"], fresh["min_gain"], fresh["n_over"], fresh["n_touched"]) == (np.float32(1.5), 1.0, 0, 0)
     y1, _ = codec.peak_limit_stream_step(xd, [(h2, n, 1000, False)])                      # a quiet stream in the loud one's slot
-    first = int(codec._lm_pool()["carry"].shape[0])
+    first = int(codec._pool("limiter").buf["carry"].shape[0])
     more = [codec.peak_limit_stream_open(fs, 2.0) for _ in range(first)]                  # every slot taken: the pool doubles under the open stream
     try:
-        assert int(codec._lm_pool()["carry"].shape[0]) == 2 * first and max(more) >= first and codec.peak_limit_streams_in_use() == first + 1
+        assert int(codec._pool("limiter").buf["carry"].shape[0]) == 2 * first and max(more) >= first and codec.peak_limit_streams_in_use() == first + 1
         y2, _ = codec.peak_limit_stream_step(xd, [(h2, n + 1000, n - 1000, True), (max(more), 0, n, True)])
         want_q, rec_q = LM.limit_segment(quiet, fs, 1.5)
         want_l, rec_l = LM.limit_segment(loud, fs, 2.0)
@@ -206,9 +206,9 @@ def test_a_refused_step_leaves_the_records_and_the_carry_as_they_were(codec):
     a, b = codec.peak_limit_stream_open(fs, 1.5), codec.peak_limit_stream_open(fs, 2.0)
     try:
         ya, _ = codec.peak_limit_stream_step(xd, [(a, 0, 2500, False), (b, 0, 100, False)])
-        pool = codec._lm_pool()
-        recs = {k: list(v) for k, v in pool["rec"].items()}
-        carry, stats = pool["carry"].clone(), pool["stats"].clone()
+        pool = codec._pool("limiter")
+        recs = dict(pool.records)
+        carry, stats = pool.buf["carry"].clone(), pool.buf["stats"].clone()
         with pytest.raises(ValueError, match="outside the tensor"):                       # the engine's own check, behind a good push
             codec.peak_limit_stream_step(xd, [(a, 2500, 100, False), (b, n - 10, 11, False)])
         with pytest.raises(ValueError, match="twice"):
@@ -218,8 +218,8 @@ def test_a_refused_step_leaves_the_records_and_the_carry_as_they_were(codec):
                             (lambda t: t["gain"].__setitem__(0, np.inf), "pre-gain"), (lambda t: t["n_out"].__setitem__(1, 5), "emits")]:
             rc, _ = _raw_step(codec, xd, [(a, 2500, 3500, True), (b, 100, 900, False)], y, mutate)   # the library's, on its second descriptor
             assert rc != 0 and why in codec.lib.ctts_last_error().decode()
-        assert {k: list(v) for k, v in pool["rec"].items()} == recs
-        assert torch.equal(pool["carry"], carry) and torch.equal(pool["stats"], stats) and bool((y == float(CANARY)).all())
+        assert dict(pool.records) == recs
+        assert torch.equal(pool.buf["carry"], carry) and torch.equal(pool.buf["stats"], stats) and bool((y == float(CANARY)).all())
         yb, _ = codec.peak_limit_stream_step(xd, [(a, 2500, n - 2500, True)])              # the stream goes on as if nothing had been asked
         want, rec = LM.limit_segment(x, fs, 1.5)
         assert torch.cat([ya, yb]).cpu().numpy().tobytes() == want.tobytes() and codec.peak_limit_stream_stats(a).tobytes() == rec.tobytes()

@@ -170,12 +170,12 @@ def test_unflagged_windows_and_limiter_none_return_todays_bytes(codec, store, pl
         assert mixed[1].tobytes() == today[1].tobytes() and mixed[2].tobytes() == today[2].tobytes()
         for s, k in ((0, 0), (3, 3)):
             assert mixed[k].tobytes() == _converted(plain[s][2][:1] + [np.zeros(0, np.float32)], LAWS[s])[0].tobytes(), s
-        rec = list(codec._lm_pool()["rec"][a])
+        rec = codec._pool("limiter").records[a]
         for kw in (dict(limiter=[True], lm_streams=[None]), dict(limiter=[True], lm_streams=[b]), dict(limiter=[False], lm_streams=[a]),
                    dict(limiter=[True, True], lm_streams=[a]), dict(limiter=[1], lm_streams=[a])):
             with pytest.raises(ValueError):                                   # refused before any launch: the stream is where it was
                 codec.decode_windows(store, [POLLS[1][0]] * len(kw["limiter"]), **kw)
-        assert codec._lm_pool()["rec"][a] == rec
+        assert codec._pool("limiter").records[a] == rec
     finally:
         codec.peak_limit_stream_close(a)
         codec.peak_limit_stream_close(b)

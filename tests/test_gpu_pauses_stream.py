@@ -130,12 +130,39 @@ def test_a_slot_is_clean_when_it_is_used_again(codec):
 def test_a_handle_given_twice_is_refused_and_every_stream_goes_on_as_it_was(codec):
     def twice(k, xd, pushes):
         if k in (1, 3):
-            state = codec._pa_pool()["state"].clone()
+            state = codec._pool("pauses").buf["state"].clone()
             recs = {h: {k: v for k, v in codec.trim_pauses_stream_stats(h).items() if k != "record"} for h, _, _, _ in pushes}
             with pytest.raises(ValueError, match="twice"):
                 codec.trim_pauses_stream_step(xd, [*pushes, pushes[0]])
             with pytest.raises(ValueError, match="outside the tensor"):
                 codec.trim_pauses_stream_step(xd, [(pushes[0][0], xd.numel(), 1, False)])
-            assert torch.equal(state, codec._pa_pool()["state"]) and recs == {h: {k: v for k, v in codec.trim_pauses_stream_stats(h).items() if k != "record"} for h, _, _, _ in pushes}
+            assert torch.equal(state, codec._pool("pauses").buf["state"]) and recs == {h: {k: v for k, v in codec.trim_pauses_stream_stats(h).items() if k != "record"} for h, _, _, _ in pushes}
     cases = [(fs, SC.DEFAULT, SC.signal(fs, SC.runs((6, 0), (2, 1), (70, 0), (1, 1), (20, 0)), seed=fs)) for fs in (11025, 24000)]
     run_streams(codec, [(fs, sp, x, [len(x) // 5] * 4 + [len(x) - 4 * (len(x) // 5)]) for fs, sp, x in cases], on_step=twice)
+
+
+def test_the_pool_grows_under_a_live_stream_and_keeps_its_state():
+    """a pool of 4 slots doubles while a stream holds frames and a record half way: the stream goes on bit for bit"""
+    from chattts_amd import _lib
+    from chattts_amd.engine import CodecEngine
+
+    class Small(CodecEngine):
+        PA_STREAM_SLOTS = 4
+
+    eng = Small.__new__(Small)                          # pause control needs the library and a device, no weights
+    eng.lib, eng.device = _lib.lib(), DEV
+    tone = (0.5 * np.sin(2 * np.pi * 440 / 8000 * np.arange(1250))).astype(np.float32)
+    xd = torch.from_numpy(np.concatenate([tone, np.zeros(1500, np.float32), tone])).to(DEV)
+    want, record = eng.trim_pauses(xd, True, rates=8000, return_stats=True)
+    h = eng.trim_pauses_stream_open(8000)
+    first, _ = eng.trim_pauses_stream_step(xd, [(h, 0, 2000, False)])
+    assert eng._pool("pauses").slots == 4
+    more = [eng.trim_pauses_stream_open(8000) for _ in range(4)]
+    pool = eng._pool("pauses")
+    assert pool.slots == 8 and int(pool.buf["carry"].shape[0]) == int(pool.buf["state"].shape[0]) == 8 and max(more) >= 4
+    rest, _ = eng.trim_pauses_stream_step(xd, [(h, 2000, 2000, True)])
+    assert np.concatenate([first.cpu().numpy(), rest.cpu().numpy()]).tobytes() == want.cpu().numpy().tobytes()
+    assert list(eng.trim_pauses_stream_stats(h)["record"]) == list(record[0])
+    for m in more + [h]:
+        eng.trim_pauses_stream_close(m)
+    assert eng.trim_pauses_streams_in_use() == 0

@@ -150,14 +150,14 @@ def test_a_reopened_slot_starts_fresh_and_a_refused_call_changes_nothing(codec, 
     assert h2 == h                                              # the same slot, not cleared
     try:
         a, _ = codec.resample_stream_step(xd, [(h2, 0, 5000, False)])
-        rec = list(codec._rs_pool()["rec"][h2])
+        rec = codec._pool("resample").records[h2]
         with pytest.raises(ValueError, match="outside the tensor"):
             codec.resample_stream_step(xd, [(h2, N - 10, 20, False)])
         with pytest.raises(ValueError, match="twice"):
             codec.resample_stream_step(xd, [(h2, 5000, 10, False), (h2, 5010, 10, False)])
         with pytest.raises(ValueError, match="not open"):
             codec.resample_stream_step(xd, [(h2, 5000, 10, False), (h2 + 1000, 5010, 10, False)])
-        assert codec._rs_pool()["rec"][h2] == rec               # nothing was committed
+        assert codec._pool("resample").records[h2] == rec               # nothing was committed
         b, _ = codec.resample_stream_step(xd, [(h2, 5000, N - 5000, True)])
         assert np.concatenate([a.cpu().numpy(), b.cpu().numpy()]).tobytes() == want.tobytes()
         with pytest.raises(ValueError, match="last push"):
@@ -166,3 +166,29 @@ def test_a_reopened_slot_starts_fresh_and_a_refused_call_changes_nothing(codec, 
         codec.resample_stream_close(h2)
     with pytest.raises(ValueError, match="carry up to"):
         codec.resample_stream_open(48000, 11025)                # K = 694: beyond what a slot keeps
+
+
+def test_the_pool_grows_under_a_live_stream_and_keeps_its_carry():
+    """a pool of 4 slots doubles while a stream is half way: the stream goes on bit for bit, and a slot of the new half works like any"""
+    from chattts_amd.engine import CodecEngine
+
+    class Small(CodecEngine):
+        RS_STREAM_SLOTS = 4
+
+    eng = Small.__new__(Small)                          # the resampler needs the library and a device, no weights
+    eng.lib, eng.device = _lib.lib(), DEV
+    xd = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, 3000).astype(np.float32)).to(DEV)
+    want = eng.resample(xd, ORIG, 8000).cpu().numpy()
+    h = eng.resample_stream_open(ORIG, 8000)
+    first, _ = eng.resample_stream_step(xd, [(h, 0, 1500, False)])
+    assert eng._pool("resample").slots == 4
+    more = [eng.resample_stream_open(ORIG, 8000) for _ in range(4)]
+    pool = eng._pool("resample")
+    assert pool.slots == 8 and int(pool.buf["carry"].shape[0]) == 8 and max(more) >= 4
+    rest, _ = eng.resample_stream_step(xd, [(h, 1500, 1500, True)])
+    assert np.concatenate([first.cpu().numpy(), rest.cpu().numpy()]).tobytes() == want.tobytes()
+    whole, _ = eng.resample_stream_step(xd, [(max(more), 0, 3000, True)])
+    assert whole.cpu().numpy().tobytes() == want.tobytes()
+    for m in more + [h]:
+        eng.resample_stream_close(m)
+    assert eng.resample_streams_in_use() == 0

@@ -175,14 +175,14 @@ def test_a_call_mixes_the_four_kinds_of_window_and_each_returns_what_it_returns_
     for i, (g, a) in enumerate(zip(got, alone)):
         assert g.dtype == a.dtype == np.int16 and g.tobytes() == a.tobytes(), (i, pairs[i], g.shape, a.shape)
     # refusals come before any launch and leave both kinds of stream as they were
-    rec_t, rec_r = list(codec._ts_pool()["rec"][ts[3]]), list(codec._rs_pool()["rec"][rs[3]])
+    rec_t, rec_r = codec._pool("time_scale").records[ts[3]], codec._pool("resample").records[rs[3]]
     for kw in (dict(speeds=[1.5], ts_streams=[ts[3]], sample_rates=[8000]),                              # no rs_streams: today's refusal
                dict(speeds=[1.5], ts_streams=[ts[3]], sample_rates=[8000], rs_streams=[None]),
                dict(speeds=[1.5], ts_streams=[ts[3]], sample_rates=[8000], rs_streams=[rs[5]]),           # a stream at another rate
                dict(speeds=[1.5, 1.0], ts_streams=[ts[3], None], sample_rates=[8000, 8000], rs_streams=[rs[3], rs[3]])):   # speed 1 names one
         with pytest.raises(ValueError):
             codec.decode_windows(store, wins[:len(kw["speeds"])], **kw)
-    assert codec._ts_pool()["rec"][ts[3]] == rec_t and codec._rs_pool()["rec"][rs[3]] == rec_r
+    assert codec._pool("time_scale").records[ts[3]] == rec_t and codec._pool("resample").records[rs[3]] == rec_r
     _close(codec, ts, rs)
     assert codec.time_scale_streams_in_use() == 0 and codec.resample_streams_in_use() == 0
 

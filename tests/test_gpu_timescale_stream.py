@@ -180,9 +180,9 @@ def test_refusals_leave_the_state_untouched(codec, sig):
     try:
         first, _ = codec.time_scale_stream_step(xd, [(h, 0, 6000, False)])
         codec.time_scale_stream_step(xd, [(other, 0, 100, True)])                               # `other` has had its last push
-        pool = codec._ts_pool()
+        pool = codec._pool("time_scale")
         torch.cuda.synchronize()
-        carry, state, rec = pool["carry"].clone(), pool["state"].clone(), {k: list(v) for k, v in pool["rec"].items()}
+        carry, state, rec = pool.buf["carry"].clone(), pool.buf["state"].clone(), dict(pool.records)
         for pushes in ([(h, 0, 100, False), (h, 100, 100, False)], [(h, 19990, 100, False)], [(h, -1, 10, False)], [(h, 0, -1, False)], [],
                        [(h, 6000, 100, False), (other, 0, 10, False)], [(h, 6000, 100, False), (9999, 0, 10, False)]):
             with pytest.raises(ValueError):
@@ -196,18 +196,18 @@ def test_refusals_leave_the_state_untouched(codec, sig):
         y = torch.full((p["n_out"] + 8,), 7.0, device=DEV)
         path = torch.full((64,), 7, dtype=torch.int32, device=DEV)
         for over in (dict(k_now=p["k_now"] + 1, n_out=p["n_out"] + HOP), dict(k_prev=p["k_prev"] - 1), dict(total=11001), dict(n_out=p["n_out"] - 1),
-                     dict(slot=int(pool["carry"].shape[0])), dict(phase=2), dict(num=100), dict(twice=True)):
+                     dict(slot=int(pool.buf["carry"].shape[0])), dict(phase=2), dict(num=100), dict(twice=True)):
             tab = np.zeros(2 if over.get("twice") else 1, _lib.TS_STREAM)
             tab[:] = tuple({**good, **over}[k] for k in _lib.TS_STREAM.names)
             tab_d = torch.from_numpy(tab.view(np.uint8)).to(DEV)
             rc = codec.lib.ctts_time_scale_stream_step(xd.data_ptr(), xd.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(tab), y.data_ptr(),
-                                                       y.numel(), path.data_ptr(), path.numel(), pool["carry"].data_ptr(), pool["state"].data_ptr(),
-                                                       int(pool["carry"].shape[0]), codec._time_scale_window().data_ptr(),
+                                                       y.numel(), path.data_ptr(), path.numel(), pool.buf["carry"].data_ptr(), pool.buf["state"].data_ptr(),
+                                                       int(pool.buf["carry"].shape[0]), codec._time_scale_window().data_ptr(),
                                                        torch.cuda.current_stream().cuda_stream)
             assert rc != 0 and b"ctts_time_scale_stream_step" in _lib.lib().ctts_last_error(), over
         torch.cuda.synchronize()
         assert bool((y == 7.0).all()) and bool((path == 7).all())
-        assert torch.equal(pool["carry"], carry) and torch.equal(pool["state"], state) and {k: list(v) for k, v in pool["rec"].items()} == rec
+        assert torch.equal(pool.buf["carry"], carry) and torch.equal(pool.buf["state"], state) and dict(pool.records) == rec
         rest, _ = codec.time_scale_stream_step(xd, [(h, 6000, len(x) - 6000, True)])
         assert np.concatenate([first.cpu().numpy(), rest.cpu().numpy()]).tobytes() == want.tobytes()
     finally:
@@ -221,10 +221,10 @@ def test_the_pool_grows_and_keeps_the_streams_it_holds(codec, sig):
     want = one_shot(codec, sig, "tone", 1.25)[0]
     h = codec.time_scale_stream_open(1.25)
     first, _ = codec.time_scale_stream_step(xd, [(h, 0, 4000, False)])
-    n = int(codec._ts_pool()["carry"].shape[0])
+    n = int(codec._pool("time_scale").buf["carry"].shape[0])
     more = [codec.time_scale_stream_open(0.5) for _ in range(n)]                                # one more than the pool held
     try:
-        assert int(codec._ts_pool()["carry"].shape[0]) == 2 * n and len(set(more + [h])) == n + 1
+        assert int(codec._pool("time_scale").buf["carry"].shape[0]) == 2 * n and len(set(more + [h])) == n + 1
         rest, _ = codec.time_scale_stream_step(xd, [(h, 4000, len(x) - 4000, True)])
         assert np.concatenate([first.cpu().numpy(), rest.cpu().numpy()]).tobytes() == want.tobytes()
     finally:

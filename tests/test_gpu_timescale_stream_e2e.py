@@ -136,7 +136,7 @@ def test_several_windows_of_one_stream_in_one_call_and_a_tail_with_nothing_left(
                dict(speeds=[1.25])):
         with pytest.raises(ValueError):
             codec.decode_windows(store, [wins[0]], **kw)
-    assert codec._ts_pool()["rec"][h] == [125, 100, 0, 0, False]
+    assert codec._pool("time_scale").records[h] == (125, 100, 0, 0, False)
     codec.time_scale_stream_close(h)
 
 

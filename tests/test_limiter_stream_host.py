@@ -13,7 +13,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from chattts_amd import _lib, limiter as LM
+from chattts_amd import _lib, limiter as LM, statepool as SP
 from tests import limiter_cases as LCs, limiter_stream_cases as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -173,7 +173,7 @@ def test_library_refuses_before_it_launches():
 def _engine():
     from chattts_amd.engine import CodecEngine
     eng = CodecEngine.__new__(CodecEngine)
-    eng.__dict__["_lm_streams"] = dict(carry=None, stats=None, free=[3, 2, 1, 0], rec={})
+    eng._pools = {"limiter": SP.StatePool("limiter", 4)}
     return eng
 
 
@@ -184,8 +184,8 @@ def test_the_engine_plans_a_step_and_commits_nothing_on_its_own():
     tab, commit = eng._lm_descriptors([(a, 0, 1000, False), (b, 1000, 500, True)])
     assert [int(v) for v in tab["n_out"]] == [840, 500] and [int(v) for v in tab["total"]] == [-1, 500] and [int(v) for v in tab["c_out"]] == [320, 0]
     assert [int(v) for v in tab["rate"]] == [8000, 48000] and [float(v) for v in tab["gain"]] == [2.0, 1.0] and [int(v) for v in tab["slot"]] == [a, b]
-    assert eng._lm_streams["rec"][a] == [8000, np.float32(2.0), 0, 0, 0, False]                 # nothing committed yet
-    assert commit[a] == [8000, np.float32(2.0), 1000, 840, 1, False] and commit[b][2:] == [500, 500, 1, True]
+    assert eng._pools["limiter"].records[a] == SP.LimiterRec(8000, np.float32(2.0), 0, 0, 0, False)                 # nothing committed yet
+    assert commit[a] == SP.LimiterRec(8000, np.float32(2.0), 1000, 840, 1, False) and commit[b] == SP.LimiterRec(48000, np.float32(1.0), 500, 500, 1, True)
     assert eng.peak_limit_stream_plan(a, 1000, False)["n_out"] == 840
     st = eng.peak_limit_stream_stats(a)                                                          # before the first push: nothing counted, no device read
     assert (st["g32"], st["min_gain"], st["n_over"], st["n_touched"]) == (np.float32(2.0), 1.0, 0, 0)
@@ -196,7 +196,7 @@ def test_the_engine_plans_a_step_and_commits_nothing_on_its_own():
     for rate, gain, why in [(7000, 1.0, "rate"), (24000, 0.0, "pre-gain"), (24000, float("inf"), "pre-gain"), (24005, 1.0, "rate")]:
         with pytest.raises(ValueError, match=why):
             eng.peak_limit_stream_open(rate, gain)
-    eng._lm_streams["rec"][b][5] = True
+    eng._pools["limiter"].commit({b: eng._pools["limiter"].get(b)._replace(done=True)})
     with pytest.raises(ValueError, match="last push"):
         eng.peak_limit_stream_plan(b, 1, False)
     eng.peak_limit_stream_close(a)
@@ -222,7 +222,7 @@ def test_decode_windows_checks_the_limiter_streams_before_anything_else():
             eng.decode_windows(None, wins, **kw)
     with pytest.raises(ValueError, match="has had its last push"):                              # a tail, then another window of the stream
         eng.decode_windows(None, [wins[1], wins[0]], limiter=[True, True], lm_streams=[h24, h24])
-    assert eng._lm_streams["rec"][h24] == [24000, np.float32(1.0), 0, 0, 0, False]
+    assert eng._pools["limiter"].records[h24] == SP.LimiterRec(24000, np.float32(1.0), 0, 0, 0, False)
 
 
 # ---- the default-off plumbing, on fakes -------------------------------------------------------------------------------------------------

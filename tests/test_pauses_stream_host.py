@@ -9,7 +9,7 @@ import re
 import numpy as np
 import pytest
 
-from chattts_amd import _lib, pauses as PA
+from chattts_amd import _lib, pauses as PA, statepool as SP
 from tests import pauses_oracle as ORACLE, pauses_stream_cases as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -262,7 +262,7 @@ def test_library_refuses_before_it_launches():
 def _engine():
     from chattts_amd.engine import CodecEngine
     eng = CodecEngine.__new__(CodecEngine)
-    eng.__dict__["_pa_streams"] = dict(carry=None, state=None, free=[3, 2, 1, 0], rec={})
+    eng._pools = {"pauses": SP.StatePool("pauses", 4)}
     return eng
 
 
@@ -275,7 +275,8 @@ def test_the_engine_plans_a_step_and_commits_nothing_on_its_own():
     assert [int(v) for v in tab["out_off"]] == [0, 34 * 80 + 1000] and [int(v) for v in tab["fr_off"]] == [0, 12] and [int(v) for v in tab["list_off"]] == [0, 81]
     assert [int(v) for v in tab["n_list"]] == [81, 14] and [int(v) for v in tab["fade"]] == [0, 80] and len(fade) == 190
     assert fade[:80].tobytes() == PA.fade_table(80).tobytes() and fade[80:].tobytes() == PA.fade_table(110).tobytes()
-    assert eng._pa_streams["rec"][a][2:] == [0, 0, False, 0, 0] and commit == {a: [1000, 1, False], b: [500, 1, True]}      # nothing committed yet
+    assert eng._pools["pauses"].records[a] == SP.PauseRec(8000, PA.PauseSpec(), 0, 0, False, 0, 0)
+    assert commit == {a: SP.PauseRec(8000, PA.PauseSpec(), 1000, 1, False, 0, 0), b: SP.PauseRec(11025, PA.check_stream(11025, SC.SPECS["bare"])[1], 500, 1, True, 0, 0)}      # nothing committed yet
     st = eng.trim_pauses_stream_stats(a)                             # before the first sample: zeros, no device read
     assert list(st["record"]) == [0] * 8 and (st["pushed"], st["emitted"], st["held"], st["done"]) == (0, 0, 0, False)
     for pushes, why in [([(a, 0, 10, False), (a, 10, 10, False)], "twice"), ([(3, 0, 10, False)], "not open"), ([(a, 0, -1, False)], "negative"),
@@ -286,7 +287,7 @@ def test_the_engine_plans_a_step_and_commits_nothing_on_its_own():
         with pytest.raises(ValueError, match=why):
             eng.trim_pauses_stream_open(rate, spec)
     assert eng.trim_pauses_streams_in_use() == 2                     # a refused open takes no slot
-    eng._pa_streams["rec"][b][4] = True
+    eng._pools["pauses"].commit({b: eng._pools["pauses"].get(b)._replace(done=True)})
     with pytest.raises(ValueError, match="last push"):
         eng._pa_descriptors([(b, 0, 1, False)])
     eng.trim_pauses_stream_close(a)
@@ -294,7 +295,7 @@ def test_the_engine_plans_a_step_and_commits_nothing_on_its_own():
         eng.trim_pauses_stream_close(a)
     with pytest.raises(ValueError, match="not open"):
         eng.trim_pauses_stream_stats(a)
-    assert eng.trim_pauses_stream_open(48000) == a and eng._pa_streams["rec"][a][2:] == [0, 0, False, 0, 0]
+    assert eng.trim_pauses_stream_open(48000) == a and eng._pools["pauses"].records[a] == SP.PauseRec(48000, PA.PauseSpec(), 0, 0, False, 0, 0)
 
 
 # ---- the default-off plumbing, on fakes -------------------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from chattts_amd import _lib, resample as RS
+from chattts_amd import _lib, resample as RS, statepool as SP
 
 ORIG = 24000
 RATES = (8000, 11025, 16000, 22050, 32000, 44100, 48000)
@@ -218,8 +218,7 @@ def test_the_window_entry_refuses_bad_resampler_tables_before_any_launch():
 def _engine():
     from chattts_amd.engine import CodecEngine
     eng = CodecEngine.__new__(CodecEngine)
-    eng.__dict__["_rs_streams"] = dict(carry=None, free=[3, 2, 1, 0], rec={})
-    eng.__dict__["_ts_streams"] = dict(carry=None, state=None, free=[3, 2, 1, 0], rec={})
+    eng._pools = {"resample": SP.StatePool("resample", 4), "time_scale": SP.StatePool("time_scale", 4)}
     return eng
 
 
@@ -234,8 +233,8 @@ def test_the_engine_plans_pushes_in_rounds_grouped_by_rate_and_commits_nothing_o
     assert [int(v) for v in tab["phase"]] == [0, 0, 0, 1] and int(tab["total"][3]) == 3000 and int(tab["total"][0]) == -1
     assert int(tab["o_lo"][3]) == int(tab["n_out"][0]) and int(tab["c_in"][3]) == int(tab["c_out"][0]) > 0
     assert int(tab["n_out"][0]) + int(tab["n_out"][3]) == 1000 and int(tab["n_out"][1]) == 0 and int(tab["c_out"][1]) == 10
-    assert eng._rs_streams["rec"][a] == [ORIG, 8000, 0, 0, 0, False]                        # nothing committed yet
-    assert commit[a] == [ORIG, 8000, 3000, 1000, 0, True] and commit[c] == [ORIG, 8000, 10, 0, 1, False]
+    assert eng._pools["resample"].records[a] == SP.ResampleRec(ORIG, 8000, 0, 0, 0, False)                        # nothing committed yet
+    assert commit[a] == SP.ResampleRec(ORIG, 8000, 3000, 1000, 0, True) and commit[c] == SP.ResampleRec(ORIG, 8000, 10, 0, 1, False)
     assert eng.resample_stream_plan(a, 3000, False)["n_out"] == int(tab["n_out"][0])
     with pytest.raises(ValueError, match="last push"):
         eng._rs_descriptors([(a, 0, 10, True), (a, 10, 10, False)])
@@ -244,7 +243,7 @@ def test_the_engine_plans_pushes_in_rounds_grouped_by_rate_and_commits_nothing_o
     eng.resample_stream_close(a)
     with pytest.raises(ValueError, match="not open"):
         eng.resample_stream_close(a)
-    assert eng.resample_stream_open(ORIG, 48000) == a and eng._rs_streams["rec"][a] == [ORIG, 48000, 0, 0, 0, False]
+    assert eng.resample_stream_open(ORIG, 48000) == a and eng._pools["resample"].records[a] == SP.ResampleRec(ORIG, 48000, 0, 0, 0, False)
     with pytest.raises(ValueError, match="nothing to convert"):
         eng.resample_stream_open(ORIG, ORIG)
     with pytest.raises(ValueError, match="carry up to 693"):
@@ -272,7 +271,7 @@ def test_decode_windows_keeps_the_refusal_without_rs_streams_and_checks_them_whe
         eng.decode_windows(store, wins, rs_streams=[r8, r16], **kw)
     with pytest.raises(ValueError, match="stays at 24000 Hz but names a resampler stream"):
         eng.decode_windows(store, wins, speeds=[1.25, 1.25], ts_streams=[t, t], sample_rates=[8000, 24000], rs_streams=[r8, r16])
-    assert eng._rs_streams["rec"][r8] == [ORIG, 8000, 0, 0, 0, False] and eng._ts_streams["rec"][t][2] == 0
+    assert eng._pools["resample"].records[r8] == SP.ResampleRec(ORIG, 8000, 0, 0, 0, False) and eng._pools["time_scale"].records[t].pushed == 0
 
 
 # ---- the default-off plumbing, on fakes ---------------------------------------------------------------------------------------------

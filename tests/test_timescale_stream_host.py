@@ -238,9 +238,11 @@ def test_chat_infer_keeps_the_refusal_without_the_flag_and_names_what_it_still_r
 def test_the_engine_plans_a_polls_pushes_in_rounds_and_commits_nothing_on_its_own():
     """CodecEngine._ts_descriptors without a device: two windows of one stream in one call go to successive rounds, with the position
     and the carry phase of the second following the first; the host records change only when the caller commits"""
+    from chattts_amd import statepool as SP
     from chattts_amd.engine import CodecEngine
     eng = CodecEngine.__new__(CodecEngine)
-    eng.__dict__["_ts_streams"] = dict(carry=None, state=None, free=[3, 2, 1, 0], rec={})
+    eng._pools = {"time_scale": SP.StatePool("time_scale", 4)}
+    recs = eng._pools["time_scale"].records
     a, b = eng.time_scale_stream_open(1.25), eng.time_scale_stream_open(0.5)
     assert (a, b) == (0, 1) and eng.time_scale_streams_in_use() == 2
     tab, round_off, order, n_path, commit = eng._ts_descriptors([(a, 0, 3000, False), (b, 3000, 2000, False), (a, 5000, 0, True)])
@@ -248,8 +250,8 @@ def test_the_engine_plans_a_polls_pushes_in_rounds_and_commits_nothing_on_its_ow
     assert [int(v) for v in tab["slot"]] == [a, b, a] and [int(v) for v in tab["pos"]] == [0, 0, 3000] and [int(v) for v in tab["phase"]] == [0, 0, 1]
     assert int(tab["total"][2]) == 3000 and int(tab["total"][0]) == -1
     assert sum(int(tab["n_out"][i]) for i in (0, 2)) == TS.out_len(3000, 125) and n_path[0] + n_path[2] == TS.frames(TS.out_len(3000, 125))
-    assert eng._ts_streams["rec"] == {a: [125, 100, 0, 0, False], b: [50, 100, 0, 0, False]}        # nothing committed yet
-    assert commit == {a: [125, 100, 3000, 0, True], b: [50, 100, 2000, 1, False]}
+    assert recs == {a: SP.TimeScaleRec(125, 100, 0, 0, False), b: SP.TimeScaleRec(50, 100, 0, 0, False)}        # nothing committed yet
+    assert commit == {a: SP.TimeScaleRec(125, 100, 3000, 0, True), b: SP.TimeScaleRec(50, 100, 2000, 1, False)}
     with pytest.raises(ValueError, match="last push"):
         eng._ts_descriptors([(a, 0, 10, True), (a, 10, 10, False)])
     with pytest.raises(ValueError, match="not open"):
@@ -258,7 +260,7 @@ def test_the_engine_plans_a_polls_pushes_in_rounds_and_commits_nothing_on_its_ow
     with pytest.raises(ValueError, match="not open"):
         eng.time_scale_stream_close(a)
     assert eng.time_scale_stream_open(2.0) == a                      # the slot is handed out again, with a fresh record
-    assert eng._ts_streams["rec"][a] == [200, 100, 0, 0, False]
+    assert recs[a] == SP.TimeScaleRec(200, 100, 0, 0, False)
     with pytest.raises(ValueError, match="nothing to scale"):
         eng.time_scale_stream_open(1.0)
 

@@ -169,7 +169,7 @@ def _stream(codec, reps, rounds):
         x = torch.from_numpy((r.uniform(-1, 1, B * CHUNK) * env).astype(np.float32)).to(dev)
         y = torch.empty_like(x)
         hs = [codec.peak_limit_stream_open(24000) for _ in range(B)]
-        pool = codec._lm_pool()
+        pool = codec._pool("limiter")
         W = 240
         # step k of every stream: the same B x CHUNK samples again, at position k * CHUNK (k = 0 emits 2 W fewer: it is the warm-up)
         tabs = []
@@ -199,7 +199,7 @@ def _stream(codec, reps, rounds):
             def run(lo=1):
                 for k in range(lo, reps + 1):
                     rc = codec.lib.ctts_peak_limit_stream_step(x.data_ptr(), x.numel(), tabs_d[k].data_ptr(), vp(tabs[k]), B, y.data_ptr(), y.numel(),
-                                                               pool["carry"].data_ptr(), pool["stats"].data_ptr(), int(pool["carry"].shape[0]), st)
+                                                               pool.buf["carry"].data_ptr(), pool.buf["stats"].data_ptr(), int(pool.buf["carry"].shape[0]), st)
                     assert rc == 0, codec.lib.ctts_last_error()
             return run
 
@@ -223,7 +223,7 @@ def _stream(codec, reps, rounds):
             run_o()
             decode()
             torch.cuda.synchronize()
-            rec = pool["stats"][hs].cpu().numpy().view(LM.STATS).reshape(-1)
+            rec = pool.buf["stats"][hs].cpu().numpy().view(LM.STATS).reshape(-1)
             times = {"stream_step": [], "one_shot": [], "window_decode": []}
             for _ in range(rounds):
                 for key, fn in (("stream_step", run_s), ("one_shot", run_o), ("window_decode", decode)):

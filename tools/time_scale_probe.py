@@ -71,8 +71,8 @@ def _stream_step_ms(codec, n_streams, speed, reps, push=12000, warm=3):
     """device time of one step of `n_streams` streams, each pushed `push` samples, and the frames it runs per stream"""
     from chattts_amd import _lib
     dev = codec.device
-    pool = codec._ts_pool()
-    assert n_streams <= int(pool["carry"].shape[0])
+    pool = codec._pool("time_scale")
+    assert n_streams <= int(pool.buf["carry"].shape[0])
     x = torch.rand(n_streams * push, device=dev) * 2 - 1
     tabs, frames, n_out = [], [], 0
     for r in range(warm + reps):
@@ -91,8 +91,8 @@ def _stream_step_ms(codec, n_streams, speed, reps, push=12000, warm=3):
     def call(r):
         tab, tab_d = tabs[r]
         rc = codec.lib.ctts_time_scale_stream_step(x.data_ptr(), x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), n_streams, y.data_ptr(),
-                                                   y.numel(), path.data_ptr(), path.numel(), pool["carry"].data_ptr(), pool["state"].data_ptr(),
-                                                   int(pool["carry"].shape[0]), win.data_ptr(), st)
+                                                   y.numel(), path.data_ptr(), path.numel(), pool.buf["carry"].data_ptr(), pool.buf["state"].data_ptr(),
+                                                   int(pool.buf["carry"].shape[0]), win.data_ptr(), st)
         assert rc == 0, codec.lib.ctts_last_error()
     for r in range(warm):
         call(r)
@@ -111,8 +111,8 @@ def _resample_step_ms(codec, n_streams, speed, rate, reps, push=12000, warm=3):
     for `push` samples, and the samples a step emits per stream"""
     from chattts_amd import _lib
     dev = codec.device
-    pool = codec._rs_pool()
-    assert n_streams <= int(pool["carry"].shape[0])
+    pool = codec._pool("resample")
+    assert n_streams <= int(pool.buf["carry"].shape[0])
     L, M = RS.ratio(24000, rate)
     K = RS.geometry(L, M)[1]
     taps = codec._resample_taps(24000, rate)
@@ -136,7 +136,7 @@ def _resample_step_ms(codec, n_streams, speed, rate, reps, push=12000, warm=3):
     def call(r):
         tab, tab_d = tabs[r]
         rc = codec.lib.ctts_resample_stream_step(x.data_ptr(), x.numel(), tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), n_streams, y.data_ptr(),
-                                                 y.numel(), pool["carry"].data_ptr(), int(pool["carry"].shape[0]), taps.data_ptr(), L, M, K, st)
+                                                 y.numel(), pool.buf["carry"].data_ptr(), int(pool.buf["carry"].shape[0]), taps.data_ptr(), L, M, K, st)
         assert rc == 0, codec.lib.ctts_last_error()
     for r in range(warm):
         call(r)
