@@ -96,6 +96,13 @@ LM_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("tota
                       ("gain", "<f4")])
 
 
+# ctts_cp_stream (104 bytes): in_off, n_in, pos, total, e_lo, n_out, out_off, cb_off int64; slot, phase, rate, A, H, tab, c_in, c_out, h_in,
+# h_out int32
+CP_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("e_lo", "<i8"), ("n_out", "<i8"),
+                      ("out_off", "<i8"), ("cb_off", "<i8"), ("slot", "<i4"), ("phase", "<i4"), ("rate", "<i4"), ("A", "<i4"), ("H", "<i4"),
+                      ("tab", "<i4"), ("c_in", "<i4"), ("c_out", "<i4"), ("h_in", "<i4"), ("h_out", "<i4")])
+
+
 # ctts_rs_stream (80 bytes): in_off, n_in, pos, total, o_lo, n_out, out_off int64; slot, phase, c_in, c_out, pad, reserved int32
 RS_STREAM = np.dtype([("in_off", "<i8"), ("n_in", "<i8"), ("pos", "<i8"), ("total", "<i8"), ("o_lo", "<i8"), ("n_out", "<i8"),
                       ("out_off", "<i8"), ("slot", "<i4"), ("phase", "<i4"), ("c_in", "<i4"), ("c_out", "<i4"), ("pad", "<i4"),
@@ -196,6 +203,8 @@ SIGNATURES = {
     "ctts_peak_limit_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, P, SZ, P]),
     "ctts_compress_ragged_scratch_bytes": (SZ, [P, I32]),
     "ctts_compress_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, P, P, I32, P, P, SZ, P]),
+    "ctts_compress_stream_scratch_bytes": (SZ, [C.c_int64]),
+    "ctts_compress_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, P, I32, P, C.c_int64, P, P, P, I32, P, SZ, P]),
     "ctts_peak_limit_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P]),
     "ctts_trim_pauses_ragged_scratch_bytes": (SZ, [C.c_int64, I32]),
     "ctts_trim_pauses_ragged": (C.c_int, [P, P, P, P, P, P, P, P, I32, P, I32, P, P, P, SZ, P]),

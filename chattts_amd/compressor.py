@@ -29,14 +29,29 @@ agree bit for bit.
 
 What follows: g <= 1 everywhere; a segment whose block peaks all lie below the knee (c == 1) comes back bit for bit; y[i] depends on x
 only in the blocks b - A - H - 1 .. b + A + 1 (a[b], a[b + 1] <- s[b - 1 .. b + 1] <- m[b - 1 - A .. b + 1] <- c[b - 1 - A - H .. b + 1 + A]):
-the bounded window that a later stream version will carry.  A segment's samples and record do not depend on what it is packed with.
+the bounded window that a stream carries (below).  A segment's samples and record do not depend on what it is packed with.
 
 Adjusted against the issue's wording, for exactness: the durations become whole blocks by ceil (a fractional attack_ms would leave
 A undefined); m is defined for every integer j, not only inside the segment (s[b] near the edges sums m[j] with j < 0); p of a block
 of NaNs is 0.
 
 One record per segment (`STATS`, 16 bytes, written on the device): the smallest g, the blocks with c < 1, the samples with g < 1, the
-largest block peak."""
+largest block peak.
+
+A STREAM (`stream_plan`, `StreamCompressor`, ctts_compress_stream_step): the segment arrives in pushes.  After a push `total` samples
+are in and nbc = total // B blocks are complete; the c of a block is computed once, when the block is complete (on the last push: the
+partial last block too, nb = ceil(total / B)).
+  emits        a push that is not the last emits samples [emitted, E'), E' = max(0, nbc - A - 1) B: sample i of block b needs
+               c[b - A - H - 1 .. b + A + 1], and every block up to nbc - 1 is complete.  The last push emits up to `total`, and only then
+               do the edge rules apply (c = 1 beyond nb, a[nb] := s[nb - 1], the partial block's peak); s[-1] := s[0] at the true start only.
+  lag          (A + 1) B samples and the open block: under A + 2 ms (7 ms at the defaults, 22 ms at most), whatever the hold.
+  carried      the raw samples [E', total), fewer than (A + 2) B (`STREAM_CARRY` = 1055 at most); the c of the blocks
+               [max(0, E' / B - A - H - 1), nbc), at most 2 A + H + 2 (`STREAM_HIST` = 542); the 16-byte record; the table (4 KiB, or an
+               index to it).  No raw sample older than E': the hold's memory, up to 500 ms, lives in c, one float per millisecond.
+  empty        a stream may end empty (total = 0, final): it emits nothing and its record is (1, 0, 0, 0).
+  the contract the chunks, end to end, are `compress_segment` of the whole signal, bit for bit, however it was cut, and the record
+               after the last push is that segment's: n_blocks and peak count once per block, when its c is computed; min_gain and
+               n_touched over the emitted samples."""
 from __future__ import annotations
 
 import math
@@ -51,6 +66,9 @@ Q0 = (127 - 24) << 5                            # bits(2^-24) >> 18
 ENTRY_MIN = 2.0 ** -18                          # THE CONDITION: no table entry lies below this
 TILE_BLOCKS = 128                               # blocks per workgroup of the apply launch (CP_TILE): a sample tile is 128 B samples
 A_MAX, H_MAX = 20, 500
+B_MIN, B_MAX = 8, 48
+STREAM_CARRY = (A_MAX + 2) * B_MAX - 1          # raw samples a stream carries, at most: fewer than (A + 2) B
+STREAM_HIST = 2 * A_MAX + H_MAX + 2             # block gains c a stream carries, at most
 
 RANGES = {"threshold_db": (-60, -6), "ratio": (1.5, 20), "knee_db": (0, 24), "attack_ms": (1, 20), "hold_ms": (0, 500)}
 DEFAULTS = {"threshold_db": -24.0, "ratio": 3.0, "knee_db": 6.0, "attack_ms": 5.0, "hold_ms": 60.0}
@@ -250,3 +268,97 @@ def compress(x: np.ndarray, spec=True, offsets=None, rates=None):
         if specs[s] is not None:
             y[off[s]: off[s + 1]], stats[s] = compress_segment(x[off[s]: off[s + 1]], int(rates[s]), specs[s])
     return y, stats
+
+
+# ---- streams ----------------------------------------------------------------------------------------------------------------------------
+def stream_plan(B: int, A: int, pushed: int, emitted: int, n_in: int, final: bool, H: int = H_MAX) -> dict:
+    """One push of a stream in Python integers: `pushed` samples are in and `emitted` out, `n_in` arrive, `final` says they are the
+    last (a stream may end empty: it emits nothing).  -> total (= pushed + n_in), e_lo (= emitted), n_out (the step emits samples
+    [emitted, E')), emitted (E': total on the last push, else max(0, total // B - A - 1) B), carry_in / carry_out (the raw samples kept
+    in front of and behind the step: [emitted, pushed) and [E', total); 0 behind the last), c_keep (the block gains kept behind the
+    step, those of the blocks [max(0, E' / B - A - H - 1), total // B); 0 behind the last; `H` defaults to the longest hold, the
+    bound).  ValueError for what the library must not be launched with."""
+    B, A, H, pushed, emitted, n_in = int(B), int(A), int(H), int(pushed), int(emitted), int(n_in)
+    if not B_MIN <= B <= B_MAX:
+        raise ValueError(f"compress: B = fs // 1000 lies in {B_MIN} .. {B_MAX} (got {B})")
+    if not 1 <= A <= A_MAX or not 0 <= H <= H_MAX:
+        raise ValueError(f"compress: the attack is 1 .. {A_MAX} blocks and the hold 0 .. {H_MAX} (got {A} and {H})")
+    if pushed < 0 or n_in < 0 or emitted < 0:
+        raise ValueError("compress: a stream's position, output count and push cannot be negative")
+    if emitted != max(0, pushed // B - A - 1) * B:
+        raise ValueError(f"compress: a stream of {pushed} samples has emitted {max(0, pushed // B - A - 1) * B}, not {emitted}")
+    total = pushed + n_in
+    if total >= 1 << 31:
+        raise ValueError("compress: the stream would hold 2^31 samples or more")
+    nbc = total // B
+    e1 = total if final else max(0, nbc - A - 1) * B
+    return dict(total=total, e_lo=emitted, n_out=e1 - emitted, emitted=e1, carry_in=pushed - emitted, carry_out=0 if final else total - e1,
+                c_keep=0 if final else nbc - max(0, e1 // B - A - H - 1))
+
+
+class StreamCompressor:
+    """the NumPy twin of one compressor stream at rate fs with `spec`: `push(x, final) -> y` float32, `stats` the STATS record so far.
+    It holds what the definition says a stream carries and nothing else: `carry`, the raw samples [emitted, pushed), and `hist`, the c
+    of the blocks [h0, pushed // B)."""
+
+    def __init__(self, fs: int, spec=True):
+        self.spec = check(spec)
+        if self.spec is None:
+            raise ValueError("compress: the spec is off")
+        self.fs, self.B = LN.check_rate(fs), LN.check_rate(fs) // 1000
+        self.A, self.H = blocks(self.spec)
+        self.tab = table(self.spec)
+        self.pushed = self.emitted = self.h0 = 0
+        self.done = False
+        self.carry = np.zeros(0, dtype=np.float32)
+        self.hist = np.zeros(0, dtype=np.float32)
+        self.stats = np.zeros((), dtype=STATS)
+        self.stats["min_gain"] = 1.0
+
+    def push(self, x, final: bool = False) -> np.ndarray:
+        if self.done:
+            raise ValueError("compress: the stream has had its last push")
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        B, A, H = self.B, self.A, self.H
+        p = stream_plan(B, A, self.pushed, self.emitted, len(x), final, H)
+        assert p["carry_in"] == len(self.carry) and self.pushed // B - self.h0 == len(self.hist)
+        buf = np.concatenate([self.carry, x])
+        base, total, e1 = self.emitted, p["total"], p["emitted"]      # buf[0] is sample `base` of the signal
+        nbc0 = self.pushed // B
+        nbc1 = -(-total // B) if final else total // B
+        if nbc1 > nbc0:                                               # the blocks this push completes (the last push: the partial one too)
+            pk = block_peaks(buf[nbc0 * B - base: min(nbc1 * B, total) - base], B)
+            c_new = lookup(pk, self.tab)
+            self.stats["n_blocks"] += int((c_new < 1).sum())
+            self.stats["peak"] = max(self.stats["peak"], pk.max())
+            call = np.concatenate([self.hist, c_new])
+        else:
+            call = self.hist
+        if e1 > base:
+            eb0, eb1 = base // B, -(-e1 // B)                         # the blocks emitted: [eb0, eb1)
+            k = np.arange(eb0 - 1 - A - H, eb1 + A + 1)               # the blocks their windows reach; beyond nbc1 on the last push only
+            inside = (k >= 0) & (k < nbc1)
+            assert np.all(k[inside] >= self.h0)
+            cext = np.ones(len(k), dtype=np.float32)
+            cext[inside] = call[k[inside] - self.h0]
+            nm = eb1 - eb0 + 2 + A
+            m = cext[:nm].copy()                                      # m[j], j from eb0 - 1 - A
+            for d in range(1, A + H + 1):
+                np.minimum(m, cext[d: d + nm], out=m)
+            s = ramp(m, A)                                            # s[b], b from eb0 - 1
+            b = np.arange(eb0, eb1 + 1)
+            a = np.minimum(s[np.maximum(b - 1, 0) - (eb0 - 1)], s[np.minimum(b, nbc1 - 1) - (eb0 - 1)]).astype(np.float64)
+            i = np.arange(base, e1)
+            bi, t = i // B - eb0, i % B
+            g = (a[bi] + (a[bi + 1] - a[bi]) * (t.astype(np.float64) / float(B))).astype(np.float32)
+            y = g * buf[: e1 - base]
+            self.stats["min_gain"] = min(self.stats["min_gain"], g.min())
+            self.stats["n_touched"] += int((g < 1).sum())
+        else:
+            y = np.zeros(0, dtype=np.float32)
+        h1 = nbc1 if final else nbc1 - p["c_keep"]
+        self.carry = buf[len(buf) - p["carry_out"]:].copy()
+        self.hist = call[h1 - self.h0:].copy()
+        self.h0 = h1
+        self.pushed, self.emitted, self.done = total, e1, bool(final)
+        return y

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import adpcm as ADPCM
+from . import compressor as CP
 from . import flac as FLAC
 from . import g711 as G711
 from . import limiter as LM
@@ -602,7 +603,7 @@ class Chat:
 
     def decode_windows_pcm16(self, store: torch.Tensor, windows, sample_rates=None, encodings=None, speeds=None, ts_streams=None,
                              rs_streams=None, flac=None, flac_streams=None, limiter=None, lm_streams=None, pauses=None,
-                             pa_streams=None, adpcm=None, adpcm_streams=None) -> List[np.ndarray]:
+                             pa_streams=None, adpcm=None, adpcm_streams=None, compress=None, cp_streams=None) -> List[np.ndarray]:
         """the chunks of many pooled streams that are due together, as the serial streamed path (`_infer`, stream, pcm16) hands them
         out one by one: (slot, prefix tokens, s_lo, s_hi, is_tail) -> int16 pieces, a tail with its silent samples removed
         (CodecEngine.decode_windows; serving.SpeechBatcher.submit_stream).  `encodings`: one per window, None / "ulaw" / "alaw" -- a
@@ -630,6 +631,8 @@ class Chat:
             kw["limiter"], kw["lm_streams"] = limiter, lm_streams
         if pauses is not None:          # a flagged window goes through its pause stream in front of all that (CodecEngine.decode_windows(pauses=))
             kw["pauses"], kw["pa_streams"] = pauses, pa_streams
+        if compress is not None:        # ... and behind that through its compressor stream, in front of the limiter's (CodecEngine.decode_windows(compress=))
+            kw["compress"], kw["cp_streams"] = compress, cp_streams
         return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, **kw)
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
@@ -752,8 +755,11 @@ class Chat:
         return self._finish_piece(y.view(B, int(off[1])), final, pcm16, encoding, on_device)
 
     def _stream_rows_paused(self, hiddens, a: int, b: Optional[int], final: bool, pa_handles, rate: Optional[int] = None, ts_handles=None,
-                            rs_handles=None, lm_handles=None, pcm16: bool = False, encoding=None, fs_handles=None, fs_step=None) -> list:
-        """One chunk of a PAUSED stream (Chat.infer's `stream_pauses`): samples [a, b) of the decode of the current prefix go through
+                            rs_handles=None, lm_handles=None, pcm16: bool = False, encoding=None, fs_handles=None, fs_step=None,
+                            cp_handles=None) -> list:
+        """One chunk of a PAUSED or COMPRESSED stream (Chat.infer's `stream_pauses`, `stream_compress`; `pa_handles` None: not paused;
+        `cp_handles`: the rows' compressor streams, stepped behind the pause streams and in front of the limiter's,
+        CodecEngine.compress_stream_step): samples [a, b) of the decode of the current prefix go through
         the rows' float stages as in `_stream_piece` / `_stream_piece_scaled` (the resampled window at `rate`, or the time scaler's
         streams `ts_handles` and behind them the resampler's `rs_handles`), then into the rows' pause streams `pa_handles`
         (CodecEngine.trim_pauses_stream_step, all rows in one step) -- the one-shot chain's order: behind the last float stage, in front
@@ -781,7 +787,10 @@ class Chat:
             y, off = step(codec.time_scale_stream_step, ts_handles)
             if rs_handles:
                 y, off = step(codec.resample_stream_step, rs_handles)
-        y, off = step(codec.trim_pauses_stream_step, pa_handles)
+        if pa_handles:
+            y, off = step(codec.trim_pauses_stream_step, pa_handles)
+        if cp_handles:
+            y, off = step(codec.compress_stream_step, cp_handles)
         if lm_handles:
             y, off = step(codec.peak_limit_stream_step, lm_handles)
         off = np.asarray(off, dtype=np.int64)
@@ -958,7 +967,7 @@ class Chat:
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
               flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None,
               stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False, adpcm: bool = False, stream_adpcm: bool = False,
-              compress=None):
+              compress=None, stream_compress: bool = False):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -1072,7 +1081,14 @@ class Chat:
         raised.  It is stage 3 1/2 of the output chain: behind the time scaler, the resampler and `pauses`, in front of the loudness
         stage -- so the target is reached on compressed samples -- the limiter, the silence strip, the 16-bit conversion, the
         companding and the file formats.  Every sentence of a split request is compressed alone (one spec only).  A streamed call
-        with it raises: a compressed stream would need the block state carried across chunks."""
+        with it raises: a compressed stream would need the block state carried across chunks -- unless
+        `stream_compress=True` (keyword-only): then `compress` goes with `stream=True` -- one spec for the whole batch; every row gets a
+        compressor stream (CodecEngine.compress_stream_*: the block gains of the hold and the few unemitted raw samples are carried on
+        the device), behind the streamed rate, speed and pause stages and in front of the limiter stream, the conversion, the
+        companding and the streamed file formats, the non-streamed order.  A row's chunks, end to end, are its uncompressed stream's
+        samples compressed as one signal, bit for bit; the stream lags by the attack and at most two more milliseconds, and the last
+        chunk brings the rest.  As with `stream_pauses` a chunk is a list with one array per row.  Not with `split_text`, nor with
+        `use_decoder=False`."""
         mkw = Plan.given("infer", limiter=limiter).kwargs()
         if gain_db is not None and np.ndim(gain_db) != 0:
             raise ValueError("gain_db is one make-up gain for the whole batch")
@@ -1115,9 +1131,19 @@ class Chat:
         if pkw:
             PA.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
         ckw = Plan.given("infer", compress=compress).kwargs()
-        if ckw and stream:
+        if ckw and stream and not stream_compress:
             raise ValueError("compress applies to non-streamed inference only (a compressed stream would need the block state carried "
                              "across chunks)")
+        sckw = {}
+        if ckw and stream:
+            if isinstance(compress, list):             # (a tuple is a checked spec, as the endpoint passes it on)
+                raise ValueError("a compressed stream takes one compressor spec for the whole batch")
+            if split_text:
+                raise ValueError("a compressed stream does not go with split_text (every split batch would end the stream)")
+            if not use_decoder:
+                raise ValueError("a compressed stream needs the hidden-state decoder (use_decoder=True)")
+            LN.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate))
+            sckw, ckw = {"cp_spec": CP.check(compress, "infer")}, {}
         if ckw and split_text and isinstance(compress, list):
             raise ValueError("a split_text request is one waveform: it takes one compressor spec")
         if ckw:
@@ -1206,7 +1232,7 @@ class Chat:
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
                               sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}),
-                              **({} if split_host else lkw), **pkw, **smkw, **spkw, **akw, **ckw)
+                              **({} if split_host else lkw), **pkw, **smkw, **spkw, **akw, **ckw, **sckw)
         if stream:
             return res_gen
         if refine_text_only:
@@ -1248,8 +1274,8 @@ class Chat:
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None, pa_spec=None,
-               adpcm: bool = False, compress=None):
-        """core.py:395-503 (generator).  `pa_spec` with `stream`: the rows' pause streams and their spec (Chat.infer's `stream_pauses`).  `lm_gain` with `stream`: the rows' limiter streams and their pre-gain (Chat.infer's `stream_limiter`).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
+               adpcm: bool = False, compress=None, cp_spec=None):
+        """core.py:395-503 (generator).  `cp_spec` with `stream`: the rows' compressor streams and their spec (Chat.infer's `stream_compress`).  `pa_spec` with `stream`: the rows' pause streams and their spec (Chat.infer's `stream_pauses`).  `lm_gain` with `stream`: the rows' limiter streams and their pre-gain (Chat.infer's `stream_limiter`).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
             text = [text]
@@ -1273,6 +1299,7 @@ class Chat:
         fs = [] if stream and (flac or adpcm) and pcm16 else None      # a streamed FLAC / ADPCM file: the rows' encoder streams, opened at the first chunk
         lm = [] if stream and lm_gain is not None else None    # a limited stream: the rows' limiter streams, opened at the first chunk
         pa = [] if stream and pa_spec is not None else None    # a paused stream: the rows' pause streams, opened at the first chunk
+        cp = [] if stream and cp_spec is not None else None    # a compressed stream: the rows' compressor streams, opened at the first chunk
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
                                            encoding, speed, ts, rs, **({"flac": True} if flac else {}),
@@ -1281,8 +1308,11 @@ class Chat:
                                            **({} if limiter is None else {"limiter": limiter}),
                                            **({} if lm is None else {"lm": lm, "lm_gain": lm_gain}),
                                            **({} if pa is None else {"pa": pa, "pa_spec": pa_spec}), **({"adpcm": True} if adpcm else {}),
-                                           **({} if compress is None else {"compress": compress}))
+                                           **({} if compress is None else {"compress": compress}),
+                                           **({} if cp is None else {"cp": cp, "cp_spec": cp_spec}))
         finally:
+            for h in cp or ():
+                self.codec.compress_stream_close(h)
             for h in pa or ():
                 self.codec.trim_pauses_stream_close(h)
             for h in lm or ():
@@ -1297,7 +1327,7 @@ class Chat:
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
                        rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None, pa=None, pa_spec=None,
-                       adpcm: bool = False, compress=None):
+                       adpcm: bool = False, compress=None, cp=None, cp_spec=None):
         """the batch loop of `_infer`"""
         # the rows' encoder streams `fs` are FLAC streams, or with `adpcm` IMA ADPCM streams: the same placement, the same host twin
         Twin = ADPCM.StreamEncoder if adpcm else FLAC.StreamEncoder
@@ -1340,16 +1370,21 @@ class Chat:
                 lm.extend(self.codec.peak_limit_stream_open(CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate, lm_gain) for _ in rows)
             return {"lm_handles": lm}
         def paused(rows, a, b, final):
-            """one chunk of a paused stream: a list with one array per row (`_stream_rows_paused`); every stream is opened at the first"""
+            """one chunk of a paused or compressed stream: a list with one array per row (`_stream_rows_paused`); every stream is opened
+            at the first"""
             out_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate
-            if not pa:
+            if pa is not None and not pa:
                 pa.extend(self.codec.trim_pauses_stream_open(out_rate, pa_spec) for _ in rows)
+            if cp is not None and not cp:
+                cp.extend(self.codec.compress_stream_open(out_rate, cp_spec) for _ in rows)
             if ts is not None and not ts:
                 open_streams(rows)
             if fs is not None and not fs:
                 fs.extend(fs_open(out_rate) for _ in rows)
             return self._stream_rows_paused(rows, a, b, final, pa, sample_rate, ts, rs, limited(rows).get("lm_handles"), pcm16,
-                                            encoding if pcm16 else None, fs, **({"fs_step": fs_step} if adpcm else {}))
+                                            encoding if pcm16 else None, fs, **({"fs_step": fs_step} if adpcm else {}),
+                                            **({} if cp is None else {"cp_handles": cp}))
+        rowwise = pa is not None or cp is not None             # the chunks are lists with one array per row
         length = 0
         pass_batch_count = 0
         for lo in range(0, len(text), step):
@@ -1399,7 +1434,7 @@ class Chat:
                 skw = {"rate": sample_rate} if sample_rate is not None else {}      # 24 kHz: today's call, argument for argument
                 if encoding is not None and pcm16:
                     skw["encoding"] = encoding
-                if pa is not None:
+                if rowwise:
                     piece = paused(src, length, length + params_infer_code.stream_speed, False)
                 elif ts is not None:
                     if not ts:
@@ -1408,7 +1443,7 @@ class Chat:
                                                       encoding if pcm16 else None, **rkw_s, **dkw, **limited(src))
                 else:
                     piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw, **dkw, **limited(src))
-                if fs is not None and pa is None:
+                if fs is not None and not rowwise:
                     piece = flac_chunks(piece, False)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
                 # that is BELOW `a`: `length` and `pass_batch_count` are not reset between split batches, so the first yields of a
@@ -1416,7 +1451,7 @@ class Chat:
                 # (the decode width of a T-token prefix is 256 (2 T - 1) samples on both decode paths; never negative for an empty yield)
                 length = min(length + params_infer_code.stream_speed, max(0, 256 * (2 * max(int(r.size(0)) for r in src) - 1)))
                 yield piece
-            if stream and last is not None and pa is not None:      # rows of different lengths: filtered and converted row by row
+            if stream and last is not None and rowwise:      # rows of different lengths: filtered and converted row by row
                 tail = paused(last.hiddens, length, None, True)
                 last.destroy()
                 yield tail

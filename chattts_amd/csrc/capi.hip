@@ -2264,6 +2264,83 @@ extern "C" int ctts_peak_limit_stream_step(const float* x, int64_t n_x, const ct
   CK(launch_peak_limit_stream(x, (const LmStream*)st_dev, n_streams, n_out_max, y, carry, stats, reset, (hipStream_t)stream));
   return 0;
 }
+// ---- the compressor of streams: the host's arithmetic (compressor.py: stream_plan) and every check the launches trust ------------------
+static_assert(sizeof(ctts_cp_stream) == 104 && sizeof(CpStream) == 104 && offsetof(ctts_cp_stream, cb_off) == offsetof(CpStream, cb_off) &&
+              offsetof(ctts_cp_stream, slot) == offsetof(CpStream, slot) && offsetof(ctts_cp_stream, rate) == offsetof(CpStream, rate) &&
+              offsetof(ctts_cp_stream, tab) == offsetof(CpStream, tab) && offsetof(ctts_cp_stream, c_in) == offsetof(CpStream, c_in) &&
+              offsetof(ctts_cp_stream, h_out) == offsetof(CpStream, h_out) && CTTS_CP_SCARRY == CP_SCARRY && CTTS_CP_SHIST == CP_SHIST,
+              "ctts_cp_stream layout");
+extern "C" size_t ctts_compress_stream_scratch_bytes(int64_t n_blocks) {
+  if (n_blocks < 0 || n_blocks >= (1ll << 31)) return 0;
+  return ((size_t)std::max<int64_t>(n_blocks, 4) * sizeof(float) + 15) / 16 * 16;
+}
+extern "C" int ctts_compress_stream_step(const float* x, int64_t n_x, const ctts_cp_stream* st_dev, const ctts_cp_stream* st_host,
+                                         int32_t n_streams, const float* tab_dev, const float* tab_host, int32_t n_tab, float* y, int64_t n_y,
+                                         float* carry, float* hold, void* stats, int32_t n_slots, void* scratch, size_t scratch_bytes,
+                                         void* stream) {
+  const char* who = "ctts_compress_stream_step";
+  if (!st_dev || !st_host || !tab_dev || !tab_host || !carry || !hold || !stats || !scratch)
+    return fail("%s: a null pointer (both descriptor tables, the gain tables on the device and the host, the carry, the hold, the stats and the scratch are needed)", who);
+  if (n_x < 0 || n_y < 0 || (!x && n_x) || (!y && n_y)) return fail("%s: a null pointer (x or y) with a length other than 0", who);
+  if (n_streams < 1 || n_streams > 1024) return fail("%s: need 1 <= n_streams <= 1024 (got %d)", who, n_streams);
+  if (n_slots < 1) return fail("%s: the state pool has no slot", who);
+  if (((uintptr_t)x & 15) || ((uintptr_t)tab_dev & 15) || ((uintptr_t)scratch & 15) || ((uintptr_t)y & 3) || ((uintptr_t)carry & 3) ||
+      ((uintptr_t)hold & 3) || ((uintptr_t)stats & 3))
+    return fail("%s: x, the gain tables and the scratch must be 16-byte aligned, y, the carry, the hold and the stats 4-byte aligned", who);
+  if (n_x && n_y && x < y + n_y && y < x + n_x) return fail("%s: y must not overlap x (a stream is never compressed in place)", who);
+  if (n_tab < 1 || n_tab > n_streams) return fail("%s: need 1 <= n_tab <= n_streams gain tables (got %d for %d streams)", who, n_tab, n_streams);
+  for (int t = 0; t < n_tab; ++t)
+    for (int q = 0; q < CP_TABLE; ++q) {
+      const float g = tab_host[(size_t)t * CP_TABLE + q];
+      if (!(g >= 0x1p-18f && g <= 1.0f)) return fail("%s: table %d: entry %d is a gain in 2^-18 .. 1 (got %g)", who, t, q, (double)g);
+    }
+  std::vector<char> seen((size_t)n_slots, 0);
+  long long nb_new_max = 0, nb_out_max = 0, cb = 0;
+  for (int i = 0; i < n_streams; ++i) {
+    const ctts_cp_stream& w = st_host[i];
+    if (w.slot < 0 || w.slot >= n_slots) return fail("%s: compressor stream %d: slot %d is outside the pool of %d", who, i, w.slot, n_slots);
+    if (seen[w.slot]) return fail("%s: compressor stream %d: slot %d appears twice in one launch", who, i, w.slot);
+    seen[w.slot] = 1;
+    if (w.phase != 0 && w.phase != 1) return fail("%s: compressor stream %d: phase %d is neither 0 nor 1", who, i, w.phase);
+    if (w.rate < 1000 * CP_BMIN || w.rate > 1000 * CP_BMAX || w.rate % 10 != 0)
+      return fail("%s: compressor stream %d: the rate is a multiple of 10 Hz in %d .. %d (got %d)", who, i, 1000 * CP_BMIN, 1000 * CP_BMAX, w.rate);
+    if (w.A < 1 || w.A > CP_AMAX) return fail("%s: compressor stream %d: the attack is 1 .. %d blocks (got %d)", who, i, CP_AMAX, w.A);
+    if (w.H < 0 || w.H > CP_HMAX) return fail("%s: compressor stream %d: the hold is 0 .. %d blocks (got %d)", who, i, CP_HMAX, w.H);
+    if (w.tab < 0 || w.tab >= n_tab) return fail("%s: compressor stream %d: gain table %d is outside the %d given", who, i, w.tab, n_tab);
+    if (w.n_in < 0 || w.pos < 0 || w.in_off < 0 || w.out_off < 0 || w.e_lo < 0 || w.n_out < 0)
+      return fail("%s: compressor stream %d: a negative length, position or offset", who, i);
+    if (w.pos >= (1ll << 31) || w.n_in >= (1ll << 31) || w.pos + w.n_in >= (1ll << 31))
+      return fail("%s: compressor stream %d would hold 2^31 samples or more", who, i);
+    if (w.in_off + w.n_in > n_x) return fail("%s: compressor stream %d: the push lies outside the input (%lld floats)", who, i, (long long)n_x);
+    const long long B = w.rate / 1000, end = w.pos + w.n_in, reach = w.A + w.H + 1;
+    const bool fin = w.total != -1;
+    if (fin && w.total != end)
+      return fail("%s: compressor stream %d: a last push ends the stream at pos + n_in = %lld, got total %lld", who, i, end, (long long)w.total);
+    const long long nbc0 = w.pos / B, nbc1 = fin ? (end + B - 1) / B : end / B;
+    const long long e0 = std::max(0ll, nbc0 - w.A - 1) * B, e1 = fin ? end : std::max(0ll, end / B - w.A - 1) * B;
+    if (w.e_lo != e0) return fail("%s: compressor stream %d: %lld samples have emitted %lld, got e_lo %lld", who, i, (long long)w.pos, e0, (long long)w.e_lo);
+    if (w.n_out != e1 - e0) return fail("%s: compressor stream %d: the step emits %lld samples, got %lld", who, i, e1 - e0, (long long)w.n_out);
+    if (w.out_off + w.n_out > n_y) return fail("%s: compressor stream %d: the chunk lies outside the output (%lld floats)", who, i, (long long)n_y);
+    const long long c_in = w.pos - e0, c_out = fin ? 0 : end - e1;
+    const long long h_in = nbc0 - std::max(0ll, e0 / B - reach), h_out = fin ? 0 : nbc1 - std::max(0ll, e1 / B - reach);
+    if (w.c_in != c_in || w.c_out != c_out)
+      return fail("%s: compressor stream %d: the step carries %lld samples in and %lld out, got %d and %d", who, i, c_in, c_out, w.c_in, w.c_out);
+    if (w.h_in != h_in || w.h_out != h_out)
+      return fail("%s: compressor stream %d: the step carries %lld block gains in and %lld out, got %d and %d", who, i, h_in, h_out, w.h_in, w.h_out);
+    if (c_in > CP_SCARRY || c_out > CP_SCARRY || h_in > CP_SHIST || h_out > CP_SHIST)       // cannot be, by the ranges above
+      return fail("%s: compressor stream %d: the carry does not fit its slot", who, i);
+    if (w.cb_off != cb) return fail("%s: compressor stream %d: its new block gains start at float %lld of the scratch, got %lld", who, i, cb, (long long)w.cb_off);
+    cb += nbc1 - nbc0;
+    nb_new_max = std::max(nb_new_max, nbc1 - nbc0);
+    nb_out_max = std::max(nb_out_max, (e1 - e0 + B - 1) / B);
+  }
+  const size_t need = ctts_compress_stream_scratch_bytes(cb);
+  if (need == 0 || scratch_bytes < need) return fail("%s: scratch too small (%zu bytes, need %zu)", who, scratch_bytes, need);
+  CttsDeviceGuard dg(stream);
+  CK(launch_compress_stream(x, (const CpStream*)st_dev, n_streams, nb_new_max, nb_out_max, tab_dev, y, carry, hold, stats, (float*)scratch,
+                            (hipStream_t)stream));
+  return 0;
+}
 extern "C" size_t ctts_trim_pauses_ragged_scratch_bytes(int64_t frames, int32_t n_seg) {
   if (frames < 1 || frames >= (1ll << 31) || n_seg < 1 || n_seg > 65535) return 0;
   return pause_scratch_bytes(frames, n_seg);

@@ -588,6 +588,23 @@ static inline long long compress_blocks(long long total, int n_seg) { return tot
 // compress_blocks(..) float32 of scratch.  A memset node and two launches.  Every bound is the caller's to check
 hipError_t launch_compress_ragged(const float* x, float* y, const long long* off, int n_seg, long long nb_max, const int32_t* rate,
                                   const int32_t* par, const float* tabs, void* stats, float* cb, hipStream_t st);
+#define CP_SCARRY 1056         // floats of one raw carry buffer of a compressor stream slot: fewer than (A + 2) B samples; a slot has two
+#define CP_SHIST 544           // floats of one history buffer of a slot: the c of at most 2 A + H + 2 blocks; a slot has two
+// ctts_cp_stream (include/chattts_amd.h), field for field (capi.hip asserts the layout): one push of one compressor stream.
+// x[in_off, in_off + n_in) are samples [pos, pos + n_in) of the stream; total: its length when this push is the last, else -1; the step
+// writes samples [e_lo, e_lo + n_out) of the compressed stream to y[out_off ..] and the c of the blocks the push completes to the
+// scratch from float cb_off; slot / phase: the state slot and which half of its carry and history the step reads (it writes the other);
+// tab: its gain table among the step's; c_in / c_out, h_in / h_out: the raw samples and the block gains kept in front of and behind it
+struct CpStream {
+  long long in_off, n_in, pos, total, e_lo, n_out, out_off, cb_off;
+  int32_t slot, phase, rate, A, H, tab, c_in, c_out, h_in, h_out;
+};
+// one step of n_streams compressor streams: tab on the device, tabs[n][CP_TABLE], y a buffer of its own, carry [n_slots][2][CP_SCARRY]
+// and hold [n_slots][2][CP_SHIST] floats, stats [n_slots] 16-byte records that the caller set to {1, 0, 0, 0} when the stream was opened,
+// cb the scratch for the new block gains.  nb_new_max / nb_out_max: the most blocks a push completes / a step emits (grid sizes).  Two
+// launches (one where no push completes a block).  Every bound is the caller's to check
+hipError_t launch_compress_stream(const float* x, const CpStream* tab, int n_streams, long long nb_new_max, long long nb_out_max,
+                                  const float* tabs, float* y, float* carry, float* hold, void* stats, float* cb, hipStream_t st);
 
 // ---- pause control (pauses.hip) -------------------------------------------------------------------
 #define PA_FMIN 80            // a frame is F = fs / 100 samples (integer division): 8 kHz ..

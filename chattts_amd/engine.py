@@ -1567,10 +1567,11 @@ class CodecEngine:
     # Every streamed stage keeps its streams in a `statepool.StatePool` of its own, built on first use: label -> (the class attribute
     # with the pool's first size -- it doubles when every slot is taken --, the device buffers' {name: (tail, dtype)}; the library is
     # told the slot count and indexes them by slot).  The records are `statepool`'s: TimeScaleRec, ResampleRec, LimiterRec, PauseRec,
-    # FlacRec, AdpcmRec.
-    TS_STREAM_SLOTS = RS_STREAM_SLOTS = LM_STREAM_SLOTS = FLAC_STREAM_SLOTS = ADPCM_STREAM_SLOTS = 64
+    # FlacRec, AdpcmRec, CompressRec.
+    TS_STREAM_SLOTS = RS_STREAM_SLOTS = LM_STREAM_SLOTS = FLAC_STREAM_SLOTS = ADPCM_STREAM_SLOTS = CP_STREAM_SLOTS = 64
     PA_STREAM_SLOTS = 16
     ADPCM_CARRY = 2048        # int16 per slot: S - 1 = 2040 at 48 kHz
+    CP_CARRY, CP_HIST = 1056, 544   # float32 per half of a slot: compressor.STREAM_CARRY / STREAM_HIST rounded up to 16 bytes (CTTS_CP_SCARRY / _SHIST)
     POOLS = {
         "time_scale": ("TS_STREAM_SLOTS", dict(carry=((2, TS.CARRY), torch.float32), state=((4,), torch.int32))),
         "resample": ("RS_STREAM_SLOTS", dict(carry=((2, RS.CARRY), torch.float32))),
@@ -1578,6 +1579,8 @@ class CodecEngine:
         "pauses": ("PA_STREAM_SLOTS", dict(carry=((2, (PA.STREAM_FRAMES + 1) * 480), torch.float32), state=((PA.STATE,), torch.int32))),
         "flac": ("FLAC_STREAM_SLOTS", dict(carry=((FLAC.MIN_BLOCK,), torch.int16))),
         "adpcm": ("ADPCM_STREAM_SLOTS", dict(carry=((ADPCM_CARRY,), torch.int16))),
+        "compress": ("CP_STREAM_SLOTS", dict(carry=((2, CP_CARRY), torch.float32), hist=((2, CP_HIST), torch.float32),
+                                             stats=((4,), torch.int32))),                                           # one compressor.STATS record per slot
     }
 
     def _pool(self, label: str) -> SP.StatePool:
@@ -2046,6 +2049,117 @@ class CodecEngine:
             return y, work[: CP.STATS.itemsize * n_seg].cpu().numpy().view(CP.STATS)
         return y
 
+    # -- the compressor of streams: per-stream device state (csrc/compressor.hip, compress_stream_*_k) -----------------------------------
+    def compress_stream_open(self, rate: int, spec=True) -> int:
+        """A stream of the compressor at `rate` Hz with `spec` (True: the defaults, or a dict of `compress`'s fields): -> its handle, a
+        slot of the engine's state pool.  The first step of a stream reads neither carry nor history, so those are not cleared; the
+        slot's RECORD is set to (1, 0, 0, 0) here, by a device-side copy in stream order in front of the stream's first step -- the
+        steps touch it by atomics only.  ValueError for a rate or spec `compress` refuses, and for a spec that is off."""
+        rate = LN.check_rate(rate)
+        spec = CP.check(spec, "compress_stream_open")
+        if spec is None:
+            raise ValueError("compress_stream_open: the spec is off, there is nothing to compress")
+        pool = self._pool("compress")
+        slot = pool.open(SP.CompressRec(rate, spec, 0, 0, 0, False))
+        if "_cp_rec0" not in self.__dict__:
+            self._cp_rec0 = torch.from_numpy(np.array([1.0, 0.0, 0.0, 0.0], dtype=np.float32).view(np.int32)).to(self.device)
+        pool.buf["stats"][slot].copy_(self._cp_rec0)
+        return slot
+
+    def compress_stream_close(self, handle: int) -> None:
+        """gives the stream's slot back (any time: finished, or abandoned half way)"""
+        self._pool("compress").close(handle)
+
+    def compress_streams_in_use(self) -> int:
+        """the streams that are open: slots of the state pool not on its free list"""
+        return self._pool("compress").in_use
+
+    def compress_stream_plan(self, handle: int, n_in: int, final: bool) -> dict:
+        """`compressor.stream_plan` of the stream's next push: what a step with `n_in` more samples would emit and keep"""
+        rec = self._pool("compress").live(handle)
+        A, H = CP.blocks(rec.spec)
+        return CP.stream_plan(rec.rate // 1000, A, rec.pushed, rec.emitted, n_in, final, H)
+
+    def compress_stream_stats(self, handle: int) -> np.ndarray:
+        """the stream's compressor.STATS record so far (a device read: it waits for the steps so far): the blocks counted as their
+        gains were computed, the samples as they were emitted; after the last push it is `compress`'s record of the whole signal."""
+        pool = self._pool("compress")
+        pool.get(handle)
+        return pool.buf["stats"][int(handle)].cpu().numpy().view(CP.STATS)[0]
+
+    def _cp_descriptors(self, pushes):
+        """pushes [(handle, in_off, n_in, final)], one per stream -> (CP_STREAM table with out_off unset, in the pushes' order, the
+        distinct specs' gain tables [n_tab, TABLE], commit: handle -> its new host record).  All in Python integers and before
+        anything is launched; the records change only when the caller commits."""
+        pool, commit, specs = self._pool("compress"), {}, {}
+        tab = np.zeros(len(pushes), _lib.CP_STREAM)
+        cb = 0
+        for i, (h, in_off, n_in, final) in enumerate(pushes):
+            h = int(h)
+            if h in commit:
+                raise ValueError("compress: a stream appears twice in one step")
+            rec = pool.live(h)
+            B = rec.rate // 1000
+            A, H = CP.blocks(rec.spec)
+            p = CP.stream_plan(B, A, rec.pushed, rec.emitted, n_in, final, H)
+            nbc0, nbc1 = rec.pushed // B, -(-p["total"] // B) if final else p["total"] // B
+            h_in = nbc0 - max(0, rec.emitted // B - A - H - 1)
+            tab[i] = (int(in_off), int(n_in), rec.pushed, p["total"] if final else -1, rec.emitted, p["n_out"], 0, cb, h, rec.phase, rec.rate,
+                      A, H, specs.setdefault(rec.spec, len(specs)), p["carry_in"], p["carry_out"], h_in, p["c_keep"])
+            cb += nbc1 - nbc0
+            commit[h] = rec._replace(pushed=p["total"], emitted=p["emitted"], phase=rec.phase ^ 1, done=bool(final))
+        return tab, np.ascontiguousarray(np.stack([CP.table(s) for s in specs])), commit, cb
+
+    def compress_stream_step(self, x: torch.Tensor, pushes, out: Optional[torch.Tensor] = None, out_off=None):
+        """ONE step of many compressor streams (ctts_compress_stream_step, two launches whatever their number, rates and specs): `x`,
+        a 1-D float32 device tensor, holds the new samples of every stream; `pushes` = [(handle, in_off, n_in, final)]: x[in_off,
+        in_off + n_in) continue stream `handle` (n_in 0: nothing new), `final`: they are its last.  -> (y, off): stream i's chunk is
+        y[off[i], off[i+1]) (possibly empty; `compress_stream_plan`'s n_out), a tensor of its own -- x is never written.  A stream
+        lags by (A + 1) blocks of 1 ms and its open block, whatever its hold; the chunks of a stream, end to end, are `compress` of
+        its concatenated pushes with the stream's spec, bit for bit, however they were cut, and after the last push
+        `compress_stream_stats` is that call's record.  A handle may appear once per call.  `out` with `out_off`: a contiguous 1-D
+        float32 device tensor of the caller's (not x) and one offset per push -- stream i's chunk is written to out[out_off[i] ..]
+        instead, and (out, out_off) comes back.  Every refusal (ValueError here, EngineError from the library) comes before the
+        first launch and leaves all streams as they were."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+            raise ValueError("compress: a contiguous 1-D float32 device tensor")
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 1
+                                    and out.is_contiguous() and out_off is not None and len(out_off) == len(pushes)):
+            raise ValueError("compress: out is a contiguous 1-D float32 device tensor, with one offset per push")
+        SP.check_pushes("compress", pushes, x.numel(), once=False)            # a stream twice: `_cp_descriptors` refuses
+        tab, tabs_h, commit, n_new = self._cp_descriptors(pushes)
+        off = np.zeros(len(pushes) + 1, np.int64)
+        np.cumsum(tab["n_out"], out=off[1:])
+        if int(off[-1]) >= 1 << 31:
+            raise ValueError("compress: the output would hold 2^31 samples or more")
+        if out is None:
+            tab["out_off"] = off[:-1]
+            y = torch.empty((int(off[-1]),), dtype=torch.float32, device=x.device)
+        else:
+            off = np.array([int(v) for v in out_off], dtype=np.int64)
+            if np.any(off < 0) or np.any(off + tab["n_out"] > out.numel()):
+                raise ValueError("compress: a chunk lies outside `out`")
+            tab["out_off"], y = off, out
+        if x.data_ptr() % 16:
+            x = x.clone()                                                     # the peak launch loads 16 bytes at a time
+        pool = self._pool("compress")
+        up = torch.from_numpy(np.concatenate([tabs_h.view(np.uint8).reshape(-1), tab.view(np.uint8)])).to(x.device)   # one upload, the gain tables first: 16-byte aligned
+        sb = int(self.lib.ctts_compress_stream_scratch_bytes(n_new))
+        if sb == 0:
+            raise ValueError("compress: the step would complete 2^31 blocks or more")
+        work = device_scratch(sb, x.device)
+        st = torch.cuda.current_stream(x.device)
+        _lib.check(self.lib.ctts_compress_stream_step(
+            x.data_ptr() if x.numel() else None, x.numel(), up.data_ptr() + tabs_h.nbytes, tab.ctypes.data_as(C.c_void_p), len(tab),
+            up.data_ptr(), tabs_h.ctypes.data_as(C.c_void_p), int(tabs_h.shape[0]), y.data_ptr() if y.numel() else None, y.numel(),
+            pool.buf["carry"].data_ptr(), pool.buf["hist"].data_ptr(), pool.buf["stats"].data_ptr(), pool.slots, work.data_ptr(), sb,
+            st.cuda_stream), "ctts_compress_stream_step")
+        up.record_stream(st)
+        work.record_stream(st)
+        x.record_stream(st)
+        pool.commit(commit)
+        return y, off
+
     # -- the limiter of streams: per-stream device state (csrc/limiter.hip, limiter_stream_k) ---------------------------------------------
     def peak_limit_stream_open(self, rate: int, gain=1.0) -> int:
         """A stream of the limiter at `rate` Hz with the float32 pre-gain `gain` (any positive finite float32): -> its handle, a slot
@@ -2510,7 +2624,8 @@ class CodecEngine:
 
     def decode_windows(self, store: torch.Tensor, windows, pcm16: bool = True, keep_thr: Optional[float] = None, product: str = "f64",
                        sample_rates=None, encodings=None, speeds=None, ts_streams=None, rs_streams=None, flac=None, flac_streams=None,
-                       limiter=None, lm_streams=None, pauses=None, pa_streams=None, adpcm=None, adpcm_streams=None):
+                       limiter=None, lm_streams=None, pauses=None, pa_streams=None, adpcm=None, adpcm_streams=None, compress=None,
+                       cp_streams=None):
         """The chunks of many streamed utterances in ONE ragged decoder pass, each at its own position (ctts_codec_decode_windows).
         `store`: a hidden-state store [slots, hid_cap, 768] float32 on the device (SlotPool.hiddens; read in place, nothing is sliced
         or copied per slot).  `windows`: a list of (slot, Tn, s_lo, s_hi) or (slot, Tn, s_lo, s_hi, tail): samples [s_lo, s_hi) (s_hi
@@ -2582,7 +2697,16 @@ class CodecEngine:
         and by the rules of a FLAC push: behind the conversion, a `tail` is the last push and is stripped by the keep mask on the
         device, an empty crop still steps its stream, several windows of one stream go to successive rounds.  ONE `adpcm_stream_step`
         for the flagged windows of the call (two launches; where no tail is stripped, one copy: the blocks).  A window takes FLAC or
-        ADPCM, not both; neither goes with an encoding."""
+        ADPCM, not both; neither goes with an encoding.
+        `compress` (None, or all None / False: the call above, argument for argument) with `cp_streams`: one flag and one entry per
+        window, the handle of the compressor stream (`compress_stream_open`, at the window's output rate; the stream holds the spec)
+        a flagged window continues.  A flagged window PUSHES its float32 samples -- behind the same float stages as the limiter's, and
+        behind its pause stream -- into its compressor stream and goes on with what that step emits (`compress_stream_step`: the
+        stream lags by its attack and two blocks of 1 ms at the most; a window marked `tail` is the stream's last push): in front of
+        the limiter stream, the conversion, a tail's strip, G.711, FLAC and ADPCM, the non-streamed order.  One compressor step per
+        round (two launches), no copy of its own.  Unflagged windows return the bytes they return without `compress`."""
+        cp = self._window_streams("compress", "cp_streams", "compressor", compress, cp_streams, windows, sample_rates,
+                                  flagged=lambda f: f is not None and f is not False)
         pa = self._window_streams("pauses", "pa_streams", "pause", pauses, pa_streams, windows, sample_rates,
                                   flagged=lambda f: f is not None and f is not False)
         lm = self._window_streams("limiter", "lm_streams", "limiter", limiter, lm_streams, windows, sample_rates,
@@ -2615,11 +2739,11 @@ class CodecEngine:
                 if not pcm16:
                     raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
                 laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
-        if lm is not None or pa is not None:
+        if lm is not None or pa is not None or cp is not None:
             return self._decode_windows_limited(store, windows, [None] * len(windows) if lm is None else lm, q, laws, fl, pcm16, keep_thr, product,
                                                 dict(sample_rates=sample_rates, encodings=encodings, speeds=speeds, ts_streams=ts_streams,
                                                      rs_streams=rs_streams, flac=flac, flac_streams=flac_streams, adpcm=adpcm,
-                                                     adpcm_streams=adpcm_streams), pa)
+                                                     adpcm_streams=adpcm_streams), pa, cp)
         if q is not None:
             rates = None
             if sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
@@ -2731,14 +2855,15 @@ class CodecEngine:
                                      np.int16 if pcm16 else np.float32, out, fl)
 
     def _decode_windows_limited(self, store: torch.Tensor, windows, lm, q, laws, fl, pcm16: bool, keep_thr: Optional[float], product: str,
-                                per_window: dict, pa=None) -> list:
-        """`decode_windows` with at least one window behind a limiter stream or a pause stream (lm, pa: the windows' handles or
-        None; q, laws, fl: the call's checked speeds, laws and FLAC streams; per_window: its per-window arguments, to be cut for the
-        passes)"""
+                                per_window: dict, pa=None, cp=None) -> list:
+        """`decode_windows` with at least one window behind a limiter stream, a pause stream or a compressor stream (lm, pa, cp: the
+        windows' handles or None; q, laws, fl: the call's checked speeds, laws and FLAC streams; per_window: its per-window
+        arguments, to be cut for the passes)"""
         pick = lambda v, ix: None if v is None else [v[i] for i in ix]
         pa = [None] * len(windows) if pa is None else pa
-        idx = [i for i in range(len(windows)) if lm[i] is not None or pa[i] is not None]
-        rest = [i for i in range(len(windows)) if lm[i] is None and pa[i] is None]
+        cp = [None] * len(windows) if cp is None else cp
+        idx = [i for i in range(len(windows)) if lm[i] is not None or pa[i] is not None or cp[i] is not None]
+        rest = [i for i in range(len(windows)) if lm[i] is None and pa[i] is None and cp[i] is None]
         out: list = [None] * len(windows)
         if rest:                                                   # the unflagged windows: the call without the limiter
             for i, a in zip(rest, self.decode_windows(store, pick(windows, rest), pcm16, keep_thr, product,
@@ -2778,12 +2903,24 @@ class CodecEngine:
                 parts.append(y)
                 base += y.numel()
             x = torch.cat(parts)
+        # the compressor streams' steps, behind the pauses' and in front of the limiter's, by the same rule; a step emits into a tensor of
+        # its own, which goes behind x
+        _, crounds = SP.rounds(cp[i] for i in idx)
+        if crounds:
+            parts, base = [x], x.numel()
+            for rnd in crounds:
+                y, o = self.compress_stream_step(x, [(cp[idx[k]], *src.get(idx[k], (0, 0)), tails[k]) for k in rnd])
+                for j, k in enumerate(rnd):
+                    src[idx[k]] = (base + int(o[j]), int(o[j + 1] - o[j]))
+                parts.append(y)
+                base += y.numel()
+            x = torch.cat(parts)
         # the limiter's steps: the r-th window of a stream in round r; the limited chunks start on multiples of 8 samples, zeros between
         recs, shadow = self._pool("limiter").records, {}
         _, rounds = SP.rounds(lm[i] for i in idx)
         n = np.zeros(len(idx), np.int64)
         for k, i in enumerate(idx):
-            if lm[i] is None:                                      # paused only: the chunk goes on as it came out
+            if lm[i] is None:                                      # paused or compressed only: the chunk goes on as it came out
                 n[k] = src.get(i, (0, 0))[1]
                 continue
             rec = shadow.get(lm[i], recs[lm[i]])

@@ -98,7 +98,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
                stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
                pauses: bool = False, limiter: bool = False, stream_limiter: bool = False, stream_pauses: bool = False,
-               adpcm: bool = False, stream_adpcm: bool = False, compress: bool = False):
+               adpcm: bool = False, stream_adpcm: bool = False, compress: bool = False, stream_compress: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -200,7 +200,11 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     the loudness stage, the limiter and the 16-bit conversion (Chat.infer(compress=) / SpeechBatcher.submit(compress=)), in whatever
     format, rate and speed the other options allow; false or null leaves the dynamics alone; a bad spec gets a 400 with the
     validator's message; `"stream": true` with it gets a 400 (a compressed stream would need the block state carried across chunks),
-    and /health carries `"compress": true`."""
+    and /health carries `"compress": true`.  `stream_compress=True` (with `compress`; default off): a body with `"stream": true` and
+    `"compress"` is served -- the stream's chunks come out of a compressor stream that carries the hold's block gains and the few
+    unemitted samples across chunks (CodecEngine.compress_stream_*), the attack and at most two milliseconds behind -- from the pool where
+    `batch_streams` allows it and the batcher was built with `stream_compress=True`, serially otherwise (Chat.infer(stream=True,
+    compress=, stream_compress=True)); /health carries `"stream_compress": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -221,7 +225,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                                 **({"stream_flac": True} if flac and stream_flac else {}),
                                 **({"stream_limiter": True} if limiter and stream_limiter else {}),
                                 **({"stream_pauses": True} if pauses and stream_pauses else {}),
-                                **({"stream_adpcm": True} if adpcm and stream_adpcm else {}))
+                                **({"stream_adpcm": True} if adpcm and stream_adpcm else {}),
+                                **({"stream_compress": True} if compress and stream_compress else {}))
     if batcher is not None:
         gpu_lock = batcher.lock
     app.state.batcher = batcher
@@ -237,6 +242,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     pool_stream_limiter = pool_streams and limiter_streams and bool(getattr(batcher, "stream_limiter", False))
     pause_streams = bool(pauses and stream_pauses)
     pool_stream_pauses = pool_streams and pause_streams and bool(getattr(batcher, "stream_pauses", False))
+    compress_streams = bool(compress and stream_compress)
+    pool_stream_compress = pool_streams and compress_streams and bool(getattr(batcher, "stream_compress", False))
     pool_refine = bool(batch_refine) and batcher is not None and bool(getattr(batcher, "refine", False))
     pool_split = bool(batch_split) and batcher is not None
     allowed = ALLOWED_PARAMS | ({"refine_text"} if pool_refine else set()) | ({"split_text"} if pool_split else set())
@@ -353,6 +360,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             kw = {**kw, "stream_limiter": True, "split_text": False, **({} if gdb is None else {"gain_db": gdb})}
         if req.stream and trim is not None:          # likewise for a paused stream
             kw = {**kw, "stream_pauses": True, "split_text": False}
+        if req.stream and comp is not None:          # likewise for a compressed stream
+            kw = {**kw, "stream_compress": True, "split_text": False}
         return chat.infer(text=[req.input], stream=bool(req.stream), lang=None, skip_refine_text=True, refine_text_only=False,
                           use_decoder=True, do_text_normalization=True, do_homophone_replacement=True,
                           params_infer_code=code_params(req.voice), pcm16=True, **kw)
@@ -433,7 +442,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 LN.check_rate(rate)
             except ValueError as e:
                 raise HTTPException(400, detail=str(e))
-            if req.stream:
+            if req.stream and not compress_streams:
                 raise HTTPException(400, detail="compress is served for non-streamed requests only: a compressed stream would need the "
                                                 "block state carried across chunks")
         lim = False                                  # the request's limiter flag where it is honoured
@@ -525,7 +534,7 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
         if req.stream and pool_streams and (spd is None or (pool_stream_speeds and (rate == SAMPLE_RATE or pool_stream_speed_rates))) \
                 and (not as_flac or pool_stream_flac) and (not lim or pool_stream_limiter) and (trim is None or pool_stream_pauses) \
-                and (not as_adpcm or pool_stream_adpcm):
+                and (not as_adpcm or pool_stream_adpcm) and (comp is None or pool_stream_compress):
             async def pooled_stream():       # the serial streamed branch's framing; the chunks come from the shared pool
                 skw = rkw if rate == SAMPLE_RATE else {**rkw, "sample_rate": rate}
                 if spd is not None:
@@ -534,6 +543,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     skw = {**skw, "limiter": True, **({} if gdb is None else {"gain_db": gdb})}
                 if trim is not None:
                     skw = {**skw, "pauses": trim}
+                if comp is not None:
+                    skw = {**skw, "compress": comp}
                 chunks = batcher.submit_stream(req.input, code_params(req.voice), **skw, **({"adpcm_blocks": True} if as_adpcm else ekw))
                 try:
                     first = True
@@ -558,7 +569,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                 async with app.state.model_lock:
                     try:
                         first = True
-                        gen = infer(req, rate, law, spd, as_flac, None, trim, lim, gdb, **akw) if trim is not None else \
+                        gen = infer(req, rate, law, spd, as_flac, None, trim, lim, gdb, **akw, comp=comp) if comp is not None else \
+                            infer(req, rate, law, spd, as_flac, None, trim, lim, gdb, **akw) if trim is not None else \
                             infer(req, rate, law, spd, as_flac, None, None, True, gdb, **akw) if lim else infer(req, rate, law, spd, True) if as_flac else \
                             infer(req, rate, None, spd, **akw) if as_adpcm else infer(req, rate, law, spd) if spd is not None else (infer(req, rate) if law is None else infer(req, rate, law))
                         async for chunk in iterate_in_threadpool(locked_chunks(gen) if batcher is not None else gen):
@@ -669,6 +681,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["stream_pauses"] = True
         if compress:
             out["compress"] = True
+        if compress_streams:
+            out["stream_compress"] = True
         return out
 
     return app

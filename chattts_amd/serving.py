@@ -677,7 +677,8 @@ class _Job:
     lm_slot: Optional[int] = None          # a limited stream: its stream of the limiter, opened at its first chunk
     pa_slot: Optional[int] = None          # a paused stream: its pause stream, opened at its first chunk
     lm_gain: Optional[float] = None        # ... and the float32 pre-gain of its `gain_db` (None: 1)
-    compress: object = None                # a checked compressor spec (non-streamed only); None: the dynamics are left alone
+    compress: object = None                # a checked compressor spec; None: the dynamics are left alone
+    cp_slot: Optional[int] = None          # a compressed stream: its compressor stream, opened at its first chunk
 
     @property
     def is_stream(self) -> bool:
@@ -800,7 +801,8 @@ class SpeechBatcher:
     def __init__(self, chat, slots: int, gpu_lock: threading.Lock, *, make_pool=None, cap: Optional[int] = None, hid_cap: int = 2048,
                  logger=None, ragged_decode: bool = False, streams: bool = False, refine: bool = False, make_text_pool=None,
                  text_cap: Optional[int] = None, refine_rng: str = "host", stream_speeds: bool = False, stream_speed_rates: bool = False,
-                 stream_flac: bool = False, stream_limiter: bool = False, stream_pauses: bool = False, stream_adpcm: bool = False):
+                 stream_flac: bool = False, stream_limiter: bool = False, stream_pauses: bool = False, stream_adpcm: bool = False,
+                 stream_compress: bool = False):
         import logging
         self.chat, self.lock, self.S = chat, gpu_lock, int(slots)
         self.ragged_decode = bool(ragged_decode)
@@ -822,6 +824,8 @@ class SpeechBatcher:
         self.stream_limited_chunks = 0     # chunks that came out of a limiter stream (empty ones included)
         self.stream_pauses = bool(stream_pauses)     # submit_stream(pauses=) is accepted
         self.stream_paused_chunks = 0      # chunks that came out of a pause stream (empty ones included)
+        self.stream_compress = bool(stream_compress)   # submit_stream(compress=) is accepted
+        self.stream_compressed_chunks = 0  # chunks that came out of a compressor stream (empty ones included)
         self.companded = 0                 # outputs handed out as G.711 (results and streamed chunks)
         self.flac_encoded = 0              # results handed out as FLAC files
         self.adpcm_encoded = 0             # results handed out as IMA ADPCM WAV files
@@ -952,7 +956,7 @@ class SpeechBatcher:
 
     def submit_stream(self, text: str, params, refine=None, split_text: bool = False, sample_rate=None, encoding=None,
                       speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False, gain_db=None,
-                      adpcm_blocks: bool = False) -> SpeechStream:
+                      adpcm_blocks: bool = False, compress=None) -> SpeechStream:
         """one streamed request: an iterator over the int16 chunks `Chat.infer([text], stream=True, skip_refine_text=True,
         params_infer_code=params, pcm16=True)` yields (each chunk flat, [n] instead of [1, n]).  Closing it cancels the request, in
         whichever pool it is.  `refine`: as in `submit`.  `split_text` is refused: the serial streamed schedule across split batches
@@ -985,7 +989,19 @@ class SpeechBatcher:
         stream_adpcm=True`; concatenated they are `adpcm.encode_blocks` of the int16 chunks of the same request without it, and behind
         `adpcm.stream_header(rate)` an open-ended WAV file.  The request gets an ADPCM stream (opened at its first chunk, given back
         where its other streams are); the chunks of all ADPCM streams due at one poll share ONE encoder step behind the one decoder
-        pass (CodecEngine.decode_windows(adpcm=))."""
+        pass (CodecEngine.decode_windows(adpcm=)).  `compress` (None / False: off; True or a dict of compressor.RANGES' fields; one spec
+        per request) is refused, with the TypeError of the time before the option: the block state would have to be carried across chunks -- unless the batcher was built with
+        `stream_compress=True`: then the request gets a compressor stream (opened at its first chunk, given back where its other
+        streams are) and its chunks are those of the serial call with `compress=, stream_compress=True`: converted, companded or
+        encoded from compressed samples, the attack and at most two milliseconds behind.  The compressor streams due at one poll
+        share one step per round behind their decoder pass and their pause streams, in front of their limiter streams
+        (CodecEngine.decode_windows(compress=))."""
+        if compress is not None and compress is not False and not self.stream_compress:     # as before the option existed: not an argument of this call
+            raise TypeError("submit_stream() got an unexpected keyword argument 'compress': it applies to non-streamed requests only "
+                            "(a stream would need the block state carried across chunks) unless the batcher is built with stream_compress=True")
+        compress = CP.check(compress, "submit_stream")
+        if compress is not None:
+            LN.check_rate(24000 if sample_rate is None else sample_rate)
         if adpcm_blocks:
             if not self.stream_adpcm:
                 raise ValueError("adpcm_blocks needs a batcher built with stream_adpcm=True (an ADPCM file is served for non-streamed "
@@ -1039,7 +1055,7 @@ class SpeechBatcher:
         h = SpeechStream(self, next(self._ids))
         self._in.put(_Job(h.rid, text, params, h, refine, None, rate, encoding, speed=speed, flac=bool(flac),
                           **({"limiter": True, "lm_gain": g32} if limiter else {}), **({} if pauses is None else {"pauses": pauses}),
-                          **({"adpcm": True} if adpcm_blocks else {})))
+                          **({"adpcm": True} if adpcm_blocks else {}), **({} if compress is None else {"compress": compress})))
         return h
 
     def _check_refine(self, refine) -> None:
@@ -1072,6 +1088,8 @@ class SpeechBatcher:
                 occ["stream_limited_chunks"] = self.stream_limited_chunks
             if self.stream_pauses:
                 occ["stream_paused_chunks"] = self.stream_paused_chunks
+            if self.stream_compress:
+                occ["stream_compressed_chunks"] = self.stream_compressed_chunks
         if self.refine:
             occ["refine"] = {"active": len(getattr(tp, "active", {})), "queued": len(getattr(tp, "queue", ())),
                              "admissions": self.refine_admissions, "max_coresident": self.refine_max_coresident,
@@ -1111,6 +1129,9 @@ class SpeechBatcher:
         if job.pa_slot is not None:        # ... and its pause stream
             slot, job.pa_slot = job.pa_slot, None
             self.chat.codec.trim_pauses_stream_close(slot)
+        if job.cp_slot is not None:        # ... and its compressor stream
+            slot, job.cp_slot = job.cp_slot, None
+            self.chat.codec.compress_stream_close(slot)
         failed = isinstance(result, BaseException)
         if cancelled:
             self.cancelled += job.is_stream
@@ -1385,6 +1406,12 @@ class SpeechBatcher:
                     if j.pauses is not None and j.pa_slot is None:
                         j.pa_slot = self.chat.codec.trim_pauses_stream_open(24000 if j.sample_rate is None else j.sample_rate, j.pauses)
                 kw["pa_streams"] = [j.pa_slot for j in jobs]
+            if "compress" in kw:          # the compressor streams due at this poll: one step per round behind the pauses', in front of the limiter's
+                self.stream_compressed_chunks += sum(j.compress is not None for j in jobs)
+                for j in jobs:
+                    if j.compress is not None and j.cp_slot is None:
+                        j.cp_slot = self.chat.codec.compress_stream_open(24000 if j.sample_rate is None else j.sample_rate, j.compress)
+                kw["cp_streams"] = [j.cp_slot for j in jobs]
             pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **kw)
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for job in dict.fromkeys(jobs):

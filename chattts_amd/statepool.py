@@ -33,6 +33,15 @@ class LimiterRec(NamedTuple):
     done: bool
 
 
+class CompressRec(NamedTuple):
+    rate: int
+    spec: Any             # a checked compressor spec (compressor.check)
+    pushed: int
+    emitted: int
+    phase: int
+    done: bool
+
+
 class PauseRec(NamedTuple):
     rate: int
     spec: Any             # pauses.PauseSpec

@@ -530,6 +530,49 @@ typedef struct {
 int ctts_peak_limit_stream_step(const float* x, int64_t n_x, const ctts_lm_stream* st_dev, const ctts_lm_stream* st_host, int32_t n_streams,
                                 float* y, int64_t n_y, float* carry, void* stats, int32_t n_slots, void* stream);
 
+/* The compressor of STREAMS (chattts_amd/compressor.py: stream_plan): the segment arrives in pushes.  B = rate / 1000; after a push,
+ * `end` = pos + n_in samples are in and end / B blocks are complete.  A step that is not the stream's last emits samples [e_lo, E'),
+ * e_lo = max(0, pos / B - A - 1) B and E' = max(0, end / B - A - 1) B: a stream lags by (A + 1) B samples and the open block, whatever the
+ * hold; the last step (total == end; 0: the stream ends empty) emits up to the end, and only then the segment's edge rules apply.  The
+ * chunks of a stream, end to end, are ctts_compress_ragged of the whole signal bit for bit, however it was cut.  y is a buffer of its own
+ * and does not overlap x.  A slot carries, in two halves each (a step reads half `phase` and writes the other: the caller flips `phase`
+ * after every accepted step of a slot):
+ *   carry: [n_slots][2][CTTS_CP_SCARRY] float32, the raw samples [e_lo, pos): c_in = pos - e_lo, fewer than (A + 2) B;
+ *   hold:  [n_slots][2][CTTS_CP_SHIST] float32, the table entries c of the blocks [max(0, e_lo / B - A - H - 1), pos / B): h_in of them, at
+ *          most 2 A + H + 2 -- the hold's memory is one float per millisecond, no raw sample older than e_lo is kept.
+ * stats: [n_slots] ctts_cp_stats on the device.  A slot's record lives across steps and is touched by order-free atomics only (n_blocks
+ * and peak once per block, when its c is computed; min_gain and n_touched over the emitted samples): the CALLER sets it to {1, 0, 0, 0}
+ * when it opens the stream, in stream order in front of the first step.  After the last push it is the one-shot record.
+ * Each descriptor names its gain table among the n_tab given (device and host; the two must agree).  The c of the blocks a push completes
+ * go through `scratch`, from float cb_off: the descriptors' counts of new blocks, end to end; ctts_compress_stream_scratch_bytes(the
+ * sum) says how much.  Two launches over up to 1024 descriptors of any rates and specs (one where no push completes a block).  A step
+ * with n_in == 0 or n_out == 0 still moves the carry.  Refused before anything is launched, from the host mirror: a null pointer,
+ * n_streams outside 1 .. 1024, a pool without a slot, misaligned buffers (x, the tables and the scratch 16 bytes), y overlapping x, a
+ * negative length, position or offset, 2^31 samples, a push outside x, a chunk outside y, a rate that is no multiple of 10 Hz in
+ * 8000 .. 48000, A outside 1 .. 20, H outside 0 .. 500, a table index outside the n_tab given, n_tab outside 1 .. n_streams, a table entry
+ * outside 2^-18 .. 1, a total that is neither -1 nor pos + n_in, e_lo, n_out, c_in, c_out, h_in, h_out or cb_off other than the above (c_out
+ * and h_out are 0 on the last push), a phase other than 0 / 1, a slot outside the pool or named twice, a scratch that is too small. */
+#define CTTS_CP_SCARRY 1056
+#define CTTS_CP_SHIST 544
+typedef struct {
+  int64_t in_off, n_in;   /* the new samples: x[in_off, in_off + n_in) */
+  int64_t pos;            /* samples pushed before them */
+  int64_t total;          /* the stream's length when this push is its last, else -1 */
+  int64_t e_lo, n_out;    /* the step emits samples [e_lo, e_lo + n_out) of the compressed stream */
+  int64_t out_off;        /* .. to y[out_off ..] */
+  int64_t cb_off;         /* the c of the blocks this push completes go to the scratch from this float */
+  int32_t slot, phase;    /* the state slot; which half of its carry and hold the step reads */
+  int32_t rate;           /* Hz */
+  int32_t A, H;           /* attack and hold, in blocks */
+  int32_t tab;            /* its gain table */
+  int32_t c_in, c_out;    /* raw samples kept in front of and behind the step */
+  int32_t h_in, h_out;    /* block gains kept in front of and behind the step */
+} ctts_cp_stream;         /* 104 bytes (compressor stream) */
+size_t ctts_compress_stream_scratch_bytes(int64_t n_blocks);
+int ctts_compress_stream_step(const float* x, int64_t n_x, const ctts_cp_stream* st_dev, const ctts_cp_stream* st_host, int32_t n_streams,
+                              const float* tab_dev, const float* tab_host, int32_t n_tab, float* y, int64_t n_y, float* carry, float* hold,
+                              void* stats, int32_t n_slots, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Pause control: packed float32 segments in[off[s], off[s+1]) lose edge silence and long inner pauses, frame by frame (the definition,
  * once, is chattts_amd/pauses.py).  Segment s has the row rows[8 s ..]: F (samples per 10 ms frame, 80 .. 480), pad, lead, tail, P (frames;
  * P = 0: the segment is copied through), thr (float32 bits, a frame is active when some sample has !(|x| < thr)), the offset of its

@@ -1,7 +1,7 @@
 """What the dynamic range compressor costs (csrc/compressor.hip, ctts_compress_ragged, behind CodecEngine.compress), next to the nearest
 existing stage, the look-ahead peak limiter, on the same packs in the same run.  Needs a GPU; writes profiles/compressor_probe.md.
 
-    python tools/compressor_probe.py [--reps 20] [--rounds 5] [--out profiles/compressor_probe.md]
+    python tools/compressor_probe.py [--reps 20] [--rounds 5] [--out profiles/compressor_probe.md] [--stream]
 
   packs         64 rows of 10 s at 24 kHz (15.4 M samples) and at 8 kHz (5.1 M): noise under an envelope that changes every 50 ms between
                 -50, -26 and -10 dBFS, so about two thirds of the blocks lie over the default knee -- the compressor's slow path on most
@@ -14,7 +14,12 @@ existing stage, the look-ahead peak limiter, on the same packs in the same run. 
   per launch    the apply launch is not callable alone, so the split comes from two variant calls: with a table of ones, in place, the
                 peak launch does all its work and every apply workgroup leaves at once (no block under 1, nothing to copy): that is
                 the peak launch plus the floor; with every segment copied through in place (table index -1) both launches leave at
-                once: the floor of a memset and two launches.  apply = full - peak."""
+                once: the floor of a memset and two launches.  apply = full - peak.
+  --stream      instead: ONE step of 64 compressor streams with pushes of 100 ms at 24 kHz (ctts_compress_stream_step, mid-stream: five
+                pushes have gone before, so the raw carry and the history of the hold are live), next to the one-shot call over the same
+                64 x 100 ms as 64 segments -- the yardstick: the step does the same work and also reads its second sources and writes
+                the next carry and history.  The same descriptors are launched again and again (a step reads one half of a slot and
+                writes the other, so a repeated step is the same step); the section replaces the file's `## stream` section."""
 from __future__ import annotations
 
 import argparse
@@ -104,16 +109,90 @@ def _measure(codec, fs: int, reps: int, rounds: int) -> dict:
                 blocks_under=int(rec["n_blocks"].sum()), blocks=nb, touched=int(rec["n_touched"].sum()))
 
 
+def _measure_stream(codec, reps: int, rounds: int, fs: int = 24000, ms: int = 100, before: int = 5) -> dict:
+    dev, lib = codec.device, codec.lib
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    push, per = ms * fs // 1000, (before + 1) * ms * fs // 1000
+    r = np.random.default_rng(5)
+    env = np.repeat(r.choice([0.003, 0.05, 0.3], size=N_SEG * per // (fs // 20)), fs // 20)
+    x_h = (r.uniform(-1, 1, N_SEG * per) * env).astype(np.float32)
+    x = up(x_h)
+    hs = [codec.compress_stream_open(fs, True) for _ in range(N_SEG)]
+    try:
+        for k in range(before):
+            codec.compress_stream_step(x, [(h, i * per + k * push, push, False) for i, h in enumerate(hs)])
+        tab, tabs_h, _, n_new = codec._cp_descriptors([(h, i * per + before * push, push, False) for i, h in enumerate(hs)])
+        o = np.zeros(N_SEG + 1, np.int64)
+        np.cumsum(tab["n_out"], out=o[1:])
+        tab["out_off"] = o[:-1]
+        pool = codec._pool("compress")
+        both = up(np.concatenate([tabs_h.view(np.uint8).reshape(-1), tab.view(np.uint8)]))
+        sb = int(lib.ctts_compress_stream_scratch_bytes(n_new))
+        work = torch.empty(sb, dtype=torch.uint8, device=dev)
+        y = torch.empty(int(o[-1]), dtype=torch.float32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+
+        def step():
+            rc = lib.ctts_compress_stream_step(x.data_ptr(), x.numel(), both.data_ptr() + tabs_h.nbytes, vp(tab), N_SEG, both.data_ptr(), vp(tabs_h),
+                                               int(tabs_h.shape[0]), y.data_ptr(), y.numel(), pool.buf["carry"].data_ptr(), pool.buf["hist"].data_ptr(),
+                                               pool.buf["stats"].data_ptr(), pool.slots, work.data_ptr(), sb, st)
+            assert rc == 0, lib.ctts_last_error()
+        t_step = _time(step, reps, rounds)
+        # the yardstick: the same 64 x 100 ms as 64 segments of one one-shot call
+        seg = np.concatenate([x_h[i * per + before * push: i * per + (before + 1) * push] for i in range(N_SEG)])
+        off, rt, par, tabs, _ = CP.tables(len(seg), True, np.arange(N_SEG + 1, dtype=np.int64) * push, fs)
+        xs, ys = up(seg), torch.empty(len(seg), dtype=torch.float32, device=dev)
+        off_d, rt_d, par_d, tabs_d = up(off), up(rt), up(par), up(tabs)
+        sb1 = int(lib.ctts_compress_ragged_scratch_bytes(vp(off), N_SEG))
+        stats, scratch = torch.empty(16 * N_SEG, dtype=torch.uint8, device=dev), torch.empty(sb1, dtype=torch.uint8, device=dev)
+
+        def one():
+            rc = lib.ctts_compress_ragged(xs.data_ptr(), ys.data_ptr(), off_d.data_ptr(), vp(off), N_SEG, rt_d.data_ptr(), vp(rt), par_d.data_ptr(), vp(par),
+                                          tabs_d.data_ptr(), vp(tabs), int(tabs.shape[0]), stats.data_ptr(), scratch.data_ptr(), sb1, st)
+            assert rc == 0, lib.ctts_last_error()
+        t_one = _time(one, reps, rounds)
+        t_engine = _time(lambda: codec.compress_stream_step(x, [(h, i * per + before * push, 0, False) for i, h in enumerate(hs)]), reps, rounds)
+        return dict(fs=fs, ms=ms, push=push, ms_step=t_step, ms_one=t_one, ms_idle_engine=t_engine, carry=int(tab["c_in"].max()), hist=int(tab["h_in"].max()),
+                    emitted=int(o[-1]))
+    finally:
+        for h in hs:
+            codec.compress_stream_close(h)
+
+
+def _stream_section(codec, a) -> str:
+    r = _measure_stream(codec, a.reps, a.rounds)
+    return "\n".join([
+        "## stream", "",
+        f"{torch.cuda.get_device_name(0)}; ONE step of {N_SEG} streams, pushes of {r['ms']} ms at {r['fs']} Hz ({r['push']} samples each, {r['emitted']} emitted), "
+        f"mid-stream: each slot carries {r['carry']} raw samples and {r['hist']} block gains in; the C entry points on preallocated buffers; device events "
+        f"around {a.reps} calls, median of {a.rounds} rounds.", "",
+        "| what | launches | ms per call |", "|---|---|---|",
+        f"| `ctts_compress_stream_step`, {N_SEG} streams x {r['ms']} ms | 2 kernels | {r['ms_step']:.4f} |",
+        f"| `ctts_compress_ragged`, the same {N_SEG} x {r['ms']} ms as {N_SEG} segments (the yardstick) | a memset node and 2 kernels | {r['ms_one']:.4f} |",
+        f"| `CodecEngine.compress_stream_step`, {N_SEG} empty pushes (planning, one upload, the scratch, 1 kernel) | 1 kernel | {r['ms_idle_engine']:.4f} |",
+        "", f"step / one-shot = {r['ms_step'] / r['ms_one']:.2f}", ""])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "compressor_probe.md"))
+    ap.add_argument("--stream", action="store_true", help="measure one step of 64 streams instead, and replace the file's `## stream` section")
     a = ap.parse_args()
     from chattts_amd.engine import CodecEngine
     dev = torch.device("cuda:0")
     w = synthetic_all()
     codec = CodecEngine(w["decoder"], w["vocos"], dev)
+    if a.stream:
+        text = _stream_section(codec, a)
+        old = open(a.out).read() if os.path.exists(a.out) else "# compressor probe\n"
+        head = old.split("\n## stream\n")[0].rstrip("\n")
+        with open(a.out, "w") as f:
+            f.write(head + "\n\n" + text)
+        print(text)
+        return
     rows = [_measure(codec, fs, a.reps, a.rounds) for fs in (24000, 8000)]
     lines = ["# compressor probe", "",
              f"{torch.cuda.get_device_name(0)}; {N_SEG} rows of {SECONDS} s, x into y, the C entry points on preallocated buffers; device events around "
