@@ -203,6 +203,8 @@ SIGNATURES = {
     "ctts_peak_limit_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, P, SZ, P]),
     "ctts_compress_ragged_scratch_bytes": (SZ, [P, I32]),
     "ctts_compress_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, P, P, I32, P, P, SZ, P]),
+    "ctts_equalize_ragged_scratch_bytes": (SZ, [P, I32]),
+    "ctts_equalize_ragged": (C.c_int, [P, P, P, P, I32, P, P, P, P, I32, P, SZ, P]),
     "ctts_compress_stream_scratch_bytes": (SZ, [C.c_int64]),
     "ctts_compress_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, P, I32, P, C.c_int64, P, P, P, I32, P, SZ, P]),
     "ctts_peak_limit_stream_step": (C.c_int, [P, C.c_int64, P, P, I32, P, C.c_int64, P, P, I32, P]),

@@ -17,7 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libchattts_amd.so")
-SOURCES = ["gemm.hip", "decode.hip", "decode32.hip", "decode32x.hip", "prefill.hip", "prefill32.hip", "prefill32x.hip", "gpt.hip", "codec.hip", "resample.hip", "timescale.hip", "loudness.hip", "limiter.hip", "compressor.hip", "pauses.hip", "g711.hip", "flac.hip", "adpcm.hip", "codec_gemm.hip", "dvae.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "decode.hip", "decode32.hip", "decode32x.hip", "prefill.hip", "prefill32.hip", "prefill32x.hip", "gpt.hip", "codec.hip", "resample.hip", "timescale.hip", "loudness.hip", "limiter.hip", "compressor.hip", "equalizer.hip", "pauses.hip", "g711.hip", "flac.hip", "adpcm.hip", "codec_gemm.hip", "dvae.hip", "capi.hip"]
 # -amdgpu-kernarg-preload-count: the dispatcher places a kernel's leading plain (pointer / integer) parameters in user SGPRs, so the
 # step kernels address their first loads without a scalar fetch of the argument segment (a by-value struct is never
 # preloaded, which is why those kernels take what their first loads need as leading parameters IN FRONT of their struct)

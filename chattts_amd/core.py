@@ -24,6 +24,7 @@ import torch
 
 from . import adpcm as ADPCM
 from . import compressor as CP
+from . import equalizer as EQ
 from . import flac as FLAC
 from . import g711 as G711
 from . import limiter as LM
@@ -285,7 +286,8 @@ class Chat:
             24, params.manual_seed, self.context, **kw))
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], use_decoder: bool = True, pad_to: Optional[int] = None, *,
-                       ragged: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None, limiter=None, compress=None):
+                       ragged: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None, limiter=None, compress=None,
+                       eq=None):
         """`Chat._decode_to_wavs` (core.py:513-539) -> np.float32 [B, n]: per-row hidden states [T_b,768] through the
         decoder, or (use_decoder=False) per-row token ids [T_b,4] through the full DVAE's codebook; then Vocos.
         `pad_to`: decode as rows of a batch whose longest row has that many tokens (dist.infer_sharded).
@@ -307,8 +309,11 @@ class Chat:
         gain.
         `compress` (None / False: off; True or a dict of compressor.RANGES' fields, also a list with one per row, None entries copied
         through): every row goes through the look-ahead compressor on the device (CodecEngine.compress; the definition of
-        compressor.py), behind `pauses` and in front of the loudness stage."""
-        plan = Plan.given("decode_to_wavs", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged, compress=compress)
+        compressor.py), behind `pauses` and in front of the loudness stage.
+        `eq` (None / False: off; an equaliser preset name or a dict of equalizer.FIELDS, also a list with one per row, None entries
+        copied through): every row goes through the biquad cascade on the device (CodecEngine.equalize; the definition of
+        equalizer.py) from zero state, behind `pauses` and in front of `compress`."""
+        plan = Plan.given("decode_to_wavs", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged, compress=compress, eq=eq)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
@@ -338,7 +343,7 @@ class Chat:
 
     def decode_to_pcm16(self, result_list: List[torch.Tensor], use_decoder: bool = True, strip: bool = True,
                         product: str = "f64", *, ragged: bool = False, sample_rate=None, encoding=None, speed=None,
-                        flac=None, loudness=None, pauses=None, limiter=None, adpcm=None, compress=None) -> List[np.ndarray]:
+                        flac=None, loudness=None, pauses=None, limiter=None, adpcm=None, compress=None, eq=None) -> List[np.ndarray]:
         """`_decode_to_wavs` followed by what the reference's callers do with every waveform -- the sample-level silence strip of
         core.py:262-265 and `float_to_int16` (tools/audio/np.py:7-11; examples/web/funcs.py:209, tools/audio/pcm.py:29), one peak per
         utterance -- with the conversion ON THE DEVICE: the batch crosses PCIe as int16 + one mask bit per sample instead of float32.
@@ -370,8 +375,11 @@ class Chat:
         with an `encoding` on the same row.
         `compress` (None / False: off; True or a dict of compressor.RANGES' fields, also a list with one per row, None entries copied
         through): `wav` above is the waveform behind the look-ahead compressor (CodecEngine.compress), every row alone -- behind
-        `pauses`, in front of the loudness stage and everything behind it."""
-        plan = Plan.given("decode_to_pcm16", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged, compress=compress)
+        `pauses`, in front of the loudness stage and everything behind it.
+        `eq` (None / False: off; an equaliser preset name or a dict of equalizer.FIELDS, also a list with one per row, None entries
+        copied through): `wav` above is the waveform behind the equaliser (CodecEngine.equalize), every row alone from zero state --
+        behind `pauses`, in front of `compress`, the loudness stage and everything behind it."""
+        plan = Plan.given("decode_to_pcm16", sample_rate, speed, loudness, pauses, limiter, one_rate=not ragged, compress=compress, eq=eq)
         if ragged and not use_decoder:
             raise NotImplementedError("ragged decoding covers the hidden-state decoder only (use_decoder=True)")
         assert self.has_loaded(use_decoder)
@@ -542,7 +550,8 @@ class Chat:
         return [p[np.unpackbits(keep_h[keep_off[i]: keep_off[i + 1]])[: p.size].astype(bool)] for i, p in enumerate(pieces)]
 
     def decode_split_to_pcm16(self, groups, strip: bool = True, product: str = "f64", sample_rate=None, encoding=None,
-                              speed=None, flac=None, loudness=None, pauses=None, limiter=None, adpcm=None, compress=None) -> List[np.ndarray]:
+                              speed=None, flac=None, loudness=None, pauses=None, limiter=None, adpcm=None, compress=None,
+                              eq=None) -> List[np.ndarray]:
         """The end of `Chat.infer(..., split_text=True, pcm16=True)` for MANY requests at once: `groups[g]` = request g's per-sentence
         hidden states ([T, 768] each, in sentence order).  ONE ragged decode over all sentences of all requests (each as if alone), ONE
         grouped conversion (CodecEngine.float_to_int16_groups: one peak per request, silent samples dropped, the rest compacted on the
@@ -572,7 +581,10 @@ class Chat:
         not together with `flac`, nor with an `encoding` on the same request.
         `compress` (None / False: off; a compressor spec, or a list with one per request, None entries copied through): every
         SENTENCE is compressed alone (CodecEngine.compress) behind `pauses`: no window spans a join; the request's one gain is then
-        computed over its compressed sentences."""
+        computed over its compressed sentences.
+        `eq` (None / False: off; an equaliser spec, or a list with one per request, None entries copied through): every SENTENCE is
+        filtered alone from zero state (CodecEngine.equalize) behind `pauses` and in front of `compress`: no filter state crosses a
+        join."""
         assert self.has_loaded()
         groups = [list(g) for g in groups]
         if len(groups) == 0:
@@ -584,14 +596,14 @@ class Chat:
         codec = self.codec
         encs, flags = self._formats(encoding, flac, len(groups), per_row=True, who="decode_split_to_pcm16", unit="request")
         aflags = self._adpcm_flags(adpcm, len(groups), encoding, flags, True, "decode_split_to_pcm16")
-        plan = Plan.given("decode_split_to_pcm16", sample_rate, speed, loudness, pauses, limiter, compress=compress)
+        plan = Plan.given("decode_split_to_pcm16", sample_rate, speed, loudness, pauses, limiter, compress=compress, eq=eq)
         rates = plan.row_rates(len(groups))
         if aflags is not None:
             for r in rates:
                 ADPCM.check_rate(r)
         plan = plan.per_sentence(groups)
         rows = [h for g in groups for h in g]
-        wav, off = codec.decode_ragged(rows, sample_rate=plan.sample_rate, **plan.kwargs("speed", "pauses", "compress"))
+        wav, off = codec.decode_ragged(rows, sample_rate=plan.sample_rate, **plan.kwargs("speed", "pauses", "compress", "eq"))
         if plan.levels:                                               # ONE gain per request: the stage runs here, over the group table
             wav = codec.loudness_normalize(wav, plan.loudness, offsets=off, groups=grp, out=wav, rates=plan.row_rates(len(rows)),
                                            **plan.kwargs("limiter"))
@@ -967,7 +979,7 @@ class Chat:
               encoding: Optional[str] = None, speed: float = 1.0, stream_time_scale: bool = False, stream_scaled_resample: bool = False,
               flac: bool = False, loudness=None, stream_flac: bool = False, pauses=None, limiter=None,
               stream_limiter: bool = False, gain_db=None, stream_pauses: bool = False, adpcm: bool = False, stream_adpcm: bool = False,
-              compress=None, stream_compress: bool = False):
+              compress=None, stream_compress: bool = False, eq=None):
         """core.py:208-270: `List[np.ndarray]` (one stripped waveform per text, or ONE concatenated waveform when
         `split_text`), a generator of `np.ndarray [B, n]` chunks when `stream`, the refined text when `refine_text_only`.
         `pcm16=True` (keyword-only, not in the reference): the same results as 16-bit PCM -- what the reference's callers get from
@@ -1088,7 +1100,25 @@ class Chat:
         companding and the streamed file formats, the non-streamed order.  A row's chunks, end to end, are its uncompressed stream's
         samples compressed as one signal, bit for bit; the stream lags by the attack and at most two more milliseconds, and the last
         chunk brings the rest.  As with `stream_pauses` a chunk is a list with one array per row.  Not with `split_text`, nor with
-        `use_decoder=False`."""
+        `use_decoder=False`.
+        `eq` (keyword-only, non-streamed only; None / False: off): an equaliser preset name ("telephone": a 300 Hz high-pass; "rumble":
+        an 80 Hz high-pass) or a dict with any of highpass_hz, lowshelf {hz, db}, highshelf {hz, db}, peaks [{hz, db, q}, ...], at most
+        four second-order sections (chattts_amd/equalizer.py) -- one, or a list with one per text.  Every utterance goes through the
+        biquad cascade on the device (CodecEngine.equalize), in float64 from zero state: stage 3 1/4 of the output chain, behind the
+        time scaler, the resampler and `pauses` -- the pause detector sees the signal it was tuned on -- and in front of `compress`, the
+        loudness stage and the limiter, which see what the listener will hear, the silence strip, the 16-bit conversion, the
+        companding and the file formats.  Frequencies lie in 20 Hz .. 0.45 of the returned rate.  Every sentence of a split request
+        is filtered alone from zero state (one spec only).  A streamed call with it raises: an equalised stream would need the
+        filter state carried across chunks."""
+        ekw = Plan.given("infer", eq=eq).kwargs()
+        if ekw and stream:
+            raise ValueError("eq applies to non-streamed inference only (an equalised stream would need the filter state carried across "
+                             "chunks)")
+        if ekw and split_text and isinstance(eq, list):
+            raise ValueError("a split_text request is one waveform: it takes one equaliser spec")
+        if ekw:
+            for e in eq if isinstance(eq, list) else [eq]:
+                EQ.check(e, "infer", LN.check_rate(CodecEngine.SAMPLE_RATE if sample_rate is None else int(sample_rate)))
         mkw = Plan.given("infer", limiter=limiter).kwargs()
         if gain_db is not None and np.ndim(gain_db) != 0:
             raise ValueError("gain_db is one make-up gain for the whole batch")
@@ -1232,7 +1262,7 @@ class Chat:
                               do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code,
                               pcm16=pcm16 and not refine_text_only and not (split_text and not stream), ragged=ragged_decode, raw=split_dev,
                               sample_rate=rate, **({} if encoding is None else {"encoding": encoding}), **skw, **({"flac": True} if flac else {}),
-                              **({} if split_host else lkw), **pkw, **smkw, **spkw, **akw, **ckw, **sckw)
+                              **({} if split_host else lkw), **pkw, **smkw, **spkw, **akw, **ckw, **sckw, **ekw)
         if stream:
             return res_gen
         if refine_text_only:
@@ -1242,7 +1272,7 @@ class Chat:
             if rows:
                 return self.decode_split_to_pcm16([rows], **({} if rate is None else {"sample_rate": rate}),
                                                   **({} if encoding is None else {"encoding": encoding}), **skw,
-                                                  **({"flac": True} if flac else {}), **lkw, **pkw, **akw, **ckw)
+                                                  **({"flac": True} if flac else {}), **lkw, **pkw, **akw, **ckw, **ekw)
             res_gen = iter(())      # no batch produced anything: what the host lines below make of that
         if pcm16 and not split_text:
             return [w for wavs in res_gen for w in wavs]          # already stripped and converted, utterance by utterance, on the device
@@ -1274,7 +1304,7 @@ class Chat:
                do_homophone_replacement, split_text, max_split_batch, params_refine_text, params_infer_code, pcm16: bool = False,
                ragged: bool = False, raw: bool = False, sample_rate: Optional[int] = None, encoding: Optional[str] = None,
                speed: Optional[float] = None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None, pa_spec=None,
-               adpcm: bool = False, compress=None, cp_spec=None):
+               adpcm: bool = False, compress=None, cp_spec=None, eq=None):
         """core.py:395-503 (generator).  `cp_spec` with `stream`: the rows' compressor streams and their spec (Chat.infer's `stream_compress`).  `pa_spec` with `stream`: the rows' pause streams and their spec (Chat.infer's `stream_pauses`).  `lm_gain` with `stream`: the rows' limiter streams and their pre-gain (Chat.infer's `stream_limiter`).  `flac` with `stream`: the rows' FLAC streams (Chat.infer's `stream_flac`).  `raw` (non-streamed, decoder path): a batch's hidden-state rows are yielded undecoded."""
         assert self.has_loaded(use_decoder=use_decoder)
         if not isinstance(text, list):
@@ -1308,7 +1338,7 @@ class Chat:
                                            **({} if limiter is None else {"limiter": limiter}),
                                            **({} if lm is None else {"lm": lm, "lm_gain": lm_gain}),
                                            **({} if pa is None else {"pa": pa, "pa_spec": pa_spec}), **({"adpcm": True} if adpcm else {}),
-                                           **({} if compress is None else {"compress": compress}),
+                                           **({} if compress is None else {"compress": compress}), **({} if eq is None else {"eq": eq}),
                                            **({} if cp is None else {"cp": cp, "cp_spec": cp_spec}))
         finally:
             for h in cp or ():
@@ -1327,7 +1357,7 @@ class Chat:
 
     def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
                        rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None, pa=None, pa_spec=None,
-                       adpcm: bool = False, compress=None, cp=None, cp_spec=None):
+                       adpcm: bool = False, compress=None, cp=None, cp_spec=None, eq=None):
         """the batch loop of `_infer`"""
         # the rows' encoder streams `fs` are FLAC streams, or with `adpcm` IMA ADPCM streams: the same placement, the same host twin
         Twin = ADPCM.StreamEncoder if adpcm else FLAC.StreamEncoder
@@ -1412,6 +1442,8 @@ class Chat:
                         rkw["pauses"] = pauses[lo: lo + step] if isinstance(pauses, list) else pauses
                     if compress is not None and not raw:
                         rkw["compress"] = compress[lo: lo + step] if isinstance(compress, list) else compress
+                    if eq is not None and not raw:
+                        rkw["eq"] = eq[lo: lo + step] if isinstance(eq, list) else eq
                     if raw:         # Chat.infer decodes the whole split request at once (decode_split_to_pcm16)
                         rows = [h.clone() for h in src]
                         result.destroy()

@@ -2214,6 +2214,54 @@ extern "C" int ctts_compress_ragged(const float* x, float* y, const int64_t* off
                             (hipStream_t)stream));
   return 0;
 }
+// ---- the output equaliser: every table is checked on its host mirror before the first launch -------------------------------------------
+static_assert(CTTS_EQ_ROW == EQ_ROW && CTTS_EQ_TILE == EQ_TILE, "the equaliser's table row and tile");
+extern "C" size_t ctts_equalize_ragged_scratch_bytes(const int64_t* off_host, int32_t n_seg) {
+  if (loudness_offsets_check("ctts_equalize_ragged_scratch_bytes", off_host, n_seg)) return 0;
+  return (size_t)equalize_records(off_host[n_seg], n_seg) * EQ_D * sizeof(double);
+}
+extern "C" int ctts_equalize_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg,
+                                    const int32_t* sel_dev, const int32_t* sel_host, const double* coef_dev, const double* coef_host,
+                                    int32_t n_rows, void* scratch, size_t scratch_bytes, void* stream) {
+  const char* who = "ctts_equalize_ragged";
+  if (!x || !y || !off_dev || !sel_dev || !sel_host || !coef_dev || !coef_host)
+    return fail("%s: a null pointer (x, y and the offset, row index and coefficient tables on the device and the host are needed)", who);
+  if (loudness_offsets_check(who, off_host, n_seg)) return -1;
+  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)coef_dev & 15))
+    return fail("%s: x, y and the coefficient table must be 16-byte aligned", who);
+  if (x != y && x < y + off_host[n_seg] && y < x + off_host[n_seg]) return fail("%s: y must be x itself or not overlap it", who);
+  if (n_rows < 1 || n_rows > n_seg) return fail("%s: need 1 <= n_rows <= n_seg coefficient rows (got %d for %d segments)", who, n_rows, n_seg);
+  for (int r = 0; r < n_rows; ++r) {
+    const double* R = coef_host + (size_t)r * EQ_ROW;
+    if (!(R[0] >= 1.0 && R[0] <= (double)EQ_NSEC) || R[0] != (double)(int)R[0])
+      return fail("%s: row %d: a cascade has 1 .. %d second-order sections (got %g)", who, r, EQ_NSEC, R[0]);
+    if (!(R[1] >= 8000.0 && R[1] <= 48000.0) || R[1] != (double)(int)R[1] || (int)R[1] % 10 != 0)
+      return fail("%s: row %d: the rate is a multiple of 10 Hz in 8000 .. 48000 (got %g)", who, r, R[1]);
+    if (R[2] != (double)EQ_CHUNK) return fail("%s: row %d: the chunk is %d samples (got %g)", who, r, EQ_CHUNK, R[2]);
+    const int ns = (int)R[0];
+    for (int i = 0; i < ns; ++i) {
+      const double* k = R + 4 + 5 * i;
+      for (int q = 0; q < 5; ++q)
+        if (!std::isfinite(k[q])) return fail("%s: row %d: section %d has a coefficient that is not finite", who, r, i);
+      if (!(std::fabs(k[4]) < 1.0 && std::fabs(k[3]) < 1.0 + k[4]))
+        return fail("%s: row %d: section %d is not stable (a1 = %g, a2 = %g)", who, r, i, k[3], k[4]);
+    }
+    for (int q = 32; q < 32 + 12 * EQ_D * EQ_D; ++q)
+      if (!std::isfinite(R[q])) return fail("%s: row %d: a power of the state matrix is not finite", who, r);
+  }
+  long long tiles_max = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    if (sel_host[i] < -1 || sel_host[i] >= n_rows)
+      return fail("%s: segment %d: coefficient row %d is outside the %d given (-1: the segment is copied through)", who, i, sel_host[i], n_rows);
+    tiles_max = std::max(tiles_max, (long long)(off_host[i + 1] - off_host[i] + EQ_TILE - 1) / EQ_TILE);
+  }
+  const size_t need = (size_t)equalize_records(off_host[n_seg], n_seg) * EQ_D * sizeof(double);
+  if (!scratch || ((uintptr_t)scratch & 15) || scratch_bytes < need)
+    return fail("%s: scratch missing, not 16-byte aligned or too small (%zu bytes, need %zu)", who, scratch_bytes, need);
+  CttsDeviceGuard dg(stream);
+  CK(launch_equalize_ragged(x, y, (const long long*)off_dev, n_seg, tiles_max, sel_dev, coef_dev, (double*)scratch, (hipStream_t)stream));
+  return 0;
+}
 // ---- the limiter of streams: the host's arithmetic (limiter.py: stream_plan) and every check the launch trusts --------------------------
 static_assert(sizeof(ctts_lm_stream) == 80 && sizeof(LmStream) == 80 && offsetof(ctts_lm_stream, n_out) == offsetof(LmStream, n_out) &&
               offsetof(ctts_lm_stream, slot) == offsetof(LmStream, slot) && offsetof(ctts_lm_stream, c_out) == offsetof(LmStream, c_out) &&

@@ -606,6 +606,21 @@ struct CpStream {
 hipError_t launch_compress_stream(const float* x, const CpStream* tab, int n_streams, long long nb_new_max, long long nb_out_max,
                                   const float* tabs, float* y, float* carry, float* hold, void* stats, float* cb, hipStream_t st);
 
+// ---- output equaliser (equalizer.hip) ----------------------------------------------------------------
+#define EQ_CHUNK 33           // samples a lane runs of its wave's tile (equalizer.CHUNK): odd, the lanes' LDS reads hit 32 banks
+#define EQ_TILE 2112          // samples of one segment per wave: 64 chunks, anchored at the segment's first sample
+#define EQ_WAVES 4            // tiles (waves) per workgroup: 4 * EQ_TILE floats of LDS
+#define EQ_NSEC 4             // second-order sections of a cascade, at most
+#define EQ_D 8                // float64 per tile record and per matrix row: two states per section
+#define EQ_ROW 800            // float64 per (rate, spec) of the coefficient table (equalizer.row)
+// tile records a pack of `total` samples in n_seg segments needs: segment s's tiles start at record off[s] / EQ_TILE + s
+static inline long long equalize_records(long long total, int n_seg) { return total / EQ_TILE + n_seg + 1; }
+// packed segments x[off[s], off[s+1]) through the cascade of row sel[s] of coef (-1: copied through): y may be x.  tiles_max: the most
+// tiles ceil(n_s / EQ_TILE) of a segment (grid sizes); rec: equalize_records(..) * EQ_D float64 of scratch.  Three launches (one where no
+// segment is longer than a tile).  Every bound is the caller's to check
+hipError_t launch_equalize_ragged(const float* x, float* y, const long long* off, int n_seg, long long tiles_max, const int32_t* sel,
+                                  const double* coef, double* rec, hipStream_t st);
+
 // ---- pause control (pauses.hip) -------------------------------------------------------------------
 #define PA_FMIN 80            // a frame is F = fs / 100 samples (integer division): 8 kHz ..
 #define PA_FMAX 480           // .. 48 kHz

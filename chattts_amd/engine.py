@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from . import adpcm as ADPCM
 from . import compressor as CP
+from . import equalizer as EQ
 from . import flac as FLAC
 from . import g711 as G711
 from . import loudness as LN
@@ -2049,6 +2050,58 @@ class CodecEngine:
             return y, work[: CP.STATS.itemsize * n_seg].cpu().numpy().view(CP.STATS)
         return y
 
+    # -- output equaliser (csrc/equalizer.hip) ------------------------------------------------------------------------------------------
+    def equalize(self, wav: torch.Tensor, spec, offsets=None, rates=None, out=None):
+        """The output equaliser on a float32 device tensor (ctts_equalize_ragged; the definition of equalizer.py): 1-D (one signal),
+        [B, n] (rows, each alone), or 1-D packed with `offsets` (n_seg + 1 sample offsets, the ragged decoder's layout; every segment
+        filtered as if alone, from zero state at its first sample).  `spec`: a preset name ("telephone", "rumble") or a dict with any
+        of highpass_hz, lowshelf {hz, db}, highshelf {hz, db}, peaks [{hz, db, q}, ...], at most four sections -- one for all, or a
+        list with one per segment; a segment whose spec is None, False or the identity is copied through bit for bit.  `rates`: the
+        segments' sample rates in Hz (one, or one per segment; default 24000), multiples of 10 in 8000 .. 48000; a section's hz lies
+        in 20 .. 0.45 of its segment's rate.  The result is the serial float64 cascade rounded once to float32, to within one float32
+        ulp where a value sits on a rounding boundary.  Returns a tensor of the input's shape (`out`, when given: a float32 device
+        tensor of that shape, possibly `wav` itself).  A segment's samples do not depend on what it is packed with.  ValueError
+        before any launch: a bad spec, a rate out of range, an empty segment, non-ascending offsets, 2^31 - 4096 samples, more than
+        65535 segments, no segment that asks for the equaliser."""
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() in (1, 2)):
+            raise ValueError("equalize: a float32 device tensor, 1-D or [B, n]")
+        if offsets is not None and wav.dim() != 1:
+            raise ValueError("equalize: offsets go with a packed 1-D tensor")
+        if wav.numel() == 0:
+            raise ValueError("equalize: nothing to equalise")
+        if wav.dim() == 2:
+            offsets = np.arange(wav.shape[0] + 1, dtype=np.int64) * int(wav.shape[1])
+        off, sel, coef_h, _ = EQ.tables(wav.numel(), spec, offsets, rates)
+        n_seg = len(off) - 1
+        if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.shape == wav.shape
+                                    and out.is_contiguous()):
+            raise ValueError("equalize: out is a contiguous float32 device tensor of the input's shape")
+        x = wav.contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()
+        y = out if out is not None and out.data_ptr() % 16 == 0 else torch.empty_like(x)
+        off_p = off.ctypes.data_as(C.c_void_p)
+        sb = int(self.lib.ctts_equalize_ragged_scratch_bytes(off_p, n_seg))
+        if sb == 0:
+            _lib.check(-1, "ctts_equalize_ragged")                # the offsets were refused: the library's message says why
+        dev = wav.device
+        host = [coef_h.view(np.uint8).reshape(-1), off.view(np.uint8), sel.view(np.uint8)]                  # the coefficient rows first: 16-byte aligned
+        tabs = torch.from_numpy(np.concatenate(host)).to(dev)                                              # one upload
+        work = device_scratch(sb, dev)
+        st = torch.cuda.current_stream(dev)
+        base = tabs.data_ptr()
+        p_off = base + coef_h.nbytes
+        _lib.check(self.lib.ctts_equalize_ragged(
+            x.data_ptr(), y.data_ptr(), p_off, off_p, n_seg, p_off + off.nbytes, sel.ctypes.data_as(C.c_void_p),
+            base, coef_h.ctypes.data_as(C.c_void_p), int(coef_h.shape[0]), work.data_ptr(), sb, st.cuda_stream), "ctts_equalize_ragged")
+        tabs.record_stream(st)
+        work.record_stream(st)
+        x.record_stream(st)
+        if out is not None and y is not out:
+            out.copy_(y.view(out.shape))
+            y = out
+        return y.view(wav.shape)
+
     # -- the compressor of streams: per-stream device state (csrc/compressor.hip, compress_stream_*_k) -----------------------------------
     def compress_stream_open(self, rate: int, spec=True) -> int:
         """A stream of the compressor at `rate` Hz with `spec` (True: the defaults, or a dict of `compress`'s fields): -> its handle, a
@@ -2406,7 +2459,7 @@ class CodecEngine:
 
     # -- ragged decode: packed utterances, each decoded as if alone ---------------------------------------------------------------
     def decode_ragged(self, rows: List[torch.Tensor], return_mel: bool = False, sample_rate=None, speed=None, loudness=None, pauses=None,
-                      limiter=None, compress=None):
+                      limiter=None, compress=None, eq=None):
         """Every [T_i, 768] hidden-state row (views allowed) through DVAE + Vocos EXACTLY AS IF DECODED ALONE, in one pass over the
         packed frames (ctts_dvae_decode_ragged / ctts_vocos_decode_ragged): each utterance gets zero padding at its own edges in every
         convolution, so its audio does not depend on what else is in the call -- unlike `decode_to_wavs`, whose zero-padded [B, Tmax]
@@ -2434,10 +2487,14 @@ class CodecEngine:
         gain.  The rows that do not ask for it are not touched by it.
         `compress` (None: off): a compressor spec (True or a dict, `compressor.check`) -- one, or a list with one per row, None entries
         copied through (`compress`, every row alone at its own rate, in place): behind `pauses` and in front of the loudness stage, so
-        the target is reached on compressed samples and the limiter still holds the ceiling."""
+        the target is reached on compressed samples and the limiter still holds the ceiling.
+        `eq` (None: off): an equaliser spec (a preset name or a dict, `equalizer.check`) -- one, or a list with one per row, None
+        entries copied through (`equalize`, every row alone at its own rate from zero state, in place): behind `pauses`, whose detector
+        sees the signal it was tuned on, and in front of `compress`, so the compressor, the loudness stage and the limiter see what the
+        listener will hear."""
         if len(rows) == 0:
             raise ValueError("decode_ragged needs at least one row")
-        plan = OC.Plan.rows("decode_ragged", len(rows), sample_rate, speed, loudness, pauses, limiter, compress)     # every refusal, before the decode
+        plan = OC.Plan.rows("decode_ragged", len(rows), sample_rate, speed, loudness, pauses, limiter, compress, eq)     # every refusal, before the decode
         if plan.on:
             out = self.decode_ragged(rows, return_mel)                # the plain decode, through the public method
             return (*OC.run(self, out[0], plan, offsets=out[1], in_place=True), *out[2:])
@@ -3704,7 +3761,7 @@ class CodecEngine:
         return out
 
     def decode_to_wavs(self, result_list: List[torch.Tensor], pad_to: Optional[int] = None, sample_rate: Optional[int] = None,
-                       speed: Optional[float] = None, loudness=None, pauses=None, limiter=None, compress=None) -> torch.Tensor:
+                       speed: Optional[float] = None, loudness=None, pauses=None, limiter=None, compress=None, eq=None) -> torch.Tensor:
         """`Chat._decode_to_wavs` (core.py:513-539): zero-pad the per-row [T_b,768] hidden lists to the
         longest row, DVAE decode, Vocos decode -> [B, 256(2Tmax-1)] float32 on the device.  `pad_to`: pad to that many tokens instead
         (>= the longest row): a data-parallel shard decodes its rows as part of the GLOBAL batch (dist.infer_sharded) -- the reference
@@ -3719,10 +3776,12 @@ class CodecEngine:
         through the look-ahead peak limiter (`peak_limit`) behind the loudness stage's gain, which then drops its ceiling term
         (`loudness_normalize(limiter=)`); without `loudness` at unity gain.  `compress` (None: off): a compressor spec, one or a
         list with one per row (None entries copied through) -- every row, padding and all, is compressed alone (`compress`) at the
-        returned rate, behind `pauses` and in front of the loudness stage."""
+        returned rate, behind `pauses` and in front of the loudness stage.  `eq` (None: off): an equaliser spec, one or a list with
+        one per row (None entries copied through) -- every row, padding and all, is filtered alone from zero state (`equalize`) at the
+        returned rate, behind `pauses` and in front of `compress`."""
         if len(result_list) == 0:
             return torch.empty((0,), dtype=torch.float32)
-        plan = OC.Plan.batch("decode_to_wavs", len(result_list), sample_rate, speed, loudness, pauses, limiter, compress)   # every refusal, before the decode
+        plan = OC.Plan.batch("decode_to_wavs", len(result_list), sample_rate, speed, loudness, pauses, limiter, compress, eq)   # every refusal, before the decode
         if plan.on:
             return OC.run(self, self.decode_to_wavs(result_list, pad_to), plan, in_place=True)   # the plain decode, through the public method
         longest = max(int(r.size(0)) for r in result_list)

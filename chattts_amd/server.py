@@ -98,7 +98,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                stream_sample_rates=None, g711: bool = False, speed: bool = False, stream_speed: bool = False,
                stream_speed_rates: bool = False, flac: bool = False, loudness: bool = False, stream_flac: bool = False,
                pauses: bool = False, limiter: bool = False, stream_limiter: bool = False, stream_pauses: bool = False,
-               adpcm: bool = False, stream_adpcm: bool = False, compress: bool = False, stream_compress: bool = False):
+               adpcm: bool = False, stream_adpcm: bool = False, compress: bool = False, stream_compress: bool = False,
+               eq: bool = False):
     """FastAPI app serving `chat` (a loaded `chattts_amd.core.Chat`).  `voices`: OpenAI voice name -> `spk_emb` string
     (`Chat.sample_random_speaker()` / the reference's speaker files); an unknown voice falls back to "default" like openai_api.py:165.
     `infer_kwargs`: extra keywords for every serial `chat.infer` call (tests).  `batch_slots`: None = one request at a time (the
@@ -204,7 +205,15 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
     `"compress"` is served -- the stream's chunks come out of a compressor stream that carries the hold's block gains and the few
     unemitted samples across chunks (CodecEngine.compress_stream_*), the attack and at most two milliseconds behind -- from the pool where
     `batch_streams` allows it and the batcher was built with `stream_compress=True`, serially otherwise (Chat.infer(stream=True,
-    compress=, stream_compress=True)); /health carries `"stream_compress": true`."""
+    compress=, stream_compress=True)); /health carries `"stream_compress": true`.  `eq=True` (default off: every response, status,
+    warning and /health list is as without it, an `"eq"` key is ignored with the "unsupported parameters" warning): a non-streamed
+    request body may carry `"eq"`: a preset name ("telephone", "rumble") or an object with any of `highpass_hz`, `lowshelf` {hz, db},
+    `highshelf` {hz, db}, `peaks` [{hz, db, q}, ...], at most four sections (chattts_amd/equalizer.py) -- the utterance goes through the
+    biquad cascade on the device, behind `pauses` and in front of the compressor, the loudness stage, the limiter and the 16-bit
+    conversion (Chat.infer(eq=) / SpeechBatcher.submit(eq=)), in whatever format, rate and speed the other options allow; false or
+    null leaves the spectrum alone; a bad spec (a frequency above 0.45 of the request's rate too) gets a 400 with the validator's
+    message; `"stream": true` with it gets a 400 (an equalised stream would need the filter state carried across chunks), and
+    /health carries `"eq": true`."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import JSONResponse, Response, StreamingResponse
     from pydantic import BaseModel, Field, ValidationError
@@ -304,6 +313,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
         from . import loudness as LN
         allowed = allowed | {"compress"}
 
+    if eq:
+        from . import equalizer as EQ
+        allowed = allowed | {"eq"}
+
     class SpeechRequest(BaseModel):                  # openai_api.py:108-127
         model: str = "tts-1"
         input: str = Field(..., max_length=2048)
@@ -328,8 +341,10 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
 
     def infer(req: "SpeechRequest", rate: int = SAMPLE_RATE, law: Optional[str] = None, spd: Optional[float] = None,
               as_flac: bool = False, lufs: Optional[float] = None, trim=None, lim: bool = False, gdb=None,
-              as_adpcm: bool = False, comp=None):                                   # openai_api.py:168-183,207-222
+              as_adpcm: bool = False, comp=None, tone=None):                        # openai_api.py:168-183,207-222
         kw = dict(extra) if rate == SAMPLE_RATE else {**extra, "sample_rate": rate}
+        if tone is not None:
+            kw = {**kw, "eq": tone}
         if comp is not None:
             kw = {**kw, "compress": comp}
         if lim:
@@ -445,6 +460,15 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             if req.stream and not compress_streams:
                 raise HTTPException(400, detail="compress is served for non-streamed requests only: a compressed stream would need the "
                                                 "block state carried across chunks")
+        tone = None                                  # the request's equaliser spec where it is honoured
+        if eq and request_data.get("eq") is not None and request_data["eq"] is not False:
+            try:
+                tone = EQ.check(request_data["eq"], "eq", rate)
+            except ValueError as e:
+                raise HTTPException(400, detail=str(e))
+            if tone is not None and req.stream:
+                raise HTTPException(400, detail="eq is served for non-streamed requests only: an equalised stream would need the filter "
+                                                "state carried across chunks")
         lim = False                                  # the request's limiter flag where it is honoured
         if limiter and request_data.get("limiter") is not None:
             if not isinstance(request_data["limiter"], bool):
@@ -601,13 +625,18 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
                     rkw = {**rkw, "limiter": True}
                 if comp is not None:
                     rkw = {**rkw, "compress": comp}
+                if tone is not None:
+                    rkw = {**rkw, "eq": tone}
                 wavs = [await asyncio.wrap_future(batcher.submit(req.input, code_params(req.voice), **rkw, **ekw))]
             except Exception as e:
                 raise HTTPException(500, detail=f"Speech synthesis failed: {e}")
         else:
             async with app.state.model_lock:
                 try:
-                    if comp is not None:
+                    if tone is not None:
+                        wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, lim, **akw,
+                                                       **({} if comp is None else {"comp": comp}), tone=tone)
+                    elif comp is not None:
                         wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, lim, **akw, comp=comp)
                     elif lim:
                         wavs = await run_in_threadpool(infer, req, rate, law, spd, as_flac, lufs, trim, True, **akw)
@@ -683,6 +712,8 @@ def create_app(chat, voices: Optional[Dict[str, str]] = None, logger: Optional[l
             out["compress"] = True
         if compress_streams:
             out["stream_compress"] = True
+        if eq:
+            out["eq"] = True
         return out
 
     return app

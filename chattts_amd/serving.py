@@ -46,6 +46,7 @@ from . import g711 as G711
 from . import loudness as LN
 from . import limiter as LM
 from . import compressor as CP
+from . import equalizer as EQ
 from . import pauses as PA
 from . import resample as RS
 from . import timescale as TS
@@ -679,6 +680,7 @@ class _Job:
     lm_gain: Optional[float] = None        # ... and the float32 pre-gain of its `gain_db` (None: 1)
     compress: object = None                # a checked compressor spec; None: the dynamics are left alone
     cp_slot: Optional[int] = None          # a compressed stream: its compressor stream, opened at its first chunk
+    eq: object = None                      # a checked equaliser spec (non-streamed only); None: the spectrum is left alone
 
     @property
     def is_stream(self) -> bool:
@@ -721,7 +723,8 @@ def _format_kw(jobs, rate_kw: str = "sample_rate", encoding_kw: str = "encoding"
     at speed 1: the collaborator is then called exactly as it was before it knew rates, encodings and speeds (the host fakes pin that)."""
     kw = option_kw({rate_kw: [j.sample_rate for j in jobs], encoding_kw: [j.encoding for j in jobs], speed_kw: [j.speed for j in jobs],
                     "flac": [j.flac for j in jobs], "loudness": [j.loudness for j in jobs], "pauses": [j.pauses for j in jobs],
-                    "limiter": [j.limiter for j in jobs], "adpcm": [j.adpcm for j in jobs], "compress": [j.compress for j in jobs]})
+                    "limiter": [j.limiter for j in jobs], "adpcm": [j.adpcm for j in jobs], "compress": [j.compress for j in jobs],
+                    "eq": [j.eq for j in jobs]})
     if rate_kw in kw:
         kw[rate_kw] = [24000 if r is None else r for r in kw[rate_kw]]
     if speed_kw in kw:
@@ -877,7 +880,7 @@ class SpeechBatcher:
     # -- public -------------------------------------------------------------------------------------------------------------
     def submit(self, text: str, params, refine=None, split_text: bool = False, max_split_batch: int = 4, sample_rate=None,
                encoding=None, speed=None, flac: bool = False, loudness=None, pauses=None, limiter: bool = False,
-               adpcm: bool = False, compress=None) -> Future:
+               adpcm: bool = False, compress=None, eq=None) -> Future:
         """one non-streamed request: `text` as the endpoint received it, `params` its InferCodeParams.  The Future resolves to the
         int16 waveform `Chat.infer([text], skip_refine_text=True, params_infer_code=params, pcm16=True)[0]` would return.
         `refine` (a `RefineTextParams`; batchers built with refine=True): the refine-text pass runs first, in the text pool -- the
@@ -913,7 +916,14 @@ class SpeechBatcher:
         `compress` (None / False: off; True or a dict of compressor.RANGES' fields): the serial call's `compress=` -- the look-ahead
         compressor on the device, behind `pauses` and in front of the loudness stage; requests that finish together with different
         specs, or none, still share the one ragged decode and ONE `CodecEngine.compress` call (a request without a spec is copied
-        through it; every sentence of a split request is compressed alone)."""
+        through it; every sentence of a split request is compressed alone).
+        `eq` (None / False: off; an equaliser preset name or a dict of equalizer.FIELDS): the serial call's `eq=` -- the biquad
+        cascade on the device, behind `pauses` and in front of `compress`; requests that finish together with different specs, or
+        none, still share the one ragged decode and ONE `CodecEngine.equalize` call (a request without a spec is copied through it;
+        every sentence of a split request is filtered alone from zero state)."""
+        eq = EQ.check(eq, "submit")
+        if eq is not None:
+            eq = EQ.check(eq, "submit", LN.check_rate(24000 if sample_rate is None else sample_rate))
         compress = CP.check(compress, "submit")
         if compress is not None:
             LN.check_rate(24000 if sample_rate is None else sample_rate)
@@ -946,7 +956,7 @@ class SpeechBatcher:
         fut.rid = next(self._ids)
         self._in.put(_Job(fut.rid, text, params, fut, refine, int(max_split_batch) if split_text else None, self._rate(sample_rate), encoding,
                           speed=speed, flac=bool(flac), loudness=loudness, pauses=pauses, limiter=limiter, adpcm=bool(adpcm),
-                          compress=compress))
+                          compress=compress, eq=eq))
         return fut
 
     def cancel(self, fut: Future) -> None:
@@ -1436,14 +1446,14 @@ class SpeechBatcher:
         self.lock.acquire()
 
     def finish(self, hid: torch.Tensor, sample_rate=None, encoding=None, speed=None, flac: bool = False, loudness=None,
-               pauses=None, limiter: bool = False, adpcm: bool = False, compress=None) -> np.ndarray:
+               pauses=None, limiter: bool = False, adpcm: bool = False, compress=None, eq=None) -> np.ndarray:
         """the serial server's path for one utterance (Chat.infer, pcm16, split_text): decode -> sample-level strip -> float_to_int16"""
         from .audio import float_to_int16
         if hid.shape[0] == 0:
             raise RuntimeError(_NO_AUDIO)
         self._count_decode(1)
         kw = option_kw({"sample_rate": [sample_rate], "speed": [speed], "loudness": [loudness], "pauses": [pauses], "limiter": [bool(limiter)],
-                        "compress": [compress]})
+                        "compress": [compress], "eq": [eq]})
         wav = self.chat.decode_to_wavs([hid], **{k: v[0] for k, v in kw.items()})[0]
         pcm = float_to_int16(wav[np.abs(wav) > np.float32(1e-5)])
         if flac:                                                            # converted on the host, encoded by the host twin
@@ -1453,18 +1463,19 @@ class SpeechBatcher:
         return pcm if encoding is None else G711.encode(pcm, encoding)      # converted on the host, companded by the host twin
 
     def finish_group(self, hids: List[torch.Tensor], sample_rates=None, encodings=None, speeds=None, flac=None, loudness=None,
-                     pauses=None, limiter=None, adpcm=None, compress=None) -> list:
+                     pauses=None, limiter=None, adpcm=None, compress=None, eq=None) -> list:
         """ragged_decode: the requests of one poll in ONE decode, each as if alone -> per request its int16 waveform (what `finish`
         returns for it) or the exception that fails it alone (an empty result).  `sample_rates`: one rate per request (None: 24000);
         `speeds`: one speed per request (None: 1.0); `loudness`: one target per request (None entries: left alone); `pauses`: one spec
         per request (None entries: copied through the one `trim_pauses` call); `limiter`: one flag per request; `flac`, `adpcm`: one flag per request (no request has both);
-        `compress`: one spec per request (None entries: copied through the one `compress` call)"""
+        `compress`: one spec per request (None entries: copied through the one `compress` call); `eq`: one equaliser spec per request
+        (None entries: copied through the one `equalize` call)"""
         out: list = [RuntimeError(_NO_AUDIO) if h.shape[0] == 0 else None for h in hids]
         live = [i for i, h in enumerate(hids) if h.shape[0] > 0]
         if live:
             self._count_decode(len(live))
             kw = option_kw({"sample_rate": sample_rates, "encoding": encodings, "speed": speeds, "flac": flac, "loudness": loudness,
-                            "pauses": pauses, "limiter": limiter, "adpcm": adpcm, "compress": compress}, rows=live)
+                            "pauses": pauses, "limiter": limiter, "adpcm": adpcm, "compress": compress, "eq": eq}, rows=live)
             for i, pcm in zip(live, self.chat.decode_to_pcm16([hids[i] for i in live], ragged=True, **kw)):
                 out[i] = pcm
         return out

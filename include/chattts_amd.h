@@ -495,6 +495,33 @@ int ctts_compress_ragged(const float* x, float* y, const int64_t* off_dev, const
                          const int32_t* rate_host, const int32_t* par_dev, const int32_t* par_host, const float* tab_dev,
                          const float* tab_host, int32_t n_tab, void* stats, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The output equaliser (the definition, once, is chattts_amd/equalizer.py): packed float32 segments x[off[s], off[s+1]), every segment
+ * through a cascade of 1 .. 4 second-order sections as if alone: transposed direct form II in float64 from zero state at the segment's
+ * first sample (per section y = b0 x + s0; s0 = b1 x - a1 y + s1; s1 = b2 x - a2 y), the last section's output rounded once to float32.
+ * sel holds one int32 per segment: its row of the coefficient table, or -1 (the segment is copied through bit for bit).  coef holds
+ * n_rows rows of CTTS_EQ_ROW float64, one per distinct (rate, spec): [0] the number of sections, [1] the rate in Hz (a multiple of 10 in
+ * 8000 .. 48000; the kernels do not read it), [2] the chunk (33), [4 + 5 i ..) section i's b0 b1 b2 a1 a2 normalised by a0, [32 + 64 j ..)
+ * the state matrix of the cascade to the power 33 * 2^j, j = 0 .. 11, 8 x 8 row-major with zeros beyond two states per section.  The chain
+ * is computed in parallel and exactly: chunks of 33 samples run from zero state, the powers carry their end states to the chunks behind
+ * them (within a tile of CTTS_EQ_TILE samples by a scan over the chunks, from tile to tile by the same scan over one record per tile),
+ * and every chunk runs again from its true entry state.  In float64 that agrees with the serial loop to about 1e-12 of the signal's
+ * level: a result differs from the loop's only where it sits on a float32 rounding boundary, by one ulp (an output within about 1e-5
+ * of the level of zero has ulps smaller than that error and can be a few of them off).  The tiles are anchored at the segment's first sample: a
+ * segment's samples do not depend on what it is packed with.  y may be x (otherwise the two do not overlap), both 16-byte aligned, as
+ * are coef_dev and the scratch.  Every table is given on the device and the host (the two must agree).  Refused before anything is
+ * launched: a null pointer, offsets that do not ascend from 0, an empty segment, a pack of 2^31 - 4096 samples or more, more than 65535
+ * segments, n_rows outside 1 .. n_seg, a row with fewer than 1 or more than 4 sections, with a rate outside the range or not a multiple
+ * of 10, with another chunk, with a coefficient or matrix entry that is not finite or a section that is not stable, a row index outside
+ * -1 .. n_rows - 1, misaligned buffers, y overlapping x in part, scratch under the companion function's size (0: the offsets were
+ * refused).  Stream-ordered, three launches: the tiles' end states, the scan of the tiles per segment, and y (one launch where no segment
+ * is longer than a tile). */
+#define CTTS_EQ_ROW 800
+#define CTTS_EQ_TILE 2112
+size_t ctts_equalize_ragged_scratch_bytes(const int64_t* off_host, int32_t n_seg);
+int ctts_equalize_ragged(const float* x, float* y, const int64_t* off_dev, const int64_t* off_host, int32_t n_seg, const int32_t* sel_dev,
+                         const int32_t* sel_host, const double* coef_dev, const double* coef_host, int32_t n_rows, void* scratch,
+                         size_t scratch_bytes, void* stream);
+
 /* The limiter of STREAMS: the segment exists nowhere as a whole, it arrives in pushes, and each step returns the samples the pushes so
  * far decide.  y[i] depends on x[i - 2 W .. i + 2 W], so with pos samples in and more to come, samples [0, pos - 2 W) are out: a stream
  * lags by 2 W samples (20 ms).  One step of one stream: x[in_off, in_off + n_in) are samples [pos, pos + n_in); it writes samples
