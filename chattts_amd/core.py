@@ -33,6 +33,7 @@ from . import outchain
 from . import pauses as PA
 from . import resample as RS
 from . import weights as W
+from . import winchain as WC
 from .audio import float_to_int16
 from .config import GPT
 from .dvae import DvaeEngine
@@ -630,21 +631,13 @@ class Chat:
         converted (CodecEngine.decode_windows(limiter=)); `adpcm` with `adpcm_streams`: as `flac` / `flac_streams`, with the handle of
         the window's IMA ADPCM stream -- the piece is the blocks the push completes (CodecEngine.decode_windows(adpcm=)); without
         them today's call, argument for argument"""
-        kw = {k: v for k, v in (("sample_rates", sample_rates), ("encodings", encodings), ("speeds", speeds)) if v is not None}
-        if speeds is not None:
-            kw["ts_streams"] = ts_streams
-            if rs_streams is not None:
-                kw["rs_streams"] = rs_streams
-        if flac is not None:
-            kw["flac"], kw["flac_streams"] = flac, flac_streams
-        if adpcm is not None:
-            kw["adpcm"], kw["adpcm_streams"] = adpcm, adpcm_streams
-        if limiter is not None:
-            kw["limiter"], kw["lm_streams"] = limiter, lm_streams
-        if pauses is not None:          # a flagged window goes through its pause stream in front of all that (CodecEngine.decode_windows(pauses=))
-            kw["pauses"], kw["pa_streams"] = pauses, pa_streams
-        if compress is not None:        # ... and behind that through its compressor stream, in front of the limiter's (CodecEngine.decode_windows(compress=))
-            kw["compress"], kw["cp_streams"] = compress, cp_streams
+        given = dict(sample_rates=sample_rates, encodings=encodings, speeds=speeds, ts_streams=ts_streams, rs_streams=rs_streams, flac=flac,
+                     flac_streams=flac_streams, limiter=limiter, lm_streams=lm_streams, pauses=pauses, pa_streams=pa_streams, adpcm=adpcm,
+                     adpcm_streams=adpcm_streams, compress=compress, cp_streams=cp_streams)
+        kw = {k: given[k] for k in ("sample_rates", "encodings", "speeds") if given[k] is not None}
+        for st in WC.STAGES:            # a stage whose flag is given: its flag and its streams (the resampler's only when given too)
+            if given[st.flag] is not None and not (st.optional and given[st.streams] is None):
+                kw[st.flag], kw[st.streams] = given[st.flag], given[st.streams]
         return self.codec.decode_windows(store, windows, pcm16=True, keep_thr=1e-5, **kw)
 
     def infer_ids(self, input_ids, attention_mask, text_mask, params: InferCodeParams = InferCodeParams(), **kw) -> np.ndarray:
@@ -1324,57 +1317,48 @@ class Chat:
             params_infer_code.spk_smp = self.refer_speaker(result.hiddens if use_decoder else result.ids, use_decoder, release=result.destroy)
             params_infer_code.txt_smp = refer_text
         step = max_split_batch if split_text else len(text)
-        ts = [] if stream and speed is not None else None      # a streamed speed: the rows' streams of the time scaler, opened at the first chunk
-        rs = [] if ts is not None and sample_rate is not None else None      # ... at another rate: and their streams of the resampler
-        fs = [] if stream and (flac or adpcm) and pcm16 else None      # a streamed FLAC / ADPCM file: the rows' encoder streams, opened at the first chunk
-        lm = [] if stream and lm_gain is not None else None    # a limited stream: the rows' limiter streams, opened at the first chunk
-        pa = [] if stream and pa_spec is not None else None    # a paused stream: the rows' pause streams, opened at the first chunk
-        cp = [] if stream and cp_spec is not None else None    # a compressed stream: the rows' compressor streams, opened at the first chunk
+        sets = [] if stream else None      # a stream: one `winchain.StreamSet` per row, opened at the first chunk (`_infer_batches`)
+        on = lambda v: stream and v is not None
         try:
             yield from self._infer_batches(text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate,
-                                           encoding, speed, ts, rs, **({"flac": True} if flac else {}),
-                                           **({} if loudness is None else {"loudness": loudness}), **({} if fs is None else {"fs": fs}),
-                                           **({} if pauses is None else {"pauses": pauses}),
-                                           **({} if limiter is None else {"limiter": limiter}),
-                                           **({} if lm is None else {"lm": lm, "lm_gain": lm_gain}),
-                                           **({} if pa is None else {"pa": pa, "pa_spec": pa_spec}), **({"adpcm": True} if adpcm else {}),
+                                           encoding, speed, sets, **({"flac": True} if flac else {}),
+                                           **({} if loudness is None else {"loudness": loudness}), **({} if pauses is None else {"pauses": pauses}),
+                                           **({} if limiter is None else {"limiter": limiter}), **({"lm_gain": lm_gain} if on(lm_gain) else {}),
+                                           **({"pa_spec": pa_spec} if on(pa_spec) else {}), **({"adpcm": True} if adpcm else {}),
                                            **({} if compress is None else {"compress": compress}), **({} if eq is None else {"eq": eq}),
-                                           **({} if cp is None else {"cp": cp, "cp_spec": cp_spec}))
+                                           **({"cp_spec": cp_spec} if on(cp_spec) else {}))
         finally:
-            for h in cp or ():
-                self.codec.compress_stream_close(h)
-            for h in pa or ():
-                self.codec.trim_pauses_stream_close(h)
-            for h in lm or ():
-                self.codec.peak_limit_stream_close(h)
-            for h in fs or ():
-                if not isinstance(h, (FLAC.StreamEncoder, ADPCM.StreamEncoder)):
-                    (self.codec.adpcm_stream_close if adpcm else self.codec.flac_stream_close)(h)
-            for h in ts or ():                                 # also when the consumer drops the generator half way
-                self.codec.time_scale_stream_close(h)
-            for h in rs or ():
-                self.codec.resample_stream_close(h)
+            for st in sets or ():              # also when the consumer drops the generator half way
+                st.close(self.codec)
 
-    def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed, ts,
-                       rs=None, flac: bool = False, loudness=None, fs=None, pauses=None, limiter=None, lm=None, lm_gain=None, pa=None, pa_spec=None,
-                       adpcm: bool = False, compress=None, cp=None, cp_spec=None, eq=None):
-        """the batch loop of `_infer`"""
-        # the rows' encoder streams `fs` are FLAC streams, or with `adpcm` IMA ADPCM streams: the same placement, the same host twin
-        Twin = ADPCM.StreamEncoder if adpcm else FLAC.StreamEncoder
-        fs_open = lambda rate: (self.codec.adpcm_stream_open if adpcm else self.codec.flac_stream_open)(rate)
+    def _infer_batches(self, text, step, stream, use_decoder, split_text, params_infer_code, pcm16, ragged, raw, sample_rate, encoding, speed,
+                       sets=None, flac: bool = False, loudness=None, pauses=None, limiter=None, lm_gain=None, pa_spec=None, adpcm: bool = False,
+                       compress=None, cp_spec=None, eq=None):
+        """the batch loop of `_infer`.  `sets` (a stream): the rows' `winchain.StreamSet`s, opened here at the first chunk, closed by `_infer`"""
+        scaled = stream and speed is not None
+        filed = stream and (flac or adpcm) and pcm16           # the chunks are FLAC frames, or with `adpcm` IMA ADPCM blocks
+        rowwise = stream and (pa_spec is not None or cp_spec is not None)      # the chunks are lists with one array per row
+        # a filed stream's encoder streams are on the device, or host twins where every chunk is converted on the host: the same placement
+        Twin, twins = ADPCM.StreamEncoder if adpcm else FLAC.StreamEncoder, []
         fs_step = lambda pcm, pushes: (self.codec.adpcm_stream_step if adpcm else self.codec.flac_stream_step)(pcm, pushes)
-        def flac_chunks(piece, final):
+
+        def handles(rows):
+            """the rows' stream sets, opened at the first chunk with what the options need -> stage name -> the rows' handles"""
+            if not sets:
+                dev = filed and (rowwise or (use_decoder and self.incremental_stream))
+                sets.extend(WC.StreamSet.open(self.codec, rate=sample_rate, speed=speed, pauses=pa_spec, compress=cp_spec, limiter_gain=lm_gain,
+                                              flac=dev and not adpcm, adpcm=dev and adpcm) for _ in rows)
+            return {name: [st[name] for st in sets] for name in (sets[0] if sets else ())}
+
+        def flac_chunks(piece, final, fs):
             """the rows of one streamed chunk (int16 [B, n]: a device tensor, or converted on the host) pushed into the rows' encoder
-            streams `fs` -> one uint8 array per row"""
-            B = int(piece.shape[0])
-            if not fs:             # opened at the first chunk: on the device, or the host twin where every chunk is converted on the host
-                rate = CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate
-                on_device = use_decoder and self.incremental_stream
-                fs.extend(fs_open(rate) if on_device else Twin(rate) for _ in range(B))
-            n = int(piece.shape[1])
-            if isinstance(fs[0], Twin):
+            streams `fs` (None: the host twins) -> one uint8 array per row"""
+            B, n = int(piece.shape[0]), int(piece.shape[1])
+            if fs is None:
+                if not twins:
+                    twins.extend(Twin(CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate) for _ in range(B))
                 piece = np.asarray(piece).astype(np.int16, copy=False)
-                return [np.frombuffer(e.push(np.ascontiguousarray(r), final), np.uint8) for e, r in zip(fs, piece)]
+                return [np.frombuffer(e.push(np.ascontiguousarray(r), final), np.uint8) for e, r in zip(twins, piece)]
             if not isinstance(piece, torch.Tensor):
                 piece = torch.from_numpy(np.ascontiguousarray(piece, dtype=np.int16)).to(self.device)
             if n == 0:
@@ -1386,35 +1370,29 @@ class Chat:
             if piece.data_ptr() % 16:          # a view into the conversion's buffer: the encoder reads 16-byte units
                 piece = piece.clone()
             return fs_step(piece.view(-1), [(h, i * row, n, final) for i, h in enumerate(fs)])
-        dkw = {} if fs is None else {"on_device": True}
-        def open_streams(rows):
-            ts.extend(self.codec.time_scale_stream_open(speed) for _ in rows)
-            if rs is not None:
-                rs.extend(self.codec.resample_stream_open(CodecEngine.SAMPLE_RATE, sample_rate) for _ in rows)
-        rkw_s = {} if rs is None else {"rs_handles": rs}
-        def limited(rows):
-            """the rows' limiter streams, opened at the first chunk at the stream's output rate -> the keyword of the piece calls"""
-            if lm is None:
-                return {}
-            if not lm:
-                lm.extend(self.codec.peak_limit_stream_open(CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate, lm_gain) for _ in rows)
-            return {"lm_handles": lm}
-        def paused(rows, a, b, final):
-            """one chunk of a paused or compressed stream: a list with one array per row (`_stream_rows_paused`); every stream is opened
-            at the first"""
-            out_rate = CodecEngine.SAMPLE_RATE if sample_rate is None else sample_rate
-            if pa is not None and not pa:
-                pa.extend(self.codec.trim_pauses_stream_open(out_rate, pa_spec) for _ in rows)
-            if cp is not None and not cp:
-                cp.extend(self.codec.compress_stream_open(out_rate, cp_spec) for _ in rows)
-            if ts is not None and not ts:
-                open_streams(rows)
-            if fs is not None and not fs:
-                fs.extend(fs_open(out_rate) for _ in rows)
-            return self._stream_rows_paused(rows, a, b, final, pa, sample_rate, ts, rs, limited(rows).get("lm_handles"), pcm16,
-                                            encoding if pcm16 else None, fs, **({"fs_step": fs_step} if adpcm else {}),
-                                            **({} if cp is None else {"cp_handles": cp}))
-        rowwise = pa is not None or cp is not None             # the chunks are lists with one array per row
+
+        def piece_of(rows, a, b, final):
+            """one chunk of the stream through the rows' streams: `_stream_rows_paused` (a list, one array per row), `_stream_piece_scaled`
+            or `_stream_piece`, each with the handle lists it takes -> (the chunk, the rows' encoder streams or None)"""
+            h = handles(rows) if stream else {}
+            fs = h.get("adpcm" if adpcm else "flac")
+            lkw = {"lm_handles": h["limiter"]} if "limiter" in h else {}
+            dkw = {"on_device": True} if filed else {}
+            if rowwise:
+                return self._stream_rows_paused(rows, a, b, final, h.get("pauses"), sample_rate, h.get("time_scale"), h.get("resample"),
+                                                h.get("limiter"), pcm16, encoding if pcm16 else None, fs, **({"fs_step": fs_step} if adpcm else {}),
+                                                **({"cp_handles": h["compress"]} if "compress" in h else {})), fs
+            if scaled:
+                rkw = {"rs_handles": h["resample"]} if "resample" in h else {}
+                if final:
+                    return self._stream_piece_scaled(rows, a, b, h["time_scale"], True, **rkw, **lkw), fs
+                return self._stream_piece_scaled(rows, a, b, h["time_scale"], False, pcm16, encoding if pcm16 else None, **rkw, **dkw, **lkw), fs
+            skw = {"rate": sample_rate} if sample_rate is not None else {}      # 24 kHz: today's call, argument for argument
+            if final:
+                return self._stream_piece(rows, a, b, use_decoder, **skw, **({**lkw, "final": True} if lkw else {})), fs
+            if encoding is not None and pcm16:
+                skw["encoding"] = encoding
+            return self._stream_piece(rows, a, b, use_decoder, pcm16, **skw, **dkw, **lkw), fs
         length = 0
         pass_batch_count = 0
         for lo in range(0, len(text), step):
@@ -1463,20 +1441,9 @@ class Chat:
                 if pass_batch_count <= params_infer_code.pass_first_n_batches:
                     continue     # the reference decodes these yields and drops the audio (core.py:482-490)
                 src = result.hiddens if use_decoder else result.ids
-                skw = {"rate": sample_rate} if sample_rate is not None else {}      # 24 kHz: today's call, argument for argument
-                if encoding is not None and pcm16:
-                    skw["encoding"] = encoding
-                if rowwise:
-                    piece = paused(src, length, length + params_infer_code.stream_speed, False)
-                elif ts is not None:
-                    if not ts:
-                        open_streams(src)
-                    piece = self._stream_piece_scaled(src, length, length + params_infer_code.stream_speed, ts, False, pcm16,
-                                                      encoding if pcm16 else None, **rkw_s, **dkw, **limited(src))
-                else:
-                    piece = self._stream_piece(src, length, length + params_infer_code.stream_speed, use_decoder, pcm16, **skw, **dkw, **limited(src))
-                if fs is not None and not rowwise:
-                    piece = flac_chunks(piece, False)
+                piece, fs = piece_of(src, length, length + params_infer_code.stream_speed, False)
+                if filed and not rowwise:
+                    piece = flac_chunks(piece, False, fs)
                 # core.py:491-496: `b = a + stream_speed`, clamped to the width of THIS decode, becomes the new `length` -- also when
                 # that is BELOW `a`: `length` and `pass_batch_count` are not reset between split batches, so the first yields of a
                 # later batch (a short prefix again) are empty and pull `length` back (tests/test_host_flow.py, stream_split_batches)
@@ -1484,19 +1451,12 @@ class Chat:
                 length = min(length + params_infer_code.stream_speed, max(0, 256 * (2 * max(int(r.size(0)) for r in src) - 1)))
                 yield piece
             if stream and last is not None and rowwise:      # rows of different lengths: filtered and converted row by row
-                tail = paused(last.hiddens, length, None, True)
+                tail, _ = piece_of(last.hiddens, length, None, True)
                 last.destroy()
                 yield tail
                 continue
             if stream and last is not None:
-                skw = {"rate": sample_rate} if sample_rate is not None else {}
-                if ts is not None:
-                    if not ts:
-                        open_streams(last.hiddens)
-                    new_wavs = self._stream_piece_scaled(last.hiddens, length, None, ts, True, **rkw_s, **limited(last.hiddens))
-                else:
-                    new_wavs = self._stream_piece(last.hiddens if use_decoder else last.ids, length, None, use_decoder, **skw,
-                                                  **({} if lm is None else {**limited(last.hiddens), "final": True}))
+                new_wavs, fs = piece_of(last.hiddens if use_decoder or scaled else last.ids, length, None, True)
                 last.destroy()
                 keep_cols = np.sum(np.abs(new_wavs) > 1e-5, axis=0) > 0
                 tail = new_wavs[:, keep_cols]
@@ -1505,6 +1465,6 @@ class Chat:
                     tail = np.stack([float_to_int16(r) for r in tail]) if tail.shape[1] else tail.astype(np.int16)
                     if encoding is not None:      # companded by the host twin, like the conversion in front of it
                         tail = G711.encode(tail, encoding)
-                    if fs is not None:            # the streams' last push: what they held leaves with it
-                        tail = flac_chunks(tail, True)
+                    if filed:                     # the streams' last push: what they held leaves with it
+                        tail = flac_chunks(tail, True, fs)
                 yield tail

@@ -31,6 +31,7 @@ from . import pauses as PA
 from . import resample as RS
 from . import statepool as SP
 from . import timescale as TS
+from . import winchain as WC
 from ._sync import wait_event, wait_stream
 from .config import DVAE, GPT, VOCOS
 from .rng import ExpDraws, penalty_table
@@ -2762,118 +2763,156 @@ class CodecEngine:
         stream lags by its attack and two blocks of 1 ms at the most; a window marked `tail` is the stream's last push): in front of
         the limiter stream, the conversion, a tail's strip, G.711, FLAC and ADPCM, the non-streamed order.  One compressor step per
         round (two launches), no copy of its own.  Unflagged windows return the bytes they return without `compress`."""
-        cp = self._window_streams("compress", "cp_streams", "compressor", compress, cp_streams, windows, sample_rates,
-                                  flagged=lambda f: f is not None and f is not False)
-        pa = self._window_streams("pauses", "pa_streams", "pause", pauses, pa_streams, windows, sample_rates,
-                                  flagged=lambda f: f is not None and f is not False)
-        lm = self._window_streams("limiter", "lm_streams", "limiter", limiter, lm_streams, windows, sample_rates,
-                                  flagged=lambda f: LM.check_flag(f, "decode_windows"), any_flag=bool)
-        fl = None
-        fl_h = self._window_codec("flac", "FLAC", flac, flac_streams, windows, pcm16, sample_rates, encodings)
-        ad_h = self._window_codec("adpcm", "ADPCM", adpcm, adpcm_streams, windows, pcm16, sample_rates, encodings)
-        if fl_h is not None or ad_h is not None:
-            if fl_h is not None and ad_h is not None and any(f is not None and a is not None for f, a in zip(fl_h, ad_h)):
-                raise ValueError("decode_windows: a window takes FLAC or ADPCM, not both")
-            one = [None] * len(windows)
-            fl = ([f or a for f, a in zip(fl_h or one, ad_h or one)], [len(w) > 4 and bool(w[4]) for w in windows])
-        q = None
-        if speeds is not None:
-            if len(speeds) != len(windows):
-                raise ValueError("decode_windows: one speed per window")
-            q = [TS.quantize(v) for v in speeds]
-            if all(n == d for n, d in q):
-                q = None
-            elif rs_streams is None and sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
-                raise ValueError("decode_windows: a streamed speed goes with 24000 Hz only (resampling the scaled stream would need "
-                                 "its history and a look-ahead carried too)")
-            elif ts_streams is None or len(ts_streams) != len(windows):
-                raise ValueError("decode_windows: speeds need ts_streams, one entry per window")
-        laws = None
-        if encodings is not None:
-            if len(encodings) != len(windows):
-                raise ValueError("decode_windows: one encoding per window")
-            if any(G711.check_encoding(e) is not None for e in encodings):
-                if not pcm16:
-                    raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
-                laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
-        if lm is not None or pa is not None or cp is not None:
-            return self._decode_windows_limited(store, windows, [None] * len(windows) if lm is None else lm, q, laws, fl, pcm16, keep_thr, product,
-                                                dict(sample_rates=sample_rates, encodings=encodings, speeds=speeds, ts_streams=ts_streams,
-                                                     rs_streams=rs_streams, flac=flac, flac_streams=flac_streams, adpcm=adpcm,
-                                                     adpcm_streams=adpcm_streams), pa, cp)
-        if q is not None:
-            rates = None
-            if sample_rates is not None and any(int(r) != self.SAMPLE_RATE for r in sample_rates):
-                if len(sample_rates) != len(windows) or len(rs_streams) != len(windows):
-                    raise ValueError("decode_windows: one sample rate and one rs_streams entry per window")
-                rates = [int(r) for r in sample_rates]
-                alone = [i for i in range(len(windows)) if q[i][0] == q[i][1] and rates[i] != self.SAMPLE_RATE]
-                if alone:         # speed 1 at another rate: the stateless window path, in a pass of its own
-                    for i in alone:
-                        if ts_streams[i] is not None or rs_streams[i] is not None:
-                            raise ValueError(f"decode_windows: window {i} is at speed 1 but names a stream")
-                    rest = [i for i in range(len(windows)) if i not in set(alone)]
-                    pick = lambda v, idx: None if v is None else [v[i] for i in idx]
-                    pick2 = lambda v, idx: None if v is None else (pick(v[0], idx), pick(v[1], idx))
-                    out: list = [None] * len(windows)
-                    got = self._decode_windows_speed(store, pick(windows, rest), pick(q, rest), pick(ts_streams, rest), pcm16, keep_thr,
-                                                     product, pick(laws, rest), pick(rates, rest), pick(rs_streams, rest), pick2(fl, rest))
-                    for i, a in zip(alone, self._decode_windows_rate(store, pick(windows, alone), pick(rates, alone), pcm16, keep_thr,
-                                                                     product, pick(laws, alone), pick2(fl, alone))):
-                        out[i] = a
-                    for i, a in zip(rest, got):
-                        out[i] = a
-                    return out
-            return self._decode_windows_speed(store, windows, q, ts_streams, pcm16, keep_thr, product, laws, rates, rs_streams, fl)
-        if sample_rates is not None:
-            if len(sample_rates) != len(windows):
-                raise ValueError("decode_windows: one sample rate per window")
-            if any(int(r) != self.SAMPLE_RATE for r in sample_rates):
-                return self._decode_windows_rate(store, windows, [int(r) for r in sample_rates], pcm16, keep_thr, product, laws, fl)
-        S, cap = self._windows_store(store)
-        out: list = [None] * len(windows)
-        rows, live = [], []
-        for i, w in enumerate(windows):
-            slot, Tn, s_lo, hi, tail = self._window_fields(i, w, S, cap, keep_thr)
-            win = window_for_samples(Tn, s_lo, hi)
-            if win is None:
-                out[i] = self._empty_window(i, pcm16, laws)
-                continue
-            rows.append((slot, *win, int(tail), 0, 0))
-            live.append(i)
-        if not live:
-            return self._windows_flac_idle(fl, out)
-        tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]: slot, t_lo, t_hi, c_lo, c_hi, keep, 0, 0
-        n = (tab[:, 4] - tab[:, 3]).astype(np.int64)
-        lay = self._windows_layout(n, tab[:, 5], pcm16, laws)
-        tab_d = torch.from_numpy(tab).to(self.device)
-        cur, tail_args = self._windows_call_tail(lay, tab[:, 5], pcm16, product, keep_thr,
-                                                 self.lib.ctts_codec_windows_workspace_bytes(len(live), int((tab[:, 2] - tab[:, 1]).sum())))
-        _lib.check(self.lib.ctts_codec_decode_windows(self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap,
-                                                      tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(live), *tail_args),
-                   "ctts_codec_decode_windows")
-        tab_d.record_stream(cur)
-        return self._windows_finish(lay, n, tab[:, 5], live, laws, pcm16, out, fl)
+        ws, S, cap, free, held, laws = self._parse_windows(store, windows, pcm16, keep_thr, dict(
+            sample_rates=sample_rates, encodings=encodings, speeds=speeds, ts_streams=ts_streams, rs_streams=rs_streams, flac=flac,
+            flac_streams=flac_streams, limiter=limiter, lm_streams=lm_streams, pauses=pauses, pa_streams=pa_streams, adpcm=adpcm,
+            adpcm_streams=adpcm_streams, compress=compress, cp_streams=cp_streams))
+        out: list = [None] * len(ws)
+        companded = laws and any(w.law >= 0 for _, p in free for w in p)
+        for kind, p in free:            # the windows behind no float stage: every pass with the epilogue of its own
+            self._windows_emit(p, self._pass(kind)(store, S, cap, p, pcm16, keep_thr, product, companded), pcm16, companded, out)
+        if held:                        # the others: float chunks left on the device, the stages' rounds, one conversion, one epilogue
+            self._windows_staged(store, S, cap, held, pcm16, keep_thr, product, laws, out)
+        return out
 
-    # -- what the three paths of `decode_windows` share: the prologue (store, one window's fields, an empty result, the crops' places in the
-    # packed decode), the output layout, the tail of the C call and the epilogue.  A further variant builds its own tables between them
+    # -- what the passes of `decode_windows` share: the store, the parsing of the call into one record per window, the crops' places in the
+    # packed decode, the output layout, the tail of the C call and the epilogue.  A further pass kind builds its own tables between them
     @staticmethod
     def _windows_store(store: torch.Tensor):
         assert store.dim() == 3 and store.dtype == torch.float32 and store.is_cuda and store.size(2) == GPT.hidden and store.stride(2) == 1
         return int(store.size(0)), int(store.size(1))
 
-    @staticmethod
-    def _window_fields(i: int, w, S: int, cap: int, keep_thr: Optional[float]):
-        """window i of the list -> slot, Tn, s_lo, hi (s_hi, or the end of the prefix's decode), tail (marked as one AND a `keep_thr`
-        given: the window is stripped)"""
-        slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
-        if not (0 <= slot < S and 0 <= Tn <= cap):
-            raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
-        return slot, Tn, s_lo, VOCOS.hop * (2 * Tn - 1) if s_hi is None else int(s_hi), len(w) > 4 and bool(w[4]) and keep_thr is not None
+    def _pass(self, kind: str):
+        """the method that runs a pass of `winchain.passes`' kind"""
+        return {"plain": self._pass_plain, "rate": self._pass_rate, "speed": self._pass_speed}[kind]
 
-    @staticmethod
-    def _empty_window(i: int, pcm16: bool, laws):
-        return np.zeros((0,), np.uint8 if laws is not None and laws[i] >= 0 else np.int16 if pcm16 else np.float32)
+    def _parse_windows(self, store, windows, pcm16: bool, keep_thr, given: dict):
+        """`decode_windows`' arguments (`given`: its arguments by name), checked once -> (one `winchain.Window` per window, S, cap, the
+        free passes, the held passes, whether the call compands).  Every refusal that reads the lists is raised here, before anything is
+        launched: the stages' in the order of `winchain.CHECKED`, then the speeds', the encodings', the rates', each window's place in
+        the store and the streams of its speed (a rate the resampler does not take and a push a stream does not take are refused by
+        their planning, in front of their pass's launch).  Nothing below looks at the lists again"""
+        n_w, SR = len(windows), self.SAMPLE_RATE
+        sample_rates, encodings, speeds, ts_streams, rs_streams = (given[k] for k in ("sample_rates", "encodings", "speeds", "ts_streams", "rs_streams"))
+        tails = [len(w) > 4 and bool(w[4]) for w in windows]
+        hs = {s.name: self._window_streams(s, given[s.flag], given[s.streams], tails, sample_rates, pcm16, encodings) for s in WC.CHECKED}
+        both = [v for s, v in zip(WC.CHECKED, hs.values()) if s.kind == "int16" and v is not None]
+        if len(both) > 1 and any(f is not None and a is not None for f, a in zip(*both)):
+            raise ValueError("decode_windows: a window takes FLAC or ADPCM, not both")
+        rated = sample_rates is not None and any(int(r) != SR for r in sample_rates)
+        q = None
+        if speeds is not None:
+            if len(speeds) != n_w:
+                raise ValueError("decode_windows: one speed per window")
+            q = [tuple(TS.quantize(v)) for v in speeds]
+            if all(n == d for n, d in q):
+                q = None
+            elif rs_streams is None and rated:
+                raise ValueError("decode_windows: a streamed speed goes with 24000 Hz only (resampling the scaled stream would need "
+                                 "its history and a look-ahead carried too)")
+            elif ts_streams is None or len(ts_streams) != n_w:
+                raise ValueError("decode_windows: speeds need ts_streams, one entry per window")
+        laws = None
+        if encodings is not None:
+            if len(encodings) != n_w:
+                raise ValueError("decode_windows: one encoding per window")
+            if any(G711.check_encoding(e) is not None for e in encodings):
+                if not pcm16:
+                    raise ValueError("decode_windows: G.711 companding comes behind the 16-bit conversion (pcm16=True)")
+                laws = [-1 if e is None else G711.LAWS[e] for e in encodings]
+        if q is not None and rated and (len(sample_rates) != n_w or len(rs_streams) != n_w):
+            raise ValueError("decode_windows: one sample rate and one rs_streams entry per window")
+        if q is None and sample_rates is not None and len(sample_rates) != n_w:
+            raise ValueError("decode_windows: one sample rate per window")
+        S, cap = self._windows_store(store)
+        none, geo, hop = [None] * n_w, [], VOCOS.hop
+        for i, w in enumerate(windows):
+            slot, Tn, s_lo, s_hi = (int(w[0]), int(w[1]), int(w[2]), w[3])
+            if not (0 <= slot < S and 0 <= Tn <= cap):
+                raise ValueError(f"decode_windows: window {i} (slot {slot}, {Tn} tokens) lies outside the [{S}, {cap}] store")
+            geo.append((i, slot, Tn, s_lo, hop * (2 * Tn - 1) if s_hi is None else int(s_hi)))
+        # the records, column by column: the handles per stage in the table's order (a speed's streams as given: `_check_speed_streams`
+        # checks them below, and only a scaled window's are read), which windows stand behind a float stage, the int16 stage of each
+        cols = {"time_scale": ts_streams if q is not None else none, "resample": rs_streams if q is not None and rated else none, **hs}
+        staged, codec = [False] * n_w, none
+        for s in WC.CHECKED:
+            if hs[s.name] is not None and s.kind == "float":
+                staged = [a or h is not None for a, h in zip(staged, hs[s.name])]
+            elif hs[s.name] is not None:
+                codec = [c if h is None else (s.name, h) for c, h in zip(codec, hs[s.name])]
+        qs = [(1, 1)] * n_w if q is None else q
+        new = tuple.__new__                        # (a NamedTuple's own constructor is a Python call per window)
+        ws = [new(WC.Window, (*g, *rest)) for g, *rest in zip(
+            geo, tails, [int(r) for r in sample_rates] if rated else [SR] * n_w, qs, [a != b for a, b in qs], [-1] * n_w if laws is None else laws,
+            zip(*(cols[s.name] or none for s in WC.STAGES)), staged, codec)]
+        free, held = WC.passes(ws, q is not None, rated)
+        if q is not None:
+            for group in ([w for _, p in free for w in p], *(p for _, p in held)):
+                self._check_speed_streams(sorted(group, key=lambda w: w.i), ts_streams, rs_streams)
+        return ws, S, cap, free, held, laws is not None
+
+    def _check_speed_streams(self, group, ts_streams, rs_streams) -> None:
+        """a group that scales (`winchain.passes`): a scaled window names an open stream of its speed and, at another rate, an open
+        resampler stream to that rate, no other window names either"""
+        if not any(w.scaled for w in group):
+            return
+        SR, rated = self.SAMPLE_RATE, any(w.rate != self.SAMPLE_RATE for w in group)
+        recs = self._pool("time_scale").records
+        rs_recs = self._pool("resample").records if rated else {}
+        for w in group:
+            h, hr = ts_streams[w.i], rs_streams[w.i] if rated else None
+            if w.scaled:
+                rec = None if h is None else recs.get(int(h))
+                if rec is None or (rec.num, rec.den) != w.q:
+                    raise ValueError(f"decode_windows: window {w.i} at speed {w.q[0]}/{w.q[1]} needs an open stream of that speed")
+            elif h is not None or hr is not None:
+                raise ValueError(f"decode_windows: window {w.i} is at speed 1 but names a stream")
+            if w.scaled and w.rate != SR:
+                rec = None if hr is None else rs_recs.get(int(hr))
+                if rec is None or (rec.orig, rec.new) != (SR, w.rate):
+                    raise ValueError(f"decode_windows: window {w.i} at {w.rate} Hz needs an open resampler stream {SR} -> {w.rate}")
+            elif hr is not None:
+                raise ValueError(f"decode_windows: window {w.i} stays at {SR} Hz but names a resampler stream")
+
+    def _window_streams(self, stage, flags, streams, tails, sample_rates, pcm16: bool, encodings):
+        """The flags and streams of one streamed stage (a row of `winchain.STAGES`) of a `decode_windows` call, checked -> per window its
+        stream's handle or None; None when no window is flagged.  A float stage refuses a stream that has had its last push, before
+        the call or by a tail window earlier in it, by window; for an int16 stage the pool's `live` refuses, and the call must
+        convert to 16 bits and give a flagged window no encoding."""
+        arg, arg_streams, name, ends = stage.flag, stage.streams, stage.title, stage.kind == "float"
+        an = lambda s: ("an " if s[0] in "aA" else "a ") + s
+        if flags is None or not any((stage.any_flag or stage.flagged)(f) for f in flags):
+            if streams is not None and any(h is not None for h in streams):
+                raise ValueError(f"decode_windows: {arg_streams} without {an(arg)} flag")
+            return None
+        if len(flags) != len(tails) or streams is None or len(streams) != len(tails):
+            raise ValueError(f"decode_windows: one {arg} flag and one {arg_streams} entry per window")
+        if stage.kind == "int16":
+            if not pcm16:
+                raise ValueError(f"decode_windows: {name} comes behind the 16-bit conversion (pcm16=True)")
+            if encodings is not None and any(f and e is not None for f, e in zip(flags, encodings)):
+                raise ValueError(f"decode_windows: {arg} does not go with an encoding ({an(name)} stream holds the 16-bit samples)")
+        pool, ended, out, flagged = self._pool(stage.name), set(), [], stage.flagged
+        records, want = pool.records, self.SAMPLE_RATE
+        for i, (f, h) in enumerate(zip(flags, streams)):
+            if f is not True and not flagged(f):
+                if h is not None:
+                    raise ValueError(f"decode_windows: window {i} has no {arg} flag but names {an(name)} stream")
+                out.append(None)
+                continue
+            if sample_rates is not None:
+                want = int(sample_rates[i])
+            rec = None if h is None else records.get(int(h)) if ends else pool.live(h)
+            if rec is None or rec.rate != want:
+                raise ValueError(f"decode_windows: window {i} needs an open {name} stream at {want} Hz")
+            h = int(h)
+            if ends:
+                if rec.done or h in ended:
+                    raise ValueError(f"decode_windows: window {i}: {name} stream {h} has had its last push")
+                if tails[i]:
+                    ended.add(h)
+            out.append(h)
+        return out
 
     @staticmethod
     def _packed_crops(tab: np.ndarray):
@@ -2902,174 +2941,101 @@ class CodecEngine:
         return cur, (1 if pcm16 else 0, buf.data_ptr(), buf.data_ptr() + n_out + n_g if keep.any() else None, {"f64": 0, "f32": 1}[product],
                      float(keep_thr or 0.0), ws.data_ptr(), nws, cur.cuda_stream)
 
-    def _windows_finish(self, lay, n, keep, live, laws, pcm16: bool, out: list, fl=None) -> list:
-        off, n_out, n_g, n_keep, buf = lay
-        sink = self.__dict__.get("_lm_sink")
-        if sink is not None:          # `_decode_windows_limited` takes the float chunks where they lie: nothing is converted or copied
-            sink.append((buf[:n_out].view(torch.float32), off, n, list(live)))
-            return out
-        return self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, off, n, keep, live, None if laws is None else [laws[i] for i in live],
-                                     np.int16 if pcm16 else np.float32, out, fl)
+    def _windows_emit(self, ws, chunks, pcm16: bool, companded: bool, out: list) -> None:
+        """the epilogue of one pass over the windows `ws`: its chunks (what a `_pass_*` hands back, or None: no window had a sample)
+        to the host -- `_windows_to_host`, the FLAC / ADPCM pushes of these windows with it -- and into the call's `out`"""
+        mine: list = [None] * len(ws)
+        if chunks is None or len(chunks[3]) < len(ws):      # the windows without a chunk come back empty
+            has = set() if chunks is None else set(chunks[3])
+            mine = [None if k in has else np.zeros((0,), np.uint8 if companded and w.law >= 0 else np.int16 if pcm16 else np.float32) for k, w in enumerate(ws)]
+        fl = ([w.codec for w in ws], [w.tail for w in ws]) if any(w.codec for w in ws) else None
+        if chunks is None:              # no window has a sample: the flagged ones still step their streams (a tail brings what its stream held)
+            idle = [k for k, w in enumerate(ws) if w.codec]
+            if idle:
+                mine = self._flac_rounds(torch.zeros((8,), dtype=torch.int16, device=self.device), None, idle, [(fl[0][k], 0, 0, fl[1][k]) for k in idle], mine)
+        else:
+            (off, n_out, n_g, n_keep, buf), n, keep, live = chunks
+            mine = self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, off, n, keep, live, [ws[k].law for k in live] if companded else None,
+                                         np.int16 if pcm16 else np.float32, mine, fl)
+        for w, a in zip(ws, mine):
+            out[w.i] = a
 
-    def _decode_windows_limited(self, store: torch.Tensor, windows, lm, q, laws, fl, pcm16: bool, keep_thr: Optional[float], product: str,
-                                per_window: dict, pa=None, cp=None) -> list:
-        """`decode_windows` with at least one window behind a limiter stream, a pause stream or a compressor stream (lm, pa, cp: the
-        windows' handles or None; q, laws, fl: the call's checked speeds, laws and FLAC streams; per_window: its per-window
-        arguments, to be cut for the passes)"""
-        pick = lambda v, ix: None if v is None else [v[i] for i in ix]
-        pa = [None] * len(windows) if pa is None else pa
-        cp = [None] * len(windows) if cp is None else cp
-        idx = [i for i in range(len(windows)) if lm[i] is not None or pa[i] is not None or cp[i] is not None]
-        rest = [i for i in range(len(windows)) if lm[i] is None and pa[i] is None and cp[i] is None]
-        out: list = [None] * len(windows)
-        if rest:                                                   # the unflagged windows: the call without the limiter
-            for i, a in zip(rest, self.decode_windows(store, pick(windows, rest), pcm16, keep_thr, product,
-                                                      **{k: pick(v, rest) for k, v in per_window.items()})):
-                out[i] = a
-        # the float chunks of the flagged windows, left on the device: the scaled windows in one pass, the others in another
-        scaled = [i for i in idx if q is not None and q[i][0] != q[i][1]]
-        plain = [i for i in idx if i not in set(scaled)]
+    def _stage_rounds(self, stage, ws, x: torch.Tensor, src: dict) -> torch.Tensor:
+        """the steps of one float stage over the held windows `ws`: the r-th push of a stream goes to round r, in the order given; what
+        a step emits lies behind x, and `src` (window -> first sample, samples) then names it there"""
+        at = WC.PLACE[stage.name]
+        _, rounds = SP.rounds(w.h[at] for w in ws)
+        if not rounds:
+            return x
+        parts, base = [x], x.numel()
+        for rnd in rounds:
+            y, o = getattr(self, stage.step)(x, [(ws[k].h[at], *src.get(ws[k].i, (0, 0)), ws[k].tail) for k in rnd])
+            for j, k in enumerate(rnd):
+                src[ws[k].i] = (base + int(o[j]), int(o[j + 1] - o[j]))
+            parts.append(y)
+            base += y.numel()
+        return torch.cat(parts)
+
+    def _windows_staged(self, store: torch.Tensor, S: int, cap: int, held, pcm16: bool, keep_thr: Optional[float], product: str, companded: bool,
+                        out: list) -> None:
+        """the windows behind a limiter stream, a pause stream or a compressor stream (`held`: their passes): the float chunks of the
+        passes stay on the device, end to end; the stages of `winchain.ROUNDS` step round by round, then the limiter; one conversion"""
+        ws = held[0][1] if len(held) == 1 else sorted((w for _, p in held for w in p), key=lambda w: w.i)      # in the call's order
         src, bufs, base = {}, [], 0                                # window -> (first sample, samples) in the passes' chunks, end to end
-        sink = self._lm_sink = []
-        try:
-            for ix in (scaled, plain):
-                if not ix:
-                    continue
-                del sink[:]
-                self.decode_windows(store, pick(windows, ix), False, None, product, sample_rates=pick(per_window["sample_rates"], ix),
-                                    speeds=pick(per_window["speeds"], ix), ts_streams=pick(per_window["ts_streams"], ix),
-                                    rs_streams=pick(per_window["rs_streams"], ix))
-                if sink:                                           # none: no window of the pass had a sample
-                    fbuf, off, n, live = sink[0]
-                    for k, j in enumerate(live):
-                        src[ix[j]] = (base + int(off[k]), int(n[k]))
-                    bufs.append(fbuf)
-                    base += fbuf.numel()
-        finally:
-            del self._lm_sink
+        for kind, p in held:
+            got = self._pass(kind)(store, S, cap, p, False, None, product, False)
+            if got is not None:                                    # None: no window of the pass had a sample
+                (off, n_out, _, _, buf), n, _, live = got
+                for k, j in enumerate(live):
+                    src[p[j].i] = (base + int(off[k]), int(n[k]))
+                bufs.append(buf[:n_out].view(torch.float32))
+                base += bufs[-1].numel()
         x = torch.cat(bufs) if len(bufs) > 1 else bufs[0] if bufs else torch.zeros((8,), dtype=torch.float32, device=self.device)
-        tails = [len(windows[i]) > 4 and bool(windows[i][4]) for i in idx]
-        # the pause streams' steps, in front of the limiter's: the r-th window of a stream in round r; what a step emits lies behind x
-        _, prounds = SP.rounds(pa[i] for i in idx)
-        if prounds:
-            parts, base = [x], x.numel()
-            for rnd in prounds:
-                y, o = self.trim_pauses_stream_step(x, [(pa[idx[k]], *src.get(idx[k], (0, 0)), tails[k]) for k in rnd])
-                for j, k in enumerate(rnd):
-                    src[idx[k]] = (base + int(o[j]), int(o[j + 1] - o[j]))
-                parts.append(y)
-                base += y.numel()
-            x = torch.cat(parts)
-        # the compressor streams' steps, behind the pauses' and in front of the limiter's, by the same rule; a step emits into a tensor of
-        # its own, which goes behind x
-        _, crounds = SP.rounds(cp[i] for i in idx)
-        if crounds:
-            parts, base = [x], x.numel()
-            for rnd in crounds:
-                y, o = self.compress_stream_step(x, [(cp[idx[k]], *src.get(idx[k], (0, 0)), tails[k]) for k in rnd])
-                for j, k in enumerate(rnd):
-                    src[idx[k]] = (base + int(o[j]), int(o[j + 1] - o[j]))
-                parts.append(y)
-                base += y.numel()
-            x = torch.cat(parts)
+        for stage in WC.ROUNDS:
+            x = self._stage_rounds(stage, ws, x, src)
         # the limiter's steps: the r-th window of a stream in round r; the limited chunks start on multiples of 8 samples, zeros between
+        lm = [w.h[WC.PLACE["limiter"]] for w in ws]
+        tails = [w.tail for w in ws]
         recs, shadow = self._pool("limiter").records, {}
-        _, rounds = SP.rounds(lm[i] for i in idx)
-        n = np.zeros(len(idx), np.int64)
-        for k, i in enumerate(idx):
-            if lm[i] is None:                                      # paused or compressed only: the chunk goes on as it came out
-                n[k] = src.get(i, (0, 0))[1]
+        _, rounds = SP.rounds(lm)
+        n = np.zeros(len(ws), np.int64)
+        for k, w in enumerate(ws):
+            if lm[k] is None:                                      # paused or compressed only: the chunk goes on as it came out
+                n[k] = src.get(w.i, (0, 0))[1]
                 continue
-            rec = shadow.get(lm[i], recs[lm[i]])
-            p = LM.stream_plan(rec.rate // 100, rec.pushed, rec.emitted, src.get(i, (0, 0))[1], tails[k])
+            rec = shadow.get(lm[k], recs[lm[k]])
+            p = LM.stream_plan(rec.rate // 100, rec.pushed, rec.emitted, src.get(w.i, (0, 0))[1], tails[k])
             n[k] = p["n_out"]
-            shadow[lm[i]] = rec._replace(pushed=p["total"], emitted=p["emitted"])
+            shadow[lm[k]] = rec._replace(pushed=p["total"], emitted=p["emitted"])
         keep = np.array([t and keep_thr is not None for t in tails], dtype=bool)
-        off = np.zeros(len(idx) + 1, np.int64)
+        off = np.zeros(len(ws) + 1, np.int64)
         np.cumsum((n + 7) // 8 * 8, out=off[1:])
         lim = torch.zeros((max(8, int(off[-1])),), dtype=torch.float32, device=self.device)
         for rnd in rounds:
-            self.peak_limit_stream_step(x, [(lm[idx[k]], *src.get(idx[k], (0, 0)), tails[k]) for k in rnd], out=lim, out_off=[int(off[k]) for k in rnd])
-        for k, i in enumerate(idx):
-            if lm[i] is None and n[k]:
-                lim[int(off[k]): int(off[k]) + int(n[k])] = x[src[i][0]: src[i][0] + int(n[k])]
-        live = [k for k in range(len(idx)) if n[k] > 0]
-        for k in range(len(idx)):
-            if n[k] == 0:
-                out[idx[k]] = self._empty_window(idx[k], pcm16, laws)
-        fl_sub = None if fl is None else ([h if i in set(idx) else None for i, h in enumerate(fl[0])], fl[1])
+            self.peak_limit_stream_step(x, [(lm[k], *src.get(ws[k].i, (0, 0)), tails[k]) for k in rnd], out=lim, out_off=[int(off[k]) for k in rnd])
+        for k, w in enumerate(ws):
+            if lm[k] is None and n[k]:
+                lim[int(off[k]): int(off[k]) + int(n[k])] = x[src[w.i][0]: src[w.i][0] + int(n[k])]
+        live = [k for k in range(len(ws)) if n[k] > 0]
         if not pcm16:
             host = self.to_host(lim)
-            for k in live:
+            for k, w in enumerate(ws):
                 a = host[int(off[k]): int(off[k]) + int(n[k])]
-                out[idx[k]] = a[np.abs(a) > keep_thr] if keep[k] else a
-            return out
-        if not live:
-            return self._windows_flac_idle(fl_sub, out)
-        # the conversion: every limited chunk with its zero pad is a segment of ctts_float_to_int16_ragged -- the pad changes no peak, and
-        # the segments' samples, codes and keep masks then lie where `_windows_to_host` expects those of a window entry
-        n_l, keep_l, laws_l = n[live], keep[live], None if laws is None else [laws[idx[k]] for k in live]
-        o, n_out, n_g, n_keep, buf = self._windows_layout(n_l, keep_l, True, laws)
-        masks = buf[n_out + n_g: n_out + n_g + int(o[-1]) // 8] if keep_l.any() else None
-        self.float_to_int16_ragged(lim[: int(o[-1])], o, product, keep_thr if keep_l.any() else None, out=(buf[:n_out].view(torch.int16), masks))
-        return self._windows_to_host(buf[: n_out + n_g + n_keep], n_out, n_g, o, n_l, keep_l, [idx[k] for k in live], laws_l, np.int16, out, fl_sub)
-
-    def _windows_flac_idle(self, fl, out: list) -> list:
-        """a call none of whose windows has a sample: the flagged ones still step their streams (a tail ends its stream and brings
-        what the stream held)"""
-        if fl is not None:
-            idle = [i for i, h in enumerate(fl[0]) if h is not None]
-            out[:] = [a for a in self._flac_rounds(torch.zeros((8,), dtype=torch.int16, device=self.device), None, idle,
-                                                   [(fl[0][i], 0, 0, fl[1][i]) for i in idle], out)]
-        return out
-
-    def _window_streams(self, arg: str, arg_streams: str, name: str, flags, streams, windows, sample_rates, flagged=bool, any_flag=None,
-                        ends: bool = True, also=None):
-        """The flags and streams of one streamed stage of a `decode_windows` call, checked -> per window its stream's handle or None;
-        None when no window is flagged.  `arg` (the stage's pool has that label) / `arg_streams`: the two arguments' names; `name`:
-        what the messages call the stream.  `flagged`: what makes a window flagged (`any_flag`, where it differs: what makes the call
-        look at the flags at all).  `ends`: a stream that has had its last push, before the call or by a tail window earlier in it,
-        is refused here, by window; without it the pool's `live` refuses.  `also`: further checks of a call with a flagged window."""
-        an = lambda s: ("an " if s[0] in "aA" else "a ") + s
-        if flags is None or not any((any_flag or flagged)(f) for f in flags):
-            if streams is not None and any(h is not None for h in streams):
-                raise ValueError(f"decode_windows: {arg_streams} without {an(arg)} flag")
-            return None
-        if len(flags) != len(windows) or streams is None or len(streams) != len(windows):
-            raise ValueError(f"decode_windows: one {arg} flag and one {arg_streams} entry per window")
-        if also is not None:
-            also()
-        pool, ended, out = self._pool(arg), set(), []
-        for i, (f, h) in enumerate(zip(flags, streams)):
-            if not flagged(f):
-                if h is not None:
-                    raise ValueError(f"decode_windows: window {i} has no {arg} flag but names {an(name)} stream")
-                out.append(None)
-                continue
-            want = self.SAMPLE_RATE if sample_rates is None else int(sample_rates[i])
-            rec = None if h is None else pool.records.get(int(h)) if ends else pool.live(h)
-            if rec is None or rec.rate != want:
-                raise ValueError(f"decode_windows: window {i} needs an open {name} stream at {want} Hz")
-            if ends:
-                if rec.done or int(h) in ended:
-                    raise ValueError(f"decode_windows: window {i}: {name} stream {int(h)} has had its last push")
-                if len(windows[i]) > 4 and bool(windows[i][4]):
-                    ended.add(int(h))
-            out.append(int(h))
-        return out
-
-    def _window_codec(self, arg: str, name: str, flags, streams, windows, pcm16: bool, sample_rates, encodings):
-        """`_window_streams` for an output format (`arg` / `name`: flac / FLAC, adpcm / ADPCM) -> per window (arg, handle) or None"""
-        def also():
-            if not pcm16:
-                raise ValueError(f"decode_windows: {name} comes behind the 16-bit conversion (pcm16=True)")
-            if encodings is not None and any(f and e is not None for f, e in zip(flags, encodings)):
-                raise ValueError(f"decode_windows: {arg} does not go with an encoding ({'an' if arg[0] == 'a' else 'a'} {name} stream holds the 16-bit samples)")
-        got = self._window_streams(arg, arg + "_streams", name, flags, streams, windows, sample_rates, ends=False, also=also)
-        return None if got is None else [None if h is None else (arg, h) for h in got]
+                out[w.i] = a[np.abs(a) > keep_thr] if keep[k] and n[k] else a
+            return
+        chunks = None
+        if live:
+            # the conversion: every limited chunk with its zero pad is a segment of ctts_float_to_int16_ragged -- the pad changes no peak, and
+            # the segments' samples, codes and keep masks then lie where `_windows_to_host` expects those of a window entry
+            n_l, keep_l = n[live], keep[live]
+            lay = o, n_out, n_g, _, buf = self._windows_layout(n_l, keep_l, True, [] if companded else None)
+            masks = buf[n_out + n_g: n_out + n_g + int(o[-1]) // 8] if keep_l.any() else None
+            self.float_to_int16_ragged(lim[: int(o[-1])], o, product, keep_thr if keep_l.any() else None, out=(buf[:n_out].view(torch.int16), masks))
+            chunks = lay, n_l, keep_l, live
+        self._windows_emit(ws, chunks, True, companded, out)
 
     def _flac_rounds(self, pcm: torch.Tensor, masks, idx, pushes, out: list) -> list:
-        """pushes[j] is window idx[j]'s, its stream an (arg, handle) of `_window_codec`: ONE `flac_stream_step` and ONE
+        """pushes[j] is window idx[j]'s, its stream the (stage, handle) of the window's record: ONE `flac_stream_step` and ONE
         `adpcm_stream_step` (each for its own windows) when no stream is named twice, else the r-th push of a stream goes to step r,
         in the order given; -> `out` with the windows' chunks in place"""
         out = list(out)
@@ -3082,50 +3048,48 @@ class CodecEngine:
                         out[i] = c
         return out
 
-    def _decode_windows_speed(self, store: torch.Tensor, windows, q, ts_streams, pcm16: bool, keep_thr: Optional[float], product: str,
-                              laws=None, rates=None, rs_streams=None, fl=None):
-        """`decode_windows` with at least one window at another speed than 1 (q: the windows' (num, den)).  `rates` (None: all 24000)
-        with `rs_streams`: the scaled windows that also leave 24 kHz, each with its resampler stream"""
-        S, cap = self._windows_store(store)
-        out: list = [None] * len(windows)
-        recs = self._pool("time_scale").records
-        rs_recs = self._pool("resample").records if rates is not None else {}
-        rows, conv, pushes = [], [], []     # decode windows; (window, decode row or None, push or None, keep); stream pushes
+    def _pass_plain(self, store: torch.Tensor, S: int, cap: int, ws, pcm16: bool, keep_thr: Optional[float], product: str, companded: bool):
+        """One decoder pass over the windows `ws`, every one at speed 1 and 24 kHz (ctts_codec_decode_windows) -> the chunks where they
+        lie on the device: (the output's layout `_windows_layout`, the chunks' lengths, their keep flags, live: the places in `ws` of
+        the windows that have a chunk); None when no window has a sample.  `_pass_rate` and `_pass_speed` hand back the same"""
+        rows, live = [], []
+        for k, w in enumerate(ws):
+            win = window_for_samples(w.Tn, w.s_lo, w.hi)
+            if win is not None:
+                rows.append((w.slot, *win, int(w.tail and keep_thr is not None), 0, 0))
+                live.append(k)
+        if not live:
+            return None
+        tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]: slot, t_lo, t_hi, c_lo, c_hi, keep, 0, 0
+        n = (tab[:, 4] - tab[:, 3]).astype(np.int64)
+        lay = self._windows_layout(n, tab[:, 5], pcm16, [] if companded else None)
+        tab_d = torch.from_numpy(tab).to(self.device)
+        cur, tail_args = self._windows_call_tail(lay, tab[:, 5], pcm16, product, keep_thr,
+                                                 self.lib.ctts_codec_windows_workspace_bytes(len(live), int((tab[:, 2] - tab[:, 1]).sum())))
+        _lib.check(self.lib.ctts_codec_decode_windows(self.handle, store.data_ptr(), int(store.stride(0)), int(store.stride(1)), S, cap,
+                                                      tab_d.data_ptr(), tab.ctypes.data_as(C.c_void_p), len(live), *tail_args),
+                   "ctts_codec_decode_windows")
+        tab_d.record_stream(cur)
+        return lay, n, tab[:, 5], live
+
+    def _pass_speed(self, store: torch.Tensor, S: int, cap: int, ws, pcm16: bool, keep_thr: Optional[float], product: str, companded: bool):
+        """`_pass_plain` for windows of which at least one is at another speed than 1: a scaled window pushes its crop into its
+        time-scale stream and, at another rate, what that emits into its resampler stream (ctts_codec_decode_windows_speed /
+        _speed_rate); an empty crop still steps its streams.  The windows at speed 1 are at 24 kHz"""
+        rows, conv, pushes = [], [], []     # decode windows; (place in ws, decode row or None, push or None, keep); stream pushes
         push_rs = []                        # per push: the resampler stream its chunk goes on into, or None
-        for i, w in enumerate(windows):
-            slot, Tn, s_lo, hi, keep = self._window_fields(i, w, S, cap, keep_thr)
-            last = len(w) > 4 and bool(w[4])               # ends the stream, with or without a `keep_thr`
-            scaled = q[i][0] != q[i][1]
-            if scaled:
-                h = ts_streams[i]
-                rec = None if h is None else recs.get(int(h))
-                if rec is None or (rec.num, rec.den) != tuple(q[i]):
-                    raise ValueError(f"decode_windows: window {i} at speed {q[i][0]}/{q[i][1]} needs an open stream of that speed")
-            elif ts_streams[i] is not None or (rates is not None and rs_streams[i] is not None):
-                raise ValueError(f"decode_windows: window {i} is at speed 1 but names a stream")
-            hr = None
-            if rates is not None and scaled and rates[i] != self.SAMPLE_RATE:
-                hr = rs_streams[i]
-                rec = None if hr is None else rs_recs.get(int(hr))
-                if rec is None or (rec.orig, rec.new) != (self.SAMPLE_RATE, rates[i]):
-                    raise ValueError(f"decode_windows: window {i} at {rates[i]} Hz needs an open resampler stream {self.SAMPLE_RATE} -> {rates[i]}")
-                hr = int(hr)
-            elif rates is not None and rs_streams[i] is not None:
-                raise ValueError(f"decode_windows: window {i} stays at {self.SAMPLE_RATE} Hz but names a resampler stream")
-            elif rates is not None and rates[i] != self.SAMPLE_RATE:
-                raise ValueError(f"decode_windows: window {i} at speed 1 and {rates[i]} Hz takes the stateless window path")
-            win = window_for_samples(Tn, s_lo, hi)
-            if win is None and not scaled:
-                out[i] = self._empty_window(i, pcm16, laws)
+        for j, w in enumerate(ws):
+            win = window_for_samples(w.Tn, w.s_lo, w.hi)
+            if win is None and not w.scaled:
                 continue
             k = None
             if win is not None:
                 k = len(rows)
-                rows.append((slot, *win, 0, 0, 0))
-            if scaled:
-                pushes.append([int(ts_streams[i]), k, 0, last])
-                push_rs.append(hr)
-            conv.append((i, k, len(pushes) - 1 if scaled else None, int(keep)))
+                rows.append((w.slot, *win, 0, 0, 0))
+            if w.scaled:
+                pushes.append([int(w.h[WC.PLACE["time_scale"]]), k, 0, w.tail])
+                push_rs.append(int(w.h[WC.PLACE["resample"]]) if w.rate != self.SAMPLE_RATE else None)
+            conv.append((j, k, len(pushes) - 1 if w.scaled else None, int(w.tail and keep_thr is not None)))
         tab = np.ascontiguousarray(np.array(rows, dtype=np.int32).reshape(-1, 8))       # ctts_window[n_win]: what is decoded
         tok, start = self._packed_crops(tab)
         width = (tab[:, 4] - tab[:, 3]).astype(np.int64)
@@ -3165,7 +3129,7 @@ class CodecEngine:
                 rs_of_ts[rank[pi]] = r
                 chunk += m + (-m % 8)
         n = np.where(rtab["rate"] >= 0, rtab["o_hi"], rtab["n_in"]).astype(np.int64)
-        lay = self._windows_layout(n, ctab[:, 5], pcm16, laws)
+        lay = self._windows_layout(n, ctab[:, 5], pcm16, [] if companded else None)
         parts = [tab.view(np.uint8).reshape(-1), ctab.view(np.uint8).reshape(-1), rtab.view(np.uint8), ts.view(np.uint8)]
         if staged:
             parts.append(rs.view(np.uint8))
@@ -3200,7 +3164,7 @@ class CodecEngine:
         pool.commit(commit)
         if staged:
             rs_pool.commit(rs_commit)
-        return self._windows_finish(lay, n, ctab[:, 5], [c[0] for c in conv], laws, pcm16, out, fl)
+        return lay, n, ctab[:, 5], [c[0] for c in conv]
 
     def _windows_to_host(self, buf: torch.Tensor, n_out: int, n_g: int, off, n, keep, live, laws, dt, out: list, fl=None) -> list:
         """the end of `decode_windows`: `buf` = samples (n_out bytes) | companded bytes (n_g, 0 without `laws`) | keep masks.  The
@@ -3583,37 +3547,33 @@ class CodecEngine:
             res.append(blob[b0: b0 + size])
         return res
 
-    def _decode_windows_rate(self, store: torch.Tensor, windows, rates, pcm16: bool, keep_thr: Optional[float], product: str, laws=None,
-                             fl=None):
-        """`decode_windows` with at least one window at another rate than 24 kHz"""
-        S, cap = self._windows_store(store)
-        out: list = [None] * len(windows)
+    def _pass_rate(self, store: torch.Tensor, S: int, cap: int, ws, pcm16: bool, keep_thr: Optional[float], product: str, companded: bool):
+        """`_pass_plain` for windows at speed 1 of which at least one is at another rate than 24 kHz: the stateless window path
+        (ctts_codec_decode_windows_rate)"""
         plans, pairs = {}, {}              # rate -> (L, M, K); rate -> (index, L, M, K) once a window at it has samples
         rows, res, live = [], [], []
-        for i, (w, r) in enumerate(zip(windows, rates)):
-            slot, Tn, s_lo, hi, tail = self._window_fields(i, w, S, cap, keep_thr)
-            total = VOCOS.hop * (2 * Tn - 1)
+        for k, w in enumerate(ws):
+            r, hi, total = w.rate, w.hi, VOCOS.hop * (2 * w.Tn - 1)
             if r == self.SAMPLE_RATE:
-                win, rs = window_for_samples(Tn, s_lo, hi), None
+                win, rs = window_for_samples(w.Tn, w.s_lo, hi), None
             else:
                 if r not in plans:
                     plans[r] = RS.plan(self.SAMPLE_RATE, r, [0, 1])[:3]        # every refusal before the launch
                 L, M, K = plans[r]
-                lo, hi = max(0, int(s_lo)), min(total, hi)
+                lo, hi = max(0, w.s_lo), min(total, hi)
                 o_lo, o_hi = (RS.out_len(lo, L, M), RS.out_len(hi, L, M)) if hi > lo else (0, 0)
                 win = None
                 if o_hi > o_lo:
                     a, b = RS.window_inputs(L, M, K, o_lo, o_hi, total)
                     q = pairs.setdefault(r, (len(pairs), L, M, K))[0]
-                    win, rs = window_for_samples(Tn, a, b), (q, a, total, o_lo, o_hi)
+                    win, rs = window_for_samples(w.Tn, a, b), (q, a, total, o_lo, o_hi)
             if win is None:
-                out[i] = self._empty_window(i, pcm16, laws)
                 continue
-            rows.append((slot, *win, int(tail), 0, 0))
+            rows.append((w.slot, *win, int(w.tail and keep_thr is not None), 0, 0))
             res.append(rs)
-            live.append(i)
+            live.append(k)
         if not live:
-            return self._windows_flac_idle(fl, out)
+            return None
         tab = np.ascontiguousarray(np.array(rows, dtype=np.int32))          # ctts_window[n]
         tok, start = self._packed_crops(tab)
         rtab = np.zeros(len(live), _lib.RS_WINDOW)                           # ctts_rs_window[n]
@@ -3629,7 +3589,7 @@ class CodecEngine:
                 chunk += m + (-m % 8)
         sel = np.array([k for q in range(len(pairs)) for k, rs in enumerate(res) if rs is not None and rs[0] == q], dtype=np.int32)
         n = np.where(rtab["rate"] >= 0, rtab["o_hi"] - rtab["o_lo"], rtab["n_in"]).astype(np.int64)
-        lay = self._windows_layout(n, tab[:, 5], pcm16, laws)
+        lay = self._windows_layout(n, tab[:, 5], pcm16, [] if companded else None)
         blob = np.concatenate([tab.view(np.uint8).reshape(-1), rtab.view(np.uint8), sel.view(np.uint8)])
         blob_d = torch.from_numpy(blob).to(self.device)                      # one upload: both tables and the selection
         by_q = sorted(pairs.items(), key=lambda kv: kv[1][0])
@@ -3644,7 +3604,7 @@ class CodecEngine:
             base + tab.nbytes, rtab.ctypes.data_as(C.c_void_p), base + tab.nbytes + rtab.nbytes, sel.ctypes.data_as(C.c_void_p), len(live),
             C.cast(rate_tab, C.c_void_p), len(by_q), *tail_args), "ctts_codec_decode_windows_rate")
         blob_d.record_stream(cur)
-        return self._windows_finish(lay, n, tab[:, 5], live, laws, pcm16, out, fl)
+        return lay, n, tab[:, 5], live
 
     def to_host(self, t: torch.Tensor) -> np.ndarray:
         """device tensor -> numpy, the `.cpu().numpy()` that ends the reference path (core.py:508-510), through a cached PINNED

@@ -54,6 +54,7 @@ from ._sync import wait_event, wait_stream
 from .config import GPT
 from .engine import GptEngine, gen_logits, plan_from_processors
 from .outchain import option_kw
+from .winchain import STAGES, StreamSet
 from .rng import ExpDraws, penalty_table
 
 
@@ -666,21 +667,15 @@ class _Job:
     code_text: Optional[str] = None        # the text of the code stage: normalised, with `refine` then refined
     in_text_pool: bool = False             # the refine-text pass of an unsplit request is queued or resident
     speed: Optional[float] = None          # None: 1.0 (on a stream only with SpeechBatcher(stream_speeds=True))
-    ts_slot: Optional[int] = None          # a stream at another speed: its stream of the time scaler, opened at its first chunk
-    rs_slot: Optional[int] = None          # ... and at another rate: its stream of the resampler, opened with it
     flac: bool = False                     # the result is the FLAC file of the int16 waveform; a stream: its chunks are FLAC frames
-    flac_slot: Optional[int] = None        # a FLAC stream: its stream of the encoder, opened at its first chunk
     adpcm: bool = False                    # the result is the IMA ADPCM WAV file of the int16 waveform; a stream: its chunks are ADPCM blocks
-    adpcm_slot: Optional[int] = None       # an ADPCM stream: its stream of the encoder, opened at its first chunk
     loudness: Optional[float] = None       # a target in LUFS (non-streamed only); None: the level is left alone
     pauses: object = None                  # a pauses.PauseSpec (non-streamed only); None: the silence is left alone
     limiter: bool = False                  # the look-ahead peak limiter behind the loudness stage's gain; a stream: in front of the conversion
-    lm_slot: Optional[int] = None          # a limited stream: its stream of the limiter, opened at its first chunk
-    pa_slot: Optional[int] = None          # a paused stream: its pause stream, opened at its first chunk
     lm_gain: Optional[float] = None        # ... and the float32 pre-gain of its `gain_db` (None: 1)
     compress: object = None                # a checked compressor spec; None: the dynamics are left alone
-    cp_slot: Optional[int] = None          # a compressed stream: its compressor stream, opened at its first chunk
     eq: object = None                      # a checked equaliser spec (non-streamed only); None: the spectrum is left alone
+    streams: Optional[StreamSet] = None    # a stream: the streams of its stages (winchain.STAGES), opened at its first chunk
 
     @property
     def is_stream(self) -> bool:
@@ -1121,27 +1116,8 @@ class SpeechBatcher:
                 self._sub.pop(k, None)
         if self._jobs.pop(job.rid, None) is None:
             return
-        if job.ts_slot is not None:        # finished, failed or cancelled: its stream of the time scaler goes back to the pool
-            slot, job.ts_slot = job.ts_slot, None
-            self.chat.codec.time_scale_stream_close(slot)
-        if job.rs_slot is not None:        # ... and its stream of the resampler
-            slot, job.rs_slot = job.rs_slot, None
-            self.chat.codec.resample_stream_close(slot)
-        if job.flac_slot is not None:      # ... and its stream of the FLAC encoder
-            slot, job.flac_slot = job.flac_slot, None
-            self.chat.codec.flac_stream_close(slot)
-        if job.adpcm_slot is not None:     # ... and its stream of the ADPCM encoder
-            slot, job.adpcm_slot = job.adpcm_slot, None
-            self.chat.codec.adpcm_stream_close(slot)
-        if job.lm_slot is not None:        # ... and its stream of the limiter
-            slot, job.lm_slot = job.lm_slot, None
-            self.chat.codec.peak_limit_stream_close(slot)
-        if job.pa_slot is not None:        # ... and its pause stream
-            slot, job.pa_slot = job.pa_slot, None
-            self.chat.codec.trim_pauses_stream_close(slot)
-        if job.cp_slot is not None:        # ... and its compressor stream
-            slot, job.cp_slot = job.cp_slot, None
-            self.chat.codec.compress_stream_close(slot)
+        if job.streams:                    # finished, failed or cancelled: the streams of its stages go back to their pools
+            job.streams.close(self.chat.codec)
         failed = isinstance(result, BaseException)
         if cancelled:
             self.cancelled += job.is_stream
@@ -1381,47 +1357,17 @@ class SpeechBatcher:
             self.stream_resampled_chunks += sum(j.sample_rate is not None for j in jobs)
             self.companded += sum(j.encoding is not None for j in jobs)
             kw = _format_kw(jobs, "sample_rates", "encodings", "speeds")
-            if "speeds" in kw:
-                self.stream_scaled_chunks += sum(j.speed is not None for j in jobs)
-                for j in jobs:
-                    if j.speed is not None and j.ts_slot is None:
-                        j.ts_slot = self.chat.codec.time_scale_stream_open(j.speed)
-                    if j.speed is not None and j.sample_rate is not None and j.rs_slot is None:
-                        j.rs_slot = self.chat.codec.resample_stream_open(24000, j.sample_rate)
-                kw["ts_streams"] = [j.ts_slot for j in jobs]
-                if any(j.rs_slot is not None for j in jobs):
-                    kw["rs_streams"] = [j.rs_slot for j in jobs]
-            if "flac" in kw:              # the FLAC streams due at this poll: one encoder step behind the one decode
-                self.stream_flac_chunks += sum(j.flac for j in jobs)
-                for j in jobs:
-                    if j.flac and j.flac_slot is None:
-                        j.flac_slot = self.chat.codec.flac_stream_open(24000 if j.sample_rate is None else j.sample_rate)
-                kw["flac_streams"] = [j.flac_slot for j in jobs]
-            if "adpcm" in kw:             # the ADPCM streams due at this poll: likewise
-                self.stream_adpcm_chunks += sum(j.adpcm for j in jobs)
-                for j in jobs:
-                    if j.adpcm and j.adpcm_slot is None:
-                        j.adpcm_slot = self.chat.codec.adpcm_stream_open(24000 if j.sample_rate is None else j.sample_rate)
-                kw["adpcm_streams"] = [j.adpcm_slot for j in jobs]
-            if "limiter" in kw:           # the limiter streams due at this poll: one step per round behind their decode
-                self.stream_limited_chunks += sum(j.limiter for j in jobs)
-                for j in jobs:
-                    if j.limiter and j.lm_slot is None:
-                        j.lm_slot = self.chat.codec.peak_limit_stream_open(24000 if j.sample_rate is None else j.sample_rate,
-                                                                           1.0 if j.lm_gain is None else j.lm_gain)
-                kw["lm_streams"] = [j.lm_slot for j in jobs]
-            if "pauses" in kw:            # the pause streams due at this poll: one step per round in front of the limiter's
-                self.stream_paused_chunks += sum(j.pauses is not None for j in jobs)
-                for j in jobs:
-                    if j.pauses is not None and j.pa_slot is None:
-                        j.pa_slot = self.chat.codec.trim_pauses_stream_open(24000 if j.sample_rate is None else j.sample_rate, j.pauses)
-                kw["pa_streams"] = [j.pa_slot for j in jobs]
-            if "compress" in kw:          # the compressor streams due at this poll: one step per round behind the pauses', in front of the limiter's
-                self.stream_compressed_chunks += sum(j.compress is not None for j in jobs)
-                for j in jobs:
-                    if j.compress is not None and j.cp_slot is None:
-                        j.cp_slot = self.chat.codec.compress_stream_open(24000 if j.sample_rate is None else j.sample_rate, j.compress)
-                kw["cp_streams"] = [j.cp_slot for j in jobs]
+            for j in jobs:                # a job's streams are opened at its first chunk: exactly those its options need
+                if j.streams is None:
+                    opts = dict(rate=j.sample_rate, speed=j.speed, pauses=j.pauses, compress=j.compress, limiter=j.limiter, limiter_gain=j.lm_gain,
+                                flac=j.flac, adpcm=j.adpcm)
+                    j.streams = StreamSet.open(self.chat.codec, **opts) if StreamSet.needed(**opts) else StreamSet()
+            for st in STAGES:             # a stage some job of the poll is in: its handles, one entry per job, and its count
+                hs = [j.streams.get(st.name) for j in jobs]
+                if any(h is not None for h in hs):
+                    kw[st.streams] = hs
+                    if st.counter:
+                        setattr(self, st.counter, getattr(self, st.counter) + sum(h is not None for h in hs))
             pieces = self.chat.decode_windows_pcm16(self.pool.hiddens, [c[1:] for c in live], **kw)
         except Exception as e:        # the decode failed: these streams fail, the worker and the other requests go on
             for job in dict.fromkeys(jobs):

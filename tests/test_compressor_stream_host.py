@@ -367,15 +367,16 @@ def test_the_serial_stream_steps_the_rows_compressor_streams_and_closes_them():
     chat.normalizer = lambda t, *a: t
     seen = {}
 
-    def batches(text, step, stream, use_decoder, split_text, params, pcm16, ragged, raw, sample_rate, encoding, speed, ts, rs=None, cp=None, cp_spec=None):
-        seen.update(cp=cp, spec=cp_spec, ts=ts)
-        cp.extend(chat.codec.compress_stream_open(sample_rate or 24000, cp_spec) for _ in text)
+    def batches(text, step, stream, use_decoder, split_text, params, pcm16, ragged, raw, sample_rate, encoding, speed, sets, cp_spec=None):
+        from chattts_amd.winchain import StreamSet
+        seen.update(sets=sets, spec=cp_spec)
+        sets.extend(StreamSet.open(chat.codec, rate=sample_rate, speed=speed, compress=cp_spec) for _ in text)
         yield "chunk"
         raise RuntimeError("the consumer's problem")
     chat._infer_batches = batches
     spec = CP.check({"hold_ms": 100})
     gen = chat._infer(["a", "b"], True, None, True, False, True, True, True, False, 4, None, SimpleNamespace(spk_smp=None), sample_rate=8000, cp_spec=spec)
-    assert next(gen) == "chunk" and seen["cp"] == [30, 31] and seen["spec"] == spec and seen["ts"] is None
+    assert next(gen) == "chunk" and [dict(st) for st in seen["sets"]] == [{"compress": 30}, {"compress": 31}] and seen["spec"] == spec      # no other stream
     with pytest.raises(RuntimeError):
         next(gen)
     assert chat.codec.log == [("cp_open", 8000, spec), ("cp_open", 8000, spec), ("cp_close", 30), ("cp_close", 31)]

@@ -305,15 +305,16 @@ def test_the_serial_stream_steps_the_rows_limiter_streams_and_closes_them():
     chat.normalizer = lambda t, *a: t
     seen = {}
 
-    def batches(text, step, stream, use_decoder, split_text, params, pcm16, ragged, raw, sample_rate, encoding, speed, ts, rs=None, lm=None, lm_gain=None):
-        seen.update(lm=lm, gain=lm_gain, ts=ts)
-        lm.extend(chat.codec.peak_limit_stream_open(sample_rate or 24000, lm_gain) for _ in text)
+    def batches(text, step, stream, use_decoder, split_text, params, pcm16, ragged, raw, sample_rate, encoding, speed, sets, lm_gain=None):
+        from chattts_amd.winchain import StreamSet
+        seen.update(sets=sets, gain=lm_gain)
+        sets.extend(StreamSet.open(chat.codec, rate=sample_rate, speed=speed, limiter_gain=lm_gain) for _ in text)
         yield "chunk"
         raise RuntimeError("the consumer's problem")
     chat._infer_batches = batches
     gen = chat._infer(["a", "b"], True, None, True, False, True, True, True, False, 4, None, SimpleNamespace(spk_smp=None), sample_rate=8000,
                       lm_gain=np.float32(2.0))
-    assert next(gen) == "chunk" and seen["lm"] == [20, 21] and seen["gain"] == np.float32(2.0) and seen["ts"] is None
+    assert next(gen) == "chunk" and [dict(st) for st in seen["sets"]] == [{"limiter": 20}, {"limiter": 21}] and seen["gain"] == np.float32(2.0)      # no other stream
     with pytest.raises(RuntimeError):
         next(gen)
     assert chat.codec.log == [("lm_open", 8000, 2.0), ("lm_open", 8000, 2.0), ("lm_close", 20), ("lm_close", 21)]

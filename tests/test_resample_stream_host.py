@@ -361,21 +361,22 @@ def test_the_serial_stream_takes_the_extra_step_and_closes_both_streams():
     chat.normalizer = lambda t, *a: t
     seen = {}
 
-    def batches(text, step, stream, use_decoder, split_text, params, pcm16, ragged, raw, sample_rate, encoding, speed, ts, rs=None):
-        seen.update(ts=ts, rs=rs, rate=sample_rate)
-        ts.extend(chat.codec.time_scale_stream_open(speed) for _ in text)
-        rs.extend(chat.codec.resample_stream_open(24000, sample_rate) for _ in text)
+    def batches(text, step, stream, use_decoder, split_text, params, pcm16, ragged, raw, sample_rate, encoding, speed, sets):
+        from chattts_amd.winchain import StreamSet
+        seen.update(sets=sets, rate=sample_rate)
+        sets.extend(StreamSet.open(chat.codec, rate=sample_rate, speed=speed) for _ in text)
         yield "chunk"
         raise RuntimeError("the consumer's problem")
     chat._infer_batches = batches
     gen = chat._infer(["a", "b"], True, None, True, False, True, True, True, False, 4, None, SimpleNamespace(spk_smp=None), sample_rate=8000, speed=1.25)
-    assert next(gen) == "chunk" and seen["ts"] == [0, 1] and seen["rs"] == [10, 11]
+    assert next(gen) == "chunk" and [dict(st) for st in seen["sets"]] == [{"time_scale": 0, "resample": 10}, {"time_scale": 1, "resample": 11}]
     with pytest.raises(RuntimeError):
         next(gen)
-    assert chat.codec.log[-4:] == [("ts_close", 0), ("ts_close", 1), ("rs_close", 10), ("rs_close", 11)]
+    assert chat.codec.log[-4:] == [("ts_close", 0), ("rs_close", 10), ("ts_close", 1), ("rs_close", 11)]            # row by row: each row's set
     gen = chat._infer(["a"], True, None, True, False, True, True, True, False, 4, None, SimpleNamespace(spk_smp=None), speed=1.25)
-    chat._infer_batches = lambda *a: iter([a[-1]])
-    assert next(gen) is None                                  # a streamed speed at 24 kHz: no resampler streams at all
+    chat._infer_batches = lambda *a: (a[-1].extend(StreamSet.open(chat.codec, rate=a[9], speed=a[11]) for _ in a[0]), iter([a[-1]]))[1]
+    from chattts_amd.winchain import StreamSet
+    assert [sorted(st) for st in next(gen)] == [["time_scale"]]       # a streamed speed at 24 kHz: no resampler streams at all
 
 
 def _speed_rate_chat():
